@@ -304,6 +304,27 @@ def _reduce(world, device, dt, sampled):
     return dt, float(sampled)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, ret):
+    """--dump-outputs DIR: what the caller of the timed train() holds after its last step, one DIR/<name>.npy per array --
+    `param.<name>` (float32) every parameter, `grad.<name>` (float32) the gradient the last step left on it (parameters without
+    one are absent), `train_return` (float64) train()'s (mean_loss, temperature, conditional_updates, total_updates)."""
+    import numpy as np
+    arrays = {"train_return": np.array([float(v) for v in ret], dtype=np.float64)}
+    for name, p in model.named_parameters():
+        arrays[f"param.{name}"] = p.detach().float().cpu().numpy()
+        if p.grad is not None:
+            arrays[f"grad.{name}"] = p.grad.detach().float().cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 # --------------------------------------------------------------------------------------------- S3 (headline)
 def run_s3(a, S, rank, world, device):
     model, opt_gnn, opt_edge, opt_all = build_model(S, device, fused=bool(a.fused_adam))
@@ -339,6 +360,8 @@ def run_s3(a, S, rank, world, device):
         _quiet_train(S, args, 0, 10, *train_args, warm, q=Q, alternate_frequency=0)
     dt, ret = _timed_train(S, world, args, 1, 10, *train_args, timed, q=Q, alternate_frequency=0)
     dt_all, sampled_all = _reduce(world, device, dt, sampled)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, ret)          # before the epochs / branch timings below train the model further
     n_above = sum(1 for b in timed if b.edge_index.shape[1] > Q)
 
     rec = {
@@ -761,7 +784,11 @@ def main():
     ap.add_argument("--score-variant", type=int, default=-1, help="scorer forward kernel for the timed steps (benchmarking A/B; -1 = library default)")
     ap.add_argument("--hipgraph", type=int, default=1, help="1 (default): every step replayed from the HIP graphs captured once over static "
                     "slots (stepgraph.py); 0: eager launches")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="S3: after the timed steps, write the model's parameters and "
+                    "the gradients of the last timed step (float32) and train()'s return values (float64) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.dump_outputs and a.config != "S3":
+        raise SystemExit("--dump-outputs is implemented for the default S3 line only")
     if a.pool is not None:
         a.parts = a.pool
 
