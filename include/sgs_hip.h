@@ -456,6 +456,15 @@ int sgs_edge_score_bwd_dfeat_fused(const uint32_t* dvbits, const float* dz, cons
 int sgs_edge_score_bwd_reduce_fused(const float* G, const float* opart, const uint32_t* dvbits, const float* dz, const float* w2, float p_drop,
                                     int64_t N, int64_t H, int64_t nnz, const int32_t* in_ptr, const int32_t* in_eid, const int32_t* out_ptr,
                                     float* out_codes, float* out_U, float* out_U_raw, sgs_stream_t stream);
+/* The same chain with the MODE 5 operand packed by the prep launch (one launch fewer; same results, bit for bit):
+ *   sgs_edge_score_bwd_prep_sd_pack      sgs_edge_score_bwd_prep_sd + the pack of diag(w2 / (1 - p)) W1a^T into ws
+ *                                        (ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0))
+ *   sgs_edge_score_bwd_dfeat_fused_packed  sgs_edge_score_bwd_dfeat_fused on the operand that the prep left in ws (the same ws) */
+int sgs_edge_score_bwd_prep_sd_pack(const float* codes, int64_t N, int64_t H, const int64_t* edge_index, int64_t E, const int64_t* active_eid,
+                                    int64_t n_active, const float* grad_p, const float* p, const uint32_t* maskbits, float* dz, uint32_t* dvbits,
+                                    int32_t* sd, const float* W1, const float* w2, float p_drop, void* ws, size_t ws_bytes, sgs_stream_t stream);
+int sgs_edge_score_bwd_dfeat_fused_packed(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t N,
+                                          int64_t H, float* G, float* opart, const void* ws, size_t ws_bytes, sgs_stream_t stream);
 int sgs_edge_score_bwd_core_bits(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
                                  int64_t edge_id_offset, const int64_t* active_eid, int64_t n_active, const float* grad_p, const float* W1,
                                  const float* b1, const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site,

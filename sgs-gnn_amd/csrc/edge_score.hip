@@ -749,10 +749,9 @@ __global__ void __launch_bounds__(kT, 2) edge_score_stream64_kernel(ScoreArgs a,
 // Requires H % 128 == 0.
 // rowscale (TRANSPOSED only): the operand is diag(rowscale * scale) W1a, i.e. entry (k, h) is scaled by rowscale[k] * scale before it is
 // split -- the mask form of dfeat folds fc2's weights and the dropout scale into the matrix (MODE 4).
-template <bool TRANSPOSED = false>      // TRANSPOSED: the pieces of W1a^T (row h of the operand = column h of W1a): the row-GEMM mode's operand
-__global__ void __launch_bounds__(kT) pack_w1a_bf16x3(const float* __restrict__ W1, int H, uint4* __restrict__ Wp16,
-                                                     const float* __restrict__ rowscale = nullptr, float scale = 1.f) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;       // one (kc, t, lane)
+template <bool TRANSPOSED>
+__device__ __forceinline__ void pack_w1a_bf16x3_one(int64_t i, const float* __restrict__ W1, int H, uint4* __restrict__ Wp16,
+                                                    const float* __restrict__ rowscale, float scale) {
     const int NTl = H / 32;
     if (i >= static_cast<int64_t>(H / 16) * NTl * 64) return;
     const int lane = i & 63;
@@ -770,6 +769,13 @@ __global__ void __launch_bounds__(kT) pack_w1a_bf16x3(const float* __restrict__ 
     uint4* o = Wp16 + (static_cast<int64_t>(kc) * NTl + t) * 3 * 64 + lane;
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c * 64] = make_uint4(p[c][0], p[c][1], p[c][2], p[c][3]);
+}
+inline int64_t pack_w1a_threads(int64_t H) { return (H / 16) * (H / 32) * 64; }       // one (kc, t, lane) each
+
+template <bool TRANSPOSED = false>      // TRANSPOSED: the pieces of W1a^T (row h of the operand = column h of W1a): the row-GEMM mode's operand
+__global__ void __launch_bounds__(kT) pack_w1a_bf16x3(const float* __restrict__ W1, int H, uint4* __restrict__ Wp16,
+                                                     const float* __restrict__ rowscale = nullptr, float scale = 1.f) {
+    pack_w1a_bf16x3_one<TRANSPOSED>(static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x, W1, H, Wp16, rowscale, scale);
 }
 
 // Measured (MI355X, E = 351 194, H = 256; launch = pack + kernel): 0.25-0.29 ms by device against 0.42-0.47 ms for variant D
@@ -1073,16 +1079,31 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) edge_score_bf16x6_kernel(Scor
         const float* cs = a.codes + static_cast<int64_t>(sr) * H + 4 * kh;
         const float* cd = a.codes + static_cast<int64_t>(dr) * H + 4 * kh;
         const int64_t wrow = (row0 + 32 * wave) >> 5;                                    // this wave's index among all 32-row tiles
+        // The endpoint rows are gathered one 64-column slice AHEAD: slice Q + 1's loads are issued once slice Q's products are stored and
+        // before its LDS walk, so their latency hides behind the walk instead of opening every slice (the main loop's operand registers
+        // are dead; issuing them before the products instead needs 64 more live registers and spills).
+        float4 s4n[8], d4n[8];
+#pragma unroll
+        for (int ii = 0; ii < 8; ++ii) {
+            s4n[ii] = *reinterpret_cast<const float4*>(cs + 8 * ii);
+            d4n[ii] = *reinterpret_cast<const float4*>(cd + 8 * ii);
+        }
 #pragma unroll
         for (int Q = 0; Q < NT / 2; ++Q) {                                               // 64 columns at a time
 #pragma unroll
             for (int ii = 0; ii < 8; ++ii) {
                 const int i = 8 * Q + ii, t = i >> 2, g4 = i & 3;
-                const float4 s4 = *reinterpret_cast<const float4*>(cs + 8 * i);
-                const float4 d4 = *reinterpret_cast<const float4*>(cd + 8 * i);
+                const float4 s4 = s4n[ii], d4 = d4n[ii];
                 const float f0 = rs * acc[t][4 * g4], f1 = rs * acc[t][4 * g4 + 1], f2 = rs * acc[t][4 * g4 + 2], f3 = rs * acc[t][4 * g4 + 3];
                 if (live) *reinterpret_cast<float4*>(a.feat + r * H + 8 * i + 4 * kh) = make_float4(f0 * s4.x, f1 * s4.y, f2 * s4.z, f3 * s4.w);
                 *reinterpret_cast<float4*>(ot + l31 * LS + 8 * ii + 4 * kh) = make_float4(f0 * d4.x, f1 * d4.y, f2 * d4.z, f3 * d4.w);
+            }
+            if (Q + 1 < NT / 2) {                                                        // the next slice's rows: in flight during the walk
+#pragma unroll
+                for (int ii = 0; ii < 8; ++ii) {
+                    s4n[ii] = *reinterpret_cast<const float4*>(cs + 8 * (8 * (Q + 1) + ii));
+                    d4n[ii] = *reinterpret_cast<const float4*>(cd + 8 * (8 * (Q + 1) + ii));
+                }
             }
             // the tile is wave-private and a wave's LDS operations execute in issue order: no workgroup barrier, only the compiler is
             // told not to move the reads above the writes (or the next pass's writes above these reads)
@@ -1714,6 +1735,37 @@ __global__ void __launch_bounds__(kT) scorer_bwd_prep(const float* __restrict__ 
             if (r0 + u < n)
                 *reinterpret_cast<float4*>(feat + (r0 + u) * H + c0) = make_float4(a[u].x * b[u].x, a[u].y * b[u].y, a[u].z * b[u].z, a[u].w * b[u].w);
     }
+}
+
+// The same pass for the FUSED backward (no feat), one active row per LANE: the three dependent loads of a row (active -> src / dst, p ->
+// dz) and its mask-bit row are in flight for 64 rows per wave, where scorer_bwd_prep keeps four rows per wave (its lanes serve the feat
+// columns).  Workgroups from n_prep_blocks on pack W1a^T for MODE 5 instead (Wp16 != nullptr): W1 and w2 are fixed for the step, so
+// the pack needs no launch of its own.  Same values as scorer_bwd_prep, bit for bit.
+__global__ void __launch_bounds__(kT) scorer_bwd_prep_sd_pack(const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
+                                                             const int64_t* __restrict__ active, int64_t n, int wpr,
+                                                             const float* __restrict__ gp, const float* __restrict__ p,
+                                                             const uint32_t* __restrict__ maskbits, float* __restrict__ dz,
+                                                             uint32_t* __restrict__ bits, int2* __restrict__ sd, int64_t n_prep_blocks,
+                                                             const float* __restrict__ W1, int H, uint4* __restrict__ Wp16,
+                                                             const float* __restrict__ w2, float scale) {
+    if (static_cast<int64_t>(blockIdx.x) >= n_prep_blocks) {
+        pack_w1a_bf16x3_one<true>((static_cast<int64_t>(blockIdx.x) - n_prep_blocks) * kT + threadIdx.x, W1, H, Wp16, w2, scale);
+        return;
+    }
+    const int64_t r = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+    if (r >= n) return;
+    const int64_t e = active ? active[r] : r;
+    const int64_t s = src[e], d = dst[e];
+    const float pe = p[e], g = gp[r];
+    if ((wpr & 3) == 0) {                                                 // rows of 16-byte multiples (H % 128 == 0)
+        const uint4* mi = reinterpret_cast<const uint4*>(maskbits + e * wpr);
+        uint4* mo = reinterpret_cast<uint4*>(bits + r * wpr);
+        for (int k = 0; k < (wpr >> 2); ++k) mo[k] = mi[k];
+    } else {
+        for (int k = 0; k < wpr; ++k) bits[r * wpr + k] = maskbits[e * wpr + k];
+    }
+    dz[r] = g * pe * (1.0f - pe);
+    sd[r] = make_int2(static_cast<int32_t>(s), static_cast<int32_t>(d));
 }
 
 // d fc2.weight without the hidden activations: hd[e, h] = bit[e, h] * scale * (W1a feat_e + U[s] - U[d] + b1)[h], so
@@ -2486,17 +2538,65 @@ int sgs_edge_score_bwd_prep(const float* codes, int64_t N, int64_t H, const int6
 
 /* The same pass for the FUSED backward: no feat (its consumers gather the code rows themselves); the endpoints of every active row
  * as int32 pairs instead (sd [n, 2]). */
+// MODE 5's operand, diag(w2 / (1 - p)) W1a^T in bf16x3 pieces, at a fixed place of the dfeat workspace
+static uint4* fused_wp16(void* ws, int64_t H) {
+    Carver cv(ws);
+    cv.take<float>(static_cast<size_t>(H) * H);
+    cv.take<float>(0);
+    cv.take<float>(0);
+    cv.take<unsigned int>(64);
+    return cv.take<uint4>(static_cast<size_t>(H) * H * 6 / 16);
+}
+
+static int bwd_prep_sd_impl(const float* codes, int64_t N, int64_t H, const int64_t* edge_index, int64_t E, const int64_t* active_eid,
+                            int64_t n_active, const float* grad_p, const float* p, const uint32_t* maskbits, float* dz, uint32_t* dvbits,
+                            int32_t* sd, const float* W1, const float* w2, float p_drop, uint4* Wp16, hipStream_t stream) {
+    SGS_REQUIRE(N > 0 && H > 0 && H % 32 == 0 && E >= 0 && n_active >= 0 && (active_eid || n_active == E), SGS_EINVAL,
+                "sgs_edge_score_bwd_prep_sd: bad arguments (H %% 32 == 0; n_active == E when active_eid is NULL)");
+    if (n_active == 0) return SGS_OK;
+    SGS_REQUIRE(codes && edge_index && grad_p && p && maskbits && dz && dvbits && sd, SGS_EINVAL, "sgs_edge_score_bwd_prep_sd: null pointer");
+    const int64_t nb = cdiv(n_active, kT), npack = Wp16 ? cdiv(pack_w1a_threads(H), kT) : 0;
+    hipLaunchKernelGGL(scorer_bwd_prep_sd_pack, dim3(static_cast<unsigned>(nb + npack)), dim3(kT), 0, stream, edge_index, edge_index + E, active_eid,
+                       n_active, static_cast<int>(H >> 5), grad_p, p, maskbits, dz, dvbits, reinterpret_cast<int2*>(sd), nb, W1,
+                       static_cast<int>(H), Wp16, w2, 1.0f / (1.0f - p_drop));
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
 int sgs_edge_score_bwd_prep_sd(const float* codes, int64_t N, int64_t H, const int64_t* edge_index, int64_t E, const int64_t* active_eid,
                                int64_t n_active, const float* grad_p, const float* p, const uint32_t* maskbits, float* dz, uint32_t* dvbits,
                                int32_t* sd, sgs_stream_t stream_) {
-    SGS_REQUIRE(sd || n_active == 0, SGS_EINVAL, "sgs_edge_score_bwd_prep_sd: null pointer");
-    return bwd_prep_impl(codes, N, H, edge_index, E, active_eid, n_active, grad_p, p, maskbits, dz, dvbits, nullptr, sd,
-                         static_cast<hipStream_t>(stream_));
+    return bwd_prep_sd_impl(codes, N, H, edge_index, E, active_eid, n_active, grad_p, p, maskbits, dz, dvbits, sd, nullptr, nullptr, 0.f,
+                            nullptr, static_cast<hipStream_t>(stream_));
+}
+
+int sgs_edge_score_bwd_prep_sd_pack(const float* codes, int64_t N, int64_t H, const int64_t* edge_index, int64_t E, const int64_t* active_eid,
+                                    int64_t n_active, const float* grad_p, const float* p, const uint32_t* maskbits, float* dz, uint32_t* dvbits,
+                                    int32_t* sd, const float* W1, const float* w2, float p_drop, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    SGS_REQUIRE(p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_edge_score_bwd_prep_sd_pack: bad arguments");
+    SGS_REQUIRE(sgs_edge_score_bwd_bits_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_prep_sd_pack: H=%lld unsupported (128 or 256)", (long long)H);
+    if (n_active == 0) return SGS_OK;
+    SGS_REQUIRE(W1 && w2, SGS_EINVAL, "sgs_edge_score_bwd_prep_sd_pack: null pointer");
+    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_prep_sd_pack: workspace too small");
+    return bwd_prep_sd_impl(codes, N, H, edge_index, E, active_eid, n_active, grad_p, p, maskbits, dz, dvbits, sd, W1, w2, p_drop,
+                            fused_wp16(ws, H), static_cast<hipStream_t>(stream_));
 }
 
 /* MODE 5 of the bf16x6 loop (see the kernel): G [n, H] = dfeat * codes[src], opart [cdiv(n, 32) + N, H] = run-end partial sums of
  * dfeat * codes[dst].  The active rows must be sorted by source. */
 size_t sgs_edge_score_bwd_fused_opart_rows(int64_t n, int64_t N) { return static_cast<size_t>(cdiv(n < 0 ? 0 : n, 32) + (N < 0 ? 0 : N)); }
+
+static int bwd_dfeat_fused_launch(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t H,
+                                  const uint4* Wp16, float* G, float* opart, hipStream_t stream) {
+    ScoreArgs a{};
+    a.inbits = dvbits; a.indz = dz; a.n = n; a.H = static_cast<int>(H); a.feat = G; a.codes = codes; a.sd = sd; a.opart = opart;
+    const dim3 grid(static_cast<unsigned>(cdiv(n, 128))), blk(256);
+    bf16x6_launch_knobs(a, 5, H);
+    if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 5>), grid, blk, 0, stream, a, Wp16);
+    else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 5>), grid, blk, 0, stream, a, Wp16);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
 
 int sgs_edge_score_bwd_dfeat_fused(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t N, int64_t H,
                                    const float* W1, const float* w2, float p_drop, float* G, float* opart, void* ws, size_t ws_bytes,
@@ -2507,22 +2607,21 @@ int sgs_edge_score_bwd_dfeat_fused(const uint32_t* dvbits, const float* dz, cons
     if (n == 0) return SGS_OK;
     SGS_REQUIRE(dvbits && dz && sd && codes && W1 && w2 && G && opart, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused: null pointer");
     SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_dfeat_fused: workspace too small");
-    Carver cv(ws);
-    cv.take<float>(static_cast<size_t>(H) * H);
-    cv.take<float>(0);
-    cv.take<float>(0);
-    cv.take<unsigned int>(64);
-    uint4* Wp16 = cv.take<uint4>(static_cast<size_t>(H) * H * 6 / 16);
-    hipLaunchKernelGGL(pack_w1a_bf16x3<true>, dim3(static_cast<unsigned>(cdiv((H / 16) * (H / 32) * 64, kT))), dim3(kT), 0, stream, W1,
+    uint4* Wp16 = fused_wp16(ws, H);
+    hipLaunchKernelGGL(pack_w1a_bf16x3<true>, dim3(static_cast<unsigned>(cdiv(pack_w1a_threads(H), kT))), dim3(kT), 0, stream, W1,
                        static_cast<int>(H), Wp16, w2, 1.0f / (1.0f - p_drop));
-    ScoreArgs a{};
-    a.inbits = dvbits; a.indz = dz; a.n = n; a.H = static_cast<int>(H); a.feat = G; a.codes = codes; a.sd = sd; a.opart = opart;
-    const dim3 grid(static_cast<unsigned>(cdiv(n, 128))), blk(256);
-    bf16x6_launch_knobs(a, 5, H);
-    if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 5>), grid, blk, 0, stream, a, Wp16);
-    else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 5>), grid, blk, 0, stream, a, Wp16);
-    SGS_LAUNCH_OK();
-    return SGS_OK;
+    return bwd_dfeat_fused_launch(dvbits, dz, sd, codes, n, H, Wp16, G, opart, stream);
+}
+
+int sgs_edge_score_bwd_dfeat_fused_packed(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t N,
+                                          int64_t H, float* G, float* opart, const void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    SGS_REQUIRE(n >= 0 && N > 0 && H > 0, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_packed: bad arguments");
+    SGS_REQUIRE(sgs_edge_score_bwd_bits_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_packed: H=%lld unsupported (128 or 256)",
+                (long long)H);
+    if (n == 0) return SGS_OK;
+    SGS_REQUIRE(dvbits && dz && sd && codes && G && opart, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_packed: null pointer");
+    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_dfeat_fused_packed: workspace too small");
+    return bwd_dfeat_fused_launch(dvbits, dz, sd, codes, n, H, fused_wp16(const_cast<void*>(ws), H), G, opart, static_cast<hipStream_t>(stream_));
 }
 
 /* The reductions that follow it: out_codes, out_U (and out_U_raw, optional) as sgs_endpoint_reduce_pair_bits produces them. */

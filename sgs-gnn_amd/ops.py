@@ -865,7 +865,8 @@ def _edge_score_backward_mask(ctx, L, codes, U, W1, b1, w2, b2, edge_index, eid,
 def _edge_score_backward_fused(ctx, L, codes, U, W1, b1, w2, edge_index, eid, graph, n, gp_act, kept, bits, dz):
     """The no-recompute backward with neither feat nor dfeat as [n, H] arrays (include/sgs_hip.h, "FUSED form"): the active rows are sorted
     by source, so the by-source half of d codes is reduced inside the dfeat contraction's epilogue, and the weight-gradient GEMM gathers
-    x_s * x_d itself.  Four launches (+ the W1a pack): prep (dz, mask rows, endpoints), dfeat + by-source sums, d W1a, the reductions."""
+    x_s * x_d itself.  Six launches: prep (dz, mask rows, endpoints; it also packs dfeat's W1a operand), dfeat + by-source sums, d W1a and
+    its slab reduction, the endpoint reductions, d fc2.weight."""
     N, H = codes.shape
     E = edge_index.shape[1]
     dev = codes.device
@@ -873,13 +874,14 @@ def _edge_score_backward_fused(ctx, L, codes, U, W1, b1, w2, edge_index, eid, gr
     p = ctx.p
     maskbits, p_out = kept
     sd = torch.empty(n, 2, dtype=torch.int32, device=dev)
-    _lib.check(L.sgs_edge_score_bwd_prep_sd(_ptr(codes), N, H, _ptr(edge_index), E, _ptr(eid), n, _ptr(gp_act), _ptr(p_out), _ptr(maskbits),
-                                            _ptr(dz), _ptr(bits), _ptr(sd), _stream()), "sgs_edge_score_bwd_prep_sd")
+    wsd = workspace(L.sgs_edge_score_workspace_bytes(0, H, 0), dev)
+    _lib.check(L.sgs_edge_score_bwd_prep_sd_pack(_ptr(codes), N, H, _ptr(edge_index), E, _ptr(eid), n, _ptr(gp_act), _ptr(p_out), _ptr(maskbits),
+                                                 _ptr(dz), _ptr(bits), _ptr(sd), _ptr(W1), _ptr(w2), p, wsd.data_ptr(), wsd.numel(), _stream()),
+               "sgs_edge_score_bwd_prep_sd_pack")
     G = torch.empty(n, H, **f32)
     opart = torch.empty(L.sgs_edge_score_bwd_fused_opart_rows(n, N), H, **f32)
-    wsd = workspace(L.sgs_edge_score_workspace_bytes(0, H, 0), dev)
-    _lib.check(L.sgs_edge_score_bwd_dfeat_fused(_ptr(bits), _ptr(dz), _ptr(sd), _ptr(codes), n, N, H, _ptr(W1), _ptr(w2), p, _ptr(G), _ptr(opart),
-                                                wsd.data_ptr(), wsd.numel(), _stream()), "sgs_edge_score_bwd_dfeat_fused")
+    _lib.check(L.sgs_edge_score_bwd_dfeat_fused_packed(_ptr(bits), _ptr(dz), _ptr(sd), _ptr(codes), n, N, H, _ptr(G), _ptr(opart), wsd.data_ptr(),
+                                                       wsd.numel(), _stream()), "sgs_edge_score_bwd_dfeat_fused_packed")
     dW1 = torch.empty_like(W1)
     db1, db2 = torch.empty(H, **f32), torch.empty(1, **f32)
     Traw, craw, Rraw = torch.empty(H, H, **f32), torch.empty(H, **f32), torch.empty(N, H, **f32)
