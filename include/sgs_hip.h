@@ -660,6 +660,40 @@ int sgs_adam_multi_max_tensors(void);
 int sgs_adam_step_multi(const int64_t* desc_host, const float* hyper_host, int64_t n_tensors, uint32_t* ticket, float* loss_sum, const float* loss,
                         uint64_t* epoch, sgs_stream_t stream);
 
+/* ---------------------------------------------------------------- batched ensemble evaluation (evaluate.py:70-173)
+ * All D draws of one partition in one pass.  Forward only (no autograd state), for the GCN head.
+ *
+ * sgs_sample_topq_multi: D draws of sgs_sample_topq over ONE candidate set.  Draw d uses stream id stream_id0 + d (or noise row d of
+ *   noise [D, E]) and is bitwise what sgs_sample_topq returns for it (small- and large-E path, ties to the lowest edge id).  Modes as
+ *   sgs_sample_topq (LEARNED with or without prior, PRIOR, p == NULL uniform).  The normaliser is reduced once; every radix-select stage
+ *   is one launch for all draws (draw index in the grid).  Outputs: mask [D, E] u8, sampled_eid [D, q] (ascending), optional
+ *   sampled_edge_index [D, 2, q], stats [D, 4] (optional unless st_weights), optional st_weights [D, q] (sgs_st_weights_fwd's values,
+ *   mode LEARNED).  1 <= D <= 65535.  Not available under sgs_dyn_edges_set.
+ * sgs_graph_filter_multi: the in-CSR + loop_eid of each draw's subgraph (D masks / sampled_eid over the parent's cached in-CSR); every
+ *   draw's arrays equal sgs_graph_filter's.  in_ptr [D, N+1], in_src / in_eid [D, q], loop_eid [D, N].  No out-CSR.
+ * sgs_gcn_norm_fwd_multi: sgs_gcn_norm_fwd's in-direction outputs per draw (dis, loopw, what_loop [D, N], what_in [D, q]); w [D, q] or
+ *   NULL (unit weights).  Same device code: bitwise equal per draw.
+ * sgs_spmm_csr_multi: Y[d] = act(A_d X_d + bias) over the per-draw CSRs (ptr [D, N+1], col / val [D, nnz], diag [D, N] or NULL);
+ *   X_d = X + d * x_stride (0: one X shared by all draws); Y [D, N, Dc]; act NONE or RELU.  Equal per draw to sgs_spmm_csr.
+ * sgs_ensemble_mean_correct: running fp32 sum of Dc logit blocks (logits + d * x_stride, [N, C] each; x_stride 0 = the same block Dc
+ *   times) into acc [N, C] (first: acc starts from block 0; else from acc), in draw order.  last: acc *= 1/D_total when D_total > 1,
+ *   then argmax (first maximum wins) against y on mask0..2 accumulated into counts [6] int64 = {correct, total} x 3 (not cleared). */
+size_t sgs_sample_topq_multi_workspace_bytes(int64_t E, int64_t D);
+int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
+                          uint64_t stream_id0, int64_t D, int64_t E, int64_t q, const int64_t* edge_index, uint8_t* mask, int64_t* sampled_eid,
+                          int64_t* sampled_edge_index, float* stats, float* st_weights, void* ws, size_t ws_bytes, sgs_stream_t stream);
+size_t sgs_graph_filter_multi_workspace_bytes(int64_t E_parent, int64_t N, int64_t D);
+int sgs_graph_filter_multi(const int32_t* pin_ptr, const int32_t* pin_src, const int32_t* pin_eid, int64_t E_parent, int64_t N, int64_t D,
+                           const uint8_t* mask, const int64_t* sampled_eid, int64_t q, int32_t* in_ptr, int32_t* in_src, int32_t* in_eid,
+                           int32_t* loop_eid, void* ws, size_t ws_bytes, sgs_stream_t stream);
+int sgs_gcn_norm_fwd_multi(const float* w, int64_t q, int64_t N, int64_t D, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid,
+                           const int32_t* loop_eid, float* dis, float* loopw, float* what_in, float* what_loop, sgs_stream_t stream);
+int sgs_spmm_csr_multi(const float* X, int64_t x_stride, int64_t N, int64_t Dc, int64_t nnz, int64_t D, const int32_t* ptr, const int32_t* col,
+                       const float* val, const float* diag, const float* bias, int act, float* Y, sgs_stream_t stream);
+int sgs_ensemble_mean_correct(const float* logits, int64_t x_stride, int64_t Dc, int64_t N, int64_t C, float* acc, int first, int last,
+                              int64_t D_total, const int64_t* y, const uint8_t* mask0, const uint8_t* mask1, const uint8_t* mask2, int64_t* counts,
+                              sgs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

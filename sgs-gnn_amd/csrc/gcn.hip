@@ -41,13 +41,8 @@ __global__ void __launch_bounds__(kT) count_degrees(const int64_t* __restrict__ 
 // Tiles of 4096 consecutive counts, four per thread (coalesced), wave scan + the 16 wave totals through LDS, a running carry; the next
 // tile's counts are loaded before this tile's barrier.  (Each thread scanning its own N / 1024 consecutive counts -- every access of a
 // wave a different cache line -- took 70 us at N = 33 869.)
-__global__ void __launch_bounds__(1024) scan_counts(const int* __restrict__ cnt_in, const int* __restrict__ cnt_out,
-                                                   int64_t N, int* __restrict__ in_ptr, int* __restrict__ out_ptr,
-                                                   int* __restrict__ cur_in, int* __restrict__ cur_out) {
+__device__ __forceinline__ void scan_counts_body(const int* __restrict__ cnt, int64_t N, int* __restrict__ ptr, int* __restrict__ cur) {
     __shared__ int wtot[2][16];
-    const int* cnt = blockIdx.x == 0 ? cnt_in : cnt_out;
-    int* ptr = blockIdx.x == 0 ? in_ptr : out_ptr;
-    int* cur = blockIdx.x == 0 ? cur_in : cur_out;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     auto load4 = [&](int64_t i, int (&v)[4]) {
 #pragma unroll
@@ -84,6 +79,12 @@ __global__ void __launch_bounds__(1024) scan_counts(const int* __restrict__ cnt_
         carry += total;
     }
     if (threadIdx.x == 0) ptr[N] = carry;
+}
+__global__ void __launch_bounds__(1024) scan_counts(const int* __restrict__ cnt_in, const int* __restrict__ cnt_out,
+                                                   int64_t N, int* __restrict__ in_ptr, int* __restrict__ out_ptr,
+                                                   int* __restrict__ cur_in, int* __restrict__ cur_out) {
+    if (blockIdx.x == 0) scan_counts_body(cnt_in, N, in_ptr, cur_in);
+    else scan_counts_body(cnt_out, N, out_ptr, cur_out);
 }
 
 __global__ void __launch_bounds__(kT) fill_rows(const int64_t* __restrict__ ei, int64_t n_edges, int* __restrict__ cur_in,
@@ -278,12 +279,13 @@ __device__ __forceinline__ bool mask_at(const uint8_t* __restrict__ mask, int e)
     return mask[e] != 0;
 }
 
+// nrows = 2N: in- and out-rows; N: in-rows only (the forward-only CSRs of sgs_graph_filter_multi)
 template <bool BITS>
-__global__ void __launch_bounds__(kT) filter_count_scatter(const int* __restrict__ in_ptr, const int* __restrict__ in_eid,
+__device__ __forceinline__ void filter_count_scatter_body(const int* __restrict__ in_ptr, const int* __restrict__ in_eid,
                                                           const int* __restrict__ out_ptr, const int* __restrict__ out_eid, int64_t N,
                                                           const uint8_t* __restrict__ mask, const int64_t* __restrict__ sampled_eid,
                                                           int64_t q, int64_t n_row_blocks, int* __restrict__ cnt_in,
-                                                          int* __restrict__ cnt_out, int* __restrict__ pos) {
+                                                          int* __restrict__ cnt_out, int* __restrict__ pos, int64_t nrows) {
     if (static_cast<int64_t>(blockIdx.x) >= n_row_blocks) {
         const int64_t j = (static_cast<int64_t>(blockIdx.x) - n_row_blocks) * kT + threadIdx.x;
         if (j < q) pos[sampled_eid[j]] = static_cast<int>(j);
@@ -291,7 +293,7 @@ __global__ void __launch_bounds__(kT) filter_count_scatter(const int* __restrict
     }
     const int lane = threadIdx.x & 63;
     const int64_t r = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
-    if (r >= 2 * N) return;
+    if (r >= nrows) return;
     const bool out = r >= N;
     const int64_t row = out ? r - N : r;
     const int* ptr = out ? out_ptr : in_ptr;
@@ -311,22 +313,30 @@ __global__ void __launch_bounds__(kT) filter_count_scatter(const int* __restrict
     c = wave_sum_int_all(c);
     if (lane == 0) (out ? cnt_out : cnt_in)[row] = c;
 }
+template <bool BITS>
+__global__ void __launch_bounds__(kT) filter_count_scatter(const int* __restrict__ in_ptr, const int* __restrict__ in_eid,
+                                                          const int* __restrict__ out_ptr, const int* __restrict__ out_eid, int64_t N,
+                                                          const uint8_t* __restrict__ mask, const int64_t* __restrict__ sampled_eid,
+                                                          int64_t q, int64_t n_row_blocks, int* __restrict__ cnt_in,
+                                                          int* __restrict__ cnt_out, int* __restrict__ pos) {
+    filter_count_scatter_body<BITS>(in_ptr, in_eid, out_ptr, out_eid, N, mask, sampled_eid, q, n_row_blocks, cnt_in, cnt_out, pos, 2 * N);
+}
 
 // SCAN: the child row pointers are not there yet -- every wave sums the counts of the rows before its own (N <= kSelfScanRows: a few
 // cached loads per lane) and writes its entry of the pointer array (the last row also the total): the scan launch between the count and
 // the fill pass goes away (partition scale: one launch = ~5 us of a ~90 us draw-to-normalisation chain).
 constexpr int64_t kSelfScanRows = 4096;
-template <bool BITS, bool SCAN = false>
-__global__ void __launch_bounds__(kT) filter_fill(const int* __restrict__ pin_ptr, const int* __restrict__ pin_src, const int* __restrict__ pin_eid,
+template <bool BITS, bool SCAN>
+__device__ __forceinline__ void filter_fill_body(int64_t nrows, const int* __restrict__ pin_ptr, const int* __restrict__ pin_src, const int* __restrict__ pin_eid,
                                                  const int* __restrict__ pout_ptr, const int* __restrict__ pout_dst,
                                                  const int* __restrict__ pout_eid, int64_t N, const uint8_t* __restrict__ mask,
                                                  const int* __restrict__ pos, int* __restrict__ in_ptr, int* __restrict__ in_src,
                                                  int* __restrict__ in_eid, int* __restrict__ out_ptr, int* __restrict__ out_dst,
-                                                 int* __restrict__ out_eid, int* __restrict__ loop_eid, const int* __restrict__ cnt_in = nullptr,
-                                                 const int* __restrict__ cnt_out = nullptr) {
+                                                 int* __restrict__ out_eid, int* __restrict__ loop_eid, const int* __restrict__ cnt_in,
+                                                 const int* __restrict__ cnt_out) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
-    if (r >= 2 * N) return;
+    if (r >= nrows) return;
     const bool out = r >= N;
     const int64_t row = out ? r - N : r;
     const int* pptr = out ? pout_ptr : pin_ptr;
@@ -378,10 +388,21 @@ __global__ void __launch_bounds__(kT) filter_fill(const int* __restrict__ pin_pt
     }
     if (!out && lane == 0) loop_eid[row] = loop;
 }
+template <bool BITS, bool SCAN = false>
+__global__ void __launch_bounds__(kT) filter_fill(const int* __restrict__ pin_ptr, const int* __restrict__ pin_src, const int* __restrict__ pin_eid,
+                                                 const int* __restrict__ pout_ptr, const int* __restrict__ pout_dst,
+                                                 const int* __restrict__ pout_eid, int64_t N, const uint8_t* __restrict__ mask,
+                                                 const int* __restrict__ pos, int* __restrict__ in_ptr, int* __restrict__ in_src,
+                                                 int* __restrict__ in_eid, int* __restrict__ out_ptr, int* __restrict__ out_dst,
+                                                 int* __restrict__ out_eid, int* __restrict__ loop_eid, const int* __restrict__ cnt_in = nullptr,
+                                                 const int* __restrict__ cnt_out = nullptr) {
+    filter_fill_body<BITS, SCAN>(2 * N, pin_ptr, pin_src, pin_eid, pout_ptr, pout_dst, pout_eid, N, mask, pos, in_ptr, in_src, in_eid, out_ptr,
+                                 out_dst, out_eid, loop_eid, cnt_in, cnt_out);
+}
 
 // ---------------------------------------------------------------- gcn_norm forward
 // One wave per node: deg_i = loopw_i + sum_{k in in-row i, src != i} w[eid_k]; dis = deg^-1/2.
-__global__ void __launch_bounds__(kT) norm_deg(const float* __restrict__ w, int64_t N, const int* __restrict__ in_ptr,
+__device__ __forceinline__ void norm_deg_body(const float* __restrict__ w, int64_t N, const int* __restrict__ in_ptr,
                                               const int* __restrict__ in_src, const int* __restrict__ in_eid,
                                               const int* __restrict__ loop_eid, float* __restrict__ dis,
                                               float* __restrict__ loopw) {
@@ -400,6 +421,12 @@ __global__ void __launch_bounds__(kT) norm_deg(const float* __restrict__ w, int6
     float di = 1.0f / sqrtf(deg);           // deg.pow(-0.5)
     if (isinf(di)) di = 0.f;                // masked_fill(inf -> 0)
     if (lane == 0) { dis[i] = di; loopw[i] = lw; }
+}
+__global__ void __launch_bounds__(kT) norm_deg(const float* __restrict__ w, int64_t N, const int* __restrict__ in_ptr,
+                                              const int* __restrict__ in_src, const int* __restrict__ in_eid,
+                                              const int* __restrict__ loop_eid, float* __restrict__ dis,
+                                              float* __restrict__ loopw) {
+    norm_deg_body(w, N, in_ptr, in_src, in_eid, loop_eid, dis, loopw);
 }
 
 // Edge-sharded graphs: each rank sums the weights of ITS in-edges (degpart), the ranks all-reduce, and
@@ -476,7 +503,7 @@ __global__ void __launch_bounds__(kT) degree_prior_logits(const int64_t* __restr
 }
 
 // Normalised weights in both CSR orders (0 for loop entries, which the loop term replaces).
-__global__ void __launch_bounds__(kT) norm_weights(const float* __restrict__ w, int64_t N, int64_t n_edges,
+__device__ __forceinline__ void norm_weights_body(int64_t nrows, const float* __restrict__ w, int64_t N, int64_t n_edges,
                                                   const int* __restrict__ in_ptr, const int* __restrict__ in_src,
                                                   const int* __restrict__ in_eid, const int* __restrict__ out_ptr,
                                                   const int* __restrict__ out_dst, const int* __restrict__ out_eid,
@@ -485,7 +512,7 @@ __global__ void __launch_bounds__(kT) norm_weights(const float* __restrict__ w, 
                                                   float* __restrict__ what_loop) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
-    if (r >= 2 * N) return;
+    if (r >= nrows) return;
     const bool out = r >= N;
     const int i = static_cast<int>(out ? r - N : r);
     const float di = dis[i];
@@ -505,6 +532,15 @@ __global__ void __launch_bounds__(kT) norm_weights(const float* __restrict__ w, 
             what_out[k] = (t == i) ? 0.f : (di * we) * dis[t];
         }
     }
+}
+__global__ void __launch_bounds__(kT) norm_weights(const float* __restrict__ w, int64_t N, int64_t n_edges,
+                                                  const int* __restrict__ in_ptr, const int* __restrict__ in_src,
+                                                  const int* __restrict__ in_eid, const int* __restrict__ out_ptr,
+                                                  const int* __restrict__ out_dst, const int* __restrict__ out_eid,
+                                                  const float* __restrict__ dis, const float* __restrict__ loopw,
+                                                  float* __restrict__ what_in, float* __restrict__ what_out,
+                                                  float* __restrict__ what_loop) {
+    norm_weights_body(2 * N, w, N, n_edges, in_ptr, in_src, in_eid, out_ptr, out_dst, out_eid, dis, loopw, what_in, what_out, what_loop);
 }
 
 // ---------------------------------------------------------------- gcn_norm backward
@@ -600,7 +636,7 @@ __global__ void __launch_bounds__(kT) edge_mate(const int* __restrict__ rev, int
 }
 
 template <int VEC, int LPR>
-__global__ void __launch_bounds__(kT) spmm_csr(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
+__device__ __forceinline__ void spmm_csr_body(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
                                               const int* __restrict__ col, const float* __restrict__ val,
                                               const float* __restrict__ diag, const float* __restrict__ bias, int act,
                                               float drop_scale, uint32_t drop_thresh, uint64_t seed, uint32_t site,
@@ -649,6 +685,14 @@ __global__ void __launch_bounds__(kT) spmm_csr(const float* __restrict__ X, int6
         *reinterpret_cast<V*>(Y + i * D + c0) = *reinterpret_cast<V*>(o);
     }
 }
+template <int VEC, int LPR>
+__global__ void __launch_bounds__(kT) spmm_csr(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
+                                              const int* __restrict__ col, const float* __restrict__ val,
+                                              const float* __restrict__ diag, const float* __restrict__ bias, int act,
+                                              float drop_scale, uint32_t drop_thresh, uint64_t seed, uint32_t site,
+                                              const uint64_t* __restrict__ epoch, float* __restrict__ Y) {
+    spmm_csr_body<VEC, LPR>(X, N, D, ptr, col, val, diag, bias, act, drop_scale, drop_thresh, seed, site, epoch, Y);
+}
 
 // Small-N variant (METIS partitions: ~1k rows of ~100-1000 nnz): one wave per row leaves the chip
 // mostly empty and hub rows serialise, so a 4-wave workgroup owns a row, each wave gathers a strided
@@ -656,7 +700,7 @@ __global__ void __launch_bounds__(kT) spmm_csr(const float* __restrict__ X, int6
 // in a fixed order (deterministic).
 // NW waves per row: 4, or 16 when rows are long (power-law partitions: the hub rows set the kernel's duration)
 template <int VEC, int NW>
-__global__ void __launch_bounds__(64 * NW) spmm_csr_rowblock(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
+__device__ __forceinline__ void spmm_csr_rowblock_body(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
                                                        const int* __restrict__ col, const float* __restrict__ val,
                                                        const float* __restrict__ diag, const float* __restrict__ bias, int act,
                                                        float drop_scale, uint32_t drop_thresh, uint64_t seed, uint32_t site,
@@ -717,6 +761,14 @@ __global__ void __launch_bounds__(64 * NW) spmm_csr_rowblock(const float* __rest
         }
         __syncthreads();
     }
+}
+template <int VEC, int NW>
+__global__ void __launch_bounds__(64 * NW) spmm_csr_rowblock(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
+                                                       const int* __restrict__ col, const float* __restrict__ val,
+                                                       const float* __restrict__ diag, const float* __restrict__ bias, int act,
+                                                       float drop_scale, uint32_t drop_thresh, uint64_t seed, uint32_t site,
+                                                       const uint64_t* __restrict__ epoch, float* __restrict__ Y) {
+    spmm_csr_rowblock_body<VEC, NW>(X, N, D, ptr, col, val, diag, bias, act, drop_scale, drop_thresh, seed, site, epoch, Y);
 }
 
 // SDDMM over the CSR: g[eid[k]] = <A[i,:], B[col[k],:]> for k in row i ; gdiag[i] = <A[i,:], B[i,:]>.
@@ -972,6 +1024,61 @@ __global__ void __launch_bounds__(1024) vecsum_small(const float* __restrict__ A
     for (; i < N; i += 1024) a0 += A[i];
     const float r = block_sum((a0 + a1) + (a2 + a3), red);
     if (threadIdx.x == 0) out[0] = r;
+}
+
+
+// ---------------------------------------------------------------- D drawn subgraphs of one partition (ensemble evaluation)
+// blockIdx.y = draw.  The bodies above run unchanged on draw d's slices, so every array equals what sgs_graph_filter /
+// sgs_gcn_norm_fwd / sgs_spmm_csr produce for that draw alone.  Forward only: in-rows (nrows = N), no out-CSR.
+__global__ void __launch_bounds__(kT) multi_filter_count(const int* __restrict__ pin_ptr, const int* __restrict__ pin_eid, int64_t N, int64_t E,
+                                                        const uint8_t* __restrict__ mask, const int64_t* __restrict__ sampled_eid, int64_t q,
+                                                        int64_t n_row_blocks, int* __restrict__ cnt, int* __restrict__ pos) {
+    const int64_t d = blockIdx.y;
+    filter_count_scatter_body<false>(pin_ptr, pin_eid, nullptr, nullptr, N, mask + d * E, sampled_eid + d * q, q, n_row_blocks, cnt + d * (N + 1),
+                                     nullptr, pos + d * E, N);
+}
+__global__ void __launch_bounds__(1024) multi_scan_counts(const int* __restrict__ cnt, int64_t N, int* __restrict__ in_ptr, int* __restrict__ cur) {
+    const int64_t d = blockIdx.y;
+    scan_counts_body(cnt + d * (N + 1), N, in_ptr + d * (N + 1), cur + d * (N + 1));
+}
+template <bool SCAN>
+__global__ void __launch_bounds__(kT) multi_filter_fill(const int* __restrict__ pin_ptr, const int* __restrict__ pin_src, const int* __restrict__ pin_eid,
+                                                       int64_t N, int64_t E, int64_t q, const uint8_t* __restrict__ mask, const int* __restrict__ pos,
+                                                       int* __restrict__ in_ptr, int* __restrict__ in_src, int* __restrict__ in_eid,
+                                                       int* __restrict__ loop_eid, const int* __restrict__ cnt) {
+    const int64_t d = blockIdx.y;
+    filter_fill_body<false, SCAN>(N, pin_ptr, pin_src, pin_eid, nullptr, nullptr, nullptr, N, mask + d * E, pos + d * E, in_ptr + d * (N + 1),
+                                  in_src + d * q, in_eid + d * q, nullptr, nullptr, nullptr, loop_eid + d * N, cnt + d * (N + 1), nullptr);
+}
+__global__ void __launch_bounds__(kT) multi_norm_deg(const float* __restrict__ w, int64_t q, int64_t N, const int* __restrict__ in_ptr,
+                                                    const int* __restrict__ in_src, const int* __restrict__ in_eid, const int* __restrict__ loop_eid,
+                                                    float* __restrict__ dis, float* __restrict__ loopw) {
+    const int64_t d = blockIdx.y;
+    norm_deg_body(w ? w + d * q : nullptr, N, in_ptr + d * (N + 1), in_src + d * q, in_eid + d * q, loop_eid + d * N, dis + d * N, loopw + d * N);
+}
+__global__ void __launch_bounds__(kT) multi_norm_weights(const float* __restrict__ w, int64_t q, int64_t N, const int* __restrict__ in_ptr,
+                                                        const int* __restrict__ in_src, const int* __restrict__ in_eid, const float* __restrict__ dis,
+                                                        const float* __restrict__ loopw, float* __restrict__ what_in, float* __restrict__ what_loop) {
+    const int64_t d = blockIdx.y;
+    norm_weights_body(N, w ? w + d * q : nullptr, N, q, in_ptr + d * (N + 1), in_src + d * q, in_eid + d * q, nullptr, nullptr, nullptr, dis + d * N,
+                      loopw + d * N, what_in + d * q, nullptr, what_loop + d * N);
+}
+template <int VEC, int LPR>
+__global__ void __launch_bounds__(kT) multi_spmm_csr(const float* __restrict__ X, int64_t xs, int64_t N, int64_t D, int64_t nnz,
+                                                    const int* __restrict__ ptr, const int* __restrict__ col, const float* __restrict__ val,
+                                                    const float* __restrict__ diag, const float* __restrict__ bias, int act, float* __restrict__ Y) {
+    const int64_t d = blockIdx.y;
+    spmm_csr_body<VEC, LPR>(X + d * xs, N, D, ptr + d * (N + 1), col + d * nnz, val + d * nnz, diag ? diag + d * N : nullptr, bias, act, 1.0f, 0u,
+                            uint64_t(0), 0u, nullptr, Y + d * N * D);
+}
+template <int VEC, int NW>
+__global__ void __launch_bounds__(64 * NW) multi_spmm_csr_rowblock(const float* __restrict__ X, int64_t xs, int64_t N, int64_t D, int64_t nnz,
+                                                                 const int* __restrict__ ptr, const int* __restrict__ col,
+                                                                 const float* __restrict__ val, const float* __restrict__ diag,
+                                                                 const float* __restrict__ bias, int act, float* __restrict__ Y) {
+    const int64_t d = blockIdx.y;
+    spmm_csr_rowblock_body<VEC, NW>(X + d * xs, N, D, ptr + d * (N + 1), col + d * nnz, val + d * nnz, diag ? diag + d * N : nullptr, bias, act,
+                                    1.0f, 0u, uint64_t(0), 0u, nullptr, Y + d * N * D);
 }
 
 inline int pick_lpr(int64_t D, int vec) {
@@ -1442,6 +1549,119 @@ int sgs_act_bwd_colsum(const float* dY, const float* Y, int64_t N, int64_t D, in
     }
     if (int rc = sgs_act_bwd(dY, Y, N * D, act, p_drop, dZ, stream_)) return rc;
     return sgs_colsum(dZ, N, D, colsum, ws, ws_bytes, stream_);
+}
+
+}  // extern "C"
+
+extern "C" {
+
+size_t sgs_graph_filter_multi_workspace_bytes(int64_t E_parent, int64_t N, int64_t D) {
+    if (E_parent < 0) E_parent = 0;
+    if (N < 0) N = 0;
+    if (D < 1) D = 1;
+    return 2 * carve_bytes(static_cast<size_t>(D * (N + 1)), 4) + carve_bytes(static_cast<size_t>(D * E_parent + 1), 4) + 256;
+}
+
+int sgs_graph_filter_multi(const int32_t* pin_ptr, const int32_t* pin_src, const int32_t* pin_eid, int64_t E_parent, int64_t N, int64_t D,
+                           const uint8_t* mask, const int64_t* sampled_eid, int64_t q, int32_t* in_ptr, int32_t* in_src, int32_t* in_eid,
+                           int32_t* loop_eid, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(E_parent >= 0 && N >= 0 && q >= 0 && q <= E_parent && E_parent < (int64_t(1) << 31) && N < (int64_t(1) << 30) && D >= 1 &&
+                    D <= 65535, SGS_EINVAL, "sgs_graph_filter_multi: bad sizes");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(pin_ptr && in_ptr && loop_eid && (E_parent == 0 || (pin_src && pin_eid && mask)) &&
+                    (q == 0 || (sampled_eid && in_src && in_eid)), SGS_EINVAL, "sgs_graph_filter_multi: null pointer");
+    SGS_REQUIRE(ws && ws_bytes >= sgs_graph_filter_multi_workspace_bytes(E_parent, N, D), SGS_EWORKSPACE,
+                "sgs_graph_filter_multi: workspace too small");
+    Carver cv(ws);
+    int* cnt = cv.take<int>(D * (N + 1));
+    int* cur = cv.take<int>(D * (N + 1));
+    int* pos = cv.take<int>(D * E_parent + 1);
+    const unsigned Du = static_cast<unsigned>(D);
+    const int64_t n_row_blocks = cdiv(N * 64, kT);
+    const dim3 g1(static_cast<unsigned>(n_row_blocks + cdiv(q, kT)), Du), g3(static_cast<unsigned>(n_row_blocks), Du), blk(kT);
+    hipLaunchKernelGGL(multi_filter_count, g1, blk, 0, stream, pin_ptr, pin_eid, N, E_parent, mask, sampled_eid, q, n_row_blocks, cnt, pos);
+    if (N <= kSelfScanRows) {
+        hipLaunchKernelGGL(multi_filter_fill<true>, g3, blk, 0, stream, pin_ptr, pin_src, pin_eid, N, E_parent, q, mask, pos, in_ptr, in_src, in_eid,
+                           loop_eid, static_cast<const int*>(cnt));
+    } else {
+        hipLaunchKernelGGL(multi_scan_counts, dim3(1, Du), dim3(1024), 0, stream, cnt, N, in_ptr, cur);
+        hipLaunchKernelGGL(multi_filter_fill<false>, g3, blk, 0, stream, pin_ptr, pin_src, pin_eid, N, E_parent, q, mask, pos, in_ptr, in_src, in_eid,
+                           loop_eid, static_cast<const int*>(cnt));
+    }
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_gcn_norm_fwd_multi(const float* w, int64_t q, int64_t N, int64_t D, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid,
+                           const int32_t* loop_eid, float* dis, float* loopw, float* what_in, float* what_loop, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(N >= 0 && q >= 0 && D >= 1 && D <= 65535, SGS_EINVAL, "sgs_gcn_norm_fwd_multi: bad sizes");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(in_ptr && loop_eid && dis && loopw && what_loop && (q == 0 || (in_src && in_eid && what_in)), SGS_EINVAL,
+                "sgs_gcn_norm_fwd_multi: null pointer");
+    const dim3 g(static_cast<unsigned>(cdiv(N * 64, kT)), static_cast<unsigned>(D));
+    hipLaunchKernelGGL(multi_norm_deg, g, dim3(kT), 0, stream, w, q, N, in_ptr, in_src, in_eid, loop_eid, dis, loopw);
+    hipLaunchKernelGGL(multi_norm_weights, g, dim3(kT), 0, stream, w, q, N, in_ptr, in_src, in_eid, dis, loopw, what_in, what_loop);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+#define DISPATCH_VEC_LPR_Y(KERNEL, vec, lpr, grid_rows, gy, ...)                                                  \
+    do {                                                                                                          \
+        const int _rpb = kT / (lpr);                                                                              \
+        const dim3 _g(static_cast<unsigned>(cdiv((grid_rows), _rpb)), (gy)), _b(kT);                              \
+        if ((vec) == 4) {                                                                                         \
+            switch (lpr) {                                                                                        \
+                case 1: hipLaunchKernelGGL((KERNEL<4, 1>), _g, _b, 0, stream, __VA_ARGS__); break;                \
+                case 2: hipLaunchKernelGGL((KERNEL<4, 2>), _g, _b, 0, stream, __VA_ARGS__); break;                \
+                case 4: hipLaunchKernelGGL((KERNEL<4, 4>), _g, _b, 0, stream, __VA_ARGS__); break;                \
+                case 8: hipLaunchKernelGGL((KERNEL<4, 8>), _g, _b, 0, stream, __VA_ARGS__); break;                \
+                case 16: hipLaunchKernelGGL((KERNEL<4, 16>), _g, _b, 0, stream, __VA_ARGS__); break;              \
+                case 32: hipLaunchKernelGGL((KERNEL<4, 32>), _g, _b, 0, stream, __VA_ARGS__); break;              \
+                default: hipLaunchKernelGGL((KERNEL<4, 64>), _g, _b, 0, stream, __VA_ARGS__); break;              \
+            }                                                                                                     \
+        } else {                                                                                                  \
+            switch (lpr) {                                                                                        \
+                case 1: hipLaunchKernelGGL((KERNEL<1, 1>), _g, _b, 0, stream, __VA_ARGS__); break;                \
+                case 2: hipLaunchKernelGGL((KERNEL<1, 2>), _g, _b, 0, stream, __VA_ARGS__); break;                \
+                case 4: hipLaunchKernelGGL((KERNEL<1, 4>), _g, _b, 0, stream, __VA_ARGS__); break;                \
+                case 8: hipLaunchKernelGGL((KERNEL<1, 8>), _g, _b, 0, stream, __VA_ARGS__); break;                \
+                case 16: hipLaunchKernelGGL((KERNEL<1, 16>), _g, _b, 0, stream, __VA_ARGS__); break;              \
+                case 32: hipLaunchKernelGGL((KERNEL<1, 32>), _g, _b, 0, stream, __VA_ARGS__); break;              \
+                default: hipLaunchKernelGGL((KERNEL<1, 64>), _g, _b, 0, stream, __VA_ARGS__); break;              \
+            }                                                                                                     \
+        }                                                                                                         \
+    } while (0)
+
+int sgs_spmm_csr_multi(const float* X, int64_t x_stride, int64_t N, int64_t Dc, int64_t nnz, int64_t D, const int32_t* ptr, const int32_t* col,
+                       const float* val, const float* diag, const float* bias, int act, float* Y, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(N >= 0 && Dc >= 0 && nnz >= 0 && D >= 1 && D <= 65535 && x_stride >= 0, SGS_EINVAL, "sgs_spmm_csr_multi: bad sizes");
+    SGS_REQUIRE(act == SGS_ACT_NONE || act == SGS_ACT_RELU, SGS_EINVAL, "sgs_spmm_csr_multi: act must be NONE or RELU (forward only)");
+    if (N == 0 || Dc == 0) return SGS_OK;
+    SGS_REQUIRE(X && ptr && Y && (nnz == 0 || (col && val)), SGS_EINVAL, "sgs_spmm_csr_multi: null pointer");
+    SGS_REQUIRE(x_stride == 0 || x_stride >= N * Dc, SGS_EINVAL, "sgs_spmm_csr_multi: x_stride must be 0 (shared X) or >= N * Dc");
+    SGS_REQUIRE(X + (D - 1) * x_stride + N * Dc <= Y || Y + D * N * Dc <= X, SGS_EINVAL, "sgs_spmm_csr_multi: X and Y overlap");
+    const int vec = (Dc % 4 == 0 && x_stride % 4 == 0 && aligned16(X) && aligned16(Y)) ? 4 : 1;
+    const int lpr = pick_lpr(Dc, vec);
+    const unsigned Du = static_cast<unsigned>(D);
+    if (N <= 65536 && nnz >= 16 * N) {        // the rowblock / row-per-lanes choice of sgs_spmm_csr, so every draw equals it
+        const bool wide = nnz >= 256 * N;
+        const dim3 g_(static_cast<unsigned>(N), Du);
+        if (vec == 4 && wide)
+            hipLaunchKernelGGL((multi_spmm_csr_rowblock<4, 16>), g_, dim3(1024), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
+        else if (vec == 4)
+            hipLaunchKernelGGL((multi_spmm_csr_rowblock<4, 4>), g_, dim3(kT), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
+        else if (wide)
+            hipLaunchKernelGGL((multi_spmm_csr_rowblock<1, 16>), g_, dim3(1024), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
+        else
+            hipLaunchKernelGGL((multi_spmm_csr_rowblock<1, 4>), g_, dim3(kT), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
+    } else {
+        DISPATCH_VEC_LPR_Y(multi_spmm_csr, vec, lpr, N, Du, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
+    }
+    SGS_LAUNCH_OK();
+    return SGS_OK;
 }
 
 }  // extern "C"

@@ -395,6 +395,47 @@ __global__ void __launch_bounds__(kT) reg_bwd_edges(const float* __restrict__ w,
     }
 }
 
+
+// ---------------------------------------------------------------- ensemble mean + the three split counts (evaluate.py, ensemble_evaluate)
+// One wave per row.  acc = ((o_0 + o_1) + o_2) + ... in draw order (fp32, as the serial loop's `out = out + o`), carried across passes in
+// `acc`; the last pass multiplies by 1/D when D > 1 -- torch's true division by a Python scalar is a multiply by the fp32 reciprocal on the
+// device -- and counts the argmax (first maximum wins, as masked_correct) against y on the three masks into counts[6] (int64, accumulated).
+__global__ void __launch_bounds__(kT) ensemble_mean_correct(const float* __restrict__ logits, int64_t xs, int Dc, int64_t N, int64_t C,
+                                                           float* __restrict__ acc, int first, int last, int D_total, float inv,
+                                                           const int64_t* __restrict__ y, const uint8_t* __restrict__ m0,
+                                                           const uint8_t* __restrict__ m1, const uint8_t* __restrict__ m2,
+                                                           unsigned long long* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    if (i >= N) return;
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int64_t c = lane; c < C; c += 64) {
+        float v = first ? logits[i * C + c] : acc[i * C + c];
+        for (int d = first ? 1 : 0; d < Dc; ++d) v = __fadd_rn(v, logits[static_cast<int64_t>(d) * xs + i * C + c]);
+        if (last && D_total > 1) v = __fmul_rn(v, inv);
+        acc[i * C + c] = v;
+        if (v > best || (v == best && static_cast<int>(c) < bi) || bi == 0x7fffffff) { best = v; bi = static_cast<int>(c); }
+    }
+    if (!last) return;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; }
+    }
+    if (lane == 0) {
+        const bool ok = static_cast<int64_t>(bi) == y[i];
+        const uint8_t* ms[3] = {m0, m1, m2};
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+            if (ms[s][i]) {
+                atomicAdd(&counts[2 * s + 1], 1ull);
+                if (ok) atomicAdd(&counts[2 * s], 1ull);
+            }
+    }
+}
+
 }  // namespace
 }  // namespace sgs
 
@@ -560,6 +601,21 @@ int sgs_edge_reg_bwd(const float* w, const int64_t* sampled_edge_index, int64_t 
                 "sgs_edge_reg_bwd: null pointer");
     hipLaunchKernelGGL(reg_bwd_edges, dim3(cdiv(q, kT / 16)), dim3(kT), 0, stream, w, sampled_edge_index, q, logits, C, y, train_mask, out,
                        coef1, coef2, static_cast<float>(q_global), grad_loss, dw, Gs, Gd);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_ensemble_mean_correct(const float* logits, int64_t x_stride, int64_t Dc, int64_t N, int64_t C, float* acc, int first, int last,
+                              int64_t D_total, const int64_t* y, const uint8_t* mask0, const uint8_t* mask1, const uint8_t* mask2, int64_t* counts,
+                              sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(Dc >= 1 && N >= 0 && C > 0 && D_total >= Dc && x_stride >= 0 && (Dc == 1 || x_stride == 0 || x_stride >= N * C), SGS_EINVAL,
+                "sgs_ensemble_mean_correct: bad sizes");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(logits && acc && (!last || (y && mask0 && mask1 && mask2 && counts)), SGS_EINVAL, "sgs_ensemble_mean_correct: null pointer");
+    const float inv = 1.0f / static_cast<float>(D_total);
+    hipLaunchKernelGGL(ensemble_mean_correct, dim3(cdiv(N * 64, kT)), dim3(kT), 0, stream, logits, x_stride, static_cast<int>(Dc), N, C, acc,
+                       first, last, static_cast<int>(D_total), inv, y, mask0, mask1, mask2, reinterpret_cast<unsigned long long*>(counts));
     SGS_LAUNCH_OK();
     return SGS_OK;
 }

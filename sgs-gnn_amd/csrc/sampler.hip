@@ -95,11 +95,11 @@ __device__ __forceinline__ float sample_prob(float pv, float Zeps, float mx, flo
 }
 
 template <int MODE>
-__global__ void __launch_bounds__(kThreads) keys_hist0(const float* __restrict__ p, const float* __restrict__ prior,
-                                                      const float* __restrict__ noise, uint64_t seed,
-                                                      uint64_t stream_id, const uint64_t* __restrict__ epoch, int64_t edge_offset, int64_t E, float one_minus_c, float c,
-                                                      const float* __restrict__ scal, uint32_t* __restrict__ keys,
-                                                      float* __restrict__ keys_out, uint32_t* __restrict__ hist) {
+__device__ __forceinline__ void keys_hist0_body(const float* __restrict__ p, const float* __restrict__ prior,
+                                                const float* __restrict__ noise, uint64_t seed,
+                                                uint64_t stream_id, const uint64_t* __restrict__ epoch, int64_t edge_offset, int64_t E, float one_minus_c, float c,
+                                                const float* __restrict__ scal, uint32_t* __restrict__ keys,
+                                                float* __restrict__ keys_out, uint32_t* __restrict__ hist) {
     __shared__ uint32_t lh[kBins];
     for (int i = threadIdx.x; i < kBins; i += kThreads) lh[i] = 0;
     __syncthreads();
@@ -133,11 +133,19 @@ __global__ void __launch_bounds__(kThreads) keys_hist0(const float* __restrict__
         if (v) atomicAdd(&hist[i], v);
     }
 }
+template <int MODE>
+__global__ void __launch_bounds__(kThreads) keys_hist0(const float* __restrict__ p, const float* __restrict__ prior,
+                                                      const float* __restrict__ noise, uint64_t seed,
+                                                      uint64_t stream_id, const uint64_t* __restrict__ epoch, int64_t edge_offset, int64_t E, float one_minus_c, float c,
+                                                      const float* __restrict__ scal, uint32_t* __restrict__ keys,
+                                                      float* __restrict__ keys_out, uint32_t* __restrict__ hist) {
+    keys_hist0_body<MODE>(p, prior, noise, seed, stream_id, epoch, edge_offset, E, one_minus_c, c, scal, keys, keys_out, hist);
+}
 
 // Histogram of the next digit among keys whose higher digits equal state->prefix.
-__global__ void __launch_bounds__(kThreads) hist_next(const uint32_t* __restrict__ keys, int64_t E, int shift,
-                                                     uint32_t digit_mask, int prev_shift,
-                                                     const SelectState* __restrict__ st, uint32_t* __restrict__ hist) {
+__device__ __forceinline__ void hist_next_body(const uint32_t* __restrict__ keys, int64_t E, int shift,
+                                               uint32_t digit_mask, int prev_shift,
+                                               const SelectState* __restrict__ st, uint32_t* __restrict__ hist) {
     __shared__ uint32_t lh[kBins];
     for (int i = threadIdx.x; i < kBins; i += kThreads) lh[i] = 0;
     __syncthreads();
@@ -159,6 +167,11 @@ __global__ void __launch_bounds__(kThreads) hist_next(const uint32_t* __restrict
         const uint32_t v = lh[i];
         if (v) atomicAdd(&hist[i], v);
     }
+}
+__global__ void __launch_bounds__(kThreads) hist_next(const uint32_t* __restrict__ keys, int64_t E, int shift,
+                                                     uint32_t digit_mask, int prev_shift,
+                                                     const SelectState* __restrict__ st, uint32_t* __restrict__ hist) {
+    hist_next_body(keys, E, shift, digit_mask, prev_shift, st, hist);
 }
 
 // One block: locate the digit bin holding the k_rem-th largest key of the current prefix.
@@ -228,8 +241,8 @@ __device__ __forceinline__ void load_keys8(const uint32_t* __restrict__ keys, in
     }
 }
 
-__global__ void __launch_bounds__(kThreads) count_blocks(const uint32_t* __restrict__ keys, int64_t E,
-                                                        const SelectState* __restrict__ st, uint2* __restrict__ cnt) {
+__device__ __forceinline__ void count_blocks_body(const uint32_t* __restrict__ keys, int64_t E,
+                                                  const SelectState* __restrict__ st, uint2* __restrict__ cnt) {
     __shared__ int red[2 * (kThreads / 64)];
     const uint32_t T = st->prefix;
     const int64_t e0 = static_cast<int64_t>(blockIdx.x) * kChunk + static_cast<int64_t>(threadIdx.x) * kItems;
@@ -252,6 +265,10 @@ __global__ void __launch_bounds__(kThreads) count_blocks(const uint32_t* __restr
         for (int w = 0; w < kThreads / 64; ++w) { g += red[2 * w]; q_ += red[2 * w + 1]; }
         cnt[blockIdx.x] = make_uint2(static_cast<uint32_t>(g), static_cast<uint32_t>(q_));
     }
+}
+__global__ void __launch_bounds__(kThreads) count_blocks(const uint32_t* __restrict__ keys, int64_t E,
+                                                        const SelectState* __restrict__ st, uint2* __restrict__ cnt) {
+    count_blocks_body(keys, E, st, cnt);
 }
 
 // One block: exclusive scan of the per-block (gt, eq) counts, in place.
@@ -574,10 +591,10 @@ __global__ void __launch_bounds__(kKeyThreads) small_keys_hist0(const float* __r
 
 // pass d (1 or 2): every workgroup first finishes digit d-1 from the complete hist_prev (+ the state workgroup 0 of the
 // previous pass published), then histograms digit d of the keys matching the prefix; workgroup 0 publishes the state.
-__global__ void __launch_bounds__(kThreads) small_hist_next(const uint32_t* __restrict__ keys, int64_t E, int shift, uint32_t digit_mask,
-                                                           int prev_shift, int first, uint32_t q, const uint32_t* __restrict__ hist_prev,
-                                                           const SelPart* __restrict__ sel_in, SelPart* __restrict__ sel_out,
-                                                           uint32_t* __restrict__ hist, const int64_t* __restrict__ dynE) {
+__device__ __forceinline__ void small_hist_next_body(const uint32_t* __restrict__ keys, int64_t E, int shift, uint32_t digit_mask,
+                                                     int prev_shift, int first, uint32_t q, const uint32_t* __restrict__ hist_prev,
+                                                     const SelPart* __restrict__ sel_in, SelPart* __restrict__ sel_out,
+                                                     uint32_t* __restrict__ hist, const int64_t* __restrict__ dynE) {
     __shared__ uint32_t lh[kBins];
     int64_t nblk_ = 0;
     if (!dyn_range(dynE, E, nblk_)) return;
@@ -606,13 +623,19 @@ __global__ void __launch_bounds__(kThreads) small_hist_next(const uint32_t* __re
         if (v) atomicAdd(&hist[i], v);
     }
 }
+__global__ void __launch_bounds__(kThreads) small_hist_next(const uint32_t* __restrict__ keys, int64_t E, int shift, uint32_t digit_mask,
+                                                           int prev_shift, int first, uint32_t q, const uint32_t* __restrict__ hist_prev,
+                                                           const SelPart* __restrict__ sel_in, SelPart* __restrict__ sel_out,
+                                                           uint32_t* __restrict__ hist, const int64_t* __restrict__ dynE) {
+    small_hist_next_body(keys, E, shift, digit_mask, prev_shift, first, q, hist_prev, sel_in, sel_out, hist, dynE);
+}
 
 // every workgroup finishes the last digit (threshold T, ties to take), counts its chunk; workgroup 0 publishes the final
 // SelectState and the stats
-__global__ void __launch_bounds__(kThreads) small_count(const uint32_t* __restrict__ keys, int64_t E, uint32_t q,
-                                                       const uint32_t* __restrict__ hist2, const SelPart* __restrict__ sel_in,
-                                                       SelectState* __restrict__ st, uint2* __restrict__ cnt, const float* __restrict__ scal,
-                                                       float* __restrict__ stats, const int64_t* __restrict__ dynE) {
+__device__ __forceinline__ void small_count_body(const uint32_t* __restrict__ keys, int64_t E, uint32_t q,
+                                                 const uint32_t* __restrict__ hist2, const SelPart* __restrict__ sel_in,
+                                                 SelectState* __restrict__ st, uint2* __restrict__ cnt, const float* __restrict__ scal,
+                                                 float* __restrict__ stats, const int64_t* __restrict__ dynE) {
     __shared__ int red[2 * (kThreads / 64)];
     int64_t nblk_ = 0;
     if (!dyn_range(dynE, E, nblk_)) return;
@@ -652,13 +675,19 @@ __global__ void __launch_bounds__(kThreads) small_count(const uint32_t* __restri
         cnt[blockIdx.x] = make_uint2(static_cast<uint32_t>(g), static_cast<uint32_t>(q_));
     }
 }
+__global__ void __launch_bounds__(kThreads) small_count(const uint32_t* __restrict__ keys, int64_t E, uint32_t q,
+                                                       const uint32_t* __restrict__ hist2, const SelPart* __restrict__ sel_in,
+                                                       SelectState* __restrict__ st, uint2* __restrict__ cnt, const float* __restrict__ scal,
+                                                       float* __restrict__ stats, const int64_t* __restrict__ dynE) {
+    small_count_body(keys, E, q, hist2, sel_in, st, cnt, scal, stats, dynE);
+}
 
 // compaction with the exclusive prefix over the preceding chunks' (gt, eq) counts recomputed by each workgroup
-__global__ void __launch_bounds__(kThreads) small_compact(const uint32_t* __restrict__ keys, int64_t E, int64_t q, const SelectState* __restrict__ st,
-                                                         const uint2* __restrict__ cnt, const float* __restrict__ p,
-                                                         const int64_t* __restrict__ edge_index, uint8_t* __restrict__ mask, int mask_aligned,
-                                                         int64_t* __restrict__ sampled_eid, int64_t* __restrict__ sei,
-                                                         float* __restrict__ sampled_p, const int64_t* __restrict__ dynE) {
+__device__ __forceinline__ void small_compact_body(const uint32_t* __restrict__ keys, int64_t E, int64_t q, const SelectState* __restrict__ st,
+                                                   const uint2* __restrict__ cnt, const float* __restrict__ p,
+                                                   const int64_t* __restrict__ edge_index, uint8_t* __restrict__ mask, int mask_aligned,
+                                                   int64_t* __restrict__ sampled_eid, int64_t* __restrict__ sei,
+                                                   float* __restrict__ sampled_p, const int64_t* __restrict__ dynE) {
     __shared__ int red[2 * (kThreads / 64)];
     __shared__ uint32_t pre[2];
     const int64_t Ecap = E;                       // row stride of edge_index (the capacity under sgs_dyn_edges_set)
@@ -678,6 +707,13 @@ __global__ void __launch_bounds__(kThreads) small_compact(const uint32_t* __rest
     }
     __syncthreads();
     compact_body(pre[0], pre[1], keys, E, Ecap, q, int64_t(-1), int64_t(0), st, p, edge_index, mask, mask_aligned, sampled_eid, sei, sampled_p);
+}
+__global__ void __launch_bounds__(kThreads) small_compact(const uint32_t* __restrict__ keys, int64_t E, int64_t q, const SelectState* __restrict__ st,
+                                                         const uint2* __restrict__ cnt, const float* __restrict__ p,
+                                                         const int64_t* __restrict__ edge_index, uint8_t* __restrict__ mask, int mask_aligned,
+                                                         int64_t* __restrict__ sampled_eid, int64_t* __restrict__ sei,
+                                                         float* __restrict__ sampled_p, const int64_t* __restrict__ dynE) {
+    small_compact_body(keys, E, q, st, cnt, p, edge_index, mask, mask_aligned, sampled_eid, sei, sampled_p, dynE);
 }
 
 // counts[0] = #keys > threshold, counts[1] = #keys == threshold in this shard (before the scan).
@@ -748,9 +784,9 @@ __global__ void dropout_keep_kernel(uint64_t seed, uint32_t site, const uint64_t
 // ---------------------------------------------------------------- straight-through weights
 // sampling.py:137-138,155:  w = clamp(p * ((one_hot - s).detach() + s), 0, 1)[mask]
 template <bool HAS_PRIOR>
-__global__ void st_fwd_kernel(const float* __restrict__ p, const float* __restrict__ prior, float one_minus_c, float c,
-                              const float* __restrict__ stats, const int64_t* __restrict__ eid, int64_t q,
-                              float* __restrict__ w) {
+__device__ __forceinline__ void st_fwd_body(const float* __restrict__ p, const float* __restrict__ prior, float one_minus_c, float c,
+                                            const float* __restrict__ stats, const int64_t* __restrict__ eid, int64_t q,
+                                            float* __restrict__ w) {
     const int64_t j = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (j >= q) return;
     const int64_t e = eid[j];
@@ -761,6 +797,12 @@ __global__ void st_fwd_kernel(const float* __restrict__ p, const float* __restri
     const float st = __fadd_rn(__fsub_rn(1.0f, s), s);
     const float v = __fmul_rn(pv, st);
     w[j] = fminf(fmaxf(v, 0.f), 1.f);
+}
+template <bool HAS_PRIOR>
+__global__ void st_fwd_kernel(const float* __restrict__ p, const float* __restrict__ prior, float one_minus_c, float c,
+                              const float* __restrict__ stats, const int64_t* __restrict__ eid, int64_t q,
+                              float* __restrict__ w) {
+    st_fwd_body<HAS_PRIOR>(p, prior, one_minus_c, c, stats, eid, q, w);
 }
 
 // backward: h_e = g_e [0 <= p_e st_e <= 1];  S = sum_sel h_e p_e^2
@@ -824,6 +866,176 @@ __global__ void st_bwd_sparse(const float* __restrict__ p, const float* __restri
     const float v = pv * st;
     const float h = (v >= 0.f && v <= 1.f) ? gw[j] : 0.f;
     dp[e] += h * (st + a * pv / Zeps);   // eids are unique: no race
+}
+
+
+// ---------------------------------------------------------------- D draws of one candidate set in one pass (ensemble evaluation)
+// sgs_sample_topq_multi: draw d is sgs_sample_topq with stream id stream_id0 + d (or noise row d), bit for bit -- the same bodies run
+// with a draw index in the grid (blockIdx.y), so every radix-select stage is ONE launch for all D draws.  The normaliser (Z, or max and
+// sum of exp) does not depend on the noise: it is reduced once.  The key pass loads p / prior once per edge and loops over a group of
+// kMultiG draws with one LDS histogram each; it STORES the D key arrays (rows padded to 64 keys, so load_keys8's 16-byte loads stay
+// aligned) rather than recomputing them from the hash in the three later passes: at partition scale the D x 4E bytes stay in the
+// Infinity Cache, and a recompute would put three more Philox evaluations per key and draw on passes that are otherwise pure loads.
+constexpr int kMultiG = 4;                   // draws per key-pass workgroup: 4 x 8 KiB of LDS histograms beside 16 waves
+
+__host__ __device__ inline int64_t multi_key_stride(int64_t E) { return (E + 63) & ~int64_t(63); }
+
+template <int MODE>
+__global__ void __launch_bounds__(kKeyThreads) multi_keys_hist0(const float* __restrict__ p, const float* __restrict__ prior,
+                                                               const float* __restrict__ noise, uint64_t seed, uint64_t stream_id0,
+                                                               const uint64_t* __restrict__ epoch, int64_t E, int D, float one_minus_c, float c,
+                                                               const float* __restrict__ part_sum, const float* __restrict__ part_max,
+                                                               int64_t nblk, float* __restrict__ scal, uint32_t* __restrict__ keys,
+                                                               int64_t ks, uint32_t* __restrict__ hist3) {
+    __shared__ uint32_t lh[kMultiG][kBins];
+    __shared__ float red[kKeyThreads / 64];
+    const int d0 = blockIdx.y * kMultiG;
+    const int G = (D - d0) < kMultiG ? (D - d0) : kMultiG;
+    for (int i = threadIdx.x; i < kMultiG * kBins; i += kKeyThreads) (&lh[0][0])[i] = 0;
+    seed = fold_epoch(seed, epoch);
+    const bool has_prior = prior != nullptr;
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * kChunk;
+    float pv[kKeyItems], qv[kKeyItems];
+#pragma unroll
+    for (int i = 0; i < kKeyItems; ++i) {
+        const int64_t e = base + static_cast<int64_t>(i) * kKeyThreads + threadIdx.x;
+        const int64_t ec = e < E ? e : E - 1;
+        pv[i] = p ? p[ec] : 1.f;
+        qv[i] = has_prior ? prior[ec] : 0.f;
+    }
+    const float mx = (MODE == SGS_SAMPLE_PRIOR) ? final_reduce_all<1>(part_max, nblk, red) : 0.f;
+    const float Z = final_reduce_all<0>(part_sum, nblk, red);          // (syncs: lh is cleared for everyone)
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { scal[0] = Z; scal[1] = mx; }
+    const float Zeps = (MODE == SGS_SAMPLE_LEARNED) ? __fadd_rn(Z, 1e-12f) : Z;
+    float sv[kKeyItems];
+#pragma unroll
+    for (int i = 0; i < kKeyItems; ++i) sv[i] = sample_prob<MODE>(pv[i], Zeps, mx, qv[i], has_prior, one_minus_c, c);
+    for (int g = 0; g < G; ++g) {
+        const int d = d0 + g;
+        float kf[kKeyItems];
+#pragma unroll
+        for (int i = 0; i < kKeyItems; ++i) {
+            const int64_t e = base + static_cast<int64_t>(i) * kKeyThreads + threadIdx.x;
+            kf[i] = 0.f;
+            if (e < E) {
+                const float nz = noise ? noise[static_cast<int64_t>(d) * E + e] : exp_noise_at(seed, stream_id0 + d, static_cast<uint64_t>(e));
+                kf[i] = __fdiv_rn(sv[i], nz);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < kKeyItems; ++i) {
+            const int64_t e = base + static_cast<int64_t>(i) * kKeyThreads + threadIdx.x;
+            if (e < E) {
+                const uint32_t bits = __float_as_uint(kf[i]);
+                keys[static_cast<int64_t>(d) * ks + e] = bits;
+                atomicAdd(&lh[g][bits >> kShift0], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int g = 0; g < G; ++g)
+        for (int i = threadIdx.x; i < kBins; i += kKeyThreads) {
+            const uint32_t v = lh[g][i];
+            if (v) atomicAdd(&hist3[static_cast<int64_t>(d0 + g) * 3 * kBins + i], v);
+        }
+}
+
+// pass 1 (first = 1) or 2 of the fused small-E path for draw blockIdx.y
+__global__ void __launch_bounds__(kThreads) multi_small_hist_next(const uint32_t* __restrict__ keys, int64_t ks, int64_t E, int shift,
+                                                                 uint32_t digit_mask, int prev_shift, int first, uint32_t q,
+                                                                 uint32_t* __restrict__ hist3, SelPart* __restrict__ sel) {
+    const int64_t d = blockIdx.y;
+    uint32_t* h = hist3 + d * 3 * kBins;
+    const int pass = first ? 1 : 2;
+    small_hist_next_body(keys + d * ks, E, shift, digit_mask, prev_shift, first, q, h + (pass - 1) * kBins,
+                         first ? nullptr : sel + 2 * d, sel + 2 * d + (first ? 0 : 1), h + pass * kBins, nullptr);
+}
+
+__global__ void __launch_bounds__(kThreads) multi_small_count(const uint32_t* __restrict__ keys, int64_t ks, int64_t E, uint32_t q,
+                                                             const uint32_t* __restrict__ hist3, const SelPart* __restrict__ sel,
+                                                             SelectState* __restrict__ st, uint2* __restrict__ cnt, int64_t cs,
+                                                             const float* __restrict__ scal, float* __restrict__ stats) {
+    const int64_t d = blockIdx.y;
+    small_count_body(keys + d * ks, E, q, hist3 + d * 3 * kBins + 2 * kBins, sel + 2 * d + 1, st + d, cnt + d * cs, scal,
+                     stats ? stats + 4 * d : nullptr, nullptr);
+}
+
+__global__ void __launch_bounds__(kThreads) multi_small_compact(const uint32_t* __restrict__ keys, int64_t ks, int64_t E, int64_t q,
+                                                               const SelectState* __restrict__ st, const uint2* __restrict__ cnt, int64_t cs,
+                                                               const float* __restrict__ p, const int64_t* __restrict__ edge_index,
+                                                               uint8_t* __restrict__ mask, int64_t* __restrict__ sampled_eid,
+                                                               int64_t* __restrict__ sei, float* __restrict__ sampled_p) {
+    const int64_t d = blockIdx.y;
+    uint8_t* m = mask + d * E;
+    small_compact_body(keys + d * ks, E, q, st + d, cnt + d * cs, p, edge_index, m, (reinterpret_cast<uintptr_t>(m) & 7) == 0,
+                       sampled_eid ? sampled_eid + d * q : nullptr, sei ? sei + d * 2 * q : nullptr, sampled_p ? sampled_p + d * q : nullptr,
+                       nullptr);
+}
+
+// large-E path, draw blockIdx.y
+template <int MODE>
+__global__ void __launch_bounds__(kThreads) multi_keys_hist0_large(const float* __restrict__ p, const float* __restrict__ prior,
+                                                                  const float* __restrict__ noise, uint64_t seed, uint64_t stream_id0,
+                                                                  const uint64_t* __restrict__ epoch, int64_t E, float one_minus_c, float c,
+                                                                  const float* __restrict__ scal, uint32_t* __restrict__ keys, int64_t ks,
+                                                                  uint32_t* __restrict__ hist) {
+    const int64_t d = blockIdx.y;
+    keys_hist0_body<MODE>(p, prior, noise ? noise + d * E : nullptr, seed, stream_id0 + d, epoch, int64_t(0), E, one_minus_c, c, scal,
+                          keys + d * ks, nullptr, hist + d * kBins);
+}
+__global__ void __launch_bounds__(kThreads) multi_select_digit(uint32_t* __restrict__ hist, int shift, int first, uint32_t q,
+                                                              SelectState* __restrict__ st) {
+    select_digit_body(hist + static_cast<int64_t>(blockIdx.y) * kBins, shift, first, q, st + blockIdx.y);
+}
+__global__ void __launch_bounds__(kThreads) multi_hist_next(const uint32_t* __restrict__ keys, int64_t ks, int64_t E, int shift,
+                                                           uint32_t digit_mask, int prev_shift, const SelectState* __restrict__ st,
+                                                           uint32_t* __restrict__ hist) {
+    const int64_t d = blockIdx.y;
+    hist_next_body(keys + d * ks, E, shift, digit_mask, prev_shift, st + d, hist + d * kBins);
+}
+__global__ void __launch_bounds__(kThreads) multi_count_blocks(const uint32_t* __restrict__ keys, int64_t ks, int64_t E,
+                                                              const SelectState* __restrict__ st, uint2* __restrict__ cnt, int64_t cs) {
+    const int64_t d = blockIdx.y;
+    count_blocks_body(keys + d * ks, E, st + d, cnt + d * cs);
+}
+__global__ void __launch_bounds__(kThreads) multi_scan_blocks(uint2* __restrict__ cnt, int64_t cs, int64_t nblk) {
+    scan_blocks_body(cnt + static_cast<int64_t>(blockIdx.y) * cs, nblk);
+}
+__global__ void __launch_bounds__(kThreads) multi_compact(const uint32_t* __restrict__ keys, int64_t ks, int64_t E, int64_t q,
+                                                         const SelectState* __restrict__ st, const uint2* __restrict__ cnt, int64_t cs,
+                                                         const float* __restrict__ p, const int64_t* __restrict__ edge_index,
+                                                         uint8_t* __restrict__ mask, int64_t* __restrict__ sampled_eid, int64_t* __restrict__ sei,
+                                                         float* __restrict__ sampled_p) {
+    const int64_t d = blockIdx.y;
+    uint8_t* m = mask + d * E;
+    const uint2 c = cnt[d * cs + blockIdx.x];
+    compact_body(c.x, c.y, keys + d * ks, E, E, q, int64_t(-1), int64_t(0), st + d, p, edge_index, m, (reinterpret_cast<uintptr_t>(m) & 7) == 0,
+                 sampled_eid ? sampled_eid + d * q : nullptr, sei ? sei + d * 2 * q : nullptr, sampled_p ? sampled_p + d * q : nullptr);
+}
+__global__ void multi_write_stats(const float* __restrict__ scal, const SelectState* __restrict__ st, float* __restrict__ stats) {
+    const int d = blockIdx.y;
+    stats[4 * d + 0] = scal[0];
+    stats[4 * d + 1] = scal[1];
+    stats[4 * d + 2] = __uint_as_float(st[d].prefix);
+    stats[4 * d + 3] = static_cast<float>(st[d].k_rem);
+}
+__global__ void multi_select_all(int64_t E, const float* __restrict__ p, const int64_t* __restrict__ edge_index, uint8_t* __restrict__ mask,
+                                 int64_t* __restrict__ sampled_eid, int64_t* __restrict__ sei, float* __restrict__ sampled_p, uint8_t value) {
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int64_t d = blockIdx.y;
+    if (e >= E) return;
+    mask[d * E + e] = value;
+    if (value) {
+        if (sampled_eid) sampled_eid[d * E + e] = e;
+        if (sei) { sei[d * 2 * E + e] = edge_index[e]; sei[d * 2 * E + E + e] = edge_index[E + e]; }
+        if (sampled_p) sampled_p[d * E + e] = p ? p[e] : 1.f;
+    }
+}
+template <bool HAS_PRIOR>
+__global__ void multi_st_fwd(const float* __restrict__ p, const float* __restrict__ prior, float one_minus_c, float c,
+                             const float* __restrict__ stats, const int64_t* __restrict__ eid, int64_t q, float* __restrict__ w) {
+    const int64_t d = blockIdx.y;
+    st_fwd_body<HAS_PRIOR>(p, prior, one_minus_c, c, stats + 4 * d, eid + d * q, q, w + d * q);
 }
 
 }  // namespace
@@ -1153,6 +1365,127 @@ int sgs_st_weights_bwd(const float* p, const float* prior, double degree_bias_co
         else
             hipLaunchKernelGGL(st_bwd_sparse<false>, dim3(cdiv(q, 256)), dim3(256), 0, stream, p, prior, one_minus_c, c, a,
                                stats, sampled_eid, grad_w, q, grad_p);
+    }
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
+
+size_t sgs_sample_topq_multi_workspace_bytes(int64_t E, int64_t D) {
+    if (E < 0) E = 0;
+    if (D < 1) D = 1;
+    const int64_t nblk = cdiv(E, kChunk) + 1;
+    return carve_bytes(static_cast<size_t>(multi_key_stride(E) * D), 4)   // keys, one padded row per draw
+           + 2 * carve_bytes(nblk, 4)                                     // partials (sum / max, sum of exp)
+           + carve_bytes(4, 4)                                            // scalars Z, max
+           + carve_bytes(static_cast<size_t>(3 * kBins * D), 4)           // digit histograms (3 per draw on the small path, 1 on the large)
+           + carve_bytes(D, sizeof(SelectState))
+           + carve_bytes(static_cast<size_t>(nblk * D), sizeof(uint2))
+           + carve_bytes(2 * D, sizeof(SelPart)) + 256;
+}
+
+int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
+                          uint64_t stream_id0, int64_t D, int64_t E, int64_t q, const int64_t* edge_index, uint8_t* mask, int64_t* sampled_eid,
+                          int64_t* sampled_edge_index, float* stats, float* st_weights, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(mode == SGS_SAMPLE_LEARNED || mode == SGS_SAMPLE_PRIOR, SGS_EINVAL, "sgs_sample_topq_multi: bad mode %d", mode);
+    SGS_REQUIRE(D >= 1 && D <= 65535, SGS_EINVAL, "sgs_sample_topq_multi: D=%lld draws (need 1 <= D <= 65535)", (long long)D);
+    SGS_REQUIRE(E >= 0 && q >= 0, SGS_EINVAL, "sgs_sample_topq_multi: negative size (E=%lld q=%lld)", (long long)E, (long long)q);
+    SGS_REQUIRE(q <= E, SGS_EINVAL,
+                "sgs_sample_topq_multi: cannot sample q=%lld > E=%lld edges without replacement", (long long)q, (long long)E);
+    SGS_REQUIRE(E < (int64_t(1) << 32), SGS_EINVAL, "sgs_sample_topq_multi: E=%lld exceeds 2^32-1", (long long)E);
+    if (E == 0) return SGS_OK;
+    SGS_REQUIRE(mask, SGS_EINVAL, "sgs_sample_topq_multi: null mask");
+    SGS_REQUIRE(p || (mode == SGS_SAMPLE_LEARNED && !prior), SGS_EINVAL,
+                "sgs_sample_topq_multi: p == NULL (uniform weights) needs mode LEARNED and no prior");
+    SGS_REQUIRE(!sampled_edge_index || edge_index, SGS_EINVAL, "sgs_sample_topq_multi: edge_index required for sampled_edge_index");
+    SGS_REQUIRE(!st_weights || (p && sampled_eid && stats && mode == SGS_SAMPLE_LEARNED), SGS_EINVAL,
+                "sgs_sample_topq_multi: st_weights needs p, sampled_eid, stats and mode LEARNED");
+    SGS_REQUIRE(!dyn_edges_ptr(), SGS_EINVAL, "sgs_sample_topq_multi: not available under a dynamic edge count (sgs_dyn_edges_set)");
+    SGS_REQUIRE(ws && ws_bytes >= sgs_sample_topq_multi_workspace_bytes(E, D), SGS_EWORKSPACE,
+                "sgs_sample_topq_multi: workspace too small (%zu < %zu)", ws_bytes, sgs_sample_topq_multi_workspace_bytes(E, D));
+    SGS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, SGS_EINVAL, "sgs_sample_topq_multi: workspace must be 256-B aligned");
+
+    const int64_t nblk = cdiv(E, kChunk), cs = nblk + 1, ks = multi_key_stride(E);
+    Carver cv(ws);
+    uint32_t* keys = cv.take<uint32_t>(ks * D);
+    float* part = cv.take<float>(nblk + 1);
+    float* part2 = cv.take<float>(nblk + 1);
+    float* scal = cv.take<float>(4);                       // scal, hist and st adjacent: one zeroing launch on the large path
+    uint32_t* hist = cv.take<uint32_t>(3 * kBins * D);
+    SelectState* st = cv.take<SelectState>(D);
+    uint2* cnt = cv.take<uint2>(cs * D);
+    SelPart* sel = cv.take<SelPart>(2 * D);
+    const unsigned Du = static_cast<unsigned>(D);
+    const dim3 blk(kThreads);
+    const float one_minus_c = static_cast<float>(1.0 - degree_bias_coef);
+    const float c = static_cast<float>(degree_bias_coef);
+
+    if (nblk <= kSmallBlocks && q > 0 && q < E) {
+        const uint32_t q32 = static_cast<uint32_t>(q);
+        const dim3 grid(static_cast<unsigned>(nblk), Du);
+        if (int rc = zero_async(hist, static_cast<size_t>(3 * kBins * D) * 4, stream)) return rc;
+        const dim3 kgrid(static_cast<unsigned>(nblk), static_cast<unsigned>(cdiv(D, kMultiG))), kblk(kKeyThreads);
+        if (mode == SGS_SAMPLE_LEARNED) {
+            hipLaunchKernelGGL(small_reduce_first<0>, dim3(static_cast<unsigned>(nblk)), blk, 0, stream, p, E, part, hist, nullptr);
+            hipLaunchKernelGGL(multi_keys_hist0<SGS_SAMPLE_LEARNED>, kgrid, kblk, 0, stream, p, prior, noise, seed, stream_id0, epoch_ptr(), E,
+                               static_cast<int>(D), one_minus_c, c, part, static_cast<const float*>(nullptr), nblk, scal, keys, ks, hist);
+        } else {
+            hipLaunchKernelGGL(small_reduce_first<1>, dim3(static_cast<unsigned>(nblk)), blk, 0, stream, p, E, part, hist, nullptr);
+            hipLaunchKernelGGL(small_reduce_sumexp, dim3(static_cast<unsigned>(nblk)), blk, 0, stream, p, E, part, nblk, part2, nullptr);
+            hipLaunchKernelGGL(multi_keys_hist0<SGS_SAMPLE_PRIOR>, kgrid, kblk, 0, stream, p, static_cast<const float*>(nullptr), noise, seed,
+                               stream_id0, epoch_ptr(), E, static_cast<int>(D), one_minus_c, c, part2, part, nblk, scal, keys, ks, hist);
+        }
+        hipLaunchKernelGGL(multi_small_hist_next, grid, blk, 0, stream, keys, ks, E, kShift1, kMask1, kShift0, 1, q32, hist, sel);
+        hipLaunchKernelGGL(multi_small_hist_next, grid, blk, 0, stream, keys, ks, E, kShift2, kMask2, kShift1, 0, q32, hist, sel);
+        hipLaunchKernelGGL(multi_small_count, grid, blk, 0, stream, keys, ks, E, q32, hist, sel, st, cnt, cs, scal, stats);
+        hipLaunchKernelGGL(multi_small_compact, grid, blk, 0, stream, keys, ks, E, q, st, cnt, cs, p, edge_index, mask, sampled_eid,
+                           sampled_edge_index, static_cast<float*>(nullptr));
+    } else {
+        if (int rc = zero_async(scal, static_cast<size_t>(reinterpret_cast<char*>(st + D) - reinterpret_cast<char*>(scal)), stream)) return rc;
+        const dim3 grid1(static_cast<unsigned>(nblk));
+        if (mode == SGS_SAMPLE_LEARNED) {
+            hipLaunchKernelGGL(reduce_partial<0>, grid1, blk, 0, stream, p, E, scal, part);
+            hipLaunchKernelGGL(reduce_final<0>, dim3(1), blk, 0, stream, part, nblk, scal);
+        } else {
+            hipLaunchKernelGGL(reduce_partial<1>, grid1, blk, 0, stream, p, E, scal, part);
+            hipLaunchKernelGGL(reduce_final<1>, dim3(1), blk, 0, stream, part, nblk, scal);
+            hipLaunchKernelGGL(reduce_partial<2>, grid1, blk, 0, stream, p, E, scal, part);
+            hipLaunchKernelGGL(reduce_final<2>, dim3(1), blk, 0, stream, part, nblk, scal);
+        }
+        if (q == 0 || q == E) {
+            hipLaunchKernelGGL(multi_select_all, dim3(static_cast<unsigned>(cdiv(E, 256)), Du), dim3(256), 0, stream, E, p, edge_index, mask,
+                               sampled_eid, sampled_edge_index, static_cast<float*>(nullptr), static_cast<uint8_t>(q == E ? 1 : 0));
+        } else {
+            const dim3 hgrid(static_cast<unsigned>(nblk < kHistGrid ? nblk : kHistGrid), Du), grid(static_cast<unsigned>(nblk), Du), one(1, Du);
+            const uint32_t q32 = static_cast<uint32_t>(q);
+            if (mode == SGS_SAMPLE_LEARNED)
+                hipLaunchKernelGGL(multi_keys_hist0_large<SGS_SAMPLE_LEARNED>, hgrid, blk, 0, stream, p, prior, noise, seed, stream_id0, epoch_ptr(),
+                                   E, one_minus_c, c, scal, keys, ks, hist);
+            else
+                hipLaunchKernelGGL(multi_keys_hist0_large<SGS_SAMPLE_PRIOR>, hgrid, blk, 0, stream, p, static_cast<const float*>(nullptr), noise,
+                                   seed, stream_id0, epoch_ptr(), E, one_minus_c, c, scal, keys, ks, hist);
+            hipLaunchKernelGGL(multi_select_digit, one, blk, 0, stream, hist, kShift0, 1, q32, st);
+            hipLaunchKernelGGL(multi_hist_next, hgrid, blk, 0, stream, keys, ks, E, kShift1, kMask1, kShift0, st, hist);
+            hipLaunchKernelGGL(multi_select_digit, one, blk, 0, stream, hist, kShift1, 0, q32, st);
+            hipLaunchKernelGGL(multi_hist_next, hgrid, blk, 0, stream, keys, ks, E, kShift2, kMask2, kShift1, st, hist);
+            hipLaunchKernelGGL(multi_select_digit, one, blk, 0, stream, hist, kShift2, 0, q32, st);
+            hipLaunchKernelGGL(multi_count_blocks, grid, blk, 0, stream, keys, ks, E, st, cnt, cs);
+            hipLaunchKernelGGL(multi_scan_blocks, one, blk, 0, stream, cnt, cs, nblk);
+            hipLaunchKernelGGL(multi_compact, grid, blk, 0, stream, keys, ks, E, q, st, cnt, cs, p, edge_index, mask, sampled_eid,
+                               sampled_edge_index, static_cast<float*>(nullptr));
+        }
+        if (stats) hipLaunchKernelGGL(multi_write_stats, dim3(1, Du), dim3(1), 0, stream, scal, st, stats);
+    }
+    if (st_weights && q > 0) {
+        const dim3 g(static_cast<unsigned>(cdiv(q, 256)), Du);
+        if (prior)
+            hipLaunchKernelGGL(multi_st_fwd<true>, g, dim3(256), 0, stream, p, prior, one_minus_c, c, stats, sampled_eid, q, st_weights);
+        else
+            hipLaunchKernelGGL(multi_st_fwd<false>, g, dim3(256), 0, stream, p, prior, one_minus_c, c, stats, sampled_eid, q, st_weights);
     }
     SGS_LAUNCH_OK();
     return SGS_OK;

@@ -4,33 +4,46 @@ not change results: the scorer runs ONCE per batch instead of once per ensemble 
 no dropout, identical inputs => identical probabilities, evaluate.py:84), logits are averaged with a
 running sum, and the per-split correct counts stay on the device until the end of the loader.
 
-Test hook: `args._sgs_noise_eval = [noise_0, noise_1, ...]` feeds explicit Exp(1) noise per draw.
+Test hooks: `args._sgs_noise_eval = [noise_0, noise_1, ...]` feeds explicit Exp(1) noise per draw; `args._sgs_trace_eval = {}`
+receives the last partition's per-draw logits [D, N, C] ("logits"), averaged logits ("mean") and drawn edge lists ("edges").
+
+Batched engine (opt-in, `args.sgs_eval_batch`; True: draws per pass from a byte budget, an int k >= 1: at most k per pass): for
+GNNModel, all draws of a partition run as one pass of batched kernels (ops.ensemble_partition) instead of the serial loop below.  Draw d
+uses the same (seed, stream id) as the serial loop's d-th draw, so the drawn edge sets are identical.  Other heads keep the serial loop.
+`PATH_COUNTS` records which path each ensemble_evaluate call took.
 """
 from __future__ import annotations
 
 import torch
 
 from . import ops
-from .sampling import draw_learned, draw_prior, random_edge_sampling
+from .model import _DropoutClock
+from .sampling import _NoiseClock, draw_learned, draw_prior, random_edge_sampling
+
+PATH_COUNTS = {"serial": 0, "batched": 0}
+EVAL_BATCH_BUDGET = 512 << 20          # bytes of per-pass buffers when args.sgs_eval_batch is True
 
 
 def _one_draw(args, model, batch, q, mode, edge_probs, noise):
+    """-> (logits, the edge list the model ran on)."""
     if mode == 'learned':
         if batch.edge_index.shape[1] > q:
             smp = draw_learned(None, edge_probs, batch.edge_index, q, args.degree_bias_coef, istest=True, noise=noise)
             w = ops.st_weights(edge_probs, None, args.degree_bias_coef, smp.stats, smp.eid)     # sampling.py:137-155
-            return model(batch, smp.edge_index, w)
-        return model(batch, batch.edge_index)
+            return model(batch, smp.edge_index, w), smp.edge_index
+        return model(batch, batch.edge_index), batch.edge_index
     if mode == 'random':
         if batch.edge_index.shape[1] > q:
-            return model(batch, random_edge_sampling(batch.edge_index, q=q))
-        return model(batch, batch.edge_index)
+            ei = random_edge_sampling(batch.edge_index, q=q)
+            return model(batch, ei), ei
+        return model(batch, batch.edge_index), batch.edge_index
     if mode == 'edge':
         if batch.edge_index.shape[1] > q:
-            return model(batch, draw_prior(batch.prob, batch.edge_index, q, noise=noise).edge_index)
-        return model(batch, batch.edge_index)
+            ei = draw_prior(batch.prob, batch.edge_index, q, noise=noise).edge_index
+            return model(batch, ei), ei
+        return model(batch, batch.edge_index), batch.edge_index
     if mode == 'full':
-        return model(batch, batch.edge_index)
+        return model(batch, batch.edge_index), batch.edge_index
     raise ValueError("Invalid mode. Choose 'learned', 'random', or 'full'.")
 
 
@@ -38,6 +51,7 @@ def _run(args, model, cluster_loader, device, q, mode, n_draws):
     model.eval()
     counts = None
     noises = list(getattr(args, "_sgs_noise_eval", None) or [])
+    trace = getattr(args, "_sgs_trace_eval", None)
     with torch.no_grad():
         for batch in cluster_loader:
             batch = batch.to(device)
@@ -47,11 +61,17 @@ def _run(args, model, cluster_loader, device, q, mode, n_draws):
                 ops.get_pairs(batch.edge_index, batch.x.shape[0], build=True)     # once per partition (cached)
                 edge_probs = model.edge_prob_mlp(batch.x, batch.edge_index).squeeze()         # encoder over the FULL batch graph
             out = None
+            logs, edges = [], []
             for _ in range(n_draws):
-                o = _one_draw(args, model, batch, q, mode, edge_probs, noises.pop(0) if noises else None)
+                o, ei = _one_draw(args, model, batch, q, mode, edge_probs, noises.pop(0) if noises else None)
                 out = o if out is None else out + o
+                if trace is not None:
+                    logs.append(o)
+                    edges.append(ei)
             if n_draws > 1:
                 out = out / n_draws                                                           # torch.mean(torch.stack(outs))
+            if trace is not None:
+                trace["logits"], trace["mean"], trace["edges"] = torch.stack(logs), out, torch.stack(edges)
             c = torch.stack([ops.masked_correct(out, batch.y, m) for m in (batch.train_mask, batch.val_mask, batch.test_mask)])
             counts = c.to(torch.int64) if counts is None else counts + c
     if counts is None:
@@ -61,6 +81,103 @@ def _run(args, model, cluster_loader, device, q, mode, n_draws):
     return tuple((c[s][0] / c[s][1]) if c[s][1] > 0 else 0 for s in range(3))
 
 
+def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget) -> list:
+    """Draws per pass of the batched engine: a list of pass sizes summing to D, each >= 1.  `budget` is True (the largest pass whose
+    per-draw buffers fit EVAL_BATCH_BUDGET bytes), an int number of bytes via ("bytes", n), or an int k >= 1 (at most k draws per pass).
+    Per draw (an upper estimate of the engine's per-draw allocations): keys 4 E + mask E + filter positions 4 E; per drawn edge 40 B
+    (int64 id 8, int64 endpoints 16 -- allocated only under the trace hook, counted always --, weight 4, CSR source and id 8, normalised
+    weight 4); per-node arrays 36 N; hidden 4 N H; two logit blocks 8 N C.  The result of the engine does not depend on the split."""
+    D = int(D)
+    if D < 1:
+        raise ValueError(f"plan_draws: D={D} draws")
+    if budget is True or (isinstance(budget, tuple) and budget[0] == "bytes"):
+        nbytes = EVAL_BATCH_BUDGET if budget is True else int(budget[1])
+        ks = (int(E) + 63) & ~63
+        per = 4 * ks + int(E) + 4 * int(E) + 40 * int(q) + 36 * (int(N) + 1) + 4 * int(N) * int(H) + 8 * int(N) * int(C) + 3 * 2048 * 4 + 64
+        k = max(1, min(D, int(nbytes) // per))
+    else:
+        k = int(budget)
+        if k < 1:
+            raise ValueError(f"sgs_eval_batch={budget}: need True or an int >= 1")
+        k = min(k, D)
+    return [k] * (D // k) + ([D % k] if D % k else [])
+
+
+def _batched_ok(args, model, n_draws) -> bool:
+    """Whether this call takes the batched engine.  A falsy flag (False, None, 0) means off; anything else must be True or an
+    int >= 1, checked here, before any partition is read."""
+    flag = getattr(args, "sgs_eval_batch", False)
+    if not flag:
+        return False
+    if flag is not True and (isinstance(flag, bool) or not isinstance(flag, int) or flag < 1):
+        raise ValueError(f"args.sgs_eval_batch={flag!r}: need True (draws per pass from a byte budget) or an int >= 1 (at most k per pass)")
+    if n_draws < 1:
+        return False
+    from .model import GNNModel
+    return isinstance(model, GNNModel)
+
+
+def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
+    """The serial loop's result with every partition's draws in batched passes (ops.ensemble_partition: one host call per partition)."""
+    if mode not in ('learned', 'random', 'edge', 'full'):
+        raise ValueError("Invalid mode. Choose 'learned', 'random', or 'full'.")
+    flag = args.sgs_eval_batch
+    model.eval()
+    counts = None
+    noises = list(getattr(args, "_sgs_noise_eval", None) or [])
+    trace = getattr(args, "_sgs_trace_eval", None)
+    H, C = model.gcn1.out_channels, model.gcn2.out_channels
+    with torch.no_grad():
+        for batch in cluster_loader:
+            batch = batch.to(device)
+            ops.new_memo_scope()
+            if counts is None:
+                counts = torch.zeros(6, dtype=torch.int64, device=device)
+            E, N = batch.edge_index.shape[1], batch.x.shape[0]
+            given = [noises.pop(0) if noises else None for _ in range(n_draws)]     # the serial loop pops one per draw, whatever the mode
+            if mode == 'full' or E <= q:
+                out = model(batch, batch.edge_index)                                 # every draw runs on the whole partition
+                _DropoutClock.tick += n_draws - 1                                    # the serial loop's other n_draws - 1 forwards
+                acc = torch.empty_like(out)
+                ops.ensemble_mean_correct(out, 0, n_draws, acc, True, True, n_draws, batch.y,
+                                          (batch.train_mask, batch.val_mask, batch.test_mask), counts)
+                if trace is not None:
+                    trace["logits"], trace["mean"] = out.unsqueeze(0).expand(n_draws, *out.shape), acc
+                    trace["edges"] = batch.edge_index.unsqueeze(0).expand(n_draws, *batch.edge_index.shape)
+                continue
+            if mode == 'learned':
+                ops.get_pairs(batch.edge_index, N, build=True)
+                p = model.edge_prob_mlp(batch.x, batch.edge_index).squeeze().contiguous()
+                kind = ops.SAMPLE_LEARNED
+            elif mode == 'edge':
+                p, kind = batch.prob, ops.SAMPLE_PRIOR
+            else:
+                p, kind = None, ops.SAMPLE_LEARNED
+                given = [None] * n_draws                                             # random_edge_sampling takes no noise
+            passes, d = [], 0
+            for k in plan_draws(E, q, N, H, C, n_draws, flag):
+                while k > 0:                                                         # a pass never mixes explicit noise and clock draws
+                    explicit = given[d] is not None
+                    n = 1
+                    while n < k and (given[d + n] is not None) == explicit:
+                        n += 1
+                    if explicit:
+                        passes.append((n, torch.stack([t.to(device, torch.float32) for t in given[d:d + n]]).contiguous(), 0, 0))
+                    else:
+                        passes.append((n, None, _NoiseClock.seed, _NoiseClock.tick + 1))
+                        _NoiseClock.tick += n
+                    d += n
+                    k -= n
+            ops.ensemble_partition(batch, model.gcn1, model.gcn2, q, kind, p, passes, counts, trace)
+            # GNNModel.forward takes one dropout seed per call, in eval mode too: leave the dropout clock where the serial loop's
+            # n_draws forwards leave it, so that training after an evaluation draws the same masks whichever path evaluated
+            _DropoutClock.tick += n_draws
+    if counts is None:
+        return 0, 0, 0
+    c = counts.tolist()
+    return tuple((c[2 * s] / c[2 * s + 1]) if c[2 * s + 1] > 0 else 0 for s in range(3))
+
+
 def evaluate(args, model, cluster_loader, device, q=500, mode=None, temperature=1.0):
     """evaluate.py:6-67."""
     return _run(args, model, cluster_loader, device, q, mode, 1)
@@ -68,4 +185,9 @@ def evaluate(args, model, cluster_loader, device, q=500, mode=None, temperature=
 
 def ensemble_evaluate(args, model, cluster_loader, device, q=500, mode=None, temperature=1.0):
     """evaluate.py:70-173: mean of the logits of args.num_samples_eval independent draws."""
-    return _run(args, model, cluster_loader, device, q, mode, int(args.num_samples_eval))
+    n_draws = int(args.num_samples_eval)
+    if _batched_ok(args, model, n_draws):
+        PATH_COUNTS["batched"] += 1
+        return _run_batched(args, model, cluster_loader, device, q, mode, n_draws)
+    PATH_COUNTS["serial"] += 1
+    return _run(args, model, cluster_loader, device, q, mode, n_draws)

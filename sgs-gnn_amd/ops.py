@@ -1535,3 +1535,133 @@ def gcn_layer(x, W, bias, nm: Norm, act=ACT_NONE, p=0.0, seed=0, site=0, xl=None
     if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != nm.graph.N:
         raise RuntimeError("gcn_layer: x must be float32 [N, F]")
     return _GCNLayer.apply(x, W, nm.handle, bias, nm, act, float(p), int(seed), int(site), xl)
+
+
+# ------------------------------------------------------------------ batched ensemble evaluation (forward only, GCN head)
+class MultiSampleResult:
+    """D draws over one candidate set (sgs_sample_topq_multi): mask [D, E] bool, eid [D, q], edge_index [D, 2, q] or None,
+    stats [D, 4], w [D, q] (straight-through weights) or None.  Row d is what sample_topq returns for stream id stream_id0 + d."""
+    __slots__ = ("mask", "eid", "edge_index", "stats", "w", "D", "E", "q")
+
+
+def sample_topq_multi(mode: int, p, prior, c: float, q: int, edge_index, D: int, noise=None, seed: int = 0, stream_id0: int = 0,
+                      want_edge_index: bool = True, want_w: bool = False) -> MultiSampleResult:
+    """D exponential-race top-q draws in one pass.  p [E] f32 (None: uniform weights), prior [E] or None, noise [D, E] f32 or None
+    (then draw d uses (seed, stream_id0 + d)).  `want_w`: also the straight-through weights of each draw (mode LEARNED)."""
+    L = _lib.lib()
+    _need_gpu(p, prior, edge_index, noise)
+    if p is None and edge_index is None:
+        raise RuntimeError("sample_topq_multi: uniform weights (p=None) need edge_index for the number of candidates")
+    E = p.numel() if p is not None else edge_index.shape[1]
+    dev = p.device if p is not None else edge_index.device
+    D = int(D)
+    if noise is not None and (noise.dim() != 2 or tuple(noise.shape) != (D, E)):
+        raise RuntimeError(f"sample_topq_multi: noise must be [D={D}, E={E}]")
+    r = MultiSampleResult()
+    r.D, r.E, r.q = D, E, q
+    r.mask = torch.empty(max(D, 1), E, dtype=torch.bool, device=dev)
+    r.eid = torch.empty(max(D, 1), q, dtype=torch.int64, device=dev)
+    r.edge_index = torch.empty(max(D, 1), 2, q, dtype=torch.int64, device=dev) if (want_edge_index and edge_index is not None) else None
+    r.stats = torch.empty(max(D, 1), 4, dtype=torch.float32, device=dev)
+    r.w = torch.empty(max(D, 1), q, dtype=torch.float32, device=dev) if want_w else None
+    ws = workspace(L.sgs_sample_topq_multi_workspace_bytes(E, max(D, 1)), dev)
+    _lib.check(L.sgs_sample_topq_multi(mode, _ptr(p, torch.float32), _ptr(prior, torch.float32), float(c), _ptr(noise, torch.float32), seed,
+                                       stream_id0, D, E, q, _ptr(edge_index, torch.int64), _ptr(r.mask), _ptr(r.eid), _ptr(r.edge_index),
+                                       _ptr(r.stats), _ptr(r.w), ws.data_ptr(), ws.numel(), _stream()), "sgs_sample_topq_multi")
+    return r
+
+
+def graph_filter_multi(parent: Graph, smp: MultiSampleResult):
+    """In-CSRs of the D drawn subgraphs of `parent` (sgs_graph_filter_multi): (in_ptr [D, N+1], in_src [D, q], in_eid [D, q],
+    loop_eid [D, N]) int32; row d equals sgs_graph_filter's arrays for draw d."""
+    L = _lib.lib()
+    D, q, N = smp.D, smp.q, parent.N
+    dev = parent.edge_index.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    in_ptr = torch.empty(D, N + 1, **i32)
+    in_src = torch.empty(D, max(q, 1), **i32)
+    in_eid = torch.empty(D, max(q, 1), **i32)
+    loop = torch.empty(D, max(N, 1), **i32)
+    ws = workspace(L.sgs_graph_filter_multi_workspace_bytes(parent.n_edges, N, D), dev)
+    _lib.check(L.sgs_graph_filter_multi(_ptr(parent.in_ptr), _ptr(parent.in_src), _ptr(parent.in_eid), parent.n_edges, N, D, _ptr(_u8(smp.mask)),
+                                        _ptr(smp.eid), q, _ptr(in_ptr), _ptr(in_src), _ptr(in_eid), _ptr(loop), ws.data_ptr(), ws.numel(),
+                                        _stream()), "sgs_graph_filter_multi")
+    return in_ptr, in_src, in_eid, loop
+
+
+def gcn_norm_multi(csr, w, q: int, N: int):
+    """sgs_gcn_norm_fwd_multi over graph_filter_multi's CSRs: (dis, loopw, what_in [D, q], what_loop) for w [D, q] or None (unit)."""
+    L = _lib.lib()
+    in_ptr, in_src, in_eid, loop = csr
+    D = in_ptr.shape[0]
+    f32 = dict(dtype=torch.float32, device=in_ptr.device)
+    dis, loopw, what_loop = torch.empty(D, N, **f32), torch.empty(D, N, **f32), torch.empty(D, N, **f32)
+    what_in = torch.empty(D, max(q, 1), **f32)
+    _lib.check(L.sgs_gcn_norm_fwd_multi(_ptr(w, torch.float32), q, N, D, _ptr(in_ptr), _ptr(in_src), _ptr(in_eid), _ptr(loop), _ptr(dis),
+                                        _ptr(loopw), _ptr(what_in), _ptr(what_loop), _stream()), "sgs_gcn_norm_fwd_multi")
+    return dis, loopw, what_in, what_loop
+
+
+def _drawn_gcn_logits(parent: Graph, smp: MultiSampleResult, w, xl1, b1, W2, b2):
+    """Logits [D, N, C] of the two GCN layers over each of the D drawn subgraphs of `parent` (one launch per stage for all draws):
+    in-CSRs filtered out of the parent's, weighted (w [D, q]) or unit gcn_norm, layer 1 over the shared x W1^T, one library GEMM
+    [D N, H] x W2^T for layer 2."""
+    L = _lib.lib()
+    D, q, N = smp.D, smp.q, parent.N
+    f32 = dict(dtype=torch.float32, device=xl1.device)
+    csr = graph_filter_multi(parent, smp)
+    in_ptr, in_src = csr[0], csr[1]
+    _, _, what_in, what_loop = gcn_norm_multi(csr, w, q, N)
+    H = xl1.shape[1]
+    h = torch.empty(D, N, H, **f32)
+    _lib.check(L.sgs_spmm_csr_multi(_ptr(xl1, torch.float32), 0, N, H, q, D, _ptr(in_ptr), _ptr(in_src), _ptr(what_in), _ptr(what_loop), _ptr(b1),
+                                    ACT_RELU, _ptr(h), _stream()), "sgs_spmm_csr_multi")
+    z = (h.view(D * N, H) @ W2.t()).contiguous()
+    C = z.shape[1]
+    out = torch.empty(D, N, C, **f32)
+    _lib.check(L.sgs_spmm_csr_multi(_ptr(z), N * C, N, C, q, D, _ptr(in_ptr), _ptr(in_src), _ptr(what_in), _ptr(what_loop), _ptr(b2), ACT_NONE,
+                                    _ptr(out), _stream()), "sgs_spmm_csr_multi")
+    return out
+
+
+def ensemble_mean_correct(logits, x_stride: int, Dc: int, acc, first: bool, last: bool, D_total: int, y, masks, counts) -> None:
+    """sgs_ensemble_mean_correct: fold Dc logit blocks into the running sum `acc` [N, C]; on the last pass acc becomes the mean and the
+    three (correct, total) counts are added to `counts` (int64 [6])."""
+    L = _lib.lib()
+    N, C = acc.shape
+    m = [_u8(x) for x in masks]
+    _lib.check(L.sgs_ensemble_mean_correct(_ptr(logits, torch.float32), int(x_stride), int(Dc), N, C, _ptr(acc, torch.float32), int(first), int(last),
+                                           int(D_total), _ptr(y, torch.int64), _ptr(m[0]), _ptr(m[1]), _ptr(m[2]), _ptr(counts, torch.int64),
+                                           _stream()), "sgs_ensemble_mean_correct")
+
+
+def ensemble_partition(batch, gcn1, gcn2, q: int, mode: int, p, passes, counts, trace=None):
+    """All draws of ONE partition, batched: `passes` is a list of (Dc, noise [Dc, E] or None, seed, stream_id0), in draw order.
+    mode SAMPLE_LEARNED with p (the scorer's probabilities, istest: straight-through weights on the edges), SAMPLE_PRIOR with p = batch.prob
+    (unit weights), or SAMPLE_LEARNED with p None (uniform draw, unit weights).  Adds the partition's three (correct, total) counts to
+    `counts`.  `trace` (dict or None): receives per-draw logits [D, N, C], mean [N, C] and the drawn edge lists [D, 2, q]."""
+    x, ei = batch.x, batch.edge_index
+    N = x.shape[0]
+    feature_csr(x, build=True)
+    xl1 = _x_wt(x, gcn1.lin.weight).contiguous()
+    parent = get_graph(ei, N)
+    D_total = sum(int(ps[0]) for ps in passes)
+    acc = None
+    done = 0
+    logs, edges = [], []
+    for k, (Dc, noise, seed, sid0) in enumerate(passes):
+        weighted = mode == SAMPLE_LEARNED and p is not None
+        smp = sample_topq_multi(mode, p, None, 0.0, q, ei, Dc, noise=noise, seed=seed, stream_id0=sid0, want_edge_index=trace is not None,
+                                want_w=weighted)
+        out = _drawn_gcn_logits(parent, smp, smp.w if weighted else None, xl1, gcn1.bias, gcn2.lin.weight, gcn2.bias)
+        if acc is None:
+            acc = torch.empty(N, out.shape[2], dtype=torch.float32, device=x.device)
+        done += Dc
+        ensemble_mean_correct(out, N * out.shape[2], Dc, acc, k == 0, done == D_total, D_total, batch.y,
+                              (batch.train_mask, batch.val_mask, batch.test_mask), counts)
+        if trace is not None:
+            logs.append(out)
+            edges.append(smp.edge_index)
+    if trace is not None:
+        trace["logits"], trace["mean"], trace["edges"] = torch.cat(logs), acc, torch.cat(edges)
+    return acc
