@@ -306,6 +306,21 @@ int sgs_colsum(const float* A, int64_t N, int64_t D, float* out, void* ws, size_
 int sgs_act_bwd_colsum(const float* dY, const float* Y, int64_t N, int64_t D, int act, float p_drop, float* dZ, float* colsum, void* ws,
                        size_t ws_bytes, sgs_stream_t stream);
 
+/* GCN layer pairs at partition scale: one SpMM launch carries the neighbouring layer's row-local work.
+ * sgs_gcn_pair_ok(N, nnz, D): 1 iff sgs_spmm_csr takes its row-block path (N <= 65536, nnz >= 16 N) and 0 < D <= 512 (rows of width
+ *   D are kept in LDS); the two calls below accept exactly these shapes.
+ * sgs_spmm_csr_next: Y = sgs_spmm_csr(X, ...) bitwise, and Z = Y Wn^T in fp32 (Wn [Dn, D] row-major: the next layer's weight; Z [N, Dn]).
+ * sgs_spmm_csr_bwd_prev: dX = A_hat^T dZ bitwise as sgs_spmm_csr over the out-CSR (dZ, dX [N, D]);  colsum[d] = sum_i dZ[i, d]
+ *   (NULL: skipped; bitwise sgs_colsum for N <= 2048);  and with W != NULL (W [D, Dp] row-major: the weight that made this layer's
+ *   input) dZp = (dX W) * act'(Yp) [N, Dp] in fp32, act' as in sgs_act_bwd (Yp [N, Dp]: the previous layer's output). */
+int sgs_gcn_pair_ok(int64_t N, int64_t nnz, int64_t D);
+int sgs_spmm_csr_next(const float* X, int64_t N, int64_t D, int64_t nnz, const int32_t* ptr, const int32_t* col, const float* val,
+                      const float* diag, const float* bias, int act, float p_drop, uint64_t seed, uint32_t site, const float* Wn, int64_t Dn,
+                      float* Y, float* Z, sgs_stream_t stream);
+int sgs_spmm_csr_bwd_prev(const float* dZ, int64_t N, int64_t D, int64_t nnz, const int32_t* ptr, const int32_t* col, const float* val,
+                          const float* diag, const float* W, int64_t Dp, const float* Yp, int act, float p_drop, float* dX, float* dZp,
+                          float* colsum, sgs_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * K1b: fused edge scorer (model.py:29-34 / 115-122 `_edge_score`; never materialises the
  * reference's [E,2H] feature or [E,H] hidden tensors):

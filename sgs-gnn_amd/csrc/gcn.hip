@@ -946,11 +946,11 @@ __global__ void __launch_bounds__(RG * 64) colsum_final(const float* __restrict_
 // written and summed in the same pass (a layer's backward then holds one launch where it held act_bwd + the two colsum stages).
 constexpr int kColSmallRows = 2048;
 template <bool ACT>
-__global__ void __launch_bounds__(1024) colsum_small(const float* __restrict__ A, const float* __restrict__ Y, int64_t N, int64_t D, int act,
-                                                    float drop_scale, float* __restrict__ dZ, float* __restrict__ out) {
+__device__ __forceinline__ void colsum_small_body(const float* __restrict__ A, const float* __restrict__ Y, int64_t N, int64_t D, int act,
+                                                  float drop_scale, float* __restrict__ dZ, float* __restrict__ out, int64_t blk) {
     __shared__ float red[64][17];
     const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
-    const int64_t c = static_cast<int64_t>(blockIdx.x) * 16 + cl;
+    const int64_t c = blk * 16 + cl;
     float acc = 0.f;
     if (c < D) {
 #pragma unroll 16
@@ -972,15 +972,20 @@ __global__ void __launch_bounds__(1024) colsum_small(const float* __restrict__ A
     }
     if (rl == 0 && c < D && out) out[c] = red[0][cl];
 }
+template <bool ACT>
+__global__ void __launch_bounds__(1024) colsum_small(const float* __restrict__ A, const float* __restrict__ Y, int64_t N, int64_t D, int act,
+                                                    float drop_scale, float* __restrict__ dZ, float* __restrict__ out) {
+    colsum_small_body<ACT>(A, Y, N, D, act, drop_scale, dZ, out, blockIdx.x);
+}
 
 // D % 4 == 0: the same pass on 16-byte words -- a thread owns four columns and N/256 rows, so every load of a thread is in flight at
 // once and the 16-column row segments stay whole 64-byte reads.
 template <bool ACT>
-__global__ void __launch_bounds__(1024) colsum_small_v4(const float* __restrict__ A, const float* __restrict__ Y, int64_t N, int64_t D, int act,
-                                                       float drop_scale, float* __restrict__ dZ, float* __restrict__ out) {
+__device__ __forceinline__ void colsum_small_v4_body(const float* __restrict__ A, const float* __restrict__ Y, int64_t N, int64_t D, int act,
+                                                     float drop_scale, float* __restrict__ dZ, float* __restrict__ out, int64_t blk) {
     __shared__ float4 red[256][4];
     const int cg = threadIdx.x & 3, rl = threadIdx.x >> 2;
-    const int64_t c = static_cast<int64_t>(blockIdx.x) * 16 + 4 * cg;
+    const int64_t c = blk * 16 + 4 * cg;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     if (c < D) {
 #pragma unroll 8
@@ -1011,6 +1016,11 @@ __global__ void __launch_bounds__(1024) colsum_small_v4(const float* __restrict_
         __syncthreads();
     }
     if (rl == 0 && c < D && out) *reinterpret_cast<float4*>(out + c) = red[0][cg];
+}
+template <bool ACT>
+__global__ void __launch_bounds__(1024) colsum_small_v4(const float* __restrict__ A, const float* __restrict__ Y, int64_t N, int64_t D, int act,
+                                                       float drop_scale, float* __restrict__ dZ, float* __restrict__ out) {
+    colsum_small_v4_body<ACT>(A, Y, N, D, act, drop_scale, dZ, out, blockIdx.x);
 }
 
 // A vector's sum (D = 1, e.g. d fc2.bias = sum of dz over the q active edges) in one workgroup: the two-stage kernels above would spend
@@ -1079,6 +1089,176 @@ __global__ void __launch_bounds__(64 * NW) multi_spmm_csr_rowblock(const float* 
     const int64_t d = blockIdx.y;
     spmm_csr_rowblock_body<VEC, NW>(X + d * xs, N, D, ptr + d * (N + 1), col + d * nnz, val + d * nnz, diag ? diag + d * N : nullptr, bias, act,
                                     1.0f, 0u, uint64_t(0), 0u, nullptr, Y + d * N * D);
+}
+
+// GCN layer pairs (partition scale, the row-block path): the SpMM of one layer with the neighbouring layer's row-local work in its
+// epilogue, so the dense product / activation backward / bias sums between two SpMMs lose their launches.  A workgroup is 16 waves:
+// RG = 16 / NW rows side by side, each gathered by NW waves exactly as spmm_csr_rowblock_body does (same entry order, same fixed-order
+// combination of the wave partials, same dropout hash), so Y is bitwise sgs_spmm_csr's.  The RG finished rows stay in LDS for:
+//   kPairFwd:  Z[i, o] = sum_d Y[i, d] Wn[o, d]   (Wn [Dn, D], the next layer's weight): a thread per (row, o).
+//   kPairBwd:  dZp[i, e] = act'(Yp[i, e]) * sum_c Y[i, c] Wn[c, e]   (Wn [D, Dn], Yp [N, Dn]: the previous layer's product and activation
+//              backward, act' as colsum_small<true>): a thread per (row, e).
+//   Both products are fp32 fma chains in lib_gemm_dot's order, the order in which the library GEMMs they replace (hipBLASLt's fp32
+//   kernels for these shapes: v_mfma_f32_16x16x4_f32, which accumulates its four products in turn) sum: Z and dZp are bitwise the
+//   GEMMs' results, so a training run with the pairs is bitwise the run without them.  (Checked by tests/test_gpu_gcn_fused.py.)
+//   kPairCol:  neither.
+// kPairBwd / kPairCol also sum the columns of X (the bias gradient of the layer whose dZ X is): the first ncs workgroups run
+// colsum_small(_v4)<false>'s pass over X -- bitwise sgs_colsum at N <= kColSmallRows -- and the row groups follow.
+enum { kPairCol = 0, kPairFwd = 1, kPairBwd = 2 };
+constexpr int kPairMaxD = 512;      // widest Y row kept in LDS
+constexpr int kPairWlds = 12288;    // kPairFwd: Wn (transposed) is staged in LDS when Dn * D fits (48 KiB; the GNN head's W2: 41 x 256)
+constexpr int kPairWpre = kPairWlds / 1024;
+// Position t of the library's summation over k = 0..K-1: 16-deep steps of two 8-element halves, each half its even k, then its odd k
+// (two k per lane per LDS read feed two MFMAs); the K % 16 tail in plain order.
+// lib_gemm_dot: sum_k y(k) w(k) as one fp32 fma chain in that order; the operands of the next 8-element half are loaded while the
+// current half's fmas run (the chain itself is the latency: a thread per output, the order fixes it).
+template <class FY, class FW>
+__device__ __forceinline__ float lib_gemm_dot(int K, FY y, FW w) {
+    const int Kmain = K / 16 * 16;
+    float z = 0.f;
+    if (Kmain > 0) {
+        float ya[8], wa[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { const int k = 2 * (u & 3) + (u >> 2); ya[u] = y(k); wa[u] = w(k); }
+        for (int b = 0; b < Kmain; b += 8) {
+            const int nb = b + 8 < Kmain ? b + 8 : b;
+            float yn[8], wn[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { const int k = nb + 2 * (u & 3) + (u >> 2); yn[u] = y(k); wn[u] = w(k); }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) z = fmaf(ya[u], wa[u], z);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { ya[u] = yn[u]; wa[u] = wn[u]; }
+        }
+    }
+    for (int k = Kmain; k < K; ++k) z = fmaf(y(k), w(k), z);
+    return z;
+}
+template <int VEC, int NW, int MODE>
+__global__ void __launch_bounds__(1024) spmm_rowgroup_pair(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
+                                                           const int* __restrict__ col, const float* __restrict__ val,
+                                                           const float* __restrict__ diag, const float* __restrict__ bias, int act,
+                                                           float drop_scale, uint32_t drop_thresh, uint64_t seed, uint32_t site,
+                                                           const uint64_t* __restrict__ epoch, float* __restrict__ Y,
+                                                           const float* __restrict__ Wn, int64_t Dn, const float* __restrict__ Yp,
+                                                           float* __restrict__ Zn, int ncs, float* __restrict__ colsum) {
+    using V = typename VecT<VEC>::type;
+    constexpr int RG = 16 / NW;
+    __shared__ float part[RG][NW][64 * VEC];
+    __shared__ __align__(16) float ys[RG * kPairMaxD];
+    __shared__ float wl[MODE == kPairFwd ? kPairWlds : 1];
+    if (MODE != kPairFwd && static_cast<int>(blockIdx.x) < ncs) {
+        if (D % 4 == 0) colsum_small_v4_body<false>(X, nullptr, N, D, SGS_ACT_NONE, 1.f, nullptr, colsum, blockIdx.x);
+        else            colsum_small_body<false>(X, nullptr, N, D, SGS_ACT_NONE, 1.f, nullptr, colsum, blockIdx.x);
+        return;
+    }
+    seed = fold_epoch(seed, epoch);
+    const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) % NW, grp = threadIdx.x / (64 * NW);
+    const int64_t row0 = static_cast<int64_t>(blockIdx.x - ncs) * RG;
+    const int64_t i = row0 + grp;
+    const bool live = i < N;
+    int b = 0, e = 0;
+    float dg = 0.f;
+    uint32_t rkey = 0;
+    const int yact = MODE == kPairBwd ? SGS_ACT_NONE : act;     // kPairBwd: act / drop_scale are the previous layer's
+    if (live) {
+        b = ptr[i];
+        e = ptr[i + 1];
+        dg = diag ? diag[i] : 0.f;
+        rkey = dropout_row_key(seed, site, static_cast<uint64_t>(i));
+    }
+    // kPairFwd with Wn staged: its elements are loaded now (coalesced, kPairWpre per thread) and written to LDS after the gathers, so
+    // their latency hides behind the rows'
+    const bool wlds = MODE == kPairFwd && Dn * D <= kPairWlds;
+    float wpre[MODE == kPairFwd ? kPairWpre : 1];
+    if (MODE == kPairFwd && wlds) {
+#pragma unroll
+        for (int u = 0; u < kPairWpre; ++u) {
+            const int64_t idx = threadIdx.x + 1024 * u;
+            wpre[u] = idx < Dn * D ? Wn[idx] : 0.f;
+        }
+    }
+    // ---- spmm_csr_rowblock_body, one row per group of NW waves
+    for (int64_t cbase = 0; cbase < D; cbase += 64 * VEC) {
+        const int64_t c0 = cbase + static_cast<int64_t>(lane) * VEC;
+        const bool in = c0 < D;
+        float acc[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+        if (in) {
+            int k = b + wave;
+            for (; k + 7 * NW < e; k += 8 * NW) {
+                int j[8]; float w[8]; V x[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { j[u] = col[k + NW * u]; w[u] = val[k + NW * u]; }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) x[u] = *reinterpret_cast<const V*>(X + static_cast<int64_t>(j[u]) * D + c0);
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    float xv[VEC];
+                    *reinterpret_cast<V*>(xv) = x[u];
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], xv[v], acc[v]);
+                }
+            }
+            for (; k < e; k += NW) {
+                float xv[VEC];
+                *reinterpret_cast<V*>(xv) = *reinterpret_cast<const V*>(X + static_cast<int64_t>(col[k]) * D + c0);
+                const float w = val[k];
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, xv[v], acc[v]);
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) part[grp][wave][lane * VEC + v] = acc[v];
+        __syncthreads();
+        const int t = threadIdx.x % (64 * NW);
+        if (live && t < 64 * VEC && cbase + t < D) {
+            const int64_t c = cbase + t;
+            float y = 0.f;
+#pragma unroll
+            for (int g = 0; g < NW; g += 4) y += (part[grp][g][t] + part[grp][g + 1][t]) + (part[grp][g + 2][t] + part[grp][g + 3][t]);
+            if (diag) y = fmaf(dg, X[i * D + c], y);
+            if (bias) y += bias[c];
+            if (yact != SGS_ACT_NONE) y = fmaxf(y, 0.f);
+            if (yact == SGS_ACT_RELU_DROPOUT) y = dropout_keep_col(rkey, static_cast<uint32_t>(c), drop_thresh) ? y * drop_scale : 0.f;
+            Y[i * D + c] = y;
+            ys[grp * D + c] = y;
+        }
+        __syncthreads();
+    }
+    if (MODE == kPairFwd) {
+        if (wlds) {
+#pragma unroll
+            for (int u = 0; u < kPairWpre; ++u) {
+                const int64_t idx = threadIdx.x + 1024 * u;
+                if (idx < Dn * D) {
+                    const int64_t o = idx / D, k = idx - o * D;
+                    wl[k * Dn + o] = wpre[u];           // [k][o]: the lanes of a wave read consecutive o
+                }
+            }
+            __syncthreads();
+        }
+        for (int64_t idx = threadIdx.x; idx < RG * Dn; idx += 1024) {
+            const int r = static_cast<int>(idx / Dn);
+            const int64_t o = idx - r * Dn, ir = row0 + r;
+            if (ir >= N) break;
+            const float* yr = ys + r * D;
+            const auto yk = [&](int k) { return yr[k]; };
+            Zn[ir * Dn + o] = wlds ? lib_gemm_dot(static_cast<int>(D), yk, [&](int k) { return wl[k * Dn + o]; })
+                                   : lib_gemm_dot(static_cast<int>(D), yk, [&](int k) { return Wn[o * D + k]; });
+        }
+    } else if (MODE == kPairBwd) {
+        for (int64_t idx = threadIdx.x; idx < RG * Dn; idx += 1024) {
+            const int r = static_cast<int>(idx / Dn);
+            const int64_t ep = idx - r * Dn, ir = row0 + r;
+            if (ir >= N) break;
+            const float* yr = ys + r * D;
+            float a = lib_gemm_dot(static_cast<int>(D), [&](int c) { return yr[c]; }, [&](int c) { return Wn[c * Dn + ep]; });
+            if (act != SGS_ACT_NONE) a = (Yp[ir * Dn + ep] > 0.f) ? (act == SGS_ACT_RELU_DROPOUT ? a * drop_scale : a) : 0.f;
+            Zn[ir * Dn + ep] = a;
+        }
+    }
 }
 
 inline int pick_lpr(int64_t D, int vec) {
@@ -1550,6 +1730,66 @@ int sgs_act_bwd_colsum(const float* dY, const float* Y, int64_t N, int64_t D, in
     if (int rc = sgs_act_bwd(dY, Y, N * D, act, p_drop, dZ, stream_)) return rc;
     return sgs_colsum(dZ, N, D, colsum, ws, ws_bytes, stream_);
 }
+
+// ---- GCN layer pairs (spmm_rowgroup_pair): only where sgs_spmm_csr takes its row-block path
+int sgs_gcn_pair_ok(int64_t N, int64_t nnz, int64_t D) {
+    return (N > 0 && N <= 65536 && nnz >= 16 * N && D > 0 && D <= kPairMaxD) ? 1 : 0;
+}
+
+#define PAIR_LAUNCH(MODE, grid, ...)                                                                                              \
+    do {                                                                                                                          \
+        if (vec == 4 && wide)  hipLaunchKernelGGL((spmm_rowgroup_pair<4, 16, MODE>), dim3(grid), dim3(1024), 0, stream, __VA_ARGS__); \
+        else if (vec == 4)     hipLaunchKernelGGL((spmm_rowgroup_pair<4, 4, MODE>), dim3(grid), dim3(1024), 0, stream, __VA_ARGS__);  \
+        else if (wide)         hipLaunchKernelGGL((spmm_rowgroup_pair<1, 16, MODE>), dim3(grid), dim3(1024), 0, stream, __VA_ARGS__); \
+        else                   hipLaunchKernelGGL((spmm_rowgroup_pair<1, 4, MODE>), dim3(grid), dim3(1024), 0, stream, __VA_ARGS__);  \
+    } while (0)
+
+int sgs_spmm_csr_next(const float* X, int64_t N, int64_t D, int64_t nnz, const int32_t* ptr, const int32_t* col, const float* val,
+                      const float* diag, const float* bias, int act, float p_drop, uint64_t seed, uint32_t site, const float* Wn, int64_t Dn,
+                      float* Y, float* Z, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(sgs_gcn_pair_ok(N, nnz, D) && Dn > 0, SGS_EINVAL, "sgs_spmm_csr_next: not a row-block shape (see sgs_gcn_pair_ok)");
+    SGS_REQUIRE(act >= SGS_ACT_NONE && act <= SGS_ACT_RELU_DROPOUT && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL,
+                "sgs_spmm_csr_next: bad activation / dropout");
+    SGS_REQUIRE(X && ptr && Y && Wn && Z && X != Y && Z != Y && Z != X, SGS_EINVAL, "sgs_spmm_csr_next: null or aliased pointer");
+    const int vec = (D % 4 == 0 && aligned16(X) && aligned16(Y)) ? 4 : 1;      // (as sgs_spmm_csr: Y is bitwise its result)
+    const bool wide = nnz >= 256 * N;
+    const float scale = 1.0f / (1.0f - p_drop);
+    const uint32_t th = dropout_thresh(p_drop);
+    if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
+    const int64_t grid = cdiv(N, wide ? 1 : 4);
+    PAIR_LAUNCH(kPairFwd, grid, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed, site, epoch_ptr(), Y, Wn, Dn,
+                static_cast<const float*>(nullptr), Z, 0, static_cast<float*>(nullptr));
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_spmm_csr_bwd_prev(const float* dZ, int64_t N, int64_t D, int64_t nnz, const int32_t* ptr, const int32_t* col, const float* val,
+                          const float* diag, const float* W, int64_t Dp, const float* Yp, int act, float p_drop, float* dX, float* dZp,
+                          float* colsum, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(sgs_gcn_pair_ok(N, nnz, D), SGS_EINVAL, "sgs_spmm_csr_bwd_prev: not a row-block shape (see sgs_gcn_pair_ok)");
+    SGS_REQUIRE(act >= SGS_ACT_NONE && act <= SGS_ACT_RELU_DROPOUT && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL,
+                "sgs_spmm_csr_bwd_prev: bad activation / dropout");
+    SGS_REQUIRE(dZ && ptr && dX && dZ != dX, SGS_EINVAL, "sgs_spmm_csr_bwd_prev: null or aliased pointer");
+    SGS_REQUIRE(!W || (Dp > 0 && dZp && (act == SGS_ACT_NONE || Yp) && dZp != dX && dZp != dZ), SGS_EINVAL,
+                "sgs_spmm_csr_bwd_prev: W needs Dp > 0, dZp and (with an activation) Yp");
+    const int vec = (D % 4 == 0 && aligned16(dZ) && aligned16(dX)) ? 4 : 1;
+    const bool wide = nnz >= 256 * N;
+    const int ncs = colsum ? static_cast<int>(cdiv(D, 16)) : 0;
+    const int64_t grid = ncs + cdiv(N, wide ? 1 : 4);
+    const float scale = 1.0f / (1.0f - p_drop);
+    if (W)
+        PAIR_LAUNCH(kPairBwd, grid, dZ, N, D, ptr, col, val, diag, static_cast<const float*>(nullptr), act, scale, 0u, uint64_t(0), 0u,
+                    static_cast<const uint64_t*>(nullptr), dX, W, Dp, Yp, dZp, ncs, colsum);
+    else
+        PAIR_LAUNCH(kPairCol, grid, dZ, N, D, ptr, col, val, diag, static_cast<const float*>(nullptr), SGS_ACT_NONE, 1.f, 0u, uint64_t(0), 0u,
+                    static_cast<const uint64_t*>(nullptr), dX, static_cast<const float*>(nullptr), int64_t(0), static_cast<const float*>(nullptr),
+                    static_cast<float*>(nullptr), ncs, colsum);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+#undef PAIR_LAUNCH
 
 }  // extern "C"
 

@@ -73,12 +73,15 @@ class GCNConv(nn.Module):
             norm = ops.gcn_norm(ops.get_graph(edge_index, x.shape[0]), edge_weight)
         xl, key = self._memo(x)
         y, xl = ops.gcn_layer(x, self.lin.weight, self.bias, norm, act=act, p=p, seed=seed, site=site, xl=xl)
+        self._remember(key, x, xl)
+        return y
+
+    def _remember(self, key, x, xl):
         try:
             import weakref
             self._lin_cache = (key, weakref.ref(x), xl)
         except TypeError:
             self._lin_cache = None
-        return y
 
 
 class GNNModel(nn.Module):
@@ -100,8 +103,12 @@ class GNNModel(nn.Module):
             norm = ops.gcn_norm(ops.get_graph(edge_index, x.shape[0]), edge_weight)   # once for both layers
             p = self.dropout.p if self.training else 0.0
             act = ops.ACT_RELU_DROPOUT if p > 0 else ops.ACT_RELU
-            h = self.gcn1(x, edge_index, norm=norm, act=act, p=p, seed=_DropoutClock.next_seed(), site=SITE_GNN)
-            return self.gcn2(h, edge_index, norm=norm)
+            # both layers in one autograd node (ops.gcn2): at partition scale the SpMMs carry h W2^T and the backward's dense work
+            xl1, key = self.gcn1._memo(x)
+            out, xl1 = ops.gcn2(x, self.gcn1.lin.weight, self.gcn1.bias, self.gcn2.lin.weight, self.gcn2.bias, norm, act=act, p=p,
+                                seed=_DropoutClock.next_seed(), site=SITE_GNN, xl1=xl1)
+            self.gcn1._remember(key, x, xl1)
+            return out
 
 
 # ------------------------------------------------------------------ GAT head (model.py:189-208)

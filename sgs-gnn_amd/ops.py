@@ -1537,6 +1537,121 @@ def gcn_layer(x, W, bias, nm: Norm, act=ACT_NONE, p=0.0, seed=0, site=0, xl=None
     return _GCNLayer.apply(x, W, nm.handle, bias, nm, act, float(p), int(seed), int(site), xl)
 
 
+# ------------------------------------------------------------------ two GCN layers as ONE autograd node (the GNN head)
+def _pair_ok(gr, *widths):
+    """sgs_gcn_pair_ok for every LDS-kept row width: the fused pair kernels apply (partition scale: sgs_spmm_csr's row-block path)."""
+    L = _lib.lib()
+    return all(L.sgs_gcn_pair_ok(gr.N, gr.n_edges, int(w)) for w in widths)
+
+
+class _GCN2(torch.autograd.Function):
+    """out = A_hat (h W2^T) + b2 with h = act(A_hat (x W1^T) + b1).  On the row-block path the first SpMM also emits h W2^T
+    (sgs_spmm_csr_next) and the backward's second-layer SpMM also emits dZ1 = (dxl2 W2) * act'(h) and d b2 (sgs_spmm_csr_bwd_prev),
+    the first-layer one d b1: the library GEMMs and column sums between the SpMMs lose their launches.  Elsewhere the two layers are
+    exactly _GCNLayer's calls.  `xl1` may be supplied (memoised x W1^T shared by the learned and the random forward of one step)."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2, handle, nm, act, p, seed, site, xl1):
+        L = _lib.lib()
+        gr = nm.graph
+        if xl1 is None:
+            xl1 = _x_wt(x, W1)
+        N, H = xl1.shape
+        C = W2.shape[0]
+        fused = _pair_ok(gr, H, C) and xl1.is_contiguous() and W2.is_contiguous() and W2.shape[1] == H
+        if fused:
+            h = torch.empty(N, H, dtype=torch.float32, device=xl1.device)
+            xl2 = torch.empty(N, C, dtype=torch.float32, device=xl1.device)
+            _lib.check(L.sgs_spmm_csr_next(_ptr(xl1, torch.float32), N, H, gr.n_edges, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(nm.what_in),
+                                           _ptr(nm.what_loop), _ptr(b1), act, float(p), seed, site, _ptr(W2, torch.float32), C, _ptr(h),
+                                           _ptr(xl2), _stream()), "sgs_spmm_csr_next")
+        else:
+            h = _spmm(xl1, gr.in_ptr, gr.in_src, nm.what_in, nm.what_loop, b1, act, p, seed, site, N, H, gr.n_edges)
+            xl2 = h @ W2.t()
+        out = _spmm(xl2, gr.in_ptr, gr.in_src, nm.what_in, nm.what_loop, b2, ACT_NONE, 0.0, 0, 0, N, C, gr.n_edges)
+        ctx.nm, ctx.act, ctx.p, ctx.fused = nm, act, p, fused
+        ctx.has_b1, ctx.has_b2, ctx.has_handle = b1 is not None, b2 is not None, handle is not None
+        ctx.save_for_backward(x, W1, xl1, h, W2, xl2)
+        ctx.mark_non_differentiable(xl1)
+        ctx.set_materialize_grads(False)
+        return out, xl1
+
+    @staticmethod
+    def backward(ctx, dout, _dxl_unused):
+        L = _lib.lib()
+        nm, gr = ctx.nm, ctx.nm.graph
+        x, W1, xl1, h, W2, xl2 = ctx.saved_tensors
+        N, H = h.shape
+        C = W2.shape[0]
+        need_x, need_W1, need_b1, need_W2, need_b2, need_g = (ctx.needs_input_grad[i] for i in range(6))
+        need_b1, need_b2, need_g = need_b1 and ctx.has_b1, need_b2 and ctx.has_b2, need_g and ctx.has_handle
+        dx = dW1 = db1 = dW2 = db2 = g = None
+        dZ2 = dout.contiguous()
+        f32 = dict(dtype=torch.float32, device=dZ2.device)
+
+        def sddmm(dZ, xl, D):
+            gg = torch.empty(gr.n_edges + gr.N, **f32)
+            _lib.check(L.sgs_sddmm_csr(_ptr(dZ), _ptr(xl), N, D, gr.n_edges, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid),
+                                       gg[:gr.n_edges].data_ptr(), gg[gr.n_edges:].data_ptr(), _stream()), "sgs_sddmm_csr")
+            return gg
+
+        # ---- layer 2 (no activation): dxl2 = A_hat^T dZ2, dZ1 = (dxl2 W2) * act'(h), d b2 = colsum(dZ2)
+        want_1 = need_x or need_W1 or need_b1 or need_g
+        dxl2 = dZ1 = None
+        if want_1 or need_W2:
+            dxl2 = torch.empty(N, C, **f32)
+            if ctx.fused:
+                dZ1 = torch.empty(N, H, **f32) if want_1 else None
+                db2 = torch.empty(C, **f32) if need_b2 else None
+                _lib.check(L.sgs_spmm_csr_bwd_prev(_ptr(dZ2), N, C, gr.n_edges, _ptr(gr.out_ptr), _ptr(gr.out_dst), _ptr(nm.what_out),
+                                                   _ptr(nm.what_loop), _ptr(W2 if want_1 else None, torch.float32), H, _ptr(h), ctx.act,
+                                                   float(ctx.p), _ptr(dxl2), _ptr(dZ1), _ptr(db2), _stream()), "sgs_spmm_csr_bwd_prev")
+            else:
+                dxl2 = _spmm(dZ2, gr.out_ptr, gr.out_dst, nm.what_out, nm.what_loop, None, ACT_NONE, 0.0, 0, 0, N, C, gr.n_edges)
+        if need_W2:
+            dW2 = _dyt_x(dxl2, h, W2.shape)
+        if want_1 and not ctx.fused:
+            dZ1h = dxl2 @ W2
+            if need_b1:
+                dZ1, db1 = _act_bwd_colsum(dZ1h, h, ctx.act, ctx.p)
+            else:
+                dZ1 = torch.empty_like(dZ1h)
+                _lib.check(L.sgs_act_bwd(_ptr(dZ1h), _ptr(h), dZ1h.numel(), ctx.act, float(ctx.p), _ptr(dZ1), _stream()), "sgs_act_bwd")
+        g2 = sddmm(dZ2, xl2, C) if need_g else None
+        if need_b2 and db2 is None:
+            db2 = _colsum(dZ2)
+        # ---- layer 1: dxl1 = A_hat^T dZ1 (+ d b1 = colsum(dZ1) in the same launch when fused)
+        if need_x or need_W1 or (need_b1 and db1 is None and ctx.fused):
+            if ctx.fused:
+                dxl1 = torch.empty(N, H, **f32)
+                db1 = torch.empty(H, **f32) if need_b1 else None
+                _lib.check(L.sgs_spmm_csr_bwd_prev(_ptr(dZ1), N, H, gr.n_edges, _ptr(gr.out_ptr), _ptr(gr.out_dst), _ptr(nm.what_out),
+                                                   _ptr(nm.what_loop), None, 0, None, ACT_NONE, 0.0, _ptr(dxl1), None, _ptr(db1), _stream()),
+                           "sgs_spmm_csr_bwd_prev")
+            else:
+                dxl1 = _spmm(dZ1, gr.out_ptr, gr.out_dst, nm.what_out, nm.what_loop, None, ACT_NONE, 0.0, 0, 0, N, H, gr.n_edges)
+            if need_W1:
+                dW1 = _dyt_x(dxl1, x, W1.shape)
+            if need_x:
+                dx = dxl1 @ W1
+        g1 = sddmm(dZ1, xl1, H) if need_g else None
+        if need_b1 and db1 is None:
+            db1 = _colsum(dZ1)
+        if need_g:          # the two layers' gradients wrt the shared normalisation, in _handle_grad's contract (layer 2 reports first)
+            r2, r1 = _handle_grad(nm, g2), _handle_grad(nm, g1)
+            g = r2 if r1 is None else (r1 if r2 is None else r2 + r1)
+        return dx, dW1, db1, dW2, db2, g, None, None, None, None, None, None
+
+
+def gcn2(x, W1, b1, W2, b2, nm: Norm, act=ACT_RELU, p=0.0, seed=0, site=0, xl1=None):
+    """Two GCN layers, A_hat (act(A_hat (x W1^T) + b1) W2^T) + b2, with autograd to x, W1, b1, W2, b2 and (through nm.handle) the
+    edge weights.  Returns (out, xl1) where xl1 = x W1^T (detached) can be passed back in for another graph over the same x, W1."""
+    _need_gpu(x, W1, b1, W2, b2)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != nm.graph.N:
+        raise RuntimeError("gcn2: x must be float32 [N, F]")
+    return _GCN2.apply(x, W1, b1, W2, b2, nm.handle, nm, act, float(p), int(seed), int(site), xl1)
+
+
 # ------------------------------------------------------------------ batched ensemble evaluation (forward only, GCN head)
 class MultiSampleResult:
     """D draws over one candidate set (sgs_sample_topq_multi): mask [D, E] bool, eid [D, q], edge_index [D, 2, q] or None,
