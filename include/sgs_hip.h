@@ -508,6 +508,46 @@ int sgs_gemm_tn_mask(const uint32_t* Abits, const float* dz, const float* rowsca
                      float* C, int64_t ldc, float* colsum_A, float* dz_sum, float* C_raw, float* colsum_raw, void* ws, size_t ws_bytes,
                      sgs_stream_t stream);
 
+/* ---- bf16 mode of the scorer's matrix-core contractions (opt-in; the entries above are the fp32-faithful default and the parity mode).
+ * Each entry below has the arguments and outputs of the entry it is named after.  Where that entry issues several bf16 MFMA products per
+ * fp32 product over exact operand splits v = v1 + v2 + v3 (v1 = RNE_bf16(v)), these issue ONLY v1 x v1, accumulated in fp32:
+ *   forward (MODE 0 unpaired, MODE 3 paired, mask-keeping)  v[e, h] = sum_k bf16(W1a[h, k]) bf16(codes[s, k] * codes[d, k]), then the
+ *                                                            unchanged fp32 epilogue (+ U[s] - U[d] + b1, ReLU, dropout, fc2, sigmoid);
+ *                                                            a mate's paired score equals the unpaired bf16 score bit for bit
+ *   dfeat (mask form, plain / fused / fused_packed)          bf16(diag(w2 / (1 - p)) W1a) against the exact 0 / 1 mask
+ *   d W1a (sgs_gemm_tn_mask / _gather)                       bf16(dz[k] * feat[k, :]) against the exact 0 / 1 mask
+ * The choice travels with the call (no global state).  H = 128 or 256 (sgs_edge_score_bf16_supported); the GEMM shapes are those of
+ * sgs_gemm_tn_mask_supported.  sgs_edge_score_bwd_dfeat_fused_packed_bf16 reads the operand that sgs_edge_score_bwd_prep_sd_pack_bf16 left
+ * in ws (the fp32 pair's packed operand is another layout). */
+int sgs_edge_score_bf16_supported(int64_t H);
+int sgs_edge_score_fwd_bf16(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
+                            int64_t edge_id_offset, const float* W1, const float* b1, const float* w2, const float* b2, float p_drop,
+                            uint64_t seed, uint32_t site, float* p_out, void* ws, size_t ws_bytes, sgs_stream_t stream);
+int sgs_edge_score_fwd_paired_bf16(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
+                                   int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
+                                   const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, void* ws,
+                                   size_t ws_bytes, sgs_stream_t stream);
+int sgs_edge_score_fwd_mask_bf16(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
+                                 int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
+                                 const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, uint32_t* maskbits,
+                                 void* ws, size_t ws_bytes, sgs_stream_t stream);
+int sgs_edge_score_bwd_dfeat_bits_bf16(const uint32_t* dvbits, const float* dz, int64_t n, int64_t H, const float* W1, const float* w2,
+                                       float p_drop, float* dfeat, void* ws, size_t ws_bytes, sgs_stream_t stream);
+int sgs_edge_score_bwd_prep_sd_pack_bf16(const float* codes, int64_t N, int64_t H, const int64_t* edge_index, int64_t E, const int64_t* active_eid,
+                                         int64_t n_active, const float* grad_p, const float* p, const uint32_t* maskbits, float* dz, uint32_t* dvbits,
+                                         int32_t* sd, const float* W1, const float* w2, float p_drop, void* ws, size_t ws_bytes, sgs_stream_t stream);
+int sgs_edge_score_bwd_dfeat_fused_bf16(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t N,
+                                        int64_t H, const float* W1, const float* w2, float p_drop, float* G, float* opart, void* ws, size_t ws_bytes,
+                                        sgs_stream_t stream);
+int sgs_edge_score_bwd_dfeat_fused_packed_bf16(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t N,
+                                               int64_t H, float* G, float* opart, const void* ws, size_t ws_bytes, sgs_stream_t stream);
+int sgs_gemm_tn_mask_bf16(const uint32_t* Abits, const float* dz, const float* rowscale, float scale, const float* B, int64_t K, int64_t M, int64_t N,
+                          float* C, int64_t ldc, float* colsum_A, float* dz_sum, float* C_raw, float* colsum_raw, void* ws, size_t ws_bytes,
+                          sgs_stream_t stream);
+int sgs_gemm_tn_mask_gather_bf16(const uint32_t* Abits, const float* dz, const float* rowscale, float scale, const float* codes, int64_t codes_rows,
+                                 const int32_t* sd, int64_t K, int64_t M, int64_t N, float* C, int64_t ldc, float* colsum_A, float* dz_sum, float* C_raw,
+                                 float* colsum_raw, void* ws, size_t ws_bytes, sgs_stream_t stream);
+
 int sgs_endpoint_reduce(const float* M_out, const float* M_in, const float* T, int64_t N, int64_t H, int64_t nnz,
                         const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, const int32_t* out_ptr,
                         const int32_t* out_dst, const int32_t* out_eid, float sign_out, float sign_in, float* out,

@@ -749,7 +749,8 @@ __global__ void __launch_bounds__(kT, 2) edge_score_stream64_kernel(ScoreArgs a,
 // Requires H % 128 == 0.
 // rowscale (TRANSPOSED only): the operand is diag(rowscale * scale) W1a, i.e. entry (k, h) is scaled by rowscale[k] * scale before it is
 // split -- the mask form of dfeat folds fc2's weights and the dropout scale into the matrix (MODE 4).
-template <bool TRANSPOSED>
+// P = 1 (bf16 mode): only the first piece, bf16(v) = RNE(v), in the same layout with one piece per (kc, t).
+template <bool TRANSPOSED, int P = 3>
 __device__ __forceinline__ void pack_w1a_bf16x3_one(int64_t i, const float* __restrict__ W1, int H, uint4* __restrict__ Wp16,
                                                     const float* __restrict__ rowscale, float scale) {
     const int NTl = H / 32;
@@ -766,16 +767,16 @@ __device__ __forceinline__ void pack_w1a_bf16x3_one(int64_t i, const float* __re
         if (TRANSPOSED && rowscale) { w0 *= rowscale[k0 + 2 * m] * scale; w1 *= rowscale[k0 + 2 * m + 1] * scale; }
         split3(w0, w1, p[0][m], p[1][m], p[2][m]);
     }
-    uint4* o = Wp16 + (static_cast<int64_t>(kc) * NTl + t) * 3 * 64 + lane;
+    uint4* o = Wp16 + (static_cast<int64_t>(kc) * NTl + t) * P * 64 + lane;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) o[c * 64] = make_uint4(p[c][0], p[c][1], p[c][2], p[c][3]);
+    for (int c = 0; c < P; ++c) o[c * 64] = make_uint4(p[c][0], p[c][1], p[c][2], p[c][3]);
 }
 inline int64_t pack_w1a_threads(int64_t H) { return (H / 16) * (H / 32) * 64; }       // one (kc, t, lane) each
 
-template <bool TRANSPOSED = false>      // TRANSPOSED: the pieces of W1a^T (row h of the operand = column h of W1a): the row-GEMM mode's operand
+template <bool TRANSPOSED = false, int P = 3>      // TRANSPOSED: the pieces of W1a^T (row h of the operand = column h of W1a): the row-GEMM mode's operand
 __global__ void __launch_bounds__(kT) pack_w1a_bf16x3(const float* __restrict__ W1, int H, uint4* __restrict__ Wp16,
                                                      const float* __restrict__ rowscale = nullptr, float scale = 1.f) {
-    pack_w1a_bf16x3_one<TRANSPOSED>(static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x, W1, H, Wp16, rowscale, scale);
+    pack_w1a_bf16x3_one<TRANSPOSED, P>(static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x, W1, H, Wp16, rowscale, scale);
 }
 
 // Measured (MI355X, E = 351 194, H = 256; launch = pack + kernel): 0.25-0.29 ms by device against 0.42-0.47 ms for variant D
@@ -834,15 +835,24 @@ __device__ __forceinline__ uint32_t shift_in_bit(uint32_t acc, uint64_t mask) {
 #endif
 #define SGS_STAMP(k) do { if (a.trace && tid == 0) a.trace[8 * blockIdx.x + (k)] = __builtin_readcyclecounter(); } while (0)
 
-template <int NT, int NW, int MODE = 0>
+// NP = 1: the bf16 mode (sgs_edge_score_fwd_bf16 and its siblings): W1a and the features are ONE bf16 piece each, bf16(v) = RNE(v), and every
+// tile issues the single product v1 x v1 (fp32 accumulation) where NP = 3 issues six (three with a 0 / 1 mask operand).  Wp16 is packed with
+// P = 1 (one piece per (kc, t)), so a k-chunk of W1a is a third of the bytes.  Only MODEs 0, 3, 4 and 5 are instantiated with NP = 1.
+// With one MFMA per tile a phase is NT MFMAs -- too short to hide the features' and the next stage's memory round trip, which NP = 3 hid
+// behind 6 NT.  The schedule is re-derived for that: the features are double-buffered (two Feat sets, chunk ph + 3 requested while chunk
+// ph + 1 is split, i.e. two phases of look-ahead instead of one), the next stage's DMA is issued BEFORE the feature loads of the phase and
+// the end-of-phase wait retires only it (vmcnt(#feature loads issued behind it)), and the gap work is spread over the first NT - 1 tiles.
+template <int NT, int NW, int MODE = 0, int NP = 3>
 __global__ void __launch_bounds__(64 * NW, 8 / NW) edge_score_bf16x6_kernel(ScoreArgs a, const uint4* __restrict__ Wp16) {
     constexpr bool BWD = MODE == 1, FUSED = MODE == 5, GEMMB = MODE == 4 || MODE == 5, GEMM = MODE == 2 || GEMMB, PAIR = MODE == 3;
+    constexpr bool ONE = NP == 1;
+    static_assert(NP == 3 || (ONE && MODE != 1 && MODE != 2), "the one-piece form exists for MODEs 0, 3, 4 and 5");
     constexpr int H = 32 * NT;
     constexpr int NPH = H / 16;              // phases: one 16-deep k-chunk each, one barrier per phase
-    constexpr int CH = NT * 3 * 64;          // 16-byte words per k-chunk of W1a (all hidden units, three pieces)
+    constexpr int CH = NT * NP * 64;         // 16-byte words per k-chunk of W1a (all hidden units, NP pieces)
     constexpr int TH = 64 * NW;              // NW waves x 32 edges per workgroup, all reading the same staged chunks of W1a
     constexpr int SPT = CH / TH;             // 16-byte words copied per thread per phase
-    static_assert(CH % TH == 0 && (SPT == 3 || SPT == 6), "unsupported shape");
+    static_assert(CH % TH == 0 && (ONE ? (SPT == 1 || SPT == 2) : (SPT == 3 || SPT == 6)), "unsupported shape");
     __shared__ uint4 wl[2][CH];
     __shared__ __attribute__((aligned(16))) float bw[2][H];          // b1, w2 for the epilogue
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -945,6 +955,10 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) edge_score_bf16x6_kernel(Scor
 #pragma unroll
             for (int m = 0; m < 4; ++m) P.F1[m] = ((b >> (2 * m)) & 1u ? 0x3F80u : 0u) | ((b >> (2 * m + 1)) & 1u ? 0x3F800000u : 0u);
             P.F2 = P.F1; P.F3 = P.F1;
+        } else if constexpr (ONE) {              // slot j: pair j, rounded once (feat = x_s * x_d in fp32, then RNE)
+            const float4 x = slot < 2 ? f.xa : f.xb, y = slot < 2 ? f.ya : f.yb;
+            const float x0 = (slot & 1) ? x.z : x.x, x1 = (slot & 1) ? x.w : x.y, y0 = (slot & 1) ? y.z : y.x, y1 = (slot & 1) ? y.w : y.y;
+            P.F1[slot] = pk_bf16(x0 * y0, x1 * y1);
         } else {
             if ((slot & 1) == 0) {
                 const float4 x = j < 2 ? f.xa : f.xb, y = j < 2 ? f.ya : f.yb;
@@ -969,7 +983,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) edge_score_bf16x6_kernel(Scor
             }
         }
     };
-    constexpr int kSlots = GEMMB ? 1 : 8;
+    constexpr int kSlots = GEMMB ? 1 : (ONE ? 4 : 8);
     auto split_feat = [&](Feat& f, int kc_, bool wr, Pieces& P) {
         SplitState st;
 #pragma unroll
@@ -1031,16 +1045,68 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) edge_score_bf16x6_kernel(Scor
             __builtin_amdgcn_sched_barrier(0);
         }
     };
+    // The one-piece phase (NP = 1; see the kernel's head): NT MFMAs, the gap work after the MFMAs of tiles 0 .. NT - 2 in the order split (of
+    // `fs`, which holds chunk kc1 + ... loaded two phases ago), DMA of the next stage, refill of `fs` with chunk kn_; the end-of-phase wait
+    // leaves the kFL feature loads in flight and retires the DMA only (vmcnt counts in issue order).
+    constexpr int kFL = GEMMB ? 1 : 4;                                 // vector-memory instructions of fload_x + fload_y
+    auto chunk1 = [&](const uint4* wcur, const uint4* wnx, int stage_next, WF& A, WF& B, WF& Cn, const Pieces& C, Pieces& Nx, Feat& fs, int kc1,
+                      int kn_) {
+        const bf16x8 f1 = __builtin_bit_cast(bf16x8, C.F1);
+        auto wload = [&](const uint4* wsrc, int t, WF& w) { w.q1 = wsrc[t * 64 + lane]; };
+        constexpr int kItems = kSlots + SPT + 2, kPer = (kItems + NT - 2) / (NT - 1);
+        SplitState st;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            if (t == NT - 1) {
+                static_assert(kFL == 1 || kFL == 4, "the wait below names the count");
+                if constexpr (kFL == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+                else                    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // this wave's part of the next stage has landed
+                SGS_PHASE_BARRIER();
+                wload(wnx, 0, A);
+                wload(wnx, 1, Cn);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, (t & 1) ? B.q1 : A.q1), f1, acc[t], 0, 0, 0);
+#pragma unroll
+            for (int q = 0; q < kPer; ++q) {
+                const int it = t * kPer + q;
+                if (t < NT - 1 && it < kItems) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (it < kSlots) split_slot(it, fs, kc1, false, Nx, st);
+                    else if (it < kSlots + SPT) dma_one(kc1, stage_next, it - kSlots);
+                    else if (it == kSlots + SPT) fload_x(kn_, fs);
+                    else fload_y(kn_, fs);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            if (t + 2 < NT) { if (t & 1) wload(wcur, t + 2, B); else wload(wcur, t + 2, A); }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
     Pieces pc, pn_;
     WF wa, wb, wc;
     {
         const uint4* w0 = wl[0];
-        wa.q1 = w0[lane]; wa.q2 = w0[64 + lane]; wa.q3 = w0[128 + lane];
-        wb.q1 = w0[192 + lane]; wb.q2 = w0[256 + lane]; wb.q3 = w0[320 + lane];
+        if constexpr (ONE) {
+            wa.q1 = w0[lane]; wb.q1 = w0[64 + lane];
+        } else {
+            wa.q1 = w0[lane]; wa.q2 = w0[64 + lane]; wa.q3 = w0[128 + lane];
+            wb.q1 = w0[192 + lane]; wb.q2 = w0[256 + lane]; wb.q3 = w0[320 + lane];
+        }
     }
     split_feat(fa, 0, true, pc);
     fload(NPH > 1 ? 1 : 0, fa);
     static_assert(NPH % 2 == 0, "the phase loop is unrolled by two (the odd fragment set and the operand pieces alternate)");
+    if constexpr (ONE) {
+        Feat fb;                                                       // chunk 2: the odd phases' feature set
+        fload(2, fb);
+#pragma unroll 1
+        for (int ph = 0; ph < NPH; ph += 2) {
+            chunk1(wl[0], wl[1], 1, wa, wb, wc, pc, pn_, fa, ph + 1, ph + 3 < NPH ? ph + 3 : NPH - 1);
+            chunk1(wl[1], wl[0], 0, wa, wc, wb, pn_, pc, fb, ph + 2 < NPH ? ph + 2 : NPH - 1, ph + 4 < NPH ? ph + 4 : NPH - 1);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the last phases' (dead) feature loads: retired before their registers are reused
+    } else
 #pragma unroll 1
     for (int ph = 0; ph < NPH; ph += 2) {
         // (the last phases reload / re-split their own chunks: no branches around the loads)
@@ -1741,6 +1807,7 @@ __global__ void __launch_bounds__(kT) scorer_bwd_prep(const float* __restrict__ 
 // dz) and its mask-bit row are in flight for 64 rows per wave, where scorer_bwd_prep keeps four rows per wave (its lanes serve the feat
 // columns).  Workgroups from n_prep_blocks on pack W1a^T for MODE 5 instead (Wp16 != nullptr): W1 and w2 are fixed for the step, so
 // the pack needs no launch of its own.  Same values as scorer_bwd_prep, bit for bit.
+template <int P = 3>     // P: pieces of the packed operand (1 = the bf16 mode's MODE 5, see edge_score_bf16x6_kernel)
 __global__ void __launch_bounds__(kT) scorer_bwd_prep_sd_pack(const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
                                                              const int64_t* __restrict__ active, int64_t n, int wpr,
                                                              const float* __restrict__ gp, const float* __restrict__ p,
@@ -1749,7 +1816,7 @@ __global__ void __launch_bounds__(kT) scorer_bwd_prep_sd_pack(const int64_t* __r
                                                              const float* __restrict__ W1, int H, uint4* __restrict__ Wp16,
                                                              const float* __restrict__ w2, float scale) {
     if (static_cast<int64_t>(blockIdx.x) >= n_prep_blocks) {
-        pack_w1a_bf16x3_one<true>((static_cast<int64_t>(blockIdx.x) - n_prep_blocks) * kT + threadIdx.x, W1, H, Wp16, w2, scale);
+        pack_w1a_bf16x3_one<true, P>((static_cast<int64_t>(blockIdx.x) - n_prep_blocks) * kT + threadIdx.x, W1, H, Wp16, w2, scale);
         return;
     }
     const int64_t r = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
@@ -2098,8 +2165,9 @@ static int g_probe_stagger = -1;                         // >= 0: forced by sgs_
 static int g_probe_prio = 0;
 static unsigned g_stagger_modes = (1u << 0) | (1u << 3); // kernel MODEs that use it
 static unsigned long long* g_probe_trace = nullptr;
-static void bf16x6_launch_knobs(ScoreArgs& a, int mode, int64_t H) {
-    a.stagger = (g_stagger_modes >> mode) & 1u ? (g_probe_stagger >= 0 ? g_probe_stagger : static_cast<int>(80 * (H / 32))) : 0;
+// (P = 1, the bf16 mode: the sleep is half a main loop of the P = 3 kernel scaled by its MFMA count, 1 / 6 -- derived, not tuned)
+static void bf16x6_launch_knobs(ScoreArgs& a, int mode, int64_t H, int P = 3) {
+    a.stagger = (g_stagger_modes >> mode) & 1u ? (g_probe_stagger >= 0 ? g_probe_stagger : static_cast<int>(80 * (H / 32)) / (P == 3 ? 1 : 6)) : 0;
     a.prio = g_probe_prio;
     a.trace = g_probe_trace;
 }
@@ -2228,7 +2296,7 @@ int sgs_edge_score_paired_supported(int64_t H) { return (H == 128 || H == 256) ?
 static int fwd_bf16x6_impl(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
                            int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
                            const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, uint32_t* maskbits,
-                           void* ws, size_t ws_bytes, sgs_stream_t stream_);
+                           void* ws, size_t ws_bytes, sgs_stream_t stream_, int P = 3);
 
 int sgs_edge_score_fwd_paired(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
                               int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
@@ -2255,7 +2323,7 @@ int sgs_edge_score_fwd_mask(const float* codes, const float* U, int64_t N, int64
 static int fwd_bf16x6_impl(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
                            int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
                            const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, uint32_t* maskbits,
-                           void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+                           void* ws, size_t ws_bytes, sgs_stream_t stream_, int P) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (int rc = check_common("sgs_edge_score_fwd_paired", N, H, E, p_drop)) return rc;
     SGS_REQUIRE(sgs_edge_score_paired_supported(H), SGS_EINVAL, "sgs_edge_score_fwd_paired: H must be 128 or 256");
@@ -2276,9 +2344,26 @@ static int fwd_bf16x6_impl(const float* codes, const float* U, int64_t N, int64_
     a.drop_scale = 1.0f / (1.0f - p_drop); a.drop_thresh = dropout_thresh(p_drop); a.seed = seed; a.epoch = epoch_ptr(); a.site = site;
     a.use_drop = p_drop > 0.f; a.p_out = p_out; a.dvbits = maskbits;
     a.canon = canon; a.mate = mate;
+    const dim3 grid(static_cast<unsigned>(cdiv(M, 128))), blk(256);
+    if (P == 1) {                                                    // the bf16 mode: one piece, one product per tile
+        hipLaunchKernelGGL((pack_w1a_bf16x3<false, 1>), dim3(static_cast<unsigned>(cdiv(pack_w1a_threads(H), kT))), dim3(kT), 0, stream, W1,
+                           static_cast<int>(H), Wp16, nullptr, 1.f);
+        if (canon) {
+            a.dyn_n = dyn_edges_ptr() ? dyn_edges_ptr() + 1 : nullptr;
+            bf16x6_launch_knobs(a, 3, H, 1);
+            if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 3, 1>), grid, blk, 0, stream, a, Wp16);
+            else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 3, 1>), grid, blk, 0, stream, a, Wp16);
+        } else {
+            a.dyn_n = dyn_edges_ptr();
+            bf16x6_launch_knobs(a, 0, H, 1);
+            if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 0, 1>), grid, blk, 0, stream, a, Wp16);
+            else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 0, 1>), grid, blk, 0, stream, a, Wp16);
+        }
+        SGS_LAUNCH_OK();
+        return SGS_OK;
+    }
     hipLaunchKernelGGL(pack_w1a_bf16x3<false>, dim3(static_cast<unsigned>(cdiv((H / 16) * (H / 32) * 64, kT))), dim3(kT), 0, stream, W1,
                        static_cast<int>(H), Wp16);
-    const dim3 grid(static_cast<unsigned>(cdiv(M, 128))), blk(256);
     if (canon) {
         a.dyn_n = dyn_edges_ptr() ? dyn_edges_ptr() + 1 : nullptr;   // word 1 of the registered dims: the live number of canonical edges
         bf16x6_launch_knobs(a, 3, H);
@@ -2293,6 +2378,37 @@ static int fwd_bf16x6_impl(const float* codes, const float* U, int64_t N, int64_
     }
     SGS_LAUNCH_OK();
     return SGS_OK;
+}
+
+/* ---- the bf16 mode (sgs_hip.h, "bf16 mode"): every fp32 product of the three forward forms and of the two mask-form dfeat contractions is
+ * ONE bf16 product, bf16(a) x bf16(b) with RNE rounding, accumulated in fp32.  Same arguments and outputs as the fp32-faithful entries. */
+int sgs_edge_score_bf16_supported(int64_t H) { return (H == 128 || H == 256) ? 1 : 0; }
+
+int sgs_edge_score_fwd_bf16(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
+                            int64_t edge_id_offset, const float* W1, const float* b1, const float* w2, const float* b2, float p_drop,
+                            uint64_t seed, uint32_t site, float* p_out, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    SGS_REQUIRE(sgs_edge_score_bf16_supported(H), SGS_EINVAL, "sgs_edge_score_fwd_bf16: H=%lld unsupported (128 or 256)", (long long)H);
+    return fwd_bf16x6_impl(codes, U, N, H, edge_index, E, edge_id_offset, nullptr, E, nullptr, W1, b1, w2, b2, p_drop, seed, site, p_out, nullptr,
+                           ws, ws_bytes, stream_, 1);
+}
+
+int sgs_edge_score_fwd_paired_bf16(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
+                                   int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
+                                   const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, void* ws,
+                                   size_t ws_bytes, sgs_stream_t stream_) {
+    SGS_REQUIRE((canon && mate) || E == 0 || M == 0, SGS_EINVAL, "sgs_edge_score_fwd_paired_bf16: null pointer");
+    return fwd_bf16x6_impl(codes, U, N, H, edge_index, E, edge_id_offset, canon, M, mate, W1, b1, w2, b2, p_drop, seed, site, p_out, nullptr, ws,
+                           ws_bytes, stream_, 1);
+}
+
+int sgs_edge_score_fwd_mask_bf16(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
+                                 int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
+                                 const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, uint32_t* maskbits,
+                                 void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    SGS_REQUIRE(maskbits || E == 0, SGS_EINVAL, "sgs_edge_score_fwd_mask_bf16: null pointer");
+    SGS_REQUIRE((canon != nullptr) == (mate != nullptr), SGS_EINVAL, "sgs_edge_score_fwd_mask_bf16: canon and mate come together");
+    return fwd_bf16x6_impl(codes, U, N, H, edge_index, E, edge_id_offset, canon, canon ? M : E, mate, W1, b1, w2, b2, p_drop, seed, site, p_out,
+                           maskbits, ws, ws_bytes, stream_, 1);
 }
 
 /* Backward core over the active rows: recomputes the hidden layer and writes
@@ -2457,6 +2573,29 @@ int sgs_edge_score_bwd_dfeat_bits(const uint32_t* dvbits, const float* dz, int64
     return SGS_OK;
 }
 
+static uint4* fused_wp16(void* ws, int64_t H);
+
+int sgs_edge_score_bwd_dfeat_bits_bf16(const uint32_t* dvbits, const float* dz, int64_t n, int64_t H, const float* W1, const float* w2,
+                                       float p_drop, float* dfeat, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(n >= 0 && H > 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_bits_bf16: bad arguments");
+    SGS_REQUIRE(sgs_edge_score_bf16_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_dfeat_bits_bf16: H=%lld unsupported (128 or 256)", (long long)H);
+    if (n == 0) return SGS_OK;
+    SGS_REQUIRE(dvbits && dz && W1 && w2 && dfeat, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_bits_bf16: null pointer");
+    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_dfeat_bits_bf16: workspace too small");
+    uint4* Wp16 = fused_wp16(ws, H);
+    hipLaunchKernelGGL((pack_w1a_bf16x3<true, 1>), dim3(static_cast<unsigned>(cdiv(pack_w1a_threads(H), kT))), dim3(kT), 0, stream, W1,
+                       static_cast<int>(H), Wp16, w2, 1.0f / (1.0f - p_drop));
+    ScoreArgs a{};
+    a.inbits = dvbits; a.indz = dz; a.n = n; a.H = static_cast<int>(H); a.feat = dfeat;
+    const dim3 grid(static_cast<unsigned>(cdiv(n, 128))), blk(256);
+    bf16x6_launch_knobs(a, 4, H, 1);
+    if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 4, 1>), grid, blk, 0, stream, a, Wp16);
+    else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 4, 1>), grid, blk, 0, stream, a, Wp16);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
 int sgs_endpoint_reduce(const float* M_out, const float* M_in, const float* T, int64_t N, int64_t H, int64_t nnz,
                         const int32_t* in_ptr, const int32_t* in_src,
                         const int32_t* in_eid, const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid,
@@ -2550,15 +2689,20 @@ static uint4* fused_wp16(void* ws, int64_t H) {
 
 static int bwd_prep_sd_impl(const float* codes, int64_t N, int64_t H, const int64_t* edge_index, int64_t E, const int64_t* active_eid,
                             int64_t n_active, const float* grad_p, const float* p, const uint32_t* maskbits, float* dz, uint32_t* dvbits,
-                            int32_t* sd, const float* W1, const float* w2, float p_drop, uint4* Wp16, hipStream_t stream) {
+                            int32_t* sd, const float* W1, const float* w2, float p_drop, uint4* Wp16, hipStream_t stream, int P = 3) {
     SGS_REQUIRE(N > 0 && H > 0 && H % 32 == 0 && E >= 0 && n_active >= 0 && (active_eid || n_active == E), SGS_EINVAL,
                 "sgs_edge_score_bwd_prep_sd: bad arguments (H %% 32 == 0; n_active == E when active_eid is NULL)");
     if (n_active == 0) return SGS_OK;
     SGS_REQUIRE(codes && edge_index && grad_p && p && maskbits && dz && dvbits && sd, SGS_EINVAL, "sgs_edge_score_bwd_prep_sd: null pointer");
     const int64_t nb = cdiv(n_active, kT), npack = Wp16 ? cdiv(pack_w1a_threads(H), kT) : 0;
-    hipLaunchKernelGGL(scorer_bwd_prep_sd_pack, dim3(static_cast<unsigned>(nb + npack)), dim3(kT), 0, stream, edge_index, edge_index + E, active_eid,
-                       n_active, static_cast<int>(H >> 5), grad_p, p, maskbits, dz, dvbits, reinterpret_cast<int2*>(sd), nb, W1,
-                       static_cast<int>(H), Wp16, w2, 1.0f / (1.0f - p_drop));
+    if (P == 1)
+        hipLaunchKernelGGL(scorer_bwd_prep_sd_pack<1>, dim3(static_cast<unsigned>(nb + npack)), dim3(kT), 0, stream, edge_index, edge_index + E,
+                           active_eid, n_active, static_cast<int>(H >> 5), grad_p, p, maskbits, dz, dvbits, reinterpret_cast<int2*>(sd), nb, W1,
+                           static_cast<int>(H), Wp16, w2, 1.0f / (1.0f - p_drop));
+    else
+        hipLaunchKernelGGL(scorer_bwd_prep_sd_pack<3>, dim3(static_cast<unsigned>(nb + npack)), dim3(kT), 0, stream, edge_index, edge_index + E,
+                           active_eid, n_active, static_cast<int>(H >> 5), grad_p, p, maskbits, dz, dvbits, reinterpret_cast<int2*>(sd), nb, W1,
+                           static_cast<int>(H), Wp16, w2, 1.0f / (1.0f - p_drop));
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -2582,16 +2726,35 @@ int sgs_edge_score_bwd_prep_sd_pack(const float* codes, int64_t N, int64_t H, co
                             fused_wp16(ws, H), static_cast<hipStream_t>(stream_));
 }
 
+/* The same with MODE 5's operand packed for the bf16 mode (one piece): the workspace then feeds sgs_edge_score_bwd_dfeat_fused_packed_bf16. */
+int sgs_edge_score_bwd_prep_sd_pack_bf16(const float* codes, int64_t N, int64_t H, const int64_t* edge_index, int64_t E, const int64_t* active_eid,
+                                         int64_t n_active, const float* grad_p, const float* p, const uint32_t* maskbits, float* dz, uint32_t* dvbits,
+                                         int32_t* sd, const float* W1, const float* w2, float p_drop, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    SGS_REQUIRE(p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_edge_score_bwd_prep_sd_pack_bf16: bad arguments");
+    SGS_REQUIRE(sgs_edge_score_bf16_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_prep_sd_pack_bf16: H=%lld unsupported (128 or 256)", (long long)H);
+    if (n_active == 0) return SGS_OK;
+    SGS_REQUIRE(W1 && w2, SGS_EINVAL, "sgs_edge_score_bwd_prep_sd_pack_bf16: null pointer");
+    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_prep_sd_pack_bf16: workspace too small");
+    return bwd_prep_sd_impl(codes, N, H, edge_index, E, active_eid, n_active, grad_p, p, maskbits, dz, dvbits, sd, W1, w2, p_drop,
+                            fused_wp16(ws, H), static_cast<hipStream_t>(stream_), 1);
+}
+
 /* MODE 5 of the bf16x6 loop (see the kernel): G [n, H] = dfeat * codes[src], opart [cdiv(n, 32) + N, H] = run-end partial sums of
  * dfeat * codes[dst].  The active rows must be sorted by source. */
 size_t sgs_edge_score_bwd_fused_opart_rows(int64_t n, int64_t N) { return static_cast<size_t>(cdiv(n < 0 ? 0 : n, 32) + (N < 0 ? 0 : N)); }
 
 static int bwd_dfeat_fused_launch(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t H,
-                                  const uint4* Wp16, float* G, float* opart, hipStream_t stream) {
+                                  const uint4* Wp16, float* G, float* opart, hipStream_t stream, int P = 3) {
     ScoreArgs a{};
     a.inbits = dvbits; a.indz = dz; a.n = n; a.H = static_cast<int>(H); a.feat = G; a.codes = codes; a.sd = sd; a.opart = opart;
     const dim3 grid(static_cast<unsigned>(cdiv(n, 128))), blk(256);
-    bf16x6_launch_knobs(a, 5, H);
+    bf16x6_launch_knobs(a, 5, H, P);
+    if (P == 1) {
+        if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 5, 1>), grid, blk, 0, stream, a, Wp16);
+        else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 5, 1>), grid, blk, 0, stream, a, Wp16);
+        SGS_LAUNCH_OK();
+        return SGS_OK;
+    }
     if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 5>), grid, blk, 0, stream, a, Wp16);
     else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 5>), grid, blk, 0, stream, a, Wp16);
     SGS_LAUNCH_OK();
@@ -2622,6 +2785,33 @@ int sgs_edge_score_bwd_dfeat_fused_packed(const uint32_t* dvbits, const float* d
     SGS_REQUIRE(dvbits && dz && sd && codes && G && opart, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_packed: null pointer");
     SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_dfeat_fused_packed: workspace too small");
     return bwd_dfeat_fused_launch(dvbits, dz, sd, codes, n, H, fused_wp16(const_cast<void*>(ws), H), G, opart, static_cast<hipStream_t>(stream_));
+}
+
+int sgs_edge_score_bwd_dfeat_fused_bf16(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t N,
+                                        int64_t H, const float* W1, const float* w2, float p_drop, float* G, float* opart, void* ws, size_t ws_bytes,
+                                        sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(n >= 0 && N > 0 && H > 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_bf16: bad arguments");
+    SGS_REQUIRE(sgs_edge_score_bf16_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_bf16: H=%lld unsupported (128 or 256)", (long long)H);
+    if (n == 0) return SGS_OK;
+    SGS_REQUIRE(dvbits && dz && sd && codes && W1 && w2 && G && opart, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_bf16: null pointer");
+    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_dfeat_fused_bf16: workspace too small");
+    uint4* Wp16 = fused_wp16(ws, H);
+    hipLaunchKernelGGL((pack_w1a_bf16x3<true, 1>), dim3(static_cast<unsigned>(cdiv(pack_w1a_threads(H), kT))), dim3(kT), 0, stream, W1,
+                       static_cast<int>(H), Wp16, w2, 1.0f / (1.0f - p_drop));
+    return bwd_dfeat_fused_launch(dvbits, dz, sd, codes, n, H, Wp16, G, opart, stream, 1);
+}
+
+int sgs_edge_score_bwd_dfeat_fused_packed_bf16(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t N,
+                                               int64_t H, float* G, float* opart, const void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    SGS_REQUIRE(n >= 0 && N > 0 && H > 0, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_packed_bf16: bad arguments");
+    SGS_REQUIRE(sgs_edge_score_bf16_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_packed_bf16: H=%lld unsupported (128 or 256)",
+                (long long)H);
+    if (n == 0) return SGS_OK;
+    SGS_REQUIRE(dvbits && dz && sd && codes && G && opart, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_packed_bf16: null pointer");
+    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE,
+                "sgs_edge_score_bwd_dfeat_fused_packed_bf16: workspace too small");
+    return bwd_dfeat_fused_launch(dvbits, dz, sd, codes, n, H, fused_wp16(const_cast<void*>(ws), H), G, opart, static_cast<hipStream_t>(stream_), 1);
 }
 
 /* The reductions that follow it: out_codes, out_U (and out_U_raw, optional) as sgs_endpoint_reduce_pair_bits produces them. */

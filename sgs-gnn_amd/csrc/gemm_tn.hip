@@ -265,12 +265,14 @@ __global__ void __launch_bounds__(64) gemm_tn_tall_tile(const float* __restrict_
 // gather needs its index first), the rows two steps before their products -- same values, same order of operations as reading a
 // materialised feat, so C is bit-identical; what goes away is the [K, N] array's round trip through HBM (written by the prep pass,
 // read once per 128-row M-tile here).
-template <int NW, bool MASK = false, bool GATHER = false>
+// ONE (with MASK; the bf16 mode, sgs_gemm_tn_mask_bf16): B is ONE piece, bf16(dz[k] * b) with RNE rounding, and a product is one MFMA.
+template <int NW, bool MASK = false, bool GATHER = false, bool ONE = false>
 __global__ void __launch_bounds__(64 * NW) gemm_tn_tall_bf16x6(const float* __restrict__ A, const float* __restrict__ B, int64_t K, int M, int N,
                                                               int ksplit, float* __restrict__ slab, float* __restrict__ cpart,
                                                               const uint32_t* __restrict__ Abits = nullptr, const float* __restrict__ dz = nullptr,
                                                               float* __restrict__ dzpart = nullptr, const int32_t* __restrict__ sd = nullptr) {
     static_assert(!GATHER || MASK, "the gathered B operand comes with the mask form of A");
+    static_assert(!ONE || MASK, "the one-piece form is the mask form's");
     extern __shared__ float red_lds[];       // NW > 1: [NW / 2][8 tiles x 16 registers][64 lanes] partial tiles + [NW / 2][4][64] column sums
     const int lane = threadIdx.x & 63, g = lane >> 5, l31 = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // wave-uniform, and the compiler should know: slice bounds in SGPRs
@@ -414,6 +416,10 @@ __global__ void __launch_bounds__(64 * NW) gemm_tn_tall_bf16x6(const float* __re
             for (int m = 0; m < 4; ++m) {
                 float e0 = w == 0 ? r.b[2 * m].x : r.b[2 * m].y, e1 = w == 0 ? r.b[2 * m + 1].x : r.b[2 * m + 1].y;
                 if constexpr (MASK) { e0 *= r.dzr[2 * m]; e1 *= r.dzr[2 * m + 1]; }
+                if constexpr (ONE) {
+                    Bp[w][0][m] = pk_bf16(e0, e1);
+                    continue;
+                }
                 uint32_t p1, p2, p3;
                 split3(e0, e1, p1, p2, p3);
                 Bp[w][0][m] = p1; Bp[w][1][m] = p2; Bp[w][2][m] = p3;
@@ -428,6 +434,10 @@ __global__ void __launch_bounds__(64 * NW) gemm_tn_tall_bf16x6(const float* __re
                 const bf16x8 a1 = __builtin_bit_cast(bf16x8, A1);
 #pragma unroll
                 for (int w = 0; w < 2; ++w) {
+                    if constexpr (ONE) {
+                        acc[t][w] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, __builtin_bit_cast(bf16x8, Bp[w][0]), acc[t][w], 0, 0, 0);
+                        continue;
+                    }
                     const bf16x8 b1 = __builtin_bit_cast(bf16x8, Bp[w][0]), b2 = __builtin_bit_cast(bf16x8, Bp[w][1]), b3 = __builtin_bit_cast(bf16x8, Bp[w][2]);
                     acc[t][w] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc[t][w], 0, 0, 0);     // smallest terms first
                     acc[t][w] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc[t][w], 0, 0, 0);
@@ -586,12 +596,18 @@ __global__ void __launch_bounds__(64 * NW) gemm_tn_tall_bf16x6(const float* __re
 // workgroup.  Three LDS stages, ONE barrier per step: step i + 1 is written while step i is multiplied; the endpoints of step i + 3 and
 // the rows of step i + 2 are in flight.  Column sums of dz * mask (d b1) are split over the NG = N / 64 column groups (rows 8 / NG each).
 // Fixed order throughout: run-to-run deterministic; NOT bit-identical to the per-wave-slice kernel (another summation order).
-template <int MT, int NG>
+// P = 1 (the bf16 mode, sgs_gemm_tn_mask_gather_bf16): the B fragments are ONE piece, bf16(feat * dz) with RNE rounding, and a step is 2 MT
+// MFMAs; the stages shrink to a third of their B bytes (the K-group sum then needs more LDS than the stages: maskfeat_lds_words).
+constexpr int maskfeat_stage_words(int MT, int P) { return 2 * P * 64 * 4 + (128 * MT / 32) * 16 + 16; }
+constexpr int maskfeat_lds_words(int MT, int P) {
+    return 2 * 3 * maskfeat_stage_words(MT, P) > 4 * 2 * 16 * 64 + 4 * MT * 64 + 8 ? 2 * 3 * maskfeat_stage_words(MT, P) : 4 * 2 * 16 * 64 + 4 * MT * 64 + 8;
+}
+template <int MT, int NG, int P = 3>
 __global__ void __launch_bounds__(512) gemm_tn_maskfeat(const uint32_t* __restrict__ Abits, const float* __restrict__ dz,
                                                         const float* __restrict__ codes, const int2* __restrict__ sd, int64_t K, int N,
                                                         float* __restrict__ slab, float* __restrict__ cpart, float* __restrict__ dzpart) {
     constexpr int M = 128 * MT, WPR = M / 32;
-    constexpr int kBst = 2 * 3 * 64 * 4;                    // dwords of B fragments per stage: [u][piece][lane][m]
+    constexpr int kBst = 2 * P * 64 * 4;                    // dwords of B fragments per stage: [u][piece][lane][m]
     constexpr int kMst = WPR * 16;                          // mask words per stage: [word][row]
     constexpr int kStage = kBst + kMst + 16;                // + 16 dz
     extern __shared__ uint32_t lds[];                       // [2 K-groups][3 stages][kStage]; reused for the K-group sum
@@ -661,11 +677,16 @@ __global__ void __launch_bounds__(512) gemm_tn_maskfeat(const uint32_t* __restri
         // feat = x_s * x_d rounded once, then the row factor, then the exact three-way split: as the materialised form did
         const float a0 = (r.as.x * r.ad.x) * da, a1 = (r.as.y * r.ad.y) * da;
         const float b0 = (r.bs.x * r.bd.x) * db, b1 = (r.bs.y * r.bd.y) * db;
+        if constexpr (P == 1) {
+            stg[((0 * P + 0) * 64 + lane) * 4 + w] = pk_bf16(a0, b0);
+            stg[((1 * P + 0) * 64 + lane) * 4 + w] = pk_bf16(a1, b1);
+        } else {
         uint32_t p1, p2, p3;
         split3(a0, b0, p1, p2, p3);                          // column n0 + 2 l31     (u = 0): rows (8 g + 2 w, + 1) = dword m = w of its fragments
         stg[((0 * 3 + 0) * 64 + lane) * 4 + w] = p1; stg[((0 * 3 + 1) * 64 + lane) * 4 + w] = p2; stg[((0 * 3 + 2) * 64 + lane) * 4 + w] = p3;
         split3(a1, b1, p1, p2, p3);                          // column n0 + 2 l31 + 1 (u = 1)
         stg[((1 * 3 + 0) * 64 + lane) * 4 + w] = p1; stg[((1 * 3 + 1) * 64 + lane) * 4 + w] = p2; stg[((1 * 3 + 2) * 64 + lane) * 4 + w] = p3;
+        }
         if (stage_mask) stg[kBst + sword * 16 + srow] = r.mw;
         if (stage_dz) stg[kBst + kMst + lane] = __float_as_uint(16 * step + lane < lim ? r.dl : 0.f);
         if (want_dz && l31 == 0) dzs += da + db;             // every row of the step exactly once over (w, g)
@@ -682,8 +703,8 @@ __global__ void __launch_bounds__(512) gemm_tn_maskfeat(const uint32_t* __restri
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int pc = 0; pc < 3; ++pc)
-                o.bq[u][pc] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(stg + ((u * 3 + pc) * 64 + lane) * 4));
+            for (int pc = 0; pc < P; ++pc)
+                o.bq[u][pc] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(stg + ((u * P + pc) * 64 + lane) * 4));
         if (want_cs) {
             // this column group's rows of every 8 (rpg of them): their mask word and dz straight from LDS (a runtime row index into
             // registers would put them in scratch)
@@ -710,6 +731,10 @@ __global__ void __launch_bounds__(512) gemm_tn_maskfeat(const uint32_t* __restri
             const bf16x8 a1 = __builtin_bit_cast(bf16x8, A1);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
+                if constexpr (P == 1) {
+                    acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, o.bq[u][0], acc[t][u], 0, 0, 0);
+                    continue;
+                }
                 acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, o.bq[u][2], acc[t][u], 0, 0, 0);      // smallest terms first
                 acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, o.bq[u][1], acc[t][u], 0, 0, 0);
                 acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, o.bq[u][0], acc[t][u], 0, 0, 0);
@@ -769,7 +794,7 @@ __global__ void __launch_bounds__(512) gemm_tn_maskfeat(const uint32_t* __restri
     dzs += __shfl_xor(dzs, 32, 64);
     float* red = reinterpret_cast<float*>(lds);
     constexpr int kRedCs = 4 * 2 * 16 * 64, kRedDz = kRedCs + 4 * MT * 64;
-    static_assert(kRedDz + 8 <= 2 * 3 * kStage, "the K-group sum reuses the stages");
+    static_assert(kRedDz + 8 <= maskfeat_lds_words(MT, P) && 2 * 3 * kStage <= maskfeat_lds_words(MT, P), "the K-group sum reuses the stages");
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
         __syncthreads();                                     // t = 0: every wave is through its last multiply; t = 1: group 0 has read tile row 0
@@ -851,7 +876,7 @@ size_t sgs_gemm_tn_workspace_bytes(int64_t K, int64_t M, int64_t N) {
 static int gemm_tn_impl(const float* A, const float* B, int64_t K, int64_t M, int64_t N, float* C, float* colsum_A, void* ws,
                         size_t ws_bytes, hipStream_t stream, int64_t ldc = 0, const uint32_t* Abits = nullptr, const float* dz = nullptr,
                         const float* rowscale = nullptr, float scale = 1.f, float* dz_sum = nullptr, float* C_raw = nullptr,
-                        float* colsum_raw = nullptr, const int32_t* sd = nullptr);
+                        float* colsum_raw = nullptr, const int32_t* sd = nullptr, bool one = false);
 // tall-K shapes: 1 = bf16x6 kernel (default; measured 147 vs 175 us incl. the 34 us slab reduction at K = 100 000, M = N = 256: the
 // operand splits, 264 vector instructions per 48 MFMAs, are at the budget the matrix pipe leaves), 0 = fp32-MFMA kernel
 static int g_tall_bf16x6 = 1;
@@ -915,9 +940,35 @@ int sgs_gemm_tn_mask_gather(const uint32_t* Abits, const float* dz, const float*
                         dz_sum, C_raw, colsum_raw, sd);
 }
 
+/* The bf16 mode of the two (sgs_hip.h, "bf16 mode"): the B operand dz[k] * feat[k, :] is ONE bf16 piece, RNE-rounded, against the exact 0 / 1
+ * mask -- one MFMA per product instead of three.  Same shapes (sgs_gemm_tn_mask_supported), arguments and outputs. */
+int sgs_gemm_tn_mask_bf16(const uint32_t* Abits, const float* dz, const float* rowscale, float scale, const float* B, int64_t K, int64_t M, int64_t N,
+                          float* C, int64_t ldc, float* colsum_A, float* dz_sum, float* C_raw, float* colsum_raw, void* ws, size_t ws_bytes,
+                          sgs_stream_t stream_) {
+    SGS_REQUIRE(ldc >= N, SGS_EINVAL, "sgs_gemm_tn_mask_bf16: ldc < N");
+    SGS_REQUIRE(Abits && dz && rowscale, SGS_EINVAL, "sgs_gemm_tn_mask_bf16: null pointer");
+    SGS_REQUIRE(sgs_gemm_tn_mask_supported(K, M, N), SGS_EINVAL, "sgs_gemm_tn_mask_bf16: shape not served (check sgs_gemm_tn_mask_supported)");
+    SGS_REQUIRE(!colsum_raw || colsum_A, SGS_EINVAL, "sgs_gemm_tn_mask_bf16: colsum_raw needs colsum_A");
+    return gemm_tn_impl(nullptr, B, K, M, N, C, colsum_A, ws, ws_bytes, static_cast<hipStream_t>(stream_), ldc, Abits, dz, rowscale, scale, dz_sum,
+                        C_raw, colsum_raw, nullptr, true);
+}
+
+int sgs_gemm_tn_mask_gather_bf16(const uint32_t* Abits, const float* dz, const float* rowscale, float scale, const float* codes, int64_t codes_rows,
+                                 const int32_t* sd, int64_t K, int64_t M, int64_t N, float* C, int64_t ldc, float* colsum_A, float* dz_sum, float* C_raw,
+                                 float* colsum_raw, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    SGS_REQUIRE(ldc >= N, SGS_EINVAL, "sgs_gemm_tn_mask_gather_bf16: ldc < N");
+    SGS_REQUIRE(codes_rows > 0 && codes_rows * N < (int64_t(1) << 32), SGS_EINVAL,
+                "sgs_gemm_tn_mask_gather_bf16: the codes table needs 32-bit element offsets");
+    SGS_REQUIRE(Abits && dz && rowscale && codes && sd, SGS_EINVAL, "sgs_gemm_tn_mask_gather_bf16: null pointer");
+    SGS_REQUIRE(sgs_gemm_tn_mask_supported(K, M, N), SGS_EINVAL, "sgs_gemm_tn_mask_gather_bf16: shape not served (check sgs_gemm_tn_mask_supported)");
+    SGS_REQUIRE(!colsum_raw || colsum_A, SGS_EINVAL, "sgs_gemm_tn_mask_gather_bf16: colsum_raw needs colsum_A");
+    return gemm_tn_impl(nullptr, codes, K, M, N, C, colsum_A, ws, ws_bytes, static_cast<hipStream_t>(stream_), ldc, Abits, dz, rowscale, scale,
+                        dz_sum, C_raw, colsum_raw, sd, true);
+}
+
 static int gemm_tn_impl(const float* A, const float* B, int64_t K, int64_t M, int64_t N, float* C, float* colsum_A, void* ws,
                         size_t ws_bytes, hipStream_t stream, int64_t ldc, const uint32_t* Abits, const float* dz, const float* rowscale,
-                        float scale, float* dz_sum, float* C_raw, float* colsum_raw, const int32_t* sd) {
+                        float scale, float* dz_sum, float* C_raw, float* colsum_raw, const int32_t* sd, bool one) {
     SGS_REQUIRE(K >= 0 && M >= 0 && N >= 0 && M < (1 << 30) && N < (1 << 30), SGS_EINVAL, "sgs_gemm_tn: bad sizes");
     if (M == 0 || N == 0) return SGS_OK;
     SGS_REQUIRE(C && (K == 0 || ((A || Abits) && B)), SGS_EINVAL, "sgs_gemm_tn: null pointer");
@@ -950,12 +1001,16 @@ static int gemm_tn_impl(const float* A, const float* B, int64_t K, int64_t M, in
             if (ns > ks) ns = ks;                                                        // the slab carving is sized for ks slices
             float* cpart2 = cv.take<float>(static_cast<size_t>(kMaskfeatMaxSlabs) * 8 * M + kMaskfeatMaxSlabs);
             float* dzp = dz_sum ? cpart2 + static_cast<size_t>(ns) * NGc * M : nullptr;
-            const size_t lds_b = static_cast<size_t>(2 * 3 * (2 * 3 * 64 * 4 + (M / 32) * 16 + 16)) * 4;
+            const size_t lds_b = static_cast<size_t>(one ? maskfeat_lds_words(M / 128, 1) : 2 * 3 * (2 * 3 * 64 * 4 + (M / 32) * 16 + 16)) * 4;
             const dim3 grid(static_cast<unsigned>(NGc), static_cast<unsigned>(ns));
             float* cpa = (colsum_A || dz_sum) ? cpart2 : static_cast<float*>(nullptr);
             const int2* sd2 = reinterpret_cast<const int2*>(sd);
             const int Ni = static_cast<int>(N);
-#define SGS_MASKFEAT(MT_, NG_) hipLaunchKernelGGL((gemm_tn_maskfeat<MT_, NG_>), grid, dim3(512), lds_b, stream, Abits, dz, B, sd2, K, Ni, slab, cpa, dzp)
+#define SGS_MASKFEAT(MT_, NG_)                                                                                                                 \
+    do {                                                                                                                                       \
+        if (one) hipLaunchKernelGGL((gemm_tn_maskfeat<MT_, NG_, 1>), grid, dim3(512), lds_b, stream, Abits, dz, B, sd2, K, Ni, slab, cpa, dzp);  \
+        else     hipLaunchKernelGGL((gemm_tn_maskfeat<MT_, NG_>), grid, dim3(512), lds_b, stream, Abits, dz, B, sd2, K, Ni, slab, cpa, dzp);     \
+    } while (0)
             if (M == 256) {
                 if (NGc == 1) SGS_MASKFEAT(2, 1); else if (NGc == 2) SGS_MASKFEAT(2, 2); else if (NGc == 4) SGS_MASKFEAT(2, 4); else SGS_MASKFEAT(2, 8);
             } else {
@@ -968,7 +1023,24 @@ static int gemm_tn_impl(const float* A, const float* B, int64_t K, int64_t M, in
             SGS_LAUNCH_OK();
             return SGS_OK;
         }
-        if (sd) {
+        if (one) {                                                   // the bf16 mode's per-wave-slice forms
+            static bool raised_1 = false;
+            if (!raised_1) {
+                SGS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_tall_bf16x6<NW, true, false, true>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+                SGS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_tall_bf16x6<NW, true, true, true>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+                raised_1 = true;
+            }
+            if (sd)
+                hipLaunchKernelGGL((gemm_tn_tall_bf16x6<NW, true, true, true>), dim3(cdiv(M, 128), cdiv(N, 64), n_slabs), dim3(64 * NW), lds, stream, A, B,
+                                   K, static_cast<int>(M), static_cast<int>(N), ks, slab, (colsum_A || dz_sum) ? cpart : static_cast<float*>(nullptr),
+                                   Abits, dz, dzpart, sd);
+            else
+                hipLaunchKernelGGL((gemm_tn_tall_bf16x6<NW, true, false, true>), dim3(cdiv(M, 128), cdiv(N, 64), n_slabs), dim3(64 * NW), lds, stream, A,
+                                   B, K, static_cast<int>(M), static_cast<int>(N), ks, slab, (colsum_A || dz_sum) ? cpart : static_cast<float*>(nullptr),
+                                   Abits, dz, dzpart);
+        } else if (sd) {
             static bool raised_g = false;
             if (!raised_g) {
                 SGS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_tall_bf16x6<NW, true, true>),

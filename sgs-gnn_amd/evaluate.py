@@ -179,15 +179,17 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
 
 
 def evaluate(args, model, cluster_loader, device, q=500, mode=None, temperature=1.0):
-    """evaluate.py:6-67."""
-    return _run(args, model, cluster_loader, device, q, mode, 1)
+    """evaluate.py:6-67.  args.sgs_precision ("fp32" default / "bf16"): the scorer's precision for the pass (ops.scorer_precision)."""
+    with ops.scorer_precision(getattr(args, "sgs_precision", None)):
+        return _run(args, model, cluster_loader, device, q, mode, 1)
 
 
 def ensemble_evaluate(args, model, cluster_loader, device, q=500, mode=None, temperature=1.0):
     """evaluate.py:70-173: mean of the logits of args.num_samples_eval independent draws."""
-    n_draws = int(args.num_samples_eval)
-    if _batched_ok(args, model, n_draws):
-        PATH_COUNTS["batched"] += 1
-        return _run_batched(args, model, cluster_loader, device, q, mode, n_draws)
-    PATH_COUNTS["serial"] += 1
-    return _run(args, model, cluster_loader, device, q, mode, n_draws)
+    with ops.scorer_precision(getattr(args, "sgs_precision", None)):
+        n_draws = int(args.num_samples_eval)
+        if _batched_ok(args, model, n_draws):
+            PATH_COUNTS["batched"] += 1
+            return _run_batched(args, model, cluster_loader, device, q, mode, n_draws)
+        PATH_COUNTS["serial"] += 1
+        return _run(args, model, cluster_loader, device, q, mode, n_draws)

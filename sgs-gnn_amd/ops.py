@@ -681,13 +681,58 @@ def src_sorted(edge_index: torch.Tensor) -> bool:
     return ok
 
 
+# ---- precision of the scorer's matrix-core contractions (include/sgs_hip.h, "bf16 mode").  "fp32" (default): every product fp32-faithful,
+# the parity mode.  "bf16": where the fp32-faithful path runs a bf16x6 / mask kernel (E >= 65 536, H in {128, 256}, the variant overrides
+# at their defaults, the mask-form backward), the one-product kernels run instead: bf16(a) x bf16(b), fp32 accumulation.  Elsewhere the
+# mode has no effect.  The choice is read when a forward is recorded and travels with it to its backward (ctx), never as library state.
+PRECISIONS = ("fp32", "bf16")
+_precision = "fp32"
+# launches per form that ran: forward / backward x fp32 / bf16 (tests prove which path was taken; reset with reset_precision_counts())
+PRECISION_COUNTS = {"fwd_fp32": 0, "fwd_bf16": 0, "bwd_fp32": 0, "bwd_bf16": 0}
+
+
+def reset_precision_counts() -> None:
+    for k in PRECISION_COUNTS:
+        PRECISION_COUNTS[k] = 0
+
+
+def check_precision(value) -> str:
+    """"fp32" / "bf16" (None: "fp32"); anything else raises ValueError."""
+    if value is None:
+        return "fp32"
+    if not isinstance(value, str) or value not in PRECISIONS:
+        raise ValueError(f"scorer precision must be one of {PRECISIONS}, got {value!r}")
+    return value
+
+
+def get_scorer_precision() -> str:
+    return _precision
+
+
+class scorer_precision:
+    """Context manager: the ambient precision of ops.edge_score inside the block (sgs_gnn_amd.scorer_precision("bf16"))."""
+
+    def __init__(self, value):
+        self.value = check_precision(value)
+
+    def __enter__(self):
+        global _precision
+        self.prev, _precision = _precision, self.value
+        return self
+
+    def __exit__(self, *exc):
+        global _precision
+        _precision = self.prev
+        return False
+
+
 class _EdgeScore(torch.autograd.Function):
     """K1b with the node-level half of fc1 inside: U = codes W1b^T (library GEMM) in forward; in backward d codes gets dU W1b on
     top of the direct term, and BOTH halves of d fc1.weight [H, 2H] are written in place by the two weight-gradient GEMMs
     (d W1a = dv^T feat, d W1b = dU^T codes; sgs_gemm_tn_ld with ldc = 2H) -- no slice views, zero fills or gradient adds."""
 
     @staticmethod
-    def forward(ctx, codes, W1, b1, w2, b2, edge_index, active, p, seed, site, edge_id_offset, pairs):
+    def forward(ctx, codes, W1, b1, w2, b2, edge_index, active, p, seed, site, edge_id_offset, pairs, precision="fp32"):
         L = _lib.lib()
         N, H = codes.shape
         E = edge_index.shape[1]
@@ -695,29 +740,37 @@ class _EdgeScore(torch.autograd.Function):
         out = torch.empty(E, dtype=torch.float32, device=codes.device)
         ws = workspace(L.sgs_edge_score_workspace_bytes(N, H, E), codes.device)
         maskbits = None
+        # the bf16 mode applies where the fp32-faithful path runs the bf16x6 loop (variant overrides win over the mode)
+        bf16 = (precision == "bf16" and E >= 65536 and L.sgs_edge_score_bf16_supported(H) and _variant_overrides_are_default())
         if (_fwd_mask and _mask_backward and E >= 65536 and L.sgs_edge_score_bwd_bits_supported(H) and ctx.needs_input_grad[0]
                 and _variant_overrides_are_default()):
             # a forward whose backward will follow: keep the ReLU x dropout mask of every scored edge (one bit per hidden unit), so that the
             # backward needs no recompute of the hidden layer (_edge_score_backward_mask)
             maskbits = torch.empty(E, H // 32, dtype=torch.int32, device=codes.device)
             canon, mate = pairs if pairs is not None else (None, None)
-            _lib.check(L.sgs_edge_score_fwd_mask(_ptr(codes, torch.float32), _ptr(U, torch.float32), N, H, _ptr(edge_index, torch.int64), E,
-                                                 edge_id_offset, _ptr(canon, torch.int32), 0 if canon is None else canon.numel(),
-                                                 _ptr(mate, torch.int32), _ptr(W1, torch.float32), _ptr(b1), _ptr(w2), _ptr(b2), float(p), seed, site,
-                                                 _ptr(out), _ptr(maskbits), ws.data_ptr(), ws.numel(), _stream()), "sgs_edge_score_fwd_mask")
+            fn = L.sgs_edge_score_fwd_mask_bf16 if bf16 else L.sgs_edge_score_fwd_mask
+            _lib.check(fn(_ptr(codes, torch.float32), _ptr(U, torch.float32), N, H, _ptr(edge_index, torch.int64), E,
+                          edge_id_offset, _ptr(canon, torch.int32), 0 if canon is None else canon.numel(),
+                          _ptr(mate, torch.int32), _ptr(W1, torch.float32), _ptr(b1), _ptr(w2), _ptr(b2), float(p), seed, site,
+                          _ptr(out), _ptr(maskbits), ws.data_ptr(), ws.numel(), _stream()), "sgs_edge_score_fwd_mask")
         elif pairs is not None and E >= 65536 and L.sgs_edge_score_paired_supported(H):
             # undirected graph stored both ways: the canonical half of the edges runs the contraction, every mate rides along
             canon, mate = pairs
-            _lib.check(L.sgs_edge_score_fwd_paired(_ptr(codes, torch.float32), _ptr(U, torch.float32), N, H, _ptr(edge_index, torch.int64), E,
-                                                   edge_id_offset, _ptr(canon, torch.int32), canon.numel(), _ptr(mate, torch.int32),
-                                                   _ptr(W1, torch.float32), _ptr(b1), _ptr(w2), _ptr(b2), float(p), seed, site, _ptr(out),
-                                                   ws.data_ptr(), ws.numel(), _stream()), "sgs_edge_score_fwd_paired")
+            fn = L.sgs_edge_score_fwd_paired_bf16 if bf16 else L.sgs_edge_score_fwd_paired
+            _lib.check(fn(_ptr(codes, torch.float32), _ptr(U, torch.float32), N, H, _ptr(edge_index, torch.int64), E,
+                          edge_id_offset, _ptr(canon, torch.int32), canon.numel(), _ptr(mate, torch.int32),
+                          _ptr(W1, torch.float32), _ptr(b1), _ptr(w2), _ptr(b2), float(p), seed, site, _ptr(out),
+                          ws.data_ptr(), ws.numel(), _stream()), "sgs_edge_score_fwd_paired")
         else:
-            _lib.check(L.sgs_edge_score_fwd(_ptr(codes, torch.float32), _ptr(U, torch.float32), N, H, _ptr(edge_index, torch.int64), E,
-                                            edge_id_offset, _ptr(W1, torch.float32), _ptr(b1), _ptr(w2), _ptr(b2), float(p), seed, site, _ptr(out),
-                                            ws.data_ptr(), ws.numel(), _stream()), "sgs_edge_score_fwd")
+            fn = L.sgs_edge_score_fwd_bf16 if bf16 else L.sgs_edge_score_fwd
+            _lib.check(fn(_ptr(codes, torch.float32), _ptr(U, torch.float32), N, H, _ptr(edge_index, torch.int64), E,
+                          edge_id_offset, _ptr(W1, torch.float32), _ptr(b1), _ptr(w2), _ptr(b2), float(p), seed, site, _ptr(out),
+                          ws.data_ptr(), ws.numel(), _stream()), "sgs_edge_score_fwd")
+        PRECISION_COUNTS["fwd_bf16" if bf16 else "fwd_fp32"] += 1
         ctx.save_for_backward(codes, U, W1, b1, w2, b2, edge_index, *((maskbits, out) if maskbits is not None else ()))
         ctx.active, ctx.p, ctx.seed, ctx.site, ctx.offset = active, float(p), seed, site, edge_id_offset
+        # the backward's one-piece contractions need the mask this forward kept (a recompute would be the fp32 function's)
+        ctx.bf16 = bf16 and maskbits is not None
         # the fused backward needs the active rows grouped by source: true for a drawn subset (ascending ids) of a row-sorted list
         ctx.src_sorted = maskbits is not None and _fused_backward and src_sorted(edge_index)
         return out
@@ -748,7 +801,9 @@ class _EdgeScore(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         if (_mask_backward and n >= 65536 and L.sgs_edge_score_bwd_bits_supported(H) and L.sgs_gemm_tn_mask_supported(n, H, H)
                 and ctx.needs_input_grad[0]):
+            PRECISION_COUNTS["bwd_bf16" if ctx.bf16 and kept else "bwd_fp32"] += 1
             return _EdgeScore._backward_mask(ctx, L, codes, U, W1, b1, w2, b2, edge_index, eid, graph, n, gp_act, kept)
+        PRECISION_COUNTS["bwd_fp32"] += 1
         # (a kept mask goes unused when the active set turns out too small for the mask-form kernels: the dense path recomputes)
         dv, feat = torch.empty(n, H, **f32), torch.empty(n, H, **f32)
         tile = L.sgs_edge_score_bwd_tile()
@@ -799,7 +854,7 @@ class _EdgeScore(torch.autograd.Function):
         wsb = workspace(L.sgs_gemm_tn_workspace_bytes(N, H, H), dev)
         _lib.check(L.sgs_gemm_tn_ld(_ptr(dU), _ptr(codes), N, H, H, dW1.data_ptr() + 4 * H, 2 * H, None, wsb.data_ptr(), wsb.numel(), _stream()),
                    "sgs_gemm_tn_ld")
-        return dcodes, dW1, db1, dw2, db2, None, None, None, None, None, None, None
+        return dcodes, dW1, db1, dw2, db2, None, None, None, None, None, None, None, None
 
 
 def _variant_overrides_are_default() -> bool:
@@ -840,14 +895,15 @@ def _edge_score_backward_mask(ctx, L, codes, U, W1, b1, w2, b2, edge_index, eid,
                                                   ws.data_ptr(), ws.numel(), _stream()), "sgs_edge_score_bwd_core_bits")
     dfeat = torch.empty(n, H, **f32)
     wsd = workspace(L.sgs_edge_score_workspace_bytes(0, H, 0), dev)
-    _lib.check(L.sgs_edge_score_bwd_dfeat_bits(_ptr(bits), _ptr(dz), n, H, _ptr(W1), _ptr(w2), p, _ptr(dfeat), wsd.data_ptr(), wsd.numel(),
+    bf16 = bool(kept) and getattr(ctx, "bf16", False)
+    _lib.check((L.sgs_edge_score_bwd_dfeat_bits_bf16 if bf16 else L.sgs_edge_score_bwd_dfeat_bits)(_ptr(bits), _ptr(dz), n, H, _ptr(W1), _ptr(w2), p, _ptr(dfeat), wsd.data_ptr(), wsd.numel(),
                                                _stream()), "sgs_edge_score_bwd_dfeat_bits")
     dW1 = torch.empty_like(W1)
     db1 = torch.empty(H, **f32)
     scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))        # as the kernels form it: 1.0f / (1.0f - p)
     wsg = workspace(L.sgs_gemm_tn_workspace_bytes(n, H, H), dev)
     db2 = torch.empty(1, **f32)
-    _lib.check(L.sgs_gemm_tn_mask(_ptr(bits), _ptr(dz), _ptr(w2), scale, _ptr(feat), n, H, H, _ptr(dW1), 2 * H, _ptr(db1), _ptr(db2), _ptr(Traw),
+    _lib.check((L.sgs_gemm_tn_mask_bf16 if bf16 else L.sgs_gemm_tn_mask)(_ptr(bits), _ptr(dz), _ptr(w2), scale, _ptr(feat), n, H, H, _ptr(dW1), 2 * H, _ptr(db1), _ptr(db2), _ptr(Traw),
                                   _ptr(craw), wsg.data_ptr(), wsg.numel(), _stream()), "sgs_gemm_tn_mask")
     dw2 = _colsum(hdz) if hdz is not None else None
     dcodes = torch.empty(N, H, **f32)
@@ -875,19 +931,20 @@ def _edge_score_backward_fused(ctx, L, codes, U, W1, b1, w2, edge_index, eid, gr
     maskbits, p_out = kept
     sd = torch.empty(n, 2, dtype=torch.int32, device=dev)
     wsd = workspace(L.sgs_edge_score_workspace_bytes(0, H, 0), dev)
-    _lib.check(L.sgs_edge_score_bwd_prep_sd_pack(_ptr(codes), N, H, _ptr(edge_index), E, _ptr(eid), n, _ptr(gp_act), _ptr(p_out), _ptr(maskbits),
+    bf16 = getattr(ctx, "bf16", False)
+    _lib.check((L.sgs_edge_score_bwd_prep_sd_pack_bf16 if bf16 else L.sgs_edge_score_bwd_prep_sd_pack)(_ptr(codes), N, H, _ptr(edge_index), E, _ptr(eid), n, _ptr(gp_act), _ptr(p_out), _ptr(maskbits),
                                                  _ptr(dz), _ptr(bits), _ptr(sd), _ptr(W1), _ptr(w2), p, wsd.data_ptr(), wsd.numel(), _stream()),
                "sgs_edge_score_bwd_prep_sd_pack")
     G = torch.empty(n, H, **f32)
     opart = torch.empty(L.sgs_edge_score_bwd_fused_opart_rows(n, N), H, **f32)
-    _lib.check(L.sgs_edge_score_bwd_dfeat_fused_packed(_ptr(bits), _ptr(dz), _ptr(sd), _ptr(codes), n, N, H, _ptr(G), _ptr(opart), wsd.data_ptr(),
+    _lib.check((L.sgs_edge_score_bwd_dfeat_fused_packed_bf16 if bf16 else L.sgs_edge_score_bwd_dfeat_fused_packed)(_ptr(bits), _ptr(dz), _ptr(sd), _ptr(codes), n, N, H, _ptr(G), _ptr(opart), wsd.data_ptr(),
                                                        wsd.numel(), _stream()), "sgs_edge_score_bwd_dfeat_fused_packed")
     dW1 = torch.empty_like(W1)
     db1, db2 = torch.empty(H, **f32), torch.empty(1, **f32)
     Traw, craw, Rraw = torch.empty(H, H, **f32), torch.empty(H, **f32), torch.empty(N, H, **f32)
     scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
     wsg = workspace(L.sgs_gemm_tn_workspace_bytes(n, H, H), dev)
-    _lib.check(L.sgs_gemm_tn_mask_gather(_ptr(bits), _ptr(dz), _ptr(w2), scale, _ptr(codes), N, _ptr(sd), n, H, H, _ptr(dW1), 2 * H, _ptr(db1), _ptr(db2),
+    _lib.check((L.sgs_gemm_tn_mask_gather_bf16 if bf16 else L.sgs_gemm_tn_mask_gather)(_ptr(bits), _ptr(dz), _ptr(w2), scale, _ptr(codes), N, _ptr(sd), n, H, H, _ptr(dW1), 2 * H, _ptr(db1), _ptr(db2),
                                          _ptr(Traw), _ptr(craw), wsg.data_ptr(), wsg.numel(), _stream()), "sgs_gemm_tn_mask_gather")
     dcodes, dU = torch.empty(N, H, **f32), torch.empty(N, H, **f32)
     _lib.check(L.sgs_edge_score_bwd_reduce_fused(_ptr(G), _ptr(opart), _ptr(bits), _ptr(dz), _ptr(w2), p, N, H, graph.n_edges, _ptr(graph.in_ptr),
@@ -906,21 +963,23 @@ def _edge_score_backward_mask_tail(L, codes, W1, dcodes, dU, dW1, db1, dw2, db2)
     wsb = workspace(L.sgs_gemm_tn_workspace_bytes(N, H, H), codes.device)
     _lib.check(L.sgs_gemm_tn_ld(_ptr(dU), _ptr(codes), N, H, H, dW1.data_ptr() + 4 * H, 2 * H, None, wsb.data_ptr(), wsb.numel(), _stream()),
                "sgs_gemm_tn_ld")
-    return dcodes, dW1, db1, dw2, db2, None, None, None, None, None, None, None
+    return dcodes, dW1, db1, dw2, db2, None, None, None, None, None, None, None, None
 
 
 _EdgeScore._backward_mask = staticmethod(_edge_score_backward_mask)
 
 
-def edge_score(codes, fc1_w, fc1_b, fc2_w, fc2_b, edge_index, active=None, p=0.0, seed=0, site=0, edge_id_offset=0, pairs="cached"):
+def edge_score(codes, fc1_w, fc1_b, fc2_w, fc2_b, edge_index, active=None, p=0.0, seed=0, site=0, edge_id_offset=0, pairs="cached",
+               precision=None):
     """K1b.  codes [N,H]; fc1_w [H,2H]; fc1_b [H]; fc2_w [1,H]; fc2_b [1]; edge_index [2,E] -> p [E].
     `pairs`: (canon, mate) of get_pairs for the paired forward, None for the plain one, "cached" (default) = whatever
-    get_pairs(edge_index) holds (nothing is built here)."""
+    get_pairs(edge_index) holds (nothing is built here).  `precision`: None = the ambient setting (scorer_precision), else "fp32" / "bf16"."""
+    precision = _precision if precision is None else check_precision(precision)
     _need_gpu(codes, fc1_w, edge_index)
     if isinstance(pairs, str):
         pairs = get_pairs(edge_index, codes.shape[0])
     return _EdgeScore.apply(codes.contiguous(), fc1_w.contiguous(), fc1_b.contiguous(), fc2_w.reshape(-1).contiguous(), fc2_b.contiguous(),
-                            edge_index.contiguous(), active, float(p), int(seed), int(site), int(edge_id_offset), pairs)
+                            edge_index.contiguous(), active, float(p), int(seed), int(site), int(edge_id_offset), pairs, precision)
 
 
 class _EdgeScoreEPD(torch.autograd.Function):

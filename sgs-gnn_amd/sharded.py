@@ -206,7 +206,7 @@ def sharded_evaluate_forward(args, model, shard: EdgeShard, q: int, noise_local=
     nm = sharded_norm(g_full, None)
     h = sharded_propagate(x @ sc.gcn1.lin.weight.t(), nm, sc.gcn1.bias, act=ops.ACT_RELU)
     codes = sharded_propagate(h @ sc.gcn2.lin.weight.t(), nm, sc.gcn2.bias, act=ops.ACT_RELU)
-    p_local = ops.edge_score(codes, sc.fc1.weight, sc.fc1.bias, sc.fc2.weight, sc.fc2.bias, shard.edge_index)
+    p_local = ops.edge_score(codes, sc.fc1.weight, sc.fc1.bias, sc.fc2.weight, sc.fc2.bias, shard.edge_index, precision="fp32")
     smp = dist_sample_topq(ops.SAMPLE_LEARNED, p_local, None, args.degree_bias_coef, q, shard.edge_index, shard.edge_offset,
                            shard.bounds, noise_local=noise_local, seed=seed, stream_id=stream_id)
     local_ids = smp.eid - shard.edge_offset
@@ -403,7 +403,7 @@ def train_step_sharded(args, model, shard: EdgeShard, optimizer_gnn, optimizer_e
     active = ops.ActiveSet()
     p_local = ops.edge_score(_F.apply(codes), _F.apply(sc.fc1.weight), _F.apply(sc.fc1.bias), _F.apply(sc.fc2.weight),
                              _F.apply(sc.fc2.bias), ei, active=active, p=p, seed=_DropoutClock.next_seed(), site=SITE_SCORE,
-                             edge_id_offset=off)
+                             edge_id_offset=off, precision="fp32")
     # K2+K3: learned draw (global)
     seed_n, tick = (0, 0) if noise.get("sample") is not None else _NoiseClock.next()
     smp = dist_sample_topq(ops.SAMPLE_LEARNED, p_local, shard.prob, args.degree_bias_coef, q, ei, off, bounds,
@@ -763,7 +763,7 @@ def train_step_blocksharded(args, model, shard: EdgeShard, optimizer_gnn, optimi
     codes = _AG.apply(codes_b, B)                                           # the scorer gathers codes by arbitrary endpoint
     active = ops.ActiveSet()
     p_local = ops.edge_score(codes, sc.fc1.weight, sc.fc1.bias, sc.fc2.weight, sc.fc2.bias, ei, active=active, p=p,
-                             seed=_DropoutClock.next_seed(), site=SITE_SCORE, edge_id_offset=off)
+                             seed=_DropoutClock.next_seed(), site=SITE_SCORE, edge_id_offset=off, precision="fp32")
     seed_n, tick = (0, 0) if noise.get("sample") is not None else _NoiseClock.next()
     smp = dist_sample_topq(ops.SAMPLE_LEARNED, p_local, shard.prob, args.degree_bias_coef, q, ei, off, bounds,
                            noise_local=noise.get("sample"), seed=seed_n, stream_id=tick)

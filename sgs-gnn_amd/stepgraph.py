@@ -206,7 +206,8 @@ class StepGraphs:
         a = self.args
         return (self.pipeline, bool(a.conditional), bool(a.sparse_edge_mlp), a.reg1 == True, a.reg2 == True,   # noqa: E712
                 float(a.regularizer1_coef), float(a.consist_reg_coef), float(a.degree_bias_coef), int(self.q),
-                bool(self.use_checkpoint), tuple(p.data_ptr() for p in self.params), _opt_signature(self.optimizers))
+                bool(self.use_checkpoint), tuple(p.data_ptr() for p in self.params), _opt_signature(self.optimizers),
+                ops.check_precision(getattr(a, "sgs_precision", None)))
 
     @classmethod
     def attach(cls, model, pipeline, args, criterion, q, use_checkpoint, optimizers=None, sync=None, loader=None):

@@ -173,9 +173,15 @@ def prepare_step_graphs(args, model, optimizer_gnn, optimizer_edge_prob, criteri
     kind (E_b > q, E_b <= q) is staged and the step is captured over both slots of that kind.  Nothing is trained: no optimiser
     step runs (a capture records, it does not execute; the warm-up pass discards its gradients).  Returns the seconds spent."""
     from .stepgraph import StepGraphs
+    precision = ops.check_precision(getattr(args, "sgs_precision", None))       # (the captures bake it in: StepGraphs._config_key)
     pipeline = getattr(args, "pipeline", "two_pass")
     if pipeline not in _PIPELINES:
         pipeline = "two_pass"
+    with ops.scorer_precision(precision):
+        return _prepare_step_graphs(StepGraphs, pipeline, args, model, optimizer_gnn, optimizer_edge_prob, criterion, cluster_loader, q)
+
+
+def _prepare_step_graphs(StepGraphs, pipeline, args, model, optimizer_gnn, optimizer_edge_prob, criterion, cluster_loader, q):
     sync = None
     if is_parallel():
         sync = getattr(model, "_sgs_gradsync", None)
@@ -223,6 +229,14 @@ def train_two_pass(args, epoch, max_epoch, model, optimizer_gnn, optimizer_edge_
 
 def _train(pipeline, args, epoch, max_epoch, model, optimizer_gnn, optimizer_edge_prob, optimizer, criterion,
            cluster_loader, q):
+    # args.sgs_precision: "fp32" (default, absent or None) or "bf16", the precision of the scorer's matrix-core contractions (ops.edge_score);
+    # checked before any partition is read
+    precision = ops.check_precision(getattr(args, "sgs_precision", None))
+    with ops.scorer_precision(precision):
+        return _train_in(pipeline, args, epoch, max_epoch, model, optimizer_gnn, optimizer_edge_prob, optimizer, criterion, cluster_loader, q)
+
+
+def _train_in(pipeline, args, epoch, max_epoch, model, optimizer_gnn, optimizer_edge_prob, optimizer, criterion, cluster_loader, q):
     device = args.device
     mode = args.mode
     use_checkpoint = bool(getattr(args, "hybrid_checkpoint", False))
