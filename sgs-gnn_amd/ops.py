@@ -619,13 +619,25 @@ class ActiveSet:
     None = all (dense backward over every scored edge).  The hybrid pipeline sets it to the
     q sampled edges after the draw (every other entry of dL/dp is exactly zero there,
     training_hybrid.py:86), which cuts the scorer's backward from E to q rows."""
-    __slots__ = ("eid", "graph", "gq")
+    __slots__ = ("eid", "graph", "gq", "ascending")
 
     def __init__(self):
         self.eid, self.graph, self.gq = None, None, None      # gq: the active rows' upstream gradient, handed over by _SelectSampled
+        self.ascending = False
 
-    def set(self, eid: torch.Tensor, graph: Graph):
-        self.eid, self.graph = eid, graph
+    def set(self, eid: torch.Tensor, graph: Graph, ascending=None):
+        """eid: the active edges' ids into the scored edge list, any order, each at most once; graph: the Graph of edge_index[:, eid] in
+        that same order (its edge k is active row k).  The fused scorer backward (_edge_score_backward_fused) additionally needs the rows
+        grouped by source -- `eid` ascending on a source-sorted edge list -- and runs only when `ascending` holds; any other order takes
+        the unfused mask-form backward, which is correct for every order.  ascending=True: the caller guarantees it (the sampler's
+        compaction and the sharded local ids emit edge order); nothing is checked.  None: checked here with one read-back, and taken as
+        False inside a stream capture (no host sync there).  False: the caller does not know."""
+        if ascending is None:
+            if torch.cuda.is_current_stream_capturing() or not eid.is_cuda:
+                ascending = False
+            else:
+                ascending = eid.numel() < 2 or bool((eid[1:] > eid[:-1]).all())
+        self.eid, self.graph, self.ascending = eid, graph, bool(ascending)
 
 
 def _act_bwd_colsum(dY, Y, act, p):
@@ -876,7 +888,10 @@ def _edge_score_backward_mask(ctx, L, codes, U, W1, b1, w2, b2, edge_index, eid,
     p = ctx.p
     bits = torch.empty(n, H // 32, dtype=torch.int32, device=dev)
     dz = torch.empty(n, **f32)
-    if kept and getattr(ctx, "src_sorted", False) and _fused_backward:      # (eid None: every edge active, in edge order -- sorted by source too)
+    # the fused form needs the active rows grouped by source: a source-sorted edge list (ctx.src_sorted) read in ascending edge order
+    # (eid None: every edge active, in edge order; else ActiveSet.ascending)
+    in_order = eid is None or bool(getattr(ctx.active, "ascending", False))
+    if kept and getattr(ctx, "src_sorted", False) and _fused_backward and in_order:
         return _edge_score_backward_fused(ctx, L, codes, U, W1, b1, w2, edge_index, eid, graph, n, gp_act, kept, bits, dz)
     feat = torch.empty(n, H, **f32)
     hdz = Traw = craw = Rraw = None

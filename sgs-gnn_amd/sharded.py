@@ -410,7 +410,7 @@ def train_step_sharded(args, model, shard: EdgeShard, optimizer_gnn, optimizer_e
                            noise_local=noise.get("sample"), seed=seed_n, stream_id=tick)
     local_ids = smp.eid - off
     g_s = ops.get_subgraph(ei, N, smp, eid=local_ids)
-    active.set(local_ids, g_s)
+    active.set(local_ids, g_s, ascending=True)           # (the draw compacts in edge order)
     w_local = p_local.index_select(0, local_ids)
     nm_s = sharded_norm_autograd(g_s, w_local)
     pg = model.dropout.p
@@ -769,7 +769,7 @@ def train_step_blocksharded(args, model, shard: EdgeShard, optimizer_gnn, optimi
                            noise_local=noise.get("sample"), seed=seed_n, stream_id=tick)
     local_ids = smp.eid - off
     g_s = ops.get_subgraph(ei, N, smp, eid=local_ids)
-    active.set(local_ids, g_s)
+    active.set(local_ids, g_s, ascending=True)           # (the draw compacts in edge order)
     w_local = p_local.index_select(0, local_ids)
     nm_s = _block_norm(g_s, w_local, B)
     pg = model.dropout.p

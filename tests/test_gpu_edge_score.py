@@ -606,3 +606,47 @@ def test_gather_weight_gradient_shared_operand_kernel(K, H, N):
             err = float((a.double() - b).abs().max() / b.abs().max().clamp_min(1e-30))
             assert err < 2e-6, (name, err)
 
+
+
+@pytest.mark.parametrize("H,p", [(128, 0.3), (256, 0.0)])
+def test_active_set_in_any_order_gives_the_fp64_gradients(ops, H, p):
+    """The fused backward reads the active rows as runs of equal source (MODE 5 partials, scorer_bwd_reduce over act.graph's out-CSR), so it
+    holds only for an ascending `eid` on a source-sorted edge list.  ActiveSet.set with the same rows PERMUTED (and the Graph built from
+    them in that order) is a valid active set too: d codes and d W must still be the fp64 gradients, and must equal the ascending set's."""
+    N, E, q = 777, 140_000, 70_001
+    codes, ei, W1, b1, W2, b2, g, eid = _sorted_case(N, H, E, q, 321)
+    seed, site = 5, 2
+    keep = ops.dropout_keep(seed, site, E, H, p, DEV).cpu() if p > 0 else None
+    gq = torch.randn(q, generator=g)
+    sub = ei[:, eid]
+    # fp64 reference over the active rows; rows with a unit within fp32 rounding of ReLU's kink carry no gradient (see the epd test)
+    leaves = [t.clone().double().requires_grad_(True) for t in (codes, W1, b1, W2, b2)]
+    co, W1o, b1o, W2o, b2o = leaves
+    with torch.no_grad():
+        x, y = co[sub[0]], co[sub[1]]
+        vpre = torch.cat([x * y, x - y], 1) @ W1o.t() + b1o
+        gq[(vpre.abs() < 1e-5).any(1)] = 0.0
+    po = O.edge_score(co[sub[0]], co[sub[1]], W1o, b1o, W2o, b2o, p, None if keep is None else keep[eid]).squeeze(1)
+    po.backward(gq.double())
+    grads = {}
+    perm = torch.randperm(q, generator=g)
+    for order, rows in (("ascending", torch.arange(q)), ("permuted", perm)):
+        e_act = eid[rows]
+        gp = torch.zeros(E)
+        gp[e_act] = gq[rows]
+        dl = [t.clone().to(DEV).requires_grad_(True) for t in (codes, W1, b1, W2, b2)]
+        act = ops.ActiveSet()
+        ei_d = ei.to(DEV)
+        assert ops.src_sorted(ei_d)
+        pd = ops.edge_score(dl[0], dl[1], dl[2], dl[3], dl[4], ei_d, active=act, p=p, seed=seed, site=site)
+        act.set(e_act.to(DEV), ops.Graph(ei[:, e_act].to(DEV), N))
+        pd.backward(gp.to(DEV))
+        grads[order] = [t.grad.detach().cpu() for t in dl]
+        for name, a, b in zip(["dcodes", "dW1", "db1", "dW2", "db2"], grads[order], leaves):
+            assert bool(torch.isfinite(a).all()), (order, name)
+            if name == "db2":
+                assert abs(float(a) - float(b.grad)) < 2e-6 * float(gq.abs().sum()) / 4, (order, name)
+            else:
+                assert _rel(a, b.grad) < 2e-5, (order, name, _rel(a, b.grad))
+    for name, a, b in zip(["dcodes", "dW1", "db1", "dW2"], grads["permuted"], grads["ascending"]):
+        assert _rel(a, b) < 3e-6, (name, _rel(a, b))
