@@ -716,7 +716,7 @@ int sgs_adam_step_multi(const int64_t* desc_host, const float* hyper_host, int64
                         uint64_t* epoch, sgs_stream_t stream);
 
 /* ---------------------------------------------------------------- batched ensemble evaluation (evaluate.py:70-173)
- * All D draws of one partition in one pass.  Forward only (no autograd state), for the GCN head.
+ * All D draws of one partition in one pass.  Forward only (no autograd state), for the GCN, GAT and GIN heads.
  *
  * sgs_sample_topq_multi: D draws of sgs_sample_topq over ONE candidate set.  Draw d uses stream id stream_id0 + d (or noise row d of
  *   noise [D, E]) and is bitwise what sgs_sample_topq returns for it (small- and large-E path, ties to the lowest edge id).  Modes as
@@ -732,7 +732,11 @@ int sgs_adam_step_multi(const int64_t* desc_host, const float* hyper_host, int64
  *   X_d = X + d * x_stride (0: one X shared by all draws); Y [D, N, Dc]; act NONE or RELU.  Equal per draw to sgs_spmm_csr.
  * sgs_ensemble_mean_correct: running fp32 sum of Dc logit blocks (logits + d * x_stride, [N, C] each; x_stride 0 = the same block Dc
  *   times) into acc [N, C] (first: acc starts from block 0; else from acc), in draw order.  last: acc *= 1/D_total when D_total > 1,
- *   then argmax (first maximum wins) against y on mask0..2 accumulated into counts [6] int64 = {correct, total} x 3 (not cleared). */
+ *   then argmax (first maximum wins) against y on mask0..2 accumulated into counts [6] int64 = {correct, total} x 3 (not cleared).
+ * sgs_gat_alpha_fwd_multi: sgs_gat_alpha_fwd without attention dropout (p = 0, no soft_* outputs) over each draw's in-CSR (in_ptr
+ *   [D, N+1], in_src [D, nnz] from sgs_graph_filter_multi): draw d reads a_src + d * a_stride, a_dst + d * a_stride (0: node scores
+ *   shared by all draws; N: [D, N] blocks) and writes alpha_in [D, nnz] (0 at (i,i) entries), alpha_loop [D, N].  Same device code:
+ *   row d is bitwise sgs_gat_alpha_fwd's.  1 <= D <= 65535. */
 size_t sgs_sample_topq_multi_workspace_bytes(int64_t E, int64_t D);
 int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
                           uint64_t stream_id0, int64_t D, int64_t E, int64_t q, const int64_t* edge_index, uint8_t* mask, int64_t* sampled_eid,
@@ -745,6 +749,9 @@ int sgs_gcn_norm_fwd_multi(const float* w, int64_t q, int64_t N, int64_t D, cons
                            const int32_t* loop_eid, float* dis, float* loopw, float* what_in, float* what_loop, sgs_stream_t stream);
 int sgs_spmm_csr_multi(const float* X, int64_t x_stride, int64_t N, int64_t Dc, int64_t nnz, int64_t D, const int32_t* ptr, const int32_t* col,
                        const float* val, const float* diag, const float* bias, int act, float* Y, sgs_stream_t stream);
+int sgs_gat_alpha_fwd_multi(const float* a_src, const float* a_dst, int64_t a_stride, int64_t N, int64_t D, int64_t nnz,
+                            const int32_t* in_ptr, const int32_t* in_src, float negative_slope, float* alpha_in, float* alpha_loop,
+                            sgs_stream_t stream);
 int sgs_ensemble_mean_correct(const float* logits, int64_t x_stride, int64_t Dc, int64_t N, int64_t C, float* acc, int first, int last,
                               int64_t D_total, const int64_t* y, const uint8_t* mask0, const uint8_t* mask1, const uint8_t* mask2, int64_t* counts,
                               sgs_stream_t stream);

@@ -20,18 +20,13 @@ constexpr int kT = 256;
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : slope * v; }
 
 // alpha_in[k] (dst-CSR order; 0 for (i,i) entries), alpha_loop[i]: post-softmax, post-dropout weights;
-// soft_in / soft_loop: the pre-dropout softmax values kept for backward.
-__global__ void __launch_bounds__(kT) gat_alpha_fwd(const float* __restrict__ a_s, const float* __restrict__ a_d, int64_t N,
+// soft_in / soft_loop: the pre-dropout softmax values kept for backward (SOFT = false: not written).  One wave per row i.
+template <bool SOFT>
+__device__ __forceinline__ void gat_alpha_fwd_body(int64_t i, int lane, const float* __restrict__ a_s, const float* __restrict__ a_d,
                                                    const int* __restrict__ in_ptr, const int* __restrict__ in_src,
-                                                   const int* __restrict__ in_eid, float slope, float drop_scale,
-                                                   uint32_t drop_thresh, int use_drop, uint64_t seed, uint32_t site,
-                                                   const uint64_t* __restrict__ epoch, float* __restrict__ soft_in,
-                                                   float* __restrict__ soft_loop, float* __restrict__ alpha_in,
-                                                   float* __restrict__ alpha_loop) {
-    seed = fold_epoch(seed, epoch);
-    const int lane = threadIdx.x & 63;
-    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
-    if (i >= N) return;
+                                                   const int* __restrict__ in_eid, float slope, float drop_scale, uint32_t drop_thresh,
+                                                   int use_drop, uint64_t seed, uint32_t site, float* __restrict__ soft_in,
+                                                   float* __restrict__ soft_loop, float* __restrict__ alpha_in, float* __restrict__ alpha_loop) {
     const int b = in_ptr[i], e = in_ptr[i + 1];
     const float ad = a_d[i];
     const float eloop = lrelu(a_s[i] + ad, slope);
@@ -57,16 +52,45 @@ __global__ void __launch_bounds__(kT) gat_alpha_fwd(const float* __restrict__ a_
             al = sm;
             if (use_drop) al = dropout_keep_at(seed, site, static_cast<uint64_t>(in_eid[k]), 0u, drop_thresh) ? sm * drop_scale : 0.f;
         }
-        soft_in[k] = sm;
+        if (SOFT) soft_in[k] = sm;
         alpha_in[k] = al;
     }
     if (lane == 0) {
         const float sm = expf(eloop - mx) * inv;
         float al = sm;
         if (use_drop) al = dropout_keep_at(seed, site + 1u, static_cast<uint64_t>(i), 0u, drop_thresh) ? sm * drop_scale : 0.f;
-        soft_loop[i] = sm;
+        if (SOFT) soft_loop[i] = sm;
         alpha_loop[i] = al;
     }
+}
+
+__global__ void __launch_bounds__(kT) gat_alpha_fwd(const float* __restrict__ a_s, const float* __restrict__ a_d, int64_t N,
+                                                   const int* __restrict__ in_ptr, const int* __restrict__ in_src,
+                                                   const int* __restrict__ in_eid, float slope, float drop_scale,
+                                                   uint32_t drop_thresh, int use_drop, uint64_t seed, uint32_t site,
+                                                   const uint64_t* __restrict__ epoch, float* __restrict__ soft_in,
+                                                   float* __restrict__ soft_loop, float* __restrict__ alpha_in,
+                                                   float* __restrict__ alpha_loop) {
+    seed = fold_epoch(seed, epoch);
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    if (i >= N) return;
+    gat_alpha_fwd_body<true>(i, lane, a_s, a_d, in_ptr, in_src, in_eid, slope, drop_scale, drop_thresh, use_drop, seed, site, soft_in, soft_loop,
+                             alpha_in, alpha_loop);
+}
+
+// D drawn graphs of one partition (ensemble evaluation, no attention dropout): blockIdx.y = draw d, which reads the node scores at
+// a_s + d * as, a_d + d * as (as = 0: shared by every draw) and its CSR slices ptr [N+1], src [nnz]; the body above runs unchanged on
+// them, so row d of alpha_in [D, nnz] / alpha_loop [D, N] is bitwise what gat_alpha_fwd (p = 0) writes for draw d alone.
+__global__ void __launch_bounds__(kT) gat_alpha_fwd_multi(const float* __restrict__ a_s, const float* __restrict__ a_d, int64_t as, int64_t N,
+                                                         int64_t nnz, const int* __restrict__ in_ptr, const int* __restrict__ in_src, float slope,
+                                                         float* __restrict__ alpha_in, float* __restrict__ alpha_loop) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    if (i >= N) return;
+    const int64_t d = blockIdx.y;
+    gat_alpha_fwd_body<false>(i, lane, a_s + d * as, a_d + d * as, in_ptr + d * (N + 1), in_src + d * nnz, nullptr, slope, 1.0f, 0u, 0,
+                              uint64_t(0), 0u, nullptr, nullptr, alpha_in + d * nnz, alpha_loop + d * N);
 }
 
 // Backward of dropout + softmax + leaky_relu for one destination row:
@@ -247,6 +271,20 @@ int sgs_gat_alpha_fwd(const float* a_src, const float* a_dst, int64_t N, int64_t
     hipLaunchKernelGGL(gat_alpha_fwd, dim3(cdiv(N * 64, kT)), dim3(kT), 0, stream, a_src, a_dst, N, in_ptr, in_src, in_eid,
                        negative_slope, 1.0f / (1.0f - p_drop), dropout_thresh(p_drop), p_drop > 0.f ? 1 : 0, seed, site, epoch_ptr(), soft_in,
                        soft_loop, alpha_in, alpha_loop);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_gat_alpha_fwd_multi(const float* a_src, const float* a_dst, int64_t a_stride, int64_t N, int64_t D, int64_t nnz,
+                            const int32_t* in_ptr, const int32_t* in_src, float negative_slope, float* alpha_in, float* alpha_loop,
+                            sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(N >= 0 && nnz >= 0 && D >= 1 && D <= 65535 && (a_stride == 0 || a_stride >= N), SGS_EINVAL,
+                "sgs_gat_alpha_fwd_multi: bad sizes (1 <= D <= 65535; a_stride 0 or >= N)");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(a_src && a_dst && in_ptr && alpha_loop && (nnz == 0 || (in_src && alpha_in)), SGS_EINVAL, "sgs_gat_alpha_fwd_multi: null pointer");
+    hipLaunchKernelGGL(gat_alpha_fwd_multi, dim3(static_cast<unsigned>(cdiv(N * 64, kT)), static_cast<unsigned>(D)), dim3(kT), 0, stream, a_src, a_dst,
+                       a_stride, N, nnz, in_ptr, in_src, negative_slope, alpha_in, alpha_loop);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }

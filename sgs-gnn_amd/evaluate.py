@@ -7,10 +7,11 @@ running sum, and the per-split correct counts stay on the device until the end o
 Test hooks: `args._sgs_noise_eval = [noise_0, noise_1, ...]` feeds explicit Exp(1) noise per draw; `args._sgs_trace_eval = {}`
 receives the last partition's per-draw logits [D, N, C] ("logits"), averaged logits ("mean") and drawn edge lists ("edges").
 
-Batched engine (opt-in, `args.sgs_eval_batch`; True: draws per pass from a byte budget, an int k >= 1: at most k per pass): for
-GNNModel, all draws of a partition run as one pass of batched kernels (ops.ensemble_partition) instead of the serial loop below.  Draw d
-uses the same (seed, stream id) as the serial loop's d-th draw, so the drawn edge sets are identical.  Other heads keep the serial loop.
-`PATH_COUNTS` records which path each ensemble_evaluate call took.
+Batched engine (opt-in, `args.sgs_eval_batch`; True: draws per pass from a byte budget, an int k >= 1: at most k per pass): all draws
+of a partition run as one pass of batched kernels (ops.ensemble_partition_head) instead of the serial loop below.  Draw d uses the same
+(seed, stream id) as the serial loop's d-th draw, so the drawn edge sets are identical.  Which heads take it is a second opt-in,
+`args.sgs_eval_batch_heads`: absent / None = ("GCN",) (GNNModel only), "all" = GCN, GAT, GIN and Cheb, or a collection of those names;
+other heads keep the serial loop.  `PATH_COUNTS` records which path each ensemble_evaluate call took.
 """
 from __future__ import annotations
 
@@ -22,6 +23,7 @@ from .sampling import _NoiseClock, draw_learned, draw_prior, random_edge_samplin
 
 PATH_COUNTS = {"serial": 0, "batched": 0}
 EVAL_BATCH_BUDGET = 512 << 20          # bytes of per-pass buffers when args.sgs_eval_batch is True
+HEADS = ("GCN", "GAT", "GIN", "Cheb")
 
 
 def _one_draw(args, model, batch, q, mode, edge_probs, noise):
@@ -81,19 +83,28 @@ def _run(args, model, cluster_loader, device, q, mode, n_draws):
     return tuple((c[s][0] / c[s][1]) if c[s][1] > 0 else 0 for s in range(3))
 
 
-def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget) -> list:
+def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str = "GCN") -> list:
     """Draws per pass of the batched engine: a list of pass sizes summing to D, each >= 1.  `budget` is True (the largest pass whose
     per-draw buffers fit EVAL_BATCH_BUDGET bytes), an int number of bytes via ("bytes", n), or an int k >= 1 (at most k draws per pass).
     Per draw (an upper estimate of the engine's per-draw allocations): keys 4 E + mask E + filter positions 4 E; per drawn edge 40 B
     (int64 id 8, int64 endpoints 16 -- allocated only under the trace hook, counted always --, weight 4, CSR source and id 8, normalised
-    weight 4); per-node arrays 36 N; hidden 4 N H; two logit blocks 8 N C.  The result of the engine does not depend on the split."""
+    weight 4); per-node arrays 36 N; hidden 4 N H; two logit blocks 8 N C.  `head` adds what that head allocates on top: GAT 4 q + 12 N
+    (attention values, loop attentions, layer-2 node scores), GIN 4 N H + 8 N C + 4 q + 4 N (the MLP's second hidden block, the second
+    conv's product and aggregate, unit edge values and the 1 + eps diagonal); GCN and Cheb nothing.  The result of the engine does not
+    depend on the split."""
     D = int(D)
     if D < 1:
         raise ValueError(f"plan_draws: D={D} draws")
+    if head not in HEADS:
+        raise ValueError(f"plan_draws: head={head!r}, need one of {HEADS}")
     if budget is True or (isinstance(budget, tuple) and budget[0] == "bytes"):
         nbytes = EVAL_BATCH_BUDGET if budget is True else int(budget[1])
         ks = (int(E) + 63) & ~63
         per = 4 * ks + int(E) + 4 * int(E) + 40 * int(q) + 36 * (int(N) + 1) + 4 * int(N) * int(H) + 8 * int(N) * int(C) + 3 * 2048 * 4 + 64
+        if head == "GAT":
+            per += 4 * int(q) + 12 * int(N)
+        elif head == "GIN":
+            per += 4 * int(N) * int(H) + 8 * int(N) * int(C) + 4 * int(q) + 4 * int(N)
         k = max(1, min(D, int(nbytes) // per))
     else:
         k = int(budget)
@@ -105,20 +116,61 @@ def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget) -> list:
 
 def _batched_ok(args, model, n_draws) -> bool:
     """Whether this call takes the batched engine.  A falsy flag (False, None, 0) means off; anything else must be True or an
-    int >= 1, checked here, before any partition is read."""
+    int >= 1, and args.sgs_eval_batch_heads (consulted only then) a valid head selection, both checked here, before any partition is
+    read."""
     flag = getattr(args, "sgs_eval_batch", False)
     if not flag:
         return False
     if flag is not True and (isinstance(flag, bool) or not isinstance(flag, int) or flag < 1):
         raise ValueError(f"args.sgs_eval_batch={flag!r}: need True (draws per pass from a byte budget) or an int >= 1 (at most k per pass)")
+    heads = _eval_heads(args)
     if n_draws < 1:
         return False
-    from .model import GNNModel
-    return isinstance(model, GNNModel)
+    return _head_of(model) in heads
+
+
+def _eval_heads(args) -> frozenset:
+    """The heads args.sgs_eval_batch_heads sends to the batched engine: absent / None -> {"GCN"}, "all" -> all four, else a list, tuple or
+    set of names from HEADS.  Anything else raises ValueError."""
+    v = getattr(args, "sgs_eval_batch_heads", None)
+    if v is None:
+        return frozenset(("GCN",))
+    if isinstance(v, str):
+        if v == "all":
+            return frozenset(HEADS)
+    elif isinstance(v, (list, tuple, set, frozenset)) and all(isinstance(h, str) and h in HEADS for h in v):
+        return frozenset(v)
+    raise ValueError(f"args.sgs_eval_batch_heads={v!r}: need None, 'all' or a collection of names from {HEADS}")
+
+
+def _head_of(model):
+    """-> "GCN" / "GAT" / "GIN" / "Cheb" for the four heads, None for any other module."""
+    from .model import ChebModel, GATModel, GINModel, GNNModel
+    for cls, name in ((GNNModel, "GCN"), (GATModel, "GAT"), (GINModel, "GIN"), (ChebModel, "Cheb")):
+        if isinstance(model, cls):
+            return name
+    return None
+
+
+def _head_dims(model, head):
+    """(hidden width, classes) of a head."""
+    if head == "GCN":
+        return model.gcn1.out_channels, model.gcn2.out_channels
+    if head == "GAT":
+        return model.GAT.convs[0].out_channels, model.GAT.convs[1].out_channels
+    if head == "GIN":
+        return model.GIN.convs[0].nn.lins[0].out_features, model.GIN.convs[1].nn.lins[0].out_features
+    return model.gcn1.lins[0].out_features, model.gcn2.lins[0].out_features
+
+
+def _eval_forward_ticks(head) -> int:
+    """Dropout seeds one eval-mode forward of the head takes: GNNModel and GAT draw one on every call, GIN and Cheb only when training
+    with p > 0."""
+    return 1 if head in ("GCN", "GAT") else 0
 
 
 def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
-    """The serial loop's result with every partition's draws in batched passes (ops.ensemble_partition: one host call per partition)."""
+    """The serial loop's result with every partition's draws in batched passes (ops.ensemble_partition_head: one host call per partition)."""
     if mode not in ('learned', 'random', 'edge', 'full'):
         raise ValueError("Invalid mode. Choose 'learned', 'random', or 'full'.")
     flag = args.sgs_eval_batch
@@ -126,7 +178,9 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
     counts = None
     noises = list(getattr(args, "_sgs_noise_eval", None) or [])
     trace = getattr(args, "_sgs_trace_eval", None)
-    H, C = model.gcn1.out_channels, model.gcn2.out_channels
+    head = _head_of(model)
+    H, C = _head_dims(model, head)
+    ticks = _eval_forward_ticks(head)
     with torch.no_grad():
         for batch in cluster_loader:
             batch = batch.to(device)
@@ -137,7 +191,7 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
             given = [noises.pop(0) if noises else None for _ in range(n_draws)]     # the serial loop pops one per draw, whatever the mode
             if mode == 'full' or E <= q:
                 out = model(batch, batch.edge_index)                                 # every draw runs on the whole partition
-                _DropoutClock.tick += n_draws - 1                                    # the serial loop's other n_draws - 1 forwards
+                _DropoutClock.tick += (n_draws - 1) * ticks                          # the serial loop's other n_draws - 1 forwards
                 acc = torch.empty_like(out)
                 ops.ensemble_mean_correct(out, 0, n_draws, acc, True, True, n_draws, batch.y,
                                           (batch.train_mask, batch.val_mask, batch.test_mask), counts)
@@ -155,7 +209,7 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
                 p, kind = None, ops.SAMPLE_LEARNED
                 given = [None] * n_draws                                             # random_edge_sampling takes no noise
             passes, d = [], 0
-            for k in plan_draws(E, q, N, H, C, n_draws, flag):
+            for k in plan_draws(E, q, N, H, C, n_draws, flag, head=head):
                 while k > 0:                                                         # a pass never mixes explicit noise and clock draws
                     explicit = given[d] is not None
                     n = 1
@@ -168,10 +222,11 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
                         _NoiseClock.tick += n
                     d += n
                     k -= n
-            ops.ensemble_partition(batch, model.gcn1, model.gcn2, q, kind, p, passes, counts, trace)
-            # GNNModel.forward takes one dropout seed per call, in eval mode too: leave the dropout clock where the serial loop's
-            # n_draws forwards leave it, so that training after an evaluation draws the same masks whichever path evaluated
-            _DropoutClock.tick += n_draws
+            ops.ensemble_partition_head(batch, model, q, kind, p, passes, counts, trace)
+            # GNNModel.forward and GAT.forward take one dropout seed per call, in eval mode too (GIN and Cheb none): leave the dropout
+            # clock where the serial loop's n_draws forwards leave it, so that training after an evaluation draws the same masks whichever
+            # path evaluated
+            _DropoutClock.tick += n_draws * ticks
     if counts is None:
         return 0, 0, 0
     c = counts.tolist()

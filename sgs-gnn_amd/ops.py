@@ -1791,26 +1791,28 @@ def gcn_norm_multi(csr, w, q: int, N: int):
     return dis, loopw, what_in, what_loop
 
 
+def _spmm_multi(X, x_stride: int, csr, val, diag, bias, act, q: int, N: int, Dc: int):
+    """sgs_spmm_csr_multi over graph_filter_multi's CSRs: Y [D, N, Dc], Y[d] = act(A_d X_d + bias) with X_d = X + d * x_stride."""
+    L = _lib.lib()
+    in_ptr, in_src = csr[0], csr[1]
+    D = in_ptr.shape[0]
+    Y = torch.empty(D, N, Dc, dtype=torch.float32, device=X.device)
+    _lib.check(L.sgs_spmm_csr_multi(_ptr(X, torch.float32), int(x_stride), N, Dc, q, D, _ptr(in_ptr), _ptr(in_src), _ptr(val), _ptr(diag), _ptr(bias),
+                                    act, _ptr(Y), _stream()), "sgs_spmm_csr_multi")
+    return Y
+
+
 def _drawn_gcn_logits(parent: Graph, smp: MultiSampleResult, w, xl1, b1, W2, b2):
     """Logits [D, N, C] of the two GCN layers over each of the D drawn subgraphs of `parent` (one launch per stage for all draws):
     in-CSRs filtered out of the parent's, weighted (w [D, q]) or unit gcn_norm, layer 1 over the shared x W1^T, one library GEMM
     [D N, H] x W2^T for layer 2."""
-    L = _lib.lib()
     D, q, N = smp.D, smp.q, parent.N
-    f32 = dict(dtype=torch.float32, device=xl1.device)
     csr = graph_filter_multi(parent, smp)
-    in_ptr, in_src = csr[0], csr[1]
     _, _, what_in, what_loop = gcn_norm_multi(csr, w, q, N)
     H = xl1.shape[1]
-    h = torch.empty(D, N, H, **f32)
-    _lib.check(L.sgs_spmm_csr_multi(_ptr(xl1, torch.float32), 0, N, H, q, D, _ptr(in_ptr), _ptr(in_src), _ptr(what_in), _ptr(what_loop), _ptr(b1),
-                                    ACT_RELU, _ptr(h), _stream()), "sgs_spmm_csr_multi")
+    h = _spmm_multi(xl1, 0, csr, what_in, what_loop, b1, ACT_RELU, q, N, H)
     z = (h.view(D * N, H) @ W2.t()).contiguous()
-    C = z.shape[1]
-    out = torch.empty(D, N, C, **f32)
-    _lib.check(L.sgs_spmm_csr_multi(_ptr(z), N * C, N, C, q, D, _ptr(in_ptr), _ptr(in_src), _ptr(what_in), _ptr(what_loop), _ptr(b2), ACT_NONE,
-                                    _ptr(out), _stream()), "sgs_spmm_csr_multi")
-    return out
+    return _spmm_multi(z, N * z.shape[1], csr, what_in, what_loop, b2, ACT_NONE, q, N, z.shape[1])
 
 
 def ensemble_mean_correct(logits, x_stride: int, Dc: int, acc, first: bool, last: bool, D_total: int, y, masks, counts) -> None:
@@ -1850,6 +1852,112 @@ def ensemble_partition(batch, gcn1, gcn2, q: int, mode: int, p, passes, counts, 
                               (batch.train_mask, batch.val_mask, batch.test_mask), counts)
         if trace is not None:
             logs.append(out)
+            edges.append(smp.edge_index)
+    if trace is not None:
+        trace["logits"], trace["mean"], trace["edges"] = torch.cat(logs), acc, torch.cat(edges)
+    return acc
+
+
+def gat_alpha_multi(a_s, a_d, a_stride: int, csr, q: int, N: int, negative_slope: float, out=None):
+    """sgs_gat_alpha_fwd_multi over graph_filter_multi's CSRs: (alpha_in [D, q], alpha_loop [D, N]), row d bitwise sgs_gat_alpha_fwd's (p = 0)
+    for draw d.  Draw d's node scores are a_s / a_d + d * a_stride (0: one [N] pair shared by all draws; N: [D, N] blocks).  `out`: reuse
+    an (alpha_in, alpha_loop) pair of these shapes."""
+    L = _lib.lib()
+    in_ptr, in_src = csr[0], csr[1]
+    D = in_ptr.shape[0]
+    f32 = dict(dtype=torch.float32, device=in_ptr.device)
+    alpha_in, alpha_loop = out if out is not None else (torch.empty(D, max(q, 1), **f32), torch.empty(D, max(N, 1), **f32))
+    _lib.check(L.sgs_gat_alpha_fwd_multi(_ptr(a_s, torch.float32), _ptr(a_d, torch.float32), int(a_stride), N, D, q, _ptr(in_ptr), _ptr(in_src),
+                                         float(negative_slope), _ptr(alpha_in), _ptr(alpha_loop), _stream()), "sgs_gat_alpha_fwd_multi")
+    return alpha_in, alpha_loop
+
+
+def _drawn_gat_logits(parent: Graph, smp: MultiSampleResult, convs, xl1, a_s1, a_d1):
+    """Logits [D, N, C] of the two GATConv layers (heads = 1, eval: no attention dropout) over each of the D drawn subgraphs: layer 1 over
+    the shared x' = lin_src(x) and its node scores, one library GEMM [D N, H] x W2^T and one sgs_gat_scores_fwd over the D N rows (row-local:
+    draw d's scores are what that kernel gives on draw d's block alone) for layer 2.  The alpha buffers are reused by layer 2."""
+    D, q, N = smp.D, smp.q, parent.N
+    c1, c2 = convs
+    csr = graph_filter_multi(parent, smp)
+    alpha = gat_alpha_multi(a_s1, a_d1, 0, csr, q, N, c1.negative_slope)
+    H = xl1.shape[1]
+    h = _spmm_multi(xl1, 0, csr, alpha[0], alpha[1], c1.bias, ACT_RELU, q, N, H)
+    z = c2.lin_src(h.view(D * N, H)).contiguous()                    # nn.Linear, as GATConv.forward
+    C = z.shape[1]
+    a_s2, a_d2 = gat_scores(z, c2.att_src, c2.att_dst)
+    alpha = gat_alpha_multi(a_s2, a_d2, N, csr, q, N, c2.negative_slope, out=alpha)
+    return _spmm_multi(z, N * C, csr, alpha[0], alpha[1], c2.bias, ACT_NONE, q, N, C)
+
+
+def _drawn_gin_logits(parent: Graph, smp: MultiSampleResult, convs, u1):
+    """Logits [D, N, C] of the two GINConv layers over each of the D drawn subgraphs: the sum aggregation of sum_norm (unit value on every
+    drawn entry, existing (i,i) entries included, diagonal 1 + eps) as the draw-strided SpMM, then each MLP's second Linear over [D N, .]
+    in one library GEMM.  u1 = x W0^T of the first conv, shared by all draws."""
+    D, q, N = smp.D, smp.q, parent.N
+    f32 = dict(dtype=torch.float32, device=u1.device)
+    csr = graph_filter_multi(parent, smp)
+    ones = torch.ones(D, max(q, 1), **f32)
+    h = u1
+    for k, conv in enumerate(convs):
+        l0, l1 = conv.nn.lins
+        x_stride = 0 if k == 0 else N * l0.out_features
+        if k > 0:
+            h = linear_nobias(h, l0.weight).contiguous()
+        diag = torch.full((D, max(N, 1)), 1.0 + conv._eps, **f32)
+        a = _spmm_multi(h, x_stride, csr, ones, diag, l0.bias, ACT_RELU, q, N, l0.out_features)
+        h = linear_nobias(a.view(D * N, -1), l1.weight)
+        h += l1.bias                                                  # GINConv.forward: linear_nobias(h, W1) + b1
+        if k == 0:
+            h.relu_()                                                 # GIN.forward: F.relu between the convs (eval: no dropout)
+    return h.view(D, N, -1)
+
+
+def ensemble_partition_head(batch, model, q: int, mode: int, p, passes, counts, trace=None):
+    """ensemble_partition for any of the four heads (GNNModel, GATModel, GINModel, ChebModel), same arguments and result.  Per pass: the D
+    draws (sample_topq_multi), their in-CSRs (graph_filter_multi) and the head's logits for all of them; the draw-independent first
+    product (GAT: lin_src(x) and its node scores; GIN: x W0^T) runs once per partition.  Chebyshev (K = 1) ignores the graph: its logits
+    are computed once and folded D times; it draws only when `trace` asks for the edge lists.  GAT and GIN ignore edge weights, so no
+    straight-through weights are drawn for them."""
+    from .model import ChebModel, GATModel, GINModel, GNNModel
+    if isinstance(model, GNNModel):
+        return ensemble_partition(batch, model.gcn1, model.gcn2, q, mode, p, passes, counts, trace)
+    x, ei = batch.x, batch.edge_index
+    N = x.shape[0]
+    if isinstance(model, GATModel):
+        convs = tuple(model.GAT.convs)
+        xl1 = convs[0].lin_src(x).contiguous()                        # the serial path's call: bitwise the same x'
+        a_s1, a_d1 = gat_scores(xl1, convs[0].att_src, convs[0].att_dst)
+        logits = lambda parent, smp: _drawn_gat_logits(parent, smp, convs, xl1, a_s1, a_d1)
+    elif isinstance(model, GINModel):
+        convs = tuple(model.GIN.convs)
+        u1 = linear_nobias(x, convs[0].nn.lins[0].weight).contiguous()
+        logits = lambda parent, smp: _drawn_gin_logits(parent, smp, convs, u1)
+    elif isinstance(model, ChebModel):
+        fixed = model(batch, ei).contiguous()                         # [N, C], the same for every draw
+        logits = None
+    else:
+        raise TypeError(f"ensemble_partition_head: no batched engine for {type(model).__name__}")
+    parent = get_graph(ei, N) if logits is not None else None
+    D_total = sum(int(ps[0]) for ps in passes)
+    acc = None
+    done = 0
+    logs, edges = [], []
+    for k, (Dc, noise, seed, sid0) in enumerate(passes):
+        smp = None
+        if logits is not None or trace is not None:
+            smp = sample_topq_multi(mode, p, None, 0.0, q, ei, Dc, noise=noise, seed=seed, stream_id0=sid0, want_edge_index=trace is not None)
+        if logits is not None:
+            out = logits(parent, smp)
+            stride = N * out.shape[2]
+        else:
+            out, stride = fixed, 0
+        if acc is None:
+            acc = torch.empty(N, out.shape[-1], dtype=torch.float32, device=x.device)
+        done += Dc
+        ensemble_mean_correct(out, stride, Dc, acc, k == 0, done == D_total, D_total, batch.y,
+                              (batch.train_mask, batch.val_mask, batch.test_mask), counts)
+        if trace is not None:
+            logs.append(out if stride else out.unsqueeze(0).expand(Dc, *out.shape))
             edges.append(smp.edge_index)
     if trace is not None:
         trace["logits"], trace["mean"], trace["edges"] = torch.cat(logs), acc, torch.cat(edges)

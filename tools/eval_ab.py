@@ -1,10 +1,12 @@
-"""Same-process A/B of ensemble_evaluate: the serial draw loop vs the batched engine (args.sgs_eval_batch) over bench S3's stream.
+"""Same-process A/B of ensemble_evaluate: the serial draw loop vs the batched engine (args.sgs_eval_batch) over bench S3's or S4's stream.
 
-    python tools/eval_ab.py [--reps 3] [--parts 230] [--out profiles/r04_eval_ab.json]
+    python tools/eval_ab.py [--reps 3] [--parts 230] [--head GCN] [--stream S3] [--out profiles/r04_eval_ab.json]
 
-The 230-partition Reddit-like stream on the device (reddit_partition_stream(num_parts=230, seed=1000), as bench.py S3 builds it), a
-GNNModel with H = 256 and the GCN scorer, num_samples_eval = 11, mode 'learned', q = 100 000.  One untimed pass of each path, then the
-two alternate; a pass is timed on the host clock around a device synchronise.  Both paths start every pass from the same noise-clock
+--stream S3 (default): the 230-partition Reddit-like stream on the device (reddit_partition_stream(num_parts=230, seed=1000), as bench.py
+S3 builds it).  --stream S4: bench.py run_s4's partitions, synthetic_graph(33 869, 463 000, 128, 5, seed=300 + i, train_frac=0.2,
+power=0.6) for i < --parts (default 5).  --head GCN (default) / GAT / GIN / Cheb picks the model (GNNModel, GATModel, ...) and is the
+batched run's args.sgs_eval_batch_heads.  H = 256 and the GCN scorer, num_samples_eval = 11, mode 'learned', q = 100 000.  One untimed
+pass of each path, then the two alternate; a pass is timed on the host clock around a device synchronise.  Both paths start every pass from the same noise-clock
 position, so they draw the same edge sets; the F1 triples are reported as they come out (a near-tie in an argmax can flip a node
 between logits that agree to 1e-5), with the node-count difference of every split.  Run it once more under
 `rocprofv3 --kernel-trace --stats -- python tools/eval_ab.py --reps 1 --path batched` (and `--path serial`) for launch counts and the
@@ -25,7 +27,9 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--parts", type=int, default=230)
+    ap.add_argument("--parts", type=int, default=None, help="partitions (default: 230 for S3, 5 for S4)")
+    ap.add_argument("--head", choices=("GCN", "GAT", "GIN", "Cheb"), default="GCN")
+    ap.add_argument("--stream", choices=("S3", "S4"), default="S3")
     ap.add_argument("--draws", type=int, default=11)
     ap.add_argument("--out", default=None)
     ap.add_argument("--path", choices=("both", "serial", "batched"), default="both")
@@ -33,13 +37,21 @@ def main():
     import sgs_gnn_amd as S
     dev = "cuda:0"
     torch.manual_seed(0)
-    parts = S.reddit_partition_stream(num_parts=a.parts, seed=1000, device=dev)
-    model = S.GNNModel(602, 256, 41, dropout_prob=0.3, edge_mlp_type="GCN").to(dev)
+    if a.stream == "S3":
+        a.parts = 230 if a.parts is None else a.parts
+        parts = S.reddit_partition_stream(num_parts=a.parts, seed=1000, device=dev)
+        fin, ncls = 602, 41
+    else:
+        a.parts = 5 if a.parts is None else a.parts
+        parts = [S.synthetic_graph(33_869, 463_000, 128, 5, seed=300 + i, train_frac=0.2, power=0.6, device=dev) for i in range(a.parts)]
+        fin, ncls = 128, 5
+    cls = {"GCN": S.GNNModel, "GAT": S.GATModel, "GIN": S.GINModel, "Cheb": S.ChebModel}[a.head]
+    model = cls(fin, 256, ncls, dropout_prob=0.3, edge_mlp_type="GCN").to(dev)
 
     def one(path):
         args = argparse.Namespace(degree_bias_coef=0.3, num_samples_eval=a.draws)
         if path == "batched":
-            args.sgs_eval_batch = True
+            args.sgs_eval_batch, args.sgs_eval_batch_heads = True, [a.head]
         S.manual_seed(11)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -58,11 +70,11 @@ def main():
             times[path].append(t)
             f1s[path] = f1
     if a.path != "both":
-        print(json.dumps({"path": a.path, "seconds": times[a.path], "f1": f1s[a.path]}))
+        print(json.dumps({"path": a.path, "head": a.head, "stream": a.stream, "seconds": times[a.path], "f1": f1s[a.path]}))
         return
     tm, vm, te = (sum(int(b.train_mask.sum()) for b in parts), sum(int(b.val_mask.sum()) for b in parts), sum(int(b.test_mask.sum()) for b in parts))
     totals = (tm, vm, te)
-    res = {"partitions": a.parts, "draws": a.draws, "q": 100_000, "mode": "learned", "reps": a.reps,
+    res = {"stream": a.stream, "head": a.head, "partitions": a.parts, "draws": a.draws, "q": 100_000, "mode": "learned", "reps": a.reps,
            "serial_s": times["serial"], "batched_s": times["batched"],
            "serial_median_s": statistics.median(times["serial"]), "batched_median_s": statistics.median(times["batched"]),
            "serial_spread_s": max(times["serial"]) - min(times["serial"]), "batched_spread_s": max(times["batched"]) - min(times["batched"]),
