@@ -329,8 +329,11 @@ int sgs_spmm_csr_bwd_prev(const float* dZ, int64_t N, int64_t D, int64_t nnz, co
  * library GEMM done by the caller, so the per-edge contraction is H x H; it runs on the f32
  * matrix cores (v_mfma_f32_32x32x2_f32, exact fp32).
  *   codes, U [N,H] f32; W1 = fc1.weight [H,2H]; b1 [H]; w2 = fc2.weight [H]; b2 [1].
- *   4 <= H <= 256, H % 4 == 0.  Dropout on the hidden layer is counter-based, row = edge_id_offset + local
- *   edge id (edge_id_offset = 0 unless the edge list is a shard of a larger graph).
+ *   4 <= H <= 256 with H % 4 == 0, or 256 < H <= 1024 with H % 32 == 0 (sgs_edge_score_hidden_supported).  The wide sizes run a
+ *   chunked kernel of their own (the hidden units swept 256 at a time, fixed-order fc2 accumulation) in sgs_edge_score_fwd,
+ *   sgs_edge_score_fwd_paired, sgs_edge_score_bwd_core and the endpoint-dropout pair; every other scorer entry point (bf16 mode,
+ *   mask form, fused backward, dfeat) stays H = 128 or 256 as its _supported predicate says.  Dropout on the hidden layer is
+ *   counter-based, row = edge_id_offset + local edge id (edge_id_offset = 0 unless the edge list is a shard of a larger graph).
  * ws: sgs_edge_score_workspace_bytes(N, H, E).
  *
  * sgs_edge_score_bwd_core runs over an explicit list of active edges (hybrid / two-pass: the q
@@ -349,16 +352,20 @@ int sgs_spmm_csr_bwd_prev(const float* dZ, int64_t N, int64_t D, int64_t nnz, co
  *   d codes (direct) = reduce(dfeat, dfeat, T = codes, +1, +1);   d U = reduce(dv, dv, NULL, +1, -1).
  * ---------------------------------------------------------------------------------- */
 size_t sgs_edge_score_workspace_bytes(int64_t N, int64_t H, int64_t E);   /* E = 0 for the backward core */
+/* 1 if the fp32 scorer entry points above take hidden size H: 4 <= H <= 256 with H % 4 == 0, or 256 < H <= 1024 with H % 32 == 0;
+ * else 0.  Host only (callable without a GPU). */
+int sgs_edge_score_hidden_supported(int64_t H);
 int sgs_edge_score_get_variant(void);          /* the overrides currently set (-1 = automatic) */
 int sgs_edge_score_get_bwd_variant(void);
-void sgs_edge_score_set_bwd_variant(int variant); /* backward core: -1 = automatic (4 at H % 128 == 0 and >= 65 536 active rows, else 0), 0 = LDS-tiled, 3 = 64-edge streaming loop (A/B: measured slower), 4 = bf16x6 loop */
+void sgs_edge_score_set_bwd_variant(int variant); /* backward core: -1 = automatic (4 at H % 128 == 0 and >= 65 536 active rows, else 0), 0 = LDS-tiled, 3 = 64-edge streaming loop (A/B: measured slower), 4 = bf16x6 loop; ignored at H > 256 */
 int sgs_edge_score_bwd_tile(void);              /* active rows per hdz_part row (64) */
 void sgs_edge_score_set_variant(int variant);   /* forward kernel: -1 = automatic (default: when E >= 65 536, 4 if H % 128 == 0 else 3; below that 1),
                                                   * 0 = LDS-tiled, 1 = register-streaming (32-edge wave tile), 2 = weight-stationary
                                                   * persistent, 3 = register-streaming with a 64-edge wave tile, 4 = bf16x6: exact
                                                   * 3-way bf16 splits of both operands, six v_mfma_f32_32x32x16_bf16 per fp32
                                                   * product (fp32-faithful; H % 128 == 0, else 3); all give the same p to fp32
-                                                  * rounding */
+                                                  * rounding.  Both switches are A/B selectors among the H <= 256
+                                                  * kernels: at H > 256 they are ignored (one chunked kernel) */
 int sgs_edge_score_fwd(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
                        int64_t edge_id_offset, const float* W1, const float* b1, const float* w2, const float* b2,
                        float p_drop, uint64_t seed, uint32_t site, float* p_out, void* ws, size_t ws_bytes,
@@ -368,7 +375,8 @@ int sgs_edge_score_fwd(const float* codes, const float* U, int64_t N, int64_t H,
  * differ in the sign of U[s] - U[d] and in their dropout rows.  sgs_edge_mates pairs the edges (mate[e] = id of (dst_e -> src_e)
  * or -1; mutual, one to one; needs the src-CSR of sgs_graph_build), the caller lists the canonical edges (mate < 0 or e < mate)
  * and sgs_edge_score_fwd_paired runs the H x H contraction for those M edges only, finishing both scores of a pair in its
- * epilogue: p_out [E] equals sgs_edge_score_fwd's bit for bit.  H = 128 or 256 (ask sgs_edge_score_paired_supported).
+ * epilogue: p_out [E] equals sgs_edge_score_fwd's bit for bit.  H = 128, 256 or any wide size 256 < H <= 1024, H % 32 == 0
+ * (ask sgs_edge_score_paired_supported).
  * Under sgs_dyn_edges_set the live M is read from word 1 of the registered dims (word 0 = live E). */
 size_t sgs_edge_mates_workspace_bytes(int64_t n_edges);
 int sgs_edge_mates(const int64_t* edge_index, int64_t n_edges, int64_t N, const int32_t* out_ptr, const int32_t* out_dst,

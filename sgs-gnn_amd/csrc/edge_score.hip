@@ -342,6 +342,281 @@ __global__ void __launch_bounds__(kT, 3) edge_score_kernel(ScoreArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Wide hidden sizes (256 < H <= 1024, H % 32 == 0; sgs_edge_score_hidden_supported).  The LDS-tiled loop above with the hidden units
+// SWEPT in chunks of kWHC = 256: a workgroup owns 64 edges (rows) and, per chunk c, the hidden units 256 c .. 256 c + 255; wave
+// (eg, hh) holds edges 32 eg .. 32 eg + 31 x hidden units 256 c + 128 hh .. + 127 -- four 32x32 accumulator tiles (64 registers), the
+// register budget of the H = 256 kernel, whatever H is.  Per chunk the k-loop runs over all K = H (EPD: 2H) features in 16-deep steps:
+// W1a^T[k0:k0+16][chunk] (16 KiB) and the [16][64] feature tile (4 KiB) are staged in LDS, double-buffered, one barrier per step --
+// 41 KiB of LDS per workgroup, three workgroups per CU.  W1a (4 MiB at H = 1024) is never resident: every chunk streams its columns
+// from L2, 4 H^2 bytes per 64-edge workgroup against 128 H^2 flops, the H = 256 kernel's ratio.  The features are re-formed per chunk
+// (2 H gathered floats per edge per chunk: H-fold fewer bytes than flops).
+// The chunk's epilogue finishes dropout(relu(.)) for its hidden units and adds their fc2 terms to the lane's running partial z in a FIXED
+// order (chunk, tile, row group, unit), so the score is run-to-run deterministic; the two hidden halves and the two lane halves are
+// combined once after the last chunk, as above.  The last chunk of H % 256 != 0 holds whole 32-unit tiles only (H % 32 == 0): a wave
+// skips its dead tiles (ntl, wave-uniform), no MFMA runs on padding.
+// PAIRED (MODE 3 of the bf16x6 loop, same contract): the rows are the canonical edges; the epilogue also finishes the mate's z from the
+// same accumulators with U[d] - U[s] and the mate's dropout row -- the operands and their order are the unpaired kernel's for the
+// mate, so both scores equal sgs_edge_score_fwd's bit for bit.
+// BWD: the backward core (same outputs as edge_score_kernel<NT, true>).  dz needs the whole z, so the chunks' dropped hidden
+// activations are parked in the dv rows (this lane's own addresses, no barrier needed), and a second sweep over the rows turns them
+// into dv = dz w2 relu' keep scale and the per-64-row column sums of dz * hidden (fixed xor tree + one add, as above).  feat is
+// written by chunk 0 only.
+constexpr int kWHC = 256;
+template <bool BWD, bool EPD, bool PAIRED>
+__global__ void __launch_bounds__(kT, 3) edge_score_wide_kernel(ScoreArgs a) {
+    constexpr int HP = kWHC;
+    constexpr int NTW = HP / 64;                                  // 32x32 tiles per wave per chunk
+    __shared__ __attribute__((aligned(16))) float Wt_s0[2 * kBK * HP];
+    __shared__ __attribute__((aligned(16))) float Ft_s0[2 * kBK * kBM];
+    __shared__ int s_idx[kBM], d_idx[kBM];
+    __shared__ float zpart[2 * kBM], zpart_m[PAIRED ? 2 * kBM : 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int eg = wave & 1, hh = __builtin_amdgcn_readfirstlane(wave >> 1);
+    const int H = a.H;
+    const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kBM;
+    if (a.dyn_n) {
+        const int64_t live_n = *a.dyn_n;                          // never more than the capacity the launch was sized for
+        if (live_n < a.n) a.n = live_n;
+        if (row0 >= a.n) return;                                  // (uniform per workgroup)
+    }
+    auto edge_of = [&](int64_t r) -> int64_t { return PAIRED ? static_cast<int64_t>(a.canon[r]) : (a.active ? a.active[r] : r); };
+    if (tid < kBM) {
+        const int64_t r = row0 + tid;
+        int s = 0, d = 0;
+        if (r < a.n) {
+            const int64_t e = edge_of(r);
+            s = static_cast<int>(a.src[e]);
+            d = static_cast<int>(a.dst[e]);
+        }
+        s_idx[tid] = s;
+        d_idx[tid] = d;
+    }
+    const int kh = lane >> 5, l31 = lane & 31;
+    __syncthreads();
+
+    constexpr int kWV = kBK * (HP / 4) / kT;                      // float4 W loads per thread per k-step (4)
+    float4 wreg[kWV], xreg, yreg;
+    const int fe = tid & (kBM - 1), fc = tid >> 6;
+    const float* xrow = a.codes + static_cast<int64_t>(s_idx[fe]) * H;
+    const float* yrow = a.codes + static_cast<int64_t>(d_idx[fe]) * H;
+    const int KT = EPD ? 2 * H : H;                               // a multiple of kBK (H % 32 == 0)
+    uint32_t rkx = 0u, rky = 0u;
+    if (EPD) {
+        const int64_t r_ = row0 + fe;
+        const int64_t e_ = r_ < a.n ? edge_of(r_) : 0;
+        rkx = dropout_row_key(fold_epoch(a.seed_x, a.epoch), a.site_x, static_cast<uint64_t>(a.row_offset + e_));
+        rky = dropout_row_key(fold_epoch(a.seed_y, a.epoch), a.site_y, static_cast<uint64_t>(a.row_offset + e_));
+    }
+    auto ep_mask = [&](float4& v, uint32_t rk, int kk) {
+        const uint32_t b0 = dropout_pair_bits(rk, static_cast<uint32_t>(kk >> 1)), b1 = dropout_pair_bits(rk, static_cast<uint32_t>((kk >> 1) + 1));
+        v.x = (b0 & 0xFFFFu) >= a.ep_thresh ? v.x * a.ep_scale : 0.f;
+        v.y = (b0 >> 16) >= a.ep_thresh ? v.y * a.ep_scale : 0.f;
+        v.z = (b1 & 0xFFFFu) >= a.ep_thresh ? v.z * a.ep_scale : 0.f;
+        v.w = (b1 >> 16) >= a.ep_thresh ? v.w * a.ep_scale : 0.f;
+    };
+    auto fetch = [&](int k0, int hc0) {
+#pragma unroll
+        for (int j = 0; j < kWV; ++j) {
+            const int i = j * kT + tid;
+            const int k = i / (HP / 4), h = hc0 + (i % (HP / 4)) * 4;
+            wreg[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            // (32-bit offsets: K H <= 2^21; 64-bit row pointers per j would not fit the register budget next to the accumulators)
+            if (h < H) wreg[j] = *reinterpret_cast<const float4*>(a.WaT + static_cast<uint32_t>((k0 + k) * H + h));
+        }
+        const int kf = k0 + 4 * fc;
+        const int kk = (EPD && kf >= H) ? kf - H : kf;
+        xreg = *reinterpret_cast<const float4*>(xrow + kk);
+        yreg = *reinterpret_cast<const float4*>(yrow + kk);
+        if (EPD && a.epd) { ep_mask(xreg, rkx, kk); ep_mask(yreg, rky, kk); }
+    };
+    auto commit = [&](int k0, int buf, bool write_feat) {
+        float* Wt_s = Wt_s0 + buf * kBK * HP;
+        float* Ft_s = Ft_s0 + buf * kBK * kBM;
+#pragma unroll
+        for (int j = 0; j < kWV; ++j) {
+            const int i = j * kT + tid;
+            const int k = i / (HP / 4), h4 = (i % (HP / 4)) * 4;
+            *reinterpret_cast<float4*>(Wt_s + k * HP + h4) = wreg[j];
+        }
+        const bool diff = EPD && (k0 + 4 * fc) >= H;
+        const float4 f = diff ? make_float4(xreg.x - yreg.x, xreg.y - yreg.y, xreg.z - yreg.z, xreg.w - yreg.w)
+                              : make_float4(xreg.x * yreg.x, xreg.y * yreg.y, xreg.z * yreg.z, xreg.w * yreg.w);
+        if (BWD && write_feat) {
+            const int64_t r = row0 + fe;
+            if (r < a.n) *reinterpret_cast<float4*>(a.feat + r * KT + k0 + 4 * fc) = f;
+        }
+        Ft_s[(4 * fc + 0) * kBM + fe] = f.x;
+        Ft_s[(4 * fc + 1) * kBM + fe] = f.y;
+        Ft_s[(4 * fc + 2) * kBM + fe] = f.z;
+        Ft_s[(4 * fc + 3) * kBM + fe] = f.w;
+    };
+    float av[2][NTW], bv[2];
+    auto lds_operands = [&](int buf, int kk, int slot) {
+        const float* Wt_s = Wt_s0 + buf * kBK * HP + hh * (HP / 2);
+        const float* Ft_s = Ft_s0 + buf * kBK * kBM;
+        bv[slot] = Ft_s[(kk + kh) * kBM + 32 * eg + l31];
+#pragma unroll
+        for (int t = 0; t < NTW; ++t) av[slot][t] = Wt_s[(kk + kh) * HP + 32 * t + l31];
+    };
+
+    // this lane's edge (and its mate) for the epilogues; what the chunk epilogue needs beyond these is re-derived there, so that
+    // nothing but the two running fc2 partials stays live across the main loop
+    const int el = 32 * eg + l31;
+    const int64_t r = row0 + el;
+    float z = 0.f, zm = 0.f;
+    const int nch = (H + HP - 1) / HP;
+
+#pragma unroll 1
+    for (int c = 0; c < nch; ++c) {
+        const int hc0 = c * HP;
+        int ntl = (H - hc0 - hh * (HP / 2)) / 32;                 // live tiles of this wave in this chunk (wave-uniform)
+        ntl = ntl < 0 ? 0 : (ntl > NTW ? NTW : ntl);
+        f32x16 acc[NTW];
+#pragma unroll
+        for (int t = 0; t < NTW; ++t)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
+        fetch(0, hc0);
+        commit(0, 0, c == 0);
+        __syncthreads();
+        int cur = 0;
+#pragma unroll 1
+        for (int k0 = 0; k0 < KT; k0 += kBK) {
+            const bool more = k0 + kBK < KT;
+            if (more) fetch(k0 + kBK, hc0);
+            lds_operands(cur, 0, 0);
+#pragma unroll
+            for (int st = 0; st < kBK / 2; ++st) {
+                if (st + 1 < kBK / 2) lds_operands(cur, 2 * (st + 1), (st + 1) & 1);
+#pragma unroll
+                for (int t = 0; t < NTW; ++t)
+                    if (t < ntl) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[st & 1][t], bv[st & 1], acc[t], 0, 0, 0);
+                if (st == kBK / 4 - 1 && more) commit(k0 + kBK, cur ^ 1, c == 0);
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+        // ---- chunk epilogue: acc[t][q] is hidden unit hc0 + 128 hh + 32 t + (q & 3) + 8 (q >> 2) + 4 kh of this lane's edge
+        const bool live = r < a.n;
+        const int64_t eid = live ? edge_of(r) : 0;                // global edge id: dropout row
+        const int64_t mid = (PAIRED && live) ? static_cast<int64_t>(a.mate[eid]) : -1;
+        const uint64_t dseed = fold_epoch(a.seed, a.epoch);
+        const uint32_t rkey = dropout_row_key(dseed, a.site, static_cast<uint64_t>(a.row_offset + eid));
+        const uint32_t rkey_m = PAIRED ? dropout_row_key(dseed, a.site, static_cast<uint64_t>(a.row_offset + (mid >= 0 ? mid : 0))) : 0u;
+        const float* Us = a.U + static_cast<int64_t>(s_idx[el]) * H;
+        const float* Ud = a.U + static_cast<int64_t>(d_idx[el]) * H;
+#pragma unroll
+        for (int t = 0; t < NTW; ++t) {
+            if (t >= ntl) continue;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int hb = hc0 + hh * (HP / 2) + 32 * t + 8 * g + 4 * kh;
+                const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 us = EPD ? z4 : *reinterpret_cast<const float4*>(Us + hb);
+                const float4 ud = EPD ? z4 : *reinterpret_cast<const float4*>(Ud + hb);
+                const float4 bb = *reinterpret_cast<const float4*>(a.b1 + hb);
+                const float4 ww = *reinterpret_cast<const float4*>(a.w2 + hb);
+                const float u4[4] = {us.x - ud.x, us.y - ud.y, us.z - ud.z, us.w - ud.w};
+                const float um4[4] = {ud.x - us.x, ud.y - us.y, ud.z - us.z, ud.w - us.w};   // the mate (d -> s)
+                const float b4[4] = {bb.x, bb.y, bb.z, bb.w};
+                const float w4[4] = {ww.x, ww.y, ww.z, ww.w};
+                uint32_t bits[2] = {0u, 0u}, bits_m[2] = {0u, 0u};
+                if (a.use_drop) {
+                    bits[0] = dropout_pair_bits(rkey, static_cast<uint32_t>(hb >> 1));
+                    bits[1] = dropout_pair_bits(rkey, static_cast<uint32_t>((hb >> 1) + 1));
+                    if (PAIRED) {
+                        bits_m[0] = dropout_pair_bits(rkey_m, static_cast<uint32_t>(hb >> 1));
+                        bits_m[1] = dropout_pair_bits(rkey_m, static_cast<uint32_t>((hb >> 1) + 1));
+                    }
+                }
+                float hd4[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float v = (acc[t][4 * g + j] + u4[j]) + b4[j];
+                    float m = v > 0.f ? 1.f : 0.f;
+                    if (a.use_drop) {
+                        const uint32_t draw = (j & 1) ? (bits[j >> 1] >> 16) : (bits[j >> 1] & 0xFFFFu);
+                        m = draw >= a.drop_thresh ? m * a.drop_scale : 0.f;
+                    }
+                    hd4[j] = v * m;
+                    z = fmaf(w4[j], hd4[j], z);
+                    if (PAIRED) {
+                        const float vm = (acc[t][4 * g + j] + um4[j]) + b4[j];
+                        float mm = vm > 0.f ? 1.f : 0.f;
+                        if (a.use_drop) {
+                            const uint32_t draw = (j & 1) ? (bits_m[j >> 1] >> 16) : (bits_m[j >> 1] & 0xFFFFu);
+                            mm = draw >= a.drop_thresh ? mm * a.drop_scale : 0.f;
+                        }
+                        zm = fmaf(w4[j], vm * mm, zm);
+                    }
+                }
+                if (BWD && live) *reinterpret_cast<float4*>(a.dv + r * H + hb) = make_float4(hd4[0], hd4[1], hd4[2], hd4[3]);   // parked
+            }
+        }
+    }
+    z += __shfl_xor(z, 32, 64);
+    if (kh == 0) zpart[hh * kBM + el] = z;
+    if (PAIRED) {
+        zm += __shfl_xor(zm, 32, 64);
+        if (kh == 0) zpart_m[hh * kBM + el] = zm;
+    }
+    __syncthreads();
+    z = (zpart[el] + zpart[kBM + el]) + a.b2[0];
+    const float p = 1.0f / (1.0f + expf(-z));
+    const bool live = r < a.n;
+    if (!BWD) {
+        if (live && hh == 0 && kh == 0) {
+            const int64_t eid = edge_of(r), mid = PAIRED ? static_cast<int64_t>(a.mate[eid]) : -1;
+            a.p_out[PAIRED ? eid : r] = p;
+            if (PAIRED && mid >= 0) {
+                const float zz = (zpart_m[el] + zpart_m[kBM + el]) + a.b2[0];
+                a.p_out[mid] = 1.0f / (1.0f + expf(-zz));
+            }
+        }
+        return;
+    }
+    // ---- backward: dz = gp p (1-p);  dv = dz w2 relu' keep scale (from the parked hidden values);  hdz = per-tile column sums of dz hd
+    const float dzv = live ? a.gp[r] * p * (1.0f - p) : 0.f;
+    if (live && hh == 0 && kh == 0) a.dz[r] = dzv;
+    float* colpart = Wt_s0;                                       // [2 edge groups][H] (8 KiB at H = 1024): the operand stages are dead
+#pragma unroll 1
+    for (int c = 0; c < nch; ++c) {
+        const int hc0 = c * HP;
+        int ntl = (H - hc0 - hh * (HP / 2)) / 32;
+        ntl = ntl < 0 ? 0 : (ntl > NTW ? NTW : ntl);
+#pragma unroll
+        for (int t = 0; t < NTW; ++t) {
+            if (t >= ntl) continue;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int hb = hc0 + hh * (HP / 2) + 32 * t + 8 * g + 4 * kh;
+                const float4 ww = *reinterpret_cast<const float4*>(a.w2 + hb);
+                const float w4[4] = {ww.x, ww.y, ww.z, ww.w};
+                const float4 h4 = live ? *reinterpret_cast<const float4*>(a.dv + r * H + hb) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float hdv[4] = {h4.x, h4.y, h4.z, h4.w};
+                float dv4[4], hz4[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float m = hdv[j] > 0.f ? (a.use_drop ? a.drop_scale : 1.f) : 0.f;
+                    dv4[j] = dzv * w4[j] * m;
+                    hz4[j] = dzv * hdv[j];
+                }
+                if (live) *reinterpret_cast<float4*>(a.dv + r * H + hb) = make_float4(dv4[0], dv4[1], dv4[2], dv4[3]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float sum = hz4[j];
+#pragma unroll
+                    for (int o = 16; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+                    if (l31 == 0) colpart[eg * H + hb + j] = sum;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int h = tid; h < H; h += kT) a.hdz[static_cast<int64_t>(blockIdx.x) * H + h] = colpart[h] + colpart[H + h];
+}
+
+// ---------------------------------------------------------------------------------------------
 // Forward variant B ("stream"): no LDS tiles, no per-k-step barriers.  Both MFMA operands are streamed
 // from L2 straight into registers:
 //   * W1a is pre-packed as Wp[tile t][j4][lane][4]: the A operands of lane (l31, kh) for the four
@@ -2147,10 +2422,20 @@ int launch_score(const ScoreArgs& a, hipStream_t stream) {
     return SGS_OK;
 }
 
+// 4 <= H <= 256 with H % 4 == 0: the kernels above; 256 < H <= 1024 with H % 32 == 0: edge_score_wide_kernel
+inline bool hidden_ok(int64_t H) { return (H >= 4 && H <= 256 && H % 4 == 0) || (H > 256 && H <= 1024 && H % 32 == 0); }
+
+template <bool BWD, bool EPD, bool PAIRED = false>
+int launch_score_wide(const ScoreArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL((edge_score_wide_kernel<BWD, EPD, PAIRED>), dim3(static_cast<unsigned>(cdiv(a.n, kBM))), dim3(kT), 0, stream, a);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
 inline int check_common(const char* who, int64_t N, int64_t H, int64_t E, float p_drop) {
     SGS_REQUIRE(N >= 0 && E >= 0 && N < (int64_t(1) << 31), SGS_EINVAL, "%s: bad sizes", who);
-    SGS_REQUIRE(H >= 4 && H <= 256 && H % 4 == 0, SGS_EINVAL, "%s: hidden size H=%lld unsupported (need 4 <= H <= 256, H %% 4 == 0)",
-                who, (long long)H);
+    SGS_REQUIRE(hidden_ok(H), SGS_EINVAL,
+                "%s: hidden size H=%lld unsupported (need 4 <= H <= 256 with H %% 4 == 0, or 256 < H <= 1024 with H %% 32 == 0)", who, (long long)H);
     SGS_REQUIRE(p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "%s: bad dropout probability", who);
     return SGS_OK;
 }
@@ -2211,6 +2496,11 @@ int sgs_edge_score_fwd(const float* codes, const float* U, int64_t N, int64_t H,
     a.drop_scale = 1.0f / (1.0f - p_drop); a.drop_thresh = dropout_thresh(p_drop); a.seed = seed; a.epoch = epoch_ptr(); a.site = site;
     a.use_drop = p_drop > 0.f; a.p_out = p_out;
     a.dyn_n = dyn_edges_ptr();
+    if (H > 256) {                                 // wide H: the chunked kernel (the variant switch selects among the H <= 256 kernels only)
+        SGS_REQUIRE(N > 0, SGS_EINVAL, "sgs_edge_score_fwd: edges without nodes");
+        hipLaunchKernelGGL(transpose_w1a, dim3(cdiv(H, 32), cdiv(H, 32)), dim3(kT), 0, stream, W1, static_cast<int>(H), WaT);
+        return launch_score_wide<false, false>(a, stream);
+    }
     int variant = g_score_variant;
     if (variant < 0) variant = (cdiv(E, kBM2) >= 512) ? (H % 128 == 0 ? 4 : 3) : 1;          // 512 = 2 resident workgroups x 256 CUs
     if (variant == 2 && a.dyn_n) variant = 3;      // the persistent kernel's tile queue is sized on the host
@@ -2291,7 +2581,33 @@ int sgs_edge_score_fwd(const float* codes, const float* U, int64_t N, int64_t H,
 }
 
 /* Paired forward (sgs_hip.h): only the `M` canonical edges run the H x H contraction; each also finishes its mate's score. */
-int sgs_edge_score_paired_supported(int64_t H) { return (H == 128 || H == 256) ? 1 : 0; }
+int sgs_edge_score_paired_supported(int64_t H) { return (H == 128 || H == 256 || (H > 256 && hidden_ok(H))) ? 1 : 0; }
+
+int sgs_edge_score_hidden_supported(int64_t H) { return hidden_ok(H) ? 1 : 0; }
+
+// 256 < H <= 1024: edge_score_wide_kernel<false, false, true> over the M canonical edges (WaT = the plain W1a^T)
+static int fwd_paired_wide(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
+                           int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
+                           const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, void* ws,
+                           size_t ws_bytes, hipStream_t stream) {
+    if (int rc = check_common("sgs_edge_score_fwd_paired", N, H, E, p_drop)) return rc;
+    SGS_REQUIRE(M >= 0 && M <= E, SGS_EINVAL, "sgs_edge_score_fwd_paired: bad canonical count");
+    if (E == 0 || M == 0) return SGS_OK;
+    SGS_REQUIRE(codes && U && edge_index && W1 && b1 && w2 && b2 && p_out && N > 0, SGS_EINVAL, "sgs_edge_score_fwd_paired: null pointer");
+    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(N, H, E), SGS_EWORKSPACE, "sgs_edge_score_fwd_paired: workspace too small");
+    Carver cv(ws);
+    float* WaT = cv.take<float>(static_cast<size_t>(H) * H);
+    ScoreArgs a{};
+    a.codes = codes; a.U = U; a.src = edge_index; a.dst = edge_index + E; a.active = nullptr; a.n = M; a.H = static_cast<int>(H);
+    a.row_offset = edge_id_offset;
+    a.WaT = WaT; a.b1 = b1; a.w2 = w2; a.b2 = b2;
+    a.drop_scale = 1.0f / (1.0f - p_drop); a.drop_thresh = dropout_thresh(p_drop); a.seed = seed; a.epoch = epoch_ptr(); a.site = site;
+    a.use_drop = p_drop > 0.f; a.p_out = p_out;
+    a.canon = canon; a.mate = mate;
+    a.dyn_n = dyn_edges_ptr() ? dyn_edges_ptr() + 1 : nullptr;   // word 1 of the registered dims: the live number of canonical edges
+    hipLaunchKernelGGL(transpose_w1a, dim3(cdiv(H, 32), cdiv(H, 32)), dim3(kT), 0, stream, W1, static_cast<int>(H), WaT);
+    return launch_score_wide<false, false, true>(a, stream);
+}
 
 static int fwd_bf16x6_impl(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
                            int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
@@ -2303,6 +2619,8 @@ int sgs_edge_score_fwd_paired(const float* codes, const float* U, int64_t N, int
                               const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, void* ws,
                               size_t ws_bytes, sgs_stream_t stream_) {
     SGS_REQUIRE((canon && mate) || E == 0 || M == 0, SGS_EINVAL, "sgs_edge_score_fwd_paired: null pointer");
+    if (H > 256) return fwd_paired_wide(codes, U, N, H, edge_index, E, edge_id_offset, canon, M, mate, W1, b1, w2, b2, p_drop, seed, site, p_out, ws,
+                                        ws_bytes, static_cast<hipStream_t>(stream_));
     return fwd_bf16x6_impl(codes, U, N, H, edge_index, E, edge_id_offset, canon, M, mate, W1, b1, w2, b2, p_drop, seed, site, p_out, nullptr, ws,
                            ws_bytes, stream_);
 }
@@ -2326,7 +2644,7 @@ static int fwd_bf16x6_impl(const float* codes, const float* U, int64_t N, int64_
                            void* ws, size_t ws_bytes, sgs_stream_t stream_, int P) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (int rc = check_common("sgs_edge_score_fwd_paired", N, H, E, p_drop)) return rc;
-    SGS_REQUIRE(sgs_edge_score_paired_supported(H), SGS_EINVAL, "sgs_edge_score_fwd_paired: H must be 128 or 256");
+    SGS_REQUIRE(H == 128 || H == 256, SGS_EINVAL, "sgs_edge_score_fwd_paired: H must be 128 or 256");   // the bf16x6 loop (wide H: fwd_paired_wide)
     SGS_REQUIRE(M >= 0 && M <= E, SGS_EINVAL, "sgs_edge_score_fwd_paired: bad canonical count");
     if (E == 0 || M == 0) return SGS_OK;
     SGS_REQUIRE(codes && U && edge_index && W1 && b1 && w2 && b2 && p_out && N > 0, SGS_EINVAL, "sgs_edge_score_fwd_paired: null pointer");
@@ -2463,6 +2781,17 @@ static int bwd_core_impl(const float* codes, const float* U, int64_t N, int64_t 
     Carver cv(ws);
     float* WaT = cv.take<float>(static_cast<size_t>(H) * H);
     float* Ceo = cv.take<float>(static_cast<size_t>(N) * H);
+    if (H > 256) {                     // wide H: the chunked core (the variant switch selects among the H <= 256 kernels only)
+        SGS_REQUIRE(dv && !dvbits && N > 0, SGS_EINVAL, "sgs_edge_score_bwd_core: H=%lld needs the dense dv form", (long long)H);
+        hipLaunchKernelGGL(transpose_w1a, dim3(cdiv(H, 32), cdiv(H, 32)), dim3(kT), 0, stream, W1, static_cast<int>(H), WaT);
+        ScoreArgs a{};
+        a.codes = codes; a.U = U; a.src = edge_index; a.dst = edge_index + E; a.active = active_eid; a.n = n_active;
+        a.row_offset = edge_id_offset;
+        a.H = static_cast<int>(H); a.WaT = WaT; a.b1 = b1; a.w2 = w2; a.b2 = b2;
+        a.drop_scale = 1.0f / (1.0f - p_drop); a.drop_thresh = dropout_thresh(p_drop); a.seed = seed; a.epoch = epoch_ptr(); a.site = site;
+        a.use_drop = p_drop > 0.f; a.gp = grad_p; a.dv = dv; a.hdz = hdz_part; a.dz = dz; a.feat = feat;
+        return launch_score_wide<true, false>(a, stream);
+    }
     // The 64-edge streaming loop is available for the backward core too (variant 3), but it is NOT the default: measured
     // (tools/bwd_probe.py) 323 / 656 / 1092 us against 227 / 558 / 997 us for the LDS-tiled core at 100 k / 262 k / 500 k active
     // rows.  The backward is bound by what it writes (dv and feat, 2 KB per row) and the tiled core produces the feature tile
@@ -2904,7 +3233,7 @@ int sgs_edge_score_epd_fwd(const float* A, int64_t N, int64_t H, const int64_t* 
     if (int rc = epd_args(a, "sgs_edge_score_epd_fwd", A, N, H, edge_index, E, edge_id_offset, W1, b1, w2, b2, p_hidden, seed, site, p_ep, seed_x, site_x,
                           seed_y, site_y, ws, ws_bytes, stream)) return rc;
     a.active = nullptr; a.n = E; a.p_out = p_out;
-    return launch_score<false, true>(a, stream);
+    return H > 256 ? launch_score_wide<false, true>(a, stream) : launch_score<false, true>(a, stream);
 }
 
 int sgs_edge_score_epd_bwd_core(const float* A, int64_t N, int64_t H, const int64_t* edge_index, int64_t E, int64_t edge_id_offset,
@@ -2920,7 +3249,7 @@ int sgs_edge_score_epd_bwd_core(const float* A, int64_t N, int64_t H, const int6
     if (int rc = epd_args(a, "sgs_edge_score_epd_bwd_core", A, N, H, edge_index, E, edge_id_offset, W1, b1, w2, b2, p_hidden, seed, site, p_ep, seed_x,
                           site_x, seed_y, site_y, ws, ws_bytes, stream)) return rc;
     a.active = active_eid; a.n = n_active; a.gp = grad_p; a.dv = dv; a.hdz = hdz_part; a.dz = dz; a.feat = feat2;
-    return launch_score<true, true>(a, stream);
+    return H > 256 ? launch_score_wide<true, true>(a, stream) : launch_score<true, true>(a, stream);
 }
 
 int sgs_edge_score_epd_reduce(const float* dfeat2, const float* A, int64_t N, int64_t H, const int32_t* in_ptr, const int32_t* in_src,
