@@ -667,6 +667,56 @@ int sgs_gather_by_eid(const float* by_eid, const int32_t* eid, int64_t n, float*
 int sgs_scatter_by_eid(const float* in_order, const int32_t* eid, int64_t n, float* by_eid, sgs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K8h: multi-head GATConv (PyG 2.3.1 semantics restated, 1 <= K <= 16 heads of C >= 1 channels; K = 1 callers keep the entry points
+ * above).  x' = lin_src(x) is [N, K C] with head-major columns (x'[i, h, c] at column h C + c), att_* are [K, C] flat.
+ * Layout: per-node arrays are [N, K]; per-edge arrays (soft, alpha, galpha, g_edge) are EDGE-MAJOR [n_edges, K], indexed by EDGE ID
+ * (v[eid * K + h]; a row's K values contiguous), so the dst-CSR and the src-CSR kernels read one array through their eid columns and
+ * no re-ordering launch exists.  Each kernel reads an entry's CSR indices once for all K heads.  No float atomics: every sum runs in
+ * CSR order over a fixed shuffle tree (run-to-run identical).  No host synchronisation, scratch from the caller: capturable.
+ * Any other (K, C) returns SGS_EINVAL with a message; sgs_gat_heads_supported is the host-only predicate (no GPU needed).
+ *   forward : sgs_gat_scores_heads_fwd -> sgs_gat_alpha_heads_fwd -> sgs_spmm_csr_heads (in-CSR; mode CONCAT or MEAN)
+ *   backward: sgs_spmm_csr_heads over the out-CSR (d x'), sgs_sddmm_csr_heads (galpha, gloop), sgs_gat_alpha_heads_bwd,
+ *             sgs_edge_sum_by_row_heads over the out-CSR (d a_src), sgs_gat_scores_heads_bwd
+ * Attention dropout is keyed (seed, site, row = edge id, col = head) for edges and (site + 1, row = node, col = head) for the loops:
+ * sgs_dropout_keep(seed, site, n_edges, K, p) / (seed, site + 1, N, K, p) export exactly the masks used, and column 0 at K = 1 is
+ * sgs_gat_alpha_fwd's mask.
+ * ---------------------------------------------------------------------------------- */
+#define SGS_HEADS_CONCAT 0    /* X [N, K C] -> Y [N, K C], per-head weights */
+#define SGS_HEADS_MEAN 1      /* X [N, K C] -> Y [N, C] = mean over heads (GATConv concat = False), fused into the aggregation */
+#define SGS_HEADS_BROADCAST 2 /* X [N, C] shared by the heads -> Y [N, K C] / K: the transposed aggregation behind MEAN's backward */
+int sgs_gat_heads_supported(int64_t K, int64_t C);
+/* a_src[i, h] = <x'[i, h, :], att_src[h, :]>, a_dst likewise, one pass over x'.  Backward as sgs_gat_scores_bwd with g_src / g_dst [N, K]
+ * and d att_* [K, C]; ws: sgs_gat_scores_heads_bwd_workspace_bytes(N, K, C). */
+int sgs_gat_scores_heads_fwd(const float* xl, int64_t N, int64_t K, int64_t C, const float* att_src, const float* att_dst, float* a_src,
+                             float* a_dst, sgs_stream_t stream);
+size_t sgs_gat_scores_heads_bwd_workspace_bytes(int64_t N, int64_t K, int64_t C);
+int sgs_gat_scores_heads_bwd(const float* xl, int64_t N, int64_t K, int64_t C, const float* att_src, const float* att_dst, const float* g_src,
+                             const float* g_dst, int accumulate, float* dxl, float* datt_src, float* datt_dst, void* ws, size_t ws_bytes,
+                             sgs_stream_t stream);
+/* Segment softmax (+ attention dropout) per (destination, head) over the dst-CSR and its backward; formulas of sgs_gat_alpha_fwd / _bwd.
+ * soft / alpha / galpha / g_edge [n_edges, K] by edge id ((i, i) entries get 0), *_loop / g_selfloop / d_a_dst [N, K]. */
+int sgs_gat_alpha_heads_fwd(const float* a_src, const float* a_dst, int64_t N, int64_t K, int64_t n_edges, const int32_t* in_ptr,
+                            const int32_t* in_src, const int32_t* in_eid, float negative_slope, float p_drop, uint64_t seed, uint32_t site,
+                            float* soft, float* soft_loop, float* alpha, float* alpha_loop, sgs_stream_t stream);
+int sgs_gat_alpha_heads_bwd(const float* a_src, const float* a_dst, int64_t N, int64_t K, int64_t n_edges, const int32_t* in_ptr,
+                            const int32_t* in_src, const int32_t* in_eid, float negative_slope, float p_drop, uint64_t seed, uint32_t site,
+                            const float* soft, const float* soft_loop, const float* galpha, const float* gloop, float* g_edge, float* g_selfloop,
+                            float* d_a_dst, sgs_stream_t stream);
+/* out[j, h] = sum over row j of the CSR (ptr, eid) of g_edge[eid_k, h] (+ g_self[j, h] unless NULL), in CSR order: d a_src over the out-CSR. */
+int sgs_edge_sum_by_row_heads(const float* g_edge, const float* g_self, int64_t N, int64_t K, int64_t nnz, const int32_t* ptr, const int32_t* eid,
+                              float* out, sgs_stream_t stream);
+/* Per-head SpMM: Y[i, h C + c] = sum_k val[eid_k, h] X[col_k, h C + c] + diag[i, h] X[i, h C + c] (diag may be NULL), then bias / act /
+ * dropout exactly as sgs_spmm_csr (bias over Y's columns; dropout keyed (site, row i, Y column)).  mode: SGS_HEADS_*.  Rows are 16-byte
+ * vectorised when C % 4 == 0 (a lane's columns then belong to one head); any other C runs column by column. */
+int sgs_spmm_csr_heads(const float* X, int64_t N, int64_t K, int64_t C, int64_t nnz, const int32_t* ptr, const int32_t* col, const int32_t* eid,
+                       const float* val, const float* diag, int mode, const float* bias, int act, float p_drop, uint64_t seed, uint32_t site,
+                       float* Y, sgs_stream_t stream);
+/* Per-head SDDMM: g[eid_k, h] = <A[i, h, :], B[col_k, h, :]> for k in row i, gdiag[i, h] = <A[i, h, :], B[i, h, :]>; A, B [N, K C].
+ * broadcast != 0: A is [N, C], shared by the heads, and the products are scaled by 1 / K (backward of SGS_HEADS_MEAN). */
+int sgs_sddmm_csr_heads(const float* A, const float* B, int64_t N, int64_t K, int64_t C, int64_t nnz, const int32_t* ptr, const int32_t* col,
+                        const int32_t* eid, int broadcast, float* g, float* gdiag, sgs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Weight-gradient GEMM of the node-level Linear layers: C[M,N] = A^T B, A [K,M], B [K,N] row-major,
  * K = number of graph nodes (dW = dY^T X for GCNConv.lin, model.py:94-95,151-153).  fp32 MFMA fed from
  * coalesced global reads, split-K with a fixed-order combine (deterministic).  Skinny shapes only (the

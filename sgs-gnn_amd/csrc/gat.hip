@@ -1,4 +1,5 @@
-// K8: GAT attention (PyG 2.3.1 GATConv, heads = 1) over the dst-sorted CSR (gfx950).
+// K8: GAT attention (PyG 2.3.1 GATConv) over the dst-sorted CSR (gfx950): the one-head kernels first (what the reference's GATModel runs),
+// the fused multi-head ones (2 <= heads <= 16; their own SpMM / SDDMM, since the weights are per head) in the second half of the file.
 //
 // Reference: model.py:189-208 builds torch_geometric.nn.models.GAT(num_layers=2, act='relu',
 // dropout=p); each GATConv layer is
@@ -10,6 +11,8 @@
 // The aggregation itself reuses sgs_spmm_csr (val = alpha, diag = loop alpha); this file holds the
 // segment softmax and its backward.  One wave per destination node; rows are walked three times
 // (max, sum, normalise) from L2.
+#include <type_traits>
+
 #include "sgs_common.h"
 
 namespace sgs {
@@ -252,6 +255,461 @@ __global__ void __launch_bounds__(1024) gat_scores_bwd_finish(const float* __res
     }
 }
 
+
+// =====================================================================================================================
+// Multi-head GATConv (1 <= K <= 16 heads of C channels; x' is [N, K C] with head-major columns).  heads = 1 keeps the kernels above.
+//
+// Per-edge arrays are EDGE-MAJOR and indexed by EDGE ID: v[eid * K + h] (a row's K weights are contiguous: 32 B at K = 8), per-node
+// arrays are [N, K].  Keeping them by edge id means the forward aggregation (dst-CSR), the transposed one (src-CSR) and the softmax
+// backward all address the same array through their CSR's eid column, so the one-head path's scatter / gather re-orderings between
+// entry orders do not exist here.
+//
+// Lane layout of the per-row kernels (softmax forward / backward, by-source sum): one wave per row, KP = K rounded up to a power of
+// two, lane = sub * KP + h: 64 / KP entries of the row per step, each entry's CSR indices loaded once (one address for the KP lanes
+// of an entry: a broadcast) and its K values by K adjacent lanes.  Reductions over a head are xor-shuffles over the lane bits above
+// KP, a fixed tree: no float atomics anywhere, results are run-to-run identical.  Lanes with h >= K (K not a power of two) read
+// head 0 and store nothing.
+constexpr int kMaxHeads = 16;
+
+template <int KP>
+__device__ __forceinline__ float head_sum_all(float v) {
+#pragma unroll
+    for (int o = 32; o >= KP; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+template <int KP>
+__device__ __forceinline__ float head_max_all(float v) {
+#pragma unroll
+    for (int o = 32; o >= KP; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// soft / alpha [n, K] by edge id (0 for (i, i) entries), soft_loop / alpha_loop [N, K].  Attention dropout is keyed (site, row = edge id,
+// col = head) and (site + 1, row = node, col = head): sgs_dropout_keep(seed, site, E, K, p) is the mask used, column 0 at K = 1 the
+// one-head kernel's.
+template <int KP>
+__global__ void __launch_bounds__(kT) gat_alpha_heads_fwd(const float* __restrict__ a_s, const float* __restrict__ a_d, int64_t N, int K,
+                                                         const int* __restrict__ in_ptr, const int* __restrict__ in_src,
+                                                         const int* __restrict__ in_eid, float slope, float drop_scale, uint32_t drop_thresh,
+                                                         int use_drop, uint64_t seed, uint32_t site, const uint64_t* __restrict__ epoch,
+                                                         float* __restrict__ soft, float* __restrict__ soft_loop, float* __restrict__ alpha,
+                                                         float* __restrict__ alpha_loop) {
+    constexpr int EPW = 64 / KP;
+    seed = fold_epoch(seed, epoch);
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    if (i >= N) return;                                       // wave-uniform
+    const int h = lane & (KP - 1), sub = lane / KP;
+    const bool hv = h < K;
+    const int hc = hv ? h : 0;
+    const int b = in_ptr[i], e = in_ptr[i + 1];
+    const float ad = a_d[i * K + hc];
+    const float eloop = lrelu(a_s[i * K + hc] + ad, slope);
+    float mx = eloop;
+    for (int k = b + sub; k < e; k += EPW) {
+        const int s = in_src[k];
+        if (s != static_cast<int>(i)) mx = fmaxf(mx, lrelu(a_s[static_cast<int64_t>(s) * K + hc] + ad, slope));
+    }
+    mx = head_max_all<KP>(mx);
+    float sum = 0.f;
+    for (int k = b + sub; k < e; k += EPW) {
+        const int s = in_src[k];
+        if (s != static_cast<int>(i)) sum += expf(lrelu(a_s[static_cast<int64_t>(s) * K + hc] + ad, slope) - mx);
+    }
+    sum = head_sum_all<KP>(sum) + expf(eloop - mx);
+    const float inv = 1.0f / (sum + 1e-16f);                  // torch_geometric.utils.softmax: / (sum + 1e-16)
+    for (int k = b + sub; k < e; k += EPW) {
+        const int s = in_src[k];
+        const int64_t ed = in_eid[k];
+        float sm = 0.f, al = 0.f;
+        if (s != static_cast<int>(i)) {
+            sm = expf(lrelu(a_s[static_cast<int64_t>(s) * K + hc] + ad, slope) - mx) * inv;
+            al = sm;
+            if (use_drop) al = dropout_keep_at(seed, site, static_cast<uint64_t>(ed), static_cast<uint32_t>(hc), drop_thresh) ? sm * drop_scale : 0.f;
+        }
+        if (hv) {
+            soft[ed * K + h] = sm;
+            alpha[ed * K + h] = al;
+        }
+    }
+    if (sub == 0 && hv) {
+        const float sm = expf(eloop - mx) * inv;
+        float al = sm;
+        if (use_drop) al = dropout_keep_at(seed, site + 1u, static_cast<uint64_t>(i), static_cast<uint32_t>(h), drop_thresh) ? sm * drop_scale : 0.f;
+        soft_loop[i * K + h] = sm;
+        alpha_loop[i * K + h] = al;
+    }
+}
+
+// Backward of dropout + softmax + leaky_relu per (destination row, head); the formulas of gat_alpha_bwd above with galpha / soft / ge [n, K]
+// by edge id and gloop / soft_loop / gsl / d_ad [N, K].
+template <int KP>
+__global__ void __launch_bounds__(kT) gat_alpha_heads_bwd(const float* __restrict__ a_s, const float* __restrict__ a_d, int64_t N, int K,
+                                                         const int* __restrict__ in_ptr, const int* __restrict__ in_src,
+                                                         const int* __restrict__ in_eid, float slope, float drop_scale, uint32_t drop_thresh,
+                                                         int use_drop, uint64_t seed, uint32_t site, const uint64_t* __restrict__ epoch,
+                                                         const float* __restrict__ soft, const float* __restrict__ soft_loop,
+                                                         const float* __restrict__ galpha, const float* __restrict__ gloop,
+                                                         float* __restrict__ ge, float* __restrict__ gsl, float* __restrict__ d_ad) {
+    constexpr int EPW = 64 / KP;
+    seed = fold_epoch(seed, epoch);
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    if (i >= N) return;
+    const int h = lane & (KP - 1), sub = lane / KP;
+    const bool hv = h < K;
+    const int hc = hv ? h : 0;
+    const int b = in_ptr[i], e = in_ptr[i + 1];
+    const float ad = a_d[i * K + hc];
+    auto dsm_edge = [&](int64_t ed) {
+        float g = galpha[ed * K + hc];
+        if (use_drop) g = dropout_keep_at(seed, site, static_cast<uint64_t>(ed), static_cast<uint32_t>(hc), drop_thresh) ? g * drop_scale : 0.f;
+        return g;
+    };
+    float gl = gloop[i * K + hc];
+    if (use_drop) gl = dropout_keep_at(seed, site + 1u, static_cast<uint64_t>(i), static_cast<uint32_t>(hc), drop_thresh) ? gl * drop_scale : 0.f;
+    const float sl = soft_loop[i * K + hc];
+    float dot = 0.f;
+    for (int k = b + sub; k < e; k += EPW)
+        if (in_src[k] != static_cast<int>(i)) {
+            const int64_t ed = in_eid[k];
+            dot += soft[ed * K + hc] * dsm_edge(ed);
+        }
+    dot = head_sum_all<KP>(dot) + sl * gl;
+    float dad = 0.f;
+    for (int k = b + sub; k < e; k += EPW) {
+        const int s = in_src[k];
+        const int64_t ed = in_eid[k];
+        float dpre = 0.f;
+        if (s != static_cast<int>(i)) {
+            const float pre = a_s[static_cast<int64_t>(s) * K + hc] + ad;
+            dpre = soft[ed * K + hc] * (dsm_edge(ed) - dot) * (pre > 0.f ? 1.f : slope);
+        }
+        if (hv) ge[ed * K + h] = dpre;
+        dad += dpre;
+    }
+    dad = head_sum_all<KP>(dad);
+    if (sub == 0 && hv) {
+        const float pre = a_s[i * K + h] + ad;
+        const float dl = sl * (gl - dot) * (pre > 0.f ? 1.f : slope);
+        gsl[i * K + h] = dl;
+        d_ad[i * K + h] = dad + dl;
+    }
+}
+
+// out[j, h] = sum over j's out-edges (src-CSR order) of ge[eid, h] + gsl[j, h]: d a_src of the layer (the one-head path runs an SpMM
+// over a column of ones for this, after a gather into src-CSR order).
+template <int KP>
+__global__ void __launch_bounds__(kT) edge_sum_by_row_heads(const float* __restrict__ ge, const float* __restrict__ gsl, int64_t N, int K,
+                                                           const int* __restrict__ ptr, const int* __restrict__ eid, float* __restrict__ out) {
+    constexpr int EPW = 64 / KP;
+    const int lane = threadIdx.x & 63;
+    const int64_t j = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    if (j >= N) return;
+    const int h = lane & (KP - 1), sub = lane / KP;
+    const bool hv = h < K;
+    const int hc = hv ? h : 0;
+    const int b = ptr[j], e = ptr[j + 1];
+    float acc = 0.f;
+    for (int k = b + sub; k < e; k += EPW) acc += ge[static_cast<int64_t>(eid[k]) * K + hc];
+    acc = head_sum_all<KP>(acc);
+    if (sub == 0 && hv) out[j * K + h] = acc + (gsl ? gsl[j * K + h] : 0.f);
+}
+
+// Node scores for K heads in one pass over x': x' viewed as [N K, C] (head-major columns make a (node, head) slice contiguous), unit
+// u = i K + h owned by G = 2^lg lanes (VEC floats per lane and step): a_s[u] = <x'[u, :], att_s[h, :]>, a_d likewise.
+template <int VEC>
+__global__ void __launch_bounds__(kT) gat_scores_heads_fwd(const float* __restrict__ xl, int64_t NU, int K, int64_t C,
+                                                          const float* __restrict__ att_s, const float* __restrict__ att_d,
+                                                          float* __restrict__ a_s, float* __restrict__ a_d, int lg) {
+    using V = typename std::conditional<VEC == 4, float4, float>::type;
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+    const int G = 1 << lg;
+    const int64_t u = t >> lg;
+    const int g = static_cast<int>(t & (G - 1));
+    const bool live = u < NU;                                 // every lane stays for the shuffles
+    float s = 0.f, d = 0.f;
+    if (live) {
+        const int h = static_cast<int>(u % K);
+        const float* x = xl + u * C;
+        const float* us = att_s + h * C;
+        const float* ud = att_d + h * C;
+        for (int64_t c = static_cast<int64_t>(g) * VEC; c < C; c += static_cast<int64_t>(G) * VEC) {
+            float xv[VEC], sv[VEC], dv[VEC];
+            *reinterpret_cast<V*>(xv) = *reinterpret_cast<const V*>(x + c);
+            *reinterpret_cast<V*>(sv) = *reinterpret_cast<const V*>(us + c);
+            *reinterpret_cast<V*>(dv) = *reinterpret_cast<const V*>(ud + c);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) { s = fmaf(xv[v], sv[v], s); d = fmaf(xv[v], dv[v], d); }
+        }
+    }
+    for (int o = G >> 1; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); d += __shfl_xor(d, o, 64); }
+    if (live && g == 0) { a_s[u] = s; a_d[u] = d; }
+}
+
+// backward of the above, gat_scores_bwd's scheme over D = K C columns: thread owns column j = h C + c, dxl[i, j] (+)= g_s[i, h] att_s[j] +
+// g_d[i, h] att_d[j]; per-workgroup partials of d att (flat [K C]) finished by gat_scores_bwd_finish in a fixed order.
+template <bool ACC>
+__global__ void __launch_bounds__(kT) gat_scores_heads_bwd(const float* __restrict__ xl, int64_t N, int K, int64_t C,
+                                                          const float* __restrict__ att_s, const float* __restrict__ att_d,
+                                                          const float* __restrict__ g_s, const float* __restrict__ g_d, float* __restrict__ dxl,
+                                                          float* __restrict__ part, int rows_per_wg) {
+    const int64_t D = static_cast<int64_t>(K) * C;
+    const int64_t r0 = static_cast<int64_t>(blockIdx.x) * rows_per_wg;
+    const int64_t r1 = r0 + rows_per_wg < N ? r0 + rows_per_wg : N;
+    for (int64_t cb = 0; cb < D; cb += kT) {
+        const int64_t c = cb + threadIdx.x;
+        const bool in = c < D;
+        const int h = in ? static_cast<int>(c / C) : 0;
+        const float us = in ? att_s[c] : 0.f, ud = in ? att_d[c] : 0.f;
+        float ps = 0.f, pd = 0.f;
+        if (in) {
+            for (int64_t i = r0; i < r1; ++i) {
+                const float gs = g_s[i * K + h], gd = g_d[i * K + h];
+                const float x = xl[i * D + c];
+                ps = fmaf(gs, x, ps);
+                pd = fmaf(gd, x, pd);
+                const float v = fmaf(gs, us, gd * ud);
+                dxl[i * D + c] = ACC ? dxl[i * D + c] + v : v;
+            }
+            part[(static_cast<int64_t>(blockIdx.x) * 2) * D + c] = ps;
+            part[(static_cast<int64_t>(blockIdx.x) * 2 + 1) * D + c] = pd;
+        }
+    }
+}
+
+// acc[0 .. VEC) = sum_k val[eid_k, h] X[col_k, xc ..] + diag[i, h] X[i, xc ..] over row i = [b, e) of the CSR, entries in order
+template <int VEC>
+__device__ __forceinline__ void spmm_heads_acc(const float* __restrict__ X, int64_t XD, int64_t xc, int K, int h, int64_t i, int b, int e,
+                                               const int* __restrict__ col, const int* __restrict__ eid, const float* __restrict__ val,
+                                               const float* __restrict__ diag, float (&acc)[VEC]) {
+    using V = typename std::conditional<VEC == 4, float4, float>::type;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+    int k = b;
+    for (; k + 4 <= e; k += 4) {          // 4 independent row gathers in flight
+        int j[4]; float w[4]; float x[4][VEC];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { j[u] = col[k + u]; w[u] = val[static_cast<int64_t>(eid[k + u]) * K + h]; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) *reinterpret_cast<V*>(x[u]) = *reinterpret_cast<const V*>(X + static_cast<int64_t>(j[u]) * XD + xc);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
+    }
+    for (; k < e; ++k) {
+        float x[VEC];
+        *reinterpret_cast<V*>(x) = *reinterpret_cast<const V*>(X + static_cast<int64_t>(col[k]) * XD + xc);
+        const float w = val[static_cast<int64_t>(eid[k]) * K + h];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, x[v], acc[v]);
+    }
+    if (diag) {
+        float x[VEC];
+        *reinterpret_cast<V*>(x) = *reinterpret_cast<const V*>(X + i * XD + xc);
+        const float w = diag[i * K + h];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, x[v], acc[v]);
+    }
+}
+
+// Per-head CSR SpMM, output [N, K C]:  Y[i, h C + c] = sum_k val[eid_k, h] X[col_k, h C + c] + diag[i, h] X[i, h C + c], then the bias / ReLU /
+// dropout epilogue of spmm_csr.  LPR = 2^lg lanes own a row, VEC consecutive columns each (VEC = 4 only when C % 4 == 0, so a lane's
+// columns belong to one head; with VEC = 1 any C is correct): at K C = 256 a wave gathers the same 1 KB row as the one-head layer and
+// the K weights of an entry arrive as one 4 K-byte read.  BCAST (backward of the head mean): X is [N, C], shared by the heads, and the
+// result is scaled by 1 / K:  Y[i, h C + c] = (1 / K) (sum_k val[eid_k, h] X[col_k, c] + diag[i, h] X[i, c]).
+template <int VEC, bool BCAST>
+__global__ void __launch_bounds__(kT) spmm_csr_heads(const float* __restrict__ X, int64_t N, int K, int64_t C, const int* __restrict__ ptr,
+                                                    const int* __restrict__ col, const int* __restrict__ eid, const float* __restrict__ val,
+                                                    const float* __restrict__ diag, const float* __restrict__ bias, int act, float drop_scale,
+                                                    uint32_t drop_thresh, uint64_t seed, uint32_t site, const uint64_t* __restrict__ epoch,
+                                                    float* __restrict__ Y, int lg) {
+    using V = typename std::conditional<VEC == 4, float4, float>::type;
+    seed = fold_epoch(seed, epoch);
+    const int LPR = 1 << lg;
+    const int sub = threadIdx.x & (LPR - 1);
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * (kT >> lg) + (threadIdx.x >> lg);
+    if (i >= N) return;
+    const int64_t D = static_cast<int64_t>(K) * C;
+    const int64_t XD = BCAST ? C : D;
+    const float post = BCAST ? 1.0f / static_cast<float>(K) : 1.0f;
+    const int b = ptr[i], e = ptr[i + 1];
+    for (int64_t c0 = static_cast<int64_t>(sub) * VEC; c0 < D; c0 += static_cast<int64_t>(LPR) * VEC) {
+        const int h = static_cast<int>(c0 / C);
+        const int64_t xc = BCAST ? c0 - h * C : c0;
+        float acc[VEC];
+        spmm_heads_acc<VEC>(X, XD, xc, K, h, i, b, e, col, eid, val, diag, acc);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            float y = BCAST ? acc[v] * post : acc[v];
+            if (bias) y += bias[c0 + v];
+            if (act != SGS_ACT_NONE) y = fmaxf(y, 0.f);
+            if (act == SGS_ACT_RELU_DROPOUT)
+                y = dropout_keep_at(seed, site, static_cast<uint64_t>(i), static_cast<uint32_t>(c0 + v), drop_thresh) ? y * drop_scale : 0.f;
+            acc[v] = y;
+        }
+        *reinterpret_cast<V*>(Y + i * D + c0) = *reinterpret_cast<V*>(acc);
+    }
+}
+
+// The head-mean form (GATConv concat = False), fused: Y[i, c] = (1 / K) sum_h (sum_k val[eid_k, h] X[col_k, h C + c] + diag[i, h] X[i, h C + c])
+// + bias[c].  A lane owns VEC output columns and walks the K heads of each gathered row itself (heads in order 0 .. K - 1 per entry, entries
+// in CSR order), so the [N, K C] per-head result is never written and no second launch averages it.
+template <int VEC>
+__global__ void __launch_bounds__(kT) spmm_csr_heads_mean(const float* __restrict__ X, int64_t N, int K, int64_t C, const int* __restrict__ ptr,
+                                                         const int* __restrict__ col, const int* __restrict__ eid, const float* __restrict__ val,
+                                                         const float* __restrict__ diag, const float* __restrict__ bias, int act, float drop_scale,
+                                                         uint32_t drop_thresh, uint64_t seed, uint32_t site, const uint64_t* __restrict__ epoch,
+                                                         float* __restrict__ Y, int lg) {
+    using V = typename std::conditional<VEC == 4, float4, float>::type;
+    seed = fold_epoch(seed, epoch);
+    const int LPR = 1 << lg;
+    const int sub = threadIdx.x & (LPR - 1);
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * (kT >> lg) + (threadIdx.x >> lg);
+    if (i >= N) return;
+    const int64_t D = static_cast<int64_t>(K) * C;
+    const float invK = 1.0f / static_cast<float>(K);
+    const int b = ptr[i], e = ptr[i + 1];
+    for (int64_t c0 = static_cast<int64_t>(sub) * VEC; c0 < C; c0 += static_cast<int64_t>(LPR) * VEC) {
+        float acc[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+        for (int k = b; k <= e; ++k) {                        // k == e: the loop term
+            const bool loop = k == e;
+            if (loop && !diag) break;
+            const float* xr = X + (loop ? i : static_cast<int64_t>(col[k])) * D + c0;
+            const float* wr = loop ? diag + i * K : val + static_cast<int64_t>(eid[k]) * K;
+            for (int h = 0; h < K; ++h) {
+                float x[VEC];
+                *reinterpret_cast<V*>(x) = *reinterpret_cast<const V*>(xr + h * C);
+                const float w = wr[h];
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, x[v], acc[v]);
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            float y = acc[v] * invK;
+            if (bias) y += bias[c0 + v];
+            if (act != SGS_ACT_NONE) y = fmaxf(y, 0.f);
+            if (act == SGS_ACT_RELU_DROPOUT)
+                y = dropout_keep_at(seed, site, static_cast<uint64_t>(i), static_cast<uint32_t>(c0 + v), drop_thresh) ? y * drop_scale : 0.f;
+            acc[v] = y;
+        }
+        *reinterpret_cast<V*>(Y + i * C + c0) = *reinterpret_cast<V*>(acc);
+    }
+}
+
+// The same head mean with the concat kernel's lane layout (a lane owns VEC columns of the [K C] per-head row, so a wave gathers whole rows and
+// long rows are walked with four gathers in flight): the per-head sums go to LDS ([rows of the workgroup][K C] floats, at most 16 KB) and
+// lanes c < C add the K heads of column c in order 0 .. K - 1.  Used when K C rows fit (kMeanLdsFloats); the kernel above walks the heads in
+// each lane with C / VEC lanes per row and was 6x slower at K = 8, C = 5 on a power-law graph, where 8 lanes served a hub row alone.
+constexpr int kMeanLdsFloats = 4096;
+template <int VEC>
+__global__ void __launch_bounds__(kT) spmm_csr_heads_mean_lds(const float* __restrict__ X, int64_t N, int K, int64_t C, const int* __restrict__ ptr,
+                                                             const int* __restrict__ col, const int* __restrict__ eid, const float* __restrict__ val,
+                                                             const float* __restrict__ diag, const float* __restrict__ bias, int act, float drop_scale,
+                                                             uint32_t drop_thresh, uint64_t seed, uint32_t site, const uint64_t* __restrict__ epoch,
+                                                             float* __restrict__ Y, int lg) {
+    __shared__ float part[kMeanLdsFloats];
+    seed = fold_epoch(seed, epoch);
+    const int LPR = 1 << lg;
+    const int sub = threadIdx.x & (LPR - 1), r = threadIdx.x >> lg;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * (kT >> lg) + r;
+    const bool live = i < N;                                  // every thread reaches the barrier
+    const int64_t D = static_cast<int64_t>(K) * C;
+    float* mine = part + r * D;
+    if (live) {
+        const int b = ptr[i], e = ptr[i + 1];
+        for (int64_t c0 = static_cast<int64_t>(sub) * VEC; c0 < D; c0 += static_cast<int64_t>(LPR) * VEC) {
+            const int h = static_cast<int>(c0 / C);
+            float acc[VEC];
+            spmm_heads_acc<VEC>(X, D, c0, K, h, i, b, e, col, eid, val, diag, acc);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) mine[c0 + v] = acc[v];
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    const float invK = 1.0f / static_cast<float>(K);
+    for (int64_t c = sub; c < C; c += LPR) {
+        float y = 0.f;
+        for (int h = 0; h < K; ++h) y += mine[h * C + c];
+        y *= invK;
+        if (bias) y += bias[c];
+        if (act != SGS_ACT_NONE) y = fmaxf(y, 0.f);
+        if (act == SGS_ACT_RELU_DROPOUT)
+            y = dropout_keep_at(seed, site, static_cast<uint64_t>(i), static_cast<uint32_t>(c), drop_thresh) ? y * drop_scale : 0.f;
+        Y[i * C + c] = y;
+    }
+}
+
+// Per-head SDDMM over the CSR: g[eid_k, h] = <A[i, h, :], B[col_k, h, :]>, gdiag[i, h] = <A[i, h, :], B[i, h, :]>.  LPR = KP G lanes per row:
+// lane (h, g) walks columns g VEC, (g + G) VEC, ... of head h's slice and the G lanes of a head are summed by xor-shuffles.  BCAST: A is
+// [N, C], shared by the heads, and the products are scaled by 1 / K (the head mean's backward).
+template <int VEC, bool BCAST>
+__global__ void __launch_bounds__(kT) sddmm_csr_heads(const float* __restrict__ A, const float* __restrict__ B, int64_t N, int K, int64_t C,
+                                                     const int* __restrict__ ptr, const int* __restrict__ col, const int* __restrict__ eid,
+                                                     float* __restrict__ g, float* __restrict__ gdiag, int lg, int lgG) {
+    using V = typename std::conditional<VEC == 4, float4, float>::type;
+    const int LPR = 1 << lg, G = 1 << lgG;
+    const int sub = threadIdx.x & (LPR - 1);
+    const int h = sub >> lgG, gl = sub & (G - 1);
+    const bool hv = h < K;
+    const int hc = hv ? h : 0;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * (kT >> lg) + (threadIdx.x >> lg);
+    const bool live = i < N;            // keep every lane in the shuffles
+    const int64_t D = static_cast<int64_t>(K) * C;
+    const float post = BCAST ? 1.0f / static_cast<float>(K) : 1.0f;
+    const int b = live ? ptr[i] : 0, e = live ? ptr[i + 1] : 0;
+    const float* Ai = A + (live ? i : 0) * (BCAST ? C : D) + (BCAST ? 0 : hc * C);
+    int trips = e - b + 1;             // +1: the loop term; made wave-uniform, dead lanes contribute 0
+    for (int o = 32; o > 0; o >>= 1) trips = max(trips, __shfl_xor(trips, o, 64));
+    for (int t = 0; t < trips; ++t) {
+        const int k = b + t;
+        const bool is_edge = live && k < e;
+        const bool is_diag = live && k == e;
+        const int64_t j = is_edge ? col[k] : i;
+        float acc = 0.f;
+        if (is_edge || is_diag) {
+            const float* Bj = B + j * D + hc * C;
+            for (int64_t c0 = static_cast<int64_t>(gl) * VEC; c0 < C; c0 += static_cast<int64_t>(G) * VEC) {
+                float a[VEC], x[VEC];
+                *reinterpret_cast<V*>(a) = *reinterpret_cast<const V*>(Ai + c0);
+                *reinterpret_cast<V*>(x) = *reinterpret_cast<const V*>(Bj + c0);
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc = fmaf(a[v], x[v], acc);
+            }
+        }
+        for (int o = G >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if (gl == 0 && hv) {
+            if (is_edge) g[static_cast<int64_t>(eid[k]) * K + h] = acc * post;
+            else if (is_diag) gdiag[i * K + h] = acc * post;
+        }
+    }
+}
+
+inline int log2_ceil(int64_t v) {
+    int l = 0;
+    while ((int64_t(1) << l) < v) ++l;
+    return l;
+}
+inline bool heads_ok(int64_t K, int64_t C) { return K >= 1 && K <= kMaxHeads && C >= 1 && C <= (int64_t(1) << 24); }
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// KP = K rounded up to a power of two selects the per-row kernels' instantiation
+#define SGS_DISPATCH_KP(KERNEL, K, GRID, STREAM, ...)                                                                   \
+    do {                                                                                                                \
+        switch (log2_ceil(K)) {                                                                                         \
+            case 0: hipLaunchKernelGGL((KERNEL<1>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                     \
+            case 1: hipLaunchKernelGGL((KERNEL<2>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                     \
+            case 2: hipLaunchKernelGGL((KERNEL<4>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                     \
+            case 3: hipLaunchKernelGGL((KERNEL<8>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                     \
+            default: hipLaunchKernelGGL((KERNEL<16>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                   \
+        }                                                                                                               \
+    } while (0)
+
 }  // namespace
 }  // namespace sgs
 
@@ -358,6 +816,182 @@ int sgs_gat_scores_bwd(const float* xl, int64_t N, int64_t D, const float* att_s
     else
         hipLaunchKernelGGL((gat_scores_bwd<false>), dim3(nwg), dim3(kT), 0, stream, xl, N, D, att_src, att_dst, g_src, g_dst, dxl, part, rp);
     hipLaunchKernelGGL(gat_scores_bwd_finish, dim3(static_cast<unsigned>((2 * D + 63) / 64)), dim3(1024), 0, stream, part, nwg, D, datt_src, datt_dst);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+
+// ---------------------------------------------------------------- multi-head entry points
+int sgs_gat_heads_supported(int64_t K, int64_t C) { return heads_ok(K, C) ? 1 : 0; }
+
+#define SGS_REQUIRE_HEADS(name)                                                                                         \
+    SGS_REQUIRE(heads_ok(K, C), SGS_EINVAL, name ": unsupported heads = %lld x channels = %lld (1 <= heads <= 16, channels >= 1)", \
+                static_cast<long long>(K), static_cast<long long>(C))
+
+int sgs_gat_scores_heads_fwd(const float* xl, int64_t N, int64_t K, int64_t C, const float* att_src, const float* att_dst, float* a_src,
+                             float* a_dst, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE_HEADS("sgs_gat_scores_heads_fwd");
+    SGS_REQUIRE(N >= 0 && N * K * 64 < (int64_t(1) << 40), SGS_EINVAL, "sgs_gat_scores_heads_fwd: bad sizes");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(xl && att_src && att_dst && a_src && a_dst, SGS_EINVAL, "sgs_gat_scores_heads_fwd: null pointer");
+    const int vec = (C % 4 == 0 && al16(xl) && al16(att_src) && al16(att_dst)) ? 4 : 1;
+    int lg = log2_ceil(cdiv(C, vec));
+    if (lg > 6) lg = 6;
+    const dim3 grid(static_cast<unsigned>(cdiv((N * K) << lg, kT)));
+    if (vec == 4)
+        hipLaunchKernelGGL((gat_scores_heads_fwd<4>), grid, dim3(kT), 0, stream, xl, N * K, static_cast<int>(K), C, att_src, att_dst, a_src, a_dst, lg);
+    else
+        hipLaunchKernelGGL((gat_scores_heads_fwd<1>), grid, dim3(kT), 0, stream, xl, N * K, static_cast<int>(K), C, att_src, att_dst, a_src, a_dst, lg);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+size_t sgs_gat_scores_heads_bwd_workspace_bytes(int64_t N, int64_t K, int64_t C) {
+    if (K < 0) K = 0;
+    if (C < 0) C = 0;
+    return sgs_gat_scores_bwd_workspace_bytes(N, K * C);
+}
+
+int sgs_gat_scores_heads_bwd(const float* xl, int64_t N, int64_t K, int64_t C, const float* att_src, const float* att_dst, const float* g_src,
+                             const float* g_dst, int accumulate, float* dxl, float* datt_src, float* datt_dst, void* ws, size_t ws_bytes,
+                             sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE_HEADS("sgs_gat_scores_heads_bwd");
+    SGS_REQUIRE(N >= 0, SGS_EINVAL, "sgs_gat_scores_heads_bwd: bad sizes");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(xl && att_src && att_dst && g_src && g_dst && dxl && datt_src && datt_dst, SGS_EINVAL, "sgs_gat_scores_heads_bwd: null pointer");
+    SGS_REQUIRE(ws && ws_bytes >= sgs_gat_scores_heads_bwd_workspace_bytes(N, K, C), SGS_EWORKSPACE, "sgs_gat_scores_heads_bwd: workspace too small");
+    const int64_t D = K * C;
+    const int rp = gat_scores_rows_per_wg(N);
+    const int nwg = static_cast<int>((N + rp - 1) / rp);
+    float* part = static_cast<float*>(ws);
+    if (accumulate)
+        hipLaunchKernelGGL((gat_scores_heads_bwd<true>), dim3(nwg), dim3(kT), 0, stream, xl, N, static_cast<int>(K), C, att_src, att_dst, g_src, g_dst,
+                           dxl, part, rp);
+    else
+        hipLaunchKernelGGL((gat_scores_heads_bwd<false>), dim3(nwg), dim3(kT), 0, stream, xl, N, static_cast<int>(K), C, att_src, att_dst, g_src, g_dst,
+                           dxl, part, rp);
+    hipLaunchKernelGGL(gat_scores_bwd_finish, dim3(static_cast<unsigned>((2 * D + 63) / 64)), dim3(1024), 0, stream, part, nwg, D, datt_src, datt_dst);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_gat_alpha_heads_fwd(const float* a_src, const float* a_dst, int64_t N, int64_t K, int64_t n_edges, const int32_t* in_ptr,
+                            const int32_t* in_src, const int32_t* in_eid, float negative_slope, float p_drop, uint64_t seed, uint32_t site,
+                            float* soft, float* soft_loop, float* alpha, float* alpha_loop, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int64_t C = 1;
+    SGS_REQUIRE_HEADS("sgs_gat_alpha_heads_fwd");
+    SGS_REQUIRE(N >= 0 && n_edges >= 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_gat_alpha_heads_fwd: bad arguments");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(a_src && a_dst && in_ptr && soft_loop && alpha_loop && (n_edges == 0 || (in_src && in_eid && soft && alpha)), SGS_EINVAL,
+                "sgs_gat_alpha_heads_fwd: null pointer");
+    SGS_DISPATCH_KP(gat_alpha_heads_fwd, K, dim3(static_cast<unsigned>(cdiv(N * 64, kT))), stream, a_src, a_dst, N, static_cast<int>(K), in_ptr, in_src,
+                    in_eid, negative_slope, 1.0f / (1.0f - p_drop), dropout_thresh(p_drop), p_drop > 0.f ? 1 : 0, seed, site, epoch_ptr(), soft,
+                    soft_loop, alpha, alpha_loop);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_gat_alpha_heads_bwd(const float* a_src, const float* a_dst, int64_t N, int64_t K, int64_t n_edges, const int32_t* in_ptr,
+                            const int32_t* in_src, const int32_t* in_eid, float negative_slope, float p_drop, uint64_t seed, uint32_t site,
+                            const float* soft, const float* soft_loop, const float* galpha, const float* gloop, float* g_edge, float* g_selfloop,
+                            float* d_a_dst, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int64_t C = 1;
+    SGS_REQUIRE_HEADS("sgs_gat_alpha_heads_bwd");
+    SGS_REQUIRE(N >= 0 && n_edges >= 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_gat_alpha_heads_bwd: bad arguments");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(a_src && a_dst && in_ptr && soft_loop && gloop && g_selfloop && d_a_dst &&
+                    (n_edges == 0 || (in_src && in_eid && soft && galpha && g_edge)),
+                SGS_EINVAL, "sgs_gat_alpha_heads_bwd: null pointer");
+    SGS_DISPATCH_KP(gat_alpha_heads_bwd, K, dim3(static_cast<unsigned>(cdiv(N * 64, kT))), stream, a_src, a_dst, N, static_cast<int>(K), in_ptr, in_src,
+                    in_eid, negative_slope, 1.0f / (1.0f - p_drop), dropout_thresh(p_drop), p_drop > 0.f ? 1 : 0, seed, site, epoch_ptr(), soft,
+                    soft_loop, galpha, gloop, g_edge, g_selfloop, d_a_dst);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_edge_sum_by_row_heads(const float* g_edge, const float* g_self, int64_t N, int64_t K, int64_t nnz, const int32_t* ptr, const int32_t* eid,
+                              float* out, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int64_t C = 1;
+    SGS_REQUIRE_HEADS("sgs_edge_sum_by_row_heads");
+    SGS_REQUIRE(N >= 0 && nnz >= 0, SGS_EINVAL, "sgs_edge_sum_by_row_heads: bad sizes");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(ptr && out && (nnz == 0 || (g_edge && eid)), SGS_EINVAL, "sgs_edge_sum_by_row_heads: null pointer");
+    SGS_DISPATCH_KP(edge_sum_by_row_heads, K, dim3(static_cast<unsigned>(cdiv(N * 64, kT))), stream, g_edge, g_self, N, static_cast<int>(K), ptr, eid,
+                    out);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_spmm_csr_heads(const float* X, int64_t N, int64_t K, int64_t C, int64_t nnz, const int32_t* ptr, const int32_t* col, const int32_t* eid,
+                       const float* val, const float* diag, int mode, const float* bias, int act, float p_drop, uint64_t seed, uint32_t site,
+                       float* Y, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE_HEADS("sgs_spmm_csr_heads");
+    SGS_REQUIRE(N >= 0 && nnz >= 0 && mode >= SGS_HEADS_CONCAT && mode <= SGS_HEADS_BROADCAST, SGS_EINVAL, "sgs_spmm_csr_heads: bad sizes / mode");
+    SGS_REQUIRE(act >= SGS_ACT_NONE && act <= SGS_ACT_RELU_DROPOUT && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL,
+                "sgs_spmm_csr_heads: bad activation / dropout");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(X && ptr && Y && X != Y && (nnz == 0 || (col && eid && val)), SGS_EINVAL, "sgs_spmm_csr_heads: null or aliased pointer");
+    const int vec = (C % 4 == 0 && al16(X) && al16(Y)) ? 4 : 1;
+    const float scale = 1.0f / (1.0f - p_drop);
+    const uint32_t th = dropout_thresh(p_drop);
+    if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
+    const int Ki = static_cast<int>(K);
+    int lg = log2_ceil(cdiv(K * C, vec));
+    if (lg > 6) lg = 6;
+    const bool mean_lds = mode == SGS_HEADS_MEAN && (kT >> lg) * K * C <= kMeanLdsFloats;
+    if (mode == SGS_HEADS_MEAN && !mean_lds) {               // rows of more than 1024 floats: lanes own output columns and walk the heads
+        lg = log2_ceil(cdiv(C, vec));
+        if (lg > 6) lg = 6;
+    }
+    const dim3 grid(static_cast<unsigned>(cdiv(N, kT >> lg)));
+#define SGS_SPMM_HEADS_ARGS X, N, Ki, C, ptr, col, eid, val, diag, bias, act, scale, th, seed, site, epoch_ptr(), Y, lg
+    if (mean_lds) {
+        if (vec == 4) hipLaunchKernelGGL((spmm_csr_heads_mean_lds<4>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_ARGS);
+        else          hipLaunchKernelGGL((spmm_csr_heads_mean_lds<1>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_ARGS);
+    } else if (mode == SGS_HEADS_MEAN) {
+        if (vec == 4) hipLaunchKernelGGL((spmm_csr_heads_mean<4>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_ARGS);
+        else          hipLaunchKernelGGL((spmm_csr_heads_mean<1>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_ARGS);
+    } else if (mode == SGS_HEADS_BROADCAST) {
+        if (vec == 4) hipLaunchKernelGGL((spmm_csr_heads<4, true>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_ARGS);
+        else          hipLaunchKernelGGL((spmm_csr_heads<1, true>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_ARGS);
+    } else {
+        if (vec == 4) hipLaunchKernelGGL((spmm_csr_heads<4, false>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_ARGS);
+        else          hipLaunchKernelGGL((spmm_csr_heads<1, false>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_ARGS);
+    }
+#undef SGS_SPMM_HEADS_ARGS
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_sddmm_csr_heads(const float* A, const float* B, int64_t N, int64_t K, int64_t C, int64_t nnz, const int32_t* ptr, const int32_t* col,
+                        const int32_t* eid, int broadcast, float* g, float* gdiag, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE_HEADS("sgs_sddmm_csr_heads");
+    SGS_REQUIRE(N >= 0 && nnz >= 0, SGS_EINVAL, "sgs_sddmm_csr_heads: bad sizes");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(A && B && ptr && gdiag && (nnz == 0 || (col && eid && g)), SGS_EINVAL, "sgs_sddmm_csr_heads: null pointer");
+    const int vec = (C % 4 == 0 && al16(A) && al16(B)) ? 4 : 1;
+    const int lgK = log2_ceil(K);
+    int lgG = log2_ceil(cdiv(C, vec));
+    if (lgG > 6 - lgK) lgG = 6 - lgK;
+    const int lg = lgK + lgG;
+    const int Ki = static_cast<int>(K);
+    const dim3 grid(static_cast<unsigned>(cdiv(N, kT >> lg)));
+#define SGS_SDDMM_HEADS_ARGS A, B, N, Ki, C, ptr, col, eid, g, gdiag, lg, lgG
+    if (broadcast) {
+        if (vec == 4) hipLaunchKernelGGL((sddmm_csr_heads<4, true>), grid, dim3(kT), 0, stream, SGS_SDDMM_HEADS_ARGS);
+        else          hipLaunchKernelGGL((sddmm_csr_heads<1, true>), grid, dim3(kT), 0, stream, SGS_SDDMM_HEADS_ARGS);
+    } else {
+        if (vec == 4) hipLaunchKernelGGL((sddmm_csr_heads<4, false>), grid, dim3(kT), 0, stream, SGS_SDDMM_HEADS_ARGS);
+        else          hipLaunchKernelGGL((sddmm_csr_heads<1, false>), grid, dim3(kT), 0, stream, SGS_SDDMM_HEADS_ARGS);
+    }
+#undef SGS_SDDMM_HEADS_ARGS
     SGS_LAUNCH_OK();
     return SGS_OK;
 }

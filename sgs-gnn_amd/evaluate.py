@@ -126,6 +126,8 @@ def _batched_ok(args, model, n_draws) -> bool:
     heads = _eval_heads(args)
     if n_draws < 1:
         return False
+    if getattr(model, "gat_heads", 1) > 1:      # the batched engine's GAT pass is written for one attention head: serial loop
+        return False
     return _head_of(model) in heads
 
 

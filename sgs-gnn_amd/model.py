@@ -116,45 +116,52 @@ SITE_GAT_ATT, SITE_GAT_ACT = 16, 32          # attention dropout uses site, site
 
 
 class GATConv(nn.Module):
-    """PyG 2.3.1 GATConv with heads = 1 as torch_geometric.nn.models.GAT instantiates it: parameters
-    `lin_src.weight` (shared with `lin_dst.weight`), `att_src`, `att_dst` [1,1,out], `bias` [out]."""
+    """PyG 2.3.1 GATConv as torch_geometric.nn.models.GAT instantiates it: parameters `lin_src.weight` [heads * out, in] (shared with
+    `lin_dst.weight`), `att_src`, `att_dst` [1, heads, out], `bias` [heads * out] (concat) or [out] (mean over heads).  heads = 1 runs the
+    one-head kernels; 2 <= heads <= 16 the fused per-head ones (x' = lin_src(x) viewed as [N, heads, out], head-major columns)."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0):
         super().__init__()
-        if heads != 1:
-            raise NotImplementedError("the reference's GATModel never passes `heads` on to GAT: heads = 1")
+        heads = int(heads)
+        if not 1 <= heads <= 16 or out_channels < 1:
+            raise ValueError(f"GATConv: heads = {heads}, out_channels = {out_channels}: 1 <= heads <= 16 and out_channels >= 1 are supported")
         self.in_channels, self.out_channels, self.negative_slope, self.dropout = in_channels, out_channels, negative_slope, dropout
-        self.lin_src = nn.Linear(in_channels, out_channels, bias=False)
+        self.heads, self.concat = heads, bool(concat)
+        self.lin_src = nn.Linear(in_channels, heads * out_channels, bias=False)
         self.lin_dst = self.lin_src
-        self.att_src = nn.Parameter(torch.empty(1, 1, out_channels))
-        self.att_dst = nn.Parameter(torch.empty(1, 1, out_channels))
-        self.bias = nn.Parameter(torch.zeros(out_channels))
-        a = math.sqrt(6.0 / (in_channels + out_channels))
+        self.att_src = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.att_dst = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.bias = nn.Parameter(torch.zeros(heads * out_channels if concat else out_channels))
+        a = math.sqrt(6.0 / (in_channels + heads * out_channels))     # glorot on the parameter's own shape, as PyG
         nn.init.uniform_(self.lin_src.weight, -a, a)
-        b = math.sqrt(6.0 / (1 + out_channels))
+        b = math.sqrt(6.0 / (heads + out_channels))                   # [1, heads, out]: size(-2) + size(-1)
         nn.init.uniform_(self.att_src, -b, b)
         nn.init.uniform_(self.att_dst, -b, b)
 
     def forward(self, x, edge_index, *, act=ops.ACT_NONE, p_act=0.0, seed=0, layer=0):
         graph = ops.get_graph(edge_index, x.shape[0])
         xl = self.lin_src(x)
-        a_s, a_d = ops.gat_scores(xl, self.att_src, self.att_dst)      # node-level dots, one pass over x'
+        a_s, a_d = ops.gat_scores(xl, self.att_src, self.att_dst, heads=self.heads)      # node-level dots, one pass over x'
         p_att = self.dropout if self.training else 0.0
         return ops.gat_aggregate(xl, a_s, a_d, self.bias, graph, self.negative_slope, p_att, seed, SITE_GAT_ATT + 2 * layer, act,
-                                 p_act, seed, SITE_GAT_ACT + layer)
+                                 p_act, seed, SITE_GAT_ACT + layer, heads=self.heads, concat=self.concat)
 
 
 class GAT(nn.Module):
-    """torch_geometric.nn.models.GAT(in, hidden, num_layers=2, out_channels, dropout, act='relu')."""
+    """torch_geometric.nn.models.GAT(in, hidden, num_layers=2, out_channels, dropout, act='relu', heads=K): as PyG's GAT.init_conv, layer 0 is
+    GATConv(in, hidden // K, heads=K, concat=True) and the last layer GATConv(hidden, out, heads=K, concat=False)."""
     supports_edge_weight = False
 
-    def __init__(self, in_channels, hidden_channels, num_layers, out_channels, dropout=0.0, act='relu'):
+    def __init__(self, in_channels, hidden_channels, num_layers, out_channels, dropout=0.0, act='relu', heads=1):
         super().__init__()
         if num_layers != 2 or act != 'relu':
             raise NotImplementedError
-        self.dropout = dropout
-        self.convs = nn.ModuleList([GATConv(in_channels, hidden_channels, dropout=dropout),
-                                    GATConv(hidden_channels, out_channels, concat=False, dropout=dropout)])
+        if hidden_channels % heads != 0:
+            raise ValueError(f"Ensure that the number of output channels of 'GATConv' (got '{hidden_channels}') is divisible by the number "
+                             f"of heads (got '{heads}')")
+        self.dropout, self.heads = dropout, int(heads)
+        self.convs = nn.ModuleList([GATConv(in_channels, hidden_channels // heads, heads=heads, concat=True, dropout=dropout),
+                                    GATConv(hidden_channels, out_channels, heads=heads, concat=False, dropout=dropout)])
 
     def forward(self, x, edge_index, edge_weight=None):
         # edge_weight is dropped, exactly as PyG's BasicGNN does for a conv without edge-weight support
@@ -166,15 +173,17 @@ class GAT(nn.Module):
 
 
 class GATModel(nn.Module):
-    """model.py:189-208 (`heads` is accepted and unused, as in the reference)."""
+    """model.py:189-208.  `heads` is accepted and unused, as in the reference (its GATModel never hands it to GAT, so reference
+    checkpoints are one-head); the keyword-only `gat_heads` is what reaches GAT (default 1 = the reference's model)."""
 
-    def __init__(self, in_channels, hidden_dim, num_classes, dropout_prob=0.3, heads=8, edge_mlp_type='MLP'):
+    def __init__(self, in_channels, hidden_dim, num_classes, dropout_prob=0.3, heads=8, edge_mlp_type='MLP', *, gat_heads=1):
         super().__init__()
         from .scorer import get_edge_mlp
         self.edge_prob_mlp = get_edge_mlp(in_channels, hidden_dim, dropout_prob, edge_mlp_type)
         self.dropout_prob = dropout_prob
+        self.gat_heads = int(gat_heads)
         self.GAT = GAT(in_channels=in_channels, hidden_channels=hidden_dim, num_layers=2, out_channels=num_classes,
-                       dropout=dropout_prob, act='relu')
+                       dropout=dropout_prob, act='relu', heads=self.gat_heads)
 
     def forward(self, data, edge_index, edge_weight=None):
         from .utils import segment

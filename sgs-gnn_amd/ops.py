@@ -1376,16 +1376,150 @@ class _GATScores(torch.autograd.Function):
         return dxl, das, dad
 
 
-def gat_scores(xl, att_src, att_dst):
+# ---- multi-head GATConv (sgs_*_heads).  Per-edge arrays are [n, K] by edge id, so forward, transposed aggregation and the softmax
+# backward share them through the CSRs' eid columns: backward = activation (as the one-head path) + 4 launches (transposed per-head SpMM,
+# per-head SDDMM, softmax backward, by-source sum) against the one-head path's activation + 8.
+HEADS_CONCAT, HEADS_MEAN, HEADS_BROADCAST = 0, 1, 2
+
+
+def gat_heads_supported(heads: int, channels: int) -> bool:
+    """Host-only: can the multi-head kernels take (heads, channels per head)?  (1 <= heads <= 16, channels >= 1.)"""
+    return bool(_lib.lib().sgs_gat_heads_supported(int(heads), int(channels)))
+
+
+def _spmm_heads(X, ptr, col, eid, val, diag, mode, bias, act, p, seed, site, N, K, C, nnz):
+    L = _lib.lib()
+    Y = torch.empty(N, C if mode == HEADS_MEAN else K * C, dtype=torch.float32, device=X.device)
+    _lib.check(L.sgs_spmm_csr_heads(_ptr(X, torch.float32), N, K, C, nnz, _ptr(ptr), _ptr(col), _ptr(eid), _ptr(val), _ptr(diag), mode, _ptr(bias),
+                                    act, float(p), seed, site, _ptr(Y), _stream()), "sgs_spmm_csr_heads")
+    return Y
+
+
+class _GATAggregateHeads(torch.autograd.Function):
+    """_GATAggregate for K heads: xl [N, K C] head-major, a_s / a_d [N, K]; out [N, K C] (concat) or the head mean [N, C]."""
+
+    @staticmethod
+    def forward(ctx, xl, a_s, a_d, bias, graph, K, concat, slope, p_att, seed_att, site_att, act, p_act, seed_act, site_act):
+        L = _lib.lib()
+        N, D = xl.shape
+        C = D // K
+        n = graph.n_edges
+        f32 = dict(dtype=torch.float32, device=xl.device)
+        soft, alpha = torch.empty(max(n, 1), K, **f32), torch.empty(max(n, 1), K, **f32)
+        soft_loop, alpha_loop = torch.empty(N, K, **f32), torch.empty(N, K, **f32)
+        _lib.check(L.sgs_gat_alpha_heads_fwd(_ptr(a_s), _ptr(a_d), N, K, n, _ptr(graph.in_ptr), _ptr(graph.in_src), _ptr(graph.in_eid),
+                                             float(slope), float(p_att), seed_att, site_att, _ptr(soft), _ptr(soft_loop), _ptr(alpha),
+                                             _ptr(alpha_loop), _stream()), "sgs_gat_alpha_heads_fwd")
+        Y = _spmm_heads(xl, graph.in_ptr, graph.in_src, graph.in_eid, alpha, alpha_loop, HEADS_CONCAT if concat else HEADS_MEAN, bias, act,
+                        p_act, seed_act, site_act, N, K, C, n)
+        ctx.save_for_backward(xl, a_s, a_d, soft, soft_loop, alpha, alpha_loop, Y if act != ACT_NONE else None)
+        ctx.graph, ctx.slope, ctx.p_att, ctx.seed_att, ctx.site_att = graph, float(slope), float(p_att), seed_att, site_att
+        ctx.act, ctx.p_act, ctx.has_bias, ctx.K, ctx.concat = act, float(p_act), bias is not None, K, bool(concat)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        L = _lib.lib()
+        xl, a_s, a_d, soft, soft_loop, alpha, alpha_loop, Y = ctx.saved_tensors
+        gr, K = ctx.graph, ctx.K
+        N, D = xl.shape
+        C = D // K
+        n = gr.n_edges
+        f32 = dict(dtype=torch.float32, device=xl.device)
+        dY = dY.contiguous()
+        dbias = None
+        if ctx.act != ACT_NONE and ctx.has_bias:
+            dZ, dbias = _act_bwd_colsum(dY, Y, ctx.act, ctx.p_act)
+        elif ctx.act != ACT_NONE:
+            dZ = torch.empty_like(dY)
+            _lib.check(L.sgs_act_bwd(_ptr(dY), _ptr(Y), dY.numel(), ctx.act, ctx.p_act, _ptr(dZ), _stream()), "sgs_act_bwd")
+        else:
+            dZ = dY
+            dbias = _colsum(dZ) if ctx.has_bias else None
+        # d x' over the src-CSR: the same alpha array through out_eid (concat = False: dZ [N, C] is shared by the heads, scaled by 1 / K)
+        dxl = _spmm_heads(dZ, gr.out_ptr, gr.out_dst, gr.out_eid, alpha, alpha_loop, HEADS_CONCAT if ctx.concat else HEADS_BROADCAST, None,
+                          ACT_NONE, 0.0, 0, 0, N, K, C, n)
+        galpha, gloop = torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32)
+        _lib.check(L.sgs_sddmm_csr_heads(_ptr(dZ), _ptr(xl), N, K, C, n, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid),
+                                         0 if ctx.concat else 1, _ptr(galpha), _ptr(gloop), _stream()), "sgs_sddmm_csr_heads")
+        g_edge, g_self, d_ad = torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32), torch.empty(N, K, **f32)
+        _lib.check(L.sgs_gat_alpha_heads_bwd(_ptr(a_s), _ptr(a_d), N, K, n, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid), ctx.slope,
+                                             ctx.p_att, ctx.seed_att, ctx.site_att, _ptr(soft), _ptr(soft_loop), _ptr(galpha), _ptr(gloop),
+                                             _ptr(g_edge), _ptr(g_self), _ptr(d_ad), _stream()), "sgs_gat_alpha_heads_bwd")
+        d_as = torch.empty(N, K, **f32)
+        _lib.check(L.sgs_edge_sum_by_row_heads(_ptr(g_edge), _ptr(g_self), N, K, n, _ptr(gr.out_ptr), _ptr(gr.out_eid), _ptr(d_as), _stream()),
+                   "sgs_edge_sum_by_row_heads")
+        return dxl, d_as, d_ad, dbias, None, None, None, None, None, None, None, None, None, None, None
+
+
+class _GATScoresHeads(torch.autograd.Function):
+    """a_s[i, h] = <x'[i, h, :], att_src[h, :]>, a_d likewise, for K heads in one pass over x' (sgs_gat_scores_heads_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, xl, att_s, att_d, K):
+        L = _lib.lib()
+        N, D = xl.shape
+        C = D // K
+        a_s, a_d = torch.empty(N, K, dtype=torch.float32, device=xl.device), torch.empty(N, K, dtype=torch.float32, device=xl.device)
+        _lib.check(L.sgs_gat_scores_heads_fwd(_ptr(xl, torch.float32), N, K, C, _ptr(att_s), _ptr(att_d), _ptr(a_s), _ptr(a_d), _stream()),
+                   "sgs_gat_scores_heads_fwd")
+        ctx.save_for_backward(xl, att_s, att_d)
+        ctx.K = K
+        return a_s, a_d
+
+    @staticmethod
+    def backward(ctx, g_s, g_d):
+        L = _lib.lib()
+        xl, att_s, att_d = ctx.saved_tensors
+        K = ctx.K
+        N, D = xl.shape
+        C = D // K
+        dev = xl.device
+        g_s = torch.zeros(N, K, dtype=torch.float32, device=dev) if g_s is None else g_s.contiguous()
+        g_d = torch.zeros(N, K, dtype=torch.float32, device=dev) if g_d is None else g_d.contiguous()
+        dxl = torch.empty_like(xl)
+        das, dad = torch.empty(D, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)
+        ws = workspace(L.sgs_gat_scores_heads_bwd_workspace_bytes(N, K, C), dev)
+        _lib.check(L.sgs_gat_scores_heads_bwd(_ptr(xl), N, K, C, _ptr(att_s), _ptr(att_d), _ptr(g_s), _ptr(g_d), 0, _ptr(dxl), _ptr(das), _ptr(dad),
+                                              ws.data_ptr(), ws.numel(), _stream()), "sgs_gat_scores_heads_bwd")
+        return dxl, das, dad, None
+
+
+def _check_heads(xl, heads):
+    heads = int(heads)
+    if xl.dim() != 2 or heads < 1 or xl.shape[1] % heads != 0:
+        raise RuntimeError(f"gat: x' must be [N, heads * channels] (got {tuple(xl.shape)} for heads = {heads})")
+    if not gat_heads_supported(heads, xl.shape[1] // heads):
+        raise RuntimeError(f"gat: unsupported heads = {heads} x channels = {xl.shape[1] // heads} (1 <= heads <= 16, channels >= 1)")
+    return heads
+
+
+def gat_scores(xl, att_src, att_dst, heads=1):
+    """Node-level attention scores: heads = 1 -> two [N] vectors (the one-head kernels); heads = K > 1 -> two [N, K] matrices from
+    x' [N, K C] (head-major columns) and att_* with K C elements ([1, K, C])."""
     _need_gpu(xl, att_src, att_dst)
-    return _GATScores.apply(xl.contiguous(), att_src.reshape(-1).contiguous(), att_dst.reshape(-1).contiguous())
+    if heads == 1:
+        return _GATScores.apply(xl.contiguous(), att_src.reshape(-1).contiguous(), att_dst.reshape(-1).contiguous())
+    heads = _check_heads(xl, heads)
+    return _GATScoresHeads.apply(xl.contiguous(), att_src.reshape(-1).contiguous(), att_dst.reshape(-1).contiguous(), heads)
 
 
 def gat_aggregate(xl, a_s, a_d, bias, graph: Graph, negative_slope=0.2, p_att=0.0, seed_att=0, site_att=0, act=ACT_NONE,
-                  p_act=0.0, seed_act=0, site_act=0):
+                  p_act=0.0, seed_act=0, site_act=0, heads=1, concat=True):
+    """Attention softmax + aggregation (+ bias / act / dropout).  heads = 1: the one-head kernels (`concat` has no effect on one head).
+    heads = K > 1: per-head softmax over x' [N, K C]; concat=True -> [N, K C], False -> the mean over heads [N, C]; `bias` matches."""
     _need_gpu(xl, a_s, a_d, bias)
-    return _GATAggregate.apply(xl.contiguous(), a_s.contiguous(), a_d.contiguous(), bias, graph, float(negative_slope),
-                               float(p_att), int(seed_att), int(site_att), act, float(p_act), int(seed_act), int(site_act))
+    if heads == 1:
+        return _GATAggregate.apply(xl.contiguous(), a_s.contiguous(), a_d.contiguous(), bias, graph, float(negative_slope),
+                                   float(p_att), int(seed_att), int(site_att), act, float(p_act), int(seed_act), int(site_act))
+    heads = _check_heads(xl, heads)
+    if tuple(a_s.shape) != (xl.shape[0], heads) or tuple(a_d.shape) != (xl.shape[0], heads):
+        raise RuntimeError("gat_aggregate: a_s / a_d must be [N, heads]")
+    width = xl.shape[1] if concat else xl.shape[1] // heads
+    if bias is not None and bias.numel() != width:
+        raise RuntimeError(f"gat_aggregate: bias must have {width} elements")
+    return _GATAggregateHeads.apply(xl.contiguous(), a_s.contiguous(), a_d.contiguous(), bias, graph, heads, bool(concat), float(negative_slope),
+                                    float(p_att), int(seed_att), int(site_att), act, float(p_act), int(seed_act), int(site_act))
 
 
 # ------------------------------------------------------------------ node-level Linear with a hand-written weight gradient
