@@ -717,6 +717,46 @@ int sgs_sddmm_csr_heads(const float* A, const float* B, int64_t N, int64_t K, in
                         const int32_t* eid, int broadcast, float* g, float* gdiag, sgs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K9: Chebyshev layers of order K > 1 (PyG 2.3.1 ChebConv, normalization = 'sym', lambda_max = 2, restated; 1 <= K <= 8 -- the bound is
+ * a choice, not a hardware limit; K = 1 callers need none of this, the layer is a Linear).  For edges (s_e -> d_e) with weights w_e:
+ *   (i, i) edges are removed (weight 0 in every formula, gradient 0);  deg_n = sum_{e: s_e = n} w_e, summed BY SOURCE (not the GCN
+ *   degree);  dis = deg^-1/2 (inf -> 0);  l_e = -dis[s_e] w_e dis[d_e]: the off-diagonal entries of L_hat = 2 L / lambda_max - I, whose
+ *   diagonal is 0 (no loop term);  (L_hat X)_i = sum_{e: d_e = i} l_e X[s_e] (duplicates count twice).
+ * Nothing assumes a symmetric edge list.  No float atomics (row sums in CSR order over a fixed tree: run-to-run identical), no host
+ * synchronisation, scratch from the caller: capturable.  An order outside 1..8 returns SGS_EINVAL ("unsupported ...");
+ * sgs_cheb_supported is the host-only predicate (no GPU needed).
+ *   sgs_cheb_norm_fwd : dis [N], l_in / l_out [n_edges] = l in dst-CSR / src-CSR entry order (bitwise equal copies); w == NULL = unit weights.
+ *   sgs_cheb_norm_bwd : g [n_edges] = dLoss/dl by EDGE ID -> dw [n_edges]:  dw_e = -dis[s] dis[d] g_e + c[s_e] with
+ *                       c_n = -1/2 dis_n^3 (sum_{e: s_e = n} -w_e dis[d_e] g_e + sum_{e: d_e = n} -dis[s_e] w_e g_e), and dw_e = 0 on (i, i)
+ *                       edges.  g2 (may be NULL): a second layer's gradient over the same normalisation, summed on read.
+ *                       ws: sgs_cheb_norm_bwd_workspace_bytes(N).
+ *   sgs_cheb_spmm     : one step of the three-term recurrence,
+ *                         Y[i, :] = act(add[i, :] + alpha * sum_{k in row i} val[k] X[col[k], :] - sub[i, :] + bias)
+ *                       over D columns.  K is the layer's order and is only validated here (the step itself does not depend on it): this
+ *                       is the entry point through which an unsupported order reports "unsupported".  X, add, sub, Y have their OWN leading dimensions (ld* >= D), so the steps of Clenshaw's recurrence
+ *                       b_k = Y_k + 2 L_hat b_{k+1} - b_{k+2} and of its backward U_k = 2 L_hat^T U_{k-1} - U_{k-2} read and write column
+ *                       blocks of the concatenated [N, K D] buffers in place.  add, sub, bias may be NULL; add may be Y itself; X must
+ *                       not overlap Y or Y2.  Y2 (may be NULL): a second copy scale2 * Y with leading dimension ldy2 (the backward
+ *                       writes 2 U_k straight into the SDDMM's operand).  act / p_drop / seed / site as sgs_spmm_csr: the mask is
+ *                       sgs_dropout_keep(seed, site, row i, column c).  The forward runs over (in_ptr, in_src, l_in), the backward over
+ *                       (out_ptr, out_dst, l_out); nnz picks the row-per-workgroup kernel as in sgs_spmm_csr.  Rows are gathered 16 bytes
+ *                       at a time when D % 4 == 0, ldx % 4 == 0 and X is 16-byte aligned, else column by column.
+ * The gradient wrt l is ONE sgs_sddmm_csr at width (K - 1) D of [G | 2 U_1 | ... | 2 U_{K-2}] against [b_1 | ... | b_{K-1}].
+ * ---------------------------------------------------------------------------------- */
+int sgs_cheb_supported(int64_t K);
+int sgs_cheb_norm_fwd(const float* w, int64_t n_edges, int64_t N, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid,
+                      const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, float* dis, float* l_in, float* l_out,
+                      sgs_stream_t stream);
+size_t sgs_cheb_norm_bwd_workspace_bytes(int64_t N);
+int sgs_cheb_norm_bwd(const float* w, const float* g, const float* g2, int64_t n_edges, int64_t N, const float* dis, const int32_t* in_ptr,
+                      const int32_t* in_src, const int32_t* in_eid, const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid,
+                      const int64_t* edge_index, float* dw, void* ws, size_t ws_bytes, sgs_stream_t stream);
+int sgs_cheb_spmm(int64_t K, const float* X, int64_t ldx, int64_t N, int64_t D, int64_t nnz, const int32_t* ptr, const int32_t* col,
+                  const float* val, float alpha, const float* add, int64_t ldadd, const float* sub, int64_t ldsub, const float* bias, int act,
+                  float p_drop, uint64_t seed, uint32_t site, float* Y, int64_t ldy, float* Y2, int64_t ldy2, float scale2,
+                  sgs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Weight-gradient GEMM of the node-level Linear layers: C[M,N] = A^T B, A [K,M], B [K,N] row-major,
  * K = number of graph nodes (dW = dY^T X for GCNConv.lin, model.py:94-95,151-153).  fp32 MFMA fed from
  * coalesced global reads, split-K with a fixed-order combine (deterministic).  Skinny shapes only (the

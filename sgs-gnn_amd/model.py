@@ -260,39 +260,68 @@ class GINModel(nn.Module):
 
 # ------------------------------------------------------------------ Chebyshev head (model.py:211-230)
 class ChebConv(nn.Module):
-    """PyG ChebConv(in, out, K=1, normalization='sym') as the reference instantiates it.  With K = 1 only T_0(L) x = x is
-    used: out = lins[0](x) + bias -- the Laplacian PyG normalises is never applied (so edge_index / edge_weight do not
-    influence the output; kept in the signature).  Keys: `lins.0.weight`, `bias`."""
+    """PyG 2.3.1 ChebConv(in, out, K, normalization='sym') with lambda_max = 2 (PyG's default for 'sym'; restated, not fixture-pinned):
+    out = sum_{k<K} T_k(L_hat) x W_k^T + bias, T_0 = x, T_1 = L_hat x, T_k = 2 L_hat T_{k-1} - T_{k-2}.  Keys: `lins.{k}.weight` [out, in]
+    (glorot, no bias), `bias` [out] (zeros).  K = 1 is what the reference instantiates: only T_0 is used, out = lins[0](x) + bias, and
+    edge_index / edge_weight do not influence the output (kept in the signature).  2 <= K <= 8 runs the fused recurrence
+    (ops.cheb_conv), where the edge weights reach the output and receive a gradient."""
 
     def __init__(self, in_channels, out_channels, K=1, normalization='sym'):
         super().__init__()
-        if K != 1:
-            raise NotImplementedError("the reference instantiates ChebConv(K=1)")
-        self.lins = nn.ModuleList([nn.Linear(in_channels, out_channels, bias=False)])
+        K = int(K)
+        if not 1 <= K <= 8:
+            raise ValueError(f"ChebConv: K = {K}: 1 <= K <= 8 is supported")
+        if normalization != 'sym':
+            raise NotImplementedError(f"ChebConv: normalization = {normalization!r}: only 'sym' is built")
+        self.in_channels, self.out_channels, self.K, self.normalization = in_channels, out_channels, K, normalization
+        self.lins = nn.ModuleList([nn.Linear(in_channels, out_channels, bias=False) for _ in range(K)])
         self.bias = nn.Parameter(torch.zeros(out_channels))
         a = math.sqrt(6.0 / (in_channels + out_channels))            # glorot, as PyG's Linear(weight_initializer='glorot')
-        nn.init.uniform_(self.lins[0].weight, -a, a)
+        for lin in self.lins:
+            nn.init.uniform_(lin.weight, -a, a)
 
-    def forward(self, x, edge_index=None, edge_weight=None):
-        return ops.linear_nobias(x, self.lins[0].weight) + self.bias
+    def forward(self, x, edge_index=None, edge_weight=None, *, norm=None, act=ops.ACT_NONE, p=0.0, seed=0, site=0):
+        if self.K == 1:
+            if norm is not None or act != ops.ACT_NONE or p != 0.0:
+                raise ValueError("ChebConv: K = 1 is a plain Linear: it has no normalisation and no fused activation / dropout epilogue")
+            return ops.linear_nobias(x, self.lins[0].weight) + self.bias
+        if norm is None:
+            norm = ops.cheb_norm(ops.get_graph(edge_index, x.shape[0]), edge_weight)
+        Wcat = torch.cat([lin.weight for lin in self.lins], 0)       # [K out, in]: one product for all orders
+        return ops.cheb_conv(x, Wcat, self.bias, norm, self.K, act=act, p=p, seed=seed, site=site)
 
 
 class ChebModel(nn.Module):
-    """model.py:211-230."""
+    """model.py:211-230.  The keyword-only `cheb_k` is the Chebyshev order of both layers (default 1 = the reference's model, in which
+    the graph never enters); with cheb_k >= 2 the sampled subgraph and its edge weights reach the logits through message passing."""
 
-    def __init__(self, in_channels, hidden_dim, num_classes, dropout_prob=0.3, edge_mlp_type='MLP'):
+    def __init__(self, in_channels, hidden_dim, num_classes, dropout_prob=0.3, edge_mlp_type='MLP', *, cheb_k=1):
         super().__init__()
         from .scorer import get_edge_mlp
         self.edge_prob_mlp = get_edge_mlp(in_channels, hidden_dim, dropout_prob, edge_mlp_type)
         self.dropout_prob = dropout_prob
-        self.gcn1 = ChebConv(in_channels, hidden_dim, K=1, normalization='sym')
+        self.cheb_k = int(cheb_k)
+        self.gcn1 = ChebConv(in_channels, hidden_dim, K=self.cheb_k, normalization='sym')
         self.dropout = nn.Dropout(dropout_prob)
-        self.gcn2 = ChebConv(hidden_dim, num_classes, K=1, normalization='sym')
+        self.gcn2 = ChebConv(hidden_dim, num_classes, K=self.cheb_k, normalization='sym')
 
     def forward(self, data, edge_index, edge_weight=None):
+        if self.cheb_k > 1:
+            return self._forward_graph(data.x, edge_index, edge_weight)
         h = F.relu(self.gcn1(data.x, edge_index, edge_weight))
         p = self.dropout.p if self.training else 0.0
         if p > 0:
             keep = ops.dropout_keep(_DropoutClock.next_seed(), SITE_GNN, h.shape[0], h.shape[1], p, h.device)
             h = h * keep / (1.0 - p)
         return self.gcn2(h, edge_index, edge_weight)
+
+    def _forward_graph(self, x, edge_index, edge_weight):
+        """cheb_k >= 2: one normalisation for both layers; ReLU and the dropout mask (the same site and seed accounting as above: one seed
+        per training forward with p > 0, none otherwise) ride on the first layer's last recurrence step."""
+        from .utils import segment
+        with segment(self, "gnn_forward"):
+            norm = ops.cheb_norm(ops.get_graph(edge_index, x.shape[0]), edge_weight)
+            p = self.dropout.p if self.training else 0.0
+            seed = _DropoutClock.next_seed() if p > 0 else 0
+            h = self.gcn1(x, norm=norm, act=ops.ACT_RELU_DROPOUT if p > 0 else ops.ACT_RELU, p=p, seed=seed, site=SITE_GNN)
+            return self.gcn2(h, norm=norm)

@@ -330,7 +330,10 @@ def st_weights(p, prior, c, stats, eid):
 # ------------------------------------------------------------------ graph + GCN
 class Graph:
     """Both CSR orientations of one edge list (sgs_graph_build).  Built once per sampled graph
-    and shared by every layer / pass that runs over it."""
+    and shared by every layer / pass that runs over it.  Results that depend on the graph alone are cached on the object (`_norm_unit`,
+    `_cheb_norm_unit`, `_norm_sum`).  A step-graph slot's graph (stepgraph.py) carries `restaged = True`: its arrays are refilled for every
+    partition, so a cached result is only valid if the slot stages it too (gcn_norm: the slot pre-seeds `_norm_unit` and copies the
+    partition's own into it); cheb_norm honours the flag and does not cache there."""
 
     def __init__(self, edge_index: torch.Tensor, N: int):
         L = _lib.lib()
@@ -2096,3 +2099,189 @@ def ensemble_partition_head(batch, model, q: int, mode: int, p, passes, counts, 
     if trace is not None:
         trace["logits"], trace["mean"], trace["edges"] = torch.cat(logs), acc, torch.cat(edges)
     return acc
+
+
+# ------------------------------------------------------------------ Chebyshev head, K > 1 (csrc/cheb.hip)
+def cheb_supported(K: int) -> bool:
+    """Whether the fused Chebyshev kernels serve order K (sgs_cheb_supported: 1 <= K <= 8; host-only)."""
+    return bool(_lib.lib().sgs_cheb_supported(int(K)))
+
+
+def _cheb_norm_forward(graph: Graph, w):
+    L = _lib.lib()
+    dev = graph.edge_index.device
+    nm = Norm()
+    nm.graph, nm.w, nm.handle, nm.loopw, nm.what_loop = graph, w, None, None, None
+    ne, Nn = max(graph.n_edges, 1), max(graph.N, 1)
+    sizes = [Nn, ne, ne]
+    offs = [0]
+    for z in sizes:
+        offs.append(offs[-1] + ((z + 63) & ~63))
+    buf = torch.empty(offs[-1], dtype=torch.float32, device=dev)
+    nm.dis, nm.what_in, nm.what_out = (buf[offs[i]:offs[i] + sizes[i]] for i in range(3))
+    _lib.check(L.sgs_cheb_norm_fwd(_ptr(w, torch.float32), graph.n_edges, graph.N, _ptr(graph.in_ptr), _ptr(graph.in_src), _ptr(graph.in_eid),
+                                   _ptr(graph.out_ptr), _ptr(graph.out_dst), _ptr(graph.out_eid), _ptr(nm.dis), _ptr(nm.what_in),
+                                   _ptr(nm.what_out), _stream()), "sgs_cheb_norm_fwd")
+    return nm
+
+
+class _ChebNorm(torch.autograd.Function):
+    """The autograd edge from the layers' gradients wrt l ([n_edges], edge-id order) back to the edge weights."""
+
+    @staticmethod
+    def forward(ctx, w, graph, box):
+        nm = _cheb_norm_forward(graph, w)
+        box.append(nm)
+        ctx.nm = nm
+        return torch.empty(graph.n_edges, dtype=torch.float32, device=w.device)
+
+    @staticmethod
+    def backward(ctx, g):
+        L = _lib.lib()
+        nm, gr = ctx.nm, ctx.nm.graph
+        g = g.contiguous()
+        n = gr.n_edges
+        extra = getattr(nm, "_g_extra", None)          # the other layer's gradient, parked by _handle_grad: summed on read
+        nm._g_first = nm._g_extra = None
+        if extra is not None and extra.numel() != g.numel():
+            g, extra = g + extra, None
+        dw = torch.empty(n, dtype=torch.float32, device=g.device)
+        if n > 0:
+            ws = workspace(L.sgs_cheb_norm_bwd_workspace_bytes(gr.N), g.device)
+            _lib.check(L.sgs_cheb_norm_bwd(_ptr(nm.w), _ptr(g), _ptr(extra), n, gr.N, _ptr(nm.dis), _ptr(gr.in_ptr), _ptr(gr.in_src),
+                                           _ptr(gr.in_eid), _ptr(gr.out_ptr), _ptr(gr.out_dst), _ptr(gr.out_eid), _ptr(gr.edge_index), _ptr(dw),
+                                           ws.data_ptr(), ws.numel(), _stream()), "sgs_cheb_norm_bwd")
+        return dw, None, None
+
+
+def cheb_norm(graph: Graph, w=None) -> Norm:
+    """The scaled-Laplacian analogue of gcn_norm (PyG ChebConv, 'sym', lambda_max = 2): dis = deg^-1/2 with the degree summed by SOURCE
+    and (i, i) edges removed, and l_e = -dis[s] w_e dis[d] in both CSR orders (`what_in` / `what_out`; there is no loop term, so `loopw` /
+    `what_loop` are None).  `handle` carries the layers' gradients wrt l ([n_edges], edge-id order) back to `w`.  The unit-weight result
+    depends on the graph alone and is kept on it -- except on a step-graph slot's graph (`restaged`), whose arrays are refilled per
+    partition: there the kernels run on every call, so that they are part of every replay.  One normalisation per forward is meant to
+    be shared by both layers of the head: the second layer's gradient is then summed on read (_handle_grad) instead of by an autograd
+    add."""
+    if w is None:
+        if getattr(graph, "restaged", False):      # a step-graph slot's CSR is refilled per partition: the kernels belong in every replay
+            return _cheb_norm_forward(graph, None)
+        nm = getattr(graph, "_cheb_norm_unit", None)
+        if nm is None:
+            nm = graph._cheb_norm_unit = _cheb_norm_forward(graph, None)
+        return nm
+    _need_gpu(w)
+    w = w.contiguous()
+    if w.dtype != torch.float32 or w.numel() != graph.n_edges:
+        raise RuntimeError(f"edge_weight must be float32 [{graph.n_edges}]")
+    if not (w.requires_grad and torch.is_grad_enabled()):
+        return _cheb_norm_forward(graph, w.detach())
+    box = []
+    handle = _ChebNorm.apply(w, graph, box)
+    nm = box[0]
+    nm.handle = handle
+    nm._park_ok = True            # _ChebNorm.backward reads the parked second gradient
+    return nm
+
+
+def _cheb_step(K, X, ldx, N, D, gr_ptr, gr_col, val, nnz, alpha, add, ldadd, sub, ldsub, bias, act, p, seed, site, Y, ldy, Y2=None, ldy2=0,
+               scale2=1.0):
+    """One sgs_cheb_spmm launch; X, add, sub, Y, Y2 are raw addresses (column blocks of wider buffers) or None."""
+    _lib.check(_lib.lib().sgs_cheb_spmm(K, X, ldx, N, D, nnz, _ptr(gr_ptr), _ptr(gr_col), _ptr(val), float(alpha), add, ldadd, sub, ldsub,
+                                        _ptr(bias), act, float(p), seed, site, Y, ldy, Y2, ldy2, float(scale2), _stream()), "sgs_cheb_spmm")
+
+
+class _ChebConv(torch.autograd.Function):
+    """out = act(sum_k T_k(L_hat) x W_k^T + bias) by Clenshaw's recurrence at the output width:
+        Y = x [W_0 | ... | W_{K-1}]^T,   b_k = Y_k + 2 L_hat b_{k+1} - b_{k+2} (k = K-1 .. 1),   out = act(Y_0 + L_hat b_1 - b_2 + bias)
+    K - 1 fused steps (sgs_cheb_spmm) over the dst-CSR.  Kept for the backward: [b_1 | ... | b_{K-1}] (the steps overwrite the GEMM's
+    column blocks in place) and, for the activation's derivative, the output.  Backward, with G = d out after the activation:
+        U_0 = G, U_1 = L_hat^T G, U_k = 2 L_hat^T U_{k-1} - U_{k-2}  (K - 1 steps over the src-CSR)
+        dW = [U_0 | ... | U_{K-1}]^T x,   dx = [U_0 | ... | U_{K-1}] Wcat,   dl = one SDDMM of [G | 2 U_1 | ... | 2 U_{K-2}] with [b_1 | ... | b_{K-1}]
+    and nothing is recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, Wcat, bias, handle, nm, K, act, p, seed, site):
+        gr = nm.graph
+        N = x.shape[0]
+        D = Wcat.shape[0] // K
+        ldb = (K - 1) * D
+        Y0 = _x_wt(x, Wcat[:D])                                  # [N, D]
+        B = _x_wt(x, Wcat[D:])                                   # [N, (K - 1) D]: Y_1 .. Y_{K-1}, becoming b_1 .. b_{K-1} in place
+        b0 = B.data_ptr()
+        blk = lambda k: b0 + 4 * (k - 1) * D                     # b_k's column block
+        for k in range(K - 2, 0, -1):
+            _cheb_step(K, blk(k + 1), ldb, N, D, gr.in_ptr, gr.in_src, nm.what_in, gr.n_edges, 2.0, blk(k), ldb,
+                       blk(k + 2) if k + 2 <= K - 1 else None, ldb, None, ACT_NONE, 0.0, 0, 0, blk(k), ldb)
+        out = torch.empty(N, D, dtype=torch.float32, device=x.device)
+        _cheb_step(K, blk(1), ldb, N, D, gr.in_ptr, gr.in_src, nm.what_in, gr.n_edges, 1.0, Y0.data_ptr(), D, blk(2) if K >= 3 else None, ldb,
+                   bias, act, p, seed, site, out.data_ptr(), D)
+        ctx.nm, ctx.K, ctx.act, ctx.p = nm, K, act, p
+        ctx.has_bias, ctx.has_handle = bias is not None, handle is not None
+        ctx.save_for_backward(x, Wcat, B, out if act != ACT_NONE else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dY):
+        L = _lib.lib()
+        nm, gr, K = ctx.nm, ctx.nm.graph, ctx.K
+        x, Wcat, B, out = ctx.saved_tensors
+        N, D = dY.shape
+        dY = dY.contiguous()
+        dx = dW = dbias = g = None
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.act != ACT_NONE and want_db:
+            G, dbias = _act_bwd_colsum(dY, out, ctx.act, ctx.p)
+        elif ctx.act != ACT_NONE:
+            G = torch.empty_like(dY)
+            _lib.check(L.sgs_act_bwd(_ptr(dY), _ptr(out), dY.numel(), ctx.act, float(ctx.p), _ptr(G), _stream()), "sgs_act_bwd")
+        else:
+            G = dY
+        if want_db and dbias is None:
+            dbias = _colsum(G)
+        need_x, need_W = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_h = ctx.has_handle and ctx.needs_input_grad[3]
+        last = K - 1 if (need_x or need_W) else (K - 2 if need_h else 0)       # highest U_k anything asks for
+        ldu, lda = K * D, (K - 1) * D
+        U = torch.empty(N, ldu, dtype=torch.float32, device=dY.device)
+        U[:, :D].copy_(G)
+        A = G                                                    # the SDDMM's left operand [G | 2 U_1 | ... | 2 U_{K-2}]
+        if need_h and K > 2:
+            A = torch.empty(N, lda, dtype=torch.float32, device=dY.device)
+            A[:, :D].copy_(G)
+        u0, a0 = U.data_ptr(), A.data_ptr()
+        for k in range(1, last + 1):
+            y2 = a0 + 4 * k * D if (need_h and k <= K - 2) else None
+            if k == 1:
+                _cheb_step(K, G.data_ptr(), D, N, D, gr.out_ptr, gr.out_dst, nm.what_out, gr.n_edges, 1.0, None, 0, None, 0, None, ACT_NONE, 0.0,
+                           0, 0, u0 + 4 * D, ldu, y2, lda, 2.0)
+            else:
+                _cheb_step(K, u0 + 4 * (k - 1) * D, ldu, N, D, gr.out_ptr, gr.out_dst, nm.what_out, gr.n_edges, 2.0, None, 0,
+                           u0 + 4 * (k - 2) * D, ldu, None, ACT_NONE, 0.0, 0, 0, u0 + 4 * k * D, ldu, y2, lda, 2.0)
+        if need_W:
+            dW = _dyt_x(U, x, Wcat.shape)
+        if need_x:
+            dx = U @ Wcat
+        if need_h:
+            g = torch.empty(gr.n_edges, dtype=torch.float32, device=dY.device)
+            _lib.check(L.sgs_sddmm_csr(_ptr(A), _ptr(B), N, lda, gr.n_edges, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid), _ptr(g), None,
+                                       _stream()), "sgs_sddmm_csr")
+        return dx, dW, dbias, (_handle_grad(nm, g) if g is not None else None), None, None, None, None, None, None
+
+
+def cheb_conv(x, Wcat, bias, nm: Norm, K: int, act=ACT_NONE, p=0.0, seed=0, site=0):
+    """One Chebyshev layer of order K >= 2 as one autograd node: act(sum_k T_k(L_hat) x W_k^T + bias), L_hat from `nm` (cheb_norm).
+    `Wcat` [K out, in] holds W_0 .. W_{K-1} stacked by rows.  Gradients go to x, Wcat, bias and, through nm.handle, the edge weights.
+    K = 1 is a plain Linear and has no graph step: ChebConv keeps that path."""
+    _need_gpu(x, Wcat, bias)
+    K = int(K)
+    if K < 2:
+        raise ValueError(f"cheb_conv: K = {K}: the fused recurrence starts at K = 2 (K = 1 is x W_0^T + bias, no graph step)")
+    if not cheb_supported(K):
+        raise ValueError(f"cheb_conv: K = {K} is not supported (1 <= K <= 8)")
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != nm.graph.N:
+        raise RuntimeError("cheb_conv: x must be float32 [N, F]")
+    if Wcat.dim() != 2 or Wcat.shape[0] % K != 0 or Wcat.shape[1] != x.shape[1] or Wcat.dtype != torch.float32:
+        raise RuntimeError(f"cheb_conv: Wcat must be float32 [K * out, {x.shape[1]}]")
+    if nm.what_loop is not None or nm.dis is None:
+        raise RuntimeError("cheb_conv: `nm` must come from cheb_norm")
+    return _ChebConv.apply(x.contiguous(), Wcat.contiguous(), bias, nm.handle, nm, K, act, float(p), int(seed), int(site))

@@ -194,11 +194,19 @@ def sharded_propagate(xl, nm, bias, act=ops.ACT_NONE, p=0.0, seed=0, site=0):
     return Y
 
 
+def _no_cheb_order(model, where):
+    """The sharded paths are written for the GCN head; a Chebyshev head of order > 1 must not fall into any K = 1 shortcut here."""
+    if getattr(model, "cheb_k", 1) > 1:
+        raise NotImplementedError(f"{where}: ChebModel(cheb_k={model.cheb_k}) is not built for the sharded trainers (single-GPU train / "
+                                  "evaluate serve cheb_k > 1)")
+
+
 @torch.no_grad()
 def sharded_evaluate_forward(args, model, shard: EdgeShard, q: int, noise_local=None, seed: int = 0, stream_id: int = 1):
     """evaluate.py:14-20 (mode 'learned', model.eval()) on an edge-sharded graph: EdgeProbGCN encoder over
     all E edges, scores for the local edges, one global istest draw, weighted 2-layer GCN -> logits
     (replicated on every rank).  Returns (logits, local SampleResult)."""
+    _no_cheb_order(model, "sharded_evaluate_forward")
     sc = model.edge_prob_mlp
     x, N = shard.x, shard.N
     H = sc.fc1.weight.shape[0]
@@ -380,6 +388,7 @@ def train_step_sharded(args, model, shard: EdgeShard, optimizer_gnn, optimizer_e
     global ids, so the result matches the unsharded step up to fp32 summation order.  Returns a trace dict."""
     from .model import _DropoutClock
     from .sampling import _NoiseClock
+    _no_cheb_order(model, "train_step_sharded")
     noise = noise or {}
     model.train()
     optimizer_edge_prob.zero_grad()
@@ -740,6 +749,7 @@ def train_step_blocksharded(args, model, shard: EdgeShard, optimizer_gnn, optimi
     `learned_out` is the full [N, C] table (all-gathered for the regulariser anyway)."""
     from .model import _DropoutClock
     from .sampling import _NoiseClock
+    _no_cheb_order(model, "train_step_blocksharded")
     noise = noise or {}
     model.train()
     optimizer_edge_prob.zero_grad()

@@ -326,6 +326,8 @@ class StepGraphs:
         g.in_ptr, g.out_ptr = torch.zeros(N + 1, **i32), torch.zeros(N + 1, **i32)
         g.in_src, g.in_eid, g.out_dst, g.out_eid = (torch.zeros(max(Ecap, 1), **i32) for _ in range(4))
         g.loop_eid = torch.full((max(N, 1),), -1, **i32)
+        g.restaged = True        # the arrays change with every partition: what is derived from them must be staged too (the unit GCN norm
+                                 # below) or recomputed inside the captured step (ops.cheb_norm), never remembered on the object
         ei._sgs_graph, ei._sgs_graph_version = g, ei._version
         ei._sgs_src_sorted = (self.src_sorted, ei._version)
         s.graph = g
