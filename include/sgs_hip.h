@@ -702,6 +702,29 @@ int sgs_gat_alpha_heads_bwd(const float* a_src, const float* a_dst, int64_t N, i
                             const int32_t* in_src, const int32_t* in_eid, float negative_slope, float p_drop, uint64_t seed, uint32_t site,
                             const float* soft, const float* soft_loop, const float* galpha, const float* gloop, float* g_edge, float* g_selfloop,
                             float* d_a_dst, sgs_stream_t stream);
+/* The same softmax with an edge term (PyG 2.3.1 GATConv(edge_dim = 1), edge_attr = the edge weight, restated): with edge_w [n_edges] by
+ * edge id and edge_coef [K] (c_h = <lin_edge.weight[h, :], att_edge[h, :]>, computed by the caller) the logit of edge e = (s -> i) is
+ * leaky_relu(a_src[s, h] + a_dst[i, h] + edge_w[e] c_h); (i, i) entries are removed, entries of weight 0 stay, and the added loop of
+ * node i carries wbar_i = the mean weight of i's remaining in-edges (fill_value = 'mean'; 0 without any).  Everything after the logit
+ * (softmax, dropout sites and keys, outputs) is sgs_gat_alpha_heads_fwd's; 1 <= K <= 16, K = 1 included.  The forward also writes
+ * loop_w [N] = wbar and loop_inv_cnt [N] = 1 / cnt_i (0 without in-edges) from the row walk it makes anyway; the backward reads them.
+ * Backward: g_edge / g_selfloop / d_a_dst as sgs_gat_alpha_heads_bwd, and
+ *   d_edge_w[e]    = sum_h c_h (g_edge[e, h] + g_selfloop[i, h] / cnt_i) (+ dw_add[e] unless NULL: a second layer's gradient, summed on
+ *                    the way out), 0 for (i, i) entries;
+ *   d_edge_coef[h] = sum_e edge_w[e] g_edge[e, h] + sum_i wbar_i g_selfloop[i, h]: per-workgroup partials in ws
+ *                    (sgs_gat_alpha_heads_edge_bwd_workspace_bytes(N, K)), added in a fixed order by a second small launch.
+ * No float atomics, no host synchronisation. */
+int sgs_gat_alpha_heads_edge_fwd(const float* a_src, const float* a_dst, const float* edge_w, const float* edge_coef, int64_t N, int64_t K,
+                                 int64_t n_edges, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, float negative_slope,
+                                 float p_drop, uint64_t seed, uint32_t site, float* soft, float* soft_loop, float* alpha, float* alpha_loop,
+                                 float* loop_w, float* loop_inv_cnt, sgs_stream_t stream);
+size_t sgs_gat_alpha_heads_edge_bwd_workspace_bytes(int64_t N, int64_t K);
+int sgs_gat_alpha_heads_edge_bwd(const float* a_src, const float* a_dst, const float* edge_w, const float* edge_coef, const float* loop_w,
+                                 const float* loop_inv_cnt, int64_t N, int64_t K, int64_t n_edges, const int32_t* in_ptr, const int32_t* in_src,
+                                 const int32_t* in_eid, float negative_slope, float p_drop, uint64_t seed, uint32_t site, const float* soft,
+                                 const float* soft_loop, const float* galpha, const float* gloop, const float* dw_add, float* g_edge,
+                                 float* g_selfloop, float* d_a_dst, float* d_edge_w, float* d_edge_coef, void* ws, size_t ws_bytes,
+                                 sgs_stream_t stream);
 /* out[j, h] = sum over row j of the CSR (ptr, eid) of g_edge[eid_k, h] (+ g_self[j, h] unless NULL), in CSR order: d a_src over the out-CSR. */
 int sgs_edge_sum_by_row_heads(const float* g_edge, const float* g_self, int64_t N, int64_t K, int64_t nnz, const int32_t* ptr, const int32_t* eid,
                               float* out, sgs_stream_t stream);

@@ -7,7 +7,8 @@
 //   existing self loops removed, one loop per node added
 //   e_k = leaky_relu(a_s[src_k] + a_d[dst_k], 0.2);  alpha = softmax over each node's in-edges
 //   alpha = dropout(alpha, p)  (training);  out[i] = sum_k alpha_k x'[src_k] + bias
-// `edge_weight` is ignored by PyG's GAT (supports_edge_weight = False).
+// `edge_weight` is ignored by PyG's GAT (supports_edge_weight = False) unless the layers are built with edge_dim = 1:
+// the gat_alpha_heads_edge_* kernels below then add the edge term to the logit.
 // The aggregation itself reuses sgs_spmm_csr (val = alpha, diag = loop alpha); this file holds the
 // segment softmax and its backward.  One wave per destination node; rows are walked three times
 // (max, sum, normalise) from L2.
@@ -394,6 +395,186 @@ __global__ void __launch_bounds__(kT) gat_alpha_heads_bwd(const float* __restric
         const float dl = sl * (gl - dot) * (pre > 0.f ? 1.f : slope);
         gsl[i * K + h] = dl;
         d_ad[i * K + h] = dad + dl;
+    }
+}
+
+// ---- edge-weighted attention (GATConv edge_dim = 1 with the edge weight as the attribute): the logit of edge e = (s -> i), head h is
+//   leaky_relu(a_s[s, h] + a_d[i, h] + w_e c_h),   c_h = <lin_edge.weight[h, :], att_edge[h, :]>  (host side, [K]),
+// and the added loop of node i carries the mean weight of i's non-self in-edges (fill_value = 'mean'; 0 without any):
+//   leaky_relu(a_s[i, h] + a_d[i, h] + wbar_i c_h).
+// `w` is [n] by edge id.  The kernels are variants of gat_alpha_heads_fwd / _bwd of their own (the unweighted kernels' code is untouched);
+// K = 1 runs their KP = 1 instantiation.  The first walk of the forward (the row maximum) also sums the row's weights, so wbar_i and
+// 1 / cnt_i cost no launch; both are kept for the backward ([N] each).
+__device__ __forceinline__ float edge_logit(float as, float ad, float w, float c, float slope) { return lrelu(fmaf(w, c, as + ad), slope); }
+
+template <int KP>
+__global__ void __launch_bounds__(kT) gat_alpha_heads_edge_fwd(const float* __restrict__ a_s, const float* __restrict__ a_d,
+                                                              const float* __restrict__ w, const float* __restrict__ coef, int64_t N, int K,
+                                                              const int* __restrict__ in_ptr, const int* __restrict__ in_src,
+                                                              const int* __restrict__ in_eid, float slope, float drop_scale, uint32_t drop_thresh,
+                                                              int use_drop, uint64_t seed, uint32_t site, const uint64_t* __restrict__ epoch,
+                                                              float* __restrict__ soft, float* __restrict__ soft_loop, float* __restrict__ alpha,
+                                                              float* __restrict__ alpha_loop, float* __restrict__ wbar, float* __restrict__ inv_cnt) {
+    constexpr int EPW = 64 / KP;
+    seed = fold_epoch(seed, epoch);
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    if (i >= N) return;                                       // wave-uniform
+    const int h = lane & (KP - 1), sub = lane / KP;
+    const bool hv = h < K;
+    const int hc = hv ? h : 0;
+    const int b = in_ptr[i], e = in_ptr[i + 1];
+    const float ad = a_d[i * K + hc];
+    const float c = coef[hc];
+    float mx = -INFINITY, wsum = 0.f, cnt = 0.f;
+    for (int k = b + sub; k < e; k += EPW) {
+        const int s = in_src[k];
+        if (s != static_cast<int>(i)) {
+            const float we = w[in_eid[k]];
+            mx = fmaxf(mx, edge_logit(a_s[static_cast<int64_t>(s) * K + hc], ad, we, c, slope));
+            wsum += we;
+            cnt += 1.f;
+        }
+    }
+    wsum = head_sum_all<KP>(wsum);                            // over the entries (the KP lanes of an entry hold the same weight)
+    cnt = head_sum_all<KP>(cnt);
+    const float icnt = cnt > 0.f ? 1.0f / cnt : 0.f;
+    const float wb = wsum * icnt;
+    const float eloop = edge_logit(a_s[i * K + hc], ad, wb, c, slope);
+    mx = fmaxf(head_max_all<KP>(mx), eloop);
+    float sum = 0.f;
+    for (int k = b + sub; k < e; k += EPW) {
+        const int s = in_src[k];
+        if (s != static_cast<int>(i)) sum += expf(edge_logit(a_s[static_cast<int64_t>(s) * K + hc], ad, w[in_eid[k]], c, slope) - mx);
+    }
+    sum = head_sum_all<KP>(sum) + expf(eloop - mx);
+    const float inv = 1.0f / (sum + 1e-16f);                  // torch_geometric.utils.softmax: / (sum + 1e-16)
+    for (int k = b + sub; k < e; k += EPW) {
+        const int s = in_src[k];
+        const int64_t ed = in_eid[k];
+        float sm = 0.f, al = 0.f;
+        if (s != static_cast<int>(i)) {
+            sm = expf(edge_logit(a_s[static_cast<int64_t>(s) * K + hc], ad, w[ed], c, slope) - mx) * inv;
+            al = sm;
+            if (use_drop) al = dropout_keep_at(seed, site, static_cast<uint64_t>(ed), static_cast<uint32_t>(hc), drop_thresh) ? sm * drop_scale : 0.f;
+        }
+        if (hv) {
+            soft[ed * K + h] = sm;
+            alpha[ed * K + h] = al;
+        }
+    }
+    if (sub == 0 && hv) {
+        const float sm = expf(eloop - mx) * inv;
+        float al = sm;
+        if (use_drop) al = dropout_keep_at(seed, site + 1u, static_cast<uint64_t>(i), static_cast<uint32_t>(h), drop_thresh) ? sm * drop_scale : 0.f;
+        soft_loop[i * K + h] = sm;
+        alpha_loop[i * K + h] = al;
+    }
+    if (lane == 0) { wbar[i] = wb; inv_cnt[i] = icnt; }
+}
+
+// gat_alpha_heads_bwd with the edge term: ge / gsl / d_ad as there, plus
+//   dw[e]  = sum_h c_h (ge[e, h] + gsl[i, h] / cnt_i)  (+ dw_add[e])   for e into i, 0 for (i, i) entries -- the K lanes of an entry are
+//            added by xor-shuffles below KP, one lane stores; `dw_add` [n] or NULL: the other layer's d w, summed on the way out;
+//   dc[h]  = sum_e w_e ge[e, h] + sum_i wbar_i gsl[i, h]: the workgroup's rows are added in wave order into part[blockIdx.x, h]
+//            ([gridDim.x, K]; gat_edge_dc_finish adds the workgroups in a fixed order).
+// The second walk runs wave-uniform trips (every lane takes part in the shuffles of its entry).
+template <int KP>
+__global__ void __launch_bounds__(kT) gat_alpha_heads_edge_bwd(const float* __restrict__ a_s, const float* __restrict__ a_d,
+                                                              const float* __restrict__ w, const float* __restrict__ coef,
+                                                              const float* __restrict__ wbar, const float* __restrict__ inv_cnt, int64_t N, int K,
+                                                              const int* __restrict__ in_ptr, const int* __restrict__ in_src,
+                                                              const int* __restrict__ in_eid, float slope, float drop_scale, uint32_t drop_thresh,
+                                                              int use_drop, uint64_t seed, uint32_t site, const uint64_t* __restrict__ epoch,
+                                                              const float* __restrict__ soft, const float* __restrict__ soft_loop,
+                                                              const float* __restrict__ galpha, const float* __restrict__ gloop,
+                                                              const float* __restrict__ dw_add, float* __restrict__ ge, float* __restrict__ gsl,
+                                                              float* __restrict__ d_ad, float* __restrict__ dw, float* __restrict__ part) {
+    constexpr int EPW = 64 / KP;
+    __shared__ float red[kT / 64][kMaxHeads];
+    seed = fold_epoch(seed, epoch);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    const int h = lane & (KP - 1), sub = lane / KP;
+    const bool hv = h < K;
+    const int hc = hv ? h : 0;
+    float dc = 0.f;
+    if (i < N) {                                              // wave-uniform; every wave reaches the barrier below
+        const int b = in_ptr[i], e = in_ptr[i + 1];
+        const float ad = a_d[i * K + hc];
+        const float c = coef[hc];
+        const float wb = wbar[i], icnt = inv_cnt[i];
+        auto dsm_edge = [&](int64_t ed) {
+            float g = galpha[ed * K + hc];
+            if (use_drop) g = dropout_keep_at(seed, site, static_cast<uint64_t>(ed), static_cast<uint32_t>(hc), drop_thresh) ? g * drop_scale : 0.f;
+            return g;
+        };
+        float gl = gloop[i * K + hc];
+        if (use_drop) gl = dropout_keep_at(seed, site + 1u, static_cast<uint64_t>(i), static_cast<uint32_t>(hc), drop_thresh) ? gl * drop_scale : 0.f;
+        const float sl = soft_loop[i * K + hc];
+        float dot = 0.f;
+        for (int k = b + sub; k < e; k += EPW)
+            if (in_src[k] != static_cast<int>(i)) {
+                const int64_t ed = in_eid[k];
+                dot += soft[ed * K + hc] * dsm_edge(ed);
+            }
+        dot = head_sum_all<KP>(dot) + sl * gl;
+        const float prel = fmaf(wb, c, a_s[i * K + hc] + ad);
+        const float dl = sl * (gl - dot) * (prel > 0.f ? 1.f : slope);
+        const float cm = hv ? c : 0.f;                        // lanes past K add nothing to an entry's d w
+        const float loop_term = dl * icnt;
+        float dad = 0.f;
+        for (int k0 = b; k0 < e; k0 += EPW) {
+            const int k = k0 + sub;
+            const bool in = k < e;
+            const int s = in ? in_src[k] : static_cast<int>(i);
+            const int64_t ed = in ? in_eid[k] : 0;
+            const bool edge = in && s != static_cast<int>(i);
+            float dpre = 0.f, t = 0.f;
+            if (edge) {
+                const float we = w[ed];
+                const float pre = fmaf(we, c, a_s[static_cast<int64_t>(s) * K + hc] + ad);
+                dpre = soft[ed * K + hc] * (dsm_edge(ed) - dot) * (pre > 0.f ? 1.f : slope);
+                dc = fmaf(we, dpre, dc);
+                t = cm * (dpre + loop_term);
+            }
+            if (in && hv) ge[ed * K + h] = dpre;
+            dad += dpre;
+#pragma unroll
+            for (int o = KP >> 1; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+            if (in && h == 0) dw[ed] = dw_add ? dw_add[ed] + t : t;
+        }
+        dad = head_sum_all<KP>(dad);
+        dc = fmaf(wb, dl, head_sum_all<KP>(dc));
+        if (sub == 0 && hv) {
+            gsl[i * K + h] = dl;
+            d_ad[i * K + h] = dad + dl;
+        }
+    }
+    if (sub == 0 && hv) red[wave][h] = dc;
+    __syncthreads();
+    if (threadIdx.x < K) {
+        float acc = 0.f;
+#pragma unroll
+        for (int v = 0; v < kT / 64; ++v) acc += red[v][threadIdx.x];
+        part[static_cast<int64_t>(blockIdx.x) * K + threadIdx.x] = acc;
+    }
+}
+
+// dc[h] = sum over the workgroups' partial rows part[nwg, K], fixed order: thread (g, h) adds rows g, g + 64, ... and the 64 groups are then
+// added in order.
+__global__ void __launch_bounds__(1024) gat_edge_dc_finish(const float* __restrict__ part, int nwg, int K, float* __restrict__ dc) {
+    __shared__ float red[64][kMaxHeads];
+    const int h = threadIdx.x & (kMaxHeads - 1), g = threadIdx.x >> 4;
+    float acc = 0.f;
+    if (h < K)
+        for (int r = g; r < nwg; r += 64) acc += part[static_cast<int64_t>(r) * K + h];
+    red[g][h] = acc;
+    __syncthreads();
+    if (threadIdx.x < K) {
+        float s = 0.f;
+        for (int v = 0; v < 64; ++v) s += red[v][threadIdx.x];
+        dc[threadIdx.x] = s;
     }
 }
 
@@ -909,6 +1090,57 @@ int sgs_gat_alpha_heads_bwd(const float* a_src, const float* a_dst, int64_t N, i
     SGS_DISPATCH_KP(gat_alpha_heads_bwd, K, dim3(static_cast<unsigned>(cdiv(N * 64, kT))), stream, a_src, a_dst, N, static_cast<int>(K), in_ptr, in_src,
                     in_eid, negative_slope, 1.0f / (1.0f - p_drop), dropout_thresh(p_drop), p_drop > 0.f ? 1 : 0, seed, site, epoch_ptr(), soft,
                     soft_loop, galpha, gloop, g_edge, g_selfloop, d_a_dst);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_gat_alpha_heads_edge_fwd(const float* a_src, const float* a_dst, const float* edge_w, const float* edge_coef, int64_t N, int64_t K,
+                                 int64_t n_edges, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, float negative_slope,
+                                 float p_drop, uint64_t seed, uint32_t site, float* soft, float* soft_loop, float* alpha, float* alpha_loop,
+                                 float* loop_w, float* loop_inv_cnt, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int64_t C = 1;
+    SGS_REQUIRE_HEADS("sgs_gat_alpha_heads_edge_fwd");
+    SGS_REQUIRE(N >= 0 && n_edges >= 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_gat_alpha_heads_edge_fwd: bad arguments");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(a_src && a_dst && edge_coef && in_ptr && soft_loop && alpha_loop && loop_w && loop_inv_cnt &&
+                    (n_edges == 0 || (edge_w && in_src && in_eid && soft && alpha)),
+                SGS_EINVAL, "sgs_gat_alpha_heads_edge_fwd: null pointer");
+    SGS_DISPATCH_KP(gat_alpha_heads_edge_fwd, K, dim3(static_cast<unsigned>(cdiv(N * 64, kT))), stream, a_src, a_dst, edge_w, edge_coef, N,
+                    static_cast<int>(K), in_ptr, in_src, in_eid, negative_slope, 1.0f / (1.0f - p_drop), dropout_thresh(p_drop), p_drop > 0.f ? 1 : 0,
+                    seed, site, epoch_ptr(), soft, soft_loop, alpha, alpha_loop, loop_w, loop_inv_cnt);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+size_t sgs_gat_alpha_heads_edge_bwd_workspace_bytes(int64_t N, int64_t K) {
+    if (N < 0) N = 0;
+    if (K < 0) K = 0;
+    return static_cast<size_t>(cdiv(N * 64, kT)) * static_cast<size_t>(K) * 4 + 256;
+}
+
+int sgs_gat_alpha_heads_edge_bwd(const float* a_src, const float* a_dst, const float* edge_w, const float* edge_coef, const float* loop_w,
+                                 const float* loop_inv_cnt, int64_t N, int64_t K, int64_t n_edges, const int32_t* in_ptr, const int32_t* in_src,
+                                 const int32_t* in_eid, float negative_slope, float p_drop, uint64_t seed, uint32_t site, const float* soft,
+                                 const float* soft_loop, const float* galpha, const float* gloop, const float* dw_add, float* g_edge,
+                                 float* g_selfloop, float* d_a_dst, float* d_edge_w, float* d_edge_coef, void* ws, size_t ws_bytes,
+                                 sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int64_t C = 1;
+    SGS_REQUIRE_HEADS("sgs_gat_alpha_heads_edge_bwd");
+    SGS_REQUIRE(N >= 0 && n_edges >= 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_gat_alpha_heads_edge_bwd: bad arguments");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(a_src && a_dst && edge_coef && loop_w && loop_inv_cnt && in_ptr && soft_loop && gloop && g_selfloop && d_a_dst && d_edge_coef &&
+                    (n_edges == 0 || (edge_w && in_src && in_eid && soft && galpha && g_edge && d_edge_w)),
+                SGS_EINVAL, "sgs_gat_alpha_heads_edge_bwd: null pointer");
+    SGS_REQUIRE(ws && ws_bytes >= sgs_gat_alpha_heads_edge_bwd_workspace_bytes(N, K), SGS_EWORKSPACE,
+                "sgs_gat_alpha_heads_edge_bwd: workspace too small");
+    const int nwg = static_cast<int>(cdiv(N * 64, kT));
+    float* part = static_cast<float*>(ws);
+    SGS_DISPATCH_KP(gat_alpha_heads_edge_bwd, K, dim3(static_cast<unsigned>(nwg)), stream, a_src, a_dst, edge_w, edge_coef, loop_w, loop_inv_cnt, N,
+                    static_cast<int>(K), in_ptr, in_src, in_eid, negative_slope, 1.0f / (1.0f - p_drop), dropout_thresh(p_drop), p_drop > 0.f ? 1 : 0,
+                    seed, site, epoch_ptr(), soft, soft_loop, galpha, gloop, dw_add, g_edge, g_selfloop, d_a_dst, d_edge_w, part);
+    hipLaunchKernelGGL(gat_edge_dc_finish, dim3(1), dim3(1024), 0, stream, part, nwg, static_cast<int>(K), d_edge_coef);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }

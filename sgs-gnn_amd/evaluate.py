@@ -128,6 +128,8 @@ def _batched_ok(args, model, n_draws) -> bool:
         return False
     if getattr(model, "gat_heads", 1) > 1:      # the batched engine's GAT pass is written for one attention head: serial loop
         return False
+    if getattr(model, "gat_edge_weight", False):    # the batched engine's GAT pass computes the logits without an edge term; with
+        return False                                # gat_edge_weight every draw's weights enter its attention: serial loop
     if getattr(model, "cheb_k", 1) > 1:         # the batched engine's Chebyshev branch computes one set of logits per partition BECAUSE the
         return False                            # graph does not enter at K = 1; with cheb_k > 1 every draw has its own: serial loop
     return _head_of(model) in heads

@@ -118,15 +118,21 @@ SITE_GAT_ATT, SITE_GAT_ACT = 16, 32          # attention dropout uses site, site
 class GATConv(nn.Module):
     """PyG 2.3.1 GATConv as torch_geometric.nn.models.GAT instantiates it: parameters `lin_src.weight` [heads * out, in] (shared with
     `lin_dst.weight`), `att_src`, `att_dst` [1, heads, out], `bias` [heads * out] (concat) or [out] (mean over heads).  heads = 1 runs the
-    one-head kernels; 2 <= heads <= 16 the fused per-head ones (x' = lin_src(x) viewed as [N, heads, out], head-major columns)."""
+    one-head kernels; 2 <= heads <= 16 the fused per-head ones (x' = lin_src(x) viewed as [N, heads, out], head-major columns).
+    edge_dim = 1 adds `lin_edge.weight` [heads * out, 1] (no bias) and `att_edge` [1, heads, out]: a forward given `edge_weight` then adds
+    edge_weight[e] * c_h, c_h = <lin_edge.weight[h, :], att_edge[h, :]>, to the logits (the added loops carry the mean weight of their
+    node's in-edges), on the per-head kernels for every head count; without `edge_weight` it is the layer above and the two parameters
+    get no gradient."""
 
-    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0):
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, edge_dim=None):
         super().__init__()
         heads = int(heads)
         if not 1 <= heads <= 16 or out_channels < 1:
             raise ValueError(f"GATConv: heads = {heads}, out_channels = {out_channels}: 1 <= heads <= 16 and out_channels >= 1 are supported")
+        if edge_dim not in (None, 1):
+            raise ValueError(f"GATConv: edge_dim = {edge_dim!r}: None and 1 (the edge weight as the attribute) are supported")
         self.in_channels, self.out_channels, self.negative_slope, self.dropout = in_channels, out_channels, negative_slope, dropout
-        self.heads, self.concat = heads, bool(concat)
+        self.heads, self.concat, self.edge_dim = heads, bool(concat), edge_dim
         self.lin_src = nn.Linear(in_channels, heads * out_channels, bias=False)
         self.lin_dst = self.lin_src
         self.att_src = nn.Parameter(torch.empty(1, heads, out_channels))
@@ -137,53 +143,75 @@ class GATConv(nn.Module):
         b = math.sqrt(6.0 / (heads + out_channels))                   # [1, heads, out]: size(-2) + size(-1)
         nn.init.uniform_(self.att_src, -b, b)
         nn.init.uniform_(self.att_dst, -b, b)
+        if edge_dim is not None:                                      # after today's parameters: the default layer draws exactly as before
+            self.lin_edge = nn.Linear(edge_dim, heads * out_channels, bias=False)
+            self.att_edge = nn.Parameter(torch.empty(1, heads, out_channels))
+            e = math.sqrt(6.0 / (edge_dim + heads * out_channels))
+            nn.init.uniform_(self.lin_edge.weight, -e, e)
+            nn.init.uniform_(self.att_edge, -b, b)
 
-    def forward(self, x, edge_index, *, act=ops.ACT_NONE, p_act=0.0, seed=0, layer=0):
+    def edge_coef(self):
+        """c [heads]: (lin_edge(w).view(-1, heads, out) * att_edge).sum(-1) = w * c for a one-column attribute."""
+        return (self.lin_edge.weight.view(self.heads, self.out_channels) * self.att_edge.view(self.heads, self.out_channels)).sum(-1)
+
+    def forward(self, x, edge_index, edge_weight=None, *, act=ops.ACT_NONE, p_act=0.0, seed=0, layer=0):
         graph = ops.get_graph(edge_index, x.shape[0])
         xl = self.lin_src(x)
         a_s, a_d = ops.gat_scores(xl, self.att_src, self.att_dst, heads=self.heads)      # node-level dots, one pass over x'
         p_att = self.dropout if self.training else 0.0
+        if edge_weight is not None and self.edge_dim is None:
+            raise ValueError("GATConv: edge_weight needs edge_dim = 1")
+        edge = {} if edge_weight is None else {"edge_weight": edge_weight, "edge_coef": self.edge_coef()}
         return ops.gat_aggregate(xl, a_s, a_d, self.bias, graph, self.negative_slope, p_att, seed, SITE_GAT_ATT + 2 * layer, act,
-                                 p_act, seed, SITE_GAT_ACT + layer, heads=self.heads, concat=self.concat)
+                                 p_act, seed, SITE_GAT_ACT + layer, heads=self.heads, concat=self.concat, **edge)
 
 
 class GAT(nn.Module):
     """torch_geometric.nn.models.GAT(in, hidden, num_layers=2, out_channels, dropout, act='relu', heads=K): as PyG's GAT.init_conv, layer 0 is
-    GATConv(in, hidden // K, heads=K, concat=True) and the last layer GATConv(hidden, out, heads=K, concat=False)."""
+    GATConv(in, hidden // K, heads=K, concat=True) and the last layer GATConv(hidden, out, heads=K, concat=False).  edge_dim = 1 is handed
+    to both layers, and `edge_weight` then reaches them as their edge attribute (PyG: GAT(..., edge_dim=1) with
+    edge_attr = edge_weight.view(-1, 1))."""
     supports_edge_weight = False
 
-    def __init__(self, in_channels, hidden_channels, num_layers, out_channels, dropout=0.0, act='relu', heads=1):
+    def __init__(self, in_channels, hidden_channels, num_layers, out_channels, dropout=0.0, act='relu', heads=1, edge_dim=None):
         super().__init__()
         if num_layers != 2 or act != 'relu':
             raise NotImplementedError
         if hidden_channels % heads != 0:
             raise ValueError(f"Ensure that the number of output channels of 'GATConv' (got '{hidden_channels}') is divisible by the number "
                              f"of heads (got '{heads}')")
-        self.dropout, self.heads = dropout, int(heads)
-        self.convs = nn.ModuleList([GATConv(in_channels, hidden_channels // heads, heads=heads, concat=True, dropout=dropout),
-                                    GATConv(hidden_channels, out_channels, heads=heads, concat=False, dropout=dropout)])
+        self.dropout, self.heads, self.edge_dim = dropout, int(heads), edge_dim
+        self.convs = nn.ModuleList([GATConv(in_channels, hidden_channels // heads, heads=heads, concat=True, dropout=dropout, edge_dim=edge_dim),
+                                    GATConv(hidden_channels, out_channels, heads=heads, concat=False, dropout=dropout, edge_dim=edge_dim)])
 
     def forward(self, x, edge_index, edge_weight=None):
-        # edge_weight is dropped, exactly as PyG's BasicGNN does for a conv without edge-weight support
+        # without edge_dim, edge_weight is dropped, exactly as PyG's BasicGNN does for a conv without edge-weight support
         p = self.dropout if self.training else 0.0
         act = ops.ACT_RELU_DROPOUT if p > 0 else ops.ACT_RELU
         seed = _DropoutClock.next_seed()
-        h = self.convs[0](x, edge_index, act=act, p_act=p, seed=seed, layer=0)
-        return self.convs[1](h, edge_index, seed=seed, layer=1)
+        if self.edge_dim is None or edge_weight is None:
+            h = self.convs[0](x, edge_index, act=act, p_act=p, seed=seed, layer=0)
+            return self.convs[1](h, edge_index, seed=seed, layer=1)
+        attr = ops.gat_edge_attr(ops.get_graph(edge_index, x.shape[0]), edge_weight)     # one autograd edge to the weights for both layers
+        h = self.convs[0](x, edge_index, attr, act=act, p_act=p, seed=seed, layer=0)
+        return self.convs[1](h, edge_index, attr, seed=seed, layer=1)
 
 
 class GATModel(nn.Module):
     """model.py:189-208.  `heads` is accepted and unused, as in the reference (its GATModel never hands it to GAT, so reference
-    checkpoints are one-head); the keyword-only `gat_heads` is what reaches GAT (default 1 = the reference's model)."""
+    checkpoints are one-head); the keyword-only `gat_heads` is what reaches GAT (default 1 = the reference's model).  The keyword-only
+    `gat_edge_weight=True` builds GAT(..., edge_dim=1): the sampled edge weights enter the attention logits and receive the task
+    gradient (default False = the reference's model, which drops them)."""
 
-    def __init__(self, in_channels, hidden_dim, num_classes, dropout_prob=0.3, heads=8, edge_mlp_type='MLP', *, gat_heads=1):
+    def __init__(self, in_channels, hidden_dim, num_classes, dropout_prob=0.3, heads=8, edge_mlp_type='MLP', *, gat_heads=1, gat_edge_weight=False):
         super().__init__()
         from .scorer import get_edge_mlp
         self.edge_prob_mlp = get_edge_mlp(in_channels, hidden_dim, dropout_prob, edge_mlp_type)
         self.dropout_prob = dropout_prob
         self.gat_heads = int(gat_heads)
+        self.gat_edge_weight = bool(gat_edge_weight)
         self.GAT = GAT(in_channels=in_channels, hidden_channels=hidden_dim, num_layers=2, out_channels=num_classes,
-                       dropout=dropout_prob, act='relu', heads=self.gat_heads)
+                       dropout=dropout_prob, act='relu', heads=self.gat_heads, edge_dim=1 if self.gat_edge_weight else None)
 
     def forward(self, data, edge_index, edge_weight=None):
         from .utils import segment

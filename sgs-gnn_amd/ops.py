@@ -1455,6 +1455,123 @@ class _GATAggregateHeads(torch.autograd.Function):
         return dxl, d_as, d_ad, dbias, None, None, None, None, None, None, None, None, None, None, None
 
 
+# ---- edge-weighted attention (GATConv edge_dim = 1 with the edge weight as the attribute; csrc/gat.hip, gat_alpha_heads_edge_*)
+class EdgeAttr(Norm):
+    """The edge weights of one forward as the GAT layers consume them: `w` [n_edges] by edge id and, when they require a gradient, the
+    autograd `handle` through which the layers' d w flow back (a Norm, so that the layers report through _handle_grad like the GCN and
+    Chebyshev heads: the second layer to finish adds the first one's d w on its way out and parks the total)."""
+    __slots__ = ("_extra_total",)
+
+
+class _GATEdgeAttr(torch.autograd.Function):
+    """The autograd edge from the layers' d w ([n_edges], edge-id order) back to the edge weights."""
+
+    @staticmethod
+    def forward(ctx, w, nm):
+        ctx.nm = nm
+        return torch.empty(w.numel(), dtype=torch.float32, device=w.device)
+
+    @staticmethod
+    def backward(ctx, g):
+        nm = ctx.nm
+        extra, total = getattr(nm, "_g_extra", None), getattr(nm, "_extra_total", False)
+        nm._g_first = nm._g_extra = None
+        nm._extra_total = False
+        if extra is None:
+            return g, None
+        return (extra if total else g + extra), None         # total: the parked gradient already holds both layers' sum
+
+
+def gat_edge_attr(graph: Graph, w) -> EdgeAttr:
+    """Wrap the edge weights `w` [n_edges] f32 for ops.gat_aggregate(edge_weight=...).  One wrapper per forward is meant to be shared by
+    both layers of the head, as one normalisation is by the GCN / Chebyshev layers."""
+    _need_gpu(w)
+    w = w.contiguous()
+    if w.dtype != torch.float32 or w.numel() != graph.n_edges:
+        raise RuntimeError(f"edge_weight must be float32 [{graph.n_edges}]")
+    nm = EdgeAttr()
+    nm.graph, nm.w, nm.handle, nm._park_ok, nm._extra_total = graph, w.detach(), None, False, False
+    nm._g_first = nm._g_extra = None
+    if w.requires_grad and torch.is_grad_enabled():
+        nm.handle = _GATEdgeAttr.apply(w, nm)
+        nm._park_ok = True        # _GATEdgeAttr.backward reads the parked second gradient
+    return nm
+
+
+class _GATAggregateEdge(torch.autograd.Function):
+    """_GATAggregateHeads with the edge term w_e c_h in the logit (and wbar_i c_h in the loop's); K = 1 included.  Forward: 2 launches
+    (softmax with the row's mean weight, aggregation); backward: _GATAggregateHeads' plus the finishing sum of d c (d w comes out of the
+    softmax backward itself)."""
+
+    @staticmethod
+    def forward(ctx, xl, a_s, a_d, bias, coef, handle, nm, K, concat, slope, p_att, seed_att, site_att, act, p_act, seed_act, site_act):
+        L = _lib.lib()
+        graph = nm.graph
+        N, D = xl.shape
+        C = D // K
+        n = graph.n_edges
+        f32 = dict(dtype=torch.float32, device=xl.device)
+        soft, alpha = torch.empty(max(n, 1), K, **f32), torch.empty(max(n, 1), K, **f32)
+        soft_loop, alpha_loop = torch.empty(N, K, **f32), torch.empty(N, K, **f32)
+        loop = torch.empty(2, max(N, 1), **f32)                # wbar, 1 / cnt
+        _lib.check(L.sgs_gat_alpha_heads_edge_fwd(_ptr(a_s), _ptr(a_d), _ptr(nm.w, torch.float32), _ptr(coef, torch.float32), N, K, n,
+                                                  _ptr(graph.in_ptr), _ptr(graph.in_src), _ptr(graph.in_eid), float(slope), float(p_att), seed_att,
+                                                  site_att, _ptr(soft), _ptr(soft_loop), _ptr(alpha), _ptr(alpha_loop), loop[0].data_ptr(),
+                                                  loop[1].data_ptr(), _stream()), "sgs_gat_alpha_heads_edge_fwd")
+        Y = _spmm_heads(xl, graph.in_ptr, graph.in_src, graph.in_eid, alpha, alpha_loop, HEADS_CONCAT if concat else HEADS_MEAN, bias, act,
+                        p_act, seed_act, site_act, N, K, C, n)
+        ctx.save_for_backward(xl, a_s, a_d, coef, soft, soft_loop, alpha, alpha_loop, loop, Y if act != ACT_NONE else None)
+        ctx.nm, ctx.slope, ctx.p_att, ctx.seed_att, ctx.site_att = nm, float(slope), float(p_att), seed_att, site_att
+        ctx.act, ctx.p_act, ctx.has_bias, ctx.K, ctx.concat = act, float(p_act), bias is not None, K, bool(concat)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        L = _lib.lib()
+        xl, a_s, a_d, coef, soft, soft_loop, alpha, alpha_loop, loop, Y = ctx.saved_tensors
+        nm, K = ctx.nm, ctx.K
+        gr = nm.graph
+        N, D = xl.shape
+        C = D // K
+        n = gr.n_edges
+        f32 = dict(dtype=torch.float32, device=xl.device)
+        dY = dY.contiguous()
+        dbias = None
+        if ctx.act != ACT_NONE and ctx.has_bias:
+            dZ, dbias = _act_bwd_colsum(dY, Y, ctx.act, ctx.p_act)
+        elif ctx.act != ACT_NONE:
+            dZ = torch.empty_like(dY)
+            _lib.check(L.sgs_act_bwd(_ptr(dY), _ptr(Y), dY.numel(), ctx.act, ctx.p_act, _ptr(dZ), _stream()), "sgs_act_bwd")
+        else:
+            dZ = dY
+            dbias = _colsum(dZ) if ctx.has_bias else None
+        dxl = _spmm_heads(dZ, gr.out_ptr, gr.out_dst, gr.out_eid, alpha, alpha_loop, HEADS_CONCAT if ctx.concat else HEADS_BROADCAST, None,
+                          ACT_NONE, 0.0, 0, 0, N, K, C, n)
+        galpha, gloop = torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32)
+        _lib.check(L.sgs_sddmm_csr_heads(_ptr(dZ), _ptr(xl), N, K, C, n, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid),
+                                         0 if ctx.concat else 1, _ptr(galpha), _ptr(gloop), _stream()), "sgs_sddmm_csr_heads")
+        g_edge, g_self, d_ad = torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32), torch.empty(N, K, **f32)
+        # the other layer's d w, if it has reported already, is added on the way out (no autograd add launch): see gat_edge_attr
+        second = nm._park_ok and nm._g_first is not None and nm._g_extra is None and nm._g_first.numel() == n
+        dw_add = nm._g_first.contiguous() if second else None
+        dw, dcoef = torch.empty(n, **f32), (torch.empty(K, **f32) if N > 0 else torch.zeros(K, **f32))
+        ws = workspace(L.sgs_gat_alpha_heads_edge_bwd_workspace_bytes(N, K), xl.device)
+        _lib.check(L.sgs_gat_alpha_heads_edge_bwd(_ptr(a_s), _ptr(a_d), _ptr(nm.w), _ptr(coef), loop[0].data_ptr(), loop[1].data_ptr(), N, K, n,
+                                                  _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid), ctx.slope, ctx.p_att, ctx.seed_att,
+                                                  ctx.site_att, _ptr(soft), _ptr(soft_loop), _ptr(galpha), _ptr(gloop), _ptr(dw_add), _ptr(g_edge),
+                                                  _ptr(g_self), _ptr(d_ad), _ptr(dw), _ptr(dcoef), ws.data_ptr(), ws.numel(), _stream()),
+                   "sgs_gat_alpha_heads_edge_bwd")
+        d_as = torch.empty(N, K, **f32)
+        _lib.check(L.sgs_edge_sum_by_row_heads(_ptr(g_edge), _ptr(g_self), N, K, n, _ptr(gr.out_ptr), _ptr(gr.out_eid), _ptr(d_as), _stream()),
+                   "sgs_edge_sum_by_row_heads")
+        g_handle = None
+        if ctx.needs_input_grad[5]:
+            g_handle = _handle_grad(nm, dw)
+            if second and g_handle is None:
+                nm._extra_total = True
+        return dxl, d_as, d_ad, dbias, dcoef, g_handle, None, None, None, None, None, None, None, None, None, None, None
+
+
 class _GATScoresHeads(torch.autograd.Function):
     """a_s[i, h] = <x'[i, h, :], att_src[h, :]>, a_d likewise, for K heads in one pass over x' (sgs_gat_scores_heads_fwd / _bwd)."""
 
@@ -1508,10 +1625,18 @@ def gat_scores(xl, att_src, att_dst, heads=1):
 
 
 def gat_aggregate(xl, a_s, a_d, bias, graph: Graph, negative_slope=0.2, p_att=0.0, seed_att=0, site_att=0, act=ACT_NONE,
-                  p_act=0.0, seed_act=0, site_act=0, heads=1, concat=True):
+                  p_act=0.0, seed_act=0, site_act=0, heads=1, concat=True, *, edge_weight=None, edge_coef=None):
     """Attention softmax + aggregation (+ bias / act / dropout).  heads = 1: the one-head kernels (`concat` has no effect on one head).
-    heads = K > 1: per-head softmax over x' [N, K C]; concat=True -> [N, K C], False -> the mean over heads [N, C]; `bias` matches."""
+    heads = K > 1: per-head softmax over x' [N, K C]; concat=True -> [N, K C], False -> the mean over heads [N, C]; `bias` matches.
+    `edge_weight` ([n_edges] f32 by edge id, or the EdgeAttr that gat_edge_attr made of it for both layers) with `edge_coef` [heads] adds
+    edge_weight[e] * edge_coef[h] to the logits (GATConv edge_dim = 1; the added loops carry their node's mean in-weight) on the per-head
+    kernels for every 1 <= heads <= 16, differentiable wrt both; both None (the default) = the kernels above, unchanged."""
     _need_gpu(xl, a_s, a_d, bias)
+    if (edge_weight is None) != (edge_coef is None):
+        raise RuntimeError("gat_aggregate: edge_weight and edge_coef come together")
+    if edge_weight is not None:
+        return _gat_aggregate_edge(xl, a_s, a_d, bias, graph, negative_slope, p_att, seed_att, site_att, act, p_act, seed_act, site_act, heads,
+                                   concat, edge_weight, edge_coef)
     if heads == 1:
         return _GATAggregate.apply(xl.contiguous(), a_s.contiguous(), a_d.contiguous(), bias, graph, float(negative_slope),
                                    float(p_att), int(seed_att), int(site_att), act, float(p_act), int(seed_act), int(site_act))
@@ -1523,6 +1648,26 @@ def gat_aggregate(xl, a_s, a_d, bias, graph: Graph, negative_slope=0.2, p_att=0.
         raise RuntimeError(f"gat_aggregate: bias must have {width} elements")
     return _GATAggregateHeads.apply(xl.contiguous(), a_s.contiguous(), a_d.contiguous(), bias, graph, heads, bool(concat), float(negative_slope),
                                     float(p_att), int(seed_att), int(site_att), act, float(p_act), int(seed_act), int(site_act))
+
+
+def _gat_aggregate_edge(xl, a_s, a_d, bias, graph, negative_slope, p_att, seed_att, site_att, act, p_act, seed_act, site_act, heads, concat,
+                        edge_weight, edge_coef):
+    nm = edge_weight if isinstance(edge_weight, EdgeAttr) else gat_edge_attr(graph, edge_weight)
+    _need_gpu(nm.w, edge_coef)
+    if nm.graph is not graph:
+        raise RuntimeError("gat_aggregate: edge_weight was wrapped for another graph")
+    heads = _check_heads(xl, heads)
+    N = xl.shape[0]
+    if a_s.numel() != N * heads or a_d.numel() != N * heads:
+        raise RuntimeError("gat_aggregate: a_s / a_d must be [N, heads]")
+    if edge_coef.numel() != heads or edge_coef.dtype != torch.float32:
+        raise RuntimeError(f"gat_aggregate: edge_coef must be float32 [{heads}]")
+    width = xl.shape[1] if concat else xl.shape[1] // heads
+    if bias is not None and bias.numel() != width:
+        raise RuntimeError(f"gat_aggregate: bias must have {width} elements")
+    return _GATAggregateEdge.apply(xl.contiguous(), a_s.reshape(N, heads).contiguous(), a_d.reshape(N, heads).contiguous(), bias,
+                                   edge_coef.reshape(heads).contiguous(), nm.handle, nm, heads, bool(concat), float(negative_slope), float(p_att),
+                                   int(seed_att), int(site_att), act, float(p_act), int(seed_act), int(site_act))
 
 
 # ------------------------------------------------------------------ node-level Linear with a hand-written weight gradient

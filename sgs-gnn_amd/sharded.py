@@ -195,10 +195,14 @@ def sharded_propagate(xl, nm, bias, act=ops.ACT_NONE, p=0.0, seed=0, site=0):
 
 
 def _no_cheb_order(model, where):
-    """The sharded paths are written for the GCN head; a Chebyshev head of order > 1 must not fall into any K = 1 shortcut here."""
+    """The sharded paths are written for the GCN head; a Chebyshev head of order > 1 must not fall into any K = 1 shortcut here, nor an
+    edge-weighted GAT head into a path that drops the weights."""
     if getattr(model, "cheb_k", 1) > 1:
         raise NotImplementedError(f"{where}: ChebModel(cheb_k={model.cheb_k}) is not built for the sharded trainers (single-GPU train / "
                                   "evaluate serve cheb_k > 1)")
+    if getattr(model, "gat_edge_weight", False):
+        raise NotImplementedError(f"{where}: GATModel(gat_edge_weight=True) is not built for the sharded trainers (single-GPU train / "
+                                  "evaluate serve gat_edge_weight)")
 
 
 @torch.no_grad()
