@@ -857,7 +857,25 @@ int sgs_adam_step_multi(const int64_t* desc_host, const float* hyper_host, int64
  * sgs_gat_alpha_fwd_multi: sgs_gat_alpha_fwd without attention dropout (p = 0, no soft_* outputs) over each draw's in-CSR (in_ptr
  *   [D, N+1], in_src [D, nnz] from sgs_graph_filter_multi): draw d reads a_src + d * a_stride, a_dst + d * a_stride (0: node scores
  *   shared by all draws; N: [D, N] blocks) and writes alpha_in [D, nnz] (0 at (i,i) entries), alpha_loop [D, N].  Same device code:
- *   row d is bitwise sgs_gat_alpha_fwd's.  1 <= D <= 65535. */
+ *   row d is bitwise sgs_gat_alpha_fwd's.  1 <= D <= 65535.
+ * The per-head GAT kernels and the Chebyshev step have the same draw-strided forms (forward only, no attention dropout, no kept softmax,
+ * no out-CSR; blockIdx.y = draw; an operand is addressed as base + d * stride, stride 0 = shared by all draws):
+ * sgs_gat_alpha_heads_fwd_multi: sgs_gat_alpha_heads_fwd (edge_coef NULL) or sgs_gat_alpha_heads_edge_fwd (edge_w [D, nnz] by the draw's
+ *   edge id, edge_coef [K]; every 1 <= K <= 16) at p = 0 over each draw's in-CSR (in_ptr [D, N+1], in_src / in_eid [D, nnz]); node
+ *   scores a_src / a_dst + d * a_stride (0: one [N, K] pair; N K: [D, N, K] blocks); alpha [D, nnz, K] by the draw's edge id,
+ *   alpha_loop [D, N, K].  The device code of a row is the single-draw kernel's: row d is bitwise its alpha / alpha_loop.
+ * sgs_spmm_csr_heads_multi: sgs_spmm_csr_heads, mode CONCAT (Y [D, N, K C]) or MEAN (Y [D, N, C]; the LDS form when a workgroup's rows fit
+ *   4096 floats, else lanes walk the heads: the single-draw choice), val [D, nnz, K], diag [D, N, K] or NULL, X + d * x_stride (0: shared);
+ *   bias / ReLU epilogue (act NONE or RELU).  Block d is bitwise sgs_spmm_csr_heads' for draw d.
+ * sgs_cheb_norm_fwd_multi: dis [D, N] and l_in [D, q] (dst-CSR entry order of each draw) of sgs_cheb_norm_fwd for w [D, q] by the draw's
+ *   edge id (NULL: unit weights).  The degree is summed by source without an out-CSR of the draws: the PARENT's out-CSR (pout_*) is walked
+ *   under draw d's mask [D, E_parent] with the weights scattered to [D, E_parent] by parent edge id (sampled_eid [D, q]; ws:
+ *   sgs_cheb_norm_fwd_multi_workspace_bytes(E_parent, D)), the selected entries handed to the lanes that own them in the filtered out-row,
+ *   so every partial sum adds the same values in the same order: dis and l_in are bitwise the single-draw results.
+ * sgs_cheb_spmm_multi: one sgs_cheb_spmm step for all draws, Y_d[i, :] = act(add_d[i, :] + alpha * sum_k val_d[k] X_d[col_d[k], :] -
+ *   sub_d[i, :] + bias); X, add, sub, Y keep their own leading dimensions and have their own draw strides (0: shared; Y's must give every
+ *   draw a block of its own); ptr [D, N+1], col / val [D, nnz]; act NONE or RELU, no Y2.  The row form (nnz per draw) and the vector width
+ *   follow sgs_cheb_spmm's rules: block d is bitwise that call's result. */
 size_t sgs_sample_topq_multi_workspace_bytes(int64_t E, int64_t D);
 int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
                           uint64_t stream_id0, int64_t D, int64_t E, int64_t q, const int64_t* edge_index, uint8_t* mask, int64_t* sampled_eid,
@@ -873,6 +891,21 @@ int sgs_spmm_csr_multi(const float* X, int64_t x_stride, int64_t N, int64_t Dc, 
 int sgs_gat_alpha_fwd_multi(const float* a_src, const float* a_dst, int64_t a_stride, int64_t N, int64_t D, int64_t nnz,
                             const int32_t* in_ptr, const int32_t* in_src, float negative_slope, float* alpha_in, float* alpha_loop,
                             sgs_stream_t stream);
+int sgs_gat_alpha_heads_fwd_multi(const float* a_src, const float* a_dst, int64_t a_stride, const float* edge_w, const float* edge_coef,
+                                  int64_t N, int64_t K, int64_t D, int64_t nnz, const int32_t* in_ptr, const int32_t* in_src,
+                                  const int32_t* in_eid, float negative_slope, float* alpha, float* alpha_loop, sgs_stream_t stream);
+int sgs_spmm_csr_heads_multi(const float* X, int64_t x_stride, int64_t N, int64_t K, int64_t C, int64_t nnz, int64_t D, const int32_t* ptr,
+                             const int32_t* col, const int32_t* eid, const float* val, const float* diag, int mode, const float* bias, int act,
+                             float* Y, sgs_stream_t stream);
+size_t sgs_cheb_norm_fwd_multi_workspace_bytes(int64_t E_parent, int64_t D);
+int sgs_cheb_norm_fwd_multi(const float* w, const int64_t* sampled_eid, const uint8_t* mask, int64_t q, int64_t N, int64_t E_parent, int64_t D,
+                            const int32_t* pout_ptr, const int32_t* pout_dst, const int32_t* pout_eid, const int32_t* in_ptr,
+                            const int32_t* in_src, const int32_t* in_eid, float* dis, float* l_in, void* ws, size_t ws_bytes,
+                            sgs_stream_t stream);
+int sgs_cheb_spmm_multi(int64_t K, const float* X, int64_t ldx, int64_t x_stride, int64_t N, int64_t D, int64_t nnz, int64_t n_draws,
+                        const int32_t* ptr, const int32_t* col, const float* val, float alpha, const float* add, int64_t ldadd,
+                        int64_t add_stride, const float* sub, int64_t ldsub, int64_t sub_stride, const float* bias, int act, float* Y, int64_t ldy,
+                        int64_t y_stride, sgs_stream_t stream);
 int sgs_ensemble_mean_correct(const float* logits, int64_t x_stride, int64_t Dc, int64_t N, int64_t C, float* acc, int first, int last,
                               int64_t D_total, const int64_t* y, const uint8_t* mask0, const uint8_t* mask1, const uint8_t* mask2, int64_t* counts,
                               sgs_stream_t stream);

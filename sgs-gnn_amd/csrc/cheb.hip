@@ -64,6 +64,75 @@ __global__ void __launch_bounds__(kT) cheb_weights(const float* __restrict__ w, 
     }
 }
 
+// ---- D drawn subgraphs of one partition (ensemble evaluation, forward only): blockIdx.y = draw d.
+// The engine has the drawn subgraphs' in-CSRs only (sgs_graph_filter_multi), and the degree is summed by SOURCE.  cheb_deg_multi walks the
+// PARENT's out-row of node i under draw d's mask instead of a filtered out-CSR: the filter keeps the parent's entry order, so the selected
+// entries of the row, in order, are the drawn subgraph's out-row, and entry number r of that row belongs to lane r % 64 of cheb_deg.  Each
+// step of 64 parent entries hands its selected values to those lanes with one ds_permute (the unselected lanes fill the other lanes with
+// +0, which changes no partial sum), so every lane adds the same values in the same order as cheb_deg over the filtered out-CSR and the
+// wave sum is the same tree: dis [D, N] is bitwise the single-draw result.  Weights are read by PARENT edge id (wE [D, E], scattered by
+// cheb_scatter_w_multi; only selected edges are read, so the rest of wE stays unwritten); wE == NULL = unit weights.
+__global__ void __launch_bounds__(kT) cheb_scatter_w_multi(const float* __restrict__ w, const int64_t* __restrict__ sampled_eid, int64_t q, int64_t E,
+                                                          float* __restrict__ wE) {
+    const int64_t j = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+    if (j >= q) return;
+    const int64_t d = blockIdx.y;
+    wE[d * E + sampled_eid[d * q + j]] = w[d * q + j];
+}
+
+__global__ void __launch_bounds__(kT) cheb_deg_multi(const float* __restrict__ wE, int64_t N, int64_t E, const int* __restrict__ pout_ptr,
+                                                    const int* __restrict__ pout_dst, const int* __restrict__ pout_eid,
+                                                    const uint8_t* __restrict__ mask, float* __restrict__ dis) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    if (i >= N) return;                                       // wave-uniform
+    const int64_t d = blockIdx.y;
+    const uint8_t* __restrict__ m = mask + d * E;
+    const float* __restrict__ w = wE ? wE + d * E : nullptr;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    float acc = 0.f;
+    int base = 0;                                             // selected entries of the row so far
+    const int b = pout_ptr[i], e = pout_ptr[i + 1];
+    for (int k0 = b; k0 < e; k0 += 64) {                      // wave-uniform trips: every lane takes part in the permute
+        const int k = k0 + lane;
+        bool sel = false;
+        float v = 0.f;
+        if (k < e) {
+            const int pe = pout_eid[k];
+            sel = m[pe] != 0;
+            if (sel && pout_dst[k] != static_cast<int>(i)) v = w ? w[pe] : 1.0f;
+        }
+        const unsigned long long bal = __ballot(sel);
+        const int cnt = __popcll(bal);
+        const int r = sel ? __popcll(bal & below) : cnt + __popcll(~bal & below);      // a permutation of 0 .. 63
+        acc += __int_as_float(__builtin_amdgcn_ds_permute(((base + r) & 63) << 2, __float_as_int(v)));
+        base += cnt;
+    }
+    acc = wave_sum_all(acc);
+    float di = 1.0f / sqrtf(acc);
+    if (isinf(di)) di = 0.f;
+    if (lane == 0) dis[d * N + i] = di;
+}
+
+// cheb_weights' in-rows for draw d: l_in [D, nnz] over the draw's in-CSR, w [D, nnz] by the draw's edge id (NULL: unit).
+__global__ void __launch_bounds__(kT) cheb_weights_multi(const float* __restrict__ w, int64_t N, int64_t nnz, const int* __restrict__ in_ptr,
+                                                        const int* __restrict__ in_src, const int* __restrict__ in_eid,
+                                                        const float* __restrict__ dis, float* __restrict__ l_in) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    if (r >= N) return;
+    const int64_t d = blockIdx.y;
+    in_ptr += d * (N + 1); in_src += d * nnz; in_eid += d * nnz; dis += d * N; l_in += d * nnz;
+    if (w) w += d * nnz;
+    const int i = static_cast<int>(r);
+    const float di = dis[i];
+    for (int k = in_ptr[i] + lane; k < in_ptr[i + 1]; k += 64) {
+        const int s = in_src[k];
+        const float we = w ? w[in_eid[k]] : 1.0f;
+        l_in[k] = (s == i) ? 0.f : -((dis[s] * we) * di);
+    }
+}
+
 // c_n = -1/2 dis_n^3 (sum_{e: s_e = n} -w_e dis[d_e] g_e + sum_{e: d_e = n} -dis[s_e] w_e g_e): what the degree of n passes back to
 // each of its out-edges' weights.  g2 (optional): a second layer's gradient over the same normalisation, summed on read.
 __global__ void __launch_bounds__(kT) cheb_norm_bwd_node(const float* __restrict__ w, const float* __restrict__ g, const float* __restrict__ g2,
@@ -138,6 +207,49 @@ __device__ __forceinline__ void finish(const StepArgs& a, int64_t i, int64_t c, 
 
 // Short rows (whole graphs of low degree): a group of LPR lanes owns one output row, each lane VEC consecutive columns per chunk,
 // four independent row gathers in flight (the load order sgs_spmm_csr settled on).
+// The *_body function below holds the same row code as the single-draw kernel after it and serves the multi-draw kernel only: calling
+// the body from the single-draw kernel as well changed that kernel's register allocation and instruction order, so it keeps its own text
+// ("The heads' options"); tests/test_gpu_ensemble_batched_variants.py pins the two bitwise equal per draw.  The
+// other *_body functions of this file follow the same rule.
+template <int VEC, int LPR>
+__device__ __forceinline__ void cheb_spmm_rows_body(const StepArgs& a, int64_t N, int64_t D, const int* __restrict__ ptr,
+                                                    const int* __restrict__ col, const float* __restrict__ val) {
+    using V = typename VecT<VEC>::type;
+    constexpr int RPB = kT / LPR;
+    const int sub = threadIdx.x % LPR;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * RPB + threadIdx.x / LPR;
+    if (i >= N) return;
+    const uint32_t rkey = dropout_row_key(fold_epoch(a.seed, a.epoch), a.site, static_cast<uint64_t>(i));
+    const int b = ptr[i], e = ptr[i + 1];
+    const float* __restrict__ X = a.X;
+    const int64_t ldx = a.ldx;
+    for (int64_t c0 = static_cast<int64_t>(sub) * VEC; c0 < D; c0 += static_cast<int64_t>(LPR) * VEC) {
+        float acc[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+        int k = b;
+        for (; k + 4 <= e; k += 4) {
+            int j[4]; float w[4]; float x[4][VEC];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { j[u] = col[k + u]; w[u] = val[k + u]; }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) *reinterpret_cast<V*>(x[u]) = *reinterpret_cast<const V*>(X + static_cast<int64_t>(j[u]) * ldx + c0);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
+        }
+        for (; k < e; ++k) {
+            float x[VEC];
+            *reinterpret_cast<V*>(x) = *reinterpret_cast<const V*>(X + static_cast<int64_t>(col[k]) * ldx + c0);
+            const float w = val[k];
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, x[v], acc[v]);
+        }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) finish(a, i, c0 + v, acc[v], rkey);
+    }
+}
 template <int VEC, int LPR>
 __global__ void __launch_bounds__(kT) cheb_spmm_rows(StepArgs a, int64_t N, int64_t D, const int* __restrict__ ptr,
                                                     const int* __restrict__ col, const float* __restrict__ val) {
@@ -180,6 +292,58 @@ __global__ void __launch_bounds__(kT) cheb_spmm_rows(StepArgs a, int64_t N, int6
 
 // Long rows (partitions: ~1k rows of tens to hundreds of entries): a workgroup of NW waves owns a row, each wave gathers a strided
 // share of its entries (8 in flight) and the partial sums meet in LDS in a fixed order.  NW = 16 for very long rows.
+template <int VEC, int NW>
+__device__ __forceinline__ void cheb_spmm_rowblock_body(const StepArgs& a, int64_t N, int64_t D, const int* __restrict__ ptr,
+                                                             const int* __restrict__ col, const float* __restrict__ val, float (*part)[64 * VEC]) {
+    using V = typename VecT<VEC>::type;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t i = blockIdx.x;
+    const int b = ptr[i], e = ptr[i + 1];
+    const uint32_t rkey = dropout_row_key(fold_epoch(a.seed, a.epoch), a.site, static_cast<uint64_t>(i));
+    const float* __restrict__ X = a.X;
+    const int64_t ldx = a.ldx;
+    for (int64_t cbase = 0; cbase < D; cbase += 64 * VEC) {
+        const int64_t c0 = cbase + static_cast<int64_t>(lane) * VEC;
+        float acc[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+        if (c0 < D) {
+            int k = b + wave;
+            for (; k + 7 * NW < e; k += 8 * NW) {
+                int j[8]; float w[8]; V x[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { j[u] = col[k + NW * u]; w[u] = val[k + NW * u]; }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) x[u] = *reinterpret_cast<const V*>(X + static_cast<int64_t>(j[u]) * ldx + c0);
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    float xv[VEC];
+                    *reinterpret_cast<V*>(xv) = x[u];
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], xv[v], acc[v]);
+                }
+            }
+            for (; k < e; k += NW) {
+                float xv[VEC];
+                *reinterpret_cast<V*>(xv) = *reinterpret_cast<const V*>(X + static_cast<int64_t>(col[k]) * ldx + c0);
+                const float w = val[k];
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, xv[v], acc[v]);
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) part[wave][lane * VEC + v] = acc[v];
+        __syncthreads();
+        const int t = threadIdx.x;                 // 64 * VEC columns finished by the first 64 * VEC threads
+        if (t < 64 * VEC && cbase + t < D) {
+            float s = 0.f;
+#pragma unroll
+            for (int g = 0; g < NW; g += 4) s += (part[g][t] + part[g + 1][t]) + (part[g + 2][t] + part[g + 3][t]);
+            finish(a, i, cbase + t, s, rkey);
+        }
+        __syncthreads();
+    }
+}
 template <int VEC, int NW>
 __global__ void __launch_bounds__(64 * NW) cheb_spmm_rowblock(StepArgs a, int64_t N, int64_t D, const int* __restrict__ ptr,
                                                              const int* __restrict__ col, const float* __restrict__ val) {
@@ -234,6 +398,34 @@ __global__ void __launch_bounds__(64 * NW) cheb_spmm_rowblock(StepArgs a, int64_
     }
 }
 
+// One recurrence step for the D drawn subgraphs of a partition (ensemble evaluation: forward only, bias / ReLU, no dropout, no Y2):
+// blockIdx.y = draw d.  Each dense operand keeps its leading dimension and has a draw stride of its own (0: shared by every draw -- the
+// layer-1 products Y_0 and, at K = 2, Y_1, which no step overwrites); ptr [D, N+1], col / val [D, nnz].  The bodies above run unchanged
+// on draw d's operands, and the host picks the row form and the vector width by sgs_cheb_spmm's rules, so block d is bitwise that call's.
+struct StepStrides { int64_t x, add, sub, y; };
+__device__ __forceinline__ StepArgs step_of_draw(StepArgs a, const StepStrides& st, int64_t d) {
+    a.X += d * st.x;
+    if (a.add) a.add += d * st.add;
+    if (a.sub) a.sub += d * st.sub;
+    a.Y += d * st.y;
+    return a;
+}
+template <int VEC, int LPR>
+__global__ void __launch_bounds__(kT) cheb_spmm_rows_multi(StepArgs a, StepStrides st, int64_t N, int64_t D, int64_t nnz,
+                                                          const int* __restrict__ ptr, const int* __restrict__ col,
+                                                          const float* __restrict__ val) {
+    const int64_t d = blockIdx.y;
+    cheb_spmm_rows_body<VEC, LPR>(step_of_draw(a, st, d), N, D, ptr + d * (N + 1), col + d * nnz, val + d * nnz);
+}
+template <int VEC, int NW>
+__global__ void __launch_bounds__(64 * NW) cheb_spmm_rowblock_multi(StepArgs a, StepStrides st, int64_t N, int64_t D, int64_t nnz,
+                                                                   const int* __restrict__ ptr, const int* __restrict__ col,
+                                                                   const float* __restrict__ val) {
+    __shared__ float part[NW][64 * VEC];
+    const int64_t d = blockIdx.y;
+    cheb_spmm_rowblock_body<VEC, NW>(step_of_draw(a, st, d), N, D, ptr + d * (N + 1), col + d * nnz, val + d * nnz, part);
+}
+
 inline int pick_lpr(int64_t D, int vec) {
     const int64_t need = (D + vec - 1) / vec;
     int lpr = 1;
@@ -253,6 +445,21 @@ void launch_rows(int lpr, hipStream_t stream, const StepArgs& a, int64_t N, int6
         case 16: hipLaunchKernelGGL((cheb_spmm_rows<VEC, 16>), g, b, 0, stream, a, N, D, ptr, col, val); break;
         case 32: hipLaunchKernelGGL((cheb_spmm_rows<VEC, 32>), g, b, 0, stream, a, N, D, ptr, col, val); break;
         default: hipLaunchKernelGGL((cheb_spmm_rows<VEC, 64>), g, b, 0, stream, a, N, D, ptr, col, val); break;
+    }
+}
+
+template <int VEC>
+void launch_rows_multi(int lpr, hipStream_t stream, const StepArgs& a, const StepStrides& st, int64_t N, int64_t D, int64_t nnz, int64_t Dr,
+                       const int* ptr, const int* col, const float* val) {
+    const dim3 g(static_cast<unsigned>(cdiv(N, kT / lpr)), static_cast<unsigned>(Dr)), b(kT);
+    switch (lpr) {
+        case 1: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 1>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
+        case 2: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 2>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
+        case 4: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 4>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
+        case 8: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 8>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
+        case 16: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 16>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
+        case 32: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 32>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
+        default: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 64>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
     }
 }
 
@@ -335,6 +542,77 @@ int sgs_cheb_spmm(int64_t K, const float* X, int64_t ldx, int64_t N, int64_t D, 
         launch_rows<4>(pick_lpr(D, 4), stream, a, N, D, ptr, col, val);
     } else {
         launch_rows<1>(pick_lpr(D, 1), stream, a, N, D, ptr, col, val);
+    }
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+// ---------------------------------------------------------------- multi-draw entry points (ensemble evaluation, forward only)
+size_t sgs_cheb_norm_fwd_multi_workspace_bytes(int64_t E_parent, int64_t D) {
+    if (E_parent < 0) E_parent = 0;
+    if (D < 0) D = 0;
+    return carve_bytes(static_cast<size_t>(E_parent) * static_cast<size_t>(D), 4) + 256;
+}
+
+int sgs_cheb_norm_fwd_multi(const float* w, const int64_t* sampled_eid, const uint8_t* mask, int64_t q, int64_t N, int64_t E_parent, int64_t D,
+                            const int32_t* pout_ptr, const int32_t* pout_dst, const int32_t* pout_eid, const int32_t* in_ptr,
+                            const int32_t* in_src, const int32_t* in_eid, float* dis, float* l_in, void* ws, size_t ws_bytes,
+                            sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(N >= 0 && q >= 0 && E_parent >= 0 && q <= E_parent && D >= 1 && D <= 65535, SGS_EINVAL,
+                "sgs_cheb_norm_fwd_multi: bad sizes (q <= E_parent; 1 <= D <= 65535)");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(pout_ptr && in_ptr && dis && (E_parent == 0 || (pout_dst && pout_eid && mask)) &&
+                    (q == 0 || (in_src && in_eid && l_in && (!w || sampled_eid))),
+                SGS_EINVAL, "sgs_cheb_norm_fwd_multi: null pointer");
+    float* wE = nullptr;
+    if (w && q > 0) {
+        SGS_REQUIRE(ws && ws_bytes >= sgs_cheb_norm_fwd_multi_workspace_bytes(E_parent, D), SGS_EWORKSPACE,
+                    "sgs_cheb_norm_fwd_multi: workspace too small");
+        Carver cv(ws);
+        wE = cv.take<float>(static_cast<size_t>(E_parent) * static_cast<size_t>(D));
+        hipLaunchKernelGGL(cheb_scatter_w_multi, dim3(static_cast<unsigned>(cdiv(q, kT)), static_cast<unsigned>(D)), dim3(kT), 0, stream, w,
+                           sampled_eid, q, E_parent, wE);
+    }
+    const dim3 grid(static_cast<unsigned>(cdiv(N * 64, kT)), static_cast<unsigned>(D));
+    hipLaunchKernelGGL(cheb_deg_multi, grid, dim3(kT), 0, stream, wE, N, E_parent, pout_ptr, pout_dst, pout_eid, mask, dis);
+    if (q > 0) hipLaunchKernelGGL(cheb_weights_multi, grid, dim3(kT), 0, stream, w, N, q, in_ptr, in_src, in_eid, dis, l_in);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_cheb_spmm_multi(int64_t K, const float* X, int64_t ldx, int64_t x_stride, int64_t N, int64_t D, int64_t nnz, int64_t n_draws,
+                        const int32_t* ptr, const int32_t* col, const float* val, float alpha, const float* add, int64_t ldadd,
+                        int64_t add_stride, const float* sub, int64_t ldsub, int64_t sub_stride, const float* bias, int act, float* Y, int64_t ldy,
+                        int64_t y_stride, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE_CHEB("sgs_cheb_spmm_multi");
+    SGS_REQUIRE(N >= 0 && D >= 0 && nnz >= 0 && n_draws >= 1 && n_draws <= 65535, SGS_EINVAL, "sgs_cheb_spmm_multi: bad sizes (1 <= draws <= 65535)");
+    SGS_REQUIRE(act == SGS_ACT_NONE || act == SGS_ACT_RELU, SGS_EINVAL, "sgs_cheb_spmm_multi: act must be NONE or RELU");
+    if (N == 0 || D == 0) return SGS_OK;
+    SGS_REQUIRE(X && ptr && Y && X != Y && (nnz == 0 || (col && val)), SGS_EINVAL, "sgs_cheb_spmm_multi: null or aliased pointer");
+    SGS_REQUIRE(ldx >= D && ldy >= D && (!add || ldadd >= D) && (!sub || ldsub >= D), SGS_EINVAL,
+                "sgs_cheb_spmm_multi: a leading dimension is smaller than D");
+    SGS_REQUIRE(x_stride >= 0 && add_stride >= 0 && sub_stride >= 0 && (n_draws == 1 || y_stride >= (N - 1) * ldy + D), SGS_EINVAL,
+                "sgs_cheb_spmm_multi: bad draw stride (every draw writes a block of its own)");
+    const int vec = (D % 4 == 0 && ldx % 4 == 0 && x_stride % 4 == 0 && aligned16(X)) ? 4 : 1;      // sgs_cheb_spmm's rule, for every draw's block
+    StepArgs a;
+    a.X = X; a.ldx = ldx; a.add = add; a.ldadd = ldadd; a.sub = sub; a.ldsub = ldsub; a.bias = bias; a.Y = Y; a.ldy = ldy;
+    a.Y2 = nullptr; a.ldy2 = 0; a.alpha = alpha; a.scale2 = 1.0f; a.act = act; a.drop_scale = 1.0f;
+    a.drop_thresh = 0u; a.seed = 0; a.site = 0u; a.epoch = nullptr;
+    StepStrides st;
+    st.x = x_stride; st.add = add_stride; st.sub = sub_stride; st.y = y_stride;
+    if (N <= 65536 && nnz >= 16 * N) {        // the single-draw choice, on the per-draw entry count
+        const bool wide = nnz >= 256 * N;
+        const dim3 g_(static_cast<unsigned>(N), static_cast<unsigned>(n_draws));
+        if (vec == 4 && wide) hipLaunchKernelGGL((cheb_spmm_rowblock_multi<4, 16>), g_, dim3(1024), 0, stream, a, st, N, D, nnz, ptr, col, val);
+        else if (vec == 4)    hipLaunchKernelGGL((cheb_spmm_rowblock_multi<4, 4>), g_, dim3(kT), 0, stream, a, st, N, D, nnz, ptr, col, val);
+        else if (wide)        hipLaunchKernelGGL((cheb_spmm_rowblock_multi<1, 16>), g_, dim3(1024), 0, stream, a, st, N, D, nnz, ptr, col, val);
+        else                  hipLaunchKernelGGL((cheb_spmm_rowblock_multi<1, 4>), g_, dim3(kT), 0, stream, a, st, N, D, nnz, ptr, col, val);
+    } else if (vec == 4) {
+        launch_rows_multi<4>(pick_lpr(D, 4), stream, a, st, N, D, nnz, n_draws, ptr, col, val);
+    } else {
+        launch_rows_multi<1>(pick_lpr(D, 1), stream, a, st, N, D, nnz, n_draws, ptr, col, val);
     }
     SGS_LAUNCH_OK();
     return SGS_OK;

@@ -288,6 +288,60 @@ __device__ __forceinline__ float head_max_all(float v) {
 // soft / alpha [n, K] by edge id (0 for (i, i) entries), soft_loop / alpha_loop [N, K].  Attention dropout is keyed (site, row = edge id,
 // col = head) and (site + 1, row = node, col = head): sgs_dropout_keep(seed, site, E, K, p) is the mask used, column 0 at K = 1 the
 // one-head kernel's.
+// The *_body function below holds the same row code as the single-draw kernel after it and serves the multi-draw kernel only: calling
+// the body from the single-draw kernel as well changed that kernel's register allocation and instruction order, so it keeps its own text
+// ("The heads' options"); tests/test_gpu_ensemble_batched_variants.py pins the two bitwise equal per draw.  The
+// other *_body functions of this file follow the same rule.
+template <int KP, bool SOFT>
+__device__ __forceinline__ void gat_alpha_heads_fwd_body(int64_t i, int lane, const float* __restrict__ a_s, const float* __restrict__ a_d, int K,
+                                                         const int* __restrict__ in_ptr, const int* __restrict__ in_src,
+                                                         const int* __restrict__ in_eid, float slope, float drop_scale, uint32_t drop_thresh,
+                                                         int use_drop, uint64_t seed, uint32_t site, float* __restrict__ soft,
+                                                         float* __restrict__ soft_loop, float* __restrict__ alpha, float* __restrict__ alpha_loop) {
+    constexpr int EPW = 64 / KP;
+    const int h = lane & (KP - 1), sub = lane / KP;
+    const bool hv = h < K;
+    const int hc = hv ? h : 0;
+    const int b = in_ptr[i], e = in_ptr[i + 1];
+    const float ad = a_d[i * K + hc];
+    const float eloop = lrelu(a_s[i * K + hc] + ad, slope);
+    float mx = eloop;
+    for (int k = b + sub; k < e; k += EPW) {
+        const int s = in_src[k];
+        if (s != static_cast<int>(i)) mx = fmaxf(mx, lrelu(a_s[static_cast<int64_t>(s) * K + hc] + ad, slope));
+    }
+    mx = head_max_all<KP>(mx);
+    float sum = 0.f;
+    for (int k = b + sub; k < e; k += EPW) {
+        const int s = in_src[k];
+        if (s != static_cast<int>(i)) sum += expf(lrelu(a_s[static_cast<int64_t>(s) * K + hc] + ad, slope) - mx);
+    }
+    sum = head_sum_all<KP>(sum) + expf(eloop - mx);
+    const float inv = 1.0f / (sum + 1e-16f);                  // torch_geometric.utils.softmax: / (sum + 1e-16)
+    for (int k = b + sub; k < e; k += EPW) {
+        const int s = in_src[k];
+        const int64_t ed = in_eid[k];
+        float sm = 0.f, al = 0.f;
+        if (s != static_cast<int>(i)) {
+            sm = expf(lrelu(a_s[static_cast<int64_t>(s) * K + hc] + ad, slope) - mx) * inv;
+            al = sm;
+            if (use_drop) al = dropout_keep_at(seed, site, static_cast<uint64_t>(ed), static_cast<uint32_t>(hc), drop_thresh) ? sm * drop_scale : 0.f;
+        }
+        if (hv) {
+            if (SOFT) soft[ed * K + h] = sm;
+            alpha[ed * K + h] = al;
+        }
+    }
+    if (sub == 0 && hv) {
+        const float sm = expf(eloop - mx) * inv;
+        float al = sm;
+        if (use_drop) al = dropout_keep_at(seed, site + 1u, static_cast<uint64_t>(i), static_cast<uint32_t>(h), drop_thresh) ? sm * drop_scale : 0.f;
+        if (SOFT) soft_loop[i * K + h] = sm;
+        alpha_loop[i * K + h] = al;
+    }
+}
+
+
 template <int KP>
 __global__ void __launch_bounds__(kT) gat_alpha_heads_fwd(const float* __restrict__ a_s, const float* __restrict__ a_d, int64_t N, int K,
                                                          const int* __restrict__ in_ptr, const int* __restrict__ in_src,
@@ -340,6 +394,23 @@ __global__ void __launch_bounds__(kT) gat_alpha_heads_fwd(const float* __restric
         soft_loop[i * K + h] = sm;
         alpha_loop[i * K + h] = al;
     }
+}
+
+// D drawn graphs of one partition (ensemble evaluation: no attention dropout, no kept softmax): blockIdx.y = draw d, which reads the node
+// scores at a_s + d * as, a_d + d * as (as = 0: one [N, K] pair shared by every draw) and its CSR slices ptr [N+1], src / eid [nnz]; the
+// body above runs unchanged on them, so row d of alpha [D, nnz, K] (by the draw's edge id) / alpha_loop [D, N, K] is bitwise what
+// gat_alpha_heads_fwd (p = 0) writes for draw d alone.
+template <int KP>
+__global__ void __launch_bounds__(kT) gat_alpha_heads_fwd_multi(const float* __restrict__ a_s, const float* __restrict__ a_d, int64_t as, int64_t N,
+                                                               int K, int64_t nnz, const int* __restrict__ in_ptr,
+                                                               const int* __restrict__ in_src, const int* __restrict__ in_eid, float slope,
+                                                               float* __restrict__ alpha, float* __restrict__ alpha_loop) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    if (i >= N) return;
+    const int64_t d = blockIdx.y;
+    gat_alpha_heads_fwd_body<KP, false>(i, lane, a_s + d * as, a_d + d * as, K, in_ptr + d * (N + 1), in_src + d * nnz, in_eid + d * nnz, slope,
+                                        1.0f, 0u, 0, uint64_t(0), 0u, nullptr, nullptr, alpha + d * nnz * K, alpha_loop + d * N * K);
 }
 
 // Backward of dropout + softmax + leaky_relu per (destination row, head); the formulas of gat_alpha_bwd above with galpha / soft / ge [n, K]
@@ -407,6 +478,71 @@ __global__ void __launch_bounds__(kT) gat_alpha_heads_bwd(const float* __restric
 // 1 / cnt_i cost no launch; both are kept for the backward ([N] each).
 __device__ __forceinline__ float edge_logit(float as, float ad, float w, float c, float slope) { return lrelu(fmaf(w, c, as + ad), slope); }
 
+// SOFT = false (the multi-draw kernel): neither the kept softmax nor wbar / inv_cnt (the backward's inputs) are written.
+template <int KP, bool SOFT>
+__device__ __forceinline__ void gat_alpha_heads_edge_fwd_body(int64_t i, int lane, const float* __restrict__ a_s, const float* __restrict__ a_d,
+                                                              const float* __restrict__ w, const float* __restrict__ coef, int K,
+                                                              const int* __restrict__ in_ptr, const int* __restrict__ in_src,
+                                                              const int* __restrict__ in_eid, float slope, float drop_scale,
+                                                              uint32_t drop_thresh, int use_drop, uint64_t seed, uint32_t site,
+                                                              float* __restrict__ soft, float* __restrict__ soft_loop, float* __restrict__ alpha,
+                                                              float* __restrict__ alpha_loop, float* __restrict__ wbar,
+                                                              float* __restrict__ inv_cnt) {
+    constexpr int EPW = 64 / KP;
+    const int h = lane & (KP - 1), sub = lane / KP;
+    const bool hv = h < K;
+    const int hc = hv ? h : 0;
+    const int b = in_ptr[i], e = in_ptr[i + 1];
+    const float ad = a_d[i * K + hc];
+    const float c = coef[hc];
+    float mx = -INFINITY, wsum = 0.f, cnt = 0.f;
+    for (int k = b + sub; k < e; k += EPW) {
+        const int s = in_src[k];
+        if (s != static_cast<int>(i)) {
+            const float we = w[in_eid[k]];
+            mx = fmaxf(mx, edge_logit(a_s[static_cast<int64_t>(s) * K + hc], ad, we, c, slope));
+            wsum += we;
+            cnt += 1.f;
+        }
+    }
+    wsum = head_sum_all<KP>(wsum);                            // over the entries (the KP lanes of an entry hold the same weight)
+    cnt = head_sum_all<KP>(cnt);
+    const float icnt = cnt > 0.f ? 1.0f / cnt : 0.f;
+    const float wb = wsum * icnt;
+    const float eloop = edge_logit(a_s[i * K + hc], ad, wb, c, slope);
+    mx = fmaxf(head_max_all<KP>(mx), eloop);
+    float sum = 0.f;
+    for (int k = b + sub; k < e; k += EPW) {
+        const int s = in_src[k];
+        if (s != static_cast<int>(i)) sum += expf(edge_logit(a_s[static_cast<int64_t>(s) * K + hc], ad, w[in_eid[k]], c, slope) - mx);
+    }
+    sum = head_sum_all<KP>(sum) + expf(eloop - mx);
+    const float inv = 1.0f / (sum + 1e-16f);                  // torch_geometric.utils.softmax: / (sum + 1e-16)
+    for (int k = b + sub; k < e; k += EPW) {
+        const int s = in_src[k];
+        const int64_t ed = in_eid[k];
+        float sm = 0.f, al = 0.f;
+        if (s != static_cast<int>(i)) {
+            sm = expf(edge_logit(a_s[static_cast<int64_t>(s) * K + hc], ad, w[ed], c, slope) - mx) * inv;
+            al = sm;
+            if (use_drop) al = dropout_keep_at(seed, site, static_cast<uint64_t>(ed), static_cast<uint32_t>(hc), drop_thresh) ? sm * drop_scale : 0.f;
+        }
+        if (hv) {
+            if (SOFT) soft[ed * K + h] = sm;
+            alpha[ed * K + h] = al;
+        }
+    }
+    if (sub == 0 && hv) {
+        const float sm = expf(eloop - mx) * inv;
+        float al = sm;
+        if (use_drop) al = dropout_keep_at(seed, site + 1u, static_cast<uint64_t>(i), static_cast<uint32_t>(h), drop_thresh) ? sm * drop_scale : 0.f;
+        if (SOFT) soft_loop[i * K + h] = sm;
+        alpha_loop[i * K + h] = al;
+    }
+    if (SOFT && lane == 0) { wbar[i] = wb; inv_cnt[i] = icnt; }
+}
+
+
 template <int KP>
 __global__ void __launch_bounds__(kT) gat_alpha_heads_edge_fwd(const float* __restrict__ a_s, const float* __restrict__ a_d,
                                                               const float* __restrict__ w, const float* __restrict__ coef, int64_t N, int K,
@@ -471,6 +607,23 @@ __global__ void __launch_bounds__(kT) gat_alpha_heads_edge_fwd(const float* __re
         alpha_loop[i * K + h] = al;
     }
     if (lane == 0) { wbar[i] = wb; inv_cnt[i] = icnt; }
+}
+
+// The multi-draw form of the above (see gat_alpha_heads_fwd_multi): draw d's weights are w + d * nnz (by the draw's edge id), coef [K] is
+// shared.  Row d is bitwise gat_alpha_heads_edge_fwd's (p = 0) alpha / alpha_loop for draw d alone.
+template <int KP>
+__global__ void __launch_bounds__(kT) gat_alpha_heads_edge_fwd_multi(const float* __restrict__ a_s, const float* __restrict__ a_d, int64_t as,
+                                                                    const float* __restrict__ w, const float* __restrict__ coef, int64_t N, int K,
+                                                                    int64_t nnz, const int* __restrict__ in_ptr, const int* __restrict__ in_src,
+                                                                    const int* __restrict__ in_eid, float slope, float* __restrict__ alpha,
+                                                                    float* __restrict__ alpha_loop) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    if (i >= N) return;
+    const int64_t d = blockIdx.y;
+    gat_alpha_heads_edge_fwd_body<KP, false>(i, lane, a_s + d * as, a_d + d * as, w + d * nnz, coef, K, in_ptr + d * (N + 1), in_src + d * nnz,
+                                             in_eid + d * nnz, slope, 1.0f, 0u, 0, uint64_t(0), 0u, nullptr, nullptr, alpha + d * nnz * K,
+                                             alpha_loop + d * N * K, nullptr, nullptr);
 }
 
 // gat_alpha_heads_bwd with the edge term: ge / gsl / d_ad as there, plus
@@ -701,6 +854,38 @@ __device__ __forceinline__ void spmm_heads_acc(const float* __restrict__ X, int6
 // the K weights of an entry arrive as one 4 K-byte read.  BCAST (backward of the head mean): X is [N, C], shared by the heads, and the
 // result is scaled by 1 / K:  Y[i, h C + c] = (1 / K) (sum_k val[eid_k, h] X[col_k, c] + diag[i, h] X[i, c]).
 template <int VEC, bool BCAST>
+__device__ __forceinline__ void spmm_csr_heads_body(const float* __restrict__ X, int64_t N, int K, int64_t C, const int* __restrict__ ptr,
+                                                    const int* __restrict__ col, const int* __restrict__ eid, const float* __restrict__ val,
+                                                    const float* __restrict__ diag, const float* __restrict__ bias, int act, float drop_scale,
+                                                    uint32_t drop_thresh, uint64_t seed, uint32_t site,
+                                                    float* __restrict__ Y, int lg) {
+    using V = typename std::conditional<VEC == 4, float4, float>::type;
+    const int LPR = 1 << lg;
+    const int sub = threadIdx.x & (LPR - 1);
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * (kT >> lg) + (threadIdx.x >> lg);
+    if (i >= N) return;
+    const int64_t D = static_cast<int64_t>(K) * C;
+    const int64_t XD = BCAST ? C : D;
+    const float post = BCAST ? 1.0f / static_cast<float>(K) : 1.0f;
+    const int b = ptr[i], e = ptr[i + 1];
+    for (int64_t c0 = static_cast<int64_t>(sub) * VEC; c0 < D; c0 += static_cast<int64_t>(LPR) * VEC) {
+        const int h = static_cast<int>(c0 / C);
+        const int64_t xc = BCAST ? c0 - h * C : c0;
+        float acc[VEC];
+        spmm_heads_acc<VEC>(X, XD, xc, K, h, i, b, e, col, eid, val, diag, acc);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            float y = BCAST ? acc[v] * post : acc[v];
+            if (bias) y += bias[c0 + v];
+            if (act != SGS_ACT_NONE) y = fmaxf(y, 0.f);
+            if (act == SGS_ACT_RELU_DROPOUT)
+                y = dropout_keep_at(seed, site, static_cast<uint64_t>(i), static_cast<uint32_t>(c0 + v), drop_thresh) ? y * drop_scale : 0.f;
+            acc[v] = y;
+        }
+        *reinterpret_cast<V*>(Y + i * D + c0) = *reinterpret_cast<V*>(acc);
+    }
+}
+template <int VEC, bool BCAST>
 __global__ void __launch_bounds__(kT) spmm_csr_heads(const float* __restrict__ X, int64_t N, int K, int64_t C, const int* __restrict__ ptr,
                                                     const int* __restrict__ col, const int* __restrict__ eid, const float* __restrict__ val,
                                                     const float* __restrict__ diag, const float* __restrict__ bias, int act, float drop_scale,
@@ -737,6 +922,49 @@ __global__ void __launch_bounds__(kT) spmm_csr_heads(const float* __restrict__ X
 // The head-mean form (GATConv concat = False), fused: Y[i, c] = (1 / K) sum_h (sum_k val[eid_k, h] X[col_k, h C + c] + diag[i, h] X[i, h C + c])
 // + bias[c].  A lane owns VEC output columns and walks the K heads of each gathered row itself (heads in order 0 .. K - 1 per entry, entries
 // in CSR order), so the [N, K C] per-head result is never written and no second launch averages it.
+template <int VEC>
+__device__ __forceinline__ void spmm_csr_heads_mean_body(const float* __restrict__ X, int64_t N, int K, int64_t C, const int* __restrict__ ptr,
+                                                         const int* __restrict__ col, const int* __restrict__ eid, const float* __restrict__ val,
+                                                         const float* __restrict__ diag, const float* __restrict__ bias, int act, float drop_scale,
+                                                         uint32_t drop_thresh, uint64_t seed, uint32_t site,
+                                                         float* __restrict__ Y, int lg) {
+    using V = typename std::conditional<VEC == 4, float4, float>::type;
+    const int LPR = 1 << lg;
+    const int sub = threadIdx.x & (LPR - 1);
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * (kT >> lg) + (threadIdx.x >> lg);
+    if (i >= N) return;
+    const int64_t D = static_cast<int64_t>(K) * C;
+    const float invK = 1.0f / static_cast<float>(K);
+    const int b = ptr[i], e = ptr[i + 1];
+    for (int64_t c0 = static_cast<int64_t>(sub) * VEC; c0 < C; c0 += static_cast<int64_t>(LPR) * VEC) {
+        float acc[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+        for (int k = b; k <= e; ++k) {                        // k == e: the loop term
+            const bool loop = k == e;
+            if (loop && !diag) break;
+            const float* xr = X + (loop ? i : static_cast<int64_t>(col[k])) * D + c0;
+            const float* wr = loop ? diag + i * K : val + static_cast<int64_t>(eid[k]) * K;
+            for (int h = 0; h < K; ++h) {
+                float x[VEC];
+                *reinterpret_cast<V*>(x) = *reinterpret_cast<const V*>(xr + h * C);
+                const float w = wr[h];
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, x[v], acc[v]);
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            float y = acc[v] * invK;
+            if (bias) y += bias[c0 + v];
+            if (act != SGS_ACT_NONE) y = fmaxf(y, 0.f);
+            if (act == SGS_ACT_RELU_DROPOUT)
+                y = dropout_keep_at(seed, site, static_cast<uint64_t>(i), static_cast<uint32_t>(c0 + v), drop_thresh) ? y * drop_scale : 0.f;
+            acc[v] = y;
+        }
+        *reinterpret_cast<V*>(Y + i * C + c0) = *reinterpret_cast<V*>(acc);
+    }
+}
 template <int VEC>
 __global__ void __launch_bounds__(kT) spmm_csr_heads_mean(const float* __restrict__ X, int64_t N, int K, int64_t C, const int* __restrict__ ptr,
                                                          const int* __restrict__ col, const int* __restrict__ eid, const float* __restrict__ val,
@@ -788,6 +1016,42 @@ __global__ void __launch_bounds__(kT) spmm_csr_heads_mean(const float* __restric
 // each lane with C / VEC lanes per row and was 6x slower at K = 8, C = 5 on a power-law graph, where 8 lanes served a hub row alone.
 constexpr int kMeanLdsFloats = 4096;
 template <int VEC>
+__device__ __forceinline__ void spmm_csr_heads_mean_lds_body(const float* __restrict__ X, int64_t N, int K, int64_t C, const int* __restrict__ ptr,
+                                                             const int* __restrict__ col, const int* __restrict__ eid, const float* __restrict__ val,
+                                                             const float* __restrict__ diag, const float* __restrict__ bias, int act, float drop_scale,
+                                                             uint32_t drop_thresh, uint64_t seed, uint32_t site,
+                                                             float* __restrict__ Y, int lg, float* __restrict__ part) {
+    const int LPR = 1 << lg;
+    const int sub = threadIdx.x & (LPR - 1), r = threadIdx.x >> lg;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * (kT >> lg) + r;
+    const bool live = i < N;                                  // every thread reaches the barrier
+    const int64_t D = static_cast<int64_t>(K) * C;
+    float* mine = part + r * D;
+    if (live) {
+        const int b = ptr[i], e = ptr[i + 1];
+        for (int64_t c0 = static_cast<int64_t>(sub) * VEC; c0 < D; c0 += static_cast<int64_t>(LPR) * VEC) {
+            const int h = static_cast<int>(c0 / C);
+            float acc[VEC];
+            spmm_heads_acc<VEC>(X, D, c0, K, h, i, b, e, col, eid, val, diag, acc);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) mine[c0 + v] = acc[v];
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    const float invK = 1.0f / static_cast<float>(K);
+    for (int64_t c = sub; c < C; c += LPR) {
+        float y = 0.f;
+        for (int h = 0; h < K; ++h) y += mine[h * C + c];
+        y *= invK;
+        if (bias) y += bias[c];
+        if (act != SGS_ACT_NONE) y = fmaxf(y, 0.f);
+        if (act == SGS_ACT_RELU_DROPOUT)
+            y = dropout_keep_at(seed, site, static_cast<uint64_t>(i), static_cast<uint32_t>(c), drop_thresh) ? y * drop_scale : 0.f;
+        Y[i * C + c] = y;
+    }
+}
+template <int VEC>
 __global__ void __launch_bounds__(kT) spmm_csr_heads_mean_lds(const float* __restrict__ X, int64_t N, int K, int64_t C, const int* __restrict__ ptr,
                                                              const int* __restrict__ col, const int* __restrict__ eid, const float* __restrict__ val,
                                                              const float* __restrict__ diag, const float* __restrict__ bias, int act, float drop_scale,
@@ -823,6 +1087,29 @@ __global__ void __launch_bounds__(kT) spmm_csr_heads_mean_lds(const float* __res
         if (act == SGS_ACT_RELU_DROPOUT)
             y = dropout_keep_at(seed, site, static_cast<uint64_t>(i), static_cast<uint32_t>(c), drop_thresh) ? y * drop_scale : 0.f;
         Y[i * C + c] = y;
+    }
+}
+
+// D drawn graphs of one partition (ensemble evaluation: ReLU / bias only, no dropout): blockIdx.y = draw d, which reads X + d * xs (xs = 0:
+// one X shared by every draw), its CSR slices ptr [N+1], col / eid [nnz], its weights val [nnz, K] / diag [N, K] and writes its block of
+// Y [D, N, W] (W = K C, or C for the head mean).  The bodies above run unchanged, so block d is bitwise sgs_spmm_csr_heads' for draw d.
+// MODE: 0 concat, 1 the LDS head mean, 2 the head mean with lanes owning output columns (rows of more than 1024 floats).
+template <int VEC, int MODE>
+__global__ void __launch_bounds__(kT) spmm_csr_heads_multi(const float* __restrict__ X, int64_t xs, int64_t N, int K, int64_t C, int64_t nnz,
+                                                          const int* __restrict__ ptr, const int* __restrict__ col, const int* __restrict__ eid,
+                                                          const float* __restrict__ val, const float* __restrict__ diag,
+                                                          const float* __restrict__ bias, int act, float* __restrict__ Y, int lg) {
+    const int64_t d = blockIdx.y;
+    const int64_t W = MODE == 0 ? static_cast<int64_t>(K) * C : C;
+    X += d * xs; ptr += d * (N + 1); col += d * nnz; eid += d * nnz; val += d * nnz * K; Y += d * N * W;
+    if (diag) diag += d * N * K;
+    if constexpr (MODE == 0) {
+        spmm_csr_heads_body<VEC, false>(X, N, K, C, ptr, col, eid, val, diag, bias, act, 1.0f, 0u, uint64_t(0), 0u, Y, lg);
+    } else if constexpr (MODE == 1) {
+        __shared__ float part[kMeanLdsFloats];
+        spmm_csr_heads_mean_lds_body<VEC>(X, N, K, C, ptr, col, eid, val, diag, bias, act, 1.0f, 0u, uint64_t(0), 0u, Y, lg, part);
+    } else {
+        spmm_csr_heads_mean_body<VEC>(X, N, K, C, ptr, col, eid, val, diag, bias, act, 1.0f, 0u, uint64_t(0), 0u, Y, lg);
     }
 }
 
@@ -1224,6 +1511,69 @@ int sgs_sddmm_csr_heads(const float* A, const float* B, int64_t N, int64_t K, in
         else          hipLaunchKernelGGL((sddmm_csr_heads<1, false>), grid, dim3(kT), 0, stream, SGS_SDDMM_HEADS_ARGS);
     }
 #undef SGS_SDDMM_HEADS_ARGS
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+// ---------------------------------------------------------------- multi-draw entry points (ensemble evaluation, forward only)
+int sgs_gat_alpha_heads_fwd_multi(const float* a_src, const float* a_dst, int64_t a_stride, const float* edge_w, const float* edge_coef,
+                                  int64_t N, int64_t K, int64_t D, int64_t nnz, const int32_t* in_ptr, const int32_t* in_src,
+                                  const int32_t* in_eid, float negative_slope, float* alpha, float* alpha_loop, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int64_t C = 1;
+    SGS_REQUIRE_HEADS("sgs_gat_alpha_heads_fwd_multi");
+    SGS_REQUIRE(N >= 0 && nnz >= 0 && D >= 1 && D <= 65535 && (a_stride == 0 || a_stride >= N * K), SGS_EINVAL,
+                "sgs_gat_alpha_heads_fwd_multi: bad sizes (1 <= D <= 65535; a_stride 0 or >= N K)");
+    SGS_REQUIRE((edge_w == nullptr) == (edge_coef == nullptr) || nnz == 0, SGS_EINVAL,
+                "sgs_gat_alpha_heads_fwd_multi: edge_w and edge_coef come together");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(a_src && a_dst && in_ptr && alpha_loop && (nnz == 0 || (in_src && in_eid && alpha)), SGS_EINVAL,
+                "sgs_gat_alpha_heads_fwd_multi: null pointer");
+    const dim3 grid(static_cast<unsigned>(cdiv(N * 64, kT)), static_cast<unsigned>(D));
+    if (edge_coef)
+        SGS_DISPATCH_KP(gat_alpha_heads_edge_fwd_multi, K, grid, stream, a_src, a_dst, a_stride, edge_w, edge_coef, N, static_cast<int>(K), nnz, in_ptr,
+                        in_src, in_eid, negative_slope, alpha, alpha_loop);
+    else
+        SGS_DISPATCH_KP(gat_alpha_heads_fwd_multi, K, grid, stream, a_src, a_dst, a_stride, N, static_cast<int>(K), nnz, in_ptr, in_src, in_eid,
+                        negative_slope, alpha, alpha_loop);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_spmm_csr_heads_multi(const float* X, int64_t x_stride, int64_t N, int64_t K, int64_t C, int64_t nnz, int64_t D, const int32_t* ptr,
+                             const int32_t* col, const int32_t* eid, const float* val, const float* diag, int mode, const float* bias, int act,
+                             float* Y, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE_HEADS("sgs_spmm_csr_heads_multi");
+    SGS_REQUIRE(N >= 0 && nnz >= 0 && D >= 1 && D <= 65535 && (x_stride == 0 || x_stride >= N * K * C) &&
+                    (mode == SGS_HEADS_CONCAT || mode == SGS_HEADS_MEAN),
+                SGS_EINVAL, "sgs_spmm_csr_heads_multi: bad sizes / mode (1 <= D <= 65535; x_stride 0 or >= N K C; CONCAT or MEAN)");
+    SGS_REQUIRE(act == SGS_ACT_NONE || act == SGS_ACT_RELU, SGS_EINVAL, "sgs_spmm_csr_heads_multi: act must be NONE or RELU");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(X && ptr && Y && X != Y && (nnz == 0 || (col && eid && val)), SGS_EINVAL, "sgs_spmm_csr_heads_multi: null or aliased pointer");
+    // the single-draw choice of vector width, made for every draw's block at once (their starts differ by multiples of 4 floats when C % 4 == 0)
+    const int vec = (C % 4 == 0 && al16(X) && al16(Y) && x_stride % 4 == 0) ? 4 : 1;
+    const int Ki = static_cast<int>(K);
+    int lg = log2_ceil(cdiv(K * C, vec));
+    if (lg > 6) lg = 6;
+    const bool mean_lds = mode == SGS_HEADS_MEAN && (kT >> lg) * K * C <= kMeanLdsFloats;
+    if (mode == SGS_HEADS_MEAN && !mean_lds) {
+        lg = log2_ceil(cdiv(C, vec));
+        if (lg > 6) lg = 6;
+    }
+    const dim3 grid(static_cast<unsigned>(cdiv(N, kT >> lg)), static_cast<unsigned>(D));
+#define SGS_SPMM_HEADS_MULTI_ARGS X, x_stride, N, Ki, C, nnz, ptr, col, eid, val, diag, bias, act, Y, lg
+    if (mean_lds) {
+        if (vec == 4) hipLaunchKernelGGL((spmm_csr_heads_multi<4, 1>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_MULTI_ARGS);
+        else          hipLaunchKernelGGL((spmm_csr_heads_multi<1, 1>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_MULTI_ARGS);
+    } else if (mode == SGS_HEADS_MEAN) {
+        if (vec == 4) hipLaunchKernelGGL((spmm_csr_heads_multi<4, 2>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_MULTI_ARGS);
+        else          hipLaunchKernelGGL((spmm_csr_heads_multi<1, 2>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_MULTI_ARGS);
+    } else {
+        if (vec == 4) hipLaunchKernelGGL((spmm_csr_heads_multi<4, 0>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_MULTI_ARGS);
+        else          hipLaunchKernelGGL((spmm_csr_heads_multi<1, 0>), grid, dim3(kT), 0, stream, SGS_SPMM_HEADS_MULTI_ARGS);
+    }
+#undef SGS_SPMM_HEADS_MULTI_ARGS
     SGS_LAUNCH_OK();
     return SGS_OK;
 }

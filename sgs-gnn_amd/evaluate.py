@@ -11,7 +11,9 @@ Batched engine (opt-in, `args.sgs_eval_batch`; True: draws per pass from a byte 
 of a partition run as one pass of batched kernels (ops.ensemble_partition_head) instead of the serial loop below.  Draw d uses the same
 (seed, stream id) as the serial loop's d-th draw, so the drawn edge sets are identical.  Which heads take it is a second opt-in,
 `args.sgs_eval_batch_heads`: absent / None = ("GCN",) (GNNModel only), "all" = GCN, GAT, GIN and Cheb, or a collection of those names;
-other heads keep the serial loop.  `PATH_COUNTS` records which path each ensemble_evaluate call took.
+other heads keep the serial loop.  A third opt-in, `args.sgs_eval_batch_variants` (absent / None / False = off, True = on), lets the heads'
+own options take the engine too: a GATModel with gat_heads in 2..16 and / or gat_edge_weight=True and a ChebModel with cheb_k in 2..8, when
+their head is selected; without it these models keep the serial loop.  `PATH_COUNTS` records which path each ensemble_evaluate call took.
 """
 from __future__ import annotations
 
@@ -83,28 +85,39 @@ def _run(args, model, cluster_loader, device, q, mode, n_draws):
     return tuple((c[s][0] / c[s][1]) if c[s][1] > 0 else 0 for s in range(3))
 
 
-def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str = "GCN") -> list:
+def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str = "GCN", *, gat_heads: int = 1, gat_edge: bool = False,
+               cheb_k: int = 1) -> list:
     """Draws per pass of the batched engine: a list of pass sizes summing to D, each >= 1.  `budget` is True (the largest pass whose
     per-draw buffers fit EVAL_BATCH_BUDGET bytes), an int number of bytes via ("bytes", n), or an int k >= 1 (at most k draws per pass).
     Per draw (an upper estimate of the engine's per-draw allocations): keys 4 E + mask E + filter positions 4 E; per drawn edge 40 B
     (int64 id 8, int64 endpoints 16 -- allocated only under the trace hook, counted always --, weight 4, CSR source and id 8, normalised
     weight 4); per-node arrays 36 N; hidden 4 N H; two logit blocks 8 N C.  `head` adds what that head allocates on top: GAT 4 q + 12 N
     (attention values, loop attentions, layer-2 node scores), GIN 4 N H + 8 N C + 4 q + 4 N (the MLP's second hidden block, the second
-    conv's product and aggregate, unit edge values and the 1 + eps diagonal); GCN and Cheb nothing.  The result of the engine does not
-    depend on the split."""
+    conv's product and aggregate, unit edge values and the 1 + eps diagonal); GCN and Cheb nothing.  The keyword-only parameters describe
+    the heads' options (their defaults reproduce the numbers above): GAT with K = gat_heads >= 1 allocates K values per attention entry,
+    so its term becomes 4 q K + 12 N K (attention values [q, K], loop terms [N, K], layer-2 node scores 2 [N, K]) plus 4 N C (K - 1) for the
+    layer-2 product [N, K C] beside the logits; gat_edge adds 8 N (the mean loop weight and count of the edge term; the kernels take them
+    as optional outputs, counted always).  Cheb with K = cheb_k >= 2 adds the (K - 1) out-wide block of b's of each layer,
+    4 N (K - 1) (H + C), the per-draw Laplacian values 4 q, dis 4 N and the weights scattered by parent edge id 4 E.  The result of the
+    engine does not depend on the split."""
     D = int(D)
     if D < 1:
         raise ValueError(f"plan_draws: D={D} draws")
     if head not in HEADS:
         raise ValueError(f"plan_draws: head={head!r}, need one of {HEADS}")
+    if not 1 <= int(gat_heads) <= 16 or not 1 <= int(cheb_k) <= 8:
+        raise ValueError(f"plan_draws: gat_heads={gat_heads}, cheb_k={cheb_k}: need 1..16 and 1..8")
     if budget is True or (isinstance(budget, tuple) and budget[0] == "bytes"):
         nbytes = EVAL_BATCH_BUDGET if budget is True else int(budget[1])
         ks = (int(E) + 63) & ~63
         per = 4 * ks + int(E) + 4 * int(E) + 40 * int(q) + 36 * (int(N) + 1) + 4 * int(N) * int(H) + 8 * int(N) * int(C) + 3 * 2048 * 4 + 64
+        K = int(gat_heads)
         if head == "GAT":
-            per += 4 * int(q) + 12 * int(N)
+            per += 4 * int(q) * K + 12 * int(N) * K + 4 * int(N) * int(C) * (K - 1) + (8 * int(N) if gat_edge else 0)
         elif head == "GIN":
             per += 4 * int(N) * int(H) + 8 * int(N) * int(C) + 4 * int(q) + 4 * int(N)
+        elif head == "Cheb" and int(cheb_k) > 1:
+            per += 4 * int(N) * (int(cheb_k) - 1) * (int(H) + int(C)) + 4 * int(q) + 4 * int(N) + 4 * int(E)
         k = max(1, min(D, int(nbytes) // per))
     else:
         k = int(budget)
@@ -116,23 +129,34 @@ def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str
 
 def _batched_ok(args, model, n_draws) -> bool:
     """Whether this call takes the batched engine.  A falsy flag (False, None, 0) means off; anything else must be True or an
-    int >= 1, and args.sgs_eval_batch_heads (consulted only then) a valid head selection, both checked here, before any partition is
-    read."""
+    int >= 1, and args.sgs_eval_batch_heads and args.sgs_eval_batch_variants (consulted only then) a valid head selection and None / a
+    bool, all checked here, before any partition is read.  A model with gat_heads > 1, gat_edge_weight or cheb_k > 1 takes the engine only
+    with sgs_eval_batch_variants=True (per-head GAT kernels / per-draw Chebyshev steps, ops.ensemble_partition_head)."""
     flag = getattr(args, "sgs_eval_batch", False)
     if not flag:
         return False
     if flag is not True and (isinstance(flag, bool) or not isinstance(flag, int) or flag < 1):
         raise ValueError(f"args.sgs_eval_batch={flag!r}: need True (draws per pass from a byte budget) or an int >= 1 (at most k per pass)")
     heads = _eval_heads(args)
+    variants = _eval_variants(args)
     if n_draws < 1:
         return False
-    if getattr(model, "gat_heads", 1) > 1:      # the batched engine's GAT pass is written for one attention head: serial loop
+    if not variants:                            # without the third opt-in the heads' options keep the serial loop, as before it existed
+        if getattr(model, "gat_heads", 1) > 1 or getattr(model, "gat_edge_weight", False) or getattr(model, "cheb_k", 1) > 1:
+            return False
+    elif not (1 <= getattr(model, "gat_heads", 1) <= 16 and 1 <= getattr(model, "cheb_k", 1) <= 8):
         return False
-    if getattr(model, "gat_edge_weight", False):    # the batched engine's GAT pass computes the logits without an edge term; with
-        return False                                # gat_edge_weight every draw's weights enter its attention: serial loop
-    if getattr(model, "cheb_k", 1) > 1:         # the batched engine's Chebyshev branch computes one set of logits per partition BECAUSE the
-        return False                            # graph does not enter at K = 1; with cheb_k > 1 every draw has its own: serial loop
     return _head_of(model) in heads
+
+
+def _eval_variants(args) -> bool:
+    """args.sgs_eval_batch_variants: absent / None / False -> False, True -> True.  Anything else raises ValueError."""
+    v = getattr(args, "sgs_eval_batch_variants", None)
+    if v is None or v is False:
+        return False
+    if v is True:
+        return True
+    raise ValueError(f"args.sgs_eval_batch_variants={v!r}: need None, False or True")
 
 
 def _eval_heads(args) -> frozenset:
@@ -163,7 +187,7 @@ def _head_dims(model, head):
     if head == "GCN":
         return model.gcn1.out_channels, model.gcn2.out_channels
     if head == "GAT":
-        return model.GAT.convs[0].out_channels, model.GAT.convs[1].out_channels
+        return model.GAT.convs[0].out_channels * model.GAT.convs[0].heads, model.GAT.convs[1].out_channels
     if head == "GIN":
         return model.GIN.convs[0].nn.lins[0].out_features, model.GIN.convs[1].nn.lins[0].out_features
     return model.gcn1.lins[0].out_features, model.gcn2.lins[0].out_features
@@ -187,6 +211,8 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
     head = _head_of(model)
     H, C = _head_dims(model, head)
     ticks = _eval_forward_ticks(head)
+    variant = dict(gat_heads=getattr(model, "gat_heads", 1), gat_edge=bool(getattr(model, "gat_edge_weight", False)),
+                   cheb_k=getattr(model, "cheb_k", 1))
     with torch.no_grad():
         for batch in cluster_loader:
             batch = batch.to(device)
@@ -215,7 +241,7 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
                 p, kind = None, ops.SAMPLE_LEARNED
                 given = [None] * n_draws                                             # random_edge_sampling takes no noise
             passes, d = [], 0
-            for k in plan_draws(E, q, N, H, C, n_draws, flag, head=head):
+            for k in plan_draws(E, q, N, H, C, n_draws, flag, head=head, **variant):
                 while k > 0:                                                         # a pass never mixes explicit noise and clock draws
                     explicit = given[d] is not None
                     n = 1

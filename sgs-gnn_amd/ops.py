@@ -2194,26 +2194,156 @@ def _drawn_gin_logits(parent: Graph, smp: MultiSampleResult, convs, u1):
     return h.view(D, N, -1)
 
 
+def gat_alpha_heads_multi(a_s, a_d, a_stride: int, csr, q: int, N: int, K: int, negative_slope: float, edge_w=None, edge_coef=None, out=None):
+    """sgs_gat_alpha_heads_fwd_multi over graph_filter_multi's CSRs: (alpha [D, q, K] by the draw's edge id, alpha_loop [D, N, K]), row d
+    bitwise sgs_gat_alpha_heads_fwd's (p = 0) for draw d -- or, with `edge_w` [D, q] and `edge_coef` [K], sgs_gat_alpha_heads_edge_fwd's
+    (every 1 <= K <= 16).  Draw d's node scores are a_s / a_d + d * a_stride (0: one [N, K] pair shared by all draws; N K: [D, N, K]
+    blocks).  `out`: reuse an (alpha, alpha_loop) pair of these shapes."""
+    L = _lib.lib()
+    in_ptr, in_src, in_eid = csr[0], csr[1], csr[2]
+    D = in_ptr.shape[0]
+    if (edge_w is None) != (edge_coef is None):
+        raise RuntimeError("gat_alpha_heads_multi: edge_w and edge_coef come together")
+    if edge_w is not None and (tuple(edge_w.shape) != (D, q) or edge_coef.numel() != K):
+        raise RuntimeError(f"gat_alpha_heads_multi: edge_w must be [D={D}, q={q}] and edge_coef [{K}]")
+    f32 = dict(dtype=torch.float32, device=in_ptr.device)
+    alpha, alpha_loop = out if out is not None else (torch.empty(D, max(q, 1), K, **f32), torch.empty(D, max(N, 1), K, **f32))
+    _lib.check(L.sgs_gat_alpha_heads_fwd_multi(_ptr(a_s, torch.float32), _ptr(a_d, torch.float32), int(a_stride), _ptr(edge_w, torch.float32),
+                                               _ptr(edge_coef, torch.float32), N, K, D, q, _ptr(in_ptr), _ptr(in_src), _ptr(in_eid),
+                                               float(negative_slope), _ptr(alpha), _ptr(alpha_loop), _stream()), "sgs_gat_alpha_heads_fwd_multi")
+    return alpha, alpha_loop
+
+
+def _spmm_heads_multi(X, x_stride: int, csr, val, diag, mode, bias, act, q: int, N: int, K: int, C: int):
+    """sgs_spmm_csr_heads_multi over graph_filter_multi's CSRs: Y [D, N, K C] (HEADS_CONCAT) or [D, N, C] (HEADS_MEAN), block d bitwise
+    sgs_spmm_csr_heads' for draw d with X_d = X + d * x_stride."""
+    L = _lib.lib()
+    in_ptr, in_src, in_eid = csr[0], csr[1], csr[2]
+    D = in_ptr.shape[0]
+    Y = torch.empty(D, N, C if mode == HEADS_MEAN else K * C, dtype=torch.float32, device=X.device)
+    _lib.check(L.sgs_spmm_csr_heads_multi(_ptr(X, torch.float32), int(x_stride), N, K, C, q, D, _ptr(in_ptr), _ptr(in_src), _ptr(in_eid), _ptr(val),
+                                          _ptr(diag), mode, _ptr(bias), act, _ptr(Y), _stream()), "sgs_spmm_csr_heads_multi")
+    return Y
+
+
+def _drawn_gat_heads_logits(parent: Graph, smp: MultiSampleResult, convs, xl1, a_s1, a_d1, w=None, coefs=None):
+    """Logits [D, N, C] of the two GATConv layers on the per-head kernels (heads K >= 2, or any K with the edge term; eval: no attention
+    dropout) over each of the D drawn subgraphs.  Layer 1 (concat) runs over the shared x' = lin_src(x) and its node scores [N, K]; layer 2
+    (head mean) is one library GEMM [D N, H] x W2^T and one gat_scores call over the D N rows (row-local).  `w` [D, q] (the draws'
+    straight-through weights) with `coefs` = the two layers' edge_coef [K] adds the edge term, as edge_weight does in GAT.forward; both
+    None = the unweighted per-head softmax.  The alpha buffers are reused by layer 2."""
+    D, q, N = smp.D, smp.q, parent.N
+    c1, c2 = convs
+    K = c1.heads
+    csr = graph_filter_multi(parent, smp)
+    edge = (lambda k: dict(edge_w=w, edge_coef=coefs[k])) if w is not None else (lambda k: {})
+    alpha = gat_alpha_heads_multi(a_s1, a_d1, 0, csr, q, N, K, c1.negative_slope, **edge(0))
+    H = xl1.shape[1]
+    h = _spmm_heads_multi(xl1, 0, csr, alpha[0], alpha[1], HEADS_CONCAT if c1.concat else HEADS_MEAN, c1.bias, ACT_RELU, q, N, K, H // K)
+    z = c2.lin_src(h.view(D * N, -1)).contiguous()                   # nn.Linear, as GATConv.forward
+    C = z.shape[1] // K
+    a_s2, a_d2 = gat_scores(z, c2.att_src, c2.att_dst, heads=K)
+    alpha = gat_alpha_heads_multi(a_s2, a_d2, N * K, csr, q, N, K, c2.negative_slope, out=alpha, **edge(1))
+    return _spmm_heads_multi(z, N * K * C, csr, alpha[0], alpha[1], HEADS_CONCAT if c2.concat else HEADS_MEAN, c2.bias, ACT_NONE, q, N, K, C)
+
+
+def cheb_norm_multi(parent: Graph, smp: MultiSampleResult, csr, w=None):
+    """sgs_cheb_norm_fwd_multi: (dis [D, N], l_in [D, q]) of the D drawn subgraphs, row d bitwise sgs_cheb_norm_fwd's dis / l_in for draw d.
+    `w` [D, q] by the draw's edge id, or None (unit weights).  The by-source degree walks the parent's out-CSR under each draw's mask."""
+    L = _lib.lib()
+    in_ptr, in_src, in_eid = csr[0], csr[1], csr[2]
+    D, q, N, E = smp.D, smp.q, parent.N, parent.n_edges
+    f32 = dict(dtype=torch.float32, device=in_ptr.device)
+    dis, l_in = torch.empty(D, max(N, 1), **f32), torch.empty(D, max(q, 1), **f32)
+    ws = workspace(L.sgs_cheb_norm_fwd_multi_workspace_bytes(E, D), in_ptr.device)
+    _lib.check(L.sgs_cheb_norm_fwd_multi(_ptr(w, torch.float32), _ptr(smp.eid, torch.int64), _ptr(_u8(smp.mask)), q, N, E, D, _ptr(parent.out_ptr),
+                                         _ptr(parent.out_dst), _ptr(parent.out_eid), _ptr(in_ptr), _ptr(in_src), _ptr(in_eid), _ptr(dis),
+                                         _ptr(l_in), ws.data_ptr(), ws.numel(), _stream()), "sgs_cheb_norm_fwd_multi")
+    return dis, l_in
+
+
+def _cheb_step_multi(K, X, ldx, xs, N, W, q, D, csr, val, alpha, add, ldadd, adds, sub, ldsub, subs, bias, act, Y, ldy, ys):
+    """One sgs_cheb_spmm_multi launch; X, add, sub, Y are raw addresses (column blocks of wider buffers) or None, each with its leading
+    dimension and draw stride."""
+    _lib.check(_lib.lib().sgs_cheb_spmm_multi(K, X, ldx, xs, N, W, q, D, _ptr(csr[0]), _ptr(csr[1]), _ptr(val), float(alpha), add, ldadd, adds,
+                                              sub, ldsub, subs, _ptr(bias), act, Y, ldy, ys, _stream()), "sgs_cheb_spmm_multi")
+
+
+def _cheb_layer_multi(K, Y0, y0_stride, B, b_stride, csr, l_in, bias, act, q, N, D):
+    """_ChebConv.forward's Clenshaw steps for D draws at once: Y0 [., N, W] and B [., N, (K - 1) W] = [Y_1 | ... | Y_{K-1}] with draw
+    strides (0: the layer-1 products, shared by all draws).  The steps k = K - 2 .. 1 overwrite B's column blocks in place, so a shared B
+    is copied per draw first when there are any (K >= 3); at K = 2 the last step only reads it.  -> [D, N, W]."""
+    W = Y0.shape[-1]
+    ldb = (K - 1) * W
+    if K >= 3 and b_stride == 0:
+        B = B.unsqueeze(0).expand(D, N, ldb).contiguous()
+        b_stride = N * ldb
+    b0 = B.data_ptr()
+    blk = lambda k: b0 + 4 * (k - 1) * W                          # b_k's column block
+    for k in range(K - 2, 0, -1):
+        _cheb_step_multi(K, blk(k + 1), ldb, b_stride, N, W, q, D, csr, l_in, 2.0, blk(k), ldb, b_stride,
+                         blk(k + 2) if k + 2 <= K - 1 else None, ldb, b_stride, None, ACT_NONE, blk(k), ldb, b_stride)
+    out = torch.empty(D, N, W, dtype=torch.float32, device=Y0.device)
+    _cheb_step_multi(K, blk(1), ldb, b_stride, N, W, q, D, csr, l_in, 1.0, Y0.data_ptr(), W, y0_stride, blk(2) if K >= 3 else None, ldb, b_stride,
+                     bias, act, out.data_ptr(), W, N * W)
+    return out
+
+
+def _drawn_cheb_logits(parent: Graph, smp: MultiSampleResult, w, convs, K: int, Y0, B):
+    """Logits [D, N, C] of the two ChebConv layers of order K >= 2 (eval: ReLU between them, no dropout) over each of the D drawn subgraphs:
+    one normalisation per draw for both layers (weighted by `w` [D, q], or unit), layer 1 from the shared products Y0 = x W_0^T and
+    B = x [W_1 | ... | W_{K-1}]^T, layer 2 from the same two library products over the [D N, H] hidden rows."""
+    D, q, N = smp.D, smp.q, parent.N
+    c1, c2 = convs
+    csr = graph_filter_multi(parent, smp)
+    _, l_in = cheb_norm_multi(parent, smp, csr, w)
+    h = _cheb_layer_multi(K, Y0, 0, B, 0, csr, l_in, c1.bias, ACT_RELU, q, N, D)
+    hf = h.view(D * N, -1)
+    C = c2.out_channels
+    Wcat = torch.cat([lin.weight for lin in c2.lins], 0)
+    Y0b, Bb = _x_wt(hf, Wcat[:C]), _x_wt(hf, Wcat[C:])               # the serial layer's two products, over all draws' rows
+    return _cheb_layer_multi(K, Y0b, N * C, Bb, N * (K - 1) * C, csr, l_in, c2.bias, ACT_NONE, q, N, D)
+
+
 def ensemble_partition_head(batch, model, q: int, mode: int, p, passes, counts, trace=None):
     """ensemble_partition for any of the four heads (GNNModel, GATModel, GINModel, ChebModel), same arguments and result.  Per pass: the D
     draws (sample_topq_multi), their in-CSRs (graph_filter_multi) and the head's logits for all of them; the draw-independent first
-    product (GAT: lin_src(x) and its node scores; GIN: x W0^T) runs once per partition.  Chebyshev (K = 1) ignores the graph: its logits
-    are computed once and folded D times; it draws only when `trace` asks for the edge lists.  GAT and GIN ignore edge weights, so no
-    straight-through weights are drawn for them."""
+    product (GAT: lin_src(x) and its node scores; GIN: x W0^T; Chebyshev K >= 2: x [W_0 | ... | W_{K-1}]^T) runs once per partition.
+    Chebyshev K = 1 ignores the graph: its logits are computed once and folded D times; it draws only when `trace` asks for the edge
+    lists.  One-head GAT without the edge term and GIN ignore edge weights, so no straight-through weights are drawn for them; GAT with
+    gat_edge_weight and Chebyshev K >= 2 take them (learned mode; the other modes have none: no edge term / unit weights, as
+    edge_weight=None in the model).  GAT with heads >= 2 or the edge term runs on the per-head kernels (_drawn_gat_heads_logits)."""
     from .model import ChebModel, GATModel, GINModel, GNNModel
     if isinstance(model, GNNModel):
         return ensemble_partition(batch, model.gcn1, model.gcn2, q, mode, p, passes, counts, trace)
     x, ei = batch.x, batch.edge_index
     N = x.shape[0]
+    weighted = mode == SAMPLE_LEARNED and p is not None              # the draws carry straight-through weights
+    want_w = False
     if isinstance(model, GATModel):
         convs = tuple(model.GAT.convs)
         xl1 = convs[0].lin_src(x).contiguous()                        # the serial path's call: bitwise the same x'
-        a_s1, a_d1 = gat_scores(xl1, convs[0].att_src, convs[0].att_dst)
-        logits = lambda parent, smp: _drawn_gat_logits(parent, smp, convs, xl1, a_s1, a_d1)
+        K = convs[0].heads
+        edge = weighted and convs[0].edge_dim is not None             # GAT.forward: the edge term needs edge_dim and weights
+        if K == 1 and not edge:
+            a_s1, a_d1 = gat_scores(xl1, convs[0].att_src, convs[0].att_dst)
+            logits = lambda parent, smp: _drawn_gat_logits(parent, smp, convs, xl1, a_s1, a_d1)
+        else:
+            a_s1, a_d1 = gat_scores(xl1, convs[0].att_src, convs[0].att_dst, heads=K)
+            coefs = tuple(c.edge_coef().reshape(K).contiguous() for c in convs) if edge else None
+            want_w = edge
+            logits = lambda parent, smp: _drawn_gat_heads_logits(parent, smp, convs, xl1, a_s1, a_d1, smp.w if edge else None, coefs)
     elif isinstance(model, GINModel):
         convs = tuple(model.GIN.convs)
         u1 = linear_nobias(x, convs[0].nn.lins[0].weight).contiguous()
         logits = lambda parent, smp: _drawn_gin_logits(parent, smp, convs, u1)
+    elif isinstance(model, ChebModel) and model.cheb_k > 1:
+        convs, K = (model.gcn1, model.gcn2), model.cheb_k
+        H = convs[0].out_channels
+        Wcat = torch.cat([lin.weight for lin in convs[0].lins], 0)
+        Y0, B = _x_wt(x, Wcat[:H]), _x_wt(x, Wcat[H:])                # _ChebConv.forward's two products: bitwise the serial path's
+        want_w = weighted
+        logits = lambda parent, smp: _drawn_cheb_logits(parent, smp, smp.w if weighted else None, convs, K, Y0, B)
     elif isinstance(model, ChebModel):
         fixed = model(batch, ei).contiguous()                         # [N, C], the same for every draw
         logits = None
@@ -2227,7 +2357,8 @@ def ensemble_partition_head(batch, model, q: int, mode: int, p, passes, counts, 
     for k, (Dc, noise, seed, sid0) in enumerate(passes):
         smp = None
         if logits is not None or trace is not None:
-            smp = sample_topq_multi(mode, p, None, 0.0, q, ei, Dc, noise=noise, seed=seed, stream_id0=sid0, want_edge_index=trace is not None)
+            smp = sample_topq_multi(mode, p, None, 0.0, q, ei, Dc, noise=noise, seed=seed, stream_id0=sid0, want_edge_index=trace is not None,
+                                    want_w=want_w)
         if logits is not None:
             out = logits(parent, smp)
             stride = N * out.shape[2]
