@@ -296,6 +296,12 @@ int sgs_spmm_csr(const float* X, int64_t N, int64_t D, int64_t nnz, const int32_
 int sgs_sddmm_csr(const float* A, const float* B, int64_t N, int64_t D, int64_t nnz, const int32_t* ptr, const int32_t* col,
                   const int32_t* eid, float* g, float* gdiag, sgs_stream_t stream);
 
+/* Which kernel the two calls above launch for a shape (pure host functions; the launchers switch on their result; aligned16 != 0: both
+ * dense operands are 16-byte aligned).  Code = kind * 1000 + VEC * 100 + W:  kind 0 = W lanes per row (LPR), kind 1 = a workgroup of
+ * W waves per row (NW);  VEC = floats per lane and load (4 needs D % 4 == 0 and the alignment).  DESIGN.md section 5 has the table. */
+int sgs_spmm_csr_variant(int64_t N, int64_t D, int64_t nnz, int aligned16);
+int sgs_sddmm_csr_variant(int64_t N, int64_t D, int64_t nnz, int aligned16);
+
 /* dZ = dY * act'(Y) for the fused epilogue above (Y is the layer OUTPUT: Y > 0 iff kept and
  * positive, so no mask is stored);  colsum: out[d] = sum_i A[i,d]  (bias gradient). */
 int sgs_act_bwd(const float* dY, const float* Y, int64_t n, int act, float p_drop, float* dZ, sgs_stream_t stream);
@@ -305,6 +311,11 @@ int sgs_colsum(const float* A, int64_t N, int64_t D, float* out, void* ws, size_
  * gradients of one layer's backward (autograd of model.py:159-161).  ws: sgs_colsum_workspace_bytes(N, D). */
 int sgs_act_bwd_colsum(const float* dY, const float* Y, int64_t N, int64_t D, int act, float p_drop, float* dZ, float* colsum, void* ws,
                        size_t ws_bytes, sgs_stream_t stream);
+
+/* Which kernels sgs_colsum (fused_act = 0) / sgs_act_bwd_colsum (fused_act != 0) launch (pure host function):
+ * kind * 1000000 + F * 100000 + rows * 100 + RG;  kind 1 = colsum_small, 2 = colsum_small_v4, 3 = vecsum_small, 4 = colsum_partial over
+ * `rows` rows per chunk + colsum_final<RG>;  F = 1 with the activation backward (in the kernel for kinds 1, 2; a launch of its own else). */
+int sgs_colsum_variant(int64_t N, int64_t D, int fused_act);
 
 /* GCN layer pairs at partition scale: one SpMM launch carries the neighbouring layer's row-local work.
  * sgs_gcn_pair_ok(N, nnz, D): 1 iff sgs_spmm_csr takes its row-block path (N <= 65536, nnz >= 16 N) and 0 < D <= 512 (rows of width

@@ -1604,6 +1604,25 @@ int sgs_gcn_norm_bwd_edge(const float* gw_hat, const float* gloop, int64_t n_edg
     return SGS_OK;
 }
 
+/* Which kernel the launchers below pick -- pure host functions of the shape, and the launchers switch on their result.
+ * sgs_spmm_csr_variant / sgs_sddmm_csr_variant:  kind * 1000 + VEC * 100 + W
+ *   kind 0: a group of W = LPR lanes per row (spmm_csr<VEC, LPR> / sddmm_csr<VEC, LPR>), LPR = the power of two >= ceil(D / VEC), at most 64
+ *   kind 1: a workgroup of W = NW waves per row (spmm_csr_rowblock<VEC, NW> / sddmm_csr_rowblock<VEC, NW>)
+ *   VEC = 4 iff D % 4 == 0 and both dense operands are 16-byte aligned (aligned16 != 0), else 1. */
+int sgs_spmm_csr_variant(int64_t N, int64_t D, int64_t nnz, int al16) {
+    const int vec = (D % 4 == 0 && al16) ? 4 : 1;
+    if (N <= 65536 && nnz >= 16 * N)          // few, long rows: a workgroup per row
+        return 1000 + vec * 100 + (nnz >= 256 * N ? 16 : 4);   // 16 waves for very long rows only: at ~100 entries per row the 16-wave form measured 5 % slower here
+    return vec * 100 + pick_lpr(D, vec);
+}
+
+int sgs_sddmm_csr_variant(int64_t N, int64_t D, int64_t nnz, int al16) {
+    const int vec = (D % 4 == 0 && al16) ? 4 : 1;
+    if (nnz >= 16 * N)                        // long rows (partitions; whole graphs of average degree >= 16): a workgroup per row
+        return 1000 + vec * 100 + (nnz >= 64 * N ? 16 : 4);
+    return vec * 100 + pick_lpr(D, vec);
+}
+
 int sgs_spmm_csr(const float* X, int64_t N, int64_t D, int64_t nnz, const int32_t* ptr, const int32_t* col, const float* val,
                  const float* diag, const float* bias, int act, float p_drop, uint64_t seed, uint32_t site, float* Y,
                  sgs_stream_t stream_) {
@@ -1613,28 +1632,32 @@ int sgs_spmm_csr(const float* X, int64_t N, int64_t D, int64_t nnz, const int32_
                 "sgs_spmm_csr: bad activation / dropout");
     if (N == 0 || D == 0) return SGS_OK;
     SGS_REQUIRE(X && ptr && Y && X != Y, SGS_EINVAL, "sgs_spmm_csr: null or aliased pointer");
-    const int vec = (D % 4 == 0 && aligned16(X) && aligned16(Y)) ? 4 : 1;
-    const int lpr = pick_lpr(D, vec);
+    const int var = sgs_spmm_csr_variant(N, D, nnz, aligned16(X) && aligned16(Y));
     const float scale = 1.0f / (1.0f - p_drop);
     const uint32_t th = dropout_thresh(p_drop);
     if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
-    if (N <= 65536 && nnz >= 16 * N) {        // few, long rows: a workgroup per row
-        const bool wide = nnz >= 256 * N;      // very long rows only: at ~100 entries per row the 16-wave form measured 5 % slower here
-        const dim3 g_(static_cast<unsigned>(N));
-        if (vec == 4 && wide)
+    const dim3 g_(static_cast<unsigned>(N));
+    switch (var) {
+        case 1416:
             hipLaunchKernelGGL((spmm_csr_rowblock<4, 16>), g_, dim3(1024), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
                                site, epoch_ptr(), Y);
-        else if (vec == 4)
+            break;
+        case 1404:
             hipLaunchKernelGGL((spmm_csr_rowblock<4, 4>), g_, dim3(kT), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
                                site, epoch_ptr(), Y);
-        else if (wide)
+            break;
+        case 1116:
             hipLaunchKernelGGL((spmm_csr_rowblock<1, 16>), g_, dim3(1024), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
                                site, epoch_ptr(), Y);
-        else
+            break;
+        case 1104:
             hipLaunchKernelGGL((spmm_csr_rowblock<1, 4>), g_, dim3(kT), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
                                site, epoch_ptr(), Y);
-    } else {
-        DISPATCH_VEC_LPR(spmm_csr, vec, lpr, N, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed, site, epoch_ptr(), Y);
+            break;
+        default: {
+            const int vec = var / 100, lpr = var % 100;
+            DISPATCH_VEC_LPR(spmm_csr, vec, lpr, N, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed, site, epoch_ptr(), Y);
+        }
     }
     SGS_LAUNCH_OK();
     return SGS_OK;
@@ -1646,17 +1669,17 @@ int sgs_sddmm_csr(const float* A, const float* B, int64_t N, int64_t D, int64_t 
     SGS_REQUIRE(N >= 0 && D >= 0, SGS_EINVAL, "sgs_sddmm_csr: bad sizes");
     if (N == 0) return SGS_OK;
     SGS_REQUIRE(A && B && ptr, SGS_EINVAL, "sgs_sddmm_csr: null pointer");
-    const int vec = (D % 4 == 0 && aligned16(A) && aligned16(B)) ? 4 : 1;
-    const int lpr = pick_lpr(D, vec);
-    if (nnz >= 16 * N) {                      // long rows (partitions; whole graphs of average degree >= 16): a workgroup per row
-        const bool wide = nnz >= 64 * N;
-        const dim3 g_(static_cast<unsigned>(N));
-        if (vec == 4 && wide) hipLaunchKernelGGL((sddmm_csr_rowblock<4, 16>), g_, dim3(1024), 0, stream, A, B, N, D, ptr, col, eid, g, gdiag);
-        else if (vec == 4)    hipLaunchKernelGGL((sddmm_csr_rowblock<4, 4>), g_, dim3(kT), 0, stream, A, B, N, D, ptr, col, eid, g, gdiag);
-        else if (wide)        hipLaunchKernelGGL((sddmm_csr_rowblock<1, 16>), g_, dim3(1024), 0, stream, A, B, N, D, ptr, col, eid, g, gdiag);
-        else                  hipLaunchKernelGGL((sddmm_csr_rowblock<1, 4>), g_, dim3(kT), 0, stream, A, B, N, D, ptr, col, eid, g, gdiag);
-    } else {
-        DISPATCH_VEC_LPR(sddmm_csr, vec, lpr, N, A, B, N, D, ptr, col, eid, g, gdiag);
+    const int var = sgs_sddmm_csr_variant(N, D, nnz, aligned16(A) && aligned16(B));
+    const dim3 g_(static_cast<unsigned>(N));
+    switch (var) {
+        case 1416: hipLaunchKernelGGL((sddmm_csr_rowblock<4, 16>), g_, dim3(1024), 0, stream, A, B, N, D, ptr, col, eid, g, gdiag); break;
+        case 1404: hipLaunchKernelGGL((sddmm_csr_rowblock<4, 4>), g_, dim3(kT), 0, stream, A, B, N, D, ptr, col, eid, g, gdiag); break;
+        case 1116: hipLaunchKernelGGL((sddmm_csr_rowblock<1, 16>), g_, dim3(1024), 0, stream, A, B, N, D, ptr, col, eid, g, gdiag); break;
+        case 1104: hipLaunchKernelGGL((sddmm_csr_rowblock<1, 4>), g_, dim3(kT), 0, stream, A, B, N, D, ptr, col, eid, g, gdiag); break;
+        default: {
+            const int vec = var / 100, lpr = var % 100;
+            DISPATCH_VEC_LPR(sddmm_csr, vec, lpr, N, A, B, N, D, ptr, col, eid, g, gdiag);
+        }
     }
     SGS_LAUNCH_OK();
     return SGS_OK;
@@ -1679,37 +1702,52 @@ size_t sgs_colsum_workspace_bytes(int64_t N, int64_t D) {
     return carve_bytes(static_cast<size_t>(cdiv(N, colsum_rows(N)) + 1) * D, 4) + 256;
 }
 
+/* Which kernels sgs_colsum (fused_act = 0) / sgs_act_bwd_colsum (fused_act != 0) launch:  kind * 1000000 + F * 100000 + rows * 100 + RG
+ *   kind 1: colsum_small<F>      (0 < N <= 2048, D % 4 != 0)        kind 2: colsum_small_v4<F>   (0 < N <= 2048, D % 4 == 0)
+ *   kind 3: vecsum_small         (D == 1, 2048 < N <= 2^20)         kind 4: colsum_partial over `rows` rows per chunk (32 | 128 | 256),
+ *                                                                           then colsum_final<RG> (16 when there are more than 64 chunks, else 4)
+ *   F = 1: the activation backward rides along -- inside the kernel for kinds 1 and 2, as an act_bwd launch in front of kinds 3 and 4;
+ *   rows = RG = 0 for kinds 1 to 3. */
+int sgs_colsum_variant(int64_t N, int64_t D, int fused_act) {
+    const int f = fused_act ? 100000 : 0;
+    if (N > 0 && N <= kColSmallRows) return (D % 4 == 0 ? 2000000 : 1000000) + f;
+    if (D == 1 && N > 0 && N <= kVecSumMax) return 3000000 + f;
+    const int rows = colsum_rows(N);
+    return 4000000 + f + rows * 100 + (cdiv(N, rows) > 64 ? 16 : 4);
+}
+
 int sgs_colsum(const float* A, int64_t N, int64_t D, float* out, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     SGS_REQUIRE(N >= 0 && D >= 0, SGS_EINVAL, "sgs_colsum: bad sizes");
     if (D == 0) return SGS_OK;
     SGS_REQUIRE(out && (N == 0 || A), SGS_EINVAL, "sgs_colsum: null pointer");
     SGS_REQUIRE(ws && ws_bytes >= sgs_colsum_workspace_bytes(N, D), SGS_EWORKSPACE, "sgs_colsum: workspace too small");
-    if (N > 0 && N <= kColSmallRows) {
-        // (round 1 tried a single launch with 64-column workgroups, N/16 rows per thread: slower than the two stages by 12 us per
-        //  backward; with 16-column workgroups a thread walks N/64 rows and all of its loads are in flight together)
-        if (D % 4 == 0)
-            hipLaunchKernelGGL(colsum_small_v4<false>, dim3(cdiv(D, 16)), dim3(1024), 0, stream, A, static_cast<const float*>(nullptr), N, D, SGS_ACT_NONE,
-                               1.f, static_cast<float*>(nullptr), out);
-        else
+    const int var = sgs_colsum_variant(N, D, 0);
+    switch (var / 1000000) {
+        case 1:
+            // (round 1 tried a single launch with 64-column workgroups, N/16 rows per thread: slower than the two stages by 12 us per
+            //  backward; with 16-column workgroups a thread walks N/64 rows and all of its loads are in flight together)
             hipLaunchKernelGGL(colsum_small<false>, dim3(cdiv(D, 16)), dim3(1024), 0, stream, A, static_cast<const float*>(nullptr), N, D, SGS_ACT_NONE, 1.f,
                                static_cast<float*>(nullptr), out);
-        SGS_LAUNCH_OK();
-        return SGS_OK;
+            break;
+        case 2:
+            hipLaunchKernelGGL(colsum_small_v4<false>, dim3(cdiv(D, 16)), dim3(1024), 0, stream, A, static_cast<const float*>(nullptr), N, D, SGS_ACT_NONE,
+                               1.f, static_cast<float*>(nullptr), out);
+            break;
+        case 3:
+            hipLaunchKernelGGL(vecsum_small, dim3(1), dim3(1024), 0, stream, A, N, out);
+            break;
+        default: {
+            Carver cv(ws);
+            const int rows = var / 100 % 1000;
+            const int64_t nchunk = cdiv(N, rows);
+            float* part = cv.take<float>(static_cast<size_t>(nchunk + 1) * D);
+            if (nchunk > 0)
+                hipLaunchKernelGGL(colsum_partial, dim3(cdiv(D, 64), nchunk), dim3(kT), 0, stream, A, N, D, rows, part);
+            if (var % 100 == 16) hipLaunchKernelGGL(colsum_final<16>, dim3(cdiv(D, 64)), dim3(1024), 0, stream, part, nchunk, D, out);
+            else                 hipLaunchKernelGGL(colsum_final<4>, dim3(cdiv(D, 64)), dim3(kT), 0, stream, part, nchunk, D, out);
+        }
     }
-    if (D == 1 && N > 0 && N <= kVecSumMax) {
-        hipLaunchKernelGGL(vecsum_small, dim3(1), dim3(1024), 0, stream, A, N, out);
-        SGS_LAUNCH_OK();
-        return SGS_OK;
-    }
-    Carver cv(ws);
-    const int rows = colsum_rows(N);
-    const int64_t nchunk = cdiv(N, rows);
-    float* part = cv.take<float>(static_cast<size_t>(nchunk + 1) * D);
-    if (nchunk > 0)
-        hipLaunchKernelGGL(colsum_partial, dim3(cdiv(D, 64), nchunk), dim3(kT), 0, stream, A, N, D, rows, part);
-    if (nchunk > 64) hipLaunchKernelGGL(colsum_final<16>, dim3(cdiv(D, 64)), dim3(1024), 0, stream, part, nchunk, D, out);
-    else             hipLaunchKernelGGL(colsum_final<4>, dim3(cdiv(D, 64)), dim3(kT), 0, stream, part, nchunk, D, out);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -1720,15 +1758,20 @@ int sgs_act_bwd_colsum(const float* dY, const float* Y, int64_t N, int64_t D, in
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     SGS_REQUIRE(N >= 0 && D >= 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_act_bwd_colsum: bad arguments");
     if (D == 0) return SGS_OK;
-    SGS_REQUIRE(dZ && colsum && (N == 0 || (dY && (act == SGS_ACT_NONE || Y))), SGS_EINVAL, "sgs_act_bwd_colsum: null pointer");
-    if (N > 0 && N <= kColSmallRows) {
-        if (D % 4 == 0) hipLaunchKernelGGL(colsum_small_v4<true>, dim3(cdiv(D, 16)), dim3(1024), 0, stream, dY, Y, N, D, act, 1.0f / (1.0f - p_drop), dZ, colsum);
-        else            hipLaunchKernelGGL(colsum_small<true>, dim3(cdiv(D, 16)), dim3(1024), 0, stream, dY, Y, N, D, act, 1.0f / (1.0f - p_drop), dZ, colsum);
-        SGS_LAUNCH_OK();
-        return SGS_OK;
+    SGS_REQUIRE(colsum && (N == 0 || (dZ && dY && (act == SGS_ACT_NONE || Y))), SGS_EINVAL, "sgs_act_bwd_colsum: null pointer");   // (an empty dZ has no address)
+    switch (sgs_colsum_variant(N, D, 1) / 1000000) {
+        case 1:
+            hipLaunchKernelGGL(colsum_small<true>, dim3(cdiv(D, 16)), dim3(1024), 0, stream, dY, Y, N, D, act, 1.0f / (1.0f - p_drop), dZ, colsum);
+            break;
+        case 2:
+            hipLaunchKernelGGL(colsum_small_v4<true>, dim3(cdiv(D, 16)), dim3(1024), 0, stream, dY, Y, N, D, act, 1.0f / (1.0f - p_drop), dZ, colsum);
+            break;
+        default:
+            if (int rc = sgs_act_bwd(dY, Y, N * D, act, p_drop, dZ, stream_)) return rc;
+            return sgs_colsum(dZ, N, D, colsum, ws, ws_bytes, stream_);
     }
-    if (int rc = sgs_act_bwd(dY, Y, N * D, act, p_drop, dZ, stream_)) return rc;
-    return sgs_colsum(dZ, N, D, colsum, ws, ws_bytes, stream_);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
 }
 
 // ---- GCN layer pairs (spmm_rowgroup_pair): only where sgs_spmm_csr takes its row-block path

@@ -46,7 +46,9 @@ def test_graph_build_matches_stable_sort(pkg, N, E):
 
 
 @pytest.mark.parametrize("N,E,Fin,D", [(40, 300, 9, 16), (40, 300, 9, 41), (200, 5000, 33, 256), (64, 900, 5, 7), (30, 200, 4, 70),
-                                       (17, 60, 3, 512), (25, 0, 3, 8)])
+                                       (17, 60, 3, 512), (25, 0, 3, 8),
+                                       # rowblock<1,16>, rowblock<4,16>, rowblock<1,4>; LPR = 32 with the two-stage column sums
+                                       (64, 20000, 5, 41), (64, 20000, 5, 256), (300, 6000, 9, 41), (3000, 9000, 6, 128)])
 @pytest.mark.parametrize("weighted", [True, False])
 def test_gcn_conv_forward_backward_vs_oracle(pkg, N, E, Fin, D, weighted):
     from sgs_gnn_amd.model import GCNConv
