@@ -751,6 +751,42 @@ int sgs_sddmm_csr_heads(const float* A, const float* B, int64_t N, int64_t K, in
                         const int32_t* eid, int broadcast, float* g, float* gdiag, sgs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K8c: GATv2 attention (PyG 2.3.1 GATv2Conv, share_weights = False, restated; csrc/gatv2.hip).  xl = lin_l(x), xr = lin_r(x) [N, K C]
+ * (head-major columns), att [K, C]; for an entry j -> i, head h:
+ *   s[c] = xl[j, h, c] + xr[i, h, c] (+ edge_w[e] lin_edge[h, c]),   logit = sum_c att[h, c] leaky_relu(s[c]).
+ * Softmax per (destination, head) over the in-entries plus one added loop, / (sum + 1e-16); existing (i, i) entries are removed (their
+ * soft / alpha / g_logit / d_edge_w are 0); attention dropout sites and keys are sgs_gat_alpha_heads_fwd's.  edge_w == NULL: no edge
+ * term (lin_edge, loop_w, loop_inv_cnt and their gradients are then ignored and may be NULL).  With it, edge_w [n_edges] by edge id,
+ * lin_edge [K, C] = lin_edge.weight, the loop of node i carries wbar_i = the mean weight of i's remaining in-edges (0 without any), and
+ * the forward writes loop_w [N] = wbar, loop_inv_cnt [N] = 1 / cnt_i (0 without in-edges) for the backward.  1 <= K <= 16, any C >= 1;
+ * rows are 16-byte vectorised when C % 4 == 0 and the pointers are 16-byte aligned.  Aggregation and the d alpha SDDMM are
+ * sgs_spmm_csr_heads / sgs_sddmm_csr_heads.  Backward, with galpha / gloop from the SDDMM:
+ *   sgs_gatv2_alpha_heads_bwd (dst-CSR): g_logit [n_edges, K] by edge id, g_loop [N, K] (the logits' gradients), and with
+ *       t[c] = g att[h, c] leaky_relu'(s[c]):  d_xr[i] = sum t over i's entries and loop;  d_att[h, c] = sum g leaky_relu(s[c]);
+ *       d_lin_edge[h, c] = sum t w;  d_edge_w[e] = sum_{h, c} t lin_edge[h, c] + the loop's own such sum / cnt_i (+ dw_add[e] unless
+ *       NULL: a second layer's gradient, summed on the way out).  d_att / d_lin_edge: per-workgroup partials in ws
+ *       (sgs_gatv2_alpha_heads_bwd_workspace_bytes(N, K, C)), added in a fixed order by a second small launch.
+ *   sgs_gatv2_dxl_heads (src-CSR): d_xl[j] (+)= sum over j's out-entries and loop of t, recomputed from g_logit / g_loop;
+ *       accumulate != 0 adds onto d_xl's contents (the aggregation's d xl).
+ * No float atomics, no host synchronisation: two identical launches give identical bits.
+ * ---------------------------------------------------------------------------------- */
+int sgs_gatv2_alpha_heads_fwd(const float* xl, const float* xr, const float* att, const float* edge_w, const float* lin_edge, int64_t N,
+                              int64_t K, int64_t C, int64_t n_edges, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid,
+                              float negative_slope, float p_drop, uint64_t seed, uint32_t site, float* soft, float* soft_loop, float* alpha,
+                              float* alpha_loop, float* loop_w, float* loop_inv_cnt, sgs_stream_t stream);
+size_t sgs_gatv2_alpha_heads_bwd_workspace_bytes(int64_t N, int64_t K, int64_t C);
+int sgs_gatv2_alpha_heads_bwd(const float* xl, const float* xr, const float* att, const float* edge_w, const float* lin_edge, const float* loop_w,
+                              const float* loop_inv_cnt, int64_t N, int64_t K, int64_t C, int64_t n_edges, const int32_t* in_ptr,
+                              const int32_t* in_src, const int32_t* in_eid, float negative_slope, float p_drop, uint64_t seed, uint32_t site,
+                              const float* soft, const float* soft_loop, const float* galpha, const float* gloop, const float* dw_add,
+                              float* g_logit, float* g_loop, float* d_xr, float* d_att, float* d_lin_edge, float* d_edge_w, void* ws,
+                              size_t ws_bytes, sgs_stream_t stream);
+int sgs_gatv2_dxl_heads(const float* xl, const float* xr, const float* att, const float* edge_w, const float* lin_edge, const float* loop_w,
+                        const float* g_logit, const float* g_loop, int64_t N, int64_t K, int64_t C, int64_t nnz, const int32_t* out_ptr,
+                        const int32_t* out_dst, const int32_t* out_eid, float negative_slope, int accumulate, float* d_xl,
+                        sgs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * K9: Chebyshev layers of order K > 1 (PyG 2.3.1 ChebConv, normalization = 'sym', lambda_max = 2, restated; 1 <= K <= 8 -- the bound is
  * a choice, not a hardware limit; K = 1 callers need none of this, the layer is a Linear).  For edges (s_e -> d_e) with weights w_e:
  *   (i, i) edges are removed (weight 0 in every formula, gradient 0);  deg_n = sum_{e: s_e = n} w_e, summed BY SOURCE (not the GCN

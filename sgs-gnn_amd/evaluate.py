@@ -131,7 +131,8 @@ def _batched_ok(args, model, n_draws) -> bool:
     """Whether this call takes the batched engine.  A falsy flag (False, None, 0) means off; anything else must be True or an
     int >= 1, and args.sgs_eval_batch_heads and args.sgs_eval_batch_variants (consulted only then) a valid head selection and None / a
     bool, all checked here, before any partition is read.  A model with gat_heads > 1, gat_edge_weight or cheb_k > 1 takes the engine only
-    with sgs_eval_batch_variants=True (per-head GAT kernels / per-draw Chebyshev steps, ops.ensemble_partition_head)."""
+    with sgs_eval_batch_variants=True (per-head GAT kernels / per-draw Chebyshev steps, ops.ensemble_partition_head).  A gat_v2 model keeps
+    the serial loop whatever the opt-ins say: there is no batched GATv2 engine."""
     flag = getattr(args, "sgs_eval_batch", False)
     if not flag:
         return False
@@ -139,7 +140,7 @@ def _batched_ok(args, model, n_draws) -> bool:
         raise ValueError(f"args.sgs_eval_batch={flag!r}: need True (draws per pass from a byte budget) or an int >= 1 (at most k per pass)")
     heads = _eval_heads(args)
     variants = _eval_variants(args)
-    if n_draws < 1:
+    if n_draws < 1 or getattr(model, "gat_v2", False):
         return False
     if not variants:                            # without the third opt-in the heads' options keep the serial loop, as before it existed
         if getattr(model, "gat_heads", 1) > 1 or getattr(model, "gat_edge_weight", False) or getattr(model, "cheb_k", 1) > 1:

@@ -166,23 +166,71 @@ class GATConv(nn.Module):
                                  p_act, seed, SITE_GAT_ACT + layer, heads=self.heads, concat=self.concat, **edge)
 
 
+class GATv2Conv(nn.Module):
+    """PyG 2.3.1 GATv2Conv(in, out, heads, concat, negative_slope, dropout, edge_dim in {None, 1}) with share_weights=False, bias=True, as
+    torch_geometric.nn.models.GAT(..., v2=True) instantiates it (restated from its published algorithm): parameters `lin_l.weight` /
+    `lin_r.weight` [heads * out, in] with `lin_l.bias` / `lin_r.bias` [heads * out] (two separate Linears), `att` [1, heads, out], `bias`
+    [heads * out] (concat) or [out] (mean over heads); edge_dim = 1 adds `lin_edge.weight` [heads * out, 1] (no bias).  The logit of an
+    entry j -> i is att_h . leaky_relu(x_l[j, h] + x_r[i, h] (+ edge_weight[e] * lin_edge.weight[h])): the non-linearity sits inside the dot
+    product, so the ranking of the neighbours depends on the destination ("dynamic attention").  The softmax, the removed (i, i) entries,
+    the added loops (carrying the mean weight of their node's in-edges) and the output are GATConv's, with x_l as the message.  Runs on
+    the gathering per-head kernels of csrc/gatv2.hip for every 1 <= heads <= 16; without `edge_weight` the edge parameter gets no gradient."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, edge_dim=None):
+        super().__init__()
+        heads = int(heads)
+        if not 1 <= heads <= 16 or out_channels < 1:
+            raise ValueError(f"GATv2Conv: heads = {heads}, out_channels = {out_channels}: 1 <= heads <= 16 and out_channels >= 1 are supported")
+        if edge_dim not in (None, 1):
+            raise ValueError(f"GATv2Conv: edge_dim = {edge_dim!r}: None and 1 (the edge weight as the attribute) are supported")
+        self.in_channels, self.out_channels, self.negative_slope, self.dropout = in_channels, out_channels, negative_slope, dropout
+        self.heads, self.concat, self.edge_dim = heads, bool(concat), edge_dim
+        self.lin_l = nn.Linear(in_channels, heads * out_channels, bias=True)
+        self.lin_r = nn.Linear(in_channels, heads * out_channels, bias=True)
+        self.att = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.bias = nn.Parameter(torch.zeros(heads * out_channels if concat else out_channels))
+        a = math.sqrt(6.0 / (in_channels + heads * out_channels))     # glorot on the parameter's own shape, as PyG
+        for lin in (self.lin_l, self.lin_r):
+            nn.init.uniform_(lin.weight, -a, a)
+            nn.init.zeros_(lin.bias)
+        b = math.sqrt(6.0 / (heads + out_channels))                   # [1, heads, out]: size(-2) + size(-1)
+        nn.init.uniform_(self.att, -b, b)
+        if edge_dim is not None:
+            self.lin_edge = nn.Linear(edge_dim, heads * out_channels, bias=False)
+            e = math.sqrt(6.0 / (edge_dim + heads * out_channels))
+            nn.init.uniform_(self.lin_edge.weight, -e, e)
+
+    def forward(self, x, edge_index, edge_weight=None, *, act=ops.ACT_NONE, p_act=0.0, seed=0, layer=0):
+        graph = ops.get_graph(edge_index, x.shape[0])
+        if edge_weight is not None and self.edge_dim is None:
+            raise ValueError("GATv2Conv: edge_weight needs edge_dim = 1")
+        D = self.heads * self.out_channels
+        Wcat = torch.cat([self.lin_l.weight, self.lin_r.weight], 0)   # [2 heads out, in]: the two Linears share x, one product
+        y = ops.linear_nobias(x, Wcat) + torch.cat([self.lin_l.bias, self.lin_r.bias])
+        p_att = self.dropout if self.training else 0.0
+        edge = {} if edge_weight is None else {"edge_weight": edge_weight, "lin_edge": self.lin_edge.weight}
+        return ops.gatv2_aggregate(y[:, :D], y[:, D:], self.att, self.bias, graph, self.negative_slope, p_att, seed, SITE_GAT_ATT + 2 * layer,
+                                   act, p_act, seed, SITE_GAT_ACT + layer, heads=self.heads, concat=self.concat, **edge)
+
+
 class GAT(nn.Module):
     """torch_geometric.nn.models.GAT(in, hidden, num_layers=2, out_channels, dropout, act='relu', heads=K): as PyG's GAT.init_conv, layer 0 is
     GATConv(in, hidden // K, heads=K, concat=True) and the last layer GATConv(hidden, out, heads=K, concat=False).  edge_dim = 1 is handed
     to both layers, and `edge_weight` then reaches them as their edge attribute (PyG: GAT(..., edge_dim=1) with
-    edge_attr = edge_weight.view(-1, 1))."""
+    edge_attr = edge_weight.view(-1, 1)).  v2=True builds the same two shapes from GATv2Conv (PyG: GAT(..., v2=True))."""
     supports_edge_weight = False
 
-    def __init__(self, in_channels, hidden_channels, num_layers, out_channels, dropout=0.0, act='relu', heads=1, edge_dim=None):
+    def __init__(self, in_channels, hidden_channels, num_layers, out_channels, dropout=0.0, act='relu', heads=1, edge_dim=None, v2=False):
         super().__init__()
         if num_layers != 2 or act != 'relu':
             raise NotImplementedError
         if hidden_channels % heads != 0:
             raise ValueError(f"Ensure that the number of output channels of 'GATConv' (got '{hidden_channels}') is divisible by the number "
                              f"of heads (got '{heads}')")
-        self.dropout, self.heads, self.edge_dim = dropout, int(heads), edge_dim
-        self.convs = nn.ModuleList([GATConv(in_channels, hidden_channels // heads, heads=heads, concat=True, dropout=dropout, edge_dim=edge_dim),
-                                    GATConv(hidden_channels, out_channels, heads=heads, concat=False, dropout=dropout, edge_dim=edge_dim)])
+        self.dropout, self.heads, self.edge_dim, self.v2 = dropout, int(heads), edge_dim, bool(v2)
+        Conv = GATv2Conv if self.v2 else GATConv
+        self.convs = nn.ModuleList([Conv(in_channels, hidden_channels // heads, heads=heads, concat=True, dropout=dropout, edge_dim=edge_dim),
+                                    Conv(hidden_channels, out_channels, heads=heads, concat=False, dropout=dropout, edge_dim=edge_dim)])
 
     def forward(self, x, edge_index, edge_weight=None):
         # without edge_dim, edge_weight is dropped, exactly as PyG's BasicGNN does for a conv without edge-weight support
@@ -201,17 +249,21 @@ class GATModel(nn.Module):
     """model.py:189-208.  `heads` is accepted and unused, as in the reference (its GATModel never hands it to GAT, so reference
     checkpoints are one-head); the keyword-only `gat_heads` is what reaches GAT (default 1 = the reference's model).  The keyword-only
     `gat_edge_weight=True` builds GAT(..., edge_dim=1): the sampled edge weights enter the attention logits and receive the task
-    gradient (default False = the reference's model, which drops them)."""
+    gradient (default False = the reference's model, which drops them).  The keyword-only `gat_v2=True` builds GAT(..., v2=True): both
+    layers are GATv2Conv (dynamic attention); it combines with `gat_heads` and `gat_edge_weight`, and the default False draws, computes and
+    counts dropout seeds exactly as the model without the keyword."""
 
-    def __init__(self, in_channels, hidden_dim, num_classes, dropout_prob=0.3, heads=8, edge_mlp_type='MLP', *, gat_heads=1, gat_edge_weight=False):
+    def __init__(self, in_channels, hidden_dim, num_classes, dropout_prob=0.3, heads=8, edge_mlp_type='MLP', *, gat_heads=1, gat_edge_weight=False,
+                 gat_v2=False):
         super().__init__()
         from .scorer import get_edge_mlp
         self.edge_prob_mlp = get_edge_mlp(in_channels, hidden_dim, dropout_prob, edge_mlp_type)
         self.dropout_prob = dropout_prob
         self.gat_heads = int(gat_heads)
         self.gat_edge_weight = bool(gat_edge_weight)
+        self.gat_v2 = bool(gat_v2)
         self.GAT = GAT(in_channels=in_channels, hidden_channels=hidden_dim, num_layers=2, out_channels=num_classes,
-                       dropout=dropout_prob, act='relu', heads=self.gat_heads, edge_dim=1 if self.gat_edge_weight else None)
+                       dropout=dropout_prob, act='relu', heads=self.gat_heads, edge_dim=1 if self.gat_edge_weight else None, v2=self.gat_v2)
 
     def forward(self, data, edge_index, edge_weight=None):
         from .utils import segment

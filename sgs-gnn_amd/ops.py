@@ -1670,6 +1670,126 @@ def _gat_aggregate_edge(xl, a_s, a_d, bias, graph, negative_slope, p_att, seed_a
                                    int(seed_att), int(site_att), act, float(p_act), int(seed_act), int(site_act))
 
 
+# ---- GATv2 attention (GATv2Conv: the non-linearity inside the dot product; csrc/gatv2.hip, sgs_gatv2_*)
+class _GATv2Aggregate(torch.autograd.Function):
+    """out = act( sum_k alpha_k xl[src_k] + alpha_loop xl[i] + bias ), alpha = dropout(softmax_h(att_h . leaky_relu(xl[src] + xr[i] (+ w le)))).
+    Forward: 2 launches (gathering softmax, aggregation); backward: the activation's + 5 (transposed per-head SpMM, per-head SDDMM, the
+    by-destination softmax backward with its finishing sum, the by-source d xl).  `nm` None: no edge term."""
+
+    @staticmethod
+    def forward(ctx, xl, xr, att, bias, le, handle, nm, graph, K, concat, slope, p_att, seed_att, site_att, act, p_act, seed_act, site_act):
+        L = _lib.lib()
+        N, D = xl.shape
+        C = D // K
+        n = graph.n_edges
+        f32 = dict(dtype=torch.float32, device=xl.device)
+        edge = nm is not None and n > 0                        # without edges every loop carries weight 0: the term vanishes
+        soft, alpha = torch.empty(max(n, 1), K, **f32), torch.empty(max(n, 1), K, **f32)
+        soft_loop, alpha_loop = torch.empty(N, K, **f32), torch.empty(N, K, **f32)
+        loop = torch.empty(2, max(N, 1), **f32) if edge else None                  # wbar, 1 / cnt
+        _lib.check(L.sgs_gatv2_alpha_heads_fwd(_ptr(xl, torch.float32), _ptr(xr, torch.float32), _ptr(att, torch.float32),
+                                               _ptr(nm.w, torch.float32) if edge else None, _ptr(le, torch.float32) if edge else None, N, K, C, n,
+                                               _ptr(graph.in_ptr), _ptr(graph.in_src), _ptr(graph.in_eid), float(slope), float(p_att), seed_att,
+                                               site_att, _ptr(soft), _ptr(soft_loop), _ptr(alpha), _ptr(alpha_loop),
+                                               loop[0].data_ptr() if edge else None, loop[1].data_ptr() if edge else None, _stream()),
+                   "sgs_gatv2_alpha_heads_fwd")
+        Y = _spmm_heads(xl, graph.in_ptr, graph.in_src, graph.in_eid, alpha, alpha_loop, HEADS_CONCAT if concat else HEADS_MEAN, bias, act,
+                        p_act, seed_act, site_act, N, K, C, n)
+        ctx.save_for_backward(xl, xr, att, le, soft, soft_loop, alpha, alpha_loop, loop, Y if act != ACT_NONE else None)
+        ctx.nm, ctx.graph, ctx.edge, ctx.slope, ctx.p_att, ctx.seed_att, ctx.site_att = nm, graph, edge, float(slope), float(p_att), seed_att, site_att
+        ctx.act, ctx.p_act, ctx.has_bias, ctx.K, ctx.concat = act, float(p_act), bias is not None, K, bool(concat)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        L = _lib.lib()
+        xl, xr, att, le, soft, soft_loop, alpha, alpha_loop, loop, Y = ctx.saved_tensors
+        nm, gr, K, edge = ctx.nm, ctx.graph, ctx.K, ctx.edge
+        N, D = xl.shape
+        C = D // K
+        n = gr.n_edges
+        f32 = dict(dtype=torch.float32, device=xl.device)
+        dY = dY.contiguous()
+        dbias = None
+        if ctx.act != ACT_NONE and ctx.has_bias:
+            dZ, dbias = _act_bwd_colsum(dY, Y, ctx.act, ctx.p_act)
+        elif ctx.act != ACT_NONE:
+            dZ = torch.empty_like(dY)
+            _lib.check(L.sgs_act_bwd(_ptr(dY), _ptr(Y), dY.numel(), ctx.act, ctx.p_act, _ptr(dZ), _stream()), "sgs_act_bwd")
+        else:
+            dZ = dY
+            dbias = _colsum(dZ) if ctx.has_bias else None
+        dxl = _spmm_heads(dZ, gr.out_ptr, gr.out_dst, gr.out_eid, alpha, alpha_loop, HEADS_CONCAT if ctx.concat else HEADS_BROADCAST, None,
+                          ACT_NONE, 0.0, 0, 0, N, K, C, n)
+        galpha, gloop = torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32)
+        _lib.check(L.sgs_sddmm_csr_heads(_ptr(dZ), _ptr(xl), N, K, C, n, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid),
+                                         0 if ctx.concat else 1, _ptr(galpha), _ptr(gloop), _stream()), "sgs_sddmm_csr_heads")
+        g_logit, g_loop = torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32)
+        dxr = torch.empty_like(xr)
+        datt = torch.empty(D, **f32) if N > 0 else torch.zeros(D, **f32)
+        dle = dw = dw_add = None
+        second = False
+        if edge:
+            # the other layer's d w, if it has reported already, is added on the way out (no autograd add launch): see gat_edge_attr
+            second = nm._park_ok and nm._g_first is not None and nm._g_extra is None and nm._g_first.numel() == n
+            dw_add = nm._g_first.contiguous() if second else None
+            dw, dle = torch.empty(n, **f32), torch.empty(D, **f32)
+        elif le is not None:
+            dle = torch.zeros(D, **f32)
+        ws = workspace(L.sgs_gatv2_alpha_heads_bwd_workspace_bytes(N, K, C), xl.device)
+        w_ptr, le_ptr = (_ptr(nm.w), _ptr(le)) if edge else (None, None)
+        wb_ptr, ic_ptr = (loop[0].data_ptr(), loop[1].data_ptr()) if edge else (None, None)
+        _lib.check(L.sgs_gatv2_alpha_heads_bwd(_ptr(xl), _ptr(xr), _ptr(att), w_ptr, le_ptr, wb_ptr, ic_ptr, N, K, C, n, _ptr(gr.in_ptr),
+                                               _ptr(gr.in_src), _ptr(gr.in_eid), ctx.slope, ctx.p_att, ctx.seed_att, ctx.site_att, _ptr(soft),
+                                               _ptr(soft_loop), _ptr(galpha), _ptr(gloop), _ptr(dw_add), _ptr(g_logit), _ptr(g_loop), _ptr(dxr),
+                                               _ptr(datt), _ptr(dle) if edge else None, _ptr(dw), ws.data_ptr(), ws.numel(), _stream()),
+                   "sgs_gatv2_alpha_heads_bwd")
+        _lib.check(L.sgs_gatv2_dxl_heads(_ptr(xl), _ptr(xr), _ptr(att), w_ptr, le_ptr, wb_ptr, _ptr(g_logit), _ptr(g_loop), N, K, C, n,
+                                         _ptr(gr.out_ptr), _ptr(gr.out_dst), _ptr(gr.out_eid), ctx.slope, 1, _ptr(dxl), _stream()),
+                   "sgs_gatv2_dxl_heads")
+        g_handle = None
+        if ctx.needs_input_grad[5]:
+            if edge:
+                g_handle = _handle_grad(nm, dw)
+                if second and g_handle is None:
+                    nm._extra_total = True
+            else:
+                g_handle = _handle_grad(nm, torch.zeros(n, **f32))
+        return (dxl, dxr, datt, dbias, dle, g_handle) + (None,) * 12
+
+
+def gatv2_aggregate(xl, xr, att, bias, graph: Graph, negative_slope=0.2, p_att=0.0, seed_att=0, site_att=0, act=ACT_NONE, p_act=0.0,
+                    seed_act=0, site_act=0, heads=1, concat=True, *, edge_weight=None, lin_edge=None):
+    """GATv2Conv's attention softmax + aggregation (+ bias / act / dropout) as one autograd node, for 1 <= heads <= 16:
+    xl = lin_l(x), xr = lin_r(x) [N, heads C] (head-major columns), att with heads C elements ([1, heads, C]); the logit of an entry j -> i
+    is att_h . leaky_relu(xl[j, h] + xr[i, h]) (+ edge_weight[e] lin_edge[h] inside the leaky_relu).  concat=True -> [N, heads C], False ->
+    the mean over heads [N, C]; `bias` matches.  `edge_weight` ([n_edges] f32 by edge id, or the EdgeAttr that gat_edge_attr made of it for
+    both layers) comes with `lin_edge` (lin_edge.weight, heads C elements); the added loops carry their node's mean in-weight.
+    Differentiable wrt xl, xr, att, bias, lin_edge and the edge weights; dropout sites and keys are gat_aggregate's."""
+    _need_gpu(xl, xr, att, bias, lin_edge)
+    if (edge_weight is None) != (lin_edge is None):
+        raise RuntimeError("gatv2_aggregate: edge_weight and lin_edge come together")
+    heads = _check_heads(xl, heads)
+    N, D = xl.shape
+    if tuple(xr.shape) != (N, D) or att.numel() != D or xl.dtype != torch.float32 or xr.dtype != torch.float32 or att.dtype != torch.float32:
+        raise RuntimeError(f"gatv2_aggregate: xr must be float32 [{N}, {D}] like xl and att have {D} elements")
+    width = D if concat else D // heads
+    if bias is not None and bias.numel() != width:
+        raise RuntimeError(f"gatv2_aggregate: bias must have {width} elements")
+    nm = handle = le = None
+    if edge_weight is not None:
+        nm = edge_weight if isinstance(edge_weight, EdgeAttr) else gat_edge_attr(graph, edge_weight)
+        _need_gpu(nm.w)
+        if nm.graph is not graph:
+            raise RuntimeError("gatv2_aggregate: edge_weight was wrapped for another graph")
+        if lin_edge.numel() != D or lin_edge.dtype != torch.float32:
+            raise RuntimeError(f"gatv2_aggregate: lin_edge must be float32 with {D} elements")
+        handle, le = nm.handle, lin_edge.reshape(D).contiguous()
+    return _GATv2Aggregate.apply(xl.contiguous(), xr.contiguous(), att.reshape(D).contiguous(), bias, le, handle, nm, graph, heads, bool(concat),
+                                 float(negative_slope), float(p_att), int(seed_att), int(site_att), act, float(p_act), int(seed_act),
+                                 int(site_act))
+
+
 # ------------------------------------------------------------------ node-level Linear with a hand-written weight gradient
 class _LinearNoBias(torch.autograd.Function):
     """y = x W^T (library GEMM); dW = dY^T x on the f32 matrix cores (sgs_gemm_tn); dx = dY W (library)."""

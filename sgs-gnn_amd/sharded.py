@@ -203,6 +203,9 @@ def _no_cheb_order(model, where):
     if getattr(model, "gat_edge_weight", False):
         raise NotImplementedError(f"{where}: GATModel(gat_edge_weight=True) is not built for the sharded trainers (single-GPU train / "
                                   "evaluate serve gat_edge_weight)")
+    if getattr(model, "gat_v2", False):
+        raise NotImplementedError(f"{where}: GATModel(gat_v2=True) is not built for the sharded trainers (single-GPU train / evaluate serve "
+                                  "gat_v2)")
 
 
 @torch.no_grad()
