@@ -847,6 +847,25 @@ int sgs_gemm_tn_colsum(const float* A, const float* B, int64_t K, int64_t M, int
  * colsum_A may be NULL (otherwise as sgs_gemm_tn_colsum).  Workspace: sgs_gemm_tn_workspace_bytes(K, M, N). */
 int sgs_gemm_tn_ld(const float* A, const float* B, int64_t K, int64_t M, int64_t N, float* C, int64_t ldc, float* colsum_A, void* ws,
                    size_t ws_bytes, sgs_stream_t stream);
+/* Several independent products in one call: the weight gradients of a training step are leaves of its backward (only the optimiser
+ * reads them), each a latency-bound launch of a few dozen workgroups at partition size.  The problems whose shape takes the
+ * partition-sized kernel (one workgroup per 32 x 32 tile of C, its waves the K-slices; sgs_gemm_tn_group_supported > 0) share ONE
+ * launch per workgroup size, up to eight problems each, over the sum of their tiles; every other problem goes through sgs_gemm_tn_ld
+ * in list order (and needs its `ws`; the grouped ones do not read it).  Every C is bit-identical to the single call's.  The
+ * problems must be independent: no C may overlap an operand or another C.  ldc = 0 means N.
+ * sgs_gemm_tn_group_supported: the waves per workgroup (2, 4, 8 or 16) the partition-sized kernel runs this shape with, 0 when the
+ * shape takes another kernel -- the single call and the grouped one both decide by it. */
+typedef struct SgsGemmTnProblem {
+    const float* A;        /* [K, M] */
+    const float* B;        /* [K, N] */
+    int64_t K, M, N;
+    float* C;              /* [M, N], row stride ldc */
+    int64_t ldc;
+    void* ws;              /* sgs_gemm_tn_workspace_bytes(K, M, N); may be NULL when sgs_gemm_tn_group_supported(K, M, N) > 0 */
+    size_t ws_bytes;
+} SgsGemmTnProblem;
+int sgs_gemm_tn_group_supported(int64_t K, int64_t M, int64_t N);
+int sgs_gemm_tn_group(const SgsGemmTnProblem* problems, int count, sgs_stream_t stream);
 
 /* ----------------------------------------------------------------------------------
  * Effective-resistance edge prior (datasets.py:159-173 add_ER; estimator: EffectiveResistanceWeights.ipynb cell 11 er_edge).

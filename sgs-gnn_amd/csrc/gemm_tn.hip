@@ -56,12 +56,13 @@ __global__ void __launch_bounds__(64) gemm_tn_tile(const float* __restrict__ A, 
 // workgroup, their partial tiles meet in LDS in a fixed tree and wave 0 writes C (row stride ldc) -- no slab round trip through
 // HBM and no reduction launch (a step of the learned branch holds eight of these products; each second launch cost ~5 us).
 constexpr int kWgUnroll = 8;              // k2-steps in flight per wave (16 measured slower by ~1.5 us per launch)
+// (the body of one workgroup = one output tile (ti, tj); shared by the single-problem kernel and the grouped one below, so that both
+// run the same products and sums in the same order)
 template <int NW>
-__global__ void __launch_bounds__(64 * NW) gemm_tn_wg(const float* __restrict__ A, const float* __restrict__ B, int64_t K, int M, int N,
-                                                     float* __restrict__ C, int64_t ldc) {
+__device__ __forceinline__ void gemm_tn_wg_tile(const float* __restrict__ A, const float* __restrict__ B, int64_t K, int M, int N,
+                                                float* __restrict__ C, int64_t ldc, int ti, int tj) {
     __shared__ float red[NW][16][64];                                       // every wave's partial tile: 4 KB each
     const int lane = threadIdx.x & 63, s = threadIdx.x >> 6, kh = lane >> 5, l31 = lane & 31;
-    const int ti = blockIdx.x, tj = blockIdx.y;
     const int i = ti * 32 + l31, j = tj * 32 + l31;
     const bool iok = i < M, jok = j < N;
     const int64_t per = ((K + NW - 1) / NW + 1) & ~int64_t(1);              // even slice length, as gemm_tn_tile with ksplit = NW
@@ -104,6 +105,43 @@ __global__ void __launch_bounds__(64 * NW) gemm_tn_wg(const float* __restrict__ 
         const int row = ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
         if (row < M) C[static_cast<int64_t>(row) * ldc + j] = sum;
     }
+}
+
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) gemm_tn_wg(const float* __restrict__ A, const float* __restrict__ B, int64_t K, int M, int N,
+                                                     float* __restrict__ C, int64_t ldc) {
+    gemm_tn_wg_tile<NW>(A, B, K, M, N, C, ldc, blockIdx.x, blockIdx.y);
+}
+
+// Several independent products in ONE launch (sgs_gemm_tn_group): the weight gradients of a step's node-level layers are leaves of the
+// backward -- only the optimiser reads them -- and each is a latency-bound launch of 16 .. 152 workgroups, so run one after the other they
+// cost their launch floors and dependent-load chains in series.  The descriptor block travels by value (the idiom of adam_multi); the grid
+// is one-dimensional over the problems' 32 x 32 tiles, problem p owning tiles first_tile[p] .. first_tile[p + 1] - 1 with ti fastest, as
+// the single kernel's two-dimensional grid is walked.  A workgroup looks its problem up (workgroup-uniform: scalar loads) and runs
+// gemm_tn_wg_tile on it: every C is bit-identical to the single launch's.
+constexpr int kGroupMax = 8;
+struct GemmTnDesc {
+    const float* A;
+    const float* B;
+    float* C;
+    int64_t K, ldc;
+    int M, N;
+    int first_tile, tiles_i;          // first tile of the problem in the grid; its number of 32-row tiles, cdiv(M, 32)
+};
+struct GemmTnGroupArgs {
+    GemmTnDesc d[kGroupMax];
+    int count;
+};
+
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) gemm_tn_wg_group(GemmTnGroupArgs a) {
+    const int t = static_cast<int>(blockIdx.x);
+    int pi = 0;
+    while (pi + 1 < a.count && t >= a.d[pi + 1].first_tile) ++pi;
+    const GemmTnDesc& d = a.d[pi];
+    const int local = t - d.first_tile;
+    const int tj = local / d.tiles_i, ti = local - tj * d.tiles_i;
+    gemm_tn_wg_tile<NW>(d.A, d.B, d.K, d.M, d.N, d.C, d.ldc, ti, tj);
 }
 
 // `N`, `ldc`: C is written with row stride ldc (>= N): the result may be a column block of a wider matrix (fc1.weight's halves)
@@ -859,6 +897,15 @@ inline int pick_ksplit(int64_t K, int64_t M, int64_t N) {
     return ks;
 }
 
+// Waves per workgroup of the partition-sized path (gemm_tn_wg<NW>: the K-slices are the waves of one workgroup), 0 for the shapes
+// that take another kernel.  The single launcher and the grouped one both switch on this.
+inline int wg_waves(int64_t K, int64_t M, int64_t N) {
+    if (K <= 0 || M <= 0 || N <= 0 || use_tall(K, M, N)) return 0;
+    const int ks = pick_ksplit(K, M, N);
+    if (ks == 8 && K >= 512) return 16;   // sixteen 64-row slices: half the dependent load batches per wave (the launch is latency-bound)
+    return (ks == 2 || ks == 4 || ks == 8) ? ks : 0;
+}
+
 }  // namespace
 }  // namespace sgs
 
@@ -1078,14 +1125,13 @@ static int gemm_tn_impl(const float* A, const float* B, int64_t K, int64_t M, in
     else if (use_tall(K, M, N))
         hipLaunchKernelGGL(gemm_tn_tall_tile, dim3(cdiv(M, 128), cdiv(N, 64), ks), dim3(64), 0, stream, A, B, K, static_cast<int>(M),
                            static_cast<int>(N), ks, dst, colsum_A ? cpart : static_cast<float*>(nullptr));
-    else if (ks == 2 || ks == 4 || ks == 8) {
+    else if (const int nw = wg_waves(K, M, N)) {
         // partition-sized K: the K-slices are the waves of one workgroup, reduced in LDS, C written in place (any ldc)
         const dim3 grid(cdiv(M, 32), cdiv(N, 32));
         const int64_t ld = ldc > 0 ? ldc : N;
-        if (ks == 8 && K >= 512)      // sixteen 64-row slices: half the dependent load batches per wave (the launch is latency-bound)
-            hipLaunchKernelGGL((gemm_tn_wg<16>), grid, dim3(1024), 0, stream, A, B, K, static_cast<int>(M), static_cast<int>(N), C, ld);
-        else if (ks == 8) hipLaunchKernelGGL((gemm_tn_wg<8>), grid, dim3(512), 0, stream, A, B, K, static_cast<int>(M), static_cast<int>(N), C, ld);
-        else if (ks == 4) hipLaunchKernelGGL((gemm_tn_wg<4>), grid, dim3(256), 0, stream, A, B, K, static_cast<int>(M), static_cast<int>(N), C, ld);
+        if (nw == 16)     hipLaunchKernelGGL((gemm_tn_wg<16>), grid, dim3(1024), 0, stream, A, B, K, static_cast<int>(M), static_cast<int>(N), C, ld);
+        else if (nw == 8) hipLaunchKernelGGL((gemm_tn_wg<8>), grid, dim3(512), 0, stream, A, B, K, static_cast<int>(M), static_cast<int>(N), C, ld);
+        else if (nw == 4) hipLaunchKernelGGL((gemm_tn_wg<4>), grid, dim3(256), 0, stream, A, B, K, static_cast<int>(M), static_cast<int>(N), C, ld);
         else              hipLaunchKernelGGL((gemm_tn_wg<2>), grid, dim3(128), 0, stream, A, B, K, static_cast<int>(M), static_cast<int>(N), C, ld);
         SGS_LAUNCH_OK();
         return SGS_OK;
@@ -1096,6 +1142,58 @@ static int gemm_tn_impl(const float* A, const float* B, int64_t K, int64_t M, in
         hipLaunchKernelGGL(gemm_tn_reduce, dim3(cdiv(M * N + (colsum_A ? M : 0), 256)), dim3(256), 0, stream, slab, M * N, n_slabs, C,
                            static_cast<const float*>(colsum_A ? cpart : nullptr), static_cast<int>(M), colsum_A, static_cast<int>(N), ldc);
     SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_gemm_tn_group_supported(int64_t K, int64_t M, int64_t N) { return wg_waves(K, M, N); }
+
+int sgs_gemm_tn_group(const SgsGemmTnProblem* problems, int count, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(count >= 0 && (count == 0 || problems), SGS_EINVAL, "sgs_gemm_tn_group: bad problem list");
+    for (int p = 0; p < count; ++p) {
+        const SgsGemmTnProblem& q = problems[p];
+        SGS_REQUIRE(q.K >= 0 && q.M >= 0 && q.N >= 0 && q.M < (1 << 30) && q.N < (1 << 30), SGS_EINVAL, "sgs_gemm_tn_group: bad sizes");
+        SGS_REQUIRE(q.ldc == 0 || q.ldc >= q.N, SGS_EINVAL, "sgs_gemm_tn_group: ldc < N");
+        SGS_REQUIRE(q.M == 0 || q.N == 0 || (q.C && (q.K == 0 || (q.A && q.B))), SGS_EINVAL, "sgs_gemm_tn_group: null pointer");
+    }
+    // the problems of every workgroup size, in list order, eight to a launch
+    for (int nw = 16; nw >= 2; nw >>= 1) {
+        GemmTnGroupArgs a;
+        a.count = 0;
+        int tiles = 0;
+        auto flush = [&]() {
+            if (a.count == 0) return;
+            for (int z = a.count; z < kGroupMax; ++z) a.d[z] = a.d[0];
+            const dim3 grid(static_cast<unsigned>(tiles));
+            if (nw == 16)     hipLaunchKernelGGL((gemm_tn_wg_group<16>), grid, dim3(1024), 0, stream, a);
+            else if (nw == 8) hipLaunchKernelGGL((gemm_tn_wg_group<8>), grid, dim3(512), 0, stream, a);
+            else if (nw == 4) hipLaunchKernelGGL((gemm_tn_wg_group<4>), grid, dim3(256), 0, stream, a);
+            else              hipLaunchKernelGGL((gemm_tn_wg_group<2>), grid, dim3(128), 0, stream, a);
+            a.count = 0;
+            tiles = 0;
+        };
+        for (int p = 0; p < count; ++p) {
+            const SgsGemmTnProblem& q = problems[p];
+            if (wg_waves(q.K, q.M, q.N) != nw) continue;
+            GemmTnDesc& d = a.d[a.count++];
+            d.A = q.A; d.B = q.B; d.C = q.C;
+            d.K = q.K; d.ldc = q.ldc > 0 ? q.ldc : q.N;
+            d.M = static_cast<int>(q.M); d.N = static_cast<int>(q.N);
+            d.first_tile = tiles;
+            d.tiles_i = static_cast<int>(cdiv(q.M, 32));
+            tiles += d.tiles_i * static_cast<int>(cdiv(q.N, 32));     // (< 1024 tiles per problem on this path: pick_ksplit)
+            if (a.count == kGroupMax) flush();
+        }
+        flush();
+    }
+    SGS_LAUNCH_OK();
+    // every other shape: the single launcher, in list order
+    for (int p = 0; p < count; ++p) {
+        const SgsGemmTnProblem& q = problems[p];
+        if (wg_waves(q.K, q.M, q.N) != 0) continue;
+        const int rc = gemm_tn_impl(q.A, q.B, q.K, q.M, q.N, q.C, nullptr, q.ws, q.ws_bytes, stream, q.ldc);
+        if (rc != SGS_OK) return rc;
+    }
     return SGS_OK;
 }
 

@@ -4,6 +4,7 @@ and autograd bookkeeping only; every numeric step of the hot path runs in libsgs
 Nothing here computes on the CPU: a non-HIP tensor raises."""
 from __future__ import annotations
 
+import ctypes
 import os
 
 import numpy as np
@@ -149,6 +150,127 @@ def drop_memos(module) -> None:
     for mod in module.modules():
         if getattr(mod, "_lin_cache", None) is not None:
             mod._lin_cache = None
+
+
+# ------------------------------------------------------------------ deferred leaf weight gradients
+# The node-level weight gradients dW = dY^T x (sgs_gemm_tn) are leaves of a backward pass: nothing in it reads them, only the optimiser
+# does.  Inside a `deferred_weight_grads` scope the autograd functions below do not launch such a product where they form it: they
+# allocate dW, queue (dY, x, dW) and return dW, and ONE sgs_gemm_tn_group call at the end of the backward (autograd's end-of-backward
+# callback) runs all of them -- a launch of 16 .. 152 workgroups is latency-bound, so together they cost about what the largest costs
+# alone.  Opt-in: without a scope every product is launched immediately, as before.  Inside one, a product is
+# deferred only if nothing can read dW before the flush (_leaf_slot_ok): the parameter's gradient is formed by exactly one node of this
+# backward, its .grad is None (AccumulateGrad then takes the tensor as it is) and it carries no hooks.  The flush checks that this is
+# what happened -- .grad IS the queued buffer -- and raises otherwise.
+GEMM_TN_LAUNCHES = {"single": 0, "group": 0}     # library calls made for leaf weight gradients (tests)
+_defer = None                                    # the open deferred_weight_grads scope
+_defer_enabled = True                            # False: the scopes do nothing (A/B switch: set_deferred_weight_grads)
+
+
+def set_deferred_weight_grads(on: bool) -> None:
+    """A/B switch (tests, tools): with False every deferred_weight_grads scope is inert and each product is launched where it is formed."""
+    global _defer_enabled
+    _defer_enabled = bool(on)
+
+
+class deferred_weight_grads:
+    """with deferred_weight_grads(loss): loss.backward(...) -- see above.  `roots`: the tensors backward() is called on (their graph is
+    walked once, to count the gradient producers of every parameter)."""
+
+    def __init__(self, *roots):
+        self.roots = roots
+        self.producers, self.queue, self.armed, self.prev = {}, [], False, None
+
+    def __enter__(self):
+        global _defer
+        self.prev = _defer
+        if not _defer_enabled:
+            return self
+        seen, stack = set(), [r.grad_fn for r in self.roots if r.grad_fn is not None]
+        prod = self.producers = {}
+        while stack:
+            fn = stack.pop()
+            if fn in seen:
+                continue
+            seen.add(fn)
+            for nxt, _ in fn.next_functions:
+                if nxt is None:
+                    continue
+                if hasattr(nxt, "variable"):                   # AccumulateGrad
+                    prod[nxt] = prod.get(nxt, 0) + 1
+                else:
+                    stack.append(nxt)
+        self.queue, self.armed = [], False
+        self.prev, _defer = _defer, self
+        return self
+
+    def __exit__(self, *exc):
+        global _defer
+        _defer = self.prev
+        pending = len(self.queue)
+        self.queue, self.producers, self.armed = [], {}, False          # (a backward that raised never reaches its callback)
+        if pending and exc[0] is None:
+            raise RuntimeError("sgs_gnn_amd: deferred weight gradients were queued but the backward pass ended without flushing them")
+        return False
+
+    def _leaf_slot_ok(self, ctx, slot):
+        """The AccumulateGrad node behind input `slot` of the running backward node if dW may be deferred, else None."""
+        node = ctx.next_functions[slot][0]
+        if node is None or self.producers.get(node) != 1:
+            return None
+        p = node.variable
+        if p.grad is not None or getattr(p, "_backward_hooks", None) or getattr(p, "_post_accumulate_grad_hooks", None):
+            return None
+        return node
+
+    def _enqueue(self, node, dY, x, grad, c_ptr, K, M, N, ldc):
+        if not self.armed:
+            torch.autograd.Variable._execution_engine.queue_callback(self._flush)
+            self.armed = True
+        # (the operands are kept alive -- and their memory out of the allocator's hands -- until the flush; `grad` is NOT: a second
+        # reference would make AccumulateGrad copy the still unwritten tensor instead of taking it)
+        self.queue.append((node, dY, x, grad.data_ptr(), c_ptr, K, M, N, ldc, grad.device.index))
+
+    def _flush(self):
+        q, self.queue, self.armed = self.queue, [], False
+        if not q:
+            return
+        L = _lib.lib()
+        for node, _, _, base, *_ in q:
+            g = node.variable.grad
+            if g is None or g.data_ptr() != base:
+                raise RuntimeError("sgs_gnn_amd: a deferred weight gradient did not become its parameter's .grad as it was (the values "
+                                   "autograd passed on were read before they were written)")
+        words = []
+        for _, dY, x, _, c_ptr, K, M, N, ldc, _ in q:
+            words += [dY.data_ptr(), x.data_ptr(), K, M, N, c_ptr, ldc, 0, 0]
+        arr = (ctypes.c_int64 * len(words))(*words)
+        dev = q[0][9]
+        stream = _raw_stream(dev) if _raw_stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        GEMM_TN_LAUNCHES["group"] += 1
+        _lib.check(L.sgs_gemm_tn_group(arr, len(q), stream), "sgs_gemm_tn_group")
+
+
+def _leaf_dw(dY, x, K, M, N, leaf=None, out=None, col0=0):
+    """dW [M, N] = dY^T x by sgs_gemm_tn, written into `out` [M, ldc] from column col0 on when given (else a new tensor).  `leaf` =
+    (ctx, input slot) of the weight in the running backward node: inside a deferred_weight_grads scope the product joins the scope's
+    grouped launch when it may (see there); otherwise it is launched here."""
+    L = _lib.lib()
+    dW = out if out is not None else torch.empty(M, N, dtype=torch.float32, device=x.device)
+    ldc = dW.shape[1]
+    c_ptr = _ptr(dW) + 4 * col0
+    dY_p, x_p = _ptr(dY, torch.float32), _ptr(x, torch.float32)
+    if _defer is not None and leaf is not None and L.sgs_gemm_tn_group_supported(K, M, N) > 0:
+        node = _defer._leaf_slot_ok(*leaf)
+        if node is not None:
+            _defer._enqueue(node, dY, x, dW, c_ptr, K, M, N, ldc)
+            return dW
+    ws = workspace(L.sgs_gemm_tn_workspace_bytes(K, M, N), x.device)
+    GEMM_TN_LAUNCHES["single"] += 1
+    if out is None:
+        _lib.check(L.sgs_gemm_tn(dY_p, x_p, K, M, N, c_ptr, ws.data_ptr(), ws.numel(), _stream()), "sgs_gemm_tn")
+    else:
+        _lib.check(L.sgs_gemm_tn_ld(dY_p, x_p, K, M, N, c_ptr, ldc, None, ws.data_ptr(), ws.numel(), _stream()), "sgs_gemm_tn_ld")
+    return dW
 
 
 # ------------------------------------------------------------------ randomness
@@ -866,9 +988,7 @@ class _EdgeScore(torch.autograd.Function):
         # the node-level half: U = codes W1b^T  ->  d codes += dU W1b (library GEMM, accumulating),  d W1b = dU^T codes (right half)
         if ctx.needs_input_grad[0]:
             dcodes.addmm_(dU, W1[:, H:])                           # in place (beta = 1): no copy of dcodes
-        wsb = workspace(L.sgs_gemm_tn_workspace_bytes(N, H, H), dev)
-        _lib.check(L.sgs_gemm_tn_ld(_ptr(dU), _ptr(codes), N, H, H, dW1.data_ptr() + 4 * H, 2 * H, None, wsb.data_ptr(), wsb.numel(), _stream()),
-                   "sgs_gemm_tn_ld")
+        _leaf_dw(dU, codes, N, H, H, leaf=(ctx, 1), out=dW1, col0=H)
         return dcodes, dW1, db1, dw2, db2, None, None, None, None, None, None, None, None
 
 
@@ -933,7 +1053,7 @@ def _edge_score_backward_mask(ctx, L, codes, U, W1, b1, w2, b2, edge_index, eid,
         dw2 = torch.empty(H, **f32)
         _lib.check(L.sgs_edge_score_dw2_from_parts(_ptr(W1), _ptr(Traw), _ptr(U), _ptr(Rraw), _ptr(b1), _ptr(craw), N, H, p, _ptr(dw2), _stream()),
                    "sgs_edge_score_dw2_from_parts")
-    return _edge_score_backward_mask_tail(L, codes, W1, dcodes, dU, dW1, db1, dw2, db2)
+    return _edge_score_backward_mask_tail(ctx, L, codes, W1, dcodes, dU, dW1, db1, dw2, db2)
 
 
 def _edge_score_backward_fused(ctx, L, codes, U, W1, b1, w2, edge_index, eid, graph, n, gp_act, kept, bits, dz):
@@ -971,16 +1091,14 @@ def _edge_score_backward_fused(ctx, L, codes, U, W1, b1, w2, edge_index, eid, gr
     dw2 = torch.empty(H, **f32)
     _lib.check(L.sgs_edge_score_dw2_from_parts(_ptr(W1), _ptr(Traw), _ptr(U), _ptr(Rraw), _ptr(b1), _ptr(craw), N, H, p, _ptr(dw2), _stream()),
                "sgs_edge_score_dw2_from_parts")
-    return _edge_score_backward_mask_tail(L, codes, W1, dcodes, dU, dW1, db1, dw2, db2)
+    return _edge_score_backward_mask_tail(ctx, L, codes, W1, dcodes, dU, dW1, db1, dw2, db2)
 
 
-def _edge_score_backward_mask_tail(L, codes, W1, dcodes, dU, dW1, db1, dw2, db2):
+def _edge_score_backward_mask_tail(ctx, L, codes, W1, dcodes, dU, dW1, db1, dw2, db2):
     """The node-level half: U = codes W1b^T  ->  d codes += dU W1b,  d W1b = dU^T codes (right half of d fc1.weight, in place)."""
     N, H = codes.shape
     dcodes.addmm_(dU, W1[:, H:])
-    wsb = workspace(L.sgs_gemm_tn_workspace_bytes(N, H, H), codes.device)
-    _lib.check(L.sgs_gemm_tn_ld(_ptr(dU), _ptr(codes), N, H, H, dW1.data_ptr() + 4 * H, 2 * H, None, wsb.data_ptr(), wsb.numel(), _stream()),
-               "sgs_gemm_tn_ld")
+    _leaf_dw(dU, codes, N, H, H, leaf=(ctx, 1), out=dW1, col0=H)
     return dcodes, dW1, db1, dw2, db2, None, None, None, None, None, None, None, None
 
 
@@ -1808,11 +1926,7 @@ class _LinearNoBias(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = dY @ W
         if ctx.needs_input_grad[1]:
-            K, M, N = x.shape[0], W.shape[0], W.shape[1]
-            dW = torch.empty(M, N, dtype=torch.float32, device=x.device)
-            ws = workspace(L.sgs_gemm_tn_workspace_bytes(K, M, N), x.device)
-            _lib.check(L.sgs_gemm_tn(_ptr(dY, torch.float32), _ptr(x.contiguous(), torch.float32), K, M, N, _ptr(dW), ws.data_ptr(),
-                                     ws.numel(), _stream()), "sgs_gemm_tn")
+            dW = _leaf_dw(dY, x.contiguous(), x.shape[0], W.shape[0], W.shape[1], leaf=(ctx, 1))
         return dx, dW
 
 
@@ -1935,20 +2049,14 @@ def _x_wt(x, W):
     return _spmm(Wt, fc.ptr, fc.col, fc.val, None, None, ACT_NONE, 0.0, 0, 0, fc.N, W.shape[0], fc.nnz)
 
 
-def _dyt_x(dY, x, W_shape):
-    """d W [M, F] = d Y^T x: over the non-zeros of x^T when x has a FeatCSR, else sgs_gemm_tn."""
-    L = _lib.lib()
+def _dyt_x(dY, x, W_shape, leaf=None):
+    """d W [M, F] = d Y^T x: over the non-zeros of x^T when x has a FeatCSR, else sgs_gemm_tn (`leaf`: see _leaf_dw)."""
     fc = feature_csr(x)
     M, Nn = W_shape
     if fc is not None:
         dWt = _spmm(dY.contiguous(), fc.tptr, fc.trow, fc.tval, None, None, ACT_NONE, 0.0, 0, 0, fc.F, M, fc.nnz)      # [F, M]
         return dWt.t().contiguous()
-    K = x.shape[0]
-    dW = torch.empty(M, Nn, dtype=torch.float32, device=x.device)
-    ws = workspace(L.sgs_gemm_tn_workspace_bytes(K, M, Nn), x.device)
-    _lib.check(L.sgs_gemm_tn(_ptr(dY, torch.float32), _ptr(x.contiguous(), torch.float32), K, M, Nn, _ptr(dW), ws.data_ptr(), ws.numel(), _stream()),
-               "sgs_gemm_tn")
-    return dW
+    return _leaf_dw(dY, x.contiguous(), x.shape[0], M, Nn, leaf=leaf)
 
 
 # ------------------------------------------------------------------ one GCN layer as ONE autograd node
@@ -1991,7 +2099,7 @@ class _GCNLayer(torch.autograd.Function):
         if need_x or need_W:
             dxl = _spmm(dZ, gr.out_ptr, gr.out_dst, nm.what_out, nm.what_loop, None, ACT_NONE, 0.0, 0, 0, N, D, gr.n_edges)
             if need_W:
-                dW = _dyt_x(dxl, x, W.shape)
+                dW = _dyt_x(dxl, x, W.shape, leaf=(ctx, 1))
             if need_x:
                 dx = dxl @ W
         if ctx.has_handle and ctx.needs_input_grad[2]:
@@ -2085,7 +2193,7 @@ class _GCN2(torch.autograd.Function):
             else:
                 dxl2 = _spmm(dZ2, gr.out_ptr, gr.out_dst, nm.what_out, nm.what_loop, None, ACT_NONE, 0.0, 0, 0, N, C, gr.n_edges)
         if need_W2:
-            dW2 = _dyt_x(dxl2, h, W2.shape)
+            dW2 = _dyt_x(dxl2, h, W2.shape, leaf=(ctx, 3))
         if want_1 and not ctx.fused:
             dZ1h = dxl2 @ W2
             if need_b1:
@@ -2107,7 +2215,7 @@ class _GCN2(torch.autograd.Function):
             else:
                 dxl1 = _spmm(dZ1, gr.out_ptr, gr.out_dst, nm.what_out, nm.what_loop, None, ACT_NONE, 0.0, 0, 0, N, H, gr.n_edges)
             if need_W1:
-                dW1 = _dyt_x(dxl1, x, W1.shape)
+                dW1 = _dyt_x(dxl1, x, W1.shape, leaf=(ctx, 1))
             if need_x:
                 dx = dxl1 @ W1
         g1 = sddmm(dZ1, xl1, H) if need_g else None

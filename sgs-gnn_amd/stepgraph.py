@@ -540,13 +540,19 @@ class StepGraphs:
         ops.new_memo_scope()
         with torch.cuda.stream(self.stream):
             if not slot.sampled:
-                _ce(self.criterion, self.model(b, b.edge_index), b).backward()
+                loss = _ce(self.criterion, self.model(b, b.edge_index), b)
+                with ops.deferred_weight_grads(loss):          # (as the captures below: the grouped launch has run once before it is recorded)
+                    loss.backward()
             else:
                 st = sampled_forward(self.pipeline, a, self.model, b, self.q, self.use_checkpoint)
                 if st.random_out is not None:
-                    _ce(self.criterion, st.random_out, b).backward(retain_graph=True)
+                    loss = _ce(self.criterion, st.random_out, b)
+                    with ops.deferred_weight_grads(loss):
+                        loss.backward(retain_graph=True)
                     self._clear_grads()
-                learned_loss(a, self.criterion, st, b).backward()
+                loss = learned_loss(a, self.criterion, st, b)
+                with ops.deferred_weight_grads(loss):
+                    loss.backward()
         self._clear_grads()
         torch.cuda.synchronize()
 
@@ -572,7 +578,9 @@ class StepGraphs:
                     self.sync.flat.zero_()                         # gradients of this step + flag word (0: nobody learned here)
                 out = self.model(batch, batch.edge_index)
                 c.loss = _ce(self.criterion, out, batch)
-                c.loss.backward(gradient=self.one)
+                # the leaf weight gradients of a captured backward run as ONE grouped launch at its end, before the optimiser's (ops.deferred_weight_grads)
+                with ops.deferred_weight_grads(c.loss):
+                    c.loss.backward(gradient=self.one)
                 self._steps_and_tick((self.optimizers[1],) if (self.optimizers is not None and not self.dp) else (), c.loss)   # optimizer_gnn (training_hybrid.py:161)
             c.grads = self._grads()
             c.loss = c.loss.detach()
@@ -609,7 +617,8 @@ class StepGraphs:
             if self.dp:
                 self.sync.flat.zero_()
             loss_l = learned_loss(a, self.criterion, st, batch)
-            loss_l.backward(gradient=self.one, retain_graph=st.random_out is not None)
+            with ops.deferred_weight_grads(loss_l):
+                loss_l.backward(gradient=self.one, retain_graph=st.random_out is not None)
             if self.dp:
                 self.sync.flag.fill_(1.0)                          # this rank's gate chose "learned"
             # optimizer_edge_prob, then optimizer_gnn (:136-137), and the step's closing tick: one launch with FusedAdam
@@ -626,7 +635,8 @@ class StepGraphs:
                 if self.dp:
                     self.sync.flat.zero_()
                 loss_r = _ce(self.criterion, st.random_out, batch)
-                loss_r.backward(gradient=self.one)
+                with ops.deferred_weight_grads(loss_r):
+                    loss_r.backward(gradient=self.one)
                 self._steps_and_tick((self.optimizers[1],) if (self.optimizers is not None and not self.dp) else (), loss_r)   # optimizer_gnn only (:141)
             c.grads_r = self._grads()
             c.loss_r = loss_r.detach()

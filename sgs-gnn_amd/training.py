@@ -39,7 +39,7 @@ def _ce(criterion, out, batch):
 
 def _backward(model, loss):
     """training_hybrid.py:22-27: loss.backward() inside the profiler's "backward" segment (a rocTX range, utils.GpuMemoryProfiler)."""
-    with segment(model, "backward"):
+    with segment(model, "backward"), ops.deferred_weight_grads(loss):      # leaf weight gradients: one grouped launch at the end of the pass
         loss.backward()
 
 
