@@ -787,6 +787,36 @@ int sgs_gatv2_dxl_heads(const float* xl, const float* xr, const float* att, cons
                         sgs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K8d: GINE aggregation (PyG 2.3.1 GINEConv, edge_dim = 1 with the edge weight as the attribute, restated; csrc/gine.hip).  x [N, D],
+ * a = lin.weight[:, 0] and b = lin.bias [D] (lin = Linear(1, D)), edge_w [n_edges] by edge id or NULL (unit weights: w = 1.0f in the
+ * same expressions, bitwise the result of a vector of ones), diag = 1 + eps:
+ *   z[i, c] = diag x[i, c] + sum_{e: j -> i} relu(x[j, c] + (edge_w[e] a[c] + b[c]))
+ * (i, i) and duplicate entries are ordinary entries.  Any D >= 1; N = 0, n_edges = 0 and empty rows are fine.  Rows are gathered 16 / 8
+ * bytes at a time when D % 4 / D % 2 == 0 and x, z / dz, d_x, a, b are aligned to that, else column by column; one wave per row, or a
+ * workgroup of 4 / 16 waves per row for few long rows (sgs_gine_variant: kind * 1000 + VEC * 100 + W, a pure host function).
+ *   sgs_gine_aggregate_fwd (dst-CSR: in_ptr / in_src / in_eid) writes z.  It stores no mask.
+ *   sgs_gine_aggregate_bwd (src-CSR: out_ptr / out_dst / out_eid), with m = dz[dst_e, c] where x[j, c] + (edge_w[e] a[c] + b[c]) > 0, else 0:
+ *       d_x[j, c]   = diag dz[j, c] + sum_{e: j -> .} m          (d_x == NULL: not computed, nothing written)
+ *       d_edge_w[e] = sum_c a[c] m (+ dw_add[e] unless NULL: another layer's gradient, summed on the way out)   (NULL: not computed)
+ *       d_a[c] = sum_e edge_w[e] m,  d_b[c] = sum_e m             (both NULL: not computed; else per-workgroup partials in ws,
+ *                                                                 sgs_gine_aggregate_bwd_workspace_bytes(N, D), added in a fixed order by
+ *                                                                 a second small launch; N = 0 writes zeros)
+ * Mask-recompute contract: the backward evaluates the pre-activation with the same explicit expression as the forward, x + (w a + b), on
+ * the same fp32 inputs, and the library is compiled with -ffp-contract=off (no fused multiply-add on either side): the two agree bit
+ * for bit, so an element passes the ReLU in the backward iff it did in the forward.
+ * No float atomics, no memset nodes, no host synchronisation: two identical launches give identical bits.
+ * ---------------------------------------------------------------------------------- */
+int sgs_gine_variant(int64_t N, int64_t D, int64_t nnz, int align_bytes);
+int sgs_gine_aggregate_fwd(const float* x, const float* edge_w, const float* a, const float* b, float diag, int64_t N, int64_t D,
+                           int64_t n_edges, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, float* z,
+                           sgs_stream_t stream);
+size_t sgs_gine_aggregate_bwd_workspace_bytes(int64_t N, int64_t D);
+int sgs_gine_aggregate_bwd(const float* x, const float* dz, const float* edge_w, const float* a, const float* b, float diag, int64_t N,
+                           int64_t D, int64_t n_edges, const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid,
+                           const float* dw_add, float* d_x, float* d_edge_w, float* d_a, float* d_b, void* ws, size_t ws_bytes,
+                           sgs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * K9: Chebyshev layers of order K > 1 (PyG 2.3.1 ChebConv, normalization = 'sym', lambda_max = 2, restated; 1 <= K <= 8 -- the bound is
  * a choice, not a hardware limit; K = 1 callers need none of this, the layer is a Linear).  For edges (s_e -> d_e) with weights w_e:
  *   (i, i) edges are removed (weight 0 in every formula, gradient 0);  deg_n = sum_{e: s_e = n} w_e, summed BY SOURCE (not the GCN

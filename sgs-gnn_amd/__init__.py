@@ -5,7 +5,7 @@ include/sgs_hip.h); this package is the host-side mirror of the reference's call
 from . import _lib, ops  # noqa: F401
 from .ops import scorer_precision  # noqa: F401
 from . import torch_ops  # noqa: F401  (registers torch.ops.sgs.*)
-from .model import GCNConv, GNNModel, GATConv, GATv2Conv, GAT, GATModel, GINConv, GIN, GINModel, ChebConv, ChebModel, set_dropout_seed  # noqa: F401
+from .model import GCNConv, GNNModel, GATConv, GATv2Conv, GAT, GATModel, GINConv, GINEConv, GIN, GINModel, ChebConv, ChebModel, set_dropout_seed  # noqa: F401
 from .scorer import EdgeProbGCN, EdgeProbMLP, EdgeProbSAGE, SAGEConv, get_edge_mlp  # noqa: F401
 from .sampling import gumbel_softmax_sampling, random_edge_sampling, manual_seed  # noqa: F401
 from .training import train, train_hybrid, train_straight_through, train_two_pass, prepare_step_graphs  # noqa: F401

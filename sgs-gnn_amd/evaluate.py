@@ -13,7 +13,9 @@ of a partition run as one pass of batched kernels (ops.ensemble_partition_head) 
 `args.sgs_eval_batch_heads`: absent / None = ("GCN",) (GNNModel only), "all" = GCN, GAT, GIN and Cheb, or a collection of those names;
 other heads keep the serial loop.  A third opt-in, `args.sgs_eval_batch_variants` (absent / None / False = off, True = on), lets the heads'
 own options take the engine too: a GATModel with gat_heads in 2..16 and / or gat_edge_weight=True and a ChebModel with cheb_k in 2..8, when
-their head is selected; without it these models keep the serial loop.  `PATH_COUNTS` records which path each ensemble_evaluate call took.
+their head is selected; without it these models keep the serial loop.  A GATModel(gat_v2=True) and a GINModel(gin_edge_weight=True) keep the
+serial loop whatever the opt-ins say (no batched engine exists for them: the batched GIN engine aggregates transformed features with unit
+weights).  `PATH_COUNTS` records which path each ensemble_evaluate call took.
 """
 from __future__ import annotations
 
@@ -132,7 +134,8 @@ def _batched_ok(args, model, n_draws) -> bool:
     int >= 1, and args.sgs_eval_batch_heads and args.sgs_eval_batch_variants (consulted only then) a valid head selection and None / a
     bool, all checked here, before any partition is read.  A model with gat_heads > 1, gat_edge_weight or cheb_k > 1 takes the engine only
     with sgs_eval_batch_variants=True (per-head GAT kernels / per-draw Chebyshev steps, ops.ensemble_partition_head).  A gat_v2 model keeps
-    the serial loop whatever the opt-ins say: there is no batched GATv2 engine."""
+    the serial loop whatever the opt-ins say: there is no batched GATv2 engine.  So does a gin_edge_weight model: the batched GIN engine
+    (ops._drawn_gin_logits) aggregates transformed features with unit weights, which is not the GINE layer."""
     flag = getattr(args, "sgs_eval_batch", False)
     if not flag:
         return False
@@ -140,7 +143,7 @@ def _batched_ok(args, model, n_draws) -> bool:
         raise ValueError(f"args.sgs_eval_batch={flag!r}: need True (draws per pass from a byte budget) or an int >= 1 (at most k per pass)")
     heads = _eval_heads(args)
     variants = _eval_variants(args)
-    if n_draws < 1 or getattr(model, "gat_v2", False):
+    if n_draws < 1 or getattr(model, "gat_v2", False) or getattr(model, "gin_edge_weight", False):
         return False
     if not variants:                            # without the third opt-in the heads' options keep the serial loop, as before it existed
         if getattr(model, "gat_heads", 1) > 1 or getattr(model, "gat_edge_weight", False) or getattr(model, "cheb_k", 1) > 1:

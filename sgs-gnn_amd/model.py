@@ -302,35 +302,74 @@ class GINConv(nn.Module):
         return ops.linear_nobias(h, l1.weight) + l1.bias
 
 
-class GIN(nn.Module):
-    """torch_geometric.nn.models.GIN(in, hidden, num_layers=2, out, dropout, act='relu'): conv -> relu -> dropout -> conv."""
+class GINEConv(nn.Module):
+    """PyG 2.3.1 GINEConv(nn=MLP, eps=0, train_eps=False, edge_dim=1) with the edge weight as the attribute (restated from its published
+    algorithm; parity with PyG itself is not fixture-pinned): out_i = nn((1 + eps) x_i + sum_{j -> i} relu(x_j + lin(w_e))), lin =
+    Linear(1, in_channels).  On top of GINConv's keys it has `lin.weight` [in, 1] and `lin.bias` [in] (torch.nn.Linear's default
+    initialisation).  The ReLU sits inside the sum, so the aggregation runs at the input width on its own gathering kernels
+    (ops.gine_aggregate); (i, i) and duplicate edges are ordinary entries.  Without edge weights every w_e is 1."""
 
-    def __init__(self, in_channels, hidden_channels, num_layers, out_channels, dropout=0.0, act='relu'):
+    def __init__(self, in_channels, out_channels, eps=0.0, edge_dim=1):
+        super().__init__()
+        if edge_dim != 1:
+            raise ValueError(f"GINEConv: edge_dim = {edge_dim!r}: 1 (the edge weight as the attribute) is supported")
+        self.in_channels, self.out_channels, self.edge_dim = in_channels, out_channels, edge_dim
+        self.nn = _MLP2(in_channels, out_channels)
+        self.register_buffer("eps", torch.tensor([float(eps)]))      # state_dict key, as PyG (train_eps=False)
+        self._eps = float(eps)                                       # host copy: reading the buffer would synchronise
+        self.lin = nn.Linear(edge_dim, in_channels)                   # after GINConv's parameters: those draw exactly as without it
+
+    def forward(self, x, edge_index, edge_weight=None):
+        """`edge_weight`: None, a float32 [n_edges] tensor, or the ops.edge_attr wrapper that both layers of a head share."""
+        attr = edge_weight if isinstance(edge_weight, ops.EdgeAttr) else ops.edge_attr(ops.get_graph(edge_index, x.shape[0]), edge_weight)
+        z = ops.gine_aggregate(x, attr, self.lin.weight, self.lin.bias, 1.0 + self._eps)
+        l0, l1 = self.nn.lins
+        h = torch.relu(ops.linear_nobias(z, l0.weight) + l0.bias)
+        return ops.linear_nobias(h, l1.weight) + l1.bias
+
+
+class GIN(nn.Module):
+    """torch_geometric.nn.models.GIN(in, hidden, num_layers=2, out, dropout, act='relu'): conv -> relu -> dropout -> conv.  edge_dim = 1
+    builds both layers as GINEConv, and `edge_weight` then reaches them as their edge attribute (edge_attr = edge_weight.view(-1, 1));
+    without edge_dim it is dropped, as PyG's BasicGNN does for a conv without edge-weight support."""
+
+    def __init__(self, in_channels, hidden_channels, num_layers, out_channels, dropout=0.0, act='relu', edge_dim=None):
         super().__init__()
         if num_layers != 2 or act != 'relu':
             raise NotImplementedError("the reference instantiates GIN(num_layers=2, act='relu')")
-        self.dropout = dropout
-        self.convs = nn.ModuleList([GINConv(in_channels, hidden_channels), GINConv(hidden_channels, out_channels)])
+        if edge_dim not in (None, 1):
+            raise ValueError(f"GIN: edge_dim = {edge_dim!r}: None and 1 (the edge weight as the attribute) are supported")
+        self.dropout, self.edge_dim = dropout, edge_dim
+        if edge_dim is None:
+            self.convs = nn.ModuleList([GINConv(in_channels, hidden_channels), GINConv(hidden_channels, out_channels)])
+        else:
+            self.convs = nn.ModuleList([GINEConv(in_channels, hidden_channels, edge_dim=edge_dim),
+                                        GINEConv(hidden_channels, out_channels, edge_dim=edge_dim)])
 
     def forward(self, x, edge_index, edge_weight=None):
-        h = F.relu(self.convs[0](x, edge_index))
+        # one wrapper of the weights for both layers: one autograd edge back to them
+        edge = () if self.edge_dim is None else (ops.edge_attr(ops.get_graph(edge_index, x.shape[0]), edge_weight),)
+        h = F.relu(self.convs[0](x, edge_index, *edge))
         p = self.dropout if self.training else 0.0
         if p > 0:
             keep = ops.dropout_keep(_DropoutClock.next_seed(), SITE_GIN, h.shape[0], h.shape[1], p, h.device)
             h = h * keep / (1.0 - p)
-        return self.convs[1](h, edge_index)
+        return self.convs[1](h, edge_index, *edge)
 
 
 class GINModel(nn.Module):
-    """model.py:165-184."""
+    """model.py:165-184.  The keyword-only `gin_edge_weight=True` builds GIN(..., edge_dim=1): both layers are GINEConv, the sampled edge
+    weights enter the messages and receive the task gradient (default False = the reference's model, which drops them: same state_dict
+    keys, same dropout-seed accounting, bitwise the same logits as the model without the keyword)."""
 
-    def __init__(self, in_channels, hidden_dim, num_classes, dropout_prob=0.3, edge_mlp_type='MLP'):
+    def __init__(self, in_channels, hidden_dim, num_classes, dropout_prob=0.3, edge_mlp_type='MLP', *, gin_edge_weight=False):
         super().__init__()
         from .scorer import get_edge_mlp
         self.edge_prob_mlp = get_edge_mlp(in_channels, hidden_dim, dropout_prob, edge_mlp_type)
         self.dropout_prob = dropout_prob
+        self.gin_edge_weight = bool(gin_edge_weight)
         self.GIN = GIN(in_channels=in_channels, hidden_channels=hidden_dim, num_layers=2, out_channels=num_classes,
-                       dropout=dropout_prob, act='relu')
+                       dropout=dropout_prob, act='relu', edge_dim=1 if self.gin_edge_weight else None)
 
     def forward(self, data, edge_index, edge_weight=None):
         from .utils import segment

@@ -1908,6 +1908,84 @@ def gatv2_aggregate(xl, xr, att, bias, graph: Graph, negative_slope=0.2, p_att=0
                                  int(site_act))
 
 
+# ---- GINE aggregation (GINEConv, edge_dim = 1 with the edge weight as the attribute; csrc/gine.hip, sgs_gine_aggregate_*)
+def edge_attr(graph: Graph, w=None) -> EdgeAttr:
+    """The edge weights of one forward as the edge-attribute layers consume them (gat_edge_attr under its general name), shared by both
+    layers of a head.  `w` None: unit weights (an EdgeAttr without weights and without an autograd handle)."""
+    if w is not None:
+        return gat_edge_attr(graph, w)
+    nm = EdgeAttr()
+    nm.graph, nm.w, nm.handle, nm._park_ok, nm._extra_total = graph, None, None, False, False
+    nm._g_first = nm._g_extra = None
+    return nm
+
+
+class _GINEAggregate(torch.autograd.Function):
+    """z = diag x + sum_{j -> i} relu(x_j + (w_e a + b)): one launch forward; backward one launch over the src-CSR (d x, d w by edge id,
+    per-workgroup partials of d a / d b) plus their finishing sum.  No mask is saved: the backward recomputes it (see csrc/gine.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, a, b, handle, nm, diag):
+        L = _lib.lib()
+        gr = nm.graph
+        N, D = x.shape
+        z = torch.empty(N, D, dtype=torch.float32, device=x.device)
+        _lib.check(L.sgs_gine_aggregate_fwd(_ptr(x, torch.float32), _ptr(nm.w, torch.float32), _ptr(a, torch.float32), _ptr(b, torch.float32),
+                                            diag, N, D, gr.n_edges, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid), _ptr(z), _stream()),
+                   "sgs_gine_aggregate_fwd")
+        ctx.save_for_backward(x, a, b)
+        ctx.nm, ctx.diag = nm, diag
+        return z
+
+    @staticmethod
+    def backward(ctx, dZ):
+        L = _lib.lib()
+        x, a, b = ctx.saved_tensors
+        nm, gr = ctx.nm, ctx.nm.graph
+        N, D = x.shape
+        n = gr.n_edges
+        f32 = dict(dtype=torch.float32, device=x.device)
+        dZ = dZ.contiguous()
+        dx = torch.empty(N, D, **f32) if ctx.needs_input_grad[0] else None      # (the first layer's input: neither written nor allocated)
+        want_ab = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dab = torch.empty(2, D, **f32) if want_ab else None
+        want_w = nm.handle is not None and ctx.needs_input_grad[3]
+        dw = dw_add = None
+        second = False
+        if want_w:
+            # the other layer's d w, if it has reported already, is added on the way out (no autograd add launch): see gat_edge_attr
+            second = nm._park_ok and nm._g_first is not None and nm._g_extra is None and nm._g_first.numel() == n
+            dw_add = nm._g_first.contiguous() if second else None
+            dw = torch.empty(n, **f32)
+        ws = workspace(L.sgs_gine_aggregate_bwd_workspace_bytes(N, D), x.device) if want_ab else None
+        _lib.check(L.sgs_gine_aggregate_bwd(_ptr(x), _ptr(dZ, torch.float32), _ptr(nm.w), _ptr(a), _ptr(b), ctx.diag, N, D, n, _ptr(gr.out_ptr),
+                                            _ptr(gr.out_dst), _ptr(gr.out_eid), _ptr(dw_add), _ptr(dx), _ptr(dw),
+                                            dab[0].data_ptr() if want_ab else None, dab[1].data_ptr() if want_ab else None,
+                                            ws.data_ptr() if want_ab else None, ws.numel() if want_ab else 0, _stream()),
+                   "sgs_gine_aggregate_bwd")
+        g_handle = None
+        if want_w:
+            g_handle = _handle_grad(nm, dw)
+            if second and g_handle is None:
+                nm._extra_total = True
+        return dx, (dab[0] if want_ab else None), (dab[1] if want_ab else None), g_handle, None, None
+
+
+def gine_aggregate(x, attr: EdgeAttr, a, b, diag: float = 1.0):
+    """GINEConv's aggregation z_i = diag x_i + sum_{e: j -> i} relu(x_j + (w_e a + b)) as one autograd node.  x float32 [N, D]; `attr` =
+    ops.edge_attr(graph, edge_weight) (one per forward, shared by both layers; without weights every w_e is 1 and there is no gradient to
+    them); a, b with D elements (lin.weight of Linear(1, D) and its bias).  Differentiable wrt x, a, b and the edge weights."""
+    if not isinstance(attr, EdgeAttr):
+        raise RuntimeError("gine_aggregate: attr must come from ops.edge_attr(graph, edge_weight)")
+    _need_gpu(x, a, b, attr.w)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != attr.graph.N or x.shape[1] < 1:
+        raise RuntimeError(f"gine_aggregate: x must be float32 [{attr.graph.N}, D >= 1]")
+    D = x.shape[1]
+    if a.numel() != D or b.numel() != D or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise RuntimeError(f"gine_aggregate: a and b must be float32 with {D} elements")
+    return _GINEAggregate.apply(x.contiguous(), a.reshape(D).contiguous(), b.reshape(D).contiguous(), attr.handle, attr, float(diag))
+
+
 # ------------------------------------------------------------------ node-level Linear with a hand-written weight gradient
 class _LinearNoBias(torch.autograd.Function):
     """y = x W^T (library GEMM); dW = dY^T x on the f32 matrix cores (sgs_gemm_tn); dx = dY W (library)."""

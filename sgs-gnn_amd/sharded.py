@@ -206,6 +206,9 @@ def _no_cheb_order(model, where):
     if getattr(model, "gat_v2", False):
         raise NotImplementedError(f"{where}: GATModel(gat_v2=True) is not built for the sharded trainers (single-GPU train / evaluate serve "
                                   "gat_v2)")
+    if getattr(model, "gin_edge_weight", False):
+        raise NotImplementedError(f"{where}: GINModel(gin_edge_weight=True) is not built for the sharded trainers (single-GPU train / "
+                                  "evaluate serve gin_edge_weight)")
 
 
 @torch.no_grad()
