@@ -12,6 +12,21 @@ namespace {
 constexpr int kT = 256;
 
 // ---------------------------------------------------------------- gate: #correct argmax on train rows
+// One lane's share of a row scan: columns lane, lane + 64, ... in increasing order, so a later equal value never replaces an earlier one.
+// The lane's first column is taken unconditionally, outside the loop: with the "no column yet" sentinel tested inside the loop
+// (`v > best || (v == best && c < bi) || bi == sentinel`) the compiled loop updated `best` but left `bi` at the sentinel whenever
+// `v > best` was false, so a row of -inf (nothing exceeds the initial -inf) had no argmax at all and never counted as correct; torch.argmax
+// gives 0 there (tests/test_gpu_loss_chain.py::test_gate_counts_exact plants such rows).
+__device__ __forceinline__ void lane_argmax(const float* __restrict__ row, int64_t C, int lane, float& best, int& bi) {
+    if (lane >= C) return;
+    best = row[lane];
+    bi = lane;
+    for (int64_t c = lane + 64; c < C; c += 64) {
+        const float v = row[c];
+        if (v > best) { best = v; bi = static_cast<int>(c); }
+    }
+}
+
 // One wave per row; torch.argmax semantics (first maximum wins).
 __global__ void __launch_bounds__(kT) masked_correct(const float* __restrict__ logits, int64_t N, int64_t C,
                                                     const int64_t* __restrict__ y, const uint8_t* __restrict__ mask,
@@ -21,10 +36,7 @@ __global__ void __launch_bounds__(kT) masked_correct(const float* __restrict__ l
     if (i >= N || !mask[i]) return;
     float best = -INFINITY;
     int bi = 0x7fffffff;
-    for (int64_t c = lane; c < C; c += 64) {
-        const float v = logits[i * C + c];
-        if (v > best || (v == best && static_cast<int>(c) < bi) || bi == 0x7fffffff) { best = v; bi = static_cast<int>(c); }
-    }
+    lane_argmax(logits + i * C, C, lane, best, bi);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(best, o, 64);
@@ -52,10 +64,7 @@ __global__ void __launch_bounds__(1024) masked_correct_pair(const float* __restr
     if (i < N && mask[i]) {
         float best = -INFINITY;
         int bi = 0x7fffffff;
-        for (int64_t c = lane; c < C; c += 64) {
-            const float v = logits[i * C + c];
-            if (v > best || (v == best && static_cast<int>(c) < bi) || bi == 0x7fffffff) { best = v; bi = static_cast<int>(c); }
-        }
+        lane_argmax(logits + i * C, C, lane, best, bi);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_xor(best, o, 64);
@@ -90,10 +99,7 @@ __global__ void __launch_bounds__(1024) gate_counts_partial(const float* __restr
     if (i < N && mask[i]) {
         float best = -INFINITY;
         int bi = 0x7fffffff;
-        for (int64_t c = lane; c < C; c += 64) {
-            const float v = logits[i * C + c];
-            if (v > best || (v == best && static_cast<int>(c) < bi) || bi == 0x7fffffff) { best = v; bi = static_cast<int>(c); }
-        }
+        lane_argmax(logits + i * C, C, lane, best, bi);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_xor(best, o, 64);
