@@ -696,6 +696,30 @@ int sgs_scatter_by_eid(const float* in_order, const int32_t* eid, int64_t n, flo
 #define SGS_HEADS_MEAN 1      /* X [N, K C] -> Y [N, C] = mean over heads (GATConv concat = False), fused into the aggregation */
 #define SGS_HEADS_BROADCAST 2 /* X [N, C] shared by the heads -> Y [N, K C] / K: the transposed aggregation behind MEAN's backward */
 int sgs_gat_heads_supported(int64_t K, int64_t C);
+/* Which kernel instantiation and launch shape an entry point of this section picks (a pure host function; the launchers decode ITS
+ * result, so the two cannot drift).  op: SGS_GAT_OP_* below; aligned16 != 0: every pointer the entry point tests is 16-byte aligned
+ * (scores fwd: xl, att_src, att_dst; SpMM: X, Y; SDDMM: A, B; ignored by the others, as is C by SGS_GAT_OP_ROW and N by all but
+ * SGS_GAT_OP_SCORES_BWD).  -1: unsupported (K, C), N < 0 or unknown op.
+ *   code = kind * 1000000 + VEC * 100000 + lg * 10000 + lgG * 1000 + W
+ *   kind  1 gat_scores_heads_fwd       VEC floats per lane and load, 2^lg lanes per (node, head) unit
+ *         2 gat_scores_heads_bwd       W = rows per workgroup (16 | 64 at N >= 4096 | 256 at N >= 65536) (+ gat_scores_bwd_finish)
+ *         3 spmm_csr_heads CONCAT      VEC, 2^lg lanes per row (256 >> lg rows per workgroup)
+ *         4 spmm_csr_heads_mean_lds    MEAN at K C <= 1024: VEC, 2^lg lanes per row over the K C per-head columns
+ *         5 spmm_csr_heads_mean        MEAN at K C > 1024: VEC, 2^lg lanes per row over the C output columns, each walking the heads
+ *         6 spmm_csr_heads BROADCAST   as kind 3
+ *         7 sddmm_csr_heads            VEC, 2^lg lanes per row = KP 2^lgG: 2^lgG lanes per head, KP = 2^(lg - lgG) head slots
+ *         8 sddmm_csr_heads broadcast  as kind 7
+ *         9 the per-row family         W = KP = K rounded up to a power of two (64 / KP entries per step); VEC 1
+ *   VEC = 4 needs C % 4 == 0 and the alignment; lg <= 6. */
+#define SGS_GAT_OP_SCORES_FWD 0      /* sgs_gat_scores_heads_fwd */
+#define SGS_GAT_OP_SCORES_BWD 1      /* sgs_gat_scores_heads_bwd */
+#define SGS_GAT_OP_SPMM_CONCAT 2     /* sgs_spmm_csr_heads, mode SGS_HEADS_CONCAT */
+#define SGS_GAT_OP_SPMM_MEAN 3       /* ... SGS_HEADS_MEAN */
+#define SGS_GAT_OP_SPMM_BROADCAST 4  /* ... SGS_HEADS_BROADCAST */
+#define SGS_GAT_OP_SDDMM 5           /* sgs_sddmm_csr_heads, broadcast == 0 */
+#define SGS_GAT_OP_SDDMM_BROADCAST 6 /* ... broadcast != 0 */
+#define SGS_GAT_OP_ROW 7             /* sgs_gat_alpha_heads_fwd / _bwd, sgs_gat_alpha_heads_edge_fwd / _bwd, sgs_edge_sum_by_row_heads */
+int sgs_gat_heads_variant(int op, int64_t N, int64_t K, int64_t C, int aligned16);
 /* a_src[i, h] = <x'[i, h, :], att_src[h, :]>, a_dst likewise, one pass over x'.  Backward as sgs_gat_scores_bwd with g_src / g_dst [N, K]
  * and d att_* [K, C]; ws: sgs_gat_scores_heads_bwd_workspace_bytes(N, K, C). */
 int sgs_gat_scores_heads_fwd(const float* xl, int64_t N, int64_t K, int64_t C, const float* att_src, const float* att_dst, float* a_src,

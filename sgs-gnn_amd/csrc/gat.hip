@@ -1167,16 +1167,27 @@ inline bool heads_ok(int64_t K, int64_t C) { return K >= 1 && K <= kMaxHeads && 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // KP = K rounded up to a power of two selects the per-row kernels' instantiation
-#define SGS_DISPATCH_KP(KERNEL, K, GRID, STREAM, ...)                                                                   \
+#define SGS_DISPATCH_KPV(KERNEL, KP, GRID, STREAM, ...)                                                                 \
     do {                                                                                                                \
-        switch (log2_ceil(K)) {                                                                                         \
-            case 0: hipLaunchKernelGGL((KERNEL<1>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                     \
-            case 1: hipLaunchKernelGGL((KERNEL<2>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                     \
-            case 2: hipLaunchKernelGGL((KERNEL<4>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                     \
-            case 3: hipLaunchKernelGGL((KERNEL<8>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                     \
+        switch (KP) {                                                                                                   \
+            case 1: hipLaunchKernelGGL((KERNEL<1>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                     \
+            case 2: hipLaunchKernelGGL((KERNEL<2>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                     \
+            case 4: hipLaunchKernelGGL((KERNEL<4>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                     \
+            case 8: hipLaunchKernelGGL((KERNEL<8>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                     \
             default: hipLaunchKernelGGL((KERNEL<16>), GRID, dim3(kT), 0, STREAM, __VA_ARGS__); break;                   \
         }                                                                                                               \
     } while (0)
+#define SGS_DISPATCH_KP(KERNEL, K, GRID, STREAM, ...) SGS_DISPATCH_KPV(KERNEL, 1 << log2_ceil(K), GRID, STREAM, __VA_ARGS__)
+
+// The launch choice of every multi-head entry point (sgs_gat_heads_variant's code, see include/sgs_hip.h), taken apart again
+struct HeadsChoice {
+    int kind, vec, lg, lgG, w;
+    explicit HeadsChoice(int code)
+        : kind(code / 1000000), vec(code / 100000 % 10), lg(code / 10000 % 10), lgG(code / 1000 % 10), w(code % 1000) {}
+};
+inline int heads_code(int kind, int vec, int lg, int lgG, int w) { return kind * 1000000 + vec * 100000 + lg * 10000 + lgG * 1000 + w; }
+inline int min6(int lg) { return lg > 6 ? 6 : lg; }
+inline int heads_kp(int64_t N, int64_t K) { return HeadsChoice(sgs_gat_heads_variant(SGS_GAT_OP_ROW, N, K, 1, 0)).w; }   // the per-row family's KP
 
 }  // namespace
 }  // namespace sgs
@@ -1292,6 +1303,32 @@ int sgs_gat_scores_bwd(const float* xl, int64_t N, int64_t D, const float* att_s
 // ---------------------------------------------------------------- multi-head entry points
 int sgs_gat_heads_supported(int64_t K, int64_t C) { return heads_ok(K, C) ? 1 : 0; }
 
+int sgs_gat_heads_variant(int op, int64_t N, int64_t K, int64_t C, int aligned16) {
+    if (op == SGS_GAT_OP_ROW) C = 1;                          // the per-row family has no channel axis
+    if (!heads_ok(K, C) || N < 0) return -1;
+    const int vec = (C % 4 == 0 && aligned16) ? 4 : 1;
+    switch (op) {
+        case SGS_GAT_OP_SCORES_FWD: return heads_code(1, vec, min6(log2_ceil(cdiv(C, vec))), 0, 0);
+        case SGS_GAT_OP_SCORES_BWD: return heads_code(2, 1, 0, 0, gat_scores_rows_per_wg(N));
+        case SGS_GAT_OP_SPMM_CONCAT: return heads_code(3, vec, min6(log2_ceil(cdiv(K * C, vec))), 0, 0);
+        case SGS_GAT_OP_SPMM_MEAN: {
+            const int lg = min6(log2_ceil(cdiv(K * C, vec)));
+            if ((kT >> lg) * K * C <= kMeanLdsFloats) return heads_code(4, vec, lg, 0, 0);
+            return heads_code(5, vec, min6(log2_ceil(cdiv(C, vec))), 0, 0);      // rows of more than 1024 floats: lanes own output columns and walk the heads
+        }
+        case SGS_GAT_OP_SPMM_BROADCAST: return heads_code(6, vec, min6(log2_ceil(cdiv(K * C, vec))), 0, 0);
+        case SGS_GAT_OP_SDDMM:
+        case SGS_GAT_OP_SDDMM_BROADCAST: {
+            const int lgK = log2_ceil(K);
+            int lgG = log2_ceil(cdiv(C, vec));
+            if (lgG > 6 - lgK) lgG = 6 - lgK;
+            return heads_code(op == SGS_GAT_OP_SDDMM ? 7 : 8, vec, lgK + lgG, lgG, 0);
+        }
+        case SGS_GAT_OP_ROW: return heads_code(9, 1, 0, 0, 1 << log2_ceil(K));
+        default: return -1;
+    }
+}
+
 #define SGS_REQUIRE_HEADS(name)                                                                                         \
     SGS_REQUIRE(heads_ok(K, C), SGS_EINVAL, name ": unsupported heads = %lld x channels = %lld (1 <= heads <= 16, channels >= 1)", \
                 static_cast<long long>(K), static_cast<long long>(C))
@@ -1303,11 +1340,10 @@ int sgs_gat_scores_heads_fwd(const float* xl, int64_t N, int64_t K, int64_t C, c
     SGS_REQUIRE(N >= 0 && N * K * 64 < (int64_t(1) << 40), SGS_EINVAL, "sgs_gat_scores_heads_fwd: bad sizes");
     if (N == 0) return SGS_OK;
     SGS_REQUIRE(xl && att_src && att_dst && a_src && a_dst, SGS_EINVAL, "sgs_gat_scores_heads_fwd: null pointer");
-    const int vec = (C % 4 == 0 && al16(xl) && al16(att_src) && al16(att_dst)) ? 4 : 1;
-    int lg = log2_ceil(cdiv(C, vec));
-    if (lg > 6) lg = 6;
+    const HeadsChoice ch(sgs_gat_heads_variant(SGS_GAT_OP_SCORES_FWD, N, K, C, al16(xl) && al16(att_src) && al16(att_dst)));
+    const int lg = ch.lg;
     const dim3 grid(static_cast<unsigned>(cdiv((N * K) << lg, kT)));
-    if (vec == 4)
+    if (ch.vec == 4)
         hipLaunchKernelGGL((gat_scores_heads_fwd<4>), grid, dim3(kT), 0, stream, xl, N * K, static_cast<int>(K), C, att_src, att_dst, a_src, a_dst, lg);
     else
         hipLaunchKernelGGL((gat_scores_heads_fwd<1>), grid, dim3(kT), 0, stream, xl, N * K, static_cast<int>(K), C, att_src, att_dst, a_src, a_dst, lg);
@@ -1331,7 +1367,7 @@ int sgs_gat_scores_heads_bwd(const float* xl, int64_t N, int64_t K, int64_t C, c
     SGS_REQUIRE(xl && att_src && att_dst && g_src && g_dst && dxl && datt_src && datt_dst, SGS_EINVAL, "sgs_gat_scores_heads_bwd: null pointer");
     SGS_REQUIRE(ws && ws_bytes >= sgs_gat_scores_heads_bwd_workspace_bytes(N, K, C), SGS_EWORKSPACE, "sgs_gat_scores_heads_bwd: workspace too small");
     const int64_t D = K * C;
-    const int rp = gat_scores_rows_per_wg(N);
+    const int rp = HeadsChoice(sgs_gat_heads_variant(SGS_GAT_OP_SCORES_BWD, N, K, C, 0)).w;
     const int nwg = static_cast<int>((N + rp - 1) / rp);
     float* part = static_cast<float*>(ws);
     if (accumulate)
@@ -1355,8 +1391,8 @@ int sgs_gat_alpha_heads_fwd(const float* a_src, const float* a_dst, int64_t N, i
     if (N == 0) return SGS_OK;
     SGS_REQUIRE(a_src && a_dst && in_ptr && soft_loop && alpha_loop && (n_edges == 0 || (in_src && in_eid && soft && alpha)), SGS_EINVAL,
                 "sgs_gat_alpha_heads_fwd: null pointer");
-    SGS_DISPATCH_KP(gat_alpha_heads_fwd, K, dim3(static_cast<unsigned>(cdiv(N * 64, kT))), stream, a_src, a_dst, N, static_cast<int>(K), in_ptr, in_src,
-                    in_eid, negative_slope, 1.0f / (1.0f - p_drop), dropout_thresh(p_drop), p_drop > 0.f ? 1 : 0, seed, site, epoch_ptr(), soft,
+    SGS_DISPATCH_KPV(gat_alpha_heads_fwd, heads_kp(N, K), dim3(static_cast<unsigned>(cdiv(N * 64, kT))), stream, a_src, a_dst, N, static_cast<int>(K),
+                     in_ptr, in_src, in_eid, negative_slope, 1.0f / (1.0f - p_drop), dropout_thresh(p_drop), p_drop > 0.f ? 1 : 0, seed, site, epoch_ptr(), soft,
                     soft_loop, alpha, alpha_loop);
     SGS_LAUNCH_OK();
     return SGS_OK;
@@ -1374,8 +1410,8 @@ int sgs_gat_alpha_heads_bwd(const float* a_src, const float* a_dst, int64_t N, i
     SGS_REQUIRE(a_src && a_dst && in_ptr && soft_loop && gloop && g_selfloop && d_a_dst &&
                     (n_edges == 0 || (in_src && in_eid && soft && galpha && g_edge)),
                 SGS_EINVAL, "sgs_gat_alpha_heads_bwd: null pointer");
-    SGS_DISPATCH_KP(gat_alpha_heads_bwd, K, dim3(static_cast<unsigned>(cdiv(N * 64, kT))), stream, a_src, a_dst, N, static_cast<int>(K), in_ptr, in_src,
-                    in_eid, negative_slope, 1.0f / (1.0f - p_drop), dropout_thresh(p_drop), p_drop > 0.f ? 1 : 0, seed, site, epoch_ptr(), soft,
+    SGS_DISPATCH_KPV(gat_alpha_heads_bwd, heads_kp(N, K), dim3(static_cast<unsigned>(cdiv(N * 64, kT))), stream, a_src, a_dst, N, static_cast<int>(K),
+                     in_ptr, in_src, in_eid, negative_slope, 1.0f / (1.0f - p_drop), dropout_thresh(p_drop), p_drop > 0.f ? 1 : 0, seed, site, epoch_ptr(), soft,
                     soft_loop, galpha, gloop, g_edge, g_selfloop, d_a_dst);
     SGS_LAUNCH_OK();
     return SGS_OK;
@@ -1393,7 +1429,7 @@ int sgs_gat_alpha_heads_edge_fwd(const float* a_src, const float* a_dst, const f
     SGS_REQUIRE(a_src && a_dst && edge_coef && in_ptr && soft_loop && alpha_loop && loop_w && loop_inv_cnt &&
                     (n_edges == 0 || (edge_w && in_src && in_eid && soft && alpha)),
                 SGS_EINVAL, "sgs_gat_alpha_heads_edge_fwd: null pointer");
-    SGS_DISPATCH_KP(gat_alpha_heads_edge_fwd, K, dim3(static_cast<unsigned>(cdiv(N * 64, kT))), stream, a_src, a_dst, edge_w, edge_coef, N,
+    SGS_DISPATCH_KPV(gat_alpha_heads_edge_fwd, heads_kp(N, K), dim3(static_cast<unsigned>(cdiv(N * 64, kT))), stream, a_src, a_dst, edge_w, edge_coef, N,
                     static_cast<int>(K), in_ptr, in_src, in_eid, negative_slope, 1.0f / (1.0f - p_drop), dropout_thresh(p_drop), p_drop > 0.f ? 1 : 0,
                     seed, site, epoch_ptr(), soft, soft_loop, alpha, alpha_loop, loop_w, loop_inv_cnt);
     SGS_LAUNCH_OK();
@@ -1424,7 +1460,7 @@ int sgs_gat_alpha_heads_edge_bwd(const float* a_src, const float* a_dst, const f
                 "sgs_gat_alpha_heads_edge_bwd: workspace too small");
     const int nwg = static_cast<int>(cdiv(N * 64, kT));
     float* part = static_cast<float*>(ws);
-    SGS_DISPATCH_KP(gat_alpha_heads_edge_bwd, K, dim3(static_cast<unsigned>(nwg)), stream, a_src, a_dst, edge_w, edge_coef, loop_w, loop_inv_cnt, N,
+    SGS_DISPATCH_KPV(gat_alpha_heads_edge_bwd, heads_kp(N, K), dim3(static_cast<unsigned>(nwg)), stream, a_src, a_dst, edge_w, edge_coef, loop_w, loop_inv_cnt, N,
                     static_cast<int>(K), in_ptr, in_src, in_eid, negative_slope, 1.0f / (1.0f - p_drop), dropout_thresh(p_drop), p_drop > 0.f ? 1 : 0,
                     seed, site, epoch_ptr(), soft, soft_loop, galpha, gloop, dw_add, g_edge, g_selfloop, d_a_dst, d_edge_w, part);
     hipLaunchKernelGGL(gat_edge_dc_finish, dim3(1), dim3(1024), 0, stream, part, nwg, static_cast<int>(K), d_edge_coef);
@@ -1440,7 +1476,7 @@ int sgs_edge_sum_by_row_heads(const float* g_edge, const float* g_self, int64_t 
     SGS_REQUIRE(N >= 0 && nnz >= 0, SGS_EINVAL, "sgs_edge_sum_by_row_heads: bad sizes");
     if (N == 0) return SGS_OK;
     SGS_REQUIRE(ptr && out && (nnz == 0 || (g_edge && eid)), SGS_EINVAL, "sgs_edge_sum_by_row_heads: null pointer");
-    SGS_DISPATCH_KP(edge_sum_by_row_heads, K, dim3(static_cast<unsigned>(cdiv(N * 64, kT))), stream, g_edge, g_self, N, static_cast<int>(K), ptr, eid,
+    SGS_DISPATCH_KPV(edge_sum_by_row_heads, heads_kp(N, K), dim3(static_cast<unsigned>(cdiv(N * 64, kT))), stream, g_edge, g_self, N, static_cast<int>(K), ptr, eid,
                     out);
     SGS_LAUNCH_OK();
     return SGS_OK;
@@ -1456,18 +1492,14 @@ int sgs_spmm_csr_heads(const float* X, int64_t N, int64_t K, int64_t C, int64_t 
                 "sgs_spmm_csr_heads: bad activation / dropout");
     if (N == 0) return SGS_OK;
     SGS_REQUIRE(X && ptr && Y && X != Y && (nnz == 0 || (col && eid && val)), SGS_EINVAL, "sgs_spmm_csr_heads: null or aliased pointer");
-    const int vec = (C % 4 == 0 && al16(X) && al16(Y)) ? 4 : 1;
+    const int op = mode == SGS_HEADS_MEAN ? SGS_GAT_OP_SPMM_MEAN : (mode == SGS_HEADS_BROADCAST ? SGS_GAT_OP_SPMM_BROADCAST : SGS_GAT_OP_SPMM_CONCAT);
+    const HeadsChoice ch(sgs_gat_heads_variant(op, N, K, C, al16(X) && al16(Y)));
+    const int vec = ch.vec, lg = ch.lg;
+    const bool mean_lds = ch.kind == 4;
     const float scale = 1.0f / (1.0f - p_drop);
     const uint32_t th = dropout_thresh(p_drop);
     if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
     const int Ki = static_cast<int>(K);
-    int lg = log2_ceil(cdiv(K * C, vec));
-    if (lg > 6) lg = 6;
-    const bool mean_lds = mode == SGS_HEADS_MEAN && (kT >> lg) * K * C <= kMeanLdsFloats;
-    if (mode == SGS_HEADS_MEAN && !mean_lds) {               // rows of more than 1024 floats: lanes own output columns and walk the heads
-        lg = log2_ceil(cdiv(C, vec));
-        if (lg > 6) lg = 6;
-    }
     const dim3 grid(static_cast<unsigned>(cdiv(N, kT >> lg)));
 #define SGS_SPMM_HEADS_ARGS X, N, Ki, C, ptr, col, eid, val, diag, bias, act, scale, th, seed, site, epoch_ptr(), Y, lg
     if (mean_lds) {
@@ -1495,11 +1527,8 @@ int sgs_sddmm_csr_heads(const float* A, const float* B, int64_t N, int64_t K, in
     SGS_REQUIRE(N >= 0 && nnz >= 0, SGS_EINVAL, "sgs_sddmm_csr_heads: bad sizes");
     if (N == 0) return SGS_OK;
     SGS_REQUIRE(A && B && ptr && gdiag && (nnz == 0 || (col && eid && g)), SGS_EINVAL, "sgs_sddmm_csr_heads: null pointer");
-    const int vec = (C % 4 == 0 && al16(A) && al16(B)) ? 4 : 1;
-    const int lgK = log2_ceil(K);
-    int lgG = log2_ceil(cdiv(C, vec));
-    if (lgG > 6 - lgK) lgG = 6 - lgK;
-    const int lg = lgK + lgG;
+    const HeadsChoice ch(sgs_gat_heads_variant(broadcast ? SGS_GAT_OP_SDDMM_BROADCAST : SGS_GAT_OP_SDDMM, N, K, C, al16(A) && al16(B)));
+    const int vec = ch.vec, lg = ch.lg, lgG = ch.lgG;
     const int Ki = static_cast<int>(K);
     const dim3 grid(static_cast<unsigned>(cdiv(N, kT >> lg)));
 #define SGS_SDDMM_HEADS_ARGS A, B, N, Ki, C, ptr, col, eid, g, gdiag, lg, lgG
