@@ -793,7 +793,24 @@ int sgs_sddmm_csr_heads(const float* A, const float* B, int64_t N, int64_t K, in
  *   sgs_gatv2_dxl_heads (src-CSR): d_xl[j] (+)= sum over j's out-entries and loop of t, recomputed from g_logit / g_loop;
  *       accumulate != 0 adds onto d_xl's contents (the aggregation's d xl).
  * No float atomics, no host synchronisation: two identical launches give identical bits.
+ *
+ * sgs_gatv2_variant: which kernel instantiation and lane geometry an entry point launches, as a pure host function (the three launchers
+ * and sgs_gatv2_alpha_heads_bwd_workspace_bytes decode its result, so the two cannot drift).  op: SGS_GATV2_OP_* below; aligned16 != 0:
+ * every pointer the entry point accesses by vectors is 16-byte aligned (forward: xl, xr, att, and lin_edge with edge_w; backward: those
+ * and d_xr; dxl: those and d_xl).  -1: unsupported (K, C), N < 0 or unknown op.
+ *   code = kind * 1000000 + VEC * 100000 + lg * 10000 + lgG * 1000 + ONE * 100 + iters
+ *   kind  1 gatv2_alpha_heads_fwd   2^lg = KP 2^lgG lanes per row (KP = K rounded up to a power of two, 2^lgG <= 64 / KP lanes per head,
+ *                                   256 >> lg rows per workgroup), VEC floats per lane and chunk of 2^lgG VEC channels; ONE = 1: a head's
+ *                                   C channels fit one chunk (C <= VEC 2^lgG) and stay in registers; iters = 0
+ *         2 gatv2_alpha_heads_bwd   the same geometry; iters = row passes per workgroup = passes / 2048 clamped to 1 .. 16 with
+ *                                   passes = ceil(N / (256 >> lg)); ceil(passes / iters) workgroups (+ gatv2_param_finish)
+ *         3 gatv2_dxl_heads         2^lg lanes per row over the K C / VEC column groups; lgG = ONE = iters = 0
+ *   VEC = 4 needs C % 4 == 0 and the alignment; lg <= 6.
  * ---------------------------------------------------------------------------------- */
+#define SGS_GATV2_OP_ALPHA_FWD 0 /* sgs_gatv2_alpha_heads_fwd */
+#define SGS_GATV2_OP_ALPHA_BWD 1 /* sgs_gatv2_alpha_heads_bwd */
+#define SGS_GATV2_OP_DXL 2       /* sgs_gatv2_dxl_heads */
+int sgs_gatv2_variant(int op, int64_t N, int64_t K, int64_t C, int aligned16);
 int sgs_gatv2_alpha_heads_fwd(const float* xl, const float* xr, const float* att, const float* edge_w, const float* lin_edge, int64_t N,
                               int64_t K, int64_t C, int64_t n_edges, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid,
                               float negative_slope, float p_drop, uint64_t seed, uint32_t site, float* soft, float* soft_loop, float* alpha,

@@ -459,7 +459,6 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 struct Geom {
     int vec, lgG, lg, iters;
     bool one;
-    int64_t nwg;
 };
 inline Geom geom(int64_t N, int64_t K, int64_t C, int vec) {
     Geom g;
@@ -472,9 +471,19 @@ inline Geom geom(int64_t N, int64_t K, int64_t C, int vec) {
     const int64_t passes = cdiv(N > 0 ? N : 1, kT >> g.lg);
     int64_t it = passes / 2048;                               // about 2048 workgroups once there are rows enough
     g.iters = static_cast<int>(it < 1 ? 1 : (it > kMaxIters ? kMaxIters : it));
-    g.nwg = cdiv(passes, g.iters);
     return g;
 }
+
+// The launch choice of every entry point (sgs_gatv2_variant's code, see include/sgs_hip.h), taken apart again: the launchers and the
+// workspace query decode the query's result instead of deciding anything themselves.
+struct V2Choice {
+    int kind, vec, lg, lgG, iters;
+    bool one;
+    explicit V2Choice(int code)
+        : kind(code / 1000000), vec(code / 100000 % 10), lg(code / 10000 % 10), lgG(code / 1000 % 10), iters(code % 100), one(code / 100 % 10 != 0) {}
+    int64_t passes(int64_t N) const { return cdiv(N > 0 ? N : 1, kT >> lg); }            // row passes of kT >> lg rows each
+    int64_t nwg(int64_t N) const { return cdiv(passes(N), iters > 0 ? iters : 1); }     // workgroups of the backward
+};
 
 }  // namespace
 }  // namespace sgs
@@ -482,6 +491,18 @@ inline Geom geom(int64_t N, int64_t K, int64_t C, int vec) {
 using namespace sgs;
 
 extern "C" {
+
+int sgs_gatv2_variant(int op, int64_t N, int64_t K, int64_t C, int aligned16) {
+    if (op < SGS_GATV2_OP_ALPHA_FWD || op > SGS_GATV2_OP_DXL || N < 0 || !heads_ok(K, C)) return -1;
+    const int vec = (C % 4 == 0 && aligned16) ? 4 : 1;
+    if (op == SGS_GATV2_OP_DXL) {
+        int lg = log2_ceil(cdiv(K * C, vec));
+        if (lg > 6) lg = 6;
+        return 3000000 + vec * 100000 + lg * 10000;
+    }
+    const Geom g = geom(N, K, C, vec);
+    return (op + 1) * 1000000 + vec * 100000 + g.lg * 10000 + g.lgG * 1000 + (g.one ? 100 : 0) + (op == SGS_GATV2_OP_ALPHA_BWD ? g.iters : 0);
+}
 
 #define SGS_REQUIRE_HEADS(name)                                                                                         \
     SGS_REQUIRE(heads_ok(K, C), SGS_EINVAL, name ": unsupported heads = %lld x channels = %lld (1 <= heads <= 16, channels >= 1)", \
@@ -500,9 +521,9 @@ int sgs_gatv2_alpha_heads_fwd(const float* xl, const float* xr, const float* att
                 "sgs_gatv2_alpha_heads_fwd: null pointer");
     SGS_REQUIRE(!edge_w || (lin_edge && loop_w && loop_inv_cnt), SGS_EINVAL,
                 "sgs_gatv2_alpha_heads_fwd: null pointer (edge_w needs lin_edge, loop_w and loop_inv_cnt)");
-    const bool v4 = C % 4 == 0 && al16(xl) && al16(xr) && al16(att) && (!edge_w || al16(lin_edge));
-    const Geom g = geom(N, K, C, v4 ? 4 : 1);
-    const dim3 grid(static_cast<unsigned>(cdiv(N, kT >> g.lg)));
+    const V2Choice g(sgs_gatv2_variant(SGS_GATV2_OP_ALPHA_FWD, N, K, C, al16(xl) && al16(xr) && al16(att) && (!edge_w || al16(lin_edge))));
+    const bool v4 = g.vec == 4;
+    const dim3 grid(static_cast<unsigned>(g.passes(N)));
 #define SGS_V2_FWD_ARGS                                                                                                              \
     xl, xr, att, edge_w, lin_edge, N, static_cast<int>(K), C, in_ptr, in_src, in_eid, negative_slope, 1.0f / (1.0f - p_drop),       \
         dropout_thresh(p_drop), p_drop > 0.f ? 1 : 0, seed, site, epoch_ptr(), soft, soft_loop, alpha, alpha_loop, loop_w, loop_inv_cnt, g.lg, g.lgG
@@ -521,11 +542,10 @@ int sgs_gatv2_alpha_heads_fwd(const float* xl, const float* xr, const float* att
 size_t sgs_gatv2_alpha_heads_bwd_workspace_bytes(int64_t N, int64_t K, int64_t C) {
     if (N < 0) N = 0;
     if (!heads_ok(K, C)) return 256;
-    int64_t nwg = geom(N, K, C, 1).nwg;                       // the vector width is chosen from the pointers at launch: room for either
-    if (C % 4 == 0) {
-        const int64_t n4 = geom(N, K, C, 4).nwg;
-        if (n4 > nwg) nwg = n4;
-    }
+    // the vector width is chosen from the pointers at launch: room for either
+    int64_t nwg = V2Choice(sgs_gatv2_variant(SGS_GATV2_OP_ALPHA_BWD, N, K, C, 0)).nwg(N);
+    const int64_t n4 = V2Choice(sgs_gatv2_variant(SGS_GATV2_OP_ALPHA_BWD, N, K, C, 1)).nwg(N);
+    if (n4 > nwg) nwg = n4;
     return static_cast<size_t>(nwg) * 2 * static_cast<size_t>(K * C) * 4 + 256;
 }
 
@@ -547,9 +567,11 @@ int sgs_gatv2_alpha_heads_bwd(const float* xl, const float* xr, const float* att
                 "sgs_gatv2_alpha_heads_bwd: null pointer (edge_w needs lin_edge, loop_w, loop_inv_cnt, d_lin_edge and d_edge_w)");
     SGS_REQUIRE(ws && ws_bytes >= sgs_gatv2_alpha_heads_bwd_workspace_bytes(N, K, C), SGS_EWORKSPACE,
                 "sgs_gatv2_alpha_heads_bwd: workspace too small");
-    const bool v4 = C % 4 == 0 && al16(xl) && al16(xr) && al16(att) && al16(d_xr) && (!edge_w || al16(lin_edge));
-    const Geom g = geom(N, K, C, v4 ? 4 : 1);
-    const dim3 grid(static_cast<unsigned>(g.nwg));
+    const V2Choice g(sgs_gatv2_variant(SGS_GATV2_OP_ALPHA_BWD, N, K, C,
+                                       al16(xl) && al16(xr) && al16(att) && al16(d_xr) && (!edge_w || al16(lin_edge))));
+    const bool v4 = g.vec == 4;
+    const int64_t nwg = g.nwg(N);
+    const dim3 grid(static_cast<unsigned>(nwg));
     float* part = static_cast<float*>(ws);
 #define SGS_V2_BWD_ARGS                                                                                                              \
     xl, xr, att, edge_w, lin_edge, loop_w, loop_inv_cnt, N, static_cast<int>(K), C, in_ptr, in_src, in_eid, negative_slope,         \
@@ -564,7 +586,7 @@ int sgs_gatv2_alpha_heads_bwd(const float* xl, const float* xr, const float* att
     }
 #undef SGS_V2_BWD_ARGS
     const int64_t D = K * C;
-    hipLaunchKernelGGL(gatv2_param_finish, dim3(static_cast<unsigned>(cdiv(2 * D, 64))), dim3(1024), 0, stream, part, static_cast<int>(g.nwg), D,
+    hipLaunchKernelGGL(gatv2_param_finish, dim3(static_cast<unsigned>(cdiv(2 * D, 64))), dim3(1024), 0, stream, part, static_cast<int>(nwg), D,
                        d_att, edge_w ? d_lin_edge : nullptr);
     SGS_LAUNCH_OK();
     return SGS_OK;
@@ -581,10 +603,10 @@ int sgs_gatv2_dxl_heads(const float* xl, const float* xr, const float* att, cons
     SGS_REQUIRE(xl && xr && att && g_loop && out_ptr && d_xl && d_xl != xl && d_xl != xr && (nnz == 0 || (out_dst && out_eid && g_logit)),
                 SGS_EINVAL, "sgs_gatv2_dxl_heads: null or aliased pointer");
     SGS_REQUIRE(!edge_w || (lin_edge && loop_w), SGS_EINVAL, "sgs_gatv2_dxl_heads: null pointer (edge_w needs lin_edge and loop_w)");
-    const bool v4 = C % 4 == 0 && al16(xl) && al16(xr) && al16(att) && al16(d_xl) && (!edge_w || al16(lin_edge));
-    const int vec = v4 ? 4 : 1;
-    int lg = log2_ceil(cdiv(K * C, vec));
-    if (lg > 6) lg = 6;
+    const V2Choice ch(sgs_gatv2_variant(SGS_GATV2_OP_DXL, N, K, C,
+                                        al16(xl) && al16(xr) && al16(att) && al16(d_xl) && (!edge_w || al16(lin_edge))));
+    const bool v4 = ch.vec == 4;
+    const int lg = ch.lg;
     const dim3 grid(static_cast<unsigned>(cdiv(N, kT >> lg)));
     if (v4)
         hipLaunchKernelGGL((gatv2_dxl_heads<4>), grid, dim3(kT), 0, stream, xl, xr, att, edge_w, lin_edge, loop_w, g_logit, g_loop, N,
