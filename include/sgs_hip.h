@@ -639,6 +639,31 @@ int sgs_hybrid_loss_fwd(const float* logits, int64_t N, int64_t C, const int64_t
 int sgs_masked_ce_bwd_acc(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* row_lse,
                           const int32_t* n_rows, const float* grad_loss, float* dlogits, sgs_stream_t stream);
 
+/* The same two chains for criterion = nn.CrossEntropyLoss(weight = w, label_smoothing = eps) (reduction "mean", ignore_index -100):
+ * F.cross_entropy(logits[train], y[train], weight, label_smoothing).  weight[C] may be NULL (all ones); label_smoothing in [0, 1], 0 skips
+ * the smoothing reduction.  With W = sum_c w_c and lse_i = logsumexp_c x_ic:
+ *   row_i = (1 - eps) w[y_i] (lse_i - x_i[y_i]) + (eps / C) (W lse_i - sum_c w_c x_ic)   on train rows, 0 elsewhere  (rowloss[N])
+ *   den   = sum over train rows of w[y_i]                                                 (den[1], a float: the backward's divisor,
+ *                                                                                          in the place n_rows has in the plain chain)
+ *   loss  = sum_i row_i / den;  nan when den == 0 (torch forms the hard term's mean on its own: 0 / 0)
+ *   dlogits[i,c] = grad_loss / den [ (1 - eps) w[y_i] (softmax_ic - [c == y_i]) + (eps / C) (W softmax_ic - w_c) ] on train rows, 0 elsewhere;
+ *                  nan on every train row when den == 0 (as torch)
+ * den and W are formed on the device (den from weight, y and the mask in the finishing block; W per workgroup of the backward): no
+ * host read-back, no atomics, fixed summation orders.  sgs_masked_ce_w_bwd_acc ADDS to dlogits; sgs_hybrid_loss_w_fwd's out[0..4] are
+ * bitwise sgs_hybrid_loss_fwd's (same launches, same order), out[5] is the weighted cross entropy, out[6] = out[5] + out[4].
+ * Labels outside [0, C) on train rows are outside the contract (they count with weight 0 here). */
+int sgs_masked_ce_w_fwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
+                        float label_smoothing, float* loss, float* row_lse, float* rowloss, float* den, sgs_stream_t stream);
+int sgs_masked_ce_w_bwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
+                        float label_smoothing, const float* row_lse, const float* den, const float* grad_loss, float* dlogits,
+                        sgs_stream_t stream);
+int sgs_masked_ce_w_bwd_acc(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
+                            float label_smoothing, const float* row_lse, const float* den, const float* grad_loss, float* dlogits,
+                            sgs_stream_t stream);
+int sgs_hybrid_loss_w_fwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* w,
+                          const int64_t* sampled_edge_index, int64_t q, float coef1, float coef2, const float* weight, float label_smoothing,
+                          float* out, float* row_lse, float* rowloss, float* den, void* ws, size_t ws_bytes, sgs_stream_t stream);
+
 /* Edge-sharded losses: raw[4] = {sum bce, sum (w-cos)^2, #valid, sum labels} over THIS rank's sampled edges; the
  * ranks all-reduce raw, form reg1 / reg2 with the global q, and call sgs_edge_reg_bwd with out[2], out[3] = the
  * global #valid / label sum and q_global = the global number of sampled edges (q_global = q when unsharded). */

@@ -342,6 +342,141 @@ __global__ void __launch_bounds__(kT) ce_bwd_acc(const float* __restrict__ logit
     dlogits[idx] += (sm - (y[i] == c ? 1.f : 0.f)) * (grad_loss[0] / static_cast<float>(n_rows[0]));
 }
 
+// ---------------------------------------------------------------- class-weighted, label-smoothed masked cross entropy
+// F.cross_entropy(logits[mask], y[mask], weight = w, label_smoothing = eps, reduction = "mean"); w == nullptr: all ones.
+//   row_i = (1 - eps) w[y_i] (lse_i - x_i[y_i]) + (eps / C) sum_c w_c (lse_i - x_ic)        on train rows, 0 elsewhere
+//   den   = sum over train rows of w[y_i];   loss = sum_i row_i / den, nan when den == 0 (torch: the hard term's own 0 / 0)
+//   dx_ic = g / den [ (1 - eps) w[y_i] (softmax_ic - [c == y_i]) + (eps / C) (W softmax_ic - w_c) ],  W = sum_c w_c;  nan on train rows when den == 0
+// The smoothing sum is taken as sum_c w_c (lse - x_c) -- one wave reduction more than ce_rows -- and not as W lse - sum_c w_c x_c, which
+// needs two and W.  eps == 0 skips it.  A label outside [0, C) on a train row is outside the contract;
+// it reads nothing out of bounds here (weight 0, no label term).
+__device__ __forceinline__ float class_weight(const float* __restrict__ weight, int64_t yi, int64_t C) {
+    if (yi < 0 || yi >= C) return 0.f;
+    return weight ? weight[yi] : 1.f;
+}
+
+__global__ void __launch_bounds__(kT) ce_rows_w(const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
+                                               const uint8_t* __restrict__ mask, const float* __restrict__ weight, float eps,
+                                               float* __restrict__ row_lse, float* __restrict__ rowloss) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    if (i >= N) return;
+    if (!mask[i]) {
+        if (lane == 0) { rowloss[i] = 0.f; row_lse[i] = 0.f; }
+        return;
+    }
+    float mx = -INFINITY;
+    for (int64_t c = lane; c < C; c += 64) mx = fmaxf(mx, logits[i * C + c]);
+    mx = wave_max_all(mx);
+    float s = 0.f;
+    for (int64_t c = lane; c < C; c += 64) s += expf(logits[i * C + c] - mx);
+    s = wave_sum_all(s);
+    const float lse = mx + logf(s);
+    float sm = 0.f;
+    if (eps != 0.f) {
+        for (int64_t c = lane; c < C; c += 64) sm += (weight ? weight[c] : 1.f) * (lse - logits[i * C + c]);
+        sm = wave_sum_all(sm);
+    }
+    if (lane == 0) {
+        const int64_t yi = y[i];
+        const float wy = class_weight(weight, yi, C);
+        const float hard = (yi >= 0 && yi < C) ? wy * (lse - logits[i * C + yi]) : 0.f;
+        row_lse[i] = lse;
+        rowloss[i] = (eps != 0.f) ? (1.f - eps) * hard + (eps / static_cast<float>(C)) * sm : hard;
+    }
+}
+
+// One block: den[0] = sum of w[y_i] over the train rows (recomputed from w, y and the mask: no [N] buffer), loss = sum(rowloss) / den.
+__global__ void __launch_bounds__(1024) ce_final_w(const float* __restrict__ rowloss, const uint8_t* __restrict__ mask,
+                                                  const int64_t* __restrict__ y, const float* __restrict__ weight, int64_t N, int64_t C,
+                                                  float* __restrict__ loss, float* __restrict__ den) {
+    __shared__ float red[16];
+    float acc = 0.f, dn = 0.f;
+    for (int64_t i = threadIdx.x; i < N; i += 1024) {
+        acc += rowloss[i];
+        if (mask[i]) dn += class_weight(weight, y[i], C);
+    }
+    const float r = block_sum(acc, red);
+    const float d = block_sum(dn, red);
+    if (threadIdx.x == 0) {
+        den[0] = d;
+        loss[0] = (d == 0.f) ? NAN : r / d;
+    }
+}
+
+// W = sum_c w_c in every thread of the block, in a fixed order (the same value in every block).  All kT threads must call it.
+__device__ __forceinline__ float block_weight_sum(const float* __restrict__ weight, int64_t C, float* red) {
+    float v = 0.f;
+    for (int64_t c = threadIdx.x; c < C; c += kT) v += weight[c];
+    v = wave_sum_all(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float r = 0.f;
+#pragma unroll
+    for (int k = 0; k < kT / 64; ++k) r += red[k];
+    return r;
+}
+
+// One entry of the gradient above (a train row's); sc = g / den (nan when den == 0).
+__device__ __forceinline__ float ce_w_grad(float x, float lse, bool is_label, float wy, float wc, float W, float eps, float invC, float sc) {
+    const float sm = expf(x - lse);
+    const float hard = wy * (sm - (is_label ? 1.f : 0.f));
+    if (eps == 0.f) return hard * sc;
+    return ((1.f - eps) * hard + (eps * invC) * (W * sm - wc)) * sc;
+}
+
+template <bool kAcc>
+__global__ void __launch_bounds__(kT) ce_bwd_w(const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
+                                              const uint8_t* __restrict__ mask, const float* __restrict__ weight, float eps,
+                                              const float* __restrict__ row_lse, const float* __restrict__ den,
+                                              const float* __restrict__ grad_loss, float* __restrict__ dlogits) {
+    __shared__ float red[kT / 64];
+    float W = static_cast<float>(C);
+    if (eps != 0.f && weight) W = block_weight_sum(weight, C, red);          // (uniform branch: every thread of every block takes it or none)
+    const int64_t idx = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+    if (idx >= N * C) return;
+    const int64_t i = idx / C, c = idx - i * C;
+    if (!mask[i]) {
+        if (!kAcc) dlogits[idx] = 0.f;
+        return;
+    }
+    const float d = den[0];
+    const float sc = (d == 0.f) ? NAN : grad_loss[0] / d;
+    const int64_t yi = y[i];
+    const float g = ce_w_grad(logits[idx], row_lse[i], yi == c, class_weight(weight, yi, C), weight ? weight[c] : 1.f, W, eps,
+                              1.f / static_cast<float>(C), sc);
+    if (kAcc) dlogits[idx] += g;
+    else dlogits[idx] = g;
+}
+
+// hybrid_loss_final with the weighted mean: out[0..4] exactly as there (same partials, same order), out[5] = sum(rowloss) / den,
+// den[0] = sum of w[y_i] over the train rows.
+__global__ void __launch_bounds__(kT) hybrid_loss_final_w(const float* __restrict__ part, int64_t nblk, int64_t q, float coef1, float coef2,
+                                                         const float* __restrict__ rowloss, const uint8_t* __restrict__ mask,
+                                                         const int64_t* __restrict__ y, const float* __restrict__ weight, int64_t N, int64_t C,
+                                                         float* __restrict__ out, float* __restrict__ den) {
+    __shared__ float red[kT / 64];
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, ce = 0.f, dn = 0.f;
+    for (int64_t b = threadIdx.x; b < nblk; b += kT) {
+        a0 += part[4 * b]; a1 += part[4 * b + 1]; a2 += part[4 * b + 2]; a3 += part[4 * b + 3];
+    }
+    for (int64_t i = threadIdx.x; i < N; i += kT) {
+        ce += rowloss[i];
+        if (mask[i]) dn += class_weight(weight, y[i], C);
+    }
+    const float r0 = block_sum(a0, red), r1 = block_sum(a1, red), r2 = block_sum(a2, red), r3 = block_sum(a3, red);
+    const float rc = block_sum(ce, red), rd = block_sum(dn, red);
+    if (threadIdx.x == 0) {
+        const float reg1 = (r3 > 1.f) ? r0 / r2 : 0.f;
+        const float reg2 = r1 / static_cast<float>(q);
+        out[0] = reg1; out[1] = reg2; out[2] = r2; out[3] = r3;
+        out[4] = coef1 * reg1 + coef2 * reg2;
+        out[5] = (rd == 0.f) ? NAN : rc / rd;
+        out[6] = out[5] + out[4];
+        den[0] = rd;
+    }
+}
+
 // raw[0..3] = {sum bce, sum (w-cos)^2, #valid, sum labels} of this rank's edges (edge-sharded losses: the
 // ranks all-reduce these four sums and finish the formulas with the global q).
 __global__ void __launch_bounds__(kT) reg_raw_final(const float* __restrict__ part, int64_t nblk, float* __restrict__ raw) {
@@ -575,6 +710,70 @@ int sgs_masked_ce_bwd_acc(const float* logits, int64_t N, int64_t C, const int64
                 "sgs_masked_ce_bwd_acc: bad arguments");
     hipLaunchKernelGGL(ce_bwd_acc, dim3(cdiv(N * C, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, row_lse, n_rows, grad_loss,
                        dlogits);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_masked_ce_w_fwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
+                        float label_smoothing, float* loss, float* row_lse, float* rowloss, float* den, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(N > 0 && N < (int64_t(1) << 24) && C > 0 && logits && y && train_mask && loss && row_lse && rowloss, SGS_EINVAL,
+                "sgs_masked_ce_w_fwd: bad arguments");
+    SGS_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, SGS_EINVAL, "sgs_masked_ce_w_fwd: label_smoothing outside [0, 1]");
+    SGS_REQUIRE(den, SGS_EINVAL, "sgs_masked_ce_w_fwd: den is NULL");
+    hipLaunchKernelGGL(ce_rows_w, dim3(cdiv(N * 64, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, weight, label_smoothing, row_lse,
+                       rowloss);
+    hipLaunchKernelGGL(ce_final_w, dim3(1), dim3(1024), 0, stream, rowloss, train_mask, y, weight, N, C, loss, den);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_masked_ce_w_bwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
+                        float label_smoothing, const float* row_lse, const float* den, const float* grad_loss, float* dlogits,
+                        sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(N > 0 && C > 0 && logits && y && train_mask && row_lse && grad_loss && dlogits, SGS_EINVAL, "sgs_masked_ce_w_bwd: bad arguments");
+    SGS_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, SGS_EINVAL, "sgs_masked_ce_w_bwd: label_smoothing outside [0, 1]");
+    SGS_REQUIRE(den, SGS_EINVAL, "sgs_masked_ce_w_bwd: den is NULL");
+    hipLaunchKernelGGL(ce_bwd_w<false>, dim3(cdiv(N * C, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, weight, label_smoothing,
+                       row_lse, den, grad_loss, dlogits);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_masked_ce_w_bwd_acc(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
+                            float label_smoothing, const float* row_lse, const float* den, const float* grad_loss, float* dlogits,
+                            sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(N > 0 && C > 0 && logits && y && train_mask && row_lse && grad_loss && dlogits, SGS_EINVAL,
+                "sgs_masked_ce_w_bwd_acc: bad arguments");
+    SGS_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, SGS_EINVAL, "sgs_masked_ce_w_bwd_acc: label_smoothing outside [0, 1]");
+    SGS_REQUIRE(den, SGS_EINVAL, "sgs_masked_ce_w_bwd_acc: den is NULL");
+    hipLaunchKernelGGL(ce_bwd_w<true>, dim3(cdiv(N * C, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, weight, label_smoothing,
+                       row_lse, den, grad_loss, dlogits);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_hybrid_loss_w_fwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* w,
+                          const int64_t* sampled_edge_index, int64_t q, float coef1, float coef2, const float* weight, float label_smoothing,
+                          float* out, float* row_lse, float* rowloss, float* den, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(q > 0 && N > 0 && N < (int64_t(1) << 24) && C > 0 && logits && y && train_mask && w && sampled_edge_index && out && row_lse &&
+                    rowloss,
+                SGS_EINVAL, "sgs_hybrid_loss_w_fwd: bad arguments");
+    SGS_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, SGS_EINVAL, "sgs_hybrid_loss_w_fwd: label_smoothing outside [0, 1]");
+    SGS_REQUIRE(den, SGS_EINVAL, "sgs_hybrid_loss_w_fwd: den is NULL");
+    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_reg_workspace_bytes(q), SGS_EWORKSPACE, "sgs_hybrid_loss_w_fwd: workspace too small");
+    Carver cv(ws);
+    const int64_t nblk = cdiv(q, kRegEdges);
+    float* part = cv.take<float>(4 * (nblk + 1));
+    hipLaunchKernelGGL(ce_rows_w, dim3(cdiv(N * 64, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, weight, label_smoothing, row_lse,
+                       rowloss);
+    hipLaunchKernelGGL(reg_fwd_partial, dim3(nblk), dim3(kT), 0, stream, w, sampled_edge_index, q, logits, C, y, train_mask,
+                       static_cast<float*>(nullptr), part);
+    hipLaunchKernelGGL(hybrid_loss_final_w, dim3(1), dim3(kT), 0, stream, part, nblk, q, coef1, coef2, rowloss, train_mask, y, weight, N, C, out,
+                       den);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }

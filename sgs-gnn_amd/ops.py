@@ -1295,10 +1295,70 @@ class _MaskedCE(torch.autograd.Function):
         return d, None, None
 
 
-def masked_cross_entropy(logits, y, train_mask):
-    """nn.CrossEntropyLoss()(logits[train_mask], y[train_mask]) without the boolean-index sync."""
+def check_ce_spec(logits, weight, label_smoothing):
+    """The class weight and smoothing of a weighted cross entropy as the library takes them: (weight or None, eps).  `weight` must be an
+    fp32, contiguous tensor of length C on the logits' device; eps a number in [0, 1].  Raises ValueError naming the mismatch (before any
+    device work: the kernels read `weight` through its pointer)."""
+    eps = float(label_smoothing)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"sgs_gnn_amd: label_smoothing must lie in [0, 1], got {label_smoothing!r}")
+    if weight is None:
+        return None, eps
+    if not torch.is_tensor(weight):
+        raise ValueError(f"sgs_gnn_amd: class weight must be a tensor, got {type(weight).__name__}")
+    C = logits.shape[-1]
+    if weight.dtype != torch.float32:
+        raise ValueError(f"sgs_gnn_amd: class weight must be float32, got dtype {weight.dtype}")
+    if weight.dim() != 1 or weight.numel() != C:
+        raise ValueError(f"sgs_gnn_amd: class weight must have length C = {C}, got shape {tuple(weight.shape)}")
+    if weight.device != logits.device:
+        raise ValueError(f"sgs_gnn_amd: class weight is on device {weight.device}, the logits on {logits.device}")
+    if not weight.is_contiguous():
+        raise ValueError("sgs_gnn_amd: class weight must be contiguous")
+    return weight.detach(), eps
+
+
+class _MaskedCEW(torch.autograd.Function):
+    """_MaskedCE for nn.CrossEntropyLoss(weight=w, label_smoothing=eps): the same two launches forward and one backward; `den` (the sum of
+    the train rows' class weights, a device float) is the backward's divisor."""
+
+    @staticmethod
+    def forward(ctx, logits, y, mask_u8, weight, eps):
+        L = _lib.lib()
+        N, C = logits.shape
+        dev = logits.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        row_lse = torch.empty(N, dtype=torch.float32, device=dev)
+        rowloss = torch.empty(N, dtype=torch.float32, device=dev)
+        den = torch.empty(1, dtype=torch.float32, device=dev)
+        _lib.check(L.sgs_masked_ce_w_fwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(weight), eps, _ptr(loss), _ptr(row_lse), _ptr(rowloss),
+                                         _ptr(den), _stream()), "sgs_masked_ce_w_fwd")
+        ctx.save_for_backward(logits, y, mask_u8, weight, row_lse, den)
+        ctx.eps = eps
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        L = _lib.lib()
+        logits, y, mask_u8, weight, row_lse, den = ctx.saved_tensors
+        N, C = logits.shape
+        g = g.reshape(1).contiguous().float()
+        d = torch.empty_like(logits)
+        _lib.check(L.sgs_masked_ce_w_bwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(weight), ctx.eps, _ptr(row_lse), _ptr(den), _ptr(g),
+                                         _ptr(d), _stream()), "sgs_masked_ce_w_bwd")
+        return d, None, None, None, None
+
+
+def masked_cross_entropy(logits, y, train_mask, *, weight=None, label_smoothing=0.0):
+    """nn.CrossEntropyLoss(weight=weight, label_smoothing=label_smoothing)(logits[train_mask], y[train_mask]) without the boolean-index
+    sync.  With both keywords at their defaults: the plain chain (sgs_masked_ce_fwd / _bwd), otherwise the weighted one
+    (sgs_masked_ce_w_fwd / _w_bwd); `weight`: check_ce_spec."""
+    if weight is None and label_smoothing == 0.0:
+        _need_gpu(logits, y, train_mask)
+        return _MaskedCE.apply(logits.contiguous(), y.contiguous(), _u8(train_mask))
+    weight, eps = check_ce_spec(logits, weight, label_smoothing)
     _need_gpu(logits, y, train_mask)
-    return _MaskedCE.apply(logits.contiguous(), y.contiguous(), _u8(train_mask))
+    return _MaskedCEW.apply(logits.contiguous(), y.contiguous(), _u8(train_mask), weight, eps)
 
 
 class _EdgeReg(torch.autograd.Function):
@@ -1351,7 +1411,7 @@ class _HybridLoss(torch.autograd.Function):
     the same sum took ten, two of them the adds autograd inserts."""
 
     @staticmethod
-    def forward(ctx, logits, y, mask_u8, w, sei, graph, coef1, coef2, box):
+    def forward(ctx, logits, y, mask_u8, w, sei, graph, coef1, coef2, box, weight=None, eps=0.0):
         L = _lib.lib()
         q = w.numel()
         N, C = logits.shape
@@ -1359,11 +1419,19 @@ class _HybridLoss(torch.autograd.Function):
         out = torch.empty(7, dtype=torch.float32, device=dev)
         row_lse = torch.empty(N, dtype=torch.float32, device=dev)
         rowloss = torch.empty(N, dtype=torch.float32, device=dev)
-        n_rows = torch.empty(1, dtype=torch.int32, device=dev)
         ws = workspace(L.sgs_edge_reg_workspace_bytes(q), dev)
-        _lib.check(L.sgs_hybrid_loss_fwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(w), _ptr(sei), q, float(coef1), float(coef2), _ptr(out),
-                                         _ptr(row_lse), _ptr(rowloss), _ptr(n_rows), ws.data_ptr(), ws.numel(), _stream()), "sgs_hybrid_loss_fwd")
-        ctx.save_for_backward(logits, y, mask_u8, w, sei, out, row_lse, n_rows)
+        ctx.plain = weight is None and eps == 0.0
+        if ctx.plain:
+            n_rows = torch.empty(1, dtype=torch.int32, device=dev)
+            _lib.check(L.sgs_hybrid_loss_fwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(w), _ptr(sei), q, float(coef1), float(coef2), _ptr(out),
+                                             _ptr(row_lse), _ptr(rowloss), _ptr(n_rows), ws.data_ptr(), ws.numel(), _stream()), "sgs_hybrid_loss_fwd")
+        else:               # weighted / smoothed criterion: `n_rows` is `den`, a float word (the sum of the train rows' class weights)
+            n_rows = torch.empty(1, dtype=torch.float32, device=dev)
+            _lib.check(L.sgs_hybrid_loss_w_fwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(w), _ptr(sei), q, float(coef1), float(coef2),
+                                               _ptr(weight), eps, _ptr(out), _ptr(row_lse), _ptr(rowloss), _ptr(n_rows), ws.data_ptr(), ws.numel(),
+                                               _stream()), "sgs_hybrid_loss_w_fwd")
+        ctx.save_for_backward(logits, y, mask_u8, w, sei, out, row_lse, n_rows, weight)
+        ctx.eps = eps
         ctx.graph, ctx.coef1, ctx.coef2 = graph, float(coef1), float(coef2)
         ctx.nm_ref = getattr(w, "_sgs_norm", None)         # the normalisation that differentiates these weights, if any (note_first_dw)
         box.append(out)
@@ -1372,7 +1440,7 @@ class _HybridLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         L = _lib.lib()
-        logits, y, mask_u8, w, sei, out, row_lse, n_rows = ctx.saved_tensors
+        logits, y, mask_u8, w, sei, out, row_lse, n_rows, weight = ctx.saved_tensors
         q = w.numel()
         N, C = logits.shape
         dev = w.device
@@ -1382,29 +1450,36 @@ class _HybridLoss(torch.autograd.Function):
         Gd = torch.empty(q, C, dtype=torch.float32, device=dev)
         _lib.check(L.sgs_edge_reg_bwd(_ptr(w), _ptr(sei), q, q, _ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(out), ctx.coef1,
                                       ctx.coef2, _ptr(g), _ptr(dw), _ptr(Gs), _ptr(Gd), _stream()), "sgs_edge_reg_bwd")
-        if ctx.coef2 != 0.0:
-            dlogits = _endpoint_reduce(Gs, Gd, None, ctx.graph, 1.0, 1.0, C)
+        dlogits = _endpoint_reduce(Gs, Gd, None, ctx.graph, 1.0, 1.0, C) if ctx.coef2 != 0.0 else torch.empty_like(logits)
+        if not ctx.plain:
+            fn, what = (L.sgs_masked_ce_w_bwd_acc, "sgs_masked_ce_w_bwd_acc") if ctx.coef2 != 0.0 else (L.sgs_masked_ce_w_bwd, "sgs_masked_ce_w_bwd")
+            _lib.check(fn(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(weight), ctx.eps, _ptr(row_lse), _ptr(n_rows), _ptr(g), _ptr(dlogits),
+                          _stream()), what)
+        elif ctx.coef2 != 0.0:
             _lib.check(L.sgs_masked_ce_bwd_acc(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(row_lse), _ptr(n_rows), _ptr(g), _ptr(dlogits),
                                                _stream()), "sgs_masked_ce_bwd_acc")
         else:
-            dlogits = torch.empty_like(logits)
             _lib.check(L.sgs_masked_ce_bwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(row_lse), _ptr(n_rows), _ptr(g), _ptr(dlogits),
                                            _stream()), "sgs_masked_ce_bwd")
         nm = ctx.nm_ref() if ctx.nm_ref is not None else None
         if nm is not None and getattr(nm, "_park_ok", False) and dw.numel() == nm.graph.n_edges:
             import weakref
             nm._dw_first = weakref.ref(dw)                 # the normalisation's backward accumulates into dw in place (no autograd add)
-        return dlogits, None, None, dw, None, None, None, None, None
+        return dlogits, None, None, dw, None, None, None, None, None, None, None
 
 
-def hybrid_loss(logits, y, train_mask, w, sampled_edge_index, coef1, coef2):
-    """nn.CrossEntropyLoss()(logits[train], y[train]) + coef1 * reg1 + coef2 * reg2 (training_hybrid.py:105-133) as one scalar, plus
-    the detached [reg1, reg2, #valid, sum labels, coef1 reg1 + coef2 reg2, cross entropy, loss] vector."""
+def hybrid_loss(logits, y, train_mask, w, sampled_edge_index, coef1, coef2, *, weight=None, label_smoothing=0.0):
+    """nn.CrossEntropyLoss(weight=weight, label_smoothing=label_smoothing)(logits[train], y[train]) + coef1 * reg1 + coef2 * reg2
+    (training_hybrid.py:105-133) as one scalar, plus the detached [reg1, reg2, #valid, sum labels, coef1 reg1 + coef2 reg2, cross entropy,
+    loss] vector.  The regularisers never see the criterion; `weight`: check_ce_spec."""
+    eps = 0.0
+    if weight is not None or label_smoothing != 0.0:
+        weight, eps = check_ce_spec(logits, weight, label_smoothing)
     _need_gpu(w, logits, sampled_edge_index, y, train_mask)
     graph = get_graph(sampled_edge_index, logits.shape[0])
     box = []
     total = _HybridLoss.apply(logits.contiguous(), y.contiguous(), _u8(train_mask), w.contiguous(), sampled_edge_index.contiguous(), graph,
-                              float(coef1), float(coef2), box)
+                              float(coef1), float(coef2), box, weight, eps)
     return total, box[0]
 
 

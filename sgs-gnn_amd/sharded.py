@@ -392,6 +392,17 @@ class _ShardedEdgeReg(torch.autograd.Function):
         return dw, dlogits, None, None, None, None, None, None, None
 
 
+def _criterion_spec(criterion, where):
+    """(class weight or None, label smoothing) of a criterion the fused cross entropy evaluates (training._ce_spec); anything else is
+    refused by name: the sharded trainers have no "run as given" path (a block holds only some of the rows)."""
+    from .training import _ce_spec
+    spec = _ce_spec(criterion)
+    if spec is None:
+        raise NotImplementedError(f"{where}: criterion {criterion!r} is not built for the sharded trainers (they evaluate exactly "
+                                  "nn.CrossEntropyLoss with reduction='mean' and ignore_index=-100; any class weight and label smoothing)")
+    return spec
+
+
 def train_step_sharded(args, model, shard: EdgeShard, optimizer_gnn, optimizer_edge_prob, criterion, q: int, noise=None):
     """One hybrid step (training_hybrid.py:35-141, mode 'learned', E > q, EdgeProbGCN scorer) on an edge-sharded
     graph.  Dropout seeds / noise ticks are consumed in the same order as the single-GPU `train`, rows are
@@ -399,6 +410,7 @@ def train_step_sharded(args, model, shard: EdgeShard, optimizer_gnn, optimizer_e
     from .model import _DropoutClock
     from .sampling import _NoiseClock
     _no_cheb_order(model, "train_step_sharded")
+    ce_w, ce_eps = _criterion_spec(criterion, "train_step_sharded")
     noise = noise or {}
     model.train()
     optimizer_edge_prob.zero_grad()
@@ -447,7 +459,7 @@ def train_step_sharded(args, model, shard: EdgeShard, optimizer_gnn, optimizer_e
         counts = cbuf.tolist()
         update_edge_mlp = counts[0] > counts[2]                  # logits are replicated: every rank takes the same branch
     if update_edge_mlp:
-        loss = ops.masked_cross_entropy(learned_out, shard.y, shard.train_mask)
+        loss = ops.masked_cross_entropy(learned_out, shard.y, shard.train_mask, weight=ce_w, label_smoothing=ce_eps)
         c1 = args.regularizer1_coef if args.reg1 else 0.0
         c2 = args.consist_reg_coef if args.reg2 else 0.0
         if c1 != 0.0 or c2 != 0.0:
@@ -457,7 +469,7 @@ def train_step_sharded(args, model, shard: EdgeShard, optimizer_gnn, optimizer_e
         optimizer_edge_prob.step()
         optimizer_gnn.step()
     else:
-        loss = ops.masked_cross_entropy(random_out, shard.y, shard.train_mask)
+        loss = ops.masked_cross_entropy(random_out, shard.y, shard.train_mask, weight=ce_w, label_smoothing=ce_eps)
         loss.backward()
         optimizer_gnn.step()
     return dict(loss=loss.detach(), sample=smp, random=rs, update_edge_mlp=update_edge_mlp, learned_out=learned_out.detach(),
@@ -694,6 +706,42 @@ class _BlockCE(torch.autograd.Function):
         return d, None, None, None
 
 
+class _BlockCEW(torch.autograd.Function):
+    """_BlockCE for nn.CrossEntropyLoss(weight=w, label_smoothing=eps): this block's train-row losses / `den`, the class weights of the
+    WHOLE graph's train rows summed (labels and mask are replicated: every rank forms the same device float, no collective)."""
+
+    @staticmethod
+    def forward(ctx, logits_b, yb, mb_u8, den, weight, eps):
+        L = _lib.lib()
+        n, C = logits_b.shape
+        dev = logits_b.device
+        if n == 0:
+            ctx.empty, ctx.C = True, C
+            return torch.zeros((), dtype=torch.float32, device=dev)
+        ctx.empty = False
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        row_lse, rowloss = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+        den_b = torch.empty(1, dtype=torch.float32, device=dev)
+        _lib.check(L.sgs_masked_ce_w_fwd(ops._ptr(logits_b), n, C, ops._ptr(yb), ops._ptr(mb_u8), ops._ptr(weight), eps, ops._ptr(loss),
+                                         ops._ptr(row_lse), ops._ptr(rowloss), ops._ptr(den_b), ops._stream()), "sgs_masked_ce_w_fwd")
+        ctx.save_for_backward(logits_b, yb, mb_u8, row_lse, den, weight)
+        ctx.eps = eps
+        return torch.where(den[0] == 0, torch.full_like(den[0], float("nan")), rowloss.sum() / den[0])
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.empty:
+            return torch.zeros(0, ctx.C, dtype=torch.float32, device=g.device), None, None, None, None, None
+        L = _lib.lib()
+        logits_b, yb, mb_u8, row_lse, den, weight = ctx.saved_tensors
+        n, C = logits_b.shape
+        g = g.reshape(1).contiguous().float()
+        d = torch.empty_like(logits_b)
+        _lib.check(L.sgs_masked_ce_w_bwd(ops._ptr(logits_b), n, C, ops._ptr(yb), ops._ptr(mb_u8), ops._ptr(weight), ctx.eps, ops._ptr(row_lse),
+                                         ops._ptr(den), ops._ptr(g), ops._ptr(d), ops._stream()), "sgs_masked_ce_w_bwd")
+        return d, None, None, None, None, None
+
+
 class _ShardedNormBlock(torch.autograd.Function):
     """As _ShardedNorm, with the self-loop term owned (added and differentiated) by the rank that owns the node."""
 
@@ -760,6 +808,7 @@ def train_step_blocksharded(args, model, shard: EdgeShard, optimizer_gnn, optimi
     from .model import _DropoutClock
     from .sampling import _NoiseClock
     _no_cheb_order(model, "train_step_blocksharded")
+    ce_w, ce_eps = _criterion_spec(criterion, "train_step_blocksharded")
     noise = noise or {}
     model.train()
     optimizer_edge_prob.zero_grad()
@@ -812,7 +861,18 @@ def train_step_blocksharded(args, model, shard: EdgeShard, optimizer_gnn, optimi
 
     mb_u8 = ops._u8(mb)
 
+    ce_den = None
+    if ce_w is not None or ce_eps != 0.0:
+        ce_w, ce_eps = ops.check_ce_spec(out_b, ce_w, ce_eps)
+        if ce_w is None:
+            ce_den = B.n_train.to(torch.float32)
+        else:                                                               # (labels and mask are replicated: the same word on every rank)
+            wy = ce_w[shard.y.clamp(0, ce_w.numel() - 1)]
+            ce_den = torch.where(shard.train_mask, wy, torch.zeros_like(wy)).sum().reshape(1)
+
     def block_ce(logits_b):                                                 # the ranks' values sum to the replicated cross entropy
+        if ce_den is not None:
+            return _BlockCEW.apply(logits_b.contiguous(), yb, mb_u8, ce_den, ce_w, ce_eps)
         return _BlockCE.apply(logits_b.contiguous(), yb, mb_u8, B.n_train)
 
     learned_out, reg = None, None

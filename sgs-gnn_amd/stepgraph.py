@@ -207,7 +207,16 @@ class StepGraphs:
         return (self.pipeline, bool(a.conditional), bool(a.sparse_edge_mlp), a.reg1 == True, a.reg2 == True,   # noqa: E712
                 float(a.regularizer1_coef), float(a.consist_reg_coef), float(a.degree_bias_coef), int(self.q),
                 bool(self.use_checkpoint), tuple(p.data_ptr() for p in self.params), _opt_signature(self.optimizers),
-                ops.check_precision(getattr(a, "sgs_precision", None)))
+                ops.check_precision(getattr(a, "sgs_precision", None)), self._criterion_key())
+
+    def _criterion_key(self):
+        """What a capture bakes in of the criterion: the class weight's ADDRESS (the kernels read the weight through it at every replay, so
+        an in-place update of the same tensor needs no re-capture) and the smoothing, a launch argument."""
+        from .training import _ce_spec
+        spec = _ce_spec(self.criterion)
+        if spec is None:
+            return "as given"
+        return (None if spec[0] is None else spec[0].data_ptr(), spec[1])
 
     @classmethod
     def attach(cls, model, pipeline, args, criterion, q, use_checkpoint, optimizers=None, sync=None, loader=None):

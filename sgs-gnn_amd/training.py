@@ -31,9 +31,22 @@ def _fused_ce_ok(criterion) -> bool:
             and criterion.ignore_index == -100 and getattr(criterion, "label_smoothing", 0.0) == 0.0)
 
 
+def _ce_spec(criterion):
+    """(weight, label_smoothing) when `criterion` is a cross entropy the fused loss chain evaluates -- exactly nn.CrossEntropyLoss (no
+    subclass) with reduction "mean" and ignore_index -100; any class weight (or none), any smoothing in [0, 1] -- and None for every other
+    criterion, which is run as given."""
+    if type(criterion) is not nn.CrossEntropyLoss or criterion.reduction != "mean" or criterion.ignore_index != -100:
+        return None
+    eps = float(getattr(criterion, "label_smoothing", 0.0))
+    if not 0.0 <= eps <= 1.0:
+        return None
+    return criterion.weight, eps
+
+
 def _ce(criterion, out, batch):
-    if _fused_ce_ok(criterion):
-        return ops.masked_cross_entropy(out, batch.y, batch.train_mask)
+    spec = _ce_spec(criterion)
+    if spec is not None:
+        return ops.masked_cross_entropy(out, batch.y, batch.train_mask, weight=spec[0], label_smoothing=spec[1])
     return criterion(out[batch.train_mask], batch.y[batch.train_mask])      # user-supplied criterion: run as given
 
 
@@ -146,9 +159,11 @@ def learned_loss(args, criterion, st: SampledForward, batch):
     """training_hybrid.py:105-133: CE + reg1 (BCE on same-class labels) + reg2 (cosine consistency)."""
     c1 = args.regularizer1_coef if args.reg1 == True else 0.0      # noqa: E712 (as the reference)
     c2 = args.consist_reg_coef if args.reg2 == True else 0.0       # noqa: E712
-    if (c1 != 0.0 or c2 != 0.0) and _fused_ce_ok(criterion):
+    spec = _ce_spec(criterion)
+    if (c1 != 0.0 or c2 != 0.0) and spec is not None:
         # the three terms as one autograd node (ten launches -> six)
-        return ops.hybrid_loss(st.learned_out, batch.y, batch.train_mask, st.edge_probs_for_loss, st.sampled_edge_index, c1, c2)[0]
+        return ops.hybrid_loss(st.learned_out, batch.y, batch.train_mask, st.edge_probs_for_loss, st.sampled_edge_index, c1, c2,
+                               weight=spec[0], label_smoothing=spec[1])[0]
     loss = _ce(criterion, st.learned_out, batch)
     if c1 != 0.0 or c2 != 0.0:
         reg, _ = ops.edge_regularizers(st.edge_probs_for_loss, st.learned_out, st.sampled_edge_index, batch.y,
@@ -251,7 +266,7 @@ def _train_in(pipeline, args, epoch, max_epoch, model, optimizer_gnn, optimizer_
         if sync is None:
             sync = model._sgs_gradsync = GradSync(model.parameters())
     graphs = None
-    if getattr(args, "sgs_hipgraph", False) and mode == 'learned' and not noise and trace is None and _fused_ce_ok(criterion):
+    if getattr(args, "sgs_hipgraph", False) and mode == 'learned' and not noise and trace is None and _ce_spec(criterion) is not None:
         from .stepgraph import StepGraphs               # opt-in: replay captured HIP graphs of each partition's step
         graphs = StepGraphs.attach(model, pipeline, args, criterion, q, use_checkpoint,
                                    optimizers=(optimizer_edge_prob, optimizer_gnn), sync=sync, loader=cluster_loader)
