@@ -120,6 +120,45 @@ int sgs_sample_topq(int mode, const float* p, const float* prior, double degree_
                     int64_t* sampled_edge_index, float* sampled_p, float* stats, float* keys_out,
                     void* ws, size_t ws_bytes, sgs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * sgs_sample_topq_cover: the same draw under the NODE-COVERING rule (opt-in; sgs_sample_topq itself is unchanged).  The rule alters WHICH
+ * edges are drawn, not how a drawn edge is weighted or differentiated (sgs_st_weights_fwd / _bwd take the selected ids as they are).
+ *
+ *   key_e    = the fp32 key of sgs_sample_topq, bit for bit (every mode, explicit or in-register noise);
+ *   forced   : for every node i, the candidate edge with dst == i and src != i that has the largest key, ties to the lowest edge id
+ *              (a node without such an edge has none; self-loops never count).  M = number of forced edges;
+ *   boosted  = float_as_uint(key_e), bit 31 set when e is forced (keys >= 0, so the bit is free);
+ *   selected = the q largest boosted keys, ties to the lowest edge id; compaction in original edge order.
+ *
+ * Hence exactly q edges are selected; M <= q: every node with a non-loop in-edge keeps its best one and the other q - M edges are the
+ * q - M largest keys of the rest; M > q: the q largest-keyed forced edges; M == 0: the plain draw.  q == 0 / q == E select nothing /
+ * everything as sgs_sample_topq does (no keys are computed then; cover_info is still written).  E == 0 returns at once and writes
+ * nothing.
+ *
+ * in_ptr [N + 1] / in_src / in_eid [E]: the destination-row CSR of the candidate graph as sgs_graph_build emits it.  Outputs as
+ * sgs_sample_topq, with: stats[2] = the threshold key with the flag bit cleared, stats[3] = the number of ties taken at the BOOSTED
+ * threshold, keys_out = the unboosted keys (bitwise the plain call's), cover_info[2] (int32, may be NULL) = {M, number of forced
+ * edges selected = min(M, q)}.
+ *
+ * Launches: the plain draw's, plus one kernel after the key pass (per row: gather the keys of the row's entries, 64-bit max of
+ * (key bits << 32 | ~edge id), set bit 31 of the winner, move its count in the top-digit histogram from bin b to bin b + 1024 --
+ * integer atomics, aggregated per workgroup first) and one finishing workgroup (M, the reported threshold).  All counting is integer:
+ * the draw is run-to-run and launch-geometry invariant.  sgs_sample_topq_cover_variant(N, E) -> lanes that share one row in that
+ * kernel: 4 (E < 8 N), 16 (E < 64 N) or 64; a row of more than 32 entries per lane (128 / 512 / 2048) is taken by the whole
+ * 256-thread workgroup instead.  A pure host function.
+ *
+ * Capturable as sgs_sample_topq is (no allocation, synchronisation or read-back) and honours sgs_dyn_edges_set with the same capacity
+ * semantics: the caller guarantees that in_ptr describes the LIVE edges, rows past the live nodes being empty (pointers padded with
+ * the live E, as sgs_stage_segments pads them).  E < 2^31 and N < 2^31 (int32 CSR).
+ * ---------------------------------------------------------------------------------- */
+size_t sgs_sample_topq_cover_workspace_bytes(int64_t E, int64_t N);
+int sgs_sample_topq_cover_variant(int64_t N, int64_t E);
+int sgs_sample_topq_cover(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise,
+                          uint64_t seed, uint64_t stream_id, int64_t E, int64_t q, const int64_t* edge_index,
+                          int64_t N, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid,
+                          uint8_t* mask, int64_t* sampled_eid, int64_t* sampled_edge_index, float* sampled_p,
+                          float* stats, float* keys_out, int32_t* cover_info, void* ws, size_t ws_bytes, sgs_stream_t stream);
+
 int sgs_gather_columns(const int64_t* edge_index, int64_t E, const int64_t* idx, int64_t q, int64_t* out, sgs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------

@@ -716,6 +716,134 @@ __global__ void __launch_bounds__(kThreads) small_compact(const uint32_t* __rest
     small_compact_body(keys, E, q, st, cnt, p, edge_index, mask, mask_aligned, sampled_eid, sei, sampled_p, dynE);
 }
 
+// ---------------------------------------------------------------- node-covering draws (sgs_sample_topq_cover)
+// After the key pass: every node's best non-loop in-edge (largest key, ties to the lowest edge id) gets bit 31 of its key set
+// (keys >= 0, so the bit is free and the top radix digit already spans it); the radix select, count and compaction then run
+// over the boosted keys unchanged.  The rows of the destination CSR partition the edges, so a row reads and writes only its
+// own keys: no ordering between rows is needed.  LPR lanes share a row (sgs_sample_topq_cover_variant: 4 / 16 / 64 from the
+// mean in-degree); a row of more than kCoverLongPerLane entries per lane (128 / 512 / 2048) is handed to the whole workgroup
+// instead, so neither a 20 000-entry row serialises behind four lanes nor 64 lanes idle on degree-3 rows.  The digit-0 histogram the key pass accumulated is
+// corrected by MOVING one count per forced edge from bin b to bin b + 1024 (integer atomics, first aggregated per workgroup
+// in LDS): all counting stays integer, so the draw does not depend on the launch geometry or on the order of the atomics.
+constexpr int kCoverThreads = 256;
+constexpr int kCoverGrid = 1024;       // workgroups at most (grid-stride over the rows); also the length of the per-workgroup counts
+constexpr int kCoverLongPerLane = 32;  // entries per lane of a row's group above which the whole workgroup takes the row
+
+// (key bits << 32 | ~edge id) of CSR entry j of `row`, 0 for a self-loop: a 64-bit max is "largest key, then lowest edge id".
+// keys == nullptr (degenerate draws, M only): any non-loop entry counts.
+__device__ __forceinline__ unsigned long long cover_cand(const uint32_t* __restrict__ keys, uint32_t E, const int32_t* __restrict__ in_src,
+                                                         const int32_t* __restrict__ in_eid, int64_t j, int64_t row) {
+    const uint32_t eid = static_cast<uint32_t>(in_eid[j]);
+    if (static_cast<int64_t>(in_src[j]) == row || eid >= E) return 0ull;
+    const uint32_t bits = keys ? keys[eid] : 0u;
+    return (static_cast<unsigned long long>(bits) << 32) | static_cast<uint32_t>(~eid);      // ~eid != 0: eid < E <= 2^31 - 1
+}
+__device__ __forceinline__ void cover_boost(unsigned long long best, uint32_t* __restrict__ keys, uint32_t* moved, uint32_t* nforced) {
+    const uint32_t eid = ~static_cast<uint32_t>(best), bits = static_cast<uint32_t>(best >> 32);
+    if (keys) {
+        keys[eid] = bits | 0x80000000u;
+        atomicAdd(&moved[(bits >> kShift0) & (kBins / 2 - 1)], 1u);
+    }
+    atomicAdd(nforced, 1u);
+}
+template <int LPR>
+__global__ void __launch_bounds__(kCoverThreads) cover_rows(uint32_t* __restrict__ keys, int64_t E, int64_t N, const int32_t* __restrict__ in_ptr,
+                                                           const int32_t* __restrict__ in_src, const int32_t* __restrict__ in_eid,
+                                                           uint32_t* __restrict__ hist0, uint32_t* __restrict__ mcnt,
+                                                           const int64_t* __restrict__ dynE) {
+    constexpr int RPB = kCoverThreads / LPR;          // rows per workgroup and sweep
+    constexpr int kLong = kCoverLongPerLane * LPR;    // a group walks at most 32 dependent gathers per lane
+    __shared__ uint32_t moved[kBins / 2];             // forced keys per (unboosted) top digit
+    __shared__ uint32_t longrow[RPB];
+    __shared__ uint32_t nlong, nforced;
+    __shared__ unsigned long long wbest[kCoverThreads / 64];
+    if (dynE) {
+        const int64_t live = *dynE;                   // rows past the live nodes are empty: their pointers are padded with the live E
+        if (live < E) E = live;
+    }
+    for (int i = threadIdx.x; i < kBins / 2; i += kCoverThreads) moved[i] = 0;
+    if (threadIdx.x == 0) { nlong = 0; nforced = 0; }
+    __syncthreads();
+    const uint32_t E32 = static_cast<uint32_t>(E);
+    const int sub = threadIdx.x % LPR, grp = threadIdx.x / LPR;
+    for (int64_t base = static_cast<int64_t>(blockIdx.x) * RPB; base < N; base += static_cast<int64_t>(gridDim.x) * RPB) {
+        const int64_t row = base + grp;
+        unsigned long long best = 0ull;
+        if (row < N) {
+            int64_t s = in_ptr[row], t = in_ptr[row + 1];
+            if (s < 0) s = 0;
+            if (t > E) t = E;
+            if (t - s > kLong) {
+                if (sub == 0) longrow[atomicAdd(&nlong, 1u)] = static_cast<uint32_t>(row);
+            } else {
+                for (int64_t j = s + sub; j < t; j += LPR) {
+                    const unsigned long long c = cover_cand(keys, E32, in_src, in_eid, j, row);
+                    best = c > best ? c : best;
+                }
+            }
+        }
+#pragma unroll
+        for (int o = LPR / 2; o > 0; o >>= 1) {
+            const unsigned long long c = __shfl_xor(best, o, 64);
+            best = c > best ? c : best;
+        }
+        if (sub == 0 && best) cover_boost(best, keys, moved, &nforced);
+        __syncthreads();
+        const uint32_t nl = nlong;
+        for (uint32_t l = 0; l < nl; ++l) {           // (uniform: every thread reads the same nlong)
+            const int64_t lrow = longrow[l];
+            int64_t s = in_ptr[lrow], t = in_ptr[lrow + 1];
+            if (s < 0) s = 0;
+            if (t > E) t = E;
+            unsigned long long b = 0ull;
+            for (int64_t j = s + threadIdx.x; j < t; j += kCoverThreads) {
+                const unsigned long long c = cover_cand(keys, E32, in_src, in_eid, j, lrow);
+                b = c > b ? c : b;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long c = __shfl_xor(b, o, 64);
+                b = c > b ? c : b;
+            }
+            if ((threadIdx.x & 63) == 0) wbest[threadIdx.x >> 6] = b;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                for (int w = 1; w < kCoverThreads / 64; ++w) b = wbest[w] > b ? wbest[w] : b;
+                if (b) cover_boost(b, keys, moved, &nforced);
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) nlong = 0;
+        __syncthreads();
+    }
+    if (hist0)
+        for (int i = threadIdx.x; i < kBins / 2; i += kCoverThreads) {
+            const uint32_t v = moved[i];
+            if (v) { atomicSub(&hist0[i], v); atomicAdd(&hist0[i + kBins / 2], v); }
+        }
+    if (threadIdx.x == 0) mcnt[blockIdx.x] = nforced;
+}
+
+// One workgroup, last launch of a covering draw: M from the per-workgroup counts, the flag bit off the reported threshold.
+__global__ void __launch_bounds__(kThreads) cover_finish(const uint32_t* __restrict__ mcnt, int nb, int64_t q, float* __restrict__ stats,
+                                                        int32_t* __restrict__ cover_info) {
+    __shared__ int red[kThreads / 64];
+    int m = 0;
+    for (int i = threadIdx.x; i < nb; i += kThreads) m += static_cast<int>(mcnt[i]);
+    m = wave_sum_int_all(m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int M = 0;
+        for (int w = 0; w < kThreads / 64; ++w) M += red[w];
+        if (cover_info) {
+            cover_info[0] = M;
+            cover_info[1] = static_cast<int64_t>(M) < q ? M : static_cast<int32_t>(q);
+        }
+        if (stats) stats[2] = __uint_as_float(__float_as_uint(stats[2]) & 0x7FFFFFFFu);
+    }
+}
+
 // counts[0] = #keys > threshold, counts[1] = #keys == threshold in this shard (before the scan).
 __global__ void __launch_bounds__(kThreads) total_counts(const uint2* __restrict__ cnt, int64_t nblk, uint32_t* __restrict__ counts) {
     __shared__ int red[2 * (kThreads / 64)];
@@ -1077,23 +1205,59 @@ size_t sgs_sample_topq_workspace_bytes(int64_t E) {
            + carve_bytes(nblk, 4) + carve_bytes(3 * kBins, 4) + 256 + 256;   // fused small-E path: second partials, per-digit histograms
 }
 
-int sgs_sample_topq(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise,
-                    uint64_t seed, uint64_t stream_id, int64_t E, int64_t q, const int64_t* edge_index,
-                    uint8_t* mask, int64_t* sampled_eid, int64_t* sampled_edge_index, float* sampled_p, float* stats,
-                    float* keys_out, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+size_t sgs_sample_topq_cover_workspace_bytes(int64_t E, int64_t N) {
+    (void)N;       // the forced-edge kernel's per-workgroup counts have a fixed length (its grid is capped at kCoverGrid)
+    return sgs_sample_topq_workspace_bytes(E) + carve_bytes(kCoverGrid, 4);
+}
+
+int sgs_sample_topq_cover_variant(int64_t N, int64_t E) {
+    if (N <= 0 || E < 8 * N) return 4;
+    return E < 64 * N ? 16 : 64;
+}
+
+// what a covering draw adds to the plain one (sgs_sample_topq_cover); nullptr = the plain draw
+struct CoverArgs {
+    int64_t N;
+    const int32_t *in_ptr, *in_src, *in_eid;
+    int32_t* info;
+    int lanes, grid;      // sgs_sample_topq_cover_variant of the shape; workgroups of cover_rows
+};
+// keys == nullptr: count M only (degenerate draws); hist0 == nullptr: no histogram to correct
+static void launch_cover_rows(const CoverArgs& c, uint32_t* keys, int64_t E, uint32_t* hist0, uint32_t* mcnt, const int64_t* dynE,
+                              hipStream_t stream) {
+    const dim3 grid(static_cast<unsigned>(c.grid)), blk(kCoverThreads);
+    if (c.lanes == 4)
+        hipLaunchKernelGGL(cover_rows<4>, grid, blk, 0, stream, keys, E, c.N, c.in_ptr, c.in_src, c.in_eid, hist0, mcnt, dynE);
+    else if (c.lanes == 16)
+        hipLaunchKernelGGL(cover_rows<16>, grid, blk, 0, stream, keys, E, c.N, c.in_ptr, c.in_src, c.in_eid, hist0, mcnt, dynE);
+    else
+        hipLaunchKernelGGL(cover_rows<64>, grid, blk, 0, stream, keys, E, c.N, c.in_ptr, c.in_src, c.in_eid, hist0, mcnt, dynE);
+}
+
+static int sample_topq_impl(const char* fn, const CoverArgs* cover, int mode, const float* p, const float* prior, double degree_bias_coef,
+                            const float* noise, uint64_t seed, uint64_t stream_id, int64_t E, int64_t q, const int64_t* edge_index,
+                            uint8_t* mask, int64_t* sampled_eid, int64_t* sampled_edge_index, float* sampled_p, float* stats,
+                            float* keys_out, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(mode == SGS_SAMPLE_LEARNED || mode == SGS_SAMPLE_PRIOR, SGS_EINVAL, "sgs_sample_topq: bad mode %d", mode);
-    SGS_REQUIRE(E >= 0 && q >= 0, SGS_EINVAL, "sgs_sample_topq: negative size (E=%lld q=%lld)", (long long)E, (long long)q);
+    SGS_REQUIRE(mode == SGS_SAMPLE_LEARNED || mode == SGS_SAMPLE_PRIOR, SGS_EINVAL, "%s: bad mode %d", fn, mode);
+    SGS_REQUIRE(E >= 0 && q >= 0, SGS_EINVAL, "%s: negative size (E=%lld q=%lld)", fn, (long long)E, (long long)q);
     SGS_REQUIRE(q <= E, SGS_EINVAL,
-                "sgs_sample_topq: cannot sample q=%lld > E=%lld edges without replacement", (long long)q, (long long)E);
-    SGS_REQUIRE(E < (int64_t(1) << 32), SGS_EINVAL, "sgs_sample_topq: E=%lld exceeds 2^32-1", (long long)E);
+                "%s: cannot sample q=%lld > E=%lld edges without replacement", fn, (long long)q, (long long)E);
+    SGS_REQUIRE(E < (int64_t(1) << 32), SGS_EINVAL, "%s: E=%lld exceeds 2^32-1", fn, (long long)E);
+    if (cover) {
+        SGS_REQUIRE(cover->N >= 0, SGS_EINVAL, "%s: negative node count (N=%lld)", fn, (long long)cover->N);
+        SGS_REQUIRE(E == 0 || (cover->in_ptr && cover->in_src && cover->in_eid), SGS_EINVAL,
+                    "%s: null destination CSR (in_ptr / in_src / in_eid) with E=%lld", fn, (long long)E);
+        SGS_REQUIRE(E < (int64_t(1) << 31) && cover->N < (int64_t(1) << 31), SGS_EINVAL,
+                    "%s: E=%lld, N=%lld exceed the int32 CSR", fn, (long long)E, (long long)cover->N);
+    }
     if (E == 0) return SGS_OK;
-    SGS_REQUIRE(mask, SGS_EINVAL, "sgs_sample_topq: null mask");
-    SGS_REQUIRE(p || (mode == SGS_SAMPLE_LEARNED && !prior), SGS_EINVAL, "sgs_sample_topq: p == NULL (uniform weights) needs mode LEARNED and no prior");
-    SGS_REQUIRE(!sampled_edge_index || edge_index, SGS_EINVAL, "sgs_sample_topq: edge_index required for sampled_edge_index");
-    SGS_REQUIRE(ws && ws_bytes >= sgs_sample_topq_workspace_bytes(E), SGS_EWORKSPACE,
-                "sgs_sample_topq: workspace too small (%zu < %zu)", ws_bytes, sgs_sample_topq_workspace_bytes(E));
-    SGS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, SGS_EINVAL, "sgs_sample_topq: workspace must be 256-B aligned");
+    SGS_REQUIRE(mask, SGS_EINVAL, "%s: null mask", fn);
+    SGS_REQUIRE(p || (mode == SGS_SAMPLE_LEARNED && !prior), SGS_EINVAL, "%s: p == NULL (uniform weights) needs mode LEARNED and no prior", fn);
+    SGS_REQUIRE(!sampled_edge_index || edge_index, SGS_EINVAL, "%s: edge_index required for sampled_edge_index", fn);
+    const size_t ws_need = cover ? sgs_sample_topq_cover_workspace_bytes(E, cover->N) : sgs_sample_topq_workspace_bytes(E);
+    SGS_REQUIRE(ws && ws_bytes >= ws_need, SGS_EWORKSPACE, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, ws_need);
+    SGS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, SGS_EINVAL, "%s: workspace must be 256-B aligned", fn);
 
     const int64_t nblk = cdiv(E, kChunk);
     Carver cv(ws);
@@ -1107,6 +1271,7 @@ int sgs_sample_topq(int mode, const float* p, const float* prior, double degree_
     float* part2 = cv.take<float>(nblk + 1);
     uint32_t* hist3 = cv.take<uint32_t>(3 * kBins);       // fused small-E path: one histogram per digit
     SelPart* sel = cv.take<SelPart>(2);
+    uint32_t* mcnt = cover ? cv.take<uint32_t>(kCoverGrid) : nullptr;      // covering draws: forced edges per workgroup of cover_rows
     const dim3 grid(static_cast<unsigned>(nblk)), blk(kThreads);
     const dim3 hgrid(static_cast<unsigned>(nblk < kHistGrid ? nblk : kHistGrid));
     // python: (1 - c) and c are doubles, cast to fp32 when they meet the fp32 tensor
@@ -1116,7 +1281,7 @@ int sgs_sample_topq(int mode, const float* p, const float* prior, double degree_
 
     const int64_t* dynE = dyn_edges_ptr();
     SGS_REQUIRE(!dynE || (nblk <= kSmallBlocks && q > 0 && q < E), SGS_EINVAL,
-                "sgs_sample_topq: a dynamic edge count (sgs_dyn_edges_set) needs 0 < q < capacity <= %lld", (long long)kSmallBlocks * kChunk);
+                "%s: a dynamic edge count (sgs_dyn_edges_set) needs 0 < q < capacity <= %lld", fn, (long long)kSmallBlocks * kChunk);
     if (nblk <= kSmallBlocks && q > 0 && q < E) {
         // fused small-E path: 6 / 7 launches (see "fused small-E path" above); same arithmetic, same results
         const uint32_t q32 = static_cast<uint32_t>(q);
@@ -1132,12 +1297,14 @@ int sgs_sample_topq(int mode, const float* p, const float* prior, double degree_
             hipLaunchKernelGGL(small_keys_hist0<SGS_SAMPLE_PRIOR>, kgrid, kblk, 0, stream, p, static_cast<const float*>(nullptr), noise, seed,
                                stream_id, epoch_ptr(), E, one_minus_c, c, part2, part, nblk, scal, keys, keys_out, h0, dynE);
         }
+        if (cover) launch_cover_rows(*cover, keys, E, h0, mcnt, dynE, stream);
         hipLaunchKernelGGL(small_hist_next, grid, blk, 0, stream, keys, E, kShift1, kMask1, kShift0, 1, q32, h0,
                            static_cast<const SelPart*>(nullptr), sel, h1, dynE);
         hipLaunchKernelGGL(small_hist_next, grid, blk, 0, stream, keys, E, kShift2, kMask2, kShift1, 0, q32, h1, sel, sel + 1, h2, dynE);
         hipLaunchKernelGGL(small_count, grid, blk, 0, stream, keys, E, q32, h2, sel + 1, st, cnt, scal, stats, dynE);
         hipLaunchKernelGGL(small_compact, grid, blk, 0, stream, keys, E, q, st, cnt, p, edge_index, mask, mask_aligned, sampled_eid,
                            sampled_edge_index, sampled_p, dynE);
+        if (cover) hipLaunchKernelGGL(cover_finish, dim3(1), blk, 0, stream, mcnt, cover->grid, q, stats, cover->info);
         SGS_LAUNCH_OK();
         return SGS_OK;
     }
@@ -1160,6 +1327,10 @@ int sgs_sample_topq(int mode, const float* p, const float* prior, double degree_
         hipLaunchKernelGGL(select_all, dim3(cdiv(E, 256)), dim3(256), 0, stream, E, p, edge_index, mask, sampled_eid,
                            sampled_edge_index, sampled_p, static_cast<uint8_t>(q == E ? 1 : 0));
         if (stats) hipLaunchKernelGGL(write_stats, dim3(1), dim3(1), 0, stream, scal, st, stats);
+        if (cover) {       // M does not depend on the keys: count the rows that have a non-loop entry
+            launch_cover_rows(*cover, nullptr, E, nullptr, mcnt, dynE, stream);
+            hipLaunchKernelGGL(cover_finish, dim3(1), blk, 0, stream, mcnt, cover->grid, q, stats, cover->info);
+        }
         SGS_LAUNCH_OK();
         return SGS_OK;
     }
@@ -1170,6 +1341,7 @@ int sgs_sample_topq(int mode, const float* p, const float* prior, double degree_
     else
         hipLaunchKernelGGL(keys_hist0<SGS_SAMPLE_PRIOR>, hgrid, blk, 0, stream, p, nullptr, noise, seed, stream_id, epoch_ptr(), int64_t(0), E,
                            one_minus_c, c, scal, keys, keys_out, hist);
+    if (cover) launch_cover_rows(*cover, keys, E, hist, mcnt, dynE, stream);
     hipLaunchKernelGGL(select_digit, dim3(1), blk, 0, stream, hist, kShift0, 1, static_cast<uint32_t>(q), st);
     hipLaunchKernelGGL(hist_next, hgrid, blk, 0, stream, keys, E, kShift1, kMask1, kShift0, st, hist);
     hipLaunchKernelGGL(select_digit, dim3(1), blk, 0, stream, hist, kShift1, 0, static_cast<uint32_t>(q), st);
@@ -1180,8 +1352,31 @@ int sgs_sample_topq(int mode, const float* p, const float* prior, double degree_
     hipLaunchKernelGGL(compact, grid, blk, 0, stream, keys, E, q, int64_t(-1), int64_t(0), st, cnt, p, edge_index, mask, mask_aligned,
                        sampled_eid, sampled_edge_index, sampled_p);
     if (stats) hipLaunchKernelGGL(write_stats, dim3(1), dim3(1), 0, stream, scal, st, stats);
+    if (cover) hipLaunchKernelGGL(cover_finish, dim3(1), blk, 0, stream, mcnt, cover->grid, q, stats, cover->info);
     SGS_LAUNCH_OK();
     return SGS_OK;
+}
+
+int sgs_sample_topq(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise,
+                    uint64_t seed, uint64_t stream_id, int64_t E, int64_t q, const int64_t* edge_index,
+                    uint8_t* mask, int64_t* sampled_eid, int64_t* sampled_edge_index, float* sampled_p, float* stats,
+                    float* keys_out, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    return sample_topq_impl("sgs_sample_topq", nullptr, mode, p, prior, degree_bias_coef, noise, seed, stream_id, E, q, edge_index, mask,
+                            sampled_eid, sampled_edge_index, sampled_p, stats, keys_out, ws, ws_bytes, stream_);
+}
+
+int sgs_sample_topq_cover(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise,
+                          uint64_t seed, uint64_t stream_id, int64_t E, int64_t q, const int64_t* edge_index,
+                          int64_t N, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid,
+                          uint8_t* mask, int64_t* sampled_eid, int64_t* sampled_edge_index, float* sampled_p,
+                          float* stats, float* keys_out, int32_t* cover_info, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    CoverArgs c{N, in_ptr, in_src, in_eid, cover_info, sgs_sample_topq_cover_variant(N, E), 1};
+    if (N > 0) {
+        const int64_t nb = cdiv(N, kCoverThreads / c.lanes);
+        c.grid = static_cast<int>(nb < kCoverGrid ? nb : kCoverGrid);
+    }
+    return sample_topq_impl("sgs_sample_topq_cover", &c, mode, p, prior, degree_bias_coef, noise, seed, stream_id, E, q, edge_index, mask,
+                            sampled_eid, sampled_edge_index, sampled_p, stats, keys_out, ws, ws_bytes, stream_);
 }
 
 

@@ -23,7 +23,7 @@ import torch
 
 from . import ops
 from .model import _DropoutClock
-from .sampling import _NoiseClock, draw_learned, draw_prior, random_edge_sampling
+from .sampling import _NoiseClock, cover_graph, cover_nodes, draw_learned, draw_prior, random_edge_sampling
 
 PATH_COUNTS = {"serial": 0, "batched": 0}
 EVAL_BATCH_BUDGET = 512 << 20          # bytes of per-pass buffers when args.sgs_eval_batch is True
@@ -34,18 +34,19 @@ def _one_draw(args, model, batch, q, mode, edge_probs, noise):
     """-> (logits, the edge list the model ran on)."""
     if mode == 'learned':
         if batch.edge_index.shape[1] > q:
-            smp = draw_learned(None, edge_probs, batch.edge_index, q, args.degree_bias_coef, istest=True, noise=noise)
+            smp = draw_learned(None, edge_probs, batch.edge_index, q, args.degree_bias_coef, istest=True, noise=noise,
+                               cover=cover_graph(args, batch))
             w = ops.st_weights(edge_probs, None, args.degree_bias_coef, smp.stats, smp.eid)     # sampling.py:137-155
             return model(batch, smp.edge_index, w), smp.edge_index
         return model(batch, batch.edge_index), batch.edge_index
     if mode == 'random':
         if batch.edge_index.shape[1] > q:
-            ei = random_edge_sampling(batch.edge_index, q=q)
+            ei = random_edge_sampling(batch.edge_index, q=q, cover=cover_graph(args, batch))
             return model(batch, ei), ei
         return model(batch, batch.edge_index), batch.edge_index
     if mode == 'edge':
         if batch.edge_index.shape[1] > q:
-            ei = draw_prior(batch.prob, batch.edge_index, q, noise=noise).edge_index
+            ei = draw_prior(batch.prob, batch.edge_index, q, noise=noise, cover=cover_graph(args, batch)).edge_index
             return model(batch, ei), ei
         return model(batch, batch.edge_index), batch.edge_index
     if mode == 'full':
@@ -54,6 +55,7 @@ def _one_draw(args, model, batch, q, mode, edge_probs, noise):
 
 
 def _run(args, model, cluster_loader, device, q, mode, n_draws):
+    cover_nodes(args)                       # args.sgs_cover_nodes: validated before any partition is read
     model.eval()
     counts = None
     noises = list(getattr(args, "_sgs_noise_eval", None) or [])
@@ -135,7 +137,11 @@ def _batched_ok(args, model, n_draws) -> bool:
     bool, all checked here, before any partition is read.  A model with gat_heads > 1, gat_edge_weight or cheb_k > 1 takes the engine only
     with sgs_eval_batch_variants=True (per-head GAT kernels / per-draw Chebyshev steps, ops.ensemble_partition_head).  A gat_v2 model keeps
     the serial loop whatever the opt-ins say: there is no batched GATv2 engine.  So does a gin_edge_weight model: the batched GIN engine
-    (ops._drawn_gin_logits) aggregates transformed features with unit weights, which is not the GINE layer."""
+    (ops._drawn_gin_logits) aggregates transformed features with unit weights, which is not the GINE layer.  Under
+    args.sgs_cover_nodes (node-covering draws, checked first) every model keeps the serial loop: sgs_sample_topq_multi has no covering
+    form."""
+    if cover_nodes(args):
+        return False
     flag = getattr(args, "sgs_eval_batch", False)
     if not flag:
         return False

@@ -324,19 +324,22 @@ def dropout_keep(seed: int, site: int, rows: int, cols: int, p: float, device) -
 
 # ------------------------------------------------------------------ sampler
 class SampleResult:
-    __slots__ = ("mask", "eid", "edge_index", "p", "stats", "keys", "E", "q")
+    __slots__ = ("mask", "eid", "edge_index", "p", "stats", "keys", "E", "q", "cover_info")
 
     def check(self) -> None:
         """torch.multinomial(replacement=False) raises when fewer than q categories have a positive weight; the fused draw cannot
         raise from the device.  It reports the case through `stats`: the threshold key is then 0 (zero-weight edges were admitted
-        by the lowest-id tie-break).  Calling this reads stats back (one synchronisation) and raises like the reference."""
+        by the lowest-id tie-break).  Calling this reads stats back (one synchronisation) and raises like the reference.
+        (A covering draw reports the threshold without its flag bit, so the meaning is the same there.)"""
         if self.q > 0 and float(self.stats[2]) <= 0.0:
             raise RuntimeError("invalid multinomial distribution (with replacement=False, not enough non-negative category to sample)")
 
 
 def sample_topq(mode: int, p: torch.Tensor, prior, c: float, q: int, edge_index, noise=None, seed: int = 0,
-                stream_id: int = 0, want_keys: bool = False, want_p: bool = True) -> SampleResult:
-    """K0/K2/K3 (see sgs_sample_topq).  p [E] f32 (None: uniform weights); prior [E] f32 or None; edge_index [2,E] i64."""
+                stream_id: int = 0, want_keys: bool = False, want_p: bool = True, cover: "Graph | None" = None) -> SampleResult:
+    """K0/K2/K3 (see sgs_sample_topq).  p [E] f32 (None: uniform weights); prior [E] f32 or None; edge_index [2,E] i64.
+    `cover`: the Graph of the candidate edges (get_graph(edge_index, N)) makes it a node-covering draw (sgs_sample_topq_cover: every
+    node keeps its best non-loop in-edge while the budget lasts); the result then carries cover_info int32 [2] = {M, min(M, q)}."""
     L = _lib.lib()
     _need_gpu(p, prior, edge_index, noise)
     if p is None and edge_index is None:
@@ -353,6 +356,19 @@ def sample_topq(mode: int, p: torch.Tensor, prior, c: float, q: int, edge_index,
     r.p = torch.empty(q, dtype=torch.float32, device=dev) if (want_p and p is not None) else None
     r.stats = torch.empty(4, dtype=torch.float32, device=dev)
     r.keys = torch.empty(E, dtype=torch.float32, device=dev) if want_keys else None
+    r.cover_info = None
+    if cover is not None:
+        if not isinstance(cover, Graph) or cover.n_edges != E:
+            raise RuntimeError(f"sample_topq: cover must be the Graph of the E={E} candidate edges"
+                               + (f" (it has {cover.n_edges})" if isinstance(cover, Graph) else ""))
+        r.cover_info = (torch.empty if E > 0 else torch.zeros)(2, dtype=torch.int32, device=dev)      # (E == 0: the call writes nothing)
+        ws = workspace(L.sgs_sample_topq_cover_workspace_bytes(E, cover.N), dev)
+        _lib.check(L.sgs_sample_topq_cover(mode, _ptr(p, torch.float32), _ptr(prior, torch.float32), float(c),
+                                           _ptr(noise, torch.float32), seed, stream_id, E, q, _ptr(edge_index, torch.int64),
+                                           cover.N, _ptr(cover.in_ptr), _ptr(cover.in_src), _ptr(cover.in_eid),
+                                           _ptr(r.mask), _ptr(r.eid), _ptr(r.edge_index), _ptr(r.p), _ptr(r.stats),
+                                           _ptr(r.keys), _ptr(r.cover_info), ws.data_ptr(), ws.numel(), _stream()), "sgs_sample_topq_cover")
+        return r
     nws = L.sgs_sample_topq_workspace_bytes(E)
     ws = workspace(nws, dev)
     _lib.check(L.sgs_sample_topq(mode, _ptr(p, torch.float32), _ptr(prior, torch.float32), float(c),

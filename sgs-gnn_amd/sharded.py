@@ -27,6 +27,7 @@ import torch.distributed as dist
 
 from . import _lib, ops
 from .model import SITE_ENC, SITE_GNN, SITE_SCORE
+from .sampling import cover_nodes
 
 
 def _world():
@@ -81,11 +82,20 @@ def _all_gather_concat(t: torch.Tensor, sizes):
     return torch.cat([o[:n] for o, n in zip(out, sizes)])
 
 
+def _no_cover(args, where):
+    """Node-covering draws (args.sgs_cover_nodes) need each node's in-edges on one rank; the edge-sharded draw has no such form."""
+    if cover_nodes(args):
+        raise NotImplementedError(f"{where}: args.sgs_cover_nodes (node-covering draws) is not available for edge-sharded draws")
+
+
 def dist_sample_topq(mode: int, p_local, prior_local, c: float, q: int, edge_index_local, edge_offset: int, bounds,
-                     noise_local=None, seed: int = 0, stream_id: int = 0, want_keys: bool = False) -> ops.SampleResult:
+                     noise_local=None, seed: int = 0, stream_id: int = 0, want_keys: bool = False, *, cover=None) -> ops.SampleResult:
     """One exact global top-q draw over edge-sharded keys.  Returns this rank's part: mask over the local
     edges, GLOBAL ids of the selected local edges (ascending), their columns and probabilities, and
-    stats = {Z, max, threshold key, #ties taken} (identical on every rank)."""
+    stats = {Z, max, threshold key, #ties taken} (identical on every rank).  `cover` (ops.sample_topq's node-covering draw) is
+    refused: a node's in-edges are spread over the ranks."""
+    if cover is not None:
+        raise NotImplementedError("dist_sample_topq: node-covering draws (sgs_cover_nodes) are not available for edge-sharded draws")
     L = _lib.lib()
     rank, world = _world()
     dev = p_local.device
@@ -216,6 +226,7 @@ def sharded_evaluate_forward(args, model, shard: EdgeShard, q: int, noise_local=
     """evaluate.py:14-20 (mode 'learned', model.eval()) on an edge-sharded graph: EdgeProbGCN encoder over
     all E edges, scores for the local edges, one global istest draw, weighted 2-layer GCN -> logits
     (replicated on every rank).  Returns (logits, local SampleResult)."""
+    _no_cover(args, "sharded_evaluate_forward")
     _no_cheb_order(model, "sharded_evaluate_forward")
     sc = model.edge_prob_mlp
     x, N = shard.x, shard.N
@@ -407,6 +418,7 @@ def train_step_sharded(args, model, shard: EdgeShard, optimizer_gnn, optimizer_e
     """One hybrid step (training_hybrid.py:35-141, mode 'learned', E > q, EdgeProbGCN scorer) on an edge-sharded
     graph.  Dropout seeds / noise ticks are consumed in the same order as the single-GPU `train`, rows are
     global ids, so the result matches the unsharded step up to fp32 summation order.  Returns a trace dict."""
+    _no_cover(args, "train_step_sharded")
     from .model import _DropoutClock
     from .sampling import _NoiseClock
     _no_cheb_order(model, "train_step_sharded")
@@ -805,6 +817,7 @@ def train_step_blocksharded(args, model, shard: EdgeShard, optimizer_gnn, optimi
     """train_step_sharded with the GCN layers in node-block form (reduce-scatter forward / all-gather backward, node-level work on
     1 / R of the rows): same draws (bit for bit), same logits and gradients up to fp32 summation order.  Returns the same trace dict;
     `learned_out` is the full [N, C] table (all-gathered for the regulariser anyway)."""
+    _no_cover(args, "train_step_blocksharded")
     from .model import _DropoutClock
     from .sampling import _NoiseClock
     _no_cheb_order(model, "train_step_blocksharded")

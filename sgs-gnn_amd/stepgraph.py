@@ -59,6 +59,7 @@ import torch
 
 from . import _lib, ops
 from .data import Batch
+from .sampling import cover_nodes
 
 _DEBUG = os.environ.get("SGS_SG_DEBUG", "")     # "fork": capture the random encoder on a second stream (measured slower)
 _PREFETCH = os.environ.get("SGS_SG_PREFETCH", "1") != "0"
@@ -207,7 +208,7 @@ class StepGraphs:
         return (self.pipeline, bool(a.conditional), bool(a.sparse_edge_mlp), a.reg1 == True, a.reg2 == True,   # noqa: E712
                 float(a.regularizer1_coef), float(a.consist_reg_coef), float(a.degree_bias_coef), int(self.q),
                 bool(self.use_checkpoint), tuple(p.data_ptr() for p in self.params), _opt_signature(self.optimizers),
-                ops.check_precision(getattr(a, "sgs_precision", None)), self._criterion_key())
+                ops.check_precision(getattr(a, "sgs_precision", None)), self._criterion_key(), cover_nodes(a))
 
     def _criterion_key(self):
         """What a capture bakes in of the criterion: the class weight's ADDRESS (the kernels read the weight through it at every replay, so

@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from . import ops
 from .dist import GradSync, is_parallel
-from .sampling import draw_learned, draw_prior, random_edge_sampling
+from .sampling import cover_graph, cover_nodes, draw_learned, draw_prior, random_edge_sampling
 from .utils import segment
 
 _PIPELINES = ("two_pass", "straight_through", "hybrid")
@@ -81,7 +81,7 @@ def sampled_prefix(args, batch, q, noise=None):
     if not (args.conditional or args.sparse_edge_mlp):
         return None
     noise = noise or {}
-    rs = draw_prior(batch.prob, batch.edge_index, q, noise=noise.get("prior"))
+    rs = draw_prior(batch.prob, batch.edge_index, q, noise=noise.get("prior"), cover=cover_graph(args, batch))
     graph_r = ops.get_subgraph(batch.edge_index, batch.x.shape[0], rs)
     ops.gcn_norm(graph_r, None)                                       # cached on the graph: every unweighted layer over it reuses it
     return rs
@@ -128,7 +128,7 @@ def sampled_forward(pipeline, args, model, batch, q, use_checkpoint=False, noise
 
     # K2+K3: learned draw on detached probabilities, compacted columns in edge order
     st.smp = smp = draw_learned(batch.prob, st.edge_probs_full, batch.edge_index, q, args.degree_bias_coef,
-                                noise=noise.get("sample"), want_p=(pipeline == "hybrid"))
+                                noise=noise.get("sample"), want_p=(pipeline == "hybrid"), cover=cover_graph(args, batch))
     st.sampled_edge_index = smp.edge_index
     graph_s = ops.get_subgraph(batch.edge_index, N, smp)
 
@@ -247,6 +247,7 @@ def _train(pipeline, args, epoch, max_epoch, model, optimizer_gnn, optimizer_edg
     # args.sgs_precision: "fp32" (default, absent or None) or "bf16", the precision of the scorer's matrix-core contractions (ops.edge_score);
     # checked before any partition is read
     precision = ops.check_precision(getattr(args, "sgs_precision", None))
+    cover_nodes(args)            # args.sgs_cover_nodes (node-covering draws, sampling.cover_nodes): validated here too, before any partition is read
     with ops.scorer_precision(precision):
         return _train_in(pipeline, args, epoch, max_epoch, model, optimizer_gnn, optimizer_edge_prob, optimizer, criterion, cluster_loader, q)
 
@@ -465,7 +466,7 @@ def _epoch_loop(pipeline, args, epoch, max_epoch, model, optimizer_gnn, optimize
         elif mode == 'random':
             batch = batch.to(device)
             if batch.edge_index.shape[1] > q:
-                out = model(batch, random_edge_sampling(batch.edge_index, q=q))
+                out = model(batch, random_edge_sampling(batch.edge_index, q=q, cover=cover_graph(args, batch)))
             else:
                 out = model(batch, batch.edge_index)
             loss = _ce(criterion, out, batch)
@@ -477,7 +478,7 @@ def _epoch_loop(pipeline, args, epoch, max_epoch, model, optimizer_gnn, optimize
         elif mode == 'edge':
             batch = batch.to(device)
             if batch.edge_index.shape[1] > q:
-                out = model(batch, draw_prior(batch.prob, batch.edge_index, q).edge_index)
+                out = model(batch, draw_prior(batch.prob, batch.edge_index, q, cover=cover_graph(args, batch)).edge_index)
             else:
                 out = model(batch, batch.edge_index)
             loss = _ce(criterion, out, batch)
