@@ -371,6 +371,26 @@ int sgs_spmm_csr_bwd_prev(const float* dZ, int64_t N, int64_t D, int64_t nnz, co
                           const float* diag, const float* W, int64_t Dp, const float* Yp, int act, float p_drop, float* dX, float* dZp,
                           float* colsum, sgs_stream_t stream);
 
+/* Two-job forms of the GNN head's two forward launches: job a and job b are two graphs over the same N rows (the learned and the random
+ * subgraph of a sampled step) that share everything but their CSR, weights, dropout seed and outputs.  One launch (gridDim.y = 2) runs
+ * both; each job's outputs are bitwise what the single-job call writes.
+ * sgs_gcn_dual_ok(N, nnz_a, nnz_b, D, Dn): 1 iff both jobs pass sgs_gcn_pair_ok(N, nnz, D), Dn > 0 and both select the same kernel
+ *   variant by their size (nnz >= 256 N or not, for both); the layer-2 call over rows of width Dn then takes its row-block path for both
+ *   jobs as well.  (The variants also depend on 16-byte alignment of X and Y, which the calls check per job.)
+ * sgs_spmm_csr_next_dual: per job sgs_spmm_csr_next(X, ..., Wn, Dn, Y_j, Z_j) with the shared X, bias, act, p_drop, site, Wn.
+ * sgs_spmm_csr_dual: per job sgs_spmm_csr(X_j, ..., Y_j) on its row-block path with the shared bias, act, p_drop, site.
+ * Both return SGS_EINVAL and launch nothing when either job is not a row-block shape or the two jobs would select different kernel
+ * variants: the caller then makes the two single-job calls. */
+int sgs_gcn_dual_ok(int64_t N, int64_t nnz_a, int64_t nnz_b, int64_t D, int64_t Dn);
+int sgs_spmm_csr_next_dual(const float* X, int64_t N, int64_t D, const float* bias, int act, float p_drop, uint32_t site, const float* Wn,
+                           int64_t Dn, int64_t nnz_a, const int32_t* ptr_a, const int32_t* col_a, const float* val_a, const float* diag_a,
+                           uint64_t seed_a, float* Y_a, float* Z_a, int64_t nnz_b, const int32_t* ptr_b, const int32_t* col_b,
+                           const float* val_b, const float* diag_b, uint64_t seed_b, float* Y_b, float* Z_b, sgs_stream_t stream);
+int sgs_spmm_csr_dual(const float* X_a, const float* X_b, int64_t N, int64_t D, const float* bias, int act, float p_drop, uint32_t site,
+                      int64_t nnz_a, const int32_t* ptr_a, const int32_t* col_a, const float* val_a, const float* diag_a, uint64_t seed_a,
+                      float* Y_a, int64_t nnz_b, const int32_t* ptr_b, const int32_t* col_b, const float* val_b, const float* diag_b,
+                      uint64_t seed_b, float* Y_b, sgs_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * K1b: fused edge scorer (model.py:29-34 / 115-122 `_edge_score`; never materialises the
  * reference's [E,2H] feature or [E,H] hidden tensors):

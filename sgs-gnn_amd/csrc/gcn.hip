@@ -1134,14 +1134,15 @@ __device__ __forceinline__ float lib_gemm_dot(int K, FY y, FW w) {
     for (int k = Kmain; k < K; ++k) z = fmaf(y(k), w(k), z);
     return z;
 }
-template <int VEC, int NW, int MODE>
-__global__ void __launch_bounds__(1024) spmm_rowgroup_pair(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
-                                                           const int* __restrict__ col, const float* __restrict__ val,
-                                                           const float* __restrict__ diag, const float* __restrict__ bias, int act,
-                                                           float drop_scale, uint32_t drop_thresh, uint64_t seed, uint32_t site,
-                                                           const uint64_t* __restrict__ epoch, float* __restrict__ Y,
-                                                           const float* __restrict__ Wn, int64_t Dn, const float* __restrict__ Yp,
-                                                           float* __restrict__ Zn, int ncs, float* __restrict__ colsum) {
+// GU: gathers in flight per wave in the main loop (the entries are taken in the same order whatever GU is: k, k + NW, k + 2 NW, ...)
+template <int VEC, int NW, int MODE, int GU = 8>
+__device__ __forceinline__ void spmm_rowgroup_pair_body(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
+                                                        const int* __restrict__ col, const float* __restrict__ val,
+                                                        const float* __restrict__ diag, const float* __restrict__ bias, int act,
+                                                        float drop_scale, uint32_t drop_thresh, uint64_t seed, uint32_t site,
+                                                        const uint64_t* __restrict__ epoch, float* __restrict__ Y,
+                                                        const float* __restrict__ Wn, int64_t Dn, const float* __restrict__ Yp,
+                                                        float* __restrict__ Zn, int ncs, float* __restrict__ colsum) {
     using V = typename VecT<VEC>::type;
     constexpr int RG = 16 / NW;
     __shared__ float part[RG][NW][64 * VEC];
@@ -1187,14 +1188,14 @@ __global__ void __launch_bounds__(1024) spmm_rowgroup_pair(const float* __restri
         for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
         if (in) {
             int k = b + wave;
-            for (; k + 7 * NW < e; k += 8 * NW) {
-                int j[8]; float w[8]; V x[8];
+            for (; k + (GU - 1) * NW < e; k += GU * NW) {
+                int j[GU]; float w[GU]; V x[GU];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) { j[u] = col[k + NW * u]; w[u] = val[k + NW * u]; }
+                for (int u = 0; u < GU; ++u) { j[u] = col[k + NW * u]; w[u] = val[k + NW * u]; }
 #pragma unroll
-                for (int u = 0; u < 8; ++u) x[u] = *reinterpret_cast<const V*>(X + static_cast<int64_t>(j[u]) * D + c0);
+                for (int u = 0; u < GU; ++u) x[u] = *reinterpret_cast<const V*>(X + static_cast<int64_t>(j[u]) * D + c0);
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
+                for (int u = 0; u < GU; ++u) {
                     float xv[VEC];
                     *reinterpret_cast<V*>(xv) = x[u];
 #pragma unroll
@@ -1259,6 +1260,61 @@ __global__ void __launch_bounds__(1024) spmm_rowgroup_pair(const float* __restri
             Zn[ir * Dn + ep] = a;
         }
     }
+}
+template <int VEC, int NW, int MODE>
+__global__ void __launch_bounds__(1024) spmm_rowgroup_pair(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
+                                                           const int* __restrict__ col, const float* __restrict__ val,
+                                                           const float* __restrict__ diag, const float* __restrict__ bias, int act,
+                                                           float drop_scale, uint32_t drop_thresh, uint64_t seed, uint32_t site,
+                                                           const uint64_t* __restrict__ epoch, float* __restrict__ Y,
+                                                           const float* __restrict__ Wn, int64_t Dn, const float* __restrict__ Yp,
+                                                           float* __restrict__ Zn, int ncs, float* __restrict__ colsum) {
+    spmm_rowgroup_pair_body<VEC, NW, MODE>(X, N, D, ptr, col, val, diag, bias, act, drop_scale, drop_thresh, seed, site, epoch, Y, Wn, Dn, Yp, Zn,
+                                           ncs, colsum);
+}
+
+// Two jobs per launch (the GNN head's learned and random forward: the same layers and weights over two graphs of N rows): gridDim.y = 2,
+// workgroup (x, y) runs the single-job body of workgroup x on job y's graph and outputs (workgroup-uniform look-up: scalar loads), so each
+// job's results are bitwise the single launch's.  Neither job reads what the other writes.
+struct SpmmDualJob {
+    const float* X;
+    const int* ptr;
+    const int* col;
+    const float* val;
+    const float* diag;
+    float* Y;
+    float* Z;               // layer pair only: Y Wn^T
+    int64_t nnz;
+    uint64_t seed;
+};
+struct SpmmDualArgs {
+    SpmmDualJob job[2];
+};
+template <int VEC, int NW>
+__global__ void __launch_bounds__(64 * NW) spmm_csr_rowblock_dual(SpmmDualArgs a, int64_t N, int64_t D, const float* __restrict__ bias, int act,
+                                                                  float drop_scale, uint32_t drop_thresh, uint32_t site,
+                                                                  const uint64_t* __restrict__ epoch) {
+    const SpmmDualJob& j = a.job[blockIdx.y];
+    spmm_csr_rowblock_body<VEC, NW>(j.X, N, D, j.ptr, j.col, j.val, j.diag, bias, act, drop_scale, drop_thresh, j.seed, site, epoch, j.Y);
+}
+// The pair kernel's 16-wave workgroups are 4 waves on every SIMD: two of them share a CU (what lets the two jobs' gathers overlap) only
+// within 512 / 8 = 64 VGPRs.  The single-job <4, 4> kernel has 78, and the bound alone spills; with 4 float4 gathers in flight instead
+// of 8 the kernel fits without scratch (60 VGPRs).  LDS: 2 x 72 KiB of the CU's 160.  -DSGS_DUAL_PAIR_CAPPED=0 builds the uncapped
+// form (the single-job kernel's registers and unroll: one workgroup per CU) for A/B timing.
+#ifndef SGS_DUAL_PAIR_CAPPED
+#define SGS_DUAL_PAIR_CAPPED 1
+#endif
+constexpr int kDualPairWaves = SGS_DUAL_PAIR_CAPPED ? 8 : 4;
+constexpr int dual_pair_gu(int vec) { return SGS_DUAL_PAIR_CAPPED && vec == 4 ? 4 : 8; }
+template <int VEC, int NW>
+__global__ void __launch_bounds__(1024, kDualPairWaves) spmm_rowgroup_pair_dual(SpmmDualArgs a, int64_t N, int64_t D,
+                                                                                const float* __restrict__ bias, int act, float drop_scale,
+                                                                                uint32_t drop_thresh, uint32_t site,
+                                                                                const uint64_t* __restrict__ epoch,
+                                                                                const float* __restrict__ Wn, int64_t Dn) {
+    const SpmmDualJob& j = a.job[blockIdx.y];
+    spmm_rowgroup_pair_body<VEC, NW, kPairFwd, dual_pair_gu(VEC)>(j.X, N, D, j.ptr, j.col, j.val, j.diag, bias, act, drop_scale, drop_thresh, j.seed,
+                                                            site, epoch, j.Y, Wn, Dn, nullptr, j.Z, 0, nullptr);
 }
 
 inline int pick_lpr(int64_t D, int vec) {
@@ -1833,6 +1889,71 @@ int sgs_spmm_csr_bwd_prev(const float* dZ, int64_t N, int64_t D, int64_t nnz, co
     return SGS_OK;
 }
 #undef PAIR_LAUNCH
+
+// ---- two-job forms of the GNN head's two forward launches (spmm_rowgroup_pair_dual, spmm_csr_rowblock_dual)
+int sgs_gcn_dual_ok(int64_t N, int64_t nnz_a, int64_t nnz_b, int64_t D, int64_t Dn) {
+    return (sgs_gcn_pair_ok(N, nnz_a, D) && sgs_gcn_pair_ok(N, nnz_b, D) && Dn > 0 && (nnz_a >= 256 * N) == (nnz_b >= 256 * N)) ? 1 : 0;
+}
+
+int sgs_spmm_csr_next_dual(const float* X, int64_t N, int64_t D, const float* bias, int act, float p_drop, uint32_t site, const float* Wn,
+                           int64_t Dn, int64_t nnz_a, const int32_t* ptr_a, const int32_t* col_a, const float* val_a, const float* diag_a,
+                           uint64_t seed_a, float* Y_a, float* Z_a, int64_t nnz_b, const int32_t* ptr_b, const int32_t* col_b,
+                           const float* val_b, const float* diag_b, uint64_t seed_b, float* Y_b, float* Z_b, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(sgs_gcn_dual_ok(N, nnz_a, nnz_b, D, Dn), SGS_EINVAL, "sgs_spmm_csr_next_dual: not two row-block shapes of one variant (see sgs_gcn_dual_ok)");
+    SGS_REQUIRE(act >= SGS_ACT_NONE && act <= SGS_ACT_RELU_DROPOUT && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL,
+                "sgs_spmm_csr_next_dual: bad activation / dropout");
+    SGS_REQUIRE(X && ptr_a && ptr_b && Y_a && Y_b && Wn && Z_a && Z_b && X != Y_a && X != Y_b && X != Z_a && X != Z_b && Y_a != Y_b &&
+                    Z_a != Z_b && Y_a != Z_a && Y_a != Z_b && Y_b != Z_a && Y_b != Z_b,
+                SGS_EINVAL, "sgs_spmm_csr_next_dual: null or aliased pointer");
+    const int vec = (D % 4 == 0 && aligned16(X) && aligned16(Y_a)) ? 4 : 1;      // (per job as sgs_spmm_csr_next picks it)
+    SGS_REQUIRE(vec == ((D % 4 == 0 && aligned16(X) && aligned16(Y_b)) ? 4 : 1), SGS_EINVAL,
+                "sgs_spmm_csr_next_dual: the two jobs select different kernel variants (alignment)");
+    const bool wide = nnz_a >= 256 * N;
+    const float scale = 1.0f / (1.0f - p_drop);
+    const uint32_t th = dropout_thresh(p_drop);
+    if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
+    SpmmDualArgs a;
+    a.job[0] = SpmmDualJob{X, ptr_a, col_a, val_a, diag_a, Y_a, Z_a, nnz_a, seed_a};
+    a.job[1] = SpmmDualJob{X, ptr_b, col_b, val_b, diag_b, Y_b, Z_b, nnz_b, seed_b};
+    const dim3 grid(static_cast<unsigned>(cdiv(N, wide ? 1 : 4)), 2);
+    if (vec == 4 && wide)  hipLaunchKernelGGL((spmm_rowgroup_pair_dual<4, 16>), grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
+    else if (vec == 4)     hipLaunchKernelGGL((spmm_rowgroup_pair_dual<4, 4>), grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
+    else if (wide)         hipLaunchKernelGGL((spmm_rowgroup_pair_dual<1, 16>), grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
+    else                   hipLaunchKernelGGL((spmm_rowgroup_pair_dual<1, 4>), grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_spmm_csr_dual(const float* X_a, const float* X_b, int64_t N, int64_t D, const float* bias, int act, float p_drop, uint32_t site,
+                      int64_t nnz_a, const int32_t* ptr_a, const int32_t* col_a, const float* val_a, const float* diag_a, uint64_t seed_a,
+                      float* Y_a, int64_t nnz_b, const int32_t* ptr_b, const int32_t* col_b, const float* val_b, const float* diag_b,
+                      uint64_t seed_b, float* Y_b, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(N > 0 && D > 0, SGS_EINVAL, "sgs_spmm_csr_dual: bad sizes");
+    SGS_REQUIRE(act >= SGS_ACT_NONE && act <= SGS_ACT_RELU_DROPOUT && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL,
+                "sgs_spmm_csr_dual: bad activation / dropout");
+    SGS_REQUIRE(X_a && X_b && ptr_a && ptr_b && Y_a && Y_b && Y_a != Y_b && X_a != Y_a && X_a != Y_b && X_b != Y_a && X_b != Y_b, SGS_EINVAL,
+                "sgs_spmm_csr_dual: null or aliased pointer");
+    const int var = sgs_spmm_csr_variant(N, D, nnz_a, aligned16(X_a) && aligned16(Y_a));
+    SGS_REQUIRE(var >= 1000 && var == sgs_spmm_csr_variant(N, D, nnz_b, aligned16(X_b) && aligned16(Y_b)), SGS_EINVAL,
+                "sgs_spmm_csr_dual: not two row-block shapes of one variant (see sgs_spmm_csr_variant)");
+    const float scale = 1.0f / (1.0f - p_drop);
+    const uint32_t th = dropout_thresh(p_drop);
+    if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
+    SpmmDualArgs a;
+    a.job[0] = SpmmDualJob{X_a, ptr_a, col_a, val_a, diag_a, Y_a, nullptr, nnz_a, seed_a};
+    a.job[1] = SpmmDualJob{X_b, ptr_b, col_b, val_b, diag_b, Y_b, nullptr, nnz_b, seed_b};
+    const dim3 g_(static_cast<unsigned>(N), 2);
+    switch (var) {
+        case 1416: hipLaunchKernelGGL((spmm_csr_rowblock_dual<4, 16>), g_, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
+        case 1404: hipLaunchKernelGGL((spmm_csr_rowblock_dual<4, 4>), g_, dim3(kT), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
+        case 1116: hipLaunchKernelGGL((spmm_csr_rowblock_dual<1, 16>), g_, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
+        default:   hipLaunchKernelGGL((spmm_csr_rowblock_dual<1, 4>), g_, dim3(kT), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
+    }
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
 
 }  // extern "C"
 

@@ -110,6 +110,27 @@ class GNNModel(nn.Module):
             self.gcn1._remember(key, x, xl1)
             return out
 
+    def forward_pair(self, data, edge_index_a, edge_weight_a, edge_index_b):
+        """(forward(data, edge_index_a, edge_weight_a), forward(data, edge_index_b)), bitwise and with the same autograd graph, but with
+        both graphs' jobs in each of the two forward launches (ops.gcn2_dual): the sampled step's learned and random forward.  Dropout
+        seeds are drawn in the order of the two calls (a, then b)."""
+        from .utils import segment
+        x = data.x
+        ops.feature_csr(x, build=True)
+        with segment(self, "gnn_forward"):
+            N = x.shape[0]
+            norm_a = ops.gcn_norm(ops.get_graph(edge_index_a, N), edge_weight_a)
+            norm_b = ops.gcn_norm(ops.get_graph(edge_index_b, N), None)
+            p = self.dropout.p if self.training else 0.0
+            act = ops.ACT_RELU_DROPOUT if p > 0 else ops.ACT_RELU
+            xl1, key = self.gcn1._memo(x)
+            seed_a = _DropoutClock.next_seed()
+            seed_b = _DropoutClock.next_seed()
+            out_a, out_b, xl1 = ops.gcn2_dual(x, self.gcn1.lin.weight, self.gcn1.bias, self.gcn2.lin.weight, self.gcn2.bias, norm_a, norm_b,
+                                              act=act, p=p, seed_a=seed_a, seed_b=seed_b, site=SITE_GNN, xl1=xl1)
+            self.gcn1._remember(key, x, xl1)
+            return out_a, out_b
+
 
 # ------------------------------------------------------------------ GAT head (model.py:189-208)
 SITE_GAT_ATT, SITE_GAT_ACT = 16, 32          # attention dropout uses site, site + 1 per layer

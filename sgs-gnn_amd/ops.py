@@ -2304,7 +2304,7 @@ class _GCN2(torch.autograd.Function):
     exactly _GCNLayer's calls.  `xl1` may be supplied (memoised x W1^T shared by the learned and the random forward of one step)."""
 
     @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, handle, nm, act, p, seed, site, xl1):
+    def forward(ctx, x, W1, b1, W2, b2, handle, nm, act, p, seed, site, xl1, pre=None):
         L = _lib.lib()
         gr = nm.graph
         if xl1 is None:
@@ -2312,7 +2312,9 @@ class _GCN2(torch.autograd.Function):
         N, H = xl1.shape
         C = W2.shape[0]
         fused = _pair_ok(gr, H, C) and xl1.is_contiguous() and W2.is_contiguous() and W2.shape[1] == H
-        if fused:
+        if pre is not None:       # (h, xl2, out) of this very forward, already computed on the fused path as one job of gcn2_dual's launches
+            h, xl2, out = pre
+        elif fused:
             h = torch.empty(N, H, dtype=torch.float32, device=xl1.device)
             xl2 = torch.empty(N, C, dtype=torch.float32, device=xl1.device)
             _lib.check(L.sgs_spmm_csr_next(_ptr(xl1, torch.float32), N, H, gr.n_edges, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(nm.what_in),
@@ -2321,7 +2323,8 @@ class _GCN2(torch.autograd.Function):
         else:
             h = _spmm(xl1, gr.in_ptr, gr.in_src, nm.what_in, nm.what_loop, b1, act, p, seed, site, N, H, gr.n_edges)
             xl2 = h @ W2.t()
-        out = _spmm(xl2, gr.in_ptr, gr.in_src, nm.what_in, nm.what_loop, b2, ACT_NONE, 0.0, 0, 0, N, C, gr.n_edges)
+        if pre is None:
+            out = _spmm(xl2, gr.in_ptr, gr.in_src, nm.what_in, nm.what_loop, b2, ACT_NONE, 0.0, 0, 0, N, C, gr.n_edges)
         ctx.nm, ctx.act, ctx.p, ctx.fused = nm, act, p, fused
         ctx.has_b1, ctx.has_b2, ctx.has_handle = b1 is not None, b2 is not None, handle is not None
         ctx.save_for_backward(x, W1, xl1, h, W2, xl2)
@@ -2393,7 +2396,7 @@ class _GCN2(torch.autograd.Function):
         if need_g:          # the two layers' gradients wrt the shared normalisation, in _handle_grad's contract (layer 2 reports first)
             r2, r1 = _handle_grad(nm, g2), _handle_grad(nm, g1)
             g = r2 if r1 is None else (r1 if r2 is None else r2 + r1)
-        return dx, dW1, db1, dW2, db2, g, None, None, None, None, None, None
+        return dx, dW1, db1, dW2, db2, g, None, None, None, None, None, None, None
 
 
 def gcn2(x, W1, b1, W2, b2, nm: Norm, act=ACT_RELU, p=0.0, seed=0, site=0, xl1=None):
@@ -2403,6 +2406,76 @@ def gcn2(x, W1, b1, W2, b2, nm: Norm, act=ACT_RELU, p=0.0, seed=0, site=0, xl1=N
     if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != nm.graph.N:
         raise RuntimeError("gcn2: x must be float32 [N, F]")
     return _GCN2.apply(x, W1, b1, W2, b2, nm.handle, nm, act, float(p), int(seed), int(site), xl1)
+
+
+# ------------------------------------------------------------------ the GNN head over two graphs: both forwards in two launches
+_gcn_dual_enabled = True                         # False: gcn2_dual is two plain gcn2 calls (A/B switch: set_gcn_dual)
+GCN_DUAL_FORWARDS = {"shared": 0}                # forwards that ran as the two two-job launches (tests)
+
+
+def set_gcn_dual(on: bool) -> None:
+    """A/B switch (tests, tools): with False gcn2_dual makes two gcn2 calls and the sampled step its two separate GNN forwards."""
+    global _gcn_dual_enabled
+    _gcn_dual_enabled = bool(on)
+
+
+def gcn_dual_enabled() -> bool:
+    return _gcn_dual_enabled
+
+
+def gcn_dual_ok(gr_a, gr_b, H: int, C: int) -> bool:
+    """sgs_gcn_dual_ok: the two graphs' forwards can share their launches (both on the row-block path, one kernel variant)."""
+    return (gr_a.N == gr_b.N and bool(_lib.lib().sgs_gcn_dual_ok(gr_a.N, gr_a.n_edges, gr_b.n_edges, int(H), int(C)))
+            and _pair_ok(gr_a, H, C) and _pair_ok(gr_b, H, C))          # (as _GCN2 decides `fused`: its backward keeps rows of width C in LDS)
+
+
+def _gcn2_dual_forward(xl1, b1, W2, b2, nm_a, nm_b, act, p, seed_a, seed_b, site):
+    """Both graphs' two layers in two launches (sgs_spmm_csr_next_dual, sgs_spmm_csr_dual): ((h, xl2, out) of a, the same of b), each
+    bitwise what _GCN2's fused forward computes for that graph alone."""
+    L = _lib.lib()
+    GCN_DUAL_FORWARDS["shared"] += 1
+    ga, gb = nm_a.graph, nm_b.graph
+    N, H = xl1.shape
+    C = W2.shape[0]
+    f32 = dict(dtype=torch.float32, device=xl1.device)
+    h_a, xl2_a, out_a = torch.empty(N, H, **f32), torch.empty(N, C, **f32), torch.empty(N, C, **f32)
+    h_b, xl2_b, out_b = torch.empty(N, H, **f32), torch.empty(N, C, **f32), torch.empty(N, C, **f32)
+    _lib.check(L.sgs_spmm_csr_next_dual(_ptr(xl1, torch.float32), N, H, _ptr(b1), act, float(p), site, _ptr(W2, torch.float32), C,
+                                        ga.n_edges, _ptr(ga.in_ptr), _ptr(ga.in_src), _ptr(nm_a.what_in), _ptr(nm_a.what_loop), seed_a,
+                                        _ptr(h_a), _ptr(xl2_a),
+                                        gb.n_edges, _ptr(gb.in_ptr), _ptr(gb.in_src), _ptr(nm_b.what_in), _ptr(nm_b.what_loop), seed_b,
+                                        _ptr(h_b), _ptr(xl2_b), _stream()), "sgs_spmm_csr_next_dual")
+    _lib.check(L.sgs_spmm_csr_dual(_ptr(xl2_a), _ptr(xl2_b), N, C, _ptr(b2), ACT_NONE, 0.0, 0,
+                                   ga.n_edges, _ptr(ga.in_ptr), _ptr(ga.in_src), _ptr(nm_a.what_in), _ptr(nm_a.what_loop), 0, _ptr(out_a),
+                                   gb.n_edges, _ptr(gb.in_ptr), _ptr(gb.in_src), _ptr(nm_b.what_in), _ptr(nm_b.what_loop), 0, _ptr(out_b),
+                                   _stream()), "sgs_spmm_csr_dual")
+    return (h_a, xl2_a, out_a), (h_b, xl2_b, out_b)
+
+
+def gcn2_dual(x, W1, b1, W2, b2, nm_a: Norm, nm_b: Norm, act=ACT_RELU, p=0.0, seed_a=0, seed_b=0, site=0, xl1=None):
+    """gcn2 over two graphs of the same nodes, (out_a, out_b, xl1): out_a = gcn2(..., nm_a, seed_a), out_b = gcn2(..., nm_b, seed_b), bitwise,
+    with the same autograd (to x, W1, b1, W2, b2 from both and, through nm_a.handle, to branch a's edge weights; nm_b carries no handle).
+    Where the two forwards can share their launches (gcn_dual_ok, contiguous operands, the switch on) they run as two launches instead of
+    four and each branch gets _GCN2's node over its precomputed forward; elsewhere these ARE the two gcn2 calls.
+    Two nodes, not one: a node holding both branches would have nm_a.handle among its inputs, and a backward from out_b alone would then
+    run everything behind the handle (the normalisation's and the scorer's backward) on zero-filled gradients -- the two-node graph leaves
+    those parameters' .grad None, which the optimisers rely on."""
+    _need_gpu(x, W1, b1, W2, b2)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != nm_a.graph.N or x.shape[0] != nm_b.graph.N:
+        raise RuntimeError("gcn2_dual: x must be float32 [N, F] over both graphs' N nodes")
+    if nm_b.handle is not None:
+        raise RuntimeError("gcn2_dual: branch b takes no edge-weight gradient (nm_b.handle must be None)")
+    H, C = W1.shape[0], W2.shape[0]
+    pre_a = pre_b = None
+    if (_gcn_dual_enabled and gcn_dual_ok(nm_a.graph, nm_b.graph, H, C) and W2.is_contiguous() and W2.shape[1] == H
+            and (xl1 is None or xl1.is_contiguous())):
+        with torch.no_grad():
+            if xl1 is None:
+                xl1 = _x_wt(x, W1).contiguous()
+            pre_a, pre_b = _gcn2_dual_forward(xl1, b1, W2, b2, nm_a, nm_b, act, float(p), int(seed_a), int(seed_b), int(site))
+    out_a, xl1 = _GCN2.apply(x, W1, b1, W2, b2, nm_a.handle, nm_a, act, float(p), int(seed_a), int(site), xl1, pre_a)
+    out_b, xl1 = _GCN2.apply(x, W1, b1, W2, b2, None, nm_b, act, float(p), int(seed_b), int(site), xl1, pre_b)
+    return out_a, out_b, xl1
 
 
 # ------------------------------------------------------------------ batched ensemble evaluation (forward only, GCN head)

@@ -87,6 +87,18 @@ def sampled_prefix(args, batch, q, noise=None):
     return rs
 
 
+def _gcn_dual_applies(args, model, batch, ei_learned, ei_random, forked) -> bool:
+    """The sampled step's two GNN forwards run as GNNModel.forward_pair: conditional runs with the GCN head, not forked onto a side
+    stream, switched on (ops.set_gcn_dual / args.sgs_gcn_dual) and of a shape whose two forwards can share launches (ops.gcn_dual_ok)."""
+    from .model import GNNModel
+    if not args.conditional or forked or ei_random is None or type(model) is not GNNModel:
+        return False
+    if not (ops.gcn_dual_enabled() and getattr(args, "sgs_gcn_dual", True)):
+        return False
+    N = batch.x.shape[0]
+    return ops.gcn_dual_ok(ops.get_graph(ei_learned, N), ops.get_graph(ei_random, N), model.gcn1.out_channels, model.gcn2.out_channels)
+
+
 def sampled_forward(pipeline, args, model, batch, q, use_checkpoint=False, noise=None, side_stream=None, prefix=None,
                     gate_publish=None) -> SampledForward:
     """training_hybrid.py:44-101 (ST 41-90, TP 41-92) up to the gate's inputs: prior draw, pass-1 scores, learned
@@ -144,7 +156,11 @@ def sampled_forward(pipeline, args, model, batch, q, use_checkpoint=False, noise
         st.edge_probs_for_loss = scorer(batch.x, smp.edge_index).squeeze()
     if forked:
         main_stream.wait_stream(side_stream)                          # join (also publishes the memoised x W^T of the GNN's first layer)
-    st.learned_out = model(batch, smp.edge_index, st.edge_probs_for_loss)
+    if _gcn_dual_applies(args, model, batch, smp.edge_index, st.rsei, forked):
+        # the learned and the random forward share their two SpMM launches (ops.gcn2_dual); same values, same seeds
+        st.learned_out, st.random_out = model.forward_pair(batch, smp.edge_index, st.edge_probs_for_loss, st.rsei)
+    else:
+        st.learned_out = model(batch, smp.edge_index, st.edge_probs_for_loss)
 
     st.cbuf = None
     if args.conditional:
