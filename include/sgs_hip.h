@@ -1066,6 +1066,24 @@ int sgs_adam_step_multi(const int64_t* desc_host, const float* hyper_host, int64
  *   is one launch for all draws (draw index in the grid).  Outputs: mask [D, E] u8, sampled_eid [D, q] (ascending), optional
  *   sampled_edge_index [D, 2, q], stats [D, 4] (optional unless st_weights), optional st_weights [D, q] (sgs_st_weights_fwd's values,
  *   mode LEARNED).  1 <= D <= 65535.  Not available under sgs_dyn_edges_set.
+ * sgs_sample_topq_multi_cover: D draws of sgs_sample_topq_cover over ONE candidate set (the node-covering rule described at that entry
+ *   point).  Arguments as sgs_sample_topq_multi plus N, in_ptr [N + 1], in_src / in_eid [E] (the destination-row CSR of the candidate
+ *   graph, as sgs_sample_topq_cover takes it) and cover_info [D, 2] int32 (may be NULL) = {M_d, min(M_d, q)} per draw.  Row d of mask,
+ *   sampled_eid, sampled_edge_index, stats, st_weights and cover_info is bitwise what sgs_sample_topq_cover (followed by
+ *   sgs_st_weights_fwd) returns for stream id stream_id0 + d or noise row d, on the small- and the large-E path: stats[d][2] is the
+ *   threshold with the flag bit cleared, stats[d][3] the ties taken at the boosted threshold.  Launches: sgs_sample_topq_multi's plus TWO
+ *   for all draws.  After the key pass one draw-grouped forced-edge kernel (grid: row blocks x ceil(D / G)) walks the CSR once per group
+ *   of G draws: a lane reads an entry (in_src[j], in_eid[j]) once, gathers that edge's key from each of the group's stored key rows
+ *   (G independent gathers in flight), keeps one 64-bit (key bits << 32 | ~edge id) maximum per draw, sets bit 31 of each draw's winner
+ *   in that draw's key row and moves its count in that draw's top-digit histogram from bin b to bin b + 1024 (integer atomics, first
+ *   aggregated per workgroup and draw in LDS).  Lanes per row (sgs_sample_topq_cover_variant), the hand-over of long rows to the whole
+ *   workgroup and the bounds checks are the single-draw kernel's.  Before the straight-through weights one finishing launch
+ *   (blockIdx.y = draw) writes cover_info and takes the flag bit off the reported thresholds.  q == 0 / q == E: M depends on neither keys
+ *   nor draw, so the single-draw key-less count runs once and every row of cover_info gets the same pair.  E == 0 returns at once and
+ *   writes nothing.  All counting is integer: results do not depend on G or the launch geometry.  Refused under sgs_dyn_edges_set;
+ *   1 <= D <= 65535, E < 2^31 and N < 2^31.  Workspace: sgs_sample_topq_multi's plus 1024 counts per draw.
+ *   sgs_sample_topq_multi_cover_group_set(G): draws per workgroup of the grouped kernel, 1, 2 or 4, or 0 for the built-in default
+ *   (process-wide).  A measurement hook (tools/eval_cover_ab.py): results are bitwise the same for every G.
  * sgs_graph_filter_multi: the in-CSR + loop_eid of each draw's subgraph (D masks / sampled_eid over the parent's cached in-CSR); every
  *   draw's arrays equal sgs_graph_filter's.  in_ptr [D, N+1], in_src / in_eid [D, q], loop_eid [D, N].  No out-CSR.
  * sgs_gcn_norm_fwd_multi: sgs_gcn_norm_fwd's in-direction outputs per draw (dis, loopw, what_loop [D, N], what_in [D, q]); w [D, q] or
@@ -1101,6 +1119,13 @@ size_t sgs_sample_topq_multi_workspace_bytes(int64_t E, int64_t D);
 int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
                           uint64_t stream_id0, int64_t D, int64_t E, int64_t q, const int64_t* edge_index, uint8_t* mask, int64_t* sampled_eid,
                           int64_t* sampled_edge_index, float* stats, float* st_weights, void* ws, size_t ws_bytes, sgs_stream_t stream);
+size_t sgs_sample_topq_multi_cover_workspace_bytes(int64_t E, int64_t N, int64_t D);
+int sgs_sample_topq_multi_cover_group_set(int G);
+int sgs_sample_topq_multi_cover(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
+                                uint64_t stream_id0, int64_t D, int64_t E, int64_t q, const int64_t* edge_index, int64_t N,
+                                const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, uint8_t* mask, int64_t* sampled_eid,
+                                int64_t* sampled_edge_index, float* stats, float* st_weights, int32_t* cover_info, void* ws, size_t ws_bytes,
+                                sgs_stream_t stream);
 size_t sgs_graph_filter_multi_workspace_bytes(int64_t E_parent, int64_t N, int64_t D);
 int sgs_graph_filter_multi(const int32_t* pin_ptr, const int32_t* pin_src, const int32_t* pin_eid, int64_t E_parent, int64_t N, int64_t D,
                            const uint8_t* mask, const int64_t* sampled_eid, int64_t q, int32_t* in_ptr, int32_t* in_src, int32_t* in_eid,

@@ -825,8 +825,8 @@ __global__ void __launch_bounds__(kCoverThreads) cover_rows(uint32_t* __restrict
 }
 
 // One workgroup, last launch of a covering draw: M from the per-workgroup counts, the flag bit off the reported threshold.
-__global__ void __launch_bounds__(kThreads) cover_finish(const uint32_t* __restrict__ mcnt, int nb, int64_t q, float* __restrict__ stats,
-                                                        int32_t* __restrict__ cover_info) {
+__device__ __forceinline__ void cover_finish_body(const uint32_t* __restrict__ mcnt, int nb, int64_t q, float* __restrict__ stats,
+                                                  int32_t* __restrict__ cover_info) {
     __shared__ int red[kThreads / 64];
     int m = 0;
     for (int i = threadIdx.x; i < nb; i += kThreads) m += static_cast<int>(mcnt[i]);
@@ -842,6 +842,10 @@ __global__ void __launch_bounds__(kThreads) cover_finish(const uint32_t* __restr
         }
         if (stats) stats[2] = __uint_as_float(__float_as_uint(stats[2]) & 0x7FFFFFFFu);
     }
+}
+__global__ void __launch_bounds__(kThreads) cover_finish(const uint32_t* __restrict__ mcnt, int nb, int64_t q, float* __restrict__ stats,
+                                                        int32_t* __restrict__ cover_info) {
+    cover_finish_body(mcnt, nb, q, stats, cover_info);
 }
 
 // counts[0] = #keys > threshold, counts[1] = #keys == threshold in this shard (before the scan).
@@ -1005,6 +1009,7 @@ __global__ void st_bwd_sparse(const float* __restrict__ p, const float* __restri
 // aligned) rather than recomputing them from the hash in the three later passes: at partition scale the D x 4E bytes stay in the
 // Infinity Cache, and a recompute would put three more Philox evaluations per key and draw on passes that are otherwise pure loads.
 constexpr int kMultiG = 4;                   // draws per key-pass workgroup: 4 x 8 KiB of LDS histograms beside 16 waves
+constexpr int kMultiCoverG = 2;              // draws per workgroup of multi_cover_rows (1, 2 or 4; measured: DESIGN.md section 5)
 
 __host__ __device__ inline int64_t multi_key_stride(int64_t E) { return (E + 63) & ~int64_t(63); }
 
@@ -1166,6 +1171,130 @@ __global__ void multi_st_fwd(const float* __restrict__ p, const float* __restric
     st_fwd_body<HAS_PRIOR>(p, prior, one_minus_c, c, stats + 4 * d, eid + d * q, q, w + d * q);
 }
 
+// ---------------------------------------------------------------- node-covering draws of the batched pass (sgs_sample_topq_multi_cover)
+// cover_rows for a GROUP of G draws (blockIdx.y): the stored key rows keys + d * ks share one candidate graph, so a lane reads a CSR
+// entry (in_src[j], in_eid[j]) once and gathers that edge's key from each of the group's rows -- G independent gathers in flight per
+// entry where the single-draw kernel has one -- with one 64-bit (bits << 32 | ~eid) running maximum per draw in registers.  The winner of
+// draw d gets bit 31 in d's own key row and moves one count of d's digit-0 histogram (hist + d * hs) from bin b to bin b + 1024, first
+// aggregated per (workgroup, draw) in LDS (4 KiB per draw of the group), flushed as integer atomicSub / atomicAdd pairs.  Rows, lanes
+// per row, the hand-over of long rows to the whole workgroup, the bounds checks and the grid-stride are cover_rows'; per draw the
+// comparisons are the same integers, so row d of the keys and histograms is bitwise what cover_rows leaves for that draw, whatever G.
+// The last group is partial: its spare slots re-read the group's last row (no branch around the gathers) and force nothing.
+template <int G>
+__device__ __forceinline__ void cover_cand_group(uint32_t* const (&krow)[G], uint32_t E, const int32_t* __restrict__ in_src,
+                                                 const int32_t* __restrict__ in_eid, int64_t j, int64_t row, unsigned long long (&best)[G]) {
+    const uint32_t eid = static_cast<uint32_t>(in_eid[j]);
+    if (static_cast<int64_t>(in_src[j]) == row || eid >= E) return;
+    uint32_t bits[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) bits[g] = krow[g][eid];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const unsigned long long c = (static_cast<unsigned long long>(bits[g]) << 32) | static_cast<uint32_t>(~eid);
+        best[g] = c > best[g] ? c : best[g];
+    }
+}
+template <int LPR, int G>
+__global__ void __launch_bounds__(kCoverThreads) multi_cover_rows(uint32_t* keys, int64_t ks, int64_t E, int D, int64_t N,
+                                                                 const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src,
+                                                                 const int32_t* __restrict__ in_eid, uint32_t* __restrict__ hist, int64_t hs,
+                                                                 uint32_t* __restrict__ mcnt) {
+    constexpr int RPB = kCoverThreads / LPR;
+    constexpr int kLong = kCoverLongPerLane * LPR;
+    __shared__ uint32_t moved[G][kBins / 2];
+    __shared__ uint32_t longrow[RPB];
+    __shared__ uint32_t nlong, nforced[G];
+    __shared__ unsigned long long wbest[G][kCoverThreads / 64];
+    const int d0 = blockIdx.y * G;
+    const int gn = (D - d0) < G ? (D - d0) : G;           // draws of this group (>= 1: the grid has ceil(D / G) groups)
+    uint32_t* krow[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) krow[g] = keys + static_cast<int64_t>(d0 + (g < gn ? g : gn - 1)) * ks;
+    for (int i = threadIdx.x; i < G * (kBins / 2); i += kCoverThreads) (&moved[0][0])[i] = 0;
+    if (threadIdx.x < G) nforced[threadIdx.x] = 0;
+    if (threadIdx.x == 0) nlong = 0;
+    __syncthreads();
+    const uint32_t E32 = static_cast<uint32_t>(E);
+    const int sub = threadIdx.x % LPR, grp = threadIdx.x / LPR;
+    for (int64_t base = static_cast<int64_t>(blockIdx.x) * RPB; base < N; base += static_cast<int64_t>(gridDim.x) * RPB) {
+        const int64_t row = base + grp;
+        unsigned long long best[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) best[g] = 0ull;
+        if (row < N) {
+            int64_t s = in_ptr[row], t = in_ptr[row + 1];
+            if (s < 0) s = 0;
+            if (t > E) t = E;
+            if (t - s > kLong) {
+                if (sub == 0) longrow[atomicAdd(&nlong, 1u)] = static_cast<uint32_t>(row);
+            } else {
+                for (int64_t j = s + sub; j < t; j += LPR) cover_cand_group<G>(krow, E32, in_src, in_eid, j, row, best);
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+#pragma unroll
+            for (int o = LPR / 2; o > 0; o >>= 1) {
+                const unsigned long long c = __shfl_xor(best[g], o, 64);
+                best[g] = c > best[g] ? c : best[g];
+            }
+        }
+        if (sub == 0) {
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+                if (g < gn && best[g]) cover_boost(best[g], krow[g], moved[g], &nforced[g]);
+        }
+        __syncthreads();
+        const uint32_t nl = nlong;
+        for (uint32_t l = 0; l < nl; ++l) {           // (uniform: every thread reads the same nlong)
+            const int64_t lrow = longrow[l];
+            int64_t s = in_ptr[lrow], t = in_ptr[lrow + 1];
+            if (s < 0) s = 0;
+            if (t > E) t = E;
+            unsigned long long b[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) b[g] = 0ull;
+            for (int64_t j = s + threadIdx.x; j < t; j += kCoverThreads) cover_cand_group<G>(krow, E32, in_src, in_eid, j, lrow, b);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const unsigned long long c = __shfl_xor(b[g], o, 64);
+                    b[g] = c > b[g] ? c : b[g];
+                }
+                if ((threadIdx.x & 63) == 0) wbest[g][threadIdx.x >> 6] = b[g];
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    unsigned long long v = b[g];
+                    for (int w = 1; w < kCoverThreads / 64; ++w) v = wbest[g][w] > v ? wbest[g][w] : v;
+                    if (g < gn && v) cover_boost(v, krow[g], moved[g], &nforced[g]);
+                }
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) nlong = 0;
+        __syncthreads();
+    }
+    for (int g = 0; g < gn; ++g) {
+        uint32_t* h = hist + static_cast<int64_t>(d0 + g) * hs;
+        for (int i = threadIdx.x; i < kBins / 2; i += kCoverThreads) {
+            const uint32_t v = moved[g][i];
+            if (v) { atomicSub(&h[i], v); atomicAdd(&h[i + kBins / 2], v); }
+        }
+    }
+    if (static_cast<int>(threadIdx.x) < gn) mcnt[static_cast<int64_t>(d0 + threadIdx.x) * kCoverGrid + blockIdx.x] = nforced[threadIdx.x];
+}
+
+// cover_finish for draw blockIdx.y; ms = kCoverGrid, or 0 when one key-less cover_rows counted M for all draws (degenerate q)
+__global__ void __launch_bounds__(kThreads) multi_cover_finish(const uint32_t* __restrict__ mcnt, int64_t ms, int nb, int64_t q,
+                                                              float* __restrict__ stats, int32_t* __restrict__ cover_info) {
+    const int64_t d = blockIdx.y;
+    cover_finish_body(mcnt + d * ms, nb, q, stats ? stats + 4 * d : nullptr, cover_info ? cover_info + 2 * d : nullptr);
+}
+
 }  // namespace
 }  // namespace sgs
 
@@ -1222,6 +1351,16 @@ struct CoverArgs {
     int32_t* info;
     int lanes, grid;      // sgs_sample_topq_cover_variant of the shape; workgroups of cover_rows
 };
+// node-covering draws: lanes per row and workgroups of the forced-edge kernels for this shape
+static CoverArgs cover_args(int64_t N, int64_t E, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, int32_t* info) {
+    CoverArgs c{N, in_ptr, in_src, in_eid, info, sgs_sample_topq_cover_variant(N, E), 1};
+    if (N > 0) {
+        const int64_t nb = cdiv(N, kCoverThreads / c.lanes);
+        c.grid = static_cast<int>(nb < kCoverGrid ? nb : kCoverGrid);
+    }
+    return c;
+}
+
 // keys == nullptr: count M only (degenerate draws); hist0 == nullptr: no histogram to correct
 static void launch_cover_rows(const CoverArgs& c, uint32_t* keys, int64_t E, uint32_t* hist0, uint32_t* mcnt, const int64_t* dynE,
                               hipStream_t stream) {
@@ -1370,11 +1509,7 @@ int sgs_sample_topq_cover(int mode, const float* p, const float* prior, double d
                           int64_t N, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid,
                           uint8_t* mask, int64_t* sampled_eid, int64_t* sampled_edge_index, float* sampled_p,
                           float* stats, float* keys_out, int32_t* cover_info, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    CoverArgs c{N, in_ptr, in_src, in_eid, cover_info, sgs_sample_topq_cover_variant(N, E), 1};
-    if (N > 0) {
-        const int64_t nb = cdiv(N, kCoverThreads / c.lanes);
-        c.grid = static_cast<int>(nb < kCoverGrid ? nb : kCoverGrid);
-    }
+    const CoverArgs c = cover_args(N, E, in_ptr, in_src, in_eid, cover_info);
     return sample_topq_impl("sgs_sample_topq_cover", &c, mode, p, prior, degree_bias_coef, noise, seed, stream_id, E, q, edge_index, mask,
                             sampled_eid, sampled_edge_index, sampled_p, stats, keys_out, ws, ws_bytes, stream_);
 }
@@ -1567,6 +1702,27 @@ int sgs_st_weights_bwd(const float* p, const float* prior, double degree_bias_co
 
 }  // extern "C"
 
+// draws per workgroup of multi_cover_rows (sgs_sample_topq_multi_cover_group_set); the result does not depend on it
+static int g_multi_cover_group = kMultiCoverG;
+template <int G>
+static void launch_multi_cover_rows_g(const CoverArgs& c, uint32_t* keys, int64_t ks, int64_t E, int64_t D, uint32_t* hist, int64_t hs,
+                                    uint32_t* mcnt, hipStream_t stream) {
+    const dim3 grid(static_cast<unsigned>(c.grid), static_cast<unsigned>(cdiv(D, G))), blk(kCoverThreads);
+    const int Di = static_cast<int>(D);
+    if (c.lanes == 4)
+        hipLaunchKernelGGL((multi_cover_rows<4, G>), grid, blk, 0, stream, keys, ks, E, Di, c.N, c.in_ptr, c.in_src, c.in_eid, hist, hs, mcnt);
+    else if (c.lanes == 16)
+        hipLaunchKernelGGL((multi_cover_rows<16, G>), grid, blk, 0, stream, keys, ks, E, Di, c.N, c.in_ptr, c.in_src, c.in_eid, hist, hs, mcnt);
+    else
+        hipLaunchKernelGGL((multi_cover_rows<64, G>), grid, blk, 0, stream, keys, ks, E, Di, c.N, c.in_ptr, c.in_src, c.in_eid, hist, hs, mcnt);
+}
+static void launch_multi_cover_rows(const CoverArgs& c, uint32_t* keys, int64_t ks, int64_t E, int64_t D, uint32_t* hist, int64_t hs,
+                                    uint32_t* mcnt, hipStream_t stream) {
+    if (g_multi_cover_group == 1) launch_multi_cover_rows_g<1>(c, keys, ks, E, D, hist, hs, mcnt, stream);
+    else if (g_multi_cover_group == 2) launch_multi_cover_rows_g<2>(c, keys, ks, E, D, hist, hs, mcnt, stream);
+    else launch_multi_cover_rows_g<4>(c, keys, ks, E, D, hist, hs, mcnt, stream);
+}
+
 extern "C" {
 
 size_t sgs_sample_topq_multi_workspace_bytes(int64_t E, int64_t D) {
@@ -1582,27 +1738,47 @@ size_t sgs_sample_topq_multi_workspace_bytes(int64_t E, int64_t D) {
            + carve_bytes(2 * D, sizeof(SelPart)) + 256;
 }
 
-int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
-                          uint64_t stream_id0, int64_t D, int64_t E, int64_t q, const int64_t* edge_index, uint8_t* mask, int64_t* sampled_eid,
-                          int64_t* sampled_edge_index, float* stats, float* st_weights, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+size_t sgs_sample_topq_multi_cover_workspace_bytes(int64_t E, int64_t N, int64_t D) {
+    (void)N;       // as sgs_sample_topq_cover_workspace_bytes: kCoverGrid per-workgroup counts, here per draw
+    if (D < 1) D = 1;
+    return sgs_sample_topq_multi_workspace_bytes(E, D) + carve_bytes(static_cast<size_t>(kCoverGrid * D), 4);
+}
+
+
+int sgs_sample_topq_multi_cover_group_set(int G) {
+    SGS_REQUIRE(G == 0 || G == 1 || G == 2 || G == 4, SGS_EINVAL, "sgs_sample_topq_multi_cover_group_set: G=%d (need 1, 2 or 4, or 0 for the default)", G);
+    g_multi_cover_group = G ? G : kMultiCoverG;
+    return SGS_OK;
+}
+
+// sgs_sample_topq_multi (cover == nullptr) and sgs_sample_topq_multi_cover
+static int sample_topq_multi_impl(const char* fn, const CoverArgs* cover, int mode, const float* p, const float* prior, double degree_bias_coef,
+                                  const float* noise, uint64_t seed, uint64_t stream_id0, int64_t D, int64_t E, int64_t q,
+                                  const int64_t* edge_index, uint8_t* mask, int64_t* sampled_eid, int64_t* sampled_edge_index, float* stats,
+                                  float* st_weights, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(mode == SGS_SAMPLE_LEARNED || mode == SGS_SAMPLE_PRIOR, SGS_EINVAL, "sgs_sample_topq_multi: bad mode %d", mode);
-    SGS_REQUIRE(D >= 1 && D <= 65535, SGS_EINVAL, "sgs_sample_topq_multi: D=%lld draws (need 1 <= D <= 65535)", (long long)D);
-    SGS_REQUIRE(E >= 0 && q >= 0, SGS_EINVAL, "sgs_sample_topq_multi: negative size (E=%lld q=%lld)", (long long)E, (long long)q);
-    SGS_REQUIRE(q <= E, SGS_EINVAL,
-                "sgs_sample_topq_multi: cannot sample q=%lld > E=%lld edges without replacement", (long long)q, (long long)E);
-    SGS_REQUIRE(E < (int64_t(1) << 32), SGS_EINVAL, "sgs_sample_topq_multi: E=%lld exceeds 2^32-1", (long long)E);
+    SGS_REQUIRE(mode == SGS_SAMPLE_LEARNED || mode == SGS_SAMPLE_PRIOR, SGS_EINVAL, "%s: bad mode %d", fn, mode);
+    SGS_REQUIRE(D >= 1 && D <= 65535, SGS_EINVAL, "%s: D=%lld draws (need 1 <= D <= 65535)", fn, (long long)D);
+    SGS_REQUIRE(E >= 0 && q >= 0, SGS_EINVAL, "%s: negative size (E=%lld q=%lld)", fn, (long long)E, (long long)q);
+    SGS_REQUIRE(q <= E, SGS_EINVAL, "%s: cannot sample q=%lld > E=%lld edges without replacement", fn, (long long)q, (long long)E);
+    SGS_REQUIRE(E < (int64_t(1) << 32), SGS_EINVAL, "%s: E=%lld exceeds 2^32-1", fn, (long long)E);
+    if (cover) {
+        SGS_REQUIRE(cover->N >= 0, SGS_EINVAL, "%s: negative node count (N=%lld)", fn, (long long)cover->N);
+        SGS_REQUIRE(E == 0 || (cover->in_ptr && cover->in_src && cover->in_eid), SGS_EINVAL,
+                    "%s: null destination CSR (in_ptr / in_src / in_eid) with E=%lld", fn, (long long)E);
+        SGS_REQUIRE(E < (int64_t(1) << 31) && cover->N < (int64_t(1) << 31), SGS_EINVAL,
+                    "%s: E=%lld, N=%lld exceed the int32 CSR", fn, (long long)E, (long long)cover->N);
+    }
     if (E == 0) return SGS_OK;
-    SGS_REQUIRE(mask, SGS_EINVAL, "sgs_sample_topq_multi: null mask");
-    SGS_REQUIRE(p || (mode == SGS_SAMPLE_LEARNED && !prior), SGS_EINVAL,
-                "sgs_sample_topq_multi: p == NULL (uniform weights) needs mode LEARNED and no prior");
-    SGS_REQUIRE(!sampled_edge_index || edge_index, SGS_EINVAL, "sgs_sample_topq_multi: edge_index required for sampled_edge_index");
+    SGS_REQUIRE(mask, SGS_EINVAL, "%s: null mask", fn);
+    SGS_REQUIRE(p || (mode == SGS_SAMPLE_LEARNED && !prior), SGS_EINVAL, "%s: p == NULL (uniform weights) needs mode LEARNED and no prior", fn);
+    SGS_REQUIRE(!sampled_edge_index || edge_index, SGS_EINVAL, "%s: edge_index required for sampled_edge_index", fn);
     SGS_REQUIRE(!st_weights || (p && sampled_eid && stats && mode == SGS_SAMPLE_LEARNED), SGS_EINVAL,
-                "sgs_sample_topq_multi: st_weights needs p, sampled_eid, stats and mode LEARNED");
-    SGS_REQUIRE(!dyn_edges_ptr(), SGS_EINVAL, "sgs_sample_topq_multi: not available under a dynamic edge count (sgs_dyn_edges_set)");
-    SGS_REQUIRE(ws && ws_bytes >= sgs_sample_topq_multi_workspace_bytes(E, D), SGS_EWORKSPACE,
-                "sgs_sample_topq_multi: workspace too small (%zu < %zu)", ws_bytes, sgs_sample_topq_multi_workspace_bytes(E, D));
-    SGS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, SGS_EINVAL, "sgs_sample_topq_multi: workspace must be 256-B aligned");
+                "%s: st_weights needs p, sampled_eid, stats and mode LEARNED", fn);
+    SGS_REQUIRE(!dyn_edges_ptr(), SGS_EINVAL, "%s: not available under a dynamic edge count (sgs_dyn_edges_set)", fn);
+    const size_t ws_need = cover ? sgs_sample_topq_multi_cover_workspace_bytes(E, cover->N, D) : sgs_sample_topq_multi_workspace_bytes(E, D);
+    SGS_REQUIRE(ws && ws_bytes >= ws_need, SGS_EWORKSPACE, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, ws_need);
+    SGS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, SGS_EINVAL, "%s: workspace must be 256-B aligned", fn);
 
     const int64_t nblk = cdiv(E, kChunk), cs = nblk + 1, ks = multi_key_stride(E);
     Carver cv(ws);
@@ -1614,6 +1790,7 @@ int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double d
     SelectState* st = cv.take<SelectState>(D);
     uint2* cnt = cv.take<uint2>(cs * D);
     SelPart* sel = cv.take<SelPart>(2 * D);
+    uint32_t* mcnt = cover ? cv.take<uint32_t>(kCoverGrid * D) : nullptr;      // covering draws: forced edges per (draw, workgroup)
     const unsigned Du = static_cast<unsigned>(D);
     const dim3 blk(kThreads);
     const float one_minus_c = static_cast<float>(1.0 - degree_bias_coef);
@@ -1634,11 +1811,14 @@ int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double d
             hipLaunchKernelGGL(multi_keys_hist0<SGS_SAMPLE_PRIOR>, kgrid, kblk, 0, stream, p, static_cast<const float*>(nullptr), noise, seed,
                                stream_id0, epoch_ptr(), E, static_cast<int>(D), one_minus_c, c, part2, part, nblk, scal, keys, ks, hist);
         }
+        if (cover) launch_multi_cover_rows(*cover, keys, ks, E, D, hist, 3 * kBins, mcnt, stream);
         hipLaunchKernelGGL(multi_small_hist_next, grid, blk, 0, stream, keys, ks, E, kShift1, kMask1, kShift0, 1, q32, hist, sel);
         hipLaunchKernelGGL(multi_small_hist_next, grid, blk, 0, stream, keys, ks, E, kShift2, kMask2, kShift1, 0, q32, hist, sel);
         hipLaunchKernelGGL(multi_small_count, grid, blk, 0, stream, keys, ks, E, q32, hist, sel, st, cnt, cs, scal, stats);
         hipLaunchKernelGGL(multi_small_compact, grid, blk, 0, stream, keys, ks, E, q, st, cnt, cs, p, edge_index, mask, sampled_eid,
                            sampled_edge_index, static_cast<float*>(nullptr));
+        // (before multi_st_fwd: the straight-through weights read the threshold the single call reports, flag bit off)
+        if (cover) hipLaunchKernelGGL(multi_cover_finish, dim3(1, Du), blk, 0, stream, mcnt, int64_t(kCoverGrid), cover->grid, q, stats, cover->info);
     } else {
         if (int rc = zero_async(scal, static_cast<size_t>(reinterpret_cast<char*>(st + D) - reinterpret_cast<char*>(scal)), stream)) return rc;
         const dim3 grid1(static_cast<unsigned>(nblk));
@@ -1654,6 +1834,8 @@ int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double d
         if (q == 0 || q == E) {
             hipLaunchKernelGGL(multi_select_all, dim3(static_cast<unsigned>(cdiv(E, 256)), Du), dim3(256), 0, stream, E, p, edge_index, mask,
                                sampled_eid, sampled_edge_index, static_cast<float*>(nullptr), static_cast<uint8_t>(q == E ? 1 : 0));
+            // M does not depend on the keys or on the draw: one key-less cover_rows, its counts read by every draw's finishing workgroup
+            if (cover) launch_cover_rows(*cover, nullptr, E, nullptr, mcnt, nullptr, stream);
         } else {
             const dim3 hgrid(static_cast<unsigned>(nblk < kHistGrid ? nblk : kHistGrid), Du), grid(static_cast<unsigned>(nblk), Du), one(1, Du);
             const uint32_t q32 = static_cast<uint32_t>(q);
@@ -1663,6 +1845,7 @@ int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double d
             else
                 hipLaunchKernelGGL(multi_keys_hist0_large<SGS_SAMPLE_PRIOR>, hgrid, blk, 0, stream, p, static_cast<const float*>(nullptr), noise,
                                    seed, stream_id0, epoch_ptr(), E, one_minus_c, c, scal, keys, ks, hist);
+            if (cover) launch_multi_cover_rows(*cover, keys, ks, E, D, hist, kBins, mcnt, stream);
             hipLaunchKernelGGL(multi_select_digit, one, blk, 0, stream, hist, kShift0, 1, q32, st);
             hipLaunchKernelGGL(multi_hist_next, hgrid, blk, 0, stream, keys, ks, E, kShift1, kMask1, kShift0, st, hist);
             hipLaunchKernelGGL(multi_select_digit, one, blk, 0, stream, hist, kShift1, 0, q32, st);
@@ -1674,6 +1857,9 @@ int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double d
                                sampled_edge_index, static_cast<float*>(nullptr));
         }
         if (stats) hipLaunchKernelGGL(multi_write_stats, dim3(1, Du), dim3(1), 0, stream, scal, st, stats);
+        if (cover)
+            hipLaunchKernelGGL(multi_cover_finish, dim3(1, Du), blk, 0, stream, mcnt, (q == 0 || q == E) ? int64_t(0) : int64_t(kCoverGrid),
+                               cover->grid, q, stats, cover->info);
     }
     if (st_weights && q > 0) {
         const dim3 g(static_cast<unsigned>(cdiv(q, 256)), Du);
@@ -1684,6 +1870,23 @@ int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double d
     }
     SGS_LAUNCH_OK();
     return SGS_OK;
+}
+
+int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
+                          uint64_t stream_id0, int64_t D, int64_t E, int64_t q, const int64_t* edge_index, uint8_t* mask, int64_t* sampled_eid,
+                          int64_t* sampled_edge_index, float* stats, float* st_weights, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    return sample_topq_multi_impl("sgs_sample_topq_multi", nullptr, mode, p, prior, degree_bias_coef, noise, seed, stream_id0, D, E, q, edge_index,
+                                  mask, sampled_eid, sampled_edge_index, stats, st_weights, ws, ws_bytes, stream_);
+}
+
+int sgs_sample_topq_multi_cover(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
+                                uint64_t stream_id0, int64_t D, int64_t E, int64_t q, const int64_t* edge_index, int64_t N,
+                                const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, uint8_t* mask, int64_t* sampled_eid,
+                                int64_t* sampled_edge_index, float* stats, float* st_weights, int32_t* cover_info, void* ws, size_t ws_bytes,
+                                sgs_stream_t stream_) {
+    const CoverArgs c = cover_args(N, E, in_ptr, in_src, in_eid, cover_info);
+    return sample_topq_multi_impl("sgs_sample_topq_multi_cover", &c, mode, p, prior, degree_bias_coef, noise, seed, stream_id0, D, E, q,
+                                  edge_index, mask, sampled_eid, sampled_edge_index, stats, st_weights, ws, ws_bytes, stream_);
 }
 
 }  // extern "C"

@@ -15,7 +15,10 @@ other heads keep the serial loop.  A third opt-in, `args.sgs_eval_batch_variants
 own options take the engine too: a GATModel with gat_heads in 2..16 and / or gat_edge_weight=True and a ChebModel with cheb_k in 2..8, when
 their head is selected; without it these models keep the serial loop.  A GATModel(gat_v2=True) and a GINModel(gin_edge_weight=True) keep the
 serial loop whatever the opt-ins say (no batched engine exists for them: the batched GIN engine aggregates transformed features with unit
-weights).  `PATH_COUNTS` records which path each ensemble_evaluate call took.
+weights).  Under `args.sgs_cover_nodes` (node-covering draws) every model keeps the serial loop unless a fourth opt-in,
+`args.sgs_eval_batch_cover` (absent / None / False = off, True = on), is set: then the cover flag no longer blocks the engine, the other
+opt-ins decide exactly as they do without the flag, and every pass draws with ops.sample_topq_multi(..., cover=) -- row d is the serial
+loop's d-th covering draw.  `PATH_COUNTS` records which path each ensemble_evaluate call took.
 """
 from __future__ import annotations
 
@@ -90,7 +93,7 @@ def _run(args, model, cluster_loader, device, q, mode, n_draws):
 
 
 def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str = "GCN", *, gat_heads: int = 1, gat_edge: bool = False,
-               cheb_k: int = 1) -> list:
+               cheb_k: int = 1, cover: bool = False) -> list:
     """Draws per pass of the batched engine: a list of pass sizes summing to D, each >= 1.  `budget` is True (the largest pass whose
     per-draw buffers fit EVAL_BATCH_BUDGET bytes), an int number of bytes via ("bytes", n), or an int k >= 1 (at most k draws per pass).
     Per draw (an upper estimate of the engine's per-draw allocations): keys 4 E + mask E + filter positions 4 E; per drawn edge 40 B
@@ -102,8 +105,10 @@ def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str
     so its term becomes 4 q K + 12 N K (attention values [q, K], loop terms [N, K], layer-2 node scores 2 [N, K]) plus 4 N C (K - 1) for the
     layer-2 product [N, K C] beside the logits; gat_edge adds 8 N (the mean loop weight and count of the edge term; the kernels take them
     as optional outputs, counted always).  Cheb with K = cheb_k >= 2 adds the (K - 1) out-wide block of b's of each layer,
-    4 N (K - 1) (H + C), the per-draw Laplacian values 4 q, dis 4 N and the weights scattered by parent edge id 4 E.  The result of the
-    engine does not depend on the split."""
+    4 N (K - 1) (H + C), the per-draw Laplacian values 4 q, dis 4 N and the weights scattered by parent edge id 4 E.  `cover`
+    (node-covering draws, ops.sample_topq_multi(..., cover=)) adds that call's per-draw workspace and output: 1024 per-workgroup counts
+    of forced edges (4096 B) and the cover_info pair (8 B); it never makes a pass larger.  The result of the engine does not depend on
+    the split."""
     D = int(D)
     if D < 1:
         raise ValueError(f"plan_draws: D={D} draws")
@@ -122,6 +127,8 @@ def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str
             per += 4 * int(N) * int(H) + 8 * int(N) * int(C) + 4 * int(q) + 4 * int(N)
         elif head == "Cheb" and int(cheb_k) > 1:
             per += 4 * int(N) * (int(cheb_k) - 1) * (int(H) + int(C)) + 4 * int(q) + 4 * int(N) + 4 * int(E)
+        if cover:
+            per += 4 * 1024 + 8
         k = max(1, min(D, int(nbytes) // per))
     else:
         k = int(budget)
@@ -138,17 +145,21 @@ def _batched_ok(args, model, n_draws) -> bool:
     with sgs_eval_batch_variants=True (per-head GAT kernels / per-draw Chebyshev steps, ops.ensemble_partition_head).  A gat_v2 model keeps
     the serial loop whatever the opt-ins say: there is no batched GATv2 engine.  So does a gin_edge_weight model: the batched GIN engine
     (ops._drawn_gin_logits) aggregates transformed features with unit weights, which is not the GINE layer.  Under
-    args.sgs_cover_nodes (node-covering draws, checked first) every model keeps the serial loop: sgs_sample_topq_multi has no covering
-    form."""
-    if cover_nodes(args):
-        return False
+    args.sgs_cover_nodes (node-covering draws, validated first) every model keeps the serial loop unless args.sgs_eval_batch_cover is
+    True: with it the cover flag no longer blocks the engine (sgs_sample_topq_multi_cover draws all of a pass's covering draws) and the
+    other opt-ins decide exactly as they do without the flag.  sgs_eval_batch_cover is validated with the other opt-ins (None / a bool,
+    only when sgs_eval_batch is truthy); absent, None or False it changes nothing."""
+    cover = cover_nodes(args)
     flag = getattr(args, "sgs_eval_batch", False)
     if not flag:
         return False
+    if cover and (getattr(args, "sgs_eval_batch_cover", None) is None or getattr(args, "sgs_eval_batch_cover", None) is False):
+        return False                            # the routing from before the opt-in existed: nothing else is consulted
     if flag is not True and (isinstance(flag, bool) or not isinstance(flag, int) or flag < 1):
         raise ValueError(f"args.sgs_eval_batch={flag!r}: need True (draws per pass from a byte budget) or an int >= 1 (at most k per pass)")
     heads = _eval_heads(args)
     variants = _eval_variants(args)
+    _eval_batch_cover(args)
     if n_draws < 1 or getattr(model, "gat_v2", False) or getattr(model, "gin_edge_weight", False):
         return False
     if not variants:                            # without the third opt-in the heads' options keep the serial loop, as before it existed
@@ -157,6 +168,16 @@ def _batched_ok(args, model, n_draws) -> bool:
     elif not (1 <= getattr(model, "gat_heads", 1) <= 16 and 1 <= getattr(model, "cheb_k", 1) <= 8):
         return False
     return _head_of(model) in heads
+
+
+def _eval_batch_cover(args) -> bool:
+    """args.sgs_eval_batch_cover: absent / None / False -> False, True -> True.  Anything else raises ValueError."""
+    v = getattr(args, "sgs_eval_batch_cover", None)
+    if v is None or v is False:
+        return False
+    if v is True:
+        return True
+    raise ValueError(f"args.sgs_eval_batch_cover={v!r}: need None, False or True")
 
 
 def _eval_variants(args) -> bool:
@@ -222,7 +243,7 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
     H, C = _head_dims(model, head)
     ticks = _eval_forward_ticks(head)
     variant = dict(gat_heads=getattr(model, "gat_heads", 1), gat_edge=bool(getattr(model, "gat_edge_weight", False)),
-                   cheb_k=getattr(model, "cheb_k", 1))
+                   cheb_k=getattr(model, "cheb_k", 1), cover=cover_nodes(args))       # (under the flag only with sgs_eval_batch_cover: _batched_ok)
     with torch.no_grad():
         for batch in cluster_loader:
             batch = batch.to(device)
@@ -264,7 +285,7 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
                         _NoiseClock.tick += n
                     d += n
                     k -= n
-            ops.ensemble_partition_head(batch, model, q, kind, p, passes, counts, trace)
+            ops.ensemble_partition_head(batch, model, q, kind, p, passes, counts, trace, cover=cover_graph(args, batch))
             # GNNModel.forward and GAT.forward take one dropout seed per call, in eval mode too (GIN and Cheb none): leave the dropout
             # clock where the serial loop's n_draws forwards leave it, so that training after an evaluation draws the same masks whichever
             # path evaluated

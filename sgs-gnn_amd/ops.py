@@ -2481,14 +2481,17 @@ def gcn2_dual(x, W1, b1, W2, b2, nm_a: Norm, nm_b: Norm, act=ACT_RELU, p=0.0, se
 # ------------------------------------------------------------------ batched ensemble evaluation (forward only, GCN head)
 class MultiSampleResult:
     """D draws over one candidate set (sgs_sample_topq_multi): mask [D, E] bool, eid [D, q], edge_index [D, 2, q] or None,
-    stats [D, 4], w [D, q] (straight-through weights) or None.  Row d is what sample_topq returns for stream id stream_id0 + d."""
-    __slots__ = ("mask", "eid", "edge_index", "stats", "w", "D", "E", "q")
+    stats [D, 4], w [D, q] (straight-through weights) or None.  Row d is what sample_topq returns for stream id stream_id0 + d.
+    cover_info: [D, 2] int32 = {M_d, min(M_d, q)} for node-covering draws (sgs_sample_topq_multi_cover), else None."""
+    __slots__ = ("mask", "eid", "edge_index", "stats", "w", "D", "E", "q", "cover_info")
 
 
 def sample_topq_multi(mode: int, p, prior, c: float, q: int, edge_index, D: int, noise=None, seed: int = 0, stream_id0: int = 0,
-                      want_edge_index: bool = True, want_w: bool = False) -> MultiSampleResult:
+                      want_edge_index: bool = True, want_w: bool = False, cover: "Graph | None" = None) -> MultiSampleResult:
     """D exponential-race top-q draws in one pass.  p [E] f32 (None: uniform weights), prior [E] or None, noise [D, E] f32 or None
-    (then draw d uses (seed, stream_id0 + d)).  `want_w`: also the straight-through weights of each draw (mode LEARNED)."""
+    (then draw d uses (seed, stream_id0 + d)).  `want_w`: also the straight-through weights of each draw (mode LEARNED).
+    `cover`: the Graph of the candidate edges (get_graph(edge_index, N)) makes every draw node-covering (sgs_sample_topq_multi_cover:
+    row d is sample_topq(..., cover=)'s draw for stream id stream_id0 + d); the result then carries cover_info int32 [D, 2]."""
     L = _lib.lib()
     _need_gpu(p, prior, edge_index, noise)
     if p is None and edge_index is None:
@@ -2505,6 +2508,19 @@ def sample_topq_multi(mode: int, p, prior, c: float, q: int, edge_index, D: int,
     r.edge_index = torch.empty(max(D, 1), 2, q, dtype=torch.int64, device=dev) if (want_edge_index and edge_index is not None) else None
     r.stats = torch.empty(max(D, 1), 4, dtype=torch.float32, device=dev)
     r.w = torch.empty(max(D, 1), q, dtype=torch.float32, device=dev) if want_w else None
+    r.cover_info = None
+    if cover is not None:
+        if not isinstance(cover, Graph) or cover.n_edges != E:
+            raise RuntimeError(f"sample_topq_multi: cover must be the Graph of the E={E} candidate edges"
+                               + (f" (it has {cover.n_edges})" if isinstance(cover, Graph) else ""))
+        r.cover_info = (torch.empty if E > 0 else torch.zeros)(max(D, 1), 2, dtype=torch.int32, device=dev)     # (E == 0: nothing is written)
+        ws = workspace(L.sgs_sample_topq_multi_cover_workspace_bytes(E, cover.N, max(D, 1)), dev)
+        _lib.check(L.sgs_sample_topq_multi_cover(mode, _ptr(p, torch.float32), _ptr(prior, torch.float32), float(c), _ptr(noise, torch.float32),
+                                                 seed, stream_id0, D, E, q, _ptr(edge_index, torch.int64), cover.N, _ptr(cover.in_ptr),
+                                                 _ptr(cover.in_src), _ptr(cover.in_eid), _ptr(r.mask), _ptr(r.eid), _ptr(r.edge_index),
+                                                 _ptr(r.stats), _ptr(r.w), _ptr(r.cover_info), ws.data_ptr(), ws.numel(), _stream()),
+                   "sgs_sample_topq_multi_cover")
+        return r
     ws = workspace(L.sgs_sample_topq_multi_workspace_bytes(E, max(D, 1)), dev)
     _lib.check(L.sgs_sample_topq_multi(mode, _ptr(p, torch.float32), _ptr(prior, torch.float32), float(c), _ptr(noise, torch.float32), seed,
                                        stream_id0, D, E, q, _ptr(edge_index, torch.int64), _ptr(r.mask), _ptr(r.eid), _ptr(r.edge_index),
@@ -2578,11 +2594,12 @@ def ensemble_mean_correct(logits, x_stride: int, Dc: int, acc, first: bool, last
                                            _stream()), "sgs_ensemble_mean_correct")
 
 
-def ensemble_partition(batch, gcn1, gcn2, q: int, mode: int, p, passes, counts, trace=None):
+def ensemble_partition(batch, gcn1, gcn2, q: int, mode: int, p, passes, counts, trace=None, *, cover=None):
     """All draws of ONE partition, batched: `passes` is a list of (Dc, noise [Dc, E] or None, seed, stream_id0), in draw order.
     mode SAMPLE_LEARNED with p (the scorer's probabilities, istest: straight-through weights on the edges), SAMPLE_PRIOR with p = batch.prob
     (unit weights), or SAMPLE_LEARNED with p None (uniform draw, unit weights).  Adds the partition's three (correct, total) counts to
-    `counts`.  `trace` (dict or None): receives per-draw logits [D, N, C], mean [N, C] and the drawn edge lists [D, 2, q]."""
+    `counts`.  `trace` (dict or None): receives per-draw logits [D, N, C], mean [N, C] and the drawn edge lists [D, 2, q].  `cover`
+    (the partition's cached get_graph(edge_index, N), the same object as the filter's parent, or None): every draw is node-covering."""
     x, ei = batch.x, batch.edge_index
     N = x.shape[0]
     feature_csr(x, build=True)
@@ -2595,7 +2612,7 @@ def ensemble_partition(batch, gcn1, gcn2, q: int, mode: int, p, passes, counts, 
     for k, (Dc, noise, seed, sid0) in enumerate(passes):
         weighted = mode == SAMPLE_LEARNED and p is not None
         smp = sample_topq_multi(mode, p, None, 0.0, q, ei, Dc, noise=noise, seed=seed, stream_id0=sid0, want_edge_index=trace is not None,
-                                want_w=weighted)
+                                want_w=weighted, cover=cover)
         out = _drawn_gcn_logits(parent, smp, smp.w if weighted else None, xl1, gcn1.bias, gcn2.lin.weight, gcn2.bias)
         if acc is None:
             acc = torch.empty(N, out.shape[2], dtype=torch.float32, device=x.device)
@@ -2775,17 +2792,18 @@ def _drawn_cheb_logits(parent: Graph, smp: MultiSampleResult, w, convs, K: int, 
     return _cheb_layer_multi(K, Y0b, N * C, Bb, N * (K - 1) * C, csr, l_in, c2.bias, ACT_NONE, q, N, D)
 
 
-def ensemble_partition_head(batch, model, q: int, mode: int, p, passes, counts, trace=None):
+def ensemble_partition_head(batch, model, q: int, mode: int, p, passes, counts, trace=None, *, cover=None):
     """ensemble_partition for any of the four heads (GNNModel, GATModel, GINModel, ChebModel), same arguments and result.  Per pass: the D
     draws (sample_topq_multi), their in-CSRs (graph_filter_multi) and the head's logits for all of them; the draw-independent first
     product (GAT: lin_src(x) and its node scores; GIN: x W0^T; Chebyshev K >= 2: x [W_0 | ... | W_{K-1}]^T) runs once per partition.
     Chebyshev K = 1 ignores the graph: its logits are computed once and folded D times; it draws only when `trace` asks for the edge
     lists.  One-head GAT without the edge term and GIN ignore edge weights, so no straight-through weights are drawn for them; GAT with
     gat_edge_weight and Chebyshev K >= 2 take them (learned mode; the other modes have none: no edge term / unit weights, as
-    edge_weight=None in the model).  GAT with heads >= 2 or the edge term runs on the per-head kernels (_drawn_gat_heads_logits)."""
+    edge_weight=None in the model).  GAT with heads >= 2 or the edge term runs on the per-head kernels (_drawn_gat_heads_logits).
+    `cover` (get_graph(edge_index, N) or None) goes to every sample_topq_multi call, the Chebyshev K = 1 trace-only draw included."""
     from .model import ChebModel, GATModel, GINModel, GNNModel
     if isinstance(model, GNNModel):
-        return ensemble_partition(batch, model.gcn1, model.gcn2, q, mode, p, passes, counts, trace)
+        return ensemble_partition(batch, model.gcn1, model.gcn2, q, mode, p, passes, counts, trace, cover=cover)
     x, ei = batch.x, batch.edge_index
     N = x.shape[0]
     weighted = mode == SAMPLE_LEARNED and p is not None              # the draws carry straight-through weights
@@ -2828,7 +2846,7 @@ def ensemble_partition_head(batch, model, q: int, mode: int, p, passes, counts, 
         smp = None
         if logits is not None or trace is not None:
             smp = sample_topq_multi(mode, p, None, 0.0, q, ei, Dc, noise=noise, seed=seed, stream_id0=sid0, want_edge_index=trace is not None,
-                                    want_w=want_w)
+                                    want_w=want_w, cover=cover)
         if logits is not None:
             out = logits(parent, smp)
             stride = N * out.shape[2]
