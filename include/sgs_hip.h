@@ -930,11 +930,25 @@ int sgs_gatv2_dxl_heads(const float* xl, const float* xr, const float* att, cons
  * the same fp32 inputs, and the library is compiled with -ffp-contract=off (no fused multiply-add on either side): the two agree bit
  * for bit, so an element passes the ReLU in the backward iff it did in the forward.
  * No float atomics, no memset nodes, no host synchronisation: two identical launches give identical bits.
+ *   sgs_gine_aggregate_fwd_multi (batched ensemble evaluation, forward only): sgs_gine_aggregate_fwd for all D draws of a pass in ONE
+ *       launch (draw = blockIdx.y) over sgs_graph_filter_multi's draw-strided dst-CSRs: in_ptr [D, N+1], in_src / in_eid [D, max(nnz, 1)].
+ *       Draw d reads x + d * x_stride (in floats; 0: one [N, Dc] block shared by all draws; else >= N Dc: per-draw blocks), edge_w
+ *       [D, max(nnz, 1)] by the DRAW's edge id (what in_eid holds: sgs_sample_topq_multi's st_weights) or NULL (unit weights, bitwise a
+ *       vector of ones), the shared a, b [Dc], and writes block d of z [D, N, Dc].  Block d is BITWISE sgs_gine_aggregate_fwd on draw d's
+ *       arrays: the same device code per workgroup (the same gather body and pre-activation expression), the row form chosen by
+ *       sgs_gine_variant(N, Dc, nnz, .) as a single-draw call with n_edges = nnz chooses it.  VEC decides which lane owns a column, never
+ *       the order of a column's additions, so it may differ from the single-draw call's without changing a bit; here it is the widest
+ *       that x, z, a, b AND the strides between draws (x_stride, N Dc) allow -- an unaligned stride drops to a narrower VEC.
+ *       Requires N >= 0, Dc >= 1, nnz >= 0, 1 <= D <= 65535, x_stride == 0 or >= N Dc ("bad sizes"); x and z must not overlap; N = 0
+ *       returns SGS_OK with nothing launched.  No workspace, no atomics, no memset nodes, no host synchronisation: capturable.
  * ---------------------------------------------------------------------------------- */
 int sgs_gine_variant(int64_t N, int64_t D, int64_t nnz, int align_bytes);
 int sgs_gine_aggregate_fwd(const float* x, const float* edge_w, const float* a, const float* b, float diag, int64_t N, int64_t D,
                            int64_t n_edges, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, float* z,
                            sgs_stream_t stream);
+int sgs_gine_aggregate_fwd_multi(const float* x, int64_t x_stride, const float* edge_w, const float* a, const float* b, float diag,
+                                 int64_t N, int64_t Dc, int64_t nnz, int64_t D, const int32_t* in_ptr, const int32_t* in_src,
+                                 const int32_t* in_eid, float* z, sgs_stream_t stream);
 size_t sgs_gine_aggregate_bwd_workspace_bytes(int64_t N, int64_t D);
 int sgs_gine_aggregate_bwd(const float* x, const float* dz, const float* edge_w, const float* a, const float* b, float diag, int64_t N,
                            int64_t D, int64_t n_edges, const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid,

@@ -88,9 +88,9 @@ __device__ __forceinline__ void gine_gather(float (&acc)[VEC], const float* __re
     }
 }
 
-// one wave per row, kT / 64 rows per workgroup
+// one wave per row, kT / 64 rows per workgroup: the body of a workgroup, shared by the single-draw and the multi-draw kernel
 template <int VEC>
-__global__ void __launch_bounds__(kT) gine_fwd_wave(const float* __restrict__ X, const float* __restrict__ w, const float* __restrict__ a,
+__device__ __forceinline__ void gine_fwd_wave_body(const float* __restrict__ X, const float* __restrict__ w, const float* __restrict__ a,
                                                    const float* __restrict__ b, float diag, int64_t N, int64_t D,
                                                    const int* __restrict__ ptr, const int* __restrict__ src, const int* __restrict__ eid,
                                                    float* __restrict__ Z) {
@@ -111,13 +111,20 @@ __global__ void __launch_bounds__(kT) gine_fwd_wave(const float* __restrict__ X,
     }
 }
 
-// a workgroup of NW waves per row
+template <int VEC>
+__global__ void __launch_bounds__(kT) gine_fwd_wave(const float* __restrict__ X, const float* __restrict__ w, const float* __restrict__ a,
+                                                   const float* __restrict__ b, float diag, int64_t N, int64_t D,
+                                                   const int* __restrict__ ptr, const int* __restrict__ src, const int* __restrict__ eid,
+                                                   float* __restrict__ Z) {
+    gine_fwd_wave_body<VEC>(X, w, a, b, diag, N, D, ptr, src, eid, Z);
+}
+
+// a workgroup of NW waves per row (row blockIdx.x)
 template <int VEC, int NW>
-__global__ void __launch_bounds__(64 * NW) gine_fwd_block(const float* __restrict__ X, const float* __restrict__ w, const float* __restrict__ a,
-                                                         const float* __restrict__ b, float diag, int64_t N, int64_t D,
-                                                         const int* __restrict__ ptr, const int* __restrict__ src,
-                                                         const int* __restrict__ eid, float* __restrict__ Z) {
-    __shared__ float part[NW][64 * VEC];
+__device__ __forceinline__ void gine_fwd_block_body(float (&part)[NW][64 * VEC], const float* __restrict__ X, const float* __restrict__ w,
+                                                    const float* __restrict__ a, const float* __restrict__ b, float diag, int64_t D,
+                                                    const int* __restrict__ ptr, const int* __restrict__ src, const int* __restrict__ eid,
+                                                    float* __restrict__ Z) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t i = blockIdx.x;
     const int bgn = ptr[i], end = ptr[i + 1];
@@ -144,6 +151,40 @@ __global__ void __launch_bounds__(64 * NW) gine_fwd_block(const float* __restric
         }
         __syncthreads();
     }
+}
+
+template <int VEC, int NW>
+__global__ void __launch_bounds__(64 * NW) gine_fwd_block(const float* __restrict__ X, const float* __restrict__ w, const float* __restrict__ a,
+                                                         const float* __restrict__ b, float diag, int64_t N, int64_t D,
+                                                         const int* __restrict__ ptr, const int* __restrict__ src,
+                                                         const int* __restrict__ eid, float* __restrict__ Z) {
+    __shared__ float part[NW][64 * VEC];
+    gine_fwd_block_body<VEC, NW>(part, X, w, a, b, diag, D, ptr, src, eid, Z);
+}
+
+// Multi-draw forms (batched ensemble evaluation): draw d = blockIdx.y runs the single-draw workgroup body on its own arrays --
+// X + d x_stride (0: one block shared by all draws), w + d nnz1, ptr + d (N + 1), src / eid + d nnz1 (nnz1 = max(nnz, 1), the row pitch of
+// graph_filter_multi's arrays), Z + d N D.  Same body, same order of every column's additions: block d is bitwise the single-draw result.
+template <int VEC>
+__global__ void __launch_bounds__(kT) gine_fwd_wave_multi(const float* __restrict__ X, int64_t x_stride, const float* __restrict__ w,
+                                                         const float* __restrict__ a, const float* __restrict__ b, float diag, int64_t N,
+                                                         int64_t D, int64_t nnz1, const int* __restrict__ ptr, const int* __restrict__ src,
+                                                         const int* __restrict__ eid, float* __restrict__ Z) {
+    const int64_t d = blockIdx.y;
+    gine_fwd_wave_body<VEC>(X + d * x_stride, w ? w + d * nnz1 : nullptr, a, b, diag, N, D, ptr + d * (N + 1), src + d * nnz1, eid + d * nnz1,
+                            Z + d * N * D);
+}
+
+template <int VEC, int NW>
+__global__ void __launch_bounds__(64 * NW) gine_fwd_block_multi(const float* __restrict__ X, int64_t x_stride, const float* __restrict__ w,
+                                                               const float* __restrict__ a, const float* __restrict__ b, float diag,
+                                                               int64_t N, int64_t D, int64_t nnz1, const int* __restrict__ ptr,
+                                                               const int* __restrict__ src, const int* __restrict__ eid,
+                                                               float* __restrict__ Z) {
+    __shared__ float part[NW][64 * VEC];
+    const int64_t d = blockIdx.y;
+    gine_fwd_block_body<VEC, NW>(part, X + d * x_stride, w ? w + d * nnz1 : nullptr, a, b, diag, D, ptr + d * (N + 1), src + d * nnz1,
+                                 eid + d * nnz1, Z + d * N * D);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- backward
@@ -360,6 +401,38 @@ int sgs_gine_aggregate_fwd(const float* x, const float* edge_w, const float* a, 
                                        diag, N, D, in_ptr, in_src, in_eid, z)
 #define FWD_BLOCK(V, W) hipLaunchKernelGGL((gine_fwd_block<V, W>), dim3(static_cast<unsigned>(N)), dim3(64 * W), 0, stream, x, edge_w, a, b, diag, \
                                            N, D, in_ptr, in_src, in_eid, z)
+    GINE_DISPATCH(var, FWD_WAVE, FWD_BLOCK)
+#undef FWD_WAVE
+#undef FWD_BLOCK
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+/* All D draws of a pass in one launch (draw = blockIdx.y) over graph_filter_multi's draw-strided in-CSRs.  The kind / NW choice is
+ * sgs_gine_variant's for (N, Dc, nnz), as a single-draw call on one draw makes it.  VEC only decides which lane owns a column, never the
+ * order of a column's additions, so it may differ from a single-draw call's without changing a bit: here every draw's base address has
+ * to be 4 VEC-byte aligned, i.e. the pointers AND the element strides between draws (x_stride, N Dc; the latter follows from Dc % VEC == 0
+ * and is checked all the same).  An unaligned stride drops to the next narrower VEC. */
+int sgs_gine_aggregate_fwd_multi(const float* x, int64_t x_stride, const float* edge_w, const float* a, const float* b, float diag, int64_t N,
+                                 int64_t Dc, int64_t nnz, int64_t D, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid,
+                                 float* z, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(N >= 0 && Dc >= 1 && nnz >= 0 && N <= 0x7FFFFFFF && nnz <= 0x7FFFFFFF && D >= 1 && D <= 65535 &&
+                    (x_stride == 0 || x_stride >= N * Dc), SGS_EINVAL,
+                "sgs_gine_aggregate_fwd_multi: bad sizes (need N >= 0, Dc >= 1, nnz >= 0, 1 <= D <= 65535, x_stride 0 or >= N * Dc)");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(x && a && b && in_ptr && z && (nnz == 0 || (in_src && in_eid)), SGS_EINVAL, "sgs_gine_aggregate_fwd_multi: null pointer");
+    SGS_REQUIRE(x + (D - 1) * x_stride + N * Dc <= z || z + D * N * Dc <= x, SGS_EINVAL, "sgs_gine_aggregate_fwd_multi: x and z overlap");
+    int al = gine_align(x, z, a, b, nullptr);
+    if (D > 1)
+        while (al > 4 && ((x_stride * 4) % al != 0 || (N * Dc * 4) % al != 0)) al /= 2;
+    const int var = sgs_gine_variant(N, Dc, nnz, al);
+    const int64_t nnz1 = nnz > 0 ? nnz : 1;
+    const unsigned Du = static_cast<unsigned>(D);
+#define FWD_WAVE(V) hipLaunchKernelGGL((gine_fwd_wave_multi<V>), dim3(static_cast<unsigned>(cdiv(N, kT / 64)), Du), dim3(kT), 0, stream, x, \
+                                       x_stride, edge_w, a, b, diag, N, Dc, nnz1, in_ptr, in_src, in_eid, z)
+#define FWD_BLOCK(V, W) hipLaunchKernelGGL((gine_fwd_block_multi<V, W>), dim3(static_cast<unsigned>(N), Du), dim3(64 * W), 0, stream, x, x_stride, \
+                                           edge_w, a, b, diag, N, Dc, nnz1, in_ptr, in_src, in_eid, z)
     GINE_DISPATCH(var, FWD_WAVE, FWD_BLOCK)
 #undef FWD_WAVE
 #undef FWD_BLOCK

@@ -13,9 +13,12 @@ of a partition run as one pass of batched kernels (ops.ensemble_partition_head) 
 `args.sgs_eval_batch_heads`: absent / None = ("GCN",) (GNNModel only), "all" = GCN, GAT, GIN and Cheb, or a collection of those names;
 other heads keep the serial loop.  A third opt-in, `args.sgs_eval_batch_variants` (absent / None / False = off, True = on), lets the heads'
 own options take the engine too: a GATModel with gat_heads in 2..16 and / or gat_edge_weight=True and a ChebModel with cheb_k in 2..8, when
-their head is selected; without it these models keep the serial loop.  A GATModel(gat_v2=True) and a GINModel(gin_edge_weight=True) keep the
-serial loop whatever the opt-ins say (no batched engine exists for them: the batched GIN engine aggregates transformed features with unit
-weights).  Under `args.sgs_cover_nodes` (node-covering draws) every model keeps the serial loop unless a fourth opt-in,
+their head is selected; without it these models keep the serial loop.  A GINModel(gin_edge_weight=True) has an engine of its own
+(ops._drawn_gine_logits: the GINE aggregation of all draws in one launch per layer, at the input width; the plain batched GIN engine
+aggregates transformed features with unit weights and would be wrong for it) behind a fifth opt-in, `args.sgs_eval_batch_gine` (absent /
+None / False = off, True = on): it takes the engine iff that is True and "GIN" is among the selected heads; without it, it keeps the serial
+loop whatever else is set.  A GATModel(gat_v2=True) keeps the serial loop whatever the opt-ins say (no batched engine exists for it).
+Under `args.sgs_cover_nodes` (node-covering draws) every model keeps the serial loop unless a fourth opt-in,
 `args.sgs_eval_batch_cover` (absent / None / False = off, True = on), is set: then the cover flag no longer blocks the engine, the other
 opt-ins decide exactly as they do without the flag, and every pass draws with ops.sample_topq_multi(..., cover=) -- row d is the serial
 loop's d-th covering draw.  `PATH_COUNTS` records which path each ensemble_evaluate call took.
@@ -93,7 +96,7 @@ def _run(args, model, cluster_loader, device, q, mode, n_draws):
 
 
 def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str = "GCN", *, gat_heads: int = 1, gat_edge: bool = False,
-               cheb_k: int = 1, cover: bool = False) -> list:
+               cheb_k: int = 1, cover: bool = False, gine_in: int = 0) -> list:
     """Draws per pass of the batched engine: a list of pass sizes summing to D, each >= 1.  `budget` is True (the largest pass whose
     per-draw buffers fit EVAL_BATCH_BUDGET bytes), an int number of bytes via ("bytes", n), or an int k >= 1 (at most k draws per pass).
     Per draw (an upper estimate of the engine's per-draw allocations): keys 4 E + mask E + filter positions 4 E; per drawn edge 40 B
@@ -107,8 +110,12 @@ def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str
     as optional outputs, counted always).  Cheb with K = cheb_k >= 2 adds the (K - 1) out-wide block of b's of each layer,
     4 N (K - 1) (H + C), the per-draw Laplacian values 4 q, dis 4 N and the weights scattered by parent edge id 4 E.  `cover`
     (node-covering draws, ops.sample_topq_multi(..., cover=)) adds that call's per-draw workspace and output: 1024 per-workgroup counts
-    of forced edges (4096 B) and the cover_info pair (8 B); it never makes a pass larger.  The result of the engine does not depend on
-    the split."""
+    of forced edges (4096 B) and the cover_info pair (8 B); it never makes a pass larger.  `gine_in` = F > 0 (head "GIN" only; 0 = the
+    numbers above for every head) describes the GINE head (gin_edge_weight) at input width F: GIN's term is replaced by what
+    ops._drawn_gine_logits allocates per draw beside the counted hidden block and two logit blocks (the second MLP's two [N, C] products),
+    4 N F + 8 N H: the first aggregate [N, F] at the input width, the first MLP's second product [N, H] and the second aggregate [N, H]
+    (its unit weights are a NULL pointer and 1 + eps a scalar: neither is allocated; the straight-through weights are the 4 B per drawn
+    edge counted above).  The result of the engine does not depend on the split."""
     D = int(D)
     if D < 1:
         raise ValueError(f"plan_draws: D={D} draws")
@@ -116,6 +123,9 @@ def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str
         raise ValueError(f"plan_draws: head={head!r}, need one of {HEADS}")
     if not 1 <= int(gat_heads) <= 16 or not 1 <= int(cheb_k) <= 8:
         raise ValueError(f"plan_draws: gat_heads={gat_heads}, cheb_k={cheb_k}: need 1..16 and 1..8")
+    gine_in = int(gine_in)
+    if gine_in < 0 or (gine_in and head != "GIN"):
+        raise ValueError(f"plan_draws: gine_in={gine_in} with head={head!r}: need 0, or the GINE head's input width >= 1 with head 'GIN'")
     if budget is True or (isinstance(budget, tuple) and budget[0] == "bytes"):
         nbytes = EVAL_BATCH_BUDGET if budget is True else int(budget[1])
         ks = (int(E) + 63) & ~63
@@ -123,6 +133,8 @@ def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str
         K = int(gat_heads)
         if head == "GAT":
             per += 4 * int(q) * K + 12 * int(N) * K + 4 * int(N) * int(C) * (K - 1) + (8 * int(N) if gat_edge else 0)
+        elif head == "GIN" and gine_in:
+            per += 4 * int(N) * gine_in + 8 * int(N) * int(H)
         elif head == "GIN":
             per += 4 * int(N) * int(H) + 8 * int(N) * int(C) + 4 * int(q) + 4 * int(N)
         elif head == "Cheb" and int(cheb_k) > 1:
@@ -143,8 +155,11 @@ def _batched_ok(args, model, n_draws) -> bool:
     int >= 1, and args.sgs_eval_batch_heads and args.sgs_eval_batch_variants (consulted only then) a valid head selection and None / a
     bool, all checked here, before any partition is read.  A model with gat_heads > 1, gat_edge_weight or cheb_k > 1 takes the engine only
     with sgs_eval_batch_variants=True (per-head GAT kernels / per-draw Chebyshev steps, ops.ensemble_partition_head).  A gat_v2 model keeps
-    the serial loop whatever the opt-ins say: there is no batched GATv2 engine.  So does a gin_edge_weight model: the batched GIN engine
-    (ops._drawn_gin_logits) aggregates transformed features with unit weights, which is not the GINE layer.  Under
+    the serial loop whatever the opt-ins say: there is no batched GATv2 engine.  A gin_edge_weight model takes the engine
+    (ops._drawn_gine_logits, the multi-draw GINE aggregation) iff args.sgs_eval_batch_gine is True and "GIN" is a selected head; the
+    plain batched GIN engine (ops._drawn_gin_logits) aggregates transformed features with unit weights, which is not the GINE layer, so
+    without that opt-in the model keeps the serial loop whatever else is set.  sgs_eval_batch_gine is validated with the other opt-ins
+    (None / a bool, only when sgs_eval_batch is truthy); absent, None or False it changes no model's routing.  Under
     args.sgs_cover_nodes (node-covering draws, validated first) every model keeps the serial loop unless args.sgs_eval_batch_cover is
     True: with it the cover flag no longer blocks the engine (sgs_sample_topq_multi_cover draws all of a pass's covering draws) and the
     other opt-ins decide exactly as they do without the flag.  sgs_eval_batch_cover is validated with the other opt-ins (None / a bool,
@@ -160,7 +175,8 @@ def _batched_ok(args, model, n_draws) -> bool:
     heads = _eval_heads(args)
     variants = _eval_variants(args)
     _eval_batch_cover(args)
-    if n_draws < 1 or getattr(model, "gat_v2", False) or getattr(model, "gin_edge_weight", False):
+    gine = _eval_batch_gine(args)
+    if n_draws < 1 or getattr(model, "gat_v2", False) or (getattr(model, "gin_edge_weight", False) and not gine):
         return False
     if not variants:                            # without the third opt-in the heads' options keep the serial loop, as before it existed
         if getattr(model, "gat_heads", 1) > 1 or getattr(model, "gat_edge_weight", False) or getattr(model, "cheb_k", 1) > 1:
@@ -178,6 +194,16 @@ def _eval_batch_cover(args) -> bool:
     if v is True:
         return True
     raise ValueError(f"args.sgs_eval_batch_cover={v!r}: need None, False or True")
+
+
+def _eval_batch_gine(args) -> bool:
+    """args.sgs_eval_batch_gine: absent / None / False -> False, True -> True.  Anything else raises ValueError."""
+    v = getattr(args, "sgs_eval_batch_gine", None)
+    if v is None or v is False:
+        return False
+    if v is True:
+        return True
+    raise ValueError(f"args.sgs_eval_batch_gine={v!r}: need None, False or True")
 
 
 def _eval_variants(args) -> bool:
@@ -244,6 +270,8 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
     ticks = _eval_forward_ticks(head)
     variant = dict(gat_heads=getattr(model, "gat_heads", 1), gat_edge=bool(getattr(model, "gat_edge_weight", False)),
                    cheb_k=getattr(model, "cheb_k", 1), cover=cover_nodes(args))       # (under the flag only with sgs_eval_batch_cover: _batched_ok)
+    if getattr(model, "gin_edge_weight", False):
+        variant["gine_in"] = model.GIN.convs[0].in_channels                          # (here only with sgs_eval_batch_gine: _batched_ok)
     with torch.no_grad():
         for batch in cluster_loader:
             batch = batch.to(device)

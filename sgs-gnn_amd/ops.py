@@ -2681,6 +2681,54 @@ def _drawn_gin_logits(parent: Graph, smp: MultiSampleResult, convs, u1):
     return h.view(D, N, -1)
 
 
+def gine_aggregate_multi(x, x_stride: int, csr, w, a, b, diag: float, q: int, N: int, Dc: int):
+    """sgs_gine_aggregate_fwd_multi over graph_filter_multi's CSRs: z [D, N, Dc], block d bitwise sgs_gine_aggregate_fwd's for draw d with
+    x_d = x + d * x_stride (0: one [N, Dc] block shared by all draws; N Dc: [D, N, Dc] blocks).  `w` [D, q] by the draw's edge id
+    (sample_topq_multi(..., want_w=True).w) or None (unit weights); a, b with Dc elements.  Forward only: no autograd node."""
+    L = _lib.lib()
+    _need_gpu(x, w, a, b)
+    in_ptr, in_src, in_eid = csr[0], csr[1], csr[2]
+    D = in_ptr.shape[0]
+    x_stride = int(x_stride)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < (D - 1) * x_stride + N * Dc or (x_stride != 0 and x_stride < N * Dc):
+        raise RuntimeError(f"gine_aggregate_multi: x must be contiguous float32 with (D - 1) x_stride + N Dc = {(D - 1) * x_stride + N * Dc} elements")
+    if a.numel() != Dc or b.numel() != Dc or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise RuntimeError(f"gine_aggregate_multi: a and b must be float32 with {Dc} elements")
+    if w is not None and (tuple(w.shape) != (D, q) or w.dtype != torch.float32):
+        raise RuntimeError(f"gine_aggregate_multi: w must be float32 [D={D}, q={q}]")
+    if tuple(in_ptr.shape) != (D, N + 1) or tuple(in_src.shape) != (D, max(q, 1)) or tuple(in_eid.shape) != (D, max(q, 1)):
+        raise RuntimeError(f"gine_aggregate_multi: csr must be graph_filter_multi's arrays for D={D}, N={N}, q={q}")
+    z = torch.empty(D, N, Dc, dtype=torch.float32, device=x.device)
+    w = w.contiguous() if w is not None and q > 0 else None
+    a, b = a.reshape(Dc).contiguous(), b.reshape(Dc).contiguous()
+    _lib.check(L.sgs_gine_aggregate_fwd_multi(_ptr(x, torch.float32), x_stride, _ptr(w), _ptr(a), _ptr(b), float(diag), N, Dc, q, D, _ptr(in_ptr),
+                                              _ptr(in_src), _ptr(in_eid), _ptr(z), _stream()), "sgs_gine_aggregate_fwd_multi")
+    return z
+
+
+def _drawn_gine_logits(parent: Graph, smp: MultiSampleResult, w, convs, x):
+    """Logits [D, N, C] of the two GINEConv layers (GIN.forward in eval mode: ReLU between the convs, no dropout and no dropout seed) over
+    each of the D drawn subgraphs of `parent`: one gine_aggregate_multi launch per layer for all draws -- layer 1 at the input width over
+    the shared `x` (x_stride = 0), layer 2 at the hidden width over the per-draw blocks (x_stride = N H) -- and each MLP Linear as one
+    library GEMM over the [D N, .] rows.  `w` [D, q]: the draws' straight-through weights (learned mode), or None (unit weights, as
+    edge_weight=None in the model)."""
+    D, q, N = smp.D, smp.q, parent.N
+    csr = graph_filter_multi(parent, smp)
+    h, x_stride = x, 0
+    for k, conv in enumerate(convs):
+        l0, l1 = conv.nn.lins
+        z = gine_aggregate_multi(h, x_stride, csr, w, conv.lin.weight, conv.lin.bias, 1.0 + conv._eps, q, N, conv.in_channels)
+        h = linear_nobias(z.view(D * N, -1), l0.weight)
+        h += l0.bias
+        h.relu_()                                                     # GINEConv.forward: relu(linear_nobias(z, W0) + b0)
+        h = linear_nobias(h, l1.weight)
+        h += l1.bias
+        if k == 0:
+            h.relu_()                                                 # GIN.forward: F.relu between the convs (eval: no dropout)
+            x_stride = N * h.shape[1]
+    return h.view(D, N, -1)
+
+
 def gat_alpha_heads_multi(a_s, a_d, a_stride: int, csr, q: int, N: int, K: int, negative_slope: float, edge_w=None, edge_coef=None, out=None):
     """sgs_gat_alpha_heads_fwd_multi over graph_filter_multi's CSRs: (alpha [D, q, K] by the draw's edge id, alpha_loop [D, N, K]), row d
     bitwise sgs_gat_alpha_heads_fwd's (p = 0) for draw d -- or, with `edge_w` [D, q] and `edge_coef` [K], sgs_gat_alpha_heads_edge_fwd's
@@ -2798,8 +2846,9 @@ def ensemble_partition_head(batch, model, q: int, mode: int, p, passes, counts, 
     product (GAT: lin_src(x) and its node scores; GIN: x W0^T; Chebyshev K >= 2: x [W_0 | ... | W_{K-1}]^T) runs once per partition.
     Chebyshev K = 1 ignores the graph: its logits are computed once and folded D times; it draws only when `trace` asks for the edge
     lists.  One-head GAT without the edge term and GIN ignore edge weights, so no straight-through weights are drawn for them; GAT with
-    gat_edge_weight and Chebyshev K >= 2 take them (learned mode; the other modes have none: no edge term / unit weights, as
-    edge_weight=None in the model).  GAT with heads >= 2 or the edge term runs on the per-head kernels (_drawn_gat_heads_logits).
+    gat_edge_weight, Chebyshev K >= 2 and GIN with gin_edge_weight (the GINE layers, _drawn_gine_logits: nothing to precompute, the
+    aggregation reads x itself) take them (learned mode; the other modes have none: no edge term / unit weights, as edge_weight=None in
+    the model).  GAT with heads >= 2 or the edge term runs on the per-head kernels (_drawn_gat_heads_logits).
     `cover` (get_graph(edge_index, N) or None) goes to every sample_topq_multi call, the Chebyshev K = 1 trace-only draw included."""
     from .model import ChebModel, GATModel, GINModel, GNNModel
     if isinstance(model, GNNModel):
@@ -2821,6 +2870,11 @@ def ensemble_partition_head(batch, model, q: int, mode: int, p, passes, counts, 
             coefs = tuple(c.edge_coef().reshape(K).contiguous() for c in convs) if edge else None
             want_w = edge
             logits = lambda parent, smp: _drawn_gat_heads_logits(parent, smp, convs, xl1, a_s1, a_d1, smp.w if edge else None, coefs)
+    elif isinstance(model, GINModel) and model.gin_edge_weight:
+        convs = tuple(model.GIN.convs)                                # GINEConv: the aggregation runs at the input width, on x itself
+        xc = x.contiguous()
+        want_w = weighted
+        logits = lambda parent, smp: _drawn_gine_logits(parent, smp, smp.w if weighted else None, convs, xc)
     elif isinstance(model, GINModel):
         convs = tuple(model.GIN.convs)
         u1 = linear_nobias(x, convs[0].nn.lins[0].weight).contiguous()
