@@ -341,6 +341,17 @@ int sgs_sddmm_csr(const float* A, const float* B, int64_t N, int64_t D, int64_t 
 int sgs_spmm_csr_variant(int64_t N, int64_t D, int64_t nnz, int aligned16);
 int sgs_sddmm_csr_variant(int64_t N, int64_t D, int64_t nnz, int aligned16);
 
+/* Long rows in the row-block SpMM kernels (kind 1 above, and every call below that gathers as they do: sgs_spmm_csr_next,
+ * sgs_spmm_csr_bwd_prev, the two-job forms, sgs_spmm_csr_multi).  On (the default), a graph of at most 4096 rows launches kernels in
+ * which a row of sgs_spmm_long_rows_threshold() entries or more loads its (col, val) stream 64 entries per wave at a time and keeps
+ * two batches of X rows in flight; every sum keeps its order, so the outputs are bitwise the same either way.  Off launches the plain
+ * kernels (for A/B timing and tests).  sgs_spmm_long_rows_set returns the previous value; the value is read when a call launches, so a
+ * captured graph keeps the kernels it was captured with.  sgs_spmm_long_rows_active(N, D): 1 iff a call on N rows of width D would launch
+ * the long-row kernels now (the switch is on and the shape is inside their range).  All three are host-only and need no GPU. */
+int sgs_spmm_long_rows_set(int on);
+int sgs_spmm_long_rows_threshold(void);
+int sgs_spmm_long_rows_active(int64_t N, int64_t D);
+
 /* dZ = dY * act'(Y) for the fused epilogue above (Y is the layer OUTPUT: Y > 0 iff kept and
  * positive, so no mask is stored);  colsum: out[d] = sum_i A[i,d]  (bias gradient). */
 int sgs_act_bwd(const float* dY, const float* Y, int64_t n, int act, float p_drop, float* dZ, sgs_stream_t stream);

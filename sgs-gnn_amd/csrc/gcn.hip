@@ -698,8 +698,84 @@ __global__ void __launch_bounds__(kT) spmm_csr(const float* __restrict__ X, int6
 // mostly empty and hub rows serialise, so a 4-wave workgroup owns a row, each wave gathers a strided
 // quarter of its nnz (8 rows in flight per wave) and the four partial sums are combined through LDS
 // in a fixed order (deterministic).
+// Long rows (sgs_spmm_long_rows_set, on by default): a row of kSpmmLongRow entries or more takes spmm_long_row_gather instead of the
+// loop in the bodies below.  The four (or sixteen) waves that own a hub row of ~1000 entries finish long after every other row of a
+// partition-sized launch, and what they are short of is instruction issue: that loop spends ~18 instructions per entry and wave (two
+// per-lane loads of a wave-uniform (col, val) pair, a 64-bit multiply and add per row address), and its time per entry does not
+// depend on the row width between 256 B and 1 KiB ("Long rows").  Here a wave loads its share of the row's
+// (col, val) 64 entries at a time, one per lane (the next 64 already in flight), turns the column into a 32-bit byte offset once per
+// lane, and walks the 64 entries in unrolled batches of GU: per entry one v_readlane (the row offset, a scalar), one add, one load
+// off the scalar base X, one v_readlane (the weight) and the fmas; two batches are in flight (PIPE) where registers allow.
+// Only loads move: wave w still sums entries b + w, b + w + NW, ... in that order as one fma chain per column, so the partials, and
+// with them Y, are bitwise the short loop's.
+// Lanes past the row's last column (c0 >= D) gather column 0 and their sums are never read: control flow stays wave-uniform.
+constexpr int kSpmmLongRow = 256;
+template <int VEC, int NW, int GU, bool PIPE>
+__device__ __forceinline__ void spmm_long_row_gather(const float* __restrict__ X, int64_t D, const int* __restrict__ col,
+                                                     const float* __restrict__ val, int b, int e, int wave, int lane, int64_t cl,
+                                                     float (&acc)[VEC]) {
+    using V = typename VecT<VEC>::type;
+    const int k0 = __builtin_amdgcn_readfirstlane(b) + __builtin_amdgcn_readfirstlane(wave);
+    const int cnt = (__builtin_amdgcn_readfirstlane(e) - k0 + NW - 1) / NW;      // this wave's entries: k0 + NW m, m < cnt
+    const uint32_t cb = static_cast<uint32_t>(cl) * 4u;     // byte offset of this lane's columns in a row
+    const uint32_t rowb = static_cast<uint32_t>(D) * 4u;    // (the launchers take this path only while N * D * 4 fits 32 bits)
+    const char* __restrict__ Xb = reinterpret_cast<const char*>(X);
+    constexpr int NG = 64 / GU;
+    int jn = 0;
+    float wn = 0.f;
+    if (lane < cnt) { jn = col[k0 + NW * lane]; wn = val[k0 + NW * lane]; }
+    for (int m0 = 0; m0 < cnt; m0 += 64) {
+        const uint32_t ol = static_cast<uint32_t>(jn) * rowb;       // this lane's entry: byte offset of its X row
+        const float wl = wn;
+        const int mn = m0 + 64 + lane;
+        if (mn < cnt) { jn = col[k0 + NW * mn]; wn = val[k0 + NW * mn]; }
+        const int nb = cnt - m0 < 64 ? cnt - m0 : 64;
+        const int ng = nb / GU;
+        // entry m of the chunk: a scalar row offset (v_readlane) + the lane's column offset beside the scalar base X; m is a
+        // constant in the unrolled batches below
+        const auto ld = [&](int m) {
+            const uint32_t off = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(ol), m)) + cb;
+            return *reinterpret_cast<const V*>(Xb + off);
+        };
+        const auto fm = [&](const V& x, int m) {
+            const float w = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wl), m));
+            float xv[VEC];
+            *reinterpret_cast<V*>(xv) = x;
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, xv[v], acc[v]);
+        };
+        V x[PIPE ? 2 : 1][GU];
+        if (PIPE && ng > 0) {
+#pragma unroll
+            for (int u = 0; u < GU; ++u) x[0][u] = ld(u);
+        }
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            if (g < ng) {
+                constexpr int one = PIPE ? 1 : 0;
+                if (PIPE) {
+                    if (g + 1 < ng) {
+#pragma unroll
+                        for (int u = 0; u < GU; ++u) x[(g + 1) & one][u] = ld((g + 1) * GU + u);
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < GU; ++u) x[0][u] = ld(g * GU + u);
+                }
+#pragma unroll
+                for (int u = 0; u < GU; ++u) fm(x[g & one][u], g * GU + u);
+            }
+        }
+        const int t0 = ng * GU, rem = nb - t0;      // < GU left: one batch, as far as it goes
+#pragma unroll
+        for (int u = 0; u < GU - 1; ++u) if (u < rem) x[0][u] = ld(t0 + u);
+#pragma unroll
+        for (int u = 0; u < GU - 1; ++u) if (u < rem) fm(x[0][u], t0 + u);
+    }
+}
+
 // NW waves per row: 4, or 16 when rows are long (power-law partitions: the hub rows set the kernel's duration)
-template <int VEC, int NW>
+template <int VEC, int NW, bool LONG>
 __device__ __forceinline__ void spmm_csr_rowblock_body(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
                                                        const int* __restrict__ col, const float* __restrict__ val,
                                                        const float* __restrict__ diag, const float* __restrict__ bias, int act,
@@ -719,7 +795,9 @@ __device__ __forceinline__ void spmm_csr_rowblock_body(const float* __restrict__
         float acc[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        if (in) {
+        if (LONG && e - b >= kSpmmLongRow) {
+            spmm_long_row_gather<VEC, NW, 8, true>(X, D, col, val, b, e, wave, lane, in ? c0 : 0, acc);
+        } else if (in) {
             int k = b + wave;
             for (; k + 7 * NW < e; k += 8 * NW) {    // 8 independent gathers (k, k+NW, ..., k+7NW)
                 int j[8]; float w[8]; V x[8];
@@ -762,13 +840,13 @@ __device__ __forceinline__ void spmm_csr_rowblock_body(const float* __restrict__
         __syncthreads();
     }
 }
-template <int VEC, int NW>
+template <int VEC, int NW, bool LONG>
 __global__ void __launch_bounds__(64 * NW) spmm_csr_rowblock(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
                                                        const int* __restrict__ col, const float* __restrict__ val,
                                                        const float* __restrict__ diag, const float* __restrict__ bias, int act,
                                                        float drop_scale, uint32_t drop_thresh, uint64_t seed, uint32_t site,
                                                        const uint64_t* __restrict__ epoch, float* __restrict__ Y) {
-    spmm_csr_rowblock_body<VEC, NW>(X, N, D, ptr, col, val, diag, bias, act, drop_scale, drop_thresh, seed, site, epoch, Y);
+    spmm_csr_rowblock_body<VEC, NW, LONG>(X, N, D, ptr, col, val, diag, bias, act, drop_scale, drop_thresh, seed, site, epoch, Y);
 }
 
 // SDDMM over the CSR: g[eid[k]] = <A[i,:], B[col[k],:]> for k in row i ; gdiag[i] = <A[i,:], B[i,:]>.
@@ -1081,13 +1159,13 @@ __global__ void __launch_bounds__(kT) multi_spmm_csr(const float* __restrict__ X
     spmm_csr_body<VEC, LPR>(X + d * xs, N, D, ptr + d * (N + 1), col + d * nnz, val + d * nnz, diag ? diag + d * N : nullptr, bias, act, 1.0f, 0u,
                             uint64_t(0), 0u, nullptr, Y + d * N * D);
 }
-template <int VEC, int NW>
+template <int VEC, int NW, bool LONG>
 __global__ void __launch_bounds__(64 * NW) multi_spmm_csr_rowblock(const float* __restrict__ X, int64_t xs, int64_t N, int64_t D, int64_t nnz,
                                                                  const int* __restrict__ ptr, const int* __restrict__ col,
                                                                  const float* __restrict__ val, const float* __restrict__ diag,
                                                                  const float* __restrict__ bias, int act, float* __restrict__ Y) {
     const int64_t d = blockIdx.y;
-    spmm_csr_rowblock_body<VEC, NW>(X + d * xs, N, D, ptr + d * (N + 1), col + d * nnz, val + d * nnz, diag ? diag + d * N : nullptr, bias, act,
+    spmm_csr_rowblock_body<VEC, NW, LONG>(X + d * xs, N, D, ptr + d * (N + 1), col + d * nnz, val + d * nnz, diag ? diag + d * N : nullptr, bias, act,
                                     1.0f, 0u, uint64_t(0), 0u, nullptr, Y + d * N * D);
 }
 
@@ -1135,7 +1213,9 @@ __device__ __forceinline__ float lib_gemm_dot(int K, FY y, FW w) {
     return z;
 }
 // GU: gathers in flight per wave in the main loop (the entries are taken in the same order whatever GU is: k, k + NW, k + 2 NW, ...)
-template <int VEC, int NW, int MODE, int GU = 8>
+// LONG: rows of kSpmmLongRow entries or more take spmm_long_row_gather<VEC, NW, LGU, LPIPE>: batches of LGU rows, two of them in flight
+// (LPIPE) or one, as the kernel's register budget allows (the batch size does not enter the sums)
+template <int VEC, int NW, int MODE, bool LONG, int GU = 8, int LGU = GU, bool LPIPE = true>
 __device__ __forceinline__ void spmm_rowgroup_pair_body(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
                                                         const int* __restrict__ col, const float* __restrict__ val,
                                                         const float* __restrict__ diag, const float* __restrict__ bias, int act,
@@ -1186,7 +1266,9 @@ __device__ __forceinline__ void spmm_rowgroup_pair_body(const float* __restrict_
         float acc[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        if (in) {
+        if (LONG && e - b >= kSpmmLongRow) {      // (b, e: one row per group of NW waves, so wave-uniform)
+            spmm_long_row_gather<VEC, NW, LGU, LPIPE>(X, D, col, val, b, e, wave, lane, in ? c0 : 0, acc);
+        } else if (in) {
             int k = b + wave;
             for (; k + (GU - 1) * NW < e; k += GU * NW) {
                 int j[GU]; float w[GU]; V x[GU];
@@ -1261,7 +1343,8 @@ __device__ __forceinline__ void spmm_rowgroup_pair_body(const float* __restrict_
         }
     }
 }
-template <int VEC, int NW, int MODE>
+// (1024-thread workgroups: 128 VGPRs at most; the long-row path's two batches of 8 float4 rows fit: 96 to 112)
+template <int VEC, int NW, int MODE, bool LONG>
 __global__ void __launch_bounds__(1024) spmm_rowgroup_pair(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
                                                            const int* __restrict__ col, const float* __restrict__ val,
                                                            const float* __restrict__ diag, const float* __restrict__ bias, int act,
@@ -1269,7 +1352,7 @@ __global__ void __launch_bounds__(1024) spmm_rowgroup_pair(const float* __restri
                                                            const uint64_t* __restrict__ epoch, float* __restrict__ Y,
                                                            const float* __restrict__ Wn, int64_t Dn, const float* __restrict__ Yp,
                                                            float* __restrict__ Zn, int ncs, float* __restrict__ colsum) {
-    spmm_rowgroup_pair_body<VEC, NW, MODE>(X, N, D, ptr, col, val, diag, bias, act, drop_scale, drop_thresh, seed, site, epoch, Y, Wn, Dn, Yp, Zn,
+    spmm_rowgroup_pair_body<VEC, NW, MODE, LONG>(X, N, D, ptr, col, val, diag, bias, act, drop_scale, drop_thresh, seed, site, epoch, Y, Wn, Dn, Yp, Zn,
                                            ncs, colsum);
 }
 
@@ -1290,12 +1373,12 @@ struct SpmmDualJob {
 struct SpmmDualArgs {
     SpmmDualJob job[2];
 };
-template <int VEC, int NW>
+template <int VEC, int NW, bool LONG>
 __global__ void __launch_bounds__(64 * NW) spmm_csr_rowblock_dual(SpmmDualArgs a, int64_t N, int64_t D, const float* __restrict__ bias, int act,
                                                                   float drop_scale, uint32_t drop_thresh, uint32_t site,
                                                                   const uint64_t* __restrict__ epoch) {
     const SpmmDualJob& j = a.job[blockIdx.y];
-    spmm_csr_rowblock_body<VEC, NW>(j.X, N, D, j.ptr, j.col, j.val, j.diag, bias, act, drop_scale, drop_thresh, j.seed, site, epoch, j.Y);
+    spmm_csr_rowblock_body<VEC, NW, LONG>(j.X, N, D, j.ptr, j.col, j.val, j.diag, bias, act, drop_scale, drop_thresh, j.seed, site, epoch, j.Y);
 }
 // The pair kernel's 16-wave workgroups are 4 waves on every SIMD: two of them share a CU (what lets the two jobs' gathers overlap) only
 // within 512 / 8 = 64 VGPRs.  The single-job <4, 4> kernel has 78, and the bound alone spills; with 4 float4 gathers in flight instead
@@ -1306,15 +1389,20 @@ __global__ void __launch_bounds__(64 * NW) spmm_csr_rowblock_dual(SpmmDualArgs a
 #endif
 constexpr int kDualPairWaves = SGS_DUAL_PAIR_CAPPED ? 8 : 4;
 constexpr int dual_pair_gu(int vec) { return SGS_DUAL_PAIR_CAPPED && vec == 4 ? 4 : 8; }
-template <int VEC, int NW>
+// the long-row path under the same cap: at VEC = 4 it does not fit (one batch of 4 in flight: 64 VGPRs and 8 bytes of scratch), so
+// that kernel keeps the short loop whatever the switch says; at VEC = 1 two batches of 4 fit (two of 8 spill)
+constexpr bool dual_pair_long(int vec) { return !(SGS_DUAL_PAIR_CAPPED && vec == 4); }
+constexpr int dual_pair_long_gu(int vec) { return SGS_DUAL_PAIR_CAPPED ? 4 : 8; }
+template <int VEC, int NW, bool LONG>
 __global__ void __launch_bounds__(1024, kDualPairWaves) spmm_rowgroup_pair_dual(SpmmDualArgs a, int64_t N, int64_t D,
                                                                                 const float* __restrict__ bias, int act, float drop_scale,
                                                                                 uint32_t drop_thresh, uint32_t site,
                                                                                 const uint64_t* __restrict__ epoch,
                                                                                 const float* __restrict__ Wn, int64_t Dn) {
     const SpmmDualJob& j = a.job[blockIdx.y];
-    spmm_rowgroup_pair_body<VEC, NW, kPairFwd, dual_pair_gu(VEC)>(j.X, N, D, j.ptr, j.col, j.val, j.diag, bias, act, drop_scale, drop_thresh, j.seed,
-                                                            site, epoch, j.Y, Wn, Dn, nullptr, j.Z, 0, nullptr);
+    spmm_rowgroup_pair_body<VEC, NW, kPairFwd, LONG && dual_pair_long(VEC), dual_pair_gu(VEC), dual_pair_long_gu(VEC)>(j.X, N, D, j.ptr, j.col, j.val, j.diag, bias, act, drop_scale,
+                                                                                  drop_thresh, j.seed, site, epoch, j.Y, Wn, Dn, nullptr, j.Z, 0,
+                                                                                  nullptr);
 }
 
 inline int pick_lpr(int64_t D, int vec) {
@@ -1357,6 +1445,22 @@ using namespace sgs;
     } while (0)
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// sgs_spmm_long_rows_set: read by the SpMM launchers at launch time; it selects the kernel (a captured graph keeps what it launched).
+// On, a graph of at most kSpmmLongMaxRows rows launches the <..., LONG = true> kernels.  Their two batches of rows in flight cost
+// 20 - 34 VGPRs at VEC = 4 (DESIGN.md section 5 has the table), which only pays where hub rows set the launch's duration: a grid of about one
+// resident round of workgroups (partitions, N ~ 1000).  A larger grid hides its hubs behind its other workgroups and is bound by
+// how many waves a CU holds, so it keeps the short loop's kernels and their occupancy.
+static int g_spmm_long_rows = 1;
+constexpr int64_t kSpmmLongMaxRows = 4096;
+static inline bool spmm_long_rows_on(int64_t N, int64_t D) {       // (D: the long path keeps byte offsets into X in 32 bits)
+    return g_spmm_long_rows && N <= kSpmmLongMaxRows && D <= (int64_t(1) << 18);
+}
+#define LAUNCH_LR(KERNEL, V_, W_, grid, block, ...)                                                              \
+    do {                                                                                                          \
+        if (lr) hipLaunchKernelGGL((KERNEL<V_, W_, true>), grid, block, __VA_ARGS__);                             \
+        else    hipLaunchKernelGGL((KERNEL<V_, W_, false>), grid, block, __VA_ARGS__);                            \
+    } while (0)
 
 extern "C" {
 
@@ -1672,6 +1776,14 @@ int sgs_spmm_csr_variant(int64_t N, int64_t D, int64_t nnz, int al16) {
     return vec * 100 + pick_lpr(D, vec);
 }
 
+int sgs_spmm_long_rows_set(int on) {
+    const int prev = g_spmm_long_rows;
+    g_spmm_long_rows = on ? 1 : 0;
+    return prev;
+}
+int sgs_spmm_long_rows_threshold(void) { return kSpmmLongRow; }
+int sgs_spmm_long_rows_active(int64_t N, int64_t D) { return spmm_long_rows_on(N, D) ? 1 : 0; }
+
 int sgs_sddmm_csr_variant(int64_t N, int64_t D, int64_t nnz, int al16) {
     const int vec = (D % 4 == 0 && al16) ? 4 : 1;
     if (nnz >= 16 * N)                        // long rows (partitions; whole graphs of average degree >= 16): a workgroup per row
@@ -1693,21 +1805,22 @@ int sgs_spmm_csr(const float* X, int64_t N, int64_t D, int64_t nnz, const int32_
     const uint32_t th = dropout_thresh(p_drop);
     if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
     const dim3 g_(static_cast<unsigned>(N));
+    const bool lr = spmm_long_rows_on(N, D);
     switch (var) {
         case 1416:
-            hipLaunchKernelGGL((spmm_csr_rowblock<4, 16>), g_, dim3(1024), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
+            LAUNCH_LR(spmm_csr_rowblock, 4, 16, g_, dim3(1024), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
                                site, epoch_ptr(), Y);
             break;
         case 1404:
-            hipLaunchKernelGGL((spmm_csr_rowblock<4, 4>), g_, dim3(kT), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
+            LAUNCH_LR(spmm_csr_rowblock, 4, 4, g_, dim3(kT), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
                                site, epoch_ptr(), Y);
             break;
         case 1116:
-            hipLaunchKernelGGL((spmm_csr_rowblock<1, 16>), g_, dim3(1024), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
+            LAUNCH_LR(spmm_csr_rowblock, 1, 16, g_, dim3(1024), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
                                site, epoch_ptr(), Y);
             break;
         case 1104:
-            hipLaunchKernelGGL((spmm_csr_rowblock<1, 4>), g_, dim3(kT), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
+            LAUNCH_LR(spmm_csr_rowblock, 1, 4, g_, dim3(kT), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
                                site, epoch_ptr(), Y);
             break;
         default: {
@@ -1835,12 +1948,17 @@ int sgs_gcn_pair_ok(int64_t N, int64_t nnz, int64_t D) {
     return (N > 0 && N <= 65536 && nnz >= 16 * N && D > 0 && D <= kPairMaxD) ? 1 : 0;
 }
 
+#define PAIR_LAUNCH1(V_, W_, MODE, grid, ...)                                                                                             \
+    do {                                                                                                                          \
+        if (lr) hipLaunchKernelGGL((spmm_rowgroup_pair<V_, W_, MODE, true>), dim3(grid), dim3(1024), 0, stream, __VA_ARGS__);      \
+        else    hipLaunchKernelGGL((spmm_rowgroup_pair<V_, W_, MODE, false>), dim3(grid), dim3(1024), 0, stream, __VA_ARGS__);     \
+    } while (0)
 #define PAIR_LAUNCH(MODE, grid, ...)                                                                                              \
     do {                                                                                                                          \
-        if (vec == 4 && wide)  hipLaunchKernelGGL((spmm_rowgroup_pair<4, 16, MODE>), dim3(grid), dim3(1024), 0, stream, __VA_ARGS__); \
-        else if (vec == 4)     hipLaunchKernelGGL((spmm_rowgroup_pair<4, 4, MODE>), dim3(grid), dim3(1024), 0, stream, __VA_ARGS__);  \
-        else if (wide)         hipLaunchKernelGGL((spmm_rowgroup_pair<1, 16, MODE>), dim3(grid), dim3(1024), 0, stream, __VA_ARGS__); \
-        else                   hipLaunchKernelGGL((spmm_rowgroup_pair<1, 4, MODE>), dim3(grid), dim3(1024), 0, stream, __VA_ARGS__);  \
+        if (vec == 4 && wide)  PAIR_LAUNCH1(4, 16, MODE, grid, __VA_ARGS__); \
+        else if (vec == 4)     PAIR_LAUNCH1(4, 4, MODE, grid, __VA_ARGS__);  \
+        else if (wide)         PAIR_LAUNCH1(1, 16, MODE, grid, __VA_ARGS__); \
+        else                   PAIR_LAUNCH1(1, 4, MODE, grid, __VA_ARGS__);  \
     } while (0)
 
 int sgs_spmm_csr_next(const float* X, int64_t N, int64_t D, int64_t nnz, const int32_t* ptr, const int32_t* col, const float* val,
@@ -1857,6 +1975,7 @@ int sgs_spmm_csr_next(const float* X, int64_t N, int64_t D, int64_t nnz, const i
     const uint32_t th = dropout_thresh(p_drop);
     if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
     const int64_t grid = cdiv(N, wide ? 1 : 4);
+    const bool lr = spmm_long_rows_on(N, D);
     PAIR_LAUNCH(kPairFwd, grid, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed, site, epoch_ptr(), Y, Wn, Dn,
                 static_cast<const float*>(nullptr), Z, 0, static_cast<float*>(nullptr));
     SGS_LAUNCH_OK();
@@ -1878,6 +1997,7 @@ int sgs_spmm_csr_bwd_prev(const float* dZ, int64_t N, int64_t D, int64_t nnz, co
     const int ncs = colsum ? static_cast<int>(cdiv(D, 16)) : 0;
     const int64_t grid = ncs + cdiv(N, wide ? 1 : 4);
     const float scale = 1.0f / (1.0f - p_drop);
+    const bool lr = spmm_long_rows_on(N, D);
     if (W)
         PAIR_LAUNCH(kPairBwd, grid, dZ, N, D, ptr, col, val, diag, static_cast<const float*>(nullptr), act, scale, 0u, uint64_t(0), 0u,
                     static_cast<const uint64_t*>(nullptr), dX, W, Dp, Yp, dZp, ncs, colsum);
@@ -1889,6 +2009,7 @@ int sgs_spmm_csr_bwd_prev(const float* dZ, int64_t N, int64_t D, int64_t nnz, co
     return SGS_OK;
 }
 #undef PAIR_LAUNCH
+#undef PAIR_LAUNCH1
 
 // ---- two-job forms of the GNN head's two forward launches (spmm_rowgroup_pair_dual, spmm_csr_rowblock_dual)
 int sgs_gcn_dual_ok(int64_t N, int64_t nnz_a, int64_t nnz_b, int64_t D, int64_t Dn) {
@@ -1917,10 +2038,11 @@ int sgs_spmm_csr_next_dual(const float* X, int64_t N, int64_t D, const float* bi
     a.job[0] = SpmmDualJob{X, ptr_a, col_a, val_a, diag_a, Y_a, Z_a, nnz_a, seed_a};
     a.job[1] = SpmmDualJob{X, ptr_b, col_b, val_b, diag_b, Y_b, Z_b, nnz_b, seed_b};
     const dim3 grid(static_cast<unsigned>(cdiv(N, wide ? 1 : 4)), 2);
-    if (vec == 4 && wide)  hipLaunchKernelGGL((spmm_rowgroup_pair_dual<4, 16>), grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
-    else if (vec == 4)     hipLaunchKernelGGL((spmm_rowgroup_pair_dual<4, 4>), grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
-    else if (wide)         hipLaunchKernelGGL((spmm_rowgroup_pair_dual<1, 16>), grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
-    else                   hipLaunchKernelGGL((spmm_rowgroup_pair_dual<1, 4>), grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
+    const bool lr = spmm_long_rows_on(N, D);
+    if (vec == 4 && wide)  LAUNCH_LR(spmm_rowgroup_pair_dual, 4, 16, grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
+    else if (vec == 4)     LAUNCH_LR(spmm_rowgroup_pair_dual, 4, 4, grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
+    else if (wide)         LAUNCH_LR(spmm_rowgroup_pair_dual, 1, 16, grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
+    else                   LAUNCH_LR(spmm_rowgroup_pair_dual, 1, 4, grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -1945,11 +2067,12 @@ int sgs_spmm_csr_dual(const float* X_a, const float* X_b, int64_t N, int64_t D, 
     a.job[0] = SpmmDualJob{X_a, ptr_a, col_a, val_a, diag_a, Y_a, nullptr, nnz_a, seed_a};
     a.job[1] = SpmmDualJob{X_b, ptr_b, col_b, val_b, diag_b, Y_b, nullptr, nnz_b, seed_b};
     const dim3 g_(static_cast<unsigned>(N), 2);
+    const bool lr = spmm_long_rows_on(N, D);
     switch (var) {
-        case 1416: hipLaunchKernelGGL((spmm_csr_rowblock_dual<4, 16>), g_, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
-        case 1404: hipLaunchKernelGGL((spmm_csr_rowblock_dual<4, 4>), g_, dim3(kT), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
-        case 1116: hipLaunchKernelGGL((spmm_csr_rowblock_dual<1, 16>), g_, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
-        default:   hipLaunchKernelGGL((spmm_csr_rowblock_dual<1, 4>), g_, dim3(kT), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
+        case 1416: LAUNCH_LR(spmm_csr_rowblock_dual, 4, 16, g_, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
+        case 1404: LAUNCH_LR(spmm_csr_rowblock_dual, 4, 4, g_, dim3(kT), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
+        case 1116: LAUNCH_LR(spmm_csr_rowblock_dual, 1, 16, g_, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
+        default:   LAUNCH_LR(spmm_csr_rowblock_dual, 1, 4, g_, dim3(kT), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
     }
     SGS_LAUNCH_OK();
     return SGS_OK;
@@ -2053,14 +2176,15 @@ int sgs_spmm_csr_multi(const float* X, int64_t x_stride, int64_t N, int64_t Dc, 
     if (N <= 65536 && nnz >= 16 * N) {        // the rowblock / row-per-lanes choice of sgs_spmm_csr, so every draw equals it
         const bool wide = nnz >= 256 * N;
         const dim3 g_(static_cast<unsigned>(N), Du);
+        const bool lr = spmm_long_rows_on(N, Dc);
         if (vec == 4 && wide)
-            hipLaunchKernelGGL((multi_spmm_csr_rowblock<4, 16>), g_, dim3(1024), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
+            LAUNCH_LR(multi_spmm_csr_rowblock, 4, 16, g_, dim3(1024), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
         else if (vec == 4)
-            hipLaunchKernelGGL((multi_spmm_csr_rowblock<4, 4>), g_, dim3(kT), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
+            LAUNCH_LR(multi_spmm_csr_rowblock, 4, 4, g_, dim3(kT), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
         else if (wide)
-            hipLaunchKernelGGL((multi_spmm_csr_rowblock<1, 16>), g_, dim3(1024), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
+            LAUNCH_LR(multi_spmm_csr_rowblock, 1, 16, g_, dim3(1024), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
         else
-            hipLaunchKernelGGL((multi_spmm_csr_rowblock<1, 4>), g_, dim3(kT), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
+            LAUNCH_LR(multi_spmm_csr_rowblock, 1, 4, g_, dim3(kT), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
     } else {
         DISPATCH_VEC_LPR_Y(multi_spmm_csr, vec, lpr, N, Du, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
     }
