@@ -888,6 +888,23 @@ int sgs_sddmm_csr_heads(const float* A, const float* B, int64_t N, int64_t K, in
  *   sgs_gatv2_dxl_heads (src-CSR): d_xl[j] (+)= sum over j's out-entries and loop of t, recomputed from g_logit / g_loop;
  *       accumulate != 0 adds onto d_xl's contents (the aggregation's d xl).
  * No float atomics, no host synchronisation: two identical launches give identical bits.
+ *   sgs_gatv2_alpha_heads_fwd_multi (batched ensemble evaluation, forward only, no attention dropout): sgs_gatv2_alpha_heads_fwd with
+ *       p_drop = 0 for all D draws of a pass in ONE launch (draw = blockIdx.y) over sgs_graph_filter_multi's draw-strided dst-CSRs:
+ *       in_ptr [D, N+1], in_src / in_eid [D, max(nnz, 1)].  Draw d reads xl / xr + d * x_stride (in floats), the shared att [K C], and --
+ *       with the edge term -- edge_w [D, max(nnz, 1)] by the DRAW's edge id (what in_eid holds: sgs_sample_topq_multi's st_weights) with
+ *       the shared lin_edge [K C]; edge_w == NULL: no edge term (lin_edge ignored).  It writes block d of alpha [D, max(nnz, 1), K] by the
+ *       draw's edge id and of alpha_loop [D, N, K].  Eval needs neither soft / soft_loop copies nor loop_w / loop_inv_cnt: none are taken,
+ *       none are written; the raw logits wait in `alpha` itself between the kernel's two sweeps (each lane re-reads only what it wrote).
+ *       Block d is BITWISE what sgs_gatv2_alpha_heads_fwd writes to alpha / alpha_loop for draw d's arrays with p_drop = 0, with and
+ *       without the edge term: both kernels instantiate one row-walk body (the same pre-activation, trip order, online max / sum,
+ *       shuffle order, 1 / (sum + 1e-16), zeros for drawn (i, i) entries), and the launch is sgs_gatv2_variant(SGS_GATV2_OP_ALPHA_FWD, N,
+ *       K, C, aligned16) of the base pointers, as the single-draw launcher chooses it.
+ *       x_stride is 0 (one [N, K C] pair shared by all draws: layer 1) or EXACTLY N K C (dense per-draw blocks: layer 2); every other
+ *       value is SGS_EINVAL.  Reason: the vector width (float4 or scalar) changes which channels a lane sums and so the bits of a logit.
+ *       With these two strides every draw's block has the base pointer's 16-byte alignment whenever C % 4 == 0, so block d takes the
+ *       variant a single-draw call on that block takes; a padded stride could not promise that.
+ *       Requires 0 <= N, nnz < 2^31, 1 <= D <= 65535, 1 <= K <= 16, C >= 1 ("bad sizes"); edge_w needs lin_edge; N = 0 returns SGS_OK with
+ *       nothing launched.  No workspace, no atomics, no memset nodes, no host synchronisation: capturable.
  *
  * sgs_gatv2_variant: which kernel instantiation and lane geometry an entry point launches, as a pure host function (the three launchers
  * and sgs_gatv2_alpha_heads_bwd_workspace_bytes decode its result, so the two cannot drift).  op: SGS_GATV2_OP_* below; aligned16 != 0:
@@ -910,6 +927,10 @@ int sgs_gatv2_alpha_heads_fwd(const float* xl, const float* xr, const float* att
                               int64_t K, int64_t C, int64_t n_edges, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid,
                               float negative_slope, float p_drop, uint64_t seed, uint32_t site, float* soft, float* soft_loop, float* alpha,
                               float* alpha_loop, float* loop_w, float* loop_inv_cnt, sgs_stream_t stream);
+int sgs_gatv2_alpha_heads_fwd_multi(const float* xl, const float* xr, int64_t x_stride, const float* att, const float* edge_w,
+                                    const float* lin_edge, int64_t N, int64_t K, int64_t C, int64_t D, int64_t nnz, const int32_t* in_ptr,
+                                    const int32_t* in_src, const int32_t* in_eid, float negative_slope, float* alpha, float* alpha_loop,
+                                    sgs_stream_t stream);
 size_t sgs_gatv2_alpha_heads_bwd_workspace_bytes(int64_t N, int64_t K, int64_t C);
 int sgs_gatv2_alpha_heads_bwd(const float* xl, const float* xr, const float* att, const float* edge_w, const float* lin_edge, const float* loop_w,
                               const float* loop_inv_cnt, int64_t N, int64_t K, int64_t C, int64_t n_edges, const int32_t* in_ptr,

@@ -49,17 +49,16 @@ __device__ __forceinline__ void zerov(float (&dst)[VEC]) {
 // head), running max and sum kept by every lane of the head; with the edge term the row's weights are summed on the way, so the loop's
 // mean weight is known when its trip comes.  Sweep 2: each lane re-reads the raw logits it wrote itself, normalises, applies the dropout
 // mask and writes soft / alpha; (i, i) entries get 0.
-template <int VEC, bool ONE>
-__global__ void __launch_bounds__(kT) gatv2_alpha_heads_fwd(const float* __restrict__ xl, const float* __restrict__ xr,
-                                                           const float* __restrict__ att, const float* __restrict__ w,
-                                                           const float* __restrict__ le, int64_t N, int K, int64_t C,
-                                                           const int* __restrict__ in_ptr, const int* __restrict__ in_src,
-                                                           const int* __restrict__ in_eid, float slope, float drop_scale, uint32_t drop_thresh,
-                                                           int use_drop, uint64_t seed, uint32_t site, const uint64_t* __restrict__ epoch,
-                                                           float* soft, float* __restrict__ soft_loop, float* __restrict__ alpha,
-                                                           float* __restrict__ alpha_loop, float* __restrict__ wbar, float* __restrict__ inv_cnt,
-                                                           int lg, int lgG) {
-    seed = fold_epoch(seed, epoch);
+// The row walk is one body, shared by the single-draw kernel and the multi-draw eval kernel below (EVAL: no dropout, no separate soft /
+// soft_loop copies, no wbar / inv_cnt outputs -- `soft` IS the alpha block then: the raw logits wait in it between the sweeps and sweep 2
+// overwrites them in place; `alpha`, `soft_loop`, `wbar`, `inv_cnt` are not touched).  Everything that decides a bit of the result is
+// common to both: v2_pre / lrelu, the trip order, the online max / sum, the shuffle order, 1 / (sum + 1e-16).  `soft` is read back, so
+// it is not restrict here or in either kernel; a caller must never hand one buffer in as both `soft` and `alpha`.
+template <int VEC, bool ONE, bool EVAL>
+__device__ __forceinline__ void v2_alpha_fwd_rows(const float* xl, const float* xr, const float* att, const float* w, const float* le, int64_t N,
+                                                  int K, int64_t C, const int* in_ptr, const int* in_src, const int* in_eid, float slope,
+                                                  float drop_scale, uint32_t drop_thresh, int use_drop, uint64_t seed, uint32_t site, float* soft,
+                                                  float* soft_loop, float* alpha, float* alpha_loop, float* wbar, float* inv_cnt, int lg, int lgG) {
     const int LPR = 1 << lg, G = 1 << lgG;
     const int sub = threadIdx.x & (LPR - 1);
     const int h = sub >> lgG, gl = sub & (G - 1);
@@ -70,6 +69,7 @@ __global__ void __launch_bounds__(kT) gatv2_alpha_heads_fwd(const float* __restr
     const int64_t ir = live ? i : 0;
     const int64_t D = static_cast<int64_t>(K) * C;
     const bool has_w = w != nullptr;
+    const bool drop = !EVAL && use_drop != 0;
     const int b = live ? in_ptr[i] : 0, deg = live ? in_ptr[i + 1] - b : 0;
     int trips = deg + 1;
     for (int o = 32; o > 0; o >>= 1) trips = max(trips, __shfl_xor(trips, o, 64));
@@ -147,20 +147,52 @@ __global__ void __launch_bounds__(kT) gatv2_alpha_heads_fwd(const float* __restr
             if (s != static_cast<int>(i)) {
                 sm = expf(soft[ed * K + h] - m) * inv;
                 al = sm;
-                if (use_drop) al = dropout_keep_at(seed, site, static_cast<uint64_t>(ed), static_cast<uint32_t>(h), drop_thresh) ? sm * drop_scale : 0.f;
+                if (drop) al = dropout_keep_at(seed, site, static_cast<uint64_t>(ed), static_cast<uint32_t>(h), drop_thresh) ? sm * drop_scale : 0.f;
             }
             soft[ed * K + h] = sm;
-            alpha[ed * K + h] = al;
+            if (!EVAL) alpha[ed * K + h] = al;
         }
         if (gl == 0) {
             const float sm = expf(lraw - m) * inv;
             float al = sm;
-            if (use_drop) al = dropout_keep_at(seed, site + 1u, static_cast<uint64_t>(i), static_cast<uint32_t>(h), drop_thresh) ? sm * drop_scale : 0.f;
-            soft_loop[i * K + h] = sm;
+            if (drop) al = dropout_keep_at(seed, site + 1u, static_cast<uint64_t>(i), static_cast<uint32_t>(h), drop_thresh) ? sm * drop_scale : 0.f;
+            if (!EVAL) soft_loop[i * K + h] = sm;
             alpha_loop[i * K + h] = al;
         }
     }
-    if (live && has_w && sub == 0) { wbar[i] = wb; inv_cnt[i] = icnt; }
+    if (!EVAL && live && has_w && sub == 0) { wbar[i] = wb; inv_cnt[i] = icnt; }
+}
+
+template <int VEC, bool ONE>
+__global__ void __launch_bounds__(kT) gatv2_alpha_heads_fwd(const float* __restrict__ xl, const float* __restrict__ xr,
+                                                           const float* __restrict__ att, const float* __restrict__ w,
+                                                           const float* __restrict__ le, int64_t N, int K, int64_t C,
+                                                           const int* __restrict__ in_ptr, const int* __restrict__ in_src,
+                                                           const int* __restrict__ in_eid, float slope, float drop_scale, uint32_t drop_thresh,
+                                                           int use_drop, uint64_t seed, uint32_t site, const uint64_t* __restrict__ epoch,
+                                                           float* soft, float* __restrict__ soft_loop, float* __restrict__ alpha,
+                                                           float* __restrict__ alpha_loop, float* __restrict__ wbar, float* __restrict__ inv_cnt,
+                                                           int lg, int lgG) {
+    seed = fold_epoch(seed, epoch);
+    v2_alpha_fwd_rows<VEC, ONE, false>(xl, xr, att, w, le, N, K, C, in_ptr, in_src, in_eid, slope, drop_scale, drop_thresh, use_drop, seed, site,
+                                       soft, soft_loop, alpha, alpha_loop, wbar, inv_cnt, lg, lgG);
+}
+
+// All D draws of a pass (ensemble evaluation: p = 0, forward only), draw = blockIdx.y, over graph_filter_multi's draw-strided in-CSRs
+// (in_ptr [D, N + 1], in_src / in_eid [D, nnz1]).  Draw d reads xl / xr + d * xs (0: one pair shared by all draws), w + d * nnz1 by the
+// draw's edge id, and writes block d of alpha [D, nnz1, K] and alpha_loop [D, N, K].  `alpha` holds the raw logits between the sweeps
+// (each lane re-reads only what it wrote itself), so it is NOT restrict; no soft / soft_loop / wbar / inv_cnt exist here.
+template <int VEC, bool ONE>
+__global__ void __launch_bounds__(kT) gatv2_alpha_heads_fwd_multi(const float* __restrict__ xl, const float* __restrict__ xr, int64_t xs,
+                                                                 const float* __restrict__ att, const float* __restrict__ w,
+                                                                 const float* __restrict__ le, int64_t N, int K, int64_t C, int64_t nnz1,
+                                                                 const int* __restrict__ in_ptr, const int* __restrict__ in_src,
+                                                                 const int* __restrict__ in_eid, float slope, float* alpha,
+                                                                 float* __restrict__ alpha_loop, int lg, int lgG) {
+    const int64_t d = blockIdx.y;
+    v2_alpha_fwd_rows<VEC, ONE, true>(xl + d * xs, xr + d * xs, att, w ? w + d * nnz1 : nullptr, le, N, K, C, in_ptr + d * (N + 1),
+                                      in_src + d * nnz1, in_eid + d * nnz1, slope, 1.0f, 0u, 0, 0, 0u, alpha + d * nnz1 * K, nullptr, nullptr,
+                                      alpha_loop + d * N * K, nullptr, nullptr, lg, lgG);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- backward, by destination
@@ -535,6 +567,42 @@ int sgs_gatv2_alpha_heads_fwd(const float* xl, const float* xr, const float* att
         else       hipLaunchKernelGGL((gatv2_alpha_heads_fwd<1, false>), grid, dim3(kT), 0, stream, SGS_V2_FWD_ARGS);
     }
 #undef SGS_V2_FWD_ARGS
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+// The vector width (float4 / scalar) changes which channels a lane sums and so the bits of a logit: block d has to take the variant a
+// single-draw call on that block takes.  Hence x_stride is 0 or exactly N K C: with C % 4 == 0 every draw's block then starts at the
+// base pointer's alignment (N K C floats are a multiple of 16 bytes), so one al16() of the bases decides for all draws, as it does for
+// the single-draw launcher; any other stride is refused rather than silently given another variant.
+int sgs_gatv2_alpha_heads_fwd_multi(const float* xl, const float* xr, int64_t x_stride, const float* att, const float* edge_w,
+                                    const float* lin_edge, int64_t N, int64_t K, int64_t C, int64_t D, int64_t nnz, const int32_t* in_ptr,
+                                    const int32_t* in_src, const int32_t* in_eid, float negative_slope, float* alpha, float* alpha_loop,
+                                    sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE_HEADS("sgs_gatv2_alpha_heads_fwd_multi");
+    SGS_REQUIRE(N >= 0 && N < (int64_t(1) << 31) && nnz >= 0 && nnz < (int64_t(1) << 31) && D >= 1 && D <= 65535, SGS_EINVAL,
+                "sgs_gatv2_alpha_heads_fwd_multi: bad sizes (need 0 <= N, nnz < 2^31 and 1 <= D <= 65535)");
+    SGS_REQUIRE(x_stride == 0 || x_stride == N * K * C, SGS_EINVAL,
+                "sgs_gatv2_alpha_heads_fwd_multi: x_stride = %lld: need 0 (one shared [N, K C] pair) or N K C = %lld (dense per-draw blocks)",
+                static_cast<long long>(x_stride), static_cast<long long>(N * K * C));
+    SGS_REQUIRE(!edge_w || lin_edge, SGS_EINVAL, "sgs_gatv2_alpha_heads_fwd_multi: null pointer (edge_w needs lin_edge)");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(xl && xr && att && in_ptr && alpha_loop && (nnz == 0 || (in_src && in_eid && alpha)), SGS_EINVAL,
+                "sgs_gatv2_alpha_heads_fwd_multi: null pointer");
+    const V2Choice g(sgs_gatv2_variant(SGS_GATV2_OP_ALPHA_FWD, N, K, C, al16(xl) && al16(xr) && al16(att) && (!edge_w || al16(lin_edge))));
+    const dim3 grid(static_cast<unsigned>(g.passes(N)), static_cast<unsigned>(D));
+    const int64_t nnz1 = nnz > 0 ? nnz : 1;
+#define SGS_V2_FWD_MULTI_ARGS                                                                                                        \
+    xl, xr, x_stride, att, edge_w, lin_edge, N, static_cast<int>(K), C, nnz1, in_ptr, in_src, in_eid, negative_slope, alpha, alpha_loop, g.lg, g.lgG
+    if (g.vec == 4) {
+        if (g.one) hipLaunchKernelGGL((gatv2_alpha_heads_fwd_multi<4, true>), grid, dim3(kT), 0, stream, SGS_V2_FWD_MULTI_ARGS);
+        else       hipLaunchKernelGGL((gatv2_alpha_heads_fwd_multi<4, false>), grid, dim3(kT), 0, stream, SGS_V2_FWD_MULTI_ARGS);
+    } else {
+        if (g.one) hipLaunchKernelGGL((gatv2_alpha_heads_fwd_multi<1, true>), grid, dim3(kT), 0, stream, SGS_V2_FWD_MULTI_ARGS);
+        else       hipLaunchKernelGGL((gatv2_alpha_heads_fwd_multi<1, false>), grid, dim3(kT), 0, stream, SGS_V2_FWD_MULTI_ARGS);
+    }
+#undef SGS_V2_FWD_MULTI_ARGS
     SGS_LAUNCH_OK();
     return SGS_OK;
 }

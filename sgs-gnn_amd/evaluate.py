@@ -17,7 +17,10 @@ their head is selected; without it these models keep the serial loop.  A GINMode
 (ops._drawn_gine_logits: the GINE aggregation of all draws in one launch per layer, at the input width; the plain batched GIN engine
 aggregates transformed features with unit weights and would be wrong for it) behind a fifth opt-in, `args.sgs_eval_batch_gine` (absent /
 None / False = off, True = on): it takes the engine iff that is True and "GIN" is among the selected heads; without it, it keeps the serial
-loop whatever else is set.  A GATModel(gat_v2=True) keeps the serial loop whatever the opt-ins say (no batched engine exists for it).
+loop whatever else is set.  A GATModel(gat_v2=True) has an engine of its own as well (ops._drawn_gatv2_logits: the gathering GATv2
+softmax of all draws in one launch per layer, sgs_gatv2_alpha_heads_fwd_multi) behind a sixth opt-in, `args.sgs_eval_batch_gatv2` (absent /
+None / False = off, True = on): it takes the engine iff that is True and "GAT" is among the selected heads, for every gat_heads in 1..16 with
+and without gat_edge_weight (sgs_eval_batch_variants is not consulted for it); without it, it keeps the serial loop whatever else is set.
 Under `args.sgs_cover_nodes` (node-covering draws) every model keeps the serial loop unless a fourth opt-in,
 `args.sgs_eval_batch_cover` (absent / None / False = off, True = on), is set: then the cover flag no longer blocks the engine, the other
 opt-ins decide exactly as they do without the flag, and every pass draws with ops.sample_topq_multi(..., cover=) -- row d is the serial
@@ -96,7 +99,7 @@ def _run(args, model, cluster_loader, device, q, mode, n_draws):
 
 
 def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str = "GCN", *, gat_heads: int = 1, gat_edge: bool = False,
-               cheb_k: int = 1, cover: bool = False, gine_in: int = 0) -> list:
+               cheb_k: int = 1, cover: bool = False, gine_in: int = 0, gat_v2: bool = False) -> list:
     """Draws per pass of the batched engine: a list of pass sizes summing to D, each >= 1.  `budget` is True (the largest pass whose
     per-draw buffers fit EVAL_BATCH_BUDGET bytes), an int number of bytes via ("bytes", n), or an int k >= 1 (at most k draws per pass).
     Per draw (an upper estimate of the engine's per-draw allocations): keys 4 E + mask E + filter positions 4 E; per drawn edge 40 B
@@ -115,7 +118,13 @@ def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str
     ops._drawn_gine_logits allocates per draw beside the counted hidden block and two logit blocks (the second MLP's two [N, C] products),
     4 N F + 8 N H: the first aggregate [N, F] at the input width, the first MLP's second product [N, H] and the second aggregate [N, H]
     (its unit weights are a NULL pointer and 1 + eps a scalar: neither is allocated; the straight-through weights are the 4 B per drawn
-    edge counted above).  The result of the engine does not depend on the split."""
+    edge counted above).  `gat_v2` (head "GAT" only; False = the numbers above for every head) describes the GATv2 head: GAT's term is
+    replaced by what ops._drawn_gatv2_logits allocates per draw beside the counted hidden block, the logits and the 4 B weight per drawn
+    edge, 4 q K + 4 N K + 16 N K C: attention values [q, K] and loop attentions [N, K] (one pair, reused by layer 2; eval takes no soft
+    copies and no mean loop weight / count, so gat_edge adds nothing), the layer-2 product [N, 2 K C] (lin_l and lin_r in one GEMM, the
+    biases added in place) and its two contiguous halves x_l, x_r [N, K C] each.  It is never below the GAT term at the same arguments
+    (12 N K C + 4 N C >= 8 N K + 8 N for K, C >= 1), so it never makes a pass larger than that term would.
+    The result of the engine does not depend on the split."""
     D = int(D)
     if D < 1:
         raise ValueError(f"plan_draws: D={D} draws")
@@ -126,12 +135,16 @@ def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str
     gine_in = int(gine_in)
     if gine_in < 0 or (gine_in and head != "GIN"):
         raise ValueError(f"plan_draws: gine_in={gine_in} with head={head!r}: need 0, or the GINE head's input width >= 1 with head 'GIN'")
+    if not isinstance(gat_v2, bool) or (gat_v2 and head != "GAT"):
+        raise ValueError(f"plan_draws: gat_v2={gat_v2!r} with head={head!r}: need False, or True with head 'GAT'")
     if budget is True or (isinstance(budget, tuple) and budget[0] == "bytes"):
         nbytes = EVAL_BATCH_BUDGET if budget is True else int(budget[1])
         ks = (int(E) + 63) & ~63
         per = 4 * ks + int(E) + 4 * int(E) + 40 * int(q) + 36 * (int(N) + 1) + 4 * int(N) * int(H) + 8 * int(N) * int(C) + 3 * 2048 * 4 + 64
         K = int(gat_heads)
-        if head == "GAT":
+        if head == "GAT" and gat_v2:
+            per += 4 * int(q) * K + 4 * int(N) * K + 16 * int(N) * K * int(C)
+        elif head == "GAT":
             per += 4 * int(q) * K + 12 * int(N) * K + 4 * int(N) * int(C) * (K - 1) + (8 * int(N) if gat_edge else 0)
         elif head == "GIN" and gine_in:
             per += 4 * int(N) * gine_in + 8 * int(N) * int(H)
@@ -154,8 +167,12 @@ def _batched_ok(args, model, n_draws) -> bool:
     """Whether this call takes the batched engine.  A falsy flag (False, None, 0) means off; anything else must be True or an
     int >= 1, and args.sgs_eval_batch_heads and args.sgs_eval_batch_variants (consulted only then) a valid head selection and None / a
     bool, all checked here, before any partition is read.  A model with gat_heads > 1, gat_edge_weight or cheb_k > 1 takes the engine only
-    with sgs_eval_batch_variants=True (per-head GAT kernels / per-draw Chebyshev steps, ops.ensemble_partition_head).  A gat_v2 model keeps
-    the serial loop whatever the opt-ins say: there is no batched GATv2 engine.  A gin_edge_weight model takes the engine
+    with sgs_eval_batch_variants=True (per-head GAT kernels / per-draw Chebyshev steps, ops.ensemble_partition_head).  A gat_v2 model takes
+    the engine (ops._drawn_gatv2_logits, the multi-draw GATv2 softmax) iff args.sgs_eval_batch_gatv2 is True and "GAT" is a selected head,
+    for every gat_heads in 1..16 with and without gat_edge_weight: sgs_eval_batch_variants is not consulted for it, and without the opt-in
+    it keeps the serial loop whatever else is set (the v1 engines take node-level scores, which GATv2 has none of).  sgs_eval_batch_gatv2
+    is validated with the other opt-ins (None / a bool, only when sgs_eval_batch is truthy); absent, None or False it changes no model's
+    routing.  A gin_edge_weight model takes the engine
     (ops._drawn_gine_logits, the multi-draw GINE aggregation) iff args.sgs_eval_batch_gine is True and "GIN" is a selected head; the
     plain batched GIN engine (ops._drawn_gin_logits) aggregates transformed features with unit weights, which is not the GINE layer, so
     without that opt-in the model keeps the serial loop whatever else is set.  sgs_eval_batch_gine is validated with the other opt-ins
@@ -176,6 +193,9 @@ def _batched_ok(args, model, n_draws) -> bool:
     variants = _eval_variants(args)
     _eval_batch_cover(args)
     gine = _eval_batch_gine(args)
+    gatv2 = _eval_batch_gatv2(args)
+    if n_draws >= 1 and gatv2 and getattr(model, "gat_v2", False):
+        return _head_of(model) == "GAT" and "GAT" in heads and 1 <= getattr(model, "gat_heads", 1) <= 16
     if n_draws < 1 or getattr(model, "gat_v2", False) or (getattr(model, "gin_edge_weight", False) and not gine):
         return False
     if not variants:                            # without the third opt-in the heads' options keep the serial loop, as before it existed
@@ -194,6 +214,16 @@ def _eval_batch_cover(args) -> bool:
     if v is True:
         return True
     raise ValueError(f"args.sgs_eval_batch_cover={v!r}: need None, False or True")
+
+
+def _eval_batch_gatv2(args) -> bool:
+    """args.sgs_eval_batch_gatv2: absent / None / False -> False, True -> True.  Anything else raises ValueError."""
+    v = getattr(args, "sgs_eval_batch_gatv2", None)
+    if v is None or v is False:
+        return False
+    if v is True:
+        return True
+    raise ValueError(f"args.sgs_eval_batch_gatv2={v!r}: need None, False or True")
 
 
 def _eval_batch_gine(args) -> bool:
@@ -272,6 +302,8 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
                    cheb_k=getattr(model, "cheb_k", 1), cover=cover_nodes(args))       # (under the flag only with sgs_eval_batch_cover: _batched_ok)
     if getattr(model, "gin_edge_weight", False):
         variant["gine_in"] = model.GIN.convs[0].in_channels                          # (here only with sgs_eval_batch_gine: _batched_ok)
+    if getattr(model, "gat_v2", False):
+        variant["gat_v2"] = True                                                     # (here only with sgs_eval_batch_gatv2: _batched_ok)
     with torch.no_grad():
         for batch in cluster_loader:
             batch = batch.to(device)

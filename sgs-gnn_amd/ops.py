@@ -2782,6 +2782,77 @@ def _drawn_gat_heads_logits(parent: Graph, smp: MultiSampleResult, convs, xl1, a
     return _spmm_heads_multi(z, N * K * C, csr, alpha[0], alpha[1], HEADS_CONCAT if c2.concat else HEADS_MEAN, c2.bias, ACT_NONE, q, N, K, C)
 
 
+def gatv2_alpha_heads_multi(xl, xr, x_stride: int, att, csr, q: int, N: int, K: int, negative_slope: float, edge_w=None, lin_edge=None, out=None):
+    """sgs_gatv2_alpha_heads_fwd_multi over graph_filter_multi's CSRs: (alpha [D, max(q, 1), K] by the draw's edge id, alpha_loop
+    [D, max(N, 1), K]), block d bitwise what sgs_gatv2_alpha_heads_fwd (p = 0) writes for draw d with xl_d / xr_d = xl / xr + d * x_stride
+    (0: one [N, K C] pair shared by all draws; exactly N K C: dense [D, N, K C] blocks; nothing else: the kernel's vector width, and with
+    it the bits, must be the single-draw call's for every block).  att with K C elements; `edge_w` [D, q] by the draw's edge id
+    (sample_topq_multi(..., want_w=True).w) comes with `lin_edge` (lin_edge.weight, K C elements), both None = no edge term.  `out`: reuse
+    an (alpha, alpha_loop) pair of these shapes.  Forward only (eval: no attention dropout): no autograd node."""
+    L = _lib.lib()
+    _need_gpu(xl, xr, att, edge_w, lin_edge)
+    in_ptr, in_src, in_eid = csr[0], csr[1], csr[2]
+    D = in_ptr.shape[0]
+    K, x_stride = int(K), int(x_stride)
+    if att.dtype != torch.float32 or att.numel() % K != 0 or att.numel() < K:
+        raise RuntimeError(f"gatv2_alpha_heads_multi: att must be float32 with K C elements (K={K})")
+    W = att.numel()
+    C = W // K
+    if x_stride not in (0, N * W):
+        raise RuntimeError(f"gatv2_alpha_heads_multi: x_stride={x_stride}: need 0 (one shared pair) or N K C = {N * W} (dense per-draw blocks)")
+    need = (D - 1) * x_stride + N * W
+    for name, t in (("xl", xl), ("xr", xr)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != need:
+            raise RuntimeError(f"gatv2_alpha_heads_multi: {name} must be contiguous float32 with (D - 1) x_stride + N K C = {need} elements")
+    if edge_w is not None and lin_edge is None:
+        raise RuntimeError("gatv2_alpha_heads_multi: edge_w needs lin_edge")
+    if edge_w is not None and (tuple(edge_w.shape) != (D, q) or edge_w.dtype != torch.float32):
+        raise RuntimeError(f"gatv2_alpha_heads_multi: edge_w must be float32 [D={D}, q={q}]")
+    if edge_w is not None and (lin_edge.numel() != W or lin_edge.dtype != torch.float32):
+        raise RuntimeError(f"gatv2_alpha_heads_multi: lin_edge must be float32 with {W} elements")
+    if tuple(in_ptr.shape) != (D, N + 1) or tuple(in_src.shape) != (D, max(q, 1)) or tuple(in_eid.shape) != (D, max(q, 1)):
+        raise RuntimeError(f"gatv2_alpha_heads_multi: csr must be graph_filter_multi's arrays for D={D}, N={N}, q={q}")
+    f32 = dict(dtype=torch.float32, device=in_ptr.device)
+    if out is not None:
+        alpha, alpha_loop = out
+        if tuple(alpha.shape) != (D, max(q, 1), K) or tuple(alpha_loop.shape) != (D, max(N, 1), K) or not alpha.is_contiguous() \
+                or not alpha_loop.is_contiguous() or alpha.dtype != torch.float32 or alpha_loop.dtype != torch.float32:
+            raise RuntimeError(f"gatv2_alpha_heads_multi: out must be contiguous float32 ([{D}, {max(q, 1)}, {K}], [{D}, {max(N, 1)}, {K}])")
+    else:
+        alpha, alpha_loop = torch.empty(D, max(q, 1), K, **f32), torch.empty(D, max(N, 1), K, **f32)
+    edge = edge_w is not None and q > 0                               # without edges every loop carries weight 0: the term vanishes
+    w = edge_w.contiguous() if edge else None
+    le = lin_edge.reshape(W).contiguous() if edge else None
+    _lib.check(L.sgs_gatv2_alpha_heads_fwd_multi(_ptr(xl), _ptr(xr), x_stride, _ptr(att.reshape(W).contiguous()), _ptr(w), _ptr(le), N, K, C, D, q,
+                                                 _ptr(in_ptr), _ptr(in_src), _ptr(in_eid), float(negative_slope), _ptr(alpha), _ptr(alpha_loop),
+                                                 _stream()), "sgs_gatv2_alpha_heads_fwd_multi")
+    return alpha, alpha_loop
+
+
+def _drawn_gatv2_logits(parent: Graph, smp: MultiSampleResult, convs, xl1, xr1, w=None):
+    """Logits [D, N, C] of the two GATv2Conv layers (eval: no attention dropout) over each of the D drawn subgraphs of `parent`, every
+    1 <= heads <= 16: one gatv2_alpha_heads_multi launch and one _spmm_heads_multi launch per layer for all draws.  Layer 1 (concat, ReLU)
+    runs over the shared xl1 = lin_l(x), xr1 = lin_r(x) (x_stride = 0).  Layer 2 (head mean) takes one library product over the [D N, H]
+    hidden rows with cat(lin_l.weight, lin_r.weight) plus the two biases -- GATv2Conv.forward's call --, sliced into contiguous
+    xl2 / xr2 [D, N, K C] (x_stride = N K C); the alpha buffers are reused.  `w` [D, q] (the draws' straight-through weights) adds the edge
+    term with each layer's lin_edge.weight, as edge_weight does in GAT.forward; None = no edge term."""
+    D, q, N = smp.D, smp.q, parent.N
+    c1, c2 = convs
+    K = c1.heads
+    csr = graph_filter_multi(parent, smp)
+    edge = (lambda c: dict(edge_w=w, lin_edge=c.lin_edge.weight)) if w is not None else (lambda c: {})
+    alpha = gatv2_alpha_heads_multi(xl1, xr1, 0, c1.att, csr, q, N, K, c1.negative_slope, **edge(c1))
+    H = xl1.shape[1]
+    h = _spmm_heads_multi(xl1, 0, csr, alpha[0], alpha[1], HEADS_CONCAT if c1.concat else HEADS_MEAN, c1.bias, ACT_RELU, q, N, K, H // K)
+    W2 = c2.heads * c2.out_channels
+    y = linear_nobias(h.view(D * N, -1), torch.cat([c2.lin_l.weight, c2.lin_r.weight], 0))
+    y += torch.cat([c2.lin_l.bias, c2.lin_r.bias])                   # in place: the same sums as GATv2Conv.forward's, no second [D N, 2 K C]
+    xl2, xr2 = y[:, :W2].contiguous(), y[:, W2:].contiguous()
+    alpha = gatv2_alpha_heads_multi(xl2, xr2, N * W2, c2.att, csr, q, N, K, c2.negative_slope, out=alpha, **edge(c2))
+    return _spmm_heads_multi(xl2, N * W2, csr, alpha[0], alpha[1], HEADS_CONCAT if c2.concat else HEADS_MEAN, c2.bias, ACT_NONE, q, N, K,
+                             c2.out_channels)
+
+
 def cheb_norm_multi(parent: Graph, smp: MultiSampleResult, csr, w=None):
     """sgs_cheb_norm_fwd_multi: (dis [D, N], l_in [D, q]) of the D drawn subgraphs, row d bitwise sgs_cheb_norm_fwd's dis / l_in for draw d.
     `w` [D, q] by the draw's edge id, or None (unit weights).  The by-source degree walks the parent's out-CSR under each draw's mask."""
@@ -2848,7 +2919,9 @@ def ensemble_partition_head(batch, model, q: int, mode: int, p, passes, counts, 
     lists.  One-head GAT without the edge term and GIN ignore edge weights, so no straight-through weights are drawn for them; GAT with
     gat_edge_weight, Chebyshev K >= 2 and GIN with gin_edge_weight (the GINE layers, _drawn_gine_logits: nothing to precompute, the
     aggregation reads x itself) take them (learned mode; the other modes have none: no edge term / unit weights, as edge_weight=None in
-    the model).  GAT with heads >= 2 or the edge term runs on the per-head kernels (_drawn_gat_heads_logits).
+    the model).  GAT with heads >= 2 or the edge term runs on the per-head kernels (_drawn_gat_heads_logits).  A GATModel(gat_v2=True)
+    runs on the gathering GATv2 softmax of all draws (_drawn_gatv2_logits; per partition: x_l = lin_l(x) and x_r = lin_r(x) as one
+    product), every head count, with the straight-through weights iff gat_edge_weight (learned mode).
     `cover` (get_graph(edge_index, N) or None) goes to every sample_topq_multi call, the Chebyshev K = 1 trace-only draw included."""
     from .model import ChebModel, GATModel, GINModel, GNNModel
     if isinstance(model, GNNModel):
@@ -2857,7 +2930,15 @@ def ensemble_partition_head(batch, model, q: int, mode: int, p, passes, counts, 
     N = x.shape[0]
     weighted = mode == SAMPLE_LEARNED and p is not None              # the draws carry straight-through weights
     want_w = False
-    if isinstance(model, GATModel):
+    if isinstance(model, GATModel) and model.gat_v2:
+        convs = tuple(model.GAT.convs)                                # GATv2Conv: the softmax gathers rows of x_l and x_r
+        W1 = convs[0].heads * convs[0].out_channels
+        y1 = linear_nobias(x, torch.cat([convs[0].lin_l.weight, convs[0].lin_r.weight], 0)) + torch.cat([convs[0].lin_l.bias, convs[0].lin_r.bias])
+        xl1, xr1 = y1[:, :W1].contiguous(), y1[:, W1:].contiguous()  # GATv2Conv.forward's call: bitwise the serial path's x_l, x_r
+        edge = weighted and convs[0].edge_dim is not None             # GAT.forward: the edge term needs edge_dim and weights
+        want_w = edge
+        logits = lambda parent, smp: _drawn_gatv2_logits(parent, smp, convs, xl1, xr1, smp.w if edge else None)
+    elif isinstance(model, GATModel):
         convs = tuple(model.GAT.convs)
         xl1 = convs[0].lin_src(x).contiguous()                        # the serial path's call: bitwise the same x'
         K = convs[0].heads
