@@ -659,6 +659,28 @@ int sgs_masked_correct(const float* logits, int64_t N, int64_t C, const int64_t*
 int sgs_masked_correct_pair(const float* logits_a, const float* logits_b, int64_t N, int64_t C, const int64_t* y,
                             const uint8_t* train_mask, int32_t* correct4, sgs_stream_t stream);
 
+/* Per-split confusion counts of an evaluation (macro / weighted F1, per-class precision and recall): for every row i and every split s
+ * with m_s[i] != 0, conf[s][y_i][argmax_c logits[i, c]] += 1.  conf is int64 [3, C, C] (split, true class, predicted class) and is
+ * ACCUMULATED: the call never clears it (the caller zeroes it once per evaluation).  The argmax is sgs_masked_correct's (torch.argmax: the
+ * first maximum wins, a row of -inf predicts class 0); NaN logits are out of scope.  A row may be in several masks and is counted in
+ * each.  y_i is read only for rows in at least one mask; rows outside every mask may hold any label.  Contract: labels of masked rows
+ * lie in [0, C) (a masked row that breaks it is skipped, never used as an index).  Integer atomics only: the result does not depend on
+ * arrival order.  One launch, no workspace, no host synchronisation (capturable).  N = 0: SGS_OK, nothing launched; N < 2^32.
+ * Two forms: 1 = direct (every C): one wave per row, lane 0 issues up to three non-returning 64-bit global adds;  2 = privatised
+ * (12 C^2 <= 65536 bytes, i.e. C <= 73, and N < 2^31): a workgroup of 16 waves keeps an int32 [3, C, C] histogram in LDS over a
+ * grid-stride loop (at most one workgroup per CU) and adds its non-zero cells to conf at the end.
+ * sgs_confusion_variant(N, C): which form a call launches now (pure host function, needs no GPU): 1 or 2; 0 for N = 0 (nothing); -1 when the
+ *   call would return SGS_EINVAL (N < 0, C < 1, or form 2 forced on a shape outside its range).  Automatic rule: 2 iff C <= 12 and
+ *   4096 <= N < 2^31, else 1.  Measured ("Per-class evaluation metrics"): the direct form's adds queue up per
+ *   128-byte line of conf (3 C^2 / 16 lines), so form 2 wins at few classes and many rows (C = 5: 16.6 against 90.3 us at N = 33 869,
+ *   from N = 4096 on; C = 12: 16.1 against 21.2 us) and loses from C = 16 on (C = 41, N = 232 965: 91.1 against 65.1 us).
+ * sgs_confusion_variant_set(code): 0 = automatic (default), 1 = direct, 2 = privatised; other codes SGS_EINVAL (the setting is kept).  Forcing 2
+ *   makes calls with C > 73 return SGS_EINVAL without a launch.  Read when a call launches; for A/B timing and tests. */
+int sgs_confusion_counts(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* m0, const uint8_t* m1, const uint8_t* m2,
+                         int64_t* conf, sgs_stream_t stream);
+int sgs_confusion_variant(int64_t N, int64_t C);
+int sgs_confusion_variant_set(int code);
+
 /* The gate of training_hybrid.py:95-103 in two launches, no zero fill, no atomics: out5[0..3] = (#correct_a, #train, #correct_b, #train)
  * (argmax of each logit matrix against y on the train rows; lowest index on ties), out5[4] = 0.  With dst_host_mapped (pinned,
  * device-mapped host int32[5]) the finishing launch also hands the four counts to the host as sgs_publish_to_host does (payload, then

@@ -4,6 +4,9 @@
 // (`consistency_loss`).  The reference copies logits to the host for sklearn's micro-F1, runs
 // two sort-based torch.isin calls and one .item() sync for reg1; here everything stays on the
 // device and every reduction uses a fixed tree (deterministic).
+#include <algorithm>
+#include <atomic>
+
 #include "sgs_common.h"
 
 namespace sgs {
@@ -577,6 +580,81 @@ __global__ void __launch_bounds__(kT) ensemble_mean_correct(const float* __restr
     }
 }
 
+// ---------------------------------------------------------------- per-split confusion counts (evaluate.py: macro / weighted F1, per-class report)
+// conf[s][y_i][argmax_c logits[i, c]] += 1 for every row i and split s with m_s[i] != 0; conf is int64 [3, C, C], accumulated.  Integer
+// atomics only, so the matrix does not depend on arrival order.  A row outside every mask is left before its label is read; a masked row
+// whose label is outside [0, C) breaks the contract and is skipped, never used as an index.
+__device__ __forceinline__ int wave_row_argmax(const float* __restrict__ row, int64_t C, int lane) {      // valid in every lane (C >= 1)
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    lane_argmax(row, C, lane, best, bi);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; }
+    }
+    return bi;
+}
+
+// Direct form: one wave per row, lane 0 issues up to three non-returning 64-bit global adds.
+__global__ void __launch_bounds__(kT) confusion_direct(const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
+                                                      const uint8_t* __restrict__ m0, const uint8_t* __restrict__ m1,
+                                                      const uint8_t* __restrict__ m2, unsigned long long* __restrict__ conf) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+    if (i >= N) return;
+    const bool in0 = m0[i] != 0, in1 = m1[i] != 0, in2 = m2[i] != 0;
+    if (!(in0 || in1 || in2)) return;
+    const int bi = wave_row_argmax(logits + i * C, C, lane);
+    if (lane != 0) return;
+    const int64_t t = y[i];
+    if (t < 0 || t >= C) return;
+    const int64_t cell = t * C + bi;
+    if (in0) atomicAdd(&conf[cell], 1ull);
+    if (in1) atomicAdd(&conf[C * C + cell], 1ull);
+    if (in2) atomicAdd(&conf[2 * C * C + cell], 1ull);
+}
+
+// Privatised form (12 C^2 <= 65536 bytes of LDS, N < 2^31): a workgroup of 16 waves keeps an int32 [3, C, C] histogram in LDS, walks rows
+// in a grid-stride loop and adds only its non-zero cells to conf at the end: the hot cells (the diagonal of a trained model) take one
+// global add per workgroup instead of one per row.
+constexpr int kConfT = 1024;
+__global__ void __launch_bounds__(kConfT) confusion_private(const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
+                                                           const uint8_t* __restrict__ m0, const uint8_t* __restrict__ m1,
+                                                           const uint8_t* __restrict__ m2, unsigned long long* __restrict__ conf) {
+    extern __shared__ int hist[];
+    const int cells = 3 * static_cast<int>(C * C);
+    for (int k = threadIdx.x; k < cells; k += kConfT) hist[k] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int cc = static_cast<int>(C * C);
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * (kConfT / 64) + wid; i < N; i += static_cast<int64_t>(gridDim.x) * (kConfT / 64)) {
+        const bool in0 = m0[i] != 0, in1 = m1[i] != 0, in2 = m2[i] != 0;
+        if (!(in0 || in1 || in2)) continue;
+        const int bi = wave_row_argmax(logits + i * C, C, lane);
+        if (lane != 0) continue;
+        const int64_t t = y[i];
+        if (t < 0 || t >= C) continue;
+        const int cell = static_cast<int>(t * C) + bi;
+        if (in0) atomicAdd(&hist[cell], 1);
+        if (in1) atomicAdd(&hist[cc + cell], 1);
+        if (in2) atomicAdd(&hist[2 * cc + cell], 1);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < cells; k += kConfT) {
+        const int v = hist[k];
+        if (v) atomicAdd(&conf[k], static_cast<unsigned long long>(v));
+    }
+}
+
+constexpr int64_t kConfPrivMaxC = 73;             // 12 * 73^2 = 63 948 <= 65 536 bytes of LDS; 74 needs 65 712
+// The automatic rule (include/sgs_hip.h; measurements in DESIGN.md section 5, "Per-class evaluation metrics"): the direct form's adds
+// queue up per 128-byte line of conf, 3 C^2 / 16 lines in all, so it loses only at few classes and many rows.
+constexpr int64_t kConfAutoMaxC = 12;
+constexpr int64_t kConfAutoMinRows = 4096;
+std::atomic<int> g_conf_variant{0};
+
 }  // namespace
 }  // namespace sgs
 
@@ -821,6 +899,48 @@ int sgs_ensemble_mean_correct(const float* logits, int64_t x_stride, int64_t Dc,
     const float inv = 1.0f / static_cast<float>(D_total);
     hipLaunchKernelGGL(ensemble_mean_correct, dim3(cdiv(N * 64, kT)), dim3(kT), 0, stream, logits, x_stride, static_cast<int>(Dc), N, C, acc,
                        first, last, static_cast<int>(D_total), inv, y, mask0, mask1, mask2, reinterpret_cast<unsigned long long*>(counts));
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_confusion_variant_set(int code) {
+    SGS_REQUIRE(code >= 0 && code <= 2, SGS_EINVAL, "sgs_confusion_variant_set: code %d, need 0 (automatic), 1 (direct) or 2 (privatised)", code);
+    g_conf_variant.store(code);
+    return SGS_OK;
+}
+
+int sgs_confusion_variant(int64_t N, int64_t C) {
+    if (N < 0 || C < 1) return -1;
+    if (N == 0) return 0;
+    const bool priv_ok = C <= kConfPrivMaxC && N < (int64_t(1) << 31);
+    switch (g_conf_variant.load()) {
+        case 1: return 1;
+        case 2: return priv_ok ? 2 : -1;
+        default: return priv_ok && C <= kConfAutoMaxC && N >= kConfAutoMinRows ? 2 : 1;
+    }
+}
+
+int sgs_confusion_counts(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* m0, const uint8_t* m1, const uint8_t* m2,
+                         int64_t* conf, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(N >= 0 && N < (int64_t(1) << 32) && C >= 1 && C < (int64_t(1) << 24) && conf, SGS_EINVAL, "sgs_confusion_counts: bad arguments");
+    if (N == 0) return SGS_OK;
+    SGS_REQUIRE(logits && y && m0 && m1 && m2, SGS_EINVAL, "sgs_confusion_counts: null pointer");
+    const int var = sgs_confusion_variant(N, C);
+    SGS_REQUIRE(var > 0, SGS_EINVAL, "sgs_confusion_counts: the privatised form (forced by sgs_confusion_variant_set(2)) needs C <= 73 and N < 2^31");
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(conf);
+    if (var == 1) {
+        hipLaunchKernelGGL(confusion_direct, dim3(cdiv(N * 64, kT)), dim3(kT), 0, stream, logits, N, C, y, m0, m1, m2, out);
+    } else {
+        static const int cus = [] {
+            int dev = 0, n = 0;
+            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
+            return n;
+        }();
+        const int64_t grid = std::min<int64_t>(cdiv(N, kConfT / 64), cus);
+        hipLaunchKernelGGL(confusion_private, dim3(static_cast<unsigned>(grid)), dim3(kConfT), static_cast<size_t>(12 * C * C), stream, logits, N, C, y,
+                           m0, m1, m2, out);
+    }
     SGS_LAUNCH_OK();
     return SGS_OK;
 }

@@ -25,6 +25,16 @@ Under `args.sgs_cover_nodes` (node-covering draws) every model keeps the serial 
 `args.sgs_eval_batch_cover` (absent / None / False = off, True = on), is set: then the cover flag no longer blocks the engine, the other
 opt-ins decide exactly as they do without the flag, and every pass draws with ops.sample_topq_multi(..., cover=) -- row d is the serial
 loop's d-th covering draw.  `PATH_COUNTS` records which path each ensemble_evaluate call took.
+
+Per-class metrics (both functions, the serial loop and every batched engine): `args.sgs_f1_average` (absent / None / "micro" = the accuracy
+triple as ever; "macro" / "weighted" = the returned triple holds that F1 average) and `args.sgs_eval_report` (absent / None = off; a dict
+receives "confusion", an int64 CPU tensor [3, C, C] (split, true class, predicted class), and "report", utils.classification_report of it;
+both None for an empty loader).  When either asks for per-class counts, one [3, C, C] int64 buffer is zeroed per evaluation, every partition
+adds one ops.confusion_counts launch on its final mean logits, and the buffer is read once after the loader is exhausted; otherwise nothing
+new is launched or allocated, and with "micro" the triple always comes from the six counters.  The averages are POOLED over the loader:
+they are taken from the confusion matrix of all masked nodes of all partitions.  (The reference, with its macro line switched on, would
+weight per-partition macro values by partition size; the two agree for micro and on a one-partition loader.  The pooled value does not
+depend on how the graph was partitioned and does not drop a class from the partitions where it happens to be absent.)
 """
 from __future__ import annotations
 
@@ -32,6 +42,7 @@ import torch
 
 from . import ops
 from .model import _DropoutClock
+from .utils import F1_AVERAGES, classification_report, f1_from_confusion
 from .sampling import _NoiseClock, cover_graph, cover_nodes, draw_learned, draw_prior, random_edge_sampling
 
 PATH_COUNTS = {"serial": 0, "batched": 0}
@@ -63,10 +74,44 @@ def _one_draw(args, model, batch, q, mode, edge_probs, noise):
     raise ValueError("Invalid mode. Choose 'learned', 'random', or 'full'.")
 
 
+def _f1_opts(args):
+    """(average, report dict or None, whether per-class counts are needed) from args.sgs_f1_average and args.sgs_eval_report; a bad value
+    raises ValueError here, before any partition is read."""
+    avg = getattr(args, "sgs_f1_average", None)
+    if avg is None:
+        avg = "micro"
+    if not isinstance(avg, str) or avg not in F1_AVERAGES:
+        raise ValueError(f"args.sgs_f1_average={avg!r}: need None or one of {F1_AVERAGES}")
+    rep = getattr(args, "sgs_eval_report", None)
+    if rep is not None and not isinstance(rep, dict):
+        raise ValueError(f"args.sgs_eval_report={rep!r}: need None or a dict (it receives 'confusion' and 'report')")
+    return avg, rep, avg != "micro" or rep is not None
+
+
+def _add_confusion(conf, out, batch):
+    """One partition's confusion counts of its final mean logits `out`, added to the evaluation's buffer (made on the first partition)."""
+    if conf is None:
+        conf = torch.zeros(3, out.shape[1], out.shape[1], dtype=torch.int64, device=out.device)
+    return ops.confusion_counts(out, batch.y, (batch.train_mask, batch.val_mask, batch.test_mask), out=conf)
+
+
+def _finish(avg, rep, conf, micro):
+    """The triple to return: `micro` (from the six counters) unless another average was asked for; fills the report dict."""
+    if rep is not None:
+        rep["confusion"] = rep["report"] = None
+    if conf is None:
+        return micro
+    M = conf.cpu()
+    if rep is not None:
+        rep["confusion"], rep["report"] = M, classification_report(M)
+    return micro if avg == "micro" else f1_from_confusion(M, avg)
+
+
 def _run(args, model, cluster_loader, device, q, mode, n_draws):
     cover_nodes(args)                       # args.sgs_cover_nodes: validated before any partition is read
+    avg, rep, per_class = _f1_opts(args)
     model.eval()
-    counts = None
+    counts = conf = None
     noises = list(getattr(args, "_sgs_noise_eval", None) or [])
     trace = getattr(args, "_sgs_trace_eval", None)
     with torch.no_grad():
@@ -91,11 +136,13 @@ def _run(args, model, cluster_loader, device, q, mode, n_draws):
                 trace["logits"], trace["mean"], trace["edges"] = torch.stack(logs), out, torch.stack(edges)
             c = torch.stack([ops.masked_correct(out, batch.y, m) for m in (batch.train_mask, batch.val_mask, batch.test_mask)])
             counts = c.to(torch.int64) if counts is None else counts + c
+            if per_class:
+                conf = _add_confusion(conf, out, batch)
     if counts is None:
-        return 0, 0, 0
+        return _finish(avg, rep, None, (0, 0, 0))
     c = counts.tolist()
     # sum_b f1_b * n_b / sum_b n_b  ==  sum_b correct_b / sum_b n_b   (utils.calculate_f1 is accuracy)
-    return tuple((c[s][0] / c[s][1]) if c[s][1] > 0 else 0 for s in range(3))
+    return _finish(avg, rep, conf, tuple((c[s][0] / c[s][1]) if c[s][1] > 0 else 0 for s in range(3)))
 
 
 def plan_draws(E: int, q: int, N: int, H: int, C: int, D: int, budget, head: str = "GCN", *, gat_heads: int = 1, gat_edge: bool = False,
@@ -291,8 +338,9 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
     if mode not in ('learned', 'random', 'edge', 'full'):
         raise ValueError("Invalid mode. Choose 'learned', 'random', or 'full'.")
     flag = args.sgs_eval_batch
+    avg, rep, per_class = _f1_opts(args)
     model.eval()
-    counts = None
+    counts = conf = None
     noises = list(getattr(args, "_sgs_noise_eval", None) or [])
     trace = getattr(args, "_sgs_trace_eval", None)
     head = _head_of(model)
@@ -321,6 +369,8 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
                 if trace is not None:
                     trace["logits"], trace["mean"] = out.unsqueeze(0).expand(n_draws, *out.shape), acc
                     trace["edges"] = batch.edge_index.unsqueeze(0).expand(n_draws, *batch.edge_index.shape)
+                if per_class:
+                    conf = _add_confusion(conf, acc, batch)
                 continue
             if mode == 'learned':
                 ops.get_pairs(batch.edge_index, N, build=True)
@@ -345,15 +395,17 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
                         _NoiseClock.tick += n
                     d += n
                     k -= n
-            ops.ensemble_partition_head(batch, model, q, kind, p, passes, counts, trace, cover=cover_graph(args, batch))
+            acc = ops.ensemble_partition_head(batch, model, q, kind, p, passes, counts, trace, cover=cover_graph(args, batch))
+            if per_class:
+                conf = _add_confusion(conf, acc, batch)                              # the mean the last sgs_ensemble_mean_correct pass left
             # GNNModel.forward and GAT.forward take one dropout seed per call, in eval mode too (GIN and Cheb none): leave the dropout
             # clock where the serial loop's n_draws forwards leave it, so that training after an evaluation draws the same masks whichever
             # path evaluated
             _DropoutClock.tick += n_draws * ticks
     if counts is None:
-        return 0, 0, 0
+        return _finish(avg, rep, None, (0, 0, 0))
     c = counts.tolist()
-    return tuple((c[2 * s] / c[2 * s + 1]) if c[2 * s + 1] > 0 else 0 for s in range(3))
+    return _finish(avg, rep, conf, tuple((c[2 * s] / c[2 * s + 1]) if c[2 * s + 1] > 0 else 0 for s in range(3)))
 
 
 def evaluate(args, model, cluster_loader, device, q=500, mode=None, temperature=1.0):

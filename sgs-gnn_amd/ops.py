@@ -1230,6 +1230,38 @@ def masked_correct(logits, y, train_mask, out=None) -> torch.Tensor:
     return out
 
 
+def confusion_counts(logits, y, masks, out=None) -> torch.Tensor:
+    """int64 [3, C, C] on device: out[s][t][p] += #{rows i in masks[s] with y_i == t and argmax logits[i] == p} (sgs_confusion_counts; the
+    argmax is masked_correct's).  `out` is accumulated into when given, else a zeroed buffer is made.  Labels of masked rows lie in
+    [0, C); rows outside every mask may hold any label.  No host sync."""
+    L = _lib.lib()
+    _need_gpu(logits, y, *masks)
+    N, C = logits.shape
+    if len(masks) != 3:
+        raise RuntimeError("confusion_counts: need three masks (train, val, test)")
+    if out is None:
+        out = torch.zeros(3, C, C, dtype=torch.int64, device=logits.device)
+    elif out.shape != (3, C, C) or not out.is_contiguous():
+        raise RuntimeError(f"confusion_counts: out must be a contiguous int64 [3, {C}, {C}] tensor")
+    lg, m = logits.contiguous(), [_u8(x) for x in masks]
+    if any(x.numel() != N for x in m) or y.numel() != N:
+        raise RuntimeError("confusion_counts: y and the masks need one entry per row of logits")
+    _lib.check(L.sgs_confusion_counts(_ptr(lg, torch.float32), N, C, _ptr(y, torch.int64), _ptr(m[0]), _ptr(m[1]), _ptr(m[2]),
+                                      _ptr(out, torch.int64), _stream()), "sgs_confusion_counts")
+    return out
+
+
+def confusion_variant(N: int, C: int) -> int:
+    """sgs_confusion_variant: the form a confusion_counts call on [N, C] logits launches now: 1 direct, 2 privatised, 0 nothing (N = 0), -1 when
+    the call would be refused.  Host-only."""
+    return int(_lib.lib().sgs_confusion_variant(int(N), int(C)))
+
+
+def confusion_variant_set(code: int) -> None:
+    """sgs_confusion_variant_set: 0 = automatic (default), 1 = direct, 2 = privatised; any other code raises."""
+    _lib.check(_lib.lib().sgs_confusion_variant_set(int(code)), "sgs_confusion_variant_set")
+
+
 def masked_correct_pair(logits_a, logits_b, y, train_mask, out) -> torch.Tensor:
     """The gate's two counts in one launch: out[0:4] = (#correct_a, #train, #correct_b, #train); `out` (int32, >= 4 entries)
     must be zero on entry."""

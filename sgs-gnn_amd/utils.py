@@ -11,11 +11,87 @@ import torch
 from . import ops
 
 
-def calculate_f1(logits, labels, mask) -> float:
+F1_AVERAGES = ("micro", "macro", "weighted")
+
+
+def calculate_f1(logits, labels, mask, average="micro") -> float:
     """utils.py:163-169: sklearn micro-F1 of the argmax on masked rows == accuracy.  Computed on
-    the device (sgs_masked_correct); only two ints cross to the host."""
-    c = ops.masked_correct(logits, labels, mask).tolist()
-    return c[0] / c[1] if c[1] else 0.0
+    the device (sgs_masked_correct); only two ints cross to the host.  average="macro" / "weighted" (the lines the reference keeps
+    commented out beside the micro one): the confusion matrix of the masked rows is counted on the device (ops.confusion_counts, the mask
+    as split 0) and C * C ints cross to the host."""
+    if average not in F1_AVERAGES:
+        raise ValueError(f"calculate_f1: average={average!r}, need one of {F1_AVERAGES}")
+    if average == "micro":
+        c = ops.masked_correct(logits, labels, mask).tolist()
+        return c[0] / c[1] if c[1] else 0.0
+    none = torch.zeros_like(mask)
+    return f1_from_confusion(ops.confusion_counts(logits, labels, (mask, none, none))[0].cpu(), average)
+
+
+def _confusion_lists(conf):
+    """-> a list of [C][C] lists of Python ints, one per split, and whether `conf` had the split axis."""
+    M = conf.tolist() if hasattr(conf, "tolist") else conf
+    if not M or not isinstance(M[0], (list, tuple)):
+        raise ValueError("confusion matrix: need [C, C] or [S, C, C] integers")
+    stacked = bool(M[0]) and isinstance(M[0][0], (list, tuple))
+    Ms = M if stacked else [M]
+    for m in Ms:
+        if any(len(r) != len(m) for r in m):
+            raise ValueError("confusion matrix: need square [C, C] blocks")
+    return Ms, stacked
+
+
+def _class_stats(m):
+    """Per class of one [C][C] matrix (rows: truth, columns: prediction): (tp, support, predicted, f1)."""
+    C = len(m)
+    tp = [m[c][c] for c in range(C)]
+    sup = [sum(m[c]) for c in range(C)]
+    pred = [sum(m[t][c] for t in range(C)) for c in range(C)]
+    f = [2.0 * tp[c] / (sup[c] + pred[c]) if sup[c] + pred[c] > 0 else 0.0 for c in range(C)]
+    return tp, sup, pred, f
+
+
+def _f1_one(m, average):
+    tp, sup, pred, f = _class_stats(m)
+    n = sum(sup)
+    if n == 0:
+        return 0.0
+    if average == "micro":
+        return sum(tp) / n
+    if average == "macro":
+        seen = [c for c in range(len(m)) if sup[c] + pred[c] > 0]          # sklearn's labels=None: present in the truth or the prediction
+        return sum(f[c] for c in seen) / len(seen)
+    return sum(f[c] * sup[c] for c in range(len(m))) / n
+
+
+def f1_from_confusion(conf, average="micro"):
+    """F1 of a confusion matrix (rows: truth, columns: prediction), as sklearn.metrics.f1_score(average=...) gives it on the labels and
+    predictions the matrix counts; computed on the host in float64.  With tp_c = M[c][c], sup_c = sum_p M[c][p], pred_c = sum_t M[t][c]:
+    f_c = 2 tp_c / (sup_c + pred_c) (0 where the denominator is 0);  "micro" = sum tp / sum M;  "macro" = the mean of f_c over the classes
+    with sup_c + pred_c > 0;  "weighted" = sum f_c sup_c / sum sup_c.  An empty matrix gives 0.  `conf`: an integer tensor, array or nested
+    list, [C, C] -> a float, or [S, C, C] -> a tuple of S floats."""
+    if average not in F1_AVERAGES:
+        raise ValueError(f"f1_from_confusion: average={average!r}, need one of {F1_AVERAGES}")
+    Ms, stacked = _confusion_lists(conf)
+    vals = tuple(_f1_one(m, average) for m in Ms)
+    return vals if stacked else vals[0]
+
+
+def classification_report(conf):
+    """Per split of a confusion matrix ([C, C] -> one dict, [S, C, C] -> a list of S dicts): "precision", "recall", "f1" and "support" per
+    class (lists of C; a ratio with a zero denominator is 0), the three averages "micro", "macro", "weighted" (f1_from_confusion) and
+    "balanced_accuracy", the mean recall over the classes that have support (0 for an empty split)."""
+    Ms, stacked = _confusion_lists(conf)
+    out = []
+    for m in Ms:
+        tp, sup, pred, f = _class_stats(m)
+        C = len(m)
+        rec = [tp[c] / sup[c] if sup[c] else 0.0 for c in range(C)]
+        have = [c for c in range(C) if sup[c]]
+        out.append({"precision": [tp[c] / pred[c] if pred[c] else 0.0 for c in range(C)], "recall": rec, "f1": f, "support": sup,
+                    "micro": _f1_one(m, "micro"), "macro": _f1_one(m, "macro"), "weighted": _f1_one(m, "weighted"),
+                    "balanced_accuracy": sum(rec[c] for c in have) / len(have) if have else 0.0})
+    return out if stacked else out[0]
 
 
 def consistency_loss(edge_probs, edge_indices, node_embeddings):
