@@ -1034,6 +1034,10 @@ int sgs_gine_aggregate_bwd(const float* x, const float* dz, const float* edge_w,
  *                       sgs_dropout_keep(seed, site, row i, column c).  The forward runs over (in_ptr, in_src, l_in), the backward over
  *                       (out_ptr, out_dst, l_out); nnz picks the row-per-workgroup kernel as in sgs_spmm_csr.  Rows are gathered 16 bytes
  *                       at a time when D % 4 == 0, ldx % 4 == 0 and X is 16-byte aligned, else column by column.
+ *   sgs_cheb_spmm_variant : which kernel sgs_cheb_spmm launches for a shape (a pure host function, no GPU needed; the launchers switch on
+ *                       it), in sgs_spmm_csr_variant's encoding: VEC * 100 + LPR for a group of LPR lanes per row, 1000 + VEC * 100 + NW
+ *                       for a workgroup of NW waves per row (N <= 65536 and nnz >= 16 N; NW = 16 from nnz >= 256 N).  aligned16 is about X
+ *                       alone.  0 for N == 0 or D == 0 (no launch), -1 for negative sizes.
  * The gradient wrt l is ONE sgs_sddmm_csr at width (K - 1) D of [G | 2 U_1 | ... | 2 U_{K-2}] against [b_1 | ... | b_{K-1}].
  * ---------------------------------------------------------------------------------- */
 int sgs_cheb_supported(int64_t K);
@@ -1044,6 +1048,7 @@ size_t sgs_cheb_norm_bwd_workspace_bytes(int64_t N);
 int sgs_cheb_norm_bwd(const float* w, const float* g, const float* g2, int64_t n_edges, int64_t N, const float* dis, const int32_t* in_ptr,
                       const int32_t* in_src, const int32_t* in_eid, const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid,
                       const int64_t* edge_index, float* dw, void* ws, size_t ws_bytes, sgs_stream_t stream);
+int sgs_cheb_spmm_variant(int64_t N, int64_t D, int64_t nnz, int64_t ldx, int aligned16);
 int sgs_cheb_spmm(int64_t K, const float* X, int64_t ldx, int64_t N, int64_t D, int64_t nnz, const int32_t* ptr, const int32_t* col,
                   const float* val, float alpha, const float* add, int64_t ldadd, const float* sub, int64_t ldsub, const float* bias, int act,
                   float p_drop, uint64_t seed, uint32_t site, float* Y, int64_t ldy, float* Y2, int64_t ldy2, float scale2,

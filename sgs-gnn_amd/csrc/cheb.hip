@@ -511,6 +511,20 @@ int sgs_cheb_norm_bwd(const float* w, const float* g, const float* g2, int64_t n
     return SGS_OK;
 }
 
+/* Which kernel sgs_cheb_spmm / sgs_cheb_spmm_multi launch -- a pure host function of the shape, and both launchers switch on its result.
+ * The encoding of sgs_spmm_csr_variant:  VEC * 100 + LPR for cheb_spmm_rows<VEC, LPR> (LPR = the power of two >= ceil(D / VEC), at most 64),
+ * 1000 + VEC * 100 + NW for cheb_spmm_rowblock<VEC, NW> (N <= 65536 and nnz >= 16 N; NW = 16 from nnz >= 256 N).  VEC = 4 iff D % 4 == 0,
+ * ldx % 4 == 0 and X is 16-byte aligned (aligned16 != 0; X only: the other operands are touched per element), else 1.  0 when nothing is
+ * launched (N == 0 or D == 0), -1 for negative sizes. */
+int sgs_cheb_spmm_variant(int64_t N, int64_t D, int64_t nnz, int64_t ldx, int al16) {
+    if (N < 0 || D < 0 || nnz < 0 || ldx < 0) return -1;
+    if (N == 0 || D == 0) return 0;
+    const int vec = (D % 4 == 0 && ldx % 4 == 0 && al16) ? 4 : 1;
+    if (N <= 65536 && nnz >= 16 * N)          // few, long rows: a workgroup per row (the choice sgs_spmm_csr makes)
+        return 1000 + vec * 100 + (nnz >= 256 * N ? 16 : 4);
+    return vec * 100 + pick_lpr(D, vec);
+}
+
 int sgs_cheb_spmm(int64_t K, const float* X, int64_t ldx, int64_t N, int64_t D, int64_t nnz, const int32_t* ptr, const int32_t* col,
                   const float* val, float alpha, const float* add, int64_t ldadd, const float* sub, int64_t ldsub, const float* bias, int act,
                   float p_drop, uint64_t seed, uint32_t site, float* Y, int64_t ldy, float* Y2, int64_t ldy2, float scale2,
@@ -525,23 +539,21 @@ int sgs_cheb_spmm(int64_t K, const float* X, int64_t ldx, int64_t N, int64_t D, 
     SGS_REQUIRE(ldx >= D && ldy >= D && (!add || ldadd >= D) && (!sub || ldsub >= D) && (!Y2 || ldy2 >= D), SGS_EINVAL,
                 "sgs_cheb_spmm: a leading dimension is smaller than D");
     // 16-byte gathers need the gathered operand's block start and row pitch aligned (the other operands are touched per element)
-    const int vec = (D % 4 == 0 && ldx % 4 == 0 && aligned16(X)) ? 4 : 1;
+    const int var = sgs_cheb_spmm_variant(N, D, nnz, ldx, aligned16(X));
     if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
     StepArgs a;
     a.X = X; a.ldx = ldx; a.add = add; a.ldadd = ldadd; a.sub = sub; a.ldsub = ldsub; a.bias = bias; a.Y = Y; a.ldy = ldy;
     a.Y2 = Y2; a.ldy2 = ldy2; a.alpha = alpha; a.scale2 = scale2; a.act = act; a.drop_scale = 1.0f / (1.0f - p_drop);
     a.drop_thresh = dropout_thresh(p_drop); a.seed = seed; a.site = site; a.epoch = epoch_ptr();
-    if (N <= 65536 && nnz >= 16 * N) {        // few, long rows: a workgroup per row (the choice sgs_spmm_csr makes)
-        const bool wide = nnz >= 256 * N;
-        const dim3 g_(static_cast<unsigned>(N));
-        if (vec == 4 && wide) hipLaunchKernelGGL((cheb_spmm_rowblock<4, 16>), g_, dim3(1024), 0, stream, a, N, D, ptr, col, val);
-        else if (vec == 4)    hipLaunchKernelGGL((cheb_spmm_rowblock<4, 4>), g_, dim3(kT), 0, stream, a, N, D, ptr, col, val);
-        else if (wide)        hipLaunchKernelGGL((cheb_spmm_rowblock<1, 16>), g_, dim3(1024), 0, stream, a, N, D, ptr, col, val);
-        else                  hipLaunchKernelGGL((cheb_spmm_rowblock<1, 4>), g_, dim3(kT), 0, stream, a, N, D, ptr, col, val);
-    } else if (vec == 4) {
-        launch_rows<4>(pick_lpr(D, 4), stream, a, N, D, ptr, col, val);
-    } else {
-        launch_rows<1>(pick_lpr(D, 1), stream, a, N, D, ptr, col, val);
+    const dim3 g_(static_cast<unsigned>(N));
+    switch (var) {
+        case 1416: hipLaunchKernelGGL((cheb_spmm_rowblock<4, 16>), g_, dim3(1024), 0, stream, a, N, D, ptr, col, val); break;
+        case 1404: hipLaunchKernelGGL((cheb_spmm_rowblock<4, 4>), g_, dim3(kT), 0, stream, a, N, D, ptr, col, val); break;
+        case 1116: hipLaunchKernelGGL((cheb_spmm_rowblock<1, 16>), g_, dim3(1024), 0, stream, a, N, D, ptr, col, val); break;
+        case 1104: hipLaunchKernelGGL((cheb_spmm_rowblock<1, 4>), g_, dim3(kT), 0, stream, a, N, D, ptr, col, val); break;
+        default:
+            if (var / 100 == 4) launch_rows<4>(var % 100, stream, a, N, D, ptr, col, val);
+            else                launch_rows<1>(var % 100, stream, a, N, D, ptr, col, val);
     }
     SGS_LAUNCH_OK();
     return SGS_OK;
@@ -595,24 +607,22 @@ int sgs_cheb_spmm_multi(int64_t K, const float* X, int64_t ldx, int64_t x_stride
                 "sgs_cheb_spmm_multi: a leading dimension is smaller than D");
     SGS_REQUIRE(x_stride >= 0 && add_stride >= 0 && sub_stride >= 0 && (n_draws == 1 || y_stride >= (N - 1) * ldy + D), SGS_EINVAL,
                 "sgs_cheb_spmm_multi: bad draw stride (every draw writes a block of its own)");
-    const int vec = (D % 4 == 0 && ldx % 4 == 0 && x_stride % 4 == 0 && aligned16(X)) ? 4 : 1;      // sgs_cheb_spmm's rule, for every draw's block
+    const int var = sgs_cheb_spmm_variant(N, D, nnz, ldx, x_stride % 4 == 0 && aligned16(X));      // sgs_cheb_spmm's rule, for every draw's block
     StepArgs a;
     a.X = X; a.ldx = ldx; a.add = add; a.ldadd = ldadd; a.sub = sub; a.ldsub = ldsub; a.bias = bias; a.Y = Y; a.ldy = ldy;
     a.Y2 = nullptr; a.ldy2 = 0; a.alpha = alpha; a.scale2 = 1.0f; a.act = act; a.drop_scale = 1.0f;
     a.drop_thresh = 0u; a.seed = 0; a.site = 0u; a.epoch = nullptr;
     StepStrides st;
     st.x = x_stride; st.add = add_stride; st.sub = sub_stride; st.y = y_stride;
-    if (N <= 65536 && nnz >= 16 * N) {        // the single-draw choice, on the per-draw entry count
-        const bool wide = nnz >= 256 * N;
-        const dim3 g_(static_cast<unsigned>(N), static_cast<unsigned>(n_draws));
-        if (vec == 4 && wide) hipLaunchKernelGGL((cheb_spmm_rowblock_multi<4, 16>), g_, dim3(1024), 0, stream, a, st, N, D, nnz, ptr, col, val);
-        else if (vec == 4)    hipLaunchKernelGGL((cheb_spmm_rowblock_multi<4, 4>), g_, dim3(kT), 0, stream, a, st, N, D, nnz, ptr, col, val);
-        else if (wide)        hipLaunchKernelGGL((cheb_spmm_rowblock_multi<1, 16>), g_, dim3(1024), 0, stream, a, st, N, D, nnz, ptr, col, val);
-        else                  hipLaunchKernelGGL((cheb_spmm_rowblock_multi<1, 4>), g_, dim3(kT), 0, stream, a, st, N, D, nnz, ptr, col, val);
-    } else if (vec == 4) {
-        launch_rows_multi<4>(pick_lpr(D, 4), stream, a, st, N, D, nnz, n_draws, ptr, col, val);
-    } else {
-        launch_rows_multi<1>(pick_lpr(D, 1), stream, a, st, N, D, nnz, n_draws, ptr, col, val);
+    const dim3 g_(static_cast<unsigned>(N), static_cast<unsigned>(n_draws));
+    switch (var) {        // the single-draw choice, on the per-draw entry count
+        case 1416: hipLaunchKernelGGL((cheb_spmm_rowblock_multi<4, 16>), g_, dim3(1024), 0, stream, a, st, N, D, nnz, ptr, col, val); break;
+        case 1404: hipLaunchKernelGGL((cheb_spmm_rowblock_multi<4, 4>), g_, dim3(kT), 0, stream, a, st, N, D, nnz, ptr, col, val); break;
+        case 1116: hipLaunchKernelGGL((cheb_spmm_rowblock_multi<1, 16>), g_, dim3(1024), 0, stream, a, st, N, D, nnz, ptr, col, val); break;
+        case 1104: hipLaunchKernelGGL((cheb_spmm_rowblock_multi<1, 4>), g_, dim3(kT), 0, stream, a, st, N, D, nnz, ptr, col, val); break;
+        default:
+            if (var / 100 == 4) launch_rows_multi<4>(var % 100, stream, a, st, N, D, nnz, n_draws, ptr, col, val);
+            else                launch_rows_multi<1>(var % 100, stream, a, st, N, D, nnz, n_draws, ptr, col, val);
     }
     SGS_LAUNCH_OK();
     return SGS_OK;

@@ -1,7 +1,9 @@
 """GPU: the Chebyshev head of order K > 1 (ops.cheb_norm / ops.cheb_conv / ChebModel(cheb_k=K)) against the fp64 dense restatement in
 tests/cheb_ref.py (direct T_k recurrence + torch autograd; the product runs Clenshaw's recurrence at the output width, so the two share
 no algebra).  Tolerances are the heads' own (tests/test_gpu_heads.py): logits < 1e-4 absolute, every gradient -- the edge weights'
-included -- within 2e-4 (1 + max |ref|)."""
+included -- within 2e-4 (1 + max |ref|).  These are model-level checks of the autograd plumbing; every kernel variant behind sgs_cheb_spmm
+and the two normalisation entry points are held to fp64 element by element in tests/test_gpu_cheb_kernels.py (references, bounds and case
+tables: tests/cheb_kernels_ref.py; coverage of the tables: tests/test_cheb_variant_table.py)."""
 import argparse
 import os
 import sys
