@@ -756,7 +756,29 @@ int sgs_hybrid_loss_w_fwd(const float* logits, int64_t N, int64_t C, const int64
                           const int64_t* sampled_edge_index, int64_t q, float coef1, float coef2, const float* weight, float label_smoothing,
                           float* out, float* row_lse, float* rowloss, float* den, void* ws, size_t ws_bytes, sgs_stream_t stream);
 
-/* Edge-sharded losses: raw[4] = {sum bce, sum (w-cos)^2, #valid, sum labels} over THIS rank's sampled edges; the
+/* The same loss and its gradients in THREE launches, bit for bit the chains above ("Hybrid loss in three launches").
+ * `weighted` != 0 selects the weighted / smoothed criterion: norm is then den (a float word), otherwise n_rows (an int32 word) and
+ * weight must be NULL, label_smoothing 0.
+ *   sgs_hybrid_loss_fused_fwd   one launch for the row losses AND the per-edge terms, then the finishing block of sgs_hybrid_loss_fwd /
+ *                               _w_fwd: out[7], row_lse[N], rowloss[N], norm[1] as there.  stash [q, 4] floats, 16-byte aligned, NULL
+ *                               when no gradient is wanted: per sampled edge {1 / sqrt(max(|x|^2 |y|^2, 1e-16)), cos / |x|^2, cos / |y|^2
+ *                               (both 0 under the clamp), 2 (w - cos) coef2 / q} -- what the backward needs of the three dot products.
+ *   sgs_hybrid_loss_fused_bwd   one launch over the sampled graph's two CSR orientations (nnz = q; the traversal sgs_endpoint_reduce
+ *                               takes for (q, N)): dlogits[N, C] = the regularisers' gradient, formed per entry from stash and two
+ *                               logits rows (no [q, C] arrays), plus the cross entropy's on train rows; dw[q] as sgs_edge_reg_bwd.
+ *                               Both outputs are written, not accumulated.  Meant for coef2 != 0 (with coef2 == 0 the stash's last
+ *                               word is 0 and dlogits gets -0 * ... terms where the chain above writes the cross entropy alone). */
+int sgs_hybrid_loss_fused_fwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* w,
+                              const int64_t* sampled_edge_index, int64_t q, float coef1, float coef2, int weighted, const float* weight,
+                              float label_smoothing, float* out, float* row_lse, float* rowloss, void* norm, float* stash, void* ws,
+                              size_t ws_bytes, sgs_stream_t stream);
+int sgs_hybrid_loss_fused_bwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* w, int64_t q,
+                              const float* stash, const float* out, float coef1, int weighted, const float* weight, float label_smoothing,
+                              const float* row_lse, const void* norm, const float* grad_loss, const int32_t* in_ptr, const int32_t* in_src,
+                              const int32_t* in_eid, const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, float* dw,
+                              float* dlogits, sgs_stream_t stream);
+
+/* Edge-sharded losses: raw[4] ={sum bce, sum (w-cos)^2, #valid, sum labels} over THIS rank's sampled edges; the
  * ranks all-reduce raw, form reg1 / reg2 with the global q, and call sgs_edge_reg_bwd with out[2], out[3] = the
  * global #valid / label sum and q_global = the global number of sampled edges (q_global = q when unsharded). */
 int sgs_edge_reg_partial(const float* w, const int64_t* sampled_edge_index, int64_t q, const float* logits, int64_t N,

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "sgs_common.h"
+#include "endpoint_reduce.h"
 
 namespace sgs {
 namespace {
@@ -1921,119 +1922,7 @@ __global__ void __launch_bounds__(kT) edge_score_finish(const float* __restrict_
     p_out[r] = 1.0f / (1.0f + expf(-z));
 }
 
-// out[v,:] = sum_{k in out-row v} sgn_out * Mo[out_eid[k],:] (* T[out_dst[k],:])
-//          + sum_{k in in-row v}  sgn_in  * Mi[in_eid[k],:]  (* T[in_src[k],:])
-// Scatter of per-edge gradient rows to both endpoints as a deterministic gather over the two
-// CSR orientations of the active edge list (no float atomics).
-template <int VEC, bool HAS_T>
-__global__ void __launch_bounds__(kT) endpoint_reduce(const float* __restrict__ Mo, const float* __restrict__ Mi,
-                                                     const float* __restrict__ T, int64_t N, int64_t H,
-                                                     const int* __restrict__ in_ptr, const int* __restrict__ in_src,
-                                                     const int* __restrict__ in_eid, const int* __restrict__ out_ptr,
-                                                     const int* __restrict__ out_dst, const int* __restrict__ out_eid,
-                                                     float sgn_out, float sgn_in, float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t v = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;   // one wave per node
-    if (v >= N) return;
-    for (int64_t c0 = static_cast<int64_t>(lane) * VEC; c0 < H; c0 += 64 * VEC) {
-        float acc[VEC];
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
-        for (int dir = 0; dir < 2; ++dir) {
-            const int* ptr = dir == 0 ? out_ptr : in_ptr;
-            const int* col = dir == 0 ? out_dst : in_src;
-            const int* eid = dir == 0 ? out_eid : in_eid;
-            const float sg = dir == 0 ? sgn_out : sgn_in;
-            const float* M = dir == 0 ? Mo : Mi;
-            const int b = ptr[v], e = ptr[v + 1];
-            for (int k = b; k < e; ++k) {
-                float m[VEC], t[VEC];
-                if (VEC == 4) {
-                    *reinterpret_cast<float4*>(m) = *reinterpret_cast<const float4*>(M + static_cast<int64_t>(eid[k]) * H + c0);
-                    if (HAS_T) *reinterpret_cast<float4*>(t) = *reinterpret_cast<const float4*>(T + static_cast<int64_t>(col[k]) * H + c0);
-                } else {
-                    m[0] = M[static_cast<int64_t>(eid[k]) * H + c0];
-                    if (HAS_T) t[0] = T[static_cast<int64_t>(col[k]) * H + c0];
-                }
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) acc[j] = fmaf(sg * m[j], HAS_T ? t[j] : 1.0f, acc[j]);
-            }
-        }
-        if (VEC == 4) *reinterpret_cast<float4*>(out + v * H + c0) = *reinterpret_cast<float4*>(acc);
-        else out[v * H + c0] = acc[0];
-    }
-}
-
-// Small-N variant: a 4-wave workgroup per node; the node's out-row then in-row entries form one list
-// that the waves stride with four independent row gathers in flight each; partial sums meet in LDS
-// in a fixed order (deterministic).
-// NW waves per node: 4 for moderate rows, 16 when rows are long -- a power-law partition has hub nodes with thousands of
-// incident sampled edges, and with 4 waves those few workgroups set the kernel's duration (92 us -> see profiles).
-template <int VEC, bool HAS_T, int NW>
-__global__ void __launch_bounds__(64 * NW) endpoint_reduce_rowblock(const float* __restrict__ Mo, const float* __restrict__ Mi,
-                                                              const float* __restrict__ T, int64_t N, int64_t H,
-                                                              const int* __restrict__ in_ptr, const int* __restrict__ in_src,
-                                                              const int* __restrict__ in_eid, const int* __restrict__ out_ptr,
-                                                              const int* __restrict__ out_dst, const int* __restrict__ out_eid,
-                                                              float sgn_out, float sgn_in, float* __restrict__ out) {
-    using V = typename std::conditional<VEC == 4, float4, float>::type;
-    __shared__ float part[NW][64 * VEC];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t v = blockIdx.x;
-    const int ob = out_ptr[v], no = out_ptr[v + 1] - ob;
-    const int ib = in_ptr[v], ni = in_ptr[v + 1] - ib;
-    const int total = no + ni;
-    for (int64_t cbase = 0; cbase < H; cbase += 64 * VEC) {
-        const int64_t c0 = cbase + static_cast<int64_t>(lane) * VEC;
-        float acc[VEC];
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
-        if (c0 < H) {
-            for (int k0 = wave; k0 < total; k0 += 4 * NW) {
-                // indices first, then every row gather, all unconditional (entries past the row: clamped to its last entry, sign 0) --
-                // under `if (k < total)` each entry's index wait (vmcnt(0)) also waited for the previous entry's rows
-                float m[4][VEC], t[4][VEC], sg[4];
-                int er[4], cr[4];
-                const float* Mp[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int k = k0 + NW * u;
-                    const int kc = k < total ? k : total - 1;
-                    const bool isout = kc < no;
-                    const int idx = isout ? ob + kc : ib + (kc - no);
-                    er[u] = (isout ? out_eid : in_eid)[idx];
-                    if (HAS_T) cr[u] = (isout ? out_dst : in_src)[idx];
-                    Mp[u] = isout ? Mo : Mi;
-                    sg[u] = k < total ? (isout ? sgn_out : sgn_in) : 0.f;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    *reinterpret_cast<V*>(m[u]) = *reinterpret_cast<const V*>(Mp[u] + static_cast<int64_t>(er[u]) * H + c0);
-                    if (HAS_T) *reinterpret_cast<V*>(t[u]) = *reinterpret_cast<const V*>(T + static_cast<int64_t>(cr[u]) * H + c0);
-                    else {
-#pragma unroll
-                        for (int j = 0; j < VEC; ++j) t[u][j] = 1.f;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int j = 0; j < VEC; ++j) acc[j] = fmaf(sg[u] * m[u][j], t[u][j], acc[j]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) part[wave][lane * VEC + j] = acc[j];
-        __syncthreads();
-        const int tt = threadIdx.x;
-        if (tt < 64 * VEC && cbase + tt < H) {
-            float sum = 0.f;
-#pragma unroll
-            for (int g = 0; g < NW; g += 4) sum += (part[g][tt] + part[g + 1][tt]) + (part[g + 2][tt] + part[g + 3][tt]);
-            out[v * H + cbase + tt] = sum;
-        }
-        __syncthreads();
-    }
-}
+// endpoint_reduce / endpoint_reduce_rowblock (the scatter of per-edge gradient rows to both endpoints): csrc/endpoint_reduce.h
 
 // The backward WITHOUT a recompute (the forward kept the mask: sgs_edge_score_fwd_mask).  Per active row r (edge e = active[r]):
 //   dz[r] = gp[r] p[e] (1 - p[e]),   bits[r, :] = maskbits[e, :],   feat[r, :] = codes[src e, :] * codes[dst e, :]
@@ -2936,31 +2825,20 @@ int sgs_endpoint_reduce(const float* M_out, const float* M_in, const float* T, i
     const bool v4 = H % 4 == 0 && (reinterpret_cast<uintptr_t>(M_out) & 15) == 0 && (reinterpret_cast<uintptr_t>(M_in) & 15) == 0 &&
                     (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                     (!T || (reinterpret_cast<uintptr_t>(T) & 15) == 0);
-    const dim3 blk(kT);
-    if (nnz >= 8 * N) {                       // long rows: a workgroup per node (partitions, and whole graphs of average degree >= 8)
-        const dim3 grid(static_cast<unsigned>(N));
-        const bool wide = nnz >= 64 * N;       // long rows (hubs with thousands of entries): 16 waves per node
-#define SGS_EPR(VEC_, HT_)                                                                                                   \
-        do {                                                                                                                    \
-            if (wide) hipLaunchKernelGGL((endpoint_reduce_rowblock<VEC_, HT_, 16>), grid, dim3(1024), 0, stream, M_out, M_in, T, N, H, in_ptr, \
-                                         in_src, in_eid, out_ptr, out_dst, out_eid, sign_out, sign_in, out);                  \
-            else      hipLaunchKernelGGL((endpoint_reduce_rowblock<VEC_, HT_, 4>), grid, blk, 0, stream, M_out, M_in, T, N, H, in_ptr,        \
-                                         in_src, in_eid, out_ptr, out_dst, out_eid, sign_out, sign_in, out);                  \
-        } while (0)
-        if (v4) { if (T) SGS_EPR(4, true); else SGS_EPR(4, false); }
-        else    { if (T) SGS_EPR(1, true); else SGS_EPR(1, false); }
+    const int nw = ep_traversal(nnz, N);
+#define SGS_EPR(VEC_, HT_)                                                                                                                        \
+    do {                                                                                                                                          \
+        const EpLoadRows<VEC_, HT_> rows{M_out, M_in, T};                                                                                         \
+        if (nw == 16)     hipLaunchKernelGGL((endpoint_reduce_rowblock<VEC_, 16, EpLoadRows<VEC_, HT_>>), dim3(static_cast<unsigned>(N)), dim3(1024), 0, stream, \
+                                             rows, N, H, in_ptr, in_src, in_eid, out_ptr, out_dst, out_eid, sign_out, sign_in, out);              \
+        else if (nw == 4) hipLaunchKernelGGL((endpoint_reduce_rowblock<VEC_, 4, EpLoadRows<VEC_, HT_>>), dim3(static_cast<unsigned>(N)), dim3(256), 0, stream,   \
+                                             rows, N, H, in_ptr, in_src, in_eid, out_ptr, out_dst, out_eid, sign_out, sign_in, out);              \
+        else              hipLaunchKernelGGL((endpoint_reduce<VEC_, EpLoadRows<VEC_, HT_>>), dim3(static_cast<unsigned>(cdiv(N * 64, kEpT))), dim3(kEpT), 0,     \
+                                             stream, rows, N, H, in_ptr, in_src, in_eid, out_ptr, out_dst, out_eid, sign_out, sign_in, out);      \
+    } while (0)
+    if (v4) { if (T) SGS_EPR(4, true); else SGS_EPR(4, false); }
+    else    { if (T) SGS_EPR(1, true); else SGS_EPR(1, false); }
 #undef SGS_EPR
-        SGS_LAUNCH_OK();
-        return SGS_OK;
-    }
-    const dim3 grid(static_cast<unsigned>(cdiv(N * 64, kT)));
-    if (v4) {
-        if (T) hipLaunchKernelGGL((endpoint_reduce<4, true>), grid, blk, 0, stream, M_out, M_in, T, N, H, in_ptr, in_src, in_eid, out_ptr, out_dst, out_eid, sign_out, sign_in, out);
-        else   hipLaunchKernelGGL((endpoint_reduce<4, false>), grid, blk, 0, stream, M_out, M_in, T, N, H, in_ptr, in_src, in_eid, out_ptr, out_dst, out_eid, sign_out, sign_in, out);
-    } else {
-        if (T) hipLaunchKernelGGL((endpoint_reduce<1, true>), grid, blk, 0, stream, M_out, M_in, T, N, H, in_ptr, in_src, in_eid, out_ptr, out_dst, out_eid, sign_out, sign_in, out);
-        else   hipLaunchKernelGGL((endpoint_reduce<1, false>), grid, blk, 0, stream, M_out, M_in, T, N, H, in_ptr, in_src, in_eid, out_ptr, out_dst, out_eid, sign_out, sign_in, out);
-    }
     SGS_LAUNCH_OK();
     return SGS_OK;
 }

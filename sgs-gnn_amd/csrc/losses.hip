@@ -8,6 +8,7 @@
 #include <atomic>
 
 #include "sgs_common.h"
+#include "endpoint_reduce.h"
 
 namespace sgs {
 namespace {
@@ -163,11 +164,9 @@ __global__ void publish_words(const int32_t* __restrict__ src, int n, const uint
 
 // ---------------------------------------------------------------- masked cross entropy
 // rowloss[i] = lse_i - logit_i[y_i] on train rows (0 elsewhere); row_lse kept for backward.
-__global__ void __launch_bounds__(kT) ce_rows(const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
-                                             const uint8_t* __restrict__ mask, float* __restrict__ row_lse,
-                                             float* __restrict__ rowloss) {
-    const int lane = threadIdx.x & 63;
-    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+// One wave's row (i, all 64 lanes); ce_rows and the merged forward launch (hybrid_fwd_pair) share it.
+__device__ __forceinline__ void ce_row(int64_t i, int lane, const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
+                                       const uint8_t* __restrict__ mask, float* __restrict__ row_lse, float* __restrict__ rowloss) {
     if (i >= N) return;
     if (!mask[i]) {
         if (lane == 0) { rowloss[i] = 0.f; row_lse[i] = 0.f; }
@@ -184,6 +183,11 @@ __global__ void __launch_bounds__(kT) ce_rows(const float* __restrict__ logits, 
         row_lse[i] = lse;
         rowloss[i] = lse - logits[i * C + y[i]];
     }
+}
+__global__ void __launch_bounds__(kT) ce_rows(const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
+                                             const uint8_t* __restrict__ mask, float* __restrict__ row_lse,
+                                             float* __restrict__ rowloss) {
+    ce_row((static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6, threadIdx.x & 63, logits, N, C, y, mask, row_lse, rowloss);
 }
 
 // One block: loss = sum(rowloss) / #train ; n_rows[0] = #train.
@@ -358,11 +362,9 @@ __device__ __forceinline__ float class_weight(const float* __restrict__ weight, 
     return weight ? weight[yi] : 1.f;
 }
 
-__global__ void __launch_bounds__(kT) ce_rows_w(const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
-                                               const uint8_t* __restrict__ mask, const float* __restrict__ weight, float eps,
-                                               float* __restrict__ row_lse, float* __restrict__ rowloss) {
-    const int lane = threadIdx.x & 63;
-    const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+__device__ __forceinline__ void ce_row_w(int64_t i, int lane, const float* __restrict__ logits, int64_t N, int64_t C,
+                                         const int64_t* __restrict__ y, const uint8_t* __restrict__ mask, const float* __restrict__ weight,
+                                         float eps, float* __restrict__ row_lse, float* __restrict__ rowloss) {
     if (i >= N) return;
     if (!mask[i]) {
         if (lane == 0) { rowloss[i] = 0.f; row_lse[i] = 0.f; }
@@ -387,6 +389,11 @@ __global__ void __launch_bounds__(kT) ce_rows_w(const float* __restrict__ logits
         row_lse[i] = lse;
         rowloss[i] = (eps != 0.f) ? (1.f - eps) * hard + (eps / static_cast<float>(C)) * sm : hard;
     }
+}
+__global__ void __launch_bounds__(kT) ce_rows_w(const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
+                                               const uint8_t* __restrict__ mask, const float* __restrict__ weight, float eps,
+                                               float* __restrict__ row_lse, float* __restrict__ rowloss) {
+    ce_row_w((static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6, threadIdx.x & 63, logits, N, C, y, mask, weight, eps, row_lse, rowloss);
 }
 
 // One block: den[0] = sum of w[y_i] over the train rows (recomputed from w, y and the mask: no [N] buffer), loss = sum(rowloss) / den.
@@ -538,6 +545,230 @@ __global__ void __launch_bounds__(kT) reg_bwd_edges(const float* __restrict__ w,
         Gd[j * C + c] = -r * (a * inv - cy * b);
     }
 }
+
+// ---------------------------------------------------------------- the hybrid loss in three launches (sgs_hybrid_loss_fused_fwd / _bwd)
+// Forward, one launch for two jobs (as spmm_rowgroup_pair_dual): the first nce workgroups do ce_rows' work (kW: ce_rows_w's), the
+// rest reg_fwd_partial's.  Partials, block-sum order and the per-thread accumulation order over the four rounds are reg_fwd_partial's, so
+// hybrid_loss_final reads the same bits.  What differs is the order of the LOADS: reg_fwd_partial reads w, tm[s], tm[d], y[s], y[d] under
+// `if (live && sub == 0)` inside each round, so its four rounds go through memory one after another (index -> rows -> scalars, four
+// times); here the indices of all four rounds are read first, then every row segment and every scalar, unconditionally on clamped
+// indices, and the arithmetic follows.  The row loop runs column-outer / round-inner: each round's three sums still take their columns
+// in increasing order.
+// `stash` (may be null: no gradient wanted) keeps per sampled edge what the backward needs of the three dot products, in
+// reg_bwd_edges' expressions: {inv, cx, cy, r0} with r = r0 * grad_loss -- 16 bytes per edge in place of two gradient rows.
+template <bool kW>
+__global__ void __launch_bounds__(kT) hybrid_fwd_pair(const float* __restrict__ w, const int64_t* __restrict__ sei, int64_t q,
+                                                     const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
+                                                     const uint8_t* __restrict__ tm, int64_t nce, float coef2, float q_norm,
+                                                     const float* __restrict__ weight, float eps, float* __restrict__ part,
+                                                     float4* __restrict__ stash, float* __restrict__ row_lse, float* __restrict__ rowloss) {
+    const int64_t blk = static_cast<int64_t>(blockIdx.x) - nce;         // the row-loss workgroups come first: short, and not the launch's tail
+    if (blk < 0) {
+        const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
+        if (kW) ce_row_w(i, threadIdx.x & 63, logits, N, C, y, tm, weight, eps, row_lse, rowloss);
+        else    ce_row(i, threadIdx.x & 63, logits, N, C, y, tm, row_lse, rowloss);
+        return;
+    }
+    __shared__ float red[4][kT / 64];
+    const int sub = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    int64_t jj[kRegRounds], s[kRegRounds], d[kRegRounds];
+    bool live[kRegRounds];
+#pragma unroll
+    for (int r = 0; r < kRegRounds; ++r) {
+        const int64_t j = blk * kRegEdges + r * (kT / 16) + grp;
+        live[r] = j < q;
+        jj[r] = live[r] ? j : 0;
+    }
+#pragma unroll
+    for (int r = 0; r < kRegRounds; ++r) { s[r] = sei[jj[r]]; d[r] = sei[q + jj[r]]; }
+    float wj[kRegRounds];
+    uint8_t ts[kRegRounds], td[kRegRounds];
+    int64_t ys[kRegRounds], yd[kRegRounds];
+#pragma unroll
+    for (int r = 0; r < kRegRounds; ++r) { wj[r] = w[jj[r]]; ts[r] = tm[s[r]]; td[r] = tm[d[r]]; ys[r] = y[s[r]]; yd[r] = y[d[r]]; }
+    float dot[kRegRounds], nx[kRegRounds], ny[kRegRounds];
+#pragma unroll
+    for (int r = 0; r < kRegRounds; ++r) { dot[r] = 0.f; nx[r] = 0.f; ny[r] = 0.f; }
+    for (int64_t c = sub; c < C; c += 16) {
+        float a[kRegRounds], b[kRegRounds];
+#pragma unroll
+        for (int r = 0; r < kRegRounds; ++r) { a[r] = logits[s[r] * C + c]; b[r] = logits[d[r] * C + c]; }
+#pragma unroll
+        for (int r = 0; r < kRegRounds; ++r) {
+            dot[r] = fmaf(a[r], b[r], dot[r]); nx[r] = fmaf(a[r], a[r], nx[r]); ny[r] = fmaf(b[r], b[r], ny[r]);
+        }
+    }
+    // Every lane of a group holds every round's three sums: lane r of the group takes round r, so the per-edge arithmetic (a logarithm,
+    // a square root, five divisions with the stash) runs once per workgroup and not once per round in lane 0 alone.
+#pragma unroll
+    for (int r = 0; r < kRegRounds; ++r) { dot[r] = row16_sum_all_dpp(dot[r]); nx[r] = row16_sum_all_dpp(nx[r]); ny[r] = row16_sum_all_dpp(ny[r]); }
+    float dt = dot[0], sx = nx[0], sy = ny[0], wr = wj[0];
+    bool on = live[0], valid = ts[0] && td[0], same = ys[0] == yd[0];
+    int64_t je = jj[0];
+#pragma unroll
+    for (int r = 1; r < kRegRounds; ++r)
+        if (sub == r) {
+            dt = dot[r]; sx = nx[r]; sy = ny[r]; wr = wj[r];
+            on = live[r]; valid = ts[r] && td[r]; same = ys[r] == yd[r];
+            je = jj[r];
+        }
+    on = on && sub < kRegRounds;
+    float t_bce = 0.f, t_sq = 0.f, t_nv = 0.f, t_nl = 0.f;
+    if (on) {
+        const float cs = cos_from(EdgeTerms{dt, sx, sy});
+        const float df = wr - cs;
+        t_sq = df * df;
+        if (valid) {
+            t_nv = 1.f;
+            t_nl = same ? 1.f : 0.f;
+            // F.binary_cross_entropy clamps each log at -100
+            t_bce = same ? -fmaxf(logf(wr), -100.f) : -fmaxf(logf(1.f - wr), -100.f);
+        }
+        if (stash) {                                   // reg_bwd_edges' expressions, in its order
+            const float den2 = fmaxf(sx * sy, 1e-16f);
+            const float inv = 1.0f / sqrtf(den2);
+            const float csb = dt * inv;
+            const float r0 = 2.0f * (wr - csb) / q_norm * coef2;
+            const bool clamped = sx * sy < 1e-16f;
+            const float cx = clamped ? 0.f : csb / sx, cy = clamped ? 0.f : csb / sy;
+            stash[je] = make_float4(inv, cx, cy, r0);
+        }
+    }
+    // lane 0 of the group adds the four rounds' terms in round order, as reg_fwd_partial's lane 0 does (a round that adds nothing there
+    // adds +0 here: the sums start at +0 and are never -0, so the bits are the same)
+    float bce = 0.f, sq = 0.f, nv = 0.f, nl = 0.f;
+    const int g0 = threadIdx.x & 48;                   // the group's first lane within the wave
+#pragma unroll
+    for (int r = 0; r < kRegRounds; ++r) {
+        bce += __shfl(t_bce, g0 + r, 64); sq += __shfl(t_sq, g0 + r, 64); nv += __shfl(t_nv, g0 + r, 64); nl += __shfl(t_nl, g0 + r, 64);
+    }
+    if (sub != 0) { bce = 0.f; sq = 0.f; nv = 0.f; nl = 0.f; }
+    // block_sum's tree for the four sums at once (one barrier in place of eight): wave sums, then thread 0 adds them in wave order
+    bce = wave_sum(bce); sq = wave_sum(sq); nv = wave_sum(nv); nl = wave_sum(nl);
+    if ((threadIdx.x & 63) == 0) {
+        const int wid = threadIdx.x >> 6;
+        red[0][wid] = bce; red[1][wid] = sq; red[2][wid] = nv; red[3][wid] = nl;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float r[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            r[k] = 0.f;
+            for (int i = 0; i < kT / 64; ++i) r[k] += red[k][i];
+        }
+        part[4 * blk + 0] = r[0]; part[4 * blk + 1] = r[1];
+        part[4 * blk + 2] = r[2]; part[4 * blk + 3] = r[3];
+    }
+}
+
+// Backward, one launch: the endpoint reduction's traversal (csrc/endpoint_reduce.h) with the terms FORMED where they are added, in
+// place of reg_bwd_edges -> endpoint_reduce -> ce_bwd_acc and their two [q, C] arrays.  For a sampled edge e = (s, d) with the forward's
+// {inv, cx, cy, r0} and r = r0 * grad_loss, the entry of e in s's out-row is reg_bwd_edges' Gs[e, c] = -r (b inv - cx a) and the entry in
+// d's in-row its Gd[e, c] = -r (a inv - cy b), a = logits[s, c], b = logits[d, c]: the node's own row is read once, the neighbour's per
+// entry (the table is cache resident).  Every sampled edge is in exactly one out-row (self-loops included), whose visitor writes dw[e]
+// by reg_bwd_edges' formula; the writer of dlogits[v, c] adds the cross entropy's term as ce_bwd_acc / ce_bwd_w<true> do.
+template <bool kW>
+struct EpHybridTerms {
+    static constexpr bool kCol = true, kVisit = true;
+    const float* __restrict__ logits;
+    int64_t C;
+    const float4* __restrict__ stash;
+    const float* __restrict__ w;
+    const int64_t* __restrict__ y;
+    const uint8_t* __restrict__ tm;
+    const float* __restrict__ out7;
+    float coef1;
+    const float* __restrict__ grad_loss;
+    float* __restrict__ dw;
+    const float* __restrict__ weight;
+    float eps;
+    const float* __restrict__ row_lse;
+    const void* __restrict__ norm;          // n_rows (int32) of the plain criterion, den (float) of the weighted one
+    // What every entry of a workgroup needs is read once: W, grad_loss and whether reg1 is on (coef1 != 0 and a label sum above 1)
+    // with its divisor out[2].
+    struct Blk { float W, gl, nvalid; bool reg1; };
+    struct Own { float x; };
+    struct Raw { float4 st; float nb; };
+    // A value that is the same in every lane and that this kernel never writes goes through the scalar cache (one request per wave, no
+    // work for the vector memory pipe, which the row loads of a hub node's workgroup keep busy).
+    template <class T>
+    static __device__ __forceinline__ T uniform_load(const T* ptr) {
+        return *(const __attribute__((address_space(4))) T*)(ptr);
+    }
+    __device__ __forceinline__ Blk block_init() const {
+        // W = sum_c w_c exactly as ce_bwd_w forms it: the workgroup's first 256 threads, block_weight_sum's order
+        __shared__ float red[4];
+        Blk b;
+        b.W = static_cast<float>(C);
+        b.gl = uniform_load(grad_loss);
+        b.nvalid = uniform_load(out7 + 2);
+        b.reg1 = coef1 != 0.f && uniform_load(out7 + 3) > 1.f;
+        if (kW && eps != 0.f && weight) {                                 // (uniform branch)
+            float v = 0.f;
+            if (threadIdx.x < 256) {
+                for (int64_t c = threadIdx.x; c < C; c += 256) v += weight[c];
+                v = wave_sum_all(v);
+                if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+            }
+            __syncthreads();
+            float r = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r += red[k];
+            b.W = r;
+        }
+        return b;
+    }
+    __device__ __forceinline__ Own own(int64_t v, int64_t, int64_t c0) const { return Own{logits[v * C + c0]}; }
+    // The four stash words of the four entries in flight are ONE load: lane l reads word (l >> 2) & 3 of entry l & 3's edge, and
+    // v_readlane hands entry u its words from lanes u, 4 + u, 8 + u, 12 + u.  (As four 64-lane loads of one address each, and as scalar
+    // loads -- a stream of misses in the scalar cache --, the same words set the kernel's time.)
+    struct Pre { float word; };
+    __device__ __forceinline__ Pre preload(int e_lane, int lane) const {
+        return Pre{reinterpret_cast<const float*>(stash)[static_cast<int64_t>(e_lane) * 4 + ((lane >> 2) & 3)]};
+    }
+    __device__ __forceinline__ Raw load(const Pre& pre, int u, bool, int, int col, int64_t, int64_t c0) const {
+        const int wd = __float_as_int(pre.word);
+        Raw r;
+        r.st = make_float4(__int_as_float(__builtin_amdgcn_readlane(wd, u)), __int_as_float(__builtin_amdgcn_readlane(wd, 4 + u)),
+                           __int_as_float(__builtin_amdgcn_readlane(wd, 8 + u)), __int_as_float(__builtin_amdgcn_readlane(wd, 12 + u)));
+        r.nb = logits[static_cast<int64_t>(col) * C + c0];
+        return r;
+    }
+    __device__ __forceinline__ void term(const Blk& blk, const Raw& rw, const Own& o, bool isout, float (&m)[1], float (&t)[1]) const {
+        const float inv = rw.st.x, cx = rw.st.y, cy = rw.st.z;
+        const float r = rw.st.w * blk.gl;
+        const float a = isout ? o.x : rw.nb, b = isout ? rw.nb : o.x;
+        m[0] = isout ? -r * (b * inv - cx * a) : -r * (a * inv - cy * b);
+        t[0] = 1.f;
+    }
+    // d w of the out entry (v, col) = edge e, one entry per thread (as a visitor inside the sums it ran in one lane, entry after entry,
+    // and its two divisions set the kernel's time).
+    __device__ __forceinline__ void visit(const Blk& blk, int64_t v, int e, int col) const {
+        const float gl = blk.gl;
+        const float wj = w[e];
+        const float r = stash[e].w * gl;
+        float g = r;
+        if (blk.reg1 && tm[v] && tm[col]) {
+            const float tgt = (y[v] == y[col]) ? 1.f : 0.f;
+            g += coef1 * gl * (wj - tgt) / fmaxf((1.f - wj) * wj, 1e-12f) / blk.nvalid;   // torch's BCE backward
+        }
+        dw[e] = g;
+    }
+    __device__ __forceinline__ float finish(const Blk& blk, int64_t v, int64_t c, float sum) const {
+        if (!tm[v]) return sum;
+        const int64_t idx = v * C + c;
+        if (!kW) {
+            const float sm = expf(logits[idx] - row_lse[v]);
+            return sum + (sm - (y[v] == c ? 1.f : 0.f)) * (grad_loss[0] / static_cast<float>(static_cast<const int*>(norm)[0]));
+        }
+        const float d = static_cast<const float*>(norm)[0];
+        const float sc = (d == 0.f) ? NAN : grad_loss[0] / d;
+        const int64_t yi = y[v];
+        return sum + ce_w_grad(logits[idx], row_lse[v], yi == c, class_weight(weight, yi, C), weight ? weight[c] : 1.f, blk.W, eps,
+                               1.f / static_cast<float>(C), sc);
+    }
+};
 
 
 // ---------------------------------------------------------------- ensemble mean + the three split counts (evaluate.py, ensemble_evaluate)
@@ -884,6 +1115,69 @@ int sgs_edge_reg_bwd(const float* w, const int64_t* sampled_edge_index, int64_t 
                 "sgs_edge_reg_bwd: null pointer");
     hipLaunchKernelGGL(reg_bwd_edges, dim3(cdiv(q, kT / 16)), dim3(kT), 0, stream, w, sampled_edge_index, q, logits, C, y, train_mask, out,
                        coef1, coef2, static_cast<float>(q_global), grad_loss, dw, Gs, Gd);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_hybrid_loss_fused_fwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* w,
+                              const int64_t* sampled_edge_index, int64_t q, float coef1, float coef2, int weighted, const float* weight,
+                              float label_smoothing, float* out, float* row_lse, float* rowloss, void* norm, float* stash, void* ws,
+                              size_t ws_bytes, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(q > 0 && N > 0 && N < (int64_t(1) << 24) && C > 0 && logits && y && train_mask && w && sampled_edge_index && out && row_lse &&
+                    rowloss && norm,
+                SGS_EINVAL, "sgs_hybrid_loss_fused_fwd: bad arguments");
+    SGS_REQUIRE(weighted ? (label_smoothing >= 0.f && label_smoothing <= 1.f) : (!weight && label_smoothing == 0.f), SGS_EINVAL,
+                "sgs_hybrid_loss_fused_fwd: label_smoothing outside [0, 1], or a weight / smoothing without `weighted`");
+    SGS_REQUIRE((reinterpret_cast<uintptr_t>(stash) & 15) == 0, SGS_EINVAL, "sgs_hybrid_loss_fused_fwd: stash must be 16-byte aligned");
+    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_reg_workspace_bytes(q), SGS_EWORKSPACE, "sgs_hybrid_loss_fused_fwd: workspace too small");
+    Carver cv(ws);
+    const int64_t nblk = cdiv(q, kRegEdges);
+    float* part = cv.take<float>(4 * (nblk + 1));
+    const int64_t nce = cdiv(N * 64, kT);
+    const dim3 grid(static_cast<unsigned>(nce + nblk));
+    float4* st = reinterpret_cast<float4*>(stash);
+    if (weighted) {
+        hipLaunchKernelGGL(hybrid_fwd_pair<true>, grid, dim3(kT), 0, stream, w, sampled_edge_index, q, logits, N, C, y, train_mask, nce, coef2,
+                           static_cast<float>(q), weight, label_smoothing, part, st, row_lse, rowloss);
+        hipLaunchKernelGGL(hybrid_loss_final_w, dim3(1), dim3(kT), 0, stream, part, nblk, q, coef1, coef2, rowloss, train_mask, y, weight, N, C, out,
+                           static_cast<float*>(norm));
+    } else {
+        hipLaunchKernelGGL(hybrid_fwd_pair<false>, grid, dim3(kT), 0, stream, w, sampled_edge_index, q, logits, N, C, y, train_mask, nce, coef2,
+                           static_cast<float>(q), weight, label_smoothing, part, st, row_lse, rowloss);
+        hipLaunchKernelGGL(hybrid_loss_final, dim3(1), dim3(kT), 0, stream, part, nblk, q, coef1, coef2, rowloss, train_mask, N, out,
+                           static_cast<int*>(norm));
+    }
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_hybrid_loss_fused_bwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* w, int64_t q,
+                              const float* stash, const float* out, float coef1, int weighted, const float* weight, float label_smoothing,
+                              const float* row_lse, const void* norm, const float* grad_loss, const int32_t* in_ptr, const int32_t* in_src,
+                              const int32_t* in_eid, const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, float* dw,
+                              float* dlogits, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(q > 0 && N > 0 && N < (int64_t(1) << 31) && C > 0 && logits && y && train_mask && w && stash && out && row_lse && norm && grad_loss &&
+                    in_ptr && in_src && in_eid && out_ptr && out_dst && out_eid && dw && dlogits,
+                SGS_EINVAL, "sgs_hybrid_loss_fused_bwd: bad arguments");
+    SGS_REQUIRE(weighted ? (label_smoothing >= 0.f && label_smoothing <= 1.f) : (!weight && label_smoothing == 0.f), SGS_EINVAL,
+                "sgs_hybrid_loss_fused_bwd: label_smoothing outside [0, 1], or a weight / smoothing without `weighted`");
+    SGS_REQUIRE((reinterpret_cast<uintptr_t>(stash) & 15) == 0, SGS_EINVAL, "sgs_hybrid_loss_fused_bwd: stash must be 16-byte aligned");
+    const int nw = ep_traversal(q, N);                  // the traversal sgs_endpoint_reduce takes for this (nnz, N)
+#define SGS_HYB(KW_)                                                                                                                              \
+    do {                                                                                                                                          \
+        const EpHybridTerms<KW_> terms{logits, C, reinterpret_cast<const float4*>(stash), w, y, train_mask, out, coef1, grad_loss, dw, weight,    \
+                                       label_smoothing, row_lse, norm};                                                                           \
+        if (nw == 16)     hipLaunchKernelGGL((endpoint_reduce_rowblock<1, 16, EpHybridTerms<KW_>>), dim3(static_cast<unsigned>(N)), dim3(1024), 0, stream, \
+                                             terms, N, C, in_ptr, in_src, in_eid, out_ptr, out_dst, out_eid, 1.0f, 1.0f, dlogits);               \
+        else if (nw == 4) hipLaunchKernelGGL((endpoint_reduce_rowblock<1, 4, EpHybridTerms<KW_>>), dim3(static_cast<unsigned>(N)), dim3(256), 0, stream,   \
+                                             terms, N, C, in_ptr, in_src, in_eid, out_ptr, out_dst, out_eid, 1.0f, 1.0f, dlogits);               \
+        else              hipLaunchKernelGGL((endpoint_reduce<1, EpHybridTerms<KW_>>), dim3(static_cast<unsigned>(cdiv(N * 64, kEpT))), dim3(kEpT), 0,     \
+                                             stream, terms, N, C, in_ptr, in_src, in_eid, out_ptr, out_dst, out_eid, 1.0f, 1.0f, dlogits);       \
+    } while (0)
+    if (weighted) SGS_HYB(true); else SGS_HYB(false);
+#undef SGS_HYB
     SGS_LAUNCH_OK();
     return SGS_OK;
 }

@@ -1454,9 +1454,10 @@ def edge_regularizers(w, logits, sampled_edge_index, y, train_mask, coef1, coef2
 
 
 class _HybridLoss(torch.autograd.Function):
-    """criterion + coef1 reg1 + coef2 reg2 as ONE node: three launches forward (row losses, per-edge terms, one finishing block),
-    three backward (per-edge gradients, their endpoint reduction, the cross entropy's gradient added in place) -- as separate nodes
-    the same sum took ten, two of them the adds autograd inserts."""
+    """criterion + coef1 reg1 + coef2 reg2 as ONE node: two launches forward (row losses and per-edge terms in one, one finishing
+    block), one backward (the endpoint reduction forms each per-edge gradient term where it adds it, writes d w and adds the cross
+    entropy's gradient) -- as separate nodes the same sum took ten, two of them the adds autograd inserts.  With coef2 == 0 the
+    earlier chain (three launches forward, two backward): there the cross entropy's gradient is written, not accumulated."""
 
     @staticmethod
     def forward(ctx, logits, y, mask_u8, w, sei, graph, coef1, coef2, box, weight=None, eps=0.0):
@@ -1469,16 +1470,23 @@ class _HybridLoss(torch.autograd.Function):
         rowloss = torch.empty(N, dtype=torch.float32, device=dev)
         ws = workspace(L.sgs_edge_reg_workspace_bytes(q), dev)
         ctx.plain = weight is None and eps == 0.0
-        if ctx.plain:
-            n_rows = torch.empty(1, dtype=torch.int32, device=dev)
+        # `n_rows` of the weighted / smoothed criterion is `den`, a float word (the sum of the train rows' class weights)
+        n_rows = torch.empty(1, dtype=torch.int32 if ctx.plain else torch.float32, device=dev)
+        stash = None
+        if coef2 != 0.0:    # two launches; the per-edge scalars of the backward are kept (16 B per edge) when a gradient is wanted
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[3]:
+                stash = torch.empty(q, 4, dtype=torch.float32, device=dev)
+            _lib.check(L.sgs_hybrid_loss_fused_fwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(w), _ptr(sei), q, float(coef1), float(coef2),
+                                                   0 if ctx.plain else 1, _ptr(weight), eps, _ptr(out), _ptr(row_lse), _ptr(rowloss), _ptr(n_rows),
+                                                   _ptr(stash), ws.data_ptr(), ws.numel(), _stream()), "sgs_hybrid_loss_fused_fwd")
+        elif ctx.plain:
             _lib.check(L.sgs_hybrid_loss_fwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(w), _ptr(sei), q, float(coef1), float(coef2), _ptr(out),
                                              _ptr(row_lse), _ptr(rowloss), _ptr(n_rows), ws.data_ptr(), ws.numel(), _stream()), "sgs_hybrid_loss_fwd")
-        else:               # weighted / smoothed criterion: `n_rows` is `den`, a float word (the sum of the train rows' class weights)
-            n_rows = torch.empty(1, dtype=torch.float32, device=dev)
+        else:
             _lib.check(L.sgs_hybrid_loss_w_fwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(w), _ptr(sei), q, float(coef1), float(coef2),
                                                _ptr(weight), eps, _ptr(out), _ptr(row_lse), _ptr(rowloss), _ptr(n_rows), ws.data_ptr(), ws.numel(),
                                                _stream()), "sgs_hybrid_loss_w_fwd")
-        ctx.save_for_backward(logits, y, mask_u8, w, sei, out, row_lse, n_rows, weight)
+        ctx.save_for_backward(logits, y, mask_u8, w, sei, out, row_lse, n_rows, weight, stash)
         ctx.eps = eps
         ctx.graph, ctx.coef1, ctx.coef2 = graph, float(coef1), float(coef2)
         ctx.nm_ref = getattr(w, "_sgs_norm", None)         # the normalisation that differentiates these weights, if any (note_first_dw)
@@ -1488,27 +1496,31 @@ class _HybridLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         L = _lib.lib()
-        logits, y, mask_u8, w, sei, out, row_lse, n_rows, weight = ctx.saved_tensors
+        logits, y, mask_u8, w, sei, out, row_lse, n_rows, weight, stash = ctx.saved_tensors
         q = w.numel()
         N, C = logits.shape
         dev = w.device
         g = g.reshape(1).contiguous().float()
         dw = torch.empty(q, dtype=torch.float32, device=dev)
-        Gs = torch.empty(q, C, dtype=torch.float32, device=dev)
-        Gd = torch.empty(q, C, dtype=torch.float32, device=dev)
-        _lib.check(L.sgs_edge_reg_bwd(_ptr(w), _ptr(sei), q, q, _ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(out), ctx.coef1,
-                                      ctx.coef2, _ptr(g), _ptr(dw), _ptr(Gs), _ptr(Gd), _stream()), "sgs_edge_reg_bwd")
-        dlogits = _endpoint_reduce(Gs, Gd, None, ctx.graph, 1.0, 1.0, C) if ctx.coef2 != 0.0 else torch.empty_like(logits)
-        if not ctx.plain:
-            fn, what = (L.sgs_masked_ce_w_bwd_acc, "sgs_masked_ce_w_bwd_acc") if ctx.coef2 != 0.0 else (L.sgs_masked_ce_w_bwd, "sgs_masked_ce_w_bwd")
-            _lib.check(fn(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(weight), ctx.eps, _ptr(row_lse), _ptr(n_rows), _ptr(g), _ptr(dlogits),
-                          _stream()), what)
-        elif ctx.coef2 != 0.0:
-            _lib.check(L.sgs_masked_ce_bwd_acc(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(row_lse), _ptr(n_rows), _ptr(g), _ptr(dlogits),
-                                               _stream()), "sgs_masked_ce_bwd_acc")
-        else:
-            _lib.check(L.sgs_masked_ce_bwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(row_lse), _ptr(n_rows), _ptr(g), _ptr(dlogits),
-                                           _stream()), "sgs_masked_ce_bwd")
+        if ctx.coef2 != 0.0:
+            gr = ctx.graph
+            dlogits = torch.empty_like(logits)
+            _lib.check(L.sgs_hybrid_loss_fused_bwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(w), q, _ptr(stash), _ptr(out), ctx.coef1,
+                                                   0 if ctx.plain else 1, _ptr(weight), ctx.eps, _ptr(row_lse), _ptr(n_rows), _ptr(g), _ptr(gr.in_ptr),
+                                                   _ptr(gr.in_src), _ptr(gr.in_eid), _ptr(gr.out_ptr), _ptr(gr.out_dst), _ptr(gr.out_eid), _ptr(dw),
+                                                   _ptr(dlogits), _stream()), "sgs_hybrid_loss_fused_bwd")
+        else:               # today's chain: with coef2 == 0 the cross entropy's gradient is written, not accumulated
+            Gs = torch.empty(q, C, dtype=torch.float32, device=dev)
+            Gd = torch.empty(q, C, dtype=torch.float32, device=dev)
+            _lib.check(L.sgs_edge_reg_bwd(_ptr(w), _ptr(sei), q, q, _ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(out), ctx.coef1,
+                                          ctx.coef2, _ptr(g), _ptr(dw), _ptr(Gs), _ptr(Gd), _stream()), "sgs_edge_reg_bwd")
+            dlogits = torch.empty_like(logits)
+            if not ctx.plain:
+                _lib.check(L.sgs_masked_ce_w_bwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(weight), ctx.eps, _ptr(row_lse), _ptr(n_rows),
+                                                 _ptr(g), _ptr(dlogits), _stream()), "sgs_masked_ce_w_bwd")
+            else:
+                _lib.check(L.sgs_masked_ce_bwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(row_lse), _ptr(n_rows), _ptr(g), _ptr(dlogits),
+                                               _stream()), "sgs_masked_ce_bwd")
         nm = ctx.nm_ref() if ctx.nm_ref is not None else None
         if nm is not None and getattr(nm, "_park_ok", False) and dw.numel() == nm.graph.n_edges:
             import weakref
