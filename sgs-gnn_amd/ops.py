@@ -2522,7 +2522,13 @@ def gcn2_dual(x, W1, b1, W2, b2, nm_a: Norm, nm_b: Norm, act=ACT_RELU, p=0.0, se
     return out_a, out_b, xl1
 
 
-# ------------------------------------------------------------------ batched ensemble evaluation (forward only, GCN head)
+# ------------------------------------------------------------------ batched ensemble evaluation (forward only; composed in eval_batch.py)
+def _empty_f32(*shape, device):
+    """An uninitialised float32 buffer that a kernel fills, for callers outside this module: allocated here, through this module's
+    `torch`, so that the SGS_POISON test hook (tests/conftest.py patches ops.torch) poisons it like every other such buffer."""
+    return torch.empty(*shape, dtype=torch.float32, device=device)
+
+
 class MultiSampleResult:
     """D draws over one candidate set (sgs_sample_topq_multi): mask [D, E] bool, eid [D, q], edge_index [D, 2, q] or None,
     stats [D, 4], w [D, q] (straight-through weights) or None.  Row d is what sample_topq returns for stream id stream_id0 + d.
@@ -2614,19 +2620,6 @@ def _spmm_multi(X, x_stride: int, csr, val, diag, bias, act, q: int, N: int, Dc:
     return Y
 
 
-def _drawn_gcn_logits(parent: Graph, smp: MultiSampleResult, w, xl1, b1, W2, b2):
-    """Logits [D, N, C] of the two GCN layers over each of the D drawn subgraphs of `parent` (one launch per stage for all draws):
-    in-CSRs filtered out of the parent's, weighted (w [D, q]) or unit gcn_norm, layer 1 over the shared x W1^T, one library GEMM
-    [D N, H] x W2^T for layer 2."""
-    D, q, N = smp.D, smp.q, parent.N
-    csr = graph_filter_multi(parent, smp)
-    _, _, what_in, what_loop = gcn_norm_multi(csr, w, q, N)
-    H = xl1.shape[1]
-    h = _spmm_multi(xl1, 0, csr, what_in, what_loop, b1, ACT_RELU, q, N, H)
-    z = (h.view(D * N, H) @ W2.t()).contiguous()
-    return _spmm_multi(z, N * z.shape[1], csr, what_in, what_loop, b2, ACT_NONE, q, N, z.shape[1])
-
-
 def ensemble_mean_correct(logits, x_stride: int, Dc: int, acc, first: bool, last: bool, D_total: int, y, masks, counts) -> None:
     """sgs_ensemble_mean_correct: fold Dc logit blocks into the running sum `acc` [N, C]; on the last pass acc becomes the mean and the
     three (correct, total) counts are added to `counts` (int64 [6])."""
@@ -2636,39 +2629,6 @@ def ensemble_mean_correct(logits, x_stride: int, Dc: int, acc, first: bool, last
     _lib.check(L.sgs_ensemble_mean_correct(_ptr(logits, torch.float32), int(x_stride), int(Dc), N, C, _ptr(acc, torch.float32), int(first), int(last),
                                            int(D_total), _ptr(y, torch.int64), _ptr(m[0]), _ptr(m[1]), _ptr(m[2]), _ptr(counts, torch.int64),
                                            _stream()), "sgs_ensemble_mean_correct")
-
-
-def ensemble_partition(batch, gcn1, gcn2, q: int, mode: int, p, passes, counts, trace=None, *, cover=None):
-    """All draws of ONE partition, batched: `passes` is a list of (Dc, noise [Dc, E] or None, seed, stream_id0), in draw order.
-    mode SAMPLE_LEARNED with p (the scorer's probabilities, istest: straight-through weights on the edges), SAMPLE_PRIOR with p = batch.prob
-    (unit weights), or SAMPLE_LEARNED with p None (uniform draw, unit weights).  Adds the partition's three (correct, total) counts to
-    `counts`.  `trace` (dict or None): receives per-draw logits [D, N, C], mean [N, C] and the drawn edge lists [D, 2, q].  `cover`
-    (the partition's cached get_graph(edge_index, N), the same object as the filter's parent, or None): every draw is node-covering."""
-    x, ei = batch.x, batch.edge_index
-    N = x.shape[0]
-    feature_csr(x, build=True)
-    xl1 = _x_wt(x, gcn1.lin.weight).contiguous()
-    parent = get_graph(ei, N)
-    D_total = sum(int(ps[0]) for ps in passes)
-    acc = None
-    done = 0
-    logs, edges = [], []
-    for k, (Dc, noise, seed, sid0) in enumerate(passes):
-        weighted = mode == SAMPLE_LEARNED and p is not None
-        smp = sample_topq_multi(mode, p, None, 0.0, q, ei, Dc, noise=noise, seed=seed, stream_id0=sid0, want_edge_index=trace is not None,
-                                want_w=weighted, cover=cover)
-        out = _drawn_gcn_logits(parent, smp, smp.w if weighted else None, xl1, gcn1.bias, gcn2.lin.weight, gcn2.bias)
-        if acc is None:
-            acc = torch.empty(N, out.shape[2], dtype=torch.float32, device=x.device)
-        done += Dc
-        ensemble_mean_correct(out, N * out.shape[2], Dc, acc, k == 0, done == D_total, D_total, batch.y,
-                              (batch.train_mask, batch.val_mask, batch.test_mask), counts)
-        if trace is not None:
-            logs.append(out)
-            edges.append(smp.edge_index)
-    if trace is not None:
-        trace["logits"], trace["mean"], trace["edges"] = torch.cat(logs), acc, torch.cat(edges)
-    return acc
 
 
 def gat_alpha_multi(a_s, a_d, a_stride: int, csr, q: int, N: int, negative_slope: float, out=None):
@@ -2683,46 +2643,6 @@ def gat_alpha_multi(a_s, a_d, a_stride: int, csr, q: int, N: int, negative_slope
     _lib.check(L.sgs_gat_alpha_fwd_multi(_ptr(a_s, torch.float32), _ptr(a_d, torch.float32), int(a_stride), N, D, q, _ptr(in_ptr), _ptr(in_src),
                                          float(negative_slope), _ptr(alpha_in), _ptr(alpha_loop), _stream()), "sgs_gat_alpha_fwd_multi")
     return alpha_in, alpha_loop
-
-
-def _drawn_gat_logits(parent: Graph, smp: MultiSampleResult, convs, xl1, a_s1, a_d1):
-    """Logits [D, N, C] of the two GATConv layers (heads = 1, eval: no attention dropout) over each of the D drawn subgraphs: layer 1 over
-    the shared x' = lin_src(x) and its node scores, one library GEMM [D N, H] x W2^T and one sgs_gat_scores_fwd over the D N rows (row-local:
-    draw d's scores are what that kernel gives on draw d's block alone) for layer 2.  The alpha buffers are reused by layer 2."""
-    D, q, N = smp.D, smp.q, parent.N
-    c1, c2 = convs
-    csr = graph_filter_multi(parent, smp)
-    alpha = gat_alpha_multi(a_s1, a_d1, 0, csr, q, N, c1.negative_slope)
-    H = xl1.shape[1]
-    h = _spmm_multi(xl1, 0, csr, alpha[0], alpha[1], c1.bias, ACT_RELU, q, N, H)
-    z = c2.lin_src(h.view(D * N, H)).contiguous()                    # nn.Linear, as GATConv.forward
-    C = z.shape[1]
-    a_s2, a_d2 = gat_scores(z, c2.att_src, c2.att_dst)
-    alpha = gat_alpha_multi(a_s2, a_d2, N, csr, q, N, c2.negative_slope, out=alpha)
-    return _spmm_multi(z, N * C, csr, alpha[0], alpha[1], c2.bias, ACT_NONE, q, N, C)
-
-
-def _drawn_gin_logits(parent: Graph, smp: MultiSampleResult, convs, u1):
-    """Logits [D, N, C] of the two GINConv layers over each of the D drawn subgraphs: the sum aggregation of sum_norm (unit value on every
-    drawn entry, existing (i,i) entries included, diagonal 1 + eps) as the draw-strided SpMM, then each MLP's second Linear over [D N, .]
-    in one library GEMM.  u1 = x W0^T of the first conv, shared by all draws."""
-    D, q, N = smp.D, smp.q, parent.N
-    f32 = dict(dtype=torch.float32, device=u1.device)
-    csr = graph_filter_multi(parent, smp)
-    ones = torch.ones(D, max(q, 1), **f32)
-    h = u1
-    for k, conv in enumerate(convs):
-        l0, l1 = conv.nn.lins
-        x_stride = 0 if k == 0 else N * l0.out_features
-        if k > 0:
-            h = linear_nobias(h, l0.weight).contiguous()
-        diag = torch.full((D, max(N, 1)), 1.0 + conv._eps, **f32)
-        a = _spmm_multi(h, x_stride, csr, ones, diag, l0.bias, ACT_RELU, q, N, l0.out_features)
-        h = linear_nobias(a.view(D * N, -1), l1.weight)
-        h += l1.bias                                                  # GINConv.forward: linear_nobias(h, W1) + b1
-        if k == 0:
-            h.relu_()                                                 # GIN.forward: F.relu between the convs (eval: no dropout)
-    return h.view(D, N, -1)
 
 
 def gine_aggregate_multi(x, x_stride: int, csr, w, a, b, diag: float, q: int, N: int, Dc: int):
@@ -2748,29 +2668,6 @@ def gine_aggregate_multi(x, x_stride: int, csr, w, a, b, diag: float, q: int, N:
     _lib.check(L.sgs_gine_aggregate_fwd_multi(_ptr(x, torch.float32), x_stride, _ptr(w), _ptr(a), _ptr(b), float(diag), N, Dc, q, D, _ptr(in_ptr),
                                               _ptr(in_src), _ptr(in_eid), _ptr(z), _stream()), "sgs_gine_aggregate_fwd_multi")
     return z
-
-
-def _drawn_gine_logits(parent: Graph, smp: MultiSampleResult, w, convs, x):
-    """Logits [D, N, C] of the two GINEConv layers (GIN.forward in eval mode: ReLU between the convs, no dropout and no dropout seed) over
-    each of the D drawn subgraphs of `parent`: one gine_aggregate_multi launch per layer for all draws -- layer 1 at the input width over
-    the shared `x` (x_stride = 0), layer 2 at the hidden width over the per-draw blocks (x_stride = N H) -- and each MLP Linear as one
-    library GEMM over the [D N, .] rows.  `w` [D, q]: the draws' straight-through weights (learned mode), or None (unit weights, as
-    edge_weight=None in the model)."""
-    D, q, N = smp.D, smp.q, parent.N
-    csr = graph_filter_multi(parent, smp)
-    h, x_stride = x, 0
-    for k, conv in enumerate(convs):
-        l0, l1 = conv.nn.lins
-        z = gine_aggregate_multi(h, x_stride, csr, w, conv.lin.weight, conv.lin.bias, 1.0 + conv._eps, q, N, conv.in_channels)
-        h = linear_nobias(z.view(D * N, -1), l0.weight)
-        h += l0.bias
-        h.relu_()                                                     # GINEConv.forward: relu(linear_nobias(z, W0) + b0)
-        h = linear_nobias(h, l1.weight)
-        h += l1.bias
-        if k == 0:
-            h.relu_()                                                 # GIN.forward: F.relu between the convs (eval: no dropout)
-            x_stride = N * h.shape[1]
-    return h.view(D, N, -1)
 
 
 def gat_alpha_heads_multi(a_s, a_d, a_stride: int, csr, q: int, N: int, K: int, negative_slope: float, edge_w=None, edge_coef=None, out=None):
@@ -2803,27 +2700,6 @@ def _spmm_heads_multi(X, x_stride: int, csr, val, diag, mode, bias, act, q: int,
     _lib.check(L.sgs_spmm_csr_heads_multi(_ptr(X, torch.float32), int(x_stride), N, K, C, q, D, _ptr(in_ptr), _ptr(in_src), _ptr(in_eid), _ptr(val),
                                           _ptr(diag), mode, _ptr(bias), act, _ptr(Y), _stream()), "sgs_spmm_csr_heads_multi")
     return Y
-
-
-def _drawn_gat_heads_logits(parent: Graph, smp: MultiSampleResult, convs, xl1, a_s1, a_d1, w=None, coefs=None):
-    """Logits [D, N, C] of the two GATConv layers on the per-head kernels (heads K >= 2, or any K with the edge term; eval: no attention
-    dropout) over each of the D drawn subgraphs.  Layer 1 (concat) runs over the shared x' = lin_src(x) and its node scores [N, K]; layer 2
-    (head mean) is one library GEMM [D N, H] x W2^T and one gat_scores call over the D N rows (row-local).  `w` [D, q] (the draws'
-    straight-through weights) with `coefs` = the two layers' edge_coef [K] adds the edge term, as edge_weight does in GAT.forward; both
-    None = the unweighted per-head softmax.  The alpha buffers are reused by layer 2."""
-    D, q, N = smp.D, smp.q, parent.N
-    c1, c2 = convs
-    K = c1.heads
-    csr = graph_filter_multi(parent, smp)
-    edge = (lambda k: dict(edge_w=w, edge_coef=coefs[k])) if w is not None else (lambda k: {})
-    alpha = gat_alpha_heads_multi(a_s1, a_d1, 0, csr, q, N, K, c1.negative_slope, **edge(0))
-    H = xl1.shape[1]
-    h = _spmm_heads_multi(xl1, 0, csr, alpha[0], alpha[1], HEADS_CONCAT if c1.concat else HEADS_MEAN, c1.bias, ACT_RELU, q, N, K, H // K)
-    z = c2.lin_src(h.view(D * N, -1)).contiguous()                   # nn.Linear, as GATConv.forward
-    C = z.shape[1] // K
-    a_s2, a_d2 = gat_scores(z, c2.att_src, c2.att_dst, heads=K)
-    alpha = gat_alpha_heads_multi(a_s2, a_d2, N * K, csr, q, N, K, c2.negative_slope, out=alpha, **edge(1))
-    return _spmm_heads_multi(z, N * K * C, csr, alpha[0], alpha[1], HEADS_CONCAT if c2.concat else HEADS_MEAN, c2.bias, ACT_NONE, q, N, K, C)
 
 
 def gatv2_alpha_heads_multi(xl, xr, x_stride: int, att, csr, q: int, N: int, K: int, negative_slope: float, edge_w=None, lin_edge=None, out=None):
@@ -2873,30 +2749,6 @@ def gatv2_alpha_heads_multi(xl, xr, x_stride: int, att, csr, q: int, N: int, K: 
     return alpha, alpha_loop
 
 
-def _drawn_gatv2_logits(parent: Graph, smp: MultiSampleResult, convs, xl1, xr1, w=None):
-    """Logits [D, N, C] of the two GATv2Conv layers (eval: no attention dropout) over each of the D drawn subgraphs of `parent`, every
-    1 <= heads <= 16: one gatv2_alpha_heads_multi launch and one _spmm_heads_multi launch per layer for all draws.  Layer 1 (concat, ReLU)
-    runs over the shared xl1 = lin_l(x), xr1 = lin_r(x) (x_stride = 0).  Layer 2 (head mean) takes one library product over the [D N, H]
-    hidden rows with cat(lin_l.weight, lin_r.weight) plus the two biases -- GATv2Conv.forward's call --, sliced into contiguous
-    xl2 / xr2 [D, N, K C] (x_stride = N K C); the alpha buffers are reused.  `w` [D, q] (the draws' straight-through weights) adds the edge
-    term with each layer's lin_edge.weight, as edge_weight does in GAT.forward; None = no edge term."""
-    D, q, N = smp.D, smp.q, parent.N
-    c1, c2 = convs
-    K = c1.heads
-    csr = graph_filter_multi(parent, smp)
-    edge = (lambda c: dict(edge_w=w, lin_edge=c.lin_edge.weight)) if w is not None else (lambda c: {})
-    alpha = gatv2_alpha_heads_multi(xl1, xr1, 0, c1.att, csr, q, N, K, c1.negative_slope, **edge(c1))
-    H = xl1.shape[1]
-    h = _spmm_heads_multi(xl1, 0, csr, alpha[0], alpha[1], HEADS_CONCAT if c1.concat else HEADS_MEAN, c1.bias, ACT_RELU, q, N, K, H // K)
-    W2 = c2.heads * c2.out_channels
-    y = linear_nobias(h.view(D * N, -1), torch.cat([c2.lin_l.weight, c2.lin_r.weight], 0))
-    y += torch.cat([c2.lin_l.bias, c2.lin_r.bias])                   # in place: the same sums as GATv2Conv.forward's, no second [D N, 2 K C]
-    xl2, xr2 = y[:, :W2].contiguous(), y[:, W2:].contiguous()
-    alpha = gatv2_alpha_heads_multi(xl2, xr2, N * W2, c2.att, csr, q, N, K, c2.negative_slope, out=alpha, **edge(c2))
-    return _spmm_heads_multi(xl2, N * W2, csr, alpha[0], alpha[1], HEADS_CONCAT if c2.concat else HEADS_MEAN, c2.bias, ACT_NONE, q, N, K,
-                             c2.out_channels)
-
-
 def cheb_norm_multi(parent: Graph, smp: MultiSampleResult, csr, w=None):
     """sgs_cheb_norm_fwd_multi: (dis [D, N], l_in [D, q]) of the D drawn subgraphs, row d bitwise sgs_cheb_norm_fwd's dis / l_in for draw d.
     `w` [D, q] by the draw's edge id, or None (unit weights).  The by-source degree walks the parent's out-CSR under each draw's mask."""
@@ -2917,131 +2769,6 @@ def _cheb_step_multi(K, X, ldx, xs, N, W, q, D, csr, val, alpha, add, ldadd, add
     dimension and draw stride."""
     _lib.check(_lib.lib().sgs_cheb_spmm_multi(K, X, ldx, xs, N, W, q, D, _ptr(csr[0]), _ptr(csr[1]), _ptr(val), float(alpha), add, ldadd, adds,
                                               sub, ldsub, subs, _ptr(bias), act, Y, ldy, ys, _stream()), "sgs_cheb_spmm_multi")
-
-
-def _cheb_layer_multi(K, Y0, y0_stride, B, b_stride, csr, l_in, bias, act, q, N, D):
-    """_ChebConv.forward's Clenshaw steps for D draws at once: Y0 [., N, W] and B [., N, (K - 1) W] = [Y_1 | ... | Y_{K-1}] with draw
-    strides (0: the layer-1 products, shared by all draws).  The steps k = K - 2 .. 1 overwrite B's column blocks in place, so a shared B
-    is copied per draw first when there are any (K >= 3); at K = 2 the last step only reads it.  -> [D, N, W]."""
-    W = Y0.shape[-1]
-    ldb = (K - 1) * W
-    if K >= 3 and b_stride == 0:
-        B = B.unsqueeze(0).expand(D, N, ldb).contiguous()
-        b_stride = N * ldb
-    b0 = B.data_ptr()
-    blk = lambda k: b0 + 4 * (k - 1) * W                          # b_k's column block
-    for k in range(K - 2, 0, -1):
-        _cheb_step_multi(K, blk(k + 1), ldb, b_stride, N, W, q, D, csr, l_in, 2.0, blk(k), ldb, b_stride,
-                         blk(k + 2) if k + 2 <= K - 1 else None, ldb, b_stride, None, ACT_NONE, blk(k), ldb, b_stride)
-    out = torch.empty(D, N, W, dtype=torch.float32, device=Y0.device)
-    _cheb_step_multi(K, blk(1), ldb, b_stride, N, W, q, D, csr, l_in, 1.0, Y0.data_ptr(), W, y0_stride, blk(2) if K >= 3 else None, ldb, b_stride,
-                     bias, act, out.data_ptr(), W, N * W)
-    return out
-
-
-def _drawn_cheb_logits(parent: Graph, smp: MultiSampleResult, w, convs, K: int, Y0, B):
-    """Logits [D, N, C] of the two ChebConv layers of order K >= 2 (eval: ReLU between them, no dropout) over each of the D drawn subgraphs:
-    one normalisation per draw for both layers (weighted by `w` [D, q], or unit), layer 1 from the shared products Y0 = x W_0^T and
-    B = x [W_1 | ... | W_{K-1}]^T, layer 2 from the same two library products over the [D N, H] hidden rows."""
-    D, q, N = smp.D, smp.q, parent.N
-    c1, c2 = convs
-    csr = graph_filter_multi(parent, smp)
-    _, l_in = cheb_norm_multi(parent, smp, csr, w)
-    h = _cheb_layer_multi(K, Y0, 0, B, 0, csr, l_in, c1.bias, ACT_RELU, q, N, D)
-    hf = h.view(D * N, -1)
-    C = c2.out_channels
-    Wcat = torch.cat([lin.weight for lin in c2.lins], 0)
-    Y0b, Bb = _x_wt(hf, Wcat[:C]), _x_wt(hf, Wcat[C:])               # the serial layer's two products, over all draws' rows
-    return _cheb_layer_multi(K, Y0b, N * C, Bb, N * (K - 1) * C, csr, l_in, c2.bias, ACT_NONE, q, N, D)
-
-
-def ensemble_partition_head(batch, model, q: int, mode: int, p, passes, counts, trace=None, *, cover=None):
-    """ensemble_partition for any of the four heads (GNNModel, GATModel, GINModel, ChebModel), same arguments and result.  Per pass: the D
-    draws (sample_topq_multi), their in-CSRs (graph_filter_multi) and the head's logits for all of them; the draw-independent first
-    product (GAT: lin_src(x) and its node scores; GIN: x W0^T; Chebyshev K >= 2: x [W_0 | ... | W_{K-1}]^T) runs once per partition.
-    Chebyshev K = 1 ignores the graph: its logits are computed once and folded D times; it draws only when `trace` asks for the edge
-    lists.  One-head GAT without the edge term and GIN ignore edge weights, so no straight-through weights are drawn for them; GAT with
-    gat_edge_weight, Chebyshev K >= 2 and GIN with gin_edge_weight (the GINE layers, _drawn_gine_logits: nothing to precompute, the
-    aggregation reads x itself) take them (learned mode; the other modes have none: no edge term / unit weights, as edge_weight=None in
-    the model).  GAT with heads >= 2 or the edge term runs on the per-head kernels (_drawn_gat_heads_logits).  A GATModel(gat_v2=True)
-    runs on the gathering GATv2 softmax of all draws (_drawn_gatv2_logits; per partition: x_l = lin_l(x) and x_r = lin_r(x) as one
-    product), every head count, with the straight-through weights iff gat_edge_weight (learned mode).
-    `cover` (get_graph(edge_index, N) or None) goes to every sample_topq_multi call, the Chebyshev K = 1 trace-only draw included."""
-    from .model import ChebModel, GATModel, GINModel, GNNModel
-    if isinstance(model, GNNModel):
-        return ensemble_partition(batch, model.gcn1, model.gcn2, q, mode, p, passes, counts, trace, cover=cover)
-    x, ei = batch.x, batch.edge_index
-    N = x.shape[0]
-    weighted = mode == SAMPLE_LEARNED and p is not None              # the draws carry straight-through weights
-    want_w = False
-    if isinstance(model, GATModel) and model.gat_v2:
-        convs = tuple(model.GAT.convs)                                # GATv2Conv: the softmax gathers rows of x_l and x_r
-        W1 = convs[0].heads * convs[0].out_channels
-        y1 = linear_nobias(x, torch.cat([convs[0].lin_l.weight, convs[0].lin_r.weight], 0)) + torch.cat([convs[0].lin_l.bias, convs[0].lin_r.bias])
-        xl1, xr1 = y1[:, :W1].contiguous(), y1[:, W1:].contiguous()  # GATv2Conv.forward's call: bitwise the serial path's x_l, x_r
-        edge = weighted and convs[0].edge_dim is not None             # GAT.forward: the edge term needs edge_dim and weights
-        want_w = edge
-        logits = lambda parent, smp: _drawn_gatv2_logits(parent, smp, convs, xl1, xr1, smp.w if edge else None)
-    elif isinstance(model, GATModel):
-        convs = tuple(model.GAT.convs)
-        xl1 = convs[0].lin_src(x).contiguous()                        # the serial path's call: bitwise the same x'
-        K = convs[0].heads
-        edge = weighted and convs[0].edge_dim is not None             # GAT.forward: the edge term needs edge_dim and weights
-        if K == 1 and not edge:
-            a_s1, a_d1 = gat_scores(xl1, convs[0].att_src, convs[0].att_dst)
-            logits = lambda parent, smp: _drawn_gat_logits(parent, smp, convs, xl1, a_s1, a_d1)
-        else:
-            a_s1, a_d1 = gat_scores(xl1, convs[0].att_src, convs[0].att_dst, heads=K)
-            coefs = tuple(c.edge_coef().reshape(K).contiguous() for c in convs) if edge else None
-            want_w = edge
-            logits = lambda parent, smp: _drawn_gat_heads_logits(parent, smp, convs, xl1, a_s1, a_d1, smp.w if edge else None, coefs)
-    elif isinstance(model, GINModel) and model.gin_edge_weight:
-        convs = tuple(model.GIN.convs)                                # GINEConv: the aggregation runs at the input width, on x itself
-        xc = x.contiguous()
-        want_w = weighted
-        logits = lambda parent, smp: _drawn_gine_logits(parent, smp, smp.w if weighted else None, convs, xc)
-    elif isinstance(model, GINModel):
-        convs = tuple(model.GIN.convs)
-        u1 = linear_nobias(x, convs[0].nn.lins[0].weight).contiguous()
-        logits = lambda parent, smp: _drawn_gin_logits(parent, smp, convs, u1)
-    elif isinstance(model, ChebModel) and model.cheb_k > 1:
-        convs, K = (model.gcn1, model.gcn2), model.cheb_k
-        H = convs[0].out_channels
-        Wcat = torch.cat([lin.weight for lin in convs[0].lins], 0)
-        Y0, B = _x_wt(x, Wcat[:H]), _x_wt(x, Wcat[H:])                # _ChebConv.forward's two products: bitwise the serial path's
-        want_w = weighted
-        logits = lambda parent, smp: _drawn_cheb_logits(parent, smp, smp.w if weighted else None, convs, K, Y0, B)
-    elif isinstance(model, ChebModel):
-        fixed = model(batch, ei).contiguous()                         # [N, C], the same for every draw
-        logits = None
-    else:
-        raise TypeError(f"ensemble_partition_head: no batched engine for {type(model).__name__}")
-    parent = get_graph(ei, N) if logits is not None else None
-    D_total = sum(int(ps[0]) for ps in passes)
-    acc = None
-    done = 0
-    logs, edges = [], []
-    for k, (Dc, noise, seed, sid0) in enumerate(passes):
-        smp = None
-        if logits is not None or trace is not None:
-            smp = sample_topq_multi(mode, p, None, 0.0, q, ei, Dc, noise=noise, seed=seed, stream_id0=sid0, want_edge_index=trace is not None,
-                                    want_w=want_w, cover=cover)
-        if logits is not None:
-            out = logits(parent, smp)
-            stride = N * out.shape[2]
-        else:
-            out, stride = fixed, 0
-        if acc is None:
-            acc = torch.empty(N, out.shape[-1], dtype=torch.float32, device=x.device)
-        done += Dc
-        ensemble_mean_correct(out, stride, Dc, acc, k == 0, done == D_total, D_total, batch.y,
-                              (batch.train_mask, batch.val_mask, batch.test_mask), counts)
-        if trace is not None:
-            logs.append(out if stride else out.unsqueeze(0).expand(Dc, *out.shape))
-            edges.append(smp.edge_index)
-    if trace is not None:
-        trace["logits"], trace["mean"], trace["edges"] = torch.cat(logs), acc, torch.cat(edges)
-    return acc
 
 
 # ------------------------------------------------------------------ Chebyshev head, K > 1 (csrc/cheb.hip)

@@ -250,7 +250,7 @@ def test_ops_signatures(pkg):
     import inspect
     ops = pkg.ops
     assert inspect.signature(ops.sample_topq_multi).parameters["cover"].default is None
-    for fn in (ops.ensemble_partition, ops.ensemble_partition_head):
+    for fn in (pkg.eval_batch.ensemble_partition, pkg.eval_batch.ensemble_partition_head):
         prm = inspect.signature(fn).parameters["cover"]
         assert prm.kind is inspect.Parameter.KEYWORD_ONLY and prm.default is None
     assert "cover_info" in ops.MultiSampleResult.__slots__

@@ -161,7 +161,7 @@ def _per_today(E, q, N, H, C, head, gat_heads=1, gat_edge=False, cheb_k=1, cover
 
 
 def _v2_allocations(q, N, C, K):
-    """What ops._drawn_gatv2_logits allocates per draw beside the hidden block, the logits and the drawn edge's weight, as plan_draws'
+    """What eval_batch._drawn_gatv2_logits allocates per draw beside the hidden block, the logits and the drawn edge's weight, as plan_draws'
     docstring lists it: attention values [q, K], loop attentions [N, K], the layer-2 product [N, 2 K C], its halves x_l, x_r [N, K C]."""
     return 4 * q * K + 4 * N * K + 4 * N * 2 * K * C + 2 * 4 * N * K * C
 
@@ -249,6 +249,6 @@ def test_ops_signatures(pkg):
     ops = pkg.ops
     assert list(inspect.signature(ops.gatv2_alpha_heads_multi).parameters) == ["xl", "xr", "x_stride", "att", "csr", "q", "N", "K", "negative_slope",
                                                                                "edge_w", "lin_edge", "out"]
-    assert list(inspect.signature(ops._drawn_gatv2_logits).parameters) == ["parent", "smp", "convs", "xl1", "xr1", "w"]
+    assert list(inspect.signature(pkg.eval_batch._drawn_gatv2_logits).parameters) == ["parent", "smp", "convs", "xl1", "xr1", "w"]
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         ops.gatv2_alpha_heads_multi(torch.zeros(4, 8), torch.zeros(4, 8), 0, torch.zeros(8), (torch.zeros(1, 5, dtype=torch.int32),) * 3, 0, 4, 2, 0.2)

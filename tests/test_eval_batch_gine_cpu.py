@@ -1,6 +1,6 @@
 """CPU: the batched engine of the GINE head (GINModel(gin_edge_weight=True)) -- the routing opt-in `args.sgs_eval_batch_gine`, the
 planner's `gine_in` term, the C entry point sgs_gine_aggregate_fwd_multi (declaration, export, every guard through the error channel) and
-an fp64 restatement of ops._drawn_gine_logits' per-draw mathematics held to gine_ref.gine_model.  Nothing here needs a GPU."""
+an fp64 restatement of eval_batch._drawn_gine_logits' per-draw mathematics held to gine_ref.gine_model.  Nothing here needs a GPU."""
 import argparse
 import ctypes
 import itertools
@@ -213,7 +213,7 @@ def _hand_draws():
 
 
 def _drawn_gine_logits_fp64(P, x, edges, w):
-    """ops._drawn_gine_logits, restated: per layer the aggregate of every draw (layer 1 over the shared x, layer 2 over the draw's own
+    """eval_batch._drawn_gine_logits, restated: per layer the aggregate of every draw (layer 1 over the shared x, layer 2 over the draw's own
     block of the stacked hidden rows), then the MLP's two Linears over the stacked [D N, .] rows, ReLU between the layers."""
     D, N = len(edges), x.shape[0]
     h = x
@@ -256,6 +256,6 @@ def test_ops_signatures(pkg):
     import inspect
     ops = pkg.ops
     assert list(inspect.signature(ops.gine_aggregate_multi).parameters) == ["x", "x_stride", "csr", "w", "a", "b", "diag", "q", "N", "Dc"]
-    assert list(inspect.signature(ops._drawn_gine_logits).parameters)[:4] == ["parent", "smp", "w", "convs"]
+    assert list(inspect.signature(pkg.eval_batch._drawn_gine_logits).parameters)[:4] == ["parent", "smp", "w", "convs"]
     prm = inspect.signature(_ev().plan_draws).parameters["gine_in"]
     assert prm.kind is inspect.Parameter.KEYWORD_ONLY and prm.default == 0

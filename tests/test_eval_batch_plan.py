@@ -31,8 +31,9 @@ def test_new_symbols_declared_and_exported(pkg):
     for name in NEW:
         assert name in protos, name
         assert name in exported and hasattr(L, name), name
-    for name in ("sample_topq_multi", "ensemble_partition", "ensemble_mean_correct"):
+    for name in ("sample_topq_multi", "ensemble_mean_correct"):
         assert callable(getattr(pkg.ops, name))
+    assert callable(pkg.eval_batch.ensemble_partition)
 
 
 def test_sample_topq_multi_argument_validation(pkg):

@@ -370,8 +370,8 @@ def test_batched_gatv2_matches_fp64_with_explicit_noise(K, edge):
         parent = ops.get_graph(bd.edge_index, bd.x.shape[0])
         with torch.no_grad():
             xl1, xr1, _ = _v2_inputs(m, bd.x)
-            unit = ops._drawn_gatv2_logits(parent, smp, tuple(m.GAT.convs), xl1, xr1, None)
-            again = ops._drawn_gatv2_logits(parent, smp, tuple(m.GAT.convs), xl1, xr1, smp.w)
+            unit = S.eval_batch._drawn_gatv2_logits(parent, smp, tuple(m.GAT.convs), xl1, xr1, None)
+            again = S.eval_batch._drawn_gatv2_logits(parent, smp, tuple(m.GAT.convs), xl1, xr1, smp.w)
         assert float((again - got).abs().max()) <= SERIAL_TOL * float(got.abs().max())
         assert float((unit - got).abs().max()) > 100 * SERIAL_TOL * float(got.abs().max())
 

@@ -255,8 +255,8 @@ def test_batched_gine_matches_fp64_with_explicit_noise_and_the_weights_reach_the
         assert err <= FWD_BOUND, (d, err)
     # the same draws with unit weights give other logits: the weights reach the messages
     with torch.no_grad():
-        unit = ops._drawn_gine_logits(ops.get_graph(bd.edge_index, bd.x.shape[0]), smp, None, tuple(m.GIN.convs), bd.x.contiguous())
-        again = ops._drawn_gine_logits(ops.get_graph(bd.edge_index, bd.x.shape[0]), smp, smp.w, tuple(m.GIN.convs), bd.x.contiguous())
+        unit = S.eval_batch._drawn_gine_logits(ops.get_graph(bd.edge_index, bd.x.shape[0]), smp, None, tuple(m.GIN.convs), bd.x.contiguous())
+        again = S.eval_batch._drawn_gine_logits(ops.get_graph(bd.edge_index, bd.x.shape[0]), smp, smp.w, tuple(m.GIN.convs), bd.x.contiguous())
     assert torch.equal(again, got)
     assert not torch.equal(unit, got)
 
