@@ -207,10 +207,8 @@ __device__ __forceinline__ void finish(const StepArgs& a, int64_t i, int64_t c, 
 
 // Short rows (whole graphs of low degree): a group of LPR lanes owns one output row, each lane VEC consecutive columns per chunk,
 // four independent row gathers in flight (the load order sgs_spmm_csr settled on).
-// The *_body function below holds the same row code as the single-draw kernel after it and serves the multi-draw kernel only: calling
-// the body from the single-draw kernel as well changed that kernel's register allocation and instruction order, so it keeps its own text
-// ("The heads' options"); tests/test_gpu_ensemble_batched_variants.py pins the two bitwise equal per draw.  The
-// other *_body functions of this file follow the same rule.
+// The *_body function below is the only copy of the row code: the single-draw kernel after it and the multi-draw kernel both call it, as
+// do the two callers of cheb_spmm_rowblock_body ("The bodies").
 template <int VEC, int LPR>
 __device__ __forceinline__ void cheb_spmm_rows_body(const StepArgs& a, int64_t N, int64_t D, const int* __restrict__ ptr,
                                                     const int* __restrict__ col, const float* __restrict__ val) {
@@ -253,46 +251,15 @@ __device__ __forceinline__ void cheb_spmm_rows_body(const StepArgs& a, int64_t N
 template <int VEC, int LPR>
 __global__ void __launch_bounds__(kT) cheb_spmm_rows(StepArgs a, int64_t N, int64_t D, const int* __restrict__ ptr,
                                                     const int* __restrict__ col, const float* __restrict__ val) {
-    using V = typename VecT<VEC>::type;
-    constexpr int RPB = kT / LPR;
-    const int sub = threadIdx.x % LPR;
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * RPB + threadIdx.x / LPR;
-    if (i >= N) return;
-    const uint32_t rkey = dropout_row_key(fold_epoch(a.seed, a.epoch), a.site, static_cast<uint64_t>(i));
-    const int b = ptr[i], e = ptr[i + 1];
-    const float* __restrict__ X = a.X;
-    const int64_t ldx = a.ldx;
-    for (int64_t c0 = static_cast<int64_t>(sub) * VEC; c0 < D; c0 += static_cast<int64_t>(LPR) * VEC) {
-        float acc[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        int k = b;
-        for (; k + 4 <= e; k += 4) {
-            int j[4]; float w[4]; float x[4][VEC];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { j[u] = col[k + u]; w[u] = val[k + u]; }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) *reinterpret_cast<V*>(x[u]) = *reinterpret_cast<const V*>(X + static_cast<int64_t>(j[u]) * ldx + c0);
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
-        }
-        for (; k < e; ++k) {
-            float x[VEC];
-            *reinterpret_cast<V*>(x) = *reinterpret_cast<const V*>(X + static_cast<int64_t>(col[k]) * ldx + c0);
-            const float w = val[k];
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, x[v], acc[v]);
-        }
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) finish(a, i, c0 + v, acc[v], rkey);
-    }
+    cheb_spmm_rows_body<VEC, LPR>(a, N, D, ptr, col, val);
 }
 
 // Long rows (partitions: ~1k rows of tens to hundreds of entries): a workgroup of NW waves owns a row, each wave gathers a strided
 // share of its entries (8 in flight) and the partial sums meet in LDS in a fixed order.  NW = 16 for very long rows.
-template <int VEC, int NW>
+// SINGLE selects no code: it is true from the single-draw kernel, so that each caller has an instantiation of its own.  The multi-draw
+// kernel's LDS array reaches the body as a constant only while that kernel is the instantiation's one caller; sharing it changed the
+// multi-draw kernel's instruction order.  (cheb_spmm_rows_body takes no such argument and is shared as it is.)
+template <int VEC, int NW, bool SINGLE = false>
 __device__ __forceinline__ void cheb_spmm_rowblock_body(const StepArgs& a, int64_t N, int64_t D, const int* __restrict__ ptr,
                                                              const int* __restrict__ col, const float* __restrict__ val, float (*part)[64 * VEC]) {
     using V = typename VecT<VEC>::type;
@@ -347,55 +314,8 @@ __device__ __forceinline__ void cheb_spmm_rowblock_body(const StepArgs& a, int64
 template <int VEC, int NW>
 __global__ void __launch_bounds__(64 * NW) cheb_spmm_rowblock(StepArgs a, int64_t N, int64_t D, const int* __restrict__ ptr,
                                                              const int* __restrict__ col, const float* __restrict__ val) {
-    using V = typename VecT<VEC>::type;
     __shared__ float part[NW][64 * VEC];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t i = blockIdx.x;
-    const int b = ptr[i], e = ptr[i + 1];
-    const uint32_t rkey = dropout_row_key(fold_epoch(a.seed, a.epoch), a.site, static_cast<uint64_t>(i));
-    const float* __restrict__ X = a.X;
-    const int64_t ldx = a.ldx;
-    for (int64_t cbase = 0; cbase < D; cbase += 64 * VEC) {
-        const int64_t c0 = cbase + static_cast<int64_t>(lane) * VEC;
-        float acc[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        if (c0 < D) {
-            int k = b + wave;
-            for (; k + 7 * NW < e; k += 8 * NW) {
-                int j[8]; float w[8]; V x[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { j[u] = col[k + NW * u]; w[u] = val[k + NW * u]; }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) x[u] = *reinterpret_cast<const V*>(X + static_cast<int64_t>(j[u]) * ldx + c0);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    float xv[VEC];
-                    *reinterpret_cast<V*>(xv) = x[u];
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], xv[v], acc[v]);
-                }
-            }
-            for (; k < e; k += NW) {
-                float xv[VEC];
-                *reinterpret_cast<V*>(xv) = *reinterpret_cast<const V*>(X + static_cast<int64_t>(col[k]) * ldx + c0);
-                const float w = val[k];
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, xv[v], acc[v]);
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) part[wave][lane * VEC + v] = acc[v];
-        __syncthreads();
-        const int t = threadIdx.x;                 // 64 * VEC columns finished by the first 64 * VEC threads
-        if (t < 64 * VEC && cbase + t < D) {
-            float s = 0.f;
-#pragma unroll
-            for (int g = 0; g < NW; g += 4) s += (part[g][t] + part[g + 1][t]) + (part[g + 2][t] + part[g + 3][t]);
-            finish(a, i, cbase + t, s, rkey);
-        }
-        __syncthreads();
-    }
+    cheb_spmm_rowblock_body<VEC, NW, true>(a, N, D, ptr, col, val, part);
 }
 
 // One recurrence step for the D drawn subgraphs of a partition (ensemble evaluation: forward only, bias / ReLU, no dropout, no Y2):

@@ -288,10 +288,13 @@ __device__ __forceinline__ float head_max_all(float v) {
 // soft / alpha [n, K] by edge id (0 for (i, i) entries), soft_loop / alpha_loop [N, K].  Attention dropout is keyed (site, row = edge id,
 // col = head) and (site + 1, row = node, col = head): sgs_dropout_keep(seed, site, E, K, p) is the mask used, column 0 at K = 1 the
 // one-head kernel's.
-// The *_body function below holds the same row code as the single-draw kernel after it and serves the multi-draw kernel only: calling
-// the body from the single-draw kernel as well changed that kernel's register allocation and instruction order, so it keeps its own text
-// ("The heads' options"); tests/test_gpu_ensemble_batched_variants.py pins the two bitwise equal per draw.  The
-// other *_body functions of this file follow the same rule.
+// The *_body function below is the only copy of the row code: the single-draw kernel after it (SOFT = true) and the multi-draw kernel
+// (SOFT = false) are its two callers, and the other *_body functions of this file follow the same rule.  Each caller gets an
+// instantiation of its own (SOFT here, SINGLE on the SpMM bodies, which have no option to tell the two apart): the multi-draw kernels pass
+// constants for the dropout arguments, the compiler folds the constants of an internal function's only caller into it before it inlines,
+// and an instantiation shared with a caller that passes variables loses that and came out with another register allocation in the
+// multi-draw kernels.  With one instantiation per caller their ISA is the one they had when they were the bodies' only users
+// ("The bodies").
 template <int KP, bool SOFT>
 __device__ __forceinline__ void gat_alpha_heads_fwd_body(int64_t i, int lane, const float* __restrict__ a_s, const float* __restrict__ a_d, int K,
                                                          const int* __restrict__ in_ptr, const int* __restrict__ in_src,
@@ -349,51 +352,12 @@ __global__ void __launch_bounds__(kT) gat_alpha_heads_fwd(const float* __restric
                                                          int use_drop, uint64_t seed, uint32_t site, const uint64_t* __restrict__ epoch,
                                                          float* __restrict__ soft, float* __restrict__ soft_loop, float* __restrict__ alpha,
                                                          float* __restrict__ alpha_loop) {
-    constexpr int EPW = 64 / KP;
     seed = fold_epoch(seed, epoch);
     const int lane = threadIdx.x & 63;
     const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
     if (i >= N) return;                                       // wave-uniform
-    const int h = lane & (KP - 1), sub = lane / KP;
-    const bool hv = h < K;
-    const int hc = hv ? h : 0;
-    const int b = in_ptr[i], e = in_ptr[i + 1];
-    const float ad = a_d[i * K + hc];
-    const float eloop = lrelu(a_s[i * K + hc] + ad, slope);
-    float mx = eloop;
-    for (int k = b + sub; k < e; k += EPW) {
-        const int s = in_src[k];
-        if (s != static_cast<int>(i)) mx = fmaxf(mx, lrelu(a_s[static_cast<int64_t>(s) * K + hc] + ad, slope));
-    }
-    mx = head_max_all<KP>(mx);
-    float sum = 0.f;
-    for (int k = b + sub; k < e; k += EPW) {
-        const int s = in_src[k];
-        if (s != static_cast<int>(i)) sum += expf(lrelu(a_s[static_cast<int64_t>(s) * K + hc] + ad, slope) - mx);
-    }
-    sum = head_sum_all<KP>(sum) + expf(eloop - mx);
-    const float inv = 1.0f / (sum + 1e-16f);                  // torch_geometric.utils.softmax: / (sum + 1e-16)
-    for (int k = b + sub; k < e; k += EPW) {
-        const int s = in_src[k];
-        const int64_t ed = in_eid[k];
-        float sm = 0.f, al = 0.f;
-        if (s != static_cast<int>(i)) {
-            sm = expf(lrelu(a_s[static_cast<int64_t>(s) * K + hc] + ad, slope) - mx) * inv;
-            al = sm;
-            if (use_drop) al = dropout_keep_at(seed, site, static_cast<uint64_t>(ed), static_cast<uint32_t>(hc), drop_thresh) ? sm * drop_scale : 0.f;
-        }
-        if (hv) {
-            soft[ed * K + h] = sm;
-            alpha[ed * K + h] = al;
-        }
-    }
-    if (sub == 0 && hv) {
-        const float sm = expf(eloop - mx) * inv;
-        float al = sm;
-        if (use_drop) al = dropout_keep_at(seed, site + 1u, static_cast<uint64_t>(i), static_cast<uint32_t>(h), drop_thresh) ? sm * drop_scale : 0.f;
-        soft_loop[i * K + h] = sm;
-        alpha_loop[i * K + h] = al;
-    }
+    gat_alpha_heads_fwd_body<KP, true>(i, lane, a_s, a_d, K, in_ptr, in_src, in_eid, slope, drop_scale, drop_thresh, use_drop, seed, site, soft,
+                                       soft_loop, alpha, alpha_loop);
 }
 
 // D drawn graphs of one partition (ensemble evaluation: no attention dropout, no kept softmax): blockIdx.y = draw d, which reads the node
@@ -551,62 +515,12 @@ __global__ void __launch_bounds__(kT) gat_alpha_heads_edge_fwd(const float* __re
                                                               int use_drop, uint64_t seed, uint32_t site, const uint64_t* __restrict__ epoch,
                                                               float* __restrict__ soft, float* __restrict__ soft_loop, float* __restrict__ alpha,
                                                               float* __restrict__ alpha_loop, float* __restrict__ wbar, float* __restrict__ inv_cnt) {
-    constexpr int EPW = 64 / KP;
     seed = fold_epoch(seed, epoch);
     const int lane = threadIdx.x & 63;
     const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
     if (i >= N) return;                                       // wave-uniform
-    const int h = lane & (KP - 1), sub = lane / KP;
-    const bool hv = h < K;
-    const int hc = hv ? h : 0;
-    const int b = in_ptr[i], e = in_ptr[i + 1];
-    const float ad = a_d[i * K + hc];
-    const float c = coef[hc];
-    float mx = -INFINITY, wsum = 0.f, cnt = 0.f;
-    for (int k = b + sub; k < e; k += EPW) {
-        const int s = in_src[k];
-        if (s != static_cast<int>(i)) {
-            const float we = w[in_eid[k]];
-            mx = fmaxf(mx, edge_logit(a_s[static_cast<int64_t>(s) * K + hc], ad, we, c, slope));
-            wsum += we;
-            cnt += 1.f;
-        }
-    }
-    wsum = head_sum_all<KP>(wsum);                            // over the entries (the KP lanes of an entry hold the same weight)
-    cnt = head_sum_all<KP>(cnt);
-    const float icnt = cnt > 0.f ? 1.0f / cnt : 0.f;
-    const float wb = wsum * icnt;
-    const float eloop = edge_logit(a_s[i * K + hc], ad, wb, c, slope);
-    mx = fmaxf(head_max_all<KP>(mx), eloop);
-    float sum = 0.f;
-    for (int k = b + sub; k < e; k += EPW) {
-        const int s = in_src[k];
-        if (s != static_cast<int>(i)) sum += expf(edge_logit(a_s[static_cast<int64_t>(s) * K + hc], ad, w[in_eid[k]], c, slope) - mx);
-    }
-    sum = head_sum_all<KP>(sum) + expf(eloop - mx);
-    const float inv = 1.0f / (sum + 1e-16f);                  // torch_geometric.utils.softmax: / (sum + 1e-16)
-    for (int k = b + sub; k < e; k += EPW) {
-        const int s = in_src[k];
-        const int64_t ed = in_eid[k];
-        float sm = 0.f, al = 0.f;
-        if (s != static_cast<int>(i)) {
-            sm = expf(edge_logit(a_s[static_cast<int64_t>(s) * K + hc], ad, w[ed], c, slope) - mx) * inv;
-            al = sm;
-            if (use_drop) al = dropout_keep_at(seed, site, static_cast<uint64_t>(ed), static_cast<uint32_t>(hc), drop_thresh) ? sm * drop_scale : 0.f;
-        }
-        if (hv) {
-            soft[ed * K + h] = sm;
-            alpha[ed * K + h] = al;
-        }
-    }
-    if (sub == 0 && hv) {
-        const float sm = expf(eloop - mx) * inv;
-        float al = sm;
-        if (use_drop) al = dropout_keep_at(seed, site + 1u, static_cast<uint64_t>(i), static_cast<uint32_t>(h), drop_thresh) ? sm * drop_scale : 0.f;
-        soft_loop[i * K + h] = sm;
-        alpha_loop[i * K + h] = al;
-    }
-    if (lane == 0) { wbar[i] = wb; inv_cnt[i] = icnt; }
+    gat_alpha_heads_edge_fwd_body<KP, true>(i, lane, a_s, a_d, w, coef, K, in_ptr, in_src, in_eid, slope, drop_scale, drop_thresh, use_drop, seed,
+                                            site, soft, soft_loop, alpha, alpha_loop, wbar, inv_cnt);
 }
 
 // The multi-draw form of the above (see gat_alpha_heads_fwd_multi): draw d's weights are w + d * nnz (by the draw's edge id), coef [K] is
@@ -853,7 +767,9 @@ __device__ __forceinline__ void spmm_heads_acc(const float* __restrict__ X, int6
 // columns belong to one head; with VEC = 1 any C is correct): at K C = 256 a wave gathers the same 1 KB row as the one-head layer and
 // the K weights of an entry arrive as one 4 K-byte read.  BCAST (backward of the head mean): X is [N, C], shared by the heads, and the
 // result is scaled by 1 / K:  Y[i, h C + c] = (1 / K) (sum_k val[eid_k, h] X[col_k, c] + diag[i, h] X[i, c]).
-template <int VEC, bool BCAST>
+// SINGLE (here and on the two head-mean bodies) selects no code: it is true from the single-draw kernel and gives each caller its own
+// instantiation (see the note at gat_alpha_heads_fwd_body).
+template <int VEC, bool BCAST, bool SINGLE = false>
 __device__ __forceinline__ void spmm_csr_heads_body(const float* __restrict__ X, int64_t N, int K, int64_t C, const int* __restrict__ ptr,
                                                     const int* __restrict__ col, const int* __restrict__ eid, const float* __restrict__ val,
                                                     const float* __restrict__ diag, const float* __restrict__ bias, int act, float drop_scale,
@@ -891,38 +807,14 @@ __global__ void __launch_bounds__(kT) spmm_csr_heads(const float* __restrict__ X
                                                     const float* __restrict__ diag, const float* __restrict__ bias, int act, float drop_scale,
                                                     uint32_t drop_thresh, uint64_t seed, uint32_t site, const uint64_t* __restrict__ epoch,
                                                     float* __restrict__ Y, int lg) {
-    using V = typename std::conditional<VEC == 4, float4, float>::type;
     seed = fold_epoch(seed, epoch);
-    const int LPR = 1 << lg;
-    const int sub = threadIdx.x & (LPR - 1);
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * (kT >> lg) + (threadIdx.x >> lg);
-    if (i >= N) return;
-    const int64_t D = static_cast<int64_t>(K) * C;
-    const int64_t XD = BCAST ? C : D;
-    const float post = BCAST ? 1.0f / static_cast<float>(K) : 1.0f;
-    const int b = ptr[i], e = ptr[i + 1];
-    for (int64_t c0 = static_cast<int64_t>(sub) * VEC; c0 < D; c0 += static_cast<int64_t>(LPR) * VEC) {
-        const int h = static_cast<int>(c0 / C);
-        const int64_t xc = BCAST ? c0 - h * C : c0;
-        float acc[VEC];
-        spmm_heads_acc<VEC>(X, XD, xc, K, h, i, b, e, col, eid, val, diag, acc);
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-            float y = BCAST ? acc[v] * post : acc[v];
-            if (bias) y += bias[c0 + v];
-            if (act != SGS_ACT_NONE) y = fmaxf(y, 0.f);
-            if (act == SGS_ACT_RELU_DROPOUT)
-                y = dropout_keep_at(seed, site, static_cast<uint64_t>(i), static_cast<uint32_t>(c0 + v), drop_thresh) ? y * drop_scale : 0.f;
-            acc[v] = y;
-        }
-        *reinterpret_cast<V*>(Y + i * D + c0) = *reinterpret_cast<V*>(acc);
-    }
+    spmm_csr_heads_body<VEC, BCAST, true>(X, N, K, C, ptr, col, eid, val, diag, bias, act, drop_scale, drop_thresh, seed, site, Y, lg);
 }
 
 // The head-mean form (GATConv concat = False), fused: Y[i, c] = (1 / K) sum_h (sum_k val[eid_k, h] X[col_k, h C + c] + diag[i, h] X[i, h C + c])
 // + bias[c].  A lane owns VEC output columns and walks the K heads of each gathered row itself (heads in order 0 .. K - 1 per entry, entries
 // in CSR order), so the [N, K C] per-head result is never written and no second launch averages it.
-template <int VEC>
+template <int VEC, bool SINGLE = false>
 __device__ __forceinline__ void spmm_csr_heads_mean_body(const float* __restrict__ X, int64_t N, int K, int64_t C, const int* __restrict__ ptr,
                                                          const int* __restrict__ col, const int* __restrict__ eid, const float* __restrict__ val,
                                                          const float* __restrict__ diag, const float* __restrict__ bias, int act, float drop_scale,
@@ -971,43 +863,8 @@ __global__ void __launch_bounds__(kT) spmm_csr_heads_mean(const float* __restric
                                                          const float* __restrict__ diag, const float* __restrict__ bias, int act, float drop_scale,
                                                          uint32_t drop_thresh, uint64_t seed, uint32_t site, const uint64_t* __restrict__ epoch,
                                                          float* __restrict__ Y, int lg) {
-    using V = typename std::conditional<VEC == 4, float4, float>::type;
     seed = fold_epoch(seed, epoch);
-    const int LPR = 1 << lg;
-    const int sub = threadIdx.x & (LPR - 1);
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * (kT >> lg) + (threadIdx.x >> lg);
-    if (i >= N) return;
-    const int64_t D = static_cast<int64_t>(K) * C;
-    const float invK = 1.0f / static_cast<float>(K);
-    const int b = ptr[i], e = ptr[i + 1];
-    for (int64_t c0 = static_cast<int64_t>(sub) * VEC; c0 < C; c0 += static_cast<int64_t>(LPR) * VEC) {
-        float acc[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        for (int k = b; k <= e; ++k) {                        // k == e: the loop term
-            const bool loop = k == e;
-            if (loop && !diag) break;
-            const float* xr = X + (loop ? i : static_cast<int64_t>(col[k])) * D + c0;
-            const float* wr = loop ? diag + i * K : val + static_cast<int64_t>(eid[k]) * K;
-            for (int h = 0; h < K; ++h) {
-                float x[VEC];
-                *reinterpret_cast<V*>(x) = *reinterpret_cast<const V*>(xr + h * C);
-                const float w = wr[h];
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, x[v], acc[v]);
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-            float y = acc[v] * invK;
-            if (bias) y += bias[c0 + v];
-            if (act != SGS_ACT_NONE) y = fmaxf(y, 0.f);
-            if (act == SGS_ACT_RELU_DROPOUT)
-                y = dropout_keep_at(seed, site, static_cast<uint64_t>(i), static_cast<uint32_t>(c0 + v), drop_thresh) ? y * drop_scale : 0.f;
-            acc[v] = y;
-        }
-        *reinterpret_cast<V*>(Y + i * C + c0) = *reinterpret_cast<V*>(acc);
-    }
+    spmm_csr_heads_mean_body<VEC, true>(X, N, K, C, ptr, col, eid, val, diag, bias, act, drop_scale, drop_thresh, seed, site, Y, lg);
 }
 
 // The same head mean with the concat kernel's lane layout (a lane owns VEC columns of the [K C] per-head row, so a wave gathers whole rows and
@@ -1015,7 +872,7 @@ __global__ void __launch_bounds__(kT) spmm_csr_heads_mean(const float* __restric
 // lanes c < C add the K heads of column c in order 0 .. K - 1.  Used when K C rows fit (kMeanLdsFloats); the kernel above walks the heads in
 // each lane with C / VEC lanes per row and was 6x slower at K = 8, C = 5 on a power-law graph, where 8 lanes served a hub row alone.
 constexpr int kMeanLdsFloats = 4096;
-template <int VEC>
+template <int VEC, bool SINGLE = false>
 __device__ __forceinline__ void spmm_csr_heads_mean_lds_body(const float* __restrict__ X, int64_t N, int K, int64_t C, const int* __restrict__ ptr,
                                                              const int* __restrict__ col, const int* __restrict__ eid, const float* __restrict__ val,
                                                              const float* __restrict__ diag, const float* __restrict__ bias, int act, float drop_scale,
@@ -1059,35 +916,7 @@ __global__ void __launch_bounds__(kT) spmm_csr_heads_mean_lds(const float* __res
                                                              float* __restrict__ Y, int lg) {
     __shared__ float part[kMeanLdsFloats];
     seed = fold_epoch(seed, epoch);
-    const int LPR = 1 << lg;
-    const int sub = threadIdx.x & (LPR - 1), r = threadIdx.x >> lg;
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * (kT >> lg) + r;
-    const bool live = i < N;                                  // every thread reaches the barrier
-    const int64_t D = static_cast<int64_t>(K) * C;
-    float* mine = part + r * D;
-    if (live) {
-        const int b = ptr[i], e = ptr[i + 1];
-        for (int64_t c0 = static_cast<int64_t>(sub) * VEC; c0 < D; c0 += static_cast<int64_t>(LPR) * VEC) {
-            const int h = static_cast<int>(c0 / C);
-            float acc[VEC];
-            spmm_heads_acc<VEC>(X, D, c0, K, h, i, b, e, col, eid, val, diag, acc);
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) mine[c0 + v] = acc[v];
-        }
-    }
-    __syncthreads();
-    if (!live) return;
-    const float invK = 1.0f / static_cast<float>(K);
-    for (int64_t c = sub; c < C; c += LPR) {
-        float y = 0.f;
-        for (int h = 0; h < K; ++h) y += mine[h * C + c];
-        y *= invK;
-        if (bias) y += bias[c];
-        if (act != SGS_ACT_NONE) y = fmaxf(y, 0.f);
-        if (act == SGS_ACT_RELU_DROPOUT)
-            y = dropout_keep_at(seed, site, static_cast<uint64_t>(i), static_cast<uint32_t>(c), drop_thresh) ? y * drop_scale : 0.f;
-        Y[i * C + c] = y;
-    }
+    spmm_csr_heads_mean_lds_body<VEC, true>(X, N, K, C, ptr, col, eid, val, diag, bias, act, drop_scale, drop_thresh, seed, site, Y, lg, part);
 }
 
 // D drawn graphs of one partition (ensemble evaluation: ReLU / bias only, no dropout): blockIdx.y = draw d, which reads X + d * xs (xs = 0:
