@@ -107,12 +107,11 @@ struct ScoreArgs {
 // Workgroup = 64 edges x all HP = 32*NT hidden units; wave (eg, hh) owns edges 32eg..32eg+31 and
 // hidden units hh*HP/2 .. (hh+1)*HP/2 - 1, i.e. NT/2 accumulator tiles of 32x32 (<= 64 registers),
 // small enough that three independent workgroups share a CU and hide each other's tile staging,
-// prologue and epilogue behind MFMAs.  EXACT: H == 32*NT (the production H = 256): every bounds
-// check on k / h folds away.
+// prologue and epilogue behind MFMAs.
 // EPD (endpoint dropout, EdgeProbMLP with dropout > 0): the endpoint codes are masked per (edge, endpoint) before the features are
 // formed, so the node-level split U[s] - U[d] does not exist: the contraction runs over all 2H features -- k < H: x_m * y_m against
 // W1[:, k], k >= H: x_m - y_m against W1[:, k] (WaT is then the full [2H][H] transpose) -- and BWD writes feat [n, 2H].
-template <int NT, bool BWD, bool EXACT, bool EPD = false>
+template <int NT, bool BWD, bool EPD = false>
 __global__ void __launch_bounds__(kT, 3) edge_score_kernel(ScoreArgs a) {
     constexpr int HP = 32 * NT;
     constexpr int NTW = NT / 2;                                   // tiles per wave
@@ -125,7 +124,7 @@ __global__ void __launch_bounds__(kT, 3) edge_score_kernel(ScoreArgs a) {
     float* zpart = reinterpret_cast<float*>(d_idx + kBM);         // [2][64]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int eg = wave & 1, hh = wave >> 1;
-    const int H = EXACT ? HP : a.H;
+    const int H = a.H;
     const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kBM;
     if (a.dyn_n) {
         const int64_t live_n = *a.dyn_n;                          // never more than the capacity the launch was sized for
@@ -182,14 +181,14 @@ __global__ void __launch_bounds__(kT, 3) edge_score_kernel(ScoreArgs a) {
             const int i = j * kT + tid;
             const int k = i / (HP / 4), h4 = (i % (HP / 4)) * 4;
             wreg[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (EXACT || (i < kBK * (HP / 4) && k0 + k < KT && h4 < H))
+            if (i < kBK * (HP / 4) && k0 + k < KT && h4 < H)
                 wreg[j] = *reinterpret_cast<const float4*>(a.WaT + static_cast<int64_t>(k0 + k) * H + h4);
         }
         const int kf = k0 + 4 * fc;                              // feature index (0 .. KT - 1)
         const int kk = (EPD && kf >= H) ? kf - H : kf;           // column of the codes it is formed from
         xreg = make_float4(0.f, 0.f, 0.f, 0.f);
         yreg = xreg;
-        if (EXACT || kf < KT) {
+        if (kf < KT) {
             xreg = *reinterpret_cast<const float4*>(a.codes + static_cast<int64_t>(my_s) * H + kk);
             yreg = *reinterpret_cast<const float4*>(a.codes + static_cast<int64_t>(my_d) * H + kk);
             if (EPD && a.epd) { ep_mask(xreg, rkx, kk); ep_mask(yreg, rky, kk); }
@@ -201,7 +200,7 @@ __global__ void __launch_bounds__(kT, 3) edge_score_kernel(ScoreArgs a) {
 #pragma unroll
         for (int j = 0; j < kWV; ++j) {
             const int i = j * kT + tid;
-            if (EXACT || i < kBK * (HP / 4)) {
+            if (i < kBK * (HP / 4)) {
                 const int k = i / (HP / 4), h4 = (i % (HP / 4)) * 4;
                 *reinterpret_cast<float4*>(Wt_s + k * HP + h4) = wreg[j];
             }
@@ -212,7 +211,7 @@ __global__ void __launch_bounds__(kT, 3) edge_score_kernel(ScoreArgs a) {
         if (BWD) {
             const int64_t r = row0 + fe;
             const int kk = k0 + 4 * fc;
-            if (r < a.n && (EXACT || kk < KT)) *reinterpret_cast<float4*>(a.feat + r * KT + kk) = f;
+            if (r < a.n && kk < KT) *reinterpret_cast<float4*>(a.feat + r * KT + kk) = f;
         }
         Ft_s[(4 * fc + 0) * kBM + fe] = f.x;
         Ft_s[(4 * fc + 1) * kBM + fe] = f.y;
@@ -265,7 +264,7 @@ __global__ void __launch_bounds__(kT, 3) edge_score_kernel(ScoreArgs a) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int hb = hh * (HP / 2) + 32 * t + 8 * g + 4 * kh;
-            if (EXACT || hb < H) {
+            if (hb < H) {
                 const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
                 const float4 us = EPD ? z4 : *reinterpret_cast<const float4*>(Us + hb);          // EPD: no node-level term
                 const float4 ud = EPD ? z4 : *reinterpret_cast<const float4*>(Ud + hb);
@@ -314,7 +313,7 @@ __global__ void __launch_bounds__(kT, 3) edge_score_kernel(ScoreArgs a) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int hb = hh * (HP / 2) + 32 * t + 8 * g + 4 * kh;
-            if (EXACT || hb < H) {
+            if (hb < H) {
                 const float4 ww = *reinterpret_cast<const float4*>(a.w2 + hb);
                 const float w4[4] = {ww.x, ww.y, ww.z, ww.w};
                 float dv4[4], hz4[4];
@@ -1265,7 +1264,9 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) edge_score_bf16x6_kernel(Scor
 #pragma unroll
         for (int q = 0; q < kSlots; ++q) split_slot(q, f, kc_, wr, P, st);
     };
+#if SGS_PHASE_PROBE
     unsigned long long pst[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // probe: stamps inside one phase (a.trace only)
+#endif
     // One phase.  On entry `A` / `B` hold the W fragments of tiles 0 / 1 of the current stage (read at the END of the previous phase, behind
     // its last tile's MFMAs); fragments of tile t + 2 are read behind the MFMAs of tile t.  Before the LAST tile: the DMA of the next stage
     // is retired, one barrier publishes it (and says every wave is through reading the stage after next's victim), and the next phase's
@@ -2288,23 +2289,21 @@ int launch_score(const ScoreArgs& a, hipStream_t stream) {
     const dim3 grid(static_cast<unsigned>(cdiv(a.n, kBM))), blk(kT);
     const size_t sm = score_smem_bytes(NT);
     // 2 stages x (16 KiB W + 4 KiB features) at H = 256: 41 KiB per workgroup, three per CU
-    // (an EXACT specialisation that folds the bounds checks makes hipcc 7.2 spill ~200 VGPRs at this
-    //  register budget; the generic variant allocates 151 VGPRs, no scratch, 3 waves/SIMD.)
-    const bool exact = false;
-#define SGS_SCORE_CASE(NT_, EX_)                                                                                   \
+    // (no specialisation for H == 32 * NT: folding the bounds checks made hipcc 7.2 spill ~200 VGPRs; this one has 151, no scratch, 3 waves/SIMD)
+#define SGS_SCORE_CASE(NT_)                                                                                        \
     do {                                                                                                            \
         static bool raised = false;                                                                                 \
         if (!raised) {                                                                                              \
-            SGS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&edge_score_kernel<NT_, BWD, EX_, EPD>),   \
+            SGS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&edge_score_kernel<NT_, BWD, EPD>),        \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));      \
             raised = true;                                                                                          \
         }                                                                                                           \
-        hipLaunchKernelGGL((edge_score_kernel<NT_, BWD, EX_, EPD>), grid, blk, sm, stream, a);                      \
+        hipLaunchKernelGGL((edge_score_kernel<NT_, BWD, EPD>), grid, blk, sm, stream, a);                           \
     } while (0)
     switch (NT) {
-        case 2: if (exact) SGS_SCORE_CASE(2, true); else SGS_SCORE_CASE(2, false); break;
-        case 4: if (exact) SGS_SCORE_CASE(4, true); else SGS_SCORE_CASE(4, false); break;
-        default: if (exact) SGS_SCORE_CASE(8, true); else SGS_SCORE_CASE(8, false); break;
+        case 2: SGS_SCORE_CASE(2); break;
+        case 4: SGS_SCORE_CASE(4); break;
+        default: SGS_SCORE_CASE(8); break;
     }
 #undef SGS_SCORE_CASE
     SGS_LAUNCH_OK();
@@ -2346,21 +2345,93 @@ static void bf16x6_launch_knobs(ScoreArgs& a, int mode, int64_t H, int P = 3) {
     a.trace = g_probe_trace;
 }
 
+// The bf16x6 loop: 4 waves x 32 rows per workgroup, two workgroups per CU.  The one place that names its instantiations (DESIGN.md has the
+// (MODE, P) table).  dyn_lds: the probe's pad at H = 256 (prio bit 6: ONE workgroup fits a CU).
+template <int MODE, int P>
+static int launch_bf16x6(ScoreArgs& a, const uint4* Wp16, int64_t rows, int64_t H, hipStream_t stream, size_t dyn_lds = 0) {
+    bf16x6_launch_knobs(a, MODE, H, P);
+    const dim3 grid(static_cast<unsigned>(cdiv(rows, 128))), blk(256);
+    if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, MODE, P>), grid, blk, dyn_lds, stream, a, Wp16);
+    else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, MODE, P>), grid, blk, 0, stream, a, Wp16);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+// The fields every scorer kernel over an edge list reads.  The caller adds its own: outputs, canon / mate, dyn_n (forwards only), epd.
+static void score_args(ScoreArgs& a, const float* codes, const float* U, const int64_t* edge_index, int64_t E, const int64_t* active, int64_t n,
+                       int64_t edge_id_offset, int64_t H, const float* WaT, const float* b1, const float* w2, const float* b2, float p_drop,
+                       uint64_t seed, uint32_t site) {
+    a.codes = codes; a.U = U; a.src = edge_index; a.dst = edge_index + E; a.active = active; a.n = n; a.row_offset = edge_id_offset;
+    a.H = static_cast<int>(H); a.WaT = WaT; a.b1 = b1; a.w2 = w2; a.b2 = b2;
+    a.drop_scale = 1.0f / (1.0f - p_drop); a.drop_thresh = dropout_thresh(p_drop); a.seed = seed; a.epoch = epoch_ptr(); a.site = site;
+    a.use_drop = p_drop > 0.f;
+}
+
+// The scorer's workspace: five regions in this order, each rounded up to 256 B.  Callers carve with the (N, E) they told
+// sgs_edge_score_workspace_bytes -- the forward (N, E), the backward core (N, 0), the dfeat forms (0, 0) -- so Wp16 sits at a different
+// offset in each; the prep_sd_pack -> dfeat_fused_packed hand-over works because both carve with (0, 0).
+struct ScoreWs {
+    float* WaT;            // [H][H] W1a^T, or the streaming kernels' packed W1a
+    float* Ceo;            // [N][H] the streaming kernels' packed codes
+    float* zpart;          // [2][E] the persistent kernel's fc2 partials
+    unsigned int* ctr;     // [64] its tile counter
+    uint4* Wp16;           // the bf16 pieces of W1a (6 B per entry used, 8 reserved)
+    size_t end;            // bytes carved
+};
+static ScoreWs carve_score_ws(void* ws, int64_t N, int64_t H, int64_t E) {
+    Carver cv(ws);
+    ScoreWs w;
+    w.WaT = cv.take<float>(static_cast<size_t>(H) * H);
+    w.Ceo = cv.take<float>(static_cast<size_t>(N) * H);
+    w.zpart = cv.take<float>(2 * static_cast<size_t>(E));
+    w.ctr = cv.take<unsigned int>(64);
+    w.Wp16 = reinterpret_cast<uint4*>(cv.take<uint64_t>(static_cast<size_t>(H) * H));
+    w.end = cv.off;
+    return w;
+}
+// the operand of the dfeat forms (MODE 2 / 4 / 5), at a fixed place of their workspace: sgs_edge_score_workspace_bytes(0, H, 0)
+static uint4* fused_wp16(void* ws, int64_t H) { return carve_score_ws(ws, 0, H, 0).Wp16; }
+
+static void launch_transpose_w1a(const float* W1, int64_t H, float* WaT, hipStream_t stream) {
+    hipLaunchKernelGGL(transpose_w1a, dim3(cdiv(H, 32), cdiv(H, 32)), dim3(kT), 0, stream, W1, static_cast<int>(H), WaT);
+}
+
+// the streaming kernels' operands: W1a and the codes, packed by one launch
+static void launch_pack_stream(const float* W1, int64_t H, float* WaT, const float* codes, int64_t N, float* Ceo, hipStream_t stream) {
+    const int n_w = static_cast<int>(cdiv(H * H, kT));
+    hipLaunchKernelGGL(pack_stream_operands, dim3(static_cast<unsigned>(n_w + cdiv(N * H, kT))), dim3(kT), 0, stream, W1, static_cast<int>(H), WaT,
+                       n_w, codes, N, Ceo);
+}
+
+// the bf16x6 loop's operand: W1a (TRANSPOSED: diag(rowscale * scale) W1a as the row GEMM's matrix) in P bf16 pieces
+template <bool TRANSPOSED>
+static void launch_pack_w1a(int P, const float* W1, int64_t H, uint4* Wp16, hipStream_t stream, const float* rowscale = nullptr, float scale = 1.f) {
+    const dim3 grid(static_cast<unsigned>(cdiv(pack_w1a_threads(H), kT)));
+    if (P == 1) hipLaunchKernelGGL((pack_w1a_bf16x3<TRANSPOSED, 1>), grid, dim3(kT), 0, stream, W1, static_cast<int>(H), Wp16, rowscale, scale);
+    else        hipLaunchKernelGGL((pack_w1a_bf16x3<TRANSPOSED, 3>), grid, dim3(kT), 0, stream, W1, static_cast<int>(H), Wp16, rowscale, scale);
+}
+
+// row-block reductions (one workgroup per node; `grid`, `nnz`, `N`, `stream` of the caller): 16 waves once a row averages 64 entries, else 4
+#define SGS_LAUNCH_ROWBLOCK(K16_, K4_, ...)                                                    \
+    do {                                                                                       \
+        if (nnz >= 64 * N) hipLaunchKernelGGL(K16_, grid, dim3(1024), 0, stream, __VA_ARGS__); \
+        else               hipLaunchKernelGGL(K4_, grid, dim3(256), 0, stream, __VA_ARGS__);   \
+    } while (0)
+
 extern "C" {
 
 size_t sgs_edge_score_workspace_bytes(int64_t N, int64_t H, int64_t E) {
-    if (N < 0) N = 0;
-    if (H < 0) H = 0;
-    if (E < 0) E = 0;
-    return carve_bytes(static_cast<size_t>(H) * H, 4) + carve_bytes(static_cast<size_t>(N) * H, 4) + carve_bytes(2 * static_cast<size_t>(E), 4) +
-           carve_bytes(64, 4) + carve_bytes(static_cast<size_t>(H) * H, 8) + 256;
+    return carve_score_ws(nullptr, N < 0 ? 0 : N, H < 0 ? 0 : H, E < 0 ? 0 : E).end + 256;
 }
 
-// 0 = LDS-tiled kernel, 1 = register-streaming kernel, 2 = weight-stationary persistent kernel (forward, H % 64 == 0).
-// A/B switch for benchmarks.  Measured (MI355X, E = 351 194, H = 256, same process): 0 -> 95, 1 -> 100.7, 2 -> 99.5 TFLOP/s;
-// whole-step throughput is equal within noise, so the fastest kernel is the default.
-static int g_bwd_variant = -1;     // -1: automatic (4 at H % 128 == 0 and >= 65 536 active rows, else 0); 0: LDS-tiled core; 3: 64-edge streaming core (A/B: slower); 4: bf16x6 loop
-static int g_score_variant = -1;   // -1: automatic (when the launch fills the chip with 128-edge workgroups: 4 if H % 128 == 0, else 3; otherwise 1)
+// Forward kernel (sgs_edge_score_fwd at H <= 256): -1 = automatic (when the launch fills the chip with 128-edge workgroups: 4 if
+// H % 128 == 0, else 3; otherwise 1), 0 = LDS-tiled, 1 = register-streaming (32-edge wave tile), 2 = weight-stationary persistent
+// (H % 64 == 0), 3 = register-streaming with a 64-edge wave tile (H % 64 == 0), 4 = the bf16x6 loop (H % 128 == 0, else 3).  A/B switch for
+// benchmarks.  Measured (MI355X, E = 351 194, H = 256, same process): 0 -> 95, 1 -> 100.7, 2 -> 99.5 TFLOP/s; 3 and 4: see their kernels.
+static int g_score_variant = -1;
+// Backward core (sgs_edge_score_bwd_core at H <= 256; the bits form is always 4): -1 = automatic (4 at H % 128 == 0 and >= 65 536 active
+// rows, else 0), 0 = LDS-tiled core, 3 = 64-edge streaming core (A/B: slower), 4 = the bf16x6 loop; other values run the LDS-tiled core.
+static int g_bwd_variant = -1;
 void sgs_edge_score_set_variant(int v) { g_score_variant = v; }
 void sgs_edge_score_set_bwd_variant(int v) { g_bwd_variant = v; }
 int sgs_edge_score_get_variant(void) { return g_score_variant; }
@@ -2375,34 +2446,27 @@ int sgs_edge_score_fwd(const float* codes, const float* U, int64_t N, int64_t H,
     if (E == 0) return SGS_OK;
     SGS_REQUIRE(codes && U && edge_index && W1 && b1 && w2 && b2 && p_out, SGS_EINVAL, "sgs_edge_score_fwd: null pointer");
     SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(N, H, E), SGS_EWORKSPACE, "sgs_edge_score_fwd: workspace too small");
-    Carver cv(ws);
-    float* WaT = cv.take<float>(static_cast<size_t>(H) * H);
-    float* Ceo = cv.take<float>(static_cast<size_t>(N) * H);
+    const ScoreWs w = carve_score_ws(ws, N, H, E);
+    float* const WaT = w.WaT;
+    float* const Ceo = w.Ceo;
     ScoreArgs a{};
-    a.codes = codes; a.U = U; a.src = edge_index; a.dst = edge_index + E; a.active = nullptr; a.n = E; a.H = static_cast<int>(H);
-    a.row_offset = edge_id_offset;
-    a.WaT = WaT; a.b1 = b1; a.w2 = w2; a.b2 = b2;
-    a.drop_scale = 1.0f / (1.0f - p_drop); a.drop_thresh = dropout_thresh(p_drop); a.seed = seed; a.epoch = epoch_ptr(); a.site = site;
-    a.use_drop = p_drop > 0.f; a.p_out = p_out;
+    score_args(a, codes, U, edge_index, E, nullptr, E, edge_id_offset, H, WaT, b1, w2, b2, p_drop, seed, site);
+    a.p_out = p_out;
     a.dyn_n = dyn_edges_ptr();
     if (H > 256) {                                 // wide H: the chunked kernel (the variant switch selects among the H <= 256 kernels only)
         SGS_REQUIRE(N > 0, SGS_EINVAL, "sgs_edge_score_fwd: edges without nodes");
-        hipLaunchKernelGGL(transpose_w1a, dim3(cdiv(H, 32), cdiv(H, 32)), dim3(kT), 0, stream, W1, static_cast<int>(H), WaT);
+        launch_transpose_w1a(W1, H, WaT, stream);
         return launch_score_wide<false, false>(a, stream);
     }
     int variant = g_score_variant;
     if (variant < 0) variant = (cdiv(E, kBM2) >= 512) ? (H % 128 == 0 ? 4 : 3) : 1;          // 512 = 2 resident workgroups x 256 CUs
     if (variant == 2 && a.dyn_n) variant = 3;      // the persistent kernel's tile queue is sized on the host
     if (variant == 2 && H % 64 == 0 && N > 0) {
-        float* zpart = cv.take<float>(2 * static_cast<size_t>(E));
-        unsigned int* ctr = cv.take<unsigned int>(64);
+        float* const zpart = w.zpart;
+        unsigned int* const ctr = w.ctr;
         if (int rc = zero_async(ctr, 256, stream)) return rc;
-        {
-            const int n_w = static_cast<int>(cdiv(H * H, kT));
-            hipLaunchKernelGGL(pack_stream_operands, dim3(static_cast<unsigned>(n_w + cdiv(N * H, kT))), dim3(kT), 0, stream, W1,
-                               static_cast<int>(H), WaT, n_w, codes, N, Ceo);
-        }
-        constexpr int TH = 768;                                             // 12 waves = 3 per SIMD (168-register budget; 16 waves spill)
+        launch_pack_stream(W1, H, WaT, codes, N, Ceo, stream);
+        constexpr int TH = 768;                                            // 12 waves = 3 per SIMD (168-register budget; 16 waves spill)
         const size_t sm = static_cast<size_t>(H / 2) * H * 4;             // this half of W1a, packed
         const int64_t n_tiles = cdiv(E, 32);
         int64_t nwg = 256;                                                // persistent: one workgroup per CU (128 per hidden half)
@@ -2426,25 +2490,12 @@ int sgs_edge_score_fwd(const float* codes, const float* U, int64_t N, int64_t H,
         return SGS_OK;
     }
     if (variant == 4 && H % 128 == 0 && N > 0) {
-        cv.take<float>(2 * static_cast<size_t>(E));
-        cv.take<unsigned int>(64);
-        uint4* Wp16 = cv.take<uint4>(static_cast<size_t>(H) * H * 6 / 16);
-        hipLaunchKernelGGL(pack_w1a_bf16x3<false>, dim3(static_cast<unsigned>(cdiv((H / 16) * (H / 32) * 64, kT))), dim3(kT), 0, stream, W1,
-                           static_cast<int>(H), Wp16);
-        const dim3 grid(static_cast<unsigned>(cdiv(E, 128))), blk(256);       // 4 waves x 32 edges; two workgroups per CU
-        bf16x6_launch_knobs(a, 0, H);
-        if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4>), grid, blk, 0, stream, a, Wp16);
-        else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4>), grid, blk, 0, stream, a, Wp16);
-        SGS_LAUNCH_OK();
-        return SGS_OK;
+        launch_pack_w1a<false>(3, W1, H, w.Wp16, stream);
+        return launch_bf16x6<0, 3>(a, w.Wp16, E, H, stream);
     }
     if (variant == 4) variant = 3;
     if (variant == 3 && H % 64 == 0 && N > 0) {
-        {
-            const int n_w = static_cast<int>(cdiv(H * H, kT));
-            hipLaunchKernelGGL(pack_stream_operands, dim3(static_cast<unsigned>(n_w + cdiv(N * H, kT))), dim3(kT), 0, stream, W1,
-                               static_cast<int>(H), WaT, n_w, codes, N, Ceo);
-        }
+        launch_pack_stream(W1, H, WaT, codes, N, Ceo, stream);
         const dim3 grid(static_cast<unsigned>(cdiv(E, kBM2))), blk(kT);
         if (H == 256)      hipLaunchKernelGGL((edge_score_stream64_kernel<8, false>), grid, blk, 0, stream, a, WaT, Ceo);
         else if (H == 128) hipLaunchKernelGGL((edge_score_stream64_kernel<4, false>), grid, blk, 0, stream, a, WaT, Ceo);
@@ -2453,11 +2504,7 @@ int sgs_edge_score_fwd(const float* codes, const float* U, int64_t N, int64_t H,
         return SGS_OK;
     }
     if (variant == 1 && H % 64 == 0 && N > 0) {
-        {
-            const int n_w = static_cast<int>(cdiv(H * H, kT));
-            hipLaunchKernelGGL(pack_stream_operands, dim3(static_cast<unsigned>(n_w + cdiv(N * H, kT))), dim3(kT), 0, stream, W1,
-                               static_cast<int>(H), WaT, n_w, codes, N, Ceo);
-        }
+        launch_pack_stream(W1, H, WaT, codes, N, Ceo, stream);
         const dim3 grid(static_cast<unsigned>(cdiv(E, kBM))), blk(kT);
         if (H == 256)      hipLaunchKernelGGL((edge_score_stream_kernel<8>), grid, blk, 0, stream, a, WaT, Ceo);
         else if (H == 128) hipLaunchKernelGGL((edge_score_stream_kernel<4>), grid, blk, 0, stream, a, WaT, Ceo);
@@ -2465,7 +2512,7 @@ int sgs_edge_score_fwd(const float* codes, const float* U, int64_t N, int64_t H,
         SGS_LAUNCH_OK();
         return SGS_OK;
     }
-    hipLaunchKernelGGL(transpose_w1a, dim3(cdiv(H, 32), cdiv(H, 32)), dim3(kT), 0, stream, W1, static_cast<int>(H), WaT);
+    launch_transpose_w1a(W1, H, WaT, stream);
     return launch_score<false>(a, stream);
 }
 
@@ -2484,53 +2531,22 @@ static int fwd_paired_wide(const float* codes, const float* U, int64_t N, int64_
     if (E == 0 || M == 0) return SGS_OK;
     SGS_REQUIRE(codes && U && edge_index && W1 && b1 && w2 && b2 && p_out && N > 0, SGS_EINVAL, "sgs_edge_score_fwd_paired: null pointer");
     SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(N, H, E), SGS_EWORKSPACE, "sgs_edge_score_fwd_paired: workspace too small");
-    Carver cv(ws);
-    float* WaT = cv.take<float>(static_cast<size_t>(H) * H);
+    float* const WaT = carve_score_ws(ws, N, H, E).WaT;
     ScoreArgs a{};
-    a.codes = codes; a.U = U; a.src = edge_index; a.dst = edge_index + E; a.active = nullptr; a.n = M; a.H = static_cast<int>(H);
-    a.row_offset = edge_id_offset;
-    a.WaT = WaT; a.b1 = b1; a.w2 = w2; a.b2 = b2;
-    a.drop_scale = 1.0f / (1.0f - p_drop); a.drop_thresh = dropout_thresh(p_drop); a.seed = seed; a.epoch = epoch_ptr(); a.site = site;
-    a.use_drop = p_drop > 0.f; a.p_out = p_out;
+    score_args(a, codes, U, edge_index, E, nullptr, M, edge_id_offset, H, WaT, b1, w2, b2, p_drop, seed, site);
+    a.p_out = p_out;
     a.canon = canon; a.mate = mate;
     a.dyn_n = dyn_edges_ptr() ? dyn_edges_ptr() + 1 : nullptr;   // word 1 of the registered dims: the live number of canonical edges
-    hipLaunchKernelGGL(transpose_w1a, dim3(cdiv(H, 32), cdiv(H, 32)), dim3(kT), 0, stream, W1, static_cast<int>(H), WaT);
+    launch_transpose_w1a(W1, H, WaT, stream);
     return launch_score_wide<false, false, true>(a, stream);
 }
 
-static int fwd_bf16x6_impl(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
+// The three bf16x6 forward forms in P pieces (3: fp32-faithful, 1: the bf16 mode): paired when canon / mate are given, every edge otherwise;
+// with maskbits also the ReLU x dropout mask.  Every error is reported under the paired entry point's name.
+static int fwd_bf16x6_impl(int P, const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
                            int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
                            const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, uint32_t* maskbits,
-                           void* ws, size_t ws_bytes, sgs_stream_t stream_, int P = 3);
-
-int sgs_edge_score_fwd_paired(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
-                              int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
-                              const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, void* ws,
-                              size_t ws_bytes, sgs_stream_t stream_) {
-    SGS_REQUIRE((canon && mate) || E == 0 || M == 0, SGS_EINVAL, "sgs_edge_score_fwd_paired: null pointer");
-    if (H > 256) return fwd_paired_wide(codes, U, N, H, edge_index, E, edge_id_offset, canon, M, mate, W1, b1, w2, b2, p_drop, seed, site, p_out, ws,
-                                        ws_bytes, static_cast<hipStream_t>(stream_));
-    return fwd_bf16x6_impl(codes, U, N, H, edge_index, E, edge_id_offset, canon, M, mate, W1, b1, w2, b2, p_drop, seed, site, p_out, nullptr, ws,
-                           ws_bytes, stream_);
-}
-
-/* The bf16x6 forward (paired when canon / mate are given, every edge otherwise) that also writes the ReLU x dropout MASK of every scored
- * edge: maskbits [E, H/32], bit h of edge e in word h / 32 of row e.  With the mask and p the backward needs no recompute for dz and dv
- * (sgs_edge_score_bwd_prep); the scores are the plain forward's bit for bit. */
-int sgs_edge_score_fwd_mask(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
-                            int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
-                            const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, uint32_t* maskbits,
-                            void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    SGS_REQUIRE(maskbits || E == 0, SGS_EINVAL, "sgs_edge_score_fwd_mask: null pointer");
-    SGS_REQUIRE((canon != nullptr) == (mate != nullptr), SGS_EINVAL, "sgs_edge_score_fwd_mask: canon and mate come together");
-    return fwd_bf16x6_impl(codes, U, N, H, edge_index, E, edge_id_offset, canon, canon ? M : E, mate, W1, b1, w2, b2, p_drop, seed, site, p_out,
-                           maskbits, ws, ws_bytes, stream_);
-}
-
-static int fwd_bf16x6_impl(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
-                           int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
-                           const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, uint32_t* maskbits,
-                           void* ws, size_t ws_bytes, sgs_stream_t stream_, int P) {
+                           void* ws, size_t ws_bytes, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (int rc = check_common("sgs_edge_score_fwd_paired", N, H, E, p_drop)) return rc;
     SGS_REQUIRE(H == 128 || H == 256, SGS_EINVAL, "sgs_edge_score_fwd_paired: H must be 128 or 256");   // the bf16x6 loop (wide H: fwd_paired_wide)
@@ -2538,53 +2554,60 @@ static int fwd_bf16x6_impl(const float* codes, const float* U, int64_t N, int64_
     if (E == 0 || M == 0) return SGS_OK;
     SGS_REQUIRE(codes && U && edge_index && W1 && b1 && w2 && b2 && p_out && N > 0, SGS_EINVAL, "sgs_edge_score_fwd_paired: null pointer");
     SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(N, H, E), SGS_EWORKSPACE, "sgs_edge_score_fwd_paired: workspace too small");
-    Carver cv(ws);
-    cv.take<float>(static_cast<size_t>(H) * H);
-    cv.take<float>(static_cast<size_t>(N) * H);
-    cv.take<float>(2 * static_cast<size_t>(E));
-    cv.take<unsigned int>(64);
-    uint4* Wp16 = cv.take<uint4>(static_cast<size_t>(H) * H * 6 / 16);
+    uint4* const Wp16 = carve_score_ws(ws, N, H, E).Wp16;
     ScoreArgs a{};
-    a.codes = codes; a.U = U; a.src = edge_index; a.dst = edge_index + E; a.active = nullptr; a.n = M; a.H = static_cast<int>(H);
-    a.row_offset = edge_id_offset;
-    a.b1 = b1; a.w2 = w2; a.b2 = b2;
-    a.drop_scale = 1.0f / (1.0f - p_drop); a.drop_thresh = dropout_thresh(p_drop); a.seed = seed; a.epoch = epoch_ptr(); a.site = site;
-    a.use_drop = p_drop > 0.f; a.p_out = p_out; a.dvbits = maskbits;
+    score_args(a, codes, U, edge_index, E, nullptr, M, edge_id_offset, H, nullptr, b1, w2, b2, p_drop, seed, site);
+    a.p_out = p_out; a.dvbits = maskbits;
     a.canon = canon; a.mate = mate;
-    const dim3 grid(static_cast<unsigned>(cdiv(M, 128))), blk(256);
-    if (P == 1) {                                                    // the bf16 mode: one piece, one product per tile
-        hipLaunchKernelGGL((pack_w1a_bf16x3<false, 1>), dim3(static_cast<unsigned>(cdiv(pack_w1a_threads(H), kT))), dim3(kT), 0, stream, W1,
-                           static_cast<int>(H), Wp16, nullptr, 1.f);
-        if (canon) {
-            a.dyn_n = dyn_edges_ptr() ? dyn_edges_ptr() + 1 : nullptr;
-            bf16x6_launch_knobs(a, 3, H, 1);
-            if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 3, 1>), grid, blk, 0, stream, a, Wp16);
-            else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 3, 1>), grid, blk, 0, stream, a, Wp16);
-        } else {
-            a.dyn_n = dyn_edges_ptr();
-            bf16x6_launch_knobs(a, 0, H, 1);
-            if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 0, 1>), grid, blk, 0, stream, a, Wp16);
-            else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 0, 1>), grid, blk, 0, stream, a, Wp16);
-        }
-        SGS_LAUNCH_OK();
-        return SGS_OK;
-    }
-    hipLaunchKernelGGL(pack_w1a_bf16x3<false>, dim3(static_cast<unsigned>(cdiv((H / 16) * (H / 32) * 64, kT))), dim3(kT), 0, stream, W1,
-                       static_cast<int>(H), Wp16);
+    launch_pack_w1a<false>(P, W1, H, Wp16, stream);
     if (canon) {
         a.dyn_n = dyn_edges_ptr() ? dyn_edges_ptr() + 1 : nullptr;   // word 1 of the registered dims: the live number of canonical edges
-        bf16x6_launch_knobs(a, 3, H);
         // (probe: prio bit 6 pads the launch with dynamic LDS so that ONE workgroup fits a CU)
-        if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 3>), grid, blk, (a.prio & 64) ? 40960 : 0, stream, a, Wp16);
-        else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 3>), grid, blk, 0, stream, a, Wp16);
-    } else {                                                         // every edge runs the contraction (no mates: a directed edge list)
-        a.dyn_n = dyn_edges_ptr();
-        bf16x6_launch_knobs(a, 0, H);
-        if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4>), grid, blk, 0, stream, a, Wp16);
-        else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4>), grid, blk, 0, stream, a, Wp16);
+        return P == 1 ? launch_bf16x6<3, 1>(a, Wp16, M, H, stream) : launch_bf16x6<3, 3>(a, Wp16, M, H, stream, (g_probe_prio & 64) ? 40960 : 0);
     }
-    SGS_LAUNCH_OK();
-    return SGS_OK;
+    a.dyn_n = dyn_edges_ptr();                                       // every edge runs the contraction (no mates: a directed edge list)
+    return P == 1 ? launch_bf16x6<0, 1>(a, Wp16, M, H, stream) : launch_bf16x6<0, 3>(a, Wp16, M, H, stream);
+}
+
+static int fwd_paired_impl(const char* who, int P, const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
+                           int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
+                           const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, void* ws,
+                           size_t ws_bytes, sgs_stream_t stream_) {
+    SGS_REQUIRE((canon && mate) || E == 0 || M == 0, SGS_EINVAL, "%s: null pointer", who);
+    if (P == 3 && H > 256)                                           // (the bf16 mode has no wide form)
+        return fwd_paired_wide(codes, U, N, H, edge_index, E, edge_id_offset, canon, M, mate, W1, b1, w2, b2, p_drop, seed, site, p_out, ws, ws_bytes,
+                               static_cast<hipStream_t>(stream_));
+    return fwd_bf16x6_impl(P, codes, U, N, H, edge_index, E, edge_id_offset, canon, M, mate, W1, b1, w2, b2, p_drop, seed, site, p_out, nullptr, ws,
+                           ws_bytes, stream_);
+}
+
+int sgs_edge_score_fwd_paired(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
+                              int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
+                              const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, void* ws,
+                              size_t ws_bytes, sgs_stream_t stream_) {
+    return fwd_paired_impl("sgs_edge_score_fwd_paired", 3, codes, U, N, H, edge_index, E, edge_id_offset, canon, M, mate, W1, b1, w2, b2, p_drop, seed,
+                           site, p_out, ws, ws_bytes, stream_);
+}
+
+/* The bf16x6 forward (paired when canon / mate are given, every edge otherwise) that also writes the ReLU x dropout MASK of every scored
+ * edge: maskbits [E, H/32], bit h of edge e in word h / 32 of row e.  With the mask and p the backward needs no recompute for dz and dv
+ * (sgs_edge_score_bwd_prep); the scores are the plain forward's bit for bit. */
+static int fwd_mask_impl(const char* who, int P, const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
+                         int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
+                         const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, uint32_t* maskbits,
+                         void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    SGS_REQUIRE(maskbits || E == 0, SGS_EINVAL, "%s: null pointer", who);
+    SGS_REQUIRE((canon != nullptr) == (mate != nullptr), SGS_EINVAL, "%s: canon and mate come together", who);
+    return fwd_bf16x6_impl(P, codes, U, N, H, edge_index, E, edge_id_offset, canon, canon ? M : E, mate, W1, b1, w2, b2, p_drop, seed, site, p_out,
+                           maskbits, ws, ws_bytes, stream_);
+}
+
+int sgs_edge_score_fwd_mask(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
+                            int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
+                            const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, uint32_t* maskbits,
+                            void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    return fwd_mask_impl("sgs_edge_score_fwd_mask", 3, codes, U, N, H, edge_index, E, edge_id_offset, canon, M, mate, W1, b1, w2, b2, p_drop, seed, site,
+                         p_out, maskbits, ws, ws_bytes, stream_);
 }
 
 /* ---- the bf16 mode (sgs_hip.h, "bf16 mode"): every fp32 product of the three forward forms and of the two mask-form dfeat contractions is
@@ -2595,27 +2618,24 @@ int sgs_edge_score_fwd_bf16(const float* codes, const float* U, int64_t N, int64
                             int64_t edge_id_offset, const float* W1, const float* b1, const float* w2, const float* b2, float p_drop,
                             uint64_t seed, uint32_t site, float* p_out, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
     SGS_REQUIRE(sgs_edge_score_bf16_supported(H), SGS_EINVAL, "sgs_edge_score_fwd_bf16: H=%lld unsupported (128 or 256)", (long long)H);
-    return fwd_bf16x6_impl(codes, U, N, H, edge_index, E, edge_id_offset, nullptr, E, nullptr, W1, b1, w2, b2, p_drop, seed, site, p_out, nullptr,
-                           ws, ws_bytes, stream_, 1);
+    return fwd_bf16x6_impl(1, codes, U, N, H, edge_index, E, edge_id_offset, nullptr, E, nullptr, W1, b1, w2, b2, p_drop, seed, site, p_out, nullptr,
+                           ws, ws_bytes, stream_);
 }
 
 int sgs_edge_score_fwd_paired_bf16(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
                                    int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
                                    const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, void* ws,
                                    size_t ws_bytes, sgs_stream_t stream_) {
-    SGS_REQUIRE((canon && mate) || E == 0 || M == 0, SGS_EINVAL, "sgs_edge_score_fwd_paired_bf16: null pointer");
-    return fwd_bf16x6_impl(codes, U, N, H, edge_index, E, edge_id_offset, canon, M, mate, W1, b1, w2, b2, p_drop, seed, site, p_out, nullptr, ws,
-                           ws_bytes, stream_, 1);
+    return fwd_paired_impl("sgs_edge_score_fwd_paired_bf16", 1, codes, U, N, H, edge_index, E, edge_id_offset, canon, M, mate, W1, b1, w2, b2, p_drop,
+                           seed, site, p_out, ws, ws_bytes, stream_);
 }
 
 int sgs_edge_score_fwd_mask_bf16(const float* codes, const float* U, int64_t N, int64_t H, const int64_t* edge_index, int64_t E,
                                  int64_t edge_id_offset, const int32_t* canon, int64_t M, const int32_t* mate, const float* W1, const float* b1,
                                  const float* w2, const float* b2, float p_drop, uint64_t seed, uint32_t site, float* p_out, uint32_t* maskbits,
                                  void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    SGS_REQUIRE(maskbits || E == 0, SGS_EINVAL, "sgs_edge_score_fwd_mask_bf16: null pointer");
-    SGS_REQUIRE((canon != nullptr) == (mate != nullptr), SGS_EINVAL, "sgs_edge_score_fwd_mask_bf16: canon and mate come together");
-    return fwd_bf16x6_impl(codes, U, N, H, edge_index, E, edge_id_offset, canon, canon ? M : E, mate, W1, b1, w2, b2, p_drop, seed, site, p_out,
-                           maskbits, ws, ws_bytes, stream_, 1);
+    return fwd_mask_impl("sgs_edge_score_fwd_mask_bf16", 1, codes, U, N, H, edge_index, E, edge_id_offset, canon, M, mate, W1, b1, w2, b2, p_drop, seed,
+                         site, p_out, maskbits, ws, ws_bytes, stream_);
 }
 
 /* Backward core over the active rows: recomputes the hidden layer and writes
@@ -2667,18 +2687,13 @@ static int bwd_core_impl(const float* codes, const float* U, int64_t N, int64_t 
     SGS_REQUIRE(codes && U && edge_index && grad_p && W1 && b1 && w2 && b2 && (dv || dvbits) && hdz_part && dz && feat, SGS_EINVAL,
                 "sgs_edge_score_bwd_core: null pointer");
     SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(N, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_core: workspace too small");
-    Carver cv(ws);
-    float* WaT = cv.take<float>(static_cast<size_t>(H) * H);
-    float* Ceo = cv.take<float>(static_cast<size_t>(N) * H);
+    const ScoreWs w = carve_score_ws(ws, N, H, 0);
+    ScoreArgs a{};                     // (dyn_n stays null: the active count is the host's)
+    score_args(a, codes, U, edge_index, E, active_eid, n_active, edge_id_offset, H, w.WaT, b1, w2, b2, p_drop, seed, site);
+    a.gp = grad_p; a.dv = dv; a.hdz = hdz_part; a.dz = dz; a.feat = feat;
     if (H > 256) {                     // wide H: the chunked core (the variant switch selects among the H <= 256 kernels only)
         SGS_REQUIRE(dv && !dvbits && N > 0, SGS_EINVAL, "sgs_edge_score_bwd_core: H=%lld needs the dense dv form", (long long)H);
-        hipLaunchKernelGGL(transpose_w1a, dim3(cdiv(H, 32), cdiv(H, 32)), dim3(kT), 0, stream, W1, static_cast<int>(H), WaT);
-        ScoreArgs a{};
-        a.codes = codes; a.U = U; a.src = edge_index; a.dst = edge_index + E; a.active = active_eid; a.n = n_active;
-        a.row_offset = edge_id_offset;
-        a.H = static_cast<int>(H); a.WaT = WaT; a.b1 = b1; a.w2 = w2; a.b2 = b2;
-        a.drop_scale = 1.0f / (1.0f - p_drop); a.drop_thresh = dropout_thresh(p_drop); a.seed = seed; a.epoch = epoch_ptr(); a.site = site;
-        a.use_drop = p_drop > 0.f; a.gp = grad_p; a.dv = dv; a.hdz = hdz_part; a.dz = dz; a.feat = feat;
+        launch_transpose_w1a(W1, H, w.WaT, stream);
         return launch_score_wide<true, false>(a, stream);
     }
     // The 64-edge streaming loop is available for the backward core too (variant 3), but it is NOT the default: measured
@@ -2690,46 +2705,20 @@ static int bwd_core_impl(const float* codes, const float* U, int64_t N, int64_t 
     const int bwd_variant = dvbits ? 4 : (g_bwd_variant >= 0 ? g_bwd_variant : ((H % 128 == 0 && cdiv(n_active, 128) >= 512) ? 4 : 0));
     if (bwd_variant == 4 && H % 128 == 0 && N > 0) {
         // the recompute on the bf16x6 loop (forward variant 4): same outputs
-        cv.take<float>(0);
-        cv.take<unsigned int>(64);
-        uint4* Wp16 = cv.take<uint4>(static_cast<size_t>(H) * H * 6 / 16);
-        hipLaunchKernelGGL(pack_w1a_bf16x3<false>, dim3(static_cast<unsigned>(cdiv((H / 16) * (H / 32) * 64, kT))), dim3(kT), 0, stream, W1,
-                           static_cast<int>(H), Wp16);
-        ScoreArgs b{};
-        b.codes = codes; b.U = U; b.src = edge_index; b.dst = edge_index + E; b.active = active_eid; b.n = n_active;
-        b.row_offset = edge_id_offset;
-        b.H = static_cast<int>(H); b.WaT = nullptr; b.b1 = b1; b.w2 = w2; b.b2 = b2;
-        b.drop_scale = 1.0f / (1.0f - p_drop); b.drop_thresh = dropout_thresh(p_drop); b.seed = seed; b.epoch = epoch_ptr(); b.site = site;
-        b.use_drop = p_drop > 0.f; b.gp = grad_p; b.dv = dv; b.dvbits = dvbits; b.hdz = hdz_part; b.dz = dz; b.feat = feat;
-        const dim3 grid(static_cast<unsigned>(cdiv(n_active, 128))), blk(256);
-        bf16x6_launch_knobs(b, 1, H);
-        if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 1>), grid, blk, 0, stream, b, Wp16);
-        else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 1>), grid, blk, 0, stream, b, Wp16);
-        SGS_LAUNCH_OK();
-        return SGS_OK;
+        launch_pack_w1a<false>(3, W1, H, w.Wp16, stream);
+        a.WaT = nullptr; a.dvbits = dvbits;
+        return launch_bf16x6<1, 3>(a, w.Wp16, n_active, H, stream);
     }
-    const bool stream64 = H % 64 == 0 && bwd_variant == 3;
-    if (stream64) {
-        const int n_w = static_cast<int>(cdiv(H * H, kT));
-        hipLaunchKernelGGL(pack_stream_operands, dim3(static_cast<unsigned>(n_w + cdiv(N * H, kT))), dim3(kT), 0, stream, W1,
-                           static_cast<int>(H), WaT, n_w, codes, N, Ceo);
-    } else {
-        hipLaunchKernelGGL(transpose_w1a, dim3(cdiv(H, 32), cdiv(H, 32)), dim3(kT), 0, stream, W1, static_cast<int>(H), WaT);
-    }
-    ScoreArgs a{};
-    a.codes = codes; a.U = U; a.src = edge_index; a.dst = edge_index + E; a.active = active_eid; a.n = n_active;
-    a.row_offset = edge_id_offset;
-    a.H = static_cast<int>(H); a.WaT = WaT; a.b1 = b1; a.w2 = w2; a.b2 = b2;
-    a.drop_scale = 1.0f / (1.0f - p_drop); a.drop_thresh = dropout_thresh(p_drop); a.seed = seed; a.epoch = epoch_ptr(); a.site = site;
-    a.use_drop = p_drop > 0.f; a.gp = grad_p; a.dv = dv; a.hdz = hdz_part; a.dz = dz; a.feat = feat;
-    if (stream64) {
+    if (H % 64 == 0 && bwd_variant == 3) {
+        launch_pack_stream(W1, H, w.WaT, codes, N, w.Ceo, stream);
         const dim3 grid(static_cast<unsigned>(cdiv(n_active, kBM2))), blk(kT);
-        if (H == 256)      hipLaunchKernelGGL((edge_score_stream64_kernel<8, true>), grid, blk, 0, stream, a, WaT, Ceo);
-        else if (H == 128) hipLaunchKernelGGL((edge_score_stream64_kernel<4, true>), grid, blk, 0, stream, a, WaT, Ceo);
-        else               hipLaunchKernelGGL((edge_score_stream64_kernel<2, true>), grid, blk, 0, stream, a, WaT, Ceo);
+        if (H == 256)      hipLaunchKernelGGL((edge_score_stream64_kernel<8, true>), grid, blk, 0, stream, a, w.WaT, w.Ceo);
+        else if (H == 128) hipLaunchKernelGGL((edge_score_stream64_kernel<4, true>), grid, blk, 0, stream, a, w.WaT, w.Ceo);
+        else               hipLaunchKernelGGL((edge_score_stream64_kernel<2, true>), grid, blk, 0, stream, a, w.WaT, w.Ceo);
         SGS_LAUNCH_OK();
         return SGS_OK;
     }
+    launch_transpose_w1a(W1, H, w.WaT, stream);
     return launch_score<true>(a, stream);
 }
 
@@ -2745,73 +2734,41 @@ int sgs_edge_score_bwd_dfeat(const float* dv, int64_t n, int64_t H, const float*
     if (n == 0) return SGS_OK;
     SGS_REQUIRE(dv && W1 && dfeat, SGS_EINVAL, "sgs_edge_score_bwd_dfeat: null pointer");
     SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_dfeat: workspace too small");
-    Carver cv(ws);
-    cv.take<float>(static_cast<size_t>(H) * H);
-    cv.take<float>(0);
-    cv.take<float>(0);
-    cv.take<unsigned int>(64);
-    uint4* Wp16 = cv.take<uint4>(static_cast<size_t>(H) * H * 6 / 16);
-    hipLaunchKernelGGL(pack_w1a_bf16x3<true>, dim3(static_cast<unsigned>(cdiv((H / 16) * (H / 32) * 64, kT))), dim3(kT), 0, stream, W1,
-                       static_cast<int>(H), Wp16);
+    uint4* const Wp16 = fused_wp16(ws, H);
+    launch_pack_w1a<true>(3, W1, H, Wp16, stream);
     ScoreArgs a{};
     a.codes = dv; a.n = n; a.H = static_cast<int>(H); a.feat = dfeat;
-    const dim3 grid(static_cast<unsigned>(cdiv(n, 128))), blk(256);
-    bf16x6_launch_knobs(a, 2, H);
-    if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 2>), grid, blk, 0, stream, a, Wp16);
-    else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 2>), grid, blk, 0, stream, a, Wp16);
-    SGS_LAUNCH_OK();
-    return SGS_OK;
+    return launch_bf16x6<2, 3>(a, Wp16, n, H, stream);
 }
 
 /* dfeat [n,H] = dv . W1[:, :H] from the mask form of dv: out[r, :] = dz[r] * (bits[r, :] . diag(w2 / (1 - p)) W1a) -- the 0 / 1 operand
- * is one exact bf16 piece, the scaled matrix is split three ways: 3 MFMA products per fp32 product. */
-int sgs_edge_score_bwd_dfeat_bits(const uint32_t* dvbits, const float* dz, int64_t n, int64_t H, const float* W1, const float* w2, float p_drop,
-                                  float* dfeat, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+ * is one exact bf16 piece, the scaled matrix is split three ways (P = 3: 3 MFMA products per fp32 product) or rounded once (P = 1, the
+ * bf16 mode). */
+static int bwd_dfeat_bits_impl(const char* who, int P, int (*supported)(int64_t), const uint32_t* dvbits, const float* dz, int64_t n, int64_t H,
+                               const float* W1, const float* w2, float p_drop, float* dfeat, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(n >= 0 && H > 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_bits: bad arguments");
-    SGS_REQUIRE(sgs_edge_score_bwd_bits_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_dfeat_bits: H=%lld unsupported (128 or 256)", (long long)H);
+    SGS_REQUIRE(n >= 0 && H > 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "%s: bad arguments", who);
+    SGS_REQUIRE(supported(H), SGS_EINVAL, "%s: H=%lld unsupported (128 or 256)", who, (long long)H);
     if (n == 0) return SGS_OK;
-    SGS_REQUIRE(dvbits && dz && W1 && w2 && dfeat, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_bits: null pointer");
-    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_dfeat_bits: workspace too small");
-    Carver cv(ws);
-    cv.take<float>(static_cast<size_t>(H) * H);
-    cv.take<float>(0);
-    cv.take<float>(0);
-    cv.take<unsigned int>(64);
-    uint4* Wp16 = cv.take<uint4>(static_cast<size_t>(H) * H * 6 / 16);
-    hipLaunchKernelGGL(pack_w1a_bf16x3<true>, dim3(static_cast<unsigned>(cdiv((H / 16) * (H / 32) * 64, kT))), dim3(kT), 0, stream, W1,
-                       static_cast<int>(H), Wp16, w2, 1.0f / (1.0f - p_drop));
+    SGS_REQUIRE(dvbits && dz && W1 && w2 && dfeat, SGS_EINVAL, "%s: null pointer", who);
+    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "%s: workspace too small", who);
+    uint4* const Wp16 = fused_wp16(ws, H);
+    launch_pack_w1a<true>(P, W1, H, Wp16, stream, w2, 1.0f / (1.0f - p_drop));
     ScoreArgs a{};
     a.inbits = dvbits; a.indz = dz; a.n = n; a.H = static_cast<int>(H); a.feat = dfeat;
-    const dim3 grid(static_cast<unsigned>(cdiv(n, 128))), blk(256);
-    bf16x6_launch_knobs(a, 4, H);
-    if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 4>), grid, blk, 0, stream, a, Wp16);
-    else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 4>), grid, blk, 0, stream, a, Wp16);
-    SGS_LAUNCH_OK();
-    return SGS_OK;
+    return P == 1 ? launch_bf16x6<4, 1>(a, Wp16, n, H, stream) : launch_bf16x6<4, 3>(a, Wp16, n, H, stream);
 }
 
-static uint4* fused_wp16(void* ws, int64_t H);
+int sgs_edge_score_bwd_dfeat_bits(const uint32_t* dvbits, const float* dz, int64_t n, int64_t H, const float* W1, const float* w2, float p_drop,
+                                  float* dfeat, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    return bwd_dfeat_bits_impl("sgs_edge_score_bwd_dfeat_bits", 3, sgs_edge_score_bwd_bits_supported, dvbits, dz, n, H, W1, w2, p_drop, dfeat, ws,
+                               ws_bytes, stream_);
+}
 
 int sgs_edge_score_bwd_dfeat_bits_bf16(const uint32_t* dvbits, const float* dz, int64_t n, int64_t H, const float* W1, const float* w2,
                                        float p_drop, float* dfeat, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(n >= 0 && H > 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_bits_bf16: bad arguments");
-    SGS_REQUIRE(sgs_edge_score_bf16_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_dfeat_bits_bf16: H=%lld unsupported (128 or 256)", (long long)H);
-    if (n == 0) return SGS_OK;
-    SGS_REQUIRE(dvbits && dz && W1 && w2 && dfeat, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_bits_bf16: null pointer");
-    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_dfeat_bits_bf16: workspace too small");
-    uint4* Wp16 = fused_wp16(ws, H);
-    hipLaunchKernelGGL((pack_w1a_bf16x3<true, 1>), dim3(static_cast<unsigned>(cdiv(pack_w1a_threads(H), kT))), dim3(kT), 0, stream, W1,
-                       static_cast<int>(H), Wp16, w2, 1.0f / (1.0f - p_drop));
-    ScoreArgs a{};
-    a.inbits = dvbits; a.indz = dz; a.n = n; a.H = static_cast<int>(H); a.feat = dfeat;
-    const dim3 grid(static_cast<unsigned>(cdiv(n, 128))), blk(256);
-    bf16x6_launch_knobs(a, 4, H, 1);
-    if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 4, 1>), grid, blk, 0, stream, a, Wp16);
-    else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 4, 1>), grid, blk, 0, stream, a, Wp16);
-    SGS_LAUNCH_OK();
-    return SGS_OK;
+    return bwd_dfeat_bits_impl("sgs_edge_score_bwd_dfeat_bits_bf16", 1, sgs_edge_score_bf16_supported, dvbits, dz, n, H, W1, w2, p_drop, dfeat, ws,
+                               ws_bytes, stream_);
 }
 
 int sgs_endpoint_reduce(const float* M_out, const float* M_in, const float* T, int64_t N, int64_t H, int64_t nnz,
@@ -2851,12 +2808,8 @@ int sgs_endpoint_reduce_pair(const float* dfeat, const float* dv, const float* c
     if (N == 0 || H == 0) return SGS_OK;
     SGS_REQUIRE(dfeat && dv && codes && in_ptr && out_ptr && out_codes && out_U, SGS_EINVAL, "sgs_endpoint_reduce_pair: null pointer");
     const dim3 grid(static_cast<unsigned>(N));
-    if (nnz >= 64 * N)
-        hipLaunchKernelGGL((endpoint_reduce_pair_rowblock<16>), grid, dim3(1024), 0, stream, dfeat, dv, codes, N, H, in_ptr, in_src, in_eid, out_ptr,
-                           out_dst, out_eid, out_codes, out_U);
-    else
-        hipLaunchKernelGGL((endpoint_reduce_pair_rowblock<4>), grid, dim3(256), 0, stream, dfeat, dv, codes, N, H, in_ptr, in_src, in_eid, out_ptr,
-                           out_dst, out_eid, out_codes, out_U);
+    SGS_LAUNCH_ROWBLOCK((endpoint_reduce_pair_rowblock<16>), (endpoint_reduce_pair_rowblock<4>), dfeat, dv, codes, N, H, in_ptr, in_src, in_eid,
+                        out_ptr, out_dst, out_eid, out_codes, out_U);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -2884,16 +2837,7 @@ int sgs_edge_score_bwd_prep(const float* codes, int64_t N, int64_t H, const int6
 
 /* The same pass for the FUSED backward: no feat (its consumers gather the code rows themselves); the endpoints of every active row
  * as int32 pairs instead (sd [n, 2]). */
-// MODE 5's operand, diag(w2 / (1 - p)) W1a^T in bf16x3 pieces, at a fixed place of the dfeat workspace
-static uint4* fused_wp16(void* ws, int64_t H) {
-    Carver cv(ws);
-    cv.take<float>(static_cast<size_t>(H) * H);
-    cv.take<float>(0);
-    cv.take<float>(0);
-    cv.take<unsigned int>(64);
-    return cv.take<uint4>(static_cast<size_t>(H) * H * 6 / 16);
-}
-
+// (MODE 5's operand, diag(w2 / (1 - p)) W1a^T in bf16 pieces, goes to fused_wp16)
 static int bwd_prep_sd_impl(const float* codes, int64_t N, int64_t H, const int64_t* edge_index, int64_t E, const int64_t* active_eid,
                             int64_t n_active, const float* grad_p, const float* p, const uint32_t* maskbits, float* dz, uint32_t* dvbits,
                             int32_t* sd, const float* W1, const float* w2, float p_drop, uint4* Wp16, hipStream_t stream, int P = 3) {
@@ -2921,104 +2865,79 @@ int sgs_edge_score_bwd_prep_sd(const float* codes, int64_t N, int64_t H, const i
                             nullptr, static_cast<hipStream_t>(stream_));
 }
 
+static int bwd_prep_sd_pack_impl(const char* who, int P, int (*supported)(int64_t), const float* codes, int64_t N, int64_t H,
+                                 const int64_t* edge_index, int64_t E, const int64_t* active_eid, int64_t n_active, const float* grad_p, const float* p,
+                                 const uint32_t* maskbits, float* dz, uint32_t* dvbits, int32_t* sd, const float* W1, const float* w2, float p_drop,
+                                 void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    SGS_REQUIRE(p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "%s: bad arguments", who);
+    SGS_REQUIRE(supported(H), SGS_EINVAL, "%s: H=%lld unsupported (128 or 256)", who, (long long)H);
+    if (n_active == 0) return SGS_OK;
+    SGS_REQUIRE(W1 && w2, SGS_EINVAL, "%s: null pointer", who);
+    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "%s: workspace too small", who);
+    return bwd_prep_sd_impl(codes, N, H, edge_index, E, active_eid, n_active, grad_p, p, maskbits, dz, dvbits, sd, W1, w2, p_drop,
+                            fused_wp16(ws, H), static_cast<hipStream_t>(stream_), P);
+}
+
 int sgs_edge_score_bwd_prep_sd_pack(const float* codes, int64_t N, int64_t H, const int64_t* edge_index, int64_t E, const int64_t* active_eid,
                                     int64_t n_active, const float* grad_p, const float* p, const uint32_t* maskbits, float* dz, uint32_t* dvbits,
                                     int32_t* sd, const float* W1, const float* w2, float p_drop, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    SGS_REQUIRE(p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_edge_score_bwd_prep_sd_pack: bad arguments");
-    SGS_REQUIRE(sgs_edge_score_bwd_bits_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_prep_sd_pack: H=%lld unsupported (128 or 256)", (long long)H);
-    if (n_active == 0) return SGS_OK;
-    SGS_REQUIRE(W1 && w2, SGS_EINVAL, "sgs_edge_score_bwd_prep_sd_pack: null pointer");
-    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_prep_sd_pack: workspace too small");
-    return bwd_prep_sd_impl(codes, N, H, edge_index, E, active_eid, n_active, grad_p, p, maskbits, dz, dvbits, sd, W1, w2, p_drop,
-                            fused_wp16(ws, H), static_cast<hipStream_t>(stream_));
+    return bwd_prep_sd_pack_impl("sgs_edge_score_bwd_prep_sd_pack", 3, sgs_edge_score_bwd_bits_supported, codes, N, H, edge_index, E, active_eid,
+                                 n_active, grad_p, p, maskbits, dz, dvbits, sd, W1, w2, p_drop, ws, ws_bytes, stream_);
 }
 
 /* The same with MODE 5's operand packed for the bf16 mode (one piece): the workspace then feeds sgs_edge_score_bwd_dfeat_fused_packed_bf16. */
 int sgs_edge_score_bwd_prep_sd_pack_bf16(const float* codes, int64_t N, int64_t H, const int64_t* edge_index, int64_t E, const int64_t* active_eid,
                                          int64_t n_active, const float* grad_p, const float* p, const uint32_t* maskbits, float* dz, uint32_t* dvbits,
                                          int32_t* sd, const float* W1, const float* w2, float p_drop, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    SGS_REQUIRE(p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_edge_score_bwd_prep_sd_pack_bf16: bad arguments");
-    SGS_REQUIRE(sgs_edge_score_bf16_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_prep_sd_pack_bf16: H=%lld unsupported (128 or 256)", (long long)H);
-    if (n_active == 0) return SGS_OK;
-    SGS_REQUIRE(W1 && w2, SGS_EINVAL, "sgs_edge_score_bwd_prep_sd_pack_bf16: null pointer");
-    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_prep_sd_pack_bf16: workspace too small");
-    return bwd_prep_sd_impl(codes, N, H, edge_index, E, active_eid, n_active, grad_p, p, maskbits, dz, dvbits, sd, W1, w2, p_drop,
-                            fused_wp16(ws, H), static_cast<hipStream_t>(stream_), 1);
+    return bwd_prep_sd_pack_impl("sgs_edge_score_bwd_prep_sd_pack_bf16", 1, sgs_edge_score_bf16_supported, codes, N, H, edge_index, E, active_eid,
+                                 n_active, grad_p, p, maskbits, dz, dvbits, sd, W1, w2, p_drop, ws, ws_bytes, stream_);
 }
 
 /* MODE 5 of the bf16x6 loop (see the kernel): G [n, H] = dfeat * codes[src], opart [cdiv(n, 32) + N, H] = run-end partial sums of
  * dfeat * codes[dst].  The active rows must be sorted by source. */
 size_t sgs_edge_score_bwd_fused_opart_rows(int64_t n, int64_t N) { return static_cast<size_t>(cdiv(n < 0 ? 0 : n, 32) + (N < 0 ? 0 : N)); }
 
-static int bwd_dfeat_fused_launch(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t H,
-                                  const uint4* Wp16, float* G, float* opart, hipStream_t stream, int P = 3) {
+// All four forms.  packed: the operand is already in ws (sgs_edge_score_bwd_prep_sd_pack* left it there), so W1 / w2 / p_drop are not given.
+static int bwd_dfeat_fused_impl(const char* who, int P, int (*supported)(int64_t), bool packed, const uint32_t* dvbits, const float* dz,
+                                const int32_t* sd, const float* codes, int64_t n, int64_t N, int64_t H, const float* W1, const float* w2, float p_drop,
+                                float* G, float* opart, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(n >= 0 && N > 0 && H > 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "%s: bad arguments", who);
+    SGS_REQUIRE(supported(H), SGS_EINVAL, "%s: H=%lld unsupported (128 or 256)", who, (long long)H);
+    if (n == 0) return SGS_OK;
+    SGS_REQUIRE(dvbits && dz && sd && codes && (packed || (W1 && w2)) && G && opart, SGS_EINVAL, "%s: null pointer", who);
+    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "%s: workspace too small", who);
+    uint4* const Wp16 = fused_wp16(ws, H);
+    if (!packed) launch_pack_w1a<true>(P, W1, H, Wp16, stream, w2, 1.0f / (1.0f - p_drop));
     ScoreArgs a{};
     a.inbits = dvbits; a.indz = dz; a.n = n; a.H = static_cast<int>(H); a.feat = G; a.codes = codes; a.sd = sd; a.opart = opart;
-    const dim3 grid(static_cast<unsigned>(cdiv(n, 128))), blk(256);
-    bf16x6_launch_knobs(a, 5, H, P);
-    if (P == 1) {
-        if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 5, 1>), grid, blk, 0, stream, a, Wp16);
-        else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 5, 1>), grid, blk, 0, stream, a, Wp16);
-        SGS_LAUNCH_OK();
-        return SGS_OK;
-    }
-    if (H == 256) hipLaunchKernelGGL((edge_score_bf16x6_kernel<8, 4, 5>), grid, blk, 0, stream, a, Wp16);
-    else          hipLaunchKernelGGL((edge_score_bf16x6_kernel<4, 4, 5>), grid, blk, 0, stream, a, Wp16);
-    SGS_LAUNCH_OK();
-    return SGS_OK;
+    return P == 1 ? launch_bf16x6<5, 1>(a, Wp16, n, H, stream) : launch_bf16x6<5, 3>(a, Wp16, n, H, stream);
 }
 
 int sgs_edge_score_bwd_dfeat_fused(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t N, int64_t H,
                                    const float* W1, const float* w2, float p_drop, float* G, float* opart, void* ws, size_t ws_bytes,
                                    sgs_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(n >= 0 && N > 0 && H > 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused: bad arguments");
-    SGS_REQUIRE(sgs_edge_score_bwd_bits_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused: H=%lld unsupported (128 or 256)", (long long)H);
-    if (n == 0) return SGS_OK;
-    SGS_REQUIRE(dvbits && dz && sd && codes && W1 && w2 && G && opart, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused: null pointer");
-    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_dfeat_fused: workspace too small");
-    uint4* Wp16 = fused_wp16(ws, H);
-    hipLaunchKernelGGL(pack_w1a_bf16x3<true>, dim3(static_cast<unsigned>(cdiv(pack_w1a_threads(H), kT))), dim3(kT), 0, stream, W1,
-                       static_cast<int>(H), Wp16, w2, 1.0f / (1.0f - p_drop));
-    return bwd_dfeat_fused_launch(dvbits, dz, sd, codes, n, H, Wp16, G, opart, stream);
+    return bwd_dfeat_fused_impl("sgs_edge_score_bwd_dfeat_fused", 3, sgs_edge_score_bwd_bits_supported, false, dvbits, dz, sd, codes, n, N, H, W1, w2,
+                                p_drop, G, opart, ws, ws_bytes, stream_);
 }
 
 int sgs_edge_score_bwd_dfeat_fused_packed(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t N,
                                           int64_t H, float* G, float* opart, const void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    SGS_REQUIRE(n >= 0 && N > 0 && H > 0, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_packed: bad arguments");
-    SGS_REQUIRE(sgs_edge_score_bwd_bits_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_packed: H=%lld unsupported (128 or 256)",
-                (long long)H);
-    if (n == 0) return SGS_OK;
-    SGS_REQUIRE(dvbits && dz && sd && codes && G && opart, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_packed: null pointer");
-    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_dfeat_fused_packed: workspace too small");
-    return bwd_dfeat_fused_launch(dvbits, dz, sd, codes, n, H, fused_wp16(const_cast<void*>(ws), H), G, opart, static_cast<hipStream_t>(stream_));
+    return bwd_dfeat_fused_impl("sgs_edge_score_bwd_dfeat_fused_packed", 3, sgs_edge_score_bwd_bits_supported, true, dvbits, dz, sd, codes, n, N, H,
+                                nullptr, nullptr, 0.f, G, opart, const_cast<void*>(ws), ws_bytes, stream_);
 }
 
 int sgs_edge_score_bwd_dfeat_fused_bf16(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t N,
                                         int64_t H, const float* W1, const float* w2, float p_drop, float* G, float* opart, void* ws, size_t ws_bytes,
                                         sgs_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(n >= 0 && N > 0 && H > 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_bf16: bad arguments");
-    SGS_REQUIRE(sgs_edge_score_bf16_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_bf16: H=%lld unsupported (128 or 256)", (long long)H);
-    if (n == 0) return SGS_OK;
-    SGS_REQUIRE(dvbits && dz && sd && codes && W1 && w2 && G && opart, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_bf16: null pointer");
-    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE, "sgs_edge_score_bwd_dfeat_fused_bf16: workspace too small");
-    uint4* Wp16 = fused_wp16(ws, H);
-    hipLaunchKernelGGL((pack_w1a_bf16x3<true, 1>), dim3(static_cast<unsigned>(cdiv(pack_w1a_threads(H), kT))), dim3(kT), 0, stream, W1,
-                       static_cast<int>(H), Wp16, w2, 1.0f / (1.0f - p_drop));
-    return bwd_dfeat_fused_launch(dvbits, dz, sd, codes, n, H, Wp16, G, opart, stream, 1);
+    return bwd_dfeat_fused_impl("sgs_edge_score_bwd_dfeat_fused_bf16", 1, sgs_edge_score_bf16_supported, false, dvbits, dz, sd, codes, n, N, H, W1, w2,
+                                p_drop, G, opart, ws, ws_bytes, stream_);
 }
 
 int sgs_edge_score_bwd_dfeat_fused_packed_bf16(const uint32_t* dvbits, const float* dz, const int32_t* sd, const float* codes, int64_t n, int64_t N,
                                                int64_t H, float* G, float* opart, const void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    SGS_REQUIRE(n >= 0 && N > 0 && H > 0, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_packed_bf16: bad arguments");
-    SGS_REQUIRE(sgs_edge_score_bf16_supported(H), SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_packed_bf16: H=%lld unsupported (128 or 256)",
-                (long long)H);
-    if (n == 0) return SGS_OK;
-    SGS_REQUIRE(dvbits && dz && sd && codes && G && opart, SGS_EINVAL, "sgs_edge_score_bwd_dfeat_fused_packed_bf16: null pointer");
-    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_score_workspace_bytes(0, H, 0), SGS_EWORKSPACE,
-                "sgs_edge_score_bwd_dfeat_fused_packed_bf16: workspace too small");
-    return bwd_dfeat_fused_launch(dvbits, dz, sd, codes, n, H, fused_wp16(const_cast<void*>(ws), H), G, opart, static_cast<hipStream_t>(stream_), 1);
+    return bwd_dfeat_fused_impl("sgs_edge_score_bwd_dfeat_fused_packed_bf16", 1, sgs_edge_score_bf16_supported, true, dvbits, dz, sd, codes, n, N, H,
+                                nullptr, nullptr, 0.f, G, opart, const_cast<void*>(ws), ws_bytes, stream_);
 }
 
 /* The reductions that follow it: out_codes, out_U (and out_U_raw, optional) as sgs_endpoint_reduce_pair_bits produces them. */
@@ -3033,12 +2952,8 @@ int sgs_edge_score_bwd_reduce_fused(const float* G, const float* opart, const ui
                 "sgs_edge_score_bwd_reduce_fused: null pointer");
     const dim3 grid(static_cast<unsigned>(N));
     const float scale = 1.0f / (1.0f - p_drop);
-    if (nnz >= 64 * N)
-        hipLaunchKernelGGL((scorer_bwd_reduce<16>), grid, dim3(1024), 0, stream, G, opart, dvbits, dz, w2, scale, N, H, in_ptr, in_eid, out_ptr,
-                           out_codes, out_U, out_U_raw);
-    else
-        hipLaunchKernelGGL((scorer_bwd_reduce<4>), grid, dim3(256), 0, stream, G, opart, dvbits, dz, w2, scale, N, H, in_ptr, in_eid, out_ptr,
-                           out_codes, out_U, out_U_raw);
+    SGS_LAUNCH_ROWBLOCK((scorer_bwd_reduce<16>), (scorer_bwd_reduce<4>), G, opart, dvbits, dz, w2, scale, N, H, in_ptr, in_eid, out_ptr, out_codes,
+                        out_U, out_U_raw);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -3067,12 +2982,8 @@ int sgs_endpoint_reduce_pair_bits(const float* dfeat, const uint32_t* dvbits, co
     const dim3 grid(static_cast<unsigned>(N));
     const float scale = 1.0f / (1.0f - p_drop);
     const float* nodv = nullptr;
-    if (nnz >= 64 * N)
-        hipLaunchKernelGGL((endpoint_reduce_pair_rowblock<16, true>), grid, dim3(1024), 0, stream, dfeat, nodv, codes, N, H, in_ptr, in_src, in_eid,
-                           out_ptr, out_dst, out_eid, out_codes, out_U, dvbits, dz, w2, scale, out_U_raw);
-    else
-        hipLaunchKernelGGL((endpoint_reduce_pair_rowblock<4, true>), grid, dim3(256), 0, stream, dfeat, nodv, codes, N, H, in_ptr, in_src, in_eid,
-                           out_ptr, out_dst, out_eid, out_codes, out_U, dvbits, dz, w2, scale, out_U_raw);
+    SGS_LAUNCH_ROWBLOCK((endpoint_reduce_pair_rowblock<16, true>), (endpoint_reduce_pair_rowblock<4, true>), dfeat, nodv, codes, N, H, in_ptr, in_src,
+                        in_eid, out_ptr, out_dst, out_eid, out_codes, out_U, dvbits, dz, w2, scale, out_U_raw);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -3080,8 +2991,9 @@ int sgs_endpoint_reduce_pair_bits(const float* dfeat, const uint32_t* dvbits, co
 /* ---- endpoint-dropout scorer (EdgeProbMLP with dropout > 0, model.py:16-45): see the EPD notes at edge_score_kernel ---- */
 size_t sgs_edge_score_epd_workspace_bytes(int64_t H) { return carve_bytes(2 * static_cast<size_t>(H < 0 ? 0 : H) * (H < 0 ? 0 : H), 4) + 256; }
 
-static int epd_args(ScoreArgs& a, const char* who, const float* A, int64_t N, int64_t H, const int64_t* edge_index, int64_t E, int64_t edge_id_offset,
-                    const float* W1, const float* b1, const float* w2, const float* b2, float p_hidden, uint64_t seed, uint32_t site, float p_ep,
+static int epd_args(ScoreArgs& a, const char* who, const float* A, int64_t N, int64_t H, const int64_t* edge_index, int64_t E, const int64_t* active,
+                    int64_t n, int64_t edge_id_offset, const float* W1, const float* b1, const float* w2, const float* b2, float p_hidden, uint64_t seed,
+                    uint32_t site, float p_ep,
                     uint64_t seed_x, uint32_t site_x, uint64_t seed_y, uint32_t site_y, void* ws, size_t ws_bytes, hipStream_t stream) {
     if (int rc = check_common(who, N, H, E, p_hidden)) return rc;
     SGS_REQUIRE(H % 16 == 0, SGS_EINVAL, "%s: the endpoint-dropout scorer needs H %% 16 == 0 (H=%lld)", who, (long long)H);
@@ -3091,10 +3003,7 @@ static int epd_args(ScoreArgs& a, const char* who, const float* A, int64_t N, in
     Carver cv(ws);
     float* WT = cv.take<float>(2 * static_cast<size_t>(H) * H);
     hipLaunchKernelGGL(transpose_w1_full, dim3(cdiv(2 * H, 32), cdiv(H, 32)), dim3(kT), 0, stream, W1, static_cast<int>(H), WT);
-    a.codes = A; a.U = nullptr; a.src = edge_index; a.dst = edge_index + E; a.H = static_cast<int>(H); a.row_offset = edge_id_offset;
-    a.WaT = WT; a.b1 = b1; a.w2 = w2; a.b2 = b2;
-    a.drop_scale = 1.0f / (1.0f - p_hidden); a.drop_thresh = dropout_thresh(p_hidden); a.seed = seed; a.epoch = epoch_ptr(); a.site = site;
-    a.use_drop = p_hidden > 0.f;
+    score_args(a, A, nullptr, edge_index, E, active, n, edge_id_offset, H, WT, b1, w2, b2, p_hidden, seed, site);
     a.epd = p_ep > 0.f; a.seed_x = seed_x; a.seed_y = seed_y; a.site_x = site_x; a.site_y = site_y;
     a.ep_scale = 1.0f / (1.0f - p_ep); a.ep_thresh = dropout_thresh(p_ep);
     return SGS_OK;
@@ -3108,9 +3017,9 @@ int sgs_edge_score_epd_fwd(const float* A, int64_t N, int64_t H, const int64_t* 
     if (E == 0) return SGS_OK;
     SGS_REQUIRE(p_out, SGS_EINVAL, "sgs_edge_score_epd_fwd: null pointer");
     ScoreArgs a{};
-    if (int rc = epd_args(a, "sgs_edge_score_epd_fwd", A, N, H, edge_index, E, edge_id_offset, W1, b1, w2, b2, p_hidden, seed, site, p_ep, seed_x, site_x,
+    if (int rc = epd_args(a, "sgs_edge_score_epd_fwd", A, N, H, edge_index, E, nullptr, E, edge_id_offset, W1, b1, w2, b2, p_hidden, seed, site, p_ep, seed_x, site_x,
                           seed_y, site_y, ws, ws_bytes, stream)) return rc;
-    a.active = nullptr; a.n = E; a.p_out = p_out;
+    a.p_out = p_out;
     return H > 256 ? launch_score_wide<false, true>(a, stream) : launch_score<false, true>(a, stream);
 }
 
@@ -3124,9 +3033,9 @@ int sgs_edge_score_epd_bwd_core(const float* A, int64_t N, int64_t H, const int6
     if (n_active == 0) return SGS_OK;
     SGS_REQUIRE(grad_p && dv && hdz_part && dz && feat2, SGS_EINVAL, "sgs_edge_score_epd_bwd_core: null pointer");
     ScoreArgs a{};
-    if (int rc = epd_args(a, "sgs_edge_score_epd_bwd_core", A, N, H, edge_index, E, edge_id_offset, W1, b1, w2, b2, p_hidden, seed, site, p_ep, seed_x,
+    if (int rc = epd_args(a, "sgs_edge_score_epd_bwd_core", A, N, H, edge_index, E, active_eid, n_active, edge_id_offset, W1, b1, w2, b2, p_hidden, seed, site, p_ep, seed_x,
                           site_x, seed_y, site_y, ws, ws_bytes, stream)) return rc;
-    a.active = active_eid; a.n = n_active; a.gp = grad_p; a.dv = dv; a.hdz = hdz_part; a.dz = dz; a.feat = feat2;
+    a.gp = grad_p; a.dv = dv; a.hdz = hdz_part; a.dz = dz; a.feat = feat2;
     return H > 256 ? launch_score_wide<true, true>(a, stream) : launch_score<true, true>(a, stream);
 }
 
@@ -3156,5 +3065,7 @@ int sgs_edge_score_probe_set(int stagger, int prio, uint32_t mode_mask) {
     g_stagger_modes = mode_mask;
     return SGS_OK;
 }
+
+#undef SGS_LAUNCH_ROWBLOCK
 
 }  // extern "C"
