@@ -590,7 +590,13 @@ class Norm:
     """gcn_norm result for (graph, w): dis, loopw and the normalised weights in both CSR orders.
     `handle` is the autograd edge through which the layers' gradients wrt the normalised
     weights ([n_edges] edge order + [N] loops) flow back to `w`; its storage is never read."""
-    __slots__ = ("graph", "w", "dis", "loopw", "what_in", "what_out", "what_loop", "handle", "_g_first", "_g_extra", "_dw_first", "_park_ok", "__weakref__")
+    __slots__ = ("graph", "w", "dis", "loopw", "what_in", "what_out", "what_loop", "handle", "_g_first", "_g_extra", "_dw_first", "_park_ok",
+                 "_extra_total", "__weakref__")
+
+    def __init__(self):
+        self.graph = self.w = self.dis = self.loopw = self.what_in = self.what_out = self.what_loop = self.handle = None
+        self._g_first = self._g_extra = self._dw_first = None          # the edge-weight gradient side band: see _handle_grad
+        self._park_ok = self._extra_total = False
 
 
 def _norm_forward(graph: Graph, w):
@@ -605,7 +611,6 @@ def _norm_forward(graph: Graph, w):
         offs.append(offs[-1] + ((z + 63) & ~63))
     buf = torch.empty(offs[-1], dtype=torch.float32, device=dev)
     nm.dis, nm.loopw, nm.what_in, nm.what_out, nm.what_loop = (buf[offs[i]:offs[i] + sizes[i]] for i in range(5))
-    nm.handle = None
     _lib.check(L.sgs_gcn_norm_fwd(_ptr(w, torch.float32), graph.n_edges, graph.N, _ptr(graph.in_ptr), _ptr(graph.in_src),
                                   _ptr(graph.in_eid), _ptr(graph.out_ptr), _ptr(graph.out_dst), _ptr(graph.out_eid),
                                   _ptr(graph.loop_eid), _ptr(nm.dis), _ptr(nm.loopw), _ptr(nm.what_in), _ptr(nm.what_out),
@@ -627,13 +632,7 @@ class _GCNNorm(torch.autograd.Function):
         nm, gr = ctx.nm, ctx.nm.graph
         g = g.contiguous()
         n = gr.n_edges
-        # side bands (see _handle_grad / note_first_dw): a second layer's gradient wrt the normalised weights is summed on read, and the
-        # edge weights' other consumer's d w (the loss's regularisers) is accumulated IN PLACE -- two autograd add launches less
-        extra = getattr(nm, "_g_extra", None)
-        nm._g_first = nm._g_extra = None
-        first = getattr(nm, "_dw_first", None)
-        first = first() if first is not None else None
-        nm._dw_first = None
+        extra, _, first = _take_parked(nm)                # the side band: see _handle_grad
         if first is not None and (first.numel() != n or not first.is_contiguous() or first.dtype != torch.float32):
             first = None
         dw = first if first is not None else torch.empty(n, dtype=torch.float32, device=g.device)
@@ -655,19 +654,53 @@ class _GCNNorm(torch.autograd.Function):
 
 
 def _handle_grad(nm, g):
-    """What a layer's backward returns for the normalisation's handle.  Both layers of a model share one Norm; autograd would add their two
-    gradients with a launch of its own before _GCNNorm.backward.  Instead the first layer to finish returns its gradient as usual and the
-    second parks its own on the Norm (summed on read by sgs_gcn_norm_bwd_sum) and returns None.  Nothing can get lost: the parked gradient
-    has exactly one consumer, _GCNNorm.backward, which runs after every layer over the Norm has reported."""
-    if not getattr(nm, "_park_ok", False):             # only Norms whose backward (_GCNNorm) reads the side band
+    """What a layer's backward returns for the handle of the Norm (or EdgeAttr) it ran over -- and the one description of the side band
+    through which the edge weights' gradient is handed over without autograd's add launches.
+
+    The layers of a model share one Norm, so autograd would add their gradients with a launch of its own before the Norm's backward.
+    Instead, on a Norm whose backward reads the side band (`_park_ok`: set by gcn_norm, cheb_norm and gat_edge_attr when they make a
+    handle; False everywhere else, and then every layer simply returns its gradient):
+      * who parks.  The first layer to finish is noted in `_g_first` and returns its gradient as usual.  The second parks its own in
+        `_g_extra` and returns None; later ones return theirs again.  The edge-attribute layers (edge GAT, GATv2, GINE) first ask
+        _dw_to_add for the noted gradient and add it inside their own kernel, so that what they park is already the total; _report_dw
+        then says so in `_extra_total`.  The hybrid loss parks a weak reference to its own d w in `_dw_first` (GCN norms only).
+      * who reads.  The three handle backwards, through _take_parked: _GCNNorm (the kernel sums `_g_extra` on read and accumulates into
+        `_dw_first` in place), _ChebNorm (`_g_extra` summed on read) and _GATEdgeAttr (`_g_extra` added, or returned as it is when it is
+        the total).  Each runs after every layer over the Norm has reported, so a parked gradient has exactly one consumer.
+      * who resets.  _take_parked, and nobody else: after a backward the side band is neutral again."""
+    if not nm._park_ok:
         return g
-    if getattr(nm, "_g_first", None) is None:
+    if nm._g_first is None:
         nm._g_first = g
         return g
-    if getattr(nm, "_g_extra", None) is None:
+    if nm._g_extra is None:
         nm._g_extra = g
         return None
     return g
+
+
+def _dw_to_add(nm, n):
+    """(second, dw_add) for an edge-attribute layer about to form its d w [n]: the other layer's, if it has reported already and nothing
+    is parked yet, to be added by this layer's own kernel (_handle_grad)."""
+    second = nm._park_ok and nm._g_first is not None and nm._g_extra is None and nm._g_first.numel() == n
+    return second, (nm._g_first.contiguous() if second else None)
+
+
+def _report_dw(nm, dw, second):
+    """_handle_grad for a d w formed with _dw_to_add's `second`: when it is parked, it holds both layers' sum."""
+    g_handle = _handle_grad(nm, dw)
+    if second and g_handle is None:
+        nm._extra_total = True
+    return g_handle
+
+
+def _take_parked(nm):
+    """(extra, total, first): the parked gradient, whether it is already the layers' sum, and the loss's live d w (or None); the side
+    band is neutral afterwards (_handle_grad)."""
+    extra, total, first = nm._g_extra, nm._extra_total, nm._dw_first
+    nm._g_first = nm._g_extra = nm._dw_first = None
+    nm._extra_total = False
+    return extra, total, (first() if first is not None else None)
 
 
 def gcn_norm(graph: Graph, w=None) -> Norm:
@@ -725,15 +758,9 @@ class _Propagate(torch.autograd.Function):
         X, Y = ctx.saved_tensors
         N, D = X.shape
         dY = dY.contiguous()
-        dX = dbias = g = None
+        dX = g = None
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.act != ACT_NONE and want_db:
-            dZ, dbias = _act_bwd_colsum(dY, Y, ctx.act, ctx.p)
-        elif ctx.act != ACT_NONE:
-            dZ = torch.empty_like(dY)
-            _lib.check(L.sgs_act_bwd(_ptr(dY), _ptr(Y), dY.numel(), ctx.act, float(ctx.p), _ptr(dZ), _stream()), "sgs_act_bwd")
-        else:
-            dZ = dY
+        dZ, dbias = _grad_through_act(dY, Y, ctx.act, ctx.p, want_db, colsum_now=False)
         if ctx.needs_input_grad[0]:
             dX = _spmm(dZ, gr.out_ptr, gr.out_dst, nm.what_out, nm.what_loop, None, ACT_NONE, 0.0, 0, 0, N, D, gr.n_edges)
         if ctx.has_handle and ctx.needs_input_grad[1]:
@@ -800,6 +827,23 @@ def _colsum(A):
     ws = workspace(L.sgs_colsum_workspace_bytes(N, D), A.device)
     _lib.check(L.sgs_colsum(_ptr(A), N, D, _ptr(out), ws.data_ptr(), ws.numel(), _stream()), "sgs_colsum")
     return out
+
+
+def _act_bwd(dY, Y, act, p):
+    """dZ = dY * act'(Y) (one sgs_act_bwd launch, also for ACT_NONE)."""
+    dZ = torch.empty_like(dY)
+    _lib.check(_lib.lib().sgs_act_bwd(_ptr(dY), _ptr(Y), dY.numel(), act, float(p), _ptr(dZ), _stream()), "sgs_act_bwd")
+    return dZ
+
+
+def _grad_through_act(dY, Y, act, p, want_db, colsum_now=True):
+    """The prologue of a layer's backward, (dZ, dbias): dZ = dY * act'(Y) -- dY itself without an activation -- and, when `want_db`,
+    dbias = colsum(dZ).  With an activation and a bias gradient both come from one pass; without an activation the plain column sum is
+    taken here, or, with colsum_now=False, left to the caller (dbias None), who takes it with _colsum after its SpMM / SDDMM.
+    `want_db` is the caller's own: the GCN / Chebyshev layers ask has_bias and needs_input_grad, the attention layers has_bias alone."""
+    if act != ACT_NONE:
+        return _act_bwd_colsum(dY, Y, act, p) if want_db else (_act_bwd(dY, Y, act, p), None)
+    return dY, (_colsum(dY) if want_db and colsum_now else None)
 
 
 def _endpoint_reduce(M_out, M_in, T, graph: Graph, s_out, s_in, H):
@@ -1522,7 +1566,7 @@ class _HybridLoss(torch.autograd.Function):
                 _lib.check(L.sgs_masked_ce_bwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(row_lse), _ptr(n_rows), _ptr(g), _ptr(dlogits),
                                                _stream()), "sgs_masked_ce_bwd")
         nm = ctx.nm_ref() if ctx.nm_ref is not None else None
-        if nm is not None and getattr(nm, "_park_ok", False) and dw.numel() == nm.graph.n_edges:
+        if nm is not None and nm._park_ok and dw.numel() == nm.graph.n_edges:
             import weakref
             nm._dw_first = weakref.ref(dw)                 # the normalisation's backward accumulates into dw in place (no autograd add)
         return dlogits, None, None, dw, None, None, None, None, None, None, None
@@ -1574,16 +1618,7 @@ class _GATAggregate(torch.autograd.Function):
         n = gr.n_edges
         dev = xl.device
         f32 = dict(dtype=torch.float32, device=dev)
-        dY = dY.contiguous()
-        dbias = None
-        if ctx.act != ACT_NONE and ctx.has_bias:
-            dZ, dbias = _act_bwd_colsum(dY, Y, ctx.act, ctx.p_act)
-        elif ctx.act != ACT_NONE:
-            dZ = torch.empty_like(dY)
-            _lib.check(L.sgs_act_bwd(_ptr(dY), _ptr(Y), dY.numel(), ctx.act, ctx.p_act, _ptr(dZ), _stream()), "sgs_act_bwd")
-        else:
-            dZ = dY
-            dbias = _colsum(dZ) if ctx.has_bias else None
+        dZ, dbias = _grad_through_act(dY.contiguous(), Y, ctx.act, ctx.p_act, ctx.has_bias)
         # alpha re-ordered into src-CSR entry order for the transposed aggregation
         by_eid = torch.empty(max(n, 1), **f32)
         alpha_out = torch.empty(max(n, 1), **f32)
@@ -1651,61 +1686,36 @@ def _spmm_heads(X, ptr, col, eid, val, diag, mode, bias, act, p, seed, site, N, 
     return Y
 
 
-class _GATAggregateHeads(torch.autograd.Function):
-    """_GATAggregate for K heads: xl [N, K C] head-major, a_s / a_d [N, K]; out [N, K C] (concat) or the head mean [N, C]."""
+def _heads_alloc(n, N, K, f32):
+    """(soft, alpha, soft_loop, alpha_loop): the per-edge [max(n, 1), K] (by edge id) and per-node [N, K] arrays a per-head softmax fills."""
+    return torch.empty(max(n, 1), K, **f32), torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32), torch.empty(N, K, **f32)
 
-    @staticmethod
-    def forward(ctx, xl, a_s, a_d, bias, graph, K, concat, slope, p_att, seed_att, site_att, act, p_act, seed_act, site_act):
-        L = _lib.lib()
-        N, D = xl.shape
-        C = D // K
-        n = graph.n_edges
-        f32 = dict(dtype=torch.float32, device=xl.device)
-        soft, alpha = torch.empty(max(n, 1), K, **f32), torch.empty(max(n, 1), K, **f32)
-        soft_loop, alpha_loop = torch.empty(N, K, **f32), torch.empty(N, K, **f32)
-        _lib.check(L.sgs_gat_alpha_heads_fwd(_ptr(a_s), _ptr(a_d), N, K, n, _ptr(graph.in_ptr), _ptr(graph.in_src), _ptr(graph.in_eid),
-                                             float(slope), float(p_att), seed_att, site_att, _ptr(soft), _ptr(soft_loop), _ptr(alpha),
-                                             _ptr(alpha_loop), _stream()), "sgs_gat_alpha_heads_fwd")
-        Y = _spmm_heads(xl, graph.in_ptr, graph.in_src, graph.in_eid, alpha, alpha_loop, HEADS_CONCAT if concat else HEADS_MEAN, bias, act,
-                        p_act, seed_act, site_act, N, K, C, n)
-        ctx.save_for_backward(xl, a_s, a_d, soft, soft_loop, alpha, alpha_loop, Y if act != ACT_NONE else None)
-        ctx.graph, ctx.slope, ctx.p_att, ctx.seed_att, ctx.site_att = graph, float(slope), float(p_att), seed_att, site_att
-        ctx.act, ctx.p_act, ctx.has_bias, ctx.K, ctx.concat = act, float(p_act), bias is not None, K, bool(concat)
-        return Y
 
-    @staticmethod
-    def backward(ctx, dY):
-        L = _lib.lib()
-        xl, a_s, a_d, soft, soft_loop, alpha, alpha_loop, Y = ctx.saved_tensors
-        gr, K = ctx.graph, ctx.K
-        N, D = xl.shape
-        C = D // K
-        n = gr.n_edges
-        f32 = dict(dtype=torch.float32, device=xl.device)
-        dY = dY.contiguous()
-        dbias = None
-        if ctx.act != ACT_NONE and ctx.has_bias:
-            dZ, dbias = _act_bwd_colsum(dY, Y, ctx.act, ctx.p_act)
-        elif ctx.act != ACT_NONE:
-            dZ = torch.empty_like(dY)
-            _lib.check(L.sgs_act_bwd(_ptr(dY), _ptr(Y), dY.numel(), ctx.act, ctx.p_act, _ptr(dZ), _stream()), "sgs_act_bwd")
-        else:
-            dZ = dY
-            dbias = _colsum(dZ) if ctx.has_bias else None
-        # d x' over the src-CSR: the same alpha array through out_eid (concat = False: dZ [N, C] is shared by the heads, scaled by 1 / K)
-        dxl = _spmm_heads(dZ, gr.out_ptr, gr.out_dst, gr.out_eid, alpha, alpha_loop, HEADS_CONCAT if ctx.concat else HEADS_BROADCAST, None,
-                          ACT_NONE, 0.0, 0, 0, N, K, C, n)
-        galpha, gloop = torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32)
-        _lib.check(L.sgs_sddmm_csr_heads(_ptr(dZ), _ptr(xl), N, K, C, n, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid),
-                                         0 if ctx.concat else 1, _ptr(galpha), _ptr(gloop), _stream()), "sgs_sddmm_csr_heads")
-        g_edge, g_self, d_ad = torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32), torch.empty(N, K, **f32)
-        _lib.check(L.sgs_gat_alpha_heads_bwd(_ptr(a_s), _ptr(a_d), N, K, n, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid), ctx.slope,
-                                             ctx.p_att, ctx.seed_att, ctx.site_att, _ptr(soft), _ptr(soft_loop), _ptr(galpha), _ptr(gloop),
-                                             _ptr(g_edge), _ptr(g_self), _ptr(d_ad), _stream()), "sgs_gat_alpha_heads_bwd")
-        d_as = torch.empty(N, K, **f32)
-        _lib.check(L.sgs_edge_sum_by_row_heads(_ptr(g_edge), _ptr(g_self), N, K, n, _ptr(gr.out_ptr), _ptr(gr.out_eid), _ptr(d_as), _stream()),
-                   "sgs_edge_sum_by_row_heads")
-        return dxl, d_as, d_ad, dbias, None, None, None, None, None, None, None, None, None, None, None
+def _heads_forward(ctx, xl, graph, alpha, alpha_loop, bias, K, concat, sm, epi):
+    """The aggregation launch of a per-head attention forward, and the context fields its backward reads whatever the softmax's family:
+    `sm` = (slope, p_att, seed_att, site_att) of the softmax, `epi` = (act, p_act, seed_act, site_act) of the epilogue.  Returns Y."""
+    N, D = xl.shape
+    act, p_act, seed_act, site_act = epi
+    Y = _spmm_heads(xl, graph.in_ptr, graph.in_src, graph.in_eid, alpha, alpha_loop, HEADS_CONCAT if concat else HEADS_MEAN, bias, act,
+                    p_act, seed_act, site_act, N, K, D // K, graph.n_edges)
+    ctx.graph, (ctx.slope, ctx.p_att, ctx.seed_att, ctx.site_att) = graph, sm
+    ctx.act, ctx.p_act, ctx.has_bias, ctx.K, ctx.concat = act, p_act, bias is not None, K, bool(concat)
+    return Y
+
+
+def _heads_backward_head(ctx, dY, Y, xl, alpha, alpha_loop, f32):
+    """What every per-head attention backward starts with, (dbias, dxl, galpha, gloop): the prologue, d x' over the src-CSR (the same
+    alpha array through out_eid; concat = False: dZ [N, C] is shared by the heads, scaled by 1 / K) and the per-head SDDMM."""
+    gr, K = ctx.graph, ctx.K
+    N, D = xl.shape
+    C, n = D // K, gr.n_edges
+    dZ, dbias = _grad_through_act(dY.contiguous(), Y, ctx.act, ctx.p_act, ctx.has_bias)
+    dxl = _spmm_heads(dZ, gr.out_ptr, gr.out_dst, gr.out_eid, alpha, alpha_loop, HEADS_CONCAT if ctx.concat else HEADS_BROADCAST, None,
+                      ACT_NONE, 0.0, 0, 0, N, K, C, n)
+    galpha, gloop = torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32)
+    _lib.check(_lib.lib().sgs_sddmm_csr_heads(_ptr(dZ), _ptr(xl), N, K, C, n, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid),
+                                              0 if ctx.concat else 1, _ptr(galpha), _ptr(gloop), _stream()), "sgs_sddmm_csr_heads")
+    return dbias, dxl, galpha, gloop
 
 
 # ---- edge-weighted attention (GATConv edge_dim = 1 with the edge weight as the attribute; csrc/gat.hip, gat_alpha_heads_edge_*)
@@ -1713,7 +1723,7 @@ class EdgeAttr(Norm):
     """The edge weights of one forward as the GAT layers consume them: `w` [n_edges] by edge id and, when they require a gradient, the
     autograd `handle` through which the layers' d w flow back (a Norm, so that the layers report through _handle_grad like the GCN and
     Chebyshev heads: the second layer to finish adds the first one's d w on its way out and parks the total)."""
-    __slots__ = ("_extra_total",)
+    __slots__ = ()
 
 
 class _GATEdgeAttr(torch.autograd.Function):
@@ -1726,10 +1736,7 @@ class _GATEdgeAttr(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        nm = ctx.nm
-        extra, total = getattr(nm, "_g_extra", None), getattr(nm, "_extra_total", False)
-        nm._g_first = nm._g_extra = None
-        nm._extra_total = False
+        extra, total, _ = _take_parked(ctx.nm)
         if extra is None:
             return g, None
         return (extra if total else g + extra), None         # total: the parked gradient already holds both layers' sum
@@ -1743,86 +1750,72 @@ def gat_edge_attr(graph: Graph, w) -> EdgeAttr:
     if w.dtype != torch.float32 or w.numel() != graph.n_edges:
         raise RuntimeError(f"edge_weight must be float32 [{graph.n_edges}]")
     nm = EdgeAttr()
-    nm.graph, nm.w, nm.handle, nm._park_ok, nm._extra_total = graph, w.detach(), None, False, False
-    nm._g_first = nm._g_extra = None
+    nm.graph, nm.w = graph, w.detach()
     if w.requires_grad and torch.is_grad_enabled():
         nm.handle = _GATEdgeAttr.apply(w, nm)
         nm._park_ok = True        # _GATEdgeAttr.backward reads the parked second gradient
     return nm
 
 
-class _GATAggregateEdge(torch.autograd.Function):
-    """_GATAggregateHeads with the edge term w_e c_h in the logit (and wbar_i c_h in the loop's); K = 1 included.  Forward: 2 launches
-    (softmax with the row's mean weight, aggregation); backward: _GATAggregateHeads' plus the finishing sum of d c (d w comes out of the
-    softmax backward itself)."""
+class _GATAggregateHeads(torch.autograd.Function):
+    """_GATAggregate for K heads: xl [N, K C] head-major, a_s / a_d [N, K]; out [N, K C] (concat) or the head mean [N, C].  With `nm`
+    (an EdgeAttr; `coef` [K] and `handle` come with it, all three None otherwise) the logit carries the edge term w_e c_h (the loop's
+    wbar_i c_h), K = 1 included.  Forward: 2 launches (softmax -- with the row's mean weight under the edge term --, aggregation);
+    backward: the activation's + 4 (transposed per-head SpMM, per-head SDDMM, softmax backward, by-source sum), the softmax backward
+    with its finishing sum of d c under the edge term (d w comes out of it too)."""
 
     @staticmethod
-    def forward(ctx, xl, a_s, a_d, bias, coef, handle, nm, K, concat, slope, p_att, seed_att, site_att, act, p_act, seed_act, site_act):
+    def forward(ctx, xl, a_s, a_d, bias, coef, handle, nm, graph, K, concat, sm, epi):
         L = _lib.lib()
-        graph = nm.graph
-        N, D = xl.shape
-        C = D // K
-        n = graph.n_edges
+        N, n = xl.shape[0], graph.n_edges
+        slope, p_att, seed_att, site_att = sm
         f32 = dict(dtype=torch.float32, device=xl.device)
-        soft, alpha = torch.empty(max(n, 1), K, **f32), torch.empty(max(n, 1), K, **f32)
-        soft_loop, alpha_loop = torch.empty(N, K, **f32), torch.empty(N, K, **f32)
-        loop = torch.empty(2, max(N, 1), **f32)                # wbar, 1 / cnt
-        _lib.check(L.sgs_gat_alpha_heads_edge_fwd(_ptr(a_s), _ptr(a_d), _ptr(nm.w, torch.float32), _ptr(coef, torch.float32), N, K, n,
-                                                  _ptr(graph.in_ptr), _ptr(graph.in_src), _ptr(graph.in_eid), float(slope), float(p_att), seed_att,
-                                                  site_att, _ptr(soft), _ptr(soft_loop), _ptr(alpha), _ptr(alpha_loop), loop[0].data_ptr(),
-                                                  loop[1].data_ptr(), _stream()), "sgs_gat_alpha_heads_edge_fwd")
-        Y = _spmm_heads(xl, graph.in_ptr, graph.in_src, graph.in_eid, alpha, alpha_loop, HEADS_CONCAT if concat else HEADS_MEAN, bias, act,
-                        p_act, seed_act, site_act, N, K, C, n)
-        ctx.save_for_backward(xl, a_s, a_d, coef, soft, soft_loop, alpha, alpha_loop, loop, Y if act != ACT_NONE else None)
-        ctx.nm, ctx.slope, ctx.p_att, ctx.seed_att, ctx.site_att = nm, float(slope), float(p_att), seed_att, site_att
-        ctx.act, ctx.p_act, ctx.has_bias, ctx.K, ctx.concat = act, float(p_act), bias is not None, K, bool(concat)
+        soft, alpha, soft_loop, alpha_loop = _heads_alloc(n, N, K, f32)
+        loop = None
+        if nm is None:
+            _lib.check(L.sgs_gat_alpha_heads_fwd(_ptr(a_s), _ptr(a_d), N, K, n, _ptr(graph.in_ptr), _ptr(graph.in_src), _ptr(graph.in_eid),
+                                                 slope, p_att, seed_att, site_att, _ptr(soft), _ptr(soft_loop), _ptr(alpha),
+                                                 _ptr(alpha_loop), _stream()), "sgs_gat_alpha_heads_fwd")
+        else:
+            loop = torch.empty(2, max(N, 1), **f32)                # wbar, 1 / cnt
+            _lib.check(L.sgs_gat_alpha_heads_edge_fwd(_ptr(a_s), _ptr(a_d), _ptr(nm.w, torch.float32), _ptr(coef, torch.float32), N, K, n,
+                                                      _ptr(graph.in_ptr), _ptr(graph.in_src), _ptr(graph.in_eid), slope, p_att, seed_att,
+                                                      site_att, _ptr(soft), _ptr(soft_loop), _ptr(alpha), _ptr(alpha_loop), loop[0].data_ptr(),
+                                                      loop[1].data_ptr(), _stream()), "sgs_gat_alpha_heads_edge_fwd")
+        Y = _heads_forward(ctx, xl, graph, alpha, alpha_loop, bias, K, concat, sm, epi)
+        ctx.save_for_backward(xl, a_s, a_d, coef, soft, soft_loop, alpha, alpha_loop, loop, Y if ctx.act != ACT_NONE else None)
+        ctx.nm = nm
         return Y
 
     @staticmethod
     def backward(ctx, dY):
         L = _lib.lib()
         xl, a_s, a_d, coef, soft, soft_loop, alpha, alpha_loop, loop, Y = ctx.saved_tensors
-        nm, K = ctx.nm, ctx.K
-        gr = nm.graph
-        N, D = xl.shape
-        C = D // K
-        n = gr.n_edges
+        nm, gr, K = ctx.nm, ctx.graph, ctx.K
+        N, n = xl.shape[0], gr.n_edges
         f32 = dict(dtype=torch.float32, device=xl.device)
-        dY = dY.contiguous()
-        dbias = None
-        if ctx.act != ACT_NONE and ctx.has_bias:
-            dZ, dbias = _act_bwd_colsum(dY, Y, ctx.act, ctx.p_act)
-        elif ctx.act != ACT_NONE:
-            dZ = torch.empty_like(dY)
-            _lib.check(L.sgs_act_bwd(_ptr(dY), _ptr(Y), dY.numel(), ctx.act, ctx.p_act, _ptr(dZ), _stream()), "sgs_act_bwd")
-        else:
-            dZ = dY
-            dbias = _colsum(dZ) if ctx.has_bias else None
-        dxl = _spmm_heads(dZ, gr.out_ptr, gr.out_dst, gr.out_eid, alpha, alpha_loop, HEADS_CONCAT if ctx.concat else HEADS_BROADCAST, None,
-                          ACT_NONE, 0.0, 0, 0, N, K, C, n)
-        galpha, gloop = torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32)
-        _lib.check(L.sgs_sddmm_csr_heads(_ptr(dZ), _ptr(xl), N, K, C, n, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid),
-                                         0 if ctx.concat else 1, _ptr(galpha), _ptr(gloop), _stream()), "sgs_sddmm_csr_heads")
+        dbias, dxl, galpha, gloop = _heads_backward_head(ctx, dY, Y, xl, alpha, alpha_loop, f32)
         g_edge, g_self, d_ad = torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32), torch.empty(N, K, **f32)
-        # the other layer's d w, if it has reported already, is added on the way out (no autograd add launch): see gat_edge_attr
-        second = nm._park_ok and nm._g_first is not None and nm._g_extra is None and nm._g_first.numel() == n
-        dw_add = nm._g_first.contiguous() if second else None
-        dw, dcoef = torch.empty(n, **f32), (torch.empty(K, **f32) if N > 0 else torch.zeros(K, **f32))
-        ws = workspace(L.sgs_gat_alpha_heads_edge_bwd_workspace_bytes(N, K), xl.device)
-        _lib.check(L.sgs_gat_alpha_heads_edge_bwd(_ptr(a_s), _ptr(a_d), _ptr(nm.w), _ptr(coef), loop[0].data_ptr(), loop[1].data_ptr(), N, K, n,
-                                                  _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid), ctx.slope, ctx.p_att, ctx.seed_att,
-                                                  ctx.site_att, _ptr(soft), _ptr(soft_loop), _ptr(galpha), _ptr(gloop), _ptr(dw_add), _ptr(g_edge),
-                                                  _ptr(g_self), _ptr(d_ad), _ptr(dw), _ptr(dcoef), ws.data_ptr(), ws.numel(), _stream()),
-                   "sgs_gat_alpha_heads_edge_bwd")
+        dcoef = g_handle = None
+        if nm is None:
+            _lib.check(L.sgs_gat_alpha_heads_bwd(_ptr(a_s), _ptr(a_d), N, K, n, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid), ctx.slope,
+                                                 ctx.p_att, ctx.seed_att, ctx.site_att, _ptr(soft), _ptr(soft_loop), _ptr(galpha), _ptr(gloop),
+                                                 _ptr(g_edge), _ptr(g_self), _ptr(d_ad), _stream()), "sgs_gat_alpha_heads_bwd")
+        else:
+            second, dw_add = _dw_to_add(nm, n)
+            dw, dcoef = torch.empty(n, **f32), (torch.empty(K, **f32) if N > 0 else torch.zeros(K, **f32))
+            ws = workspace(L.sgs_gat_alpha_heads_edge_bwd_workspace_bytes(N, K), xl.device)
+            _lib.check(L.sgs_gat_alpha_heads_edge_bwd(_ptr(a_s), _ptr(a_d), _ptr(nm.w), _ptr(coef), loop[0].data_ptr(), loop[1].data_ptr(), N, K,
+                                                      n, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid), ctx.slope, ctx.p_att, ctx.seed_att,
+                                                      ctx.site_att, _ptr(soft), _ptr(soft_loop), _ptr(galpha), _ptr(gloop), _ptr(dw_add),
+                                                      _ptr(g_edge), _ptr(g_self), _ptr(d_ad), _ptr(dw), _ptr(dcoef), ws.data_ptr(), ws.numel(),
+                                                      _stream()), "sgs_gat_alpha_heads_edge_bwd")
         d_as = torch.empty(N, K, **f32)
         _lib.check(L.sgs_edge_sum_by_row_heads(_ptr(g_edge), _ptr(g_self), N, K, n, _ptr(gr.out_ptr), _ptr(gr.out_eid), _ptr(d_as), _stream()),
                    "sgs_edge_sum_by_row_heads")
-        g_handle = None
-        if ctx.needs_input_grad[5]:
-            g_handle = _handle_grad(nm, dw)
-            if second and g_handle is None:
-                nm._extra_total = True
-        return dxl, d_as, d_ad, dbias, dcoef, g_handle, None, None, None, None, None, None, None, None, None, None, None
+        if nm is not None and ctx.needs_input_grad[5]:
+            g_handle = _report_dw(nm, dw, second)
+        return (dxl, d_as, d_ad, dbias, dcoef, g_handle) + (None,) * 6
 
 
 class _GATScoresHeads(torch.autograd.Function):
@@ -1899,8 +1892,9 @@ def gat_aggregate(xl, a_s, a_d, bias, graph: Graph, negative_slope=0.2, p_att=0.
     width = xl.shape[1] if concat else xl.shape[1] // heads
     if bias is not None and bias.numel() != width:
         raise RuntimeError(f"gat_aggregate: bias must have {width} elements")
-    return _GATAggregateHeads.apply(xl.contiguous(), a_s.contiguous(), a_d.contiguous(), bias, graph, heads, bool(concat), float(negative_slope),
-                                    float(p_att), int(seed_att), int(site_att), act, float(p_act), int(seed_act), int(site_act))
+    return _GATAggregateHeads.apply(xl.contiguous(), a_s.contiguous(), a_d.contiguous(), bias, None, None, None, graph, heads, bool(concat),
+                                    (float(negative_slope), float(p_att), int(seed_att), int(site_att)),
+                                    (act, float(p_act), int(seed_act), int(site_act)))
 
 
 def _gat_aggregate_edge(xl, a_s, a_d, bias, graph, negative_slope, p_att, seed_att, site_att, act, p_act, seed_act, site_act, heads, concat,
@@ -1918,9 +1912,10 @@ def _gat_aggregate_edge(xl, a_s, a_d, bias, graph, negative_slope, p_att, seed_a
     width = xl.shape[1] if concat else xl.shape[1] // heads
     if bias is not None and bias.numel() != width:
         raise RuntimeError(f"gat_aggregate: bias must have {width} elements")
-    return _GATAggregateEdge.apply(xl.contiguous(), a_s.reshape(N, heads).contiguous(), a_d.reshape(N, heads).contiguous(), bias,
-                                   edge_coef.reshape(heads).contiguous(), nm.handle, nm, heads, bool(concat), float(negative_slope), float(p_att),
-                                   int(seed_att), int(site_att), act, float(p_act), int(seed_act), int(site_act))
+    return _GATAggregateHeads.apply(xl.contiguous(), a_s.reshape(N, heads).contiguous(), a_d.reshape(N, heads).contiguous(), bias,
+                                    edge_coef.reshape(heads).contiguous(), nm.handle, nm, graph, heads, bool(concat),
+                                    (float(negative_slope), float(p_att), int(seed_att), int(site_att)),
+                                    (act, float(p_act), int(seed_act), int(site_act)))
 
 
 # ---- GATv2 attention (GATv2Conv: the non-linearity inside the dot product; csrc/gatv2.hip, sgs_gatv2_*)
@@ -1930,27 +1925,25 @@ class _GATv2Aggregate(torch.autograd.Function):
     by-destination softmax backward with its finishing sum, the by-source d xl).  `nm` None: no edge term."""
 
     @staticmethod
-    def forward(ctx, xl, xr, att, bias, le, handle, nm, graph, K, concat, slope, p_att, seed_att, site_att, act, p_act, seed_act, site_act):
+    def forward(ctx, xl, xr, att, bias, le, handle, nm, graph, K, concat, sm, epi):
         L = _lib.lib()
         N, D = xl.shape
         C = D // K
         n = graph.n_edges
+        slope, p_att, seed_att, site_att = sm
         f32 = dict(dtype=torch.float32, device=xl.device)
         edge = nm is not None and n > 0                        # without edges every loop carries weight 0: the term vanishes
-        soft, alpha = torch.empty(max(n, 1), K, **f32), torch.empty(max(n, 1), K, **f32)
-        soft_loop, alpha_loop = torch.empty(N, K, **f32), torch.empty(N, K, **f32)
+        soft, alpha, soft_loop, alpha_loop = _heads_alloc(n, N, K, f32)
         loop = torch.empty(2, max(N, 1), **f32) if edge else None                  # wbar, 1 / cnt
         _lib.check(L.sgs_gatv2_alpha_heads_fwd(_ptr(xl, torch.float32), _ptr(xr, torch.float32), _ptr(att, torch.float32),
                                                _ptr(nm.w, torch.float32) if edge else None, _ptr(le, torch.float32) if edge else None, N, K, C, n,
-                                               _ptr(graph.in_ptr), _ptr(graph.in_src), _ptr(graph.in_eid), float(slope), float(p_att), seed_att,
+                                               _ptr(graph.in_ptr), _ptr(graph.in_src), _ptr(graph.in_eid), slope, p_att, seed_att,
                                                site_att, _ptr(soft), _ptr(soft_loop), _ptr(alpha), _ptr(alpha_loop),
                                                loop[0].data_ptr() if edge else None, loop[1].data_ptr() if edge else None, _stream()),
                    "sgs_gatv2_alpha_heads_fwd")
-        Y = _spmm_heads(xl, graph.in_ptr, graph.in_src, graph.in_eid, alpha, alpha_loop, HEADS_CONCAT if concat else HEADS_MEAN, bias, act,
-                        p_act, seed_act, site_act, N, K, C, n)
-        ctx.save_for_backward(xl, xr, att, le, soft, soft_loop, alpha, alpha_loop, loop, Y if act != ACT_NONE else None)
-        ctx.nm, ctx.graph, ctx.edge, ctx.slope, ctx.p_att, ctx.seed_att, ctx.site_att = nm, graph, edge, float(slope), float(p_att), seed_att, site_att
-        ctx.act, ctx.p_act, ctx.has_bias, ctx.K, ctx.concat = act, float(p_act), bias is not None, K, bool(concat)
+        Y = _heads_forward(ctx, xl, graph, alpha, alpha_loop, bias, K, concat, sm, epi)
+        ctx.save_for_backward(xl, xr, att, le, soft, soft_loop, alpha, alpha_loop, loop, Y if ctx.act != ACT_NONE else None)
+        ctx.nm, ctx.edge = nm, edge
         return Y
 
     @staticmethod
@@ -1962,30 +1955,14 @@ class _GATv2Aggregate(torch.autograd.Function):
         C = D // K
         n = gr.n_edges
         f32 = dict(dtype=torch.float32, device=xl.device)
-        dY = dY.contiguous()
-        dbias = None
-        if ctx.act != ACT_NONE and ctx.has_bias:
-            dZ, dbias = _act_bwd_colsum(dY, Y, ctx.act, ctx.p_act)
-        elif ctx.act != ACT_NONE:
-            dZ = torch.empty_like(dY)
-            _lib.check(L.sgs_act_bwd(_ptr(dY), _ptr(Y), dY.numel(), ctx.act, ctx.p_act, _ptr(dZ), _stream()), "sgs_act_bwd")
-        else:
-            dZ = dY
-            dbias = _colsum(dZ) if ctx.has_bias else None
-        dxl = _spmm_heads(dZ, gr.out_ptr, gr.out_dst, gr.out_eid, alpha, alpha_loop, HEADS_CONCAT if ctx.concat else HEADS_BROADCAST, None,
-                          ACT_NONE, 0.0, 0, 0, N, K, C, n)
-        galpha, gloop = torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32)
-        _lib.check(L.sgs_sddmm_csr_heads(_ptr(dZ), _ptr(xl), N, K, C, n, _ptr(gr.in_ptr), _ptr(gr.in_src), _ptr(gr.in_eid),
-                                         0 if ctx.concat else 1, _ptr(galpha), _ptr(gloop), _stream()), "sgs_sddmm_csr_heads")
+        dbias, dxl, galpha, gloop = _heads_backward_head(ctx, dY, Y, xl, alpha, alpha_loop, f32)
         g_logit, g_loop = torch.empty(max(n, 1), K, **f32), torch.empty(N, K, **f32)
         dxr = torch.empty_like(xr)
         datt = torch.empty(D, **f32) if N > 0 else torch.zeros(D, **f32)
         dle = dw = dw_add = None
         second = False
         if edge:
-            # the other layer's d w, if it has reported already, is added on the way out (no autograd add launch): see gat_edge_attr
-            second = nm._park_ok and nm._g_first is not None and nm._g_extra is None and nm._g_first.numel() == n
-            dw_add = nm._g_first.contiguous() if second else None
+            second, dw_add = _dw_to_add(nm, n)
             dw, dle = torch.empty(n, **f32), torch.empty(D, **f32)
         elif le is not None:
             dle = torch.zeros(D, **f32)
@@ -2002,13 +1979,8 @@ class _GATv2Aggregate(torch.autograd.Function):
                    "sgs_gatv2_dxl_heads")
         g_handle = None
         if ctx.needs_input_grad[5]:
-            if edge:
-                g_handle = _handle_grad(nm, dw)
-                if second and g_handle is None:
-                    nm._extra_total = True
-            else:
-                g_handle = _handle_grad(nm, torch.zeros(n, **f32))
-        return (dxl, dxr, datt, dbias, dle, g_handle) + (None,) * 12
+            g_handle = _report_dw(nm, dw, second) if edge else _handle_grad(nm, torch.zeros(n, **f32))
+        return (dxl, dxr, datt, dbias, dle, g_handle) + (None,) * 6
 
 
 def gatv2_aggregate(xl, xr, att, bias, graph: Graph, negative_slope=0.2, p_att=0.0, seed_att=0, site_att=0, act=ACT_NONE, p_act=0.0,
@@ -2039,8 +2011,8 @@ def gatv2_aggregate(xl, xr, att, bias, graph: Graph, negative_slope=0.2, p_att=0
             raise RuntimeError(f"gatv2_aggregate: lin_edge must be float32 with {D} elements")
         handle, le = nm.handle, lin_edge.reshape(D).contiguous()
     return _GATv2Aggregate.apply(xl.contiguous(), xr.contiguous(), att.reshape(D).contiguous(), bias, le, handle, nm, graph, heads, bool(concat),
-                                 float(negative_slope), float(p_att), int(seed_att), int(site_att), act, float(p_act), int(seed_act),
-                                 int(site_act))
+                                 (float(negative_slope), float(p_att), int(seed_att), int(site_att)),
+                                 (act, float(p_act), int(seed_act), int(site_act)))
 
 
 # ---- GINE aggregation (GINEConv, edge_dim = 1 with the edge weight as the attribute; csrc/gine.hip, sgs_gine_aggregate_*)
@@ -2050,8 +2022,7 @@ def edge_attr(graph: Graph, w=None) -> EdgeAttr:
     if w is not None:
         return gat_edge_attr(graph, w)
     nm = EdgeAttr()
-    nm.graph, nm.w, nm.handle, nm._park_ok, nm._extra_total = graph, None, None, False, False
-    nm._g_first = nm._g_extra = None
+    nm.graph = graph
     return nm
 
 
@@ -2088,9 +2059,7 @@ class _GINEAggregate(torch.autograd.Function):
         dw = dw_add = None
         second = False
         if want_w:
-            # the other layer's d w, if it has reported already, is added on the way out (no autograd add launch): see gat_edge_attr
-            second = nm._park_ok and nm._g_first is not None and nm._g_extra is None and nm._g_first.numel() == n
-            dw_add = nm._g_first.contiguous() if second else None
+            second, dw_add = _dw_to_add(nm, n)
             dw = torch.empty(n, **f32)
         ws = workspace(L.sgs_gine_aggregate_bwd_workspace_bytes(N, D), x.device) if want_ab else None
         _lib.check(L.sgs_gine_aggregate_bwd(_ptr(x), _ptr(dZ, torch.float32), _ptr(nm.w), _ptr(a), _ptr(b), ctx.diag, N, D, n, _ptr(gr.out_ptr),
@@ -2098,11 +2067,7 @@ class _GINEAggregate(torch.autograd.Function):
                                             dab[0].data_ptr() if want_ab else None, dab[1].data_ptr() if want_ab else None,
                                             ws.data_ptr() if want_ab else None, ws.numel() if want_ab else 0, _stream()),
                    "sgs_gine_aggregate_bwd")
-        g_handle = None
-        if want_w:
-            g_handle = _handle_grad(nm, dw)
-            if second and g_handle is None:
-                nm._extra_total = True
+        g_handle = _report_dw(nm, dw, second) if want_w else None
         return dx, (dab[0] if want_ab else None), (dab[1] if want_ab else None), g_handle, None, None
 
 
@@ -2154,7 +2119,7 @@ def mean_norm(graph: Graph) -> Norm:
     L = _lib.lib()
     dev = graph.edge_index.device
     nm = Norm()
-    nm.graph, nm.w, nm.handle, nm.dis, nm.loopw, nm.what_loop = graph, None, None, None, None, None
+    nm.graph = graph
     ne = max(graph.n_edges, 1)
     nm.what_in = torch.empty(ne, dtype=torch.float32, device=dev)
     nm.what_out = torch.empty(ne, dtype=torch.float32, device=dev)
@@ -2170,7 +2135,7 @@ def sum_norm(graph: Graph, diag: float = 1.0) -> Norm:
         return nm[1]
     dev = graph.edge_index.device
     nm = Norm()
-    nm.graph, nm.w, nm.handle, nm.dis, nm.loopw = graph, None, None, None, None
+    nm.graph = graph
     ne = max(graph.n_edges, 1)
     nm.what_in = torch.ones(ne, dtype=torch.float32, device=dev)
     nm.what_out = nm.what_in
@@ -2299,15 +2264,9 @@ class _GCNLayer(torch.autograd.Function):
         x, W, xl, Y = ctx.saved_tensors
         N, D = xl.shape
         dY = dY.contiguous()
-        dx = dW = g = dbias = None
+        dx = dW = g = None
         want_db = ctx.has_bias and ctx.needs_input_grad[3]
-        if ctx.act != ACT_NONE and want_db:
-            dZ, dbias = _act_bwd_colsum(dY, Y, ctx.act, ctx.p)
-        elif ctx.act != ACT_NONE:
-            dZ = torch.empty_like(dY)
-            _lib.check(L.sgs_act_bwd(_ptr(dY), _ptr(Y), dY.numel(), ctx.act, float(ctx.p), _ptr(dZ), _stream()), "sgs_act_bwd")
-        else:
-            dZ = dY
+        dZ, dbias = _grad_through_act(dY, Y, ctx.act, ctx.p, want_db, colsum_now=False)
         need_x, need_W = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if need_x or need_W:
             dxl = _spmm(dZ, gr.out_ptr, gr.out_dst, nm.what_out, nm.what_loop, None, ACT_NONE, 0.0, 0, 0, N, D, gr.n_edges)
@@ -2411,12 +2370,8 @@ class _GCN2(torch.autograd.Function):
         if need_W2:
             dW2 = _dyt_x(dxl2, h, W2.shape, leaf=(ctx, 3))
         if want_1 and not ctx.fused:
-            dZ1h = dxl2 @ W2
-            if need_b1:
-                dZ1, db1 = _act_bwd_colsum(dZ1h, h, ctx.act, ctx.p)
-            else:
-                dZ1 = torch.empty_like(dZ1h)
-                _lib.check(L.sgs_act_bwd(_ptr(dZ1h), _ptr(h), dZ1h.numel(), ctx.act, float(ctx.p), _ptr(dZ1), _stream()), "sgs_act_bwd")
+            dZ1h = dxl2 @ W2         # (not _grad_through_act: this product always goes through the activation kernel, ACT_NONE included)
+            dZ1, db1 = _act_bwd_colsum(dZ1h, h, ctx.act, ctx.p) if need_b1 else (_act_bwd(dZ1h, h, ctx.act, ctx.p), None)
         g2 = sddmm(dZ2, xl2, C) if need_g else None
         if need_b2 and db2 is None:
             db2 = _colsum(dZ2)
@@ -2781,7 +2736,7 @@ def _cheb_norm_forward(graph: Graph, w):
     L = _lib.lib()
     dev = graph.edge_index.device
     nm = Norm()
-    nm.graph, nm.w, nm.handle, nm.loopw, nm.what_loop = graph, w, None, None, None
+    nm.graph, nm.w = graph, w
     ne, Nn = max(graph.n_edges, 1), max(graph.N, 1)
     sizes = [Nn, ne, ne]
     offs = [0]
@@ -2811,8 +2766,7 @@ class _ChebNorm(torch.autograd.Function):
         nm, gr = ctx.nm, ctx.nm.graph
         g = g.contiguous()
         n = gr.n_edges
-        extra = getattr(nm, "_g_extra", None)          # the other layer's gradient, parked by _handle_grad: summed on read
-        nm._g_first = nm._g_extra = None
+        extra, _, _ = _take_parked(nm)                 # the other layer's gradient (_handle_grad): summed on read
         if extra is not None and extra.numel() != g.numel():
             g, extra = g + extra, None
         dw = torch.empty(n, dtype=torch.float32, device=g.device)
@@ -2897,17 +2851,8 @@ class _ChebConv(torch.autograd.Function):
         x, Wcat, B, out = ctx.saved_tensors
         N, D = dY.shape
         dY = dY.contiguous()
-        dx = dW = dbias = g = None
-        want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.act != ACT_NONE and want_db:
-            G, dbias = _act_bwd_colsum(dY, out, ctx.act, ctx.p)
-        elif ctx.act != ACT_NONE:
-            G = torch.empty_like(dY)
-            _lib.check(L.sgs_act_bwd(_ptr(dY), _ptr(out), dY.numel(), ctx.act, float(ctx.p), _ptr(G), _stream()), "sgs_act_bwd")
-        else:
-            G = dY
-        if want_db and dbias is None:
-            dbias = _colsum(G)
+        dx = dW = g = None
+        G, dbias = _grad_through_act(dY, out, ctx.act, ctx.p, ctx.has_bias and ctx.needs_input_grad[2])
         need_x, need_W = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_h = ctx.has_handle and ctx.needs_input_grad[3]
         last = K - 1 if (need_x or need_W) else (K - 2 if need_h else 0)       # highest U_k anything asks for

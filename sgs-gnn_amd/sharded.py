@@ -296,14 +296,9 @@ class _BiasAct(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dY):
-        L = _lib.lib()
         (Y,) = ctx.saved_tensors
-        dY = dY.contiguous()
-        if ctx.act != ops.ACT_NONE:
-            dZ = torch.empty_like(dY)
-            _lib.check(L.sgs_act_bwd(ops._ptr(dY), ops._ptr(Y), dY.numel(), ctx.act, ctx.p, ops._ptr(dZ), ops._stream()), "sgs_act_bwd")
-        else:
-            dZ = dY
+        # (the bias gradient as a column sum of its own, as ever: asked for with the activation it would become one fused pass)
+        dZ, _ = ops._grad_through_act(dY.contiguous(), Y, ctx.act, ctx.p, False)
         return dZ, (ops._colsum(dZ) if ctx.has_bias else None), None, None, None, None
 
 
@@ -669,14 +664,10 @@ class _BiasActRows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dY):
-        L = _lib.lib()
         (Y,) = ctx.saved_tensors
         dY = dY.contiguous()
-        if ctx.act != ops.ACT_NONE and dY.numel() > 0:
-            dZ = torch.empty_like(dY)
-            _lib.check(L.sgs_act_bwd(ops._ptr(dY), ops._ptr(Y), dY.numel(), ctx.act, ctx.p, ops._ptr(dZ), ops._stream()), "sgs_act_bwd")
-        else:
-            dZ = dY
+        # (not ops._grad_through_act: a rank's row block may be empty, and then neither kernel is called)
+        dZ = ops._act_bwd(dY, Y, ctx.act, ctx.p) if ctx.act != ops.ACT_NONE and dY.numel() > 0 else dY
         db = None
         if ctx.has_bias:
             db = ops._colsum(dZ) if dZ.shape[0] > 0 else torch.zeros(dZ.shape[1], dtype=dZ.dtype, device=dZ.device)
