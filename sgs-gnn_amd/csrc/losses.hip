@@ -162,11 +162,55 @@ __global__ void publish_words(const int32_t* __restrict__ src, int n, const uint
     }
 }
 
-// ---------------------------------------------------------------- masked cross entropy
-// rowloss[i] = lse_i - logit_i[y_i] on train rows (0 elsewhere); row_lse kept for backward.
-// One wave's row (i, all 64 lanes); ce_rows and the merged forward launch (hybrid_fwd_pair) share it.
+// ---------------------------------------------------------------- masked cross entropy, plain (kW = false) and class-weighted / label-smoothed (kW = true)
+// F.cross_entropy(logits[mask], y[mask], weight = w, label_smoothing = eps, reduction = "mean"); w == nullptr: all ones.
+//   row_i = (1 - eps) w[y_i] (lse_i - x_i[y_i]) + (eps / C) sum_c w_c (lse_i - x_ic)        on train rows, 0 elsewhere; row_lse kept for backward
+//   den   = sum over train rows of w[y_i];   loss = sum_i row_i / den, nan when den == 0 (torch: the hard term's own 0 / 0)
+//   dx_ic = g / den [ (1 - eps) w[y_i] (softmax_ic - [c == y_i]) + (eps / C) (W softmax_ic - w_c) ],  W = sum_c w_c;  nan on train rows when den == 0
+// The plain criterion is w = 1, eps = 0 with the terms that vanish never formed: row_i = lse_i - x_i[y_i], den = #train rows (an int32
+// word; 0 / 0 = nan, as torch's mean over an empty selection), dx_ic = g / #train (softmax_ic - [c == y_i]).
+// The smoothing sum is taken as sum_c w_c (lse - x_c) -- one wave reduction more than the plain row -- and not as W lse - sum_c w_c x_c, which
+// needs two and W.  eps == 0 skips it.  A label outside [0, C) on a train row is outside the contract; only the weighted criterion indexes
+// by it (`class_weight`), and it reads nothing out of bounds there (weight 0, no label term).
+//
+// CeNorm<kW>: the divisor of the mean and what the weighted criterion alone reads.  A kernel takes it by value as its LAST argument: the
+// plain one is empty, so the plain instantiations keep the plain kernels' argument layout.
+template <bool kW>
+struct CeNorm;
+template <>
+struct CeNorm<false> {
+    using Word = int;                                   // the stored divisor: n_rows, the number of train rows
+    static __host__ __device__ CeNorm make(const float*, float, const int64_t*, int64_t) { return CeNorm{}; }
+    __device__ __forceinline__ int row(int64_t) const { return 1; }                          // what a train row adds to the divisor
+    static __device__ __forceinline__ float mean(float sum, float n) { return sum / n; }     // 0/0 = nan, as torch's mean over an empty selection
+    static __device__ __forceinline__ float scale(float gl, const int* n_rows) { return gl / static_cast<float>(n_rows[0]); }
+};
+template <>
+struct CeNorm<true> {
+    using Word = float;                                 // den, the sum of the train rows' class weights
+    const float* __restrict__ weight;
+    float eps;
+    const int64_t* __restrict__ y;
+    int64_t C;
+    static __host__ __device__ CeNorm make(const float* weight, float eps, const int64_t* y, int64_t C) { return CeNorm{weight, eps, y, C}; }
+    __device__ __forceinline__ float of_label(int64_t yi) const {
+        if (yi < 0 || yi >= C) return 0.f;
+        return weight ? weight[yi] : 1.f;
+    }
+    __device__ __forceinline__ float of_class(int64_t c) const { return weight ? weight[c] : 1.f; }
+    __device__ __forceinline__ float row(int64_t i) const { return of_label(y[i]); }
+    static __device__ __forceinline__ float mean(float sum, float den) { return (den == 0.f) ? NAN : sum / den; }
+    static __device__ __forceinline__ float scale(float gl, const float* den) {
+        const float d = den[0];
+        return (d == 0.f) ? NAN : gl / d;
+    }
+};
+
+// rowloss[i] and row_lse[i] of one wave's row (i, all 64 lanes); ce_rows and the merged forward launch (hybrid_fwd_pair) share it.
+template <bool kW>
 __device__ __forceinline__ void ce_row(int64_t i, int lane, const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
-                                       const uint8_t* __restrict__ mask, float* __restrict__ row_lse, float* __restrict__ rowloss) {
+                                       const uint8_t* __restrict__ mask, const CeNorm<kW>& cn, float* __restrict__ row_lse,
+                                       float* __restrict__ rowloss) {
     if (i >= N) return;
     if (!mask[i]) {
         if (lane == 0) { rowloss[i] = 0.f; row_lse[i] = 0.f; }
@@ -179,50 +223,120 @@ __device__ __forceinline__ void ce_row(int64_t i, int lane, const float* __restr
     for (int64_t c = lane; c < C; c += 64) s += expf(logits[i * C + c] - mx);
     s = wave_sum_all(s);
     const float lse = mx + logf(s);
-    if (lane == 0) {
-        row_lse[i] = lse;
-        rowloss[i] = lse - logits[i * C + y[i]];
+    if constexpr (!kW) {
+        if (lane == 0) {
+            row_lse[i] = lse;
+            rowloss[i] = lse - logits[i * C + y[i]];
+        }
+    } else {
+        const float eps = cn.eps;
+        float sm = 0.f;
+        if (eps != 0.f) {
+            for (int64_t c = lane; c < C; c += 64) sm += cn.of_class(c) * (lse - logits[i * C + c]);
+            sm = wave_sum_all(sm);
+        }
+        if (lane == 0) {
+            const int64_t yi = y[i];
+            const float hard = (yi >= 0 && yi < C) ? cn.of_label(yi) * (lse - logits[i * C + yi]) : 0.f;
+            row_lse[i] = lse;
+            rowloss[i] = (eps != 0.f) ? (1.f - eps) * hard + (eps / static_cast<float>(C)) * sm : hard;
+        }
     }
 }
+template <bool kW>
 __global__ void __launch_bounds__(kT) ce_rows(const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
-                                             const uint8_t* __restrict__ mask, float* __restrict__ row_lse,
-                                             float* __restrict__ rowloss) {
-    ce_row((static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6, threadIdx.x & 63, logits, N, C, y, mask, row_lse, rowloss);
+                                             const uint8_t* __restrict__ mask, float* __restrict__ row_lse, float* __restrict__ rowloss,
+                                             const CeNorm<kW> cn) {
+    ce_row<kW>((static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6, threadIdx.x & 63, logits, N, C, y, mask, cn, row_lse, rowloss);
 }
 
-// One block: loss = sum(rowloss) / #train ; n_rows[0] = #train.
+// One block of 1024: norm[0] = the divisor (recomputed from the mask, and from w and y when weighted: no [N] buffer), loss = sum(rowloss) / norm[0].
+template <bool kW>
 __global__ void __launch_bounds__(1024) ce_final(const float* __restrict__ rowloss, const uint8_t* __restrict__ mask, int64_t N,
-                                                float* __restrict__ loss, int* __restrict__ n_rows) {
+                                                float* __restrict__ loss, typename CeNorm<kW>::Word* __restrict__ norm, const CeNorm<kW> cn) {
     __shared__ float red[16];
-    __shared__ int redi[16];
     float acc = 0.f;
-    int cnt = 0;
-    for (int64_t i = threadIdx.x; i < N; i += 1024) { acc += rowloss[i]; cnt += mask[i] ? 1 : 0; }
+    typename CeNorm<kW>::Word dn = 0;
+    for (int64_t i = threadIdx.x; i < N; i += 1024) {
+        acc += rowloss[i];
+        dn += mask[i] ? cn.row(i) : 0;
+    }
     const float r = block_sum(acc, red);
-    cnt = wave_sum_int_all(cnt);
-    if ((threadIdx.x & 63) == 0) redi[threadIdx.x >> 6] = cnt;
-    __syncthreads();
+    if constexpr (kW) {
+        dn = block_sum(dn, red);
+    } else {                                            // the count stays an integer: no N < 2^24 limit on the plain entry
+        __shared__ int redi[16];
+        dn = wave_sum_int_all(dn);
+        if ((threadIdx.x & 63) == 0) redi[threadIdx.x >> 6] = dn;
+        __syncthreads();
+        dn = 0;
+        if (threadIdx.x == 0)
+            for (int w = 0; w < 16; ++w) dn += redi[w];
+    }
     if (threadIdx.x == 0) {
-        int n = 0;
-        for (int w = 0; w < 16; ++w) n += redi[w];
-        n_rows[0] = n;
-        loss[0] = r / static_cast<float>(n);     // 0/0 = nan, as torch's mean over an empty selection
+        norm[0] = dn;
+        loss[0] = CeNorm<kW>::mean(r, static_cast<float>(dn));
     }
 }
 
+// W = sum_c w_c in every thread of the block, in a fixed order (the same value in every block).  Every thread of the block must call it;
+// the first kThreads (a multiple of 64) form the sum.
+template <int kThreads>
+__device__ __forceinline__ float block_weight_sum(const float* __restrict__ weight, int64_t C, float* red) {
+    if (threadIdx.x < kThreads) {
+        float v = 0.f;
+        for (int64_t c = threadIdx.x; c < C; c += kThreads) v += weight[c];
+        v = wave_sum_all(v);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    }
+    __syncthreads();
+    float r = 0.f;
+#pragma unroll
+    for (int k = 0; k < kThreads / 64; ++k) r += red[k];
+    return r;
+}
+
+// One entry of the gradient above (a train row's), scaled by CeNorm<kW>::scale(grad_loss[0], norm); W = sum_c w_c (read when weighted and
+// eps != 0).
+template <bool kW>
+__device__ __forceinline__ float ce_grad(const CeNorm<kW>& cn, float x, float lse, int64_t yi, int64_t c, int64_t C, float W,
+                                         const float* __restrict__ grad_loss, const typename CeNorm<kW>::Word* __restrict__ norm) {
+    if constexpr (!kW) {
+        const float sm = expf(x - lse);
+        return (sm - (yi == c ? 1.f : 0.f)) * CeNorm<kW>::scale(grad_loss[0], norm);
+    } else {
+        const float sc = CeNorm<kW>::scale(grad_loss[0], norm);
+        const float sm = expf(x - lse);
+        const float hard = cn.of_label(yi) * (sm - (yi == c ? 1.f : 0.f));
+        if (cn.eps == 0.f) return hard * sc;
+        return ((1.f - cn.eps) * hard + (cn.eps * (1.f / static_cast<float>(C))) * (W * sm - cn.of_class(c))) * sc;
+    }
+}
+
+// dlogits = (kAcc: +=) the gradient above.  Off the train rows the plain writing form stores a computed 0, the weighted one stores 0 and
+// leaves, the accumulating forms leave without touching memory.
+template <bool kW, bool kAcc>
 __global__ void __launch_bounds__(kT) ce_bwd(const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
                                             const uint8_t* __restrict__ mask, const float* __restrict__ row_lse,
-                                            const int* __restrict__ n_rows, const float* __restrict__ grad_loss,
-                                            float* __restrict__ dlogits) {
+                                            const typename CeNorm<kW>::Word* __restrict__ norm, const float* __restrict__ grad_loss,
+                                            float* __restrict__ dlogits, const CeNorm<kW> cn) {
+    float W = static_cast<float>(C);
+    if constexpr (kW) {
+        __shared__ float red[kT / 64];
+        if (cn.eps != 0.f && cn.weight) W = block_weight_sum<kT>(cn.weight, C, red);        // (uniform branch: every thread of every block takes it or none)
+    }
     const int64_t idx = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
     if (idx >= N * C) return;
     const int64_t i = idx / C, c = idx - i * C;
     float g = 0.f;
     if (mask[i]) {
-        const float sm = expf(logits[idx] - row_lse[i]);
-        g = (sm - (y[i] == c ? 1.f : 0.f)) * (grad_loss[0] / static_cast<float>(n_rows[0]));
+        g = ce_grad<kW>(cn, logits[idx], row_lse[i], y[i], c, C, W, grad_loss, norm);
+    } else if (kW || kAcc) {
+        if (!kAcc) dlogits[idx] = 0.f;
+        return;
     }
-    dlogits[idx] = g;
+    if (kAcc) dlogits[idx] += g;
+    else dlogits[idx] = g;
 }
 
 // ---------------------------------------------------------------- edge regularisers
@@ -293,197 +407,59 @@ __global__ void __launch_bounds__(kT) reg_fwd_partial(const float* __restrict__ 
     }
 }
 
-// out[0] = reg1 (0 unless sum(labels) > 1), out[1] = reg2, out[2] = #valid, out[3] = sum labels,
-// out[4] = coef1 * reg1 + coef2 * reg2
+// The four column sums of the per-block partials part[4 b + k], for one finishing block of kT threads: `gather` is a thread's share
+// (blocks threadIdx.x, threadIdx.x + kT, ...), `reduce` the block's four sums, taken in column order (valid in thread 0).
+struct RegSums {
+    float bce = 0.f, sq = 0.f, nv = 0.f, nl = 0.f;
+    __device__ __forceinline__ void gather(const float* __restrict__ part, int64_t nblk) {
+        for (int64_t b = threadIdx.x; b < nblk; b += kT) {
+            bce += part[4 * b]; sq += part[4 * b + 1]; nv += part[4 * b + 2]; nl += part[4 * b + 3];
+        }
+    }
+    __device__ __forceinline__ void reduce(float* red) {
+        bce = block_sum(bce, red); sq = block_sum(sq, red); nv = block_sum(nv, red); nl = block_sum(nl, red);
+    }
+    // out[0] = reg1 (0 unless sum(labels) > 1), out[1] = reg2, out[2] = #valid, out[3] = sum labels, out[4] = coef1 * reg1 + coef2 * reg2
+    __device__ __forceinline__ void store(int64_t q, float coef1, float coef2, float* __restrict__ out) const {
+        const float reg1 = (nl > 1.f) ? bce / nv : 0.f;             // training_hybrid.py:125-128
+        const float reg2 = sq / static_cast<float>(q);
+        out[0] = reg1; out[1] = reg2; out[2] = nv; out[3] = nl;
+        out[4] = coef1 * reg1 + coef2 * reg2;
+    }
+};
+
 __global__ void __launch_bounds__(kT) reg_fwd_final(const float* __restrict__ part, int64_t nblk, int64_t q, float coef1, float coef2,
                                                    float* __restrict__ out) {
     __shared__ float red[kT / 64];
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    for (int64_t b = threadIdx.x; b < nblk; b += kT) {
-        a0 += part[4 * b]; a1 += part[4 * b + 1]; a2 += part[4 * b + 2]; a3 += part[4 * b + 3];
-    }
-    const float r0 = block_sum(a0, red), r1 = block_sum(a1, red), r2 = block_sum(a2, red), r3 = block_sum(a3, red);
-    if (threadIdx.x == 0) {
-        const float reg1 = (r3 > 1.f) ? r0 / r2 : 0.f;             // training_hybrid.py:125-128
-        const float reg2 = r1 / static_cast<float>(q);
-        out[0] = reg1; out[1] = reg2; out[2] = r2; out[3] = r3;
-        out[4] = coef1 * reg1 + coef2 * reg2;
-    }
+    RegSums s;
+    s.gather(part, nblk);
+    s.reduce(red);
+    if (threadIdx.x == 0) s.store(q, coef1, coef2, out);
 }
 
 // The learned branch's whole loss in one finishing launch (training_hybrid.py:105-133): the cross entropy's mean over the train rows
-// (as ce_final) and the two regularisers (as reg_fwd_final);  out[0..4] as reg_fwd_final, out[5] = cross entropy,
-// out[6] = out[5] + out[4] = the loss.
+// (as ce_final<kW>, in a block of kT) and the two regularisers (as reg_fwd_final: same partials, same order);  out[0..4] as reg_fwd_final,
+// out[5] = cross entropy, out[6] = out[5] + out[4] = the loss, norm[0] = the cross entropy's divisor.
+template <bool kW>
 __global__ void __launch_bounds__(kT) hybrid_loss_final(const float* __restrict__ part, int64_t nblk, int64_t q, float coef1, float coef2,
                                                        const float* __restrict__ rowloss, const uint8_t* __restrict__ mask, int64_t N,
-                                                       float* __restrict__ out, int* __restrict__ n_rows) {
+                                                       float* __restrict__ out, typename CeNorm<kW>::Word* __restrict__ norm,
+                                                       const CeNorm<kW> cn) {
     __shared__ float red[kT / 64];
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, ce = 0.f, cnt = 0.f;
-    for (int64_t b = threadIdx.x; b < nblk; b += kT) {
-        a0 += part[4 * b]; a1 += part[4 * b + 1]; a2 += part[4 * b + 2]; a3 += part[4 * b + 3];
-    }
-    for (int64_t i = threadIdx.x; i < N; i += kT) { ce += rowloss[i]; cnt += mask[i] ? 1.f : 0.f; }     // (counts < 2^24: exact in fp32)
-    const float r0 = block_sum(a0, red), r1 = block_sum(a1, red), r2 = block_sum(a2, red), r3 = block_sum(a3, red);
-    const float rc = block_sum(ce, red), rn = block_sum(cnt, red);
-    if (threadIdx.x == 0) {
-        const float reg1 = (r3 > 1.f) ? r0 / r2 : 0.f;
-        const float reg2 = r1 / static_cast<float>(q);
-        out[0] = reg1; out[1] = reg2; out[2] = r2; out[3] = r3;
-        out[4] = coef1 * reg1 + coef2 * reg2;
-        out[5] = rc / rn;                                  // 0/0 = nan, as torch's mean over an empty selection
-        out[6] = out[5] + out[4];
-        n_rows[0] = static_cast<int>(rn);
-    }
-}
-
-// ce_bwd on top of a gradient that is already there: dlogits += (softmax - onehot) g / #train on the train rows.
-__global__ void __launch_bounds__(kT) ce_bwd_acc(const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
-                                                const uint8_t* __restrict__ mask, const float* __restrict__ row_lse,
-                                                const int* __restrict__ n_rows, const float* __restrict__ grad_loss,
-                                                float* __restrict__ dlogits) {
-    const int64_t idx = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-    if (idx >= N * C) return;
-    const int64_t i = idx / C, c = idx - i * C;
-    if (!mask[i]) return;
-    const float sm = expf(logits[idx] - row_lse[i]);
-    dlogits[idx] += (sm - (y[i] == c ? 1.f : 0.f)) * (grad_loss[0] / static_cast<float>(n_rows[0]));
-}
-
-// ---------------------------------------------------------------- class-weighted, label-smoothed masked cross entropy
-// F.cross_entropy(logits[mask], y[mask], weight = w, label_smoothing = eps, reduction = "mean"); w == nullptr: all ones.
-//   row_i = (1 - eps) w[y_i] (lse_i - x_i[y_i]) + (eps / C) sum_c w_c (lse_i - x_ic)        on train rows, 0 elsewhere
-//   den   = sum over train rows of w[y_i];   loss = sum_i row_i / den, nan when den == 0 (torch: the hard term's own 0 / 0)
-//   dx_ic = g / den [ (1 - eps) w[y_i] (softmax_ic - [c == y_i]) + (eps / C) (W softmax_ic - w_c) ],  W = sum_c w_c;  nan on train rows when den == 0
-// The smoothing sum is taken as sum_c w_c (lse - x_c) -- one wave reduction more than ce_rows -- and not as W lse - sum_c w_c x_c, which
-// needs two and W.  eps == 0 skips it.  A label outside [0, C) on a train row is outside the contract;
-// it reads nothing out of bounds here (weight 0, no label term).
-__device__ __forceinline__ float class_weight(const float* __restrict__ weight, int64_t yi, int64_t C) {
-    if (yi < 0 || yi >= C) return 0.f;
-    return weight ? weight[yi] : 1.f;
-}
-
-__device__ __forceinline__ void ce_row_w(int64_t i, int lane, const float* __restrict__ logits, int64_t N, int64_t C,
-                                         const int64_t* __restrict__ y, const uint8_t* __restrict__ mask, const float* __restrict__ weight,
-                                         float eps, float* __restrict__ row_lse, float* __restrict__ rowloss) {
-    if (i >= N) return;
-    if (!mask[i]) {
-        if (lane == 0) { rowloss[i] = 0.f; row_lse[i] = 0.f; }
-        return;
-    }
-    float mx = -INFINITY;
-    for (int64_t c = lane; c < C; c += 64) mx = fmaxf(mx, logits[i * C + c]);
-    mx = wave_max_all(mx);
-    float s = 0.f;
-    for (int64_t c = lane; c < C; c += 64) s += expf(logits[i * C + c] - mx);
-    s = wave_sum_all(s);
-    const float lse = mx + logf(s);
-    float sm = 0.f;
-    if (eps != 0.f) {
-        for (int64_t c = lane; c < C; c += 64) sm += (weight ? weight[c] : 1.f) * (lse - logits[i * C + c]);
-        sm = wave_sum_all(sm);
-    }
-    if (lane == 0) {
-        const int64_t yi = y[i];
-        const float wy = class_weight(weight, yi, C);
-        const float hard = (yi >= 0 && yi < C) ? wy * (lse - logits[i * C + yi]) : 0.f;
-        row_lse[i] = lse;
-        rowloss[i] = (eps != 0.f) ? (1.f - eps) * hard + (eps / static_cast<float>(C)) * sm : hard;
-    }
-}
-__global__ void __launch_bounds__(kT) ce_rows_w(const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
-                                               const uint8_t* __restrict__ mask, const float* __restrict__ weight, float eps,
-                                               float* __restrict__ row_lse, float* __restrict__ rowloss) {
-    ce_row_w((static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6, threadIdx.x & 63, logits, N, C, y, mask, weight, eps, row_lse, rowloss);
-}
-
-// One block: den[0] = sum of w[y_i] over the train rows (recomputed from w, y and the mask: no [N] buffer), loss = sum(rowloss) / den.
-__global__ void __launch_bounds__(1024) ce_final_w(const float* __restrict__ rowloss, const uint8_t* __restrict__ mask,
-                                                  const int64_t* __restrict__ y, const float* __restrict__ weight, int64_t N, int64_t C,
-                                                  float* __restrict__ loss, float* __restrict__ den) {
-    __shared__ float red[16];
-    float acc = 0.f, dn = 0.f;
-    for (int64_t i = threadIdx.x; i < N; i += 1024) {
-        acc += rowloss[i];
-        if (mask[i]) dn += class_weight(weight, y[i], C);
-    }
-    const float r = block_sum(acc, red);
-    const float d = block_sum(dn, red);
-    if (threadIdx.x == 0) {
-        den[0] = d;
-        loss[0] = (d == 0.f) ? NAN : r / d;
-    }
-}
-
-// W = sum_c w_c in every thread of the block, in a fixed order (the same value in every block).  All kT threads must call it.
-__device__ __forceinline__ float block_weight_sum(const float* __restrict__ weight, int64_t C, float* red) {
-    float v = 0.f;
-    for (int64_t c = threadIdx.x; c < C; c += kT) v += weight[c];
-    v = wave_sum_all(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = 0.f;
-#pragma unroll
-    for (int k = 0; k < kT / 64; ++k) r += red[k];
-    return r;
-}
-
-// One entry of the gradient above (a train row's); sc = g / den (nan when den == 0).
-__device__ __forceinline__ float ce_w_grad(float x, float lse, bool is_label, float wy, float wc, float W, float eps, float invC, float sc) {
-    const float sm = expf(x - lse);
-    const float hard = wy * (sm - (is_label ? 1.f : 0.f));
-    if (eps == 0.f) return hard * sc;
-    return ((1.f - eps) * hard + (eps * invC) * (W * sm - wc)) * sc;
-}
-
-template <bool kAcc>
-__global__ void __launch_bounds__(kT) ce_bwd_w(const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
-                                              const uint8_t* __restrict__ mask, const float* __restrict__ weight, float eps,
-                                              const float* __restrict__ row_lse, const float* __restrict__ den,
-                                              const float* __restrict__ grad_loss, float* __restrict__ dlogits) {
-    __shared__ float red[kT / 64];
-    float W = static_cast<float>(C);
-    if (eps != 0.f && weight) W = block_weight_sum(weight, C, red);          // (uniform branch: every thread of every block takes it or none)
-    const int64_t idx = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-    if (idx >= N * C) return;
-    const int64_t i = idx / C, c = idx - i * C;
-    if (!mask[i]) {
-        if (!kAcc) dlogits[idx] = 0.f;
-        return;
-    }
-    const float d = den[0];
-    const float sc = (d == 0.f) ? NAN : grad_loss[0] / d;
-    const int64_t yi = y[i];
-    const float g = ce_w_grad(logits[idx], row_lse[i], yi == c, class_weight(weight, yi, C), weight ? weight[c] : 1.f, W, eps,
-                              1.f / static_cast<float>(C), sc);
-    if (kAcc) dlogits[idx] += g;
-    else dlogits[idx] = g;
-}
-
-// hybrid_loss_final with the weighted mean: out[0..4] exactly as there (same partials, same order), out[5] = sum(rowloss) / den,
-// den[0] = sum of w[y_i] over the train rows.
-__global__ void __launch_bounds__(kT) hybrid_loss_final_w(const float* __restrict__ part, int64_t nblk, int64_t q, float coef1, float coef2,
-                                                         const float* __restrict__ rowloss, const uint8_t* __restrict__ mask,
-                                                         const int64_t* __restrict__ y, const float* __restrict__ weight, int64_t N, int64_t C,
-                                                         float* __restrict__ out, float* __restrict__ den) {
-    __shared__ float red[kT / 64];
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, ce = 0.f, dn = 0.f;
-    for (int64_t b = threadIdx.x; b < nblk; b += kT) {
-        a0 += part[4 * b]; a1 += part[4 * b + 1]; a2 += part[4 * b + 2]; a3 += part[4 * b + 3];
-    }
+    RegSums s;
+    float ce = 0.f, dn = 0.f;
+    s.gather(part, nblk);
     for (int64_t i = threadIdx.x; i < N; i += kT) {
         ce += rowloss[i];
-        if (mask[i]) dn += class_weight(weight, y[i], C);
+        dn += mask[i] ? static_cast<float>(cn.row(i)) : 0.f;        // (plain: counts < 2^24, exact in fp32)
     }
-    const float r0 = block_sum(a0, red), r1 = block_sum(a1, red), r2 = block_sum(a2, red), r3 = block_sum(a3, red);
-    const float rc = block_sum(ce, red), rd = block_sum(dn, red);
+    s.reduce(red);
+    const float rc = block_sum(ce, red), rn = block_sum(dn, red);
     if (threadIdx.x == 0) {
-        const float reg1 = (r3 > 1.f) ? r0 / r2 : 0.f;
-        const float reg2 = r1 / static_cast<float>(q);
-        out[0] = reg1; out[1] = reg2; out[2] = r2; out[3] = r3;
-        out[4] = coef1 * reg1 + coef2 * reg2;
-        out[5] = (rd == 0.f) ? NAN : rc / rd;
+        s.store(q, coef1, coef2, out);
+        out[5] = CeNorm<kW>::mean(rc, rn);
         out[6] = out[5] + out[4];
-        den[0] = rd;
+        norm[0] = static_cast<typename CeNorm<kW>::Word>(rn);
     }
 }
 
@@ -491,13 +467,27 @@ __global__ void __launch_bounds__(kT) hybrid_loss_final_w(const float* __restric
 // ranks all-reduce these four sums and finish the formulas with the global q).
 __global__ void __launch_bounds__(kT) reg_raw_final(const float* __restrict__ part, int64_t nblk, float* __restrict__ raw) {
     __shared__ float red[kT / 64];
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    for (int64_t b = threadIdx.x; b < nblk; b += kT) {
-        a0 += part[4 * b]; a1 += part[4 * b + 1]; a2 += part[4 * b + 2]; a3 += part[4 * b + 3];
-    }
-    const float r0 = block_sum(a0, red), r1 = block_sum(a1, red), r2 = block_sum(a2, red), r3 = block_sum(a3, red);
-    if (threadIdx.x == 0) { raw[0] = r0; raw[1] = r1; raw[2] = r2; raw[3] = r3; }
+    RegSums s;
+    s.gather(part, nblk);
+    s.reduce(red);
+    if (threadIdx.x == 0) { raw[0] = s.bce; raw[1] = s.sq; raw[2] = s.nv; raw[3] = s.nl; }
 }
+
+// What the backward needs of a sampled edge's three dot products: {inv, cx, cy, r0}.  cos = dot inv; r0 = (2 (w - cos) / q_norm) coef2, so
+// that dL/d(w - cos) = r0 * grad_loss (q_norm = global #sampled edges); d cos / d x = y inv - cx x, d cos / d y = x inv - cy y, cx = cos /
+// |x|^2 and cy = cos / |y|^2 while F.cosine_similarity's eps clamp is inactive and 0 under it, as autograd.
+struct EdgeBwdScalars {
+    float inv, cx, cy, r0;
+    __device__ __forceinline__ EdgeBwdScalars(float dot, float nx, float ny, float wj, float q_norm, float coef2) {
+        const float den2 = fmaxf(nx * ny, 1e-16f);
+        inv = 1.0f / sqrtf(den2);
+        const float cs = dot * inv;
+        r0 = 2.0f * (wj - cs) / q_norm * coef2;
+        const bool clamped = nx * ny < 1e-16f;
+        cx = clamped ? 0.f : cs / nx;
+        cy = clamped ? 0.f : cs / ny;
+    }
+};
 
 // Per sampled edge: dw[j] and the gradient rows wrt logits[src] (Gs) and logits[dst] (Gd).
 // One 16-lane group per sampled edge (16 edges per workgroup): the group's lanes stride the C logit columns, so the two
@@ -523,11 +513,10 @@ __global__ void __launch_bounds__(kT) reg_bwd_edges(const float* __restrict__ w,
     }
     dot = row16_sum_all_dpp(dot); nx = row16_sum_all_dpp(nx); ny = row16_sum_all_dpp(ny);      // all 16 lanes of a group end with the same sums
     if (!live) return;
-    const float den2 = fmaxf(nx * ny, 1e-16f);
-    const float inv = 1.0f / sqrtf(den2);
-    const float cs = dot * inv;
     const float wj = w[j];
-    const float r = 2.0f * (wj - cs) / q_norm * coef2 * gl;                        // dL/d(w - cos); q_norm = global #sampled edges
+    const EdgeBwdScalars st(dot, nx, ny, wj, q_norm, coef2);
+    const float inv = st.inv, cx = st.cx, cy = st.cy;
+    const float r = st.r0 * gl;                                                    // dL/d(w - cos) = ((2 (w - cos) / q_norm) coef2) gl
     if (sub == 0) {
         float g = r;
         if (coef1 != 0.f && out[3] > 1.f && tm[s] && tm[d]) {
@@ -536,9 +525,6 @@ __global__ void __launch_bounds__(kT) reg_bwd_edges(const float* __restrict__ w,
         }
         dw[j] = g;
     }
-    // d cos / d x = y * inv - cos * x / |x|^2  (only while the eps clamp is inactive, as autograd)
-    const bool clamped = nx * ny < 1e-16f;
-    const float cx = clamped ? 0.f : cs / nx, cy = clamped ? 0.f : cs / ny;
     for (int64_t c = sub; c < C; c += 16) {
         const float a = x[c], b = yv[c];
         Gs[j * C + c] = -r * (b * inv - cx * a);
@@ -547,15 +533,15 @@ __global__ void __launch_bounds__(kT) reg_bwd_edges(const float* __restrict__ w,
 }
 
 // ---------------------------------------------------------------- the hybrid loss in three launches (sgs_hybrid_loss_fused_fwd / _bwd)
-// Forward, one launch for two jobs (as spmm_rowgroup_pair_dual): the first nce workgroups do ce_rows' work (kW: ce_rows_w's), the
+// Forward, one launch for two jobs (as spmm_rowgroup_pair_dual): the first nce workgroups do ce_rows<kW>'s work, the
 // rest reg_fwd_partial's.  Partials, block-sum order and the per-thread accumulation order over the four rounds are reg_fwd_partial's, so
 // hybrid_loss_final reads the same bits.  What differs is the order of the LOADS: reg_fwd_partial reads w, tm[s], tm[d], y[s], y[d] under
 // `if (live && sub == 0)` inside each round, so its four rounds go through memory one after another (index -> rows -> scalars, four
 // times); here the indices of all four rounds are read first, then every row segment and every scalar, unconditionally on clamped
 // indices, and the arithmetic follows.  The row loop runs column-outer / round-inner: each round's three sums still take their columns
 // in increasing order.
-// `stash` (may be null: no gradient wanted) keeps per sampled edge what the backward needs of the three dot products, in
-// reg_bwd_edges' expressions: {inv, cx, cy, r0} with r = r0 * grad_loss -- 16 bytes per edge in place of two gradient rows.
+// `stash` (may be null: no gradient wanted) keeps per sampled edge what the backward needs of the three dot products:
+// EdgeBwdScalars' {inv, cx, cy, r0} with r = r0 * grad_loss -- 16 bytes per edge in place of two gradient rows.
 template <bool kW>
 __global__ void __launch_bounds__(kT) hybrid_fwd_pair(const float* __restrict__ w, const int64_t* __restrict__ sei, int64_t q,
                                                      const float* __restrict__ logits, int64_t N, int64_t C, const int64_t* __restrict__ y,
@@ -565,8 +551,7 @@ __global__ void __launch_bounds__(kT) hybrid_fwd_pair(const float* __restrict__ 
     const int64_t blk = static_cast<int64_t>(blockIdx.x) - nce;         // the row-loss workgroups come first: short, and not the launch's tail
     if (blk < 0) {
         const int64_t i = (static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x) >> 6;
-        if (kW) ce_row_w(i, threadIdx.x & 63, logits, N, C, y, tm, weight, eps, row_lse, rowloss);
-        else    ce_row(i, threadIdx.x & 63, logits, N, C, y, tm, row_lse, rowloss);
+        ce_row<kW>(i, threadIdx.x & 63, logits, N, C, y, tm, CeNorm<kW>::make(weight, eps, y, C), row_lse, rowloss);
         return;
     }
     __shared__ float red[4][kT / 64];
@@ -624,14 +609,9 @@ __global__ void __launch_bounds__(kT) hybrid_fwd_pair(const float* __restrict__ 
             // F.binary_cross_entropy clamps each log at -100
             t_bce = same ? -fmaxf(logf(wr), -100.f) : -fmaxf(logf(1.f - wr), -100.f);
         }
-        if (stash) {                                   // reg_bwd_edges' expressions, in its order
-            const float den2 = fmaxf(sx * sy, 1e-16f);
-            const float inv = 1.0f / sqrtf(den2);
-            const float csb = dt * inv;
-            const float r0 = 2.0f * (wr - csb) / q_norm * coef2;
-            const bool clamped = sx * sy < 1e-16f;
-            const float cx = clamped ? 0.f : csb / sx, cy = clamped ? 0.f : csb / sy;
-            stash[je] = make_float4(inv, cx, cy, r0);
+        if (stash) {
+            const EdgeBwdScalars st(dt, sx, sy, wr, q_norm, coef2);
+            stash[je] = make_float4(st.inv, st.cx, st.cy, st.r0);
         }
     }
     // lane 0 of the group adds the four rounds' terms in round order, as reg_fwd_partial's lane 0 does (a round that adds nothing there
@@ -663,11 +643,11 @@ __global__ void __launch_bounds__(kT) hybrid_fwd_pair(const float* __restrict__ 
 }
 
 // Backward, one launch: the endpoint reduction's traversal (csrc/endpoint_reduce.h) with the terms FORMED where they are added, in
-// place of reg_bwd_edges -> endpoint_reduce -> ce_bwd_acc and their two [q, C] arrays.  For a sampled edge e = (s, d) with the forward's
+// place of reg_bwd_edges -> endpoint_reduce -> ce_bwd<kW, true> and their two [q, C] arrays.  For a sampled edge e = (s, d) with the forward's
 // {inv, cx, cy, r0} and r = r0 * grad_loss, the entry of e in s's out-row is reg_bwd_edges' Gs[e, c] = -r (b inv - cx a) and the entry in
 // d's in-row its Gd[e, c] = -r (a inv - cy b), a = logits[s, c], b = logits[d, c]: the node's own row is read once, the neighbour's per
 // entry (the table is cache resident).  Every sampled edge is in exactly one out-row (self-loops included), whose visitor writes dw[e]
-// by reg_bwd_edges' formula; the writer of dlogits[v, c] adds the cross entropy's term as ce_bwd_acc / ce_bwd_w<true> do.
+// by reg_bwd_edges' formula; the writer of dlogits[v, c] adds the cross entropy's term, ce_bwd<kW, true>'s.
 template <bool kW>
 struct EpHybridTerms {
     static constexpr bool kCol = true, kVisit = true;
@@ -684,7 +664,7 @@ struct EpHybridTerms {
     const float* __restrict__ weight;
     float eps;
     const float* __restrict__ row_lse;
-    const void* __restrict__ norm;          // n_rows (int32) of the plain criterion, den (float) of the weighted one
+    const typename CeNorm<kW>::Word* __restrict__ norm;          // n_rows (int32) of the plain criterion, den (float) of the weighted one
     // What every entry of a workgroup needs is read once: W, grad_loss and whether reg1 is on (coef1 != 0 and a label sum above 1)
     // with its divisor out[2].
     struct Blk { float W, gl, nvalid; bool reg1; };
@@ -697,25 +677,14 @@ struct EpHybridTerms {
         return *(const __attribute__((address_space(4))) T*)(ptr);
     }
     __device__ __forceinline__ Blk block_init() const {
-        // W = sum_c w_c exactly as ce_bwd_w forms it: the workgroup's first 256 threads, block_weight_sum's order
-        __shared__ float red[4];
         Blk b;
         b.W = static_cast<float>(C);
         b.gl = uniform_load(grad_loss);
         b.nvalid = uniform_load(out7 + 2);
         b.reg1 = coef1 != 0.f && uniform_load(out7 + 3) > 1.f;
-        if (kW && eps != 0.f && weight) {                                 // (uniform branch)
-            float v = 0.f;
-            if (threadIdx.x < 256) {
-                for (int64_t c = threadIdx.x; c < C; c += 256) v += weight[c];
-                v = wave_sum_all(v);
-                if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-            }
-            __syncthreads();
-            float r = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) r += red[k];
-            b.W = r;
+        if constexpr (kW) {                                 // W = sum_c w_c as ce_bwd<true, *> has it: the workgroup's first kT threads form it
+            __shared__ float red[kT / 64];
+            if (eps != 0.f && weight) b.W = block_weight_sum<kT>(weight, C, red);         // (uniform branch)
         }
         return b;
     }
@@ -757,16 +726,7 @@ struct EpHybridTerms {
     }
     __device__ __forceinline__ float finish(const Blk& blk, int64_t v, int64_t c, float sum) const {
         if (!tm[v]) return sum;
-        const int64_t idx = v * C + c;
-        if (!kW) {
-            const float sm = expf(logits[idx] - row_lse[v]);
-            return sum + (sm - (y[v] == c ? 1.f : 0.f)) * (grad_loss[0] / static_cast<float>(static_cast<const int*>(norm)[0]));
-        }
-        const float d = static_cast<const float*>(norm)[0];
-        const float sc = (d == 0.f) ? NAN : grad_loss[0] / d;
-        const int64_t yi = y[v];
-        return sum + ce_w_grad(logits[idx], row_lse[v], yi == c, class_weight(weight, yi, C), weight ? weight[c] : 1.f, blk.W, eps,
-                               1.f / static_cast<float>(C), sc);
+        return sum + ce_grad<kW>(CeNorm<kW>::make(weight, eps, y, C), logits[v * C + c], row_lse[v], y[v], c, C, blk.W, grad_loss, norm);
     }
 };
 
@@ -891,6 +851,84 @@ std::atomic<int> g_conf_variant{0};
 
 using namespace sgs;
 
+namespace {
+
+// The cross entropy entries' argument checks: `ok` is the entry's own condition; the plain entries count a null n_rows among the bad
+// arguments, the weighted ones name the smoothing and `den` on their own.
+template <bool kW>
+int ce_check(const char* fn, bool ok, const void* norm, float eps) {
+    SGS_REQUIRE(ok && (kW || norm), SGS_EINVAL, "%s: bad arguments", fn);
+    if (kW) {
+        SGS_REQUIRE(eps >= 0.f && eps <= 1.f, SGS_EINVAL, "%s: label_smoothing outside [0, 1]", fn);
+        SGS_REQUIRE(norm, SGS_EINVAL, "%s: den is NULL", fn);
+    }
+    return SGS_OK;
+}
+
+template <bool kW>
+int masked_ce_fwd(const char* fn, const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
+                  float eps, float* loss, float* row_lse, float* rowloss, typename CeNorm<kW>::Word* norm, sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // (the weighted divisor is summed in fp32 by one block: N < 2^24 as in the hybrid forwards)
+    if (int rc = ce_check<kW>(fn, N > 0 && (!kW || N < (int64_t(1) << 24)) && C > 0 && logits && y && train_mask && loss && row_lse && rowloss, norm, eps))
+        return rc;
+    const CeNorm<kW> cn = CeNorm<kW>::make(weight, eps, y, C);
+    hipLaunchKernelGGL(ce_rows<kW>, dim3(cdiv(N * 64, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, row_lse, rowloss, cn);
+    hipLaunchKernelGGL(ce_final<kW>, dim3(1), dim3(1024), 0, stream, static_cast<const float*>(rowloss), train_mask, N, loss, norm, cn);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+template <bool kW, bool kAcc>
+int masked_ce_bwd(const char* fn, const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
+                  float eps, const float* row_lse, const typename CeNorm<kW>::Word* norm, const float* grad_loss, float* dlogits,
+                  sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (int rc = ce_check<kW>(fn, N > 0 && C > 0 && logits && y && train_mask && row_lse && grad_loss && dlogits, norm, eps)) return rc;
+    hipLaunchKernelGGL((ce_bwd<kW, kAcc>), dim3(cdiv(N * C, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, row_lse, norm, grad_loss, dlogits,
+                       CeNorm<kW>::make(weight, eps, y, C));
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+// The launches of the three hybrid forwards, after their checks: row losses and per-edge partials (`fused`: in one launch, with the
+// backward's stash), then the finishing block.
+template <bool kW>
+int hybrid_loss_launch(bool fused, const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* w,
+                       const int64_t* sei, int64_t q, float coef1, float coef2, const float* weight, float eps, float* out, float* row_lse,
+                       float* rowloss, void* norm, float* stash, void* ws, hipStream_t stream) {
+    Carver cv(ws);
+    const int64_t nblk = cdiv(q, kRegEdges);
+    float* part = cv.take<float>(4 * (nblk + 1));
+    const int64_t nce = cdiv(N * 64, kT);
+    const CeNorm<kW> cn = CeNorm<kW>::make(weight, eps, y, C);
+    if (fused) {
+        hipLaunchKernelGGL(hybrid_fwd_pair<kW>, dim3(static_cast<unsigned>(nce + nblk)), dim3(kT), 0, stream, w, sei, q, logits, N, C, y, train_mask, nce,
+                           coef2, static_cast<float>(q), weight, eps, part, reinterpret_cast<float4*>(stash), row_lse, rowloss);
+    } else {
+        hipLaunchKernelGGL(ce_rows<kW>, dim3(nce), dim3(kT), 0, stream, logits, N, C, y, train_mask, row_lse, rowloss, cn);
+        hipLaunchKernelGGL(reg_fwd_partial, dim3(nblk), dim3(kT), 0, stream, w, sei, q, logits, C, y, train_mask, static_cast<float*>(nullptr), part);
+    }
+    hipLaunchKernelGGL(hybrid_loss_final<kW>, dim3(1), dim3(kT), 0, stream, static_cast<const float*>(part), nblk, q, coef1, coef2,
+                       static_cast<const float*>(rowloss), train_mask, N, out, static_cast<typename CeNorm<kW>::Word*>(norm), cn);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+template <bool kW>
+int hybrid_loss_fwd(const char* fn, const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* w,
+                    const int64_t* sei, int64_t q, float coef1, float coef2, const float* weight, float eps, float* out, float* row_lse,
+                    float* rowloss, typename CeNorm<kW>::Word* norm, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    if (int rc = ce_check<kW>(fn, q > 0 && N > 0 && N < (int64_t(1) << 24) && C > 0 && logits && y && train_mask && w && sei && out && row_lse && rowloss,
+                              norm, eps))
+        return rc;
+    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_reg_workspace_bytes(q), SGS_EWORKSPACE, "%s: workspace too small", fn);
+    return hybrid_loss_launch<kW>(false, logits, N, C, y, train_mask, w, sei, q, coef1, coef2, weight, eps, out, row_lse, rowloss, norm, nullptr, ws,
+                                  static_cast<hipStream_t>(stream_));
+}
+
+}  // namespace
+
 extern "C" {
 
 int sgs_masked_correct(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask,
@@ -953,25 +991,51 @@ int sgs_publish_to_host(const int32_t* src_dev, int64_t n, const uint64_t* seq_d
 
 int sgs_masked_ce_fwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, float* loss,
                       float* row_lse, float* rowloss, int32_t* n_rows, sgs_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(N > 0 && C > 0 && logits && y && train_mask && loss && row_lse && rowloss && n_rows, SGS_EINVAL,
-                "sgs_masked_ce_fwd: bad arguments");
-    hipLaunchKernelGGL(ce_rows, dim3(cdiv(N * 64, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, row_lse, rowloss);
-    hipLaunchKernelGGL(ce_final, dim3(1), dim3(1024), 0, stream, rowloss, train_mask, N, loss, n_rows);
-    SGS_LAUNCH_OK();
-    return SGS_OK;
+    return masked_ce_fwd<false>("sgs_masked_ce_fwd", logits, N, C, y, train_mask, nullptr, 0.f, loss, row_lse, rowloss, n_rows, stream_);
 }
 
 int sgs_masked_ce_bwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask,
                       const float* row_lse, const int32_t* n_rows, const float* grad_loss, float* dlogits,
                       sgs_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(N > 0 && C > 0 && logits && y && train_mask && row_lse && n_rows && grad_loss && dlogits, SGS_EINVAL,
-                "sgs_masked_ce_bwd: bad arguments");
-    hipLaunchKernelGGL(ce_bwd, dim3(cdiv(N * C, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, row_lse, n_rows, grad_loss,
-                       dlogits);
-    SGS_LAUNCH_OK();
-    return SGS_OK;
+    return masked_ce_bwd<false, false>("sgs_masked_ce_bwd", logits, N, C, y, train_mask, nullptr, 0.f, row_lse, n_rows, grad_loss, dlogits, stream_);
+}
+
+int sgs_masked_ce_bwd_acc(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* row_lse,
+                          const int32_t* n_rows, const float* grad_loss, float* dlogits, sgs_stream_t stream_) {
+    return masked_ce_bwd<false, true>("sgs_masked_ce_bwd_acc", logits, N, C, y, train_mask, nullptr, 0.f, row_lse, n_rows, grad_loss, dlogits, stream_);
+}
+
+int sgs_masked_ce_w_fwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
+                        float label_smoothing, float* loss, float* row_lse, float* rowloss, float* den, sgs_stream_t stream_) {
+    return masked_ce_fwd<true>("sgs_masked_ce_w_fwd", logits, N, C, y, train_mask, weight, label_smoothing, loss, row_lse, rowloss, den, stream_);
+}
+
+int sgs_masked_ce_w_bwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
+                        float label_smoothing, const float* row_lse, const float* den, const float* grad_loss, float* dlogits,
+                        sgs_stream_t stream_) {
+    return masked_ce_bwd<true, false>("sgs_masked_ce_w_bwd", logits, N, C, y, train_mask, weight, label_smoothing, row_lse, den, grad_loss, dlogits,
+                                      stream_);
+}
+
+int sgs_masked_ce_w_bwd_acc(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
+                            float label_smoothing, const float* row_lse, const float* den, const float* grad_loss, float* dlogits,
+                            sgs_stream_t stream_) {
+    return masked_ce_bwd<true, true>("sgs_masked_ce_w_bwd_acc", logits, N, C, y, train_mask, weight, label_smoothing, row_lse, den, grad_loss, dlogits,
+                                     stream_);
+}
+
+int sgs_hybrid_loss_fwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* w,
+                        const int64_t* sampled_edge_index, int64_t q, float coef1, float coef2, float* out, float* row_lse, float* rowloss,
+                        int32_t* n_rows, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    return hybrid_loss_fwd<false>("sgs_hybrid_loss_fwd", logits, N, C, y, train_mask, w, sampled_edge_index, q, coef1, coef2, nullptr, 0.f, out, row_lse,
+                                  rowloss, n_rows, ws, ws_bytes, stream_);
+}
+
+int sgs_hybrid_loss_w_fwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* w,
+                          const int64_t* sampled_edge_index, int64_t q, float coef1, float coef2, const float* weight, float label_smoothing,
+                          float* out, float* row_lse, float* rowloss, float* den, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    return hybrid_loss_fwd<true>("sgs_hybrid_loss_w_fwd", logits, N, C, y, train_mask, w, sampled_edge_index, q, coef1, coef2, weight, label_smoothing,
+                                 out, row_lse, rowloss, den, ws, ws_bytes, stream_);
 }
 
 size_t sgs_edge_reg_workspace_bytes(int64_t q) { return carve_bytes(4 * (cdiv(q < 0 ? 0 : q, kRegEdges) + 1), 4) + 256; }
@@ -989,100 +1053,6 @@ int sgs_edge_reg_fwd(const float* w, const int64_t* sampled_edge_index, int64_t 
     hipLaunchKernelGGL(reg_fwd_partial, dim3(nblk), dim3(kT), 0, stream, w, sampled_edge_index, q, logits, C, y, train_mask, cos_out,
                        part);
     hipLaunchKernelGGL(reg_fwd_final, dim3(1), dim3(kT), 0, stream, part, nblk, q, coef1, coef2, out);
-    SGS_LAUNCH_OK();
-    return SGS_OK;
-}
-
-int sgs_hybrid_loss_fwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* w,
-                        const int64_t* sampled_edge_index, int64_t q, float coef1, float coef2, float* out, float* row_lse, float* rowloss,
-                        int32_t* n_rows, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(q > 0 && N > 0 && N < (int64_t(1) << 24) && C > 0 && logits && y && train_mask && w && sampled_edge_index && out && row_lse &&
-                    rowloss && n_rows,
-                SGS_EINVAL, "sgs_hybrid_loss_fwd: bad arguments");
-    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_reg_workspace_bytes(q), SGS_EWORKSPACE, "sgs_hybrid_loss_fwd: workspace too small");
-    Carver cv(ws);
-    const int64_t nblk = cdiv(q, kRegEdges);
-    float* part = cv.take<float>(4 * (nblk + 1));
-    hipLaunchKernelGGL(ce_rows, dim3(cdiv(N * 64, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, row_lse, rowloss);
-    hipLaunchKernelGGL(reg_fwd_partial, dim3(nblk), dim3(kT), 0, stream, w, sampled_edge_index, q, logits, C, y, train_mask,
-                       static_cast<float*>(nullptr), part);
-    hipLaunchKernelGGL(hybrid_loss_final, dim3(1), dim3(kT), 0, stream, part, nblk, q, coef1, coef2, rowloss, train_mask, N, out, n_rows);
-    SGS_LAUNCH_OK();
-    return SGS_OK;
-}
-
-int sgs_masked_ce_bwd_acc(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* row_lse,
-                          const int32_t* n_rows, const float* grad_loss, float* dlogits, sgs_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(N > 0 && C > 0 && logits && y && train_mask && row_lse && n_rows && grad_loss && dlogits, SGS_EINVAL,
-                "sgs_masked_ce_bwd_acc: bad arguments");
-    hipLaunchKernelGGL(ce_bwd_acc, dim3(cdiv(N * C, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, row_lse, n_rows, grad_loss,
-                       dlogits);
-    SGS_LAUNCH_OK();
-    return SGS_OK;
-}
-
-int sgs_masked_ce_w_fwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
-                        float label_smoothing, float* loss, float* row_lse, float* rowloss, float* den, sgs_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(N > 0 && N < (int64_t(1) << 24) && C > 0 && logits && y && train_mask && loss && row_lse && rowloss, SGS_EINVAL,
-                "sgs_masked_ce_w_fwd: bad arguments");
-    SGS_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, SGS_EINVAL, "sgs_masked_ce_w_fwd: label_smoothing outside [0, 1]");
-    SGS_REQUIRE(den, SGS_EINVAL, "sgs_masked_ce_w_fwd: den is NULL");
-    hipLaunchKernelGGL(ce_rows_w, dim3(cdiv(N * 64, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, weight, label_smoothing, row_lse,
-                       rowloss);
-    hipLaunchKernelGGL(ce_final_w, dim3(1), dim3(1024), 0, stream, rowloss, train_mask, y, weight, N, C, loss, den);
-    SGS_LAUNCH_OK();
-    return SGS_OK;
-}
-
-int sgs_masked_ce_w_bwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
-                        float label_smoothing, const float* row_lse, const float* den, const float* grad_loss, float* dlogits,
-                        sgs_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(N > 0 && C > 0 && logits && y && train_mask && row_lse && grad_loss && dlogits, SGS_EINVAL, "sgs_masked_ce_w_bwd: bad arguments");
-    SGS_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, SGS_EINVAL, "sgs_masked_ce_w_bwd: label_smoothing outside [0, 1]");
-    SGS_REQUIRE(den, SGS_EINVAL, "sgs_masked_ce_w_bwd: den is NULL");
-    hipLaunchKernelGGL(ce_bwd_w<false>, dim3(cdiv(N * C, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, weight, label_smoothing,
-                       row_lse, den, grad_loss, dlogits);
-    SGS_LAUNCH_OK();
-    return SGS_OK;
-}
-
-int sgs_masked_ce_w_bwd_acc(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* weight,
-                            float label_smoothing, const float* row_lse, const float* den, const float* grad_loss, float* dlogits,
-                            sgs_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(N > 0 && C > 0 && logits && y && train_mask && row_lse && grad_loss && dlogits, SGS_EINVAL,
-                "sgs_masked_ce_w_bwd_acc: bad arguments");
-    SGS_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, SGS_EINVAL, "sgs_masked_ce_w_bwd_acc: label_smoothing outside [0, 1]");
-    SGS_REQUIRE(den, SGS_EINVAL, "sgs_masked_ce_w_bwd_acc: den is NULL");
-    hipLaunchKernelGGL(ce_bwd_w<true>, dim3(cdiv(N * C, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, weight, label_smoothing,
-                       row_lse, den, grad_loss, dlogits);
-    SGS_LAUNCH_OK();
-    return SGS_OK;
-}
-
-int sgs_hybrid_loss_w_fwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* w,
-                          const int64_t* sampled_edge_index, int64_t q, float coef1, float coef2, const float* weight, float label_smoothing,
-                          float* out, float* row_lse, float* rowloss, float* den, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(q > 0 && N > 0 && N < (int64_t(1) << 24) && C > 0 && logits && y && train_mask && w && sampled_edge_index && out && row_lse &&
-                    rowloss,
-                SGS_EINVAL, "sgs_hybrid_loss_w_fwd: bad arguments");
-    SGS_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, SGS_EINVAL, "sgs_hybrid_loss_w_fwd: label_smoothing outside [0, 1]");
-    SGS_REQUIRE(den, SGS_EINVAL, "sgs_hybrid_loss_w_fwd: den is NULL");
-    SGS_REQUIRE(ws && ws_bytes >= sgs_edge_reg_workspace_bytes(q), SGS_EWORKSPACE, "sgs_hybrid_loss_w_fwd: workspace too small");
-    Carver cv(ws);
-    const int64_t nblk = cdiv(q, kRegEdges);
-    float* part = cv.take<float>(4 * (nblk + 1));
-    hipLaunchKernelGGL(ce_rows_w, dim3(cdiv(N * 64, kT)), dim3(kT), 0, stream, logits, N, C, y, train_mask, weight, label_smoothing, row_lse,
-                       rowloss);
-    hipLaunchKernelGGL(reg_fwd_partial, dim3(nblk), dim3(kT), 0, stream, w, sampled_edge_index, q, logits, C, y, train_mask,
-                       static_cast<float*>(nullptr), part);
-    hipLaunchKernelGGL(hybrid_loss_final_w, dim3(1), dim3(kT), 0, stream, part, nblk, q, coef1, coef2, rowloss, train_mask, y, weight, N, C, out,
-                       den);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -1131,25 +1101,8 @@ int sgs_hybrid_loss_fused_fwd(const float* logits, int64_t N, int64_t C, const i
                 "sgs_hybrid_loss_fused_fwd: label_smoothing outside [0, 1], or a weight / smoothing without `weighted`");
     SGS_REQUIRE((reinterpret_cast<uintptr_t>(stash) & 15) == 0, SGS_EINVAL, "sgs_hybrid_loss_fused_fwd: stash must be 16-byte aligned");
     SGS_REQUIRE(ws && ws_bytes >= sgs_edge_reg_workspace_bytes(q), SGS_EWORKSPACE, "sgs_hybrid_loss_fused_fwd: workspace too small");
-    Carver cv(ws);
-    const int64_t nblk = cdiv(q, kRegEdges);
-    float* part = cv.take<float>(4 * (nblk + 1));
-    const int64_t nce = cdiv(N * 64, kT);
-    const dim3 grid(static_cast<unsigned>(nce + nblk));
-    float4* st = reinterpret_cast<float4*>(stash);
-    if (weighted) {
-        hipLaunchKernelGGL(hybrid_fwd_pair<true>, grid, dim3(kT), 0, stream, w, sampled_edge_index, q, logits, N, C, y, train_mask, nce, coef2,
-                           static_cast<float>(q), weight, label_smoothing, part, st, row_lse, rowloss);
-        hipLaunchKernelGGL(hybrid_loss_final_w, dim3(1), dim3(kT), 0, stream, part, nblk, q, coef1, coef2, rowloss, train_mask, y, weight, N, C, out,
-                           static_cast<float*>(norm));
-    } else {
-        hipLaunchKernelGGL(hybrid_fwd_pair<false>, grid, dim3(kT), 0, stream, w, sampled_edge_index, q, logits, N, C, y, train_mask, nce, coef2,
-                           static_cast<float>(q), weight, label_smoothing, part, st, row_lse, rowloss);
-        hipLaunchKernelGGL(hybrid_loss_final, dim3(1), dim3(kT), 0, stream, part, nblk, q, coef1, coef2, rowloss, train_mask, N, out,
-                           static_cast<int*>(norm));
-    }
-    SGS_LAUNCH_OK();
-    return SGS_OK;
+    return (weighted ? hybrid_loss_launch<true> : hybrid_loss_launch<false>)(true, logits, N, C, y, train_mask, w, sampled_edge_index, q, coef1, coef2,
+                                                                             weight, label_smoothing, out, row_lse, rowloss, norm, stash, ws, stream);
 }
 
 int sgs_hybrid_loss_fused_bwd(const float* logits, int64_t N, int64_t C, const int64_t* y, const uint8_t* train_mask, const float* w, int64_t q,
@@ -1168,7 +1121,7 @@ int sgs_hybrid_loss_fused_bwd(const float* logits, int64_t N, int64_t C, const i
 #define SGS_HYB(KW_)                                                                                                                              \
     do {                                                                                                                                          \
         const EpHybridTerms<KW_> terms{logits, C, reinterpret_cast<const float4*>(stash), w, y, train_mask, out, coef1, grad_loss, dw, weight,    \
-                                       label_smoothing, row_lse, norm};                                                                           \
+                                       label_smoothing, row_lse, static_cast<const CeNorm<KW_>::Word*>(norm)};                                    \
         if (nw == 16)     hipLaunchKernelGGL((endpoint_reduce_rowblock<1, 16, EpHybridTerms<KW_>>), dim3(static_cast<unsigned>(N)), dim3(1024), 0, stream, \
                                              terms, N, C, in_ptr, in_src, in_eid, out_ptr, out_dst, out_eid, 1.0f, 1.0f, dlogits);               \
         else if (nw == 4) hipLaunchKernelGGL((endpoint_reduce_rowblock<1, 4, EpHybridTerms<KW_>>), dim3(static_cast<unsigned>(N)), dim3(256), 0, stream,   \

@@ -1360,31 +1360,57 @@ def publish_to_host(src, n, seq, dst_pinned) -> None:
                "sgs_publish_to_host")
 
 
+def _ce_kind(weight, eps):
+    """Which entries of the library a criterion takes: ("", int32, ()) for the plain one (no class weight, no smoothing: sgs_masked_ce_*,
+    sgs_hybrid_loss_fwd, the divisor word a count of train rows) and ("_w", float32, (weight, eps)) otherwise (sgs_masked_ce_w_*,
+    sgs_hybrid_loss_w_fwd, the divisor `den` a sum of class weights).  The third item is what the weighted entries take in addition."""
+    if weight is None and eps == 0.0:
+        return "", torch.int32, ()
+    return "_w", torch.float32, (_ptr(weight), eps)
+
+
+def _masked_ce_fwd(logits, y, mask_u8, weight, eps):
+    """Two launches: (loss [1], row_lse [N], rowloss [N], the divisor word [1]) of the rows on the mask."""
+    L = _lib.lib()
+    N, C = logits.shape
+    dev = logits.device
+    w_, norm_dtype, crit = _ce_kind(weight, eps)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    row_lse = torch.empty(N, dtype=torch.float32, device=dev)
+    rowloss = torch.empty(N, dtype=torch.float32, device=dev)
+    norm = torch.empty(1, dtype=norm_dtype, device=dev)
+    name = f"sgs_masked_ce{w_}_fwd"
+    _lib.check(getattr(L, name)(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), *crit, _ptr(loss), _ptr(row_lse), _ptr(rowloss), _ptr(norm), _stream()),
+               name)
+    return loss, row_lse, rowloss, norm
+
+
+def _masked_ce_bwd(logits, y, mask_u8, weight, eps, row_lse, norm, g):
+    """One launch: d logits (written, zero off the mask) for the upstream gradient g [1] and the divisor word `norm`."""
+    L = _lib.lib()
+    N, C = logits.shape
+    w_, _, crit = _ce_kind(weight, eps)
+    d = torch.empty_like(logits)
+    name = f"sgs_masked_ce{w_}_bwd"
+    _lib.check(getattr(L, name)(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), *crit, _ptr(row_lse), _ptr(norm), _ptr(g), _ptr(d), _stream()), name)
+    return d
+
+
 class _MaskedCE(torch.autograd.Function):
+    """nn.CrossEntropyLoss(weight=w, label_smoothing=eps) over the rows on the mask: two launches forward, one backward; the divisor word
+    (_ce_kind) is kept on the device for the backward."""
+
     @staticmethod
-    def forward(ctx, logits, y, mask_u8):
-        L = _lib.lib()
-        N, C = logits.shape
-        dev = logits.device
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        row_lse = torch.empty(N, dtype=torch.float32, device=dev)
-        rowloss = torch.empty(N, dtype=torch.float32, device=dev)
-        n_rows = torch.empty(1, dtype=torch.int32, device=dev)
-        _lib.check(L.sgs_masked_ce_fwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(loss), _ptr(row_lse), _ptr(rowloss),
-                                       _ptr(n_rows), _stream()), "sgs_masked_ce_fwd")
-        ctx.save_for_backward(logits, y, mask_u8, row_lse, n_rows)
+    def forward(ctx, logits, y, mask_u8, weight, eps):
+        loss, row_lse, _, norm = _masked_ce_fwd(logits, y, mask_u8, weight, eps)
+        ctx.save_for_backward(logits, y, mask_u8, weight, row_lse, norm)
+        ctx.eps = eps
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        L = _lib.lib()
-        logits, y, mask_u8, row_lse, n_rows = ctx.saved_tensors
-        N, C = logits.shape
-        g = g.reshape(1).contiguous().float()
-        d = torch.empty_like(logits)
-        _lib.check(L.sgs_masked_ce_bwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(row_lse), _ptr(n_rows), _ptr(g), _ptr(d),
-                                       _stream()), "sgs_masked_ce_bwd")
-        return d, None, None
+        logits, y, mask_u8, weight, row_lse, norm = ctx.saved_tensors
+        return _masked_ce_bwd(logits, y, mask_u8, weight, ctx.eps, row_lse, norm, g.reshape(1).contiguous().float()), None, None, None, None
 
 
 def check_ce_spec(logits, weight, label_smoothing):
@@ -1410,47 +1436,15 @@ def check_ce_spec(logits, weight, label_smoothing):
     return weight.detach(), eps
 
 
-class _MaskedCEW(torch.autograd.Function):
-    """_MaskedCE for nn.CrossEntropyLoss(weight=w, label_smoothing=eps): the same two launches forward and one backward; `den` (the sum of
-    the train rows' class weights, a device float) is the backward's divisor."""
-
-    @staticmethod
-    def forward(ctx, logits, y, mask_u8, weight, eps):
-        L = _lib.lib()
-        N, C = logits.shape
-        dev = logits.device
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        row_lse = torch.empty(N, dtype=torch.float32, device=dev)
-        rowloss = torch.empty(N, dtype=torch.float32, device=dev)
-        den = torch.empty(1, dtype=torch.float32, device=dev)
-        _lib.check(L.sgs_masked_ce_w_fwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(weight), eps, _ptr(loss), _ptr(row_lse), _ptr(rowloss),
-                                         _ptr(den), _stream()), "sgs_masked_ce_w_fwd")
-        ctx.save_for_backward(logits, y, mask_u8, weight, row_lse, den)
-        ctx.eps = eps
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        L = _lib.lib()
-        logits, y, mask_u8, weight, row_lse, den = ctx.saved_tensors
-        N, C = logits.shape
-        g = g.reshape(1).contiguous().float()
-        d = torch.empty_like(logits)
-        _lib.check(L.sgs_masked_ce_w_bwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(weight), ctx.eps, _ptr(row_lse), _ptr(den), _ptr(g),
-                                         _ptr(d), _stream()), "sgs_masked_ce_w_bwd")
-        return d, None, None, None, None
-
-
 def masked_cross_entropy(logits, y, train_mask, *, weight=None, label_smoothing=0.0):
     """nn.CrossEntropyLoss(weight=weight, label_smoothing=label_smoothing)(logits[train_mask], y[train_mask]) without the boolean-index
     sync.  With both keywords at their defaults: the plain chain (sgs_masked_ce_fwd / _bwd), otherwise the weighted one
     (sgs_masked_ce_w_fwd / _w_bwd); `weight`: check_ce_spec."""
-    if weight is None and label_smoothing == 0.0:
-        _need_gpu(logits, y, train_mask)
-        return _MaskedCE.apply(logits.contiguous(), y.contiguous(), _u8(train_mask))
-    weight, eps = check_ce_spec(logits, weight, label_smoothing)
+    eps = 0.0
+    if weight is not None or label_smoothing != 0.0:
+        weight, eps = check_ce_spec(logits, weight, label_smoothing)
     _need_gpu(logits, y, train_mask)
-    return _MaskedCEW.apply(logits.contiguous(), y.contiguous(), _u8(train_mask), weight, eps)
+    return _MaskedCE.apply(logits.contiguous(), y.contiguous(), _u8(train_mask), weight, eps)
 
 
 class _EdgeReg(torch.autograd.Function):
@@ -1513,23 +1507,20 @@ class _HybridLoss(torch.autograd.Function):
         row_lse = torch.empty(N, dtype=torch.float32, device=dev)
         rowloss = torch.empty(N, dtype=torch.float32, device=dev)
         ws = workspace(L.sgs_edge_reg_workspace_bytes(q), dev)
-        ctx.plain = weight is None and eps == 0.0
-        # `n_rows` of the weighted / smoothed criterion is `den`, a float word (the sum of the train rows' class weights)
-        n_rows = torch.empty(1, dtype=torch.int32 if ctx.plain else torch.float32, device=dev)
+        w_, norm_dtype, crit = _ce_kind(weight, eps)
+        ctx.weighted = 1 if w_ else 0
+        n_rows = torch.empty(1, dtype=norm_dtype, device=dev)          # the divisor word of the criterion (_ce_kind)
         stash = None
         if coef2 != 0.0:    # two launches; the per-edge scalars of the backward are kept (16 B per edge) when a gradient is wanted
             if ctx.needs_input_grad[0] or ctx.needs_input_grad[3]:
                 stash = torch.empty(q, 4, dtype=torch.float32, device=dev)
             _lib.check(L.sgs_hybrid_loss_fused_fwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(w), _ptr(sei), q, float(coef1), float(coef2),
-                                                   0 if ctx.plain else 1, _ptr(weight), eps, _ptr(out), _ptr(row_lse), _ptr(rowloss), _ptr(n_rows),
+                                                   ctx.weighted, _ptr(weight), eps, _ptr(out), _ptr(row_lse), _ptr(rowloss), _ptr(n_rows),
                                                    _ptr(stash), ws.data_ptr(), ws.numel(), _stream()), "sgs_hybrid_loss_fused_fwd")
-        elif ctx.plain:
-            _lib.check(L.sgs_hybrid_loss_fwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(w), _ptr(sei), q, float(coef1), float(coef2), _ptr(out),
-                                             _ptr(row_lse), _ptr(rowloss), _ptr(n_rows), ws.data_ptr(), ws.numel(), _stream()), "sgs_hybrid_loss_fwd")
         else:
-            _lib.check(L.sgs_hybrid_loss_w_fwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(w), _ptr(sei), q, float(coef1), float(coef2),
-                                               _ptr(weight), eps, _ptr(out), _ptr(row_lse), _ptr(rowloss), _ptr(n_rows), ws.data_ptr(), ws.numel(),
-                                               _stream()), "sgs_hybrid_loss_w_fwd")
+            name = f"sgs_hybrid_loss{w_}_fwd"
+            _lib.check(getattr(L, name)(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(w), _ptr(sei), q, float(coef1), float(coef2), *crit, _ptr(out),
+                                        _ptr(row_lse), _ptr(rowloss), _ptr(n_rows), ws.data_ptr(), ws.numel(), _stream()), name)
         ctx.save_for_backward(logits, y, mask_u8, w, sei, out, row_lse, n_rows, weight, stash)
         ctx.eps = eps
         ctx.graph, ctx.coef1, ctx.coef2 = graph, float(coef1), float(coef2)
@@ -1550,7 +1541,7 @@ class _HybridLoss(torch.autograd.Function):
             gr = ctx.graph
             dlogits = torch.empty_like(logits)
             _lib.check(L.sgs_hybrid_loss_fused_bwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(w), q, _ptr(stash), _ptr(out), ctx.coef1,
-                                                   0 if ctx.plain else 1, _ptr(weight), ctx.eps, _ptr(row_lse), _ptr(n_rows), _ptr(g), _ptr(gr.in_ptr),
+                                                   ctx.weighted, _ptr(weight), ctx.eps, _ptr(row_lse), _ptr(n_rows), _ptr(g), _ptr(gr.in_ptr),
                                                    _ptr(gr.in_src), _ptr(gr.in_eid), _ptr(gr.out_ptr), _ptr(gr.out_dst), _ptr(gr.out_eid), _ptr(dw),
                                                    _ptr(dlogits), _stream()), "sgs_hybrid_loss_fused_bwd")
         else:               # today's chain: with coef2 == 0 the cross entropy's gradient is written, not accumulated
@@ -1558,13 +1549,7 @@ class _HybridLoss(torch.autograd.Function):
             Gd = torch.empty(q, C, dtype=torch.float32, device=dev)
             _lib.check(L.sgs_edge_reg_bwd(_ptr(w), _ptr(sei), q, q, _ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(out), ctx.coef1,
                                           ctx.coef2, _ptr(g), _ptr(dw), _ptr(Gs), _ptr(Gd), _stream()), "sgs_edge_reg_bwd")
-            dlogits = torch.empty_like(logits)
-            if not ctx.plain:
-                _lib.check(L.sgs_masked_ce_w_bwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(weight), ctx.eps, _ptr(row_lse), _ptr(n_rows),
-                                                 _ptr(g), _ptr(dlogits), _stream()), "sgs_masked_ce_w_bwd")
-            else:
-                _lib.check(L.sgs_masked_ce_bwd(_ptr(logits), N, C, _ptr(y), _ptr(mask_u8), _ptr(row_lse), _ptr(n_rows), _ptr(g), _ptr(dlogits),
-                                               _stream()), "sgs_masked_ce_bwd")
+            dlogits = _masked_ce_bwd(logits, y, mask_u8, weight, ctx.eps, row_lse, n_rows, g)
         nm = ctx.nm_ref() if ctx.nm_ref is not None else None
         if nm is not None and nm._park_ok and dw.numel() == nm.graph.n_edges:
             import weakref

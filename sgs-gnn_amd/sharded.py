@@ -675,74 +675,32 @@ class _BiasActRows(torch.autograd.Function):
 
 
 class _BlockCE(torch.autograd.Function):
-    """This block's share of nn.CrossEntropyLoss()(logits[train], y[train]): sum of the block's train-row losses / #train rows of
-    the WHOLE graph, so the ranks' values add up to the replicated loss (training_hybrid.py:113)."""
+    """This block's share of nn.CrossEntropyLoss(weight=w, label_smoothing=eps)(logits[train], y[train]): sum of the block's train-row
+    losses / `norm`, the divisor of the WHOLE graph, so the ranks' values add up to the replicated loss (training_hybrid.py:113).  `norm` is
+    the number of train rows (int32) for the plain criterion, else the class weights of the train rows summed (labels and mask are
+    replicated: every rank forms the same device float, no collective)."""
 
     @staticmethod
-    def forward(ctx, logits_b, yb, mb_u8, n_train):
-        L = _lib.lib()
+    def forward(ctx, logits_b, yb, mb_u8, norm, weight, eps):
         n, C = logits_b.shape
-        dev = logits_b.device
         if n == 0:
             ctx.empty, ctx.C = True, C
-            return torch.zeros((), dtype=torch.float32, device=dev)
+            return torch.zeros((), dtype=torch.float32, device=logits_b.device)
         ctx.empty = False
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        row_lse, rowloss = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
-        nb = torch.empty(1, dtype=torch.int32, device=dev)
-        _lib.check(L.sgs_masked_ce_fwd(ops._ptr(logits_b), n, C, ops._ptr(yb), ops._ptr(mb_u8), ops._ptr(loss), ops._ptr(row_lse), ops._ptr(rowloss),
-                                       ops._ptr(nb), ops._stream()), "sgs_masked_ce_fwd")
-        ctx.save_for_backward(logits_b, yb, mb_u8, row_lse, n_train)
-        return rowloss.sum() / n_train[0].to(torch.float32)
+        assert norm.dtype == ops._ce_kind(weight, eps)[1], "the divisor word must be the criterion's own (ops._ce_kind)"
+        _, row_lse, rowloss, _ = ops._masked_ce_fwd(logits_b, yb, mb_u8, weight, eps)
+        ctx.save_for_backward(logits_b, yb, mb_u8, row_lse, norm, weight)
+        ctx.eps = eps
+        if norm.dtype == torch.int32:                    # plain
+            return rowloss.sum() / norm[0].to(torch.float32)
+        return torch.where(norm[0] == 0, torch.full_like(norm[0], float("nan")), rowloss.sum() / norm[0])
 
     @staticmethod
     def backward(ctx, g):
         if ctx.empty:                                    # an empty gradient, not None: the layers above hold collectives every rank must enter
-            return torch.zeros(0, ctx.C, dtype=torch.float32, device=g.device), None, None, None
-        L = _lib.lib()
-        logits_b, yb, mb_u8, row_lse, n_train = ctx.saved_tensors
-        n, C = logits_b.shape
-        g = g.reshape(1).contiguous().float()
-        d = torch.empty_like(logits_b)
-        _lib.check(L.sgs_masked_ce_bwd(ops._ptr(logits_b), n, C, ops._ptr(yb), ops._ptr(mb_u8), ops._ptr(row_lse), ops._ptr(n_train), ops._ptr(g),
-                                       ops._ptr(d), ops._stream()), "sgs_masked_ce_bwd")
-        return d, None, None, None
-
-
-class _BlockCEW(torch.autograd.Function):
-    """_BlockCE for nn.CrossEntropyLoss(weight=w, label_smoothing=eps): this block's train-row losses / `den`, the class weights of the
-    WHOLE graph's train rows summed (labels and mask are replicated: every rank forms the same device float, no collective)."""
-
-    @staticmethod
-    def forward(ctx, logits_b, yb, mb_u8, den, weight, eps):
-        L = _lib.lib()
-        n, C = logits_b.shape
-        dev = logits_b.device
-        if n == 0:
-            ctx.empty, ctx.C = True, C
-            return torch.zeros((), dtype=torch.float32, device=dev)
-        ctx.empty = False
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        row_lse, rowloss = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
-        den_b = torch.empty(1, dtype=torch.float32, device=dev)
-        _lib.check(L.sgs_masked_ce_w_fwd(ops._ptr(logits_b), n, C, ops._ptr(yb), ops._ptr(mb_u8), ops._ptr(weight), eps, ops._ptr(loss),
-                                         ops._ptr(row_lse), ops._ptr(rowloss), ops._ptr(den_b), ops._stream()), "sgs_masked_ce_w_fwd")
-        ctx.save_for_backward(logits_b, yb, mb_u8, row_lse, den, weight)
-        ctx.eps = eps
-        return torch.where(den[0] == 0, torch.full_like(den[0], float("nan")), rowloss.sum() / den[0])
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.empty:
             return torch.zeros(0, ctx.C, dtype=torch.float32, device=g.device), None, None, None, None, None
-        L = _lib.lib()
-        logits_b, yb, mb_u8, row_lse, den, weight = ctx.saved_tensors
-        n, C = logits_b.shape
-        g = g.reshape(1).contiguous().float()
-        d = torch.empty_like(logits_b)
-        _lib.check(L.sgs_masked_ce_w_bwd(ops._ptr(logits_b), n, C, ops._ptr(yb), ops._ptr(mb_u8), ops._ptr(weight), ctx.eps, ops._ptr(row_lse),
-                                         ops._ptr(den), ops._ptr(g), ops._ptr(d), ops._stream()), "sgs_masked_ce_w_bwd")
-        return d, None, None, None, None, None
+        logits_b, yb, mb_u8, row_lse, norm, weight = ctx.saved_tensors
+        return ops._masked_ce_bwd(logits_b, yb, mb_u8, weight, ctx.eps, row_lse, norm, g.reshape(1).contiguous().float()), None, None, None, None, None
 
 
 class _ShardedNormBlock(torch.autograd.Function):
@@ -875,9 +833,7 @@ def train_step_blocksharded(args, model, shard: EdgeShard, optimizer_gnn, optimi
             ce_den = torch.where(shard.train_mask, wy, torch.zeros_like(wy)).sum().reshape(1)
 
     def block_ce(logits_b):                                                 # the ranks' values sum to the replicated cross entropy
-        if ce_den is not None:
-            return _BlockCEW.apply(logits_b.contiguous(), yb, mb_u8, ce_den, ce_w, ce_eps)
-        return _BlockCE.apply(logits_b.contiguous(), yb, mb_u8, B.n_train)
+        return _BlockCE.apply(logits_b.contiguous(), yb, mb_u8, B.n_train if ce_den is None else ce_den, ce_w, ce_eps)
 
     learned_out, reg = None, None
     if update_edge_mlp:

@@ -1,5 +1,5 @@
-"""fp64 CPU restatement of the class-weighted, label-smoothed masked cross entropy (csrc/losses.hip: ce_rows_w, ce_final_w,
-ce_bwd_w<false> / ce_bwd_w<true>, hybrid_loss_final_w) and the seeded case table of tests/test_ce_weighted_cpu.py and
+"""fp64 CPU restatement of the class-weighted, label-smoothed masked cross entropy (csrc/losses.hip: ce_rows<true>, ce_final<true>,
+ce_bwd<true, false> / ce_bwd<true, true>, hybrid_loss_final<true>) and the seeded case table of tests/test_ce_weighted_cpu.py and
 tests/test_gpu_ce_weighted.py.  Plain torch on the CPU; nothing here imports the product.
 
 The definition of correct is F.cross_entropy(logits[mask], y[mask], weight=w, label_smoothing=eps, reduction="mean") in fp64
@@ -17,7 +17,7 @@ its backward puts -w[y_i] g / den = nan into the label's column of every train r
 (the bare quotient would give +-inf or nan entry by entry).  Without a train row there is no row to receive a gradient: d x = 0.
 
 `closed_form(c, torch.float32)` is the error model of loss_ref.bound, as in tests/loss_ref.py.  It is the form above as stated;
-`form="kernel"` writes the smoothing term as sum_c w_c (lse - x_c), the way ce_rows_w sums it.  tests/test_ce_weighted_cpu.py shows that
+`form="kernel"` writes the smoothing term as sum_c w_c (lse - x_c), the way ce_rows<true> sums it.  tests/test_ce_weighted_cpu.py shows that
 the two fp32 evaluations give the same bound on every case, the logits x 80 ones included (W lse - sum_c w_c x_c is of the order of W lse
 itself there: nothing cancels), so the stated form does not loosen the bound for the kernel.  `block_shares` is the node-block split of
 sharded.train_step_blocksharded: each block's row sum over the GLOBAL den."""

@@ -1,5 +1,5 @@
-"""GPU: the class-weighted / label-smoothed cross entropy on the hot path (csrc/losses.hip: ce_rows_w, ce_final_w, ce_bwd_w<acc>,
-hybrid_loss_final_w through ops.masked_cross_entropy / ops.hybrid_loss with keywords, training.train under args.sgs_hipgraph, and the two
+"""GPU: the class-weighted / label-smoothed cross entropy on the hot path (csrc/losses.hip: ce_rows<true>, ce_final<true>, ce_bwd<true, acc>,
+hybrid_loss_final<true> through ops.masked_cross_entropy / ops.hybrid_loss with keywords, training.train under args.sgs_hipgraph, and the two
 sharded trainers) against the fp64 closed form of tests/ce_weighted_ref.py, which tests/test_ce_weighted_cpu.py holds to torch's own
 F.cross_entropy.  Every floating quantity under loss_ref.bound -- 8 x the deviation of the fp32 evaluation of the closed form from the
 fp64 one + 4 ulp at the quantity's largest magnitude, per case and quantity --, nan patterns exactly, and what is bitwise by reading of the

@@ -102,7 +102,7 @@ def test_hybrid_loss_against_fp64(ops, name):
 def test_fused_equals_unfused(ops, name):
     """ops.hybrid_loss against ops.masked_cross_entropy + ops.edge_regularizers on the same inputs.  d w: the same kernel with the same
     arguments; d logits: the unfused path adds (softmax - onehot) g / n to the regularisers' rows by autograd's add, the fused one adds
-    the same product to the same rows inside ce_bwd_acc (the library is built without contraction: a product, then one add) -- both
+    the same product to the same rows inside ce_bwd<false, true> (the library is built without contraction: a product, then one add) -- both
     bitwise.  The five regulariser outputs come from the same partials through the same 256-stride finish: bitwise.  The cross entropy is
     summed over 256 strides here and 1024 there: both within the case's bound of the fp64 value, so within twice it of each other."""
     c = R.make_case(name)

@@ -6,7 +6,7 @@
 kernels: forward + backward of the cross entropy alone on a partition's logits at bench S3's partition shape (N = 1 013, C = 41) and
 S4's (N = 33 869, C = 5), 60 % train rows, HIP events around one forward + backward, three arms alternating in one process:
   (a) plain     ops.masked_cross_entropy(logits, y, mask)                                    (ce_rows, ce_final, ce_bwd)
-  (b) weighted  ops.masked_cross_entropy(logits, y, mask, weight=w, label_smoothing=0.1)     (ce_rows_w, ce_final_w, ce_bwd_w)
+  (b) weighted  ops.masked_cross_entropy(logits, y, mask, weight=w, label_smoothing=0.1)     (ce_rows<true>, ce_final<true>, ce_bwd<true, false>)
   (c) as given  nn.CrossEntropyLoss(weight=w, label_smoothing=0.1)(logits[mask], y[mask])    (the boolean-index gathers and their
                 device-to-host sync; what a run did with this criterion before the fused chain took it)
 (b) and (c) must agree to 1e-5 relative in loss and gradient, else the timing is void and the probe raises.  3 untimed rounds, then
