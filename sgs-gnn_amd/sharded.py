@@ -14,10 +14,18 @@ whose boundaries are multiples of the sampler chunk (2048).  Per rank and step:
     bias / ReLU / dropout run after the all-reduce on every rank (replicated).
 
 Built: the inference path (`sharded_evaluate_forward` = evaluate.py's learned mode) and the hybrid TRAINING
-step (`train_step_sharded`): replicated tensors enter sharded compute through `_F` (identity forward,
-all-reduce backward) and partial results leave through `_G` (all-reduce forward, identity backward), the
-gcn_norm backward's per-node term and the regulariser sums are all-reduced, so every rank finishes backward
-with complete, identical gradients and no separate gradient synchronisation is needed.
+step.  The step is ONE function, `_train_step`: the stage order and every tick of the noise and dropout clocks,
+which is what makes it reproduce the single-GPU `train()`.  It runs in two forms, each a small class of the
+places where they differ:
+  * `train_step_sharded` (`_AllReduceForm`): replicated tensors enter sharded compute through `_F` (identity
+    forward, all-reduce backward) and partial results leave through `_G` (all-reduce forward, identity
+    backward), so every rank finishes backward with complete, identical gradients and no separate gradient
+    synchronisation is needed;
+  * `train_step_blocksharded` (`_NodeBlockForm`): each rank keeps the node block its shard's sources span,
+    layers reduce-scatter forward and all-gather backward, and parameter gradients meet in one flat all-reduce.
+Both share the layer epilogue (`_BiasAct`), the norm (`_ShardedNorm`: the forms differ in who owns the
+self-loop term) and the regularisers; the gcn_norm backward's per-node term and the regulariser sums are
+all-reduced in either.
 Collectives go through torch.distributed: backend "nccl" is RCCL on ROCm; tests use gloo (R processes on one GPU).
 """
 from __future__ import annotations
@@ -204,21 +212,21 @@ def sharded_propagate(xl, nm, bias, act=ops.ACT_NONE, p=0.0, seed=0, site=0):
     return Y
 
 
+# (model attribute, refused when, the head as the message names it, what the single-GPU paths serve instead)
+_UNBUILT_HEADS = (("cheb_k", lambda v: v > 1, "ChebModel(cheb_k={})", "cheb_k > 1"),
+                  ("gat_edge_weight", bool, "GATModel(gat_edge_weight={})", "gat_edge_weight"),
+                  ("gat_v2", bool, "GATModel(gat_v2={})", "gat_v2"),
+                  ("gin_edge_weight", bool, "GINModel(gin_edge_weight={})", "gin_edge_weight"))
+
+
 def _no_cheb_order(model, where):
     """The sharded paths are written for the GCN head; a Chebyshev head of order > 1 must not fall into any K = 1 shortcut here, nor an
     edge-weighted GAT head into a path that drops the weights."""
-    if getattr(model, "cheb_k", 1) > 1:
-        raise NotImplementedError(f"{where}: ChebModel(cheb_k={model.cheb_k}) is not built for the sharded trainers (single-GPU train / "
-                                  "evaluate serve cheb_k > 1)")
-    if getattr(model, "gat_edge_weight", False):
-        raise NotImplementedError(f"{where}: GATModel(gat_edge_weight=True) is not built for the sharded trainers (single-GPU train / "
-                                  "evaluate serve gat_edge_weight)")
-    if getattr(model, "gat_v2", False):
-        raise NotImplementedError(f"{where}: GATModel(gat_v2=True) is not built for the sharded trainers (single-GPU train / evaluate serve "
-                                  "gat_v2)")
-    if getattr(model, "gin_edge_weight", False):
-        raise NotImplementedError(f"{where}: GINModel(gin_edge_weight=True) is not built for the sharded trainers (single-GPU train / "
-                                  "evaluate serve gin_edge_weight)")
+    for attr, refused, head, served in _UNBUILT_HEADS:
+        v = getattr(model, attr, 0)
+        if refused(v):
+            raise NotImplementedError(f"{where}: {head.format(v)} is not built for the sharded trainers (single-GPU train / evaluate serve "
+                                      f"{served})")
 
 
 @torch.no_grad()
@@ -248,10 +256,11 @@ def sharded_evaluate_forward(args, model, shard: EdgeShard, q: int, noise_local=
 
 
 # ======================================================================================================
-# Edge-sharded TRAINING step (hybrid pipeline).  Replicated tensors enter sharded compute through `_F`
-# (identity forward, all-reduce backward) and partial results leave it through `_G` (all-reduce forward,
-# identity backward), so every rank ends the backward pass with complete, identical parameter gradients
-# and the replicas stay in lock-step without a separate gradient synchronisation.
+# Edge-sharded TRAINING step (hybrid pipeline): the pieces of the ALL-REDUCE form, and those both forms share (the layer epilogue,
+# the norm, the regularisers).  Replicated tensors enter sharded compute through `_F` (identity forward, all-reduce backward) and
+# partial results leave it through `_G` (all-reduce forward, identity backward), so every rank ends the backward pass with complete,
+# identical parameter gradients and the replicas stay in lock-step without a separate gradient synchronisation.  The step itself
+# (`_train_step`) is at the end of the file, after the node-block pieces.
 # ======================================================================================================
 class _F(torch.autograd.Function):
     @staticmethod
@@ -281,15 +290,17 @@ class _G(torch.autograd.Function):
 
 
 class _BiasAct(torch.autograd.Function):
-    """Replicated layer epilogue after the embedding all-reduce: Y = act(X + bias)."""
+    """Layer epilogue Y = act(X + bias) on the rows row0 .. row0 + n - 1 of the node table (dropout is keyed by the global node id):
+    the whole table after the embedding all-reduce (row0 = 0), or one rank's block of rows."""
 
     @staticmethod
-    def forward(ctx, X, bias, act, p, seed, site):
+    def forward(ctx, X, bias, row0, act, p, seed, site):
         L = _lib.lib()
-        N, D = X.shape
+        n, D = X.shape
         Y = torch.empty_like(X)
-        _lib.check(L.sgs_bias_act(ops._ptr(X.contiguous()), ops._ptr(bias), N, D, act, float(p), seed, site, ops._ptr(Y), ops._stream()),
-                   "sgs_bias_act")
+        if n > 0:
+            _lib.check(L.sgs_bias_act_rows(ops._ptr(X.contiguous()), ops._ptr(bias), n, D, int(row0), act, float(p), seed, site, ops._ptr(Y),
+                                           ops._stream()), "sgs_bias_act_rows")
         ctx.act, ctx.p, ctx.has_bias = act, float(p), bias is not None
         ctx.save_for_backward(Y if act != ops.ACT_NONE else None)
         return Y
@@ -297,32 +308,51 @@ class _BiasAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dY):
         (Y,) = ctx.saved_tensors
-        # (the bias gradient as a column sum of its own, as ever: asked for with the activation it would become one fused pass)
-        dZ, _ = ops._grad_through_act(dY.contiguous(), Y, ctx.act, ctx.p, False)
-        return dZ, (ops._colsum(dZ) if ctx.has_bias else None), None, None, None, None
+        dY = dY.contiguous()
+        # (the bias gradient as a column sum of its own, not ops._grad_through_act's fused pass; and a rank's row block may be empty:
+        # then neither kernel is called)
+        dZ = ops._act_bwd(dY, Y, ctx.act, ctx.p) if ctx.act != ops.ACT_NONE and dY.numel() > 0 else dY
+        db = None
+        if ctx.has_bias:
+            db = ops._colsum(dZ) if dZ.shape[0] > 0 else torch.zeros(dZ.shape[1], dtype=dZ.dtype, device=dZ.device)
+        return dZ, db, None, None, None, None, None
+
+
+def _claim_loop(nm, own):
+    """Leave in nm.what_loop only the self-loop terms this rank adds (and differentiates).  own=None: all of them on rank 0, and no
+    diagonal at all on the other ranks; own=(lo, hi): those of the rank's own nodes.  Returns the 0 / 1 mask over the nodes, None
+    for own=None."""
+    if own is None:
+        if _world()[0] != 0:
+            nm.what_loop = None
+        return None
+    keep = torch.zeros_like(nm.what_loop)
+    keep[own[0]:own[1]] = 1.0
+    nm.what_loop = nm.what_loop * keep
+    return keep
 
 
 class _ShardedNorm(torch.autograd.Function):
-    """gcn_norm over the union of all ranks' edges, differentiable wrt this rank's edge weights."""
+    """gcn_norm over the union of all ranks' edges, differentiable wrt this rank's edge weights; `own`: _claim_loop."""
 
     @staticmethod
-    def forward(ctx, w, graph, box):
+    def forward(ctx, w, graph, box, own):
         nm = sharded_norm(graph, w)
-        if _world()[0] != 0:
-            nm.what_loop = None                      # the self-loop term is added (and differentiated) on rank 0 only
+        ctx.nm, ctx.keep = nm, _claim_loop(nm, own)
         box.append(nm)
-        ctx.nm = nm
         return torch.empty(graph.n_edges + graph.N, dtype=torch.float32, device=w.device)
 
     @staticmethod
     def backward(ctx, g):
         L = _lib.lib()
         nm, gr = ctx.nm, ctx.nm.graph
-        rank, world = _world()
         g = g.contiguous()
         n, N = gr.n_edges, gr.N
         gw = g[:n].contiguous() if n > 0 else torch.zeros(1, dtype=torch.float32, device=g.device)
-        gl = g[n:].contiguous() if rank == 0 else torch.zeros(N, dtype=torch.float32, device=g.device)
+        if ctx.keep is not None:
+            gl = (g[n:] * ctx.keep).contiguous()
+        else:
+            gl = g[n:].contiguous() if _world()[0] == 0 else torch.zeros(N, dtype=torch.float32, device=g.device)
         Hn = torch.empty(N, dtype=torch.float32, device=g.device)
         wv = nm.w if n > 0 else torch.zeros(1, dtype=torch.float32, device=g.device)
         _lib.check(L.sgs_gcn_norm_bwd_node(ops._ptr(wv), ops._ptr(gw), ops._ptr(gl), n, N, ops._ptr(nm.dis), ops._ptr(nm.loopw),
@@ -334,18 +364,18 @@ class _ShardedNorm(torch.autograd.Function):
         if n > 0:
             _lib.check(L.sgs_gcn_norm_bwd_edge(ops._ptr(gw), ops._ptr(gl), n, N, ops._ptr(nm.dis), ops._ptr(gr.loop_eid),
                                                ops._ptr(gr.edge_index), ops._ptr(Hn), ops._ptr(dw), ops._stream()), "sgs_gcn_norm_bwd_edge")
-        return dw, None, None
+        return dw, None, None, None
 
 
-def sharded_norm_autograd(graph, w):
-    rank, _ = _world()
+def sharded_norm_autograd(graph, w, own=None):
+    """sharded_norm with this rank's share of the self-loop term (`own`: _claim_loop) and, for weights that require a gradient, the
+    autograd handle the layers hang on."""
     if w is None or not (w.requires_grad and torch.is_grad_enabled()):
         nm = sharded_norm(graph, None if w is None else w.detach().contiguous())
-        if rank != 0:
-            nm.what_loop = None
+        _claim_loop(nm, own)
         return nm
     box = []
-    handle = _ShardedNorm.apply(w.contiguous(), graph, box)
+    handle = _ShardedNorm.apply(w.contiguous(), graph, box, own)
     nm = box[0]
     nm.handle = handle
     return nm
@@ -355,7 +385,7 @@ def sharded_gcn_layer(x, W, bias, nm, act=ops.ACT_NONE, p=0.0, seed=0, site=0):
     """One GCN layer on an edge-sharded graph with autograd: replicated X W^T -> f -> local aggregate -> g -> epilogue."""
     xl = _F.apply(ops.linear_nobias(x, W))
     part = ops._Propagate.apply(xl.contiguous(), nm.handle, None, nm, ops.ACT_NONE, 0.0, 0, 0)
-    return _BiasAct.apply(_G.apply(part), bias, act, float(p), int(seed), int(site))
+    return _BiasAct.apply(_G.apply(part), bias, 0, act, float(p), int(seed), int(site))
 
 
 class _ShardedEdgeReg(torch.autograd.Function):
@@ -409,80 +439,6 @@ def _criterion_spec(criterion, where):
     return spec
 
 
-def train_step_sharded(args, model, shard: EdgeShard, optimizer_gnn, optimizer_edge_prob, criterion, q: int, noise=None):
-    """One hybrid step (training_hybrid.py:35-141, mode 'learned', E > q, EdgeProbGCN scorer) on an edge-sharded
-    graph.  Dropout seeds / noise ticks are consumed in the same order as the single-GPU `train`, rows are
-    global ids, so the result matches the unsharded step up to fp32 summation order.  Returns a trace dict."""
-    _no_cover(args, "train_step_sharded")
-    from .model import _DropoutClock
-    from .sampling import _NoiseClock
-    _no_cheb_order(model, "train_step_sharded")
-    ce_w, ce_eps = _criterion_spec(criterion, "train_step_sharded")
-    noise = noise or {}
-    model.train()
-    optimizer_edge_prob.zero_grad()
-    optimizer_gnn.zero_grad()
-    sc = model.edge_prob_mlp
-    x, N, ei = shard.x, shard.N, shard.edge_index
-    p = sc.dropout.p
-    act = ops.ACT_RELU_DROPOUT if p > 0 else ops.ACT_RELU
-    off, bounds = shard.edge_offset, shard.bounds
-
-    # K0: prior-only draw (global), this rank's random edges
-    seed_n, tick = (0, 0) if noise.get("prior") is not None else _NoiseClock.next()
-    rs = dist_sample_topq(ops.SAMPLE_PRIOR, shard.prob, None, 0.0, q, ei, off, bounds, noise_local=noise.get("prior"), seed=seed_n,
-                          stream_id=tick)
-    g_r = ops.get_subgraph(ei, N, rs, eid=rs.eid - off)
-    nm_r = sharded_norm_autograd(g_r, None)
-    # scorer encoder over the random graph (model.py:106-108)
-    h = sharded_gcn_layer(x, sc.gcn1.lin.weight, sc.gcn1.bias, nm_r, act=act, p=p, seed=_DropoutClock.next_seed(), site=SITE_ENC)
-    codes = sharded_gcn_layer(h, sc.gcn2.lin.weight, sc.gcn2.bias, nm_r, act=ops.ACT_RELU)
-    # scores for this rank's edges; replicated inputs pass through f so their partial gradients are summed
-    active = ops.ActiveSet()
-    p_local = ops.edge_score(_F.apply(codes), _F.apply(sc.fc1.weight), _F.apply(sc.fc1.bias), _F.apply(sc.fc2.weight),
-                             _F.apply(sc.fc2.bias), ei, active=active, p=p, seed=_DropoutClock.next_seed(), site=SITE_SCORE,
-                             edge_id_offset=off, precision="fp32")
-    # K2+K3: learned draw (global)
-    seed_n, tick = (0, 0) if noise.get("sample") is not None else _NoiseClock.next()
-    smp = dist_sample_topq(ops.SAMPLE_LEARNED, p_local, shard.prob, args.degree_bias_coef, q, ei, off, bounds,
-                           noise_local=noise.get("sample"), seed=seed_n, stream_id=tick)
-    local_ids = smp.eid - off
-    g_s = ops.get_subgraph(ei, N, smp, eid=local_ids)
-    active.set(local_ids, g_s, ascending=True)           # (the draw compacts in edge order)
-    w_local = p_local.index_select(0, local_ids)
-    nm_s = sharded_norm_autograd(g_s, w_local)
-    pg = model.dropout.p
-    actg = ops.ACT_RELU_DROPOUT if pg > 0 else ops.ACT_RELU
-    h1 = sharded_gcn_layer(x, model.gcn1.lin.weight, model.gcn1.bias, nm_s, act=actg, p=pg, seed=_DropoutClock.next_seed(), site=SITE_GNN)
-    learned_out = sharded_gcn_layer(h1, model.gcn2.lin.weight, model.gcn2.bias, nm_s)
-    update_edge_mlp, random_out, counts = True, None, None
-    if args.conditional:
-        h1r = sharded_gcn_layer(x, model.gcn1.lin.weight, model.gcn1.bias, nm_r, act=actg, p=pg, seed=_DropoutClock.next_seed(),
-                                site=SITE_GNN)
-        random_out = sharded_gcn_layer(h1r, model.gcn2.lin.weight, model.gcn2.bias, nm_r)
-        cbuf = torch.empty(4, dtype=torch.int32, device=x.device)
-        ops.masked_correct(learned_out, shard.y, shard.train_mask, out=cbuf[0:2])
-        ops.masked_correct(random_out, shard.y, shard.train_mask, out=cbuf[2:4])
-        counts = cbuf.tolist()
-        update_edge_mlp = counts[0] > counts[2]                  # logits are replicated: every rank takes the same branch
-    if update_edge_mlp:
-        loss = ops.masked_cross_entropy(learned_out, shard.y, shard.train_mask, weight=ce_w, label_smoothing=ce_eps)
-        c1 = args.regularizer1_coef if args.reg1 else 0.0
-        c2 = args.consist_reg_coef if args.reg2 else 0.0
-        if c1 != 0.0 or c2 != 0.0:
-            loss = loss + _ShardedEdgeReg.apply(w_local.contiguous(), _F.apply(learned_out).contiguous(), smp.edge_index, shard.y,
-                                                ops._u8(shard.train_mask), g_s, float(c1), float(c2), q)
-        loss.backward()
-        optimizer_edge_prob.step()
-        optimizer_gnn.step()
-    else:
-        loss = ops.masked_cross_entropy(random_out, shard.y, shard.train_mask, weight=ce_w, label_smoothing=ce_eps)
-        loss.backward()
-        optimizer_gnn.step()
-    return dict(loss=loss.detach(), sample=smp, random=rs, update_edge_mlp=update_edge_mlp, learned_out=learned_out.detach(),
-                counts=counts)
-
-
 # ======================================================================================================
 # NODE-BLOCK variant of the edge-sharded step (SURVEY.md section 8e): half the embedding bytes of the all-reduce form.
 #
@@ -495,8 +451,29 @@ def train_step_sharded(args, model, shard: EdgeShard, optimizer_gnn, optimizer_e
 # rebuilt only where edges gather by arbitrary endpoint: the node codes for the scorer and the logits for the consistency
 # regulariser (all-gather forward, reduce-scatter backward).  The one source row a shard boundary may split is exchanged as a
 # one-row halo.  Parameter gradients are partial sums on every rank: ONE flat all-reduce at the end of backward.
-# Sampling, scoring, gcn_norm and the losses are the same kernels and collectives as in train_step_sharded.
+# Sampling, scoring, gcn_norm and the regularisers are the same kernels and collectives as in the all-reduce form, and the step is
+# the same `_train_step`: this section holds what `_NodeBlockForm` puts into it.
 # ======================================================================================================
+def block_layout(firsts, N: int, rank: int, world: int):
+    """The node blocks of `world` source-sorted edge shards over N nodes, from the first source of every shard (N for a shard
+    without edges), as `rank` sees them: (nb, lo, hi, halo_owner, halo, halo_users) -- the attributes of NodeBlocks.  Host
+    arithmetic on Python ints, no collective."""
+    nb = [int(f) for f in firsts]
+    for r in range(world - 2, -1, -1):                    # an empty shard owns nothing: its block collapses onto the next one's start
+        nb[r] = min(nb[r], nb[r + 1])
+    nb[0] = 0
+    nb.append(N)
+    lo, hi = nb[rank], nb[rank + 1]
+    size = [nb[r + 1] - nb[r] for r in range(world)]
+
+    def next_owner(r):                                    # the next rank with a non-empty block (a hub whose edges fill whole shards
+        return next((k for k in range(r + 1, world) if size[k] > 0), None)      # leaves empty blocks between)
+
+    halo_owner = next_owner(rank) if hi < N else None     # owner of node `hi`
+    halo_users = [r for r in range(rank) if size[rank] > 0 and nb[r + 1] == lo and next_owner(r) == rank]
+    return nb, lo, hi, halo_owner, 0 if halo_owner is None else 1, halo_users
+
+
 class NodeBlocks:
     """nb [R+1]: rank r owns nodes nb[r] .. nb[r+1]-1 and needs the source rows nb[r] .. nb[r+1] (the last one is the halo: the
     first node of the next non-empty block, whose edges may start in this shard)."""
@@ -509,25 +486,12 @@ class NodeBlocks:
         if n > 1 and not bool((ei[0, 1:] >= ei[0, :-1]).all()):
             raise RuntimeError("NodeBlocks: the shard's edge list is not sorted by source (ClusterData / ResidentPartitions emit it sorted)")
         first = ei[0, :1].clone() if n > 0 else torch.full((1,), shard.N, dtype=torch.int64, device=dev)
+        firsts = [first]
         if _comm():
             firsts = [torch.empty_like(first) for _ in range(world)]
             dist.all_gather(firsts, first)
-            nb = [int(f) for f in firsts]
-        else:
-            nb = [int(first)]
-        nb[0] = 0
-        for r in range(len(nb) - 2, -1, -1):              # an empty shard owns nothing: its block collapses onto the next one's start
-            nb[r] = min(nb[r], nb[r + 1])
-        nb[0] = 0
-        self.nb = nb + [shard.N]
-        self.lo, self.hi = self.nb[rank], self.nb[rank + 1]
-        size = [self.nb[r + 1] - self.nb[r] for r in range(world)]
-        # owner of node `hi` = the next rank with a non-empty block (a hub whose edges fill whole shards leaves empty blocks between)
-        self.halo_owner = next((r for r in range(rank + 1, world) if size[r] > 0), None) if self.hi < shard.N else None
-        self.halo = 0 if self.halo_owner is None else 1
-        self.halo_users = [r for r in range(rank) if size[rank] > 0 and self.nb[r + 1] == self.lo
-                           and next((k for k in range(r + 1, world) if size[k] > 0), None) == rank]
-        self.maxb = max(size)
+        self.nb, self.lo, self.hi, self.halo_owner, self.halo, self.halo_users = block_layout(firsts, shard.N, rank, world)
+        self.maxb = max(self.nb[r + 1] - self.nb[r] for r in range(world))
         n_tot = shard.train_mask.sum().to(torch.int32).reshape(1)          # the mask is replicated: every rank counts the same rows
         self.n_train = n_tot.contiguous()
 
@@ -647,33 +611,6 @@ class _EmbedRows(torch.autograd.Function):
         return g[ctx.a:ctx.a + ctx.n].contiguous(), None, None
 
 
-class _BiasActRows(torch.autograd.Function):
-    """Layer epilogue on a block of rows; dropout rows are global node ids (sgs_bias_act_rows)."""
-
-    @staticmethod
-    def forward(ctx, X, bias, row0, act, p, seed, site):
-        L = _lib.lib()
-        n, D = X.shape
-        Y = torch.empty_like(X)
-        if n > 0:
-            _lib.check(L.sgs_bias_act_rows(ops._ptr(X.contiguous()), ops._ptr(bias), n, D, int(row0), act, float(p), seed, site, ops._ptr(Y),
-                                           ops._stream()), "sgs_bias_act_rows")
-        ctx.act, ctx.p, ctx.has_bias = act, float(p), bias is not None
-        ctx.save_for_backward(Y if act != ops.ACT_NONE else None)
-        return Y
-
-    @staticmethod
-    def backward(ctx, dY):
-        (Y,) = ctx.saved_tensors
-        dY = dY.contiguous()
-        # (not ops._grad_through_act: a rank's row block may be empty, and then neither kernel is called)
-        dZ = ops._act_bwd(dY, Y, ctx.act, ctx.p) if ctx.act != ops.ACT_NONE and dY.numel() > 0 else dY
-        db = None
-        if ctx.has_bias:
-            db = ops._colsum(dZ) if dZ.shape[0] > 0 else torch.zeros(dZ.shape[1], dtype=dZ.dtype, device=dZ.device)
-        return dZ, db, None, None, None, None, None
-
-
 class _BlockCE(torch.autograd.Function):
     """This block's share of nn.CrossEntropyLoss(weight=w, label_smoothing=eps)(logits[train], y[train]): sum of the block's train-row
     losses / `norm`, the divisor of the WHOLE graph, so the ranks' values add up to the replicated loss (training_hybrid.py:113).  `norm` is
@@ -703,55 +640,6 @@ class _BlockCE(torch.autograd.Function):
         return ops._masked_ce_bwd(logits_b, yb, mb_u8, weight, ctx.eps, row_lse, norm, g.reshape(1).contiguous().float()), None, None, None, None, None
 
 
-class _ShardedNormBlock(torch.autograd.Function):
-    """As _ShardedNorm, with the self-loop term owned (added and differentiated) by the rank that owns the node."""
-
-    @staticmethod
-    def forward(ctx, w, graph, box, lo, hi):
-        nm = sharded_norm(graph, w)
-        keep = torch.zeros_like(nm.what_loop)
-        keep[lo:hi] = 1.0
-        nm.what_loop = nm.what_loop * keep
-        box.append(nm)
-        ctx.nm, ctx.keep = nm, keep
-        return torch.empty(graph.n_edges + graph.N, dtype=torch.float32, device=w.device)
-
-    @staticmethod
-    def backward(ctx, g):
-        L = _lib.lib()
-        nm, gr = ctx.nm, ctx.nm.graph
-        g = g.contiguous()
-        n, N = gr.n_edges, gr.N
-        gw = g[:n].contiguous() if n > 0 else torch.zeros(1, dtype=torch.float32, device=g.device)
-        gl = (g[n:] * ctx.keep).contiguous()
-        Hn = torch.empty(N, dtype=torch.float32, device=g.device)
-        wv = nm.w if n > 0 else torch.zeros(1, dtype=torch.float32, device=g.device)
-        _lib.check(L.sgs_gcn_norm_bwd_node(ops._ptr(wv), ops._ptr(gw), ops._ptr(gl), n, N, ops._ptr(nm.dis), ops._ptr(nm.loopw),
-                                           ops._ptr(gr.in_ptr), ops._ptr(gr.in_src), ops._ptr(gr.in_eid), ops._ptr(gr.out_ptr),
-                                           ops._ptr(gr.out_dst), ops._ptr(gr.out_eid), ops._ptr(Hn), ops._stream()), "sgs_gcn_norm_bwd_node")
-        if _comm():
-            dist.all_reduce(Hn)
-        dw = torch.empty(n, dtype=torch.float32, device=g.device)
-        if n > 0:
-            _lib.check(L.sgs_gcn_norm_bwd_edge(ops._ptr(gw), ops._ptr(gl), n, N, ops._ptr(nm.dis), ops._ptr(gr.loop_eid),
-                                               ops._ptr(gr.edge_index), ops._ptr(Hn), ops._ptr(dw), ops._stream()), "sgs_gcn_norm_bwd_edge")
-        return dw, None, None, None, None
-
-
-def _block_norm(graph, w, B: NodeBlocks):
-    if w is None or not (w.requires_grad and torch.is_grad_enabled()):
-        nm = sharded_norm(graph, None if w is None else w.detach().contiguous())
-        keep = torch.zeros_like(nm.what_loop)
-        keep[B.lo:B.hi] = 1.0
-        nm.what_loop = nm.what_loop * keep
-        return nm
-    box = []
-    handle = _ShardedNormBlock.apply(w.contiguous(), graph, box, B.lo, B.hi)
-    nm = box[0]
-    nm.handle = handle
-    return nm
-
-
 def block_gcn_layer(src_rows, W, bias, nm, B: NodeBlocks, act=ops.ACT_NONE, p=0.0, seed=0, site=0):
     """One GCN layer in node-block form.  `src_rows` [rows + halo, Fin]: the layer input for this rank's source rows; returns the
     layer output for this rank's BLOCK [rows, D]."""
@@ -759,99 +647,104 @@ def block_gcn_layer(src_rows, W, bias, nm, B: NodeBlocks, act=ops.ACT_NONE, p=0.
     xl = _EmbedRows.apply(xl_rows, B.lo, B.N)
     part = ops._Propagate.apply(xl, nm.handle, None, nm, ops.ACT_NONE, 0.0, 0, 0)      # this rank's edges -> partial [N, D]
     yb = _RS.apply(part, B)
-    return _BiasActRows.apply(yb, bias, B.lo, act, float(p), int(seed), int(site))
+    return _BiasAct.apply(yb, bias, B.lo, act, float(p), int(seed), int(site))
 
 
-def train_step_blocksharded(args, model, shard: EdgeShard, optimizer_gnn, optimizer_edge_prob, criterion, q: int, noise=None):
-    """train_step_sharded with the GCN layers in node-block form (reduce-scatter forward / all-gather backward, node-level work on
-    1 / R of the rows): same draws (bit for bit), same logits and gradients up to fp32 summation order.  Returns the same trace dict;
-    `learned_out` is the full [N, C] table (all-gathered for the regulariser anyway)."""
-    _no_cover(args, "train_step_blocksharded")
-    from .model import _DropoutClock
-    from .sampling import _NoiseClock
-    _no_cheb_order(model, "train_step_blocksharded")
-    ce_w, ce_eps = _criterion_spec(criterion, "train_step_blocksharded")
-    noise = noise or {}
-    model.train()
-    optimizer_edge_prob.zero_grad()
-    optimizer_gnn.zero_grad()
-    sc = model.edge_prob_mlp
-    x, N, ei = shard.x, shard.N, shard.edge_index
-    p = sc.dropout.p
-    act = ops.ACT_RELU_DROPOUT if p > 0 else ops.ACT_RELU
-    off, bounds = shard.edge_offset, shard.bounds
-    B = node_blocks(shard)
-    x_rows = x[B.lo:B.hi + B.halo]
-    yb, mb = shard.y[B.lo:B.hi].contiguous(), shard.train_mask[B.lo:B.hi].contiguous()
+# ======================================================================================================
+# The training step.  `_train_step` holds the stage order and every tick of the noise and dropout clocks once -- that order is what
+# makes a sharded step reproduce the single-GPU `train()` -- and a form object holds what the two forms do differently: how a norm is
+# built, what a layer takes and returns, how codes / logits become a full table and how scorer parameters enter, the gate counts, the
+# cross entropy, what follows backward() and how the reported loss is formed.
+# ======================================================================================================
+class _AllReduceForm:
+    """Every node-level tensor is the full table, replicated; parameter gradients are complete when backward() returns."""
 
-    seed_n, tick = (0, 0) if noise.get("prior") is not None else _NoiseClock.next()
-    rs = dist_sample_topq(ops.SAMPLE_PRIOR, shard.prob, None, 0.0, q, ei, off, bounds, noise_local=noise.get("prior"), seed=seed_n,
-                          stream_id=tick)
-    g_r = ops.get_subgraph(ei, N, rs, eid=rs.eid - off)
-    nm_r = _block_norm(g_r, None, B)
-    h = block_gcn_layer(x_rows, sc.gcn1.lin.weight, sc.gcn1.bias, nm_r, B, act=act, p=p, seed=_DropoutClock.next_seed(), site=SITE_ENC)
-    codes_b = block_gcn_layer(_Halo.apply(h, B), sc.gcn2.lin.weight, sc.gcn2.bias, nm_r, B, act=ops.ACT_RELU)
-    codes = _AG.apply(codes_b, B)                                           # the scorer gathers codes by arbitrary endpoint
-    active = ops.ActiveSet()
-    p_local = ops.edge_score(codes, sc.fc1.weight, sc.fc1.bias, sc.fc2.weight, sc.fc2.bias, ei, active=active, p=p,
-                             seed=_DropoutClock.next_seed(), site=SITE_SCORE, edge_id_offset=off, precision="fp32")
-    seed_n, tick = (0, 0) if noise.get("sample") is not None else _NoiseClock.next()
-    smp = dist_sample_topq(ops.SAMPLE_LEARNED, p_local, shard.prob, args.degree_bias_coef, q, ei, off, bounds,
-                           noise_local=noise.get("sample"), seed=seed_n, stream_id=tick)
-    local_ids = smp.eid - off
-    g_s = ops.get_subgraph(ei, N, smp, eid=local_ids)
-    active.set(local_ids, g_s, ascending=True)           # (the draw compacts in edge order)
-    w_local = p_local.index_select(0, local_ids)
-    nm_s = _block_norm(g_s, w_local, B)
-    pg = model.dropout.p
-    actg = ops.ACT_RELU_DROPOUT if pg > 0 else ops.ACT_RELU
-    h1 = block_gcn_layer(x_rows, model.gcn1.lin.weight, model.gcn1.bias, nm_s, B, act=actg, p=pg, seed=_DropoutClock.next_seed(), site=SITE_GNN)
-    out_b = block_gcn_layer(_Halo.apply(h1, B), model.gcn2.lin.weight, model.gcn2.bias, nm_s, B)
-    update_edge_mlp, random_b, counts = True, None, None
-    dev = x.device
-    if args.conditional:
-        h1r = block_gcn_layer(x_rows, model.gcn1.lin.weight, model.gcn1.bias, nm_r, B, act=actg, p=pg, seed=_DropoutClock.next_seed(), site=SITE_GNN)
-        random_b = block_gcn_layer(_Halo.apply(h1r, B), model.gcn2.lin.weight, model.gcn2.bias, nm_r, B)
-        cbuf = torch.zeros(4, dtype=torch.int32, device=dev)
-        if B.rows > 0:
-            ops.masked_correct(out_b, yb, mb, out=cbuf[0:2])
-            ops.masked_correct(random_b, yb, mb, out=cbuf[2:4])
+    def __init__(self, shard: EdgeShard):
+        self.shard, self.x = shard, shard.x
+
+    def norm(self, graph, w):
+        return sharded_norm_autograd(graph, w)
+
+    def layer(self, h, W, bias, nm, **kw):
+        return sharded_gcn_layer(h, W, bias, nm, **kw)
+
+    def rows(self, h):                                   # a layer's output as the next layer's input
+        return h
+
+    def table(self, t):                                  # replicated inputs of per-edge work pass through f: their partial gradients are summed
+        return _F.apply(t)
+
+    param = table
+
+    def gate_counts(self, out, rnd):
+        cbuf = torch.empty(4, dtype=torch.int32, device=out.device)
+        ops.masked_correct(out, self.shard.y, self.shard.train_mask, out=cbuf[0:2])
+        ops.masked_correct(rnd, self.shard.y, self.shard.train_mask, out=cbuf[2:4])
+        return cbuf.tolist()                             # logits are replicated: every rank takes the same branch
+
+    def ce(self, logits, weight, eps):
+        return ops.masked_cross_entropy(logits, self.shard.y, self.shard.train_mask, weight=weight, label_smoothing=eps)
+
+    def after_backward(self, model):
+        pass
+
+    def reported_loss(self, loss, ce, reg):
+        return loss.detach()
+
+    def full_logits(self, out, table):
+        return out.detach()
+
+
+class _NodeBlockForm:
+    """Node-level tensors are this rank's block of rows (layer inputs: plus the halo row); parameter gradients are partial sums."""
+
+    def __init__(self, shard: EdgeShard):
+        self.shard, self.B = shard, node_blocks(shard)
+        B = self.B
+        self.x = shard.x[B.lo:B.hi + B.halo]
+        self.y, self.mask = shard.y[B.lo:B.hi].contiguous(), shard.train_mask[B.lo:B.hi].contiguous()
+
+    def norm(self, graph, w):
+        return sharded_norm_autograd(graph, w, own=(self.B.lo, self.B.hi))
+
+    def layer(self, src_rows, W, bias, nm, **kw):
+        return block_gcn_layer(src_rows, W, bias, nm, self.B, **kw)
+
+    def rows(self, h):
+        return _Halo.apply(h, self.B)
+
+    def table(self, block):                              # per-edge work gathers rows by arbitrary endpoint
+        return _AG.apply(block, self.B)
+
+    def param(self, t):
+        return t
+
+    def gate_counts(self, out, rnd):
+        cbuf = torch.zeros(4, dtype=torch.int32, device=out.device)
+        if self.B.rows > 0:
+            ops.masked_correct(out, self.y, self.mask, out=cbuf[0:2])
+            ops.masked_correct(rnd, self.y, self.mask, out=cbuf[2:4])
         if _comm():
-            dist.all_reduce(cbuf)                                           # gate counts: block sums -> global
-        counts = cbuf.tolist()
-        update_edge_mlp = counts[0] > counts[2]
+            dist.all_reduce(cbuf)                                           # block sums -> global
+        return cbuf.tolist()
 
-    mb_u8 = ops._u8(mb)
+    def ce(self, logits_b, weight, eps):
+        """This block's share: the ranks' values sum to the replicated cross entropy (_BlockCE)."""
+        mask_u8 = ops._u8(self.mask)
+        den = self.B.n_train
+        if weight is not None or eps != 0.0:
+            weight, eps = ops.check_ce_spec(logits_b, weight, eps)
+            if weight is None:
+                den = den.to(torch.float32)
+            else:                                                           # (labels and mask are replicated: the same word on every rank)
+                wy = weight[self.shard.y.clamp(0, weight.numel() - 1)]
+                den = torch.where(self.shard.train_mask, wy, torch.zeros_like(wy)).sum().reshape(1)
+        return _BlockCE.apply(logits_b.contiguous(), self.y, mask_u8, den, weight, eps)
 
-    ce_den = None
-    if ce_w is not None or ce_eps != 0.0:
-        ce_w, ce_eps = ops.check_ce_spec(out_b, ce_w, ce_eps)
-        if ce_w is None:
-            ce_den = B.n_train.to(torch.float32)
-        else:                                                               # (labels and mask are replicated: the same word on every rank)
-            wy = ce_w[shard.y.clamp(0, ce_w.numel() - 1)]
-            ce_den = torch.where(shard.train_mask, wy, torch.zeros_like(wy)).sum().reshape(1)
-
-    def block_ce(logits_b):                                                 # the ranks' values sum to the replicated cross entropy
-        return _BlockCE.apply(logits_b.contiguous(), yb, mb_u8, B.n_train if ce_den is None else ce_den, ce_w, ce_eps)
-
-    learned_out, reg = None, None
-    if update_edge_mlp:
-        ce = block_ce(out_b)
-        loss = ce
-        c1 = args.regularizer1_coef if args.reg1 else 0.0
-        c2 = args.consist_reg_coef if args.reg2 else 0.0
-        learned_out = _AG.apply(out_b, B)                                   # the consistency regulariser gathers logits by endpoint
-        if c1 != 0.0 or c2 != 0.0:
-            reg = _ShardedEdgeReg.apply(w_local.contiguous(), learned_out.contiguous(), smp.edge_index, shard.y, ops._u8(shard.train_mask),
-                                        g_s, float(c1), float(c2), q)
-            loss = ce + reg                        # the global value on every rank; its backward yields this rank's edges' share only
-        loss.backward()
-    else:
-        ce = block_ce(random_b)
-        ce.backward()
-    # every parameter gradient is a partial sum: ONE flat all-reduce
-    if _comm():                                    # (every rank built the same autograd graph, so the same parameters hold gradients)
+    def after_backward(self, model):
+        if not _comm():
+            return
+        # ONE flat all-reduce (every rank built the same autograd graph, so the same parameters hold gradients)
         params = [p_ for p_ in model.parameters() if p_.grad is not None]
         flat = torch.cat([p_.grad.reshape(-1) for p_ in params])
         dist.all_reduce(flat)
@@ -860,14 +753,95 @@ def train_step_blocksharded(args, model, shard: EdgeShard, optimizer_gnn, optimi
             n_ = p_.numel()
             p_.grad.copy_(flat[o:o + n_].view_as(p_))
             o += n_
-    total = ce.detach().clone()
-    if _comm():
-        dist.all_reduce(total)
-    if reg is not None:
-        total = total + reg.detach()
+
+    def reported_loss(self, loss, ce, reg):
+        total = ce.detach().clone()
+        if _comm():
+            dist.all_reduce(total)
+        return total if reg is None else total + reg.detach()               # (the regulariser's value is global already)
+
+    def full_logits(self, out_b, table):
+        return table.detach() if table is not None else _gather_blocks(out_b.detach(), self.B)
+
+
+def _train_step(Form, where, args, model, shard: EdgeShard, optimizer_gnn, optimizer_edge_prob, criterion, q: int, noise):
+    """One hybrid step (training_hybrid.py:35-141, mode 'learned', E > q, EdgeProbGCN scorer) on an edge-sharded graph, in the form
+    `Form` builds.  Dropout seeds / noise ticks are consumed in the same order as the single-GPU `train`, rows are global ids, so the
+    result matches the unsharded step up to fp32 summation order.  Returns a trace dict."""
+    _no_cover(args, where)
+    from .model import _DropoutClock
+    from .sampling import _NoiseClock
+    _no_cheb_order(model, where)
+    ce_w, ce_eps = _criterion_spec(criterion, where)
+    noise = noise or {}
+    model.train()
+    optimizer_edge_prob.zero_grad()
+    optimizer_gnn.zero_grad()
+    sc = model.edge_prob_mlp
+    N, ei, off = shard.N, shard.edge_index, shard.edge_offset
+    form = Form(shard)
+
+    def draw(mode, given, p_, prior, c):                  # one global draw; a noise array given by the caller takes no clock tick
+        seed_n, tick = (0, 0) if noise.get(given) is not None else _NoiseClock.next()
+        return dist_sample_topq(mode, p_, prior, c, q, ei, off, shard.bounds, noise_local=noise.get(given), seed=seed_n, stream_id=tick)
+
+    def two_layers(m, nm, site, act2=ops.ACT_NONE):       # gcn1 -> ReLU (-> dropout) -> gcn2 of the scorer's encoder or of the head
+        p = m.dropout.p
+        h = form.layer(form.x, m.gcn1.lin.weight, m.gcn1.bias, nm, act=ops.ACT_RELU_DROPOUT if p > 0 else ops.ACT_RELU, p=p,
+                       seed=_DropoutClock.next_seed(), site=site)
+        return form.layer(form.rows(h), m.gcn2.lin.weight, m.gcn2.bias, nm, act=act2)
+
+    # K0: prior-only draw, this rank's random edges; the scorer's encoder over the random graph (model.py:106-108)
+    rs = draw(ops.SAMPLE_PRIOR, "prior", shard.prob, None, 0.0)
+    g_r = ops.get_subgraph(ei, N, rs, eid=rs.eid - off)
+    nm_r = form.norm(g_r, None)
+    codes = form.table(two_layers(sc, nm_r, SITE_ENC, ops.ACT_RELU))
+    # scores for this rank's edges
+    active = ops.ActiveSet()
+    p_local = ops.edge_score(codes, form.param(sc.fc1.weight), form.param(sc.fc1.bias), form.param(sc.fc2.weight), form.param(sc.fc2.bias),
+                             ei, active=active, p=sc.dropout.p, seed=_DropoutClock.next_seed(), site=SITE_SCORE, edge_id_offset=off,
+                             precision="fp32")
+    # K2+K3: learned draw, the head over its subgraph
+    smp = draw(ops.SAMPLE_LEARNED, "sample", p_local, shard.prob, args.degree_bias_coef)
+    local_ids = smp.eid - off
+    g_s = ops.get_subgraph(ei, N, smp, eid=local_ids)
+    active.set(local_ids, g_s, ascending=True)           # (the draw compacts in edge order)
+    w_local = p_local.index_select(0, local_ids)
+    nm_s = form.norm(g_s, w_local)
+    out = two_layers(model, nm_s, SITE_GNN)
+    update_edge_mlp, rnd, counts = True, None, None
+    if args.conditional:
+        rnd = two_layers(model, nm_r, SITE_GNN)
+        counts = form.gate_counts(out, rnd)
+        update_edge_mlp = counts[0] > counts[2]
+    table, reg = None, None
+    if update_edge_mlp:
+        loss = ce = form.ce(out, ce_w, ce_eps)
+        c1 = args.regularizer1_coef if args.reg1 else 0.0
+        c2 = args.consist_reg_coef if args.reg2 else 0.0
+        table = form.table(out)                          # the consistency regulariser gathers logits by endpoint
+        if c1 != 0.0 or c2 != 0.0:
+            reg = _ShardedEdgeReg.apply(w_local.contiguous(), table.contiguous(), smp.edge_index, shard.y, ops._u8(shard.train_mask), g_s,
+                                        float(c1), float(c2), q)
+            loss = ce + reg                              # the global value on every rank; its backward yields this rank's edges' share only
+    else:
+        loss = ce = form.ce(rnd, ce_w, ce_eps)
+    loss.backward()
+    form.after_backward(model)
+    total = form.reported_loss(loss, ce, reg)
     if update_edge_mlp:
         optimizer_edge_prob.step()
     optimizer_gnn.step()
-    if learned_out is None:
-        learned_out = _gather_blocks(out_b.detach(), B)
-    return dict(loss=total, sample=smp, random=rs, update_edge_mlp=update_edge_mlp, learned_out=learned_out.detach(), counts=counts)
+    return dict(loss=total, sample=smp, random=rs, update_edge_mlp=update_edge_mlp, learned_out=form.full_logits(out, table), counts=counts)
+
+
+def train_step_sharded(args, model, shard: EdgeShard, optimizer_gnn, optimizer_edge_prob, criterion, q: int, noise=None):
+    """The step in the all-reduce form: partial [N, D] aggregates are all-reduced, everything node-level runs replicated."""
+    return _train_step(_AllReduceForm, "train_step_sharded", args, model, shard, optimizer_gnn, optimizer_edge_prob, criterion, q, noise)
+
+
+def train_step_blocksharded(args, model, shard: EdgeShard, optimizer_gnn, optimizer_edge_prob, criterion, q: int, noise=None):
+    """The step with the GCN layers in node-block form (reduce-scatter forward / all-gather backward, node-level work on 1 / R of the
+    rows): same draws (bit for bit), same logits and gradients up to fp32 summation order.  Returns the same trace dict; `learned_out`
+    is the full [N, C] table (all-gathered for the regulariser anyway)."""
+    return _train_step(_NodeBlockForm, "train_step_blocksharded", args, model, shard, optimizer_gnn, optimizer_edge_prob, criterion, q, noise)
