@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -795,7 +796,7 @@ class ActiveSet:
 
     def set(self, eid: torch.Tensor, graph: Graph, ascending=None):
         """eid: the active edges' ids into the scored edge list, any order, each at most once; graph: the Graph of edge_index[:, eid] in
-        that same order (its edge k is active row k).  The fused scorer backward (_edge_score_backward_fused) additionally needs the rows
+        that same order (its edge k is active row k).  The fused scorer backward (_score_bwd_fused) additionally needs the rows
         grouped by source -- `eid` ascending on a source-sorted edge list -- and runs only when `ascending` holds; any other order takes
         the unfused mask-form backward, which is correct for every order.  ascending=True: the caller guarantees it (the sampler's
         compaction and the sharded local ids emit edge order); nothing is checked.  None: checked here with one read-back, and taken as
@@ -858,6 +859,7 @@ def _endpoint_reduce(M_out, M_in, T, graph: Graph, s_out, s_in, H):
 _mask_backward = True        # False: the dense fp32 dv path at every size (tests compare the two)
 _fwd_mask = True             # False: the forward keeps no mask; the backward recomputes the hidden layer (sgs_edge_score_bwd_core_bits)
 _fused_backward = os.environ.get("SGS_FUSED_BWD", "1") != "0"   # False: feat / dfeat as [n, H] arrays and sgs_endpoint_reduce_pair_bits (the form for edge lists not sorted by source)
+_PRODUCTION_ROWS = 65536     # rows (scored edges in the forward, active rows in the backward) from which the production-size kernels are chosen
 
 
 def src_sorted(edge_index: torch.Tensor) -> bool:
@@ -923,6 +925,79 @@ class scorer_precision:
         return False
 
 
+class _FwdPlan(NamedTuple):
+    form: str              # "mask": keeps the ReLU x dropout bit of every hidden unit for the backward / "paired" / "plain"
+    bf16: bool             # the one-product kernels (the entry point's "_bf16" twin)
+    ask_sorted: bool       # the fused backward may follow if the edge list is sorted by source: worth asking src_sorted() (after the launch)
+
+
+class _BwdPlan(NamedTuple):
+    form: str              # "dense" / "recompute" (mask form, hidden layer recomputed) / "kept" (mask form on the forward's bits) / "fused"
+    bf16: bool
+    core: bool = True      # the dense form's own choices: run the core at all (no active row: nothing to launch),
+    row_gemm: bool = False       # dfeat as the bf16x6 row GEMM (else F.linear),
+    fused_colsum: bool = False   # d b1 as a by-product of the d W1a GEMM (else a column sum of its own),
+    pair_reduce: bool = False    # both endpoint reductions in one pass (H % 4 == 0)
+
+
+_FWD_ENTRY = {"mask": "sgs_edge_score_fwd_mask", "paired": "sgs_edge_score_fwd_paired", "plain": "sgs_edge_score_fwd"}
+
+
+def _plan_forward(L, E, H, precision, want_dcodes, has_pairs) -> _FwdPlan:
+    """Every choice of one scorer forward, from sizes, switches and the library's host answers alone (no tensor is touched).  The
+    library's variant overrides (sgs_edge_score_set_variant / _set_bwd_variant) win over the bf16 mode and over the mask-keeping forward,
+    which is always the bf16x6 loop: only at their defaults may either stand in for the kernels a test or the bench asked for by name."""
+    big = E >= _PRODUCTION_ROWS
+    default = big and L.sgs_edge_score_get_variant() < 0 and L.sgs_edge_score_get_bwd_variant() < 0
+    bf16 = bool(default and precision == "bf16" and L.sgs_edge_score_bf16_supported(H))
+    if default and _fwd_mask and _mask_backward and want_dcodes and L.sgs_edge_score_bwd_bits_supported(H):
+        return _FwdPlan("mask", bf16, bool(_fused_backward))       # a forward whose backward will follow
+    if has_pairs and big and L.sgs_edge_score_paired_supported(H):
+        return _FwdPlan("paired", bf16, False)       # undirected graph stored both ways: the canonical half runs the contraction, every mate rides along
+    return _FwdPlan("plain", bf16, False)
+
+
+def _plan_backward(L, n, H, kept, bf16, src_sorted, want_dcodes, ascending) -> _BwdPlan:
+    """Every choice of one scorer backward over n active rows.  kept / bf16 / src_sorted: what the forward recorded (_ScoreSaved);
+    ascending: ActiveSet.ascending, None when every edge is active (in edge order).  The one-product contractions need the mask the forward
+    kept (a recompute would be the fp32 function's), and a kept mask goes unused when the active set turns out too small for the mask-form
+    kernels: the dense form recomputes.  The fused form needs the active rows grouped by source: a source-sorted edge list read in
+    ascending edge order."""
+    big = n >= _PRODUCTION_ROWS
+    if _mask_backward and big and L.sgs_edge_score_bwd_bits_supported(H) and L.sgs_gemm_tn_mask_supported(n, H, H) and want_dcodes:
+        if not kept:
+            return _BwdPlan("recompute", False)
+        return _BwdPlan("fused" if src_sorted and _fused_backward and ascending is not False else "kept", bool(bf16))
+    return _BwdPlan("dense", False, n > 0, bool(big and L.sgs_edge_score_bwd_dfeat_supported(H)), bool(L.sgs_gemm_tn_can_colsum(n, H, H)), H % 4 == 0)
+
+
+def _call(L, name, bf16, *args):
+    """Run entry point `name`, or its one-product twin `name`_bf16, and check the answer under the name that ran."""
+    name = name + "_bf16" if bf16 else name
+    _lib.check(getattr(L, name)(*args), name)
+
+
+class _ScoreSaved(NamedTuple):
+    """What the scorer's backward reads (_edge_score_backward): _EdgeScore.backward builds it from its ctx, torch_ops.edge_score_backward
+    from its arguments."""
+    codes: torch.Tensor
+    U: torch.Tensor                   # codes W1b^T
+    W1: torch.Tensor
+    b1: torch.Tensor
+    w2: torch.Tensor
+    b2: torch.Tensor
+    edge_index: torch.Tensor
+    kept: Optional[tuple]             # (maskbits, scores) of a mask-keeping forward, else None
+    active: Optional[ActiveSet]
+    p: float
+    seed: int
+    site: int
+    offset: int
+    bf16: bool = False                # the forward ran the one-product kernels
+    src_sorted: bool = False          # a mask-keeping forward found its edge list sorted by source (_FwdPlan.ask_sorted)
+    want_dcodes: bool = True          # codes wants a gradient
+
+
 class _EdgeScore(torch.autograd.Function):
     """K1b with the node-level half of fc1 inside: U = codes W1b^T (library GEMM) in forward; in backward d codes gets dU W1b on
     top of the direct term, and BOTH halves of d fc1.weight [H, 2H] are written in place by the two weight-gradient GEMMs
@@ -936,233 +1011,198 @@ class _EdgeScore(torch.autograd.Function):
         U = torch.mm(codes, W1[:, H:].t())
         out = torch.empty(E, dtype=torch.float32, device=codes.device)
         ws = workspace(L.sgs_edge_score_workspace_bytes(N, H, E), codes.device)
-        maskbits = None
-        # the bf16 mode applies where the fp32-faithful path runs the bf16x6 loop (variant overrides win over the mode)
-        bf16 = (precision == "bf16" and E >= 65536 and L.sgs_edge_score_bf16_supported(H) and _variant_overrides_are_default())
-        if (_fwd_mask and _mask_backward and E >= 65536 and L.sgs_edge_score_bwd_bits_supported(H) and ctx.needs_input_grad[0]
-                and _variant_overrides_are_default()):
-            # a forward whose backward will follow: keep the ReLU x dropout mask of every scored edge (one bit per hidden unit), so that the
-            # backward needs no recompute of the hidden layer (_edge_score_backward_mask)
-            maskbits = torch.empty(E, H // 32, dtype=torch.int32, device=codes.device)
-            canon, mate = pairs if pairs is not None else (None, None)
-            fn = L.sgs_edge_score_fwd_mask_bf16 if bf16 else L.sgs_edge_score_fwd_mask
-            _lib.check(fn(_ptr(codes, torch.float32), _ptr(U, torch.float32), N, H, _ptr(edge_index, torch.int64), E,
-                          edge_id_offset, _ptr(canon, torch.int32), 0 if canon is None else canon.numel(),
-                          _ptr(mate, torch.int32), _ptr(W1, torch.float32), _ptr(b1), _ptr(w2), _ptr(b2), float(p), seed, site,
-                          _ptr(out), _ptr(maskbits), ws.data_ptr(), ws.numel(), _stream()), "sgs_edge_score_fwd_mask")
-        elif pairs is not None and E >= 65536 and L.sgs_edge_score_paired_supported(H):
-            # undirected graph stored both ways: the canonical half of the edges runs the contraction, every mate rides along
-            canon, mate = pairs
-            fn = L.sgs_edge_score_fwd_paired_bf16 if bf16 else L.sgs_edge_score_fwd_paired
-            _lib.check(fn(_ptr(codes, torch.float32), _ptr(U, torch.float32), N, H, _ptr(edge_index, torch.int64), E,
-                          edge_id_offset, _ptr(canon, torch.int32), canon.numel(), _ptr(mate, torch.int32),
-                          _ptr(W1, torch.float32), _ptr(b1), _ptr(w2), _ptr(b2), float(p), seed, site, _ptr(out),
-                          ws.data_ptr(), ws.numel(), _stream()), "sgs_edge_score_fwd_paired")
-        else:
-            fn = L.sgs_edge_score_fwd_bf16 if bf16 else L.sgs_edge_score_fwd
-            _lib.check(fn(_ptr(codes, torch.float32), _ptr(U, torch.float32), N, H, _ptr(edge_index, torch.int64), E,
-                          edge_id_offset, _ptr(W1, torch.float32), _ptr(b1), _ptr(w2), _ptr(b2), float(p), seed, site, _ptr(out),
-                          ws.data_ptr(), ws.numel(), _stream()), "sgs_edge_score_fwd")
-        PRECISION_COUNTS["fwd_bf16" if bf16 else "fwd_fp32"] += 1
+        plan = _plan_forward(L, E, H, precision, ctx.needs_input_grad[0], pairs is not None)
+        maskbits = torch.empty(E, H // 32, dtype=torch.int32, device=codes.device) if plan.form == "mask" else None
+        canon, mate = pairs if pairs is not None else (None, None)
+        # the three forms take the same arguments but for the pairs (mask, paired) and the mask to keep (mask)
+        pair_args = () if plan.form == "plain" else (_ptr(canon, torch.int32), 0 if canon is None else canon.numel(), _ptr(mate, torch.int32))
+        _call(L, _FWD_ENTRY[plan.form], plan.bf16, _ptr(codes, torch.float32), _ptr(U, torch.float32), N, H, _ptr(edge_index, torch.int64), E,
+              edge_id_offset, *pair_args, _ptr(W1, torch.float32), _ptr(b1), _ptr(w2), _ptr(b2), float(p), seed, site, _ptr(out),
+              *(() if maskbits is None else (_ptr(maskbits),)), ws.data_ptr(), ws.numel(), _stream())
+        PRECISION_COUNTS["fwd_bf16" if plan.bf16 else "fwd_fp32"] += 1
         ctx.save_for_backward(codes, U, W1, b1, w2, b2, edge_index, *((maskbits, out) if maskbits is not None else ()))
-        ctx.active, ctx.p, ctx.seed, ctx.site, ctx.offset = active, float(p), seed, site, edge_id_offset
-        # the backward's one-piece contractions need the mask this forward kept (a recompute would be the fp32 function's)
-        ctx.bf16 = bf16 and maskbits is not None
-        # the fused backward needs the active rows grouped by source: true for a drawn subset (ascending ids) of a row-sorted list
-        ctx.src_sorted = maskbits is not None and _fused_backward and src_sorted(edge_index)
+        # (src_sorted may read a word back the first time it sees an edge list: asked only where the plan needs it, and after the launch)
+        ctx.active, ctx.cfg = active, (float(p), seed, site, edge_id_offset, plan.bf16, plan.ask_sorted and src_sorted(edge_index))
         return out
 
     @staticmethod
     def backward(ctx, gp):
-        L = _lib.lib()
-        codes, U, W1, b1, w2, b2, edge_index = ctx.saved_tensors[:7]
-        kept = ctx.saved_tensors[7:]                  # (maskbits, p) when the forward kept the mask
-        N, H = codes.shape
-        E = edge_index.shape[1]
-        dev = codes.device
-        act = ctx.active
-        if act is not None and act.eid is not None:
-            eid, graph = act.eid, act.graph
-            n = eid.numel()
-            tok = _zero_token(dev)
-            if act.gq is not None and gp.numel() == E and gp.stride(0) == 0 and gp.data_ptr() == tok.data_ptr():
-                gp_act = act.gq                     # handed over by _SelectSampled: `gp` is the stride-0 zero, nothing to gather
-            else:
-                gp_act = gp.index_select(0, eid)
-                if act.gq is not None:              # another consumer of the scores contributed a dense gradient as well
-                    gp_act = gp_act + act.gq
-            act.gq = None
-        else:
-            eid, graph, n = None, get_graph(edge_index, N), E
-            gp_act = gp.contiguous()
-        f32 = dict(dtype=torch.float32, device=dev)
-        if (_mask_backward and n >= 65536 and L.sgs_edge_score_bwd_bits_supported(H) and L.sgs_gemm_tn_mask_supported(n, H, H)
-                and ctx.needs_input_grad[0]):
-            PRECISION_COUNTS["bwd_bf16" if ctx.bf16 and kept else "bwd_fp32"] += 1
-            return _EdgeScore._backward_mask(ctx, L, codes, U, W1, b1, w2, b2, edge_index, eid, graph, n, gp_act, kept)
-        PRECISION_COUNTS["bwd_fp32"] += 1
-        # (a kept mask goes unused when the active set turns out too small for the mask-form kernels: the dense path recomputes)
-        dv, feat = torch.empty(n, H, **f32), torch.empty(n, H, **f32)
-        tile = L.sgs_edge_score_bwd_tile()
-        hdz = torch.empty((n + tile - 1) // tile, H, **f32)          # per-tile column sums of dz * hidden (rows sum to d w2)
-        dz = torch.empty(n, **f32)
-        if n > 0:
-            ws = workspace(L.sgs_edge_score_workspace_bytes(N, H, 0), dev)
-            _lib.check(L.sgs_edge_score_bwd_core(_ptr(codes), _ptr(U), N, H, _ptr(edge_index), E, ctx.offset, _ptr(eid), n, _ptr(gp_act),
-                                                 _ptr(W1), _ptr(b1), _ptr(w2), _ptr(b2), ctx.p, ctx.seed, ctx.site, _ptr(dv),
-                                                 _ptr(hdz), _ptr(dz), _ptr(feat), ws.data_ptr(), ws.numel(), _stream()),
-                       "sgs_edge_score_bwd_core")
-        if n >= 65536 and L.sgs_edge_score_bwd_dfeat_supported(H):
-            # dfeat = dv W1a on the forward's bf16x6 loop as a row GEMM (fp32-faithful): ~75 us at 100 k rows against 122 us below
-            dfeat = torch.empty(n, H, **f32)
-            wsd = workspace(L.sgs_edge_score_workspace_bytes(0, H, 0), dev)
-            _lib.check(L.sgs_edge_score_bwd_dfeat(_ptr(dv), n, H, _ptr(W1), _ptr(dfeat), wsd.data_ptr(), wsd.numel(), _stream()),
-                       "sgs_edge_score_bwd_dfeat")
-        else:
-            # as F.linear with a contiguous W1a^T: the vendor GEMM runs that form at 110 TFLOP/s (85 with the strided view)
-            W1a_t = W1[:, :H].t().contiguous()
-            dfeat = torch.nn.functional.linear(dv, W1a_t)          # [n,H]
-        # d fc1.weight [H, 2H], both halves written in place.  Left: dW1a = dv^T feat (K = n rows): sgs_gemm_tn's tall-K kernel (the
-        # vendor GEMM picks a 42 TFLOP/s kernel for this shape), with d b1 = colsum(dv) as a by-product of the same pass over dv
-        dW1 = torch.empty_like(W1)
-        wsg = workspace(L.sgs_gemm_tn_workspace_bytes(n, H, H), dev)
-        if L.sgs_gemm_tn_can_colsum(n, H, H):
-            db1 = torch.empty(H, dtype=torch.float32, device=dev)
-            _lib.check(L.sgs_gemm_tn_ld(_ptr(dv), _ptr(feat), n, H, H, _ptr(dW1), 2 * H, _ptr(db1), wsg.data_ptr(), wsg.numel(), _stream()),
-                       "sgs_gemm_tn_ld")
-        else:
-            _lib.check(L.sgs_gemm_tn_ld(_ptr(dv), _ptr(feat), n, H, H, _ptr(dW1), 2 * H, None, wsg.data_ptr(), wsg.numel(), _stream()),
-                       "sgs_gemm_tn_ld")
-            db1 = _colsum(dv)
-        dw2 = _colsum(hdz)
-        db2 = _colsum(dz.view(n, 1)).reshape(1)
-        if H % 4 == 0:                                         # both endpoint reductions in one pass over the incident-edge lists
-            dcodes = torch.empty(N, H, dtype=torch.float32, device=dev)
-            dU = torch.empty(N, H, dtype=torch.float32, device=dev)
-            _lib.check(L.sgs_endpoint_reduce_pair(_ptr(dfeat), _ptr(dv), _ptr(codes), N, H, graph.n_edges, _ptr(graph.in_ptr), _ptr(graph.in_src),
-                                                  _ptr(graph.in_eid), _ptr(graph.out_ptr), _ptr(graph.out_dst), _ptr(graph.out_eid),
-                                                  _ptr(dcodes), _ptr(dU), _stream()), "sgs_endpoint_reduce_pair")
-        else:
-            dcodes = _endpoint_reduce(dfeat, dfeat, codes, graph, 1.0, 1.0, H)
-            dU = _endpoint_reduce(dv, dv, None, graph, 1.0, -1.0, H)
-        # the node-level half: U = codes W1b^T  ->  d codes += dU W1b (library GEMM, accumulating),  d W1b = dU^T codes (right half)
-        if ctx.needs_input_grad[0]:
-            dcodes.addmm_(dU, W1[:, H:])                           # in place (beta = 1): no copy of dcodes
-        _leaf_dw(dU, codes, N, H, H, leaf=(ctx, 1), out=dW1, col0=H)
-        return dcodes, dW1, db1, dw2, db2, None, None, None, None, None, None, None, None
+        t = ctx.saved_tensors
+        saved = _ScoreSaved(*t[:7], t[7:] or None, ctx.active, *ctx.cfg, ctx.needs_input_grad[0])
+        return _edge_score_backward(saved, gp, leaf=(ctx, 1)) + (None,) * 8
 
 
-def _variant_overrides_are_default() -> bool:
-    """True while the library's forward / backward variant overrides are at their defaults (sgs_edge_score_set_variant(-1),
-    sgs_edge_score_set_bwd_variant(-1)): only then may the mask-keeping forward (always the bf16x6 loop) stand in for the kernels a test or
-    the bench asked for by name."""
+def _active_rows(act, gp, edge_index, N):
+    """The rows a scorer backward runs over, (eid, graph, n, gp_act): the ActiveSet's, with their upstream gradient -- act.gq as it is when
+    _SelectSampled handed it over and `gp` is its stride-0 zero (nothing to gather), else gp[eid] (+ act.gq) -- or every edge (eid None).
+    act.gq is taken: it is None afterwards."""
+    if act is None or act.eid is None:
+        return None, get_graph(edge_index, N), edge_index.shape[1], gp.contiguous()
+    eid, tok = act.eid, _zero_token(gp.device)
+    if act.gq is not None and gp.numel() == edge_index.shape[1] and gp.stride(0) == 0 and gp.data_ptr() == tok.data_ptr():
+        gp_act = act.gq
+    else:
+        gp_act = gp.index_select(0, eid)
+        if act.gq is not None:              # another consumer of the scores contributed a dense gradient as well
+            gp_act = gp_act + act.gq
+    act.gq = None
+    return eid, act.graph, eid.numel(), gp_act
+
+
+def _edge_score_backward(s: _ScoreSaved, gp, leaf=None):
+    """-> (d codes, d fc1.weight, d fc1.bias, d fc2.weight, d fc2.bias).  `leaf`: _leaf_dw's handle on fc1.weight in the running
+    backward node, None outside one."""
     L = _lib.lib()
-    return L.sgs_edge_score_get_variant() < 0 and L.sgs_edge_score_get_bwd_variant() < 0
+    N, H = s.codes.shape
+    eid, graph, n, gp_act = _active_rows(s.active, gp, s.edge_index, N)
+    plan = _plan_backward(L, n, H, s.kept is not None, s.bf16, s.src_sorted, s.want_dcodes, None if eid is None else s.active.ascending)
+    PRECISION_COUNTS["bwd_bf16" if plan.bf16 else "bwd_fp32"] += 1
+    dcodes, dU, dW1, db1, dw2, db2 = _SCORE_BWD[plan.form](L, s, plan, eid, graph, n, gp_act)
+    # the node-level half: U = codes W1b^T  ->  d codes += dU W1b (library GEMM, accumulating),  d W1b = dU^T codes (right half of
+    # d fc1.weight, in place)
+    if s.want_dcodes:
+        dcodes.addmm_(dU, s.W1[:, H:])                             # in place (beta = 1): no copy of dcodes
+    _leaf_dw(dU, s.codes, N, H, H, leaf=leaf, out=dW1, col0=H)
+    return dcodes, dW1, db1, dw2, db2
 
 
-def _edge_score_backward_mask(ctx, L, codes, U, W1, b1, w2, b2, edge_index, eid, graph, n, gp_act, kept=()):
+def _score_bwd_dense(L, s, plan, eid, graph, n, gp_act):
+    """dv as an fp32 [n, H] matrix, the hidden layer recomputed: every size and hidden width.  (With no row at all only the core is
+    skipped; the other launches accept n = 0 and write the zeros -- _EdgeScoreEPD returns early instead, both on purpose.  d w2 / d b2 are
+    this form's own column sums of hdz / dz: the mask forms get them from their consumers.)"""
+    N, H = s.codes.shape
+    dev = s.codes.device
+    dv, feat = _empty_f32(n, H, device=dev), _empty_f32(n, H, device=dev)
+    tile = L.sgs_edge_score_bwd_tile()
+    hdz = _empty_f32((n + tile - 1) // tile, H, device=dev)          # per-tile column sums of dz * hidden (rows sum to d w2)
+    dz = _empty_f32(n, device=dev)
+    if plan.core:
+        ws = workspace(L.sgs_edge_score_workspace_bytes(N, H, 0), dev)
+        _lib.check(L.sgs_edge_score_bwd_core(_ptr(s.codes), _ptr(s.U), N, H, _ptr(s.edge_index), s.edge_index.shape[1], s.offset, _ptr(eid), n,
+                                             _ptr(gp_act), _ptr(s.W1), _ptr(s.b1), _ptr(s.w2), _ptr(s.b2), s.p, s.seed, s.site, _ptr(dv),
+                                             _ptr(hdz), _ptr(dz), _ptr(feat), ws.data_ptr(), ws.numel(), _stream()), "sgs_edge_score_bwd_core")
+    if plan.row_gemm:
+        # dfeat = dv W1a on the forward's bf16x6 loop as a row GEMM (fp32-faithful): ~75 us at 100 k rows against 122 us below
+        dfeat = _empty_f32(n, H, device=dev)
+        wsd = workspace(L.sgs_edge_score_workspace_bytes(0, H, 0), dev)
+        _lib.check(L.sgs_edge_score_bwd_dfeat(_ptr(dv), n, H, _ptr(s.W1), _ptr(dfeat), wsd.data_ptr(), wsd.numel(), _stream()),
+                   "sgs_edge_score_bwd_dfeat")
+    else:
+        # as F.linear with a contiguous W1a^T: the vendor GEMM runs that form at 110 TFLOP/s (85 with the strided view)
+        dfeat = torch.nn.functional.linear(dv, s.W1[:, :H].t().contiguous())          # [n,H]
+    # d fc1.weight [H, 2H], both halves written in place.  Left: dW1a = dv^T feat (K = n rows): sgs_gemm_tn's tall-K kernel (the
+    # vendor GEMM picks a 42 TFLOP/s kernel for this shape), with d b1 = colsum(dv) as a by-product of the same pass over dv
+    dW1 = torch.empty_like(s.W1)
+    wsg = workspace(L.sgs_gemm_tn_workspace_bytes(n, H, H), dev)
+    db1 = _empty_f32(H, device=dev) if plan.fused_colsum else None
+    _lib.check(L.sgs_gemm_tn_ld(_ptr(dv), _ptr(feat), n, H, H, _ptr(dW1), 2 * H, _ptr(db1), wsg.data_ptr(), wsg.numel(), _stream()),
+               "sgs_gemm_tn_ld")
+    if db1 is None:
+        db1 = _colsum(dv)
+    dw2 = _colsum(hdz)
+    db2 = _colsum(dz.view(n, 1)).reshape(1)
+    if plan.pair_reduce:                                   # both endpoint reductions in one pass over the incident-edge lists
+        dcodes, dU = _empty_f32(N, H, device=dev), _empty_f32(N, H, device=dev)
+        _lib.check(L.sgs_endpoint_reduce_pair(_ptr(dfeat), _ptr(dv), _ptr(s.codes), N, H, graph.n_edges, _ptr(graph.in_ptr), _ptr(graph.in_src),
+                                              _ptr(graph.in_eid), _ptr(graph.out_ptr), _ptr(graph.out_dst), _ptr(graph.out_eid),
+                                              _ptr(dcodes), _ptr(dU), _stream()), "sgs_endpoint_reduce_pair")
+    else:
+        dcodes = _endpoint_reduce(dfeat, dfeat, s.codes, graph, 1.0, 1.0, H)
+        dU = _endpoint_reduce(dv, dv, None, graph, 1.0, -1.0, H)
+    return dcodes, dU, dW1, db1, dw2, db2
+
+
+def _dropout_scale(p):
+    """1 / (1 - p) as the kernels form it: 1.0f / (1.0f - p)."""
+    return float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
+
+
+def _dw2_parts(N, H, dev):
+    """(Traw, craw, Rraw): what the weight-gradient GEMM and the endpoint reduction leave for sgs_edge_score_dw2_from_parts."""
+    return _empty_f32(H, H, device=dev), _empty_f32(H, device=dev), _empty_f32(N, H, device=dev)
+
+
+def _dw2_from_parts(L, s, Traw, craw, Rraw):
+    N, H = s.codes.shape
+    dw2 = _empty_f32(H, device=s.codes.device)
+    _lib.check(L.sgs_edge_score_dw2_from_parts(_ptr(s.W1), _ptr(Traw), _ptr(s.U), _ptr(Rraw), _ptr(s.b1), _ptr(craw), N, H, s.p, _ptr(dw2), _stream()),
+               "sgs_edge_score_dw2_from_parts")
+    return dw2
+
+
+def _score_bwd_mask(L, s, plan, eid, graph, n, gp_act):
     """The backward at production size in its MASK form (include/sgs_hip.h, sgs_edge_score_bwd_core_bits): dv = dz x [hidden > 0] x w2 / (1 - p)
     never exists as an fp32 [n, H] matrix -- the core writes one bit per entry and the three consumers rebuild what they need, the two
-    contractions with a 0 / 1 operand at half the MFMA work."""
-    N, H = codes.shape
-    E = edge_index.shape[1]
-    dev = codes.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    p = ctx.p
+    contractions with a 0 / 1 operand at half the MFMA work.  "kept": the forward kept the mask and p, so nothing is recomputed -- dz, the
+    active rows' mask and feat in one pass, d fc2.weight from the consumers' parts; "recompute": the core forms them, and d fc2.weight's
+    per-tile sums."""
+    N, H = s.codes.shape
+    E = s.edge_index.shape[1]
+    dev = s.codes.device
     bits = torch.empty(n, H // 32, dtype=torch.int32, device=dev)
-    dz = torch.empty(n, **f32)
-    # the fused form needs the active rows grouped by source: a source-sorted edge list (ctx.src_sorted) read in ascending edge order
-    # (eid None: every edge active, in edge order; else ActiveSet.ascending)
-    in_order = eid is None or bool(getattr(ctx.active, "ascending", False))
-    if kept and getattr(ctx, "src_sorted", False) and _fused_backward and in_order:
-        return _edge_score_backward_fused(ctx, L, codes, U, W1, b1, w2, edge_index, eid, graph, n, gp_act, kept, bits, dz)
-    feat = torch.empty(n, H, **f32)
+    dz, feat = _empty_f32(n, device=dev), _empty_f32(n, H, device=dev)
     hdz = Traw = craw = Rraw = None
-    if kept:
-        # the forward kept the mask and p: no recompute -- dz, the active rows' mask and feat in one pass; d fc2.weight from the consumers' parts
-        maskbits, p_out = kept
-        _lib.check(L.sgs_edge_score_bwd_prep(_ptr(codes), N, H, _ptr(edge_index), E, _ptr(eid), n, _ptr(gp_act), _ptr(p_out), _ptr(maskbits),
+    if plan.form == "kept":
+        maskbits, p_out = s.kept
+        _lib.check(L.sgs_edge_score_bwd_prep(_ptr(s.codes), N, H, _ptr(s.edge_index), E, _ptr(eid), n, _ptr(gp_act), _ptr(p_out), _ptr(maskbits),
                                              _ptr(dz), _ptr(bits), _ptr(feat), _stream()), "sgs_edge_score_bwd_prep")
-        Traw, craw, Rraw = torch.empty(H, H, **f32), torch.empty(H, **f32), torch.empty(N, H, **f32)
+        Traw, craw, Rraw = _dw2_parts(N, H, dev)
     else:
         tile = L.sgs_edge_score_bwd_tile()
-        hdz = torch.empty((n + tile - 1) // tile, H, **f32)
+        hdz = _empty_f32((n + tile - 1) // tile, H, device=dev)
         ws = workspace(L.sgs_edge_score_workspace_bytes(N, H, 0), dev)
-        _lib.check(L.sgs_edge_score_bwd_core_bits(_ptr(codes), _ptr(U), N, H, _ptr(edge_index), E, ctx.offset, _ptr(eid), n, _ptr(gp_act), _ptr(W1),
-                                                  _ptr(b1), _ptr(w2), _ptr(b2), p, ctx.seed, ctx.site, _ptr(bits), _ptr(hdz), _ptr(dz), _ptr(feat),
-                                                  ws.data_ptr(), ws.numel(), _stream()), "sgs_edge_score_bwd_core_bits")
-    dfeat = torch.empty(n, H, **f32)
+        _lib.check(L.sgs_edge_score_bwd_core_bits(_ptr(s.codes), _ptr(s.U), N, H, _ptr(s.edge_index), E, s.offset, _ptr(eid), n, _ptr(gp_act),
+                                                  _ptr(s.W1), _ptr(s.b1), _ptr(s.w2), _ptr(s.b2), s.p, s.seed, s.site, _ptr(bits), _ptr(hdz), _ptr(dz),
+                                                  _ptr(feat), ws.data_ptr(), ws.numel(), _stream()), "sgs_edge_score_bwd_core_bits")
+    dfeat = _empty_f32(n, H, device=dev)
     wsd = workspace(L.sgs_edge_score_workspace_bytes(0, H, 0), dev)
-    bf16 = bool(kept) and getattr(ctx, "bf16", False)
-    _lib.check((L.sgs_edge_score_bwd_dfeat_bits_bf16 if bf16 else L.sgs_edge_score_bwd_dfeat_bits)(_ptr(bits), _ptr(dz), n, H, _ptr(W1), _ptr(w2), p, _ptr(dfeat), wsd.data_ptr(), wsd.numel(),
-                                               _stream()), "sgs_edge_score_bwd_dfeat_bits")
-    dW1 = torch.empty_like(W1)
-    db1 = torch.empty(H, **f32)
-    scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))        # as the kernels form it: 1.0f / (1.0f - p)
+    _call(L, "sgs_edge_score_bwd_dfeat_bits", plan.bf16, _ptr(bits), _ptr(dz), n, H, _ptr(s.W1), _ptr(s.w2), s.p, _ptr(dfeat), wsd.data_ptr(),
+          wsd.numel(), _stream())
+    dW1 = torch.empty_like(s.W1)
+    db1, db2 = _empty_f32(H, device=dev), _empty_f32(1, device=dev)
     wsg = workspace(L.sgs_gemm_tn_workspace_bytes(n, H, H), dev)
-    db2 = torch.empty(1, **f32)
-    _lib.check((L.sgs_gemm_tn_mask_bf16 if bf16 else L.sgs_gemm_tn_mask)(_ptr(bits), _ptr(dz), _ptr(w2), scale, _ptr(feat), n, H, H, _ptr(dW1), 2 * H, _ptr(db1), _ptr(db2), _ptr(Traw),
-                                  _ptr(craw), wsg.data_ptr(), wsg.numel(), _stream()), "sgs_gemm_tn_mask")
+    _call(L, "sgs_gemm_tn_mask", plan.bf16, _ptr(bits), _ptr(dz), _ptr(s.w2), _dropout_scale(s.p), _ptr(feat), n, H, H, _ptr(dW1), 2 * H, _ptr(db1),
+          _ptr(db2), _ptr(Traw), _ptr(craw), wsg.data_ptr(), wsg.numel(), _stream())
     dw2 = _colsum(hdz) if hdz is not None else None
-    dcodes = torch.empty(N, H, **f32)
-    dU = torch.empty(N, H, **f32)
-    _lib.check(L.sgs_endpoint_reduce_pair_bits(_ptr(dfeat), _ptr(bits), _ptr(dz), _ptr(w2), p, _ptr(codes), N, H, graph.n_edges, _ptr(graph.in_ptr),
+    dcodes, dU = _empty_f32(N, H, device=dev), _empty_f32(N, H, device=dev)
+    _lib.check(L.sgs_endpoint_reduce_pair_bits(_ptr(dfeat), _ptr(bits), _ptr(dz), _ptr(s.w2), s.p, _ptr(s.codes), N, H, graph.n_edges, _ptr(graph.in_ptr),
                                                _ptr(graph.in_src), _ptr(graph.in_eid), _ptr(graph.out_ptr), _ptr(graph.out_dst),
                                                _ptr(graph.out_eid), _ptr(dcodes), _ptr(dU), _ptr(Rraw), _stream()), "sgs_endpoint_reduce_pair_bits")
-    if dw2 is None:
-        dw2 = torch.empty(H, **f32)
-        _lib.check(L.sgs_edge_score_dw2_from_parts(_ptr(W1), _ptr(Traw), _ptr(U), _ptr(Rraw), _ptr(b1), _ptr(craw), N, H, p, _ptr(dw2), _stream()),
-                   "sgs_edge_score_dw2_from_parts")
-    return _edge_score_backward_mask_tail(ctx, L, codes, W1, dcodes, dU, dW1, db1, dw2, db2)
+    return dcodes, dU, dW1, db1, (dw2 if dw2 is not None else _dw2_from_parts(L, s, Traw, craw, Rraw)), db2
 
 
-def _edge_score_backward_fused(ctx, L, codes, U, W1, b1, w2, edge_index, eid, graph, n, gp_act, kept, bits, dz):
+def _score_bwd_fused(L, s, plan, eid, graph, n, gp_act):
     """The no-recompute backward with neither feat nor dfeat as [n, H] arrays (include/sgs_hip.h, "FUSED form"): the active rows are sorted
     by source, so the by-source half of d codes is reduced inside the dfeat contraction's epilogue, and the weight-gradient GEMM gathers
     x_s * x_d itself.  Six launches: prep (dz, mask rows, endpoints; it also packs dfeat's W1a operand), dfeat + by-source sums, d W1a and
     its slab reduction, the endpoint reductions, d fc2.weight."""
-    N, H = codes.shape
-    E = edge_index.shape[1]
-    dev = codes.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    p = ctx.p
-    maskbits, p_out = kept
+    N, H = s.codes.shape
+    dev = s.codes.device
+    maskbits, p_out = s.kept
+    bits = torch.empty(n, H // 32, dtype=torch.int32, device=dev)
+    dz = _empty_f32(n, device=dev)
     sd = torch.empty(n, 2, dtype=torch.int32, device=dev)
     wsd = workspace(L.sgs_edge_score_workspace_bytes(0, H, 0), dev)
-    bf16 = getattr(ctx, "bf16", False)
-    _lib.check((L.sgs_edge_score_bwd_prep_sd_pack_bf16 if bf16 else L.sgs_edge_score_bwd_prep_sd_pack)(_ptr(codes), N, H, _ptr(edge_index), E, _ptr(eid), n, _ptr(gp_act), _ptr(p_out), _ptr(maskbits),
-                                                 _ptr(dz), _ptr(bits), _ptr(sd), _ptr(W1), _ptr(w2), p, wsd.data_ptr(), wsd.numel(), _stream()),
-               "sgs_edge_score_bwd_prep_sd_pack")
-    G = torch.empty(n, H, **f32)
-    opart = torch.empty(L.sgs_edge_score_bwd_fused_opart_rows(n, N), H, **f32)
-    _lib.check((L.sgs_edge_score_bwd_dfeat_fused_packed_bf16 if bf16 else L.sgs_edge_score_bwd_dfeat_fused_packed)(_ptr(bits), _ptr(dz), _ptr(sd), _ptr(codes), n, N, H, _ptr(G), _ptr(opart), wsd.data_ptr(),
-                                                       wsd.numel(), _stream()), "sgs_edge_score_bwd_dfeat_fused_packed")
-    dW1 = torch.empty_like(W1)
-    db1, db2 = torch.empty(H, **f32), torch.empty(1, **f32)
-    Traw, craw, Rraw = torch.empty(H, H, **f32), torch.empty(H, **f32), torch.empty(N, H, **f32)
-    scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
+    _call(L, "sgs_edge_score_bwd_prep_sd_pack", plan.bf16, _ptr(s.codes), N, H, _ptr(s.edge_index), s.edge_index.shape[1], _ptr(eid), n, _ptr(gp_act),
+          _ptr(p_out), _ptr(maskbits), _ptr(dz), _ptr(bits), _ptr(sd), _ptr(s.W1), _ptr(s.w2), s.p, wsd.data_ptr(), wsd.numel(), _stream())
+    G = _empty_f32(n, H, device=dev)
+    opart = _empty_f32(L.sgs_edge_score_bwd_fused_opart_rows(n, N), H, device=dev)
+    _call(L, "sgs_edge_score_bwd_dfeat_fused_packed", plan.bf16, _ptr(bits), _ptr(dz), _ptr(sd), _ptr(s.codes), n, N, H, _ptr(G), _ptr(opart),
+          wsd.data_ptr(), wsd.numel(), _stream())
+    dW1 = torch.empty_like(s.W1)
+    db1, db2 = _empty_f32(H, device=dev), _empty_f32(1, device=dev)
+    Traw, craw, Rraw = _dw2_parts(N, H, dev)
     wsg = workspace(L.sgs_gemm_tn_workspace_bytes(n, H, H), dev)
-    _lib.check((L.sgs_gemm_tn_mask_gather_bf16 if bf16 else L.sgs_gemm_tn_mask_gather)(_ptr(bits), _ptr(dz), _ptr(w2), scale, _ptr(codes), N, _ptr(sd), n, H, H, _ptr(dW1), 2 * H, _ptr(db1), _ptr(db2),
-                                         _ptr(Traw), _ptr(craw), wsg.data_ptr(), wsg.numel(), _stream()), "sgs_gemm_tn_mask_gather")
-    dcodes, dU = torch.empty(N, H, **f32), torch.empty(N, H, **f32)
-    _lib.check(L.sgs_edge_score_bwd_reduce_fused(_ptr(G), _ptr(opart), _ptr(bits), _ptr(dz), _ptr(w2), p, N, H, graph.n_edges, _ptr(graph.in_ptr),
+    _call(L, "sgs_gemm_tn_mask_gather", plan.bf16, _ptr(bits), _ptr(dz), _ptr(s.w2), _dropout_scale(s.p), _ptr(s.codes), N, _ptr(sd), n, H, H, _ptr(dW1),
+          2 * H, _ptr(db1), _ptr(db2), _ptr(Traw), _ptr(craw), wsg.data_ptr(), wsg.numel(), _stream())
+    dcodes, dU = _empty_f32(N, H, device=dev), _empty_f32(N, H, device=dev)
+    _lib.check(L.sgs_edge_score_bwd_reduce_fused(_ptr(G), _ptr(opart), _ptr(bits), _ptr(dz), _ptr(s.w2), s.p, N, H, graph.n_edges, _ptr(graph.in_ptr),
                                                  _ptr(graph.in_eid), _ptr(graph.out_ptr), _ptr(dcodes), _ptr(dU), _ptr(Rraw), _stream()),
                "sgs_edge_score_bwd_reduce_fused")
-    dw2 = torch.empty(H, **f32)
-    _lib.check(L.sgs_edge_score_dw2_from_parts(_ptr(W1), _ptr(Traw), _ptr(U), _ptr(Rraw), _ptr(b1), _ptr(craw), N, H, p, _ptr(dw2), _stream()),
-               "sgs_edge_score_dw2_from_parts")
-    return _edge_score_backward_mask_tail(ctx, L, codes, W1, dcodes, dU, dW1, db1, dw2, db2)
+    return dcodes, dU, dW1, db1, _dw2_from_parts(L, s, Traw, craw, Rraw), db2
 
 
-def _edge_score_backward_mask_tail(ctx, L, codes, W1, dcodes, dU, dW1, db1, dw2, db2):
-    """The node-level half: U = codes W1b^T  ->  d codes += dU W1b,  d W1b = dU^T codes (right half of d fc1.weight, in place)."""
-    N, H = codes.shape
-    dcodes.addmm_(dU, W1[:, H:])
-    _leaf_dw(dU, codes, N, H, H, leaf=(ctx, 1), out=dW1, col0=H)
-    return dcodes, dW1, db1, dw2, db2, None, None, None, None, None, None, None, None
-
-
-_EdgeScore._backward_mask = staticmethod(_edge_score_backward_mask)
+_SCORE_BWD = {"dense": _score_bwd_dense, "recompute": _score_bwd_mask, "kept": _score_bwd_mask, "fused": _score_bwd_fused}
 
 
 def edge_score(codes, fc1_w, fc1_b, fc2_w, fc2_b, edge_index, active=None, p=0.0, seed=0, site=0, edge_id_offset=0, pairs="cached",
@@ -1206,28 +1246,14 @@ class _EdgeScoreEPD(torch.autograd.Function):
         N, H = A.shape
         E = edge_index.shape[1]
         dev = A.device
-        act = ctx.active
-        if act is not None and act.eid is not None:
-            eid, graph = act.eid, act.graph
-            n = eid.numel()
-            tok = _zero_token(dev)
-            if act.gq is not None and gp.numel() == E and gp.stride(0) == 0 and gp.data_ptr() == tok.data_ptr():
-                gp_act = act.gq
-            else:
-                gp_act = gp.index_select(0, eid)
-                if act.gq is not None:
-                    gp_act = gp_act + act.gq
-            act.gq = None
-        else:
-            eid, graph, n = None, get_graph(edge_index, N), E
-            gp_act = gp.contiguous()
+        eid, graph, n, gp_act = _active_rows(ctx.active, gp, edge_index, N)
         f32 = dict(dtype=torch.float32, device=dev)
         dv, feat2, dz = torch.empty(n, H, **f32), torch.empty(n, 2 * H, **f32), torch.empty(n, **f32)
         tile = L.sgs_edge_score_bwd_tile()
         hdz = torch.empty((n + tile - 1) // tile, H, **f32)
         dA = torch.zeros(N, H, **f32) if n == 0 else torch.empty(N, H, **f32)
         dW1 = torch.zeros_like(W1) if n == 0 else torch.empty_like(W1)
-        if n == 0:
+        if n == 0:          # (no active row: zeros, nothing launched -- _score_bwd_dense skips only its core; both on purpose)
             return dA, dW1, torch.zeros(H, **f32), torch.zeros(H, **f32), torch.zeros(1, **f32), *([None] * 11)
         ws = workspace(L.sgs_edge_score_epd_workspace_bytes(H), dev)
         _lib.check(L.sgs_edge_score_epd_bwd_core(_ptr(A), N, H, _ptr(edge_index), E, offset, _ptr(eid), n, _ptr(gp_act), _ptr(W1), _ptr(b1), _ptr(w2),

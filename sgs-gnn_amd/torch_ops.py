@@ -17,7 +17,6 @@ No CPU kernels are registered: a CPU tensor raises, as everywhere in this packag
 """
 from __future__ import annotations
 
-from types import SimpleNamespace
 from typing import Optional, Tuple
 
 import torch
@@ -63,11 +62,10 @@ def edge_score_backward(grad_p: Tensor, node_codes: Tensor, edge_index: Tensor, 
                         seed: int, offset: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     H = node_codes.shape[1]
     codes = node_codes.contiguous()
-    ctx = SimpleNamespace(saved_tensors=(codes, torch.mm(codes, W1[:, H:].t()), W1.contiguous(), b1.contiguous(), w2.reshape(-1).contiguous(),
-                                         b2.contiguous(), edge_index.contiguous()),
-                          active=None, p=float(p_drop), seed=int(seed), site=SITE_SCORE, offset=int(offset), needs_input_grad=(True,) * 12)
+    saved = ops._ScoreSaved(codes, torch.mm(codes, W1[:, H:].t()), W1.contiguous(), b1.contiguous(), w2.reshape(-1).contiguous(), b2.contiguous(),
+                            edge_index.contiguous(), kept=None, active=None, p=float(p_drop), seed=int(seed), site=SITE_SCORE, offset=int(offset))
     with torch.no_grad():
-        g = ops._EdgeScore.backward(ctx, grad_p.contiguous())
+        g = ops._edge_score_backward(saved, grad_p.contiguous())
     return g[0], g[1], g[2], g[3].reshape(w2.shape), g[4]
 
 

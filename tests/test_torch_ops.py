@@ -28,6 +28,41 @@ def test_operators_are_registered_with_fake_kernels():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("E,form", ((65535, "dense"), (65536, "recompute")))
+def test_edge_score_operator_on_both_sides_of_the_mask_form_threshold(E, form):
+    """The operator's backward builds the scorer's saved record without a kept mask: from ops._PRODUCTION_ROWS active rows on it runs the
+    mask form with the hidden layer recomputed, one row below the dense form.  ops.edge_score with _fwd_mask off calls the same entry
+    points with the same arguments in the same order, so values and all five gradients are equal bit for bit.  (While the operator
+    handed the backward a stand-in for the autograd context, the E = 65536 case raised AttributeError: the stand-in had no `bf16`.)"""
+    import sgs_gnn_amd as S
+    ops = S.ops
+    L = S._lib.lib()
+    N, H = 777, 128
+    assert L.sgs_gemm_tn_mask_supported(65536, H, H) == 1
+    assert ops._plan_backward(L, E, H, False, False, False, True, None).form == form
+    g = torch.Generator().manual_seed(1)
+    codes = torch.relu(torch.randn(N, H, generator=g)).to(DEV)
+    ei = torch.randint(0, N, (2, E), generator=g).to(DEV)
+    W1 = (torch.randn(H, 2 * H, generator=g) * 0.1).to(DEV)
+    b1, w2, b2 = (torch.randn(H, generator=g) * 0.1).to(DEV), (torch.randn(H, generator=g) * 0.3).to(DEV), torch.zeros(1, device=DEV)
+    gp = torch.randn(E, generator=g).to(DEV)
+    la = [t.clone().requires_grad_(True) for t in (codes, W1, b1, w2, b2)]
+    lb = [t.clone().requires_grad_(True) for t in (codes, W1, b1, w2, b2)]
+    pa = torch.ops.sgs.edge_score(la[0], ei, la[1], la[2], la[3], la[4], 0.3, 5, 0, True)
+    pa.backward(gp)
+    prev = ops._fwd_mask
+    try:
+        ops._fwd_mask = False
+        pb = ops.edge_score(lb[0], lb[1], lb[2], lb[3].reshape(1, -1), lb[4], ei, p=0.3, seed=5, site=2)
+        pb.backward(gp)
+    finally:
+        ops._fwd_mask = prev
+    assert torch.equal(pa, pb)
+    for name, a, b in zip(("codes", "W1", "b1", "w2", "b2"), la, lb):
+        assert a.grad is not None and torch.isfinite(a.grad).all() and torch.equal(a.grad, b.grad), name
+
+
+@pytest.mark.gpu
 def test_custom_ops_match_the_ops_layer_and_pass_opcheck():
     import sgs_gnn_amd as S
     ops = S.ops
