@@ -1251,6 +1251,48 @@ int sgs_ensemble_mean_correct(const float* logits, int64_t x_stride, int64_t Dc,
                               int64_t D_total, const int64_t* y, const uint8_t* mask0, const uint8_t* mask1, const uint8_t* mask2, int64_t* counts,
                               sgs_stream_t stream);
 
+/* ---------------------------------------------------------------- sparsifier export: consensus of D draws (sparsify.py)
+ * The fixed sparse graph a trained sparsifier is deployed with: every candidate edge is counted over D draws, and the q edges drawn
+ * most often -- ties broken by the score -- are kept.  All counting is integer and every result is independent of arrival order and of
+ * the launch geometry.  No call allocates, synchronises or reads back; zero fills are kernels.
+ *
+ * sgs_consensus_accum: count[e] = (first ? 0 : count[e]) + #{d < Dc : mask[d * mask_stride + e] != 0} for e < E.  `mask` is a pass's
+ *   [Dc, E] block of sgs_sample_topq_multi (any non-zero byte counts once; mask_stride >= E in bytes, any alignment).  A thread keeps 16
+ *   edges' counts as packed bytes and reads each row through the aligned 16-byte granules that hold its bytes; a granule that is not wholly
+ *   inside the block [mask, mask + (Dc - 1) mask_stride + E) is read byte by byte, so no byte outside the block is touched.  `hist` (may be
+ *   NULL): int64 [128], ACCUMULATED, never cleared: after this pass's addition hist[count[e]] += 1 for every e (privatised in LDS per
+ *   workgroup, non-zero bins flushed with 64-bit adds).  0 <= Dc <= 127 (a count stays below 128 as long as the caller folds at most 127
+ *   draws in total; a larger stored count breaks the contract and lands in bin 127).  E = 0: SGS_OK, nothing launched.  Dc = 0: SGS_OK; with
+ *   `first` the counts are still zeroed.  E < 2^32.
+ * sgs_consensus_select: key_e = (uint32(count_e) << 25) | (bits(p_e) >> 6), the low part 0 when p == NULL or when !(p_e >= 0) (negative,
+ *   -0, NaN); a count outside [0, 127] breaks the contract and is clamped, never used as an index.  The q largest keys are selected, ties to
+ *   the lowest edge id, by sgs_sample_topq's radix select, count and stable compaction (the fused small-E path up to 2 M edges, the large-E
+ *   path above; the key pass fuses the first digit's histogram) and emitted in ORIGINAL edge order: mask [E] u8, eid [q] ascending,
+ *   edge_index_out [2, q] (needs edge_index [2, E]), count_out [q] (the clamped counts), p_out [q] = p[eid] (1 when p == NULL), keys_out [E]
+ *   (tests).  Every output but mask may be NULL.  The key is a pure integer function of its inputs.  SCORES THAT DIFFER ONLY IN THEIR 6 LOWEST
+ *   MANTISSA BITS TIE (and go to the lower edge id): the price of a 32-bit key for the existing select.  q == 0 selects nothing, q == E
+ *   everything; q > E returns SGS_EINVAL.  E = 0: SGS_OK.  ws: sgs_consensus_select_workspace_bytes(E), 256-B aligned.  The call takes its
+ *   sizes as given (it ignores sgs_dyn_edges_set).
+ * sgs_edge_class_counts: pairs[y[src_e]][y[dst_e]] += 1 for every e < n with mask == NULL or mask[e] != 0.  pairs is int64 [C, C],
+ *   ACCUMULATED (the caller zeroes it); edge_index is [2, n] with row stride n.  An edge with an endpoint outside [0, N) or a label outside
+ *   [0, C) is skipped, never used as an index.  Two forms, chosen by capability alone: 2 = privatised (an int32 [C, C] table in LDS per
+ *   workgroup over a grid-stride loop, non-zero cells flushed at the end) when 4 C^2 <= 65536 bytes (C <= 128) and n < 2^31; 1 = direct
+ *   (one 64-bit global add per edge) otherwise.  With few classes nearly every edge of a homophilous graph hits one of C diagonal cells,
+ *   hence the privatised default.  n = 0: SGS_OK, nothing launched.
+ * sgs_edge_class_variant(n, C): the form a call launches now (pure host function): 2 or 1; 0 for n = 0; -1 when the call would return
+ *   SGS_EINVAL (n < 0, C < 1, or form 2 forced outside its range).
+ * sgs_edge_class_variant_set(code): 0 = automatic (default), 1 = direct, 2 = privatised; other codes SGS_EINVAL.  For tests and A/B timing. */
+int sgs_consensus_accum(const uint8_t* mask, int64_t mask_stride, int64_t Dc, int64_t E, int first, int32_t* count, int64_t* hist,
+                        sgs_stream_t stream);
+size_t sgs_consensus_select_workspace_bytes(int64_t E);
+int sgs_consensus_select(const int32_t* count, const float* p, int64_t E, int64_t q, const int64_t* edge_index, uint8_t* mask, int64_t* eid,
+                         int64_t* edge_index_out, int32_t* count_out, float* p_out, uint32_t* keys_out, void* ws, size_t ws_bytes,
+                         sgs_stream_t stream);
+int sgs_edge_class_counts(const int64_t* edge_index, int64_t n, const uint8_t* mask, const int64_t* y, int64_t N, int64_t C, int64_t* pairs,
+                          sgs_stream_t stream);
+int sgs_edge_class_variant(int64_t n, int64_t C);
+int sgs_edge_class_variant_set(int code);
+
 #ifdef __cplusplus
 }
 #endif

@@ -846,6 +846,49 @@ constexpr int64_t kConfAutoMaxC = 12;
 constexpr int64_t kConfAutoMinRows = 4096;
 std::atomic<int> g_conf_variant{0};
 
+// ---------------------------------------------------------------- class-pair edge counts (sparsify.py: the export's quality report)
+// pairs[y[src_e]][y[dst_e]] += 1 for every edge e with mask == nullptr or mask[e] != 0; pairs is int64 [C, C], accumulated.  Integer
+// atomics only.  An edge with an endpoint outside [0, N) or a label outside [0, C) is skipped, never used as an index.
+__device__ __forceinline__ int64_t edge_class_cell(const int64_t* __restrict__ edge_index, int64_t n, const uint8_t* __restrict__ mask,
+                                                   const int64_t* __restrict__ y, int64_t N, int64_t C, int64_t e) {      // -1: skipped
+    if (mask && mask[e] == 0) return -1;
+    const int64_t s = edge_index[e], d = edge_index[n + e];
+    if (s < 0 || s >= N || d < 0 || d >= N) return -1;
+    const int64_t a = y[s], b = y[d];
+    if (a < 0 || a >= C || b < 0 || b >= C) return -1;
+    return a * C + b;
+}
+// Direct form: one thread per edge, one non-returning 64-bit global add.
+__global__ void __launch_bounds__(kT) edge_class_direct(const int64_t* __restrict__ edge_index, int64_t n, const uint8_t* __restrict__ mask,
+                                                       const int64_t* __restrict__ y, int64_t N, int64_t C, unsigned long long* __restrict__ pairs) {
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+    if (e >= n) return;
+    const int64_t cell = edge_class_cell(edge_index, n, mask, y, N, C, e);
+    if (cell >= 0) atomicAdd(&pairs[cell], 1ull);
+}
+// Privatised form (4 C^2 <= 65536 bytes of LDS, n < 2^31): an int32 [C, C] table per workgroup over a grid-stride loop, the non-zero cells
+// added to pairs at the end.  With few classes nearly every edge of a homophilous graph hits one of the C diagonal cells: those take one
+// global add per workgroup instead of one per edge.
+__global__ void __launch_bounds__(kConfT) edge_class_private(const int64_t* __restrict__ edge_index, int64_t n, const uint8_t* __restrict__ mask,
+                                                            const int64_t* __restrict__ y, int64_t N, int64_t C,
+                                                            unsigned long long* __restrict__ pairs) {
+    extern __shared__ int hist[];
+    const int cells = static_cast<int>(C * C);
+    for (int k = threadIdx.x; k < cells; k += kConfT) hist[k] = 0;
+    __syncthreads();
+    for (int64_t e = static_cast<int64_t>(blockIdx.x) * kConfT + threadIdx.x; e < n; e += static_cast<int64_t>(gridDim.x) * kConfT) {
+        const int64_t cell = edge_class_cell(edge_index, n, mask, y, N, C, e);
+        if (cell >= 0) atomicAdd(&hist[static_cast<int>(cell)], 1);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < cells; k += kConfT) {
+        const int v = hist[k];
+        if (v) atomicAdd(&pairs[k], static_cast<unsigned long long>(v));
+    }
+}
+constexpr int64_t kPairPrivMaxC = 128;            // 4 * 128^2 = 65 536 bytes of LDS
+std::atomic<int> g_pair_variant{0};
+
 }  // namespace
 }  // namespace sgs
 
@@ -1187,6 +1230,49 @@ int sgs_confusion_counts(const float* logits, int64_t N, int64_t C, const int64_
         const int64_t grid = std::min<int64_t>(cdiv(N, kConfT / 64), cus);
         hipLaunchKernelGGL(confusion_private, dim3(static_cast<unsigned>(grid)), dim3(kConfT), static_cast<size_t>(12 * C * C), stream, logits, N, C, y,
                            m0, m1, m2, out);
+    }
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+int sgs_edge_class_variant_set(int code) {
+    SGS_REQUIRE(code >= 0 && code <= 2, SGS_EINVAL, "sgs_edge_class_variant_set: code %d, need 0 (automatic), 1 (direct) or 2 (privatised)", code);
+    g_pair_variant.store(code);
+    return SGS_OK;
+}
+
+int sgs_edge_class_variant(int64_t n, int64_t C) {
+    if (n < 0 || C < 1) return -1;
+    if (n == 0) return 0;
+    const bool priv_ok = C <= kPairPrivMaxC && n < (int64_t(1) << 31);
+    switch (g_pair_variant.load()) {
+        case 1: return 1;
+        case 2: return priv_ok ? 2 : -1;
+        default: return priv_ok ? 2 : 1;          // by capability alone
+    }
+}
+
+int sgs_edge_class_counts(const int64_t* edge_index, int64_t n, const uint8_t* mask, const int64_t* y, int64_t N, int64_t C, int64_t* pairs,
+                          sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(n >= 0 && N >= 0 && C >= 1 && C < (int64_t(1) << 24), SGS_EINVAL, "sgs_edge_class_counts: bad sizes (n=%lld N=%lld C=%lld)",
+                (long long)n, (long long)N, (long long)C);
+    const int var = sgs_edge_class_variant(n, C);
+    SGS_REQUIRE(var >= 0, SGS_EINVAL, "sgs_edge_class_counts: the privatised form (forced by sgs_edge_class_variant_set(2)) needs C <= 128 and n < 2^31");
+    if (n == 0) return SGS_OK;
+    SGS_REQUIRE(edge_index && pairs && (N == 0 || y), SGS_EINVAL, "sgs_edge_class_counts: null pointer");
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(pairs);
+    if (var == 1) {
+        hipLaunchKernelGGL(edge_class_direct, dim3(static_cast<unsigned>(cdiv(n, kT))), dim3(kT), 0, stream, edge_index, n, mask, y, N, C, out);
+    } else {
+        static const int cus = [] {
+            int dev = 0, k = 0;
+            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&k, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || k < 1) k = 256;
+            return k;
+        }();
+        const int64_t grid = std::min<int64_t>(cdiv(n, kConfT), cus);
+        hipLaunchKernelGGL(edge_class_private, dim3(static_cast<unsigned>(grid)), dim3(kConfT), static_cast<size_t>(4 * C * C), stream, edge_index, n,
+                           mask, y, N, C, out);
     }
     SGS_LAUNCH_OK();
     return SGS_OK;

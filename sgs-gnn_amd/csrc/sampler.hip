@@ -1295,6 +1295,154 @@ __global__ void __launch_bounds__(kThreads) multi_cover_finish(const uint32_t* _
     cover_finish_body(mcnt + d * ms, nb, q, stats ? stats + 4 * d : nullptr, cover_info ? cover_info + 2 * d : nullptr);
 }
 
+// ---------------------------------------------------------------- consensus of D draws (sgs_consensus_accum / sgs_consensus_select)
+// The fold: count[e] (+)= #{d < Dc : mask[d, e] != 0}.  A thread owns 16 consecutive edges and keeps their 16 counts as packed bytes in two
+// 64-bit words (Dc <= 127, so a byte never carries).  Row d's 16 bytes at mask + d * stride + e0 are rarely 16-byte aligned (the stride is E),
+// so the thread loads the one or two ALIGNED 16-byte granules that hold them and shifts the bytes into place; a granule that is not wholly
+// inside the mask block [mask, mask + (Dc - 1) * stride + E) -- the head of the first row, the tail of the last -- is read byte by byte, the
+// bytes outside as 0, so nothing outside the block is ever touched.  The count histogram is privatised in LDS.
+constexpr int kAccItems = 16;
+constexpr int kAccChunk = kThreads * kAccItems;       // 4096 edges per workgroup
+constexpr int kCountBins = 128;                       // counts 0..127
+constexpr int kCountMax = kCountBins - 1;
+
+__device__ __forceinline__ void load_granule(const uint8_t* g, const uint8_t* lo, const uint8_t* hi, uint64_t& a, uint64_t& b) {
+    if (g >= lo && g + 16 <= hi) {
+        const uint4 v = *reinterpret_cast<const uint4*>(g);
+        a = (static_cast<uint64_t>(v.y) << 32) | v.x;
+        b = (static_cast<uint64_t>(v.w) << 32) | v.z;
+    } else {
+        a = b = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (g + j >= lo && g + j < hi) a |= static_cast<uint64_t>(g[j]) << (8 * j);
+            if (g + 8 + j >= lo && g + 8 + j < hi) b |= static_cast<uint64_t>(g[8 + j]) << (8 * j);
+        }
+    }
+}
+// 0x01 in every byte of x that is not 0
+__device__ __forceinline__ uint64_t nonzero_bytes(uint64_t x) {
+    constexpr uint64_t k7f = 0x7F7F7F7F7F7F7F7FULL;
+    return ((((x & k7f) + k7f) | x) >> 7) & 0x0101010101010101ULL;
+}
+__device__ __forceinline__ int clamp_count(int c) { return c < 0 ? 0 : (c > kCountMax ? kCountMax : c); }
+
+__global__ void __launch_bounds__(kThreads) consensus_accum_kernel(const uint8_t* __restrict__ mask, int64_t stride, int Dc, int64_t E, int first,
+                                                                  int32_t* __restrict__ count, unsigned long long* __restrict__ hist) {
+    __shared__ uint32_t lh[kCountBins];
+    if (hist) {
+        if (threadIdx.x < kCountBins) lh[threadIdx.x] = 0;
+        __syncthreads();
+    }
+    const int64_t e0 = static_cast<int64_t>(blockIdx.x) * kAccChunk + static_cast<int64_t>(threadIdx.x) * kAccItems;
+    if (e0 < E) {
+        const uint8_t* lo = mask;
+        const uint8_t* hi = Dc > 0 ? mask + static_cast<int64_t>(Dc - 1) * stride + E : mask;
+        uint64_t acc0 = 0, acc1 = 0;
+        for (int d = 0; d < Dc; ++d) {
+            const uint8_t* a = mask + static_cast<int64_t>(d) * stride + e0;
+            const int sh = static_cast<int>(reinterpret_cast<uintptr_t>(a) & 15);
+            const uint8_t* g = a - sh;
+            uint64_t w0, w1, w2 = 0, w3 = 0;
+            load_granule(g, lo, hi, w0, w1);
+            if (sh) load_granule(g + 16, lo, hi, w2, w3);
+            if (sh >= 8) { w0 = w1; w1 = w2; w2 = w3; }
+            const int s = 8 * (sh & 7);
+            if (s) {
+                w0 = (w0 >> s) | (w1 << (64 - s));
+                w1 = (w1 >> s) | (w2 << (64 - s));
+            }
+            acc0 += nonzero_bytes(w0);
+            acc1 += nonzero_bytes(w1);
+        }
+        // (bytes past the row's end were counted from the next row or as 0: they are never stored)
+        const bool whole = e0 + kAccItems <= E && (reinterpret_cast<uintptr_t>(count + e0) & 15) == 0;
+        int c[kAccItems];
+        if (first) {
+#pragma unroll
+            for (int j = 0; j < kAccItems; ++j) c[j] = 0;
+        } else if (whole) {
+#pragma unroll
+            for (int j = 0; j < kAccItems; j += 4) {
+                const int4 v = *reinterpret_cast<const int4*>(count + e0 + j);
+                c[j] = v.x; c[j + 1] = v.y; c[j + 2] = v.z; c[j + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < kAccItems; ++j) c[j] = e0 + j < E ? count[e0 + j] : 0;
+        }
+#pragma unroll
+        for (int j = 0; j < kAccItems; ++j) c[j] += static_cast<int>(((j < 8 ? acc0 : acc1) >> (8 * (j & 7))) & 0xFF);
+        if (whole) {
+#pragma unroll
+            for (int j = 0; j < kAccItems; j += 4) *reinterpret_cast<int4*>(count + e0 + j) = make_int4(c[j], c[j + 1], c[j + 2], c[j + 3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < kAccItems; ++j)
+                if (e0 + j < E) count[e0 + j] = c[j];
+        }
+        if (hist) {
+#pragma unroll
+            for (int j = 0; j < kAccItems; ++j)
+                if (e0 + j < E) atomicAdd(&lh[clamp_count(c[j])], 1u);
+        }
+    }
+    if (hist) {
+        __syncthreads();
+        if (threadIdx.x < kCountBins) {
+            const uint32_t v = lh[threadIdx.x];
+            if (v) atomicAdd(&hist[threadIdx.x], static_cast<unsigned long long>(v));
+        }
+    }
+}
+
+// key_e = (count_e << 25) | (bits(p_e) >> 6): the count is the primary key, the score breaks ties among equal counts.  p == nullptr, or a
+// score that is not >= 0 (negative, -0, NaN): low part 0.  A non-negative float's bits are below 2^31, so the low part is below 2^25.
+__device__ __forceinline__ uint32_t consensus_key(int c, const float* __restrict__ p, int64_t e) {
+    uint32_t low = 0;
+    if (p) {
+        const float v = p[e];
+        const uint32_t b = __float_as_uint(v);
+        if (v >= 0.f && !(b >> 31)) low = b >> 6;
+    }
+    return (static_cast<uint32_t>(clamp_count(c)) << 25) | low;
+}
+// The key pass with the first digit's histogram fused in, as keys_hist0 (grid-stride over the 2048-edge chunks; hist0 zeroed by the caller).
+__global__ void __launch_bounds__(kThreads) consensus_keys_hist0(const int32_t* __restrict__ count, const float* __restrict__ p, int64_t E,
+                                                                uint32_t* __restrict__ keys, uint32_t* __restrict__ keys_out,
+                                                                uint32_t* __restrict__ hist0) {
+    __shared__ uint32_t lh[kBins];
+    for (int i = threadIdx.x; i < kBins; i += kThreads) lh[i] = 0;
+    __syncthreads();
+    const int64_t nchunk = (E + kChunk - 1) / kChunk;
+    for (int64_t chunk = blockIdx.x; chunk < nchunk; chunk += gridDim.x) {
+        const int64_t base = chunk * kChunk;
+#pragma unroll
+        for (int i = 0; i < kItems; ++i) {
+            const int64_t e = base + static_cast<int64_t>(i) * kThreads + threadIdx.x;
+            if (e < E) {
+                const uint32_t bits = consensus_key(count[e], p, e);
+                keys[e] = bits;
+                if (keys_out) keys_out[e] = bits;
+                atomicAdd(&lh[bits >> kShift0], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kBins; i += kThreads) {
+        const uint32_t v = lh[i];
+        if (v) atomicAdd(&hist0[i], v);
+    }
+}
+// count_out[i] = count[eid[i]] (clamped as the key clamps it) for the q selected edges
+__global__ void consensus_gather_count(const int32_t* __restrict__ count, const int64_t* __restrict__ eid, int64_t q, int64_t E,
+                                       int32_t* __restrict__ count_out) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= q) return;
+    const int64_t e = eid[i];
+    count_out[i] = (e >= 0 && e < E) ? clamp_count(count[e]) : 0;
+}
+
 }  // namespace
 }  // namespace sgs
 
@@ -1512,6 +1660,103 @@ int sgs_sample_topq_cover(int mode, const float* p, const float* prior, double d
     const CoverArgs c = cover_args(N, E, in_ptr, in_src, in_eid, cover_info);
     return sample_topq_impl("sgs_sample_topq_cover", &c, mode, p, prior, degree_bias_coef, noise, seed, stream_id, E, q, edge_index, mask,
                             sampled_eid, sampled_edge_index, sampled_p, stats, keys_out, ws, ws_bytes, stream_);
+}
+
+/* ---------------------------------------------------------------- consensus of D draws (the sparsifier export)
+ * sgs_consensus_accum folds a pass's masks into per-edge keep counts; sgs_consensus_select builds one uint32 key per edge from
+ * (count, score) and hands it to the sampler's own select / count / compact chain (small- and large-E path). */
+int sgs_consensus_accum(const uint8_t* mask, int64_t mask_stride, int64_t Dc, int64_t E, int first, int32_t* count, int64_t* hist,
+                        sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    SGS_REQUIRE(Dc >= 0 && E >= 0, SGS_EINVAL, "sgs_consensus_accum: negative size (Dc=%lld E=%lld)", (long long)Dc, (long long)E);
+    SGS_REQUIRE(Dc <= kCountMax, SGS_EINVAL, "sgs_consensus_accum: Dc=%lld draws in a pass, at most %d (a count is kept below %d)",
+                (long long)Dc, kCountMax, kCountBins);
+    SGS_REQUIRE(E < (int64_t(1) << 32), SGS_EINVAL, "sgs_consensus_accum: E=%lld exceeds 2^32-1", (long long)E);
+    SGS_REQUIRE(Dc <= 1 || mask_stride >= E, SGS_EINVAL, "sgs_consensus_accum: mask_stride=%lld below E=%lld", (long long)mask_stride, (long long)E);
+    if (E == 0) return SGS_OK;
+    SGS_REQUIRE(count && (Dc == 0 || mask), SGS_EINVAL, "sgs_consensus_accum: null pointer");
+    if (Dc == 0 && !first && !hist) return SGS_OK;
+    hipLaunchKernelGGL(consensus_accum_kernel, dim3(static_cast<unsigned>(cdiv(E, kAccChunk))), dim3(kThreads), 0, stream, mask, mask_stride,
+                       static_cast<int>(Dc), E, first, count, reinterpret_cast<unsigned long long*>(hist));
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+size_t sgs_consensus_select_workspace_bytes(int64_t E) {
+    if (E < 0) E = 0;
+    return sgs_sample_topq_workspace_bytes(E) + carve_bytes(E, 8);      // the sampler's carvings + edge ids for count_out when eid == NULL
+}
+
+int sgs_consensus_select(const int32_t* count, const float* p, int64_t E, int64_t q, const int64_t* edge_index, uint8_t* mask, int64_t* eid,
+                         int64_t* edge_index_out, int32_t* count_out, float* p_out, uint32_t* keys_out, void* ws, size_t ws_bytes,
+                         sgs_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const char* fn = "sgs_consensus_select";
+    SGS_REQUIRE(E >= 0 && q >= 0, SGS_EINVAL, "%s: negative size (E=%lld q=%lld)", fn, (long long)E, (long long)q);
+    SGS_REQUIRE(q <= E, SGS_EINVAL, "%s: cannot select q=%lld > E=%lld edges without replacement", fn, (long long)q, (long long)E);
+    SGS_REQUIRE(E < (int64_t(1) << 32), SGS_EINVAL, "%s: E=%lld exceeds 2^32-1", fn, (long long)E);
+    if (E == 0) return SGS_OK;
+    SGS_REQUIRE(count && mask, SGS_EINVAL, "%s: null count or mask", fn);
+    SGS_REQUIRE(!edge_index_out || edge_index, SGS_EINVAL, "%s: edge_index required for edge_index_out", fn);
+    const size_t ws_need = sgs_consensus_select_workspace_bytes(E);
+    SGS_REQUIRE(ws && ws_bytes >= ws_need, SGS_EWORKSPACE, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, ws_need);
+    SGS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, SGS_EINVAL, "%s: workspace must be 256-B aligned", fn);
+
+    // sample_topq_impl's carvings, in its order
+    const int64_t nblk = cdiv(E, kChunk);
+    Carver cv(ws);
+    uint32_t* keys = cv.take<uint32_t>(E);
+    cv.take<float>(nblk + 1);
+    float* scal = cv.take<float>(4);
+    uint32_t* hist = cv.take<uint32_t>(kBins);
+    SelectState* st = cv.take<SelectState>(1);
+    uint2* cnt = cv.take<uint2>(nblk + 1);
+    cv.take<float>(nblk + 1);
+    uint32_t* hist3 = cv.take<uint32_t>(3 * kBins);
+    SelPart* sel = cv.take<SelPart>(2);
+    int64_t* eid_ws = cv.take<int64_t>(E);
+    if (count_out && !eid) eid = eid_ws;
+    const dim3 grid(static_cast<unsigned>(nblk)), blk(kThreads);
+    const dim3 hgrid(static_cast<unsigned>(nblk < kHistGrid ? nblk : kHistGrid));
+    const int mask_aligned = (reinterpret_cast<uintptr_t>(mask) & 7) == 0;
+    const int64_t* no_dyn = nullptr;                 // the consensus is not a captured path: sizes are taken as given
+
+    if (q == 0 || q == E) {                          // nothing / everything: the keys only for keys_out
+        if (keys_out) {
+            if (int rc = zero_async(hist, kBins * sizeof(uint32_t), stream)) return rc;
+            hipLaunchKernelGGL(consensus_keys_hist0, hgrid, blk, 0, stream, count, p, E, keys, keys_out, hist);
+        }
+        hipLaunchKernelGGL(select_all, dim3(cdiv(E, 256)), dim3(256), 0, stream, E, p, edge_index, mask, eid, edge_index_out, p_out,
+                           static_cast<uint8_t>(q == E ? 1 : 0));
+    } else if (nblk <= kSmallBlocks) {
+        // fused small-E path: the digit selections and the block scan are recomputed by every workgroup of the next pass
+        const uint32_t q32 = static_cast<uint32_t>(q);
+        uint32_t *h0 = hist3, *h1 = hist3 + kBins, *h2 = hist3 + 2 * kBins;
+        if (int rc = zero_async(hist3, 3 * kBins * sizeof(uint32_t), stream)) return rc;
+        hipLaunchKernelGGL(consensus_keys_hist0, grid, blk, 0, stream, count, p, E, keys, keys_out, h0);
+        hipLaunchKernelGGL(small_hist_next, grid, blk, 0, stream, keys, E, kShift1, kMask1, kShift0, 1, q32, h0,
+                           static_cast<const SelPart*>(nullptr), sel, h1, no_dyn);
+        hipLaunchKernelGGL(small_hist_next, grid, blk, 0, stream, keys, E, kShift2, kMask2, kShift1, 0, q32, h1, sel, sel + 1, h2, no_dyn);
+        hipLaunchKernelGGL(small_count, grid, blk, 0, stream, keys, E, q32, h2, sel + 1, st, cnt, scal, static_cast<float*>(nullptr), no_dyn);
+        hipLaunchKernelGGL(small_compact, grid, blk, 0, stream, keys, E, q, st, cnt, p, edge_index, mask, mask_aligned, eid, edge_index_out,
+                           p_out, no_dyn);
+    } else {
+        if (int rc = zero_async(scal, static_cast<size_t>(reinterpret_cast<char*>(st + 1) - reinterpret_cast<char*>(scal)), stream)) return rc;
+        hipLaunchKernelGGL(consensus_keys_hist0, hgrid, blk, 0, stream, count, p, E, keys, keys_out, hist);
+        hipLaunchKernelGGL(select_digit, dim3(1), blk, 0, stream, hist, kShift0, 1, static_cast<uint32_t>(q), st);
+        hipLaunchKernelGGL(hist_next, hgrid, blk, 0, stream, keys, E, kShift1, kMask1, kShift0, st, hist);
+        hipLaunchKernelGGL(select_digit, dim3(1), blk, 0, stream, hist, kShift1, 0, static_cast<uint32_t>(q), st);
+        hipLaunchKernelGGL(hist_next, hgrid, blk, 0, stream, keys, E, kShift2, kMask2, kShift1, st, hist);
+        hipLaunchKernelGGL(select_digit, dim3(1), blk, 0, stream, hist, kShift2, 0, static_cast<uint32_t>(q), st);
+        hipLaunchKernelGGL(count_blocks, grid, blk, 0, stream, keys, E, st, cnt);
+        hipLaunchKernelGGL(scan_blocks, dim3(1), blk, 0, stream, cnt, nblk);
+        hipLaunchKernelGGL(compact, grid, blk, 0, stream, keys, E, q, int64_t(-1), int64_t(0), st, cnt, p, edge_index, mask, mask_aligned, eid,
+                           edge_index_out, p_out);
+    }
+    if (count_out && q > 0)
+        hipLaunchKernelGGL(consensus_gather_count, dim3(cdiv(q, 256)), dim3(256), 0, stream, count, eid, q, E, count_out);
+    SGS_LAUNCH_OK();
+    return SGS_OK;
 }
 
 

@@ -2544,6 +2544,120 @@ def sample_topq_multi(mode: int, p, prior, c: float, q: int, edge_index, D: int,
     return r
 
 
+# ------------------------------------------------------------------ consensus of D draws (the sparsifier export; composed in sparsify.py)
+CONSENSUS_MAX_DRAWS = 127          # a keep count fills 7 bits of the selection key (sgs_consensus_select)
+
+
+def consensus_accum(smp_or_mask, count=None, first: bool = True, hist=None) -> torch.Tensor:
+    """sgs_consensus_accum: count[e] = (0 if first else count[e]) + #{d : mask[d, e] != 0}, int32 [E] on the device.  `smp_or_mask`: a
+    MultiSampleResult (its D draws) or a bool / uint8 tensor [Dc, E] with unit column stride (rows may be strided and unaligned).  `count`
+    None (only with first=True): a new buffer.  `hist` (int64 [128] or None) is accumulated into, never cleared: hist[count[e]] += 1 for
+    every e after this pass.  At most 127 draws per call, and in total.  No host sync."""
+    L = _lib.lib()
+    if isinstance(smp_or_mask, MultiSampleResult):
+        mask, Dc = smp_or_mask.mask, int(smp_or_mask.D)
+    else:
+        mask = smp_or_mask
+        if not torch.is_tensor(mask) or mask.dim() != 2:
+            raise RuntimeError("consensus_accum: mask must be a MultiSampleResult or a [Dc, E] tensor")
+        Dc = mask.shape[0]
+    _need_gpu(mask, count, hist)
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError(f"consensus_accum: mask must be a bool or uint8 tensor, got {mask.dtype}")
+    E = mask.shape[1]
+    if E > 1 and mask.stride(1) != 1:
+        raise RuntimeError("consensus_accum: mask must have unit column stride")
+    stride = mask.stride(0) if mask.shape[0] > 1 else E
+    if Dc > 1 and stride < E:
+        raise RuntimeError("consensus_accum: mask rows overlap")
+    if count is None:
+        if not first:
+            raise RuntimeError("consensus_accum: count is required when first=False")
+        count = torch.empty(E, dtype=torch.int32, device=mask.device)
+    elif count.dtype != torch.int32 or count.dim() != 1 or count.numel() != E or not count.is_contiguous():
+        raise RuntimeError(f"consensus_accum: count must be a contiguous int32 [{E}] tensor")
+    if hist is not None and (hist.dtype != torch.int64 or hist.dim() != 1 or hist.numel() != 128 or not hist.is_contiguous()):
+        raise RuntimeError("consensus_accum: hist must be a contiguous int64 [128] tensor")
+    _lib.check(L.sgs_consensus_accum(mask.data_ptr() if Dc > 0 and E > 0 else None, stride, Dc, E, 1 if first else 0, _ptr(count),
+                                     _ptr(hist), _stream()), "sgs_consensus_accum")
+    return count
+
+
+class ConsensusResult:
+    """sgs_consensus_select's outputs: mask [E] bool, eid [q] (ascending), edge_index [2, q] or None, count [q] int32, p [q] float32
+    (ones when no scores were given), keys [E] (int64 holding the uint32 keys; only with want_keys), E, q."""
+    __slots__ = ("mask", "eid", "edge_index", "count", "p", "keys", "E", "q")
+
+
+def consensus_select(count, p, q: int, edge_index, want_keys: bool = False) -> ConsensusResult:
+    """The q edges with the largest (count, score) keys, ties to the lowest edge id, in original edge order (sgs_consensus_select).
+    count int32 [E] in [0, 127]; p float32 [E] or None (the count alone); edge_index int64 [2, E] or None.  Scores that differ only in
+    their 6 lowest mantissa bits tie.  q > E raises.  No host sync."""
+    L = _lib.lib()
+    _need_gpu(count, p, edge_index)
+    if count.dtype != torch.int32 or count.dim() != 1 or not count.is_contiguous():
+        raise RuntimeError("consensus_select: count must be a contiguous int32 [E] tensor")
+    E, q = count.numel(), int(q)
+    if p is not None and (p.dtype != torch.float32 or p.dim() != 1 or p.numel() != E or not p.is_contiguous()):
+        raise RuntimeError(f"consensus_select: p must be a contiguous float32 [{E}] tensor")
+    if edge_index is not None and (edge_index.dtype != torch.int64 or tuple(edge_index.shape) != (2, E) or not edge_index.is_contiguous()):
+        raise RuntimeError(f"consensus_select: edge_index must be a contiguous int64 [2, {E}] tensor")
+    if q < 0:
+        raise RuntimeError(f"consensus_select: q={q} is negative")
+    dev = count.device
+    r = ConsensusResult()
+    r.E, r.q = E, q
+    n = min(q, E)                                 # (q > E: the library refuses below; nothing of size q is allocated first)
+    r.mask = torch.empty(E, dtype=torch.bool, device=dev)
+    r.eid = torch.empty(n, dtype=torch.int64, device=dev)
+    r.edge_index = torch.empty(2, n, dtype=torch.int64, device=dev) if edge_index is not None else None
+    r.count = torch.empty(n, dtype=torch.int32, device=dev)
+    r.p = torch.empty(n, dtype=torch.float32, device=dev)
+    keys = torch.empty(E, dtype=torch.int32, device=dev) if want_keys else None
+    ws = workspace(L.sgs_consensus_select_workspace_bytes(E), dev)
+    _lib.check(L.sgs_consensus_select(_ptr(count), _ptr(p), E, q, _ptr(edge_index), _ptr(r.mask), _ptr(r.eid), _ptr(r.edge_index),
+                                      _ptr(r.count), _ptr(r.p), _ptr(keys), ws.data_ptr(), ws.numel(), _stream()), "sgs_consensus_select")
+    r.keys = (keys.to(torch.int64) & 0xFFFFFFFF) if want_keys else None
+    return r
+
+
+def edge_class_counts(edge_index, y, N: int, C: int, mask=None, out=None) -> torch.Tensor:
+    """int64 [C, C] on device: out[y[src_e]][y[dst_e]] += 1 for every edge e (with mask[e] set, when a mask is given)
+    (sgs_edge_class_counts).  `out` is accumulated into when given, else a zeroed buffer is made.  Edges with an endpoint outside [0, N) or
+    a label outside [0, C) are skipped.  No host sync."""
+    L = _lib.lib()
+    _need_gpu(edge_index, y, mask, out)
+    N, C = int(N), int(C)
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise RuntimeError("edge_class_counts: edge_index must be an int64 [2, n] tensor")
+    if y.dtype != torch.int64 or y.dim() != 1 or y.numel() != N:
+        raise RuntimeError(f"edge_class_counts: y must be an int64 [{N}] tensor")
+    if C < 1:
+        raise RuntimeError(f"edge_class_counts: C={C} classes")
+    n = edge_index.shape[1]
+    if mask is not None:
+        mask = _u8(mask)
+        if mask.numel() != n:
+            raise RuntimeError("edge_class_counts: mask needs one entry per edge")
+    if out is None:
+        out = torch.zeros(C, C, dtype=torch.int64, device=edge_index.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (C, C) or not out.is_contiguous():
+        raise RuntimeError(f"edge_class_counts: out must be a contiguous int64 [{C}, {C}] tensor")
+    _lib.check(L.sgs_edge_class_counts(_ptr(edge_index.contiguous()), n, _ptr(mask), _ptr(y.contiguous()), N, C, _ptr(out), _stream()),
+               "sgs_edge_class_counts")
+    return out
+
+
+def edge_class_variant(n: int, C: int) -> int:
+    """sgs_edge_class_variant: the form an edge_class_counts call launches now: 2 privatised, 1 direct, 0 nothing (n = 0), -1 refused.  Host-only."""
+    return int(_lib.lib().sgs_edge_class_variant(int(n), int(C)))
+
+
+def edge_class_variant_set(code: int) -> None:
+    """sgs_edge_class_variant_set: 0 = automatic (default), 1 = direct, 2 = privatised; any other code raises."""
+    _lib.check(_lib.lib().sgs_edge_class_variant_set(int(code)), "sgs_edge_class_variant_set")
+
+
 def graph_filter_multi(parent: Graph, smp: MultiSampleResult):
     """In-CSRs of the D drawn subgraphs of `parent` (sgs_graph_filter_multi): (in_ptr [D, N+1], in_src [D, q], in_eid [D, q],
     loop_eid [D, N]) int32; row d equals sgs_graph_filter's arrays for draw d."""

@@ -94,6 +94,32 @@ def classification_report(conf):
     return out if stacked else out[0]
 
 
+def different_label_stats(pairs, total_edges: int) -> dict:
+    """One graph's entry of count_edges_with_different_labels' dictionary from its class-pair table `pairs` (int [C, C], rows: the
+    source's class, columns: the destination's; ops.edge_class_counts) and its number of edges: the off-diagonal mass, the edge count and
+    their ratio in per cent (0 for a graph without edges)."""
+    M = pairs.tolist() if hasattr(pairs, "tolist") else pairs
+    diff = sum(int(v) for r, row in enumerate(M) for c, v in enumerate(row) if r != c)
+    total = int(total_edges)
+    return {"different_label_edges": diff, "total_edges": total, "percentage": (diff / total) * 100 if total > 0 else 0}
+
+
+def count_edges_with_different_labels(data, sampled_edge_index) -> dict:
+    """utils.py:291-343: how many edges join nodes of different labels, in `data.edge_index` ("original_graph") and in `sampled_edge_index`
+    ("sampled_graph"); each entry holds "different_label_edges", "total_edges" and "percentage".  Two ops.edge_class_counts launches over
+    the edge lists in place of the reference's Python loops over edges; the two [C, C] tables cross to the host in one copy.  The number of
+    classes is read from the labels (max + 1)."""
+    y = data.y.reshape(-1).to(torch.int64)
+    N = y.numel()
+    C = int(y.max()) + 1 if N else 1
+    both = torch.zeros(2, C, C, dtype=torch.int64, device=y.device)
+    ops.edge_class_counts(data.edge_index, y, N, C, out=both[0])
+    ops.edge_class_counts(sampled_edge_index, y, N, C, out=both[1])
+    M = both.cpu()
+    return {"original_graph": different_label_stats(M[0], data.edge_index.shape[1]),
+            "sampled_graph": different_label_stats(M[1], sampled_edge_index.shape[1])}
+
+
 def consistency_loss(edge_probs, edge_indices, node_embeddings):
     """utils.py:187-211: MSE(edge_probs, cos(emb[src], emb[dst]))."""
     N = node_embeddings.shape[0]
