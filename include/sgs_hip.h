@@ -107,6 +107,18 @@ int sgs_stage_segments(const int64_t* desc_host, int64_t n_segments, int64_t* di
  * p == NULL (mode LEARNED, prior == NULL): uniform weights, i.e. a uniformly random q-subset of the edges -- the selection
  * behind `random_edge_sampling` (sampling.py:159-163, torch.randperm(E)[:q]), emitted in original edge order.
  *
+ * Order of the keys: by the uint32 BIT PATTERN of the fp32 key, not by its float value.  Every key the sampler computes is >= +0 and
+ * finite, where the two orders agree.  For other bits (reachable through negative or NaN inputs) the bit order holds: a key with bit
+ * 31 set (-0 included) ranks above every positive key, a NaN ranks by its bits, -0 and +0 are different keys.
+ * Z and max are reduced in one fixed order (per 2048-edge chunk, then over the chunk partials): stats[0] and stats[1] are the same bits
+ * on the fused small-E path, the general path (E > 2 097 152, q == 0, q == E) and the phase API below, for any shard count.
+ * q == 0 / q == E: nothing / everything is selected without a race: no keys are computed (keys_out is left untouched), stats[2] =
+ * stats[3] = 0, and q == 0 leaves sampled_eid / sampled_edge_index / sampled_p untouched.
+ * Under sgs_dyn_edges_set (capacity = the E argument, live = the registered word; 0 < q < E <= 2 097 152 is required, else SGS_EINVAL):
+ * every output is what the plain call with E = live returns on the first `live` entries, edge_index keeping the capacity as its row
+ * stride; mask[live .. capacity) and keys_out[live .. capacity) are NOT written (the caller owns their contents).  q <= live is the
+ * caller's responsibility.  (tests/test_gpu_sampler_kernels.py pins all of this.)
+ *
  * sgs_gather_columns: out[:, j] = edge_index[:, idx[j]] (sampling.py:163 with an explicit index vector, e.g. the first q
  * entries of a given permutation); indices outside [0, E) give (-1, -1).
  * ---------------------------------------------------------------------------------- */
@@ -193,7 +205,8 @@ int sgs_sampler_shard_compact(const uint32_t* keys, int64_t E, const void* state
  *   w_j = clamp(p_e * ((1 - s_e) + s_e), 0, 1),  e = sampled_eid[j]   (forward value)
  * and its exact autograd backward wrt p (s depends on every p through sum(p)):
  *   dp_e += [e selected] g_e ((1 - s_e) + s_e) + ... (see DESIGN.md "straight-through").
- * Used by --pipeline straight_through and by evaluate.py.  prior == NULL <=> istest. */
+ * Used by --pipeline straight_through and by evaluate.py.  prior == NULL <=> istest.
+ * Under sgs_dyn_edges_set the backward writes exactly +0 to grad_p[live .. E); the selected ids must lie below the live count. */
 int sgs_st_weights_fwd(const float* p, const float* prior, double degree_bias_coef, const float* stats,
                        const int64_t* sampled_eid, int64_t E, int64_t q, float* w, sgs_stream_t stream);
 size_t sgs_st_weights_bwd_workspace_bytes(int64_t E, int64_t q);

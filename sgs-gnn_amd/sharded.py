@@ -96,6 +96,19 @@ def _no_cover(args, where):
         raise NotImplementedError(f"{where}: args.sgs_cover_nodes (node-covering draws) is not available for edge-sharded draws")
 
 
+def tie_quotas(k_rem: int, counts):
+    """How many of the keys EQUAL to the threshold each rank takes: the k_rem ties of the global draw go to the lowest global edge ids,
+    and the shards are contiguous in rank order, so the lowest ranks are served first, each taking min(what is left, its #equal).
+    counts: per rank (#greater, #equal), as sgs_sampler_shard_count reports them.  Pure host code."""
+    ties = []
+    left = int(k_rem)
+    for _, e_ in counts:
+        t_ = min(left, int(e_))
+        ties.append(t_)
+        left -= t_
+    return ties
+
+
 def dist_sample_topq(mode: int, p_local, prior_local, c: float, q: int, edge_index_local, edge_offset: int, bounds,
                      noise_local=None, seed: int = 0, stream_id: int = 0, want_keys: bool = False, *, cover=None) -> ops.SampleResult:
     """One exact global top-q draw over edge-sharded keys.  Returns this rank's part: mask over the local
@@ -154,12 +167,7 @@ def dist_sample_topq(mode: int, p_local, prior_local, c: float, q: int, edge_ind
     else:
         allc = [counts.tolist()]
     k_rem = int(state[1].item())                                       # ties to take globally, lowest ids first
-    ties = []
-    left = k_rem
-    for g_, e_ in allc:
-        t_ = min(left, e_)
-        ties.append(t_)
-        left -= t_
+    ties = tie_quotas(k_rem, allc)
     q_local = allc[rank][0] + ties[rank]
     r.mask = torch.empty(E, dtype=torch.bool, device=dev)
     r.eid = torch.empty(q_local, dtype=torch.int64, device=dev)

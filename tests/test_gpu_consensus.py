@@ -11,38 +11,15 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import consensus_ref as R  # noqa: E402
+from zoned import DEV, Zoned  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-ZONE = 64            # elements on either side of an output
 
 
 @pytest.fixture(scope="module")
 def lib():
     import sgs_gnn_amd as S
     return S._lib.lib(), S.ops._stream
-
-
-class Zoned:
-    """`n` elements of `dtype` on the device between two red zones; `shift` elements move the payload off its natural alignment."""
-
-    def __init__(self, n, dtype, fill, shift=0):
-        self.n, self.lo = n, ZONE + shift
-        self.fill = fill
-        self.buf = torch.full((n + 2 * ZONE + shift,), fill, dtype=dtype, device=DEV)
-        self.t = self.buf[self.lo:self.lo + n]
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.lo * self.buf.element_size()
-
-    def set(self, arr):
-        self.t.copy_(torch.from_numpy(np.ascontiguousarray(arr)).to(DEV).view(self.buf.dtype))
-
-    def get(self):
-        b = self.buf.cpu()
-        assert bool((b[:self.lo] == self.fill).all()) and bool((b[self.lo + self.n:] == self.fill).all()), "a red zone was written"
-        return b[self.lo:self.lo + self.n].numpy()
 
 
 def _dev_bytes(buf, shift):
