@@ -694,6 +694,41 @@ int sgs_confusion_counts(const float* logits, int64_t N, int64_t C, const int64_
 int sgs_confusion_variant(int64_t N, int64_t C);
 int sgs_confusion_variant_set(int code);
 
+/* Exact ROC-AUC counts of an evaluation (binary and one-vs-rest), threshold-free and pooled over a loader.
+ * Scores are fp32 [N, S], computed by the caller: C = 2 -> S = 1, score = logits[:, 1] - logits[:, 0], an item is positive iff y == 1;
+ * C > 2 -> S = C, score = log_softmax(logits, 1), an item of column c is positive iff y == c.  The items of (split s, column c) are the
+ * rows with m_s[i] != 0, a label in [0, C) and a non-NaN score.  Order is by float value: -0.0 == +0.0, -inf lowest, +inf highest.  With
+ * P, Nn the positive / negative items:  twoU = sum over positive i, negative j of (2 [x_j < x_i] + [x_j == x_i]),  AUC = twoU / (2 P Nn)
+ * (undefined when P Nn == 0): sklearn.metrics.roc_auc_score, ties count one half.  twoU is an integer, so every figure here is exact.
+ *
+ * sgs_auc_block_items(): host only; the number of sorted items one workgroup of the rank-sum kernel owns (tests place tie runs across it).
+ * sgs_auc_pack: writes N * S 64-bit keys, keys[i * S + c] =
+ *     bits 0-2  the three masks (!= 0 -> 1)          bit 3  positive (y_i == 1 for S = 1, y_i == c otherwise)
+ *     bits 4-35 the order-preserving image of the score: -0.0 becomes +0.0, then a negative value has all 32 bits flipped and a
+ *               non-negative one its sign bit             bits 36..  the column c
+ *   A NaN score clears that item's mask bits; a row whose label is outside [0, C) has the mask bits of all its S items cleared (the label
+ *   is compared, never used as an index), so rows outside every mask may hold any label.  Needs (C == 2 and S == 1) or (C > 2 and S == C),
+ *   S <= 65536 and N * S < 2^31.  One launch, no workspace, capturable.  N = 0: SGS_OK, nothing launched.
+ * sgs_auc_counts: `keys` is any concatenation of packed blocks in any order, n of them; out is int64 [3, S, 3] = {twoU, P, Nn} per
+ *   (split, column), WRITTEN (not accumulated).  The call sorts the keys on bits [4, 36 + ceil(log2 S)) into the workspace (the hipCUB
+ *   device radix sort: stable, the flag bits ride along; `keys` is not modified) and makes one streaming pass over the sorted keys in tiles of
+ *   sgs_auc_block_items(): per-tile negative counts per split, a scan over the tiles, then per tile the inclusive negative prefix, the
+ *   tie-run start b and end e of every positive item and its contribution Cn_s(e) + Cn_s(b - 1) (Cn_s: the split's negatives up to a
+ *   position, relative to the item's column start; column starts follow from the Nn totals).  A run that reaches a tile edge is closed by
+ *   one search in the sorted keys (a bisection done 256 probes at a time by the workgroup) plus one partial-tile count per tile edge,
+ *   whatever the run's length.  Integer arithmetic and
+ *   integer atomic adds only: the result does not depend on arrival order, and two identical calls give identical bits.  Contract:
+ *   every key's column is < S (a key that breaks it is never used as an index; the counts are then unspecified).  Requires n < 2^31 and
+ *   S <= 65536, else SGS_EINVAL; n = 0 gives zeros and SGS_OK.
+ *   ws: sgs_auc_counts_workspace_bytes(n, S) (host only, needs no GPU).  NOT capturable into a HIP graph: hipCUB clears its counters with
+ *   hipMemsetAsync, which must not become a graph node (the reason the sort-path sgs_graph_build is not capturable either); evaluation
+ *   is not a captured path. */
+int64_t sgs_auc_block_items(void);
+int sgs_auc_pack(const float* scores, int64_t N, int64_t S, int64_t C, const int64_t* y, const uint8_t* m0, const uint8_t* m1, const uint8_t* m2,
+                 uint64_t* keys, sgs_stream_t stream);
+size_t sgs_auc_counts_workspace_bytes(int64_t n, int64_t S);
+int sgs_auc_counts(const uint64_t* keys, int64_t n, int64_t S, int64_t* out, void* ws, size_t ws_bytes, sgs_stream_t stream);
+
 /* The gate of training_hybrid.py:95-103 in two launches, no zero fill, no atomics: out5[0..3] = (#correct_a, #train, #correct_b, #train)
  * (argmax of each logit matrix against y on the train rows; lowest index on ties), out5[4] = 0.  With dst_host_mapped (pinned,
  * device-mapped host int32[5]) the finishing launch also hands the four counts to the host as sgs_publish_to_host does (payload, then

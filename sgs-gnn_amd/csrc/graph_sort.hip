@@ -164,4 +164,21 @@ int graph_build_by_sort(const int64_t* ei, int64_t n, int64_t N, int32_t* in_ptr
     return SGS_OK;
 }
 
+// ---- the key sort of sgs_auc_counts (csrc/auc.hip): 64-bit keys ordered on bits [begin_bit, end_bit); the bits below ride along (a stable
+// LSD sort never looks at them).  It lives in this object because hipCUB clears its own counters with hipMemsetAsync, which only this
+// object may import (tests/test_abi.py); like the sort-path CSR build above it is therefore never captured into a graph.
+size_t auc_sort_temp_bytes(int64_t n, int begin_bit, int end_bit) {
+    size_t bytes = 0;
+    const uint64_t* kin = nullptr;
+    uint64_t* kout = nullptr;
+    (void)hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, kin, kout, static_cast<int>(n), begin_bit, end_bit, nullptr);
+    return bytes;
+}
+
+int auc_sort_keys(const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int begin_bit, int end_bit, void* temp, size_t temp_bytes,
+                  hipStream_t stream) {
+    SGS_HIP_OK(hipcub::DeviceRadixSort::SortKeys(temp, temp_bytes, keys_in, keys_out, static_cast<int>(n), begin_bit, end_bit, stream));
+    return SGS_OK;
+}
+
 }  // namespace sgs

@@ -20,6 +20,16 @@ new is launched or allocated, and with "micro" the triple always comes from the 
 they are taken from the confusion matrix of all masked nodes of all partitions.  (The reference, with its macro line switched on, would
 weight per-partition macro values by partition size; the two agree for micro and on a one-partition loader.  The pooled value does not
 depend on how the graph was partitioned and does not drop a class from the partitions where it happens to be absent.)
+
+ROC-AUC (both functions, the serial loop, the `full` / E <= q shortcut and every batched engine): `args.sgs_eval_auc` (absent / None / False
+= off; True = the returned triple is the AUC triple; together with a macro / weighted sgs_f1_average it raises: two claims on one triple) and
+`args.sgs_eval_auc_report` (None or a dict that receives "counts", an int64 CPU tensor [3, S, 3] = {twoU, P, Nn} per (split, column), "per_class",
+"auc", "kind" ("binary" for C = 2, "ovr_macro" otherwise) and "classes_defined"; all None for an empty loader).  The definition is
+include/sgs_hip.h's (sklearn.metrics.roc_auc_score: ties count one half; NaN scores and labels outside [0, C) drop the item).  When either is
+set, every partition runs the score ops (ops.auc_scores) and ONE sgs_auc_pack on its final mean logits into its own key tensor, and after
+the loader there is one concatenation, one sgs_auc_counts and one read-back; otherwise nothing new is launched or allocated.  Like the F1
+averages the figure is POOLED over the loader: the ranking is over all masked nodes of all partitions.  Neither clock moves.  Test hook:
+`args._sgs_trace_auc = {}` receives the pooled "scores" [M, S], "y" [M] and "masks" [3, M] in loader order.
 """
 from __future__ import annotations
 
@@ -29,7 +39,7 @@ from . import ops
 from .eval_batch import (EVAL_BATCH_BUDGET, HEADS, _head_dims, _head_of,  # noqa: F401  (these four: reached as evaluate.X by tests and tools)
                          _batched_ok, engine_of, plan_draws, run_partition, split_passes)
 from .model import _DropoutClock
-from .utils import F1_AVERAGES, classification_report, f1_from_confusion
+from .utils import F1_AVERAGES, auc_from_counts, classification_report, f1_from_confusion
 from .sampling import _NoiseClock, cover_graph, cover_nodes, draw_learned, draw_prior, random_edge_sampling
 
 PATH_COUNTS = {"serial": 0, "batched": 0}
@@ -80,8 +90,10 @@ def _add_confusion(conf, out, batch):
     return ops.confusion_counts(out, batch.y, (batch.train_mask, batch.val_mask, batch.test_mask), out=conf)
 
 
-def _finish(avg, rep, conf, micro):
-    """The triple to return: `micro` (from the six counters) unless another average was asked for; fills the report dict."""
+def _finish(avg, rep, conf, micro, auc=None):
+    """The triple to return: `micro` (from the six counters) unless another average or the AUC was asked for; fills the report dicts."""
+    if auc is not None:
+        micro = auc.finish(micro)
     if rep is not None:
         rep["confusion"] = rep["report"] = None
     if conf is None:
@@ -92,9 +104,67 @@ def _finish(avg, rep, conf, micro):
     return micro if avg == "micro" else f1_from_confusion(M, avg)
 
 
+AUC_REPORT_KEYS = ("counts", "per_class", "auc", "kind", "classes_defined")
+
+
+class _AucPool:
+    """The ROC-AUC side of one evaluation: per partition the score ops and ONE sgs_auc_pack into that partition's own key tensor; after the
+    loader one concatenation, one sgs_auc_counts and one read-back of the [3, S, 3] counts."""
+
+    def __init__(self, on, rep, trace):
+        self.on, self.rep, self.trace = on, rep, trace
+        self.keys, self.S, self.traced = [], None, []
+
+    def add(self, out, batch):
+        scores = ops.auc_scores(out)                                                 # [N, 1] (C = 2) or log_softmax [N, C]; C = 1: ValueError
+        masks = (batch.train_mask, batch.val_mask, batch.test_mask)
+        self.keys.append(ops.auc_pack(scores, batch.y, masks, out.shape[1]))
+        self.S = scores.shape[1]
+        if self.trace is not None:
+            self.traced.append((scores, batch.y, torch.stack(masks)))
+
+    def finish(self, triple):
+        """`triple` unless args.sgs_eval_auc asked for the AUC triple; fills the report dict (None everywhere for an empty loader)."""
+        if self.rep is not None:
+            self.rep.update(dict.fromkeys(AUC_REPORT_KEYS))
+        if not self.keys:
+            return (0, 0, 0) if self.on else triple
+        if self.trace is not None:
+            self.trace["scores"] = torch.cat([t[0] for t in self.traced])
+            self.trace["y"] = torch.cat([t[1] for t in self.traced])
+            self.trace["masks"] = torch.cat([t[2] for t in self.traced], dim=1)
+        keys = self.keys[0] if len(self.keys) == 1 else torch.cat(self.keys)
+        counts = ops.auc_counts(keys, self.S).cpu()
+        auc, per_class = auc_from_counts(counts)
+        if self.rep is not None:
+            self.rep.update(counts=counts, per_class=per_class, auc=auc, kind="binary" if self.S == 1 else "ovr_macro",
+                            classes_defined=[sum(1 for v in row if v == v) for row in per_class])
+        return auc if self.on else triple
+
+
+def _auc_opts(args, avg):
+    """The evaluation's _AucPool, or None when neither args.sgs_eval_auc nor args.sgs_eval_auc_report asks for one; a bad value, or
+    sgs_eval_auc together with a macro / weighted sgs_f1_average (two claims on the one returned triple), raises ValueError here, before
+    any partition is read."""
+    on = getattr(args, "sgs_eval_auc", None)
+    if on is None:
+        on = False
+    if not isinstance(on, bool):
+        raise ValueError(f"args.sgs_eval_auc={on!r}: need None, False or True")
+    rep = getattr(args, "sgs_eval_auc_report", None)
+    if rep is not None and not isinstance(rep, dict):
+        raise ValueError(f"args.sgs_eval_auc_report={rep!r}: need None or a dict (it receives {AUC_REPORT_KEYS})")
+    if on and avg != "micro":
+        raise ValueError(f"args.sgs_eval_auc=True together with args.sgs_f1_average={avg!r}: both claim the returned triple; set one of them")
+    if not on and rep is None:
+        return None
+    return _AucPool(on, rep, getattr(args, "_sgs_trace_auc", None))
+
+
 def _run(args, model, cluster_loader, device, q, mode, n_draws):
     cover_nodes(args)                       # args.sgs_cover_nodes: validated before any partition is read
     avg, rep, per_class = _f1_opts(args)
+    auc = _auc_opts(args, avg)
     model.eval()
     counts = conf = None
     noises = list(getattr(args, "_sgs_noise_eval", None) or [])
@@ -123,11 +193,13 @@ def _run(args, model, cluster_loader, device, q, mode, n_draws):
             counts = c.to(torch.int64) if counts is None else counts + c
             if per_class:
                 conf = _add_confusion(conf, out, batch)
+            if auc is not None:
+                auc.add(out, batch)
     if counts is None:
-        return _finish(avg, rep, None, (0, 0, 0))
+        return _finish(avg, rep, None, (0, 0, 0), auc)
     c = counts.tolist()
     # sum_b f1_b * n_b / sum_b n_b  ==  sum_b correct_b / sum_b n_b   (utils.calculate_f1 is accuracy)
-    return _finish(avg, rep, conf, tuple((c[s][0] / c[s][1]) if c[s][1] > 0 else 0 for s in range(3)))
+    return _finish(avg, rep, conf, tuple((c[s][0] / c[s][1]) if c[s][1] > 0 else 0 for s in range(3)), auc)
 
 
 def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
@@ -135,6 +207,7 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
     if mode not in ('learned', 'random', 'edge', 'full'):
         raise ValueError("Invalid mode. Choose 'learned', 'random', or 'full'.")
     avg, rep, per_class = _f1_opts(args)
+    auc = _auc_opts(args, avg)
     model.eval()
     counts = conf = None
     noises = list(getattr(args, "_sgs_noise_eval", None) or [])
@@ -162,6 +235,8 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
                     trace["edges"] = batch.edge_index.unsqueeze(0).expand(n_draws, *batch.edge_index.shape)
                 if per_class:
                     conf = _add_confusion(conf, acc, batch)
+                if auc is not None:
+                    auc.add(acc, batch)
                 continue
             if mode == 'learned':
                 ops.get_pairs(batch.edge_index, N, build=True)
@@ -178,14 +253,16 @@ def _run_batched(args, model, cluster_loader, device, q, mode, n_draws):
             acc = run_partition(batch, prepare, q, kind, p, passes, counts, trace, cover_graph(args, batch))
             if per_class:
                 conf = _add_confusion(conf, acc, batch)                              # the mean the last sgs_ensemble_mean_correct pass left
+            if auc is not None:
+                auc.add(acc, batch)
             # GNNModel.forward and GAT.forward take one dropout seed per call, in eval mode too (GIN and Cheb none): leave the dropout
             # clock where the serial loop's n_draws forwards leave it, so that training after an evaluation draws the same masks whichever
             # path evaluated
             _DropoutClock.tick += n_draws * engine.ticks
     if counts is None:
-        return _finish(avg, rep, None, (0, 0, 0))
+        return _finish(avg, rep, None, (0, 0, 0), auc)
     c = counts.tolist()
-    return _finish(avg, rep, conf, tuple((c[2 * s] / c[2 * s + 1]) if c[2 * s + 1] > 0 else 0 for s in range(3)))
+    return _finish(avg, rep, conf, tuple((c[2 * s] / c[2 * s + 1]) if c[2 * s + 1] > 0 else 0 for s in range(3)), auc)
 
 
 def evaluate(args, model, cluster_loader, device, q=500, mode=None, temperature=1.0):

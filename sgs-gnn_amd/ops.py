@@ -1332,6 +1332,60 @@ def confusion_variant_set(code: int) -> None:
     _lib.check(_lib.lib().sgs_confusion_variant_set(int(code)), "sgs_confusion_variant_set")
 
 
+def auc_scores(logits) -> torch.Tensor:
+    """The fp32 score matrix [N, S] whose ranking ROC-AUC is taken of (include/sgs_hip.h): C = 2 -> S = 1, logits[:, 1] - logits[:, 0];
+    C > 2 -> S = C, log_softmax over the classes (one-vs-rest).  Plain torch ops on the device, outside any kernel, so that the key bits
+    can be restated on the host from the same values.  C = 1 raises ValueError."""
+    _need_gpu(logits)
+    if logits.dim() != 2 or logits.shape[1] < 2:
+        raise ValueError(f"auc_scores: need [N, C] logits with C >= 2 (ROC-AUC of one class is undefined), got {tuple(logits.shape)}")
+    lg = logits.float()
+    if lg.shape[1] == 2:
+        return (lg[:, 1] - lg[:, 0]).unsqueeze(1).contiguous()
+    return torch.log_softmax(lg, 1).contiguous()
+
+
+def auc_block_items() -> int:
+    """sgs_auc_block_items: the sorted items one workgroup of auc_counts' rank-sum pass owns.  Host-only."""
+    return int(_lib.lib().sgs_auc_block_items())
+
+
+def auc_pack(scores, y, masks, C: int, out=None) -> torch.Tensor:
+    """int64 [N * S] on device: one sort key per (row, column) item of `scores` [N, S] (sgs_auc_pack: masks in bits 0-2, positive in bit 3,
+    the order-preserving image of the score in bits 4-35, the column above).  C = 2 needs S = 1, C > 2 needs S = C.  One launch, no host
+    sync."""
+    L = _lib.lib()
+    _need_gpu(scores, y, *masks)
+    if len(masks) != 3:
+        raise RuntimeError("auc_pack: need three masks (train, val, test)")
+    if scores.dim() != 2:
+        raise RuntimeError("auc_pack: scores must be [N, S]")
+    N, S = scores.shape
+    sc, m = scores.contiguous(), [_u8(x) for x in masks]
+    if any(x.numel() != N for x in m) or y.numel() != N:
+        raise RuntimeError("auc_pack: y and the masks need one entry per row of scores")
+    if out is None:
+        out = torch.empty(N * S, dtype=torch.int64, device=scores.device)
+    elif out.numel() != N * S:
+        raise RuntimeError(f"auc_pack: out must hold {N * S} int64 keys")
+    _lib.check(L.sgs_auc_pack(_ptr(sc, torch.float32), N, S, int(C), _ptr(y, torch.int64), _ptr(m[0]), _ptr(m[1]), _ptr(m[2]),
+                              _ptr(out, torch.int64), _stream()), "sgs_auc_pack")
+    return out
+
+
+def auc_counts(keys, S: int) -> torch.Tensor:
+    """int64 [3, S, 3] on device: {twoU, P, Nn} per (split, column) of any concatenation of auc_pack blocks (sgs_auc_counts: one device
+    radix sort, then the tie-aware rank-sum pass; exact integers, the same bits on every call).  No host sync; not capturable."""
+    L = _lib.lib()
+    _need_gpu(keys)
+    n, S = keys.numel(), int(S)
+    out = torch.empty(3, S, 3, dtype=torch.int64, device=keys.device)
+    nbytes = int(L.sgs_auc_counts_workspace_bytes(n, S))
+    ws = workspace(nbytes, keys.device)
+    _lib.check(L.sgs_auc_counts(_ptr(keys, torch.int64), n, S, _ptr(out), _ptr(ws), nbytes, _stream()), "sgs_auc_counts")
+    return out
+
+
 def masked_correct_pair(logits_a, logits_b, y, train_mask, out) -> torch.Tensor:
     """The gate's two counts in one launch: out[0:4] = (#correct_a, #train, #correct_b, #train); `out` (int32, >= 4 entries)
     must be zero on entry."""

@@ -94,6 +94,33 @@ def classification_report(conf):
     return out if stacked else out[0]
 
 
+def auc_from_counts(counts):
+    """ROC-AUC from the integer counts of ops.auc_counts: `counts` is [3, S, 3] = {twoU, P, Nn} per (split, column) (an integer tensor, array
+    or nested list).  -> (triple, per_class): per_class[s][c] = twoU / (2 P Nn) in float64 from exact Python integers, NaN where P Nn == 0
+    (a column without a positive or without a negative item has no ROC curve); triple[s] = the unweighted mean over the split's defined
+    columns (the binary figure for S = 1, one-vs-rest macro otherwise), 0.0 for a split with no defined column."""
+    M = counts.tolist() if hasattr(counts, "tolist") else counts
+    if len(M) != 3 or any(len(cell) != 3 for row in M for cell in row):
+        raise ValueError("auc_from_counts: need [3, S, 3] integers {twoU, P, Nn}")
+    per_class = [[int(u) / (2 * int(p) * int(n)) if int(p) * int(n) > 0 else float("nan") for u, p, n in row] for row in M]
+    triple = []
+    for row in per_class:
+        have = [v for v in row if v == v]
+        triple.append(sum(have) / len(have) if have else 0.0)
+    return tuple(triple), per_class
+
+
+def calculate_auc(logits, labels, mask) -> float:
+    """ROC-AUC of `logits` [N, C] on the masked rows, as sklearn.metrics.roc_auc_score gives it (ties count one half): binary for C = 2 (the
+    score is logits[:, 1] - logits[:, 0]), the unweighted one-vs-rest mean over the classes that have both kinds of rows for C > 2 (scores:
+    log_softmax).  Sorted and counted on the device (ops.auc_pack, ops.auc_counts); 9 S integers cross to the host.  0.0 when no class is
+    defined; C = 1 raises ValueError."""
+    scores = ops.auc_scores(logits)
+    none = torch.zeros_like(mask)
+    keys = ops.auc_pack(scores, labels, (mask, none, none), logits.shape[1])
+    return auc_from_counts(ops.auc_counts(keys, scores.shape[1]).cpu())[0][0]
+
+
 def different_label_stats(pairs, total_edges: int) -> dict:
     """One graph's entry of count_edges_with_different_labels' dictionary from its class-pair table `pairs` (int [C, C], rows: the
     source's class, columns: the destination's; ops.edge_class_counts) and its number of edges: the off-diagonal mass, the edge count and
