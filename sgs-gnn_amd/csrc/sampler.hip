@@ -28,6 +28,31 @@ struct SelectState {
     uint32_t n_gt;     // (final) number of keys strictly greater than the threshold
     uint32_t pad;
 };
+struct SelPart { uint32_t prefix, k_rem; };   // fused small-E path: the state after digit 0 and after digit 1
+
+// D draws over one candidate set, by value to every kernel of the selection chain; a kernel's draw is d = blockIdx.y.  A single
+// draw is D == 1 on a one-row grid: d == 0, so every stride multiplies by zero.
+struct DrawSet {
+    uint32_t* keys; int64_t ks;     // key row of draw d at keys + d * ks
+    uint32_t* hist; int64_t hs;     // digit histograms of draw d at hist + d * hs (3 * kBins on the small path, kBins on the large)
+    SelectState* st;                // st[d]
+    SelPart* sel;                   // sel[2 d], sel[2 d + 1]
+    uint2* cnt; int64_t cs;         // per-chunk (gt, eq) counts of draw d at cnt + d * cs
+    int D;
+};
+// the output rows of draw d: mask + d * E, eid / p + d * q, sei + d * 2 q, stats + 4 d (any but the mask may be null)
+struct DrawOut {
+    uint8_t* mask;
+    int64_t *eid, *sei;
+    float *p, *stats;
+};
+// row `off` of an optional output: null stays null.  The OFFSET is selected, not the pointer: straight-line scalar code, so a kernel's
+// argument loads stay in one batch ahead of its first wait (a branch here split them into two dependent round trips).
+template <typename T>
+__device__ __forceinline__ T* opt_row(T* p, int64_t off) { return p + (p ? off : int64_t(0)); }
+__device__ __forceinline__ DrawOut out_row(const DrawOut& o, int64_t d, int64_t E, int64_t q) {
+    return DrawOut{o.mask + d * E, opt_row(o.eid, d * q), opt_row(o.sei, d * 2 * q), opt_row(o.p, d * q), opt_row(o.stats, 4 * d)};
+}
 
 // ---------------------------------------------------------------- reductions (deterministic tree)
 // MODE 0: sum(p)   MODE 1: max(p)   MODE 2: sum(exp(p - max))
@@ -133,13 +158,15 @@ __device__ __forceinline__ void keys_hist0_body(const float* __restrict__ p, con
         if (v) atomicAdd(&hist[i], v);
     }
 }
+// large-E path and phase API: draw d reads noise row d (or stream stream_id0 + d)
 template <int MODE>
 __global__ void __launch_bounds__(kThreads) keys_hist0(const float* __restrict__ p, const float* __restrict__ prior,
-                                                      const float* __restrict__ noise, uint64_t seed,
-                                                      uint64_t stream_id, const uint64_t* __restrict__ epoch, int64_t edge_offset, int64_t E, float one_minus_c, float c,
-                                                      const float* __restrict__ scal, uint32_t* __restrict__ keys,
-                                                      float* __restrict__ keys_out, uint32_t* __restrict__ hist) {
-    keys_hist0_body<MODE>(p, prior, noise, seed, stream_id, epoch, edge_offset, E, one_minus_c, c, scal, keys, keys_out, hist);
+                                                      const float* __restrict__ noise, uint64_t seed, uint64_t stream_id0,
+                                                      const uint64_t* __restrict__ epoch, int64_t edge_offset, int64_t E, float one_minus_c,
+                                                      float c, const float* __restrict__ scal, DrawSet ds, float* __restrict__ keys_out) {
+    const int64_t d = blockIdx.y;
+    keys_hist0_body<MODE>(p, prior, noise ? noise + d * E : nullptr, seed, stream_id0 + d, epoch, edge_offset, E, one_minus_c, c, scal,
+                          ds.keys + d * ds.ks, opt_row(keys_out, d * E), ds.hist + d * ds.hs);
 }
 
 // Histogram of the next digit among keys whose higher digits equal state->prefix.
@@ -168,10 +195,9 @@ __device__ __forceinline__ void hist_next_body(const uint32_t* __restrict__ keys
         if (v) atomicAdd(&hist[i], v);
     }
 }
-__global__ void __launch_bounds__(kThreads) hist_next(const uint32_t* __restrict__ keys, int64_t E, int shift,
-                                                     uint32_t digit_mask, int prev_shift,
-                                                     const SelectState* __restrict__ st, uint32_t* __restrict__ hist) {
-    hist_next_body(keys, E, shift, digit_mask, prev_shift, st, hist);
+__global__ void __launch_bounds__(kThreads) hist_next(DrawSet ds, int64_t E, int shift, uint32_t digit_mask, int prev_shift) {
+    const int64_t d = blockIdx.y;
+    hist_next_body(ds.keys + d * ds.ks, E, shift, digit_mask, prev_shift, ds.st + d, ds.hist + d * ds.hs);
 }
 
 // One block: locate the digit bin holding the k_rem-th largest key of the current prefix.
@@ -223,9 +249,8 @@ __device__ void select_digit_body(uint32_t* __restrict__ hist, int shift, int fi
     for (int i = threadIdx.x; i < kBins; i += kThreads) hist[i] = 0;
     __syncthreads();
 }
-__global__ void __launch_bounds__(kThreads) select_digit(uint32_t* __restrict__ hist, int shift, int first,
-                                                        uint32_t q, SelectState* __restrict__ st) {
-    select_digit_body(hist, shift, first, q, st);
+__global__ void __launch_bounds__(kThreads) select_digit(DrawSet ds, int shift, int first, uint32_t q) {
+    select_digit_body(ds.hist + static_cast<int64_t>(blockIdx.y) * ds.hs, shift, first, q, ds.st + blockIdx.y);
 }
 
 // ---------------------------------------------------------------- counting + scan + compaction
@@ -266,9 +291,9 @@ __device__ __forceinline__ void count_blocks_body(const uint32_t* __restrict__ k
         cnt[blockIdx.x] = make_uint2(static_cast<uint32_t>(g), static_cast<uint32_t>(q_));
     }
 }
-__global__ void __launch_bounds__(kThreads) count_blocks(const uint32_t* __restrict__ keys, int64_t E,
-                                                        const SelectState* __restrict__ st, uint2* __restrict__ cnt) {
-    count_blocks_body(keys, E, st, cnt);
+__global__ void __launch_bounds__(kThreads) count_blocks(DrawSet ds, int64_t E) {
+    const int64_t d = blockIdx.y;
+    count_blocks_body(ds.keys + d * ds.ks, E, ds.st + d, ds.cnt + d * ds.cs);
 }
 
 // One block: exclusive scan of the per-block (gt, eq) counts, in place.
@@ -295,7 +320,9 @@ __device__ void scan_blocks_body(uint2* __restrict__ cnt, int64_t nblk) {
         rg += c.x; re += c.y;
     }
 }
-__global__ void __launch_bounds__(kThreads) scan_blocks(uint2* __restrict__ cnt, int64_t nblk) { scan_blocks_body(cnt, nblk); }
+__global__ void __launch_bounds__(kThreads) scan_blocks(DrawSet ds, int64_t nblk) {
+    scan_blocks_body(ds.cnt + static_cast<int64_t>(blockIdx.y) * ds.cs, nblk);
+}
 
 // blk_gt / blk_eq: number of keys > T / == T in all chunks before this workgroup's
 __device__ __forceinline__ void compact_body(uint32_t blk_gt, uint32_t blk_eq, const uint32_t* __restrict__ keys, int64_t E, int64_t Ecap, int64_t q,
@@ -372,14 +399,14 @@ __device__ __forceinline__ void compact_body(uint32_t blk_gt, uint32_t blk_eq, c
             if (e0 + j < E) mask[e0 + j] = static_cast<uint8_t>((mbits >> (8 * j)) & 1u);
     }
 }
-__global__ void __launch_bounds__(kThreads) compact(const uint32_t* __restrict__ keys, int64_t E, int64_t q, int64_t ties_override,
-                                                   int64_t eid_offset, const SelectState* __restrict__ st, const uint2* __restrict__ cnt,
-                                                   const float* __restrict__ p, const int64_t* __restrict__ edge_index,
-                                                   uint8_t* __restrict__ mask, int mask_aligned,
-                                                   int64_t* __restrict__ sampled_eid, int64_t* __restrict__ sei,
-                                                   float* __restrict__ sampled_p) {
-    compact_body(cnt[blockIdx.x].x, cnt[blockIdx.x].y, keys, E, E, q, ties_override, eid_offset, st, p, edge_index, mask, mask_aligned,
-                 sampled_eid, sei, sampled_p);
+// ties_override / eid_offset: the phase API's share of the ties and its shard's first global edge id (-1 / 0 otherwise)
+__global__ void __launch_bounds__(kThreads) compact(DrawSet ds, int64_t E, int64_t q, int64_t ties_override, int64_t eid_offset,
+                                                   const float* __restrict__ p, const int64_t* __restrict__ edge_index, DrawOut out) {
+    const int64_t d = blockIdx.y;
+    const DrawOut o = out_row(out, d, E, q);
+    const uint2 c = ds.cnt[d * ds.cs + blockIdx.x];
+    compact_body(c.x, c.y, ds.keys + d * ds.ks, E, E, q, ties_override, eid_offset, ds.st + d, p, edge_index, o.mask,
+                 (reinterpret_cast<uintptr_t>(o.mask) & 7) == 0, o.eid, o.sei, o.p);
 }
 
 // ---------------------------------------------------------------- fused small-E path (partition scale)
@@ -391,8 +418,6 @@ __global__ void __launch_bounds__(kThreads) compact(const uint32_t* __restrict__
 // variant with tickets was measured slower on MI355X: the device-scope fences write back / invalidate the per-XCD L2s.)
 constexpr int kSmallBlocks = 1024;
 constexpr int kHistGrid = 2048;        // workgroups of the histogram passes on the large-E path (grid-stride over chunks)     // small path when E <= 1024 chunks (2 M candidate edges)
-
-struct SelPart { uint32_t prefix, k_rem; };
 
 // sgs_dyn_edges_set: the live candidate count comes from a device word; the launch was sized for the capacity.  Returns false
 // for a workgroup that has no chunk of the live range (it leaves at once: it has no part in the recomputed reductions either).
@@ -623,11 +648,14 @@ __device__ __forceinline__ void small_hist_next_body(const uint32_t* __restrict_
         if (v) atomicAdd(&hist[i], v);
     }
 }
-__global__ void __launch_bounds__(kThreads) small_hist_next(const uint32_t* __restrict__ keys, int64_t E, int shift, uint32_t digit_mask,
-                                                           int prev_shift, int first, uint32_t q, const uint32_t* __restrict__ hist_prev,
-                                                           const SelPart* __restrict__ sel_in, SelPart* __restrict__ sel_out,
-                                                           uint32_t* __restrict__ hist, const int64_t* __restrict__ dynE) {
-    small_hist_next_body(keys, E, shift, digit_mask, prev_shift, first, q, hist_prev, sel_in, sel_out, hist, dynE);
+// pass 1 (first = 1) or 2: the draw's three digit histograms are consecutive at ds.hist + d * ds.hs
+__global__ void __launch_bounds__(kThreads) small_hist_next(DrawSet ds, int64_t E, int shift, uint32_t digit_mask, int prev_shift, int first,
+                                                           uint32_t q, const int64_t* __restrict__ dynE) {
+    const int64_t d = blockIdx.y;
+    uint32_t* h = ds.hist + d * ds.hs;
+    const int pass = first ? 1 : 2;
+    small_hist_next_body(ds.keys + d * ds.ks, E, shift, digit_mask, prev_shift, first, q, h + (pass - 1) * kBins,
+                         first ? nullptr : ds.sel + 2 * d, ds.sel + 2 * d + (first ? 0 : 1), h + pass * kBins, dynE);
 }
 
 // every workgroup finishes the last digit (threshold T, ties to take), counts its chunk; workgroup 0 publishes the final
@@ -675,11 +703,11 @@ __device__ __forceinline__ void small_count_body(const uint32_t* __restrict__ ke
         cnt[blockIdx.x] = make_uint2(static_cast<uint32_t>(g), static_cast<uint32_t>(q_));
     }
 }
-__global__ void __launch_bounds__(kThreads) small_count(const uint32_t* __restrict__ keys, int64_t E, uint32_t q,
-                                                       const uint32_t* __restrict__ hist2, const SelPart* __restrict__ sel_in,
-                                                       SelectState* __restrict__ st, uint2* __restrict__ cnt, const float* __restrict__ scal,
+__global__ void __launch_bounds__(kThreads) small_count(DrawSet ds, int64_t E, uint32_t q, const float* __restrict__ scal,
                                                        float* __restrict__ stats, const int64_t* __restrict__ dynE) {
-    small_count_body(keys, E, q, hist2, sel_in, st, cnt, scal, stats, dynE);
+    const int64_t d = blockIdx.y;
+    small_count_body(ds.keys + d * ds.ks, E, q, ds.hist + d * ds.hs + 2 * kBins, ds.sel + 2 * d + 1, ds.st + d, ds.cnt + d * ds.cs, scal,
+                     opt_row(stats, 4 * d), dynE);
 }
 
 // compaction with the exclusive prefix over the preceding chunks' (gt, eq) counts recomputed by each workgroup
@@ -708,12 +736,13 @@ __device__ __forceinline__ void small_compact_body(const uint32_t* __restrict__ 
     __syncthreads();
     compact_body(pre[0], pre[1], keys, E, Ecap, q, int64_t(-1), int64_t(0), st, p, edge_index, mask, mask_aligned, sampled_eid, sei, sampled_p);
 }
-__global__ void __launch_bounds__(kThreads) small_compact(const uint32_t* __restrict__ keys, int64_t E, int64_t q, const SelectState* __restrict__ st,
-                                                         const uint2* __restrict__ cnt, const float* __restrict__ p,
-                                                         const int64_t* __restrict__ edge_index, uint8_t* __restrict__ mask, int mask_aligned,
-                                                         int64_t* __restrict__ sampled_eid, int64_t* __restrict__ sei,
-                                                         float* __restrict__ sampled_p, const int64_t* __restrict__ dynE) {
-    small_compact_body(keys, E, q, st, cnt, p, edge_index, mask, mask_aligned, sampled_eid, sei, sampled_p, dynE);
+__global__ void __launch_bounds__(kThreads) small_compact(DrawSet ds, int64_t E, int64_t q, const float* __restrict__ p,
+                                                         const int64_t* __restrict__ edge_index, DrawOut out,
+                                                         const int64_t* __restrict__ dynE) {
+    const int64_t d = blockIdx.y;
+    const DrawOut o = out_row(out, d, E, q);
+    small_compact_body(ds.keys + d * ds.ks, E, q, ds.st + d, ds.cnt + d * ds.cs, p, edge_index, o.mask,
+                       (reinterpret_cast<uintptr_t>(o.mask) & 7) == 0, o.eid, o.sei, o.p, dynE);
 }
 
 // ---------------------------------------------------------------- node-covering draws (sgs_sample_topq_cover)
@@ -843,9 +872,11 @@ __device__ __forceinline__ void cover_finish_body(const uint32_t* __restrict__ m
         if (stats) stats[2] = __uint_as_float(__float_as_uint(stats[2]) & 0x7FFFFFFFu);
     }
 }
-__global__ void __launch_bounds__(kThreads) cover_finish(const uint32_t* __restrict__ mcnt, int nb, int64_t q, float* __restrict__ stats,
-                                                        int32_t* __restrict__ cover_info) {
-    cover_finish_body(mcnt, nb, q, stats, cover_info);
+// ms = kCoverGrid, or 0 when one key-less cover_rows counted M for all draws (degenerate q)
+__global__ void __launch_bounds__(kThreads) cover_finish(const uint32_t* __restrict__ mcnt, int64_t ms, int nb, int64_t q,
+                                                        float* __restrict__ stats, int32_t* __restrict__ cover_info) {
+    const int64_t d = blockIdx.y;
+    cover_finish_body(mcnt + d * ms, nb, q, opt_row(stats, 4 * d), opt_row(cover_info, 2 * d));
 }
 
 // counts[0] = #keys > threshold, counts[1] = #keys == threshold in this shard (before the scan).
@@ -866,22 +897,23 @@ __global__ void __launch_bounds__(kThreads) total_counts(const uint2* __restrict
 }
 
 __global__ void write_stats(const float* __restrict__ scal, const SelectState* __restrict__ st, float* __restrict__ stats) {
-    stats[0] = scal[0];
-    stats[1] = scal[1];
-    stats[2] = __uint_as_float(st->prefix);
-    stats[3] = static_cast<float>(st->k_rem);
+    const int d = blockIdx.y;
+    stats[4 * d + 0] = scal[0];
+    stats[4 * d + 1] = scal[1];
+    stats[4 * d + 2] = __uint_as_float(st[d].prefix);
+    stats[4 * d + 3] = static_cast<float>(st[d].k_rem);
 }
 
-__global__ void select_all(int64_t E, const float* __restrict__ p, const int64_t* __restrict__ edge_index,
-                           uint8_t* __restrict__ mask, int64_t* __restrict__ sampled_eid, int64_t* __restrict__ sei,
-                           float* __restrict__ sampled_p, uint8_t value) {
+// degenerate draws: nothing (value 0) or everything (value 1, q == E)
+__global__ void select_all(int64_t E, const float* __restrict__ p, const int64_t* __restrict__ edge_index, DrawOut out, uint8_t value) {
     const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (e >= E) return;
-    mask[e] = value;
+    const DrawOut o = out_row(out, blockIdx.y, E, E);
+    o.mask[e] = value;
     if (value) {
-        if (sampled_eid) sampled_eid[e] = e;
-        if (sei) { sei[e] = edge_index[e]; sei[E + e] = edge_index[E + e]; }
-        if (sampled_p) sampled_p[e] = p ? p[e] : 1.f;
+        if (o.eid) o.eid[e] = e;
+        if (o.sei) { o.sei[e] = edge_index[e]; o.sei[E + e] = edge_index[E + e]; }
+        if (o.p) o.p[e] = p ? p[e] : 1.f;
     }
 }
 
@@ -931,10 +963,10 @@ __device__ __forceinline__ void st_fwd_body(const float* __restrict__ p, const f
     w[j] = fminf(fmaxf(v, 0.f), 1.f);
 }
 template <bool HAS_PRIOR>
-__global__ void st_fwd_kernel(const float* __restrict__ p, const float* __restrict__ prior, float one_minus_c, float c,
-                              const float* __restrict__ stats, const int64_t* __restrict__ eid, int64_t q,
-                              float* __restrict__ w) {
-    st_fwd_body<HAS_PRIOR>(p, prior, one_minus_c, c, stats, eid, q, w);
+__global__ void st_fwd(const float* __restrict__ p, const float* __restrict__ prior, float one_minus_c, float c,
+                       const float* __restrict__ stats, const int64_t* __restrict__ eid, int64_t q, float* __restrict__ w) {
+    const int64_t d = blockIdx.y;
+    st_fwd_body<HAS_PRIOR>(p, prior, one_minus_c, c, stats + 4 * d, eid + d * q, q, w + d * q);
 }
 
 // backward: h_e = g_e [0 <= p_e st_e <= 1];  S = sum_sel h_e p_e^2
@@ -1009,7 +1041,7 @@ __global__ void st_bwd_sparse(const float* __restrict__ p, const float* __restri
 // aligned) rather than recomputing them from the hash in the three later passes: at partition scale the D x 4E bytes stay in the
 // Infinity Cache, and a recompute would put three more Philox evaluations per key and draw on passes that are otherwise pure loads.
 constexpr int kMultiG = 4;                   // draws per key-pass workgroup: 4 x 8 KiB of LDS histograms beside 16 waves
-constexpr int kMultiCoverG = 2;              // draws per workgroup of multi_cover_rows (1, 2 or 4; measured: DESIGN.md section 5)
+constexpr int kMultiCoverG = 2;              // draws per workgroup of a batched pass's cover_rows (1, 2 or 4; measured: DESIGN.md section 5)
 
 __host__ __device__ inline int64_t multi_key_stride(int64_t E) { return (E + 63) & ~int64_t(63); }
 
@@ -1073,113 +1105,17 @@ __global__ void __launch_bounds__(kKeyThreads) multi_keys_hist0(const float* __r
         }
 }
 
-// pass 1 (first = 1) or 2 of the fused small-E path for draw blockIdx.y
-__global__ void __launch_bounds__(kThreads) multi_small_hist_next(const uint32_t* __restrict__ keys, int64_t ks, int64_t E, int shift,
-                                                                 uint32_t digit_mask, int prev_shift, int first, uint32_t q,
-                                                                 uint32_t* __restrict__ hist3, SelPart* __restrict__ sel) {
-    const int64_t d = blockIdx.y;
-    uint32_t* h = hist3 + d * 3 * kBins;
-    const int pass = first ? 1 : 2;
-    small_hist_next_body(keys + d * ks, E, shift, digit_mask, prev_shift, first, q, h + (pass - 1) * kBins,
-                         first ? nullptr : sel + 2 * d, sel + 2 * d + (first ? 0 : 1), h + pass * kBins, nullptr);
-}
-
-__global__ void __launch_bounds__(kThreads) multi_small_count(const uint32_t* __restrict__ keys, int64_t ks, int64_t E, uint32_t q,
-                                                             const uint32_t* __restrict__ hist3, const SelPart* __restrict__ sel,
-                                                             SelectState* __restrict__ st, uint2* __restrict__ cnt, int64_t cs,
-                                                             const float* __restrict__ scal, float* __restrict__ stats) {
-    const int64_t d = blockIdx.y;
-    small_count_body(keys + d * ks, E, q, hist3 + d * 3 * kBins + 2 * kBins, sel + 2 * d + 1, st + d, cnt + d * cs, scal,
-                     stats ? stats + 4 * d : nullptr, nullptr);
-}
-
-__global__ void __launch_bounds__(kThreads) multi_small_compact(const uint32_t* __restrict__ keys, int64_t ks, int64_t E, int64_t q,
-                                                               const SelectState* __restrict__ st, const uint2* __restrict__ cnt, int64_t cs,
-                                                               const float* __restrict__ p, const int64_t* __restrict__ edge_index,
-                                                               uint8_t* __restrict__ mask, int64_t* __restrict__ sampled_eid,
-                                                               int64_t* __restrict__ sei, float* __restrict__ sampled_p) {
-    const int64_t d = blockIdx.y;
-    uint8_t* m = mask + d * E;
-    small_compact_body(keys + d * ks, E, q, st + d, cnt + d * cs, p, edge_index, m, (reinterpret_cast<uintptr_t>(m) & 7) == 0,
-                       sampled_eid ? sampled_eid + d * q : nullptr, sei ? sei + d * 2 * q : nullptr, sampled_p ? sampled_p + d * q : nullptr,
-                       nullptr);
-}
-
-// large-E path, draw blockIdx.y
-template <int MODE>
-__global__ void __launch_bounds__(kThreads) multi_keys_hist0_large(const float* __restrict__ p, const float* __restrict__ prior,
-                                                                  const float* __restrict__ noise, uint64_t seed, uint64_t stream_id0,
-                                                                  const uint64_t* __restrict__ epoch, int64_t E, float one_minus_c, float c,
-                                                                  const float* __restrict__ scal, uint32_t* __restrict__ keys, int64_t ks,
-                                                                  uint32_t* __restrict__ hist) {
-    const int64_t d = blockIdx.y;
-    keys_hist0_body<MODE>(p, prior, noise ? noise + d * E : nullptr, seed, stream_id0 + d, epoch, int64_t(0), E, one_minus_c, c, scal,
-                          keys + d * ks, nullptr, hist + d * kBins);
-}
-__global__ void __launch_bounds__(kThreads) multi_select_digit(uint32_t* __restrict__ hist, int shift, int first, uint32_t q,
-                                                              SelectState* __restrict__ st) {
-    select_digit_body(hist + static_cast<int64_t>(blockIdx.y) * kBins, shift, first, q, st + blockIdx.y);
-}
-__global__ void __launch_bounds__(kThreads) multi_hist_next(const uint32_t* __restrict__ keys, int64_t ks, int64_t E, int shift,
-                                                           uint32_t digit_mask, int prev_shift, const SelectState* __restrict__ st,
-                                                           uint32_t* __restrict__ hist) {
-    const int64_t d = blockIdx.y;
-    hist_next_body(keys + d * ks, E, shift, digit_mask, prev_shift, st + d, hist + d * kBins);
-}
-__global__ void __launch_bounds__(kThreads) multi_count_blocks(const uint32_t* __restrict__ keys, int64_t ks, int64_t E,
-                                                              const SelectState* __restrict__ st, uint2* __restrict__ cnt, int64_t cs) {
-    const int64_t d = blockIdx.y;
-    count_blocks_body(keys + d * ks, E, st + d, cnt + d * cs);
-}
-__global__ void __launch_bounds__(kThreads) multi_scan_blocks(uint2* __restrict__ cnt, int64_t cs, int64_t nblk) {
-    scan_blocks_body(cnt + static_cast<int64_t>(blockIdx.y) * cs, nblk);
-}
-__global__ void __launch_bounds__(kThreads) multi_compact(const uint32_t* __restrict__ keys, int64_t ks, int64_t E, int64_t q,
-                                                         const SelectState* __restrict__ st, const uint2* __restrict__ cnt, int64_t cs,
-                                                         const float* __restrict__ p, const int64_t* __restrict__ edge_index,
-                                                         uint8_t* __restrict__ mask, int64_t* __restrict__ sampled_eid, int64_t* __restrict__ sei,
-                                                         float* __restrict__ sampled_p) {
-    const int64_t d = blockIdx.y;
-    uint8_t* m = mask + d * E;
-    const uint2 c = cnt[d * cs + blockIdx.x];
-    compact_body(c.x, c.y, keys + d * ks, E, E, q, int64_t(-1), int64_t(0), st + d, p, edge_index, m, (reinterpret_cast<uintptr_t>(m) & 7) == 0,
-                 sampled_eid ? sampled_eid + d * q : nullptr, sei ? sei + d * 2 * q : nullptr, sampled_p ? sampled_p + d * q : nullptr);
-}
-__global__ void multi_write_stats(const float* __restrict__ scal, const SelectState* __restrict__ st, float* __restrict__ stats) {
-    const int d = blockIdx.y;
-    stats[4 * d + 0] = scal[0];
-    stats[4 * d + 1] = scal[1];
-    stats[4 * d + 2] = __uint_as_float(st[d].prefix);
-    stats[4 * d + 3] = static_cast<float>(st[d].k_rem);
-}
-__global__ void multi_select_all(int64_t E, const float* __restrict__ p, const int64_t* __restrict__ edge_index, uint8_t* __restrict__ mask,
-                                 int64_t* __restrict__ sampled_eid, int64_t* __restrict__ sei, float* __restrict__ sampled_p, uint8_t value) {
-    const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const int64_t d = blockIdx.y;
-    if (e >= E) return;
-    mask[d * E + e] = value;
-    if (value) {
-        if (sampled_eid) sampled_eid[d * E + e] = e;
-        if (sei) { sei[d * 2 * E + e] = edge_index[e]; sei[d * 2 * E + E + e] = edge_index[E + e]; }
-        if (sampled_p) sampled_p[d * E + e] = p ? p[e] : 1.f;
-    }
-}
-template <bool HAS_PRIOR>
-__global__ void multi_st_fwd(const float* __restrict__ p, const float* __restrict__ prior, float one_minus_c, float c,
-                             const float* __restrict__ stats, const int64_t* __restrict__ eid, int64_t q, float* __restrict__ w) {
-    const int64_t d = blockIdx.y;
-    st_fwd_body<HAS_PRIOR>(p, prior, one_minus_c, c, stats + 4 * d, eid + d * q, q, w + d * q);
-}
-
 // ---------------------------------------------------------------- node-covering draws of the batched pass (sgs_sample_topq_multi_cover)
-// cover_rows for a GROUP of G draws (blockIdx.y): the stored key rows keys + d * ks share one candidate graph, so a lane reads a CSR
-// entry (in_src[j], in_eid[j]) once and gathers that edge's key from each of the group's rows -- G independent gathers in flight per
-// entry where the single-draw kernel has one -- with one 64-bit (bits << 32 | ~eid) running maximum per draw in registers.  The winner of
+// cover_rows for a GROUP of G draws (blockIdx.y): the key rows keys + d * ks share one candidate graph, so a lane reads a CSR entry
+// (in_src[j], in_eid[j]) once and gathers that edge's key from each of the group's rows -- G independent gathers in flight per entry
+// where the single-draw kernel has one -- with one 64-bit (bits << 32 | ~eid) running maximum per draw in registers.  The winner of
 // draw d gets bit 31 in d's own key row and moves one count of d's digit-0 histogram (hist + d * hs) from bin b to bin b + 1024, first
 // aggregated per (workgroup, draw) in LDS (4 KiB per draw of the group), flushed as integer atomicSub / atomicAdd pairs.  Rows, lanes
 // per row, the hand-over of long rows to the whole workgroup, the bounds checks and the grid-stride are cover_rows'; per draw the
 // comparisons are the same integers, so row d of the keys and histograms is bitwise what cover_rows leaves for that draw, whatever G.
 // The last group is partial: its spare slots re-read the group's last row (no branch around the gathers) and force nothing.
+// (A single covering draw does NOT run this kernel with G = 1: measured on an MI355X that form takes 0.4 to 0.7 us longer than
+// cover_rows<LPR> at a partition's size -- 10.3 to 10.6 against 9.9 us -- for a reason that was not found; DESIGN.md.)
 template <int G>
 __device__ __forceinline__ void cover_cand_group(uint32_t* const (&krow)[G], uint32_t E, const int32_t* __restrict__ in_src,
                                                  const int32_t* __restrict__ in_eid, int64_t j, int64_t row, unsigned long long (&best)[G]) {
@@ -1195,9 +1131,8 @@ __device__ __forceinline__ void cover_cand_group(uint32_t* const (&krow)[G], uin
     }
 }
 template <int LPR, int G>
-__global__ void __launch_bounds__(kCoverThreads) multi_cover_rows(uint32_t* keys, int64_t ks, int64_t E, int D, int64_t N,
-                                                                 const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src,
-                                                                 const int32_t* __restrict__ in_eid, uint32_t* __restrict__ hist, int64_t hs,
+__global__ void __launch_bounds__(kCoverThreads) cover_rows_group(DrawSet ds, int64_t E, int64_t N, const int32_t* __restrict__ in_ptr,
+                                                                 const int32_t* __restrict__ in_src, const int32_t* __restrict__ in_eid,
                                                                  uint32_t* __restrict__ mcnt) {
     constexpr int RPB = kCoverThreads / LPR;
     constexpr int kLong = kCoverLongPerLane * LPR;
@@ -1206,10 +1141,10 @@ __global__ void __launch_bounds__(kCoverThreads) multi_cover_rows(uint32_t* keys
     __shared__ uint32_t nlong, nforced[G];
     __shared__ unsigned long long wbest[G][kCoverThreads / 64];
     const int d0 = blockIdx.y * G;
-    const int gn = (D - d0) < G ? (D - d0) : G;           // draws of this group (>= 1: the grid has ceil(D / G) groups)
+    const int gn = (ds.D - d0) < G ? (ds.D - d0) : G;     // draws of this group (>= 1: the grid has ceil(D / G) groups)
     uint32_t* krow[G];
 #pragma unroll
-    for (int g = 0; g < G; ++g) krow[g] = keys + static_cast<int64_t>(d0 + (g < gn ? g : gn - 1)) * ks;
+    for (int g = 0; g < G; ++g) krow[g] = ds.keys + static_cast<int64_t>(d0 + (g < gn ? g : gn - 1)) * ds.ks;
     for (int i = threadIdx.x; i < G * (kBins / 2); i += kCoverThreads) (&moved[0][0])[i] = 0;
     if (threadIdx.x < G) nforced[threadIdx.x] = 0;
     if (threadIdx.x == 0) nlong = 0;
@@ -1279,20 +1214,13 @@ __global__ void __launch_bounds__(kCoverThreads) multi_cover_rows(uint32_t* keys
         __syncthreads();
     }
     for (int g = 0; g < gn; ++g) {
-        uint32_t* h = hist + static_cast<int64_t>(d0 + g) * hs;
+        uint32_t* h = ds.hist + static_cast<int64_t>(d0 + g) * ds.hs;
         for (int i = threadIdx.x; i < kBins / 2; i += kCoverThreads) {
             const uint32_t v = moved[g][i];
             if (v) { atomicSub(&h[i], v); atomicAdd(&h[i + kBins / 2], v); }
         }
     }
     if (static_cast<int>(threadIdx.x) < gn) mcnt[static_cast<int64_t>(d0 + threadIdx.x) * kCoverGrid + blockIdx.x] = nforced[threadIdx.x];
-}
-
-// cover_finish for draw blockIdx.y; ms = kCoverGrid, or 0 when one key-less cover_rows counted M for all draws (degenerate q)
-__global__ void __launch_bounds__(kThreads) multi_cover_finish(const uint32_t* __restrict__ mcnt, int64_t ms, int nb, int64_t q,
-                                                              float* __restrict__ stats, int32_t* __restrict__ cover_info) {
-    const int64_t d = blockIdx.y;
-    cover_finish_body(mcnt + d * ms, nb, q, stats ? stats + 4 * d : nullptr, cover_info ? cover_info + 2 * d : nullptr);
 }
 
 // ---------------------------------------------------------------- consensus of D draws (sgs_consensus_accum / sgs_consensus_select)
@@ -1471,45 +1399,70 @@ int sgs_dropout_keep(uint64_t seed, uint32_t site, int64_t rows, int64_t cols, f
     return SGS_OK;
 }
 
-size_t sgs_sample_topq_workspace_bytes(int64_t E) {
+}  // extern "C"
+
+// ---------------------------------------------------------------- one workspace layout
+// Every carving of a draw's workspace for (E, D, covering?, consensus?); on a null base only `bytes`, the size, means anything.  scal, st
+// and hist are adjacent, in that order: the large path clears them, through the one histogram per draw it uses, in one zero_async.  The
+// key rows are padded to 64 keys (multi_key_stride) for load_keys8's 16-byte loads.
+struct SamplerWs {
+    uint32_t* keys; int64_t ks;
+    float *part, *part2, *scal;     // per-chunk partials (sum or max; sum of exp); the scalars Z and max
+    SelectState* st;
+    uint32_t* hist;                 // 3 * kBins per draw: a draw's three digits on the small path; the first kBins * D as one row per draw on the large
+    uint2* cnt; int64_t cs;
+    SelPart* sel;
+    uint32_t* mcnt;                 // covering draws: forced edges per (draw, workgroup of cover_rows)
+    int64_t* eid;                   // consensus: edge ids for count_out when the caller asks for none
+    size_t bytes;
+};
+static SamplerWs sampler_ws(void* base, int64_t E, int64_t D, bool cover, bool consensus) {
     if (E < 0) E = 0;
-    const int64_t nblk = cdiv(E, kChunk) + 1;
-    return carve_bytes(E, 4)            // keys
-           + carve_bytes(nblk, 4)       // partial sums
-           + carve_bytes(4, 4)          // scalars Z, max
-           + carve_bytes(kBins, 4)      // histogram
-           + carve_bytes(1, sizeof(SelectState)) + carve_bytes(nblk, sizeof(uint2))
-           + carve_bytes(nblk, 4) + carve_bytes(3 * kBins, 4) + 256 + 256;   // fused small-E path: second partials, per-digit histograms
+    if (D < 1) D = 1;
+    SamplerWs w{};
+    w.ks = multi_key_stride(E);
+    w.cs = cdiv(E, kChunk) + 1;
+    Carver cv(base);
+    w.keys = cv.take<uint32_t>(w.ks * D);
+    w.part = cv.take<float>(w.cs);
+    w.part2 = cv.take<float>(w.cs);
+    w.scal = cv.take<float>(4);
+    w.st = cv.take<SelectState>(D);
+    w.hist = cv.take<uint32_t>(3 * kBins * D);
+    w.cnt = cv.take<uint2>(w.cs * D);
+    w.sel = cv.take<SelPart>(2 * D);
+    if (cover) w.mcnt = cv.take<uint32_t>(kCoverGrid * D);
+    if (consensus) w.eid = cv.take<int64_t>(E);
+    w.bytes = cv.off;
+    return w;
+}
+static int check_ws(const char* fn, const void* ws, size_t ws_bytes, size_t ws_need) {
+    SGS_REQUIRE(ws && ws_bytes >= ws_need, SGS_EWORKSPACE, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, ws_need);
+    SGS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, SGS_EINVAL, "%s: workspace must be 256-B aligned", fn);
+    return SGS_OK;
 }
 
-size_t sgs_sample_topq_cover_workspace_bytes(int64_t E, int64_t N) {
-    (void)N;       // the forced-edge kernel's per-workgroup counts have a fixed length (its grid is capped at kCoverGrid)
-    return sgs_sample_topq_workspace_bytes(E) + carve_bytes(kCoverGrid, 4);
-}
-
-int sgs_sample_topq_cover_variant(int64_t N, int64_t E) {
-    if (N <= 0 || E < 8 * N) return 4;
-    return E < 64 * N ? 16 : 64;
-}
-
-// what a covering draw adds to the plain one (sgs_sample_topq_cover); nullptr = the plain draw
+// ---------------------------------------------------------------- one selection chain
+// what a covering draw adds to the plain one (sgs_sample_topq[_multi]_cover); nullptr = the plain draw
 struct CoverArgs {
     int64_t N;
     const int32_t *in_ptr, *in_src, *in_eid;
     int32_t* info;
-    int lanes, grid;      // sgs_sample_topq_cover_variant of the shape; workgroups of cover_rows
+    int lanes, grid, group;      // sgs_sample_topq_cover_variant of the shape; workgroups of cover_rows; draws per workgroup of it
+    bool batched;                // sgs_sample_topq_multi_cover: a degenerate pass counts M before it writes the stats, a single draw after
 };
-// node-covering draws: lanes per row and workgroups of the forced-edge kernels for this shape
-static CoverArgs cover_args(int64_t N, int64_t E, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, int32_t* info) {
-    CoverArgs c{N, in_ptr, in_src, in_eid, info, sgs_sample_topq_cover_variant(N, E), 1};
+// draws per workgroup of a batched pass's cover_rows (sgs_sample_topq_multi_cover_group_set); the result does not depend on it
+static int g_multi_cover_group = kMultiCoverG;
+static CoverArgs cover_args(int64_t N, int64_t E, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, int32_t* info, int group,
+                            bool batched) {
+    CoverArgs c{N, in_ptr, in_src, in_eid, info, sgs_sample_topq_cover_variant(N, E), 1, group, batched};
     if (N > 0) {
         const int64_t nb = cdiv(N, kCoverThreads / c.lanes);
         c.grid = static_cast<int>(nb < kCoverGrid ? nb : kCoverGrid);
     }
     return c;
 }
-
-// keys == nullptr: count M only (degenerate draws); hist0 == nullptr: no histogram to correct
+// a single draw's forced-edge kernel.  keys == nullptr: count M only (degenerate draws); hist0 == nullptr: no histogram to correct
 static void launch_cover_rows(const CoverArgs& c, uint32_t* keys, int64_t E, uint32_t* hist0, uint32_t* mcnt, const int64_t* dynE,
                               hipStream_t stream) {
     const dim3 grid(static_cast<unsigned>(c.grid)), blk(kCoverThreads);
@@ -1520,16 +1473,160 @@ static void launch_cover_rows(const CoverArgs& c, uint32_t* keys, int64_t E, uin
     else
         hipLaunchKernelGGL(cover_rows<64>, grid, blk, 0, stream, keys, E, c.N, c.in_ptr, c.in_src, c.in_eid, hist0, mcnt, dynE);
 }
+// a batched pass's: c.group draws per workgroup
+template <int G>
+static void launch_cover_rows_group_g(const CoverArgs& c, const DrawSet& ds, int64_t E, uint32_t* mcnt, hipStream_t stream) {
+    const dim3 grid(static_cast<unsigned>(c.grid), static_cast<unsigned>(cdiv(ds.D, G))), blk(kCoverThreads);
+    if (c.lanes == 4)
+        hipLaunchKernelGGL((cover_rows_group<4, G>), grid, blk, 0, stream, ds, E, c.N, c.in_ptr, c.in_src, c.in_eid, mcnt);
+    else if (c.lanes == 16)
+        hipLaunchKernelGGL((cover_rows_group<16, G>), grid, blk, 0, stream, ds, E, c.N, c.in_ptr, c.in_src, c.in_eid, mcnt);
+    else
+        hipLaunchKernelGGL((cover_rows_group<64, G>), grid, blk, 0, stream, ds, E, c.N, c.in_ptr, c.in_src, c.in_eid, mcnt);
+}
+static void launch_cover_rows_group(const CoverArgs& c, const DrawSet& ds, int64_t E, uint32_t* mcnt, hipStream_t stream) {
+    if (c.group == 1) launch_cover_rows_group_g<1>(c, ds, E, mcnt, stream);
+    else if (c.group == 2) launch_cover_rows_group_g<2>(c, ds, E, mcnt, stream);
+    else launch_cover_rows_group_g<4>(c, ds, E, mcnt, stream);
+}
 
-static int sample_topq_impl(const char* fn, const CoverArgs* cover, int mode, const float* p, const float* prior, double degree_bias_coef,
-                            const float* noise, uint64_t seed, uint64_t stream_id, int64_t E, int64_t q, const int64_t* edge_index,
-                            uint8_t* mask, int64_t* sampled_eid, int64_t* sampled_edge_index, float* sampled_p, float* stats,
-                            float* keys_out, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+enum SelPath { kSelAll, kSelSmall, kSelLarge };   // q == 0 or q == E; at most kSmallBlocks chunks (2 M candidate edges); more
+
+// Everything of a draw set but its keys, once for sgs_sample_topq[_multi][_cover] and sgs_consensus_select.  key_pass(path, ds) launches
+// the caller's zeroing, normalisers and key pass for the path chosen here (no keys on kSelAll).  The forced-edge kernel runs between it
+// and the first selection pass; cover_finish after the stats are written, so before a caller's st_fwd.
+//   kSelSmall: 4 launches, the one-workgroup steps between the passes recomputed by every workgroup (see "fused small-E path" above)
+//   kSelLarge: 9 launches + the stats
+template <class KeyPass>
+static int select_chain(const SamplerWs& w, int64_t D, int64_t E, int64_t q, const float* p, const int64_t* edge_index, const DrawOut& out,
+                        const CoverArgs* cover, const int64_t* dynE, hipStream_t stream, KeyPass key_pass) {
+    const int64_t nblk = cdiv(E, kChunk);
+    const SelPath path = (q == 0 || q == E) ? kSelAll : nblk <= kSmallBlocks ? kSelSmall : kSelLarge;
+    // a draw's three digit histograms on the small path; one per draw, packed, on the large
+    const DrawSet ds{w.keys, w.ks, w.hist, path == kSelSmall ? 3 * kBins : kBins, w.st, w.sel, w.cnt, w.cs, static_cast<int>(D)};
+    const float* scal = w.scal;
+    uint32_t* mcnt = w.mcnt;
+    const unsigned Du = static_cast<unsigned>(ds.D), nb = static_cast<unsigned>(nblk);
+    const dim3 blk(kThreads), grid(nb, Du), hgrid(nblk < kHistGrid ? nb : kHistGrid, Du), one(1, Du);
+    const uint32_t q32 = static_cast<uint32_t>(q);
+    if (int rc = key_pass(path, ds)) return rc;
+    if (cover && path != kSelAll) {
+        if (cover->batched) launch_cover_rows_group(*cover, ds, E, mcnt, stream);
+        else launch_cover_rows(*cover, ds.keys, E, ds.hist, mcnt, dynE, stream);
+    }
+    if (path == kSelAll) {
+        hipLaunchKernelGGL(select_all, dim3(static_cast<unsigned>(cdiv(E, 256)), Du), dim3(256), 0, stream, E, p, edge_index, out,
+                           static_cast<uint8_t>(q == E ? 1 : 0));
+    } else if (path == kSelSmall) {
+        hipLaunchKernelGGL(small_hist_next, grid, blk, 0, stream, ds, E, kShift1, kMask1, kShift0, 1, q32, dynE);
+        hipLaunchKernelGGL(small_hist_next, grid, blk, 0, stream, ds, E, kShift2, kMask2, kShift1, 0, q32, dynE);
+        hipLaunchKernelGGL(small_count, grid, blk, 0, stream, ds, E, q32, scal, out.stats, dynE);
+        hipLaunchKernelGGL(small_compact, grid, blk, 0, stream, ds, E, q, p, edge_index, out, dynE);
+    } else {
+        hipLaunchKernelGGL(select_digit, one, blk, 0, stream, ds, kShift0, 1, q32);
+        hipLaunchKernelGGL(hist_next, hgrid, blk, 0, stream, ds, E, kShift1, kMask1, kShift0);
+        hipLaunchKernelGGL(select_digit, one, blk, 0, stream, ds, kShift1, 0, q32);
+        hipLaunchKernelGGL(hist_next, hgrid, blk, 0, stream, ds, E, kShift2, kMask2, kShift1);
+        hipLaunchKernelGGL(select_digit, one, blk, 0, stream, ds, kShift2, 0, q32);
+        hipLaunchKernelGGL(count_blocks, grid, blk, 0, stream, ds, E);
+        hipLaunchKernelGGL(scan_blocks, one, blk, 0, stream, ds, nblk);
+        hipLaunchKernelGGL(compact, grid, blk, 0, stream, ds, E, q, int64_t(-1), int64_t(0), p, edge_index, out);
+    }
+    // degenerate draws: M does not depend on the keys or on the draw -- one key-less launch counts the rows that have a non-loop entry,
+    // and every draw's finishing workgroup reads those counts
+    if (cover && path == kSelAll && cover->batched) launch_cover_rows(*cover, nullptr, E, nullptr, mcnt, dynE, stream);
+    if (path != kSelSmall && out.stats) hipLaunchKernelGGL(write_stats, one, dim3(1), 0, stream, scal, ds.st, out.stats);
+    if (cover) {
+        if (path == kSelAll && !cover->batched) launch_cover_rows(*cover, nullptr, E, nullptr, mcnt, dynE, stream);
+        hipLaunchKernelGGL(cover_finish, one, blk, 0, stream, mcnt, path == kSelAll ? int64_t(0) : int64_t(kCoverGrid), cover->grid, q,
+                           out.stats, cover->info);
+    }
+    SGS_LAUNCH_OK();
+    return SGS_OK;
+}
+
+// ---------------------------------------------------------------- the exponential race's draws
+struct RaceArgs {
+    int mode;
+    const float *p, *prior, *noise;
+    uint64_t seed, stream_id0;      // draw d: noise row d, or stream stream_id0 + d
+    float one_minus_c, c;           // python: (1 - c) and c are doubles, cast to fp32 when they meet the fp32 tensor
+    float* keys_out;                // single draws only
+};
+static RaceArgs race_args(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
+                          uint64_t stream_id0, float* keys_out) {
+    return RaceArgs{mode, p, prior, noise, seed, stream_id0, static_cast<float>(1.0 - degree_bias_coef), static_cast<float>(degree_bias_coef),
+                    keys_out};
+}
+
+// select_chain's key pass for the race.  The normaliser (Z, or max and sum of exp) does not depend on the noise: one reduction for all
+// draws.  A batched pass differs from a single draw on the small path alone: its key kernel, and the zeroing of the histograms that
+// small_reduce_first clears for one draw only.
+static int race_key_pass(SelPath path, const DrawSet& ds, const RaceArgs& a, const SamplerWs& w, int64_t E, bool multi, const int64_t* dynE,
+                         hipStream_t stream) {
+    const int64_t nblk = cdiv(E, kChunk);
+    const unsigned nb = static_cast<unsigned>(nblk), Du = static_cast<unsigned>(ds.D);
+    const dim3 blk(kThreads), grid(nb);
+    const bool learned = a.mode == SGS_SAMPLE_LEARNED;
+    const float* prior = learned ? a.prior : nullptr;
+    if (path == kSelSmall) {
+        if (multi)
+            if (int rc = zero_async(ds.hist, static_cast<size_t>(3 * kBins) * ds.D * 4, stream)) return rc;
+        const dim3 kgrid(nb, multi ? static_cast<unsigned>(cdiv(ds.D, kMultiG)) : 1u), kblk(kKeyThreads);
+        const float *part_sum = learned ? w.part : w.part2, *part_max = learned ? nullptr : w.part;
+        if (learned) {
+            hipLaunchKernelGGL(small_reduce_first<0>, grid, blk, 0, stream, a.p, E, w.part, ds.hist, dynE);
+        } else {
+            hipLaunchKernelGGL(small_reduce_first<1>, grid, blk, 0, stream, a.p, E, w.part, ds.hist, dynE);
+            hipLaunchKernelGGL(small_reduce_sumexp, grid, blk, 0, stream, a.p, E, w.part, nblk, w.part2, dynE);
+        }
+        if (multi && learned)
+            hipLaunchKernelGGL(multi_keys_hist0<SGS_SAMPLE_LEARNED>, kgrid, kblk, 0, stream, a.p, prior, a.noise, a.seed, a.stream_id0, epoch_ptr(),
+                               E, ds.D, a.one_minus_c, a.c, part_sum, part_max, nblk, w.scal, ds.keys, ds.ks, ds.hist);
+        else if (multi)
+            hipLaunchKernelGGL(multi_keys_hist0<SGS_SAMPLE_PRIOR>, kgrid, kblk, 0, stream, a.p, prior, a.noise, a.seed, a.stream_id0, epoch_ptr(),
+                               E, ds.D, a.one_minus_c, a.c, part_sum, part_max, nblk, w.scal, ds.keys, ds.ks, ds.hist);
+        else if (learned)
+            hipLaunchKernelGGL(small_keys_hist0<SGS_SAMPLE_LEARNED>, kgrid, kblk, 0, stream, a.p, prior, a.noise, a.seed, a.stream_id0, epoch_ptr(),
+                               E, a.one_minus_c, a.c, part_sum, part_max, nblk, w.scal, ds.keys, a.keys_out, ds.hist, dynE);
+        else
+            hipLaunchKernelGGL(small_keys_hist0<SGS_SAMPLE_PRIOR>, kgrid, kblk, 0, stream, a.p, prior, a.noise, a.seed, a.stream_id0, epoch_ptr(),
+                               E, a.one_minus_c, a.c, part_sum, part_max, nblk, w.scal, ds.keys, a.keys_out, ds.hist, dynE);
+        return SGS_OK;
+    }
+    // scal, st and the histograms are adjacent carvings: one zeroing launch (a kernel, not a memset node: see zero_async).  A single draw
+    // clears the one histogram it uses; a batched pass all three per draw, as it always has
+    if (int rc = zero_async(w.scal, static_cast<size_t>(reinterpret_cast<char*>(ds.hist + (multi ? 3 : 1) * kBins * ds.D) - reinterpret_cast<char*>(w.scal)), stream))
+        return rc;
+    if (learned) {
+        hipLaunchKernelGGL(reduce_partial<0>, grid, blk, 0, stream, a.p, E, w.scal, w.part);
+        hipLaunchKernelGGL(reduce_final<0>, dim3(1), blk, 0, stream, w.part, nblk, w.scal);
+    } else {
+        hipLaunchKernelGGL(reduce_partial<1>, grid, blk, 0, stream, a.p, E, w.scal, w.part);
+        hipLaunchKernelGGL(reduce_final<1>, dim3(1), blk, 0, stream, w.part, nblk, w.scal);
+        hipLaunchKernelGGL(reduce_partial<2>, grid, blk, 0, stream, a.p, E, w.scal, w.part);
+        hipLaunchKernelGGL(reduce_final<2>, dim3(1), blk, 0, stream, w.part, nblk, w.scal);
+    }
+    if (path == kSelLarge) {
+        const dim3 hgrid(nblk < kHistGrid ? nb : kHistGrid, Du);
+        if (learned)
+            hipLaunchKernelGGL(keys_hist0<SGS_SAMPLE_LEARNED>, hgrid, blk, 0, stream, a.p, prior, a.noise, a.seed, a.stream_id0, epoch_ptr(),
+                               int64_t(0), E, a.one_minus_c, a.c, w.scal, ds, a.keys_out);
+        else
+            hipLaunchKernelGGL(keys_hist0<SGS_SAMPLE_PRIOR>, hgrid, blk, 0, stream, a.p, prior, a.noise, a.seed, a.stream_id0, epoch_ptr(),
+                               int64_t(0), E, a.one_minus_c, a.c, w.scal, ds, a.keys_out);
+    }
+    return SGS_OK;
+}
+
+// sgs_sample_topq[_cover] (multi == false: D == 1) and sgs_sample_topq_multi[_cover]
+static int sample_draws(const char* fn, bool multi, const CoverArgs* cover, const RaceArgs& a, int64_t D, int64_t E, int64_t q,
+                        const int64_t* edge_index, const DrawOut& out, float* st_weights, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(mode == SGS_SAMPLE_LEARNED || mode == SGS_SAMPLE_PRIOR, SGS_EINVAL, "%s: bad mode %d", fn, mode);
+    SGS_REQUIRE(a.mode == SGS_SAMPLE_LEARNED || a.mode == SGS_SAMPLE_PRIOR, SGS_EINVAL, "%s: bad mode %d", fn, a.mode);
+    SGS_REQUIRE(D >= 1 && D <= 65535, SGS_EINVAL, "%s: D=%lld draws (need 1 <= D <= 65535)", fn, (long long)D);
     SGS_REQUIRE(E >= 0 && q >= 0, SGS_EINVAL, "%s: negative size (E=%lld q=%lld)", fn, (long long)E, (long long)q);
-    SGS_REQUIRE(q <= E, SGS_EINVAL,
-                "%s: cannot sample q=%lld > E=%lld edges without replacement", fn, (long long)q, (long long)E);
+    SGS_REQUIRE(q <= E, SGS_EINVAL, "%s: cannot sample q=%lld > E=%lld edges without replacement", fn, (long long)q, (long long)E);
     SGS_REQUIRE(E < (int64_t(1) << 32), SGS_EINVAL, "%s: E=%lld exceeds 2^32-1", fn, (long long)E);
     if (cover) {
         SGS_REQUIRE(cover->N >= 0, SGS_EINVAL, "%s: negative node count (N=%lld)", fn, (long long)cover->N);
@@ -1539,108 +1636,49 @@ static int sample_topq_impl(const char* fn, const CoverArgs* cover, int mode, co
                     "%s: E=%lld, N=%lld exceed the int32 CSR", fn, (long long)E, (long long)cover->N);
     }
     if (E == 0) return SGS_OK;
-    SGS_REQUIRE(mask, SGS_EINVAL, "%s: null mask", fn);
-    SGS_REQUIRE(p || (mode == SGS_SAMPLE_LEARNED && !prior), SGS_EINVAL, "%s: p == NULL (uniform weights) needs mode LEARNED and no prior", fn);
-    SGS_REQUIRE(!sampled_edge_index || edge_index, SGS_EINVAL, "%s: edge_index required for sampled_edge_index", fn);
-    const size_t ws_need = cover ? sgs_sample_topq_cover_workspace_bytes(E, cover->N) : sgs_sample_topq_workspace_bytes(E);
-    SGS_REQUIRE(ws && ws_bytes >= ws_need, SGS_EWORKSPACE, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, ws_need);
-    SGS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, SGS_EINVAL, "%s: workspace must be 256-B aligned", fn);
-
-    const int64_t nblk = cdiv(E, kChunk);
-    Carver cv(ws);
-    uint32_t* keys = cv.take<uint32_t>(E);
-    float* part = cv.take<float>(nblk + 1);
-    float* scal = cv.take<float>(4);
-    uint32_t* hist = cv.take<uint32_t>(kBins);
-    SelectState* st = cv.take<SelectState>(1);
-    uint2* cnt = cv.take<uint2>(nblk + 1);
-
-    float* part2 = cv.take<float>(nblk + 1);
-    uint32_t* hist3 = cv.take<uint32_t>(3 * kBins);       // fused small-E path: one histogram per digit
-    SelPart* sel = cv.take<SelPart>(2);
-    uint32_t* mcnt = cover ? cv.take<uint32_t>(kCoverGrid) : nullptr;      // covering draws: forced edges per workgroup of cover_rows
-    const dim3 grid(static_cast<unsigned>(nblk)), blk(kThreads);
-    const dim3 hgrid(static_cast<unsigned>(nblk < kHistGrid ? nblk : kHistGrid));
-    // python: (1 - c) and c are doubles, cast to fp32 when they meet the fp32 tensor
-    const float one_minus_c = static_cast<float>(1.0 - degree_bias_coef);
-    const float c = static_cast<float>(degree_bias_coef);
-    const int mask_aligned = (reinterpret_cast<uintptr_t>(mask) & 7) == 0;
-
+    SGS_REQUIRE(out.mask, SGS_EINVAL, "%s: null mask", fn);
+    SGS_REQUIRE(a.p || (a.mode == SGS_SAMPLE_LEARNED && !a.prior), SGS_EINVAL, "%s: p == NULL (uniform weights) needs mode LEARNED and no prior", fn);
+    SGS_REQUIRE(!out.sei || edge_index, SGS_EINVAL, "%s: edge_index required for sampled_edge_index", fn);
+    SGS_REQUIRE(!st_weights || (a.p && out.eid && out.stats && a.mode == SGS_SAMPLE_LEARNED), SGS_EINVAL,
+                "%s: st_weights needs p, sampled_eid, stats and mode LEARNED", fn);
     const int64_t* dynE = dyn_edges_ptr();
-    SGS_REQUIRE(!dynE || (nblk <= kSmallBlocks && q > 0 && q < E), SGS_EINVAL,
+    SGS_REQUIRE(!multi || !dynE, SGS_EINVAL, "%s: not available under a dynamic edge count (sgs_dyn_edges_set)", fn);
+    if (int rc = check_ws(fn, ws, ws_bytes, sampler_ws(nullptr, E, D, cover != nullptr, false).bytes)) return rc;
+    SGS_REQUIRE(!dynE || (cdiv(E, kChunk) <= kSmallBlocks && q > 0 && q < E), SGS_EINVAL,
                 "%s: a dynamic edge count (sgs_dyn_edges_set) needs 0 < q < capacity <= %lld", fn, (long long)kSmallBlocks * kChunk);
-    if (nblk <= kSmallBlocks && q > 0 && q < E) {
-        // fused small-E path: 6 / 7 launches (see "fused small-E path" above); same arithmetic, same results
-        const uint32_t q32 = static_cast<uint32_t>(q);
-        uint32_t *h0 = hist3, *h1 = hist3 + kBins, *h2 = hist3 + 2 * kBins;
-        const dim3 kgrid(static_cast<unsigned>(nblk)), kblk(kKeyThreads);
-        if (mode == SGS_SAMPLE_LEARNED) {
-            hipLaunchKernelGGL(small_reduce_first<0>, grid, blk, 0, stream, p, E, part, hist3, dynE);
-            hipLaunchKernelGGL(small_keys_hist0<SGS_SAMPLE_LEARNED>, kgrid, kblk, 0, stream, p, prior, noise, seed, stream_id, epoch_ptr(), E,
-                               one_minus_c, c, part, static_cast<const float*>(nullptr), nblk, scal, keys, keys_out, h0, dynE);
-        } else {
-            hipLaunchKernelGGL(small_reduce_first<1>, grid, blk, 0, stream, p, E, part, hist3, dynE);
-            hipLaunchKernelGGL(small_reduce_sumexp, grid, blk, 0, stream, p, E, part, nblk, part2, dynE);
-            hipLaunchKernelGGL(small_keys_hist0<SGS_SAMPLE_PRIOR>, kgrid, kblk, 0, stream, p, static_cast<const float*>(nullptr), noise, seed,
-                               stream_id, epoch_ptr(), E, one_minus_c, c, part2, part, nblk, scal, keys, keys_out, h0, dynE);
-        }
-        if (cover) launch_cover_rows(*cover, keys, E, h0, mcnt, dynE, stream);
-        hipLaunchKernelGGL(small_hist_next, grid, blk, 0, stream, keys, E, kShift1, kMask1, kShift0, 1, q32, h0,
-                           static_cast<const SelPart*>(nullptr), sel, h1, dynE);
-        hipLaunchKernelGGL(small_hist_next, grid, blk, 0, stream, keys, E, kShift2, kMask2, kShift1, 0, q32, h1, sel, sel + 1, h2, dynE);
-        hipLaunchKernelGGL(small_count, grid, blk, 0, stream, keys, E, q32, h2, sel + 1, st, cnt, scal, stats, dynE);
-        hipLaunchKernelGGL(small_compact, grid, blk, 0, stream, keys, E, q, st, cnt, p, edge_index, mask, mask_aligned, sampled_eid,
-                           sampled_edge_index, sampled_p, dynE);
-        if (cover) hipLaunchKernelGGL(cover_finish, dim3(1), blk, 0, stream, mcnt, cover->grid, q, stats, cover->info);
+
+    const SamplerWs w = sampler_ws(ws, E, D, cover != nullptr, false);
+    if (int rc = select_chain(w, D, E, q, a.p, edge_index, out, cover, dynE, stream,
+                              [&](SelPath path, const DrawSet& ds) { return race_key_pass(path, ds, a, w, E, multi, dynE, stream); }))
+        return rc;
+    if (st_weights && q > 0) {   // (after cover_finish: the straight-through weights read the threshold the single call reports, flag bit off)
+        const dim3 g(static_cast<unsigned>(cdiv(q, 256)), static_cast<unsigned>(D));
+        if (a.prior)
+            hipLaunchKernelGGL(st_fwd<true>, g, dim3(256), 0, stream, a.p, a.prior, a.one_minus_c, a.c, out.stats, out.eid, q, st_weights);
+        else
+            hipLaunchKernelGGL(st_fwd<false>, g, dim3(256), 0, stream, a.p, a.prior, a.one_minus_c, a.c, out.stats, out.eid, q, st_weights);
         SGS_LAUNCH_OK();
-        return SGS_OK;
     }
+    return SGS_OK;
+}
 
-    // scal, hist and st are adjacent carvings: one zeroing launch (a kernel, not a memset node: see zero_async)
-    if (int rc = zero_async(scal, static_cast<size_t>(reinterpret_cast<char*>(st + 1) - reinterpret_cast<char*>(scal)), stream)) return rc;
+extern "C" {
 
-    if (mode == SGS_SAMPLE_LEARNED) {
-        hipLaunchKernelGGL(reduce_partial<0>, grid, blk, 0, stream, p, E, scal, part);
-        hipLaunchKernelGGL(reduce_final<0>, dim3(1), blk, 0, stream, part, nblk, scal);
-    } else {
-        hipLaunchKernelGGL(reduce_partial<1>, grid, blk, 0, stream, p, E, scal, part);
-        hipLaunchKernelGGL(reduce_final<1>, dim3(1), blk, 0, stream, part, nblk, scal);
-        hipLaunchKernelGGL(reduce_partial<2>, grid, blk, 0, stream, p, E, scal, part);
-        hipLaunchKernelGGL(reduce_final<2>, dim3(1), blk, 0, stream, part, nblk, scal);
-    }
-    SGS_LAUNCH_OK();
+size_t sgs_sample_topq_workspace_bytes(int64_t E) { return sampler_ws(nullptr, E, 1, false, false).bytes; }
+// (N: the forced-edge kernel's per-workgroup counts have a fixed length, its grid is capped at kCoverGrid)
+size_t sgs_sample_topq_cover_workspace_bytes(int64_t E, int64_t N) { (void)N; return sampler_ws(nullptr, E, 1, true, false).bytes; }
+size_t sgs_sample_topq_multi_workspace_bytes(int64_t E, int64_t D) { return sampler_ws(nullptr, E, D, false, false).bytes; }
+size_t sgs_sample_topq_multi_cover_workspace_bytes(int64_t E, int64_t N, int64_t D) { (void)N; return sampler_ws(nullptr, E, D, true, false).bytes; }
+size_t sgs_consensus_select_workspace_bytes(int64_t E) { return sampler_ws(nullptr, E, 1, false, true).bytes; }
 
-    if (q == 0 || q == E) {   // degenerate draws: nothing / everything
-        hipLaunchKernelGGL(select_all, dim3(cdiv(E, 256)), dim3(256), 0, stream, E, p, edge_index, mask, sampled_eid,
-                           sampled_edge_index, sampled_p, static_cast<uint8_t>(q == E ? 1 : 0));
-        if (stats) hipLaunchKernelGGL(write_stats, dim3(1), dim3(1), 0, stream, scal, st, stats);
-        if (cover) {       // M does not depend on the keys: count the rows that have a non-loop entry
-            launch_cover_rows(*cover, nullptr, E, nullptr, mcnt, dynE, stream);
-            hipLaunchKernelGGL(cover_finish, dim3(1), blk, 0, stream, mcnt, cover->grid, q, stats, cover->info);
-        }
-        SGS_LAUNCH_OK();
-        return SGS_OK;
-    }
+int sgs_sample_topq_cover_variant(int64_t N, int64_t E) {
+    if (N <= 0 || E < 8 * N) return 4;
+    return E < 64 * N ? 16 : 64;
+}
 
-    if (mode == SGS_SAMPLE_LEARNED)
-        hipLaunchKernelGGL(keys_hist0<SGS_SAMPLE_LEARNED>, hgrid, blk, 0, stream, p, prior, noise, seed, stream_id, epoch_ptr(), int64_t(0), E,
-                           one_minus_c, c, scal, keys, keys_out, hist);
-    else
-        hipLaunchKernelGGL(keys_hist0<SGS_SAMPLE_PRIOR>, hgrid, blk, 0, stream, p, nullptr, noise, seed, stream_id, epoch_ptr(), int64_t(0), E,
-                           one_minus_c, c, scal, keys, keys_out, hist);
-    if (cover) launch_cover_rows(*cover, keys, E, hist, mcnt, dynE, stream);
-    hipLaunchKernelGGL(select_digit, dim3(1), blk, 0, stream, hist, kShift0, 1, static_cast<uint32_t>(q), st);
-    hipLaunchKernelGGL(hist_next, hgrid, blk, 0, stream, keys, E, kShift1, kMask1, kShift0, st, hist);
-    hipLaunchKernelGGL(select_digit, dim3(1), blk, 0, stream, hist, kShift1, 0, static_cast<uint32_t>(q), st);
-    hipLaunchKernelGGL(hist_next, hgrid, blk, 0, stream, keys, E, kShift2, kMask2, kShift1, st, hist);
-    hipLaunchKernelGGL(select_digit, dim3(1), blk, 0, stream, hist, kShift2, 0, static_cast<uint32_t>(q), st);
-    hipLaunchKernelGGL(count_blocks, grid, blk, 0, stream, keys, E, st, cnt);
-    hipLaunchKernelGGL(scan_blocks, dim3(1), blk, 0, stream, cnt, nblk);
-    hipLaunchKernelGGL(compact, grid, blk, 0, stream, keys, E, q, int64_t(-1), int64_t(0), st, cnt, p, edge_index, mask, mask_aligned,
-                       sampled_eid, sampled_edge_index, sampled_p);
-    if (stats) hipLaunchKernelGGL(write_stats, dim3(1), dim3(1), 0, stream, scal, st, stats);
-    if (cover) hipLaunchKernelGGL(cover_finish, dim3(1), blk, 0, stream, mcnt, cover->grid, q, stats, cover->info);
-    SGS_LAUNCH_OK();
+int sgs_sample_topq_multi_cover_group_set(int G) {
+    SGS_REQUIRE(G == 0 || G == 1 || G == 2 || G == 4, SGS_EINVAL, "sgs_sample_topq_multi_cover_group_set: G=%d (need 1, 2 or 4, or 0 for the default)", G);
+    g_multi_cover_group = G ? G : kMultiCoverG;
     return SGS_OK;
 }
 
@@ -1648,8 +1686,8 @@ int sgs_sample_topq(int mode, const float* p, const float* prior, double degree_
                     uint64_t seed, uint64_t stream_id, int64_t E, int64_t q, const int64_t* edge_index,
                     uint8_t* mask, int64_t* sampled_eid, int64_t* sampled_edge_index, float* sampled_p, float* stats,
                     float* keys_out, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    return sample_topq_impl("sgs_sample_topq", nullptr, mode, p, prior, degree_bias_coef, noise, seed, stream_id, E, q, edge_index, mask,
-                            sampled_eid, sampled_edge_index, sampled_p, stats, keys_out, ws, ws_bytes, stream_);
+    return sample_draws("sgs_sample_topq", false, nullptr, race_args(mode, p, prior, degree_bias_coef, noise, seed, stream_id, keys_out), 1, E, q,
+                        edge_index, DrawOut{mask, sampled_eid, sampled_edge_index, sampled_p, stats}, nullptr, ws, ws_bytes, stream_);
 }
 
 int sgs_sample_topq_cover(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise,
@@ -1657,9 +1695,26 @@ int sgs_sample_topq_cover(int mode, const float* p, const float* prior, double d
                           int64_t N, const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid,
                           uint8_t* mask, int64_t* sampled_eid, int64_t* sampled_edge_index, float* sampled_p,
                           float* stats, float* keys_out, int32_t* cover_info, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    const CoverArgs c = cover_args(N, E, in_ptr, in_src, in_eid, cover_info);
-    return sample_topq_impl("sgs_sample_topq_cover", &c, mode, p, prior, degree_bias_coef, noise, seed, stream_id, E, q, edge_index, mask,
-                            sampled_eid, sampled_edge_index, sampled_p, stats, keys_out, ws, ws_bytes, stream_);
+    const CoverArgs c = cover_args(N, E, in_ptr, in_src, in_eid, cover_info, 1, false);
+    return sample_draws("sgs_sample_topq_cover", false, &c, race_args(mode, p, prior, degree_bias_coef, noise, seed, stream_id, keys_out), 1, E, q,
+                        edge_index, DrawOut{mask, sampled_eid, sampled_edge_index, sampled_p, stats}, nullptr, ws, ws_bytes, stream_);
+}
+
+int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
+                          uint64_t stream_id0, int64_t D, int64_t E, int64_t q, const int64_t* edge_index, uint8_t* mask, int64_t* sampled_eid,
+                          int64_t* sampled_edge_index, float* stats, float* st_weights, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    return sample_draws("sgs_sample_topq_multi", true, nullptr, race_args(mode, p, prior, degree_bias_coef, noise, seed, stream_id0, nullptr), D, E,
+                        q, edge_index, DrawOut{mask, sampled_eid, sampled_edge_index, nullptr, stats}, st_weights, ws, ws_bytes, stream_);
+}
+
+int sgs_sample_topq_multi_cover(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
+                                uint64_t stream_id0, int64_t D, int64_t E, int64_t q, const int64_t* edge_index, int64_t N,
+                                const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, uint8_t* mask, int64_t* sampled_eid,
+                                int64_t* sampled_edge_index, float* stats, float* st_weights, int32_t* cover_info, void* ws, size_t ws_bytes,
+                                sgs_stream_t stream_) {
+    const CoverArgs c = cover_args(N, E, in_ptr, in_src, in_eid, cover_info, g_multi_cover_group, true);
+    return sample_draws("sgs_sample_topq_multi_cover", true, &c, race_args(mode, p, prior, degree_bias_coef, noise, seed, stream_id0, nullptr), D,
+                        E, q, edge_index, DrawOut{mask, sampled_eid, sampled_edge_index, nullptr, stats}, st_weights, ws, ws_bytes, stream_);
 }
 
 /* ---------------------------------------------------------------- consensus of D draws (the sparsifier export)
@@ -1682,11 +1737,6 @@ int sgs_consensus_accum(const uint8_t* mask, int64_t mask_stride, int64_t Dc, in
     return SGS_OK;
 }
 
-size_t sgs_consensus_select_workspace_bytes(int64_t E) {
-    if (E < 0) E = 0;
-    return sgs_sample_topq_workspace_bytes(E) + carve_bytes(E, 8);      // the sampler's carvings + edge ids for count_out when eid == NULL
-}
-
 int sgs_consensus_select(const int32_t* count, const float* p, int64_t E, int64_t q, const int64_t* edge_index, uint8_t* mask, int64_t* eid,
                          int64_t* edge_index_out, int32_t* count_out, float* p_out, uint32_t* keys_out, void* ws, size_t ws_bytes,
                          sgs_stream_t stream_) {
@@ -1698,67 +1748,31 @@ int sgs_consensus_select(const int32_t* count, const float* p, int64_t E, int64_
     if (E == 0) return SGS_OK;
     SGS_REQUIRE(count && mask, SGS_EINVAL, "%s: null count or mask", fn);
     SGS_REQUIRE(!edge_index_out || edge_index, SGS_EINVAL, "%s: edge_index required for edge_index_out", fn);
-    const size_t ws_need = sgs_consensus_select_workspace_bytes(E);
-    SGS_REQUIRE(ws && ws_bytes >= ws_need, SGS_EWORKSPACE, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, ws_need);
-    SGS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, SGS_EINVAL, "%s: workspace must be 256-B aligned", fn);
+    if (int rc = check_ws(fn, ws, ws_bytes, sgs_consensus_select_workspace_bytes(E))) return rc;
 
-    // sample_topq_impl's carvings, in its order
-    const int64_t nblk = cdiv(E, kChunk);
-    Carver cv(ws);
-    uint32_t* keys = cv.take<uint32_t>(E);
-    cv.take<float>(nblk + 1);
-    float* scal = cv.take<float>(4);
-    uint32_t* hist = cv.take<uint32_t>(kBins);
-    SelectState* st = cv.take<SelectState>(1);
-    uint2* cnt = cv.take<uint2>(nblk + 1);
-    cv.take<float>(nblk + 1);
-    uint32_t* hist3 = cv.take<uint32_t>(3 * kBins);
-    SelPart* sel = cv.take<SelPart>(2);
-    int64_t* eid_ws = cv.take<int64_t>(E);
-    if (count_out && !eid) eid = eid_ws;
-    const dim3 grid(static_cast<unsigned>(nblk)), blk(kThreads);
-    const dim3 hgrid(static_cast<unsigned>(nblk < kHistGrid ? nblk : kHistGrid));
-    const int mask_aligned = (reinterpret_cast<uintptr_t>(mask) & 7) == 0;
-    const int64_t* no_dyn = nullptr;                 // the consensus is not a captured path: sizes are taken as given
-
-    if (q == 0 || q == E) {                          // nothing / everything: the keys only for keys_out
-        if (keys_out) {
-            if (int rc = zero_async(hist, kBins * sizeof(uint32_t), stream)) return rc;
-            hipLaunchKernelGGL(consensus_keys_hist0, hgrid, blk, 0, stream, count, p, E, keys, keys_out, hist);
-        }
-        hipLaunchKernelGGL(select_all, dim3(cdiv(E, 256)), dim3(256), 0, stream, E, p, edge_index, mask, eid, edge_index_out, p_out,
-                           static_cast<uint8_t>(q == E ? 1 : 0));
-    } else if (nblk <= kSmallBlocks) {
-        // fused small-E path: the digit selections and the block scan are recomputed by every workgroup of the next pass
-        const uint32_t q32 = static_cast<uint32_t>(q);
-        uint32_t *h0 = hist3, *h1 = hist3 + kBins, *h2 = hist3 + 2 * kBins;
-        if (int rc = zero_async(hist3, 3 * kBins * sizeof(uint32_t), stream)) return rc;
-        hipLaunchKernelGGL(consensus_keys_hist0, grid, blk, 0, stream, count, p, E, keys, keys_out, h0);
-        hipLaunchKernelGGL(small_hist_next, grid, blk, 0, stream, keys, E, kShift1, kMask1, kShift0, 1, q32, h0,
-                           static_cast<const SelPart*>(nullptr), sel, h1, no_dyn);
-        hipLaunchKernelGGL(small_hist_next, grid, blk, 0, stream, keys, E, kShift2, kMask2, kShift1, 0, q32, h1, sel, sel + 1, h2, no_dyn);
-        hipLaunchKernelGGL(small_count, grid, blk, 0, stream, keys, E, q32, h2, sel + 1, st, cnt, scal, static_cast<float*>(nullptr), no_dyn);
-        hipLaunchKernelGGL(small_compact, grid, blk, 0, stream, keys, E, q, st, cnt, p, edge_index, mask, mask_aligned, eid, edge_index_out,
-                           p_out, no_dyn);
-    } else {
-        if (int rc = zero_async(scal, static_cast<size_t>(reinterpret_cast<char*>(st + 1) - reinterpret_cast<char*>(scal)), stream)) return rc;
-        hipLaunchKernelGGL(consensus_keys_hist0, hgrid, blk, 0, stream, count, p, E, keys, keys_out, hist);
-        hipLaunchKernelGGL(select_digit, dim3(1), blk, 0, stream, hist, kShift0, 1, static_cast<uint32_t>(q), st);
-        hipLaunchKernelGGL(hist_next, hgrid, blk, 0, stream, keys, E, kShift1, kMask1, kShift0, st, hist);
-        hipLaunchKernelGGL(select_digit, dim3(1), blk, 0, stream, hist, kShift1, 0, static_cast<uint32_t>(q), st);
-        hipLaunchKernelGGL(hist_next, hgrid, blk, 0, stream, keys, E, kShift2, kMask2, kShift1, st, hist);
-        hipLaunchKernelGGL(select_digit, dim3(1), blk, 0, stream, hist, kShift2, 0, static_cast<uint32_t>(q), st);
-        hipLaunchKernelGGL(count_blocks, grid, blk, 0, stream, keys, E, st, cnt);
-        hipLaunchKernelGGL(scan_blocks, dim3(1), blk, 0, stream, cnt, nblk);
-        hipLaunchKernelGGL(compact, grid, blk, 0, stream, keys, E, q, int64_t(-1), int64_t(0), st, cnt, p, edge_index, mask, mask_aligned, eid,
-                           edge_index_out, p_out);
-    }
+    const SamplerWs w = sampler_ws(ws, E, 1, false, true);
+    if (count_out && !eid) eid = w.eid;
+    // the key pass with the histograms it needs cleared first; nothing / everything needs the keys only for keys_out.  No dynamic edge
+    // count: the consensus is not a captured path, sizes are taken as given.
+    auto key_pass = [&](SelPath path, const DrawSet& ds) -> int {
+        if (path == kSelAll && !keys_out) return SGS_OK;
+        const int64_t nblk = cdiv(E, kChunk);
+        const unsigned nb = static_cast<unsigned>(nblk);
+        int rc;
+        if (path == kSelLarge) rc = zero_async(w.scal, static_cast<size_t>(reinterpret_cast<char*>(ds.hist + kBins) - reinterpret_cast<char*>(w.scal)), stream);
+        else rc = zero_async(ds.hist, (path == kSelSmall ? 3 : 1) * kBins * sizeof(uint32_t), stream);
+        if (rc) return rc;
+        hipLaunchKernelGGL(consensus_keys_hist0, dim3(nblk < kHistGrid ? nb : kHistGrid), dim3(kThreads), 0, stream, count, p,
+                           E, ds.keys, keys_out, ds.hist);
+        return SGS_OK;
+    };
+    if (int rc = select_chain(w, 1, E, q, p, edge_index, DrawOut{mask, eid, edge_index_out, p_out, nullptr}, nullptr, nullptr, stream, key_pass))
+        return rc;
     if (count_out && q > 0)
         hipLaunchKernelGGL(consensus_gather_count, dim3(cdiv(q, 256)), dim3(256), 0, stream, count, eid, q, E, count_out);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
-
 
 /* ---------------------------------------------------------------- phase API (edge-sharded draws)
  * The same kernels as sgs_sample_topq, exposed per phase so that R ranks holding contiguous,
@@ -1771,6 +1785,10 @@ size_t sgs_sampler_shard_workspace_bytes(int64_t E_local) {
     return carve_bytes(E_local, 4) + carve_bytes(cdiv(E_local, kChunk) + 1, sizeof(uint2)) + 256;
 }
 int64_t sgs_sampler_chunk(void) { return kChunk; }
+// a phase's one draw over the caller's own buffers (those a phase does not touch are null)
+static DrawSet shard_draw(const uint32_t* keys, uint32_t* hist, const void* state, uint2* cnt) {
+    return DrawSet{const_cast<uint32_t*>(keys), 0, hist, 0, static_cast<SelectState*>(const_cast<void*>(state)), nullptr, cnt, 0, 1};
+}
 
 int sgs_sampler_shard_partials(int stage, const float* p, int64_t E, const float* scal, float* part, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -1808,10 +1826,10 @@ int sgs_sampler_shard_keys(int mode, const float* p, const float* prior, double 
     const dim3 hgrid(static_cast<unsigned>(nb_ < kHistGrid ? nb_ : kHistGrid)), blk(kThreads);
     if (mode == SGS_SAMPLE_LEARNED)
         hipLaunchKernelGGL(keys_hist0<SGS_SAMPLE_LEARNED>, hgrid, blk, 0, stream, p, prior, noise, seed, stream_id, epoch_ptr(), edge_offset, E,
-                           one_minus_c, c, scal, keys, keys_out, hist);
+                           one_minus_c, c, scal, shard_draw(keys, hist, nullptr, nullptr), keys_out);
     else
         hipLaunchKernelGGL(keys_hist0<SGS_SAMPLE_PRIOR>, hgrid, blk, 0, stream, p, nullptr, noise, seed, stream_id, epoch_ptr(), edge_offset, E,
-                           one_minus_c, c, scal, keys, keys_out, hist);
+                           one_minus_c, c, scal, shard_draw(keys, hist, nullptr, nullptr), keys_out);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -1822,8 +1840,9 @@ int sgs_sampler_shard_hist(const uint32_t* keys, int64_t E, int pass, const void
     if (E == 0) return SGS_OK;
     const int64_t nb_ = cdiv(E, kChunk);
     const dim3 hgrid(static_cast<unsigned>(nb_ < kHistGrid ? nb_ : kHistGrid)), blk(kThreads);
-    if (pass == 1) hipLaunchKernelGGL(hist_next, hgrid, blk, 0, stream, keys, E, kShift1, kMask1, kShift0, static_cast<const SelectState*>(state), hist);
-    else hipLaunchKernelGGL(hist_next, hgrid, blk, 0, stream, keys, E, kShift2, kMask2, kShift1, static_cast<const SelectState*>(state), hist);
+    const DrawSet ds = shard_draw(keys, hist, state, nullptr);
+    if (pass == 1) hipLaunchKernelGGL(hist_next, hgrid, blk, 0, stream, ds, E, kShift1, kMask1, kShift0);
+    else hipLaunchKernelGGL(hist_next, hgrid, blk, 0, stream, ds, E, kShift2, kMask2, kShift1);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -1832,8 +1851,8 @@ int sgs_sampler_select(uint32_t* hist, int pass, int64_t q, void* state, sgs_str
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     SGS_REQUIRE(pass >= 0 && pass <= 2 && q > 0 && hist && state, SGS_EINVAL, "sgs_sampler_select: bad arguments");
     const int shift = pass == 0 ? kShift0 : pass == 1 ? kShift1 : kShift2;
-    hipLaunchKernelGGL(select_digit, dim3(1), dim3(kThreads), 0, stream, hist, shift, pass == 0 ? 1 : 0, static_cast<uint32_t>(q),
-                       static_cast<SelectState*>(state));
+    hipLaunchKernelGGL(select_digit, dim3(1), dim3(kThreads), 0, stream, shard_draw(nullptr, hist, state, nullptr), shift, pass == 0 ? 1 : 0,
+                       static_cast<uint32_t>(q));
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -1847,9 +1866,10 @@ int sgs_sampler_shard_count(const uint32_t* keys, int64_t E, const void* state, 
     cv.take<uint32_t>(E);                                  // keys live in the caller's copy of this region
     uint2* cnt = cv.take<uint2>(cdiv(E, kChunk) + 1);
     const int64_t nblk = cdiv(E, kChunk);
-    if (nblk > 0) hipLaunchKernelGGL(count_blocks, dim3(nblk), dim3(kThreads), 0, stream, keys, E, static_cast<const SelectState*>(state), cnt);
+    const DrawSet ds = shard_draw(keys, nullptr, state, cnt);
+    if (nblk > 0) hipLaunchKernelGGL(count_blocks, dim3(nblk), dim3(kThreads), 0, stream, ds, E);
     hipLaunchKernelGGL(total_counts, dim3(1), dim3(kThreads), 0, stream, cnt, nblk, counts);
-    if (nblk > 0) hipLaunchKernelGGL(scan_blocks, dim3(1), dim3(kThreads), 0, stream, cnt, nblk);
+    if (nblk > 0) hipLaunchKernelGGL(scan_blocks, dim3(1), dim3(kThreads), 0, stream, ds, nblk);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -1866,10 +1886,8 @@ int sgs_sampler_shard_compact(const uint32_t* keys, int64_t E, const void* state
     Carver cv(ws);
     cv.take<uint32_t>(E);
     uint2* cnt = cv.take<uint2>(cdiv(E, kChunk) + 1);      // scanned by sgs_sampler_shard_count
-    const int mask_aligned = (reinterpret_cast<uintptr_t>(mask) & 7) == 0;
-    hipLaunchKernelGGL(compact, dim3(cdiv(E, kChunk)), dim3(kThreads), 0, stream, keys, E, q_local, ties_local, edge_offset,
-                       static_cast<const SelectState*>(state), cnt, p, edge_index_local, mask, mask_aligned, sampled_eid,
-                       sampled_edge_index, sampled_p);
+    hipLaunchKernelGGL(compact, dim3(cdiv(E, kChunk)), dim3(kThreads), 0, stream, shard_draw(keys, nullptr, state, cnt), E, q_local, ties_local,
+                       edge_offset, p, edge_index_local, DrawOut{mask, sampled_eid, sampled_edge_index, sampled_p, nullptr});
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -1892,10 +1910,10 @@ int sgs_st_weights_fwd(const float* p, const float* prior, double degree_bias_co
     SGS_REQUIRE(p && stats && sampled_eid && w, SGS_EINVAL, "sgs_st_weights_fwd: null pointer");
     const float one_minus_c = static_cast<float>(1.0 - degree_bias_coef), c = static_cast<float>(degree_bias_coef);
     if (prior)
-        hipLaunchKernelGGL(st_fwd_kernel<true>, dim3(cdiv(q, 256)), dim3(256), 0, stream, p, prior, one_minus_c, c, stats,
+        hipLaunchKernelGGL(st_fwd<true>, dim3(cdiv(q, 256)), dim3(256), 0, stream, p, prior, one_minus_c, c, stats,
                            sampled_eid, q, w);
     else
-        hipLaunchKernelGGL(st_fwd_kernel<false>, dim3(cdiv(q, 256)), dim3(256), 0, stream, p, prior, one_minus_c, c, stats,
+        hipLaunchKernelGGL(st_fwd<false>, dim3(cdiv(q, 256)), dim3(256), 0, stream, p, prior, one_minus_c, c, stats,
                            sampled_eid, q, w);
     SGS_LAUNCH_OK();
     return SGS_OK;
@@ -1943,195 +1961,6 @@ int sgs_st_weights_bwd(const float* p, const float* prior, double degree_bias_co
     }
     SGS_LAUNCH_OK();
     return SGS_OK;
-}
-
-}  // extern "C"
-
-// draws per workgroup of multi_cover_rows (sgs_sample_topq_multi_cover_group_set); the result does not depend on it
-static int g_multi_cover_group = kMultiCoverG;
-template <int G>
-static void launch_multi_cover_rows_g(const CoverArgs& c, uint32_t* keys, int64_t ks, int64_t E, int64_t D, uint32_t* hist, int64_t hs,
-                                    uint32_t* mcnt, hipStream_t stream) {
-    const dim3 grid(static_cast<unsigned>(c.grid), static_cast<unsigned>(cdiv(D, G))), blk(kCoverThreads);
-    const int Di = static_cast<int>(D);
-    if (c.lanes == 4)
-        hipLaunchKernelGGL((multi_cover_rows<4, G>), grid, blk, 0, stream, keys, ks, E, Di, c.N, c.in_ptr, c.in_src, c.in_eid, hist, hs, mcnt);
-    else if (c.lanes == 16)
-        hipLaunchKernelGGL((multi_cover_rows<16, G>), grid, blk, 0, stream, keys, ks, E, Di, c.N, c.in_ptr, c.in_src, c.in_eid, hist, hs, mcnt);
-    else
-        hipLaunchKernelGGL((multi_cover_rows<64, G>), grid, blk, 0, stream, keys, ks, E, Di, c.N, c.in_ptr, c.in_src, c.in_eid, hist, hs, mcnt);
-}
-static void launch_multi_cover_rows(const CoverArgs& c, uint32_t* keys, int64_t ks, int64_t E, int64_t D, uint32_t* hist, int64_t hs,
-                                    uint32_t* mcnt, hipStream_t stream) {
-    if (g_multi_cover_group == 1) launch_multi_cover_rows_g<1>(c, keys, ks, E, D, hist, hs, mcnt, stream);
-    else if (g_multi_cover_group == 2) launch_multi_cover_rows_g<2>(c, keys, ks, E, D, hist, hs, mcnt, stream);
-    else launch_multi_cover_rows_g<4>(c, keys, ks, E, D, hist, hs, mcnt, stream);
-}
-
-extern "C" {
-
-size_t sgs_sample_topq_multi_workspace_bytes(int64_t E, int64_t D) {
-    if (E < 0) E = 0;
-    if (D < 1) D = 1;
-    const int64_t nblk = cdiv(E, kChunk) + 1;
-    return carve_bytes(static_cast<size_t>(multi_key_stride(E) * D), 4)   // keys, one padded row per draw
-           + 2 * carve_bytes(nblk, 4)                                     // partials (sum / max, sum of exp)
-           + carve_bytes(4, 4)                                            // scalars Z, max
-           + carve_bytes(static_cast<size_t>(3 * kBins * D), 4)           // digit histograms (3 per draw on the small path, 1 on the large)
-           + carve_bytes(D, sizeof(SelectState))
-           + carve_bytes(static_cast<size_t>(nblk * D), sizeof(uint2))
-           + carve_bytes(2 * D, sizeof(SelPart)) + 256;
-}
-
-size_t sgs_sample_topq_multi_cover_workspace_bytes(int64_t E, int64_t N, int64_t D) {
-    (void)N;       // as sgs_sample_topq_cover_workspace_bytes: kCoverGrid per-workgroup counts, here per draw
-    if (D < 1) D = 1;
-    return sgs_sample_topq_multi_workspace_bytes(E, D) + carve_bytes(static_cast<size_t>(kCoverGrid * D), 4);
-}
-
-
-int sgs_sample_topq_multi_cover_group_set(int G) {
-    SGS_REQUIRE(G == 0 || G == 1 || G == 2 || G == 4, SGS_EINVAL, "sgs_sample_topq_multi_cover_group_set: G=%d (need 1, 2 or 4, or 0 for the default)", G);
-    g_multi_cover_group = G ? G : kMultiCoverG;
-    return SGS_OK;
-}
-
-// sgs_sample_topq_multi (cover == nullptr) and sgs_sample_topq_multi_cover
-static int sample_topq_multi_impl(const char* fn, const CoverArgs* cover, int mode, const float* p, const float* prior, double degree_bias_coef,
-                                  const float* noise, uint64_t seed, uint64_t stream_id0, int64_t D, int64_t E, int64_t q,
-                                  const int64_t* edge_index, uint8_t* mask, int64_t* sampled_eid, int64_t* sampled_edge_index, float* stats,
-                                  float* st_weights, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(mode == SGS_SAMPLE_LEARNED || mode == SGS_SAMPLE_PRIOR, SGS_EINVAL, "%s: bad mode %d", fn, mode);
-    SGS_REQUIRE(D >= 1 && D <= 65535, SGS_EINVAL, "%s: D=%lld draws (need 1 <= D <= 65535)", fn, (long long)D);
-    SGS_REQUIRE(E >= 0 && q >= 0, SGS_EINVAL, "%s: negative size (E=%lld q=%lld)", fn, (long long)E, (long long)q);
-    SGS_REQUIRE(q <= E, SGS_EINVAL, "%s: cannot sample q=%lld > E=%lld edges without replacement", fn, (long long)q, (long long)E);
-    SGS_REQUIRE(E < (int64_t(1) << 32), SGS_EINVAL, "%s: E=%lld exceeds 2^32-1", fn, (long long)E);
-    if (cover) {
-        SGS_REQUIRE(cover->N >= 0, SGS_EINVAL, "%s: negative node count (N=%lld)", fn, (long long)cover->N);
-        SGS_REQUIRE(E == 0 || (cover->in_ptr && cover->in_src && cover->in_eid), SGS_EINVAL,
-                    "%s: null destination CSR (in_ptr / in_src / in_eid) with E=%lld", fn, (long long)E);
-        SGS_REQUIRE(E < (int64_t(1) << 31) && cover->N < (int64_t(1) << 31), SGS_EINVAL,
-                    "%s: E=%lld, N=%lld exceed the int32 CSR", fn, (long long)E, (long long)cover->N);
-    }
-    if (E == 0) return SGS_OK;
-    SGS_REQUIRE(mask, SGS_EINVAL, "%s: null mask", fn);
-    SGS_REQUIRE(p || (mode == SGS_SAMPLE_LEARNED && !prior), SGS_EINVAL, "%s: p == NULL (uniform weights) needs mode LEARNED and no prior", fn);
-    SGS_REQUIRE(!sampled_edge_index || edge_index, SGS_EINVAL, "%s: edge_index required for sampled_edge_index", fn);
-    SGS_REQUIRE(!st_weights || (p && sampled_eid && stats && mode == SGS_SAMPLE_LEARNED), SGS_EINVAL,
-                "%s: st_weights needs p, sampled_eid, stats and mode LEARNED", fn);
-    SGS_REQUIRE(!dyn_edges_ptr(), SGS_EINVAL, "%s: not available under a dynamic edge count (sgs_dyn_edges_set)", fn);
-    const size_t ws_need = cover ? sgs_sample_topq_multi_cover_workspace_bytes(E, cover->N, D) : sgs_sample_topq_multi_workspace_bytes(E, D);
-    SGS_REQUIRE(ws && ws_bytes >= ws_need, SGS_EWORKSPACE, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, ws_need);
-    SGS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, SGS_EINVAL, "%s: workspace must be 256-B aligned", fn);
-
-    const int64_t nblk = cdiv(E, kChunk), cs = nblk + 1, ks = multi_key_stride(E);
-    Carver cv(ws);
-    uint32_t* keys = cv.take<uint32_t>(ks * D);
-    float* part = cv.take<float>(nblk + 1);
-    float* part2 = cv.take<float>(nblk + 1);
-    float* scal = cv.take<float>(4);                       // scal, hist and st adjacent: one zeroing launch on the large path
-    uint32_t* hist = cv.take<uint32_t>(3 * kBins * D);
-    SelectState* st = cv.take<SelectState>(D);
-    uint2* cnt = cv.take<uint2>(cs * D);
-    SelPart* sel = cv.take<SelPart>(2 * D);
-    uint32_t* mcnt = cover ? cv.take<uint32_t>(kCoverGrid * D) : nullptr;      // covering draws: forced edges per (draw, workgroup)
-    const unsigned Du = static_cast<unsigned>(D);
-    const dim3 blk(kThreads);
-    const float one_minus_c = static_cast<float>(1.0 - degree_bias_coef);
-    const float c = static_cast<float>(degree_bias_coef);
-
-    if (nblk <= kSmallBlocks && q > 0 && q < E) {
-        const uint32_t q32 = static_cast<uint32_t>(q);
-        const dim3 grid(static_cast<unsigned>(nblk), Du);
-        if (int rc = zero_async(hist, static_cast<size_t>(3 * kBins * D) * 4, stream)) return rc;
-        const dim3 kgrid(static_cast<unsigned>(nblk), static_cast<unsigned>(cdiv(D, kMultiG))), kblk(kKeyThreads);
-        if (mode == SGS_SAMPLE_LEARNED) {
-            hipLaunchKernelGGL(small_reduce_first<0>, dim3(static_cast<unsigned>(nblk)), blk, 0, stream, p, E, part, hist, nullptr);
-            hipLaunchKernelGGL(multi_keys_hist0<SGS_SAMPLE_LEARNED>, kgrid, kblk, 0, stream, p, prior, noise, seed, stream_id0, epoch_ptr(), E,
-                               static_cast<int>(D), one_minus_c, c, part, static_cast<const float*>(nullptr), nblk, scal, keys, ks, hist);
-        } else {
-            hipLaunchKernelGGL(small_reduce_first<1>, dim3(static_cast<unsigned>(nblk)), blk, 0, stream, p, E, part, hist, nullptr);
-            hipLaunchKernelGGL(small_reduce_sumexp, dim3(static_cast<unsigned>(nblk)), blk, 0, stream, p, E, part, nblk, part2, nullptr);
-            hipLaunchKernelGGL(multi_keys_hist0<SGS_SAMPLE_PRIOR>, kgrid, kblk, 0, stream, p, static_cast<const float*>(nullptr), noise, seed,
-                               stream_id0, epoch_ptr(), E, static_cast<int>(D), one_minus_c, c, part2, part, nblk, scal, keys, ks, hist);
-        }
-        if (cover) launch_multi_cover_rows(*cover, keys, ks, E, D, hist, 3 * kBins, mcnt, stream);
-        hipLaunchKernelGGL(multi_small_hist_next, grid, blk, 0, stream, keys, ks, E, kShift1, kMask1, kShift0, 1, q32, hist, sel);
-        hipLaunchKernelGGL(multi_small_hist_next, grid, blk, 0, stream, keys, ks, E, kShift2, kMask2, kShift1, 0, q32, hist, sel);
-        hipLaunchKernelGGL(multi_small_count, grid, blk, 0, stream, keys, ks, E, q32, hist, sel, st, cnt, cs, scal, stats);
-        hipLaunchKernelGGL(multi_small_compact, grid, blk, 0, stream, keys, ks, E, q, st, cnt, cs, p, edge_index, mask, sampled_eid,
-                           sampled_edge_index, static_cast<float*>(nullptr));
-        // (before multi_st_fwd: the straight-through weights read the threshold the single call reports, flag bit off)
-        if (cover) hipLaunchKernelGGL(multi_cover_finish, dim3(1, Du), blk, 0, stream, mcnt, int64_t(kCoverGrid), cover->grid, q, stats, cover->info);
-    } else {
-        if (int rc = zero_async(scal, static_cast<size_t>(reinterpret_cast<char*>(st + D) - reinterpret_cast<char*>(scal)), stream)) return rc;
-        const dim3 grid1(static_cast<unsigned>(nblk));
-        if (mode == SGS_SAMPLE_LEARNED) {
-            hipLaunchKernelGGL(reduce_partial<0>, grid1, blk, 0, stream, p, E, scal, part);
-            hipLaunchKernelGGL(reduce_final<0>, dim3(1), blk, 0, stream, part, nblk, scal);
-        } else {
-            hipLaunchKernelGGL(reduce_partial<1>, grid1, blk, 0, stream, p, E, scal, part);
-            hipLaunchKernelGGL(reduce_final<1>, dim3(1), blk, 0, stream, part, nblk, scal);
-            hipLaunchKernelGGL(reduce_partial<2>, grid1, blk, 0, stream, p, E, scal, part);
-            hipLaunchKernelGGL(reduce_final<2>, dim3(1), blk, 0, stream, part, nblk, scal);
-        }
-        if (q == 0 || q == E) {
-            hipLaunchKernelGGL(multi_select_all, dim3(static_cast<unsigned>(cdiv(E, 256)), Du), dim3(256), 0, stream, E, p, edge_index, mask,
-                               sampled_eid, sampled_edge_index, static_cast<float*>(nullptr), static_cast<uint8_t>(q == E ? 1 : 0));
-            // M does not depend on the keys or on the draw: one key-less cover_rows, its counts read by every draw's finishing workgroup
-            if (cover) launch_cover_rows(*cover, nullptr, E, nullptr, mcnt, nullptr, stream);
-        } else {
-            const dim3 hgrid(static_cast<unsigned>(nblk < kHistGrid ? nblk : kHistGrid), Du), grid(static_cast<unsigned>(nblk), Du), one(1, Du);
-            const uint32_t q32 = static_cast<uint32_t>(q);
-            if (mode == SGS_SAMPLE_LEARNED)
-                hipLaunchKernelGGL(multi_keys_hist0_large<SGS_SAMPLE_LEARNED>, hgrid, blk, 0, stream, p, prior, noise, seed, stream_id0, epoch_ptr(),
-                                   E, one_minus_c, c, scal, keys, ks, hist);
-            else
-                hipLaunchKernelGGL(multi_keys_hist0_large<SGS_SAMPLE_PRIOR>, hgrid, blk, 0, stream, p, static_cast<const float*>(nullptr), noise,
-                                   seed, stream_id0, epoch_ptr(), E, one_minus_c, c, scal, keys, ks, hist);
-            if (cover) launch_multi_cover_rows(*cover, keys, ks, E, D, hist, kBins, mcnt, stream);
-            hipLaunchKernelGGL(multi_select_digit, one, blk, 0, stream, hist, kShift0, 1, q32, st);
-            hipLaunchKernelGGL(multi_hist_next, hgrid, blk, 0, stream, keys, ks, E, kShift1, kMask1, kShift0, st, hist);
-            hipLaunchKernelGGL(multi_select_digit, one, blk, 0, stream, hist, kShift1, 0, q32, st);
-            hipLaunchKernelGGL(multi_hist_next, hgrid, blk, 0, stream, keys, ks, E, kShift2, kMask2, kShift1, st, hist);
-            hipLaunchKernelGGL(multi_select_digit, one, blk, 0, stream, hist, kShift2, 0, q32, st);
-            hipLaunchKernelGGL(multi_count_blocks, grid, blk, 0, stream, keys, ks, E, st, cnt, cs);
-            hipLaunchKernelGGL(multi_scan_blocks, one, blk, 0, stream, cnt, cs, nblk);
-            hipLaunchKernelGGL(multi_compact, grid, blk, 0, stream, keys, ks, E, q, st, cnt, cs, p, edge_index, mask, sampled_eid,
-                               sampled_edge_index, static_cast<float*>(nullptr));
-        }
-        if (stats) hipLaunchKernelGGL(multi_write_stats, dim3(1, Du), dim3(1), 0, stream, scal, st, stats);
-        if (cover)
-            hipLaunchKernelGGL(multi_cover_finish, dim3(1, Du), blk, 0, stream, mcnt, (q == 0 || q == E) ? int64_t(0) : int64_t(kCoverGrid),
-                               cover->grid, q, stats, cover->info);
-    }
-    if (st_weights && q > 0) {
-        const dim3 g(static_cast<unsigned>(cdiv(q, 256)), Du);
-        if (prior)
-            hipLaunchKernelGGL(multi_st_fwd<true>, g, dim3(256), 0, stream, p, prior, one_minus_c, c, stats, sampled_eid, q, st_weights);
-        else
-            hipLaunchKernelGGL(multi_st_fwd<false>, g, dim3(256), 0, stream, p, prior, one_minus_c, c, stats, sampled_eid, q, st_weights);
-    }
-    SGS_LAUNCH_OK();
-    return SGS_OK;
-}
-
-int sgs_sample_topq_multi(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
-                          uint64_t stream_id0, int64_t D, int64_t E, int64_t q, const int64_t* edge_index, uint8_t* mask, int64_t* sampled_eid,
-                          int64_t* sampled_edge_index, float* stats, float* st_weights, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    return sample_topq_multi_impl("sgs_sample_topq_multi", nullptr, mode, p, prior, degree_bias_coef, noise, seed, stream_id0, D, E, q, edge_index,
-                                  mask, sampled_eid, sampled_edge_index, stats, st_weights, ws, ws_bytes, stream_);
-}
-
-int sgs_sample_topq_multi_cover(int mode, const float* p, const float* prior, double degree_bias_coef, const float* noise, uint64_t seed,
-                                uint64_t stream_id0, int64_t D, int64_t E, int64_t q, const int64_t* edge_index, int64_t N,
-                                const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, uint8_t* mask, int64_t* sampled_eid,
-                                int64_t* sampled_edge_index, float* stats, float* st_weights, int32_t* cover_info, void* ws, size_t ws_bytes,
-                                sgs_stream_t stream_) {
-    const CoverArgs c = cover_args(N, E, in_ptr, in_src, in_eid, cover_info);
-    return sample_topq_multi_impl("sgs_sample_topq_multi_cover", &c, mode, p, prior, degree_bias_coef, noise, seed, stream_id0, D, E, q,
-                                  edge_index, mask, sampled_eid, sampled_edge_index, stats, st_weights, ws, ws_bytes, stream_);
 }
 
 }  // extern "C"

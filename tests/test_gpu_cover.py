@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import cover_ref as CR
+import sampler_ref as SR
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -145,6 +146,57 @@ def test_grid_through_the_c_abi(S, ops, E, q, N, kind):
     L = S._lib.lib()
     assert (E > 1024 * 2048) == (E == GRID[-1][0])                                        # only the last shape takes the large-E path
     assert L.sgs_sample_topq_cover_variant(N, E) in (4, 16, 64)
+
+
+# ------------------------------------------------------------------ a covering draw under sgs_dyn_edges_set
+@pytest.mark.parametrize("live", SR.DYN_LIVE)
+def test_dyn_edges_covering_draw_with_a_long_row(S, ops, live):
+    """Capacity 6151 edges over 1000 nodes (4 lanes per row: a row above 128 entries goes to the whole workgroup), live 4097 and 1.  The
+    call gets the capacity as E and the CSR of the live prefix in capacity-sized arrays, as a replayed step does: the pointers of the
+    rows past the live nodes are the live E, the entries past it are stale.  Node 7 has 700 in-edges or more in the capacity graph, at least
+    400 of them among the first 4097 edges.  Mask, edge ids, columns, M, threshold and ties against cover_ref of the live prefix, exactly, with
+    the keys replayed by sampler_ref (which the call's own keys must equal bit for bit)."""
+    cap, N, c = SR.DYN_CAPACITY, 1000, SR.C_COEF
+    q = 800 if live > 1 else 1
+    L = S._lib.lib()
+    assert L.sgs_sample_topq_cover_variant(N, cap) == 4
+    p, prior, noise, _ = SR.make_inputs(cap, "learned_prior", 71 + live)
+    g = np.random.default_rng(73 + live)
+    dst = g.integers(0, N, cap)
+    hub = np.concatenate([g.permutation(4097)[:400], 4097 + g.permutation(cap - 4097)[:300]])
+    dst[hub] = 7
+    src = np.where(g.random(cap) < 0.1, dst, g.integers(0, N, cap))
+    ei = np.stack([src, dst]).astype(np.int64)
+    if live > 1:
+        assert int((dst[:live] == 7).sum()) >= 400 > 32 * 4
+    n_live = int(dst[:live].max()) + 1                                                # the live partition's nodes
+    order = np.argsort(dst[:live], kind="stable")
+    in_ptr = np.full(N + 1, live, dtype=np.int32)
+    in_ptr[:n_live + 1] = np.concatenate([[0], np.cumsum(np.bincount(dst[:live], minlength=n_live))])
+    in_src, in_eid = g.integers(0, N, cap).astype(np.int32), g.integers(0, cap, cap).astype(np.int32)      # stale past the live E
+    in_src[:live], in_eid[:live] = src[:live][order], order
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    csr = argparse.Namespace(in_ptr=d(in_ptr), in_src=d(in_src), in_eid=d(in_eid))
+    word = torch.tensor([live], dtype=torch.int64, device=DEV)
+    try:
+        assert L.sgs_dyn_edges_set(word.data_ptr()) == 0
+        r = _abi_draw(S, ops.SAMPLE_LEARNED, d(p), d(prior), c, d(noise), 0, 0, cap, q, d(ei), N, csr)
+        torch.cuda.synchronize()
+    finally:
+        assert L.sgs_dyn_edges_set(None) == 0
+    Z, _ = SR.tree_sum(p[:live])
+    kbits = SR.keys(SR.LEARNED, p[:live], prior[:live], c, noise[:live], Z, n=live)
+    assert np.array_equal(r.keys.cpu().numpy()[:live].view(np.uint32), kbits)
+    ref = CR.cover_ref(kbits.view(np.float32), ei[:, :live], N, q)
+    assert np.array_equal(r.mask.cpu().numpy()[:live], ref["mask"])
+    assert np.array_equal(r.eid.cpu().numpy(), ref["eid"]) and np.array_equal(r.edge_index.cpu().numpy(), ei[:, ref["eid"]])
+    assert np.array_equal(r.p.cpu().numpy().view(np.uint32), p[ref["eid"]].view(np.uint32))
+    assert r.cover_info.tolist() == [ref["M"], min(ref["M"], q)] == [ref["M"], ref["n_forced_selected"]]
+    st = r.stats.cpu()
+    assert int(st[2:3].view(torch.int32)) == ref["threshold_bits"] and int(st[3]) == ref["ties"]
+    assert st[:1].numpy().view(np.uint32)[0] == np.array([Z], dtype=np.float32).view(np.uint32)[0]
+    if live > 1:
+        assert ref["forced"][dst[:live] == 7].sum() == 1                              # the long row forced its one best edge
 
 
 # ------------------------------------------------------------------ degree classes

@@ -15,7 +15,9 @@ untouched.
 Sections: A the phase API with one shard (= the general path's kernels at any E), B with R shards emulated in one process (the host does
 the collectives) against the reference AND bit for bit against one sgs_sample_topq call on the small path, C sgs_sample_topq across the
 path boundary (1024 / 1025 / 1026 / 2050 chunks; the last is the only size at which the histogram grid strides), D the byte-wise
-branches, E q == 0 / q == E and the identity of Z across the paths, F sgs_dyn_edges_set, G the straight-through weights.
+branches, E q == 0 / q == E and the identity of Z across the paths, F sgs_dyn_edges_set, G the straight-through weights, H every entry
+that takes a workspace (single, covering, batched, batched covering, consensus) with a buffer of exactly the reported size between red
+zones, against sampler_ref / cover_ref / consensus_ref, and refused with one byte less.
 
 Largest error / bound per quantity measured on an MI355X over all cases of this file (plain and with SGS_POISON=1: the same figures; the
 module prints them as WORST lines): Z against the float64 sum 0.05 of the tree bound, prior-mode Z 0.11, prior-mode keys 0.06 of the
@@ -630,3 +632,111 @@ def test_st_weights_bwd_dyn_edges(lib):
         _st_run(lib, p, prior, eid, gw, Z, "G_dyn", live=live)
     finally:
         assert L.sgs_dyn_edges_set(None) == 0
+
+
+# ------------------------------------------------------------------ H. every entry that takes a workspace, at exactly the reported size
+WS_ENTRIES = ("topq", "cover", "multi", "multi_cover", "consensus")
+WS_CASES = ((2049, 700), (1025 * R.CHUNK + 1, 400_000), (2049, 0), (2049, 2049))     # two chunks (small path), the large path, nothing, everything
+WS_D, WS_N = 3, 300
+
+
+@functools.lru_cache(maxsize=2)
+def _ws_inputs(E):
+    """What the five entries read at one E (shared, never modified): scores, a noise row per draw, a graph over WS_N nodes (a tenth of
+    its edges self-loops) with its destination CSR, consensus counts and scores; plus the key bits of every draw from the reference."""
+    import consensus_ref as CoR
+    p, prior, _, _ = R.make_inputs(E, "learned_prior", 41 + E)
+    g = np.random.default_rng(43 + E)
+    noise = np.clip(g.standard_exponential((WS_D, E), dtype=F32), F32(2.0 ** -20), F32(32.0)).astype(F32)
+    dst = g.integers(0, WS_N, E)
+    src = np.where(g.random(E) < 0.1, dst, g.integers(0, WS_N, E))
+    ei = np.stack([src, dst]).astype(np.int64)
+    order = np.argsort(dst, kind="stable")
+    in_ptr = np.concatenate([[0], np.cumsum(np.bincount(dst, minlength=WS_N))]).astype(np.int32)
+    count, score = CoR.make_counts_scores(E, 11, 47 + E)
+    Z, _ = R.tree_sum(p)
+    kbits = [R.keys(R.LEARNED, p, prior, C, noise[d], Z, n=E) for d in range(WS_D)]
+    dev = SimpleNamespace(p=_d(p), prior=_d(prior), noise=_d(noise), ei=_d(ei), in_ptr=_d(in_ptr), in_src=_d(src[order].astype(np.int32)),
+                          in_eid=_d(order.astype(np.int32)), count=_d(count), score=_d(score))
+    return SimpleNamespace(E=E, p=p, ei=ei, count=count, score=score, Z=Z, kbits=kbits, dev=dev, CoR=CoR)
+
+
+def _ws_call(lib, entry, c, q, short):
+    """One call of `entry` with a workspace of (reported size - short) bytes between red zones -> (rc, outputs, D).  Every buffer is
+    read back through Zoned.get, which asserts its zones."""
+    L, stream = lib
+    E, d = c.E, c.dev
+    D = WS_D if entry.startswith("multi") else 1
+    nb = {"topq": lambda: L.sgs_sample_topq_workspace_bytes(E), "cover": lambda: L.sgs_sample_topq_cover_workspace_bytes(E, WS_N),
+          "multi": lambda: L.sgs_sample_topq_multi_workspace_bytes(E, D), "multi_cover": lambda: L.sgs_sample_topq_multi_cover_workspace_bytes(E, WS_N, D),
+          "consensus": lambda: L.sgs_consensus_select_workspace_bytes(E)}[entry]()
+    assert nb % 256 == 0
+    ws = Zoned(nb, torch.uint8, 0xFF, shift=192)                                         # 64 + 192 zone bytes: the payload is 256-B aligned
+    assert ws.ptr % 256 == 0
+    z = dict(mask=Zoned(D * E, torch.uint8, 0xAB), eid=Zoned(D * q, torch.int64, -9), sei=Zoned(D * 2 * q, torch.int64, -9),
+             sp=Zoned(q, torch.float32, -9.0), stats=Zoned(4 * D, torch.float32, -9.0), info=Zoned(2 * D, torch.int32, -7),
+             cnt=Zoned(q, torch.int32, -9), keys=Zoned(E, torch.int32, -9))
+    P = {k: v.ptr for k, v in z.items()}
+    race = (R.LEARNED, _p(d.p), _p(d.prior), C, _p(d.noise), 0, 0)
+    csr = (WS_N, _p(d.in_ptr), _p(d.in_src), _p(d.in_eid))
+    tail = (ws.ptr, nb - short, stream())
+    if entry == "topq":
+        rc = L.sgs_sample_topq(*race, E, q, _p(d.ei), P["mask"], P["eid"], P["sei"], P["sp"], P["stats"], None, *tail)
+    elif entry == "cover":
+        rc = L.sgs_sample_topq_cover(*race, E, q, _p(d.ei), *csr, P["mask"], P["eid"], P["sei"], P["sp"], P["stats"], None, P["info"], *tail)
+    elif entry == "multi":
+        rc = L.sgs_sample_topq_multi(*race, D, E, q, _p(d.ei), P["mask"], P["eid"], P["sei"], P["stats"], None, *tail)
+    elif entry == "multi_cover":
+        rc = L.sgs_sample_topq_multi_cover(*race, D, E, q, _p(d.ei), *csr, P["mask"], P["eid"], P["sei"], P["stats"], None, P["info"], *tail)
+    else:
+        rc = L.sgs_consensus_select(_p(d.count), _p(d.score), E, q, _p(d.ei), P["mask"], P["eid"], P["sei"], P["cnt"], P["sp"], P["keys"], *tail)
+    torch.cuda.synchronize()
+    out = {k: v.get() for k, v in z.items()}
+    out["ws"] = ws.get()
+    return rc, out, D
+
+
+@pytest.mark.parametrize("E,q", WS_CASES)
+@pytest.mark.parametrize("entry", WS_ENTRIES)
+def test_exact_size_workspace_between_guard_zones(lib, entry, E, q):
+    import cover_ref as CR
+    L, _ = lib
+    c = _ws_inputs(E)
+    fills = dict(mask=0xAB, eid=-9, sei=-9, sp=-9.0, stats=-9.0, info=-7, cnt=-9, keys=-9, ws=0xFF)
+    rc, out, D = _ws_call(lib, entry, c, q, short=1)                                     # one byte short: refused, nothing written
+    assert rc == -2 and b"workspace too small" in L.sgs_last_error(), (rc, L.sgs_last_error())
+    for k, v in out.items():
+        assert bool((v == fills[k]).all()), (entry, k, "written by a refused call")
+    rc, out, D = _ws_call(lib, entry, c, q, short=0)
+    assert rc == 0, L.sgs_last_error()
+    mask, eid, sei = out["mask"].reshape(D, E), out["eid"].reshape(D, q), out["sei"].reshape(D, 2, q)
+    stats, info = out["stats"].reshape(D, 4), out["info"].reshape(D, 2)
+    if entry == "consensus":
+        ref = c.CoR.select_ref(c.count, c.score, q, c.ei)
+        assert np.array_equal(mask[0], ref["mask"]) and np.array_equal(eid[0], ref["eid"]) and np.array_equal(sei[0], ref["edge_index"])
+        assert np.array_equal(out["cnt"], ref["count"]) and np.array_equal(_bits(out["sp"]), _bits(ref["p"]))
+        assert np.array_equal(out["keys"].view(U32), ref["keys"])
+        return
+    covering = entry.endswith("cover")
+    for d in range(D):
+        tag = (entry, E, q, d)
+        if covering:
+            ref = CR.cover_ref(c.kbits[d].view(F32), c.ei, WS_N, q)
+            want_mask, want_eid, T, ties = ref["mask"].astype(np.uint8), ref["eid"], ref["threshold_bits"], ref["ties"]
+            assert info[d].tolist() == [ref["M"], min(ref["M"], q)] == [ref["M"], ref["n_forced_selected"]], tag
+        else:
+            sel = R.select(c.kbits[d], q) if 0 < q < E else None
+            want_mask = sel["mask"] if sel else np.full(E, q == E, dtype=np.uint8)
+            want_eid = sel["eid"] if sel else np.arange(q, dtype=np.int64)
+            T, ties = (sel["T"], sel["ties"]) if sel else (0, 0)
+            assert bool((info[d] == -7).all()), tag
+        assert np.array_equal(mask[d], want_mask), tag
+        assert np.array_equal(eid[d], want_eid) and np.array_equal(sei[d], c.ei[:, want_eid]), tag
+        if D == 1:
+            assert np.array_equal(_bits(out["sp"]), _bits(c.p[want_eid])), tag
+        assert _bits(stats[d, :1])[0] == _bits(np.array([c.Z]))[0] and stats[d, 1] == 0.0, tag
+        if 0 < q < E:
+            assert _bits(stats[d, 2:3])[0] == T and float(stats[d, 3]) == float(ties), tag
+        else:
+            assert np.array_equal(_bits(stats[d, 2:]), np.zeros(2, dtype=U32)), tag     # no threshold, no ties
+

@@ -189,6 +189,38 @@ def test_tie_quotas_hand_written_and_the_product_helper():
         assert got == R.tie_quotas(k, counts) and sum(got) == k and all(0 <= t <= b for t, (_, b) in zip(got, counts))
 
 
+# ------------------------------------------------------------------ the one workspace layout (the library loads without a device)
+WS_E = (0, 1, 2047, 2048, 2049, 1025 * 2048 + 1)
+WS_D = (1, 2, 11)
+
+
+def test_workspace_sizes_come_from_one_layout():
+    import sgs_gnn_amd
+    L = sgs_gnn_amd._lib.lib()
+    N = 1013                                                                            # the node count does not enter a size
+    sizes = {
+        "topq": lambda E, D: L.sgs_sample_topq_workspace_bytes(E),
+        "cover": lambda E, D: L.sgs_sample_topq_cover_workspace_bytes(E, N),
+        "multi": lambda E, D: L.sgs_sample_topq_multi_workspace_bytes(E, D),
+        "multi_cover": lambda E, D: L.sgs_sample_topq_multi_cover_workspace_bytes(E, N, D),
+        "consensus": lambda E, D: L.sgs_consensus_select_workspace_bytes(E),
+        "shard": lambda E, D: L.sgs_sampler_shard_workspace_bytes(E),
+    }
+    for name, f in sizes.items():
+        tab = np.array([[f(E, D) for D in WS_D] for E in WS_E], dtype=np.int64)
+        assert (tab % 256 == 0).all() and (tab > 0).all(), name
+        assert (np.diff(tab, axis=0) >= 0).all() and (np.diff(tab, axis=1) >= 0).all(), name   # non-decreasing in E and in D
+        assert f(-5, 1) == f(0, 1) and f(2049, 0) == f(2049, 1) == f(2049, -3), name            # E < 0 is 0, D < 1 is 1
+    for D in WS_D:
+        extra = {sizes["multi_cover"](E, D) - sizes["multi"](E, D) for E in WS_E}
+        assert len(extra) == 1 and extra.pop() >= 4 * 1024 * D, D                       # per-workgroup counts: no function of E
+    assert len({sizes["cover"](E, 1) - sizes["topq"](E, 1) for E in WS_E}) == 1
+    for E in WS_E:
+        assert sizes["multi"](E, 1) == sizes["topq"](E, 1) and sizes["multi_cover"](E, 1) == sizes["cover"](E, 1)
+        assert sizes["consensus"](E, 1) >= sizes["topq"](E, 1) + 8 * E
+        assert sizes["topq"](E, 1) >= 4 * E and sizes["multi"](E, 11) >= 11 * 4 * E     # the key rows
+
+
 # ------------------------------------------------------------------ straight-through weights
 @pytest.mark.parametrize("with_prior", [False, True])
 def test_st_closed_form_against_autograd_of_the_oracle(with_prior):

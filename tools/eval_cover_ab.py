@@ -20,7 +20,7 @@ reported and the acceptance compares the engine's spread with the union of the t
 --kernels: per shape one representative partition (s3: the partition nearest 351 000 edges; s4: partition 0), q = 100 000, no timing
 of its own: per group size G in {1, 2, 4} it issues 20 calls of ops.sample_topq_multi(..., cover=) with D = 11, then 20 x 11 single
 ops.sample_topq(..., cover=) calls, so that `rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/eval_cover_ab.py
---kernels --shapes s3` lists multi_cover_rows<LPR, G> (one dispatch per call) beside cover_rows<LPR> (eleven per round of singles).
+--kernels --shapes s3` lists cover_rows_group<LPR, G> (one dispatch per call) beside cover_rows<LPR> (eleven per round of singles).
 --trace-csv s3=DIR,s4=DIR --out FILE.csv turns such traces (one per shape) into the table of the forced-edge and finishing kernels."""
 import argparse
 import json
@@ -144,7 +144,7 @@ def trace_csv(spec, out):
         by = {}
         for fn in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
             for r in csv.DictReader(open(fn)):
-                m = re.search(r"(multi_cover_rows|multi_cover_finish|cover_rows|cover_finish|multi_keys_hist0|small_keys_hist0)(<[0-9, ]+>)?", r["Kernel_Name"])
+                m = re.search(r"(cover_rows_group|cover_rows|cover_finish|multi_keys_hist0|small_keys_hist0)(<[0-9, ]+>)?", r["Kernel_Name"])
                 if not m:
                     continue
                 name = m.group(1) + (m.group(2) or "").replace(" ", "")
