@@ -82,6 +82,42 @@ int sgs_stage_segments(const int64_t* desc_host, int64_t n_segments, int64_t* di
                        sgs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Multi-partition batches: the collate of ClusterLoader(cluster_data, batch_size=k) (main.py:63-65 uses batch_size=1) for a graph
+ * that is resident on the device -- the union of k partitions with the cut edges between them restored.
+ *
+ * The whole graph is held as a row-sorted CSR whose nodes are grouped by partition: full_ptr [N+1] int64, full_col [E] int64,
+ * full_prob [E] (may be NULL).  Partition p owns the node range [node_ptr[p], node_ptr[p+1]).  A group is k ranges in ASCENDING
+ * order: ranges_host [k][2] int64 = {lo, hi}, HOST memory, read during the call and passed to the kernels by value (as
+ * sgs_stage_segments does with its descriptors): no allocation, no synchronisation and no device-side table that would have to be
+ * refilled per batch, so the call can be captured.  k <= sgs_cluster_collate_max_parts() (32).
+ *
+ * Batch node r is the r-th node of the concatenated ranges (n_b of them).  Every edge (s, d) of the whole graph with both endpoints
+ * in the ranges is emitted with local ids, ordered by (local src, local dst): relabelling is monotone because the group is ascending,
+ * so a row's kept columns keep their order.  Outputs: edge_index_out [2, E_b] int64; prob_out [E_b] = full_prob gathered (bit for
+ * bit; may be NULL); eid_out [E_b] int64 = position of each emitted edge in full_col (may be NULL).  Per-node BYTE attributes (the
+ * boolean masks: their per-partition slices are not whole aligned words, so they cannot go through sgs_stage_segments like x and y):
+ * attr_in [n_attr][N] -> attr_out [n_attr][n_b], n_attr <= 4, may be 0.
+ *
+ * E_b is the HOST's edge count of the batch (the caller knows it without a read-back from a P x P block count table;
+ * sgs_cluster_collate_count gives it otherwise: it runs the count and the scan only and writes the total to *total_dev).  If
+ * mismatch_dev (device int32, may be NULL) is given and the device count differs from E_b, the word is set to 1 (it is never
+ * cleared here); nothing is written outside [0, E_b) of any output either way.
+ *
+ * Launches: count per row (one wave per row; also the byte attributes), scan, fill.  Rows longer than 1024 columns are walked by
+ * the 16 waves of their workgroup together.  Integer work and gathers only; no atomics.  ws: 8-byte aligned.
+ * Errors (SGS_EINVAL, message in sgs_last_error): k < 1 or k > cap, ranges unsorted / overlapping / not n_b nodes
+ * in total, n_b or E_b >= 2^31, workspace too small.
+ * ---------------------------------------------------------------------------------- */
+int sgs_cluster_collate_max_parts(void);
+size_t sgs_cluster_collate_workspace_bytes(int64_t n_b);
+int sgs_cluster_collate_count(const int64_t* full_ptr, const int64_t* full_col, const int64_t* ranges_host, int64_t k, int64_t n_b,
+                              int64_t* total_dev, void* ws, size_t ws_bytes, sgs_stream_t stream);
+int sgs_cluster_collate(const int64_t* full_ptr, const int64_t* full_col, const float* full_prob, const int64_t* ranges_host, int64_t k,
+                        int64_t n_b, int64_t E_b, int64_t* edge_index_out, float* prob_out, int64_t* eid_out, const uint8_t* attr_in,
+                        uint8_t* attr_out, int64_t n_attr, int64_t N, int32_t* mismatch_dev, void* ws, size_t ws_bytes,
+                        sgs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * K0 / K2 / K3: fused exponential-race top-q edge sampler + stable compaction.
  *
  * Replaces, in one call:

@@ -108,8 +108,13 @@ class ResidentPartitions:
     from the full graph's prior (`prior="global"`, what the reference does: add_degree runs before partitioning,
     datasets.py:141-156) or recomputed on the partition (`prior="local"`)."""
 
+    CUT_TABLE_MAX_PARTS = 2048       # the P x P block edge-count table is kept up to here (32 MiB of int64 on the host)
+
     def __init__(self, x, edge_index, y, train_mask, val_mask, test_mask, part_id, num_parts=None, device="cuda:0", prior="global",
-                 prob=None, shuffle=False, seed=0):
+                 prob=None, shuffle=False, seed=0, *, keep_cut_edges=False):
+        """`keep_cut_edges=True` additionally keeps the WHOLE graph in the permuted node order (a row-sorted CSR `full_ptr` /
+        `full_col` over all E edges, `full_prob`, the node attributes) and the host-side tables `ResidentClusterLoader` needs to
+        build batches of several partitions with the edges between them restored."""
         dev = torch.device(device)
         part_id = part_id.to(dev).to(torch.int64)
         N = x.shape[0]
@@ -168,6 +173,39 @@ class ResidentPartitions:
                                       node_ids=perm[a:b]))
         self.shuffle = shuffle
         self._gen = torch.Generator().manual_seed(seed)
+        self.keep_cut_edges = bool(keep_cut_edges)
+        if keep_cut_edges:
+            fs, fd = new_id[ei[0]], new_id[ei[1]]
+            forder = torch.argsort(fs * N + fd)
+            fptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+            fptr[1:] = torch.cumsum(torch.bincount(fs, minlength=N), 0)
+            self.full_ptr, self.full_col = fptr, fd[forder].contiguous()
+            self.full_prob = prob[forder].contiguous() if prob is not None else None      # None: prior="local", recomputed per batch
+            self.x_all, self.y_all = xs.contiguous(), ys.contiguous()
+            self.masks_all = torch.stack([tm, vm, sm]).to(torch.uint8).contiguous()       # [3, N] bytes: train / val / test
+            self.num_nodes, self.num_edges = N, E
+            self.node_ptr_host, self.edge_ptr_host = nptr_h, eptr_h
+            # E_b of any group without a read-back: edges between every pair of partitions, counted once (one read-back here)
+            self.size_path = "table" if P <= self.CUT_TABLE_MAX_PARTS else "readback"
+            self.block_edges = torch.bincount(ps * P + pd, minlength=P * P).view(P, P).cpu() if self.size_path == "table" else None
+            self.collate_mismatch = torch.zeros(1, dtype=torch.int32, device=dev)         # set by the device collate if its count != E_b
+
+    def batch_sizes(self, group):
+        """(n_b, E_b) of the union of the partitions in `group` from host tables alone; E_b is None when P is above the block
+        table's limit (`size_path == "readback"`: the collate counts on the device and reads 8 bytes back)."""
+        if not self.keep_cut_edges:
+            raise ValueError("ResidentPartitions was built without keep_cut_edges=True: the edges between partitions are gone")
+        n_b = sum(self.node_ptr_host[p + 1] - self.node_ptr_host[p] for p in group)
+        E_b = None
+        if self.block_edges is not None:
+            g = torch.as_tensor(list(group), dtype=torch.int64)
+            E_b = int(self.block_edges[g][:, g].sum())
+        if n_b >= 2 ** 31 or (E_b is not None and E_b >= 2 ** 31):
+            raise ValueError(f"a batch of {n_b} nodes / {E_b} edges does not fit the int32 graph kernels (limit 2^31)")
+        return n_b, E_b
+
+    def loader(self, batch_size, regroup="fixed", shuffle=False, seed=0) -> "ResidentClusterLoader":
+        return ResidentClusterLoader(self, batch_size, regroup=regroup, shuffle=shuffle, seed=seed)
 
     def __len__(self):
         return self.num_parts
@@ -206,9 +244,12 @@ class ResidentPartitions:
         return path
 
     @classmethod
-    def load(cls, save_dir: str, num_parts: int, device="cuda:0", shuffle=False, seed=0) -> "ResidentPartitions":
+    def load(cls, save_dir: str, num_parts: int, device="cuda:0", shuffle=False, seed=0, *, keep_cut_edges=False) -> "ResidentPartitions":
         """Rebuild the resident partition tables from `save()`'s file: memory-mapped read, one host-to-device copy per tensor,
         then per-partition views (no re-partitioning, no prior recomputation)."""
+        if keep_cut_edges:
+            raise ValueError(f"the {cls.FORMAT} cache holds intra-partition edges only: keep_cut_edges=True needs the whole graph, "
+                             "build ResidentPartitions(..., keep_cut_edges=True) from it instead")
         from safetensors import safe_open
         dev = torch.device(device)
         path = cls.cache_path(save_dir, num_parts)
@@ -232,9 +273,154 @@ class ResidentPartitions:
                                       val_mask=vm[a:b], test_mask=sm[a:b], prob=t["prob"][ea:eb], part=p, node_ids=t["perm"][a:b]))
         self.shuffle = shuffle
         self._gen = torch.Generator().manual_seed(seed)
+        self.keep_cut_edges = False
         return self
 
     def __iter__(self):
         order = torch.randperm(self.num_parts, generator=self._gen).tolist() if self.shuffle else range(self.num_parts)
         for i in order:
             yield self.batches[i]
+
+
+# ---------------------------------------------------------------------------------------------------- multi-partition batches
+def collate_torch(parts: ResidentPartitions, group) -> Batch:
+    """The union of the partitions in `group` (ascending) with the cut edges between them restored, as a plain torch composition
+    over `parts`' whole-graph CSR.  It defines the batch (nodes = the partitions' node lists concatenated, edges relabelled and
+    ordered by (local src, local dst), `prob` gathered or -- prior="local" -- recomputed) and is what runs on a CPU device; on a HIP
+    device the loader calls `ops.cluster_collate` instead and this composition only serves as the yardstick of
+    tools/cluster_batch_probe.py."""
+    group = _check_group(parts, group)
+    dev = parts.full_ptr.device
+    nptr = parts.node_ptr_host
+    rows = torch.cat([torch.arange(nptr[p], nptr[p + 1], device=dev) for p in group])
+    n_b = rows.numel()
+    loc = torch.full((parts.num_nodes,), -1, dtype=torch.int64, device=dev)
+    loc[rows] = torch.arange(n_b, device=dev)
+    beg = parts.full_ptr[rows]
+    deg = parts.full_ptr[rows + 1] - beg
+    src = torch.repeat_interleave(torch.arange(n_b, device=dev), deg)
+    eid = torch.repeat_interleave(beg - (torch.cumsum(deg, 0) - deg), deg) + torch.arange(int(src.numel()), device=dev)
+    dst = loc[parts.full_col[eid]]
+    keep = dst >= 0
+    ei = torch.stack([src[keep], dst[keep]]).contiguous()           # rows ascending; a row's columns keep their order (monotone relabelling)
+    if parts.full_prob is not None:
+        prob = parts.full_prob[eid[keep]]
+    elif dev.type == "cuda" and ei.shape[1] > 0:
+        from . import ops
+        prob = ops.degree_prior(ei, n_b)
+    else:
+        prob = degree_prior(ei, n_b)
+    m = parts.masks_all[:, rows].bool()
+    return Batch(x=parts.x_all[rows], edge_index=ei, y=parts.y_all[rows], train_mask=m[0].contiguous(), val_mask=m[1].contiguous(),
+                 test_mask=m[2].contiguous(), prob=prob, node_ids=parts.perm[rows], parts=group,
+                 restored_edges=int(ei.shape[1]) - _intra_edges(parts, group))
+
+
+def _check_group(parts, group):
+    if not getattr(parts, "keep_cut_edges", False):
+        raise ValueError("ResidentPartitions was built without keep_cut_edges=True: the edges between partitions are gone")
+    g = tuple(sorted(int(p) for p in group))
+    if len(g) < 1 or len(set(g)) != len(g) or g[0] < 0 or g[-1] >= parts.num_parts:
+        raise ValueError(f"a group is a non-empty set of distinct partition ids below {parts.num_parts}, got {tuple(group)}")
+    return g
+
+
+def _intra_edges(parts, group) -> int:
+    return sum(parts.edge_ptr_host[p + 1] - parts.edge_ptr_host[p] for p in group)
+
+
+class ResidentClusterLoader:
+    """`ClusterLoader(cluster_data, batch_size=k, shuffle=...)` over a resident graph: every step trains on the union of k partitions
+    with the edges between those k partitions put back (Cluster-GCN's stochastic multiple partitions).  Groups are the consecutive
+    chunks of k of `randperm(P)` (or of `range(P)`), each taken in ascending partition id.
+
+    regroup="fixed": the order is drawn once; the merged batches are built once and stay resident in `self.batches`, so everything
+    downstream (captured replay included) sees ordinary resident batches.  regroup="epoch": a fresh order at every `__iter__`, a fresh
+    batch every step -- on a HIP device each one is built by `ops.cluster_collate` (four launches), never by a torch composition.
+    `dropped_edges`: edges of the graph that no batch holds (fixed), or that the last completed epoch did not see (epoch)."""
+
+    def __init__(self, parts: ResidentPartitions, batch_size: int, regroup: str = "fixed", shuffle: bool = False, seed: int = 0):
+        if not getattr(parts, "keep_cut_edges", False):
+            raise ValueError("ResidentClusterLoader needs ResidentPartitions(..., keep_cut_edges=True)")
+        if regroup not in ("fixed", "epoch"):
+            raise ValueError(f"regroup must be 'fixed' or 'epoch', got {regroup!r}")
+        k = int(batch_size)
+        if k < 1:
+            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        self._on_device = parts.full_ptr.is_cuda
+        if self._on_device:
+            from . import ops
+            cap = ops.cluster_collate_max_parts()
+            if k > cap:
+                raise ValueError(f"batch_size {k} is above the device collate's limit of {cap} partitions per batch")
+        self.parts, self.batch_size, self.regroup, self.shuffle = parts, k, regroup, bool(shuffle)
+        self.size_path = parts.size_path
+        self._gen = torch.Generator().manual_seed(seed)
+        self.groups, self.batches, self.dropped_edges = None, None, None
+        if regroup == "fixed":
+            self.groups = self._draw()
+            self.batches = [self._collate(g) for g in self.groups]
+            self.dropped_edges = parts.num_edges - sum(int(b.edge_index.shape[1]) for b in self.batches)
+
+    def _draw(self):
+        P, k = self.parts.num_parts, self.batch_size
+        order = torch.randperm(P, generator=self._gen).tolist() if self.shuffle else list(range(P))
+        return [tuple(sorted(order[i:i + k])) for i in range(0, P, k)]
+
+    def _collate(self, group) -> Batch:
+        if self._on_device:
+            from . import ops
+            return ops.cluster_collate(self.parts, group)
+        return collate_torch(self.parts, group)
+
+    def __len__(self):
+        return -(-self.parts.num_parts // self.batch_size)
+
+    def __iter__(self):
+        if self.regroup == "fixed":
+            yield from self.batches
+            return
+        self.groups = self._draw()
+        seen = 0
+        for g in self.groups:
+            b = self._collate(g)
+            seen += int(b.edge_index.shape[1])
+            yield b
+        self.dropped_edges = self.parts.num_edges - seen
+
+
+def synthetic_partitioned_graph(num_parts: int, n_per_part: int, e_intra, cut_frac: float, nfeat: int, ncls: int, seed: int, device="cpu"):
+    """-> (Batch, part_id): `num_parts` graphs of `synthetic_graph(n_per_part, e_intra, ...)` (`e_intra`: one stored-edge target or one per
+    partition) on disjoint node ranges, plus cut_frac * (undirected intra-partition edges) further undirected edges between uniformly drawn
+    nodes of DIFFERENT partitions (drawn until that many distinct pairs exist), coalesced, row-sorted, stored both ways, with the degree
+    prior of the whole graph.  Node ids are then shuffled, so a partition is not a contiguous id range.  `reddit_partition_stream` makes
+    independent partitions with no edge between them; this is the same material with a cut structure -- a synthetic one."""
+    dev = torch.device(device)
+    P, n = int(num_parts), int(n_per_part)
+    N = P * n
+    targets = [int(e_intra)] * P if not hasattr(e_intra, "__len__") else [int(e) for e in e_intra]
+    if len(targets) != P:
+        raise ValueError("e_intra must be one number or one per partition")
+    g = torch.Generator(device=dev).manual_seed(seed)
+    kw = dict(generator=g, device=dev)
+    subs = [synthetic_graph(n, targets[p], nfeat, ncls, seed * 1000 + p, device=dev) for p in range(P)]
+    intra = torch.cat([(b.edge_index[0] + p * n) * N + (b.edge_index[1] + p * n) for p, b in enumerate(subs)])
+    m_cut = int(cut_frac * (intra.numel() // 2)) if P > 1 else 0
+    cut = torch.zeros(0, dtype=torch.int64, device=dev)
+    while cut.numel() < m_cut:
+        need = int((m_cut - cut.numel()) * 1.3) + 16
+        a, b = torch.randint(0, N, (need,), **kw), torch.randint(0, N, (need,), **kw)
+        ok = (a // n) != (b // n)
+        lo, hi = torch.minimum(a[ok], b[ok]), torch.maximum(a[ok], b[ok])
+        cut = torch.unique(torch.cat([cut, lo * N + hi]))
+    cut = cut[torch.randperm(cut.numel(), **kw)[:m_cut]]
+    lo, hi = cut // N, cut % N
+    keys = torch.cat([intra, lo * N + hi, hi * N + lo])
+    sigma = torch.randperm(N, **kw)                                   # contiguous id -> shuffled id
+    keys = torch.unique(sigma[keys // N] * N + sigma[keys % N])       # sorted -> row-sorted, coalesced
+    ei = torch.stack([keys // N, keys % N])
+    cat = lambda k: torch.cat([getattr(b, k) for b in subs])          # noqa: E731
+    scat = lambda t: torch.empty_like(t).index_copy_(0, sigma, t)     # noqa: E731
+    part_id = scat(torch.arange(N, device=dev) // n)
+    return Batch(x=scat(cat("x")), edge_index=ei, y=scat(cat("y")), train_mask=scat(cat("train_mask")), val_mask=scat(cat("val_mask")),
+                 test_mask=scat(cat("test_mask")), prob=degree_prior(ei, N)), part_id

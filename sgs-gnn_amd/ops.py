@@ -3079,3 +3079,81 @@ def cheb_conv(x, Wcat, bias, nm: Norm, K: int, act=ACT_NONE, p=0.0, seed=0, site
     if nm.what_loop is not None or nm.dis is None:
         raise RuntimeError("cheb_conv: `nm` must come from cheb_norm")
     return _ChebConv.apply(x.contiguous(), Wcat.contiguous(), bias, nm.handle, nm, K, act, float(p), int(seed), int(site))
+
+
+# ------------------------------------------------------------------ multi-partition batches (csrc/cluster.hip)
+def cluster_collate_max_parts() -> int:
+    return int(_lib.lib().sgs_cluster_collate_max_parts())
+
+
+def _stage_spans(spans) -> int:
+    """(src address, dst address, bytes) spans -> sgs_stage_segments, as few launches as its segment limit allows.  Returns the launches."""
+    L = _lib.lib()
+    spans = [s for s in spans if s[2] > 0]
+    cap = int(L.sgs_stage_max_segments())
+    for i in range(0, len(spans), cap):
+        words = []
+        for s, d, nb in spans[i:i + cap]:
+            words += [s, d, nb, nb, 0]
+        arr = (ctypes.c_int64 * len(words))(*words)
+        _lib.check(L.sgs_stage_segments(arr, len(words) // 5, None, None, 0, _stream()), "sgs_stage_segments")
+    return -(-len(spans) // cap)
+
+
+def cluster_collate(parts, group, want_eid: bool = False):
+    """The batch of the partitions in `group` (a data.ResidentPartitions built with keep_cut_edges=True), cut edges between them
+    restored: data.collate_torch's result, built by sgs_cluster_collate (count, scan, fill: edges, prior and masks) and one
+    sgs_stage_segments launch per 24 spans (x, y, node ids).  The sizes come from the host tables, so nothing is read back --
+    unless `parts.size_path == "readback"` (more partitions than the block table holds): then the edge count is one 8-byte
+    read-back.  `want_eid`: also return, as `batch.eid`, each edge's position in `parts.full_col`."""
+    from .data import Batch, _check_group, _intra_edges, degree_prior as _degree_prior_torch
+    L = _lib.lib()
+    _need_gpu(parts.full_ptr, parts.full_col, parts.x_all)
+    group = _check_group(parts, group)
+    k = len(group)
+    if k > cluster_collate_max_parts():
+        raise ValueError(f"cluster_collate: {k} partitions in one batch, the limit is {cluster_collate_max_parts()}")
+    n_b, E_b = parts.batch_sizes(group)
+    dev = parts.full_ptr.device
+    nptr = parts.node_ptr_host
+    ranges = (ctypes.c_int64 * (2 * k))(*[v for p in group for v in (nptr[p], nptr[p + 1])])
+    nbytes = int(L.sgs_cluster_collate_workspace_bytes(n_b))
+    ws = workspace(nbytes, dev)
+    if E_b is None:
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        _lib.check(L.sgs_cluster_collate_count(_ptr(parts.full_ptr, torch.int64), _ptr(parts.full_col, torch.int64), ranges, k, n_b,
+                                               _ptr(total), ws.data_ptr(), ws.numel(), _stream()), "sgs_cluster_collate_count")
+        E_b = int(total.item())
+        if E_b >= 2 ** 31:
+            raise ValueError(f"a batch of {E_b} edges does not fit the int32 graph kernels (limit 2^31)")
+    x_all, y_all = parts.x_all, parts.y_all
+    F = int(x_all.shape[1])
+    if (F * x_all.element_size()) % 4 or y_all.element_size() % 4 or not x_all.is_contiguous() or not y_all.is_contiguous() or y_all.dim() != 1:
+        raise RuntimeError("cluster_collate: x rows and y entries must be contiguous whole 4-byte words")
+    ei = torch.empty(2, E_b, dtype=torch.int64, device=dev)
+    prob = torch.empty(E_b, dtype=torch.float32, device=dev) if parts.full_prob is not None else None
+    eid = torch.empty(E_b, dtype=torch.int64, device=dev) if want_eid else None
+    masks = torch.empty(3, n_b, dtype=torch.uint8, device=dev)
+    x = torch.empty(n_b, F, dtype=x_all.dtype, device=dev)
+    y = torch.empty(n_b, dtype=y_all.dtype, device=dev)
+    node_ids = torch.empty(n_b, dtype=torch.int64, device=dev)
+    _lib.check(L.sgs_cluster_collate(_ptr(parts.full_ptr, torch.int64), _ptr(parts.full_col, torch.int64), _ptr(parts.full_prob), ranges, k,
+                                     n_b, E_b, _ptr(ei), _ptr(prob), _ptr(eid), _ptr(parts.masks_all, torch.uint8), _ptr(masks), 3,
+                                     parts.num_nodes, _ptr(parts.collate_mismatch, torch.int32), ws.data_ptr(), ws.numel(), _stream()),
+               "sgs_cluster_collate")
+    spans, at = [], 0
+    xb, yb = F * x_all.element_size(), y_all.element_size()
+    for p in group:
+        a, n = nptr[p], nptr[p + 1] - nptr[p]
+        spans += [(x_all.data_ptr() + a * xb, x.data_ptr() + at * xb, n * xb), (y_all.data_ptr() + a * yb, y.data_ptr() + at * yb, n * yb),
+                  (parts.perm.data_ptr() + a * 8, node_ids.data_ptr() + at * 8, n * 8)]
+        at += n
+    _stage_spans(spans)
+    if prob is None:
+        prob = degree_prior(ei, n_b) if E_b > 0 else _degree_prior_torch(ei, n_b)      # prior="local": of the batch's own edge list
+    m = masks.view(torch.bool)
+    b = Batch(x=x, edge_index=ei, y=y, train_mask=m[0], val_mask=m[1], test_mask=m[2], prob=prob, node_ids=node_ids, parts=group,
+              restored_edges=E_b - _intra_edges(parts, group))
+    if want_eid:
+        b.eid = eid
+    return b

@@ -284,6 +284,12 @@ def _train_in(pipeline, args, epoch, max_epoch, model, optimizer_gnn, optimizer_
             sync = model._sgs_gradsync = GradSync(model.parameters())
     graphs = None
     if getattr(args, "sgs_hipgraph", False) and mode == 'learned' and not noise and trace is None and _ce_spec(criterion) is not None:
+        if getattr(cluster_loader, "regroup", None) == "epoch":
+            # a ResidentClusterLoader that re-draws its groups yields a NEW batch object every step.  The replay path keeps per batch
+            # a staging descriptor that pins the batch's tensors and derived arrays (StepGraphs.stage_cache, up to 8192 entries) and
+            # builds them with host read-backs the first time a batch is seen -- for such a loader that is every step ("Multi-partition batches")
+            raise ValueError("args.sgs_hipgraph cannot be combined with ResidentClusterLoader(regroup='epoch'): every step's batch is new, "
+                             "so nothing can be replayed from resident buffers; use regroup='fixed' or run eagerly")
         from .stepgraph import StepGraphs               # opt-in: replay captured HIP graphs of each partition's step
         graphs = StepGraphs.attach(model, pipeline, args, criterion, q, use_checkpoint,
                                    optimizers=(optimizer_edge_prob, optimizer_gnn), sync=sync, loader=cluster_loader)
