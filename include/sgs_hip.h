@@ -1377,6 +1377,34 @@ int sgs_edge_class_counts(const int64_t* edge_index, int64_t n, const uint8_t* m
 int sgs_edge_class_variant(int64_t n, int64_t C);
 int sgs_edge_class_variant_set(int code);
 
+/* ---- device partitioner (partition.py: partition_graph; csrc/partition.hip; numpy restatement: tests/partition_ref.py)
+ * One sweep of a balanced k-way label propagation is sgs_lp_propose followed by sgs_lp_commit; all of it is integer arithmetic, so the
+ * results are exact and the same on every call.  The graph is an int32 CSR (ptr [N + 1], col [nnz]) of an undirected graph stored both ways;
+ * entries with col == row are ignored, repeated entries count with their multiplicity.  part is int32 [N] with values in [0, P) or -1
+ * (unassigned); 1 <= P <= min(N, 4096); N, nnz < 2^31.  A column outside [0, N) or a part outside [0, P) is skipped, never used as an index.
+ * sgs_lp_propose: for every ELIGIBLE node v (eligible = 0: part[v] == -1; eligible = 1: fmix32(v ^ fmix32(hash_key)) & 1, fmix32 = murmur3's
+ *   32-bit finaliser) with conn[p] = the number of non-loop entries u of row v with part[u] = p >= 0, own = conn[part[v]] (0 when unassigned):
+ *   best[v] = the p != part[v] with the largest conn[p] > 0 (ties: the lower p), gain[v] = conn[best] - own -- if such a p exists and
+ *   gain >= mingain; best[v] = -1, gain[v] = 0 otherwise and for every node that is not eligible.  One wave per row, a slab of P counters in
+ *   LDS per wave; a row of more than sgs_lp_propose_hub_row() entries is walked by its workgroup's four waves together (one kernel, both
+ *   forms in it).  No float arithmetic, no global atomics.
+ * sgs_lp_commit: with size [P] and part as they stand on entry, key(v) = best << 51 | (2^20 - 1 - clamp(gain, 0, 2^20 - 1)) << 31 | v:
+ *   within each target, in ascending key order, the first max(cap - size[target], 0) proposals survive; among the survivors with a source
+ *   part s >= 0, ordered by the same key with s in place of best, the first max(size[s] - lo, 0) per source survive; survivors without a
+ *   source always pass.  Survivors move: part and size are updated in place and *moved (a device int32) is SET to their number.  Two library
+ *   radix sorts (csrc/graph_sort.hip), so the call is not capturable into a HIP graph.  ws: sgs_lp_commit_workspace_bytes(N, P) (host only).
+ * sgs_partition_stats: size[p] = #{v: part[v] = p} (int32 [P]) and *cut (device int64) = the number of stored non-loop entries (v, u) with
+ *   part[v] != part[u] -- every undirected edge twice -- in one pass; both outputs are overwritten.
+ * Argument errors (SGS_EINVAL, message in sgs_last_error): N or nnz negative or >= 2^31; P outside [1, 4096]; P > N; a null pointer. */
+int64_t sgs_lp_propose_hub_row(void);
+int sgs_lp_propose(const int32_t* ptr, const int32_t* col, int64_t N, int64_t nnz, int64_t P, const int32_t* part, int eligible, uint32_t hash_key,
+                   int mingain, int32_t* best, int32_t* gain, sgs_stream_t stream);
+size_t sgs_lp_commit_workspace_bytes(int64_t N, int64_t P);
+int sgs_lp_commit(const int32_t* best, const int32_t* gain, int64_t N, int64_t P, int64_t cap, int64_t lo, int32_t* part, int32_t* size,
+                  int32_t* moved, void* ws, size_t ws_bytes, sgs_stream_t stream);
+int sgs_partition_stats(const int32_t* ptr, const int32_t* col, int64_t N, int64_t nnz, int64_t P, const int32_t* part, int32_t* size,
+                        int64_t* cut, sgs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,9 +99,11 @@ class ResidentPartitions:
     """All partitions of one graph resident in HBM: the device-side counterpart of the reference's
     `ClusterData(data, num_parts)` + `ClusterLoader(cluster_data, batch_size=1, shuffle=True)` (main.py:63-65; SURVEY.md
     section 8f item 2).  The reference re-slices every batch on the CPU and copies it to the GPU each time it is visited;
-    here the partitioning is applied ONCE on the device (METIS itself stays a host preprocessing step: pass its node ->
-    partition vector as `part_id`) and iteration yields `Batch` objects whose tensors never move again -- which is also
-    what the HIP-graph replay of the step needs (captures are keyed on the batch tensors' addresses).
+    here the partitioning is applied ONCE on the device and iteration yields `Batch` objects whose tensors never move again --
+    which is also what the HIP-graph replay of the step needs (captures are keyed on the batch tensors' addresses).  The node ->
+    partition vector `part_id` is the caller's (METIS run on the host, or any other partitioner) or the project's own:
+    `ResidentPartitions.from_graph` computes it on the device with `partition_graph` (partition.py: balanced k-way label
+    propagation; single level, so its cuts are honest but not METIS-grade).
 
     Semantics follow ClusterData: partition p holds the nodes with part_id == p (in ascending original id), the edges with
     BOTH endpoints in p (relabelled, row-sorted), the node attributes x / y / masks, and the edge attribute `prob` sliced
@@ -189,6 +191,18 @@ class ResidentPartitions:
             self.size_path = "table" if P <= self.CUT_TABLE_MAX_PARTS else "readback"
             self.block_edges = torch.bincount(ps * P + pd, minlength=P * P).view(P, P).cpu() if self.size_path == "table" else None
             self.collate_mismatch = torch.zeros(1, dtype=torch.int32, device=dev)         # set by the device collate if its count != E_b
+
+    @classmethod
+    def from_graph(cls, x, edge_index, y, train_mask, val_mask, test_mask, num_parts, *, partition=None, **kw):
+        """`partition_graph(edge_index, N, num_parts, **partition)` on the constructor's device, then the constructor with its result:
+        a raw undirected `edge_index` (stored both ways) in, resident partitions out.  `partition`: keyword arguments of
+        `partition_graph` (eps, hot, cold, seed, init, report); `kw`: the constructor's.  The vector is kept as `part_id`."""
+        from .partition import partition_graph
+        dev = torch.device(kw.get("device", "cuda:0"))
+        part_id = partition_graph(edge_index.to(dev), x.shape[0], num_parts, **dict(partition or {}))
+        self = cls(x, edge_index, y, train_mask, val_mask, test_mask, part_id, num_parts=num_parts, **kw)
+        self.part_id = part_id
+        return self
 
     def batch_sizes(self, group):
         """(n_b, E_b) of the union of the partitions in `group` from host tables alone; E_b is None when P is above the block

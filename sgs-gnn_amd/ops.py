@@ -3157,3 +3157,59 @@ def cluster_collate(parts, group, want_eid: bool = False):
     if want_eid:
         b.eid = eid
     return b
+
+
+# ------------------------------------------------------------------ device partitioner (csrc/partition.hip; partition.py)
+LP_UNASSIGNED, LP_HASH = 0, 1          # sgs_lp_propose's eligibility rule
+
+
+def _lp_csr(ptr, col, part, P):
+    _need_gpu(ptr, col, part)
+    N, P = part.numel(), int(P)
+    if ptr.numel() != N + 1:
+        raise RuntimeError("partitioner: ptr must hold N + 1 entries for part's N nodes")
+    return N, col.numel(), P
+
+
+def lp_propose(ptr, col, part, P: int, eligible: int, hash_key: int = 0, mingain: int = 0, best=None, gain=None):
+    """(best, gain) int32 [N] of one sweep's proposals (sgs_lp_propose): per eligible node the neighbouring part with the most entries
+    other than its own, and how many more entries that is; best = -1 where a node proposes nothing.  int32 CSR and part; one launch."""
+    L = _lib.lib()
+    N, nnz, P = _lp_csr(ptr, col, part, P)
+    _need_gpu(best, gain)
+    best = torch.empty(N, dtype=torch.int32, device=part.device) if best is None else best
+    gain = torch.empty(N, dtype=torch.int32, device=part.device) if gain is None else gain
+    if best.numel() != N or gain.numel() != N:
+        raise RuntimeError("lp_propose: best and gain need one entry per node")
+    _lib.check(L.sgs_lp_propose(_ptr(ptr, torch.int32), _ptr(col, torch.int32), N, nnz, P, _ptr(part, torch.int32), int(eligible),
+                                int(hash_key) & 0xFFFFFFFF, int(mingain), _ptr(best, torch.int32), _ptr(gain, torch.int32), _stream()),
+               "sgs_lp_propose")
+    return best, gain
+
+
+def lp_commit(best, gain, part, size, cap: int, lo: int, moved=None) -> torch.Tensor:
+    """Accepts the reference's subset of one sweep's proposals (sgs_lp_commit) and moves those nodes: `part` [N] and `size` [P] (int32) are
+    updated in place; returns `moved`, a device int32 [1] set to the number moved.  No host sync; not capturable (library sorts)."""
+    L = _lib.lib()
+    _need_gpu(best, gain, part, size, moved)
+    N, P = part.numel(), size.numel()
+    if best.numel() != N or gain.numel() != N:
+        raise RuntimeError("lp_commit: best and gain need one entry per node")
+    moved = torch.empty(1, dtype=torch.int32, device=part.device) if moved is None else moved
+    nbytes = int(L.sgs_lp_commit_workspace_bytes(N, P))
+    ws = workspace(nbytes, part.device)
+    _lib.check(L.sgs_lp_commit(_ptr(best, torch.int32), _ptr(gain, torch.int32), N, P, int(cap), int(lo), _ptr(part, torch.int32),
+                               _ptr(size, torch.int32), _ptr(moved, torch.int32), _ptr(ws), nbytes, _stream()), "sgs_lp_commit")
+    return moved
+
+
+def partition_stats(ptr, col, part, P: int):
+    """(size int32 [P], cut int64 [1]) on device (sgs_partition_stats): the nodes of every part and the stored non-loop entries whose ends
+    lie in different parts (every undirected edge twice).  One pass, no host sync."""
+    L = _lib.lib()
+    N, nnz, P = _lp_csr(ptr, col, part, P)
+    size = torch.empty(max(P, 1), dtype=torch.int32, device=part.device)
+    cut = torch.empty(1, dtype=torch.int64, device=part.device)
+    _lib.check(L.sgs_partition_stats(_ptr(ptr, torch.int32), _ptr(col, torch.int32), N, nnz, P, _ptr(part, torch.int32), _ptr(size),
+                                     _ptr(cut), _stream()), "sgs_partition_stats")
+    return size, cut
