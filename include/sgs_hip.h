@@ -1405,6 +1405,62 @@ int sgs_lp_commit(const int32_t* best, const int32_t* gain, int64_t N, int64_t P
 int sgs_partition_stats(const int32_t* ptr, const int32_t* col, int64_t N, int64_t nnz, int64_t P, const int32_t* part, int32_t* size,
                         int64_t* cut, sgs_stream_t stream);
 
+/* ---- neighbour-sampled batches (data.py: ResidentGraph, NeighborLoader; csrc/neighbor.hip; numpy restatement: tests/neighbor_ref.py)
+ * A batch is a set of distinct seed nodes plus a sampled k-hop in-neighbourhood.  The graph is the edge list sorted by (src, dst) (int64
+ * [2, E]; an edge's id is its position), its two int32 CSRs as sgs_graph_build emits them (rows in ascending edge id) and N nodes; N, E < 2^31.
+ * All of it is integer arithmetic: results are exact and the same on every call.  A row id, an edge id or a column outside its range is
+ * skipped and never used as an index -- with one exception that indexes nothing: sgs_nbr_select passes the ids of a row through unread.
+ * sgs_nbr_select: for frontier row r (node rows[r]; deg = its in-CSR row length, 0 when the node is outside [0, N)) writes take = deg
+ *   (fanout = -1 or deg <= fanout) or take = fanout ids to chosen[offs[r] .. offs[r] + take), offs = the exclusive scan of take over the rows
+ *   (kept in ws; from in_ptr alone).  Of a longer row the ids e with the `fanout` smallest keys fmix32(e ^ key) are taken (fmix32 = murmur3's
+ *   32-bit finaliser, a bijection: distinct ids never tie), in row order.  *total_dev (may be NULL) = offs[n_rows]; nothing is written at or
+ *   beyond chosen[cap].  One wave per row: four 8-bit radix passes over a 256-bin LDS histogram, keys recomputed, then a ballot compaction; a
+ *   row of more than sgs_nbr_select_hub_row() entries is walked by its workgroup's four waves together (one kernel, both forms in it).  Two
+ *   launches (scan, rows).  ws: sgs_nbr_select_workspace_bytes(n_rows), 8-byte aligned.
+ * state: sgs_nbr_state_bytes(N) bytes, 4-byte aligned: three bitmaps of ceil(N / 32) words -- batch members, reached this hop, seeds.
+ * sgs_nbr_begin: clears the state and sets the seeds in `members` and `seeds` (two launches).
+ * sgs_nbr_frontier: the sources edge_index[0][e] of the chosen ids that are not members yet become the next frontier: written ascending to
+ *   frontier_out (nothing at or beyond cap), merged into the members; sizes_dev[0] = their number, sizes_dev[1] = the sum over them of
+ *   min(next_fanout, in-degree) (next_fanout = -1: the in-degree; 0: not computed) -- what the next sgs_nbr_select will emit, so one 16-byte
+ *   read-back per hop sizes both buffers.  Two launches: an atomic-OR pass over the chosen ids, a single-workgroup popcount scan over the words.
+ * sgs_nbr_nodes: node_ids [n] int64 = the members ascending (a node's local id is its rank there), wpre [ceil(N / 32)] int32 = the members
+ *   below each word; *mismatch_dev (may be NULL) is set to 1 if the members are not n.  One launch.
+ * sgs_nbr_induced_count / _fill: every stored edge with both ends among the members, in ascending edge id: count per out-CSR row of the
+ *   members and scan (rowptr [n + 1] int64, *total_dev = E_b; two launches), then fill edge_index_out [2, E_b] (local ids), prob_out = prob[id]
+ *   and eid_out = id (either may be NULL) (one launch).  One wave per row; membership and local ids from the bitmap and wpre.
+ * sgs_nbr_directional: the chosen ids of all hops (segments_host [n_segments][2] = {device address of int32 ids, count}, by value; at most
+ *   sgs_nbr_max_hops() segments, m ids in all), ascending, as edges: edge_index_out [2, m] (row stride m), prob_out, eid_out.  An id outside
+ *   [0, E) or with an end outside the members is dropped; *total_dev = the number kept (the first *total_dev columns are written).  Uses the
+ *   library radix sort, so the call is not capturable.  ws: sgs_nbr_directional_workspace_bytes(m), 8-byte aligned.
+ * sgs_nbr_gather: one launch gathers, for the n members, x rows (row_bytes a multiple of 4), y (int64), masks [3, N] -> masks_out [3, n]
+ *   ANDed with "is a seed", and seed_mask_out [n] (bytes).
+ * Argument errors (SGS_EINVAL, message in sgs_last_error): N outside [1, 2^31); E, nnz, n_rows, m negative or >= 2^31; fanout 0 or below -1;
+ *   n above N; a misaligned or null pointer; segments that do not add up to m.  SGS_EWORKSPACE: state or workspace too small. */
+int64_t sgs_nbr_select_hub_row(void);
+int sgs_nbr_max_hops(void);
+size_t sgs_nbr_select_workspace_bytes(int64_t n_rows);
+int sgs_nbr_select(const int32_t* in_ptr, const int32_t* in_eid, int64_t N, int64_t nnz, const int32_t* rows, int64_t n_rows, int64_t fanout,
+                   uint32_t key, int32_t* chosen, int64_t cap, int64_t* total_dev, void* ws, size_t ws_bytes, sgs_stream_t stream);
+size_t sgs_nbr_state_bytes(int64_t N);
+int sgs_nbr_begin(const int32_t* seeds, int64_t n_seeds, int64_t N, void* state, size_t state_bytes, sgs_stream_t stream);
+int sgs_nbr_frontier(const int32_t* chosen, int64_t n_chosen, const int64_t* edge_index, int64_t E, int64_t N, const int32_t* in_ptr,
+                     int64_t next_fanout, void* state, size_t state_bytes, int32_t* frontier_out, int64_t cap, int64_t* sizes_dev,
+                     sgs_stream_t stream);
+int sgs_nbr_nodes(const void* state, size_t state_bytes, int64_t N, int64_t n, int32_t* wpre, int64_t* node_ids, int32_t* mismatch_dev,
+                  sgs_stream_t stream);
+int sgs_nbr_induced_count(const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, int64_t N, int64_t E, const void* state,
+                          size_t state_bytes, const int32_t* wpre, const int64_t* node_ids, int64_t n, int64_t* rowptr, int64_t* total_dev,
+                          sgs_stream_t stream);
+int sgs_nbr_induced_fill(const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, const float* prob, int64_t N, int64_t E,
+                         const void* state, size_t state_bytes, const int32_t* wpre, const int64_t* node_ids, int64_t n, const int64_t* rowptr,
+                         int64_t E_b, int64_t* edge_index_out, float* prob_out, int64_t* eid_out, sgs_stream_t stream);
+size_t sgs_nbr_directional_workspace_bytes(int64_t m);
+int sgs_nbr_directional(const int64_t* segments_host, int64_t n_segments, int64_t m, const int64_t* edge_index, int64_t E, int64_t N,
+                        const float* prob, const void* state, size_t state_bytes, const int32_t* wpre, int64_t* edge_index_out, float* prob_out,
+                        int64_t* eid_out, int64_t* total_dev, void* ws, size_t ws_bytes, sgs_stream_t stream);
+int sgs_nbr_gather(const int64_t* node_ids, int64_t n, int64_t N, const void* x, int64_t row_bytes, void* x_out, const int64_t* y, int64_t* y_out,
+                   const uint8_t* masks, const void* state, size_t state_bytes, uint8_t* masks_out, uint8_t* seed_mask_out, sgs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,4 +14,5 @@ from .sparsify import sparsify  # noqa: F401
 from .utils import calculate_f1, calculate_auc, auc_from_counts, f1_from_confusion, classification_report, consistency_loss, count_edges_with_different_labels, fix_seeds, GpuMemoryProfiler  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 from .partition import partition_graph  # noqa: F401
+from .data import ResidentGraph, NeighborLoader, neighbor_collate_torch, neighbor_stream_key  # noqa: F401
 from .data import Batch, ResidentPartitions, ResidentClusterLoader, degree_prior, synthetic_graph, synthetic_partitioned_graph, reddit_partition_stream, reddit_partition_sizes  # noqa: F401

@@ -403,6 +403,269 @@ class ResidentClusterLoader:
         self.dropped_edges = self.parts.num_edges - seen
 
 
+# ---------------------------------------------------------------------------------------------------- neighbour-sampled batches
+_M32 = 0xFFFFFFFF
+SUBGRAPH_TYPES = ("induced", "directional")
+
+
+def fmix32(h: int) -> int:
+    """murmur3's 32-bit finaliser (partition.py's hash)"""
+    h &= _M32
+    h ^= h >> 16
+    h = (h * 0x85EBCA6B) & _M32
+    h ^= h >> 13
+    h = (h * 0xC2B2AE35) & _M32
+    return h ^ (h >> 16)
+
+
+def neighbor_stream_key(seed: int, epoch: int, batch: int, hop: int) -> int:
+    """K(seed, epoch, batch, hop) = fmix32(hop + fmix32(batch + fmix32(epoch + fmix32(seed)))), additions modulo 2^32: the key under which
+    hop `hop` of batch `batch` of epoch `epoch` ranks edge id e by fmix32(e ^ K)."""
+    k = fmix32(int(seed))
+    for t in (epoch, batch, hop):
+        k = fmix32(int(t) + k)
+    return k
+
+
+def _fmix32_tensor(h):
+    h = h & _M32
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & _M32
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & _M32
+    return h ^ (h >> 16)
+
+
+def _expand_rows(ptr, rows):
+    """-> (row number, position in the CSR arrays) of every entry of the CSR rows `rows`, rows back to back"""
+    dev = ptr.device
+    beg = ptr[rows].to(torch.int64)
+    deg = ptr[rows + 1].to(torch.int64) - beg
+    rid = torch.repeat_interleave(torch.arange(rows.numel(), device=dev), deg)
+    pos = torch.repeat_interleave(beg - (torch.cumsum(deg, 0) - deg), deg) + torch.arange(int(rid.numel()), device=dev)
+    return rid, pos
+
+
+def check_fanouts(num_neighbors):
+    fan = [int(f) for f in num_neighbors]
+    if len(fan) < 1:
+        raise ValueError("num_neighbors must name at least one hop")
+    if any(f == 0 or f < -1 for f in fan):
+        raise ValueError(f"a fan-out is >= 1, or -1 for every neighbour; got {fan}")
+    return fan
+
+
+def check_subgraph_type(subgraph_type):
+    if subgraph_type == "bidirectional":
+        raise ValueError("subgraph_type='bidirectional' is not supported: use 'induced' (every stored edge among the batch's nodes) "
+                         "or 'directional' (the sampled edges)")
+    if subgraph_type not in SUBGRAPH_TYPES:
+        raise ValueError(f"subgraph_type must be one of {SUBGRAPH_TYPES}, got {subgraph_type!r}")
+    return subgraph_type
+
+
+class ResidentGraph:
+    """One whole graph resident on `device`, for batches that are SAMPLED from it rather than cut out of it (`neighbor_loader`): the edge
+    list sorted by (src, dst) -- an edge's id is its position there; `edge_order` maps it back to the caller's list --, both CSR orientations
+    (ops.get_graph's on a HIP device), the full-graph prior `prob` in sorted order (`prior="global"`: ops.degree_prior unless given;
+    `prior="local"`: none, every batch computes the prior of its own edge list), x, y and the three masks as [3, N] bytes.  The graph may be
+    directed and may hold self loops and repeated edges."""
+
+    def __init__(self, x, edge_index, y, train_mask, val_mask, test_mask, device="cuda:0", prior="global", prob=None):
+        if prior not in ("global", "local"):
+            raise ValueError(f"prior must be 'global' or 'local', got {prior!r}")
+        dev = torch.device(device)
+        N, E = int(x.shape[0]), int(edge_index.shape[1])
+        if not 1 <= N < 2 ** 31 or E >= 2 ** 31:
+            raise ValueError(f"a graph of {N} nodes / {E} edges does not fit the int32 graph kernels (need 1 <= N < 2^31, E < 2^31)")
+        ei = edge_index.to(dev).to(torch.int64)
+        if E and (int(ei.min()) < 0 or int(ei.max()) >= N):
+            raise ValueError("edge_index holds a node id outside [0, N)")
+        order = torch.argsort(ei[0] * N + ei[1], stable=True)
+        ei = ei[:, order].contiguous()
+        self.num_nodes, self.num_edges, self.edge_index, self.edge_order = N, E, ei, order
+        self.on_device = dev.type == "cuda"
+        if self.on_device:
+            from . import ops
+            g = ops.get_graph(ei, N)
+            self.in_ptr, self.in_eid, self.out_ptr, self.out_dst, self.out_eid = g.in_ptr, g.in_eid, g.out_ptr, g.out_dst, g.out_eid
+            self._nbr_state = ops.nbr_state(N, dev)
+            self.collate_mismatch = torch.zeros(1, dtype=torch.int32, device=dev)       # set if a batch's members are not the nodes counted
+        else:
+            by_dst = torch.argsort(ei[1], stable=True)                                  # rows in ascending edge id, like sgs_graph_build's
+            ptr_of = lambda r: torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(torch.bincount(r, minlength=N), 0)]).to(torch.int32)  # noqa: E731
+            self.in_ptr, self.in_eid = ptr_of(ei[1]), by_dst.to(torch.int32)
+            self.out_ptr, self.out_dst, self.out_eid = ptr_of(ei[0]), ei[1].to(torch.int32), torch.arange(E, dtype=torch.int32)
+        if prob is not None:
+            prob = prob.to(dev)[order].contiguous()
+        elif prior == "global":
+            if self.on_device and E > 0:
+                from . import ops
+                prob = ops.degree_prior(ei, N)
+            else:
+                prob = degree_prior(ei, N)
+        self.prob, self.prior = prob, prior
+        self.x, self.y = x.to(dev).contiguous(), y.to(dev).to(torch.int64).contiguous()
+        self.masks = torch.stack([train_mask, val_mask, test_mask]).to(dev).to(torch.uint8).contiguous()
+        ip = self.in_ptr.cpu().to(torch.int64)                                          # one read-back at construction: the seeds' rows are sized on the host
+        self.in_deg_host = ip[1:] - ip[:-1]
+
+    def neighbor_loader(self, num_neighbors, batch_size, input_nodes="train", shuffle=True, seed=0, subgraph_type="induced", resample="epoch",
+                        drop_last=False) -> "NeighborLoader":
+        return NeighborLoader(self, num_neighbors, batch_size, input_nodes=input_nodes, shuffle=shuffle, seed=seed, subgraph_type=subgraph_type,
+                              resample=resample, drop_last=drop_last)
+
+    def check_seeds(self, seeds):
+        s = torch.as_tensor(seeds, dtype=torch.int64).cpu().reshape(-1)
+        if s.numel() and (int(s.min()) < 0 or int(s.max()) >= self.num_nodes):
+            raise ValueError(f"a seed node id lies outside [0, {self.num_nodes})")
+        if torch.unique(s).numel() != s.numel():
+            raise ValueError("the seed nodes must be distinct")
+        return s
+
+    def batch(self, seeds, num_neighbors, keys, subgraph_type="induced") -> Batch:
+        """One batch: distinct `seeds`, one fan-out and one 32-bit stream key per hop.  On a HIP device it is built by the kernels of
+        csrc/neighbor.hip (ops.neighbor_batch), never by a torch composition; on the CPU by `neighbor_collate_torch`."""
+        fan, subgraph_type, seeds = check_fanouts(num_neighbors), check_subgraph_type(subgraph_type), self.check_seeds(seeds)
+        if len(keys) != len(fan):
+            raise ValueError("one stream key per hop")
+        if self.on_device:
+            from . import ops
+            if len(fan) > ops.nbr_max_hops():
+                raise ValueError(f"{len(fan)} hops, the device builder's limit is {ops.nbr_max_hops()}")
+            return ops.neighbor_batch(self, seeds, fan, keys, subgraph_type)
+        return neighbor_collate_torch(self, seeds, fan, keys, subgraph_type)
+
+
+def neighbor_collate_torch(graph: ResidentGraph, seeds, num_neighbors, keys, subgraph_type="induced") -> Batch:
+    """The neighbour-sampled batch as a plain torch composition over `graph`'s tensors, wherever they live.  It is what runs when the graph is
+    on the CPU and the yardstick of tools/neighbor_probe.py; on a HIP device the loader calls ops.neighbor_batch instead.  Rules
+    ("Neighbour-sampled batches"): hop h takes, for every frontier node, all its in-edges if there are at most f_h (or
+    f_h = -1), else the f_h whose keys fmix32(edge id ^ K_h) are smallest; the sources not yet in the batch form the next frontier;
+    node_ids ascending; `induced` = every stored edge among them, `directional` = the chosen edges, both in ascending edge id."""
+    fan, subgraph_type = check_fanouts(num_neighbors), check_subgraph_type(subgraph_type)
+    dev, N = graph.edge_index.device, graph.num_nodes
+    seeds = torch.as_tensor(seeds, dtype=torch.int64).to(dev)
+    member = torch.zeros(N, dtype=torch.bool, device=dev)
+    member[seeds] = True
+    front, hop_nodes, chosen = seeds, [int(seeds.numel())], []
+    for f, K in zip(fan, keys):
+        rid, pos = _expand_rows(graph.in_ptr, front)
+        ids = graph.in_eid[pos].to(torch.int64)
+        if f >= 0:
+            key = _fmix32_tensor(ids ^ int(K))
+            order = torch.argsort((rid << 32) | key)                     # by row, then by key: distinct ids have distinct keys
+            deg = torch.bincount(rid, minlength=front.numel())
+            start = torch.cumsum(deg, 0) - deg
+            keep = torch.zeros(ids.numel(), dtype=torch.bool, device=dev)
+            keep[order] = (torch.arange(ids.numel(), device=dev) - start[rid[order]]) < f
+            ids = ids[keep]
+        chosen.append(ids)
+        u = graph.edge_index[0][ids]
+        front = torch.unique(u[~member[u]])
+        member[front] = True
+        hop_nodes.append(int(front.numel()))
+    node_ids = torch.nonzero(member).reshape(-1)
+    loc = torch.cumsum(member, 0) - 1
+    if subgraph_type == "induced":
+        rid, pos = _expand_rows(graph.out_ptr, node_ids)
+        eid = graph.out_eid[pos].to(torch.int64)
+        keep = member[graph.edge_index[1][eid]]
+        eid = eid[keep]
+        ei = torch.stack([rid[keep], loc[graph.edge_index[1][eid]]]).contiguous()
+    else:
+        eid = torch.sort(torch.cat(chosen)).values
+        ei = torch.stack([loc[graph.edge_index[0][eid]], loc[graph.edge_index[1][eid]]]).contiguous()
+    n = int(node_ids.numel())
+    if graph.prob is not None:
+        prob = graph.prob[eid]
+    elif dev.type == "cuda" and ei.shape[1] > 0:
+        from . import ops
+        prob = ops.degree_prior(ei, n)
+    else:
+        prob = degree_prior(ei, n)
+    is_seed = torch.zeros(N, dtype=torch.bool, device=dev)
+    is_seed[seeds] = True
+    seed_mask = is_seed[node_ids]
+    m = graph.masks[:, node_ids].bool() & seed_mask[None, :]
+    return Batch(x=graph.x[node_ids], edge_index=ei, y=graph.y[node_ids], train_mask=m[0].contiguous(), val_mask=m[1].contiguous(),
+                 test_mask=m[2].contiguous(), prob=prob, eid=eid, node_ids=node_ids, seed_mask=seed_mask, n_seeds=int(seeds.numel()),
+                 hop_nodes=hop_nodes)
+
+
+class NeighborLoader:
+    """GraphSAGE-style mini-batches over a `ResidentGraph` (PyG's `NeighborLoader`): batch b of an epoch is the b-th chunk of `batch_size`
+    seed nodes of the (shuffled) input list plus their sampled len(num_neighbors)-hop in-neighbourhood.  The shuffle is drawn on the host by a
+    generator seeded with (seed, epoch); the neighbours by the integer stream keys `neighbor_stream_key(seed, epoch, b, hop)`, so a
+    (seed, epoch) pair names its batches exactly.  `epoch` advances at every `__iter__`; `set_epoch(e)` pins it (None: advance again).
+
+    Only the seeds of a batch have a sampled receptive field: its train / val / test masks are the graph's ANDed with `seed_mask`, so loss,
+    gate and metrics count seeds only, and a pass with `input_nodes` covering every node once counts every node exactly once.
+    resample="epoch": a fresh batch every step (eager training only).  resample="fixed": the batches of epoch 0 are built once and stay
+    resident in `self.batches` -- ordinary resident batches, which replay under args.sgs_hipgraph.  `q` stays per step, the caller's to scale."""
+
+    def __init__(self, graph: ResidentGraph, num_neighbors, batch_size: int, input_nodes="train", shuffle: bool = True, seed: int = 0,
+                 subgraph_type: str = "induced", resample: str = "epoch", drop_last: bool = False):
+        self.num_neighbors, self.subgraph_type = check_fanouts(num_neighbors), check_subgraph_type(subgraph_type)
+        if int(batch_size) < 1:
+            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        if resample not in ("fixed", "epoch"):
+            raise ValueError(f"resample must be 'fixed' or 'epoch', got {resample!r}")
+        if graph.on_device:
+            from . import ops
+            if len(self.num_neighbors) > ops.nbr_max_hops():
+                raise ValueError(f"{len(self.num_neighbors)} hops, the device builder's limit is {ops.nbr_max_hops()}")
+        if isinstance(input_nodes, str):
+            if input_nodes not in ("train", "val", "test", "all"):
+                raise ValueError(f"input_nodes must be 'train', 'val', 'test', 'all', a bool mask or a list of node ids, got {input_nodes!r}")
+            ids = (torch.arange(graph.num_nodes) if input_nodes == "all"
+                   else torch.nonzero(graph.masks[("train", "val", "test").index(input_nodes)]).reshape(-1).cpu())
+        else:
+            t = torch.as_tensor(input_nodes)
+            if t.dtype == torch.bool:
+                if t.numel() != graph.num_nodes:
+                    raise ValueError("a bool input_nodes mask needs one entry per node")
+                ids = torch.nonzero(t).reshape(-1).cpu()
+            else:
+                ids = graph.check_seeds(t)
+        self.graph, self.batch_size, self.shuffle, self.seed = graph, int(batch_size), bool(shuffle), int(seed)
+        self.resample, self.drop_last, self.input_ids = resample, bool(drop_last), ids.to(torch.int64)
+        self.epoch, self._pinned, self.batches = 0, None, None
+        if resample == "fixed":
+            self.batches = list(self._build(0))
+
+    def set_epoch(self, epoch) -> None:
+        self._pinned = None if epoch is None else int(epoch)
+
+    def seed_lists(self, epoch: int):
+        ids = self.input_ids
+        if self.shuffle:
+            g = torch.Generator().manual_seed((self.seed * 0x9E3779B1 + int(epoch)) % (1 << 63))
+            ids = ids[torch.randperm(ids.numel(), generator=g)]
+        out = [ids[i:i + self.batch_size] for i in range(0, ids.numel(), self.batch_size)]
+        if self.drop_last and out and out[-1].numel() < self.batch_size:
+            out.pop()
+        return out
+
+    def _build(self, epoch: int):
+        L = len(self.num_neighbors)
+        for b, seeds in enumerate(self.seed_lists(epoch)):
+            keys = [neighbor_stream_key(self.seed, epoch, b, h) for h in range(L)]
+            yield self.graph.batch(seeds, self.num_neighbors, keys, self.subgraph_type)
+
+    def __len__(self):
+        n = self.input_ids.numel()
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def __iter__(self):
+        if self.resample == "fixed":
+            yield from self.batches
+            return
+        epoch = self.epoch if self._pinned is None else self._pinned
+        self.epoch = epoch + 1
+        yield from self._build(epoch)
+
+
 def synthetic_partitioned_graph(num_parts: int, n_per_part: int, e_intra, cut_frac: float, nfeat: int, ncls: int, seed: int, device="cpu"):
     """-> (Batch, part_id): `num_parts` graphs of `synthetic_graph(n_per_part, e_intra, ...)` (`e_intra`: one stored-edge target or one per
     partition) on disjoint node ranges, plus cut_frac * (undirected intra-partition edges) further undirected edges between uniformly drawn

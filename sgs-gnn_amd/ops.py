@@ -3213,3 +3213,132 @@ def partition_stats(ptr, col, part, P: int):
     _lib.check(L.sgs_partition_stats(_ptr(ptr, torch.int32), _ptr(col, torch.int32), N, nnz, P, _ptr(part, torch.int32), _ptr(size),
                                      _ptr(cut), _stream()), "sgs_partition_stats")
     return size, cut
+
+
+# ------------------------------------------------------------------ neighbour-sampled batches (csrc/neighbor.hip; data.py: ResidentGraph)
+def nbr_select_hub_row() -> int:
+    return int(_lib.lib().sgs_nbr_select_hub_row())
+
+
+def nbr_max_hops() -> int:
+    return int(_lib.lib().sgs_nbr_max_hops())
+
+
+def nbr_state(N: int, device) -> torch.Tensor:
+    """The three node bitmaps of a batch under construction (sgs_nbr_state_bytes), uninitialised: nbr_begin clears them."""
+    return torch.empty(int(_lib.lib().sgs_nbr_state_bytes(int(N))), dtype=torch.uint8, device=device)
+
+
+def nbr_select(in_ptr, in_eid, N: int, rows, fanout: int, key: int, total: int):
+    """int32 [total] chosen edge ids (sgs_nbr_select): per frontier row min(fanout, in-degree) of its in-edges, of a longer row the ones with
+    the `fanout` smallest keys fmix32(id ^ key), in row order; rows back to back.  `total` is the caller's (nbr_frontier reports it for the
+    next hop; for the seeds it follows from the in-degrees).  Two launches, no host sync."""
+    L = _lib.lib()
+    _need_gpu(in_ptr, in_eid, rows)
+    n_rows = rows.numel()
+    chosen = torch.empty(int(total), dtype=torch.int32, device=in_ptr.device)
+    nbytes = int(L.sgs_nbr_select_workspace_bytes(n_rows))
+    ws = workspace(nbytes, in_ptr.device)
+    _lib.check(L.sgs_nbr_select(_ptr(in_ptr, torch.int32), _ptr(in_eid, torch.int32), int(N), in_eid.numel(), _ptr(rows, torch.int32), n_rows,
+                                int(fanout), int(key) & 0xFFFFFFFF, _ptr(chosen), int(total), None, _ptr(ws), ws.numel(), _stream()), "sgs_nbr_select")
+    return chosen
+
+
+def nbr_begin(seeds, N: int, state) -> None:
+    """Clears `state` and marks the seeds (int32 node ids) as members and as seeds (sgs_nbr_begin)."""
+    _need_gpu(seeds, state)
+    _lib.check(_lib.lib().sgs_nbr_begin(_ptr(seeds, torch.int32), seeds.numel(), int(N), _ptr(state), state.numel(), _stream()), "sgs_nbr_begin")
+
+
+def nbr_frontier(chosen, edge_index, N: int, in_ptr, next_fanout: int, state, cap: int):
+    """(frontier int32 [cap], sizes int64 [2] on the device) of sgs_nbr_frontier: the sources of the chosen edges that are new to the batch,
+    ascending, merged into the members; sizes = (their number, what the next nbr_select will emit for them under `next_fanout`; 0: no next hop)."""
+    _need_gpu(chosen, edge_index, in_ptr, state)
+    dev = chosen.device
+    frontier = torch.empty(int(cap), dtype=torch.int32, device=dev)
+    sizes = torch.empty(2, dtype=torch.int64, device=dev)
+    _lib.check(_lib.lib().sgs_nbr_frontier(_ptr(chosen, torch.int32), chosen.numel(), _ptr(edge_index, torch.int64), edge_index.shape[1], int(N),
+                                           _ptr(in_ptr, torch.int32), int(next_fanout), _ptr(state), state.numel(), _ptr(frontier), int(cap),
+                                           _ptr(sizes), _stream()), "sgs_nbr_frontier")
+    return frontier, sizes
+
+
+def nbr_collate(graph, n: int, chosen, subgraph_type: str, n_seeds: int, hop_nodes):
+    """The Batch of the members in `graph._nbr_state` (a data.ResidentGraph on a HIP device; `n` of them): node ids and word prefixes
+    (sgs_nbr_nodes), the edges -- induced: count, scan, ONE 8-byte read-back of the edge count, fill; directional: `chosen` (the per-hop id
+    tensors) sorted and gathered, no read-back -- and one gathering launch for x, y, the masks and the seed flags."""
+    from .data import Batch, degree_prior as _degree_prior_torch
+    L = _lib.lib()
+    st, N, E, dev = graph._nbr_state, graph.num_nodes, graph.num_edges, graph.edge_index.device
+    sp, sb = _ptr(st), st.numel()
+    wpre = torch.empty((N + 31) // 32, dtype=torch.int32, device=dev)
+    node_ids = torch.empty(n, dtype=torch.int64, device=dev)
+    _lib.check(L.sgs_nbr_nodes(sp, sb, N, n, _ptr(wpre), _ptr(node_ids), _ptr(graph.collate_mismatch, torch.int32), _stream()), "sgs_nbr_nodes")
+    want_prob = graph.prob is not None
+    if subgraph_type == "induced":
+        rowptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        csr = (_ptr(graph.out_ptr, torch.int32), _ptr(graph.out_dst, torch.int32), _ptr(graph.out_eid, torch.int32))
+        _lib.check(L.sgs_nbr_induced_count(*csr, N, E, sp, sb, _ptr(wpre), _ptr(node_ids), n, _ptr(rowptr), _ptr(total), _stream()),
+                   "sgs_nbr_induced_count")
+        E_b = int(total.item())
+        ei = torch.empty(2, E_b, dtype=torch.int64, device=dev)
+        prob = torch.empty(E_b, dtype=torch.float32, device=dev) if want_prob else None
+        eid = torch.empty(E_b, dtype=torch.int64, device=dev)
+        _lib.check(L.sgs_nbr_induced_fill(*csr, _ptr(graph.prob), N, E, sp, sb, _ptr(wpre), _ptr(node_ids), n, _ptr(rowptr), E_b, _ptr(ei),
+                                          _ptr(prob), _ptr(eid), _stream()), "sgs_nbr_induced_fill")
+    else:
+        segs = [(c.data_ptr(), c.numel()) for c in chosen if c.numel() > 0] or [(0, 0)]
+        E_b = sum(c for _, c in segs)
+        ei = torch.empty(2, E_b, dtype=torch.int64, device=dev)
+        prob = torch.empty(E_b, dtype=torch.float32, device=dev) if want_prob else None
+        eid = torch.empty(E_b, dtype=torch.int64, device=dev)
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        table = (ctypes.c_int64 * (2 * len(segs)))(*[v for s in segs for v in s])
+        nbytes = int(L.sgs_nbr_directional_workspace_bytes(E_b))
+        ws = workspace(nbytes, dev)
+        _lib.check(L.sgs_nbr_directional(table, len(segs), E_b, _ptr(graph.edge_index, torch.int64), E, N, _ptr(graph.prob), sp, sb, _ptr(wpre),
+                                         _ptr(ei), _ptr(prob), _ptr(eid), _ptr(total), _ptr(ws), ws.numel(), _stream()), "sgs_nbr_directional")
+    x_all, y_all = graph.x, graph.y
+    row_bytes = int(x_all.shape[1]) * x_all.element_size()
+    if row_bytes % 4 or y_all.dtype != torch.int64 or not x_all.is_contiguous() or y_all.dim() != 1:
+        raise RuntimeError("nbr_collate: x rows must be contiguous whole 4-byte words and y an int64 vector")
+    x = torch.empty(n, x_all.shape[1], dtype=x_all.dtype, device=dev)
+    y = torch.empty(n, dtype=torch.int64, device=dev)
+    masks = torch.empty(3, n, dtype=torch.uint8, device=dev)
+    seed_mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    _lib.check(L.sgs_nbr_gather(_ptr(node_ids), n, N, _ptr(x_all), row_bytes, _ptr(x), _ptr(y_all), _ptr(y), _ptr(graph.masks, torch.uint8), sp, sb,
+                                _ptr(masks), _ptr(seed_mask), _stream()), "sgs_nbr_gather")
+    if prob is None:
+        prob = degree_prior(ei, n) if E_b > 0 else _degree_prior_torch(ei, n)          # prior="local": of the batch's own edge list
+    m = masks.view(torch.bool)
+    return Batch(x=x, edge_index=ei, y=y, train_mask=m[0], val_mask=m[1], test_mask=m[2], prob=prob, eid=eid, node_ids=node_ids,
+                 seed_mask=seed_mask.view(torch.bool), n_seeds=int(n_seeds), hop_nodes=list(hop_nodes))
+
+
+def neighbor_batch(graph, seeds, fanouts, keys, subgraph_type: str = "induced"):
+    """One neighbour-sampled Batch on the device: `seeds` (distinct node ids on the host), one fan-out and one stream key per hop.  Per hop
+    two selection launches, two frontier launches and ONE 16-byte read-back (the new frontier's size and what its rows will emit); then
+    nbr_collate.  data.neighbor_collate_torch is the same batch as a torch composition."""
+    _need_gpu(graph.edge_index)
+    dev, N = graph.edge_index.device, graph.num_nodes
+    seeds = torch.as_tensor(seeds, dtype=torch.int64)
+    front = seeds.to(torch.int32).to(dev)
+    deg = graph.in_deg_host[seeds]
+    total = int(deg.sum() if fanouts[0] < 0 else deg.clamp(max=int(fanouts[0])).sum())
+    nbr_begin(front, N, graph._nbr_state)
+    hop_nodes, chosen, n = [int(seeds.numel())], [], int(seeds.numel())
+    for h, (f, K) in enumerate(zip(fanouts, keys)):
+        if front.numel() == 0 or total == 0:
+            hop_nodes.append(0)
+            front, total = front[:0], 0
+            continue
+        c = nbr_select(graph.in_ptr, graph.in_eid, N, front, f, K, total)
+        chosen.append(c)
+        nxt = int(fanouts[h + 1]) if h + 1 < len(fanouts) else 0
+        front, sizes = nbr_frontier(c, graph.edge_index, N, graph.in_ptr, nxt, graph._nbr_state, min(total, N - n))
+        n_new, total = (int(v) for v in sizes.tolist())
+        front = front[:n_new]
+        hop_nodes.append(n_new)
+        n += n_new
+    return nbr_collate(graph, n, chosen, subgraph_type, int(seeds.numel()), hop_nodes)

@@ -290,6 +290,10 @@ def _train_in(pipeline, args, epoch, max_epoch, model, optimizer_gnn, optimizer_
             # builds them with host read-backs the first time a batch is seen -- for such a loader that is every step ("Multi-partition batches")
             raise ValueError("args.sgs_hipgraph cannot be combined with ResidentClusterLoader(regroup='epoch'): every step's batch is new, "
                              "so nothing can be replayed from resident buffers; use regroup='fixed' or run eagerly")
+        if getattr(cluster_loader, "resample", None) == "epoch":
+            # the same for a NeighborLoader that samples afresh: nothing is checked out of the loader before the refusal
+            raise ValueError("args.sgs_hipgraph cannot be combined with NeighborLoader(resample='epoch'): every step samples a new batch, "
+                             "so nothing can be replayed from resident buffers; use resample='fixed' or run eagerly")
         from .stepgraph import StepGraphs               # opt-in: replay captured HIP graphs of each partition's step
         graphs = StepGraphs.attach(model, pipeline, args, criterion, q, use_checkpoint,
                                    optimizers=(optimizer_edge_prob, optimizer_gnn), sync=sync, loader=cluster_loader)
