@@ -1417,6 +1417,19 @@ int sgs_partition_stats(const int32_t* ptr, const int32_t* col, int64_t N, int64
  *   beyond chosen[cap].  One wave per row: four 8-bit radix passes over a 256-bin LDS histogram, keys recomputed, then a ballot compaction; a
  *   row of more than sgs_nbr_select_hub_row() entries is walked by its workgroup's four waves together (one kernel, both forms in it).  Two
  *   launches (scan, rows).  ws: sgs_nbr_select_workspace_bytes(n_rows), 8-byte aligned.
+ * sgs_nbr_select_weighted: the same contract, workspace and two launches, with a weighted draw.  in_wq: int32 [nnz] in in-CSR order (entry j is
+ *   the weight of edge in_eid[j]), a quantised weight in [0, 2^24 - 1] (read as unsigned; a larger value counts as 2^24 - 1).  The key of id e is
+ *   sgs_nbr_weighted_key(fmix32(e ^ key), wq): with x = max(hash, 1) and NL = 32 * 2^24 - LOG2Q(x) in [1, 2^29] (-log2 of a uniform variate in
+ *   24-bit fixed point), LOG2Q(NL) - LOG2Q(wq) + 24 * 2^24 < 2^30 for wq >= 1, and 2^32 - 1 for wq = 0.  Its order is that of -ln(u) / w, so the
+ *   `fanout` smallest keys are `fanout` successive draws proportional to the weight, without replacement.  LOG2Q(x), 1 <= x < 2^32: n =
+ *   floor(log2 x), m = the 32 bits below the leading one, i = m >> 24, r = (m >> 8) & 0xFFFF, (n << 24) + T[i] + (((T[i + 1] - T[i]) r) >> 16),
+ *   T[i] = floor(2^24 log2(1 + i / 256)) (sgs_nbr_log2_table writes the 257 words; built by integer squaring at compile time); within
+ *   [-2.9e-6, 0] of log2 x and monotone.  Keys can tie: a longer row takes every id with a key below the fanout-th smallest key t and then the
+ *   first fanout - #{key < t} ids with key == t in row order; so zero-weight ids are taken only when a row has fewer than `fanout` positive
+ *   ones, first come first.  A row still emits min(fanout, deg) ids.  Only the ratios of the weights inside one row matter.  The row forms are
+ *   sgs_nbr_select's; a one-wave row computes its keys in the first radix pass and keeps them in LDS (32 KiB per workgroup, plus 1 KiB for the
+ *   table), a row above sgs_nbr_select_hub_row() recomputes them in every pass.  Both pins run on the host (no device needed) and are the
+ *   function the kernel evaluates.
  * state: sgs_nbr_state_bytes(N) bytes, 4-byte aligned: three bitmaps of ceil(N / 32) words -- batch members, reached this hop, seeds.
  * sgs_nbr_begin: clears the state and sets the seeds in `members` and `seeds` (two launches).
  * sgs_nbr_frontier: the sources edge_index[0][e] of the chosen ids that are not members yet become the next frontier: written ascending to
@@ -1441,6 +1454,11 @@ int sgs_nbr_max_hops(void);
 size_t sgs_nbr_select_workspace_bytes(int64_t n_rows);
 int sgs_nbr_select(const int32_t* in_ptr, const int32_t* in_eid, int64_t N, int64_t nnz, const int32_t* rows, int64_t n_rows, int64_t fanout,
                    uint32_t key, int32_t* chosen, int64_t cap, int64_t* total_dev, void* ws, size_t ws_bytes, sgs_stream_t stream);
+int sgs_nbr_select_weighted(const int32_t* in_ptr, const int32_t* in_eid, const int32_t* in_wq, int64_t N, int64_t nnz, const int32_t* rows,
+                            int64_t n_rows, int64_t fanout, uint32_t key, int32_t* chosen, int64_t cap, int64_t* total_dev, void* ws,
+                            size_t ws_bytes, sgs_stream_t stream);
+void sgs_nbr_log2_table(int32_t* out /* [257] */);
+uint32_t sgs_nbr_weighted_key(uint32_t hash, uint32_t wq);
 size_t sgs_nbr_state_bytes(int64_t N);
 int sgs_nbr_begin(const int32_t* seeds, int64_t n_seeds, int64_t N, void* state, size_t state_bytes, sgs_stream_t stream);
 int sgs_nbr_frontier(const int32_t* chosen, int64_t n_chosen, const int64_t* edge_index, int64_t E, int64_t N, const int32_t* in_ptr,

@@ -8,6 +8,14 @@
 // order (ballot + prefix popcount).  Distinct ids have distinct keys (fmix32 is a bijection), so exactly f ids pass.  A row of more than
 // kHubRow entries is left to the end of its tile, where the workgroup's four waves walk it together on histogram 0.  A row's output offset is
 // the exclusive scan of min(f, deg) over the frontier, from ptr alone (one single-workgroup scan launch before the row kernel).
+// WEIGHTED SELECTION (sgs_nbr_select_weighted): the same kernel template with another key.  Edge e with quantised weight wq in [1, 2^24) gets
+// key = LOG2Q(-log2 u) - LOG2Q(wq) + 24 * 2^24, u = max(fmix32(e ^ K), 1) / 2^32: the order of -ln(u) / w, an exponential clock, so the f
+// smallest keys are f successive draws proportional to the weight, without replacement.  LOG2Q is a 24-bit fixed-point log2 from a 257-word
+// table (built at compile time by integer squaring, copied to LDS by every workgroup) with linear interpolation: integers only, the same
+// bits as tests/neighbor_weighted_ref.py.  wq = 0 has the key 2^32 - 1.  These keys CAN tie, so the compaction has two parts: every id with
+// a key below the f-th smallest, plus the first `k` ids with that key in row order, k = the rank the last radix pass leaves (two ballots per
+// step; in the hub form two count rows).  A one-wave row (at most kHubRow keys) computes its keys once, in the first pass, and keeps them in
+// LDS for the other three passes and the compaction (8 KiB per wave; measured 17-24 % faster than recomputing them); a hub row recomputes.
 // FRONTIER (sgs_nbr_begin / sgs_nbr_frontier): three node bitmaps of ceil(N / 32) words (batch members, reached this hop, seeds).  The sources
 // of the chosen edges are OR-ed into `reached` unless already members; one single-workgroup popcount scan over the words then emits the new
 // nodes ascending, merges them into the members and clears `reached`.  Nothing is proportional to E, and to N only through the words.
@@ -38,6 +46,58 @@ __host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
     h ^= h >> 13; h *= 0xC2B2AE35u;
     h ^= h >> 16;
     return h;
+}
+
+// ---------------------------------------------------------------- the weighted key
+// T[i] = floor(2^24 log2(1 + i / 256)), i = 0 .. 256, by integer squaring: y in [1, 2) as a 2.62 fixed-point number; 24 times y <- y^2 and
+// one bit of the logarithm (y >= 2: the bit is set and y is halved).  Every step truncates, so y only ever errs low, by less than 2^-36
+// after 24 doublings: a bit would be wrong only where a true y came that close to 2.  tests/neighbor_weighted_ref.py brackets y from both
+// sides at 200 bits and finds the same 257 words.
+constexpr uint32_t kWqMax = (1u << 24) - 1u, kNoKey = 0xFFFFFFFFu;
+struct Log2Table {
+    int32_t t[257];
+};
+constexpr uint64_t square_q62(uint64_t y) {          // y < 2^63 -> floor(y^2 / 2^62) from 32-bit halves
+    const uint64_t a = y >> 32, b = y & 0xFFFFFFFFull;
+    const uint64_t ab = a * b, mid = ab << 33;
+    const uint64_t lo = b * b + mid;
+    const uint64_t hi = a * a + (ab >> 31) + (lo < mid ? 1u : 0u);
+    return (hi << 2) | (lo >> 62);
+}
+constexpr Log2Table make_log2_table() {
+    Log2Table tab{};
+    for (int i = 0; i < 256; ++i) {
+        uint64_t y = static_cast<uint64_t>(256 + i) << 54;
+        int32_t t = 0;
+        for (int b = 0; b < 24; ++b) {
+            y = square_q62(y);
+            t <<= 1;
+            if (y >> 63) {
+                t |= 1;
+                y >>= 1;
+            }
+        }
+        tab.t[i] = t;
+    }
+    tab.t[256] = 1 << 24;
+    return tab;
+}
+constexpr Log2Table kLog2Host = make_log2_table();
+__device__ const Log2Table kLog2Dev = make_log2_table();
+
+// LOG2Q(x), 1 <= x < 2^32: 2^24 log2(x) in [-2.9e-6 * 2^24, 0] of the true value, monotone.  T: the table (LDS on the device).
+__host__ __device__ __forceinline__ uint32_t log2q(uint32_t x, const int32_t* T) {
+    const int n = 31 - __builtin_clz(x);
+    const uint32_t m = (x << (31 - n)) << 1;         // the 32 bits below the leading one
+    const uint32_t i = m >> 24, r = (m >> 8) & 0xFFFFu;
+    const uint32_t lo = static_cast<uint32_t>(T[i]), d = static_cast<uint32_t>(T[i + 1]) - lo;
+    return (static_cast<uint32_t>(n) << 24) + lo + static_cast<uint32_t>((static_cast<uint64_t>(d) * r) >> 16);
+}
+// the key of an edge whose id hashes to h, under the quantised weight wq (read as unsigned; above 2^24 - 1 it counts as 2^24 - 1)
+__host__ __device__ __forceinline__ uint32_t weighted_key(uint32_t h, uint32_t wq, const int32_t* T) {
+    if (wq == 0u) return kNoKey;
+    const uint32_t nl = (32u << 24) - log2q(h ? h : 1u, T);               // -log2 of a uniform variate, in [1, 2^29]
+    return log2q(nl, T) - log2q(wq > kWqMax ? kWqMax : wq, T) + (24u << 24);
 }
 
 // LDS traffic of ONE wave: its lanes' atomics / stores are visible to its lanes' later loads
@@ -207,20 +267,42 @@ __device__ __forceinline__ uint32_t find_digit(const uint32_t* hist, uint32_t& k
     return __shfl(d, src, 64);
 }
 
+// the key of entry e of the in-CSR under id `id`: the hash, or the weighted key from wq[e] and the table T
+template <bool kWeighted>
+__device__ __forceinline__ uint32_t entry_key(int id, const int* __restrict__ wq, int64_t e, uint32_t K, const int32_t* T) {
+    const uint32_t h = fmix32(static_cast<uint32_t>(id) ^ K);
+    if constexpr (kWeighted) return weighted_key(h, static_cast<uint32_t>(wq[e]), T);
+    else return h;
+}
+
 // `who` of `team` threads walk the entries [beg, end) of a row: the keys that agree with `prefix` on the bits of `mask` go into hist
-__device__ __forceinline__ void tally_keys(const int* __restrict__ eid, int64_t beg, int64_t end, int who, int team, uint32_t K, uint32_t prefix,
-                                           uint32_t mask, int shift, uint32_t* hist) {
+template <bool kWeighted>
+__device__ __forceinline__ void tally_keys(const int* __restrict__ eid, const int* __restrict__ wq, const int32_t* T, int64_t beg, int64_t end,
+                                           int who, int team, uint32_t K, uint32_t prefix, uint32_t mask, int shift, uint32_t* hist) {
     for (int64_t e = beg + who; e < end; e += team) {
-        const uint32_t key = fmix32(static_cast<uint32_t>(eid[e]) ^ K);
+        const uint32_t key = entry_key<kWeighted>(eid[e], wq, e, K, T);
         if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
     }
 }
 
+// kWeighted = false: keys fmix32(id ^ K), distinct, one-part compaction (key <= threshold).  kWeighted = true: keys from wq (aligned with eid)
+// through the LDS copy of the log2 table, two-part compaction (key < threshold, then the first k ties in row order).
+template <bool kWeighted>
 __global__ void __launch_bounds__(kT) nbr_select(const int* __restrict__ ptr, const int* __restrict__ eid, int64_t N, const int* __restrict__ rows,
                                                  int64_t n_rows, int64_t f, uint32_t K, const int64_t* __restrict__ offs, int* __restrict__ chosen,
-                                                 int64_t cap) {
+                                                 int64_t cap, const int* __restrict__ wq) {
     __shared__ uint32_t hist[kWaves][256];
     __shared__ int wcnt[2][kWaves];
+    const int32_t* T = nullptr;
+    uint32_t* skey = nullptr;
+    if constexpr (kWeighted) {
+        __shared__ int32_t tab[257];
+        __shared__ uint32_t staged[kWaves][kHubRow];                    // a one-wave row's keys, computed once (32 KiB per workgroup)
+        skey = staged[threadIdx.x >> 6];
+        for (int i = threadIdx.x; i < 257; i += kT) tab[i] = kLog2Dev.t[i];
+        __syncthreads();
+        T = tab;
+    }
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int64_t tiles = (n_rows + kWaves - 1) / kWaves;
     for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {           // the trip count is the same for every wave: barriers below are safe
@@ -240,7 +322,20 @@ __global__ void __launch_bounds__(kT) nbr_select(const int* __restrict__ ptr, co
 #pragma unroll
                         for (int j = 0; j < 4; ++j) hs[lane * 4 + j] = 0u;
                         wave_sync();
-                        tally_keys(eid, beg, end, lane, kWave, K, prefix, mask, shift, hs);
+                        if constexpr (kWeighted) {                           // first pass: the keys go to LDS; a lane re-reads its own
+                            for (int64_t e = beg + lane; e < end; e += kWave) {
+                                uint32_t key;
+                                if (shift == 24) {
+                                    key = entry_key<true>(eid[e], wq, e, K, T);
+                                    skey[e - beg] = key;
+                                } else {
+                                    key = skey[e - beg];
+                                }
+                                if ((key & mask) == prefix) atomicAdd(&hs[(key >> shift) & 255u], 1u);
+                            }
+                        } else {
+                            tally_keys<false>(eid, wq, T, beg, end, lane, kWave, K, prefix, mask, shift, hs);
+                        }
                         wave_sync();
                         const uint32_t d = find_digit(hs, k);
                         wave_sync();
@@ -248,16 +343,30 @@ __global__ void __launch_bounds__(kT) nbr_select(const int* __restrict__ ptr, co
                         mask |= 255u << shift;
                     }
                     int64_t run = 0;                                     // prefix is now the f-th smallest key itself
+                    int64_t ties = 0;                                    // (weighted) and k how many ids with exactly that key are taken
                     for (int64_t b = beg; b < end; b += kWave) {
                         const int64_t e = b + lane;
                         int id = 0;
-                        bool in = false;
+                        bool in = false, tie = false;
                         if (e < end) {
                             id = eid[e];
-                            in = fmix32(static_cast<uint32_t>(id) ^ K) <= prefix;
+                            if constexpr (kWeighted) {
+                                const uint32_t key = skey[e - beg];
+                                in = key < prefix;
+                                tie = key == prefix;
+                            } else {
+                                in = entry_key<false>(id, wq, e, K, T) <= prefix;
+                            }
                         }
                         const u64 m = __ballot(in);
-                        const int64_t pos = run + __popcll(m & ((1ull << lane) - 1ull));
+                        int64_t pos = run + __popcll(m & ((1ull << lane) - 1ull));
+                        if constexpr (kWeighted) {                           // the ties before this lane that are taken: the first k of them
+                            const u64 mt = __ballot(tie);
+                            const int64_t before = ties + __popcll(mt & ((1ull << lane) - 1ull));
+                            pos += before < k ? before : k;
+                            in = in || (tie && before < k);
+                            ties += __popcll(mt);
+                        }
                         if (in && pos < f && out + pos < cap) chosen[out + pos] = id;       // (pos < f: repeated ids would tie)
                         run += __popcll(m);
                     }
@@ -282,25 +391,50 @@ __global__ void __launch_bounds__(kT) nbr_select(const int* __restrict__ ptr, co
                 __syncthreads();                                        // wave 0 is done with histogram 0; the last find is over
                 hist[0][threadIdx.x] = 0u;
                 __syncthreads();
-                tally_keys(eid, beg, end, threadIdx.x, kT, K, prefix, mask, shift, hist[0]);
+                tally_keys<kWeighted>(eid, wq, T, beg, end, threadIdx.x, kT, K, prefix, mask, shift, hist[0]);
                 __syncthreads();
                 const uint32_t d = find_digit(hist[0], k);              // every wave finds the same digit
                 prefix |= d << shift;
                 mask |= 255u << shift;
             }
-            int64_t run = 0;
+            int64_t run = 0, ties = 0;
             int buf = 0;
             for (int64_t b = beg; b < end; b += kT, buf ^= 1) {
                 const int64_t e = b + threadIdx.x;
                 int id = 0;
-                bool in = false;
+                bool in = false, tie = false;
                 if (e < end) {
                     id = eid[e];
-                    in = fmix32(static_cast<uint32_t>(id) ^ K) <= prefix;
+                    const uint32_t key = entry_key<kWeighted>(id, wq, e, K, T);
+                    if constexpr (kWeighted) {
+                        in = key < prefix;
+                        tie = key == prefix;
+                    } else {
+                        in = key <= prefix;
+                    }
                 }
                 const u64 m = __ballot(in);
                 if (lane == 0) wcnt[buf][wid] = __popcll(m);
-                __syncthreads();                                        // (two rows of counts alternate: one barrier per step)
+                int64_t taken_ties = 0;                                 // (weighted) the ties before this thread that are taken
+                if constexpr (kWeighted) {                               // a second row of counts: the ties of every wave
+                    __shared__ int wties[2][kWaves];
+                    const u64 mt = __ballot(tie);
+                    if (lane == 0) wties[buf][wid] = __popcll(mt);
+                    __syncthreads();
+                    int tbefore = 0, ttotal = 0;
+#pragma unroll
+                    for (int x = 0; x < kWaves; ++x) {
+                        const int c = wties[buf][x];
+                        tbefore += x < wid ? c : 0;
+                        ttotal += c;
+                    }
+                    const int64_t tb = ties + tbefore + __popcll(mt & ((1ull << lane) - 1ull));
+                    ties += ttotal;
+                    taken_ties = tb < k ? tb : k;
+                    in = in || (tie && tb < k);
+                } else {
+                    __syncthreads();                                    // (two rows of counts alternate: one barrier per step)
+                }
                 int before = 0, total = 0;
 #pragma unroll
                 for (int x = 0; x < kWaves; ++x) {
@@ -308,7 +442,7 @@ __global__ void __launch_bounds__(kT) nbr_select(const int* __restrict__ ptr, co
                     before += x < wid ? c : 0;
                     total += c;
                 }
-                const int64_t pos = run + before + __popcll(m & ((1ull << lane) - 1ull));
+                const int64_t pos = run + before + __popcll(m & ((1ull << lane) - 1ull)) + taken_ties;
                 if (in && pos < f && out + pos < cap) chosen[out + pos] = id;
                 run += total;
             }
@@ -488,28 +622,56 @@ int sgs_nbr_max_hops(void) { return sgs::kMaxHops; }
 
 size_t sgs_nbr_select_workspace_bytes(int64_t n_rows) { return sgs::carve_bytes(static_cast<size_t>(n_rows > 0 ? n_rows : 0) + 1, 8); }
 
-int sgs_nbr_select(const int32_t* in_ptr, const int32_t* in_eid, int64_t N, int64_t nnz, const int32_t* rows, int64_t n_rows, int64_t fanout,
-                   uint32_t key, int32_t* chosen, int64_t cap, int64_t* total_dev, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
-    using namespace sgs;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+}  // extern "C"
+
+namespace sgs {
+namespace {
+// both selection entry points: the same checks, the same scan, the row kernel with or without weights
+template <bool kWeighted>
+int select_rows(const char* who, const int32_t* in_ptr, const int32_t* in_eid, const int32_t* in_wq, int64_t N, int64_t nnz, const int32_t* rows,
+                int64_t n_rows, int64_t fanout, uint32_t key, int32_t* chosen, int64_t cap, int64_t* total_dev, void* ws, size_t ws_bytes,
+                hipStream_t stream) {
     SGS_REQUIRE(N >= 1 && nnz >= 0 && N < (int64_t(1) << 31) && nnz < (int64_t(1) << 31), SGS_EINVAL,
-                "sgs_nbr_select: bad sizes (N = %lld, nnz = %lld): need 1 <= N < 2^31, 0 <= nnz < 2^31", (long long)N, (long long)nnz);
-    SGS_REQUIRE(n_rows >= 0 && n_rows < (int64_t(1) << 31) && cap >= 0, SGS_EINVAL, "sgs_nbr_select: bad n_rows or cap");
-    SGS_REQUIRE(fanout == -1 || (fanout >= 1 && fanout < (int64_t(1) << 31)), SGS_EINVAL,
-                "sgs_nbr_select: fanout = %lld, need >= 1 or -1 (every neighbour)", (long long)fanout);
-    SGS_REQUIRE(in_ptr && (in_eid || nnz == 0) && (rows || n_rows == 0) && (chosen || cap == 0) && ws, SGS_EINVAL, "sgs_nbr_select: null pointer");
-    SGS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, SGS_EINVAL, "sgs_nbr_select: workspace must be 8-byte aligned");
-    SGS_REQUIRE(ws_bytes >= sgs_nbr_select_workspace_bytes(n_rows), SGS_EWORKSPACE, "sgs_nbr_select: workspace too small");
+                "%s: bad sizes (N = %lld, nnz = %lld): need 1 <= N < 2^31, 0 <= nnz < 2^31", who, (long long)N, (long long)nnz);
+    SGS_REQUIRE(n_rows >= 0 && n_rows < (int64_t(1) << 31) && cap >= 0, SGS_EINVAL, "%s: bad n_rows or cap", who);
+    SGS_REQUIRE(fanout == -1 || (fanout >= 1 && fanout < (int64_t(1) << 31)), SGS_EINVAL, "%s: fanout = %lld, need >= 1 or -1 (every neighbour)", who,
+                (long long)fanout);
+    SGS_REQUIRE(in_ptr && (in_eid || nnz == 0) && (!kWeighted || in_wq || nnz == 0) && (rows || n_rows == 0) && (chosen || cap == 0) && ws, SGS_EINVAL,
+                "%s: null pointer", who);
+    SGS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, SGS_EINVAL, "%s: workspace must be 8-byte aligned", who);
+    SGS_REQUIRE(ws_bytes >= sgs_nbr_select_workspace_bytes(n_rows), SGS_EWORKSPACE, "%s: workspace too small", who);
     int64_t* offs = static_cast<int64_t*>(ws);
     hipLaunchKernelGGL(scan_one<OffsOp>, dim3(1), dim3(kST), 0, stream, OffsOp{in_ptr, rows, N, fanout, offs, n_rows, total_dev}, n_rows);
     SGS_LAUNCH_OK();
     if (n_rows > 0 && cap > 0) {
-        hipLaunchKernelGGL(nbr_select, dim3(static_cast<unsigned>(grid_rows(n_rows))), dim3(kT), 0, stream, in_ptr, in_eid, N, rows, n_rows, fanout,
-                           key, offs, chosen, cap);
+        hipLaunchKernelGGL(nbr_select<kWeighted>, dim3(static_cast<unsigned>(grid_rows(n_rows))), dim3(kT), 0, stream, in_ptr, in_eid, N, rows, n_rows,
+                           fanout, key, offs, chosen, cap, in_wq);
         SGS_LAUNCH_OK();
     }
     return SGS_OK;
 }
+}  // namespace
+}  // namespace sgs
+
+extern "C" {
+int sgs_nbr_select(const int32_t* in_ptr, const int32_t* in_eid, int64_t N, int64_t nnz, const int32_t* rows, int64_t n_rows, int64_t fanout,
+                   uint32_t key, int32_t* chosen, int64_t cap, int64_t* total_dev, void* ws, size_t ws_bytes, sgs_stream_t stream_) {
+    return sgs::select_rows<false>("sgs_nbr_select", in_ptr, in_eid, nullptr, N, nnz, rows, n_rows, fanout, key, chosen, cap, total_dev, ws, ws_bytes,
+                                   static_cast<hipStream_t>(stream_));
+}
+
+int sgs_nbr_select_weighted(const int32_t* in_ptr, const int32_t* in_eid, const int32_t* in_wq, int64_t N, int64_t nnz, const int32_t* rows,
+                            int64_t n_rows, int64_t fanout, uint32_t key, int32_t* chosen, int64_t cap, int64_t* total_dev, void* ws,
+                            size_t ws_bytes, sgs_stream_t stream_) {
+    return sgs::select_rows<true>("sgs_nbr_select_weighted", in_ptr, in_eid, in_wq, N, nnz, rows, n_rows, fanout, key, chosen, cap, total_dev, ws,
+                                  ws_bytes, static_cast<hipStream_t>(stream_));
+}
+
+void sgs_nbr_log2_table(int32_t* out) {
+    for (int i = 0; i < 257; ++i) out[i] = sgs::kLog2Host.t[i];
+}
+
+uint32_t sgs_nbr_weighted_key(uint32_t hash, uint32_t wq) { return sgs::weighted_key(hash, wq, sgs::kLog2Host.t); }
 
 size_t sgs_nbr_state_bytes(int64_t N) { return (N < 1 || N >= (int64_t(1) << 31)) ? 256 : sgs::state_bytes_for(N); }
 

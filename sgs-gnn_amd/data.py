@@ -436,6 +436,46 @@ def _fmix32_tensor(h):
     return h ^ (h >> 16)
 
 
+def _log2_table():
+    """T[i] = floor(2^24 log2(1 + i / 256)), i = 0 .. 256, by repeated squaring with Python integers at 200 fractional bits (the table of
+    csrc/neighbor.hip, which builds it at compile time)"""
+    bits, out = 200, []
+    for i in range(256):
+        y, t = (256 + i) << (bits - 8), 0
+        for _ in range(24):
+            y = (y * y) >> bits
+            t <<= 1
+            if y >> (bits + 1):
+                t, y = t | 1, y >> 1
+        out.append(t)
+    return out + [1 << 24]
+
+
+_LOG2_TABLE = {}
+
+
+def _log2q_tensor(x):
+    """LOG2Q of include/sgs_hip.h on an int64 tensor of values in [1, 2^32), integer ops only"""
+    T = _LOG2_TABLE.get(x.device)
+    if T is None:
+        T = _LOG2_TABLE[x.device] = torch.tensor(_log2_table(), dtype=torch.int64, device=x.device)
+    n, t = torch.zeros_like(x), x
+    for sh in (16, 8, 4, 2, 1):
+        big = (t >> sh) > 0
+        n = n + big * sh
+        t = torch.where(big, t >> sh, t)
+    m = (x << (32 - n)) & _M32
+    i, r = m >> 24, (m >> 8) & 0xFFFF
+    return (n << 24) + T[i] + (((T[i + 1] - T[i]) * r) >> 16)
+
+
+def _weighted_key_tensor(h, wq):
+    """sgs_nbr_weighted_key on int64 tensors: the hash h of an edge id and its quantised weight -> the key (2^32 - 1 where wq == 0)"""
+    nl = (32 << 24) - _log2q_tensor(h.clamp(min=1))
+    key = _log2q_tensor(nl) - _log2q_tensor(wq.clamp(min=1)) + (24 << 24)
+    return torch.where(wq >= 1, key, torch.full_like(key, _M32))
+
+
 def _expand_rows(ptr, rows):
     """-> (row number, position in the CSR arrays) of every entry of the CSR rows `rows`, rows back to back"""
     dev = ptr.device
@@ -511,9 +551,29 @@ class ResidentGraph:
         self.in_deg_host = ip[1:] - ip[:-1]
 
     def neighbor_loader(self, num_neighbors, batch_size, input_nodes="train", shuffle=True, seed=0, subgraph_type="induced", resample="epoch",
-                        drop_last=False) -> "NeighborLoader":
+                        drop_last=False, weight=None) -> "NeighborLoader":
         return NeighborLoader(self, num_neighbors, batch_size, input_nodes=input_nodes, shuffle=shuffle, seed=seed, subgraph_type=subgraph_type,
-                              resample=resample, drop_last=drop_last)
+                              resample=resample, drop_last=drop_last, weight=weight)
+
+    def neighbor_weights(self, weight):
+        """The `weight_q` of `batch` for a loader's `weight`: None -> None (the uniform draw); "prob" -> the full-graph prior; a float tensor
+        [E] of weights >= 0 in the CALLER's edge order (learned edge scores, an effective-resistance prior, ...).  -> int32 [E] on the graph's
+        device, quantised (ops.nbr_quantize_weights) and in in-CSR order, aligned with `in_eid`."""
+        if weight is None:
+            return None
+        from . import ops
+        if isinstance(weight, str):
+            if weight != "prob":
+                raise ValueError(f"weight must be None, 'prob' or a tensor of one weight per edge, got {weight!r}")
+            if self.prob is None:
+                raise ValueError("weight='prob' needs the full-graph prior: this graph was built with prior='local'")
+            w = self.prob
+        else:
+            w = torch.as_tensor(weight)
+            if w.dim() != 1 or w.numel() != self.num_edges or not w.is_floating_point():
+                raise ValueError(f"a weight tensor holds one floating-point weight per edge ({self.num_edges}), in the order of the edge list given")
+            w = w.to(self.edge_index.device)[self.edge_order]
+        return ops.nbr_quantize_weights(w)[self.in_eid.to(torch.int64)].contiguous()
 
     def check_seeds(self, seeds):
         s = torch.as_tensor(seeds, dtype=torch.int64).cpu().reshape(-1)
@@ -523,26 +583,31 @@ class ResidentGraph:
             raise ValueError("the seed nodes must be distinct")
         return s
 
-    def batch(self, seeds, num_neighbors, keys, subgraph_type="induced") -> Batch:
+    def batch(self, seeds, num_neighbors, keys, subgraph_type="induced", weight_q=None) -> Batch:
         """One batch: distinct `seeds`, one fan-out and one 32-bit stream key per hop.  On a HIP device it is built by the kernels of
-        csrc/neighbor.hip (ops.neighbor_batch), never by a torch composition; on the CPU by `neighbor_collate_torch`."""
+        csrc/neighbor.hip (ops.neighbor_batch), never by a torch composition; on the CPU by `neighbor_collate_torch`.  `weight_q`
+        (`neighbor_weights`): quantised weights in in-CSR order for a weighted draw; None: the uniform one."""
         fan, subgraph_type, seeds = check_fanouts(num_neighbors), check_subgraph_type(subgraph_type), self.check_seeds(seeds)
         if len(keys) != len(fan):
             raise ValueError("one stream key per hop")
+        if weight_q is not None and (weight_q.dtype != torch.int32 or weight_q.numel() != self.num_edges or weight_q.device != self.in_eid.device):
+            raise ValueError("weight_q: int32, one entry per in-CSR entry, on the graph's device (ResidentGraph.neighbor_weights)")
         if self.on_device:
             from . import ops
             if len(fan) > ops.nbr_max_hops():
                 raise ValueError(f"{len(fan)} hops, the device builder's limit is {ops.nbr_max_hops()}")
-            return ops.neighbor_batch(self, seeds, fan, keys, subgraph_type)
-        return neighbor_collate_torch(self, seeds, fan, keys, subgraph_type)
+            return ops.neighbor_batch(self, seeds, fan, keys, subgraph_type, weight_q)
+        return neighbor_collate_torch(self, seeds, fan, keys, subgraph_type, weight_q)
 
 
-def neighbor_collate_torch(graph: ResidentGraph, seeds, num_neighbors, keys, subgraph_type="induced") -> Batch:
+def neighbor_collate_torch(graph: ResidentGraph, seeds, num_neighbors, keys, subgraph_type="induced", weight_q=None) -> Batch:
     """The neighbour-sampled batch as a plain torch composition over `graph`'s tensors, wherever they live.  It is what runs when the graph is
     on the CPU and the yardstick of tools/neighbor_probe.py; on a HIP device the loader calls ops.neighbor_batch instead.  Rules
     ("Neighbour-sampled batches"): hop h takes, for every frontier node, all its in-edges if there are at most f_h (or
     f_h = -1), else the f_h whose keys fmix32(edge id ^ K_h) are smallest; the sources not yet in the batch form the next frontier;
-    node_ids ascending; `induced` = every stored edge among them, `directional` = the chosen edges, both in ascending edge id."""
+    node_ids ascending; `induced` = every stored edge among them, `directional` = the chosen edges, both in ascending edge id.
+    `weight_q` (int32 [E] in in-CSR order): the keys are sgs_nbr_weighted_key's, computed with torch integer ops; they can tie, and a stable
+    sort by (row, key) then takes the earliest ties in row order ("Weighted neighbour sampling" in the same section)."""
     fan, subgraph_type = check_fanouts(num_neighbors), check_subgraph_type(subgraph_type)
     dev, N = graph.edge_index.device, graph.num_nodes
     seeds = torch.as_tensor(seeds, dtype=torch.int64).to(dev)
@@ -554,7 +619,10 @@ def neighbor_collate_torch(graph: ResidentGraph, seeds, num_neighbors, keys, sub
         ids = graph.in_eid[pos].to(torch.int64)
         if f >= 0:
             key = _fmix32_tensor(ids ^ int(K))
-            order = torch.argsort((rid << 32) | key)                     # by row, then by key: distinct ids have distinct keys
+            if weight_q is None:
+                order = torch.argsort((rid << 32) | key)                 # by row, then by key: distinct ids have distinct keys
+            else:
+                order = torch.argsort((rid << 32) | _weighted_key_tensor(key, weight_q[pos].to(torch.int64)), stable=True)
             deg = torch.bincount(rid, minlength=front.numel())
             start = torch.cumsum(deg, 0) - deg
             keep = torch.zeros(ids.numel(), dtype=torch.bool, device=dev)
@@ -602,10 +670,16 @@ class NeighborLoader:
     Only the seeds of a batch have a sampled receptive field: its train / val / test masks are the graph's ANDed with `seed_mask`, so loss,
     gate and metrics count seeds only, and a pass with `input_nodes` covering every node once counts every node exactly once.
     resample="epoch": a fresh batch every step (eager training only).  resample="fixed": the batches of epoch 0 are built once and stay
-    resident in `self.batches` -- ordinary resident batches, which replay under args.sgs_hipgraph.  `q` stays per step, the caller's to scale."""
+    resident in `self.batches` -- ordinary resident batches, which replay under args.sgs_hipgraph.  `q` stays per step, the caller's to scale.
+
+    weight=None: every hop draws uniformly.  weight="prob" (the graph's full-graph prior) or a float tensor [E] in the caller's edge order:
+    a frontier node with more than f in-edges draws f of them without replacement, each draw proportional to the weight among those left
+    (`ResidentGraph.neighbor_weights`; zero-weight edges only when fewer than f positive ones exist).  Still a pure integer function of
+    (seed, epoch, batch, hop) and the quantised weights.  `set_weight` swaps the weights between epochs, e.g. for the scorer's latest edge
+    probabilities."""
 
     def __init__(self, graph: ResidentGraph, num_neighbors, batch_size: int, input_nodes="train", shuffle: bool = True, seed: int = 0,
-                 subgraph_type: str = "induced", resample: str = "epoch", drop_last: bool = False):
+                 subgraph_type: str = "induced", resample: str = "epoch", drop_last: bool = False, weight=None):
         self.num_neighbors, self.subgraph_type = check_fanouts(num_neighbors), check_subgraph_type(subgraph_type)
         if int(batch_size) < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
@@ -631,11 +705,18 @@ class NeighborLoader:
         self.graph, self.batch_size, self.shuffle, self.seed = graph, int(batch_size), bool(shuffle), int(seed)
         self.resample, self.drop_last, self.input_ids = resample, bool(drop_last), ids.to(torch.int64)
         self.epoch, self._pinned, self.batches = 0, None, None
+        self.weight_q = graph.neighbor_weights(weight)
         if resample == "fixed":
             self.batches = list(self._build(0))
 
     def set_epoch(self, epoch) -> None:
         self._pinned = None if epoch is None else int(epoch)
+
+    def set_weight(self, weight) -> None:
+        """Replaces the fan-out weights (None, "prob" or a tensor, as at construction); the next `__iter__` draws with them."""
+        if self.batches is not None:
+            raise ValueError("set_weight: the batches of a resample='fixed' loader are already built; make a new loader")
+        self.weight_q = self.graph.neighbor_weights(weight)
 
     def seed_lists(self, epoch: int):
         ids = self.input_ids
@@ -651,7 +732,7 @@ class NeighborLoader:
         L = len(self.num_neighbors)
         for b, seeds in enumerate(self.seed_lists(epoch)):
             keys = [neighbor_stream_key(self.seed, epoch, b, h) for h in range(L)]
-            yield self.graph.batch(seeds, self.num_neighbors, keys, self.subgraph_type)
+            yield self.graph.batch(seeds, self.num_neighbors, keys, self.subgraph_type, self.weight_q)
 
     def __len__(self):
         n = self.input_ids.numel()

@@ -3216,6 +3216,9 @@ def partition_stats(ptr, col, part, P: int):
 
 
 # ------------------------------------------------------------------ neighbour-sampled batches (csrc/neighbor.hip; data.py: ResidentGraph)
+NBR_WQ_MAX = (1 << 24) - 1                 # the largest quantised weight of the weighted fan-out draw
+
+
 def nbr_select_hub_row() -> int:
     return int(_lib.lib().sgs_nbr_select_hub_row())
 
@@ -3229,18 +3232,45 @@ def nbr_state(N: int, device) -> torch.Tensor:
     return torch.empty(int(_lib.lib().sgs_nbr_state_bytes(int(N))), dtype=torch.uint8, device=device)
 
 
-def nbr_select(in_ptr, in_eid, N: int, rows, fanout: int, key: int, total: int):
+def nbr_quantize_weights(w) -> torch.Tensor:
+    """int32 [E] quantised weights in [0, 2^24 - 1] for the weighted fan-out draw, on w's device, in float64: 0 where w == 0, else
+    clamp(floor(w / max(w) (2^24 - 1) + 0.5), 1, 2^24 - 1).  Only the ratios of the weights inside one in-row matter to the draw; a positive
+    weight below max(w) / 2^24 is rounded UP to that size (it stays drawable).  ValueError: a negative or non-finite weight, or no positive one."""
+    w = torch.as_tensor(w).reshape(-1).to(torch.float64)
+    if w.numel() == 0:
+        return torch.zeros(0, dtype=torch.int32, device=w.device)
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("nbr_quantize_weights: a weight is not finite")
+    if bool((w < 0).any()):
+        raise ValueError("nbr_quantize_weights: a weight is negative")
+    top = w.max()
+    if not bool(top > 0):
+        raise ValueError("nbr_quantize_weights: every weight is zero")
+    q = torch.floor(w / top * float(NBR_WQ_MAX) + 0.5).clamp(1, NBR_WQ_MAX)
+    return torch.where(w == 0, torch.zeros_like(q), q).to(torch.int32)
+
+
+def nbr_select(in_ptr, in_eid, N: int, rows, fanout: int, key: int, total: int, wq=None):
     """int32 [total] chosen edge ids (sgs_nbr_select): per frontier row min(fanout, in-degree) of its in-edges, of a longer row the ones with
     the `fanout` smallest keys fmix32(id ^ key), in row order; rows back to back.  `total` is the caller's (nbr_frontier reports it for the
-    next hop; for the seeds it follows from the in-degrees).  Two launches, no host sync."""
+    next hop; for the seeds it follows from the in-degrees).  Two launches, no host sync.  `wq` (int32 [nnz] quantised weights aligned with
+    in_eid, nbr_quantize_weights): the weighted draw of sgs_nbr_select_weighted instead, same launches."""
     L = _lib.lib()
     _need_gpu(in_ptr, in_eid, rows)
     n_rows = rows.numel()
     chosen = torch.empty(int(total), dtype=torch.int32, device=in_ptr.device)
     nbytes = int(L.sgs_nbr_select_workspace_bytes(n_rows))
     ws = workspace(nbytes, in_ptr.device)
-    _lib.check(L.sgs_nbr_select(_ptr(in_ptr, torch.int32), _ptr(in_eid, torch.int32), int(N), in_eid.numel(), _ptr(rows, torch.int32), n_rows,
-                                int(fanout), int(key) & 0xFFFFFFFF, _ptr(chosen), int(total), None, _ptr(ws), ws.numel(), _stream()), "sgs_nbr_select")
+    if wq is None:
+        _lib.check(L.sgs_nbr_select(_ptr(in_ptr, torch.int32), _ptr(in_eid, torch.int32), int(N), in_eid.numel(), _ptr(rows, torch.int32), n_rows,
+                                    int(fanout), int(key) & 0xFFFFFFFF, _ptr(chosen), int(total), None, _ptr(ws), ws.numel(), _stream()), "sgs_nbr_select")
+        return chosen
+    _need_gpu(wq)
+    if wq.numel() != in_eid.numel():
+        raise ValueError(f"nbr_select: {wq.numel()} weights for {in_eid.numel()} in-CSR entries")
+    _lib.check(L.sgs_nbr_select_weighted(_ptr(in_ptr, torch.int32), _ptr(in_eid, torch.int32), _ptr(wq, torch.int32), int(N), in_eid.numel(),
+                                         _ptr(rows, torch.int32), n_rows, int(fanout), int(key) & 0xFFFFFFFF, _ptr(chosen), int(total), None, _ptr(ws),
+                                         ws.numel(), _stream()), "sgs_nbr_select_weighted")
     return chosen
 
 
@@ -3316,10 +3346,11 @@ def nbr_collate(graph, n: int, chosen, subgraph_type: str, n_seeds: int, hop_nod
                  seed_mask=seed_mask.view(torch.bool), n_seeds=int(n_seeds), hop_nodes=list(hop_nodes))
 
 
-def neighbor_batch(graph, seeds, fanouts, keys, subgraph_type: str = "induced"):
+def neighbor_batch(graph, seeds, fanouts, keys, subgraph_type: str = "induced", weight_q=None):
     """One neighbour-sampled Batch on the device: `seeds` (distinct node ids on the host), one fan-out and one stream key per hop.  Per hop
     two selection launches, two frontier launches and ONE 16-byte read-back (the new frontier's size and what its rows will emit); then
-    nbr_collate.  data.neighbor_collate_torch is the same batch as a torch composition."""
+    nbr_collate.  data.neighbor_collate_torch is the same batch as a torch composition.  `weight_q` (int32 [E] in in-CSR order, aligned with
+    graph.in_eid): every hop draws in proportion to it (nbr_select's `wq`); the launches and read-backs are the same."""
     _need_gpu(graph.edge_index)
     dev, N = graph.edge_index.device, graph.num_nodes
     seeds = torch.as_tensor(seeds, dtype=torch.int64)
@@ -3333,7 +3364,7 @@ def neighbor_batch(graph, seeds, fanouts, keys, subgraph_type: str = "induced"):
             hop_nodes.append(0)
             front, total = front[:0], 0
             continue
-        c = nbr_select(graph.in_ptr, graph.in_eid, N, front, f, K, total)
+        c = nbr_select(graph.in_ptr, graph.in_eid, N, front, f, K, total, weight_q)
         chosen.append(c)
         nxt = int(fanouts[h + 1]) if h + 1 < len(fanouts) else 0
         front, sizes = nbr_frontier(c, graph.edge_index, N, graph.in_ptr, nxt, graph._nbr_state, min(total, N - n))
