@@ -103,8 +103,10 @@ int sgs_stage_segments(const int64_t* desc_host, int64_t n_segments, int64_t* di
  * mismatch_dev (device int32, may be NULL) is given and the device count differs from E_b, the word is set to 1 (it is never
  * cleared here); nothing is written outside [0, E_b) of any output either way.
  *
- * Launches: count per row (one wave per row; also the byte attributes), scan, fill.  Rows longer than 1024 columns are walked by
- * the 16 waves of their workgroup together.  Integer work and gathers only; no atomics.  ws: 8-byte aligned.
+ * Launches: count per row (one wave per row; also the byte attributes), scan, fill -- the row squeeze and the single-workgroup scan
+ * that sgs_nbr_induced_count / _fill run too (csrc/batch_rows.h).  Rows longer than 1024 columns are walked by the 16 waves of their
+ * workgroup together.  Integer work and gathers only; no atomics.  ws: sgs_cluster_collate_workspace_bytes(n_b) bytes, 8-byte
+ * aligned: the int64 rowptr [n_b + 1], which holds the row counts until the scan turns them into offsets in place.
  * Errors (SGS_EINVAL, message in sgs_last_error): k < 1 or k > cap, ranges unsorted / overlapping / not n_b nodes
  * in total, n_b or E_b >= 2^31, workspace too small.
  * ---------------------------------------------------------------------------------- */
@@ -1440,7 +1442,9 @@ int sgs_partition_stats(const int32_t* ptr, const int32_t* col, int64_t N, int64
  *   below each word; *mismatch_dev (may be NULL) is set to 1 if the members are not n.  One launch.
  * sgs_nbr_induced_count / _fill: every stored edge with both ends among the members, in ascending edge id: count per out-CSR row of the
  *   members and scan (rowptr [n + 1] int64, *total_dev = E_b; two launches), then fill edge_index_out [2, E_b] (local ids), prob_out = prob[id]
- *   and eid_out = id (either may be NULL) (one launch).  One wave per row; membership and local ids from the bitmap and wpre.
+ *   and eid_out = id (either may be NULL) (one launch).  One wave per row, a row of more than sgs_nbr_select_hub_row() entries by the four
+ *   waves of its workgroup together (the row squeeze of sgs_cluster_collate, csrc/batch_rows.h); membership and local ids from the bitmap
+ *   and wpre.  rowptr holds the row counts between the two launches of the count; nothing is written outside [0, E_b) of an output.
  * sgs_nbr_directional: the chosen ids of all hops (segments_host [n_segments][2] = {device address of int32 ids, count}, by value; at most
  *   sgs_nbr_max_hops() segments, m ids in all), ascending, as edges: edge_index_out [2, m] (row stride m), prob_out, eid_out.  An id outside
  *   [0, E) or with an end outside the members is dropped; *total_dev = the number kept (the first *total_dev columns are written).  Uses the

@@ -20,12 +20,6 @@
 #include "sgs_common.h"
 
 namespace sgs {
-size_t auc_sort_temp_bytes(int64_t n, int begin_bit, int end_bit);
-int auc_sort_keys(const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int begin_bit, int end_bit, void* temp, size_t temp_bytes,
-                  hipStream_t stream);
-}
-
-namespace sgs {
 namespace {
 constexpr int kT = 256;                 // threads per workgroup
 constexpr int kI = 8;                   // consecutive sorted items per thread

@@ -8,12 +8,14 @@
 // one binary search over the k range starts, the source row of a local row is the same search over the k prefix sums.  The group is
 // ascending, so relabelling is monotone: the kept columns of a row keep their order and the output is row-sorted without a sort.
 //
-// Three launches: count per row -> scan -> fill.  One wave per local row, 64 columns per step, a ballot gives the kept count / the
-// output positions (the sgs_graph_filter pattern).  HUB ROWS: a row longer than kHubDeg is not walked by its own wave; after the
-// short rows of a workgroup are done, its 16 waves walk each hub row together (16 contiguous slices; the fill counts the slices
-// first and offsets each by the kept counts before it).  A hub therefore costs deg / 1024 steps of one workgroup instead of
-// deg / 64 steps of one wave.  Integer work only: prob_out is a gather.  No atomics.
-#include "sgs_common.h"
+// Three launches: count per row -> scan -> fill, all three the shared kernels of csrc/batch_rows.h (the row squeeze with its hub
+// form, the single-workgroup scan; the neighbour loader's induced collate runs the same two).  This file holds what is the cluster
+// collate's own: the policy `ClusterRows` (the range searches and the byte-attribute gather of the count pass), the launch shape --
+// kCT = 1024 threads, 16 rows per workgroup, a row longer than kHubDeg = 1024 walked by all 16 waves --, the checks of the host's
+// range table and the entry points.  The workspace is the int64 rowptr alone: the count pass writes the counts into it and the scan
+// turns them into offsets in place, compares the total with the host's E_b and sets the mismatch word.  Integer work only: prob_out
+// is a gather.  No atomics.
+#include "batch_rows.h"
 
 namespace sgs {
 namespace {
@@ -42,172 +44,61 @@ __device__ __forceinline__ int last_le(const int64_t* a, int k, int64_t v) {
     return l - 1;
 }
 
-// One wave walks the columns [beg, end) of a source row.  kWrite: the kept ones go to positions out_base, out_base + 1, ...
-// Returns the kept count (the same in every lane).
-template <bool kWrite>
-__device__ __forceinline__ int walk_span(const int64_t* __restrict__ col, const float* __restrict__ prob, int64_t beg, int64_t end,
-                                         const int64_t* s_lo, const int64_t* s_hi, const int64_t* s_pre, int k, int64_t out_base,
-                                         int64_t local_row, int64_t E_b, int64_t* __restrict__ ei_out, float* __restrict__ prob_out,
-                                         int64_t* __restrict__ eid_out) {
-    const int lane = threadIdx.x & 63;
-    int run = 0;
-    for (int64_t b = beg; b < end; b += kWave) {
-        const int64_t e = b + lane;
-        bool in = false;
-        int64_t lc = 0;
-        if (e < end) {
-            const int64_t c = col[e];
-            const int j = last_le(s_lo, k, c);
-            if (j >= 0 && c < s_hi[j]) {
-                in = true;
-                lc = s_pre[j] + (c - s_lo[j]);
-            }
+// The squeeze's policy (csrc/batch_rows.h): the three range tables live in LDS; local row r and a column's membership / local id are
+// one binary search each; an entry's id is its position in full_col; the count pass gathers the node's byte attributes.
+struct ClusterRows {
+    static constexpr bool kStaged = true;
+    struct Lds {
+        int64_t lo[kMaxParts], hi[kMaxParts], pre[kMaxParts + 1];
+    };
+    ClusterArgs a;
+    const int64_t* full_ptr;
+    const int64_t* full_col;
+    const uint8_t* attr_in;
+    uint8_t* attr_out;
+    int n_attr;
+    int64_t n_b, N;
+    __device__ void stage(Lds& s) const {
+        if (threadIdx.x < kMaxParts) {
+            s.lo[threadIdx.x] = a.lo[threadIdx.x];
+            s.hi[threadIdx.x] = a.hi[threadIdx.x];
         }
-        const unsigned long long m = __ballot(in);
-        if (kWrite && in) {
-            const int64_t pos = out_base + run + __popcll(m & ((1ull << lane) - 1ull));
-            // (a host E_b that disagrees with the device count is reported through the mismatch word; nothing leaves [0, E_b))
-            if (static_cast<uint64_t>(pos) < static_cast<uint64_t>(E_b)) {
-                ei_out[pos] = local_row;
-                ei_out[E_b + pos] = lc;
-                if (prob_out) prob_out[pos] = prob[e];
-                if (eid_out) eid_out[pos] = e;
-            }
-        }
-        run += __popcll(m);
+        if (threadIdx.x <= kMaxParts) s.pre[threadIdx.x] = a.pre[threadIdx.x];
     }
-    return run;
-}
-
-// kWrite = false: cnt[r] = kept columns of local row r (+ the per-node byte attributes, gathered by the row's wave).
-// kWrite = true : the kept columns of row r go to [rowptr[r], rowptr[r + 1]).
-template <bool kWrite>
-__global__ void __launch_bounds__(kCT) cluster_rows(const ClusterArgs a, const int64_t* __restrict__ full_ptr, const int64_t* __restrict__ full_col,
-                                                    const float* __restrict__ full_prob, int64_t n_b, int64_t E_b, int* __restrict__ cnt,
-                                                    const int64_t* __restrict__ rowptr, int64_t* __restrict__ ei_out,
-                                                    float* __restrict__ prob_out, int64_t* __restrict__ eid_out,
-                                                    const uint8_t* __restrict__ attr_in, uint8_t* __restrict__ attr_out, int n_attr,
-                                                    int64_t N) {
-    __shared__ int64_t s_lo[kMaxParts], s_hi[kMaxParts], s_pre[kMaxParts + 1];
-    __shared__ int64_t s_beg[kRows], s_end[kRows];
-    __shared__ int s_part[kRows][kRows];            // [hub row of the workgroup][wave]: kept count of that wave's slice
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int k = a.k;
-    if (threadIdx.x < kMaxParts) {
-        s_lo[threadIdx.x] = a.lo[threadIdx.x];
-        s_hi[threadIdx.x] = a.hi[threadIdx.x];
+    __device__ RowSpan row(const Lds& s, int64_t r) const {
+        const int j = last_le(s.pre, a.k, r);
+        const int64_t src = s.lo[j] + (r - s.pre[j]);
+        return RowSpan{full_ptr[src], full_ptr[src + 1], src};
     }
-    if (threadIdx.x <= kMaxParts) s_pre[threadIdx.x] = a.pre[threadIdx.x];
-    __syncthreads();
-    const int64_t r = static_cast<int64_t>(blockIdx.x) * kRows + wid;
-    int64_t beg = 0, end = 0;
-    if (r < n_b) {
-        const int j = last_le(s_pre, k, r);
-        const int64_t src = s_lo[j] + (r - s_pre[j]);
-        beg = full_ptr[src];
-        end = full_ptr[src + 1];
-        if (!kWrite && lane < n_attr) attr_out[static_cast<int64_t>(lane) * n_b + r] = attr_in[static_cast<int64_t>(lane) * N + src];
+    __device__ void side_work(int64_t r, int64_t src, int lane) const {
+        if (lane < n_attr) attr_out[static_cast<int64_t>(lane) * n_b + r] = attr_in[static_cast<int64_t>(lane) * N + src];
     }
-    if (lane == 0) { s_beg[wid] = beg; s_end[wid] = end; }
-    if (r < n_b && end - beg <= kHubDeg) {
-        const int n = walk_span<kWrite>(full_col, full_prob, beg, end, s_lo, s_hi, s_pre, k, kWrite ? rowptr[r] : 0, r, E_b, ei_out,
-                                        prob_out, eid_out);
-        if (!kWrite && lane == 0) cnt[r] = n;
+    __device__ bool keep(const Lds& s, int64_t e, int64_t& lc, int64_t& id) const {
+        const int64_t c = full_col[e];
+        const int j = last_le(s.lo, a.k, c);
+        if (j < 0 || c >= s.hi[j]) return false;
+        lc = s.pre[j] + (c - s.lo[j]);
+        id = e;
+        return true;
     }
-    __syncthreads();
-    // hub rows of this workgroup (the conditions below read LDS only: uniform over the workgroup, so every barrier is met by all)
-    bool any_hub = false;
-    for (int h = 0; h < kRows; ++h) any_hub = any_hub || (s_end[h] - s_beg[h] > kHubDeg);
-    if (!any_hub) return;
-    for (int h = 0; h < kRows; ++h) {
-        const int64_t hb = s_beg[h], he = s_end[h];
-        if (he - hb <= kHubDeg) continue;
-        const int64_t slice = ((he - hb + kRows - 1) / kRows + kWave - 1) / kWave * kWave;
-        const int64_t b0 = hb + slice * wid < he ? hb + slice * wid : he;
-        const int64_t b1 = b0 + slice < he ? b0 + slice : he;
-        const int64_t hr = static_cast<int64_t>(blockIdx.x) * kRows + h;
-        const int n = walk_span<false>(full_col, full_prob, b0, b1, s_lo, s_hi, s_pre, k, 0, hr, E_b, ei_out, prob_out, eid_out);
-        if (lane == 0) s_part[h][wid] = n;
-    }
-    __syncthreads();
-    for (int h = 0; h < kRows; ++h) {
-        const int64_t hb = s_beg[h], he = s_end[h];
-        if (he - hb <= kHubDeg) continue;
-        const int64_t hr = static_cast<int64_t>(blockIdx.x) * kRows + h;
-        int before = 0, total = 0;
-        for (int w = 0; w < kRows; ++w) {
-            const int t = s_part[h][w];
-            before += w < wid ? t : 0;
-            total += t;
-        }
-        if (!kWrite) {
-            if (wid == h && lane == 0) cnt[hr] = total;
-        } else {
-            const int64_t slice = ((he - hb + kRows - 1) / kRows + kWave - 1) / kWave * kWave;
-            const int64_t b0 = hb + slice * wid < he ? hb + slice * wid : he;
-            const int64_t b1 = b0 + slice < he ? b0 + slice : he;
-            walk_span<true>(full_col, full_prob, b0, b1, s_lo, s_hi, s_pre, k, rowptr[hr] + before, hr, E_b, ei_out, prob_out, eid_out);
-        }
-    }
-}
-
-// Exclusive scan of the n_b row counts -> rowptr[n_b + 1] (int64), one workgroup: tiles of 4096 counts, four per thread, wave scan +
-// the 16 wave totals through LDS, a running carry (the scan of gcn.hip's CSR build).  Thread 0 compares the total with the host's
-// E_b and publishes it.
-__global__ void __launch_bounds__(kCT) cluster_scan(const int* __restrict__ cnt, int64_t n_b, int64_t* __restrict__ rowptr, int64_t E_b,
-                                                    int* __restrict__ mismatch, int64_t* __restrict__ total_out) {
-    __shared__ int wtot[2][16];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int64_t carry = 0;
-    int buf = 0;
-    for (int64_t base = 0; base < n_b; base += 4096, buf ^= 1) {
-        const int64_t i = base + static_cast<int64_t>(threadIdx.x) * 4;
-        int v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = i + j < n_b ? cnt[i + j] : 0;
-        const int mine = (v[0] + v[1]) + (v[2] + v[3]);
-        int inc = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
-        if (lane == 63) wtot[buf][wid] = inc;
-        __syncthreads();                            // (two LDS rows alternate: one barrier per tile)
-        int64_t run = carry + (inc - mine);
-        int64_t total = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-            const int t = wtot[buf][w];
-            run += w < wid ? t : 0;
-            total += t;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (i + j < n_b) rowptr[i + j] = run;
-            run += v[j];
-        }
-        carry += total;
-    }
-    if (threadIdx.x == 0) {
-        rowptr[n_b] = carry;
-        if (total_out) *total_out = carry;
-        if (mismatch && carry != E_b) *mismatch = 1;
-    }
-}
+};
 
 struct Plan {
     ClusterArgs a;
-    int* cnt;
     int64_t* rowptr;
 };
 
-size_t ws_bytes_for(int64_t n_b) {
-    const size_t n = static_cast<size_t>(n_b > 0 ? n_b : 0);
-    return carve_bytes(n + 1, sizeof(int)) + carve_bytes(n + 1, sizeof(int64_t));
+size_t ws_bytes_for(int64_t n_b) { return carve_bytes(static_cast<size_t>(n_b > 0 ? n_b : 0) + 1, sizeof(int64_t)); }
+
+// count (kWrite = false: into rowptr, in place) or fill of the n_b local rows
+template <bool kWrite>
+void launch_rows(const ClusterRows& rows, int64_t E_b, int64_t* rowptr, const float* full_prob, int64_t* ei_out, float* prob_out, int64_t* eid_out,
+                 hipStream_t st) {
+    hipLaunchKernelGGL((squeeze_rows<ClusterRows, kCT, kHubDeg, kWrite>), dim3(static_cast<unsigned>(cdiv(rows.n_b, kRows))), dim3(kCT), 0, st, rows,
+                       rows.n_b, E_b, rowptr, full_prob, ei_out, prob_out, eid_out);
 }
 
-// Checks the host descriptors and carves the workspace.  ranges_host [k][2] = {lo, hi} of each part, ascending and disjoint.
+// Checks the host descriptors and the workspace (rowptr[n_b + 1], counted and scanned in place).  ranges_host [k][2] = {lo, hi} of each part, ascending and disjoint.
 int make_plan(const char* who, const int64_t* ranges_host, int64_t k, int64_t n_b, void* ws, size_t ws_bytes, Plan& p) {
     SGS_REQUIRE(k >= 1 && k <= kMaxParts, SGS_EINVAL, "%s: k = %lld parts, must be in [1, %d]", who, (long long)k, kMaxParts);
     SGS_REQUIRE(ranges_host != nullptr, SGS_EINVAL, "%s: null range table", who);
@@ -230,9 +121,7 @@ int make_plan(const char* who, const int64_t* ranges_host, int64_t k, int64_t n_
     SGS_REQUIRE(pre == n_b, SGS_EINVAL, "%s: the ranges hold %lld nodes, n_b = %lld", who, (long long)pre, (long long)n_b);
     SGS_REQUIRE(ws && ws_bytes >= ws_bytes_for(n_b), SGS_EINVAL, "%s: workspace too small", who);
     SGS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, SGS_EINVAL, "%s: workspace must be 8-byte aligned", who);
-    Carver c(ws);
-    p.cnt = c.take<int>(static_cast<size_t>(n_b) + 1);
-    p.rowptr = c.take<int64_t>(static_cast<size_t>(n_b) + 1);
+    p.rowptr = static_cast<int64_t*>(ws);
     return SGS_OK;
 }
 
@@ -254,13 +143,10 @@ int sgs_cluster_collate_count(const int64_t* full_ptr, const int64_t* full_col, 
     SGS_REQUIRE(full_ptr && full_col && total_dev, SGS_EINVAL, "sgs_cluster_collate_count: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_b > 0) {
-        hipLaunchKernelGGL(cluster_rows<false>, dim3(static_cast<unsigned>(cdiv(n_b, kRows))), dim3(kCT), 0, st, p.a, full_ptr, full_col,
-                           static_cast<const float*>(nullptr), n_b, int64_t(0), p.cnt, static_cast<const int64_t*>(nullptr),
-                           static_cast<int64_t*>(nullptr), static_cast<float*>(nullptr), static_cast<int64_t*>(nullptr),
-                           static_cast<const uint8_t*>(nullptr), static_cast<uint8_t*>(nullptr), 0, int64_t(0));
+        launch_rows<false>(ClusterRows{p.a, full_ptr, full_col, nullptr, nullptr, 0, n_b, 0}, 0, p.rowptr, nullptr, nullptr, nullptr, nullptr, st);
         SGS_LAUNCH_OK();
     }
-    hipLaunchKernelGGL(cluster_scan, dim3(1), dim3(kCT), 0, st, p.cnt, n_b, p.rowptr, int64_t(0), static_cast<int*>(nullptr), total_dev);
+    hipLaunchKernelGGL(scan_one<RowptrOp>, dim3(1), dim3(kST), 0, st, RowptrOp{p.rowptr, n_b, total_dev, 0, nullptr}, n_b);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -279,18 +165,15 @@ int sgs_cluster_collate(const int64_t* full_ptr, const int64_t* full_col, const 
     SGS_REQUIRE(n_attr >= 0 && n_attr <= kMaxBytesAttr && (n_attr == 0 || (attr_in && attr_out && N >= p.a.hi[k - 1])), SGS_EINVAL,
                 "sgs_cluster_collate: bad node attribute arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
+    const ClusterRows rows{p.a, full_ptr, full_col, attr_in, attr_out, static_cast<int>(n_attr), n_b, N};
     if (n_b > 0) {
-        hipLaunchKernelGGL(cluster_rows<false>, dim3(static_cast<unsigned>(cdiv(n_b, kRows))), dim3(kCT), 0, st, p.a, full_ptr, full_col,
-                           full_prob, n_b, E_b, p.cnt, static_cast<const int64_t*>(nullptr), static_cast<int64_t*>(nullptr),
-                           static_cast<float*>(nullptr), static_cast<int64_t*>(nullptr), attr_in, attr_out, static_cast<int>(n_attr), N);
+        launch_rows<false>(rows, E_b, p.rowptr, full_prob, nullptr, nullptr, nullptr, st);
         SGS_LAUNCH_OK();
     }
-    hipLaunchKernelGGL(cluster_scan, dim3(1), dim3(kCT), 0, st, p.cnt, n_b, p.rowptr, E_b, mismatch_dev, static_cast<int64_t*>(nullptr));
+    hipLaunchKernelGGL(scan_one<RowptrOp>, dim3(1), dim3(kST), 0, st, RowptrOp{p.rowptr, n_b, nullptr, E_b, mismatch_dev}, n_b);
     SGS_LAUNCH_OK();
     if (n_b > 0 && E_b > 0) {
-        hipLaunchKernelGGL(cluster_rows<true>, dim3(static_cast<unsigned>(cdiv(n_b, kRows))), dim3(kCT), 0, st, p.a, full_ptr, full_col,
-                           full_prob, n_b, E_b, static_cast<int*>(nullptr), p.rowptr, edge_index_out, prob_out, eid_out,
-                           static_cast<const uint8_t*>(nullptr), static_cast<uint8_t*>(nullptr), 0, N);
+        launch_rows<true>(rows, E_b, p.rowptr, full_prob, edge_index_out, prob_out, eid_out, st);
         SGS_LAUNCH_OK();
     }
     return SGS_OK;

@@ -21,32 +21,18 @@
 // nodes ascending, merges them into the members and clears `reached`.  Nothing is proportional to E, and to N only through the words.
 // COLLATE (sgs_nbr_nodes, sgs_nbr_induced_count / _fill, sgs_nbr_directional, sgs_nbr_gather): a node's local id is its rank among the
 // members = the popcount prefix of its word + the popcount of the lower bits of that word.  induced: count -> scan -> fill over the out-CSR
-// rows of the members, one wave per row.  directional: the chosen ids of all hops sorted (library radix sort) and gathered.
-#include "sgs_common.h"
-
-namespace sgs {
-size_t auc_sort_temp_bytes(int64_t n, int begin_bit, int end_bit);      // csrc/graph_sort.hip
-int auc_sort_keys(const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int begin_bit, int end_bit, void* temp, size_t temp_bytes,
-                  hipStream_t stream);
-}
+// rows of the members -- the row squeeze and the scan of csrc/batch_rows.h, which the cluster collate runs too: one wave per row, a row of
+// more than kHubRow entries walked by the workgroup's four waves in slices; here only the policy `InducedRows`.  directional: the chosen ids of all hops sorted (library radix sort) and gathered.
+#include "batch_rows.h"
 
 namespace sgs {
 namespace {
 constexpr int kT = 256;
 constexpr int kWaves = kT / kWave;          // frontier rows per tile of nbr_select
 constexpr int kHubRow = 2048;               // a row with more entries than this is walked by the whole workgroup
-constexpr int kST = 1024;                   // threads of the single-workgroup scans
-constexpr int kSPer = 4;                    // items per thread and tile there
 constexpr int kMaxHops = 8;
 constexpr int kSortBits = 33;               // edge ids below 2^31, the marker of a skipped id at 2^32
 using u64 = unsigned long long;
-
-__host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu;
-    h ^= h >> 13; h *= 0xC2B2AE35u;
-    h ^= h >> 16;
-    return h;
-}
 
 // ---------------------------------------------------------------- the weighted key
 // T[i] = floor(2^24 log2(1 + i / 256)), i = 0 .. 256, by integer squaring: y in [1, 2) as a 2.62 fixed-point number; 24 times y <- y^2 and
@@ -112,49 +98,7 @@ __device__ __forceinline__ int64_t row_deg(const int* __restrict__ ptr, int64_t 
 }
 __device__ __forceinline__ int64_t row_take(int64_t deg, int64_t f) { return (f < 0 || deg <= f) ? deg : f; }
 
-// ---------------------------------------------------------------- single-workgroup exclusive scan with a per-item action
-// op.load(i) -> the item's count (int); op.store(i, before, count); op.finish(total) by thread 0
-template <class Op>
-__global__ void __launch_bounds__(kST) scan_one(Op op, int64_t n) {
-    __shared__ int wtot[2][kST / kWave];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int64_t carry = 0;
-    int buf = 0;
-    for (int64_t base = 0; base < n; base += kST * kSPer, buf ^= 1) {
-        const int64_t i = base + static_cast<int64_t>(threadIdx.x) * kSPer;
-        int v[kSPer];
-        int mine = 0;
-#pragma unroll
-        for (int j = 0; j < kSPer; ++j) {
-            v[j] = i + j < n ? op.load(i + j) : 0;
-            mine += v[j];
-        }
-        int inc = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
-        if (lane == 63) wtot[buf][wid] = inc;
-        __syncthreads();                            // (two LDS rows alternate: one barrier per tile)
-        int64_t run = carry + (inc - mine);
-        int64_t total = 0;
-#pragma unroll
-        for (int w = 0; w < kST / kWave; ++w) {
-            const int t = wtot[buf][w];
-            run += w < wid ? t : 0;
-            total += t;
-        }
-#pragma unroll
-        for (int j = 0; j < kSPer; ++j) {
-            if (i + j < n) op.store(i + j, run, v[j]);
-            run += v[j];
-        }
-        carry += total;
-    }
-    if (threadIdx.x == 0) op.finish(carry);
-}
-
+// ---------------------------------------------------------------- the per-item actions of the scans (scan_one: csrc/batch_rows.h)
 struct OffsOp {                                     // offs[r] = sum of min(f, deg) over the frontier rows before r
     const int* ptr;
     const int* rows;
@@ -219,18 +163,6 @@ struct RankOp {                                     // wpre[w] = members below w
     }
     __device__ void finish(int64_t t) const {
         if (mismatch && t != n) *mismatch = 1;
-    }
-};
-
-struct RowptrOp {                                   // counts -> exclusive prefix, in place
-    int64_t* rowptr;
-    int64_t n;
-    int64_t* total;
-    __device__ int load(int64_t i) const { return static_cast<int>(rowptr[i]); }
-    __device__ void store(int64_t i, int64_t before, int) const { rowptr[i] = before; }
-    __device__ void finish(int64_t t) const {
-        rowptr[n] = t;
-        if (total) *total = t;
     }
 };
 
@@ -482,43 +414,38 @@ __device__ __forceinline__ int64_t local_id(const uint32_t* __restrict__ member,
     return static_cast<int64_t>(wpre[v >> 5]) + __popc(member[v >> 5] & ((1u << (v & 31)) - 1u));
 }
 
-// kWrite = false: rowptr[r] = kept entries of the out-CSR row of member r.  kWrite = true: they go to [rowptr[r], rowptr[r + 1]).
-template <bool kWrite>
-__global__ void __launch_bounds__(kT) nbr_induced(const int* __restrict__ optr, const int* __restrict__ odst, const int* __restrict__ oeid, int64_t N,
-                                                  int64_t E, const uint32_t* __restrict__ member, const int* __restrict__ wpre,
-                                                  const int64_t* __restrict__ node_ids, int64_t n, int64_t* __restrict__ rowptr, int64_t E_b,
-                                                  const float* __restrict__ prob, int64_t* __restrict__ ei_out, float* __restrict__ prob_out,
-                                                  int64_t* __restrict__ eid_out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = static_cast<int64_t>(blockIdx.x) * kWaves + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const int64_t v = node_ids[r];
-    int64_t run = 0;
-    if (v >= 0 && v < N) {
-        const int64_t beg = optr[v], end = optr[v + 1], out = kWrite ? rowptr[r] : 0;
-        for (int64_t b = beg; b < end; b += kWave) {
-            const int64_t e = b + lane;
-            bool in = false;
-            int64_t c = 0, id = 0;
-            if (e < end) {
-                c = odst[e];
-                id = oeid[e];
-                in = c >= 0 && c < N && id >= 0 && id < E && is_member(member, c);
-            }
-            const u64 m = __ballot(in);
-            if (kWrite && in) {
-                const int64_t pos = out + run + __popcll(m & ((1ull << lane) - 1ull));
-                if (pos < E_b) {
-                    ei_out[pos] = r;
-                    ei_out[E_b + pos] = local_id(member, wpre, c);
-                    if (prob_out) prob_out[pos] = prob[id];
-                    if (eid_out) eid_out[pos] = id;
-                }
-            }
-            run += __popcll(m);
-        }
+// The squeeze's policy (csrc/batch_rows.h): local row r is the out-CSR row of member node_ids[r]; an entry is kept when its column is a
+// member (and column and id are in range); its local column is the column's rank among the members, its id the stored edge id.
+struct InducedRows {
+    static constexpr bool kStaged = false;
+    struct Lds {};
+    const int* optr;
+    const int* odst;
+    const int* oeid;
+    int64_t N, E;
+    const uint32_t* member;
+    const int* wpre;
+    const int64_t* node_ids;
+    __device__ void stage(Lds&) const {}
+    __device__ RowSpan row(const Lds&, int64_t r) const {
+        const int64_t v = node_ids[r];
+        if (v < 0 || v >= N) return RowSpan{0, 0, v};
+        return RowSpan{optr[v], optr[v + 1], v};
     }
-    if (!kWrite && lane == 0) rowptr[r] = run;
+    __device__ void side_work(int64_t, int64_t, int) const {}
+    __device__ bool keep(const Lds&, int64_t e, int64_t& lc, int64_t& id) const {
+        const int64_t c = odst[e];
+        id = oeid[e];
+        if (!(c >= 0 && c < N && id >= 0 && id < E && is_member(member, c))) return false;
+        lc = local_id(member, wpre, c);
+        return true;
+    }
+};
+template <bool kWrite>
+void launch_induced(const InducedRows& rows, int64_t n, int64_t E_b, int64_t* rowptr, const float* prob, int64_t* ei_out, float* prob_out,
+                    int64_t* eid_out, hipStream_t stream) {
+    hipLaunchKernelGGL((squeeze_rows<InducedRows, kT, kHubRow, kWrite>), dim3(static_cast<unsigned>(cdiv(n, kWaves))), dim3(kT), 0, stream, rows, n,
+                       E_b, rowptr, prob, ei_out, prob_out, eid_out);
 }
 
 struct Segments {
@@ -733,12 +660,11 @@ int sgs_nbr_induced_count(const int32_t* out_ptr, const int32_t* out_dst, const 
     SGS_REQUIRE(out_ptr && (E == 0 || (out_dst && out_eid)) && wpre && (node_ids || n == 0) && rowptr, SGS_EINVAL,
                 "sgs_nbr_induced_count: null pointer");
     if (n > 0) {
-        hipLaunchKernelGGL(nbr_induced<false>, dim3(static_cast<unsigned>(cdiv(n, kWaves))), dim3(kT), 0, stream, out_ptr, out_dst, out_eid, N, E,
-                           s.member, wpre, node_ids, n, rowptr, int64_t(0), static_cast<const float*>(nullptr), static_cast<int64_t*>(nullptr),
-                           static_cast<float*>(nullptr), static_cast<int64_t*>(nullptr));
+        launch_induced<false>(InducedRows{out_ptr, out_dst, out_eid, N, E, s.member, wpre, node_ids}, n, 0, rowptr, nullptr, nullptr, nullptr, nullptr,
+                              stream);
         SGS_LAUNCH_OK();
     }
-    hipLaunchKernelGGL(scan_one<RowptrOp>, dim3(1), dim3(kST), 0, stream, RowptrOp{rowptr, n, total_dev}, n);
+    hipLaunchKernelGGL(scan_one<RowptrOp>, dim3(1), dim3(kST), 0, stream, RowptrOp{rowptr, n, total_dev, 0, nullptr}, n);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -754,9 +680,8 @@ int sgs_nbr_induced_fill(const int32_t* out_ptr, const int32_t* out_dst, const i
                 "sgs_nbr_induced_fill: null pointer");
     SGS_REQUIRE(prob_out == nullptr || prob != nullptr, SGS_EINVAL, "sgs_nbr_induced_fill: prob_out without prob");
     if (n > 0 && E_b > 0) {
-        hipLaunchKernelGGL(nbr_induced<true>, dim3(static_cast<unsigned>(cdiv(n, kWaves))), dim3(kT), 0, static_cast<hipStream_t>(stream_), out_ptr,
-                           out_dst, out_eid, N, E, s.member, wpre, node_ids, n, const_cast<int64_t*>(rowptr), E_b, prob, edge_index_out, prob_out,
-                           eid_out);
+        launch_induced<true>(InducedRows{out_ptr, out_dst, out_eid, N, E, s.member, wpre, node_ids}, n, E_b, const_cast<int64_t*>(rowptr), prob,
+                             edge_index_out, prob_out, eid_out, static_cast<hipStream_t>(stream_));
         SGS_LAUNCH_OK();
     }
     return SGS_OK;

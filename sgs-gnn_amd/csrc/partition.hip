@@ -19,12 +19,6 @@
 #include "sgs_common.h"
 
 namespace sgs {
-size_t auc_sort_temp_bytes(int64_t n, int begin_bit, int end_bit);      // csrc/graph_sort.hip: the library radix sort of 64-bit keys on a bit
-int auc_sort_keys(const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int begin_bit, int end_bit, void* temp, size_t temp_bytes,
-                  hipStream_t stream);                                  // range (stable; the only object that may import the library's memset)
-}
-
-namespace sgs {
 namespace {
 constexpr int kT = 256;
 constexpr int kWaves = kT / kWave;          // rows per tile of sgs_lp_propose
@@ -35,13 +29,6 @@ constexpr int kGainBits = 20, kNodeBits = 31, kPartShift = kGainBits + kNodeBits
 constexpr uint32_t kGainMax = (1u << kGainBits) - 1;
 constexpr uint64_t kLowMask = (uint64_t(1) << kPartShift) - 1;
 using u64 = unsigned long long;
-
-__host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu;
-    h ^= h >> 13; h *= 0xC2B2AE35u;
-    h ^= h >> 16;
-    return h;
-}
 
 // (count, part) candidates packed so that "better" is "larger": count in the high word, ~part in the low one; 0 = no candidate
 __device__ __forceinline__ u64 cand(uint32_t count, uint32_t p) { return (static_cast<u64>(count) << 32) | (0xFFFFFFFFu - p); }

@@ -82,6 +82,20 @@ inline size_t carve_bytes(size_t n, size_t elem) { return (n * elem + 255) & ~si
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---------------------------------------------------------------- the library radix sort (csrc/graph_sort.hip)
+// 64-bit keys on the bit range [begin_bit, end_bit), stable; graph_sort.hip is the only object that may import the library's memset
+size_t auc_sort_temp_bytes(int64_t n, int begin_bit, int end_bit);
+int auc_sort_keys(const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int begin_bit, int end_bit, void* temp, size_t temp_bytes,
+                  hipStream_t stream);
+
+// ---------------------------------------------------------------- murmur3's 32-bit finaliser (a bijection of the 32-bit words)
+__host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
+    h ^= h >> 16; h *= 0x85EBCA6Bu;
+    h ^= h >> 13; h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+
 // ---------------------------------------------------------------- device: wave / block reductions
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

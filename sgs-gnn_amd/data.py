@@ -36,6 +36,18 @@ def degree_prior(edge_index: torch.Tensor, num_nodes: int) -> torch.Tensor:
     return F.softmax(prob * E ** -0.5, dim=0)
 
 
+def batch_prior(global_prob, index, edge_index: torch.Tensor, num_nodes: int) -> torch.Tensor:
+    """The `prob` of a batch with the row-sorted local edge list `edge_index`: `global_prob[index]` where a whole-graph prior exists
+    (prior="global"), else the degree prior of the batch's own edge list (prior="local") -- ops.degree_prior on a HIP device, the torch
+    composition above on the CPU and for an empty edge list."""
+    if global_prob is not None:
+        return global_prob[index].contiguous()
+    if edge_index.is_cuda and edge_index.shape[1] > 0:
+        from . import ops
+        return ops.degree_prior(edge_index, num_nodes)
+    return degree_prior(edge_index, num_nodes)
+
+
 def synthetic_graph(n: int, n_edges_target: int, nfeat: int, ncls: int, seed: int, train_frac: float = 0.66,
                     power: float = 0.8, device="cpu") -> Batch:
     """Undirected, loop-free, coalesced, row-sorted degree-corrected random graph with power-law
@@ -163,13 +175,7 @@ class ResidentPartitions:
         for p in range(P):
             a, b, ea, eb = nptr_h[p], nptr_h[p + 1], eptr_h[p], eptr_h[p + 1]
             lei = torch.stack([src[ea:eb] - a, dst[ea:eb] - a]).contiguous()
-            if eprob is not None:
-                bp = eprob[ea:eb].contiguous()
-            elif dev.type == "cuda" and eb > ea:
-                from . import ops
-                bp = ops.degree_prior(lei, b - a)
-            else:
-                bp = degree_prior(lei, b - a)
+            bp = batch_prior(eprob, slice(ea, eb), lei, b - a)
             self.batches.append(Batch(x=xs[a:b].contiguous(), edge_index=lei, y=ys[a:b].contiguous(), train_mask=tm[a:b].contiguous(),
                                       val_mask=vm[a:b].contiguous(), test_mask=sm[a:b].contiguous(), prob=bp, part=p,
                                       node_ids=perm[a:b]))
@@ -310,20 +316,11 @@ def collate_torch(parts: ResidentPartitions, group) -> Batch:
     n_b = rows.numel()
     loc = torch.full((parts.num_nodes,), -1, dtype=torch.int64, device=dev)
     loc[rows] = torch.arange(n_b, device=dev)
-    beg = parts.full_ptr[rows]
-    deg = parts.full_ptr[rows + 1] - beg
-    src = torch.repeat_interleave(torch.arange(n_b, device=dev), deg)
-    eid = torch.repeat_interleave(beg - (torch.cumsum(deg, 0) - deg), deg) + torch.arange(int(src.numel()), device=dev)
+    src, eid = _expand_rows(parts.full_ptr, rows)
     dst = loc[parts.full_col[eid]]
     keep = dst >= 0
     ei = torch.stack([src[keep], dst[keep]]).contiguous()           # rows ascending; a row's columns keep their order (monotone relabelling)
-    if parts.full_prob is not None:
-        prob = parts.full_prob[eid[keep]]
-    elif dev.type == "cuda" and ei.shape[1] > 0:
-        from . import ops
-        prob = ops.degree_prior(ei, n_b)
-    else:
-        prob = degree_prior(ei, n_b)
+    prob = batch_prior(parts.full_prob, eid[keep], ei, n_b)
     m = parts.masks_all[:, rows].bool()
     return Batch(x=parts.x_all[rows], edge_index=ei, y=parts.y_all[rows], train_mask=m[0].contiguous(), val_mask=m[1].contiguous(),
                  test_mask=m[2].contiguous(), prob=prob, node_ids=parts.perm[rows], parts=group,
@@ -427,7 +424,8 @@ def neighbor_stream_key(seed: int, epoch: int, batch: int, hop: int) -> int:
     return k
 
 
-def _fmix32_tensor(h):
+def fmix32_tensor(h):
+    """`fmix32` on an int64 tensor of 32-bit values (partition.py's parity hash, the neighbour sampler's keys)"""
     h = h & _M32
     h = h ^ (h >> 16)
     h = (h * 0x85EBCA6B) & _M32
@@ -539,11 +537,7 @@ class ResidentGraph:
         if prob is not None:
             prob = prob.to(dev)[order].contiguous()
         elif prior == "global":
-            if self.on_device and E > 0:
-                from . import ops
-                prob = ops.degree_prior(ei, N)
-            else:
-                prob = degree_prior(ei, N)
+            prob = batch_prior(None, None, ei, N)
         self.prob, self.prior = prob, prior
         self.x, self.y = x.to(dev).contiguous(), y.to(dev).to(torch.int64).contiguous()
         self.masks = torch.stack([train_mask, val_mask, test_mask]).to(dev).to(torch.uint8).contiguous()
@@ -618,7 +612,7 @@ def neighbor_collate_torch(graph: ResidentGraph, seeds, num_neighbors, keys, sub
         rid, pos = _expand_rows(graph.in_ptr, front)
         ids = graph.in_eid[pos].to(torch.int64)
         if f >= 0:
-            key = _fmix32_tensor(ids ^ int(K))
+            key = fmix32_tensor(ids ^ int(K))
             if weight_q is None:
                 order = torch.argsort((rid << 32) | key)                 # by row, then by key: distinct ids have distinct keys
             else:
@@ -645,13 +639,7 @@ def neighbor_collate_torch(graph: ResidentGraph, seeds, num_neighbors, keys, sub
         eid = torch.sort(torch.cat(chosen)).values
         ei = torch.stack([loc[graph.edge_index[0][eid]], loc[graph.edge_index[1][eid]]]).contiguous()
     n = int(node_ids.numel())
-    if graph.prob is not None:
-        prob = graph.prob[eid]
-    elif dev.type == "cuda" and ei.shape[1] > 0:
-        from . import ops
-        prob = ops.degree_prior(ei, n)
-    else:
-        prob = degree_prior(ei, n)
+    prob = batch_prior(graph.prob, eid, ei, n)
     is_seed = torch.zeros(N, dtype=torch.bool, device=dev)
     is_seed[seeds] = True
     seed_mask = is_seed[node_ids]

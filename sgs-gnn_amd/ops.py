@@ -3100,13 +3100,29 @@ def _stage_spans(spans) -> int:
     return -(-len(spans) // cap)
 
 
+def _edge_outputs(E_b: int, dev, want_prob: bool, want_eid: bool):
+    """The edge outputs of a device collate, uninitialised: (edge_index [2, E_b], prob [E_b] or None, eid [E_b] or None)"""
+    return (torch.empty(2, E_b, dtype=torch.int64, device=dev), torch.empty(E_b, dtype=torch.float32, device=dev) if want_prob else None,
+            torch.empty(E_b, dtype=torch.int64, device=dev) if want_eid else None)
+
+
+def _collated_batch(x, ei, y, masks, prob, node_ids, **extra):
+    """The tail of a device collate: `prob` None (prior="local") -> the prior of the batch's own edge list; `masks` (uint8 [3, n], the
+    kernels' output) handed over as the three bool masks; the caller's extra fields."""
+    from .data import Batch, batch_prior
+    if prob is None:
+        prob = batch_prior(None, None, ei, x.shape[0])
+    m = masks.view(torch.bool)
+    return Batch(x=x, edge_index=ei, y=y, train_mask=m[0], val_mask=m[1], test_mask=m[2], prob=prob, node_ids=node_ids, **extra)
+
+
 def cluster_collate(parts, group, want_eid: bool = False):
     """The batch of the partitions in `group` (a data.ResidentPartitions built with keep_cut_edges=True), cut edges between them
     restored: data.collate_torch's result, built by sgs_cluster_collate (count, scan, fill: edges, prior and masks) and one
     sgs_stage_segments launch per 24 spans (x, y, node ids).  The sizes come from the host tables, so nothing is read back --
     unless `parts.size_path == "readback"` (more partitions than the block table holds): then the edge count is one 8-byte
     read-back.  `want_eid`: also return, as `batch.eid`, each edge's position in `parts.full_col`."""
-    from .data import Batch, _check_group, _intra_edges, degree_prior as _degree_prior_torch
+    from .data import _check_group, _intra_edges
     L = _lib.lib()
     _need_gpu(parts.full_ptr, parts.full_col, parts.x_all)
     group = _check_group(parts, group)
@@ -3130,9 +3146,7 @@ def cluster_collate(parts, group, want_eid: bool = False):
     F = int(x_all.shape[1])
     if (F * x_all.element_size()) % 4 or y_all.element_size() % 4 or not x_all.is_contiguous() or not y_all.is_contiguous() or y_all.dim() != 1:
         raise RuntimeError("cluster_collate: x rows and y entries must be contiguous whole 4-byte words")
-    ei = torch.empty(2, E_b, dtype=torch.int64, device=dev)
-    prob = torch.empty(E_b, dtype=torch.float32, device=dev) if parts.full_prob is not None else None
-    eid = torch.empty(E_b, dtype=torch.int64, device=dev) if want_eid else None
+    ei, prob, eid = _edge_outputs(E_b, dev, parts.full_prob is not None, want_eid)
     masks = torch.empty(3, n_b, dtype=torch.uint8, device=dev)
     x = torch.empty(n_b, F, dtype=x_all.dtype, device=dev)
     y = torch.empty(n_b, dtype=y_all.dtype, device=dev)
@@ -3149,11 +3163,7 @@ def cluster_collate(parts, group, want_eid: bool = False):
                   (parts.perm.data_ptr() + a * 8, node_ids.data_ptr() + at * 8, n * 8)]
         at += n
     _stage_spans(spans)
-    if prob is None:
-        prob = degree_prior(ei, n_b) if E_b > 0 else _degree_prior_torch(ei, n_b)      # prior="local": of the batch's own edge list
-    m = masks.view(torch.bool)
-    b = Batch(x=x, edge_index=ei, y=y, train_mask=m[0], val_mask=m[1], test_mask=m[2], prob=prob, node_ids=node_ids, parts=group,
-              restored_edges=E_b - _intra_edges(parts, group))
+    b = _collated_batch(x, ei, y, masks, prob, node_ids, parts=group, restored_edges=E_b - _intra_edges(parts, group))
     if want_eid:
         b.eid = eid
     return b
@@ -3261,16 +3271,14 @@ def nbr_select(in_ptr, in_eid, N: int, rows, fanout: int, key: int, total: int, 
     chosen = torch.empty(int(total), dtype=torch.int32, device=in_ptr.device)
     nbytes = int(L.sgs_nbr_select_workspace_bytes(n_rows))
     ws = workspace(nbytes, in_ptr.device)
-    if wq is None:
-        _lib.check(L.sgs_nbr_select(_ptr(in_ptr, torch.int32), _ptr(in_eid, torch.int32), int(N), in_eid.numel(), _ptr(rows, torch.int32), n_rows,
-                                    int(fanout), int(key) & 0xFFFFFFFF, _ptr(chosen), int(total), None, _ptr(ws), ws.numel(), _stream()), "sgs_nbr_select")
-        return chosen
-    _need_gpu(wq)
-    if wq.numel() != in_eid.numel():
-        raise ValueError(f"nbr_select: {wq.numel()} weights for {in_eid.numel()} in-CSR entries")
-    _lib.check(L.sgs_nbr_select_weighted(_ptr(in_ptr, torch.int32), _ptr(in_eid, torch.int32), _ptr(wq, torch.int32), int(N), in_eid.numel(),
-                                         _ptr(rows, torch.int32), n_rows, int(fanout), int(key) & 0xFFFFFFFF, _ptr(chosen), int(total), None, _ptr(ws),
-                                         ws.numel(), _stream()), "sgs_nbr_select_weighted")
+    name, weights = "sgs_nbr_select", ()
+    if wq is not None:
+        _need_gpu(wq)
+        if wq.numel() != in_eid.numel():
+            raise ValueError(f"nbr_select: {wq.numel()} weights for {in_eid.numel()} in-CSR entries")
+        name, weights = "sgs_nbr_select_weighted", (_ptr(wq, torch.int32),)
+    _lib.check(getattr(L, name)(_ptr(in_ptr, torch.int32), _ptr(in_eid, torch.int32), *weights, int(N), in_eid.numel(), _ptr(rows, torch.int32),
+                                n_rows, int(fanout), int(key) & 0xFFFFFFFF, _ptr(chosen), int(total), None, _ptr(ws), ws.numel(), _stream()), name)
     return chosen
 
 
@@ -3297,7 +3305,6 @@ def nbr_collate(graph, n: int, chosen, subgraph_type: str, n_seeds: int, hop_nod
     """The Batch of the members in `graph._nbr_state` (a data.ResidentGraph on a HIP device; `n` of them): node ids and word prefixes
     (sgs_nbr_nodes), the edges -- induced: count, scan, ONE 8-byte read-back of the edge count, fill; directional: `chosen` (the per-hop id
     tensors) sorted and gathered, no read-back -- and one gathering launch for x, y, the masks and the seed flags."""
-    from .data import Batch, degree_prior as _degree_prior_torch
     L = _lib.lib()
     st, N, E, dev = graph._nbr_state, graph.num_nodes, graph.num_edges, graph.edge_index.device
     sp, sb = _ptr(st), st.numel()
@@ -3312,17 +3319,13 @@ def nbr_collate(graph, n: int, chosen, subgraph_type: str, n_seeds: int, hop_nod
         _lib.check(L.sgs_nbr_induced_count(*csr, N, E, sp, sb, _ptr(wpre), _ptr(node_ids), n, _ptr(rowptr), _ptr(total), _stream()),
                    "sgs_nbr_induced_count")
         E_b = int(total.item())
-        ei = torch.empty(2, E_b, dtype=torch.int64, device=dev)
-        prob = torch.empty(E_b, dtype=torch.float32, device=dev) if want_prob else None
-        eid = torch.empty(E_b, dtype=torch.int64, device=dev)
+        ei, prob, eid = _edge_outputs(E_b, dev, want_prob, True)
         _lib.check(L.sgs_nbr_induced_fill(*csr, _ptr(graph.prob), N, E, sp, sb, _ptr(wpre), _ptr(node_ids), n, _ptr(rowptr), E_b, _ptr(ei),
                                           _ptr(prob), _ptr(eid), _stream()), "sgs_nbr_induced_fill")
     else:
         segs = [(c.data_ptr(), c.numel()) for c in chosen if c.numel() > 0] or [(0, 0)]
         E_b = sum(c for _, c in segs)
-        ei = torch.empty(2, E_b, dtype=torch.int64, device=dev)
-        prob = torch.empty(E_b, dtype=torch.float32, device=dev) if want_prob else None
-        eid = torch.empty(E_b, dtype=torch.int64, device=dev)
+        ei, prob, eid = _edge_outputs(E_b, dev, want_prob, True)
         total = torch.empty(1, dtype=torch.int64, device=dev)
         table = (ctypes.c_int64 * (2 * len(segs)))(*[v for s in segs for v in s])
         nbytes = int(L.sgs_nbr_directional_workspace_bytes(E_b))
@@ -3339,11 +3342,8 @@ def nbr_collate(graph, n: int, chosen, subgraph_type: str, n_seeds: int, hop_nod
     seed_mask = torch.empty(n, dtype=torch.uint8, device=dev)
     _lib.check(L.sgs_nbr_gather(_ptr(node_ids), n, N, _ptr(x_all), row_bytes, _ptr(x), _ptr(y_all), _ptr(y), _ptr(graph.masks, torch.uint8), sp, sb,
                                 _ptr(masks), _ptr(seed_mask), _stream()), "sgs_nbr_gather")
-    if prob is None:
-        prob = degree_prior(ei, n) if E_b > 0 else _degree_prior_torch(ei, n)          # prior="local": of the batch's own edge list
-    m = masks.view(torch.bool)
-    return Batch(x=x, edge_index=ei, y=y, train_mask=m[0], val_mask=m[1], test_mask=m[2], prob=prob, eid=eid, node_ids=node_ids,
-                 seed_mask=seed_mask.view(torch.bool), n_seeds=int(n_seeds), hop_nodes=list(hop_nodes))
+    return _collated_batch(x, ei, y, masks, prob, node_ids, eid=eid, seed_mask=seed_mask.view(torch.bool), n_seeds=int(n_seeds),
+                           hop_nodes=list(hop_nodes))
 
 
 def neighbor_batch(graph, seeds, fanouts, keys, subgraph_type: str = "induced", weight_q=None):

@@ -12,6 +12,7 @@ import math
 import torch
 
 from . import ops
+from .data import fmix32, fmix32_tensor
 
 MAX_PARTS = 4096
 
@@ -21,19 +22,9 @@ def bounds(N: int, P: int, eps: float):
     return int(math.ceil((1.0 + eps) * N / P)), int(math.floor((1.0 - eps) * N / P)), -(-N // P)
 
 
-def _fmix32(h):
-    h = h & 0xFFFFFFFF
-    h = h ^ (h >> 16)
-    h = (h * 0x85EBCA6B) & 0xFFFFFFFF        # (the int64 product may wrap: its low 32 bits do not care)
-    h = h ^ (h >> 13)
-    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
-    return h ^ (h >> 16)
-
-
 def node_hash(N: int, k: int, device) -> torch.Tensor:
     """H(v, k) = fmix32(v ^ fmix32(k)) for v < N, int64 values below 2^32"""
-    hk = int(_fmix32(torch.tensor(int(k) & 0xFFFFFFFF, dtype=torch.int64)))
-    return _fmix32(torch.arange(N, dtype=torch.int64, device=device) ^ hk)
+    return fmix32_tensor(torch.arange(N, dtype=torch.int64, device=device) ^ fmix32(int(k)))
 
 
 def _check_init(init, N, P, cap, dev):

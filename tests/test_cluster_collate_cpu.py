@@ -178,7 +178,7 @@ def test_library_refuses_bad_groups_without_a_device(S):
     L = S._lib.lib()
     cap = L.sgs_cluster_collate_max_parts()
     assert cap >= 16 and cap == S.ops.cluster_collate_max_parts()
-    assert L.sgs_cluster_collate_workspace_bytes(1000) >= 1001 * 12
+    assert L.sgs_cluster_collate_workspace_bytes(1000) >= 1001 * 8              # the int64 rowptr, counted and scanned in place
 
     def call(ranges, n_b, ws_bytes=1 << 20, k=None):
         arr = (ctypes.c_int64 * max(len(ranges), 1))(*ranges)

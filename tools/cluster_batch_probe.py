@@ -1,6 +1,7 @@
 """Multi-partition batches on the MI355X: what a batch costs to build and what an epoch over them costs.
 
     python tools/cluster_batch_probe.py [--parts 64] [--cut-frac 0.25] [--rounds 5] [--out profiles/r31_cluster_batch_probe.json]
+                                        [--collate-only --root DIR]
 
 Graph: data.synthetic_partitioned_graph of `--parts` partitions at bench S3's partition shape (n = 1 013, F = 602, 41 classes, stored
 edges per partition from reddit_partition_sizes, seed 1000) plus cut_frac as many undirected edges again between partitions.  The cut
@@ -17,7 +18,9 @@ epoch     one training epoch (hybrid pipeline, GCN head, bench.py's model and ar
           that exists without this loader).  An arm whose batches exceed what the captured step accepts is recorded as not run.
           Two untimed epochs per arm, then the arms alternate for `rounds` epochs each.  Per arm: steps/s, sampled edges/s (sum
           over the epoch's batches of min(E_b, q), over the epoch's time) and the share of the graph's edges the epoch sees
-          (1 - dropped / E)."""
+          (1 - dropped / E).
+`--collate-only --root DIR`: the "hip" arm of `collate` alone, with the package imported from DIR (a checkout of another commit with its
+library built); tools/batch_rows_ab.py runs this tree and the parent's that way, in child processes of their own."""
 import argparse
 import json
 import os
@@ -28,7 +31,6 @@ import time
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 Q = 100_000
 REPLAY_MAX_EDGES = 2_097_152      # the captured step's sampler reads its edge count from a device word up to this capacity (csrc/sampler.hip)
 
@@ -51,13 +53,15 @@ def _launches(fn):
         return f"not measured ({type(exc).__name__}: {exc})"
 
 
-def collate_cost(S, parts, rounds):
+def collate_cost(S, parts, rounds, hip_only=False):
     from sgs_gnn_amd.data import collate_torch
     out = {}
     for k in (2, 4, 8):
         groups = parts.loader(k, regroup="epoch", shuffle=True, seed=k)._draw()
         arms = {"hip": lambda g: S.ops.cluster_collate(parts, g), "torch": lambda g: collate_torch(parts, g)}
-        for g in groups[:2]:
+        if hip_only:
+            del arms["torch"]
+        for g in groups[:0 if hip_only else 2]:
             a, b = arms["hip"](g), arms["torch"](g)
             for key in ("x", "edge_index", "y", "train_mask", "val_mask", "test_mask", "prob", "node_ids"):
                 assert torch.equal(getattr(a, key), getattr(b, key)), (k, g, key)
@@ -73,9 +77,10 @@ def collate_cost(S, parts, rounds):
                     t[n].append((time.perf_counter() - t0) / len(groups) * 1e6)
         b0 = arms["hip"](groups[0])
         out[f"k={k}"] = {"batches": len(groups), "nodes_first_batch": int(b0.x.shape[0]), "edges_first_batch": int(b0.edge_index.shape[1]),
-                         "us_per_batch": {n: _stat(v) for n, v in t.items()},
-                         "torch_over_hip": statistics.median(t["torch"]) / statistics.median(t["hip"]),
-                         "launches_per_batch": {n: _launches(lambda fn=fn: fn(groups[0])) for n, fn in arms.items()}}
+                         "us_per_batch": {n: _stat(v) for n, v in t.items()}}
+        if not hip_only:
+            out[f"k={k}"].update(torch_over_hip=statistics.median(t["torch"]) / statistics.median(t["hip"]),
+                                 launches_per_batch={n: _launches(lambda fn=fn: fn(groups[0])) for n, fn in arms.items()})
         print(f"[collate] k={k}: " + json.dumps(out[f"k={k}"]["us_per_batch"]), flush=True)
     return out
 
@@ -137,10 +142,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r31_cluster_batch_probe.json"))
     ap.add_argument("--bench-ab", default=None, help="a JSON file of bench.py results (parent / branch) to embed as `bench_ab`")
+    ap.add_argument("--collate-only", action="store_true")
+    ap.add_argument("--root", default=ROOT)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("cluster_batch_probe: needs the MI355X (there is no CPU timing)")
+    sys.path[:0] = [a.root, ROOT]
     import sgs_gnn_amd as S
+    assert os.path.abspath(os.path.dirname(S.__file__)).startswith(os.path.abspath(a.root)), (S.__file__, a.root)
     dev = "cuda:0"
     sizes = S.reddit_partition_sizes(a.parts, seed=1000, q=Q)
     b, part = S.synthetic_partitioned_graph(a.parts, 1013, sizes, a.cut_frac, 602, 41, seed=31, device=dev)
@@ -151,11 +160,13 @@ def main():
            "graph": {"partitions": a.parts, "nodes": int(b.x.shape[0]), "features": 602, "edges": E, "cut_edges": parts.dropped_edges,
                      "cut_share": parts.dropped_edges / E, "cut_frac": a.cut_frac,
                      "note": "synthetic cut structure (uniform random pairs between partitions); no real graph, no F1 measured"},
-           "rounds": a.rounds, "collate": collate_cost(S, parts, max(a.rounds, 7)), "epoch": epoch_cost(S, parts, a.rounds),
-           "collate_mismatch_word": int(parts.collate_mismatch.item())}
+           "rounds": a.rounds, "collate": collate_cost(S, parts, max(a.rounds, 7), a.collate_only)}
+    if not a.collate_only:
+        res["epoch"] = epoch_cost(S, parts, a.rounds)
+    res["collate_mismatch_word"] = int(parts.collate_mismatch.item())
     if a.bench_ab and os.path.exists(a.bench_ab):
         res["bench_ab"] = json.load(open(a.bench_ab))
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
     print("wrote", a.out)

@@ -217,9 +217,9 @@ def main():
             res["weights"] = weight_ratio(S, rg, a.batches, {"prob": (wq_prob, rg.prob),
                                                              "random_20pct_zero": (wq_rand, w_rand.to(rg.edge_index.device)[rg.edge_order])})
             res["weights"]["prior_max_over_min"] = float(rg.prob.max() / rg.prob.min())
-        res["collate_mismatch_word"] = int(rg.collate_mismatch.item())
         if a.parent_root:
             res["uniform_against_parent"] = parent_comparison(a)
+    res["collate_mismatch_word"] = int(rg.collate_mismatch.item())
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
