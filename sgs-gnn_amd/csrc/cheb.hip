@@ -12,6 +12,7 @@
 //
 // No float atomics: every per-row sum runs in CSR order over a fixed tree (run-to-run identical).  No host synchronisation.
 #include "sgs_common.h"
+#include "spmm_plan.h"
 
 namespace sgs {
 namespace {
@@ -346,43 +347,6 @@ __global__ void __launch_bounds__(64 * NW) cheb_spmm_rowblock_multi(StepArgs a, 
     cheb_spmm_rowblock_body<VEC, NW>(step_of_draw(a, st, d), N, D, ptr + d * (N + 1), col + d * nnz, val + d * nnz, part);
 }
 
-inline int pick_lpr(int64_t D, int vec) {
-    const int64_t need = (D + vec - 1) / vec;
-    int lpr = 1;
-    while (lpr < need && lpr < 64) lpr <<= 1;
-    return lpr;
-}
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-template <int VEC>
-void launch_rows(int lpr, hipStream_t stream, const StepArgs& a, int64_t N, int64_t D, const int* ptr, const int* col, const float* val) {
-    const dim3 g(static_cast<unsigned>(cdiv(N, kT / lpr))), b(kT);
-    switch (lpr) {
-        case 1: hipLaunchKernelGGL((cheb_spmm_rows<VEC, 1>), g, b, 0, stream, a, N, D, ptr, col, val); break;
-        case 2: hipLaunchKernelGGL((cheb_spmm_rows<VEC, 2>), g, b, 0, stream, a, N, D, ptr, col, val); break;
-        case 4: hipLaunchKernelGGL((cheb_spmm_rows<VEC, 4>), g, b, 0, stream, a, N, D, ptr, col, val); break;
-        case 8: hipLaunchKernelGGL((cheb_spmm_rows<VEC, 8>), g, b, 0, stream, a, N, D, ptr, col, val); break;
-        case 16: hipLaunchKernelGGL((cheb_spmm_rows<VEC, 16>), g, b, 0, stream, a, N, D, ptr, col, val); break;
-        case 32: hipLaunchKernelGGL((cheb_spmm_rows<VEC, 32>), g, b, 0, stream, a, N, D, ptr, col, val); break;
-        default: hipLaunchKernelGGL((cheb_spmm_rows<VEC, 64>), g, b, 0, stream, a, N, D, ptr, col, val); break;
-    }
-}
-
-template <int VEC>
-void launch_rows_multi(int lpr, hipStream_t stream, const StepArgs& a, const StepStrides& st, int64_t N, int64_t D, int64_t nnz, int64_t Dr,
-                       const int* ptr, const int* col, const float* val) {
-    const dim3 g(static_cast<unsigned>(cdiv(N, kT / lpr)), static_cast<unsigned>(Dr)), b(kT);
-    switch (lpr) {
-        case 1: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 1>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
-        case 2: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 2>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
-        case 4: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 4>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
-        case 8: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 8>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
-        case 16: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 16>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
-        case 32: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 32>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
-        default: hipLaunchKernelGGL((cheb_spmm_rows_multi<VEC, 64>), g, b, 0, stream, a, st, N, D, nnz, ptr, col, val); break;
-    }
-}
-
 }  // namespace
 }  // namespace sgs
 
@@ -439,10 +403,7 @@ int sgs_cheb_norm_bwd(const float* w, const float* g, const float* g2, int64_t n
 int sgs_cheb_spmm_variant(int64_t N, int64_t D, int64_t nnz, int64_t ldx, int al16) {
     if (N < 0 || D < 0 || nnz < 0 || ldx < 0) return -1;
     if (N == 0 || D == 0) return 0;
-    const int vec = (D % 4 == 0 && ldx % 4 == 0 && al16) ? 4 : 1;
-    if (N <= 65536 && nnz >= 16 * N)          // few, long rows: a workgroup per row (the choice sgs_spmm_csr makes)
-        return 1000 + vec * 100 + (nnz >= 256 * N ? 16 : 4);
-    return vec * 100 + pick_lpr(D, vec);
+    return spmm_plan(N, D, nnz, ldx % 4 == 0 && al16).code();      // sgs_spmm_csr's plan; the gathered rows' pitch enters VEC
 }
 
 int sgs_cheb_spmm(int64_t K, const float* X, int64_t ldx, int64_t N, int64_t D, int64_t nnz, const int32_t* ptr, const int32_t* col,
@@ -459,22 +420,15 @@ int sgs_cheb_spmm(int64_t K, const float* X, int64_t ldx, int64_t N, int64_t D, 
     SGS_REQUIRE(ldx >= D && ldy >= D && (!add || ldadd >= D) && (!sub || ldsub >= D) && (!Y2 || ldy2 >= D), SGS_EINVAL,
                 "sgs_cheb_spmm: a leading dimension is smaller than D");
     // 16-byte gathers need the gathered operand's block start and row pitch aligned (the other operands are touched per element)
-    const int var = sgs_cheb_spmm_variant(N, D, nnz, ldx, aligned16(X));
+    const SpmmPlan p = SpmmPlan::of_code(sgs_cheb_spmm_variant(N, D, nnz, ldx, aligned16(X)));
     if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
     StepArgs a;
     a.X = X; a.ldx = ldx; a.add = add; a.ldadd = ldadd; a.sub = sub; a.ldsub = ldsub; a.bias = bias; a.Y = Y; a.ldy = ldy;
     a.Y2 = Y2; a.ldy2 = ldy2; a.alpha = alpha; a.scale2 = scale2; a.act = act; a.drop_scale = 1.0f / (1.0f - p_drop);
     a.drop_thresh = dropout_thresh(p_drop); a.seed = seed; a.site = site; a.epoch = epoch_ptr();
-    const dim3 g_(static_cast<unsigned>(N));
-    switch (var) {
-        case 1416: hipLaunchKernelGGL((cheb_spmm_rowblock<4, 16>), g_, dim3(1024), 0, stream, a, N, D, ptr, col, val); break;
-        case 1404: hipLaunchKernelGGL((cheb_spmm_rowblock<4, 4>), g_, dim3(kT), 0, stream, a, N, D, ptr, col, val); break;
-        case 1116: hipLaunchKernelGGL((cheb_spmm_rowblock<1, 16>), g_, dim3(1024), 0, stream, a, N, D, ptr, col, val); break;
-        case 1104: hipLaunchKernelGGL((cheb_spmm_rowblock<1, 4>), g_, dim3(kT), 0, stream, a, N, D, ptr, col, val); break;
-        default:
-            if (var / 100 == 4) launch_rows<4>(var % 100, stream, a, N, D, ptr, col, val);
-            else                launch_rows<1>(var % 100, stream, a, N, D, ptr, col, val);
-    }
+    const dim3 g_(p.blocks(N)), b_(p.block());
+    dispatch_plan(p, [&](auto V, auto W) { hipLaunchKernelGGL((cheb_spmm_rows<V(), W()>), g_, b_, 0, stream, a, N, D, ptr, col, val); },
+                  [&](auto V, auto W) { hipLaunchKernelGGL((cheb_spmm_rowblock<V(), W()>), g_, b_, 0, stream, a, N, D, ptr, col, val); });
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -527,23 +481,17 @@ int sgs_cheb_spmm_multi(int64_t K, const float* X, int64_t ldx, int64_t x_stride
                 "sgs_cheb_spmm_multi: a leading dimension is smaller than D");
     SGS_REQUIRE(x_stride >= 0 && add_stride >= 0 && sub_stride >= 0 && (n_draws == 1 || y_stride >= (N - 1) * ldy + D), SGS_EINVAL,
                 "sgs_cheb_spmm_multi: bad draw stride (every draw writes a block of its own)");
-    const int var = sgs_cheb_spmm_variant(N, D, nnz, ldx, x_stride % 4 == 0 && aligned16(X));      // sgs_cheb_spmm's rule, for every draw's block
+    // sgs_cheb_spmm's rule, for every draw's block and on the per-draw entry count
+    const SpmmPlan p = SpmmPlan::of_code(sgs_cheb_spmm_variant(N, D, nnz, ldx, x_stride % 4 == 0 && aligned16(X)));
     StepArgs a;
     a.X = X; a.ldx = ldx; a.add = add; a.ldadd = ldadd; a.sub = sub; a.ldsub = ldsub; a.bias = bias; a.Y = Y; a.ldy = ldy;
     a.Y2 = nullptr; a.ldy2 = 0; a.alpha = alpha; a.scale2 = 1.0f; a.act = act; a.drop_scale = 1.0f;
     a.drop_thresh = 0u; a.seed = 0; a.site = 0u; a.epoch = nullptr;
     StepStrides st;
     st.x = x_stride; st.add = add_stride; st.sub = sub_stride; st.y = y_stride;
-    const dim3 g_(static_cast<unsigned>(N), static_cast<unsigned>(n_draws));
-    switch (var) {        // the single-draw choice, on the per-draw entry count
-        case 1416: hipLaunchKernelGGL((cheb_spmm_rowblock_multi<4, 16>), g_, dim3(1024), 0, stream, a, st, N, D, nnz, ptr, col, val); break;
-        case 1404: hipLaunchKernelGGL((cheb_spmm_rowblock_multi<4, 4>), g_, dim3(kT), 0, stream, a, st, N, D, nnz, ptr, col, val); break;
-        case 1116: hipLaunchKernelGGL((cheb_spmm_rowblock_multi<1, 16>), g_, dim3(1024), 0, stream, a, st, N, D, nnz, ptr, col, val); break;
-        case 1104: hipLaunchKernelGGL((cheb_spmm_rowblock_multi<1, 4>), g_, dim3(kT), 0, stream, a, st, N, D, nnz, ptr, col, val); break;
-        default:
-            if (var / 100 == 4) launch_rows_multi<4>(var % 100, stream, a, st, N, D, nnz, n_draws, ptr, col, val);
-            else                launch_rows_multi<1>(var % 100, stream, a, st, N, D, nnz, n_draws, ptr, col, val);
-    }
+    const dim3 g_(p.blocks(N), static_cast<unsigned>(n_draws)), b_(p.block());
+    dispatch_plan(p, [&](auto V, auto W) { hipLaunchKernelGGL((cheb_spmm_rows_multi<V(), W()>), g_, b_, 0, stream, a, st, N, D, nnz, ptr, col, val); },
+                  [&](auto V, auto W) { hipLaunchKernelGGL((cheb_spmm_rowblock_multi<V(), W()>), g_, b_, 0, stream, a, st, N, D, nnz, ptr, col, val); });
     SGS_LAUNCH_OK();
     return SGS_OK;
 }

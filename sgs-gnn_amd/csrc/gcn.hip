@@ -9,6 +9,7 @@
 //
 // All kernels are HBM/L2-bandwidth bound gathers: per nnz 4 B col + 4 B weight + 4*D B row.
 #include "sgs_common.h"
+#include "spmm_plan.h"
 
 namespace sgs {
 size_t graph_sort_workspace_bytes(int64_t n, int64_t N);
@@ -774,6 +775,59 @@ __device__ __forceinline__ void spmm_long_row_gather(const float* __restrict__ X
     }
 }
 
+// The row gather of every waves-per-row kernel: wave `wave` of the NW that own row [b, e) sums entries b + wave, b + wave + NW, ... in
+// that order, one fma chain per column, into acc (zero on entry) -- the row's partial for the lane's VEC columns from c0 (in: c0 < D).
+// GU: gathers in flight in the main loop (the entries are taken in the same order whatever GU is).
+// LONG: rows of kSpmmLongRow entries or more take spmm_long_row_gather<VEC, NW, LGU, LPIPE>: batches of LGU rows, two of them in flight
+// (LPIPE) or one, as the kernel's register budget allows (the batch size does not enter the sums).  b, e are wave-uniform.
+template <int VEC, int NW, bool LONG, int GU, int LGU, bool LPIPE>
+__device__ __forceinline__ void spmm_row_gather(const float* __restrict__ X, int64_t D, const int* __restrict__ col,
+                                                const float* __restrict__ val, int b, int e, int wave, int lane, int64_t c0, bool in,
+                                                float (&acc)[VEC]) {
+    using V = typename VecT<VEC>::type;
+    if (LONG && e - b >= kSpmmLongRow) {
+        spmm_long_row_gather<VEC, NW, LGU, LPIPE>(X, D, col, val, b, e, wave, lane, in ? c0 : 0, acc);
+    } else if (in) {
+        int k = b + wave;
+        for (; k + (GU - 1) * NW < e; k += GU * NW) {    // GU independent gathers (k, k+NW, ..., k+(GU-1)NW)
+            int j[GU]; float w[GU]; V x[GU];
+#pragma unroll
+            for (int u = 0; u < GU; ++u) { j[u] = col[k + NW * u]; w[u] = val[k + NW * u]; }
+#pragma unroll
+            for (int u = 0; u < GU; ++u) x[u] = *reinterpret_cast<const V*>(X + static_cast<int64_t>(j[u]) * D + c0);
+#pragma unroll
+            for (int u = 0; u < GU; ++u) {
+                float xv[VEC];
+                *reinterpret_cast<V*>(xv) = x[u];
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], xv[v], acc[v]);
+            }
+        }
+        for (; k < e; k += NW) {
+            float xv[VEC];
+            *reinterpret_cast<V*>(xv) = *reinterpret_cast<const V*>(X + static_cast<int64_t>(col[k]) * D + c0);
+            const float w = val[k];
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, xv[v], acc[v]);
+        }
+    }
+}
+// Column c of row i, finished by thread t of the row's waves: the NW wave partials in a fixed order (deterministic), then the diagonal
+// term, bias, ReLU and the dropout hash.  Returns Y[i, c].
+template <int VEC, int NW>
+__device__ __forceinline__ float spmm_row_finish(const float (*part)[64 * VEC], int t, const float* __restrict__ X, int64_t D, int64_t i,
+                                                 int64_t c, const float* __restrict__ diag, float dg, const float* __restrict__ bias,
+                                                 int act, float drop_scale, uint32_t drop_thresh, uint32_t rkey) {
+    float y = 0.f;
+#pragma unroll
+    for (int g = 0; g < NW; g += 4) y += (part[g][t] + part[g + 1][t]) + (part[g + 2][t] + part[g + 3][t]);
+    if (diag) y = fmaf(dg, X[i * D + c], y);
+    if (bias) y += bias[c];
+    if (act != SGS_ACT_NONE) y = fmaxf(y, 0.f);
+    if (act == SGS_ACT_RELU_DROPOUT) y = dropout_keep_col(rkey, static_cast<uint32_t>(c), drop_thresh) ? y * drop_scale : 0.f;
+    return y;
+}
+
 // NW waves per row: 4, or 16 when rows are long (power-law partitions: the hub rows set the kernel's duration)
 template <int VEC, int NW, bool LONG>
 __device__ __forceinline__ void spmm_csr_rowblock_body(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
@@ -781,7 +835,6 @@ __device__ __forceinline__ void spmm_csr_rowblock_body(const float* __restrict__
                                                        const float* __restrict__ diag, const float* __restrict__ bias, int act,
                                                        float drop_scale, uint32_t drop_thresh, uint64_t seed, uint32_t site,
                                                        const uint64_t* __restrict__ epoch, float* __restrict__ Y) {
-    using V = typename VecT<VEC>::type;
     __shared__ float part[NW][64 * VEC];
     seed = fold_epoch(seed, epoch);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -795,32 +848,7 @@ __device__ __forceinline__ void spmm_csr_rowblock_body(const float* __restrict__
         float acc[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        if (LONG && e - b >= kSpmmLongRow) {
-            spmm_long_row_gather<VEC, NW, 8, true>(X, D, col, val, b, e, wave, lane, in ? c0 : 0, acc);
-        } else if (in) {
-            int k = b + wave;
-            for (; k + 7 * NW < e; k += 8 * NW) {    // 8 independent gathers (k, k+NW, ..., k+7NW)
-                int j[8]; float w[8]; V x[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { j[u] = col[k + NW * u]; w[u] = val[k + NW * u]; }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) x[u] = *reinterpret_cast<const V*>(X + static_cast<int64_t>(j[u]) * D + c0);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    float xv[VEC];
-                    *reinterpret_cast<V*>(xv) = x[u];
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], xv[v], acc[v]);
-                }
-            }
-            for (; k < e; k += NW) {
-                float xv[VEC];
-                *reinterpret_cast<V*>(xv) = *reinterpret_cast<const V*>(X + static_cast<int64_t>(col[k]) * D + c0);
-                const float w = val[k];
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, xv[v], acc[v]);
-            }
-        }
+        spmm_row_gather<VEC, NW, LONG, 8, 8, true>(X, D, col, val, b, e, wave, lane, c0, in, acc);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) part[wave][lane * VEC + v] = acc[v];
         __syncthreads();
@@ -828,14 +856,7 @@ __device__ __forceinline__ void spmm_csr_rowblock_body(const float* __restrict__
         const int t = threadIdx.x;
         if (t < 64 * VEC && cbase + t < D) {
             const int64_t c = cbase + t;
-            float y = 0.f;
-#pragma unroll
-            for (int g = 0; g < NW; g += 4) y += (part[g][t] + part[g + 1][t]) + (part[g + 2][t] + part[g + 3][t]);
-            if (diag) y = fmaf(dg, X[i * D + c], y);
-            if (bias) y += bias[c];
-            if (act != SGS_ACT_NONE) y = fmaxf(y, 0.f);
-            if (act == SGS_ACT_RELU_DROPOUT) y = dropout_keep_col(rkey, static_cast<uint32_t>(c), drop_thresh) ? y * drop_scale : 0.f;
-            Y[i * D + c] = y;
+            Y[i * D + c] = spmm_row_finish<VEC, NW>(part, t, X, D, i, c, diag, dg, bias, act, drop_scale, drop_thresh, rkey);
         }
         __syncthreads();
     }
@@ -1212,9 +1233,7 @@ __device__ __forceinline__ float lib_gemm_dot(int K, FY y, FW w) {
     for (int k = Kmain; k < K; ++k) z = fmaf(y(k), w(k), z);
     return z;
 }
-// GU: gathers in flight per wave in the main loop (the entries are taken in the same order whatever GU is: k, k + NW, k + 2 NW, ...)
-// LONG: rows of kSpmmLongRow entries or more take spmm_long_row_gather<VEC, NW, LGU, LPIPE>: batches of LGU rows, two of them in flight
-// (LPIPE) or one, as the kernel's register budget allows (the batch size does not enter the sums)
+// GU, LGU, LPIPE: spmm_row_gather's (the row-block body's values unless a kernel's register budget asks for less)
 template <int VEC, int NW, int MODE, bool LONG, int GU = 8, int LGU = GU, bool LPIPE = true>
 __device__ __forceinline__ void spmm_rowgroup_pair_body(const float* __restrict__ X, int64_t N, int64_t D, const int* __restrict__ ptr,
                                                         const int* __restrict__ col, const float* __restrict__ val,
@@ -1223,7 +1242,6 @@ __device__ __forceinline__ void spmm_rowgroup_pair_body(const float* __restrict_
                                                         const uint64_t* __restrict__ epoch, float* __restrict__ Y,
                                                         const float* __restrict__ Wn, int64_t Dn, const float* __restrict__ Yp,
                                                         float* __restrict__ Zn, int ncs, float* __restrict__ colsum) {
-    using V = typename VecT<VEC>::type;
     constexpr int RG = 16 / NW;
     __shared__ float part[RG][NW][64 * VEC];
     __shared__ __align__(16) float ys[RG * kPairMaxD];
@@ -1266,45 +1284,14 @@ __device__ __forceinline__ void spmm_rowgroup_pair_body(const float* __restrict_
         float acc[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        if (LONG && e - b >= kSpmmLongRow) {      // (b, e: one row per group of NW waves, so wave-uniform)
-            spmm_long_row_gather<VEC, NW, LGU, LPIPE>(X, D, col, val, b, e, wave, lane, in ? c0 : 0, acc);
-        } else if (in) {
-            int k = b + wave;
-            for (; k + (GU - 1) * NW < e; k += GU * NW) {
-                int j[GU]; float w[GU]; V x[GU];
-#pragma unroll
-                for (int u = 0; u < GU; ++u) { j[u] = col[k + NW * u]; w[u] = val[k + NW * u]; }
-#pragma unroll
-                for (int u = 0; u < GU; ++u) x[u] = *reinterpret_cast<const V*>(X + static_cast<int64_t>(j[u]) * D + c0);
-#pragma unroll
-                for (int u = 0; u < GU; ++u) {
-                    float xv[VEC];
-                    *reinterpret_cast<V*>(xv) = x[u];
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], xv[v], acc[v]);
-                }
-            }
-            for (; k < e; k += NW) {
-                float xv[VEC];
-                *reinterpret_cast<V*>(xv) = *reinterpret_cast<const V*>(X + static_cast<int64_t>(col[k]) * D + c0);
-                const float w = val[k];
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, xv[v], acc[v]);
-            }
-        }
+        spmm_row_gather<VEC, NW, LONG, GU, LGU, LPIPE>(X, D, col, val, b, e, wave, lane, c0, in, acc);   // (a dead row: b = e = 0)
 #pragma unroll
         for (int v = 0; v < VEC; ++v) part[grp][wave][lane * VEC + v] = acc[v];
         __syncthreads();
         const int t = threadIdx.x % (64 * NW);
         if (live && t < 64 * VEC && cbase + t < D) {
             const int64_t c = cbase + t;
-            float y = 0.f;
-#pragma unroll
-            for (int g = 0; g < NW; g += 4) y += (part[grp][g][t] + part[grp][g + 1][t]) + (part[grp][g + 2][t] + part[grp][g + 3][t]);
-            if (diag) y = fmaf(dg, X[i * D + c], y);
-            if (bias) y += bias[c];
-            if (yact != SGS_ACT_NONE) y = fmaxf(y, 0.f);
-            if (yact == SGS_ACT_RELU_DROPOUT) y = dropout_keep_col(rkey, static_cast<uint32_t>(c), drop_thresh) ? y * drop_scale : 0.f;
+            const float y = spmm_row_finish<VEC, NW>(part[grp], t, X, D, i, c, diag, dg, bias, yact, drop_scale, drop_thresh, rkey);
             Y[i * D + c] = y;
             ys[grp * D + c] = y;
         }
@@ -1405,46 +1392,10 @@ __global__ void __launch_bounds__(1024, kDualPairWaves) spmm_rowgroup_pair_dual(
                                                                                   nullptr);
 }
 
-inline int pick_lpr(int64_t D, int vec) {
-    const int64_t need = (D + vec - 1) / vec;
-    int lpr = 1;
-    while (lpr < need && lpr < 64) lpr <<= 1;
-    return lpr;
-}
-
 }  // namespace
 }  // namespace sgs
 
 using namespace sgs;
-
-#define DISPATCH_VEC_LPR(KERNEL, vec, lpr, grid_rows, ...)                                                       \
-    do {                                                                                                          \
-        const int _rpb = kT / (lpr);                                                                              \
-        const dim3 _g(static_cast<unsigned>(cdiv((grid_rows), _rpb))), _b(kT);                                    \
-        if ((vec) == 4) {                                                                                         \
-            switch (lpr) {                                                                                        \
-                case 1: hipLaunchKernelGGL((KERNEL<4, 1>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 2: hipLaunchKernelGGL((KERNEL<4, 2>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 4: hipLaunchKernelGGL((KERNEL<4, 4>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 8: hipLaunchKernelGGL((KERNEL<4, 8>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 16: hipLaunchKernelGGL((KERNEL<4, 16>), _g, _b, 0, stream, __VA_ARGS__); break;              \
-                case 32: hipLaunchKernelGGL((KERNEL<4, 32>), _g, _b, 0, stream, __VA_ARGS__); break;              \
-                default: hipLaunchKernelGGL((KERNEL<4, 64>), _g, _b, 0, stream, __VA_ARGS__); break;              \
-            }                                                                                                     \
-        } else {                                                                                                  \
-            switch (lpr) {                                                                                        \
-                case 1: hipLaunchKernelGGL((KERNEL<1, 1>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 2: hipLaunchKernelGGL((KERNEL<1, 2>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 4: hipLaunchKernelGGL((KERNEL<1, 4>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 8: hipLaunchKernelGGL((KERNEL<1, 8>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 16: hipLaunchKernelGGL((KERNEL<1, 16>), _g, _b, 0, stream, __VA_ARGS__); break;              \
-                case 32: hipLaunchKernelGGL((KERNEL<1, 32>), _g, _b, 0, stream, __VA_ARGS__); break;              \
-                default: hipLaunchKernelGGL((KERNEL<1, 64>), _g, _b, 0, stream, __VA_ARGS__); break;              \
-            }                                                                                                     \
-        }                                                                                                         \
-    } while (0)
-
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // sgs_spmm_long_rows_set: read by the SpMM launchers at launch time; it selects the kernel (a captured graph keeps what it launched).
 // On, a graph of at most kSpmmLongMaxRows rows launches the <..., LONG = true> kernels.  Their two batches of rows in flight cost
@@ -1456,11 +1407,22 @@ constexpr int64_t kSpmmLongMaxRows = 4096;
 static inline bool spmm_long_rows_on(int64_t N, int64_t D) {       // (D: the long path keeps byte offsets into X in 32 bits)
     return g_spmm_long_rows && N <= kSpmmLongMaxRows && D <= (int64_t(1) << 18);
 }
-#define LAUNCH_LR(KERNEL, V_, W_, grid, block, ...)                                                              \
-    do {                                                                                                          \
-        if (lr) hipLaunchKernelGGL((KERNEL<V_, W_, true>), grid, block, __VA_ARGS__);                             \
-        else    hipLaunchKernelGGL((KERNEL<V_, W_, false>), grid, block, __VA_ARGS__);                            \
-    } while (0)
+// The one kernel choice of every GCN SpMM entry point (so a pair, a two-job launch and every draw of a multi launch equal sgs_spmm_csr)
+static inline SpmmPlan gcn_spmm_plan(int64_t N, int64_t D, int64_t nnz, bool al16) {
+    return spmm_plan(N, D, nnz, al16, spmm_long_rows_on(N, D));
+}
+// a pair kernel's grid: the column-sum workgroups, then 16 / NW rows per 16-wave workgroup
+static inline dim3 pair_grid(const SpmmPlan& p, int64_t N, int ncs = 0, unsigned jobs = 1) {
+    return dim3(static_cast<unsigned>(ncs + cdiv(N, 16 / p.w)), jobs);
+}
+
+// The activation / dropout arguments of entry point `who`, checked and normalised (p = 0: RELU_DROPOUT is plain RELU)
+struct ActDrop { int act; float scale; uint32_t thresh; };
+static int act_drop(const char* who, int act, float p_drop, ActDrop* o) {
+    SGS_REQUIRE(act >= SGS_ACT_NONE && act <= SGS_ACT_RELU_DROPOUT && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "%s: bad activation / dropout", who);
+    *o = ActDrop{(act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) ? SGS_ACT_RELU : act, 1.0f / (1.0f - p_drop), dropout_thresh(p_drop)};
+    return SGS_OK;
+}
 
 extern "C" {
 
@@ -1658,13 +1620,13 @@ int sgs_bias_act(const float* X, const float* bias, int64_t N, int64_t D, int ac
 int sgs_bias_act_rows(const float* X, const float* bias, int64_t N, int64_t D, int64_t row_offset, int act, float p_drop, uint64_t seed,
                       uint32_t site, float* Y, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(N >= 0 && D >= 0 && D < (int64_t(1) << 32) && act >= SGS_ACT_NONE && act <= SGS_ACT_RELU_DROPOUT && p_drop >= 0.f &&
-                    p_drop < 1.f, SGS_EINVAL, "sgs_bias_act: bad arguments");
+    SGS_REQUIRE(N >= 0 && D >= 0 && D < (int64_t(1) << 32), SGS_EINVAL, "sgs_bias_act: bad arguments");
+    ActDrop ad;
+    if (int rc = act_drop("sgs_bias_act", act, p_drop, &ad)) return rc;
     if (N * D == 0) return SGS_OK;
     SGS_REQUIRE(X && Y, SGS_EINVAL, "sgs_bias_act: null pointer");
-    if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
-    hipLaunchKernelGGL(bias_act, dim3(cdiv(N * D, kT)), dim3(kT), 0, stream, X, bias, N, D, act, 1.0f / (1.0f - p_drop),
-                       dropout_thresh(p_drop), seed, site, epoch_ptr(), Y, row_offset);
+    hipLaunchKernelGGL(bias_act, dim3(cdiv(N * D, kT)), dim3(kT), 0, stream, X, bias, N, D, ad.act, ad.scale, ad.thresh, seed, site, epoch_ptr(), Y,
+                       row_offset);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -1764,17 +1726,12 @@ int sgs_gcn_norm_bwd_edge(const float* gw_hat, const float* gloop, int64_t n_edg
     return SGS_OK;
 }
 
-/* Which kernel the launchers below pick -- pure host functions of the shape, and the launchers switch on their result.
+/* Which kernel the launchers below pick -- pure host functions of the shape: the code of the launchers' own plan (spmm_plan.h).
  * sgs_spmm_csr_variant / sgs_sddmm_csr_variant:  kind * 1000 + VEC * 100 + W
  *   kind 0: a group of W = LPR lanes per row (spmm_csr<VEC, LPR> / sddmm_csr<VEC, LPR>), LPR = the power of two >= ceil(D / VEC), at most 64
  *   kind 1: a workgroup of W = NW waves per row (spmm_csr_rowblock<VEC, NW> / sddmm_csr_rowblock<VEC, NW>)
  *   VEC = 4 iff D % 4 == 0 and both dense operands are 16-byte aligned (aligned16 != 0), else 1. */
-int sgs_spmm_csr_variant(int64_t N, int64_t D, int64_t nnz, int al16) {
-    const int vec = (D % 4 == 0 && al16) ? 4 : 1;
-    if (N <= 65536 && nnz >= 16 * N)          // few, long rows: a workgroup per row
-        return 1000 + vec * 100 + (nnz >= 256 * N ? 16 : 4);   // 16 waves for very long rows only: at ~100 entries per row the 16-wave form measured 5 % slower here
-    return vec * 100 + pick_lpr(D, vec);
-}
+int sgs_spmm_csr_variant(int64_t N, int64_t D, int64_t nnz, int al16) { return spmm_plan(N, D, nnz, al16 != 0).code(); }
 
 int sgs_spmm_long_rows_set(int on) {
     const int prev = g_spmm_long_rows;
@@ -1784,11 +1741,9 @@ int sgs_spmm_long_rows_set(int on) {
 int sgs_spmm_long_rows_threshold(void) { return kSpmmLongRow; }
 int sgs_spmm_long_rows_active(int64_t N, int64_t D) { return spmm_long_rows_on(N, D) ? 1 : 0; }
 
+// long rows (partitions; whole graphs of average degree >= 16) at any N: a workgroup per row, 16 waves from 64 entries a row
 int sgs_sddmm_csr_variant(int64_t N, int64_t D, int64_t nnz, int al16) {
-    const int vec = (D % 4 == 0 && al16) ? 4 : 1;
-    if (nnz >= 16 * N)                        // long rows (partitions; whole graphs of average degree >= 16): a workgroup per row
-        return 1000 + vec * 100 + (nnz >= 64 * N ? 16 : 4);
-    return vec * 100 + pick_lpr(D, vec);
+    return spmm_row_form(N, D, nnz, (D % 4 == 0 && al16) ? 4 : 1, INT64_MAX, 64).code();
 }
 
 int sgs_spmm_csr(const float* X, int64_t N, int64_t D, int64_t nnz, const int32_t* ptr, const int32_t* col, const float* val,
@@ -1796,38 +1751,22 @@ int sgs_spmm_csr(const float* X, int64_t N, int64_t D, int64_t nnz, const int32_
                  sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     SGS_REQUIRE(N >= 0 && D >= 0, SGS_EINVAL, "sgs_spmm_csr: bad sizes");
-    SGS_REQUIRE(act >= SGS_ACT_NONE && act <= SGS_ACT_RELU_DROPOUT && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL,
-                "sgs_spmm_csr: bad activation / dropout");
+    ActDrop ad;
+    if (int rc = act_drop("sgs_spmm_csr", act, p_drop, &ad)) return rc;
     if (N == 0 || D == 0) return SGS_OK;
     SGS_REQUIRE(X && ptr && Y && X != Y, SGS_EINVAL, "sgs_spmm_csr: null or aliased pointer");
-    const int var = sgs_spmm_csr_variant(N, D, nnz, aligned16(X) && aligned16(Y));
-    const float scale = 1.0f / (1.0f - p_drop);
-    const uint32_t th = dropout_thresh(p_drop);
-    if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
-    const dim3 g_(static_cast<unsigned>(N));
-    const bool lr = spmm_long_rows_on(N, D);
-    switch (var) {
-        case 1416:
-            LAUNCH_LR(spmm_csr_rowblock, 4, 16, g_, dim3(1024), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
-                               site, epoch_ptr(), Y);
-            break;
-        case 1404:
-            LAUNCH_LR(spmm_csr_rowblock, 4, 4, g_, dim3(kT), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
-                               site, epoch_ptr(), Y);
-            break;
-        case 1116:
-            LAUNCH_LR(spmm_csr_rowblock, 1, 16, g_, dim3(1024), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
-                               site, epoch_ptr(), Y);
-            break;
-        case 1104:
-            LAUNCH_LR(spmm_csr_rowblock, 1, 4, g_, dim3(kT), 0, stream, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed,
-                               site, epoch_ptr(), Y);
-            break;
-        default: {
-            const int vec = var / 100, lpr = var % 100;
-            DISPATCH_VEC_LPR(spmm_csr, vec, lpr, N, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed, site, epoch_ptr(), Y);
-        }
-    }
+    const SpmmPlan p = gcn_spmm_plan(N, D, nnz, aligned16(X) && aligned16(Y));
+    const dim3 g_(p.blocks(N)), b_(p.block());
+    if (p.kind)
+        dispatch_waves_long(p, [&](auto V, auto W, auto L) {
+            hipLaunchKernelGGL((spmm_csr_rowblock<V(), W(), L()>), g_, b_, 0, stream, X, N, D, ptr, col, val, diag, bias, ad.act, ad.scale, ad.thresh,
+                               seed, site, epoch_ptr(), Y);
+        });
+    else
+        dispatch_lanes(p, [&](auto V, auto W) {
+            hipLaunchKernelGGL((spmm_csr<V(), W()>), g_, b_, 0, stream, X, N, D, ptr, col, val, diag, bias, ad.act, ad.scale, ad.thresh, seed, site,
+                               epoch_ptr(), Y);
+        });
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -1838,29 +1777,22 @@ int sgs_sddmm_csr(const float* A, const float* B, int64_t N, int64_t D, int64_t 
     SGS_REQUIRE(N >= 0 && D >= 0, SGS_EINVAL, "sgs_sddmm_csr: bad sizes");
     if (N == 0) return SGS_OK;
     SGS_REQUIRE(A && B && ptr, SGS_EINVAL, "sgs_sddmm_csr: null pointer");
-    const int var = sgs_sddmm_csr_variant(N, D, nnz, aligned16(A) && aligned16(B));
-    const dim3 g_(static_cast<unsigned>(N));
-    switch (var) {
-        case 1416: hipLaunchKernelGGL((sddmm_csr_rowblock<4, 16>), g_, dim3(1024), 0, stream, A, B, N, D, ptr, col, eid, g, gdiag); break;
-        case 1404: hipLaunchKernelGGL((sddmm_csr_rowblock<4, 4>), g_, dim3(kT), 0, stream, A, B, N, D, ptr, col, eid, g, gdiag); break;
-        case 1116: hipLaunchKernelGGL((sddmm_csr_rowblock<1, 16>), g_, dim3(1024), 0, stream, A, B, N, D, ptr, col, eid, g, gdiag); break;
-        case 1104: hipLaunchKernelGGL((sddmm_csr_rowblock<1, 4>), g_, dim3(kT), 0, stream, A, B, N, D, ptr, col, eid, g, gdiag); break;
-        default: {
-            const int vec = var / 100, lpr = var % 100;
-            DISPATCH_VEC_LPR(sddmm_csr, vec, lpr, N, A, B, N, D, ptr, col, eid, g, gdiag);
-        }
-    }
+    const SpmmPlan p = SpmmPlan::of_code(sgs_sddmm_csr_variant(N, D, nnz, aligned16(A) && aligned16(B)));
+    const dim3 g_(p.blocks(N)), b_(p.block());
+    dispatch_plan(p, [&](auto V, auto W) { hipLaunchKernelGGL((sddmm_csr<V(), W()>), g_, b_, 0, stream, A, B, N, D, ptr, col, eid, g, gdiag); },
+                  [&](auto V, auto W) { hipLaunchKernelGGL((sddmm_csr_rowblock<V(), W()>), g_, b_, 0, stream, A, B, N, D, ptr, col, eid, g, gdiag); });
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
 
 int sgs_act_bwd(const float* dY, const float* Y, int64_t n, int act, float p_drop, float* dZ, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(n >= 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_act_bwd: bad arguments");
+    SGS_REQUIRE(n >= 0, SGS_EINVAL, "sgs_act_bwd: bad arguments");
+    ActDrop ad;
+    if (int rc = act_drop("sgs_act_bwd", act, p_drop, &ad)) return rc;
     if (n == 0) return SGS_OK;
     SGS_REQUIRE(dY && dZ && (act == SGS_ACT_NONE || Y), SGS_EINVAL, "sgs_act_bwd: null pointer");
-    if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
-    hipLaunchKernelGGL(act_bwd, dim3(cdiv(n, kT)), dim3(kT), 0, stream, dY, Y, n, act, 1.0f / (1.0f - p_drop), dZ);
+    hipLaunchKernelGGL(act_bwd, dim3(cdiv(n, kT)), dim3(kT), 0, stream, dY, Y, n, ad.act, ad.scale, dZ);
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -1925,15 +1857,17 @@ int sgs_colsum(const float* A, int64_t N, int64_t D, float* out, void* ws, size_
 int sgs_act_bwd_colsum(const float* dY, const float* Y, int64_t N, int64_t D, int act, float p_drop, float* dZ, float* colsum, void* ws,
                        size_t ws_bytes, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    SGS_REQUIRE(N >= 0 && D >= 0 && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL, "sgs_act_bwd_colsum: bad arguments");
+    SGS_REQUIRE(N >= 0 && D >= 0, SGS_EINVAL, "sgs_act_bwd_colsum: bad arguments");
+    ActDrop ad;
+    if (int rc = act_drop("sgs_act_bwd_colsum", act, p_drop, &ad)) return rc;
     if (D == 0) return SGS_OK;
     SGS_REQUIRE(colsum && (N == 0 || (dZ && dY && (act == SGS_ACT_NONE || Y))), SGS_EINVAL, "sgs_act_bwd_colsum: null pointer");   // (an empty dZ has no address)
     switch (sgs_colsum_variant(N, D, 1) / 1000000) {
         case 1:
-            hipLaunchKernelGGL(colsum_small<true>, dim3(cdiv(D, 16)), dim3(1024), 0, stream, dY, Y, N, D, act, 1.0f / (1.0f - p_drop), dZ, colsum);
+            hipLaunchKernelGGL(colsum_small<true>, dim3(cdiv(D, 16)), dim3(1024), 0, stream, dY, Y, N, D, ad.act, ad.scale, dZ, colsum);
             break;
         case 2:
-            hipLaunchKernelGGL(colsum_small_v4<true>, dim3(cdiv(D, 16)), dim3(1024), 0, stream, dY, Y, N, D, act, 1.0f / (1.0f - p_drop), dZ, colsum);
+            hipLaunchKernelGGL(colsum_small_v4<true>, dim3(cdiv(D, 16)), dim3(1024), 0, stream, dY, Y, N, D, ad.act, ad.scale, dZ, colsum);
             break;
         default:
             if (int rc = sgs_act_bwd(dY, Y, N * D, act, p_drop, dZ, stream_)) return rc;
@@ -1945,39 +1879,23 @@ int sgs_act_bwd_colsum(const float* dY, const float* Y, int64_t N, int64_t D, in
 
 // ---- GCN layer pairs (spmm_rowgroup_pair): only where sgs_spmm_csr takes its row-block path
 int sgs_gcn_pair_ok(int64_t N, int64_t nnz, int64_t D) {
-    return (N > 0 && N <= 65536 && nnz >= 16 * N && D > 0 && D <= kPairMaxD) ? 1 : 0;
+    return (N > 0 && D > 0 && D <= kPairMaxD && spmm_plan(N, D, nnz, false).kind == 1) ? 1 : 0;
 }
-
-#define PAIR_LAUNCH1(V_, W_, MODE, grid, ...)                                                                                             \
-    do {                                                                                                                          \
-        if (lr) hipLaunchKernelGGL((spmm_rowgroup_pair<V_, W_, MODE, true>), dim3(grid), dim3(1024), 0, stream, __VA_ARGS__);      \
-        else    hipLaunchKernelGGL((spmm_rowgroup_pair<V_, W_, MODE, false>), dim3(grid), dim3(1024), 0, stream, __VA_ARGS__);     \
-    } while (0)
-#define PAIR_LAUNCH(MODE, grid, ...)                                                                                              \
-    do {                                                                                                                          \
-        if (vec == 4 && wide)  PAIR_LAUNCH1(4, 16, MODE, grid, __VA_ARGS__); \
-        else if (vec == 4)     PAIR_LAUNCH1(4, 4, MODE, grid, __VA_ARGS__);  \
-        else if (wide)         PAIR_LAUNCH1(1, 16, MODE, grid, __VA_ARGS__); \
-        else                   PAIR_LAUNCH1(1, 4, MODE, grid, __VA_ARGS__);  \
-    } while (0)
 
 int sgs_spmm_csr_next(const float* X, int64_t N, int64_t D, int64_t nnz, const int32_t* ptr, const int32_t* col, const float* val,
                       const float* diag, const float* bias, int act, float p_drop, uint64_t seed, uint32_t site, const float* Wn, int64_t Dn,
                       float* Y, float* Z, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     SGS_REQUIRE(sgs_gcn_pair_ok(N, nnz, D) && Dn > 0, SGS_EINVAL, "sgs_spmm_csr_next: not a row-block shape (see sgs_gcn_pair_ok)");
-    SGS_REQUIRE(act >= SGS_ACT_NONE && act <= SGS_ACT_RELU_DROPOUT && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL,
-                "sgs_spmm_csr_next: bad activation / dropout");
+    ActDrop ad;
+    if (int rc = act_drop("sgs_spmm_csr_next", act, p_drop, &ad)) return rc;
     SGS_REQUIRE(X && ptr && Y && Wn && Z && X != Y && Z != Y && Z != X, SGS_EINVAL, "sgs_spmm_csr_next: null or aliased pointer");
-    const int vec = (D % 4 == 0 && aligned16(X) && aligned16(Y)) ? 4 : 1;      // (as sgs_spmm_csr: Y is bitwise its result)
-    const bool wide = nnz >= 256 * N;
-    const float scale = 1.0f / (1.0f - p_drop);
-    const uint32_t th = dropout_thresh(p_drop);
-    if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
-    const int64_t grid = cdiv(N, wide ? 1 : 4);
-    const bool lr = spmm_long_rows_on(N, D);
-    PAIR_LAUNCH(kPairFwd, grid, X, N, D, ptr, col, val, diag, bias, act, scale, th, seed, site, epoch_ptr(), Y, Wn, Dn,
-                static_cast<const float*>(nullptr), Z, 0, static_cast<float*>(nullptr));
+    const SpmmPlan p = gcn_spmm_plan(N, D, nnz, aligned16(X) && aligned16(Y));      // (as sgs_spmm_csr: Y is bitwise its result)
+    dispatch_waves_long(p, [&](auto V, auto W, auto L) {
+        hipLaunchKernelGGL((spmm_rowgroup_pair<V(), W(), kPairFwd, L()>), pair_grid(p, N), dim3(1024), 0, stream, X, N, D, ptr, col, val, diag, bias,
+                           ad.act, ad.scale, ad.thresh, seed, site, epoch_ptr(), Y, Wn, Dn, static_cast<const float*>(nullptr), Z, 0,
+                           static_cast<float*>(nullptr));
+    });
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -1987,33 +1905,32 @@ int sgs_spmm_csr_bwd_prev(const float* dZ, int64_t N, int64_t D, int64_t nnz, co
                           float* colsum, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     SGS_REQUIRE(sgs_gcn_pair_ok(N, nnz, D), SGS_EINVAL, "sgs_spmm_csr_bwd_prev: not a row-block shape (see sgs_gcn_pair_ok)");
-    SGS_REQUIRE(act >= SGS_ACT_NONE && act <= SGS_ACT_RELU_DROPOUT && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL,
-                "sgs_spmm_csr_bwd_prev: bad activation / dropout");
+    ActDrop ad;
+    if (int rc = act_drop("sgs_spmm_csr_bwd_prev", act, p_drop, &ad)) return rc;
     SGS_REQUIRE(dZ && ptr && dX && dZ != dX, SGS_EINVAL, "sgs_spmm_csr_bwd_prev: null or aliased pointer");
     SGS_REQUIRE(!W || (Dp > 0 && dZp && (act == SGS_ACT_NONE || Yp) && dZp != dX && dZp != dZ), SGS_EINVAL,
                 "sgs_spmm_csr_bwd_prev: W needs Dp > 0, dZp and (with an activation) Yp");
-    const int vec = (D % 4 == 0 && aligned16(dZ) && aligned16(dX)) ? 4 : 1;
-    const bool wide = nnz >= 256 * N;
+    const SpmmPlan p = gcn_spmm_plan(N, D, nnz, aligned16(dZ) && aligned16(dX));
     const int ncs = colsum ? static_cast<int>(cdiv(D, 16)) : 0;
-    const int64_t grid = ncs + cdiv(N, wide ? 1 : 4);
-    const float scale = 1.0f / (1.0f - p_drop);
-    const bool lr = spmm_long_rows_on(N, D);
-    if (W)
-        PAIR_LAUNCH(kPairBwd, grid, dZ, N, D, ptr, col, val, diag, static_cast<const float*>(nullptr), act, scale, 0u, uint64_t(0), 0u,
-                    static_cast<const uint64_t*>(nullptr), dX, W, Dp, Yp, dZp, ncs, colsum);
-    else
-        PAIR_LAUNCH(kPairCol, grid, dZ, N, D, ptr, col, val, diag, static_cast<const float*>(nullptr), SGS_ACT_NONE, 1.f, 0u, uint64_t(0), 0u,
-                    static_cast<const uint64_t*>(nullptr), dX, static_cast<const float*>(nullptr), int64_t(0), static_cast<const float*>(nullptr),
-                    static_cast<float*>(nullptr), ncs, colsum);
+    dispatch_waves_long(p, [&](auto V, auto W_, auto L) {
+        const float* const no_bias = nullptr;
+        const uint64_t* const no_epoch = nullptr;
+        if (W)
+            hipLaunchKernelGGL((spmm_rowgroup_pair<V(), W_(), kPairBwd, L()>), pair_grid(p, N, ncs), dim3(1024), 0, stream, dZ, N, D, ptr, col, val, diag,
+                               no_bias, ad.act, ad.scale, 0u, uint64_t(0), 0u, no_epoch, dX, W, Dp, Yp, dZp, ncs, colsum);
+        else
+            hipLaunchKernelGGL((spmm_rowgroup_pair<V(), W_(), kPairCol, L()>), pair_grid(p, N, ncs), dim3(1024), 0, stream, dZ, N, D, ptr, col, val, diag,
+                               no_bias, int(SGS_ACT_NONE), 1.f, 0u, uint64_t(0), 0u, no_epoch, dX, no_bias, int64_t(0), no_bias,
+                               static_cast<float*>(nullptr), ncs, colsum);
+    });
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
-#undef PAIR_LAUNCH
-#undef PAIR_LAUNCH1
 
 // ---- two-job forms of the GNN head's two forward launches (spmm_rowgroup_pair_dual, spmm_csr_rowblock_dual)
 int sgs_gcn_dual_ok(int64_t N, int64_t nnz_a, int64_t nnz_b, int64_t D, int64_t Dn) {
-    return (sgs_gcn_pair_ok(N, nnz_a, D) && sgs_gcn_pair_ok(N, nnz_b, D) && Dn > 0 && (nnz_a >= 256 * N) == (nnz_b >= 256 * N)) ? 1 : 0;
+    return (sgs_gcn_pair_ok(N, nnz_a, D) && sgs_gcn_pair_ok(N, nnz_b, D) && Dn > 0 &&
+            spmm_plan(N, D, nnz_a, false).w == spmm_plan(N, D, nnz_b, false).w) ? 1 : 0;
 }
 
 int sgs_spmm_csr_next_dual(const float* X, int64_t N, int64_t D, const float* bias, int act, float p_drop, uint32_t site, const float* Wn,
@@ -2022,27 +1939,21 @@ int sgs_spmm_csr_next_dual(const float* X, int64_t N, int64_t D, const float* bi
                            const float* val_b, const float* diag_b, uint64_t seed_b, float* Y_b, float* Z_b, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     SGS_REQUIRE(sgs_gcn_dual_ok(N, nnz_a, nnz_b, D, Dn), SGS_EINVAL, "sgs_spmm_csr_next_dual: not two row-block shapes of one variant (see sgs_gcn_dual_ok)");
-    SGS_REQUIRE(act >= SGS_ACT_NONE && act <= SGS_ACT_RELU_DROPOUT && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL,
-                "sgs_spmm_csr_next_dual: bad activation / dropout");
+    ActDrop ad;
+    if (int rc = act_drop("sgs_spmm_csr_next_dual", act, p_drop, &ad)) return rc;
     SGS_REQUIRE(X && ptr_a && ptr_b && Y_a && Y_b && Wn && Z_a && Z_b && X != Y_a && X != Y_b && X != Z_a && X != Z_b && Y_a != Y_b &&
                     Z_a != Z_b && Y_a != Z_a && Y_a != Z_b && Y_b != Z_a && Y_b != Z_b,
                 SGS_EINVAL, "sgs_spmm_csr_next_dual: null or aliased pointer");
-    const int vec = (D % 4 == 0 && aligned16(X) && aligned16(Y_a)) ? 4 : 1;      // (per job as sgs_spmm_csr_next picks it)
-    SGS_REQUIRE(vec == ((D % 4 == 0 && aligned16(X) && aligned16(Y_b)) ? 4 : 1), SGS_EINVAL,
+    const SpmmPlan p = gcn_spmm_plan(N, D, nnz_a, aligned16(X) && aligned16(Y_a));      // (per job as sgs_spmm_csr_next picks it)
+    SGS_REQUIRE(p.vec == gcn_spmm_plan(N, D, nnz_b, aligned16(X) && aligned16(Y_b)).vec, SGS_EINVAL,
                 "sgs_spmm_csr_next_dual: the two jobs select different kernel variants (alignment)");
-    const bool wide = nnz_a >= 256 * N;
-    const float scale = 1.0f / (1.0f - p_drop);
-    const uint32_t th = dropout_thresh(p_drop);
-    if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
     SpmmDualArgs a;
     a.job[0] = SpmmDualJob{X, ptr_a, col_a, val_a, diag_a, Y_a, Z_a, nnz_a, seed_a};
     a.job[1] = SpmmDualJob{X, ptr_b, col_b, val_b, diag_b, Y_b, Z_b, nnz_b, seed_b};
-    const dim3 grid(static_cast<unsigned>(cdiv(N, wide ? 1 : 4)), 2);
-    const bool lr = spmm_long_rows_on(N, D);
-    if (vec == 4 && wide)  LAUNCH_LR(spmm_rowgroup_pair_dual, 4, 16, grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
-    else if (vec == 4)     LAUNCH_LR(spmm_rowgroup_pair_dual, 4, 4, grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
-    else if (wide)         LAUNCH_LR(spmm_rowgroup_pair_dual, 1, 16, grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
-    else                   LAUNCH_LR(spmm_rowgroup_pair_dual, 1, 4, grid, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr(), Wn, Dn);
+    dispatch_waves_long(p, [&](auto V, auto W, auto L) {
+        hipLaunchKernelGGL((spmm_rowgroup_pair_dual<V(), W(), L()>), pair_grid(p, N, 0, 2), dim3(1024), 0, stream, a, N, D, bias, ad.act, ad.scale,
+                           ad.thresh, site, epoch_ptr(), Wn, Dn);
+    });
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -2053,27 +1964,20 @@ int sgs_spmm_csr_dual(const float* X_a, const float* X_b, int64_t N, int64_t D, 
                       uint64_t seed_b, float* Y_b, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     SGS_REQUIRE(N > 0 && D > 0, SGS_EINVAL, "sgs_spmm_csr_dual: bad sizes");
-    SGS_REQUIRE(act >= SGS_ACT_NONE && act <= SGS_ACT_RELU_DROPOUT && p_drop >= 0.f && p_drop < 1.f, SGS_EINVAL,
-                "sgs_spmm_csr_dual: bad activation / dropout");
+    ActDrop ad;
+    if (int rc = act_drop("sgs_spmm_csr_dual", act, p_drop, &ad)) return rc;
     SGS_REQUIRE(X_a && X_b && ptr_a && ptr_b && Y_a && Y_b && Y_a != Y_b && X_a != Y_a && X_a != Y_b && X_b != Y_a && X_b != Y_b, SGS_EINVAL,
                 "sgs_spmm_csr_dual: null or aliased pointer");
-    const int var = sgs_spmm_csr_variant(N, D, nnz_a, aligned16(X_a) && aligned16(Y_a));
-    SGS_REQUIRE(var >= 1000 && var == sgs_spmm_csr_variant(N, D, nnz_b, aligned16(X_b) && aligned16(Y_b)), SGS_EINVAL,
+    const SpmmPlan p = gcn_spmm_plan(N, D, nnz_a, aligned16(X_a) && aligned16(Y_a));
+    SGS_REQUIRE(p.kind == 1 && p.code() == gcn_spmm_plan(N, D, nnz_b, aligned16(X_b) && aligned16(Y_b)).code(), SGS_EINVAL,
                 "sgs_spmm_csr_dual: not two row-block shapes of one variant (see sgs_spmm_csr_variant)");
-    const float scale = 1.0f / (1.0f - p_drop);
-    const uint32_t th = dropout_thresh(p_drop);
-    if (act == SGS_ACT_RELU_DROPOUT && p_drop == 0.f) act = SGS_ACT_RELU;
     SpmmDualArgs a;
     a.job[0] = SpmmDualJob{X_a, ptr_a, col_a, val_a, diag_a, Y_a, nullptr, nnz_a, seed_a};
     a.job[1] = SpmmDualJob{X_b, ptr_b, col_b, val_b, diag_b, Y_b, nullptr, nnz_b, seed_b};
-    const dim3 g_(static_cast<unsigned>(N), 2);
-    const bool lr = spmm_long_rows_on(N, D);
-    switch (var) {
-        case 1416: LAUNCH_LR(spmm_csr_rowblock_dual, 4, 16, g_, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
-        case 1404: LAUNCH_LR(spmm_csr_rowblock_dual, 4, 4, g_, dim3(kT), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
-        case 1116: LAUNCH_LR(spmm_csr_rowblock_dual, 1, 16, g_, dim3(1024), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
-        default:   LAUNCH_LR(spmm_csr_rowblock_dual, 1, 4, g_, dim3(kT), 0, stream, a, N, D, bias, act, scale, th, site, epoch_ptr()); break;
-    }
+    dispatch_waves_long(p, [&](auto V, auto W, auto L) {
+        hipLaunchKernelGGL((spmm_csr_rowblock_dual<V(), W(), L()>), dim3(p.blocks(N), 2), dim3(p.block()), 0, stream, a, N, D, bias, ad.act, ad.scale,
+                           ad.thresh, site, epoch_ptr());
+    });
     SGS_LAUNCH_OK();
     return SGS_OK;
 }
@@ -2134,33 +2038,6 @@ int sgs_gcn_norm_fwd_multi(const float* w, int64_t q, int64_t N, int64_t D, cons
     return SGS_OK;
 }
 
-#define DISPATCH_VEC_LPR_Y(KERNEL, vec, lpr, grid_rows, gy, ...)                                                  \
-    do {                                                                                                          \
-        const int _rpb = kT / (lpr);                                                                              \
-        const dim3 _g(static_cast<unsigned>(cdiv((grid_rows), _rpb)), (gy)), _b(kT);                              \
-        if ((vec) == 4) {                                                                                         \
-            switch (lpr) {                                                                                        \
-                case 1: hipLaunchKernelGGL((KERNEL<4, 1>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 2: hipLaunchKernelGGL((KERNEL<4, 2>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 4: hipLaunchKernelGGL((KERNEL<4, 4>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 8: hipLaunchKernelGGL((KERNEL<4, 8>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 16: hipLaunchKernelGGL((KERNEL<4, 16>), _g, _b, 0, stream, __VA_ARGS__); break;              \
-                case 32: hipLaunchKernelGGL((KERNEL<4, 32>), _g, _b, 0, stream, __VA_ARGS__); break;              \
-                default: hipLaunchKernelGGL((KERNEL<4, 64>), _g, _b, 0, stream, __VA_ARGS__); break;              \
-            }                                                                                                     \
-        } else {                                                                                                  \
-            switch (lpr) {                                                                                        \
-                case 1: hipLaunchKernelGGL((KERNEL<1, 1>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 2: hipLaunchKernelGGL((KERNEL<1, 2>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 4: hipLaunchKernelGGL((KERNEL<1, 4>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 8: hipLaunchKernelGGL((KERNEL<1, 8>), _g, _b, 0, stream, __VA_ARGS__); break;                \
-                case 16: hipLaunchKernelGGL((KERNEL<1, 16>), _g, _b, 0, stream, __VA_ARGS__); break;              \
-                case 32: hipLaunchKernelGGL((KERNEL<1, 32>), _g, _b, 0, stream, __VA_ARGS__); break;              \
-                default: hipLaunchKernelGGL((KERNEL<1, 64>), _g, _b, 0, stream, __VA_ARGS__); break;              \
-            }                                                                                                     \
-        }                                                                                                         \
-    } while (0)
-
 int sgs_spmm_csr_multi(const float* X, int64_t x_stride, int64_t N, int64_t Dc, int64_t nnz, int64_t D, const int32_t* ptr, const int32_t* col,
                        const float* val, const float* diag, const float* bias, int act, float* Y, sgs_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -2170,24 +2047,17 @@ int sgs_spmm_csr_multi(const float* X, int64_t x_stride, int64_t N, int64_t Dc, 
     SGS_REQUIRE(X && ptr && Y && (nnz == 0 || (col && val)), SGS_EINVAL, "sgs_spmm_csr_multi: null pointer");
     SGS_REQUIRE(x_stride == 0 || x_stride >= N * Dc, SGS_EINVAL, "sgs_spmm_csr_multi: x_stride must be 0 (shared X) or >= N * Dc");
     SGS_REQUIRE(X + (D - 1) * x_stride + N * Dc <= Y || Y + D * N * Dc <= X, SGS_EINVAL, "sgs_spmm_csr_multi: X and Y overlap");
-    const int vec = (Dc % 4 == 0 && x_stride % 4 == 0 && aligned16(X) && aligned16(Y)) ? 4 : 1;
-    const int lpr = pick_lpr(Dc, vec);
-    const unsigned Du = static_cast<unsigned>(D);
-    if (N <= 65536 && nnz >= 16 * N) {        // the rowblock / row-per-lanes choice of sgs_spmm_csr, so every draw equals it
-        const bool wide = nnz >= 256 * N;
-        const dim3 g_(static_cast<unsigned>(N), Du);
-        const bool lr = spmm_long_rows_on(N, Dc);
-        if (vec == 4 && wide)
-            LAUNCH_LR(multi_spmm_csr_rowblock, 4, 16, g_, dim3(1024), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
-        else if (vec == 4)
-            LAUNCH_LR(multi_spmm_csr_rowblock, 4, 4, g_, dim3(kT), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
-        else if (wide)
-            LAUNCH_LR(multi_spmm_csr_rowblock, 1, 16, g_, dim3(1024), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
-        else
-            LAUNCH_LR(multi_spmm_csr_rowblock, 1, 4, g_, dim3(kT), 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
-    } else {
-        DISPATCH_VEC_LPR_Y(multi_spmm_csr, vec, lpr, N, Du, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
-    }
+    // sgs_spmm_csr's plan on the per-draw entry count, so every draw equals it (16-byte gathers: every draw's block of X aligned as well)
+    const SpmmPlan p = gcn_spmm_plan(N, Dc, nnz, x_stride % 4 == 0 && aligned16(X) && aligned16(Y));
+    const dim3 g_(p.blocks(N), static_cast<unsigned>(D)), b_(p.block());
+    if (p.kind)
+        dispatch_waves_long(p, [&](auto V, auto W, auto L) {
+            hipLaunchKernelGGL((multi_spmm_csr_rowblock<V(), W(), L()>), g_, b_, 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
+        });
+    else
+        dispatch_lanes(p, [&](auto V, auto W) {
+            hipLaunchKernelGGL((multi_spmm_csr<V(), W()>), g_, b_, 0, stream, X, x_stride, N, Dc, nnz, ptr, col, val, diag, bias, act, Y);
+        });
     SGS_LAUNCH_OK();
     return SGS_OK;
 }

@@ -82,6 +82,26 @@ def test_csr_reachable_set_is_the_dispatch_s_whole_range(L):
         assert seen == set(CSR_REACHABLE)
 
 
+def test_pair_dual_and_cheb_queries_are_answers_of_the_spmm_variant(L):
+    """The layer-pair / two-job predicates and the Chebyshev step's variant are read off sgs_spmm_csr_variant's choice, on a grid that
+    straddles every threshold (host queries only; nothing is launched)."""
+    Dn = 41
+    for N in (1, 64, 65536, 65537):
+        counts = (16 * N - 1, 16 * N, 256 * N - 1, 256 * N)
+        for D in (1, 4, 41, 512, 513):
+            for nnz in counts:
+                for al in (0, 1):
+                    code = L.sgs_spmm_csr_variant(N, D, nnz, al)
+                    assert L.sgs_gcn_pair_ok(N, nnz, D) == int(code >= 1000 and D <= 512), (N, nnz, D, al)
+                    if D % 4 == 0 or al == 0:
+                        assert L.sgs_cheb_spmm_variant(N, D, nnz, D, al) == code, (N, nnz, D, al)
+            for a in counts:
+                for b in counts:
+                    both = L.sgs_gcn_pair_ok(N, a, D) and L.sgs_gcn_pair_ok(N, b, D)
+                    same_w = L.sgs_spmm_csr_variant(N, D, a, 1) % 100 == L.sgs_spmm_csr_variant(N, D, b, 1) % 100
+                    assert L.sgs_gcn_dual_ok(N, a, b, D, Dn) == int(bool(both and same_w)), (N, a, b, D)
+
+
 def test_colsum_table_reaches_every_variant(L):
     want = set(COLSUM_REACHABLE) | {c + R.FUSED for c in COLSUM_REACHABLE}
     got = set()

@@ -8,19 +8,30 @@
 Timed: sgs_spmm_csr at D = 256 and 41 (the GNN head's widths) and at D = 64, 128, 512 (does the hub cost follow the row's bytes?),
 sgs_spmm_csr_next, and sgs_spmm_csr_bwd_prev with the previous layer's product and with the column sums only.
 "skewed / flat" of a call says how much of the hub penalty is left (flat has the nnz of skew_small; skew_draw is shown per entry).
-One GPU process; prints one JSON document (and writes it to argv[1] if given).
+One GPU process; prints one JSON document (and writes it to out.json if given).
 
-    python tools/spmm_skew_probe.py [out.json]
+    python tools/spmm_skew_probe.py [out.json] [--root DIR]
+
+`--root DIR`: the package is imported from DIR (a checkout of another commit with its library built); tools/gcn_spmm_ab.py runs this
+tree and the parent's that way, in child processes of their own.
 """
 import json
 import os
 import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ARGS = sys.argv[1:]
+ROOT = HERE
+if "--root" in ARGS:
+    ROOT = os.path.abspath(ARGS[ARGS.index("--root") + 1])
+    del ARGS[ARGS.index("--root"):ARGS.index("--root") + 2]
+sys.path[:0] = [ROOT, HERE]
 import torch  # noqa: E402
 
 import sgs_gnn_amd as S  # noqa: E402
+
+assert os.path.abspath(os.path.dirname(S.__file__)).startswith(ROOT), (S.__file__, ROOT)
 
 DEV = "cuda:0"
 N, H, C, Q = 1013, 256, 41, 100_000
@@ -117,9 +128,9 @@ def main():
     res["skewed_over_flat"] = {e: {sw: round(v["skew_small"][sw] / v["flat"][sw], 3) for sw in ("on", "off")} for e, v in res["us"].items()}
     txt = json.dumps(res, indent=1)
     print(txt)
-    if len(sys.argv) > 1:
-        os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
-        open(sys.argv[1], "w").write(txt + "\n")
+    if ARGS:
+        os.makedirs(os.path.dirname(os.path.abspath(ARGS[0])), exist_ok=True)
+        open(ARGS[0], "w").write(txt + "\n")
 
 
 if __name__ == "__main__":
